@@ -14,7 +14,9 @@ Other workloads (never substituted for the C3 headline; `config.workload` names 
   --workload c5   PP-OCRv4 server det+rec in fp16 (BASELINE config 5), own roofline against the fp16 MFMA peak
 
 Prints ONE JSON line on rank 0 (driver contract) with `roofline` for the dominant kernel family (HIP-event
-times measured live on the session's stream) and `cpu_baseline` (rank 0, N=1 only).
+times measured live on the session's stream) and `cpu_baseline` (rank 0, N=1 only).  `--dump-outputs DIR` also writes
+what the last timed step returned on rank 0 (boxes, scores, labels, token ids, det checksum) as DIR/<name>.npy; inputs
+and weights are seeded, so two builds run with the same arguments can be compared output for output.
 """
 from __future__ import annotations
 
@@ -81,7 +83,11 @@ def parse():
     ap.add_argument("--inflight", type=int, default=None,
                     help="batches submitted ahead in the timed region (rt_submit_batch / rt_wait_batch; default 2, C2: 4); 1 = one synchronous rt_run_batch per step")
     ap.add_argument("--repeat", type=int, default=2, help="extra repetitions of the K timed steps after the timed region (spread, reported in `repeat`)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed region, write what the last timed step returned (rank 0's pages) as DIR/<name>.npy")
     a = ap.parse_args()
+    if a.steps is not None and a.steps < 1:
+        ap.error("--steps must be at least 1")
     if a.workload == "c5":
         a.dtype = a.dtype or "f16"; a.models = a.models or "server"
         a.pages = a.pages or 128; a.steps = a.steps or 3; a.warmup = a.warmup if a.warmup is not None else 3   # (the arenas of the 3 lanes settle after 3 calls)
@@ -113,6 +119,55 @@ def page_digest(lib, r, i):
             nt = lib.rt_results_rec_tokens(r, i, k, C.byref(tp))
             hsh.update(bytes(np.ctypeslib.as_array(tp, (nt,)).tobytes()) if nt else b"-")
     return hsh.hexdigest()[:16], n
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(lib, outs, d):
+    """--dump-outputs: what a caller of the timed path receives from its results handles [(handle, pages)], pages in order and
+    the lines of a page in result order: box corners, det score, cls label and score, rec score and CTC token ids (padded with
+    -1) per text line, the line count of every page, and the det checksum of every handle -- float32 / float64 .npy files in
+    `d`.  Should the per-line arrays exceed DUMP_LIMIT_BYTES, a seeded sample of lines is kept; `line_index` names the lines."""
+    counts, boxes, det_s, cls_l, cls_s, rec_s, toks = [], [], [], [], [], [], []
+    for r, n in outs:
+        for i in range(n):
+            m = lib.rt_results_count(r, i)
+            counts.append(m)
+            if not m:
+                continue
+            boxes.append(np.ctypeslib.as_array(lib.rt_results_boxes(r, i), (m, 8)).copy())
+            det_s.append(np.ctypeslib.as_array(lib.rt_results_det_scores(r, i), (m,)).copy())
+            cls_l.append(np.ctypeslib.as_array(lib.rt_results_cls_labels(r, i), (m,)).copy())
+            cls_s.append(np.ctypeslib.as_array(lib.rt_results_cls_scores(r, i), (m,)).copy())
+            rec_s.append(np.ctypeslib.as_array(lib.rt_results_rec_scores(r, i), (m,)).copy())
+            for k in range(m):
+                tp = C.POINTER(C.c_int32)()
+                nt = lib.rt_results_rec_tokens(r, i, k, C.byref(tp))
+                toks.append(np.ctypeslib.as_array(tp, (nt,)).copy() if nt else np.zeros(0, np.int32))
+    n_lines = sum(counts)
+    width = max((len(t) for t in toks), default=0)
+    tokens = np.full((n_lines, width), -1.0, np.float32)
+    for k, t in enumerate(toks):
+        tokens[k, :len(t)] = t
+    def cat(parts, shape):
+        return np.concatenate(parts).astype(np.float32) if parts else np.zeros(shape, np.float32)
+    per_line = {"boxes": cat(boxes, (0, 8)), "det_scores": cat(det_s, (0,)), "cls_labels": cat(cls_l, (0,)),
+                "cls_scores": cat(cls_s, (0,)), "rec_scores": cat(rec_s, (0,)), "rec_tokens": tokens}
+    line_bytes = 8 + sum(v[:1].nbytes for v in per_line.values())   # (+ 8: the line's entry in line_index)
+    budget = DUMP_LIMIT_BYTES - 8 * (len(counts) + len(outs))         # (lines_per_page, det_checksum)
+    idx = np.arange(n_lines)
+    if n_lines * line_bytes > budget:
+        idx = np.sort(np.random.default_rng(0).choice(n_lines, budget // line_bytes, replace=False))
+    arrays = {k: v[idx] for k, v in per_line.items()}
+    arrays["line_index"] = idx.astype(np.float64)
+    arrays["lines_per_page"] = np.array(counts, np.float64)
+    arrays["det_checksum"] = np.array([lib.rt_results_det_checksum(r) for r, _n in outs], np.float64)
+    os.makedirs(d, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(d, k + ".npy"), v)
+    return {"dir": d, "files": sorted(k + ".npy" for k in arrays), "lines": n_lines, "lines_written": int(len(idx)),
+            "bytes": int(sum(v.nbytes for v in arrays.values()))}
 
 
 def launch_ranks(n):
@@ -336,14 +391,15 @@ def main():
         res = process_shard(my_ids, lambda ids: run_ids(ids, on_host, "raw" if keep else "free"), chunk)
         return [x for _i, x in res if x is not None] if keep else []
 
-    def run_steps(k, on_host=False):
+    def run_steps(k, on_host=False, keep_last=False):
         """k steps.  --inflight N > 1 (default 2): batches are submitted ahead (rt_submit_batch / rt_wait_batch), at most N in
         flight -- every step still processes its whole batch; the results of step i are collected while step i + 1 runs.
-        N = 1: one synchronous rt_run_batch per step (what rounds 1-3 timed)."""
+        N = 1: one synchronous rt_run_batch per step (what rounds 1-3 timed).  keep_last: the last step's results are not
+        freed but returned as [(results handle, pages)] (caller frees)."""
         if a.inflight <= 1 or global_mode:
-            for _ in range(k):
-                step(on_host)
-            return
+            for i in range(k):
+                last = step(on_host, keep=keep_last and i == k - 1)
+            return last if keep_last else None
         ks = list(range(n_my))
         q = []
         for _ in range(k):
@@ -353,8 +409,9 @@ def main():
                 q.append(sess.submit_batch_raw(d_pages, hs, ws, retto_amd.RT_MEM_DEVICE, d_maps))
             if len(q) >= a.inflight:
                 lib.rt_results_free(sess.wait_batch_raw(q.pop(0)))
-        while q:
+        while len(q) > (1 if keep_last else 0):
             lib.rt_results_free(sess.wait_batch_raw(q.pop(0)))
+        return [(sess.wait_batch_raw(q.pop(0)), n_my)] if keep_last else None
 
     def barrier():
         lib.rt_synchronize(h)
@@ -395,11 +452,18 @@ def main():
     th0 = thread_cpu()
     ru0 = resource.getrusage(resource.RUSAGE_SELF)
     t0 = time.perf_counter()
-    run_steps(a.steps, on_host)
+    last_outs = run_steps(a.steps, on_host, keep_last=bool(a.dump_outputs) and rank == 0)
     barrier()
     elapsed = time.perf_counter() - t0
     ru1 = resource.getrusage(resource.RUSAGE_SELF)
     th1 = thread_cpu()
+    dumped = None
+    if last_outs is not None:
+        try:
+            dumped = dump_outputs(lib, last_outs, a.dump_outputs)
+        finally:
+            for r, _n in last_outs:
+                lib.rt_results_free(r)
     per_thread = sorted(((th1[t][1] - th0.get(t, (None, 0.0))[1], th1[t][0]) for t in th1), reverse=True)[:6]
     # host budget of one rank: CPU time (user + system, all threads) per step and the threads it keeps -- eight ranks share the
     # node's CPUs (the pod on the MI355X box: 16), so a rank that needs more than cpus / 8 of a core-second per second is the limit
@@ -826,6 +890,8 @@ def main():
         out["c2"] = c2
     if rank_invariance:
         out["rank_invariance"] = rank_invariance
+    if dumped:
+        out["dump_outputs"] = dumped
     if sess is not None:
         sess.close()
     if dist_on:

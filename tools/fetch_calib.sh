@@ -3,6 +3,7 @@
 out=gpurun_out/${1:-fetch_calib}
 mkdir -p $out
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
+/opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 tools/scratch/fetch_calib.hip -o tools/scratch/fetch_calib || exit 1
 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $out/f -o f -- ./tools/scratch/fetch_calib > /dev/null 2>&1
 rocprofv3 --pmc TCC_EA0_RDREQ_sum TCC_EA0_RDREQ_32B_sum TCC_BUBBLE_sum --output-format csv -d $out/r -o r -- ./tools/scratch/fetch_calib > /dev/null 2>&1
 python3 - $out <<'PY'
