@@ -247,9 +247,9 @@ static float* run_lc(RunCtx& c, const LcBlock& b, const float* x, const Level& L
   long long min_pix = Lout.maxPix;
   for (const ImgGeom& g : Lout.h) min_pix = std::min<long long>(min_pix, (long long)g.H * g.W);
   // 256: k_gemm32p (3-int table entries), 128: register-staged wide tiles (2-int entries), 0: no fused form
-  const int tile_rows = b.se ? nn::gemm_se_tile_rows(b.dw.Cp, Lout.total, b.pw.K, b.pw.N, b.pw.Npad, ACT_HSWISH, min_pix) : 0;
+  const int tile_rows = b.se ? nn::gemm_se_rows(b.dw.Cp, Lout.total, b.pw.K, b.pw.N, b.pw.Npad, ACT_HSWISH, min_pix) : 0;
   static const bool no_se_fusion = getenv("RT_NO_SE_FUSION") != nullptr;  // A/B switch
-  const bool fuse_se = b.se && tile_rows > 0 && b.pw.K <= 512 && (b.dw.k == 3 || b.dw.k == 5) && !no_se_fusion;
+  const bool fuse_se = tile_rows > 0 && (b.dw.k == 3 || b.dw.k == 5) && !no_se_fusion;
   float* pool = nullptr; int chunks = 0, strip_R = 0, strips_pb = 32;
   if (fuse_se) {
     nn::dwconv_pool_layout(b.dw.k, b.sh, b.sw, b.dw.Cp, Lout.maxH, Lout.maxW, &chunks, &strip_R, &strips_pb);
@@ -287,8 +287,9 @@ static float* run_lc(RunCtx& c, const LcBlock& b, const float* x, const Level& L
   }
   int Cpo = chan_pitch(b.cout);
   float* y2 = c.arena->alloc<float>((size_t)Lout.total * Cpo);
-  { ProfScope ps(c.prof, c.st, nn::gemm_pw_label(Lout.total, b.pw.Npad, fuse_se, tile_rows), shape_str(Lout.total, b.pw.K, b.pw.N, 0));
-    nn::gemm(c.st, y1, b.dw.Cp, Lout.total, b.pw.K, b.pw.w, b.pw.N, b.pw.Npad, y2, Cpo, 0, epi); }
+  const nn::GemmPlan plan = nn::gemm_plan(b.dw.Cp, Lout.total, b.pw.K, b.pw.N, b.pw.Npad, Cpo, 0, epi, stream_cus(c.st));
+  { ProfScope ps(c.prof, c.st, plan.label, shape_str(Lout.total, b.pw.K, b.pw.N, 0));
+    nn::gemm(c.st, plan, y1, b.dw.Cp, Lout.total, b.pw.K, b.pw.w, b.pw.N, b.pw.Npad, y2, Cpo, 0, epi); }
   return y2;
 }
 

@@ -3,37 +3,34 @@
 // images described by device arrays of rt::ImgGeom.
 #pragma once
 #include "common.h"
+#include "gemm_plan.h"
 
 namespace rt {
 namespace nn {
 
 constexpr int KC = 32;  // K-chunk of the MFMA GEMM / conv kernels (weights are packed in KC slabs)
 
-// C[M, ldc] (+coff) = epi(A[M, lda] x W), W packed as [ceil(K/KC)][Npad16][KC].
+// C[M, ldc] (+coff) = epi(A[M, lda] x W), W packed as [ceil(K/KC)][Npad16][KC]: the kernel of gemm_plan() (gemm_plan.h).
 void gemm(hipStream_t st, const float* A, int lda, long long M, int K, const float* Wp, int N, int Npad16, float* C,
           int ldc, int coff, const Epilogue& epi);
-const char* gemm_pw_label(long long M, int Npad16, bool a_scale = false, int se_tile_rows = 0);   // se_tile_rows: gemm_se_tile_rows() of the layer
-// Persistent LDS-DMA form of the 256 x 240 tile (nn_gemm_dma.hip): N a multiple of 240, K whole 16-deep groups, plain
-// bias / activation / LAB epilogue.  gemm() takes it for the large 240- / 480-channel layers.
-// k_gemm32w: K = N = 128 with the weights resident in LDS (nn_gemm_dma.hip)
-bool gemm_w_supported(int lda, long long M, int K, int N, int Npad16, const Epilogue& epi, int ldc = 0, int coff = 0);
+// ... with the plan already made (p = gemm_plan() of the same arguments; callers that also need its label)
+void gemm(hipStream_t st, const GemmPlan& p, const float* A, int lda, long long M, int K, const float* Wp, int N, int Npad16,
+          float* C, int ldc, int coff, const Epilogue& epi);
+// Launchers of the persistent kernels (nn_gemm_dma.hip; gemm() calls them where the plan names them):
+// k_gemm32w: K = N = 128 with the weights resident in LDS
 void gemm_w(hipStream_t st, const float* A, int lda, long long M, int K, const float* Wp, int N, int Npad16, float* C, int ldc, int coff,
             const Epilogue& epi);
-bool gemm_dma_supported(int lda, long long M, int K, int N, int Npad16, const Epilogue& epi);
+// k_gemm32p: persistent LDS-DMA form of the 256 x 240 tile, for the large 240- / 480-channel layers
 void gemm_dma(hipStream_t st, const float* A, int lda, long long M, int K, const float* Wp, int N, int Npad16, float* C,
               int ldc, int coff, const Epilogue& epi);
 // Split-bf16 form of the same layers (nn_gemm_split.hip): three bf16 planes per operand, six v_mfma_f32_16x16x32_bf16 products
 // per fp32 product, fp32 accumulation.  Opt-in: g_gemm_split (RT_GEMM_SPLIT=1, rt_debug_set_variants flag bit 12).
-extern int g_gemm_split;
-bool gemm_split_supported(int lda, long long M, int K, int N, int Npad16, const Epilogue& epi);
 void gemm_split(hipStream_t st, const float* A, int lda, long long M, int K, const float* Wp, int N, int Npad16, float* C,
                 int ldc, int coff, const Epilogue& epi);
 void gemm_split_forget(const float* Wp);   // drops the cached split planes of a weight pack (before its memory is freed / reused)
 void set_dw_xcd(int v);  // A/B: XCD-aware block order of the depthwise kernel (default on)
 extern int g_dw_wide_slab_min, g_dw_wide3_min, g_dw_wide_lp;
-extern int g_dw_variant;    // same for dwconv
-extern int g_gemm_variant;  // kernel micro-benchmark hook (0 = production dispatch)
-extern int g_gemm_dma;      // A/B: persistent LDS-DMA wide GEMM on (default) / off
+extern int g_dw_variant;    // kernel micro-benchmark hook of dwconv (g_gemm_variant: gemm_plan.h)
 extern int g_dw_sweep;      // A/B: column-sweep 5x5 depthwise kernel: pixels per thread (0: off)
 
 // Dense stride-1 "same" convolution, kernel (KH,KW) in {(3,3),(1,3)}; W packed as
@@ -56,19 +53,10 @@ void dwconv_pool_layout(int K, int sh, int sw, int Cp, int maxHo, int maxWo, int
 void se_fc_from_dw(hipStream_t st, const float* partial, const ImgGeom* geom, int n_img, int chunks, int strip_R,
                    int strips_per_block, int C, int Cp, const float* w1, const float* b1, const float* w2, const float* b2,
                    int Cr, float slope, int residual, float* scale);
-// Row-tile height of the wide GEMM the dispatcher picks for (M, Npad16), 0 when it picks the narrow
-// kernel: Epilogue::a_scale (squeeze-excite scale folded into the A staging) needs a wide tile and
-// every image at least that many rows.
-int gemm_tile_rows(long long M, int Npad16);
-// ... and which fused squeeze-excite form gemm() will take for this layer: 256 (k_gemm32p: a_tab entries of 3 ints per
-// 256-row block, Epilogue::a_tab_stride = 3, n_img set), 128 (wide register-staged tiles: 2 ints per 128-row block) or 0 (none:
-// scale the tensor in a pass of its own).  min_pix: rows of the smallest image.
-int gemm_se_tile_rows(int lda, long long M, int K, int N, int Npad16, int act, long long min_pix);
 // Fused CTC head: gemm() with Epilogue::am_* set (am_tiles = gemm_argmax_tiles(Npad16), buffers of
 // M * am_tiles elements) leaves softmax statistics per column tile; argmax_merge gives, per row, the
 // argmax over the N logits and softmax(logits)[argmax] -- the [M, 6625] logits never reach HBM.
-extern int g_argmax_wide;
-int gemm_argmax_tiles(int Npad16);
+int gemm_argmax_tiles(int Npad16);   // (gemm_plan.cpp: depends on g_argmax_wide)
 void argmax_merge(hipStream_t st, const float* pm, const int* pi, const float* ps, int tiles, long long rows, int* idx,
                   float* prob);
 

@@ -79,12 +79,11 @@ struct GemmPArgs {
   Epilogue epi;
 };
 
-constexpr int P_BM = 256, P_BN = 240, P_MT = 4, P_NT = 5, P_WN = 3, P_NW = 12, P_NTHR = 768;
+constexpr int P_MT = 4, P_NT = 5, P_WN = 3, P_NW = 12, P_NTHR = 768;
 constexpr unsigned P_ABYTES = P_BM * 128, P_WBYTES = P_BN * 128, P_STAGE = P_ABYTES + P_WBYTES;   // 63488 bytes per slab
 constexpr int P_AJ = P_BM / 8, P_WJ = P_BN / 8;              // 1-KB DMA pieces (8 rows of 128 bytes) per operand and slab
 constexpr int P_NSTORE = P_MT * P_NT;                        // store instructions of one wave's epilogue
-constexpr int P_BIAS_MAX = 960;                              // bias vector kept in LDS (N <= 960)
-constexpr int P_SCK = 512;                                   // ASC: K <= 512; scale table = 2 tile parities x 3 images x P_SCK floats
+// (P_BM x P_BN tile, P_BIAS_MAX bias floats, P_SCK: ASC K <= 512 -- gemm_plan.h; scale table = 2 tile parities x 3 images x P_SCK floats)
 constexpr size_t P_LDS = 2 * (size_t)P_STAGE + P_BIAS_MAX * 4 + 16;   // slabs | bias | tile queue
 constexpr size_t P_LDS_ASC = P_LDS + 2 * 3 * P_SCK * 4;               // ... | scale tables
 
@@ -545,7 +544,7 @@ struct GemmWArgs {
   int lda, ldc, coff, n_tiles;
   Epilogue epi;
 };
-constexpr int W_BM = 64, W_NTHR = 512;
+constexpr int W_NTHR = 512;   // (W_BM: gemm_plan.h)
 constexpr unsigned W_WBYTES = 128 * 128 * 4, W_ABYTES = W_BM * 128 * 4;
 constexpr size_t W_LDS = W_WBYTES + 2 * (size_t)W_ABYTES + 128 * 4;   // weights | two pixel tiles | bias
 
@@ -639,15 +638,6 @@ __global__ __launch_bounds__(W_NTHR, 1) void k_gemm32w(const GemmWArgs g) {
   });
 }
 
-bool gemm_w_supported(int lda, long long M, int K, int N, int Npad16, const Epilogue& epi, int ldc, int coff) {
-  static const int on = getenv("RT_GEMM_W") ? atoi(getenv("RT_GEMM_W")) : 1;   // A/B: 0 = k_gemm<8>
-  if (!on || epi.am_max || epi.residual || epi.a_scale) return false;
-  if (K != 128 || N != 128 || Npad16 != 128) return false;
-  if (lda < 128 || (lda & 3) || (long long)lda * 4 * W_BM >= (1ll << 31)) return false;
-  if ((ldc & 3) || (coff & 3)) return false;   // 16-byte stores of four consecutive channels
-  return M >= 65536;
-}
-
 void gemm_w(hipStream_t st, const float* A, int lda, long long M, int K, const float* Wp, int N, int Npad16, float* C, int ldc, int coff,
             const Epilogue& epi) {
   GemmWArgs g;
@@ -656,19 +646,6 @@ void gemm_w(hipStream_t st, const float* A, int lda, long long M, int K, const f
   const int grid = std::min(g.n_tiles, stream_cus(st));
   allow_big_lds((const void*)k_gemm32w, 160 * 1024);
   RT_LAUNCH(k_gemm32w, dim3((unsigned)grid), dim3(W_NTHR), W_LDS, st, g);
-}
-
-bool gemm_dma_supported(int lda, long long M, int K, int N, int Npad16, const Epilogue& epi) {
-  if (epi.am_max || epi.residual) return false;
-  // squeeze-excite scale: 3-int row-block table (gemm_se_tile_rows() == 256), hardswish epilogue, K within the LDS scale table
-  if (epi.a_scale && (epi.a_tab_stride != 3 || !epi.a_tab || K > P_SCK || epi.act != ACT_HSWISH || epi.n_img <= 0)) return false;
-  if ((N + 3) / 4 * 4 != N) return false;
-  if (Npad16 != N || N % P_BN != 0 || N > P_BIAS_MAX) return false;
-  // (>= 4 slabs: the request side reads the next tile's id when it has issued a tile's last slab, at the hand-over of the
-  //  tile's slab nkc - 3; the id is published at the hand-over of slab 1)
-  if (K % 16 != 0 || K <= 3 * KC || lda < round_up(K, KC) || (lda & 3)) return false;   // whole 16-deep groups; 32-deep slabs readable
-  if ((long long)lda * 4 * P_BM >= (1ll << 31)) return false;
-  return M >= P_BM;
 }
 
 void gemm_dma(hipStream_t st, const float* A, int lda, long long M, int K, const float* Wp, int N, int Npad16, float* C,

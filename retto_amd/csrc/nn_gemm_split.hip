@@ -107,7 +107,7 @@ __device__ __forceinline__ f32x4 mfma_bf16(const u32x4 w, const u32x4 a, const f
 
 }  // namespace
 
-constexpr int S_BM = 128, S_BN = 240, S_NT = 15, S_NW = 4, S_NTHR = 256;
+constexpr int S_BM = 128, S_NT = 15, S_NW = 4, S_NTHR = 256;   // (S_BN = 240: gemm_plan.h)
 constexpr int S_GT = 5;                                         // tiles per weight group: a slab = 3 groups (0..4 | 5..9 | 10..14)
 constexpr unsigned S_WSLAB = S_NT * 3 * 1024;                   // 46080 bytes of split weights per K slab and column block
 constexpr unsigned S_WGRP = S_GT * 3 * 1024;                    // ring buffer of one group: 15 KB
@@ -586,21 +586,6 @@ __global__ __launch_bounds__(S_NTHR, 2) void k_gemm_split(const GemmSArgs g) {
 }
 
 // ---- host side ----------------------------------------------------------------------------------------------------------------
-int g_gemm_split = getenv("RT_GEMM_SPLIT") ? atoi(getenv("RT_GEMM_SPLIT")) : 0;   // opt-in (RT_GEMM_SPLIT=1 / rt_debug_set_variants): gemm() takes the split-bf16 kernel where it applies
-
-bool gemm_split_supported(int lda, long long M, int K, int N, int Npad16, const Epilogue& epi) {
-  if (epi.am_max || epi.residual) return false;
-  static const int only = getenv("RT_GS_ONLY") ? atoi(getenv("RT_GS_ONLY")) : 3;   // (triage: 1 = plain launches only, 2 = +se only)
-  if (!(only & (epi.a_scale ? 2 : 1))) return false;
-  // squeeze-excite scale: a row-block table of either form, hardswish epilogue, images of >= 128 rows (what gemm_se_tile_rows() > 0 says)
-  if (epi.a_scale && (!epi.a_tab || (epi.a_tab_stride != 2 && epi.a_tab_stride != 3) || epi.act != ACT_HSWISH || epi.n_img <= 0 || epi.ld_scale < K)) return false;
-  if (Npad16 != N || N % S_BN != 0 || N > 960) return false;
-  if (lda < round_up(K, KC) || (lda & 3)) return false;          // whole 32-deep slabs readable (padding channels hold zeros)
-  if ((long long)lda * 4 * 32 >= (1ll << 31)) return false;
-  // (large launches only: the small-batch dispatch of a one-page call stays on the narrow fp32 kernel)
-  return M >= 32768 && K > 3 * KC;   // (>= 4 slabs: the request streams read the next tile's id two slabs before a tile ends; it is published in the tile's first slab)
-}
-
 // the split planes of a packed fp32 weight matrix, built on first use and kept for the life of the process (keyed by the
 // device pointer of the fp32 pack: the networks' weights live as long as their session)
 static std::mutex g_split_mu;

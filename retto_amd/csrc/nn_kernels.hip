@@ -728,37 +728,6 @@ void lc_thin(hipStream_t st, int sh, int sw, const float* x, const ImgGeom* gin,
 #undef RT_LCT_T
 }
 
-int g_gemm_variant = 0;  // 0 = production choice; others are forced by the kernel micro-benchmark
-int g_gemm_dma = getenv("RT_GEMM_DMA") ? atoi(getenv("RT_GEMM_DMA")) : 1;   // A/B: 0 keeps the register-staged 256 x 240 tile
-
-// production dispatch (tools/bench_gemm.py): wide tiles once N and M are large; 0 = narrow k_gemm<NT>
-static int gemm_dispatch(long long M, int Npad16) {
-  if (Npad16 % 240 == 0 && M >= 131072) return 15;  // 256 x 240 tile: halves the weight re-fetch per row
-  // (round 5: the 128 x 240 tile only where it fills the chip twice -- 38 k rows x 240 channels, a one-page batch, are 300
-  //  workgroups of 768 threads on 256 CUs: two rounds for 1.17 rounds of work; the narrow kernel's 600 workgroups sit four to a CU)
-  static const int mid_env = getenv("RT_GEMM_MID") ? atoi(getenv("RT_GEMM_MID")) : 1;   // A/B: 0 = the 128 x 240 tile from 16384 rows
-  if (Npad16 % 240 == 0 && M >= 16384 && (!mid_env || (M + 127) / 128 * (Npad16 / 240) >= 512)) return 10;
-  // (the 128 x 128 tile, variant 8, lost to the narrow kernel once that prefetched its next K-slab: 192 x 192 at
-  // 115200 rows 85 vs 65 TFLOP/s, 128 x 128 at 2.4 M rows 76 vs 72; it remains the squeeze-excite (a_scale) and CTC tile)
-  return 0;  // gemm() picks the streaming kernel when K, N <= 64, else the narrow LDS kernel
-}
-// Profiler label of a pointwise-conv GEMM: family + the kernel symbol the dispatcher picks, so the
-// per-kernel numbers of bench.py can be compared with rocprofv3's kernel stats one to one.
-const char* gemm_pw_label(long long M, int Npad16, bool a_scale, int se_tile_rows) {
-  if (!g_gemm_variant && g_gemm_split && Npad16 % 240 == 0 && M >= 32768 && (!a_scale || se_tile_rows > 0)) return a_scale ? "gemm_pw/k_gemm_split+se" : "gemm_pw/k_gemm_split";   // (K > 96 is what the rec net's layers have)
-  if (a_scale && se_tile_rows == 256) return "gemm_pw/k_gemm32p+se";
-  if (a_scale && !g_gemm_variant) return gemm_dispatch(M, Npad16) == 0 ? "gemm_pw/k_gemm_wide<2,4,4,2>+se" : "gemm_pw/k_gemm_wide<2,5,4,3>+se";
-  switch (g_gemm_variant ? -1 : gemm_dispatch(M, Npad16)) {
-    case 15: return g_gemm_dma ? "gemm_pw/k_gemm32p" : "gemm_pw/k_gemm_wide<4,5,4,3>";
-    case 10: return "gemm_pw/k_gemm_wide<2,5,4,3>";
-    case 0: return "gemm_pw/thin";  // k_gemm_stream (K, N <= 64) or k_gemm<NT>
-    default: return "gemm_pw/variant";
-  }
-}
-
-int g_argmax_wide = 0;  // CTC head: 0 = narrow kernel with 128-column blocks; 2 = 128 x 128 wide tile (0.92 ms); 1 = 256 x 240 tile (0.97 ms)
-int gemm_argmax_tiles(int Npad16) { return g_argmax_wide == 1 ? (Npad16 + 239) / 240 : (Npad16 + 127) / 128; }
-
 // one thread per row: fold the column tiles in ascending order -> argmax (first maximum) and softmax(max) = 1 / sum
 __global__ __launch_bounds__(256) void k_argmax_merge(const float* __restrict__ pm, const int* __restrict__ pi,
                                                       const float* __restrict__ ps, int tiles, long long rows,
@@ -782,131 +751,56 @@ void argmax_merge(hipStream_t st, const float* pm, const int* pi, const float* p
   RT_LAUNCH(k_argmax_merge, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, st, pm, pi, ps, tiles, rows, idx, prob);
 }
 
-// Row-block height of the squeeze-excite (a_scale) form the dispatcher will take: 256 = k_gemm32p (3-int a_tab entries, images
-// of >= 128 rows), 128 = the register-staged wide tiles (2-int entries, images >= 128 rows), 0 = no fused form.
-int gemm_se_tile_rows(int lda, long long M, int K, int N, int Npad16, int act, long long min_pix) {
-  if (g_gemm_variant) return 0;
-  Epilogue probe; probe.act = act;
-  if (g_gemm_dma && gemm_dispatch(M, Npad16) == 15 && min_pix >= 128 && K <= 512 && act == ACT_HSWISH &&
-      gemm_dma_supported(lda, M, K, N, Npad16, probe))
-    return 256;
-  const int r = gemm_tile_rows(M, Npad16);
-  return (r > 0 && min_pix >= r) ? r : 0;
-}
-int gemm_tile_rows(long long M, int Npad16) {
-  if (g_gemm_variant) return 0;
-  if (gemm_dispatch(M, Npad16) != 0) return 128;  // (a_scale runs the 256 x 240 shapes on the 128 x 240 tile)
-  return (Npad16 >= 128 && M >= 8192) ? 128 : 0;  // a_scale on the 128 x 128 tile
-}
-
 void gemm(hipStream_t st, const float* A, int lda, long long M, int K, const float* Wp, int N, int Npad16, float* C,
           int ldc, int coff, const Epilogue& epi) {
-  if (M <= 0) return;
-  int v = g_gemm_variant;
-  if (v == 0) v = gemm_dispatch(M, Npad16);
-  if (epi.am_max) {  // CTC head: softmax statistics per column tile instead of the logits (argmax_merge folds them)
-    if (epi.am_tiles != gemm_argmax_tiles(Npad16)) throw RtError(8, "gemm: am_tiles must be gemm_argmax_tiles(Npad16)");
-    if (g_argmax_wide == 1) {
-      dim3 grid((unsigned)((M + 255) / 256), (unsigned)((Npad16 + 239) / 240));
-      RT_LAUNCH((k_gemm_wide<4, 5, 4, 3, 0, 0, 0, 1>), grid, dim3(768), 0, st, A, lda, M, K, Wp, N, Npad16, C, ldc, coff, epi);
-    } else if (g_argmax_wide == 2) {
-      dim3 grid((unsigned)((M + 127) / 128), (unsigned)((Npad16 + 127) / 128));
-      RT_LAUNCH((k_gemm_wide<2, 4, 4, 2, 0, 0, 0, 1>), grid, dim3(512), 0, st, A, lda, M, K, Wp, N, Npad16, C, ldc, coff, epi);
-    } else {  // narrow kernel, 128-column blocks
-      dim3 grid((unsigned)((M + 127) / 128), (unsigned)((Npad16 + 127) / 128));
-      static const int bf_env1 = getenv("RT_GEMM_BF") ? atoi(getenv("RT_GEMM_BF")) : 1;
-      if (bf_env1 && (long long)128 * lda * 4 < (1ll << 31) && (long long)((K + KC - 1) / KC) * Npad16 * KC * 4 < (1ll << 31))
-        RT_LAUNCH((k_gemm<8, 1, true>), grid, dim3(256), 0, st, A, lda, M, K, Wp, N, Npad16, C, ldc, coff, epi);
-      else
-      RT_LAUNCH((k_gemm<8, 1>), grid, dim3(256), 0, st, A, lda, M, K, Wp, N, Npad16, C, ldc, coff, epi);
-    }
-    return;
-  }
-  if ((v == 40 || (!g_gemm_variant && g_gemm_split)) && gemm_split_supported(lda, M, K, N, Npad16, epi)) {
-    gemm_split(st, A, lda, M, K, Wp, N, Npad16, C, ldc, coff, epi);
-    return;
-  }
-  if (v == 40) v = 30;
-  if (!g_gemm_variant && gemm_w_supported(lda, M, K, N, Npad16, epi, ldc, coff)) { gemm_w(st, A, lda, M, K, Wp, N, Npad16, C, ldc, coff, epi); return; }
-  // persistent LDS-DMA form of the 256 x 240 tile (variant 30; production for the large N = 240 / 480 layers)
-  if ((v == 30 || (v == 15 && !g_gemm_variant && g_gemm_dma)) && gemm_dma_supported(lda, M, K, N, Npad16, epi)) {
-    gemm_dma(st, A, lda, M, K, Wp, N, Npad16, C, ldc, coff, epi);
-    return;
-  }
-  if (v == 30) v = 15;
-  if (epi.a_scale && epi.a_tab_stride != 2) throw RtError(8, "gemm: a 3-int a_tab is only understood by k_gemm32p (gemm_se_tile_rows() == 256)");
-  if (epi.a_scale) {  // squeeze-excite scale folded into the A staging: wide tiles only (gemm_tile_rows)
-    if (K > 512 || !epi.a_tab) throw RtError(8, "gemm: a_scale needs K <= 512 and a row-tile table");
-    if (v == 15) v = 10;  // the 256-row tile has no registers to spare for the scaling (spills): 128 x 240 measured faster
-    if (v == 0 && Npad16 >= 128) v = 8;
-    if (v == 10) {
-      dim3 grid((unsigned)((M + 127) / 128), (unsigned)((Npad16 + 239) / 240));
-      RT_LAUNCH((k_gemm_wide<2, 5, 4, 3, 0, 0, 1>), grid, dim3(768), 0, st, A, lda, M, K, Wp, N, Npad16, C, ldc, coff, epi);
-    } else if (v == 8) {
-      dim3 grid((unsigned)((M + 127) / 128), (unsigned)((Npad16 + 127) / 128));
-      RT_LAUNCH((k_gemm_wide<2, 4, 4, 2, 0, 0, 1>), grid, dim3(512), 0, st, A, lda, M, K, Wp, N, Npad16, C, ldc, coff, epi);
-    } else {
-      throw RtError(8, "gemm: a_scale is only implemented for the wide tiles");
-    }
-    return;
-  }
-  if (v == 8) {
-    dim3 grid((unsigned)((M + 127) / 128), (unsigned)((Npad16 + 127) / 128));
-    RT_LAUNCH((k_gemm_wide<2, 4, 4, 2>), grid, dim3(512), 0, st, A, lda, M, K, Wp, N, Npad16, C, ldc, coff, epi);
-    return;
-  }
-  if ((v == 20 && Npad16 <= 128 && K <= 128) || (v == 0 && !g_gemm_variant && Npad16 <= 64 && K <= 64 && M >= 65536)) {  // streaming kernel for the thin layers
-    const int ntl = Npad16 / 16, kg = (K + 15) / 16;
-    const long long tiles = (M + 31) / 32;
-    const unsigned blocks = (unsigned)std::min<long long>((tiles + 3) / 4, 256 * 8);
-#define RT_GS(NTV, KGV) RT_LAUNCH((k_gemm_stream<NTV, KGV>), dim3(blocks), dim3(256), 0, st, A, lda, M, K, Wp, N, Npad16, C, ldc, coff, epi)
-#define RT_GS_K(NTV) do { if (kg <= 1) RT_GS(NTV, 1); else if (kg <= 2) RT_GS(NTV, 2); else if (kg <= 4) RT_GS(NTV, 4); else if (kg <= 6) RT_GS(NTV, 6); else RT_GS(NTV, 8); } while (0)
-    if (ntl <= 1) RT_GS_K(1); else if (ntl <= 2) RT_GS_K(2); else if (ntl <= 3) RT_GS_K(3); else if (ntl <= 4) RT_GS_K(4);
-    else if (ntl <= 6) RT_GS_K(6); else RT_GS_K(8);
+  gemm(st, gemm_plan(lda, M, K, N, Npad16, ldc, coff, epi, stream_cus(st)), A, lda, M, K, Wp, N, Npad16, C, ldc, coff, epi);
+}
+
+void gemm(hipStream_t st, const GemmPlan& p, const float* A, int lda, long long M, int K, const float* Wp, int N, int Npad16,
+          float* C, int ldc, int coff, const Epilogue& epi) {
+  const dim3 grid(p.grid_x, p.grid_y);
+#define RT_GEMM_ARGS A, lda, M, K, Wp, N, Npad16, C, ldc, coff, epi
+  switch (p.kernel) {
+    case GemmKernel::none: return;
+    case GemmKernel::invalid: throw RtError(8, p.error);
+    case GemmKernel::split: gemm_split(st, RT_GEMM_ARGS); return;
+    case GemmKernel::w: gemm_w(st, RT_GEMM_ARGS); return;
+    case GemmKernel::dma: gemm_dma(st, RT_GEMM_ARGS); return;
+    case GemmKernel::wide_256x240: RT_LAUNCH((k_gemm_wide<4, 5, 4, 3>), grid, dim3(768), 0, st, RT_GEMM_ARGS); return;
+    case GemmKernel::wide_128x240:
+      if (p.se) RT_LAUNCH((k_gemm_wide<2, 5, 4, 3, 0, 0, 1>), grid, dim3(768), 0, st, RT_GEMM_ARGS);
+      else RT_LAUNCH((k_gemm_wide<2, 5, 4, 3>), grid, dim3(768), 0, st, RT_GEMM_ARGS);
+      return;
+    case GemmKernel::wide_128x128:
+      if (p.se) RT_LAUNCH((k_gemm_wide<2, 4, 4, 2, 0, 0, 1>), grid, dim3(512), 0, st, RT_GEMM_ARGS);
+      else RT_LAUNCH((k_gemm_wide<2, 4, 4, 2>), grid, dim3(512), 0, st, RT_GEMM_ARGS);
+      return;
+    case GemmKernel::stream:
+#define RT_GS(NTV, KGV) case KGV: RT_LAUNCH((k_gemm_stream<NTV, KGV>), grid, dim3(256), 0, st, RT_GEMM_ARGS); return;
+#define RT_GS_K(NTV) case NTV: switch (p.kg) { RT_GS(NTV, 1) RT_GS(NTV, 2) RT_GS(NTV, 4) RT_GS(NTV, 6) RT_GS(NTV, 8) } break;
+      switch (p.nt) { RT_GS_K(1) RT_GS_K(2) RT_GS_K(3) RT_GS_K(4) RT_GS_K(6) RT_GS_K(8) }
 #undef RT_GS_K
 #undef RT_GS
-    return;
-  }
-  if (v == 15) {
-    dim3 grid((unsigned)((M + 255) / 256), (unsigned)((Npad16 + 239) / 240));
-    RT_LAUNCH((k_gemm_wide<4, 5, 4, 3>), grid, dim3(768), 0, st, A, lda, M, K, Wp, N, Npad16, C, ldc, coff, epi);
-    return;
-  }
-  if (v == 10) {
-    dim3 grid((unsigned)((M + 127) / 128), (unsigned)((Npad16 + 239) / 240));
-    RT_LAUNCH((k_gemm_wide<2, 5, 4, 3>), grid, dim3(768), 0, st, A, lda, M, K, Wp, N, Npad16, C, ldc, coff, epi);
-    return;
-  }
-  int ntiles = Npad16 / 16;
-  int NT = ntiles >= 8 ? 8 : ntiles;
-  if (ntiles > 8) {  // pick the split with least padding among 8 / 6 / 5
-    int best = 8, waste = round_up(ntiles, 8) - ntiles;
-    for (int c : {6, 5, 4}) {
-      int w = round_up(ntiles, c) - ntiles;
-      if (w < waste) { waste = w; best = c; }
-    }
-    NT = best;
-  }
-  // small M (one page, the coarse pyramid levels): fewer columns per workgroup until there is a workgroup per CU -- 3600 x 480 x
-  // 480 on 128 x 128 tiles is 116 workgroups walking 15 slabs each, 35 us; the column tiles are independent: same bits
-  {
-    const long long rbs = (M + 127) / 128;
-    static const int occ_env = getenv("RT_GEMM_OCC") ? atoi(getenv("RT_GEMM_OCC")) : 2;   // workgroups per CU to aim for
-    const long long want = (long long)stream_cus(st) * occ_env;
-    while (NT > 1 && rbs * ((ntiles + NT - 1) / NT) < want) NT = (NT + 1) / 2;
-  }
-  dim3 grid((unsigned)((M + 127) / 128), (unsigned)((ntiles + NT - 1) / NT));
-  // buffer-resource fetch (k_gemm<NT, 0, true>): a tile's 128 rows and the packed weights within the 2-GB offset range
-  static const int bf_env = getenv("RT_GEMM_BF") ? atoi(getenv("RT_GEMM_BF")) : 1;
-  const bool bf = bf_env && (long long)128 * lda * 4 < (1ll << 31) && (long long)((K + KC - 1) / KC) * Npad16 * KC * 4 < (1ll << 31);
+      break;
+    case GemmKernel::narrow:
 #define RT_GEMM_CASE(n) \
-  case n: if (bf) RT_LAUNCH((k_gemm<n, 0, true>), grid, dim3(256), 0, st, A, lda, M, K, Wp, N, Npad16, C, ldc, coff, epi); \
-          else RT_LAUNCH(k_gemm<n>, grid, dim3(256), 0, st, A, lda, M, K, Wp, N, Npad16, C, ldc, coff, epi); break;
-  switch (NT) {
-    RT_GEMM_CASE(1) RT_GEMM_CASE(2) RT_GEMM_CASE(3) RT_GEMM_CASE(4) RT_GEMM_CASE(5) RT_GEMM_CASE(6) RT_GEMM_CASE(7)
-    RT_GEMM_CASE(8)
-  }
+  case n: if (p.bf) RT_LAUNCH((k_gemm<n, 0, true>), grid, dim3(256), 0, st, RT_GEMM_ARGS); \
+          else RT_LAUNCH(k_gemm<n>, grid, dim3(256), 0, st, RT_GEMM_ARGS); return;
+      switch (p.nt) {
+        RT_GEMM_CASE(1) RT_GEMM_CASE(2) RT_GEMM_CASE(3) RT_GEMM_CASE(4) RT_GEMM_CASE(5) RT_GEMM_CASE(6) RT_GEMM_CASE(7)
+        RT_GEMM_CASE(8)
+      }
 #undef RT_GEMM_CASE
+      break;
+    case GemmKernel::argmax_256x240: RT_LAUNCH((k_gemm_wide<4, 5, 4, 3, 0, 0, 0, 1>), grid, dim3(768), 0, st, RT_GEMM_ARGS); return;
+    case GemmKernel::argmax_128x128: RT_LAUNCH((k_gemm_wide<2, 4, 4, 2, 0, 0, 0, 1>), grid, dim3(512), 0, st, RT_GEMM_ARGS); return;
+    case GemmKernel::argmax_narrow:
+      if (p.bf) RT_LAUNCH((k_gemm<8, 1, true>), grid, dim3(256), 0, st, RT_GEMM_ARGS);
+      else RT_LAUNCH((k_gemm<8, 1>), grid, dim3(256), 0, st, RT_GEMM_ARGS);
+      return;
+  }
+#undef RT_GEMM_ARGS
+  throw RtError(8, "gemm: the plan names no kernel instance");
 }
 
 // ---------------------------------------------------------------------------

@@ -20,28 +20,41 @@ def _down(v: int, s: int) -> int:
     return (v - 1) // s + 1
 
 
-def gemm_pw_label(M: int, N: int, se: bool = False, K: int = 0, min_pix: int = 1 << 30) -> str:
-    """Mirror of nn::gemm_pw_label + the predicates behind it (retto_amd/csrc/nn_kernels.hip gemm_dispatch / gemm_se_tile_rows,
-    nn_gemm_dma.hip gemm_dma_supported): which kernel symbol the dispatcher picks for a pointwise conv of M rows, K input and
-    N output channels.  `se`: the block has a squeeze-excite whose scale is folded into the GEMM's A staging; `min_pix`: rows
-    of the smallest image of the level (the fused form needs every image to cover a row tile).  K = 0: unknown, assumed to
-    satisfy the K conditions (callers inside this module always pass it)."""
-    npad = (N + 15) // 16 * 16
-    dma_on = os.environ.get("RT_GEMM_DMA", "1") != "0"
-    # k_gemm32p: N == Npad16 a multiple of 240 (<= 480 per bias table), whole 16-deep K groups, more than 3 slabs of 32, M >= 131072
-    dma_shape = npad == N and N % 240 == 0 and M >= 131072 and (K == 0 or (K % 16 == 0 and K > 96))
-    if se:
-        if dma_on and dma_shape and min_pix >= 128 and (K == 0 or K <= 512):
+def _chan_pitch(c: int) -> int:
+    return (c + 31) // 32 * 32 if c >= 128 else (c + 3) // 4 * 4
+
+
+def gemm_pw_label(M: int, K: int, N: int, se: bool = False, min_pix: int = 1 << 30) -> str:
+    """Mirror of the label of nn::gemm_plan() (retto_amd/csrc/gemm_plan.cpp) for a pointwise conv of M rows, K input and N output
+    channels as nets.cpp run_lc launches it: A pitch chan_pitch(K), C pitch chan_pitch(N), hardswish epilogue, the production
+    choice with the split-bf16 kernels off.  `se`: the block has a squeeze-excite, folded into the GEMM's A staging where
+    nn::gemm_se_rows() offers a row table; `min_pix`: rows of the smallest image of the level (a row table needs >= 128)."""
+    K = (K + 3) // 4 * 4
+    npad, lda = (N + 15) // 16 * 16, _chan_pitch(K)
+    mid_rule = os.environ.get("RT_GEMM_MID", "1") != "0"
+    if npad % 240 == 0 and M >= 131072:
+        tile = "256x240"
+    elif npad % 240 == 0 and M >= 16384 and (not mid_rule or (M + 127) // 128 * (npad // 240) >= 512):
+        tile = "128x240"
+    else:
+        tile = None
+    # k_gemm32p: N == Npad16 a multiple of 240 (<= 960), whole 16-deep K groups, more than 3 slabs of 32, whole slabs readable
+    dma = (tile == "256x240" and os.environ.get("RT_GEMM_DMA", "1") != "0" and npad == N and N <= 960 and K % 16 == 0 and K > 96
+           and lda >= (K + 31) // 32 * 32)
+    if se and min_pix >= 128 and K <= 512:
+        if dma:
             return "gemm_pw/k_gemm32p+se"
-        wide = npad % 240 == 0 and M >= 16384
-        rows_ok = min_pix >= 128
-        if rows_ok and (K == 0 or K <= 512) and (wide or (M >= 8192 and npad >= 128)):
-            return "gemm_pw/k_gemm_wide<2,5,4,3>+se" if wide else "gemm_pw/k_gemm_wide<2,4,4,2>+se"
+        if tile:
+            return "gemm_pw/k_gemm_wide<2,5,4,3>+se"
+        if npad >= 128 and M >= 8192:
+            return "gemm_pw/k_gemm_wide<2,4,4,2>+se"
         # no fused form: the tensor is scaled in a pass of its own and the GEMM is the plain one
-    if npad % 240 == 0 and M >= 131072:   # (the persistent LDS-DMA form unless RT_GEMM_DMA=0 / an unsupported K keeps the register-staged tile)
-        return "gemm_pw/k_gemm32p" if (dma_on and dma_shape) else "gemm_pw/k_gemm_wide<4,5,4,3>"
-    if npad % 240 == 0 and M >= 16384:
-        return "gemm_pw/k_gemm_wide<2,5,4,3>"
+    if K == 128 and N == 128 and M >= 65536 and os.environ.get("RT_GEMM_W", "1") != "0":
+        return "gemm_pw/k_gemm32w"
+    if dma:
+        return "gemm_pw/k_gemm32p"
+    if tile:
+        return "gemm_pw/k_gemm_wide<4,5,4,3>" if tile == "256x240" else "gemm_pw/k_gemm_wide<2,5,4,3>"
     return "gemm_pw/thin"
 
 
@@ -112,7 +125,7 @@ def det_work(pages: Iterable[Tuple[int, int]], phase=None) -> Dict[str, Dict[str
                 scale = (ho * wo) / float(H * W)
                 m_group = int(round(sum(gh * gw for gh, gw in grp) * scale))
                 min_pix = int(round(min(gh * gw for gh, gw in grp) * scale))
-                add(gemm_pw_label(m_group, cout, se, cin, min_pix), ho * wo * (cin + cout) * F + cin * cout * F, 2 * ho * wo * cin * cout)
+                add(gemm_pw_label(m_group, cin, cout, se, min_pix), ho * wo * (cin + cout) * F + cin * cout * F, 2 * ho * wo * cin * cout)
             h, ww = ho, wo
             for j, (tn, tc, oc) in enumerate(synth.DET_TAPS):
                 if tn == name:
@@ -177,10 +190,10 @@ def rec_work(widths: Iterable[int], classes: int = synth.REC_CLASSES) -> Dict[st
         w[fam]["bytes"] += b; w[fam]["flops"] += f
 
     widths = list(widths)
-    group_of = {}
+    group_of, narrowest = {}, {}
     for g in _groups([48 * w_ for w_ in widths], REC_GROUP_PX):
         for i in g:
-            group_of[i] = g
+            group_of[i], narrowest[i] = g, min(widths[j] for j in g)
     for wi, W in enumerate(widths):
         H = 48
         grp_px = sum(48 * widths[i] for i in group_of[wi])
@@ -193,8 +206,8 @@ def rec_work(widths: Iterable[int], classes: int = synth.REC_CLASSES) -> Dict[st
             else:
                 add("dwconv%d" % k, (h * ww + ho * wo) * cin * F + k * k * cin * F, 2 * ho * wo * cin * k * k)
                 m_group = int(round(grp_px * (ho * wo) / float(H * W)))
-                min_pix = min(_rows_at(widths[i], name) for i in group_of[wi])
-                add(gemm_pw_label(m_group, cout, se, cin, min_pix), ho * wo * (cin + cout) * F + cin * cout * F, 2 * ho * wo * cin * cout)
+                min_pix = _rows_at(narrowest[wi], name)   # (the narrowest line of the launch group has the fewest rows)
+                add(gemm_pw_label(m_group, cin, cout, se, min_pix), ho * wo * (cin + cout) * F + cin * cout * F, 2 * ho * wo * cin * cout)
             h, ww = ho, wo
         T = (ww - 2) // 2 + 1
         add("avgpool", (h * ww + T) * 480 * F)

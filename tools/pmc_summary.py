@@ -50,6 +50,7 @@ LABELS = {"gemm_pw/k_gemm32p": "family:gemm32p", "gemm_pw/k_gemm32p+se": "family
           "gemm_pw/k_gemm_wide<4,5,4,3>": "k_gemm_wide<4, 5, 4, 3, 0, 0, 0, 0, 0>",
           "gemm_pw/k_gemm_wide<2,5,4,3>+se": "k_gemm_wide<2, 5, 4, 3, 0, 0, 1, 0, 0>",
           "gemm_pw/k_gemm_wide<2,4,4,2>": "k_gemm_wide<2, 4, 4, 2, 0, 0, 0, 0, 0>",
+          "gemm_pw/k_gemm32w": "k_gemm32w",
           "gemm_pw/k_gemm_split": "family:gemm_split", "gemm_pw/k_gemm_split+se": "family:gemm_split_se",
           "conv16_3x3": "family:conv16_3x3", "gemm16": "family:gemm16", "conv16_9x9": "family:conv16_9x9"}
 # fp16 families that several template instances serve: their "family:<name>" entry is the launch-weighted mean over the
