@@ -291,10 +291,9 @@ RT_API int rt_broadcast_blobs(const void* id, int rank, int world, int device_id
 /* ---- diagnostics for tools/ (kernel A/B switches and the GEMM micro-benchmark; no reference
  * counterpart, not needed by a drop-in host) ------------------------------------------------
  * rt_debug_set_variants: gemm_variant 0 = production dispatch, 8 / 10 / 15 / 20 force the
- * 128x128 / 128x240 / 256x240 wide tiles / the streaming kernel; dw_variant 0 = production,
- * 4 = 2-row depthwise strips; flags bits: 1 fused thin blocks OFF, 2 thin blocks on the
- * 128-pixel tile, 3 plain (not XCD-aware) depthwise block order, 4 32-channel depthwise slabs
- * only, 5 128- instead of 64-channel wide slabs, 6 CTC head on the 128x128 wide tile, 7 thin
+ * 128x128 / 128x240 / 256x240 wide tiles / the streaming kernel; dw_variant has no effect;
+ * flags bits: 0-5 no effect (their depthwise / thin-block variants were removed), 6 CTC head on
+ * the 128x128 wide tile, 7 thin
  * LCNetV3 blocks back on k_lc_thin / the unfused pair (instead of k_lc_lds), 8 the wide fp32 GEMM
  * back on the register-staged tile (instead of k_gemm32p), 9 5x5 depthwise back on
  * k_dwconv_rows (instead of the column sweep), 10 the angle classifier's blocks as the unfused launch
@@ -319,8 +318,7 @@ RT_API int rt_bench_gemm(rt_session* s, long long M, int K, int N, int variant, 
 RT_API int rt_bench_gemm_err(rt_session* s, long long M, int K, int N, int variant, int rows, int act, unsigned seed, double* out4);
 /* times the fused thin LCNetV3 block (3x3 depthwise -> 1x1 conv; n images of h x w, random data).  form: 0 = k_lc_thin
  * (workgroup-staged; the unfused depthwise + GEMM pair where it has no instance), 1 = k_lc_wave (direct loads, stride 1 only),
- * 3 = k_lc_lds (production), 5 = k_lc_lds incl. the opt-in 128 -> 128 split.  stride: 1, 2, or 21 = (2, 1).  Returns the average
- * ms and the max |diff| against form RT_BENCH_LC_REF (environment, default 0); RT_BENCH_LC_DUMP=1 prints where they differ. */
+ * 3 = k_lc_lds (production).  stride: 1, 2, or 21 = (2, 1).  Returns the average ms and the max |diff| against form 0. */
 RT_API int rt_bench_lc(rt_session* s, int n, int h, int w, int cin, int cout, int stride, int form, int iters, float* ms_out, float* maxdiff_out);
 
 #ifdef __cplusplus

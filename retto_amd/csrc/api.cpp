@@ -459,13 +459,8 @@ static void capture_variant_defaults() {
 }
 RT_API void rt_debug_set_variants(int gemm_variant, int dw_variant, int flags) {
   capture_variant_defaults();
+  (void)dw_variant;   // (no effect; bits 1-5 of flags neither)
   nn::g_gemm_variant = gemm_variant;
-  nn::g_dw_variant = dw_variant;
-  nn::g_lc_thin = (flags & 2) ? 0 : ((flags & 4) ? 2 : 4);
-  nn::set_dw_xcd((flags & 8) ? 0 : 1);
-  nn::g_dw_wide_slab_min = (flags & 16) ? (1 << 30) : 192;
-  nn::g_dw_wide3_min = (flags & 16) ? (1 << 30) : 128;
-  nn::g_dw_wide_lp = (flags & 32) ? 32 : 16;
   nn::g_argmax_wide = (flags & 64) ? 2 : 0;
   // round-3 kernels: bits 7-9 send their layers back to the kernels they replaced (defaults = what the environment selected at load)
   const int lc_wave0 = g_default_lc_wave, gemm_dma0 = g_default_gemm_dma, dw_sweep0 = g_default_dw_sweep, cls_fused0 = g_default_cls_fused;
@@ -652,8 +647,8 @@ RT_API int rt_bench_gemm_err(rt_session* s, long long M, int K, int N, int varia
 
 // Kernel micro-benchmark: the fused thin LCNetV3 block (3x3 depthwise -> pointwise) on n images of h x w pixels, random data.
 // form = nn::g_lc_wave for the timed launches: 0 = k_lc_thin (workgroup-staged; the unfused depthwise + GEMM pair where it has no
-// instance), 1 = k_lc_wave (direct loads, stride 1), 3 = k_lc_lds (production), 5 = also the opt-in 128 -> 128 split; stride 21
-// means (2, 1).  maxdiff compares with form RT_BENCH_LC_REF (default 0); RT_BENCH_LC_DUMP prints where the two differ.
+// instance), 1 = k_lc_wave (direct loads, stride 1), 3 = k_lc_lds (production); stride 21 means (2, 1).  maxdiff compares with
+// form 0.
 RT_API int rt_bench_lc(rt_session* s, int n, int h, int w, int cin, int cout, int stride, int form, int iters, float* ms_out, float* maxdiff_out) {
   RT_REQUIRE(s && ms_out && n > 0 && h > 0 && w > 0 && (stride == 1 || stride == 2 || stride == 21), s, "rt_bench_lc: bad argument");
   return guarded(s, [&] {
@@ -692,7 +687,7 @@ RT_API int rt_bench_lc(rt_session* s, int n, int h, int w, int cin, int cout, in
       }
       nn::lc_thin(s->st, sh, sw, dx, dgi, dgo, n, ho, wo, Cp, cin, dwd, dbd, dw_act, dw_lab, 0.99f, 0.01f, dw, cout, Np, out, ldy, e);
     };
-    nn::g_lc_wave = getenv("RT_BENCH_LC_REF") ? atoi(getenv("RT_BENCH_LC_REF")) : 0; run(dy0);
+    nn::g_lc_wave = 0; run(dy0);
     nn::g_lc_wave = form; run(dy);
     Events ev; RT_HIP_CHECK(hipEventCreate(&ev.a)); RT_HIP_CHECK(hipEventCreate(&ev.b));
     hipEvent_t a = ev.a, b = ev.b;
@@ -707,18 +702,9 @@ RT_API int rt_bench_lc(rt_session* s, int n, int h, int w, int cin, int cout, in
       float md = 0;
       for (size_t off : {(size_t)0, nout - cnt}) {
         RT_HIP_CHECK(hipMemcpy(c0.data(), dy0 + off, cnt * 4, hipMemcpyDeviceToHost)); RT_HIP_CHECK(hipMemcpy(c1.data(), dy + off, cnt * 4, hipMemcpyDeviceToHost));
-        size_t bad = 0;
-        std::map<std::string, int> hist;
         for (size_t i = 0; i < cnt; i++) {
           const float d = std::fabs(c0[i] - c1[i]); md = (d > md || d != d) ? (d != d ? INFINITY : d) : md;
-          if (d != 0 && getenv("RT_BENCH_LC_DUMP")) {
-            const size_t e = off + i, px = e / ldy; const int ch = (int)(e % ldy), img = (int)(px / ((size_t)ho * wo)), yy = (int)(px % ((size_t)ho * wo)) / wo, xx = (int)(px % wo);
-            if (bad++ < 4) fprintf(stderr, "  diff img %d y %d x %d ch %d: %g vs %g\n", img, yy, xx, ch, c0[i], c1[i]);
-            hist["x%16=" + std::to_string(xx % 16)]++; hist["ch%4=" + std::to_string(ch % 4)]++; hist["ch/16=" + std::to_string(ch / 16)]++; hist["y%2=" + std::to_string(yy % 2)]++;
-            hist["tx=" + std::to_string(xx / 16)]++; hist["q=" + std::to_string((ch % 16) / 4)]++;
-          }
         }
-        if (bad) { fprintf(stderr, "  %zu of %zu differ:", bad, cnt); for (auto& kv : hist) fprintf(stderr, " %s:%d", kv.first.c_str(), kv.second); fprintf(stderr, "\n"); }
       }
       *maxdiff_out = md;
     }

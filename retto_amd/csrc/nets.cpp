@@ -519,17 +519,10 @@ float* DetNet::run(RunCtx& c, const float* x, Level& L0, const nn::U8Page* pages
     a.coarse = p[1]; a.ld_coarse = 24; a.coarse_scale = p_scale[2]; a.ld_cs = 24; a.Wc = head_wc_;
     a.G = V45; a.gg = L16.d; a.g_plane = L16.total; a.y = h1; a.ldy = 24; a.act = ACT_RELU;
     nn::fpn_phase(c.st, a, 24, 24, L4.d, L8.d, L4.n(), L4.maxH, L4.maxW);
-  } else if (nn::conv3_fpn_fused_supported(24, 24)) {   // the head conv gathers the four levels itself: no 96-channel fuse tensor
+  } else {   // the head conv gathers the four levels itself: no 96-channel fuse tensor
     ProfScope ps(c.prof, c.st, "conv3x3", shape_str(L4.total, 9 * 96, 24, 1));
     nn::conv3_fpn_fused(c.st, p[3], p[2], p[1], p[0], L32.d, L16.d, L8.d, L4.d, L4.n(), L4.maxH, L4.maxW, 24, p_scale,
                         head_conv1_.w, 24, head_conv1_.Npad, h1, 24, make_epi(head_conv1_, ACT_RELU));
-  } else {
-    float* fuse = c.arena->alloc<float>((size_t)L4.total * 96);
-    { ProfScope ps(c.prof, c.st, "fpn_concat");
-      nn::fpn_concat(c.st, p[3], p[2], p[1], p[0], L32.d, L16.d, L8.d, L4.d, L4.n(), L4.maxPix, 24, fuse, p_scale); }
-    ProfScope ps(c.prof, c.st, "conv3x3", shape_str(L4.total, 9 * 96, 24, 1));
-    nn::conv_sp(c.st, 3, 3, fuse, 96, L4.d, L4.n(), L4.maxH, L4.maxW, 96, head_conv1_.w, 24, head_conv1_.Npad, h1, 24,
-                make_epi(head_conv1_, ACT_RELU));
   }
   float* map = c.arena->alloc<float>((size_t)L0.total);
   { ProfScope ps(c.prof, c.st, "db_head_tail");

@@ -28,10 +28,7 @@ void gemm_dma(hipStream_t st, const float* A, int lda, long long M, int K, const
 void gemm_split(hipStream_t st, const float* A, int lda, long long M, int K, const float* Wp, int N, int Npad16, float* C,
                 int ldc, int coff, const Epilogue& epi);
 void gemm_split_forget(const float* Wp);   // drops the cached split planes of a weight pack (before its memory is freed / reused)
-void set_dw_xcd(int v);  // A/B: XCD-aware block order of the depthwise kernel (default on)
-extern int g_dw_wide_slab_min, g_dw_wide3_min, g_dw_wide_lp;
-extern int g_dw_variant;    // kernel micro-benchmark hook of dwconv (g_gemm_variant: gemm_plan.h)
-extern int g_dw_sweep;      // A/B: column-sweep 5x5 depthwise kernel: pixels per thread (0: off)
+extern int g_dw_sweep;      // A/B: column-sweep depthwise kernels on short maps (0: off; rt_debug_set_variants bit 9)
 
 // Dense stride-1 "same" convolution, kernel (KH,KW) in {(3,3),(1,3)}; W packed as
 // [ceil(Cin/KC)][KH*KW][Npad16][KC].
@@ -69,7 +66,6 @@ void cls_block(hipStream_t st, int k, int sh, bool se, int act, const float* x, 
                const float* Wdw, const float* bdw, const float* w1, const float* b1, const float* w2, const float* b2, int cr, float slope,
                const float* Wlin, const float* blin, bool shortcut, float* y, float* dscr);   // dscr: n_pixels_out x round_up(mid, 16) floats when se
 // Fused thin LCNetV3 block (3x3 depthwise -> 1x1 conv, C_in <= 64, no SE): see k_lc_thin.
-extern int g_lc_thin;
 bool lc_thin_supported(int K, int sh, int sw, int Cp, int C, int Npad16);
 void lc_thin(hipStream_t st, int sh, int sw, const float* x, const ImgGeom* gin, const ImgGeom* gout, int n_img, int maxHo,
              int maxWo, int Cp, int C, const float* Wd, const float* bd, int dw_act, int dw_has_lab, float dw_a, float dw_c,
@@ -119,13 +115,8 @@ void lateral_add(hipStream_t st, const float* x, int Cin, int Cin_p, const float
 // out = a * scale_a[image] + nearest_up2(b)   (in place on a allowed; scale_a [image][Cp] optional)
 void upsample_add(hipStream_t st, const float* a, const float* b, const ImgGeom* ga, const ImgGeom* gb, int n_img,
                   long long max_pix, int Cp, float* out, const float* scale_a = nullptr);
-// fuse = concat(up8(p5), up4(p4), up2(p3), p2) along channels; every input has pitch Cq, output pitch 4*Cq
-void fpn_concat(hipStream_t st, const float* p5, const float* p4, const float* p3, const float* p2, const ImgGeom* g5,
-                const ImgGeom* g4, const ImgGeom* g3, const ImgGeom* g2, int n_img, long long max_pix, int Cq,
-                float* out, const float* const* scales = nullptr);  // scales[4]: per-level [img][Cq] factors (p5..p2) or null
-// The DB head's first 3x3 conv reading concat(up8(p5), up4(p4), up2(p3), p2) (x per-level scales) directly from the four levels
-// (fpn_concat + conv_sp in one kernel; the pair's result to fp32 rounding: the K slabs are the four levels).
-bool conv3_fpn_fused_supported(int Cq, int N);
+// The DB head's first 3x3 conv reading concat(up8(p5), up4(p4), up2(p3), p2) (x per-level scales: scales[4], per-level
+// [img][Cq] factors p5..p2, or null) directly from the four levels: the K slabs are the four levels.  Cq = N = 24.
 void conv3_fpn_fused(hipStream_t st, const float* p5, const float* p4, const float* p3, const float* p2, const ImgGeom* g5,
                      const ImgGeom* g4, const ImgGeom* g3, const ImgGeom* g2, int n_img, int maxH, int maxW, int Cq,
                      const float* const* scales, const float* Wp, int N, int Npad16, float* y, int ldy, const Epilogue& epi);

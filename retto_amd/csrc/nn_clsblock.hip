@@ -314,8 +314,6 @@ void cls_block(hipStream_t st, int k, int sh, bool se, int act, const float* x, 
                const float* Wdw, const float* bdw, const float* w1, const float* b1, const float* w2, const float* b2, int cr, float slope,
                const float* Wlin, const float* blin, bool shortcut, float* y, float* dscr) {
   if (n_img <= 0) return;
-  static const int dbg = getenv("RT_CLS_DBG") ? atoi(getenv("RT_CLS_DBG")) : 0;   // timing experiments only (wrong results)
-  if (dbg & 1) se = false;
   if (se && !dscr) throw RtError(8, "cls_block: a squeeze-excite block needs the scratch tensor");
   ClsBlkArgs a{x, y, gin, gout, Wexp, bexp, Wdw, bdw, w1, b1, w2, b2, Wlin, blin, dscr,
                cin, mid, mid_cp, cout, round_up(mid, 16), round_up(cout, 16), cr, shortcut ? 1 : 0, maxH_in * maxW * 64, slope};
@@ -324,7 +322,6 @@ void cls_block(hipStream_t st, int k, int sh, bool se, int act, const float* x, 
   // crops per CU, so a crop's latency chain, not the CU's wave slots, is what counts); 9 row tiles per wave where needed
   const int shape = nt_out > 40 ? 0 : 1;   // 8 waves x 9 tiles | 8 x 5
   const int nw = 8;
-  if (dbg & 2) a.npad_e = 16;   // one slice only
   const int small = (nw * 16 + 2 * a.npad_e + 128 + (k * k + 1) * 16) * 4;
   const long long padded = (long long)maxH_in * (maxW + 2 * (k / 2)) * 80;
   const long long xs_bytes = (long long)maxH_in * maxW * (cin + 4) * 4;

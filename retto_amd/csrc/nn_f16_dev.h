@@ -59,7 +59,6 @@ struct ConvArgs {
   half_t* y; int ldy, coff;
   int TH, TW, nzb;   // pixel tile, number of channel blocks (fastest block coordinate: neighbours share the input in L2)
   int lp;            // LDS row pitch in halves: min(Cin, 32) rounded up to 16, + 8
-  int xcd;           // 1: logical workgroup ids are remapped so that neighbours (the channel blocks of one pixel tile, adjacent tiles) run on ONE XCD and share its L2
   long long* stamps; // diagnostics (RT_CONV_STAMPS): s_memtime of wave 0 at 5 points of every stage of one workgroup, or null
   Epi16 epi;
 };

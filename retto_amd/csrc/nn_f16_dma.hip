@@ -1,4 +1,4 @@
-// fp16 convolution kernels staged by LDS-DMA (global_load_lds) for gfx950: k_conv16v2 (3x3 / 1x3 / 3x1 layers) and k_gemm16
+// fp16 convolution kernels staged by LDS-DMA (global_load_lds) for gfx950: k_conv16v2 (3x3 / 1x3 / 3x1 layers) and k_gemm16p
 // (1x1 layers over a flat pixel list).  Same fragment maps, K order and epilogue as k_conv16 (nn_f16.hip).
 #include "nn_f16_dev.h"
 
@@ -115,11 +115,8 @@ __global__ __launch_bounds__(64 * NW, 2) void k_conv16v2(const ConvArgs2 c2) {
   constexpr int NTHR = 64 * NW, NTP = 2, BN = 32 * NTN, ROW = KS;  // LDS row = 32 halves (64 bytes), un-padded
   const int TH = a.TH, TW = a.TW;
   // logical block coordinates (bx: tile x channel block, by: image)
-  unsigned bx = blockIdx.x, by = blockIdx.y;
-  if (a.xcd) {
-    const unsigned lin = xcd_remap(blockIdx.y * gridDim.x + blockIdx.x, gridDim.x * gridDim.y);
-    by = lin / gridDim.x; bx = lin - by * gridDim.x;
-  }
+  const unsigned lin = xcd_remap(blockIdx.y * gridDim.x + blockIdx.x, gridDim.x * gridDim.y);
+  const unsigned by = lin / gridDim.x, bx = lin - by * gridDim.x;
   const ImgGeom go = a.gout[by];
   const int tiles_x = (go.W + TW - 1) / TW, tiles_y = (go.H + TH - 1) / TH;
   const int zb = bx % a.nzb, tile = bx / a.nzb;
@@ -392,143 +389,20 @@ static const half_t* zero_page16() {   // per device: DMA source of padding (one
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
-// k_gemm16: a 1x1 convolution over a flat list of M pixels, Y[M][N] = X[M][K] . W^T, as a 256-pixel x (64 * NTN)-channel
+// k_gemm16p: a 1x1 convolution over a flat list of M pixels, Y[M][N] = X[M][K] . W^T, as a 256-pixel x (64 * NTN)-channel
 // tile per workgroup of 8 waves (2 over the channels x 4 over the pixels; a wave owns 32 * NTN channels x 64 pixels).
-// K is walked in stages of 64 channels: both operands of a stage go global -> LDS by DMA into one of two stage buffers
-// ([2 slabs][rows][32 halves], 64-byte rows, XOR-swizzled like k_conv16v2), the next stage is requested right behind the
-// first MFMA group of the current one and has the whole stage (32 MFMAs per wave) to land; one vmcnt(0) + barrier per
-// stage.  The four 16-deep k-steps of a stage are software-pipelined (fragments of step i + 1 requested before the MFMAs
-// of step i).  The packed weights and the DMA zero source pad K to whole stages.
+// Both operands go global -> LDS by DMA (64-byte rows, XOR-swizzled like k_conv16v2); the packed weights and the DMA zero
+// source pad K to whole slabs.
 // ---------------------------------------------------------------------------------------------------------------------
 struct GemmArgs16 {
   ConvArgs a;            // x, ldx, gin/gout (one flat image), Cin = K, w, N, Npad, y, ldy, coff, nzb, epi
   const half_t* zeros;
 };
 
-template <int NTN>
-__global__ __launch_bounds__(512, 1) void k_gemm16(const GemmArgs16 g) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char smemg[];
-  const ConvArgs& a = g.a;
-  constexpr int NTHR = 512, NTP = 2, BN = 64 * NTN, BP = 256, ROW = KS;
-  constexpr int XCH = 2 * BP * 4 / NTHR, WCH = 2 * BN * 4 / NTHR;          // DMA instructions per thread and stage: 4 and NTN
-  constexpr int XHALVES = 2 * BP * ROW, WHALVES = 2 * BN * ROW, STAGE = XHALVES + WHALVES;
-  const ImgGeom gi = a.gin[0], go = a.gout[0];
-  const long long M = go.W;
-  const int zb = blockIdx.x % a.nzb;
-  const long long m0 = (long long)(blockIdx.x / a.nzb) * BP;
-  if (m0 >= M) return;
-  const int nblk = zb * BN;
-  half_t* lds = reinterpret_cast<half_t*>(smemg);
-  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-  const int wn = wid & 1, wp = wid >> 1;
-  const int r = lane & 31, h = lane >> 5;
-  const int aswz = (r >> 2) & 3;
-  const int nb0 = nblk + wn * 32 * NTN;      // first channel of this wave
-
-  f32x16 acc[NTN][NTP];
-#pragma unroll
-  for (int i = 0; i < NTN; i++)
-#pragma unroll
-    for (int j = 0; j < NTP; j++)
-#pragma unroll
-      for (int e = 0; e < 16; e++) acc[i][j][e] = 0.f;
-
-  const int K = a.Cin, nslab = (K + KS - 1) / KS, nst = (nslab + 1) >> 1;
-  // per-thread DMA sources (slot e = tid + 512 i of an operand's stage image: slab e / (rows * 4), row, physical chunk)
-  const half_t* xsrc[XCH]; int xk[XCH];
-#pragma unroll
-  for (int i = 0; i < XCH; i++) {
-    const int e = tid + i * NTHR, slab = e / (BP * 4), rem = e - slab * (BP * 4), row = rem >> 2, cl = (rem & 3) ^ ((row >> 2) & 3);
-    xk[i] = slab * KS + cl * 8;
-    xsrc[i] = (m0 + row < M) ? a.x + (gi.off + m0 + row) * a.ldx + xk[i] : nullptr;
-  }
-  const half_t* wsrc[WCH]; int wslab[WCH];
-#pragma unroll
-  for (int i = 0; i < WCH; i++) {
-    const int e = tid + i * NTHR, slab = e / (BN * 4), rem = e - slab * (BN * 4), row = rem >> 2, cl = (rem & 3) ^ ((row >> 2) & 3);
-    wslab[i] = slab;
-    wsrc[i] = (nblk + row < a.Npad) ? a.w + ((size_t)slab * a.Npad + nblk + row) * KS + cl * 8 : nullptr;
-  }
-  const int wave_slot = wid * 64 * 8;
-  auto dma_stage = [&](int s) {
-    half_t* dst = lds + (size_t)(s & 1) * STAGE + wave_slot;
-    const int k0 = s * 2 * KS;
-#pragma unroll
-    for (int i = 0; i < XCH; i++) {
-      const half_t* src = (xsrc[i] && k0 + xk[i] < K) ? xsrc[i] + k0 : g.zeros;
-      RT_GLDS16(src, dst + (size_t)i * NTHR * 8);
-    }
-#pragma unroll
-    for (int i = 0; i < WCH; i++) {
-      const half_t* src = (wsrc[i] && s * 2 + wslab[i] < nslab) ? wsrc[i] + (size_t)s * 2 * a.Npad * KS : g.zeros;
-      RT_GLDS16(src, dst + XHALVES + (size_t)i * NTHR * 8);
-    }
-  };
-  dma_stage(0);
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-
-  for (int s = 0; s < nst; s++) {
-    const half_t* xb = lds + (size_t)(s & 1) * STAGE;
-    const half_t* wb = xb + XHALVES;
-    auto frags = [&](int it, h8 (&A)[NTN], h8 (&B)[NTP]) {
-      const int slab = it >> 1, cl = (it & 1) * 2 + h;
-      const int co = (cl ^ aswz) << 3;
-      const half_t* wrow = wb + (size_t)(slab * BN + wn * 32 * NTN + r) * ROW + co;
-      const half_t* xrow = xb + (size_t)(slab * BP + wp * 64 + r) * ROW + co;
-#pragma unroll
-      for (int j = 0; j < NTP; j++) B[j] = *reinterpret_cast<const h8*>(xrow + j * 32 * ROW);
-#pragma unroll
-      for (int i = 0; i < NTN; i++) A[i] = *reinterpret_cast<const h8*>(wrow + i * 32 * ROW);
-    };
-    auto mfmas = [&](const h8 (&A)[NTN], const h8 (&B)[NTP]) {
-#pragma unroll
-      for (int i = 0; i < NTN; i++)
-#pragma unroll
-        for (int j = 0; j < NTP; j++) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(A[i], B[j], acc[i][j], 0, 0, 0);
-    };
-    h8 Af[2][NTN], Bf[2][NTP];
-    frags(0, Af[0], Bf[0]);
-    frags(1, Af[1], Bf[1]);
-    __builtin_amdgcn_sched_barrier(0);
-    mfmas(Af[0], Bf[0]);
-    __builtin_amdgcn_sched_barrier(0);
-    if (s + 1 < nst) dma_stage(s + 1);   // into the buffer every wave finished reading before the last barrier
-    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-    for (int it = 1; it < 4; it++) {
-      if (it + 1 < 4) frags(it + 1, Af[(it + 1) & 1], Bf[(it + 1) & 1]);
-      __builtin_amdgcn_sched_barrier(0);
-      mfmas(Af[it & 1], Bf[it & 1]);
-      __builtin_amdgcn_sched_barrier(0);
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-  }
-  // (the last barrier also says that every wave is done with the stage buffers: they become the transpose scratch)
-  int oys[NTP], oxs[NTP];
-#pragma unroll
-  for (int j = 0; j < NTP; j++) {
-    const long long m = m0 + wp * 64 + j * 32 + r;
-    oys[j] = m < M ? 0 : -1;
-    oxs[j] = (int)m;
-  }
-  store_tile16<NTN, NTP>(a, acc, lds + (size_t)wid * epi_scratch_halves<NTN>(), lane, nb0, oys, oxs, go);
-}
-
-template <int NTN>
-static void launch_gemm16(hipStream_t st, const GemmArgs16& g, long long mtiles) {
-  constexpr size_t lds = (size_t)2 * (2 * 256 * KS + 2 * 64 * NTN * KS) * 2;   // two stage buffers (>= the epilogue scratch)
-  static_assert(lds >= (size_t)8 * (32 * (32 * NTN + 8) + 128) * 2, "epilogue scratch must fit in the stage buffers");
-  allow_big_lds((const void*)k_gemm16<NTN>, 160 * 1024);
-  RT_LAUNCH((k_gemm16<NTN>), dim3((unsigned)(mtiles * g.a.nzb)), dim3(512), lds, st, g);
-}
-
 // ---------------------------------------------------------------------------------------------------------------------
-// k_gemm16p: the same tile as k_gemm16 with the K loop pipelined ACROSS the stage boundaries.  k_gemm16 ends every
-// 64-channel stage with vmcnt(0) + barrier and then starts the next one with exposed fragment reads: the MFMA stream
-// drains once per 32 MFMAs.  Here a stage is one 32-channel slab in a ring of R buffers and the one barrier of a stage
-// sits in its MIDDLE:
+// The K loop is pipelined ACROSS the stage boundaries.  (The first form, k_gemm16, ended every 64-channel stage with
+// vmcnt(0) + barrier and then started the next one with exposed fragment reads: the MFMA stream drained once per 32 MFMAs.)
+// Here a stage is one 32-channel slab in a ring of R buffers and the one barrier of a stage sits in its MIDDLE:
 //     stage s:   reads(s, step 1) | MFMAs(s, step 0) | vmcnt: slab s + 1 landed | BARRIER | request slab s + R - 1 |
 //                reads(s + 1, step 0) | MFMAs(s, step 1)
 //   * after the barrier every wave's part of slab s + 1 is visible, so its first fragments are read before the stage ends
@@ -546,7 +420,7 @@ __global__ __launch_bounds__(512, 1) void k_gemm16p(const GemmArgs16 g) {
   constexpr unsigned STAGE_B = STAGE * 2;
   const ImgGeom gi = a.gin[0], go = a.gout[0];
   const long long M = go.W;
-  const unsigned bx = a.xcd ? xcd_remap(blockIdx.x, gridDim.x) : blockIdx.x;
+  const unsigned bx = xcd_remap(blockIdx.x, gridDim.x);
   const int zb = bx % a.nzb;
   const long long m0 = (long long)(bx / a.nzb) * BP;
   if (m0 >= M) return;
@@ -708,7 +582,7 @@ static void launch_gemm16p(hipStream_t st, const GemmArgs16& g, long long mtiles
 
 bool conv16_dma(hipStream_t st, const ConvArgs& a0, int n_img, int maxHo, int maxWo) {
   const int KH = a0.KH, KW = a0.KW, SH = a0.SH, SW = a0.SW, Npad = a0.Npad, Cin = a0.Cin;
-  // ---- 1x1 over one flat image: k_gemm16 when the channel blocks of 256 / 128 waste little ----
+  // ---- 1x1 over one flat image: k_gemm16p when the channel blocks of 256 / 128 waste little ----
   if (KH == 1 && KW == 1 && SH == 1 && SW == 1 && a0.PT == 0 && a0.PL == 0 && n_img == 1 && maxHo == 1 && Cin >= 64 && maxWo >= 4096 && !a0.epi.dot_w) {
     // channel block of 64 * NTN with the least padded work; taken when at most 10 % of the block columns are padding
     // (N = 480 -> 2 x 256, 240 -> 256, 384 -> 2 x 192; 96 or 160 stay with k_conv16's 96 / 160-wide blocks)
@@ -723,15 +597,8 @@ bool conv16_dma(hipStream_t st, const ConvArgs& a0, int n_img, int maxHo, int ma
       g.a = a0; g.a.nzb = (Npad + bn - 1) / bn; g.zeros = zero_page16();
       const long long mtiles = ((long long)maxWo + 255) / 256;
       if (mtiles * g.a.nzb < (1ll << 31)) {
-        static const int pipe = getenv("RT_GEMM16_PIPE") ? atoi(getenv("RT_GEMM16_PIPE")) : 4;   // 0: k_gemm16 (64-deep stages, 256 / 128 only); 4 / 5: k_gemm16p ring depth
-        if (pipe == 0 && (bn == 256 || bn == 128)) { if (bn == 256) launch_gemm16<4>(st, g, mtiles); else launch_gemm16<2>(st, g, mtiles); }
-        else if (pipe == 5) {
-          switch (bn / 64) { case 4: launch_gemm16p<4, 5>(st, g, mtiles); break; case 3: launch_gemm16p<3, 5>(st, g, mtiles); break;
-                             case 2: launch_gemm16p<2, 5>(st, g, mtiles); break; default: launch_gemm16p<1, 5>(st, g, mtiles); break; }
-        } else {
-          switch (bn / 64) { case 4: launch_gemm16p<4, 4>(st, g, mtiles); break; case 3: launch_gemm16p<3, 4>(st, g, mtiles); break;
-                             case 2: launch_gemm16p<2, 4>(st, g, mtiles); break; default: launch_gemm16p<1, 4>(st, g, mtiles); break; }
-        }
+        switch (bn / 64) { case 4: launch_gemm16p<4, 4>(st, g, mtiles); break; case 3: launch_gemm16p<3, 4>(st, g, mtiles); break;
+                           case 2: launch_gemm16p<2, 4>(st, g, mtiles); break; default: launch_gemm16p<1, 4>(st, g, mtiles); break; }
         return true;
       }
     }
@@ -753,13 +620,11 @@ bool conv16_dma(hipStream_t st, const ConvArgs& a0, int n_img, int maxHo, int ma
   // recognition maps 615216 x 1728 x 192: 6.29 -> 5.46, 1230432 x 1440 x 160: 4.92 -> 4.26, 1x3 neck convs 0.61 -> 0.35; the
   // 480^2 det maps 1.35 -> 1.22; the 240^2 / 120^2 maps 3.43 -> 3.42 / 1.44 -> 1.34 (with the tile-shape search below; 1.53
   // without); only the 9x9 rows lose (4.28 -> 5.17: their 37-KB weight rows leave a 4-wave workgroup one buffer) and stay on
-  // 8 waves.  RT_CONV16_NW=8 / 4 forces one form (A/B runs).
-  static const int nw_env = getenv("RT_CONV16_NW") ? atoi(getenv("RT_CONV16_NW")) : 0;
-  static const int group3 = getenv("RT_CONV3_GROUP") ? atoi(getenv("RT_CONV3_GROUP")) : 1;
-  int nw = nw_env == 4 ? 4 : (nw_env == 8 ? 8 : (k9 ? 8 : 4));
+  // 8 waves.
+  int nw = k9 ? 8 : 4;
   // (4 waves: the nine-tap form also where the 128-channel blocks of the row-wise form would be partly empty -- N = 224:
   //  2.36 -> 2.08 ms per step for the five 307608 x 2016 x 224 layers)
-  const bool g3 = KH == 3 && KW == 3 && Npad >= 64 && (group3 == 2 || (group3 == 1 && (bn2 < 128 || (nw == 4 && Npad % 128 != 0))));
+  const bool g3 = KH == 3 && KW == 3 && Npad >= 64 && (bn2 < 128 || (nw == 4 && Npad % 128 != 0));
   if (g3) bn2 = 64;
   const int taps = g3 ? 9 : (k22 ? 4 : KW);
   auto hpix = [&](int t_h, int t_w) { return ((t_h - 1) * SH + KH) * ((t_w - 1) * SW + KW); };
@@ -773,11 +638,10 @@ bool conv16_dma(hipStream_t st, const ConvArgs& a0, int n_img, int maxHo, int ma
     // full-height tiles on short maps; on taller ones the tile shape that wastes the fewest of the workgroup's pixel slots on
     // the largest image (a 120 x 120 map under 15 x 17 tiles pays for 136 columns; 12 x 20 tiles fill 94 % of their slots),
     // ties (within 3 %) going to the shape with the smaller halo; the halo tile must fit V2_HMAX DMA instructions per thread
-    static const int tile_search = getenv("RT_CONV16_TILES") ? atoi(getenv("RT_CONV16_TILES")) : 1;
     int th, tw;
     if (maxHo >= 16) { const int ny = (maxHo + 15) / 16; th = maxHo >= 64 ? 16 : (maxHo + ny - 1) / ny; } else th = std::max(maxHo, 1);
     tw = std::max(1, std::min(px / th, maxWo));
-    if (tile_search && nw == 4 && maxHo >= 16) {   // (8 waves: the 16 x 32 tiles the kernel was tuned with measured better)
+    if (nw == 4 && maxHo >= 16) {   // (8 waves: the 16 x 32 tiles the kernel was tuned with measured better)
       double best_eff = 0, best_halo = 1e30;
       int bh = th, bw = tw;
       for (int h = 8; h <= std::min(32, maxHo); h++) {

@@ -73,9 +73,7 @@ struct GemmPArgs {
   // a_tab holds 3 ints per row block: {image of the block's first row, first row of the next image, of the one after}
   // (INT_MAX when there is none); every image has >= 128 rows, so a 256-row block touches at most 3.
   const float* a_scale; const int* a_tab; int ld_scale, n_img;
-  unsigned* sched;     // tile counters ([16 q]: queue q, tiles handed out beyond the workgroups' first ones) and [128] workgroups done; zero between launches
-  int xcdq;            // 1: one tile queue per XCD (workgroup b is on XCD b % 8 and takes the row blocks rb % 8 == b % 8, both column
-                       // tiles of a row block consecutively: they meet in that XCD's L2); 0: one queue, tile ids in launch order
+  unsigned* sched;     // tile counters: [0] tiles handed out beyond the workgroups' first ones, [128] workgroups done; zero between launches
   Epilogue epi;
 };
 
@@ -88,8 +86,7 @@ constexpr size_t P_LDS = 2 * (size_t)P_STAGE + P_BIAS_MAX * 4 + 16;   // slabs |
 constexpr size_t P_LDS_ASC = P_LDS + 2 * 3 * P_SCK * 4;               // ... | scale tables
 
 // ACT / LAB: compile-time epilogue (-1 = decided per element); HALF: K = 32 j + 16, the last slab holds one group
-// DBG (timing experiments, wrong results): 1 no stores, 2 no requests after the first two, 4 no epilogue math, 8 stamps
-template <int ACT, int LAB, bool HALF, int DBG = 0, bool ASC = false>
+template <int ACT, int LAB, bool HALF, bool ASC = false>
 __global__ __launch_bounds__(P_NTHR, 1) void k_gemm32p(const GemmPArgs g) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem32p[];
   constexpr int MT = P_MT, NT = P_NT, WN = P_WN;
@@ -101,8 +98,6 @@ __global__ __launch_bounds__(P_NTHR, 1) void k_gemm32p(const GemmPArgs g) {
   float* bias_l = reinterpret_cast<float*>(smem32p + 2 * P_STAGE);
   const int nkc = (g.K + KC - 1) / KC;
   const int G = gridDim.x;
-  unsigned long long ck_t0 = 0, ck_r0 = 0;
-  if (DBG & 16) { ck_t0 = __builtin_amdgcn_s_memtime(); ck_r0 = __builtin_amdgcn_s_memrealtime(); }
 
   // bias -> LDS once (the epilogue must not issue loads of its own: the vmcnt bookkeeping below counts its stores)
   for (int i = tid; i < P_BIAS_MAX; i += P_NTHR) bias_l[i] = (g.epi.bias && i < g.Npad) ? g.epi.bias[i] : 0.f;
@@ -121,19 +116,7 @@ __global__ __launch_bounds__(P_NTHR, 1) void k_gemm32p(const GemmPArgs g) {
   // hand-over barrier; the request side needs it 2 slabs before tile j + 1 ends, the MFMA side when tile j + 1 ends.
   const int n_tiles = g.n_rb * g.n_cb;
   volatile int* tileq = reinterpret_cast<volatile int*>(smem32p + 2 * P_STAGE + P_BIAS_MAX * 4);   // ids of the tiles j, j + 1, .. (slot j & 3)
-  // (round 4) per-XCD queues: PMC showed the N = 480 layers fetching 1.93x their input -- the two 240-column tiles of a row
-  // block went to workgroups on different XCDs, each L2 read the 256 x K pixel block from the fabric.  Queue q holds the row
-  // blocks rb = 8 i + q with their column tiles in order; local index t -> tile (8 (t / n_cb) + q) * n_cb + t % n_cb.
-  const int xq = g.xcdq ? (int)(blockIdx.x & 7) : 0;
-  const int q_wgs = g.xcdq ? (G - xq + 7) >> 3 : G;                                   // workgroups of this queue (their first tiles: local 0 .. q_wgs - 1)
-  const int q_tiles = g.xcdq ? ((g.n_rb - xq + 7) >> 3) * g.n_cb : n_tiles;           // tiles of this queue
-  auto tile_of = [&](int t) __attribute__((always_inline)) {
-    if (!g.xcdq) return t;
-    if (t >= q_tiles) return n_tiles;   // (dead: past the queue's end)
-    const int i = t / g.n_cb;
-    return (8 * i + xq) * g.n_cb + (t - i * g.n_cb);
-  };
-  const int first_tile = tile_of(g.xcdq ? (int)(blockIdx.x >> 3) : (int)blockIdx.x);
+  const int first_tile = blockIdx.x;
   if (tid == 0) tileq[0] = first_tile;
   int it_tile = first_tile, it_j = 0, it_kc = 0;
   int it_rb = it_tile / g.n_cb, it_cb = it_tile - it_rb * g.n_cb;
@@ -143,7 +126,6 @@ __global__ __launch_bounds__(P_NTHR, 1) void k_gemm32p(const GemmPArgs g) {
   int pub_slot = 0;
   const bool p2_is_a = wid + 2 * P_NW < P_AJ;
   const unsigned pitch = (unsigned)(g.lda * 4);
-  int dbg_issued = 0;
 #if RT_G32P_BUF
   // per-lane request offsets: lane i of a wave's piece addresses row 8 wid + i / 8 of the piece group, physical chunk i % 8
   constexpr bool REQ_HELD = ASC;
@@ -156,8 +138,7 @@ __global__ __launch_bounds__(P_NTHR, 1) void k_gemm32p(const GemmPArgs g) {
   }
 #endif
   auto dma_issue = [&]() __attribute__((always_inline)) {
-    if (it_live && !((DBG & 2) && dbg_issued >= 2)) {
-      dbg_issued++;
+    if (it_live) {
       const long long m0 = (long long)it_rb * P_BM;
       const unsigned dst = lds_b + it_buf * P_STAGE + (unsigned)wid * 1024;
 #if RT_G32P_BUF
@@ -275,11 +256,6 @@ __global__ __launch_bounds__(P_NTHR, 1) void k_gemm32p(const GemmPArgs g) {
   __builtin_amdgcn_sched_barrier(0);
   bool after_epi = false;   // the next slab wait follows an epilogue whose stores may stay in flight
 
-  // DBG & 8: s_memtime stamps of one wave (diagnostic instantiation only; sums over the kernel go to g.epi.am_max)
-  constexpr bool ST = (DBG & 8) != 0;
-  const bool st_on = ST && blockIdx.x == 7 && wid == (int)g.epi.am_tiles;
-  unsigned long long st_t[8] = {0, 0, 0, 0, 0, 0, 0, 0}, st_sum[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-#define RT_ST(i) do { if (ST) { if (st_on) st_t[i] = __builtin_amdgcn_s_memtime(); __builtin_amdgcn_sched_barrier(0); } } while (0)
   // The slab hand-over (before the last two weight fragments of a slab are multiplied): this wave has all its fragments
   // of the current slab in registers and its part of the next slab has landed; after the barrier that holds for every
   // wave, so the current buffer goes to the slab after the next one and the next slab's first fragments can be read.
@@ -289,27 +265,14 @@ __global__ __launch_bounds__(P_NTHR, 1) void k_gemm32p(const GemmPArgs g) {
   // here 2.55 M, at the start of the next slab 2.58 M -- the placement is not what the requests cost.
   // fetched / pub: wave 0, lane 0 holds the counter value an atomic issued at the start of this slab returns (tile id - G)
   auto handover = [&](unsigned fetched, bool pub) __attribute__((always_inline)) {
-    RT_ST(1);
     if (after_epi) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(P_NSTORE) : "memory");
     else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     after_epi = false;
     if (pub) {   // (the atomic was issued eight steps ago: the wait above covered it)
-      if (wid == 0 && lane_id() == 0) tileq[pub_slot] = tile_of(q_wgs + (int)fetched);
+      if (wid == 0 && lane_id() == 0) tileq[pub_slot] = G + (int)fetched;
     }
-    RT_ST(2);
     __builtin_amdgcn_s_barrier();
     __builtin_amdgcn_sched_barrier(0);
-    RT_ST(3);
-  };
-  auto st_slab_end = [&]() __attribute__((always_inline)) {
-    if (ST) {
-      if (st_on) {
-        st_t[5] = __builtin_amdgcn_s_memtime();
-        for (int i = 0; i < 5; i++) st_sum[i] += st_t[i + 1] - st_t[i];
-        st_sum[7] += 1;
-      }
-      __builtin_amdgcn_sched_barrier(0);
-    }
   };
 
   // ---- epilogue of the PREVIOUS tile, one 16-channel column tile at a time: bias / activation / LAB, 16-byte stores (a lane
@@ -331,7 +294,7 @@ __global__ __launch_bounds__(P_NTHR, 1) void k_gemm32p(const GemmPArgs g) {
 #pragma unroll
     for (int mt = 0; mt < MT; mt++) {
       f32x4 o;
-      if constexpr (ACT == ACT_HSWISH && (LAB == 0 || LAB == 1) && !(DBG & 4)) {
+      if constexpr (ACT == ACT_HSWISH && (LAB == 0 || LAB == 1)) {
         // the same expressions and rounding as epi_val, written on the 4-vector: packed add / mul / fma (2 values per VALU op --
         // an fp32 MFMA loop pays every VALU cycle of its epilogue) and one v_med3 per value for the clamp
         const f32x4 v = acc[mt][nt] + bias;
@@ -343,10 +306,9 @@ __global__ __launch_bounds__(P_NTHR, 1) void k_gemm32p(const GemmPArgs g) {
         if (LAB == 1) { const f32x4 a4 = {g.epi.lab_a, g.epi.lab_a, g.epi.lab_a, g.epi.lab_a}, c4 = {g.epi.lab_c, g.epi.lab_c, g.epi.lab_c, g.epi.lab_c}; o = __builtin_elementwise_fma(o, a4, c4); }
       } else {
 #pragma unroll
-        for (int j = 0; j < 4; j++) o[j] = (DBG & 4) ? acc[mt][nt][j] : epi_val<ACT, LAB>(acc[mt][nt][j] + bias[j], g.epi.act, g.epi.has_lab, g.epi.lab_a, g.epi.lab_c);
+        for (int j = 0; j < 4; j++) o[j] = epi_val<ACT, LAB>(acc[mt][nt][j] + bias[j], g.epi.act, g.epi.has_lab, g.epi.lab_a, g.epi.lab_c);
       }
-      if (DBG & 4) { if (o[0] == 123.456f) *reinterpret_cast<f32x4*>(pend_cbase + (lo + mt * mt_step + nt * 64)) = o; }
-      else if (!(DBG & 1) || o[0] == 123.456f) { if (rowb < pend_rows - mt * 16) *reinterpret_cast<f32x4*>(pend_cbase + (lo + mt * mt_step + nt * 64)) = o; }
+      if (rowb < pend_rows - mt * 16) *reinterpret_cast<f32x4*>(pend_cbase + (lo + mt * mt_step + nt * 64)) = o;
       __builtin_amdgcn_sched_barrier(0);   // (one pixel fragment at a time: interleaved, the four fragments' temporaries spill accumulators)
     }
   };
@@ -387,12 +349,11 @@ __global__ __launch_bounds__(P_NTHR, 1) void k_gemm32p(const GemmPArgs g) {
     constexpr bool COPY = decltype(copy)::value, EPI = decltype(epi)::value;
     const unsigned nxt_b = lds_b + ((cur_b - lds_b) ^ P_STAGE);
     const unsigned wa0 = cur_b + wo0, wa1 = wa0 ^ 64u, xa1 = (cur_b + xo0) ^ 64u;
-    RT_ST(0);
     unsigned fetched = 0;   // (live inside this slab only: a spill right behind the asm would store the register before the atomic returns)
     bool pub = false;
     if (!EPI && fetch_now) {
       if (wid == 0 && lane_id() == 0)
-        asm volatile("s_nop 4\n\tglobal_atomic_add %0, %1, %2, %3 sc0" : "=v"(fetched) : "v"((unsigned)(xq * 64)), "v"(1u), "s"(g.sched) : "memory");
+        asm volatile("s_nop 4\n\tglobal_atomic_add %0, %1, %2, %3 sc0" : "=v"(fetched) : "v"(0u), "v"(1u), "s"(g.sched) : "memory");
       fetch_now = false; pub = true;
       __builtin_amdgcn_sched_barrier(0);
     }
@@ -428,17 +389,14 @@ __global__ __launch_bounds__(P_NTHR, 1) void k_gemm32p(const GemmPArgs g) {
     RT_RDA(nxt_b + xo0, A0); RT_RDB(nxt_b + wo0, 0);
     __builtin_amdgcn_sched_barrier(0);
     dma_issue();   // the slab after the next one, into the buffer every wave has just left
-    RT_ST(4);
     RT_RDB(nxt_b + wo0, 1);
     __builtin_amdgcn_sched_barrier(0);
     RT_MF(A1, 4);
-    st_slab_end();
     cur_b = nxt_b;
   };
   auto slab_half = [&](int kc) __attribute__((always_inline)) {   // group 0 only; the next slab's pixel fragments go to A1
     const unsigned nxt_b = lds_b + ((cur_b - lds_b) ^ P_STAGE);
     const unsigned wa0 = cur_b + wo0;
-    RT_ST(0);
     RT_RDB(wa0, 2); lgkm_wait<2>(); scale_a(A0, kc, 0); RT_MF(A0, 0);
     RT_RDB(wa0, 3); lgkm_wait<2>(); RT_MF(A0, 1);
     RT_RDB(wa0, 4); lgkm_wait<2>(); RT_MF(A0, 2);
@@ -448,16 +406,13 @@ __global__ __launch_bounds__(P_NTHR, 1) void k_gemm32p(const GemmPArgs g) {
     RT_RDA(nxt_b + xo0, A1); RT_RDB(nxt_b + wo0, 0);
     __builtin_amdgcn_sched_barrier(0);
     dma_issue();
-    RT_ST(4);
     RT_RDB(nxt_b + wo0, 1);
     __builtin_amdgcn_sched_barrier(0);
     RT_MF(A0, 4);
-    st_slab_end();
     cur_b = nxt_b;
   };
   // the slabs of one tile; FIRST: no tile precedes it (nothing to store yet)
   auto tile = [&](int j, int rb, int cb) __attribute__((always_inline)) {
-    RT_ST(6);
     // The first slab carries the previous tile's 20 stores per wave (steps 0-4); at its hand-over they are the youngest
     // vector-memory operations of the wave, behind the slab request it waits for: exactly they may stay in flight.
     // (The stores of a partial row block may be skipped by whole waves: then nothing is assumed to be in flight.)
@@ -469,7 +424,6 @@ __global__ __launch_bounds__(P_NTHR, 1) void k_gemm32p(const GemmPArgs g) {
       sc_b2 = (int)min((long long)0x7fffffff, max(0ll, (long long)g.a_tab[3 * rb + 2] - m0s));
     }
     slab_full(std::integral_constant<bool, HALF>{}, std::true_type{}, 0);
-    if (ST) { if (st_on) { st_sum[5] += st_t[1] - st_t[6]; st_sum[6] += 1; } __builtin_amdgcn_sched_barrier(0); }
     // The id of tile j + 1 of this workgroup: one returning atomic of wave 0, issued at the start of the tile's second slab
     // and published at that slab's hand-over, whose vmcnt(0) covers its return.  (Inline asm: through the builtin hipcc waits
     // vmcnt(0) right behind the atomic, i.e. for the slab requests just issued; and not in the first slab, where the
@@ -506,20 +460,10 @@ __global__ __launch_bounds__(P_NTHR, 1) void k_gemm32p(const GemmPArgs g) {
   if (tid == 0) {
     const unsigned done = __hip_atomic_fetch_add(g.sched + 128, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     if (done == (unsigned)G - 1) {
-      for (int qq = 0; qq < 8; qq++) __hip_atomic_store(g.sched + 16 * qq, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      __hip_atomic_store(g.sched, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       __hip_atomic_store(g.sched + 128, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
   }
-  if ((DBG & 16) && wid == 0 && lane == 0) {
-    unsigned long long* o = reinterpret_cast<unsigned long long*>(g.epi.am_max);
-    if (blockIdx.x == 7) { o[0] = __builtin_amdgcn_s_memtime() - ck_t0; o[1] = __builtin_amdgcn_s_memrealtime() - ck_r0; }
-    o[8 + 2 * blockIdx.x] = ck_r0; o[9 + 2 * blockIdx.x] = __builtin_amdgcn_s_memrealtime();   // per block: [start, end] in 10 ns ticks
-  }
-  if (ST && st_on && lane == 0) {
-    unsigned long long* o = reinterpret_cast<unsigned long long*>(g.epi.am_max);
-    for (int i = 0; i < 8; i++) o[i] = st_sum[i];
-  }
-#undef RT_ST
 #undef RT_RDA
 #undef RT_RDB
 #undef RT_MF
@@ -670,51 +614,12 @@ void gemm_dma(hipStream_t st, const float* A, int lda, long long M, int K, const
   g.n_rb = (int)((M + P_BM - 1) / P_BM); g.n_cb = N / P_BN; g.epi = epi;
   g.a_scale = epi.a_scale; g.a_tab = epi.a_tab; g.ld_scale = epi.ld_scale; g.n_img = epi.n_img;
   const int grid = std::min(g.n_rb * g.n_cb, stream_cus(st));   // (one workgroup per CU of the stream's CU partition)
-  // per-XCD tile queues (RT_G32P_XCDQ=0: one queue): needs every workgroup's first tile to exist in its queue
-  // Measured (round 4, same box, alternating runs): bit-identical results; in isolation 1.5 % SLOWER (615216 x 480 x 480: 2.311 vs
-  // 2.274 ms -- eight queues of 32 workgroups balance worse than one queue of 256), production step 27.90 / 27.91 / 28.41 / 27.90
-  // vs 27.99 / 28.53 / 28.69 / 28.15 ms (inside the noise): opt-in.
-  static const int xcdq_env = getenv("RT_G32P_XCDQ") ? atoi(getenv("RT_G32P_XCDQ")) : 0;
-  g.xcdq = (xcdq_env && g.n_rb >= 64 && grid % 8 == 0) ? 1 : 0;
   const bool half = K % KC != 0;   // (supported K are whole 16-deep groups)
 #define RT_G32P(ACTV, LABV) do { if (half) { allow_big_lds((const void*)k_gemm32p<ACTV, LABV, true>, 160 * 1024); RT_LAUNCH((k_gemm32p<ACTV, LABV, true>), dim3((unsigned)grid), dim3(P_NTHR), P_LDS, st, g); } \
                                  else { allow_big_lds((const void*)k_gemm32p<ACTV, LABV, false>, 160 * 1024); RT_LAUNCH((k_gemm32p<ACTV, LABV, false>), dim3((unsigned)grid), dim3(P_NTHR), P_LDS, st, g); } } while (0)
-  static const int dbg = getenv("RT_G32P_DBG") ? atoi(getenv("RT_G32P_DBG")) : 0;   // timing experiments only (wrong results)
-  if (dbg) {
-    static unsigned long long* dst = nullptr;
-    if (!dst) RT_HIP_CHECK(hipMalloc((void**)&dst, 64 + 16 * 1024));
-    RT_HIP_CHECK(hipMemsetAsync(dst, 0, 64 + 16 * 1024, st));
-    g.epi.am_max = reinterpret_cast<float*>(dst);
-    g.epi.am_tiles = getenv("RT_G32P_WAVE") ? atoi(getenv("RT_G32P_WAVE")) : 0;
-#define RT_DBG_LAUNCH(D) case D: allow_big_lds((const void*)k_gemm32p<ACT_HSWISH, 1, true, D>, 160 * 1024); \
-                                 RT_LAUNCH((k_gemm32p<ACT_HSWISH, 1, true, D>), dim3((unsigned)grid), dim3(P_NTHR), P_LDS, st, g); break;
-    switch (dbg) {
-      RT_DBG_LAUNCH(1) RT_DBG_LAUNCH(2) RT_DBG_LAUNCH(4) RT_DBG_LAUNCH(6) RT_DBG_LAUNCH(8)
-      RT_DBG_LAUNCH(16) RT_DBG_LAUNCH(17) RT_DBG_LAUNCH(18) RT_DBG_LAUNCH(20) RT_DBG_LAUNCH(22) RT_DBG_LAUNCH(23)
-      default: throw RtError(8, "gemm_dma: unknown RT_G32P_DBG");
-    }
-#undef RT_DBG_LAUNCH
-    unsigned long long h[8 + 2048];
-    RT_HIP_CHECK(hipMemcpyAsync(h, dst, sizeof(h), hipMemcpyDeviceToHost, st));
-    RT_HIP_CHECK(hipStreamSynchronize(st));
-    if (dbg & 16) {
-      unsigned long long t0 = ~0ull, t1 = 0;
-      for (int b = 0; b < grid; b++) { t0 = std::min(t0, h[8 + 2 * b]); t1 = std::max(t1, h[9 + 2 * b]); }
-      std::string line = "g32p blocks (start / end in us after the first start, by block): ";
-      char buf[64];
-      for (int b = 0; b < grid; b += std::max(1, grid / 32)) { snprintf(buf, sizeof buf, "%d:%.0f/%.0f ", b, (h[8 + 2 * b] - t0) / 100.0, (h[9 + 2 * b] - t0) / 100.0); line += buf; }
-      double s_end = 0, mx = 0, mn = 1e30;
-      for (int b = 0; b < grid; b++) { const double e = (h[9 + 2 * b] - t0) / 100.0; s_end += e; mx = std::max(mx, e); mn = std::min(mn, e); }
-      fprintf(stderr, "%s\n  span %.1f us; block end times min %.1f mean %.1f max %.1f us\n", line.c_str(), (t1 - t0) / 100.0, mn, s_end / grid, mx);
-    }
-    if ((dbg & 16) && h[1]) fprintf(stderr, "g32p clock: %llu shader cycles in %.1f us = %.3f GHz\n", h[0], h[1] / 100.0, h[0] / (h[1] * 10.0));
-    if ((dbg & 8) && h[7]) fprintf(stderr, "g32p stamps (wave %d of block 7): %llu slabs, per slab: steps0-7 %llu | lgkm+vmcnt wait %llu | barrier %llu | step 8 + dma issue %llu | step 9 %llu ; %llu first slabs with epilogue chunks: steps 0-7 %llu cycles\n",
-                                   g.epi.am_tiles, h[7], h[0] / h[7], h[1] / h[7], h[2] / h[7], h[3] / h[7], h[4] / h[7], h[6], h[6] ? h[5] / h[6] : 0);
-    return;
-  }
   if (epi.a_scale) {
-#define RT_G32P_SE(LABV) do { if (half) { allow_big_lds((const void*)k_gemm32p<ACT_HSWISH, LABV, true, 0, true>, 160 * 1024); RT_LAUNCH((k_gemm32p<ACT_HSWISH, LABV, true, 0, true>), dim3((unsigned)grid), dim3(P_NTHR), P_LDS_ASC, st, g); } \
-                              else { allow_big_lds((const void*)k_gemm32p<ACT_HSWISH, LABV, false, 0, true>, 160 * 1024); RT_LAUNCH((k_gemm32p<ACT_HSWISH, LABV, false, 0, true>), dim3((unsigned)grid), dim3(P_NTHR), P_LDS_ASC, st, g); } } while (0)
+#define RT_G32P_SE(LABV) do { if (half) { allow_big_lds((const void*)k_gemm32p<ACT_HSWISH, LABV, true, true>, 160 * 1024); RT_LAUNCH((k_gemm32p<ACT_HSWISH, LABV, true, true>), dim3((unsigned)grid), dim3(P_NTHR), P_LDS_ASC, st, g); } \
+                              else { allow_big_lds((const void*)k_gemm32p<ACT_HSWISH, LABV, false, true>, 160 * 1024); RT_LAUNCH((k_gemm32p<ACT_HSWISH, LABV, false, true>), dim3((unsigned)grid), dim3(P_NTHR), P_LDS_ASC, st, g); } } while (0)
     if (epi.has_lab) RT_G32P_SE(1); else RT_G32P_SE(0);
 #undef RT_G32P_SE
     return;

@@ -99,9 +99,7 @@ __device__ __forceinline__ void split8(const f32x4 x0, const f32x4 x1, u32x4& h,
   split_pair(x1[2], x1[3], hh[3], mm[3], ll[3]);
   h = u32x4{hh[0], hh[1], hh[2], hh[3]}; m = u32x4{mm[0], mm[1], mm[2], mm[3]}; l = u32x4{ll[0], ll[1], ll[2], ll[3]};
 }
-template <bool OFF = false>
 __device__ __forceinline__ f32x4 mfma_bf16(const u32x4 w, const u32x4 a, const f32x4 c) {
-  if (OFF) { f32x4 d = c; d[0] += __uint_as_float(w[0] ^ a[0]); return d; }
   return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, w), __builtin_bit_cast(bf16x8, a), c, 0, 0, 0);
 }
 
@@ -124,7 +122,6 @@ struct GemmSArgs {
   long long M;
   int lda, nslab, N, ldc, coff;
   int n_rb, n_cb;
-  int dyn;           // 1: tile ids from the queue; 2 (debugging): the queue runs, the ids stay static
   // ASC (squeeze-excite scale folded into the pixel operand): row m of image i is multiplied by a_scale[i * ld_scale + k] before
   // it is split.  a_tab: per 256-row block {image of its first row, first row of the next image, of the one after} (stride 3,
   // what k_gemm32p+se reads) or per 128-row block {image, first row of the next image} (stride 2); every image has >= 128 rows.
@@ -159,9 +156,7 @@ __global__ void k_split_pack(const float* __restrict__ Wp, int nslab, int Npad, 
   }
 }
 
-// DBG (timing experiments, wrong results): 1 no stores, 2 no pixel requests after the prologue, 4 no weight requests after it,
-// 8 no split arithmetic, 16 no MFMAs
-template <int ACT, int LAB, int DBG = 0, bool ASC = false>
+template <int ACT, int LAB, bool ASC = false>
 __global__ __launch_bounds__(S_NTHR, 2) void k_gemm_split(const GemmSArgs g) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_s[];
   const int tid = threadIdx.x, lane = tid & 63;
@@ -210,7 +205,6 @@ __global__ __launch_bounds__(S_NTHR, 2) void k_gemm_split(const GemmSArgs g) {
   //  all read the same 128 bytes of their 1-KB rows at the same time -- requests only, no MFMAs: 0.489 vs 0.501 ms, whole kernel
   //  0.966 vs 0.979: not channel camping)
   int aq_p = 0, wq_p = 0, wq_g = 0;   // slab of the next pixel / weight request, weight group within it
-  bool dbg_pro = true;   // (DBG: requests of the prologue are always issued)
   auto a_desc = [&](int t) __attribute__((always_inline)) {
     const bool live = t < n_tiles;
     const int rb = live ? t / g.n_cb : 0;
@@ -264,7 +258,7 @@ __global__ __launch_bounds__(S_NTHR, 2) void k_gemm_split(const GemmSArgs g) {
   const unsigned pitch8 = 8u * pitch;
   auto a_piece = [&](auto ktag) __attribute__((always_inline)) {
     constexpr int k = decltype(ktag)::value;
-    if (!(DBG & 2) || dbg_pro) { blds16(((k & 1) ? rq_a1 : rq_a0) + (unsigned)k * pitch8, ars, aq_dst + k * 1024u, aq_so); vm_note(1); }
+    { blds16(((k & 1) ? rq_a1 : rq_a0) + (unsigned)k * pitch8, ars, aq_dst + k * 1024u, aq_so); vm_note(1); }
     if (ASC && k == 0) {
       sc_bnd[aq_slot] = sc_bnd_t;
       {   // lane i: image sc_img + i / 32 (clamped), channel 32 slab + i % 32 (beyond K: out of range, zero).
@@ -283,7 +277,7 @@ __global__ __launch_bounds__(S_NTHR, 2) void k_gemm_split(const GemmSArgs g) {
     if (k == 3) {
       aq_slot ^= 1;
       aq_p = aq_p + 1 == nslab ? 0 : aq_p + 1;
-      if (++aq_s == nslab) { aq_s = 0; aq_j++; { const int q_ = (g.dyn & 8) ? tq_read(aq_j) : 0; aq_t = (g.dyn & 1) ? q_ : aq_t + G; } ars = a_desc(aq_t); aq_p = 0; if (ASC) tile_images(aq_t, &sc_img, &sc_bnd_t); }
+      if (++aq_s == nslab) { aq_s = 0; aq_j++; aq_t = tq_read(aq_j); ars = a_desc(aq_t); aq_p = 0; if (ASC) tile_images(aq_t, &sc_img, &sc_bnd_t); }
       aq_dst = a_dst0 + (unsigned)aq_slot * S_ASLOT; aq_so = (unsigned)aq_p * 128u;
     }
     __builtin_amdgcn_sched_barrier(0);
@@ -291,12 +285,12 @@ __global__ __launch_bounds__(S_NTHR, 2) void k_gemm_split(const GemmSArgs g) {
   // (a group has 15 pieces: wave w takes w, w + 4, w + 8, w + 12 -- wave 3 has three; its bookkeeping still runs at k == 3)
   auto w_piece = [&](auto ktag) __attribute__((always_inline)) {
     constexpr int k = decltype(ktag)::value;
-    if ((!(DBG & 4) || dbg_pro) && (k < 3 || wid < 3)) { blds16(rq_w, wrs, wq_dst + k * 4096u, wq_sow + k * 4096u); vm_note(1); }
+    if (k < 3 || wid < 3) { blds16(rq_w, wrs, wq_dst + k * 4096u, wq_sow + k * 4096u); vm_note(1); }
     if (k == 3) {
       vs_later = vc_ops;
       wq_buf = wq_buf == 2 ? 0 : wq_buf + 1;
       if (++wq_g == 3) { wq_g = 0; wq_p = wq_p + 1 == nslab ? 0 : wq_p + 1; }
-      if (++wq_h == 3 * nslab) { wq_h = 0; wq_j++; { const int q_ = (g.dyn & 8) ? tq_read(wq_j) : 0; wq_t = (g.dyn & 1) ? q_ : wq_t + G; } wrs = w_desc(wq_t); wq_p = 0; wq_g = 0; }
+      if (++wq_h == 3 * nslab) { wq_h = 0; wq_j++; wq_t = tq_read(wq_j); wrs = w_desc(wq_t); wq_p = 0; wq_g = 0; }
       wq_so = (unsigned)wq_p * S_WSLAB + (unsigned)wq_g * S_WGRP;
       wq_sow = wq_so + (unsigned)wid * 1024u; wq_dst = w_dst0 + (unsigned)wq_buf * S_WGRP;
     }
@@ -380,9 +374,7 @@ __global__ __launch_bounds__(S_NTHR, 2) void k_gemm_split(const GemmSArgs g) {
 #pragma unroll
         for (int j = 0; j < 4; j++) o[j] = epi_val<ACT, LAB>(acc[mt][nt][j] + bias[j], g.epi.act, g.epi.has_lab, g.epi.lab_a, g.epi.lab_c);
       }
-      if (DBG & 64) { *reinterpret_cast<f32x4*>(pend_c + ((nt * 2 + mt) * (g.ldc * 4) + ln * 16)) = o; }   // (timing: 1 KB contiguous per instruction)
-      else if (DBG & 128) { constexpr int k_ = nt * 2; *reinterpret_cast<f32x4*>(pend_c + (((ln >> 3) + 8 * ((k_ + mt) & 3)) * (g.ldc * 4) + (ln & 7) * 16 + 128 * ((k_ + mt) >> 2))) = o; }   // (timing: 8 rows x 128 bytes)
-      else if ((DBG & 1) ? o[0] == 123.456f : rr + mt * 16 < pend_rows) *reinterpret_cast<f32x4*>(pend_c + (lo + mt * mt_step)) = o;
+      if (rr + mt * 16 < pend_rows) *reinterpret_cast<f32x4*>(pend_c + (lo + mt * mt_step)) = o;
     }
     if (pend_full) vm_note(2);   // (stores a partial row block may skip are not counted: the waits then wait for more)
   };
@@ -390,31 +382,19 @@ __global__ __launch_bounds__(S_NTHR, 2) void k_gemm_split(const GemmSArgs g) {
   // 12 MFMAs of one weight tile (16 output channels) against the wave's 32 pixels; ZERO: the accumulators start from zero
 #define RT_SMF(SL, nt, ZERO) do { \
     _Pragma("unroll") for (int mt_ = 0; mt_ < 2; mt_++) \
-      acc[mt_][nt] = mfma_bf16<(DBG & 16) != 0>(Bf[SL][2], Ah[mt_], (ZERO) ? f32x4{0.f, 0.f, 0.f, 0.f} : acc[mt_][nt]); \
-    _Pragma("unroll") for (int mt_ = 0; mt_ < 2; mt_++) acc[mt_][nt] = mfma_bf16<(DBG & 16) != 0>(Bf[SL][0], Al[mt_], acc[mt_][nt]); \
-    _Pragma("unroll") for (int mt_ = 0; mt_ < 2; mt_++) acc[mt_][nt] = mfma_bf16<(DBG & 16) != 0>(Bf[SL][1], Am[mt_], acc[mt_][nt]); \
-    _Pragma("unroll") for (int mt_ = 0; mt_ < 2; mt_++) acc[mt_][nt] = mfma_bf16<(DBG & 16) != 0>(Bf[SL][1], Ah[mt_], acc[mt_][nt]); \
-    _Pragma("unroll") for (int mt_ = 0; mt_ < 2; mt_++) acc[mt_][nt] = mfma_bf16<(DBG & 16) != 0>(Bf[SL][0], Am[mt_], acc[mt_][nt]); \
-    _Pragma("unroll") for (int mt_ = 0; mt_ < 2; mt_++) acc[mt_][nt] = mfma_bf16<(DBG & 16) != 0>(Bf[SL][0], Ah[mt_], acc[mt_][nt]); \
+      acc[mt_][nt] = mfma_bf16(Bf[SL][2], Ah[mt_], (ZERO) ? f32x4{0.f, 0.f, 0.f, 0.f} : acc[mt_][nt]); \
+    _Pragma("unroll") for (int mt_ = 0; mt_ < 2; mt_++) acc[mt_][nt] = mfma_bf16(Bf[SL][0], Al[mt_], acc[mt_][nt]); \
+    _Pragma("unroll") for (int mt_ = 0; mt_ < 2; mt_++) acc[mt_][nt] = mfma_bf16(Bf[SL][1], Am[mt_], acc[mt_][nt]); \
+    _Pragma("unroll") for (int mt_ = 0; mt_ < 2; mt_++) acc[mt_][nt] = mfma_bf16(Bf[SL][1], Ah[mt_], acc[mt_][nt]); \
+    _Pragma("unroll") for (int mt_ = 0; mt_ < 2; mt_++) acc[mt_][nt] = mfma_bf16(Bf[SL][0], Am[mt_], acc[mt_][nt]); \
+    _Pragma("unroll") for (int mt_ = 0; mt_ < 2; mt_++) acc[mt_][nt] = mfma_bf16(Bf[SL][0], Ah[mt_], acc[mt_][nt]); \
   } while (0)
 
-  // DBG & 256: in-kernel clock and the cycles one wave spends in the two waits of a slab (diagnostic instantiation only)
-  constexpr bool ST = (DBG & 256) != 0;
-  const bool st_on = ST && blockIdx.x == 7 && wid == (int)g.epi.am_tiles;
-  unsigned long long st_c0 = 0, st_r0 = 0, st_a = 0, st_sum[4] = {0, 0, 0, 0};
-  if (ST) { st_c0 = __builtin_amdgcn_s_memtime(); st_r0 = __builtin_amdgcn_s_memrealtime(); }
-  // DBG & 512: the same wave's time inside a step: fragment request + wait | request pieces | 12 MFMAs (+ woven VALU)
-  constexpr bool ST2 = ST && (DBG & 512) != 0;
-  unsigned long long st2_t = 0, st2_sum[4] = {0, 0, 0, 0};
-#define RT_ST2(i) do { if (ST2) { if (st_on) { const unsigned long long n_ = __builtin_amdgcn_s_memtime(); if (i) st2_sum[i] += n_ - st2_t; st2_t = n_; } __builtin_amdgcn_sched_barrier(0); } } while (0)
-#define RT_STA() do { if (ST) { if (st_on) st_a = __builtin_amdgcn_s_memtime(); __builtin_amdgcn_sched_barrier(0); } } while (0)
-#define RT_STB(i) do { if (ST) { if (st_on) { const unsigned long long n_ = __builtin_amdgcn_s_memtime(); st_sum[i] += n_ - st_a; st_a = n_; } __builtin_amdgcn_sched_barrier(0); } } while (0)
   // ---- prologue ---------------------------------------------------------------------------------------------------------------
   w_issue();
   w_issue();
   a_issue();
   a_issue();
-  dbg_pro = false;
   vs_next = vs_later = vc_ops;
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
@@ -426,8 +406,7 @@ __global__ __launch_bounds__(S_NTHR, 2) void k_gemm_split(const GemmSArgs g) {
       raw[mt][0] *= *reinterpret_cast<const f32x4*>(t);
       raw[mt][1] *= *reinterpret_cast<const f32x4*>(t + 16);
     }
-    if (DBG & 8) { h = __builtin_bit_cast(u32x4, raw[mt][0]); m = __builtin_bit_cast(u32x4, raw[mt][1]); l = h ^ m; }
-    else split8(raw[mt][0], raw[mt][1], h, m, l);
+    split8(raw[mt][0], raw[mt][1], h, m, l);
   };
   read_raw2(0);
   split_into(0, Ah[0], Am[0], Al[0], 0);
@@ -454,29 +433,22 @@ __global__ __launch_bounds__(S_NTHR, 2) void k_gemm_split(const GemmSArgs g) {
     // VALU work that rides along woven in, four instructions behind each MFMA: the epilogue chunk of the NEXT step's tile (whose
     // accumulators this step does not touch) and WORK (the split)
 #define RT_STEP_V(SL, nt, NOFF, REQ, WORK) do { \
-      RT_ST2(0); \
       read_b(IntTag<1 - SL>{}, IntTag<NOFF>{}, wf); \
       lgkm_wait<3>(); \
-      RT_ST2(1); \
       REQ; \
-      RT_ST2(2); \
       RT_SMF(SL, nt, EPI); \
       if (EPI && pend) epi_chunk(IntTag<(nt) + 1>{}); \
       WORK; \
       RT_WEAVE(); \
-      __builtin_amdgcn_sched_barrier(0); \
-      RT_ST2(3); } while (0)
+      __builtin_amdgcn_sched_barrier(0); } while (0)
 #define RT_STEP(SL, nt, NOFF, REQ) RT_STEP_V(SL, nt, NOFF, REQ, (void)0)
     // last step of a group: this tile's fragments are in registers; the next group's weights have landed (this wave's pieces:
     // vm_wait; everybody's: the barrier), its first fragments are requested, then the 12 MFMAs
-#define RT_LAST(SL, nt, REQ, WORK, STI, VME) do { \
-      RT_STA(); \
+#define RT_LAST(SL, nt, REQ, WORK, VME) do { \
       lgkm_wait<0>(); \
       vm_wait(IntTag<VME>{}); \
-      RT_STB(STI); \
       __builtin_amdgcn_s_barrier(); \
       __builtin_amdgcn_sched_barrier(0); \
-      RT_STB(STI + 1); \
       wb = wb == 2 ? 0 : wb + 1; \
       wf = w_fr + (unsigned)wb * S_WGRP; \
       read_b(IntTag<1 - SL>{}, IntTag<0>{}, wf); \
@@ -494,7 +466,7 @@ __global__ __launch_bounds__(S_NTHR, 2) void k_gemm_split(const GemmSArgs g) {
     // behind the write (published at the slab's end, with no barrier in between, the other waves raced it: memory faults that
     // depended on how the session's lanes happened to line up).
     unsigned fetched = 0;
-    if (EPI && (g.dyn & 2)) {
+    if (EPI) {
       if (wid == 0) {
         if (lane_id() == 0) asm volatile("s_nop 4\n\tglobal_atomic_add %0, %1, %2, %3 sc0" : "=v"(fetched) : "v"(0u), "v"(1u), "s"(g.sched) : "memory");
         vm_note(1); vs_at = vc_ops;
@@ -504,18 +476,18 @@ __global__ __launch_bounds__(S_NTHR, 2) void k_gemm_split(const GemmSArgs g) {
     if (EPI && pend) epi_chunk(IntTag<0>{});
     // ---- group 0: tiles 0..4
     RT_STEP(0, 0, 1 * 3072, RT_WA(0)); RT_STEP(1, 1, 2 * 3072, RT_WA(1)); RT_STEP(0, 2, 3 * 3072, RT_WA(2)); RT_STEP(1, 3, 4 * 3072, RT_WA(3));
-    RT_LAST(0, 4, (void)0, (void)0, 0, 8);
+    RT_LAST(0, 4, (void)0, (void)0, 8);
     // ---- group 1: tiles 5..9
     RT_STEP(1, 5, 1 * 3072, w_piece(IntTag<0>{})); RT_STEP(0, 6, 2 * 3072, w_piece(IntTag<1>{})); RT_STEP(1, 7, 3 * 3072, w_piece(IntTag<2>{}));
     RT_STEP(0, 8, 4 * 3072, w_piece(IntTag<3>{}));
-    if (EPI && (g.dyn & 4)) {   // the next tile's id has returned (everything issued since may stay in flight)
+    if (EPI) {   // the next tile's id has returned (everything issued since may stay in flight)
       if (wid == 0) {
         vm_wait_n(vc_ops - vs_at);
         if (lane_id() == 0) tq_write(tile_j + 1, G + (int)fetched);
       }
       __builtin_amdgcn_sched_barrier(0);
     }
-    RT_LAST(1, 9, (void)0, (void)0, 2, 5);
+    RT_LAST(1, 9, (void)0, (void)0, 5);
     // ---- group 2: tiles 10..14.  The next slab's pixels have landed: their request is older than the weights the barrier
     // above waited for (requested in this slab's first steps, behind them).
     read_raw2(a_slot ^ 1);
@@ -523,7 +495,7 @@ __global__ __launch_bounds__(S_NTHR, 2) void k_gemm_split(const GemmSArgs g) {
     RT_STEP_V(0, 10, 1 * 3072, w_piece(IntTag<0>{}), split_into(0, Nh[0], Nm[0], Nl[0], a_slot ^ 1));
     RT_STEP_V(1, 11, 2 * 3072, w_piece(IntTag<1>{}), split_into(1, Nh[1], Nm[1], Nl[1], a_slot ^ 1));
     RT_STEP(0, 12, 3 * 3072, w_piece(IntTag<2>{})); RT_STEP(1, 13, 4 * 3072, w_piece(IntTag<3>{}));
-    RT_LAST(0, 14, (void)0, (void)0, 2, 4);
+    RT_LAST(0, 14, (void)0, (void)0, 4);
 #undef RT_STEP
 #undef RT_STEP_V
 #undef RT_LAST
@@ -541,7 +513,7 @@ __global__ __launch_bounds__(S_NTHR, 2) void k_gemm_split(const GemmSArgs g) {
   for (int t = (int)blockIdx.x; t < n_tiles; ) {
     const int rb = t / g.n_cb, cb = t - rb * g.n_cb;
     const bool pend = pend_c != nullptr;
-    pend_full = pend && pend_rows >= 32 && !(DBG & 1);
+    pend_full = pend && pend_rows >= 32;
     slab(std::true_type{}, pend);
     // (the pending tile's last bias read lies before the last barrier of the slab above; this tile's epilogue -- the next reader --
     //  begins with the next tile's first slab or the tail below, barriers away)
@@ -551,8 +523,7 @@ __global__ __launch_bounds__(S_NTHR, 2) void k_gemm_split(const GemmSArgs g) {
     pend_c = reinterpret_cast<char*>(g.C + m0 * g.ldc + g.coff + cb * S_BN);
     pend_rows = (int)max(0ll, min(32ll, g.M - m0));
     tile_j++;
-    { const int q_ = (g.dyn & 8) ? tq_read(tile_j) : 0;
-      t = (g.dyn & 1) ? q_ : t + G; }   // (published in this tile's first slab, barriers ago)
+    t = tq_read(tile_j);   // (published in this tile's first slab, barriers ago)
   }
   __syncthreads();
   if (pend_c) {
@@ -562,26 +533,13 @@ __global__ __launch_bounds__(S_NTHR, 2) void k_gemm_split(const GemmSArgs g) {
   }
   asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");   // (requests issued for tiles that do not exist write zeros into LDS)
   // the last workgroup to finish leaves the two counters at zero for the next launch on this stream
-  if (tid == 0 && (g.dyn & 16)) {
+  if (tid == 0) {
     const unsigned done = __hip_atomic_fetch_add(g.sched + 1, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     if (done == (unsigned)G - 1) {
       __hip_atomic_store(g.sched, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       __hip_atomic_store(g.sched + 1, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
   }
-  if (ST && wid == 0 && lane == 0) {
-    unsigned long long* o = reinterpret_cast<unsigned long long*>(g.epi.am_max);
-    o[8 + 2 * blockIdx.x] = st_r0; o[9 + 2 * blockIdx.x] = __builtin_amdgcn_s_memrealtime();
-  }
-  if (ST && st_on && lane == 0) {
-    unsigned long long* o = reinterpret_cast<unsigned long long*>(g.epi.am_max);
-    o[0] = __builtin_amdgcn_s_memtime() - st_c0; o[1] = __builtin_amdgcn_s_memrealtime() - st_r0;
-    for (int i = 0; i < 4; i++) o[2 + i] = st_sum[i];
-    for (int i = 0; i < 4; i++) o[1040 + i] = st2_sum[i];
-  }
-#undef RT_STA
-#undef RT_ST2
-#undef RT_STB
 #undef RT_SMF
 }
 
@@ -638,57 +596,13 @@ void gemm_split(hipStream_t st, const float* A, int lda, long long M, int K, con
     unsigned*& c = counters[{dev, st}];
     if (!c) { RT_HIP_CHECK(hipMalloc((void**)&c, 256)); RT_HIP_CHECK(hipMemset(c, 0, 256)); }
     g.sched = c;
-    static const int stat = getenv("RT_GS_STATIC") ? atoi(getenv("RT_GS_STATIC")) : 0;   // A/B: static tile lists
-    g.dyn = stat ? 0 : 31;   // (bits: 1 ids from the queue, 2 atomic, 4 publish, 8 queue reads, 16 end-of-kernel counters)
   }
-  const int grid0 = std::min(g.n_rb * g.n_cb, 2 * stream_cus(st));   // two workgroups per CU
+  const int grid = std::min(g.n_rb * g.n_cb, 2 * stream_cus(st));   // two workgroups per CU
 #define RT_GS(ACTV, LABV) do { allow_big_lds((const void*)k_gemm_split<ACTV, LABV>, 160 * 1024); \
     RT_LAUNCH((k_gemm_split<ACTV, LABV>), dim3((unsigned)grid), dim3(S_NTHR), S_LDS, st, g); } while (0)
-  static const int dbg = getenv("RT_GS_DBG") ? atoi(getenv("RT_GS_DBG")) : 0;   // timing experiments only (wrong results)
-  const int grid_env = getenv("RT_GS_GRID") ? atoi(getenv("RT_GS_GRID")) : 0;   // (experiments: e.g. 256 = one workgroup per CU)
-  const int grid = grid_env > 0 ? std::min(grid0, grid_env) : grid0;
-  if (dbg & 256) {
-    static unsigned long long* dst = nullptr;
-    if (!dst) RT_HIP_CHECK(hipMalloc((void**)&dst, 64 + 16 * 1024));
-    RT_HIP_CHECK(hipMemsetAsync(dst, 0, 64 + 16 * 1024, st));
-    g.epi.am_max = reinterpret_cast<float*>(dst);
-    g.epi.am_tiles = getenv("RT_GS_WAVE") ? atoi(getenv("RT_GS_WAVE")) : 0;
-    if (dbg & 512) { allow_big_lds((const void*)k_gemm_split<ACT_HSWISH, 1, 768>, 160 * 1024);
-      RT_LAUNCH((k_gemm_split<ACT_HSWISH, 1, 768>), dim3((unsigned)grid), dim3(S_NTHR), S_LDS, st, g); }
-    else { allow_big_lds((const void*)k_gemm_split<ACT_HSWISH, 1, 256>, 160 * 1024);
-      RT_LAUNCH((k_gemm_split<ACT_HSWISH, 1, 256>), dim3((unsigned)grid), dim3(S_NTHR), S_LDS, st, g); }
-    unsigned long long h[8 + 2048];
-    RT_HIP_CHECK(hipMemcpyAsync(h, dst, sizeof(h), hipMemcpyDeviceToHost, st));
-    RT_HIP_CHECK(hipStreamSynchronize(st));
-    {
-      int occ = -1;
-      (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, (const void*)k_gemm_split<ACT_HSWISH, 1, 256>, S_NTHR, S_LDS);
-      unsigned long long t0 = ~0ull, t1 = 0;
-      for (int b = 0; b < grid && b < 1024; b++) { t0 = std::min(t0, h[8 + 2 * b]); t1 = std::max(t1, h[9 + 2 * b]); }
-      int late_start = 0; double s_end = 0, mn = 1e30, mx = 0;
-      for (int b = 0; b < grid && b < 1024; b++) {
-        if ((h[8 + 2 * b] - t0) > 5000) late_start++;
-        const double e = (h[9 + 2 * b] - t0) / 100.0; s_end += e; mn = std::min(mn, e); mx = std::max(mx, e);
-      }
-      fprintf(stderr, "gsplit blocks: occupancy API %d per CU; grid %d; span %.1f us; %d blocks started > 50 us after the first; block end min %.1f mean %.1f max %.1f us\n",
-              occ, grid, (t1 - t0) / 100.0, late_start, mn, s_end / std::min(grid, 1024), mx);
-    }
-    if (dbg & 512) fprintf(stderr, "gsplit step stamps: fragment request + wait %llu | request pieces %llu | MFMAs + woven work %llu cycles per launch\n", h[1041], h[1042], h[1043]);
-    if (h[1]) fprintf(stderr, "gsplit wave %d of block 7: %llu cycles in %.1f us = %.3f GHz; per launch: mid wait %llu + barrier %llu, end wait %llu + barrier %llu cycles (%d slabs per tile)\n",
-                      g.epi.am_tiles, h[0], h[1] / 100.0, h[0] / (h[1] * 10.0), h[2], h[3], h[4], h[5], g.nslab);
-    return;
-  }
-  if (dbg) {
-#define RT_GSD(D) case D: allow_big_lds((const void*)k_gemm_split<ACT_HSWISH, 1, D>, 160 * 1024); \
-    RT_LAUNCH((k_gemm_split<ACT_HSWISH, 1, D>), dim3((unsigned)grid), dim3(S_NTHR), S_LDS, st, g); break;
-    switch (dbg) { RT_GSD(1) RT_GSD(2) RT_GSD(4) RT_GSD(6) RT_GSD(8) RT_GSD(7) RT_GSD(24) RT_GSD(25) RT_GSD(26) RT_GSD(28) RT_GSD(30) RT_GSD(94) RT_GSD(158) RT_GSD(64) RT_GSD(128)
-      default: throw RtError(8, "gemm_split: unknown RT_GS_DBG"); }
-#undef RT_GSD
-    return;
-  }
   if (epi.a_scale) {
-#define RT_GSE(LABV) do { allow_big_lds((const void*)k_gemm_split<ACT_HSWISH, LABV, 0, true>, 160 * 1024); \
-    RT_LAUNCH((k_gemm_split<ACT_HSWISH, LABV, 0, true>), dim3((unsigned)grid), dim3(S_NTHR), S_LDS_ASC, st, g); } while (0)
+#define RT_GSE(LABV) do { allow_big_lds((const void*)k_gemm_split<ACT_HSWISH, LABV, true>, 160 * 1024); \
+    RT_LAUNCH((k_gemm_split<ACT_HSWISH, LABV, true>), dim3((unsigned)grid), dim3(S_NTHR), S_LDS_ASC, st, g); } while (0)
     if (epi.has_lab) RT_GSE(1); else RT_GSE(0);
 #undef RT_GSE
     return;

@@ -670,7 +670,6 @@ __global__ __launch_bounds__(64 * TH) void k_lc_thin(const float* __restrict__ x
 }
 
 int g_lc_wave = getenv("RT_LC_WAVE") ? atoi(getenv("RT_LC_WAVE")) : 3;   // 3 = wave-private LDS form for the stride-1 blocks (nn_lcwave.hip, default); 1 = direct-load form, every shape (A/B); 0 = k_lc_thin
-int g_lc_thin = 4;  // 4 = fused thin blocks (default); 2 / 3 = force the 128- / 64-pixel tile; 0 = separate depthwise + GEMM kernels (A/B)
 static int lc_thin_code(int sh, int sw, int Cp, int Npad16) {  // instantiated (stride, C_in/4, column tiles) combinations
   const int c4 = Cp / 4, nt = (Npad16 + 31) / 32;
   if (sh == 1 && sw == 1) {
@@ -685,7 +684,7 @@ static int lc_thin_code(int sh, int sw, int Cp, int Npad16) {  // instantiated (
   return 0;
 }
 bool lc_thin_supported(int K, int sh, int sw, int Cp, int C, int Npad16) {
-  return g_lc_thin && K == 3 && Cp == round_up(C, 4) && lc_thin_code(sh, sw, Cp, Npad16) != 0;
+  return K == 3 && Cp == round_up(C, 4) && lc_thin_code(sh, sw, Cp, Npad16) != 0;
 }
 // (k_lc_lds / k_lc_wave address an image through a 32-bit buffer offset, out-of-range marker 0x80000000: images up to 1 GB)
 static bool lc_wave_fits(int maxHo, int maxWo, int sh, int sw, int Cp, int ldy) {
@@ -695,7 +694,7 @@ static bool lc_wave_fits(int maxHo, int maxWo, int sh, int sw, int Cp, int ldy) 
 bool lc_block_supported(int K, int sh, int sw, int Cp, int C, int N, int Npad16, int dw_act, int dw_has_lab, const Epilogue& epi,
                         int maxHo, int maxWo) {
   if (lc_thin_supported(K, sh, sw, Cp, C, Npad16)) return true;
-  return g_lc_wave && g_lc_thin == 4 && lc_wave_supported(K, sh, sw, Cp, C, N, Npad16, dw_act, dw_has_lab, epi) &&
+  return g_lc_wave && lc_wave_supported(K, sh, sw, Cp, C, N, Npad16, dw_act, dw_has_lab, epi) &&
          lc_wave_fits(maxHo, maxWo, sh, sw, Cp, chan_pitch(N));
 }
 void lc_thin(hipStream_t st, int sh, int sw, const float* x, const ImgGeom* gin, const ImgGeom* gout, int n_img, int maxHo,
@@ -703,29 +702,26 @@ void lc_thin(hipStream_t st, int sh, int sw, const float* x, const ImgGeom* gin,
              const float* Wp, int N, int Npad16, float* y, int ldy, const Epilogue& epi) {
   if (n_img <= 0) return;
   if (epi.residual || epi.a_scale) throw RtError(8, "lc_thin: residual / a_scale epilogues are not supported");
-  if (g_lc_wave && g_lc_thin == 4 && lc_wave_supported(3, sh, sw, Cp, C, N, Npad16, dw_act, dw_has_lab, epi) && lc_wave_fits(maxHo, maxWo, sh, sw, Cp, ldy)) {
+  if (g_lc_wave && lc_wave_supported(3, sh, sw, Cp, C, N, Npad16, dw_act, dw_has_lab, epi) && lc_wave_fits(maxHo, maxWo, sh, sw, Cp, ldy)) {
     lc_wave(st, sh, sw, x, gin, gout, n_img, maxHo, maxWo, Cp, C, Wd, bd, dw_act, dw_has_lab, dw_a, dw_c, Wp, N, Npad16, y, ldy, epi);
     return;
   }
-  // measured per shape: 64-pixel tiles (more workgroups per CU) win from 48 channels up, 128-pixel tiles below
+  // measured per shape: 64-pixel tiles (TH = 4: more workgroups per CU) win from 48 channels up, 128-pixel tiles below
   const int code = lc_thin_code(sh, sw, Cp, Npad16);
-  const int TH = code >= 6 ? 4 : (g_lc_thin == 2 ? 8 : (g_lc_thin == 3 ? 4 : (Cp >= 48 ? 4 : 8)));  // 2 / 3 force a variant (A/B)
-  static const int tpb_env = getenv("RT_LCT_TPB") ? atoi(getenv("RT_LCT_TPB")) : 0;
-  const int tiles = ((maxWo + 15) / 16) * ((maxHo + TH - 1) / TH), tpb = tpb_env > 0 ? tpb_env : 8;
+  const int TH = code >= 6 || Cp >= 48 ? 4 : 8, tpb = 8;
+  const int tiles = ((maxWo + 15) / 16) * ((maxHo + TH - 1) / TH);
   dim3 grid((tiles + tpb - 1) / tpb, n_img);
-#define RT_LCT_T(CC, NN, TT, S1, S2) RT_LAUNCH((k_lc_thin<CC, NN, TT, S1, S2>), grid, dim3(64 * TT), 0, st, x, gin, gout, C, Wd, bd, dw_act, dw_has_lab, dw_a, dw_c, Wp, N, Npad16, y, ldy, epi, tpb)
-#define RT_LCT(CC, NN) do { if (TH == 4) RT_LCT_T(CC, NN, 4, 1, 1); else RT_LCT_T(CC, NN, 8, 1, 1); } while (0)
+#define RT_LCT(CC, NN, TT, S1, S2) RT_LAUNCH((k_lc_thin<CC, NN, TT, S1, S2>), grid, dim3(64 * TT), 0, st, x, gin, gout, C, Wd, bd, dw_act, dw_has_lab, dw_a, dw_c, Wp, N, Npad16, y, ldy, epi, tpb)
   switch (code) {
-    case 1: RT_LCT(4, 1); break;
-    case 2: RT_LCT(8, 2); break;
-    case 3: RT_LCT(12, 2); break;
-    case 4: RT_LCT(16, 2); break;
-    case 6: RT_LCT_T(8, 2, 4, 2, 2); break;
-    case 7: RT_LCT_T(12, 3, 4, 2, 2); break;
+    case 1: RT_LCT(4, 1, 8, 1, 1); break;
+    case 2: RT_LCT(8, 2, 8, 1, 1); break;
+    case 3: RT_LCT(12, 2, 4, 1, 1); break;
+    case 4: RT_LCT(16, 2, 4, 1, 1); break;
+    case 6: RT_LCT(8, 2, 4, 2, 2); break;
+    case 7: RT_LCT(12, 3, 4, 2, 2); break;
     default: throw RtError(8, "lc_thin: unsupported shape (check lc_thin_supported)");
   }
 #undef RT_LCT
-#undef RT_LCT_T
 }
 
 // one thread per row: fold the column tiles in ascending order -> argmax (first maximum) and softmax(max) = 1 / sum
@@ -1044,14 +1040,12 @@ __global__ __launch_bounds__(256, 2) void k_conv3_few(const float* __restrict__ 
   });
 }
 
-static const int g_conv3_few = getenv("RT_CONV3_FEW") ? atoi(getenv("RT_CONV3_FEW")) : 1;   // A/B: 0 keeps the 16-wide tiles for every N
-
-// DB head's first 3x3 conv (4 * Cq -> N) straight from the four FPN levels: conv_sp over fpn_concat's result without building it.
-bool conv3_fpn_fused_supported(int Cq, int N) { return g_conv3_few && Cq == 24 && N == 24 && getenv("RT_NO_FPN_FUSE") == nullptr; }
+// DB head's first 3x3 conv (4 * Cq -> N) straight from the four FPN levels: conv_sp over their concatenation without building it.
 void conv3_fpn_fused(hipStream_t st, const float* p5, const float* p4, const float* p3, const float* p2, const ImgGeom* g5,
                      const ImgGeom* g4, const ImgGeom* g3, const ImgGeom* g2, int n_img, int maxH, int maxW, int Cq,
                      const float* const* scales, const float* Wp, int N, int Npad16, float* y, int ldy, const Epilogue& epi) {
   if (n_img <= 0) return;
+  if (Cq != 24 || N != 24) throw RtError(8, "conv3_fpn_fused: 4 x 24 -> 24 channels only");
   FpnSrc fs;
   fs.p[0] = p5; fs.p[1] = p4; fs.p[2] = p3; fs.p[3] = p2;
   fs.g[0] = g5; fs.g[1] = g4; fs.g[2] = g3; fs.g[3] = g2;
@@ -1163,8 +1157,7 @@ __global__ __launch_bounds__(256) void k_conv13_flat(const float* __restrict__ x
   epilogue_store<NT>(acc, nt_valid, epi, n0, N, nstore, y + t0 * ldy, y + t1 * ldy, t0 < rows, t1 < rows,
                      epi.residual ? epi.residual + t0 * epi.ld_res : nullptr, epi.residual ? epi.residual + t1 * epi.ld_res : nullptr, q);
 }
-int g_conv13_flat = getenv("RT_CONV13_FLAT") ? atoi(getenv("RT_CONV13_FLAT")) : 1;   // A/B: 0 = k_conv_sp<1,3,1,128,NT> (a tile per line)
-bool conv13_flat_supported(int N, int Npad16) { return g_conv13_flat && Npad16 <= 64 && N > 0; }
+bool conv13_flat_supported(int N, int Npad16) { return Npad16 <= 64 && N > 0; }
 void conv13_flat(hipStream_t st, const float* x, int ldx, long long rows, const unsigned char* flags, int Cin, const float* Wp, int N,
                  int Npad16, float* y, int ldy, const Epilogue& epi) {
   if (rows <= 0) return;
@@ -1188,7 +1181,7 @@ void conv_sp(hipStream_t st, int KH, int KW, const float* x, int ldx, const ImgG
   if (n_img <= 0) return;
   int ntiles = Npad16 / 16;
   // few output channels that do not fill 16-wide tiles (N = 24: a quarter of k_conv_sp's MFMA work would be padding)
-  if (KH == 3 && KW == 3 && g_conv3_few && N % 16 != 0 && N <= 32 && !epi.residual && ldy >= round_up(N, 4)) {
+  if (KH == 3 && KW == 3 && N % 16 != 0 && N <= 32 && !epi.residual && ldy >= round_up(N, 4)) {
     dim3 gridf(((maxW + 15) / 16) * ((maxH + 15) / 16), n_img);
     switch ((N + 3) / 4) {
 #define RT_C3F(n) case n: RT_LAUNCH((k_conv3_few<n>), gridf, dim3(256), 0, st, x, ldx, geom, Cin, Wp, N, Npad16, y, ldy, epi, FpnSrc{}); return;
@@ -1232,7 +1225,6 @@ void conv_sp(hipStream_t st, int KH, int KW, const float* x, int ldx, const ImgG
 // spanning whole pixels with all the weights in LDS (1.2-1.5x slower), one-row-ahead register
 // prefetch (hipcc hoists every load: spills).  On short maps (<= 24 rows, no pooling) the 5x5 stride-1 layers run on
 // k_dwconv_sweep below instead (every input row fetched once).
-__device__ int g_dw_xcd_dev = 1;  // XCD-aware block order of k_dwconv_rows (A/B: set_dw_xcd)
 template <int K, int R, int SH, int SW, int POOL, int LP = 8>  // LP lanes (16 bytes each) side by side on a pixel: 32- or 64-channel slabs
 __global__ __launch_bounds__(256, 4) void k_dwconv_rows(const float* __restrict__ x, const ImgGeom* __restrict__ gin,
                                                      const ImgGeom* __restrict__ gout, int Cp, int C,
@@ -1248,7 +1240,7 @@ __global__ __launch_bounds__(256, 4) void k_dwconv_rows(const float* __restrict_
   // (xcd, seq) is mapped to work item xcd * (total / 8) + seq: every XCD walks one contiguous eighth of the
   // (strip block, image, slab) space, neighbours meet in the same L2 shortly after each other.
   unsigned bx = blockIdx.x, by = blockIdx.y, bz = blockIdx.z;
-  if (g_dw_xcd_dev) {
+  {
     // (within one channel slab: an XCD per slab -- the same remap over all three grid dimensions -- measured
     // 1.4x slower at C = 256)
     const unsigned gx = gridDim.x, gy = gridDim.y, total = gx * gy, per = total >> 3;
@@ -1469,17 +1461,11 @@ __global__ __launch_bounds__(256, WAVES) void k_dwconv_sweep(const float* __rest
   });
 }
 
-void set_dw_xcd(int v) { RT_HIP_CHECK(hipMemcpyToSymbol(HIP_SYMBOL(g_dw_xcd_dev), &v, sizeof(int))); }
-int g_dw_wide_slab_min = 192;      // channel pitch from which the 5x5 kernels use wide slabs (1 << 30: never, A/B)
 static int dw_lanes_per_pixel(int K, int sh, int sw, int R, int Cp, bool pool);
-int g_dw_wide3_min = 128;          // same for the 3x3 kernels (64-channel slabs)
-int g_dw_wide_lp = 16;             // 16 = 64-channel slabs, 32 = 128-channel slabs
-int g_dw_variant = 0;
-int g_dw_sweep = getenv("RT_DW_SWEEP") ? atoi(getenv("RT_DW_SWEEP")) : 4;   // column-sweep 5x5 kernel on short maps: pixels per thread (0: off)
+int g_dw_sweep = getenv("RT_DW_SWEEP") ? atoi(getenv("RT_DW_SWEEP")) : 4;   // column-sweep kernels on short maps (0: off)
 // Output rows per thread of k_dwconv_rows: 4 (stride 1) or 2 (stride 2); 3 for the 3- and 6-row maps of the
 // recognition net's last stages, where 4-row (2-row) strips would leave a quarter of the lanes' rows empty.
 static int dw_strip_rows(int sh, int maxHo) {
-  if (g_dw_variant == 4) return 2;
   if (maxHo == 6 || (maxHo == 3 && sh == 1)) return 3;  // (stride 2 onto 3 rows: 2-row strips measured faster)
   return sh == 1 ? 4 : 2;
 }
@@ -1488,19 +1474,17 @@ void dwconv(hipStream_t st, int K, int sh, int sw, const float* x, const ImgGeom
             int maxHo, int maxWo, int Cp, int C, const float* Wd, const float* bias, int act, int has_lab, float lab_a,
             float lab_c, float* y, float* pool) {
   if (n_img <= 0) return;
-  if ((K == 3 || K == 5) && sh >= 1 && sh <= 2 && sw >= 1 && sw <= 2 && (g_dw_variant == 0 || g_dw_variant == 4)) {  // 4 = 2-row strips (A/B)
+  if ((K == 3 || K == 5) && sh >= 1 && sh <= 2 && sw >= 1 && sw <= 2) {
     const int R = dw_strip_rows(sh, maxHo);  // input rows streamed: stride 1 -> R+K-1, stride 2 -> 2R+K-2
     long long strips = (long long)((maxWo + 3) / 4) * ((maxHo + R - 1) / R);
-    // 64- / 128-channel slabs (256 / 512 contiguous bytes per pixel and load) for wide tensors: the 5x5 kernel on
-    // 256 channels goes from 2.9 to 4.1 TB/s with 64-channel slabs; 32-channel slabs otherwise
+    // 64-channel slabs (256 contiguous bytes per pixel and load) for wide tensors: the 5x5 kernel on 256 channels goes from
+    // 2.9 to 4.1 TB/s with them; 32-channel slabs otherwise
     const int lp = dw_lanes_per_pixel(K, sh, sw, R, Cp, pool != nullptr);
-    // short, wide maps: one thread column sweeps the whole height (RT_DW_SWEEP: 0 off; 2 / 3 / 4 = form, A/B)
+    // short, wide maps: one thread column sweeps the whole height (RT_DW_SWEEP=0: off)
     if (g_dw_sweep && K == 5 && sh == 1 && sw == 1 && !pool && lp == 16 && maxHo >= 5 && maxHo <= 24) {
-      const int spb = 256 / 16, px = g_dw_sweep == 4 ? 4 : 2;
-      dim3 grids((unsigned)(((maxWo + px - 1) / px + spb - 1) / spb), n_img, (Cp + 63) / 64);
-      if (px == 4) RT_LAUNCH((k_dwconv_sweep<5, 16, 4, 3>), grids, dim3(256), 0, st, x, gin, gout, Cp, C, Wd, bias, act, has_lab, lab_a, lab_c, y);
-      else if (g_dw_sweep == 3) RT_LAUNCH((k_dwconv_sweep<5, 16, 2, 5>), grids, dim3(256), 0, st, x, gin, gout, Cp, C, Wd, bias, act, has_lab, lab_a, lab_c, y);
-      else RT_LAUNCH((k_dwconv_sweep<5, 16, 2, 4>), grids, dim3(256), 0, st, x, gin, gout, Cp, C, Wd, bias, act, has_lab, lab_a, lab_c, y);
+      const int spb = 256 / 16;
+      dim3 grids((unsigned)(((maxWo + 3) / 4 + spb - 1) / spb), n_img, (Cp + 63) / 64);
+      RT_LAUNCH((k_dwconv_sweep<5, 16, 4, 3>), grids, dim3(256), 0, st, x, gin, gout, Cp, C, Wd, bias, act, has_lab, lab_a, lab_c, y);
       return;
     }
     // (round 4) the same sweep for the 3x3 stride-1 layer on the 12-row, 128-channel maps of the recognition net: k_dwconv_rows
@@ -1511,23 +1495,21 @@ void dwconv(hipStream_t st, int K, int sh, int sw, const float* x, const ImgGeom
       RT_LAUNCH((k_dwconv_sweep<3, 16, 4, 4>), grids, dim3(256), 0, st, x, gin, gout, Cp, C, Wd, bias, act, has_lab, lab_a, lab_c, y);
       return;
     }
-    if (lp != 8) {
-      const int spb = 256 / lp;
-      dim3 gridw((unsigned)((strips + spb - 1) / spb), n_img, (Cp + lp * 4 - 1) / (lp * 4));
-#define RT_DWW(KK, RR, SH_, SW_, LL)                                                                                         \
+    if (lp == 16) {
+      const int spb = 256 / 16;
+      dim3 gridw((unsigned)((strips + spb - 1) / spb), n_img, (Cp + 63) / 64);
+#define RT_DWW(KK, RR, SH_, SW_)                                                                                             \
   do {                                                                                                                       \
-    if (pool) RT_LAUNCH((k_dwconv_rows<KK, RR, SH_, SW_, 1, LL>), gridw, dim3(256), 0, st, x, gin, gout, Cp, C, Wd, bias, act, has_lab, lab_a, lab_c, y, pool); \
-    else RT_LAUNCH((k_dwconv_rows<KK, RR, SH_, SW_, 0, LL>), gridw, dim3(256), 0, st, x, gin, gout, Cp, C, Wd, bias, act, has_lab, lab_a, lab_c, y, pool); \
+    if (pool) RT_LAUNCH((k_dwconv_rows<KK, RR, SH_, SW_, 1, 16>), gridw, dim3(256), 0, st, x, gin, gout, Cp, C, Wd, bias, act, has_lab, lab_a, lab_c, y, pool); \
+    else RT_LAUNCH((k_dwconv_rows<KK, RR, SH_, SW_, 0, 16>), gridw, dim3(256), 0, st, x, gin, gout, Cp, C, Wd, bias, act, has_lab, lab_a, lab_c, y, pool); \
   } while (0)
-#define RT_DWW_L(KK, RR, SH_, SW_) do { if (lp == 16) RT_DWW(KK, RR, SH_, SW_, 16); else RT_DWW(KK, RR, SH_, SW_, 32); } while (0)
-      if (K == 5 && sh == 1 && sw == 1 && R == 4) { RT_DWW_L(5, 4, 1, 1); return; }
-      if (K == 5 && sh == 1 && sw == 1 && R == 3) { RT_DWW_L(5, 3, 1, 1); return; }
-      if (K == 5 && sh == 2 && sw == 1 && R == 2) { RT_DWW_L(5, 2, 2, 1); return; }
-      if (K == 5 && sh == 2 && sw == 1 && R == 3) { RT_DWW_L(5, 3, 2, 1); return; }
-      if (K == 5 && sh == 2 && sw == 2 && R == 2) { RT_DWW_L(5, 2, 2, 2); return; }
-      if (K == 3 && sh == 1 && sw == 1 && R == 4 && !pool) { RT_DWW(3, 4, 1, 1, 16); return; }
-      if (K == 3 && sh == 1 && sw == 2 && R == 4 && !pool) { RT_DWW(3, 4, 1, 2, 16); return; }
-#undef RT_DWW_L
+      if (K == 5 && sh == 1 && sw == 1 && R == 4) { RT_DWW(5, 4, 1, 1); return; }
+      if (K == 5 && sh == 1 && sw == 1 && R == 3) { RT_DWW(5, 3, 1, 1); return; }
+      if (K == 5 && sh == 2 && sw == 1 && R == 2) { RT_DWW(5, 2, 2, 1); return; }
+      if (K == 5 && sh == 2 && sw == 1 && R == 3) { RT_DWW(5, 3, 2, 1); return; }
+      if (K == 5 && sh == 2 && sw == 2 && R == 2) { RT_DWW(5, 2, 2, 2); return; }
+      if (K == 3 && sh == 1 && sw == 1 && R == 4 && !pool) { RT_DWW(3, 4, 1, 1); return; }
+      if (K == 3 && sh == 1 && sw == 2 && R == 4 && !pool) { RT_DWW(3, 4, 1, 2); return; }
 #undef RT_DWW
       throw RtError(8, "dwconv: no wide-slab instantiation for a shape dw_lanes_per_pixel() lists");
     }
@@ -1538,8 +1520,7 @@ void dwconv(hipStream_t st, int K, int sh, int sw, const float* x, const ImgGeom
     else RT_LAUNCH((k_dwconv_rows<KK, RR, SH_, SW_, 0>), grid, dim3(256), 0, st, x, gin, gout, Cp, C, Wd, bias, act, has_lab, lab_a, lab_c, y, pool); \
   } while (0)
     const int code = (K == 5 ? 4 : 0) + (sh == 2 ? 2 : 0) + (sw == 2 ? 1 : 0);
-#define RT_DWR_R(KK, SH_, SW_, RBIG) \
-  do { if (R == 3) RT_DWR(KK, 3, SH_, SW_); else if (R == RBIG) RT_DWR(KK, RBIG, SH_, SW_); else RT_DWR(KK, 2, SH_, SW_); } while (0)
+#define RT_DWR_R(KK, SH_, SW_, RBIG) do { if (R == 3) RT_DWR(KK, 3, SH_, SW_); else RT_DWR(KK, RBIG, SH_, SW_); } while (0)
     switch (code) {
       case 0: RT_DWR_R(3, 1, 1, 4); break; case 1: RT_DWR_R(3, 1, 2, 4); break;
       case 2: RT_DWR_R(3, 2, 1, 2); break; case 3: RT_DWR_R(3, 2, 2, 2); break;
@@ -1596,66 +1577,9 @@ __global__ __launch_bounds__(256) void k_stem(const float* __restrict__ x, const
   }
 }
 
-// Det stem straight from the RGB8 pages: DetProcessor::preprocess's normalise (det_processor.rs:151-155: BGR order,
-// (v * scale - mean) / std, each operation rounded on its own like k_det_normalize) is applied while the 3x3 window
-// is read, so the [H, W, 4] f32 input tensor (16 bytes per pixel written and read back) never exists.
-template <int COUT>
-__global__ __launch_bounds__(256) void k_stem_u8(const U8Page* __restrict__ pages, float scale, float m0, float m1, float m2,
-                                                 float s0, float s1, float s2, const ImgGeom* __restrict__ gin,
-                                                 const ImgGeom* __restrict__ gout, const float* __restrict__ Ws,
-                                                 const float* __restrict__ bias, int act, float* __restrict__ y) {
-  __shared__ float w[27 * COUT + COUT];
-  for (int i = threadIdx.x; i < 27 * COUT; i += 256) w[i] = Ws[i];
-  for (int i = threadIdx.x; i < COUT; i += 256) w[27 * COUT + i] = bias[i];
-  __syncthreads();
-  const ImgGeom gi = gin[blockIdx.y], go = gout[blockIdx.y];
-  const uint8_t* rgb = pages[blockIdx.y].rgb;
-  long long p = (long long)blockIdx.x * 256 + threadIdx.x;
-  if (p >= (long long)go.H * go.W) return;
-  int oy = (int)(p / go.W), ox = (int)(p % go.W);
-  const float mean[3] = {m0, m1, m2}, stdv[3] = {s0, s1, s2};
-  float acc[COUT];
-#pragma unroll
-  for (int c = 0; c < COUT; c++) acc[c] = w[27 * COUT + c];
-#pragma unroll
-  for (int dy = 0; dy < 3; dy++) {
-    int iy = oy * 2 - 1 + dy;
-    if (iy < 0 || iy >= gi.H) continue;
-#pragma unroll
-    for (int dx = 0; dx < 3; dx++) {
-      int ix = ox * 2 - 1 + dx;
-      if (ix < 0 || ix >= gi.W) continue;
-      const uint8_t* px = rgb + ((long long)iy * gi.W + ix) * 3;
-      const float* wt = w + (dy * 3 + dx) * 3 * COUT;
-#pragma unroll
-      for (int ci = 0; ci < 3; ci++) {  // channel ci of BGR
-        float v;
-        {
-          // this file is compiled with -ffp-contract=fast; HIP's __fmul_rn / __fsub_rn are plain operators and
-          // `#pragma clang fp contract(off)` did not stop the fusion either (caught by the checksum test): the
-          // multiply and the subtract are pinned as separate instructions so that the value is k_det_normalize's
-          float t, u;
-          const float xf = (float)px[2 - ci], mc = mean[ci];
-          asm volatile("v_mul_f32_e32 %0, %1, %2" : "=v"(t) : "v"(xf), "v"(scale));
-          asm volatile("v_sub_f32_e32 %0, %1, %2" : "=v"(u) : "v"(t), "v"(mc));
-          v = u / stdv[ci];
-        }
-#pragma unroll
-        for (int c = 0; c < COUT; c++) acc[c] = fmaf(v, wt[ci * COUT + c], acc[c]);
-      }
-    }
-  }
-  float* o = y + (go.off + p) * COUT;
-#pragma unroll
-  for (int c = 0; c < COUT; c += 4) {
-    f32x4 t = {act_apply(acc[c], act), act_apply(acc[c + 1], act), act_apply(acc[c + 2], act),
-               act_apply(acc[c + 3], act)};
-    *reinterpret_cast<f32x4*>(o + c) = t;
-  }
-}
 // ---------------------------------------------------------------------------
 // Stem on the matrix cores (round 4): 3x3 stride 2, 3 -> 16 channels = a [pixels, 27] x [27, 16] contraction, seven
-// v_mfma_f32_16x16x4_f32 steps per 16 pixels.  The thread-per-pixel kernels above ran at 2.1 TB/s of their bytes: 27 strided
+// v_mfma_f32_16x16x4_f32 steps per 16 pixels.  The thread-per-pixel kernels it replaced ran at 2.1 TB/s of their bytes: 27 strided
 // byte loads + 27 IEEE divisions (U8) and 432 scalar FMAs per output pixel.  Here a workgroup stages the (2 TH + 1) x (2 TW + 1)
 // input patch of a TH x TW = 8 x 32 output tile ONCE into LDS as normalised floats (coalesced byte / 16-byte loads, each input
 // element converted once), and lane (r, q) of a wave reads operand k = 4 step + q of pixel r with one ds_read_b32 per step
@@ -1783,36 +1707,27 @@ __global__ __launch_bounds__(256) void k_stem_mfma(const float* __restrict__ x, 
     }
   }
 }
-static const int g_stem_mfma = getenv("RT_STEM_MFMA") ? atoi(getenv("RT_STEM_MFMA")) : 1;   // A/B: 0 = thread-per-pixel stems
-
 void stem_conv_u8(hipStream_t st, const U8Page* pages, float scale, const float* mean3, const float* std3, const ImgGeom* gin,
                   const ImgGeom* gout, int n_img, int maxHo, int maxWo, int COUT, const float* Ws, const float* bias, int act,
                   float* y) {
   if (n_img <= 0) return;
   if (COUT != 16) throw RtError(8, "stem_conv_u8: unsupported COUT");
-  if (g_stem_mfma) {
-    dim3 gridm((unsigned)(((maxWo + 31) / 32) * ((maxHo + 7) / 8)), n_img);
-    RT_LAUNCH(k_stem_mfma<1>, gridm, dim3(256), 0, st, (const float*)nullptr, pages, scale, mean3[0], mean3[1], mean3[2], std3[0],
-              std3[1], std3[2], gin, gout, Ws, bias, act, y);
-    return;
-  }
-  dim3 grid((unsigned)(((long long)maxHo * maxWo + 255) / 256), n_img);
-  RT_LAUNCH(k_stem_u8<16>, grid, dim3(256), 0, st, pages, scale, mean3[0], mean3[1], mean3[2], std3[0], std3[1],
-                     std3[2], gin, gout, Ws, bias, act, y);
+  dim3 gridm((unsigned)(((maxWo + 31) / 32) * ((maxHo + 7) / 8)), n_img);
+  RT_LAUNCH(k_stem_mfma<1>, gridm, dim3(256), 0, st, (const float*)nullptr, pages, scale, mean3[0], mean3[1], mean3[2], std3[0],
+            std3[1], std3[2], gin, gout, Ws, bias, act, y);
 }
 
 void stem_conv(hipStream_t st, const float* x, const ImgGeom* gin, const ImgGeom* gout, int n_img, int maxHo, int maxWo,
                int COUT, const float* Ws, const float* bias, int act, float* y) {
   if (n_img <= 0) return;
-  if (COUT == 16 && g_stem_mfma) {
+  if (COUT == 16) {
     dim3 gridm((unsigned)(((maxWo + 31) / 32) * ((maxHo + 7) / 8)), n_img);
     RT_LAUNCH(k_stem_mfma<0>, gridm, dim3(256), 0, st, x, (const U8Page*)nullptr, 0.f, 0.f, 0.f, 0.f, 1.f, 1.f, 1.f, gin, gout, Ws,
               bias, act, y);
     return;
   }
   dim3 grid((unsigned)(((long long)maxHo * maxWo + 255) / 256), n_img);
-  if (COUT == 16) RT_LAUNCH(k_stem<16>, grid, dim3(256), 0, st, x, gin, gout, Ws, bias, act, y);
-  else if (COUT == 8) RT_LAUNCH(k_stem<8>, grid, dim3(256), 0, st, x, gin, gout, Ws, bias, act, y);
+  if (COUT == 8) RT_LAUNCH(k_stem<8>, grid, dim3(256), 0, st, x, gin, gout, Ws, bias, act, y);   // (the classifier's stem)
   else throw RtError(8, "stem_conv: unsupported COUT");
 }
 
@@ -2058,14 +1973,14 @@ void se_scale_projected(hipStream_t st, const float* x_in, const ImgGeom* geom, 
 // wide AND a wide instantiation exists for the shape, else 8 (32-channel slabs).  The one place that decides it: the
 // launch (dwconv) and the layout of the fused pooling partials (dwconv_pool_layout -> k_se_fc) must agree.
 static int dw_lanes_per_pixel(int K, int sh, int sw, int R, int Cp, bool pool) {
-  int lp = 8;
-  if (K == 5 && Cp >= g_dw_wide_slab_min) lp = g_dw_wide_lp;
-  else if (K == 3 && Cp >= g_dw_wide3_min) lp = 16;
-  if (lp == 8) return 8;
-  if (K == 5 && sh == 1 && sw == 1 && (R == 4 || R == 3)) return lp;
-  if (K == 5 && sh == 2 && sw == 1 && (R == 2 || R == 3)) return lp;
-  if (K == 5 && sh == 2 && sw == 2 && R == 2) return lp;
-  if (K == 3 && sh == 1 && (sw == 1 || sw == 2) && R == 4 && !pool) return 16;
+  // 64-channel slabs from 192 channels (5x5) / 128 channels (3x3) up, for the shapes with a wide-slab instantiation
+  if (K == 5 && Cp >= 192) {
+    if (sh == 1 && sw == 1 && (R == 4 || R == 3)) return 16;
+    if (sh == 2 && sw == 1 && (R == 2 || R == 3)) return 16;
+    if (sh == 2 && sw == 2 && R == 2) return 16;
+  } else if (K == 3 && Cp >= 128) {
+    if (sh == 1 && (sw == 1 || sw == 2) && R == 4 && !pool) return 16;
+  }
   return 8;
 }
 void dwconv_pool_layout(int K, int sh, int sw, int Cp, int maxHo, int maxWo, int* chunks, int* strip_R, int* strips_per_block) {
@@ -2210,96 +2125,9 @@ void upsample_add(hipStream_t st, const float* a, const float* b, const ImgGeom*
                      out, scale_a);
 }
 
-__global__ __launch_bounds__(256) void k_fpn_concat(const float* __restrict__ p5, const float* __restrict__ p4,
-                                                    const float* __restrict__ p3, const float* __restrict__ p2,
-                                                    const ImgGeom* __restrict__ g5, const ImgGeom* __restrict__ g4,
-                                                    const ImgGeom* __restrict__ g3, const ImgGeom* __restrict__ g2,
-                                                    int Cq, float* __restrict__ out, const float* __restrict__ s5,
-                                                    const float* __restrict__ s4, const float* __restrict__ s3,
-                                                    const float* __restrict__ s2) {
-  const ImgGeom G2 = g2[blockIdx.y];
-  const int Q4 = Cq >> 2, C4 = Q4 * 4;
-  long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
-  if (idx >= (long long)G2.H * G2.W * C4) return;
-  int c4 = (int)(idx % C4);
-  long long p = idx / C4;
-  int y = (int)(p / G2.W), x = (int)(p % G2.W);
-  int lvl = c4 / Q4, cc = c4 % Q4;
-  const float* src;
-  const float* sc;  // optional squeeze-excite scale of that level ([image][Cq]), folded into the gather
-  ImgGeom G;
-  int sh;
-  if (lvl == 0) { src = p5; sc = s5; G = g5[blockIdx.y]; sh = 3; }
-  else if (lvl == 1) { src = p4; sc = s4; G = g4[blockIdx.y]; sh = 2; }
-  else if (lvl == 2) { src = p3; sc = s3; G = g3[blockIdx.y]; sh = 1; }
-  else { src = p2; sc = s2; G = G2; sh = 0; }
-  int sy = min(y >> sh, G.H - 1), sx = min(x >> sh, G.W - 1);
-  f32x4 v = *reinterpret_cast<const f32x4*>(src + (G.off + (long long)sy * G.W + sx) * Cq + cc * 4);
-  if (sc) v *= *reinterpret_cast<const f32x4*>(sc + (long long)blockIdx.y * Cq + cc * 4);
-  *reinterpret_cast<f32x4*>(out + (G2.off + p) * (4 * Cq) + c4 * 4) = v;
-}
-void fpn_concat(hipStream_t st, const float* p5, const float* p4, const float* p3, const float* p2, const ImgGeom* g5,
-                const ImgGeom* g4, const ImgGeom* g3, const ImgGeom* g2, int n_img, long long max_pix, int Cq,
-                float* out, const float* const* scales) {
-  if (n_img <= 0) return;
-  long long total = max_pix * Cq;  // 4 levels * Cq/4 groups
-  const float* nul = nullptr;
-  RT_LAUNCH(k_fpn_concat, dim3((unsigned)((total + 255) / 256), n_img), dim3(256), 0, st, p5, p4, p3, p2, g5,
-                     g4, g3, g2, Cq, out, scales ? scales[0] : nul, scales ? scales[1] : nul, scales ? scales[2] : nul,
-                     scales ? scales[3] : nul);
-}
-
-// DB head tail. w1 [24][24][2][2] (cin, cout, dy, dx), w2 [24][1][2][2].
-__global__ __launch_bounds__(256) void k_db_head_tail(const float* __restrict__ x, const ImgGeom* __restrict__ gin,
-                                                      const ImgGeom* __restrict__ gout, const float* __restrict__ w1,
-                                                      const float* __restrict__ b1, const float* __restrict__ w2,
-                                                      const float* __restrict__ b2, float* __restrict__ out) {
-  __shared__ float sw1[4 * 24 * 24];  // [pos][ci][co]
-  __shared__ float sw2[4 * 24];       // [pos][co]
-  __shared__ float sb1[24];
-  for (int i = threadIdx.x; i < 4 * 24 * 24; i += 256) {
-    int pos = i / 576, ci = (i / 24) % 24, co = i % 24;
-    sw1[i] = w1[(ci * 24 + co) * 4 + pos];
-  }
-  for (int i = threadIdx.x; i < 96; i += 256) { int pos = i / 24, co = i % 24; sw2[i] = w2[co * 4 + pos]; }
-  if (threadIdx.x < 24) sb1[threadIdx.x] = b1[threadIdx.x];
-  __syncthreads();
-  const ImgGeom gi = gin[blockIdx.y], go = gout[blockIdx.y];
-  long long p = (long long)blockIdx.x * 256 + threadIdx.x;
-  if (p >= (long long)gi.H * gi.W) return;
-  int iy = (int)(p / gi.W), ix = (int)(p % gi.W);
-  float in[24];
-  const f32x4* src = reinterpret_cast<const f32x4*>(x + (gi.off + p) * 24);
-#pragma unroll
-  for (int i = 0; i < 6; i++) { f32x4 v = src[i]; in[4 * i] = v[0]; in[4 * i + 1] = v[1]; in[4 * i + 2] = v[2]; in[4 * i + 3] = v[3]; }
-  const float bias2 = b2[0];
-  float o[4][4];
-#pragma unroll
-  for (int pos1 = 0; pos1 < 4; pos1++) {
-    float mid[24];
-#pragma unroll
-    for (int co = 0; co < 24; co++) mid[co] = sb1[co];
-#pragma unroll
-    for (int ci = 0; ci < 24; ci++)
-#pragma unroll
-      for (int co = 0; co < 24; co++) mid[co] = fmaf(in[ci], sw1[(pos1 * 24 + ci) * 24 + co], mid[co]);
-#pragma unroll
-    for (int pos2 = 0; pos2 < 4; pos2++) {
-      float s = bias2;
-#pragma unroll
-      for (int co = 0; co < 24; co++) s = fmaf(fmaxf(mid[co], 0.f), sw2[pos2 * 24 + co], s);
-      int oy = (pos1 >> 1) * 2 + (pos2 >> 1), ox = (pos1 & 1) * 2 + (pos2 & 1);
-      o[oy][ox] = 1.0f / (1.0f + expf(-s));
-    }
-  }
-#pragma unroll
-  for (int r = 0; r < 4; r++) {
-    f32x4 v = {o[r][0], o[r][1], o[r][2], o[r][3]};
-    *reinterpret_cast<f32x4*>(out + go.off + (long long)(iy * 4 + r) * go.W + ix * 4) = v;
-  }
-}
-// The same tail on the matrix cores (round 4).  Both transposed convs are per-pixel maps (2 x 2 kernels at stride 2 do not
-// overlap): 24 -> 4 x 24 -> 4 x 4 values, 2688 MACs per input pixel, which the VALU form above pays as scalar FMAs (0.22 ms per 32
+// DB head tail on the matrix cores (round 4).  w1 [24][24][2][2] (cin, cout, dy, dx), w2 [24][1][2][2].  Both transposed convs are
+// per-pixel maps (2 x 2 kernels at stride 2 do not overlap): 24 -> 4 x 24 -> 4 x 4 values, 2688 MACs per input pixel, which the
+// VALU form it replaced paid as scalar FMAs (0.22 ms per 32
 // pages for 0.3 GB of traffic).  v_mfma_f32_4x4x1_16B_f32 with the A-operand broadcast (as k_conv3_few: lane = pixel, D[i] =
 // output 4 g + i): the pixel's own 24 channels are the B operands straight from its registers, the weights come from LDS
 // ([position][output][k] rows, one ds_read_b128 per four k), the ReLU'd first-stage accumulators are the B operands of the second
@@ -2374,17 +2202,10 @@ __global__ __launch_bounds__(256) void k_db_head_tail_mfma(const float* __restri
     *reinterpret_cast<f32x4*>(out + go.off + (long long)(iy * 4 + r) * go.W + ix * 4) = v;
   }
 }
-static const int g_tail_mfma = getenv("RT_TAIL_MFMA") ? atoi(getenv("RT_TAIL_MFMA")) : 1;   // A/B: 0 = the VALU form
-
 void db_head_tail(hipStream_t st, const float* x, const ImgGeom* gin, const ImgGeom* gout, int n_img, long long max_pix,
                   const float* w1, const float* b1, const float* w2, const float* b2, float* out) {
   if (n_img <= 0) return;
-  if (g_tail_mfma) {
-    RT_LAUNCH(k_db_head_tail_mfma, dim3((unsigned)((max_pix + 255) / 256), n_img), dim3(256), 0, st, x, gin, gout, w1, b1, w2, b2, out);
-    return;
-  }
-  RT_LAUNCH(k_db_head_tail, dim3((unsigned)((max_pix + 255) / 256), n_img), dim3(256), 0, st, x, gin, gout, w1,
-                     b1, w2, b2, out);
+  RT_LAUNCH(k_db_head_tail_mfma, dim3((unsigned)((max_pix + 255) / 256), n_img), dim3(256), 0, st, x, gin, gout, w1, b1, w2, b2, out);
 }
 
 // ---------------------------------------------------------------------------
@@ -2536,7 +2357,7 @@ __global__ __launch_bounds__(64) void k_attention(const float* __restrict__ qkv,
 // contiguous bytes), re-laid per head into 16-float LDS rows, and a thread owns one (query, head) pair: a key costs 8
 // ds_read_b128 (lanes of a wave are consecutive queries of one head: broadcast reads) instead of 30 ds_read_b32.  Same keys in
 // the same order through the same online-softmax recurrence; exp by v_exp_f32 (__expf) where k_attention calls expf: equal to
-// ~2 ulp of the exponentials, NOT bit-identical (RT_ATT_LINE=0/1 is an fp32-tolerance A/B).
+// ~2 ulp of the exponentials, NOT bit-identical.
 template <int HD>
 __global__ __launch_bounds__(256) void k_attention_line(const float* __restrict__ qkv, const ImgGeom* __restrict__ geom,
                                                         int heads, float* __restrict__ out) {
@@ -2726,19 +2547,17 @@ __global__ __launch_bounds__(512) void k_attention_mfma(const float* __restrict_
     }
   }
 }
-int g_attention_line = getenv("RT_ATT_LINE") ? atoi(getenv("RT_ATT_LINE")) : 1;   // A/B: 0 = k_attention (one wave per 64 queries and head)
 void attention(hipStream_t st, const float* qkv, const ImgGeom* geom, int n_img, int maxT, int heads, int hd,
                float* out) {
   if (n_img <= 0) return;
   if (hd != 15) throw RtError(8, "attention: head dim must be 15");
-  static const int att_mfma = getenv("RT_ATT_MFMA") ? atoi(getenv("RT_ATT_MFMA")) : 1;   // A/B: 0 = k_attention_line for every line
-  if (att_mfma && g_attention_line && maxT <= 128 && heads <= 8) {
+  if (maxT <= 128 && heads <= 8) {
     const size_t lds = (size_t)2 * ((maxT + 15) & ~15) * 64 * 4;   // K and V of four heads: 64 KB at 128 tokens
     allow_big_lds((const void*)k_attention_mfma<15>, 64 * 1024);
     RT_LAUNCH(k_attention_mfma<15>, dim3((unsigned)n_img), dim3(512), lds, st, qkv, geom, heads, out);
     return;
   }
-  if (g_attention_line && (heads * hd) % 4 == 0 && heads <= 8) {
+  if ((heads * hd) % 4 == 0 && heads <= 8) {
     const size_t lds = (size_t)2 * 64 * heads * 16 * 4;   // 64 KB at 8 heads
     allow_big_lds((const void*)k_attention_line<15>, 64 * 1024);
     RT_LAUNCH(k_attention_line<15>, dim3((unsigned)n_img), dim3(256), lds, st, qkv, geom, heads, out);

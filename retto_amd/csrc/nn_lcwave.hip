@@ -433,9 +433,6 @@ static int lc_wave_code(int sh, int sw, int Cp, int Npad16) {
     if (gq == 2 && nt == 4) return 2;   // 32 -> 64
     if (gq == 3 && nt == 3) return 3;   // 48 -> 48
     if (gq == 4 && nt == 4) return 4;   // 64 -> 64
-    // 128 -> 128 in two blocks of 64 output channels: 1.35 vs 1.56 ms on uniform images, but 1.69 vs 1.52 ms on the ragged C3
-    // batch (every block recomputes the depthwise half): opt-in (RT_LC_WAVE=5)
-    if (gq == 8 && nt == 8 && g_lc_wave == 5) return 9;
   } else if (sh == 2 && sw == 2) {
     if (gq == 2 && nt == 3) return 6;   // 32 -> 48
     if (gq == 3 && nt == 6) return 7;   // 48 -> 96
@@ -457,17 +454,15 @@ void lc_wave(hipStream_t st, int sh, int sw, const float* x, const ImgGeom* gin,
              const float* Wp, int N, int Npad16, float* y, int ldy, const Epilogue& epi) {
   if (n_img <= 0) return;
   if (!lc_wave_supported(3, sh, sw, Cp, C, N, Npad16, dw_act, dw_has_lab, epi)) throw RtError(8, "lc_wave: unsupported block (check lc_wave_supported)");
-  static const int tpw_env = getenv("RT_LCW_TPW") ? atoi(getenv("RT_LCW_TPW")) : 0;
-  static const int mt_env = getenv("RT_LCW_MT") ? atoi(getenv("RT_LCW_MT")) : 0;
   const int code = lc_wave_code(sh, sw, Cp, Npad16);
-  const int tpw = tpw_env > 0 ? tpw_env : 4;
+  const int tpw = 4;   // tiles per wave
   if (g_lc_wave >= 3 || code >= 6) {   // (the direct-load form below is kept for the stride-1 blocks only: A/B, RT_LC_WAVE=1)
     // LDS-staged form: 4-row tiles at stride 1 (2 waves per SIMD), 2-row tiles at stride 2
-    const int mtl = (sh == 1 && mt_env != 2) ? 4 : 2;
+    const int mtl = sh == 1 ? 4 : 2;
     const int tiles = ((maxWo + 15) / 16) * ((maxHo + mtl - 1) / mtl);
     dim3 grid((tiles + 4 * tpw - 1) / (4 * tpw), n_img);
     LcwArgs a{x, gin, gout, Wd, bd, Wp, epi.bias, y, dw_a, dw_c, epi.has_lab ? epi.lab_a : 1.f, epi.has_lab ? epi.lab_c : 0.f, Npad16, ldy, tpw};
-#define RT_LCL(GG, NN) do { if (mtl == 2) RT_LAUNCH((k_lc_lds<GG, NN, 2, 1, 1, true, 3>), grid, dim3(256), 0, st, a); else RT_LAUNCH((k_lc_lds<GG, NN, 4, 1, 1, true, 2>), grid, dim3(256), 0, st, a); } while (0)
+#define RT_LCL(GG, NN) RT_LAUNCH((k_lc_lds<GG, NN, 4, 1, 1, true, 2>), grid, dim3(256), 0, st, a)
     switch (code) {
       case 1: RT_LCL(1, 2); break;
       case 2: RT_LCL(2, 4); break;
@@ -475,27 +470,23 @@ void lc_wave(hipStream_t st, int sh, int sw, const float* x, const ImgGeom* gin,
       case 4: RT_LCL(4, 4); break;
       case 6: RT_LAUNCH((k_lc_lds<2, 3, 2, 2, 2, false, 2>), grid, dim3(256), 0, st, a); break;
       case 7: RT_LAUNCH((k_lc_lds<3, 6, 2, 2, 2, false, 2>), grid, dim3(256), 0, st, a); break;
-      case 9: grid.z = 2; RT_LAUNCH((k_lc_lds<8, 4, 4, 1, 1, true, 2>), grid, dim3(256), 0, st, a); break;
       default: RT_LAUNCH((k_lc_lds<4, 8, 2, 2, 1, true, 2>), grid, dim3(256), 0, st, a); break;
     }
 #undef RT_LCL
     return;
   }
-  const int mt = mt_env == 1 ? 1 : 2;
-  const int tiles = ((maxWo + 15) / 16) * ((maxHo + mt - 1) / mt);
+  const int tiles = ((maxWo + 15) / 16) * ((maxHo + 1) / 2);   // 2-row tiles
   dim3 grid((tiles + 4 * tpw - 1) / (4 * tpw), n_img);
   LcwArgs a{x, gin, gout, Wd, bd, Wp, epi.bias, y, dw_a, dw_c, epi.has_lab ? epi.lab_a : 1.f, epi.has_lab ? epi.lab_c : 0.f, Npad16, ldy, tpw};
-#define RT_LCW_T(GG, NN, MM, SS) RT_LAUNCH((k_lc_wave<GG, NN, MM, true>), grid, dim3(256), 0, st, a)
-#define RT_LCW(GG, NN, SS) do { if (mt == 1) RT_LCW_T(GG, NN, 1, SS); else RT_LCW_T(GG, NN, 2, SS); } while (0)
+#define RT_LCW(GG, NN) RT_LAUNCH((k_lc_wave<GG, NN, 2, true>), grid, dim3(256), 0, st, a)
   switch (code) {
-    case 1: RT_LCW(1, 2, 1); break;
-    case 2: RT_LCW(2, 4, 1); break;
-    case 3: RT_LCW(3, 3, 1); break;
-    case 4: RT_LCW(4, 4, 1); break;
+    case 1: RT_LCW(1, 2); break;
+    case 2: RT_LCW(2, 4); break;
+    case 3: RT_LCW(3, 3); break;
+    case 4: RT_LCW(4, 4); break;
     default: throw RtError(8, "lc_wave: unsupported shape (check lc_wave_supported)");
   }
 #undef RT_LCW
-#undef RT_LCW_T
 }
 
 }  // namespace nn

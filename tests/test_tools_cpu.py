@@ -36,6 +36,21 @@ def test_pmc_summary_families_know_the_current_kernel_names(tmp_path):
     assert abs(k["family:conv16_3x3"]["sq"]["mfma_util"] - 0.5) < 1e-6      # 512000 / (1024 SIMDs x 8000 / 8)
 
 
+def test_pmc_summary_families_know_the_gemm_names_without_the_timing_argument(tmp_path):
+    names = ["void rt::nn::k_gemm32p<2, 1, true, false>(rt::nn::GemmPArgs)", "void rt::nn::k_gemm32p<2, 1, false, true>(rt::nn::GemmPArgs)",
+             "void rt::nn::k_gemm32p<-1, -1, true, false>(rt::nn::GemmPArgs)",
+             "void rt::nn::k_gemm_split<2, 1, false>(rt::nn::GemmSArgs)", "void rt::nn::k_gemm_split<2, 1, true>(rt::nn::GemmSArgs)"]
+    f, w = tmp_path / "f.csv", tmp_path / "w.csv"
+    _write(f, [(n, "FETCH_SIZE", 1000, 0, 100) for n in names])
+    _write(w, [(n, "WRITE_SIZE", 500, 0, 100) for n in names])
+    out = tmp_path / "o.json"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "pmc_summary.py"), str(f), str(w), str(out)], capture_output=True, text=True, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-1500:]
+    k = json.load(open(out))["kernels"]
+    for fam, members in (("family:gemm32p", 2), ("family:gemm32p_se", 1), ("family:gemm_split", 1), ("family:gemm_split_se", 1)):
+        assert fam in k and len(k[fam]["members"]) == members, (fam, k.get(fam))
+
+
 def test_pmc_det_bytes_sums_the_det_launches_only(tmp_path):
     det = ["void rt::nn::k_stem_mfma<1>(rt::nn::StemArgs)", "void rt::nn::k_lc_lds<2, 3, 2, 2, 2, false, 2>(rt::nn::LcwArgs)", "void rt::nn::k_fpn_phase<6, 1, 1>(rt::nn::FpnArgs)"]
     other = ["rt::pp::k_ccl_rows(rt::pp::DbPage const*, float, int)", "rt::pp::k_contour_boxes(rt::pp::DbPage const*, rt::pp::DbParams)", "__amd_rocclr_copyBuffer", "rt::pp::k_sum_partial(float const*, long long, double*)"]
