@@ -106,6 +106,10 @@ typedef struct rt_config {
   int32_t dtype;              /* rt_dtype: arithmetic of the three networks.  RT_DTYPE_F32 (default) = what the reference's
                                  ort-CPU path computes in; RT_DTYPE_F16 = fp16 storage / MFMA, fp32 accumulation
                                  (BASELINE.json config 5).  The PP-OCRv4 server graphs are built in fp16 only. */
+  int32_t det_score_mode;     /* 0 = Fast (default), 1 = Slow: DetProcessorConfig::score_mode (det_processor.rs:22-31,69).  Slow
+                                 scores a box by the mean over the contour's own polygon (its full point chain) instead of its
+                                 min-area rect, as the field's doc comment specifies; the reference itself never reads the field
+                                 and computes Fast either way.  rt_create rejects other values with RT_ERR_INVALID. */
 } rt_config;
 typedef enum rt_dtype { RT_DTYPE_F32 = 0, RT_DTYPE_F16 = 1 } rt_dtype;
 

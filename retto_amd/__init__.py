@@ -88,6 +88,7 @@ class DetProcessorConfig:  # det_processor.rs:44-93
     use_dilation: bool = True
     min_mini_box_size: int = 3
     dilation_kernel: Optional[np.ndarray] = field(default_factory=lambda: np.ones((2, 2), np.uint64))
+    score_mode: str = "Fast"  # ScoreMode (det_processor.rs:22-31): "Fast" = min-area rect, "Slow" = the contour's own polygon
 
 
 @dataclass
@@ -218,6 +219,9 @@ class _Handle:
             if k.shape != (2, 2) or not np.all(k != 0):
                 raise InvalidArgument("only the reference's default 2x2 all-ones dilation kernel (or None) is supported")
             c.det_dilation = 1
+        if d.score_mode not in ("Fast", "Slow"):
+            raise InvalidArgument("score_mode must be 'Fast' or 'Slow'")
+        c.det_score_mode = 1 if d.score_mode == "Slow" else 0
         cl, rc = cfg.cls_processor_config, cfg.rec_processor_config
         for i in range(3):
             c.cls_image_shape[i] = cl.image_shape[i]; c.rec_image_shape[i] = rc.image_shape[i]

@@ -31,6 +31,8 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--batch", type=int, default=32, help="pages per rt_run_batch call")
     ap.add_argument("--synthetic", action="store_true", help="seeded synthetic weights + dictionary instead of model files")
     ap.add_argument("--json", default=None, help="write one JSON object per image (det/cls/rec stage results)")
+    ap.add_argument("--det-score-mode", choices=["Fast", "Slow"], default="Fast",
+                    help="DetProcessorConfig.score_mode: box score over the min-area rect (Fast) or the contour's own polygon (Slow)")
     return ap
 
 
@@ -56,6 +58,7 @@ def main(argv=None) -> int:
         cfg.worker_config = retto_amd.RettoHipWorkerConfig(device=a.device_id, models=retto_amd.RettoWorkerModelProvider(
             det=S.Path(a.det_model_path), rec=S.Path(a.rec_model_path), cls=S.Path(a.cls_model_path)))
         cfg.rec_processor_config.character_source = S.Path(a.rec_keys_path)
+    cfg.det_processor_config.score_mode = a.det_score_mode
     session = retto_amd.RettoSession(cfg)
     files = walk_files(a.images)
     log.info("Found %d files, processing...", len(files))

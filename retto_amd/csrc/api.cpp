@@ -99,6 +99,7 @@ void rt_config_default(rt_config* c) {
   c->rec_image_shape[0] = 3; c->rec_image_shape[1] = 48; c->rec_image_shape[2] = 320;
   c->rec_batch_num = 6;
   c->max_boxes_per_page = 0; c->det_sub_batch = 0; c->lanes = 0; c->dtype = RT_DTYPE_F32;
+  c->det_score_mode = 0;
 }
 
 int rt_create(const rt_config* cfg, rt_session** out) {
@@ -114,6 +115,7 @@ int rt_create(const rt_config* cfg, rt_session** out) {
   RT_REQUIRE(cfg->dtype == RT_DTYPE_F32 || cfg->dtype == RT_DTYPE_F16, (rt_session*)nullptr, "dtype must be RT_DTYPE_F32 or RT_DTYPE_F16");
   RT_REQUIRE(cfg->max_boxes_per_page >= 0 && cfg->max_boxes_per_page <= 65536, (rt_session*)nullptr,
              "max_boxes_per_page must be in [0, 65536]");
+  RT_REQUIRE(cfg->det_score_mode == 0 || cfg->det_score_mode == 1, (rt_session*)nullptr, "det_score_mode must be 0 (Fast) or 1 (Slow)");
   capture_variant_defaults();
   return guarded(nullptr, [&] { *out = rt_session_create(cfg); });
 }

@@ -18,13 +18,15 @@ struct Contour { int root, type, ymin, rows, base, hbase; };
 struct DbWs {
   u8* mask; u8* outside;
   int *parent, *ymin, *ymax, *cidx;
-  int* counters;  // 0 nContours 1 rowUsed 2 hullUsed 3 nCand 4 overflow
+  int* counters;  // 0 nContours 1 rowUsed 2 hullUsed 3 nCand 4 overflow 5 nBig (score_mode Slow)
   Contour* contours; int contour_cap;
   int *rowmin, *rowmax; int row_cap;
   int2* hull; int hull_cap;
   DbBox* cand; int cand_cap;
   unsigned *sort_a, *sort_b;   // index runs of the reading-order sort when a page has more candidates than fit in LDS
   float *sort_cx, *sort_cy;
+  // score_mode Slow only (empty in Fast): contours too large for LDS, and the P / N planes of k_contour_boxes_slow_big
+  int* big; unsigned* slow_bits; size_t slow_slot_words;
 };
 struct DbPage {
   const float* pred; int H, W, ori_h, ori_w;
@@ -33,7 +35,9 @@ struct DbPage {
 };
 
 static inline size_t al256(size_t v) { return (v + 255) & ~(size_t)255; }
-static DbWs carve(void* base, int H, int W, int max_boxes, size_t* total) {
+__host__ __device__ __forceinline__ int slow_pitch(int w) { return 2 * ((w + 63) >> 6); }   // words per row of a P / N plane
+#define RT_SLOW_BIG_BLOCKS 4
+static DbWs carve(void* base, int H, int W, int max_boxes, int slow, size_t* total) {
   size_t N = (size_t)H * W, o = 0;
   DbWs ws;
   char* b = (char*)base;
@@ -51,10 +55,14 @@ static DbWs carve(void* base, int H, int W, int max_boxes, size_t* total) {
   ws.cand = (DbBox*)take((size_t)max_boxes * sizeof(DbBox));
   ws.sort_a = (unsigned*)take((size_t)max_boxes * 4); ws.sort_b = (unsigned*)take((size_t)max_boxes * 4);
   ws.sort_cx = (float*)take((size_t)max_boxes * 4); ws.sort_cy = (float*)take((size_t)max_boxes * 4);
+  // Slow: one entry per contour at most; RT_SLOW_BIG_BLOCKS slots of two page-sized bit planes (a frame lies inside the page)
+  ws.slow_slot_words = slow ? (size_t)2 * slow_pitch(W) * H : 0;
+  ws.big = (int*)take(slow ? (size_t)ws.contour_cap * 4 : 0);
+  ws.slow_bits = (unsigned*)take((size_t)RT_SLOW_BIG_BLOCKS * ws.slow_slot_words * 4);
   *total = o;
   return ws;
 }
-size_t db_workspace_bytes(int H, int W, int max_boxes) { size_t t; carve(nullptr, H, W, max_boxes, &t); return t; }
+size_t db_workspace_bytes(int H, int W, int max_boxes, int score_mode) { size_t t; carve(nullptr, H, W, max_boxes, score_mode, &t); return t; }
 size_t db_page_desc_bytes() { return sizeof(DbPage); }
 
 __device__ __forceinline__ int uf_find(const int* parent, int x) {
@@ -750,6 +758,38 @@ __device__ __forceinline__ float euclid_f32(float ax, float ay, float bx, float 
 }
 
 
+// det_processor.rs:306-321, everything after the score test: unclip, second min-area rect, size filters, scale to the page,
+// append to the page's candidate list (k_contour_boxes and the score_mode Slow kernels)
+__device__ __forceinline__ void emit_box(const DbPage& pg, const DbParams& prm, const Contour& ct, const int* box, float mean_score) {
+  const DbWs& ws = pg.ws;
+  const int H = pg.H, W = pg.W;
+  float ox[RT_MAX_OFFSET_PTS], oy[RT_MAX_OFFSET_PTS];
+  short hidx[RT_MAX_OFFSET_PTS];
+  int ovf = 0;
+  int on = unclip_box(box, prm.unclip_ratio, ox, oy, &ovf);
+  if (ovf) { ws.counters[4] = 1; return; }
+  if (on == 0) return;
+  int h2 = hull_jarvis(ox, oy, on, hidx);
+  double r2[8];
+  min_area_rect_hull(h2, [&](int i) { return DP{(double)ox[hidx[i]], (double)oy[hidx[i]]}; }, r2);
+  DbBox b;
+  for (int i = 0; i < 8; i++) b.pts[i] = (float)r2[i];
+  float t1 = euclid_f32(b.pts[0], b.pts[1], b.pts[2], b.pts[3]);
+  float t2 = euclid_f32(b.pts[6], b.pts[7], b.pts[4], b.pts[5]);
+  if (fminf(t1, t2) < (float)(prm.min_size + 2)) return;
+  gm::scale_and_clip(b.pts, (double)W, (double)H, (double)pg.ori_w, (double)pg.ori_h);
+  float pb_h = gm::side_len(&b.pts[0], &b.pts[6]);
+  float pb_w = gm::side_len(&b.pts[0], &b.pts[2]);
+  if (pb_h <= 3.0f || pb_w <= 3.0f) return;
+  b.score = mean_score;
+  b.key = ct.type == 0 ? ct.root : ct.root - 1;
+  if ((threadIdx.x & 63) == 0) {
+    int slot = atomicAdd(&ws.counters[3], 1);
+    if (slot >= ws.cand_cap) ws.counters[4] = 1;
+    else ws.cand[slot] = b;
+  }
+}
+
 #define RT_CONTOUR_WAVES 128
 __global__ __launch_bounds__(64) void k_contour_boxes(const DbPage* __restrict__ pages, DbParams prm) {
   const DbPage pg = pages[blockIdx.y];
@@ -772,31 +812,239 @@ __global__ __launch_bounds__(64) void k_contour_boxes(const DbPage* __restrict__
   if (sside < (float)prm.min_size) continue;
   float mean_score = box_score_fast(pred, H, W, box);
   if (mean_score < prm.box_thresh) continue;
-  float ox[RT_MAX_OFFSET_PTS], oy[RT_MAX_OFFSET_PTS];
-  short hidx[RT_MAX_OFFSET_PTS];
-  int ovf = 0;
-  int on = unclip_box(box, prm.unclip_ratio, ox, oy, &ovf);
-  if (ovf) { ws.counters[4] = 1; continue; }
-  if (on == 0) continue;
-  int h2 = hull_jarvis(ox, oy, on, hidx);
-  double r2[8];
-  min_area_rect_hull(h2, [&](int i) { return DP{(double)ox[hidx[i]], (double)oy[hidx[i]]}; }, r2);
-  DbBox b;
-  for (int i = 0; i < 8; i++) b.pts[i] = (float)r2[i];
-  float t1 = euclid_f32(b.pts[0], b.pts[1], b.pts[2], b.pts[3]);
-  float t2 = euclid_f32(b.pts[6], b.pts[7], b.pts[4], b.pts[5]);
-  if (fminf(t1, t2) < (float)(prm.min_size + 2)) continue;
-  gm::scale_and_clip(b.pts, (double)W, (double)H, (double)pg.ori_w, (double)pg.ori_h);
-  float pb_h = gm::side_len(&b.pts[0], &b.pts[6]);
-  float pb_w = gm::side_len(&b.pts[0], &b.pts[2]);
-  if (pb_h <= 3.0f || pb_w <= 3.0f) continue;
-  b.score = mean_score;
-  b.key = ct.type == 0 ? ct.root : ct.root - 1;
-  if ((threadIdx.x & 63) == 0) {
-    int slot = atomicAdd(&ws.counters[3], 1);
-    if (slot >= ws.cand_cap) ws.counters[4] = 1;
-    else ws.cand[slot] = b;
+  emit_box(pg, prm, ct, box, mean_score);
   }
+}
+
+// ---- score_mode Slow: the mean over the contour's own polygon ------------------------
+// DetProcessorConfig::score_mode (det_processor.rs:22-31,69) documents Slow as the mean score "based on all pixels within the
+// original polygon ... relatively slow but more accurate".  The reference declares the field but never reads it: its binary
+// computes Fast when asked for Slow.  Here Slow follows the doc comment: box_score_fast (det_processor.rs:188-221) applied to
+// the contour's full point chain instead of the 4 corners of its min-area rect -- canvas = bounding box of the chain,
+// imageproc draw_polygon_mut over the closed chain, sequential f32 mean; a one-point chain scores 0 (as SURVEY A.4 fixes for
+// the 4-point form).
+//
+// What the kernels rely on (tests/test_score_mode_cpu.py checks each against find_contours):
+//  * a chain is rebuilt from the mask alone: the border-following step only asks whether a pixel is nonzero (the labels
+//    find_contours writes steer discovery, not the trace), so every chain is traced on its own, in parallel.  Start = the
+//    component's root entered from W (outer border), or the pixel left of the hole's root entered from E (hole border);
+//  * consecutive chain points (and last / first) are 8-adjacent: an edge spans at most one row, so draw_polygon_mut never
+//    interpolates -- every intersection is a chain point's x -- and its Bresenham outline is the set of chain points.  With a
+//    row's intersections sorted x0 <= x1 <= ... and [x0,x1], [x2,x3], ... filled, pixel x is covered iff an odd number of
+//    intersections lie left of it or it is a chain point.  The trace records per pixel the parity of its intersection count
+//    (plane P) and whether it is a chain point (plane N); the fill is then a prefix xor along each row;
+//  * the chain lies inside the bounding box of the contour's row extents (its convex hull is the one k_contour_boxes builds
+//    from them).  A point outside it would be reported as an overflow (RT_ERR_CAPACITY), never dropped.
+// Nothing of the chain is stored.  A contour whose frame (mask with a 1-pixel margin, P and N, one bit per pixel each) fits in
+// RT_SLOW_LDS_WORDS is done in LDS by k_contour_boxes_slow: every text line of a 960- or 1984-wide page.  Larger ones go to
+// k_contour_boxes_slow_big, whose RT_SLOW_BIG_BLOCKS workgroups per page each own a page-sized P + N slot of the workspace
+// (db_workspace_bytes with score_mode 1) and read the mask from global memory.
+#define RT_SLOW_LDS_WORDS 12288   // 48 KB
+
+struct SlowFrame { int x0, y0, w, h; };   // bounding box of the chain, image coordinates
+
+// bounding box of the contour's row extents (rows dealt over the lanes); false when it has none
+__device__ bool contour_frame(const DbWs& ws, const Contour& ct, SlowFrame& f) {
+  int top = 0x7fffffff, bot = -1, xl = 0x7fffffff, xr = -1;
+  for (int r = (int)(threadIdx.x & 63); r < ct.rows; r += 64) {
+    const int hi = ws.rowmax[ct.base + r];
+    if (hi < 0) continue;
+    top = min(top, r); bot = max(bot, r);
+    xl = min(xl, ws.rowmin[ct.base + r]); xr = max(xr, hi);
+  }
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) {
+    top = min(top, __shfl_xor(top, d)); bot = max(bot, __shfl_xor(bot, d));
+    xl = min(xl, __shfl_xor(xl, d)); xr = max(xr, __shfl_xor(xr, d));
+  }
+  if (bot < 0) return false;
+  f.x0 = xl; f.y0 = ct.ymin + top; f.w = xr - xl + 1; f.h = bot - top + 1;
+  return true;
+}
+// words per row of the staged mask (slow_pitch: of P / N -- whole 64-bit chunks, the score pass reads one per 64 lanes)
+__device__ __forceinline__ int slow_mask_pitch(int w) { return 2 * ((w + 2 + 63) >> 6); }
+// (+1: LdsMask::row3 reads the word after a 3-bit group's own, which for the last staged row lies past the plane)
+__device__ __forceinline__ int slow_lds_words(const SlowFrame& f) { return slow_mask_pitch(f.w) * (f.h + 2) + 1 + 2 * slow_pitch(f.w) * f.h; }
+
+// The 8-neighbour ring of (x, y) as one bit per direction, W NW N NE E SE S SW (find_contours' order; bit d = direction d).
+__device__ __forceinline__ int ring_bits(int top, int mid, int bot) {   // 3-bit rows: bit 0 = column x - 1, bit 2 = x + 1
+  return (mid & 1) | ((top & 1) << 1) | (((top >> 1) & 1) << 2) | (((top >> 2) & 1) << 3) | (((mid >> 2) & 1) << 4) |
+         (((bot >> 2) & 1) << 5) | (((bot >> 1) & 1) << 6) | ((bot & 1) << 7);
+}
+struct LdsMask {   // the frame's mask in LDS, staged with a 1-pixel margin (pixels off the page are 0)
+  const unsigned* m; int pitch, sx0, sy0;   // image coordinates of staged column 0 / row 0
+  __device__ __forceinline__ int row3(int r, int b) const {
+    const unsigned* w = m + r * pitch + (b >> 5);
+    const unsigned long long v = (unsigned long long)w[0] | ((unsigned long long)w[1] << 32);
+    return (int)(v >> (b & 31)) & 7;
+  }
+  __device__ __forceinline__ int ring(int x, int y) const {
+    const int b = x - 1 - sx0, r = y - sy0;
+    return ring_bits(row3(r - 1, b), row3(r, b), row3(r + 1, b));
+  }
+};
+struct GlobalMask {   // the page's mask in global memory (u8, 0 / 255)
+  const u8* m; int H, W;
+  __device__ __forceinline__ int px(int x, int y) const { return x >= 0 && y >= 0 && x < W && y < H && m[(size_t)y * W + x] ? 1 : 0; }
+  __device__ __forceinline__ int ring(int x, int y) const {
+    return ring_bits(px(x - 1, y - 1) | (px(x, y - 1) << 1) | (px(x + 1, y - 1) << 2), px(x - 1, y) | (px(x + 1, y) << 2),
+                     px(x - 1, y + 1) | (px(x, y + 1) << 1) | (px(x + 1, y + 1) << 2));
+  }
+};
+
+// Trace the chain of `ct` (find_contours' border following, retto_oracle.cpp find_contours) and record P / N for its polygon
+// fill.  Every lane runs the (wave-uniform) trace; lane 0 alone writes the planes.  Returns the number of chain points, or
+// -1 when a point leaves the frame or the trace exceeds its bound (neither happens: see the header).
+template <class Mask>
+__device__ int trace_chain(const Mask& mk, unsigned* P, unsigned* N, int pitch, const SlowFrame& f, const Contour& ct, int W) {
+  const int dx[8] = {-1, -1, 0, 1, 1, 1, 0, -1}, dy[8] = {0, -1, -1, -1, 0, 1, 1, 1};
+  const bool writer = (threadIdx.x & 63) == 0;
+  auto at = [&](int x, int y) { return (y - f.y0) * pitch + ((x - f.x0) >> 5); };
+  auto bit = [&](int x) { return 1u << ((x - f.x0) & 31); };
+  auto toggle = [&](int x, int y) { if (writer) P[at(x, y)] ^= bit(x); };
+  auto edge = [&](int px, int py, int qx, int qy) {   // intersections of edge p -> q (|qy - py| <= 1), draw_polygon_mut's rules
+    if (py == qy) { toggle(px, py); toggle(qx, qy); }
+    else if (qy > py) toggle(px, py);
+    else toggle(qx, qy);
+  };
+  const int start = ct.type == 0 ? ct.root : ct.root - 1;
+  const int cx = start % W, cy = start / W;
+  int r = mk.ring(cx, cy);
+  if (r == 0) return 1;   // isolated pixel: a one-point chain
+  int d = ct.type == 0 ? 0 : 4;   // enter from W (outer) / E (hole); the first nonzero neighbour clockwise from there
+  while (!((r >> d) & 1)) d = (d + 1) & 7;
+  const int p1x = cx + dx[d], p1y = cy + dy[d];
+  int x = cx, y = cy, dv = d, lx = 0, ly = 0, n = 0;
+  const long long limit = 8ll * f.w * f.h + 8;   // (pixel, entry direction) states: the trace is a cycle through distinct ones
+  while (true) {
+    if (x < f.x0 || y < f.y0 || x >= f.x0 + f.w || y >= f.y0 + f.h || n > limit) return -1;
+    if (writer) N[at(x, y)] |= bit(x);
+    if (n > 0) edge(lx, ly, x, y);
+    lx = x; ly = y; n++;
+    r = mk.ring(x, y);
+    int d4 = (dv + 7) & 7;   // counter-clockwise from the previous point
+    while (!((r >> d4) & 1)) d4 = (d4 + 7) & 7;
+    const int nx = x + dx[d4], ny = y + dy[d4];
+    if (nx == cx && ny == cy && x == p1x && y == p1y) break;
+    dv = (d4 + 4) & 7;
+    x = nx; y = ny;
+  }
+  edge(lx, ly, cx, cy);   // closing edge, last -> first
+  return n;
+}
+
+// box_score_fast's mean over the filled chain polygon: canvas = the frame, row-major; per row the 64 lanes take 64
+// consecutive pixels, the covered ones are folded into `sum` one lane at a time (the same fold as box_score_fast).
+__device__ float slow_mean(const float* pred, int W, const SlowFrame& f, const unsigned* P, const unsigned* N, int pitch) {
+  const int lane = threadIdx.x & 63;
+  const unsigned long long below = (1ull << lane) - 1ull;
+  float sum = 0.0f; unsigned long long count = 0;
+  for (int y = 0; y < f.h; y++) {
+    const float* prow = pred + (size_t)(y + f.y0) * W + f.x0;
+    const unsigned* prw = P + y * pitch;
+    const unsigned* nrw = N + y * pitch;
+    int par = 0;   // parity of the intersections left of the current 64-pixel chunk
+    for (int x0 = 0; x0 < f.w; x0 += 64) {
+      const int x = x0 + lane, wi = (x0 >> 5) + (lane >> 5), b = lane & 31;
+      const bool inside = x < f.w;
+      const bool pb = inside && ((prw[wi] >> b) & 1u), nb = inside && ((nrw[wi] >> b) & 1u);
+      const unsigned long long pm = __ballot(pb);
+      const bool in = inside && (nb || ((par ^ __popcll(pm & below)) & 1));
+      par ^= __popcll(pm) & 1;
+      const float v = in ? prow[x] : 0.0f;
+      const unsigned long long m = __ballot(in);
+      if (m == 0) continue;   // (wave-uniform)
+      count += (unsigned long long)__popcll(m);
+      const int vb = __float_as_int(v);
+#pragma unroll
+      for (int l = 0; l < 64; l++) sum = sum + __int_as_float(__builtin_amdgcn_readlane(vb, l));
+    }
+  }
+  return count > 0 ? sum / (float)count : 0.0f;
+}
+
+// min-area rect + sside filter of one contour (k_contour_boxes' first steps); false when the contour is dropped
+__device__ __forceinline__ bool contour_rect(const DbWs& ws, const Contour& ct, const DbParams& prm, int* box) {
+  int2* hs = ws.hull + ct.hbase;
+  const int hn = hull_from_rows(ws.rowmin + ct.base, ws.rowmax + ct.base, ct.rows, ct.ymin, hs);
+  if (hn == 0) return false;
+  double r[8];
+  min_area_rect_hull(hn, [&](int i) { return DP{(double)hs[i].x, (double)hs[i].y}; }, r);
+  for (int i = 0; i < 8; i++) box[i] = (int)r[i];
+  const float s1 = euclid_f32((float)box[0], (float)box[1], (float)box[2], (float)box[3]);
+  const float s2 = euclid_f32((float)box[6], (float)box[7], (float)box[4], (float)box[5]);
+  return !(fminf(s1, s2) < (float)prm.min_size);
+}
+
+// Contours whose frame fits in LDS (the others: k_contour_boxes_slow_big).  Same grid as k_contour_boxes.
+__global__ __launch_bounds__(64) void k_contour_boxes_slow(const DbPage* __restrict__ pages, DbParams prm) {
+  __shared__ unsigned lds[RT_SLOW_LDS_WORDS];
+  const DbPage pg = pages[blockIdx.y];
+  const DbWs& ws = pg.ws;
+  const int H = pg.H, W = pg.W, lane = threadIdx.x & 63;
+  const int ncont = min(ws.counters[0], ws.contour_cap);
+  for (int ci = blockIdx.x; ci < ncont; ci += RT_CONTOUR_WAVES) {
+    const Contour ct = ws.contours[ci];
+    SlowFrame f;
+    if (!contour_frame(ws, ct, f)) continue;
+    if (slow_lds_words(f) > RT_SLOW_LDS_WORDS) {   // -> k_contour_boxes_slow_big (each contour once: the list cannot overflow)
+      if (lane == 0) ws.big[atomicAdd(&ws.counters[5], 1)] = ci;
+      continue;
+    }
+    int box[8];
+    if (!contour_rect(ws, ct, prm, box)) continue;
+    const int mp = slow_mask_pitch(f.w), pp = slow_pitch(f.w);
+    unsigned* M = lds;
+    unsigned* P = lds + mp * (f.h + 2) + 1;
+    unsigned* N = P + pp * f.h;
+    __syncthreads();   // (the previous contour's score pass has read the planes)
+    for (int i = lane; i < 2 * pp * f.h; i += 64) P[i] = 0u;
+    // stage the mask of the frame plus a 1-pixel margin, 64 pixels per ballot
+    for (int sy = 0; sy < f.h + 2; sy++) {
+      const int y = f.y0 - 1 + sy;
+      for (int c = 0; c < mp; c += 2) {
+        const int sx = 32 * c + lane, x = f.x0 - 1 + sx;
+        const bool on = sx < f.w + 2 && y >= 0 && y < H && x >= 0 && x < W && ws.mask[(size_t)y * W + x];
+        const unsigned long long b = __ballot(on);
+        if (lane < 2) M[sy * mp + c + lane] = (unsigned)(b >> (32 * lane));
+      }
+    }
+    __syncthreads();
+    const int n = trace_chain(LdsMask{M, mp, f.x0 - 1, f.y0 - 1}, P, N, pp, f, ct, W);
+    __syncthreads();
+    if (n < 0) { if (lane == 0) ws.counters[4] = 1; continue; }
+    const float mean_score = n == 1 ? 0.0f : slow_mean(pg.pred, W, f, P, N, pp);
+    if (mean_score < prm.box_thresh) continue;
+    emit_box(pg, prm, ct, box, mean_score);
+  }
+}
+
+// The contours k_contour_boxes_slow listed as too large for LDS: P / N in this workgroup's slot of the page's workspace, the
+// mask read from global memory.
+__global__ __launch_bounds__(64) void k_contour_boxes_slow_big(const DbPage* __restrict__ pages, DbParams prm) {
+  const DbPage pg = pages[blockIdx.y];
+  const DbWs& ws = pg.ws;
+  const int H = pg.H, W = pg.W, lane = threadIdx.x & 63;
+  const int nbig = ws.counters[5];
+  unsigned* P = ws.slow_bits + (size_t)blockIdx.x * ws.slow_slot_words;
+  for (int k = blockIdx.x; k < nbig; k += RT_SLOW_BIG_BLOCKS) {
+    const Contour ct = ws.contours[ws.big[k]];
+    SlowFrame f;
+    contour_frame(ws, ct, f);
+    int box[8];
+    if (!contour_rect(ws, ct, prm, box)) continue;
+    const int pp = slow_pitch(f.w);
+    if ((size_t)2 * pp * f.h > ws.slow_slot_words) { if (lane == 0) ws.counters[4] = 1; continue; }   // (frames lie inside the page)
+    unsigned* N = P + pp * f.h;
+    __syncthreads();
+    for (int i = lane; i < 2 * pp * f.h; i += 64) P[i] = 0u;
+    __syncthreads();
+    const int n = trace_chain(GlobalMask{ws.mask, H, W}, P, N, pp, f, ct, W);
+    __syncthreads();
+    if (n < 0) { if (lane == 0) ws.counters[4] = 1; continue; }
+    const float mean_score = n == 1 ? 0.0f : slow_mean(pg.pred, W, f, P, N, pp);
+    if (mean_score < prm.box_thresh) continue;
+    emit_box(pg, prm, ct, box, mean_score);
   }
 }
 
@@ -902,7 +1150,7 @@ void db_postprocess_batch(hipStream_t st, int n, const DbPageIn* in, const DbPar
   for (int i = 0; i < n; i++) {
     size_t total;
     hp[i].pred = in[i].pred; hp[i].H = in[i].H; hp[i].W = in[i].W; hp[i].ori_h = in[i].ori_h; hp[i].ori_w = in[i].ori_w;
-    hp[i].ws = carve(workspaces[i], in[i].H, in[i].W, max_boxes, &total);
+    hp[i].ws = carve(workspaces[i], in[i].H, in[i].W, max_boxes, p.score_mode, &total);
     hp[i].boxes_out = boxes_out[i]; hp[i].count_out = count_out[i];
     maxN = std::max(maxN, in[i].H * in[i].W); maxH = std::max(maxH, in[i].H);
     maxC = std::max(maxC, hp[i].ws.contour_cap);
@@ -919,7 +1167,12 @@ void db_postprocess_batch(hipStream_t st, int n, const DbPageIn* in, const DbPar
   RT_LAUNCH(k_contour_alloc, grid, blk, 0, st, dp);
   RT_LAUNCH(k_row_extents, grid, blk, 0, st, dp);
   (void)maxC;
-  RT_LAUNCH(k_contour_boxes, dim3(RT_CONTOUR_WAVES, n), dim3(64), 0, st, dp, p);
+  if (p.score_mode == 0) {
+    RT_LAUNCH(k_contour_boxes, dim3(RT_CONTOUR_WAVES, n), dim3(64), 0, st, dp, p);
+  } else {
+    RT_LAUNCH(k_contour_boxes_slow, dim3(RT_CONTOUR_WAVES, n), dim3(64), 0, st, dp, p);
+    RT_LAUNCH(k_contour_boxes_slow_big, dim3(RT_SLOW_BIG_BLOCKS, n), dim3(64), 0, st, dp, p);
+  }
   RT_LAUNCH(k_sort_boxes, dim3(n), dim3(256), 0, st, dp);
 }
 

@@ -23,14 +23,15 @@ void det_normalize(hipStream_t st, const uint8_t* rgb, int h, int w, float scale
 struct DbParams {
   float thresh, box_thresh, unclip_ratio;
   int min_size, dilate;
+  int score_mode;   // rt_config.det_score_mode: 0 = Fast (min-area rect), 1 = Slow (the contour's own polygon)
 };
 struct DbBox { float pts[8]; float score; int key; };
-// Work buffers for one page of H x W; sized by db_workspace_bytes().
-size_t db_workspace_bytes(int H, int W, int max_boxes);
+// Work buffers for one page of H x W; sized by db_workspace_bytes() (score_mode 1 adds the Slow kernels' buffers).
+size_t db_workspace_bytes(int H, int W, int max_boxes, int score_mode);
 struct DbPageIn { const float* pred; int H, W, ori_h, ori_w; };
 size_t db_page_desc_bytes();
 // Runs the whole post-process for n pages with shared launches (blockIdx.y = page).
-// workspaces[i]: device buffer of db_workspace_bytes(H_i, W_i, max_boxes); boxes_out[i]
+// workspaces[i]: device buffer of db_workspace_bytes(H_i, W_i, max_boxes, p.score_mode); boxes_out[i]
 // (device, max_boxes entries) receives the sorted boxes in after_* coordinates,
 // count_out[i][0] the number, count_out[i][1] != 0 signals a capacity overflow.
 // h_desc (pinned host) / d_desc (device): n * db_page_desc_bytes() scratch for the page table.

@@ -353,6 +353,7 @@ static pp::DbParams db_params(const rt_config& c) {
   pp::DbParams p;
   p.thresh = c.det_thresh; p.box_thresh = c.det_box_thresh; p.unclip_ratio = c.det_unclip_ratio;
   p.min_size = c.det_min_mini_box_size; p.dilate = c.det_dilation;
+  p.score_mode = c.det_score_mode;
   return p;
 }
 static int max_boxes_of(const rt_config& c) { return c.max_boxes_per_page > 0 ? c.max_boxes_per_page : 8192; }
@@ -363,7 +364,7 @@ void rt_session::det_postprocess(const float* pred, int h, int w, int ori_h, int
   float* d = arena.alloc<float>((size_t)h * w);
   RT_HIP_CHECK(hipMemcpyAsync(d, pred, (size_t)h * w * 4, hipMemcpyHostToDevice, st));
   const int mb = max_boxes_of(cfg);
-  void* ws = dbws.alloc_bytes(pp::db_workspace_bytes(h, w, mb));
+  void* ws = dbws.alloc_bytes(pp::db_workspace_bytes(h, w, mb, cfg.det_score_mode));
   pp::DbBox* db = arena.alloc<pp::DbBox>(mb);
   int* cnt = arena.alloc<int>(2);
   {
@@ -656,7 +657,7 @@ rt_results* rt_session::run_pages(const uint8_t* const* rgb, const int* hs, cons
       p.d_boxes = d_boxes_all + (size_t)i * mb;
       p.d_count = d_counts_all + 2 * i;
       in[i] = pp::DbPageIn{pred, p.det_h, p.det_w, p.after_h, p.after_w};
-      wsp[i] = dbws.alloc_bytes(pp::db_workspace_bytes(p.det_h, p.det_w, mb));
+      wsp[i] = dbws.alloc_bytes(pp::db_workspace_bytes(p.det_h, p.det_w, mb, cfg.det_score_mode));
       bo[i] = p.d_boxes; co[i] = p.d_count;
     }
     void* hd = pinned.alloc_bytes((size_t)n_pages * pp::db_page_desc_bytes());
