@@ -267,6 +267,33 @@ RT_API int rt_host_cpu_budget(void);
 RT_API int rt_decode_image(const void* data, size_t len, uint8_t** rgb, int* h, int* w, char* err, size_t err_cap);
 RT_API int rt_run_encoded_batch(rt_session* s, const void* const* files, const size_t* lens, int n_pages,
                                 rt_stage_callback cb, void* user, rt_results** out);
+/* Encoded pages with the pixel work on the GPU.  The host only entropy-decodes each JPEG page (on the thread pool of
+ * rt_run_encoded_batch) into quantised int16 coefficients; dequantisation, the inverse DCT, chroma upsampling and colour
+ * conversion run on the device, bit-identical to rt_decode_image.  A JPEG page goes to the device when every coefficient fits
+ * int16 and its sampling is grey, 4:4:4, 4:2:2 or 4:2:0 (each chroma factor 1x1, 2x1 or 2x2); every other page -- other JPEG
+ * layouts, PNG, PNM, BMP -- is decoded on the host as rt_decode_image does and its pixels are uploaded.  Decode errors are
+ * rt_decode_image's (RT_ERR_IMAGE, "image decode: ..."), reported for the first failing page in page order.
+ *
+ * rt_submit_encoded_batch is rt_submit_batch over encoded files: the pages are decoded inside the call, the returned ticket
+ * is collected with rt_wait_batch and gives what rt_run_encoded_batch gives for the same files.  Unlike rt_submit_batch's
+ * pages, the FILE BUFFERS may be freed as soon as the call returns: the ticket owns the coefficients.  Each lane part's upload
+ * and reconstruction run on the session's copy stream before that lane starts, so the host decode of batch i + 1 (inside this
+ * call) overlaps the GPU work of batch i.  On a decode error nothing is queued, *out is NULL and tickets in flight are not
+ * affected.  Legal wherever rt_submit_batch is.
+ *
+ * rt_decode_batch decodes n files synchronously through the same host stage and kernels.  out == NULL: hs / ws only, from the
+ * headers (no pixel work, the rest of a file is not checked).  Otherwise out[i] receives hs[i] * ws[i] * 3 bytes of RGB8 in
+ * `mem` (RT_MEM_HOST or RT_MEM_DEVICE); on_device (optional) [i] = 1 where the kernels reconstructed page i.  Fails with
+ * RT_ERR_INVALID while tickets are in flight, like every call other than rt_submit_batch / rt_wait_batch.
+ *
+ * rt_debug_jpeg_reconstruct: one file through the same host stage, then the kernels' arithmetic (retto_amd/csrc/jpeg_recon.h)
+ * run on the CPU; *on_device tells whether the device path would take the page (otherwise *rgb is the host decode).  GPU-free,
+ * sessionless; *rgb is library-owned until rt_buffer_free. */
+RT_API int rt_submit_encoded_batch(rt_session* s, const void* const* files, const size_t* lens, int n_pages, rt_ticket** out);
+RT_API int rt_decode_batch(rt_session* s, const void* const* files, const size_t* lens, int n, int* hs, int* ws,
+                           uint8_t* const* out, int mem, int* on_device);
+RT_API int rt_debug_jpeg_reconstruct(const void* data, size_t len, uint8_t** rgb, int* h, int* w, int* on_device, char* err,
+                                     size_t err_cap);
 /* RecCharacter::new (retto-core/src/processor/rec_processor.rs:29-46) on the bytes of ppocr_keys_v1.txt, with
  * Rust's semantics: strict String::from_utf8 (RT_ERR_UTF8 on overlong forms, surrogates, > U+10FFFF), str::lines,
  * str::trim over the Unicode White_Space set (a U+3000-only line becomes ""), "blank" inserted at 0 and " "

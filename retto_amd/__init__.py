@@ -315,6 +315,22 @@ def decode_image(data: bytes) -> np.ndarray:
         lib.rt_buffer_free(out)
 
 
+def debug_jpeg_reconstruct(data: bytes):
+    """rt_debug_jpeg_reconstruct: the device decode path's host stage plus the reconstruction kernels' arithmetic, run on the
+    CPU.  Returns (RGB8 [H,W,3], on_device); on_device False means the device path decodes this file on the host."""
+    lib = _lib.load()
+    data = bytes(data)
+    out = C.c_void_p(); h = C.c_int(); w = C.c_int(); dev = C.c_int()
+    err = C.create_string_buffer(512)
+    rc = lib.rt_debug_jpeg_reconstruct(data, len(data), C.byref(out), C.byref(h), C.byref(w), C.byref(dev), err, len(err))
+    if rc != 0:
+        raise _ERRS.get(rc, RettoError)(err.value.decode("utf-8", "replace"))
+    try:
+        return np.ctypeslib.as_array(C.cast(out, C.POINTER(C.c_uint8)), (h.value, w.value, 3)).copy(), bool(dev.value)
+    finally:
+        lib.rt_buffer_free(out)
+
+
 class RettoSession:
     """RettoSession<RettoHipWorker> (session.rs:58-144), batched."""
 
@@ -467,6 +483,38 @@ class RettoSession:
             return [self._collect(out, i) for i in range(n)]
         finally:
             self._hd.lib.rt_results_free(out)
+
+    def submit_encoded_batch(self, files: Sequence[bytes]):
+        """rt_submit_encoded_batch: host entropy decoding inside the call, pixel reconstruction on the GPU ahead of the lanes.
+        Returns a ticket for wait_batch_raw / wait_batch; the ticket owns the decoded data, the file bytes are not kept."""
+        n = len(files)
+        files = [bytes(f) for f in files]
+        ptrs = (C.c_char_p * max(n, 1))(*files); lens = (C.c_size_t * max(n, 1))(*[len(f) for f in files])
+        out = C.c_void_p()
+        _check(self._hd.lib.rt_submit_encoded_batch(self._hd.h, ptrs, lens, n, C.byref(out)), self._hd.h)
+        return out, []
+
+    def wait_batch(self, ticket) -> List[RettoWorkerResult]:
+        """wait_batch_raw, collected: one RettoWorkerResult per page."""
+        r = self.wait_batch_raw(ticket)
+        try:
+            self.last_det_checksum = self._hd.lib.rt_results_det_checksum(r)
+            return [self._collect(r, i) for i in range(self._hd.lib.rt_results_pages(r))]
+        finally:
+            self._hd.lib.rt_results_free(r)
+
+    def decode_batch(self, files: Sequence[bytes]):
+        """rt_decode_batch into host memory: (list of RGB8 [H,W,3] pages, list of on_device flags)."""
+        n = len(files)
+        files = [bytes(f) for f in files]
+        ptrs = (C.c_char_p * max(n, 1))(*files); lens = (C.c_size_t * max(n, 1))(*[len(f) for f in files])
+        hs = (C.c_int * max(n, 1))(); ws = (C.c_int * max(n, 1))(); dev = (C.c_int * max(n, 1))()
+        lib, h = self._hd.lib, self._hd.h
+        _check(lib.rt_decode_batch(h, ptrs, lens, n, hs, ws, None, RT_MEM_HOST, None), h)
+        pages = [np.empty((hs[i], ws[i], 3), np.uint8) for i in range(n)]
+        outs = (C.c_void_p * max(n, 1))(*[p.ctypes.data for p in pages])
+        _check(lib.rt_decode_batch(h, ptrs, lens, n, hs, ws, outs, RT_MEM_HOST, dev), h)
+        return pages, [bool(dev[i]) for i in range(n)]
 
     def run_stream(self, image, sender: Callable[[str, list], None]) -> None:
         """session.rs:133-143: emits ("Det", ...), ("Cls", ...), ("Rec", ...) in that order.  Det arrives while

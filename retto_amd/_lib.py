@@ -53,6 +53,7 @@ EXPORTS = [
     "rt_device_malloc", "rt_device_free", "rt_memcpy_h2d", "rt_memcpy_d2h", "rt_synchronize",
     "rt_set_lanes", "rt_profile_enable", "rt_profile_get",
     "rt_onnx_to_rtwb", "rt_buffer_free", "rt_model_manifest", "rt_decode_image", "rt_run_encoded_batch",
+    "rt_submit_encoded_batch", "rt_decode_batch", "rt_debug_jpeg_reconstruct",
     "rt_debug_set_variants", "rt_bench_gemm", "rt_bench_gemm_err", "rt_bench_lc", "rt_debug_conv16", "rt_parse_dictionary", "rt_format_f32", "rt_rccl_unique_id", "rt_broadcast_blobs",
 ]
 
@@ -150,6 +151,11 @@ def load():
     lib.rt_model_manifest.argtypes = [C.c_int, C.c_char_p, C.c_size_t]
     lib.rt_decode_image.argtypes = [C.c_char_p, C.c_size_t, P(C.c_void_p), P(C.c_int), P(C.c_int), C.c_char_p, C.c_size_t]
     lib.rt_run_encoded_batch.argtypes = [C.c_void_p, P(C.c_char_p), P(C.c_size_t), C.c_int, C.c_void_p, C.c_void_p, P(C.c_void_p)]
+    lib.rt_submit_encoded_batch.argtypes = [C.c_void_p, P(C.c_char_p), P(C.c_size_t), C.c_int, P(C.c_void_p)]
+    lib.rt_decode_batch.argtypes = [C.c_void_p, P(C.c_char_p), P(C.c_size_t), C.c_int, P(C.c_int), P(C.c_int), P(C.c_void_p),
+                                    C.c_int, P(C.c_int)]
+    lib.rt_debug_jpeg_reconstruct.argtypes = [C.c_char_p, C.c_size_t, P(C.c_void_p), P(C.c_int), P(C.c_int), P(C.c_int),
+                                              C.c_char_p, C.c_size_t]
     lib.rt_model_manifest.restype = C.c_size_t
     _lib = lib
     return lib

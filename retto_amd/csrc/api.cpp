@@ -349,6 +349,84 @@ int rt_run_encoded_batch(rt_session* s, const void* const* files, const size_t* 
     *out = s->run_batch(ptrs.data(), hs.data(), ws.data(), n_pages, RT_MEM_HOST, nullptr, cb, user);
   });
 }
+// The host stage of the device decode path: every page parsed and entropy-decoded (JPEG) or decoded (anything else) on the
+// same thread pool as rt_run_encoded_batch; the first failing page in page order is reported.
+static std::vector<rt::EncodedPage> host_stage(const void* const* files, const size_t* lens, int n_pages) {
+  std::vector<rt::EncodedPage> enc((size_t)n_pages);
+  std::vector<std::exception_ptr> errs((size_t)n_pages);
+  std::atomic<int> next{0};
+  auto work = [&] {
+    for (int i; (i = next.fetch_add(1)) < n_pages;) {
+      try {
+        if (!files[i]) throw RtError(RT_ERR_IMAGE, "image decode: null input");
+        rt::decode_for_device((const uint8_t*)files[i], lens[i], &enc[(size_t)i]);
+      } catch (...) { errs[(size_t)i] = std::current_exception(); }
+    }
+  };
+  const int nt = std::max(1, std::min<int>(n_pages, std::min<int>(16, rt_host_cpu_budget())));
+  std::vector<std::thread> th;
+  for (int t = 1; t < nt; t++) th.emplace_back(work);
+  work();
+  for (auto& t : th) t.join();
+  for (auto& e : errs) if (e) std::rethrow_exception(e);
+  return enc;
+}
+int rt_submit_encoded_batch(rt_session* s, const void* const* files, const size_t* lens, int n_pages, rt_ticket** out) {
+  if (out) *out = nullptr;
+  RT_REQUIRE(s && out && n_pages >= 0 && (n_pages == 0 || (files && lens)), s, "rt_submit_encoded_batch: bad argument");
+  RT_REQUIRE(s->inflight.load() < RT_MAX_INFLIGHT, s, "rt_submit_encoded_batch: too many batches in flight (RT_MAX_INFLIGHT)");
+  return guarded<true>(s, [&] {
+    std::vector<rt::EncodedPage> enc = host_stage(files, lens, n_pages);
+    std::vector<const uint8_t*> rgb((size_t)n_pages, nullptr);
+    std::vector<int> hs((size_t)n_pages), ws((size_t)n_pages);
+    for (int i = 0; i < n_pages; i++) { hs[(size_t)i] = enc[(size_t)i].h; ws[(size_t)i] = enc[(size_t)i].w; }
+    *out = s->submit_batch(rgb.data(), hs.data(), ws.data(), n_pages, RT_MEM_HOST, nullptr, nullptr, nullptr, &enc);
+  });
+}
+int rt_decode_batch(rt_session* s, const void* const* files, const size_t* lens, int n, int* hs, int* ws, uint8_t* const* out,
+                    int mem, int* on_device) {
+  RT_REQUIRE(s && n >= 0 && (n == 0 || (files && lens && hs && ws)), s, "rt_decode_batch: bad argument");
+  RT_REQUIRE(!out || mem == RT_MEM_HOST || mem == RT_MEM_DEVICE, s, "rt_decode_batch: bad mem kind");
+  for (int i = 0; out && i < n; i++) RT_REQUIRE(out[i], s, "rt_decode_batch: null output page");
+  return guarded(s, [&] {
+    if (!out) {
+      for (int i = 0; i < n; i++) {
+        if (!files[i]) throw RtError(RT_ERR_IMAGE, "image decode: null input");
+        rt::image_dims((const uint8_t*)files[i], lens[i], &hs[i], &ws[i]);
+        if (on_device) on_device[i] = 0;
+      }
+      return;
+    }
+    std::vector<rt::EncodedPage> enc = host_stage(files, lens, n);
+    for (int i = 0; i < n; i++) {
+      hs[i] = enc[(size_t)i].h; ws[i] = enc[(size_t)i].w;
+      if (on_device) on_device[i] = enc[(size_t)i].on_device ? 1 : 0;
+    }
+    if (n) s->decode_batch(enc, out, mem);
+  });
+}
+int rt_debug_jpeg_reconstruct(const void* data, size_t len, uint8_t** rgb, int* h, int* w, int* on_device, char* err,
+                              size_t err_cap) {
+  if (err && err_cap) err[0] = 0;
+  if (!data || !rgb || !h || !w || !on_device) { if (err && err_cap) snprintf(err, err_cap, "rt_debug_jpeg_reconstruct: null argument"); return RT_ERR_INVALID; }
+  *rgb = nullptr;
+  try {
+    rt::EncodedPage e;
+    rt::decode_for_device((const uint8_t*)data, len, &e);
+    if (e.on_device) rt::reconstruct_host(e.jpeg, &e.rgb);
+    uint8_t* p = (uint8_t*)malloc(std::max<size_t>(e.rgb.size(), 1));
+    if (!p) throw RtError(RT_ERR_BACKEND, "out of memory");
+    memcpy(p, e.rgb.data(), e.rgb.size());
+    *rgb = p; *h = e.h; *w = e.w; *on_device = e.on_device ? 1 : 0;
+    return RT_OK;
+  } catch (const RtError& e) {
+    if (err && err_cap) snprintf(err, err_cap, "%s", e.what());
+    return e.code;
+  } catch (const std::exception& e) {
+    if (err && err_cap) snprintf(err, err_cap, "%s", e.what());
+    return RT_ERR_BACKEND;
+  }
+}
 void rt_results_free(rt_results* r) { delete r; }
 int rt_results_pages(const rt_results* r) { return r ? (int)r->pages.size() : 0; }
 #define RT_PAGE(r, page) ((r) && (page) >= 0 && (size_t)(page) < (r)->pages.size() ? &(r)->pages[(size_t)(page)] : nullptr)

@@ -12,6 +12,7 @@
 
 #include "../../include/retto_hip.h"
 #include "common.h"
+#include "jpeg_recon.h"
 
 namespace rt {
 namespace {
@@ -270,6 +271,8 @@ struct JComp {
   int pred = 0;
   std::vector<uint8_t> plane;
   std::vector<int> coef;   // progressive: all coefficients of the (MCU-padded) component, 64 per block, natural order
+  std::vector<int16_t> q16;  // coefficient mode, sequential: the quantised coefficients, same layout
+  uint16_t qn[64];         // coefficient mode, sequential: the table the component's scan used, natural order
 };
 
 struct JpegDec {
@@ -281,6 +284,9 @@ struct JpegDec {
   Huff dc[4], ac[4];
   uint64_t bits = 0; int nbits = 0; bool hit_marker = false;
   bool progressive = false; int Ss = 0, Se = 63, Ah = 0, Al = 0, eobrun = 0;
+  // coefficient mode (decode_for_device): sequential blocks keep their quantised coefficients in JComp::q16 instead of being
+  // transformed; `wide` records a DC predictor that left int16 (only a corrupt stream does that)
+  bool coef_mode = false, wide = false;
 
   void fill() {
     while (nbits <= 56) {
@@ -396,6 +402,21 @@ struct JpegDec {
     if (s > 11) bad("JPEG: corrupt DC coefficient");
     // (corrupt streams may drive the predictor or a product anywhere: wrap / clamp instead of overflowing)
     if (s) cm.pred = (int)((unsigned)cm.pred + (unsigned)extend(getbits(s), s));
+    if (coef_mode) {   // the same entropy decoding; an AC value has at most 15 bits, so only the DC predictor can leave int16
+      int16_t* blk = cm.q16.data() + ((size_t)by * (cm.stride / 8) + bx) * 64;
+      memset(blk, 0, 64 * sizeof(int16_t));
+      if (cm.pred < -32768 || cm.pred > 32767) wide = true;
+      blk[0] = (int16_t)cm.pred;
+      for (int k = 1; k < 64;) {
+        const int rs = decode(ha), r = rs >> 4, sz = rs & 15;
+        if (sz == 0) { if (r != 15) break; k += 16; continue; }
+        k += r;
+        if (k > 63) bad("JPEG: corrupt AC coefficients");
+        blk[kZigzag[k]] = (int16_t)extend(getbits(sz), sz);
+        k++;
+      }
+      return;
+    }
     auto clampc = [](long v) { return (int)(v < -(1L << 24) ? -(1L << 24) : v > (1L << 24) ? (1L << 24) : v); };
     coef[0] = clampc((long)cm.pred * q[0]);
     bool any_ac = false;
@@ -518,6 +539,7 @@ struct JpegDec {
       const bool need_dc = !progressive || (Ss == 0 && Ah == 0), need_ac = !progressive || Ss > 0;
       if ((need_dc && !dc[cm.td].ok) || (need_ac && !ac[cm.ta].ok)) bad("JPEG: scan refers to a missing Huffman table");
       if (!progressive && !qt_ok[cm.tq]) bad("JPEG: frame refers to a missing quantisation table");
+      if (coef_mode && !progressive) for (int k = 0; k < 64; k++) cm.qn[kZigzag[k]] = qt[cm.tq][k];
       cm.pred = 0;
     }
     if (progressive) {
@@ -609,7 +631,8 @@ struct JpegDec {
     }
   }
 
-  void run(std::vector<uint8_t>* rgb, int* oh, int* ow) {
+  // the marker segments and every scan; header_only: stop after the frame header (W, H)
+  void parse(bool header_only) {
     bool done = false;
     int scans = 0;
     while (!done) {
@@ -665,11 +688,13 @@ struct JpegDec {
         for (int i = 0; i < nc; i++) {
           c[i].cw = (W * c[i].hs + hmax - 1) / hmax; c[i].ch = (H * c[i].vs + vmax - 1) / vmax;
           c[i].stride = mx * c[i].hs * 8; c[i].rows = my * c[i].vs * 8;
-          c[i].plane.assign((size_t)c[i].stride * c[i].rows, 128);
+          if (!coef_mode) c[i].plane.assign((size_t)c[i].stride * c[i].rows, 128);
+          else if (m != 0xc2) c[i].q16.assign((size_t)c[i].stride * c[i].rows, 0);
           if (m == 0xc2) c[i].coef.assign((size_t)c[i].stride * c[i].rows, 0);
         }
         progressive = m == 0xc2;
         have_sof = true;
+        if (header_only) return;
       }
       else if (m == 0xc3 || (m >= 0xc5 && m <= 0xcf && m != 0xc8 && m != 0xcc)) bad("JPEG: lossless / hierarchical / arithmetic-coded files are not supported");
       else if (m == 0xdd) { if (sl < 2) bad("JPEG: bad DRI"); restart = (int)be16(s); }
@@ -697,6 +722,12 @@ struct JpegDec {
       // everything else (APPn, COM, ...) is skipped
     }
     if (!have_sof || !scans) bad("JPEG: no image data");
+  }
+
+  bool is_rgb() const { return adobe ? adobe_tf == 0 : (c[0].id == 'R' && c[1].id == 'G' && c[2].id == 'B'); }
+
+  void run(std::vector<uint8_t>* rgb, int* oh, int* ow) {
+    parse(false);
     if (progressive) finish_progressive();
     rgb->assign((size_t)W * H * 3, 0);
     if (nc == 1) {
@@ -708,10 +739,9 @@ struct JpegDec {
     } else {
       std::vector<uint8_t> p[3];
       for (int i = 0; i < 3; i++) upsample(c[i], p[i]);
-      const bool is_rgb = adobe ? adobe_tf == 0 : (c[0].id == 'R' && c[1].id == 'G' && c[2].id == 'B');
       const size_t np = (size_t)W * H;
       uint8_t* o = rgb->data();
-      if (is_rgb) {
+      if (is_rgb()) {
         for (size_t i = 0; i < np; i++) { o[3 * i] = p[0][i]; o[3 * i + 1] = p[1][i]; o[3 * i + 2] = p[2][i]; }
       } else {
         // jdcolor: 16-bit fixed point, FIX(x) = (int)(x * 65536 + 0.5)
@@ -730,17 +760,148 @@ struct JpegDec {
     }
     *oh = H; *ow = W;
   }
+
+  // coefficient mode: the page's description and quantised coefficients.  false: the kernels do not reconstruct this page
+  // (a coefficient outside int16, a sampling layout they do not implement, or anything the pixel path would reject after the
+  // scans) -- the caller decodes it with decode_image, which also reports those errors exactly as before.
+  bool coefs(JpegCoefs* out) {
+    parse(false);
+    if (wide) return false;
+    int fh[3], fv[3];
+    for (int i = 0; i < nc; i++) {
+      if (hmax % c[i].hs || vmax % c[i].vs) return false;
+      fh[i] = hmax / c[i].hs; fv[i] = vmax / c[i].vs;
+      if (progressive && !qt_ok[c[i].tq]) return false;
+    }
+    if (!jpeg::layout_on_device(nc, fh, fv)) return false;
+    out->W = W; out->H = H; out->nc = nc; out->hmax = hmax; out->vmax = vmax;
+    out->is_rgb = nc == 3 && is_rgb();
+    for (int i = 0; i < nc; i++) {
+      JComp& cm = c[i];
+      JpegCoefs::Comp& o = out->c[i];
+      o.hs = cm.hs; o.vs = cm.vs; o.cw = cm.cw; o.ch = cm.ch; o.stride = cm.stride; o.rows = cm.rows;
+      if (progressive) {
+        for (int k = 0; k < 64; k++) o.q[kZigzag[k]] = qt[cm.tq][k];
+        o.coef.resize(cm.coef.size());
+        for (size_t k = 0; k < cm.coef.size(); k++) {
+          const int v = cm.coef[k];
+          if (v < -32768 || v > 32767) return false;
+          o.coef[k] = (int16_t)v;
+        }
+      } else {
+        memcpy(o.q, cm.qn, sizeof(o.q));
+        o.coef = std::move(cm.q16);
+      }
+    }
+    return true;
+  }
 };
+
+const uint8_t png_sig[8] = {0x89, 'P', 'N', 'G', 0x0d, 0x0a, 0x1a, 0x0a};
+inline bool is_png(const uint8_t* d, size_t n) { return n >= 8 && !memcmp(d, png_sig, 8); }
+inline bool is_jpeg(const uint8_t* d) { return d[0] == 0xff && d[1] == 0xd8; }
+inline bool is_pnm(const uint8_t* d) { return d[0] == 'P' && (d[1] == '2' || d[1] == '3' || d[1] == '5' || d[1] == '6'); }
+inline bool is_bmp(const uint8_t* d) { return d[0] == 'B' && d[1] == 'M'; }
+[[noreturn]] void unsupported(const uint8_t* data, size_t len);
 
 }  // namespace
 
 void decode_image(const uint8_t* data, size_t len, std::vector<uint8_t>* rgb, int* h, int* w) {
-  static const uint8_t png_sig[8] = {0x89, 'P', 'N', 'G', 0x0d, 0x0a, 0x1a, 0x0a};
   if (!data || len < 4) bad("empty or truncated input");
-  if (len >= 8 && !memcmp(data, png_sig, 8)) return decode_png(data, len, rgb, h, w);
-  if (data[0] == 0xff && data[1] == 0xd8) { JpegDec j{data, len}; return j.run(rgb, h, w); }
-  if (data[0] == 'P' && (data[1] == '2' || data[1] == '3' || data[1] == '5' || data[1] == '6')) return decode_pnm(data, len, rgb, h, w);
-  if (data[0] == 'B' && data[1] == 'M') return decode_bmp(data, len, rgb, h, w);
+  if (is_png(data, len)) return decode_png(data, len, rgb, h, w);
+  if (is_jpeg(data)) { JpegDec j{data, len}; return j.run(rgb, h, w); }
+  if (is_pnm(data)) return decode_pnm(data, len, rgb, h, w);
+  if (is_bmp(data)) return decode_bmp(data, len, rgb, h, w);
+  unsupported(data, len);
+}
+
+void decode_for_device(const uint8_t* data, size_t len, EncodedPage* out) {
+  out->on_device = false;
+  if (data && len >= 4 && is_jpeg(data)) {
+    JpegDec j{data, len};
+    j.coef_mode = true;
+    if (j.coefs(&out->jpeg)) { out->on_device = true; out->h = j.H; out->w = j.W; return; }
+    out->jpeg = JpegCoefs();
+  }
+  decode_image(data, len, &out->rgb, &out->h, &out->w);
+}
+
+void reconstruct_host(const JpegCoefs& J, std::vector<uint8_t>* rgb) {
+  std::vector<uint8_t> planes[3];
+  for (int k = 0; k < J.nc; k++) {
+    const JpegCoefs::Comp& C = J.c[k];
+    planes[k].assign((size_t)C.stride * C.rows, 0);
+    const int bw = C.stride / 8, nb = bw * (C.rows / 8);
+    int ws[64];
+    for (int b = 0; b < nb; b++) {
+      const int by = b / bw, bx = b % bw;
+      for (int col = 0; col < 8; col++) jpeg::idct_col(C.coef.data() + (size_t)b * 64, C.q, col, ws, 8);
+      for (int r = 0; r < 8; r++) jpeg::idct_row(ws + 8 * r, planes[k].data() + (size_t)(by * 8 + r) * C.stride + (size_t)bx * 8);
+    }
+  }
+  rgb->assign((size_t)J.W * J.H * 3, 0);
+  for (int y = 0; y < J.H; y++)
+    for (int x = 0; x < J.W; x++) {
+      uint8_t* o = rgb->data() + ((size_t)y * J.W + x) * 3;
+      if (J.nc == 1) { o[0] = o[1] = o[2] = planes[0][(size_t)y * J.c[0].stride + x]; continue; }
+      uint8_t v[3];
+      for (int i = 0; i < 3; i++) {
+        const JpegCoefs::Comp& C = J.c[i];
+        v[i] = jpeg::up_sample(planes[i].data(), C.stride, C.cw, C.ch, J.hmax / C.hs, J.vmax / C.vs, x, y);
+      }
+      if (J.is_rgb) { o[0] = v[0]; o[1] = v[1]; o[2] = v[2]; }
+      else jpeg::ycc_rgb(v[0], v[1], v[2], o);
+    }
+}
+
+void image_dims(const uint8_t* data, size_t len, int* h, int* w) {
+  if (!data || len < 4) bad("empty or truncated input");
+  if (is_png(data, len)) {   // the first chunk must be IHDR (decode_png's first checks)
+    if (len < 8 + 25 || be32(data + 8) != 13 || memcmp(data + 12, "IHDR", 4)) bad("PNG: first chunk is not IHDR");
+    const uint32_t W = be32(data + 16), H = be32(data + 20);
+    check_dims(W, H);
+    *h = (int)H; *w = (int)W;
+    return;
+  }
+  if (is_jpeg(data)) {
+    JpegDec j{data, len};
+    j.parse(true);
+    if (!j.have_sof) bad("JPEG: no image data");
+    *h = j.H; *w = j.W;
+    return;
+  }
+  if (is_pnm(data)) {   // the three header numbers, as decode_pnm reads them
+    size_t pos = 2;
+    auto token = [&]() -> long {
+      for (;;) {
+        while (pos < len && (data[pos] == ' ' || data[pos] == '\n' || data[pos] == '\r' || data[pos] == '\t' || data[pos] == '\v' || data[pos] == '\f')) pos++;
+        if (pos < len && data[pos] == '#') { while (pos < len && data[pos] != '\n') pos++; continue; }
+        break;
+      }
+      if (pos >= len || data[pos] < '0' || data[pos] > '9') bad("PNM: malformed header or sample");
+      long v = 0;
+      while (pos < len && data[pos] >= '0' && data[pos] <= '9') { v = v * 10 + (data[pos++] - '0'); if (v > 0x7fffffffL) bad("PNM: number out of range"); }
+      return v;
+    };
+    const long W = token(), H = token();
+    check_dims((uint64_t)W, (uint64_t)H);
+    *h = (int)H; *w = (int)W;
+    return;
+  }
+  if (is_bmp(data)) {
+    if (len < 54) bad("BMP: truncated header");
+    const int32_t W = (int32_t)le32(data + 18), Hs = (int32_t)le32(data + 22);
+    const int64_t H = Hs < 0 ? -(int64_t)Hs : Hs;
+    if (W <= 0) bad("BMP: bad width");
+    check_dims((uint64_t)W, (uint64_t)H);
+    *h = (int)H; *w = (int)W;
+    return;
+  }
+  unsupported(data, len);
+}
+
+namespace {
+void unsupported(const uint8_t* data, size_t len) {
   // Formats image 0.25.6 reads with its default features (/root/reference/Cargo.toml:23) that this decoder does not: named,
   // so that a caller sees WHICH decoder is missing instead of the reference's "format could not be determined".
   struct Sig { const char* magic; size_t n; size_t off; const char* name; };
@@ -752,5 +913,6 @@ void decode_image(const uint8_t* data, size_t len, std::vector<uint8_t>* rgb, in
       bad(std::string(g.name) + " input: the reference decodes it (image crate default features), this decoder reads PNG, JPEG, PNM and BMP only");
   bad("unrecognised image format (PNG, JPEG, PNM and BMP are read)");
 }
+}  // namespace
 
 }  // namespace rt

@@ -935,7 +935,131 @@ void rt_session::ensure_workers() {
 // done) with nothing queued on its stream: about 3 ms per 11-page part.  rt_submit_batch therefore copies the host pages of the
 // whole batch itself, on a copy stream, into a slot of HBM the session keeps per batch in flight; the lanes' streams wait for the
 // slot's event.  With one batch submitted ahead the copy of batch i+1 runs on the DMA engines under the kernels of batch i.
+int rt_session::acquire_slot(size_t total, int nl) {
+  RT_HIP_CHECK(hipSetDevice(device));   // (the caller's thread: nothing else has chosen the device on the submit path)
+  int slot = -1;
+  for (size_t k = 0; k < stage_slots.size(); k++) if (!stage_slots[k].busy) { slot = (int)k; break; }
+  if (slot < 0) { stage_slots.emplace_back(); slot = (int)stage_slots.size() - 1; }
+  StageSlot& S = stage_slots[(size_t)slot];
+  if (!st_copy) RT_HIP_CHECK(hipStreamCreateWithFlags(&st_copy, hipStreamNonBlocking));
+  while ((int)S.ev.size() < nl) {
+    hipEvent_t e = nullptr;
+    RT_HIP_CHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    S.ev.push_back(e);
+  }
+  if (S.cap < total) {
+    if (S.p) { (void)hipFree(S.p); S.p = nullptr; S.cap = 0; }
+    if (hipMalloc((void**)&S.p, total) != hipSuccess) { (void)hipGetLastError(); S.p = nullptr; return -1; }
+    S.cap = total;
+  }
+  return slot;
+}
+
+// ---- encoded pages (rt_submit_encoded_batch, rt_decode_batch) -----------------------------------------------------------------
+// Layout of pages [i0, i1) inside a slot from byte `at`: each page's RGB8 result, then for a page the kernels reconstruct its
+// MCU-padded component planes and int16 coefficients, then the part's DevComp / DevPage tables.  Returns the end offset.
+static size_t al256(size_t v) { return (v + 255) & ~(size_t)255; }
+static size_t enc_layout(const std::vector<rt::EncodedPage>& enc, int i0, int i1, size_t at, std::vector<size_t>& rgb_off,
+                         rt_ticket::EncPart& P) {
+  int64_t blocks = 0;
+  for (int i = i0; i < i1; i++) {
+    const rt::EncodedPage& e = enc[(size_t)i];
+    rgb_off[(size_t)i] = at;
+    at += al256((size_t)e.h * e.w * 3);
+    if (!e.on_device) continue;
+    const rt::JpegCoefs& J = e.jpeg;
+    rt::jpeg::DevPage dp{};
+    dp.rgb_off = rgb_off[(size_t)i]; dp.pix_base = P.pixels; dp.W = J.W; dp.H = J.H; dp.nc = J.nc; dp.is_rgb = J.is_rgb;
+    for (int k = 0; k < J.nc; k++) {
+      const rt::JpegCoefs::Comp& C = J.c[k];
+      rt::jpeg::DevComp dc{};
+      dc.plane_off = at; at += al256((size_t)C.stride * C.rows);
+      dc.coef_off = at; at += al256(C.coef.size() * sizeof(int16_t));
+      dc.blocks_w = C.stride / 8; dc.nblocks = (C.stride / 8) * (C.rows / 8); dc.block_base = (int)blocks;
+      blocks += dc.nblocks;
+      if (blocks > 0x7fffffff || C.coef.size() != (size_t)dc.nblocks * 64) throw RtError(RT_ERR_BACKEND, "encoded batch: too many JPEG blocks in one part");
+      dc.stride = C.stride; dc.cw = C.cw; dc.ch = C.ch; dc.fh = J.hmax / C.hs; dc.fv = J.vmax / C.vs;
+      memcpy(dc.q, C.q, sizeof(dc.q));
+      dp.comp[k] = (int)P.comps.size();
+      P.comps.push_back(dc);
+    }
+    P.pixels += (int64_t)J.W * J.H;
+    P.pages.push_back(dp);
+  }
+  P.blocks = (int)blocks;
+  P.comps_off = at; at += al256(P.comps.size() * sizeof(rt::jpeg::DevComp));
+  P.pages_off = at; at += al256(P.pages.size() * sizeof(rt::jpeg::DevPage));
+  return at;
+}
+// uploads pages [i0, i1) (coefficients of the device pages, pixels of the others) and the tables, then reconstructs on `st`
+static void enc_upload(uint8_t* base, const std::vector<rt::EncodedPage>& enc, int i0, int i1, const std::vector<size_t>& rgb_off,
+                       const rt_ticket::EncPart& P, hipStream_t st) {
+  size_t c = 0;
+  for (int i = i0; i < i1; i++) {
+    const rt::EncodedPage& e = enc[(size_t)i];
+    if (!e.on_device) {
+      RT_HIP_CHECK(hipMemcpyAsync(base + rgb_off[(size_t)i], e.rgb.data(), e.rgb.size(), hipMemcpyHostToDevice, st));
+      continue;
+    }
+    for (int k = 0; k < e.jpeg.nc; k++, c++) {
+      const std::vector<int16_t>& q = e.jpeg.c[k].coef;
+      RT_HIP_CHECK(hipMemcpyAsync(base + P.comps[c].coef_off, q.data(), q.size() * sizeof(int16_t), hipMemcpyHostToDevice, st));
+    }
+  }
+  if (P.pages.empty()) return;
+  RT_HIP_CHECK(hipMemcpyAsync(base + P.comps_off, P.comps.data(), P.comps.size() * sizeof(rt::jpeg::DevComp), hipMemcpyHostToDevice, st));
+  RT_HIP_CHECK(hipMemcpyAsync(base + P.pages_off, P.pages.data(), P.pages.size() * sizeof(rt::jpeg::DevPage), hipMemcpyHostToDevice, st));
+  const auto* comps = (const rt::jpeg::DevComp*)(base + P.comps_off);
+  rt::launch_jpeg_idct(base, comps, (int)P.comps.size(), P.blocks, st);
+  rt::launch_jpeg_color(base, comps, (const rt::jpeg::DevPage*)(base + P.pages_off), (int)P.pages.size(), P.pixels, st);
+}
+// an encoded ticket: every part in one slot, laid out part after part (staging is not optional here: the lanes need pixels)
+static void stage_encoded_layout(rt_ticket* t, size_t* total) {
+  t->enc_parts.assign((size_t)t->nl, rt_ticket::EncPart());
+  t->stage_off.assign((size_t)t->n_pages, (size_t)-1);
+  size_t at = 0;
+  for (int l = 0; l < t->nl; l++) at = enc_layout(t->enc, t->first[l], t->first[l + 1], at, t->stage_off, t->enc_parts[(size_t)l]);
+  *total = at;
+}
+void rt_session::decode_batch(std::vector<rt::EncodedPage>& enc, uint8_t* const* out, int mem) {
+  const int n = (int)enc.size();
+  std::vector<size_t> off((size_t)n, 0);
+  rt_ticket::EncPart P;
+  const size_t total = enc_layout(enc, 0, n, 0, off, P);
+  bool any_dev = false;
+  for (auto& e : enc) any_dev |= e.on_device || mem == RT_MEM_DEVICE;
+  if (!any_dev) {   // host pages into host memory: nothing to do on the device
+    for (int i = 0; i < n; i++) memcpy(out[i], enc[(size_t)i].rgb.data(), enc[(size_t)i].rgb.size());
+    return;
+  }
+  const int slot = acquire_slot(std::max<size_t>(total, 256), 1);
+  if (slot < 0) throw RtError(RT_ERR_BACKEND, "rt_decode_batch: out of device memory for the pages");
+  uint8_t* base = stage_slots[(size_t)slot].p;
+  enc_upload(base, enc, 0, n, off, P, st_copy);
+  for (int i = 0; i < n; i++) {
+    const rt::EncodedPage& e = enc[(size_t)i];
+    const size_t bytes = (size_t)e.h * e.w * 3;
+    if (mem == RT_MEM_DEVICE) RT_HIP_CHECK(hipMemcpyAsync(out[i], base + off[(size_t)i], bytes, hipMemcpyDeviceToDevice, st_copy));
+    else if (e.on_device) RT_HIP_CHECK(hipMemcpyAsync(out[i], base + off[(size_t)i], bytes, hipMemcpyDeviceToHost, st_copy));
+    else memcpy(out[i], e.rgb.data(), bytes);
+  }
+  RT_HIP_CHECK(hipStreamSynchronize(st_copy));
+}
+
 void rt_session::stage_pages(rt_ticket* t) {
+  if (!t->enc.empty()) {
+    size_t total = 0;
+    stage_encoded_layout(t, &total);
+    const int slot = acquire_slot(std::max<size_t>(total, 256), t->nl);
+    if (slot < 0) throw RtError(RT_ERR_BACKEND, "rt_submit_encoded_batch: out of device memory for the pages");
+    StageSlot& S = stage_slots[(size_t)slot];
+    S.busy = true;
+    t->stage_slot = slot;
+    t->ev_up.assign(S.ev.begin(), S.ev.begin() + t->nl);
+    for (int i = 0; i < t->n_pages; i++) t->rgb[(size_t)i] = S.p + t->stage_off[(size_t)i];
+    t->mem_lane = RT_MEM_STAGED_MAPS_HOST;
+    return;
+  }
   if (t->mem != RT_MEM_HOST && t->mem != RT_MEM_HOST_MAPS_DEVICE) return;
   size_t total = 0;
   std::vector<size_t> off((size_t)t->n_pages, (size_t)-1);
@@ -945,22 +1069,9 @@ void rt_session::stage_pages(rt_ticket* t) {
     total += ((size_t)t->hs[i] * t->ws[i] * 3 + 255) & ~(size_t)255;
   }
   if (!total) return;
-  RT_HIP_CHECK(hipSetDevice(device));   // (the caller's thread: nothing else has chosen the device on the submit path)
-  int slot = -1;
-  for (size_t k = 0; k < stage_slots.size(); k++) if (!stage_slots[k].busy) { slot = (int)k; break; }
-  if (slot < 0) { stage_slots.emplace_back(); slot = (int)stage_slots.size() - 1; }
+  const int slot = acquire_slot(total, t->nl);
+  if (slot < 0) return;   // out of device memory: the lanes copy, as before
   StageSlot& S = stage_slots[(size_t)slot];
-  if (!st_copy) RT_HIP_CHECK(hipStreamCreateWithFlags(&st_copy, hipStreamNonBlocking));
-  while ((int)S.ev.size() < t->nl) {
-    hipEvent_t e = nullptr;
-    RT_HIP_CHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    S.ev.push_back(e);
-  }
-  if (S.cap < total) {
-    if (S.p) { (void)hipFree(S.p); S.p = nullptr; S.cap = 0; }
-    if (hipMalloc((void**)&S.p, total) != hipSuccess) { (void)hipGetLastError(); S.p = nullptr; return; }   // the lanes copy, as before
-    S.cap = total;
-  }
   S.busy = true;
   t->stage_slot = slot;
   t->stage_off = std::move(off);
@@ -971,6 +1082,11 @@ void rt_session::stage_pages(rt_ticket* t) {
 void rt_session::stage_part(rt_ticket* t, int l) {
   if (t->stage_slot < 0) return;
   StageSlot& S = stage_slots[(size_t)t->stage_slot];
+  if (!t->enc.empty()) {
+    enc_upload(S.p, t->enc, t->first[l], t->first[l + 1], t->stage_off, t->enc_parts[(size_t)l], st_copy);
+    RT_HIP_CHECK(hipEventRecord(t->ev_up[(size_t)l], st_copy));
+    return;
+  }
   for (int i = t->first[l]; i < t->first[l + 1]; i++) {
     const size_t o = t->stage_off[(size_t)i];
     if (o == (size_t)-1) continue;
@@ -991,7 +1107,8 @@ void rt_session::free_stage() {
 }
 
 rt_ticket* rt_session::submit_batch(const uint8_t* const* rgb, const int* hs, const int* ws, int n_pages, int mem,
-                                    const float* const* det_map_override, rt_stage_callback cb, void* user) {
+                                    const float* const* det_map_override, rt_stage_callback cb, void* user,
+                                    std::vector<rt::EncodedPage>* enc) {
   ensure_workers();
   std::unique_ptr<rt_ticket> t(new rt_ticket());
   const int nl = std::max(1, std::min<int>(std::min<int>((int)helpers.size() + 1, active_lanes), std::max(n_pages, 1)));
@@ -1023,7 +1140,8 @@ rt_ticket* rt_session::submit_batch(const uint8_t* const* rgb, const int* hs, co
   t->mem_lane = mem;
   rt_ticket* tp = t.get();
   static const bool no_stage = getenv("RT_NO_STAGE") && atoi(getenv("RT_NO_STAGE"));   // (A/B switch of the measurement in DESIGN.md)
-  if (!no_stage) stage_pages(tp);
+  if (enc) tp->enc = std::move(*enc);
+  if (!no_stage || !tp->enc.empty()) stage_pages(tp);
   // parts go to consecutive lanes starting behind the previous batch's last one: batches that fill fewer lanes than the session
   // has (single pages: one lane each) run side by side instead of queueing on lane 0
   const int total_lanes = (int)helpers.size() + 1;

@@ -14,6 +14,8 @@
 #include <vector>
 
 #include "../../include/retto_hip.h"
+#include "image_decode.h"
+#include "jpeg_recon.h"
 #include "nets.h"
 #include "nets_f16.h"
 #include "prepost.h"
@@ -71,6 +73,17 @@ struct rt_ticket {
   int mem_lane = 0;                 // what the lanes are told: mem, or pages-on-device once staged
   std::vector<size_t> stage_off;    // per page: offset inside the slot, (size_t)-1 = not staged (empty page)
   std::vector<hipEvent_t> ev_up;    // per lane part; owned by the staging slot
+  // rt_submit_encoded_batch: the ticket owns the host-decoded pages (coefficients or pixels); stage_part uploads lane part l and
+  // reconstructs its JPEG pages with jpeg_kernels.hip into the slot before recording ev_up[l]
+  std::vector<rt::EncodedPage> enc;
+  struct EncPart {
+    std::vector<rt::jpeg::DevComp> comps;
+    std::vector<rt::jpeg::DevPage> pages;
+    size_t comps_off = 0, pages_off = 0;   // the two tables inside the slot
+    int blocks = 0;
+    int64_t pixels = 0;
+  };
+  std::vector<EncPart> enc_parts;   // per lane part
 };
 
 // internal to the library (never accepted from a caller): pages already in HBM, det map overrides still host pointers
@@ -142,13 +155,17 @@ struct rt_session {
   struct StageSlot { uint8_t* p = nullptr; size_t cap = 0; std::vector<hipEvent_t> ev; bool busy = false; };
   std::vector<StageSlot> stage_slots;
   hipStream_t st_copy = nullptr;
+  int acquire_slot(size_t bytes, int nl);  // a free slot of at least `bytes` with nl events (-1: out of device memory)
   void stage_pages(rt_ticket* t);          // picks the slot
   void stage_part(rt_ticket* t, int l);    // copies the pages of lane part l
   void release_stage(rt_ticket* t);
   void free_stage();
   void ensure_workers();
   rt_ticket* submit_batch(const uint8_t* const* rgb, const int* hs, const int* ws, int n_pages, int mem,
-                          const float* const* det_map_override, rt_stage_callback cb = nullptr, void* user = nullptr);
+                          const float* const* det_map_override, rt_stage_callback cb = nullptr, void* user = nullptr,
+                          std::vector<rt::EncodedPage>* enc = nullptr);
+  // rt_decode_batch: pages through the host stage and the reconstruction kernels into out[i] (mem: RT_MEM_HOST / RT_MEM_DEVICE)
+  void decode_batch(std::vector<rt::EncodedPage>& enc, uint8_t* const* out, int mem);
   rt_results* wait_batch(rt_ticket* t);   // consumes the ticket
   rt_results* run_batch(const uint8_t* const* rgb, const int* hs, const int* ws, int n_pages, int mem,
                         const float* const* det_map_override, rt_stage_callback cb = nullptr, void* user = nullptr);
