@@ -110,6 +110,10 @@ typedef struct rt_config {
                                  scores a box by the mean over the contour's own polygon (its full point chain) instead of its
                                  min-area rect, as the field's doc comment specifies; the reference itself never reads the field
                                  and computes Fast either way.  rt_create rejects other values with RT_ERR_INVALID. */
+  int32_t rec_return_word_box; /* 0 = off (default), 1 = word boxes (rt_results_rec_words): RecCharacter::decode's
+                                 `return_word_box` (rec_processor.rs:48-56), which the reference declares but never implements
+                                 (its only caller passes false, :199-206).  Off: no extra launch and no extra workspace.
+                                 rt_create rejects other values with RT_ERR_INVALID. */
 } rt_config;
 typedef enum rt_dtype { RT_DTYPE_F32 = 0, RT_DTYPE_F16 = 1 } rt_dtype;
 
@@ -216,6 +220,36 @@ RT_API const float* rt_results_cls_scores(const rt_results* r, int page);
 RT_API const float* rt_results_rec_scores(const rt_results* r, int page);
 RT_API int rt_results_rec_tokens(const rt_results* r, int page, int line, const int32_t** tokens);
 RT_API const char* rt_results_rec_text(const rt_results* r, int page, int line); /* UTF-8 */
+/* ---- word boxes (rt_config.rec_return_word_box = 1) ------------------------------------------------------------------------
+ * The words of each line, from the time steps of its kept CTC tokens.  The rule is this library's own (the reference has none);
+ * retto_amd/csrc/word_boxes.h states it, and k_word_boxes runs it on the device right after the CTC decode.  In short:
+ *   - each dictionary entry gets a raw class: DIGIT (all ASCII 0-9), ALPHA (ASCII [A-Za-z0-9], not DIGIT), DOT ".", HYPHEN "-",
+ *     CJK (every code point in U+4E00-U+9FFF), SPLIT (anything else, the appended " " included);
+ *   - kept tokens become ALNUM (ALPHA, DIGIT; "-" after ALNUM; "." between ALNUM and a DIGIT), CJK or SPLIT;
+ *   - every CJK token is a word (kind 0), every maximal run of ALNUM tokens is a word (kind 1), SPLIT tokens belong to none;
+ *   - an ALNUM word spans its columns [c_first, c_last + 1) times the crop pixels per column; a CJK word is centred on its
+ *     column with the mean CJK pitch of the line as its width; spans are clamped to the crop, y covers the whole crop;
+ *   - the span is mapped back through the cls rotate180, the crop's rotate270 and the crop homography to the page, then
+ *     scale_and_clip'd like the line boxes.  quad: TL, TR, BR, BL in the line box's corner order.
+ * Differences from PaddleOCR's return_word_box: no pixel parity with cal_ocr_word_box is intended; the spans go through the
+ * crop's homography (rotated boxes and crops map correctly) instead of an axis-aligned offset, and CJK / ALNUM splitting is by
+ * the classes above.  first_token / n_tokens index rt_results_rec_tokens of the line; first_col / last_col are time steps. */
+typedef struct rt_word {
+  float quad[8];
+  int32_t first_token, n_tokens, first_col, last_col, kind;   /* kind: 0 CJK character, 1 alphanumeric run */
+} rt_word;
+/* number of words of the line (0 when the option is off); *words: library-owned, valid until rt_results_free */
+RT_API int rt_results_rec_words(const rt_results* r, int page, int line, const rt_word** words);
+/* UTF-8 text of one word: the dictionary entries of its tokens, joined (NULL when out of range) */
+RT_API const char* rt_results_rec_word_text(rt_results* r, int page, int line, int word);
+/* The word rule on the CPU, GPU-free and sessionless.  dict: dictionary file bytes (parsed as rt_parse_dictionary does);
+ * tokens / cols: n kept class ids and their time steps (cols strictly increasing, < T); T, W, resized_w: the line's rec
+ * tensor (tokens_for_width(W) steps, padded width W, resized width); box8_after: the line's det box in after-resize_both
+ * coordinates, from which the crop's size, rotate270 and homography are derived exactly as the pipeline does; rot180: the
+ * cls rotation was applied.  out: room for n words; *n_words their number.  Quads in original-image coordinates. */
+RT_API int rt_debug_word_boxes(const void* dict, size_t dict_len, const int32_t* tokens, const int32_t* cols, int n, int T, int W,
+                               int resized_w, const float* box8_after, int rot180, int after_w, int after_h, int ori_w, int ori_h,
+                               rt_word* out, int* n_words);
 /* f32 sum of every det probability map produced in the call (keeps the network's
  * output observable when det_map_override is used) */
 RT_API double rt_results_det_checksum(const rt_results* r);

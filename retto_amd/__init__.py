@@ -104,6 +104,9 @@ class RecProcessorConfig:  # rec_processor.rs:102-136
     character_source: Optional[RettoWorkerModelSource] = None
     image_shape: Sequence[int] = (3, 48, 320)
     batch_num: int = 6
+    # RecCharacter::decode's return_word_box (rec_processor.rs:48-56; the reference never implements it): per-word boxes in
+    # RecProcessorSingleResult.words (include/retto_hip.h "word boxes" for the rule)
+    return_word_box: bool = False
 
 
 @dataclass
@@ -158,10 +161,24 @@ class ClsProcessorSingleResult:
 
 
 @dataclass
+class RecWord:
+    """One word of a line (rt_word): its text, its quad in original-image coordinates, kind "cjk" (one CJK character) or
+    "alnum" (a run of ASCII letters / digits with inner "." / "-"), its kept-token range and first / last time step."""
+    text: str
+    box: PointBox
+    kind: str
+    first_token: int
+    n_tokens: int
+    first_col: int
+    last_col: int
+
+
+@dataclass
 class RecProcessorSingleResult:
     text: str
     score: float
     tokens: np.ndarray = None  # kept CTC token ids (not in the reference struct; exposed for parity checks)
+    words: Optional[List[RecWord]] = None  # RecProcessorConfig.return_word_box; None when off
 
 
 @dataclass
@@ -227,6 +244,7 @@ class _Handle:
             c.cls_image_shape[i] = cl.image_shape[i]; c.rec_image_shape[i] = rc.image_shape[i]
         c.cls_batch_num, c.cls_thresh = cl.batch_num, cl.thresh
         c.rec_batch_num = rc.batch_num
+        c.rec_return_word_box = 1 if rc.return_word_box else 0
         if tuple(cl.label) != (0, 180):
             raise InvalidArgument("cls label set other than [0, 180] is not supported")
         c.max_boxes_per_page = cfg.max_boxes_per_page; c.det_sub_batch = cfg.det_sub_batch; c.lanes = cfg.lanes
@@ -327,6 +345,51 @@ def debug_jpeg_reconstruct(data: bytes):
         raise _ERRS.get(rc, RettoError)(err.value.decode("utf-8", "replace"))
     try:
         return np.ctypeslib.as_array(C.cast(out, C.POINTER(C.c_uint8)), (h.value, w.value, 3)).copy(), bool(dev.value)
+    finally:
+        lib.rt_buffer_free(out)
+
+
+def _rec_word(w, text: str) -> RecWord:
+    q = [float(v) for v in w.quad]
+    return RecWord(text, PointBox([Point(q[2 * i], q[2 * i + 1]) for i in range(4)]), "cjk" if w.kind == 0 else "alnum",
+                   int(w.first_token), int(w.n_tokens), int(w.first_col), int(w.last_col))
+
+
+def debug_word_boxes(dict_bytes: bytes, tokens, cols, T: int, W: int, resized_w: int, box_after, rot180: bool,
+                     after_w: int, after_h: int, ori_w: int, ori_h: int) -> List[RecWord]:
+    """rt_debug_word_boxes: the word rule (retto_amd/csrc/word_boxes.h) on the CPU for one line.  tokens / cols: kept class
+    ids and their time steps; box_after: the line's det box [4,2] in after-resize_both coordinates.  Word texts are the
+    dictionary entries of each word's tokens."""
+    lib = _lib.load()
+    dict_bytes = bytes(dict_bytes)
+    tok = np.ascontiguousarray(tokens, np.int32); col = np.ascontiguousarray(cols, np.int32)
+    n = len(tok)
+    if len(col) != n:
+        raise ShapeError("tokens and cols differ in length")
+    box = np.ascontiguousarray(box_after, np.float32).reshape(8)
+    out = (_lib.Word * max(n, 1))(); nw = C.c_int()
+    P = C.POINTER
+    rc = lib.rt_debug_word_boxes(dict_bytes, len(dict_bytes), tok.ctypes.data_as(P(C.c_int32)), col.ctypes.data_as(P(C.c_int32)),
+                                 n, T, W, resized_w, box.ctypes.data_as(P(C.c_float)), 1 if rot180 else 0, after_w, after_h,
+                                 ori_w, ori_h, out, C.byref(nw))
+    if rc != 0:
+        raise _ERRS.get(rc, RettoError)("rt_debug_word_boxes failed")
+    ents = parse_dictionary(dict_bytes)
+    return [_rec_word(out[j], "".join(ents[int(t)] for t in tok[out[j].first_token:out[j].first_token + out[j].n_tokens]))
+            for j in range(nw.value)]
+
+
+def parse_dictionary(data: bytes) -> List[str]:
+    """rt_parse_dictionary: RecCharacter::new (rec_processor.rs:29-46) -- "blank", the file's trimmed lines, " "."""
+    lib = _lib.load()
+    data = bytes(data)
+    out, ln, n = C.c_void_p(), C.c_size_t(), C.c_int()
+    err = C.create_string_buffer(256)
+    rc = lib.rt_parse_dictionary(data, len(data), C.byref(out), C.byref(ln), C.byref(n), err, len(err))
+    if rc != 0:
+        raise _ERRS.get(rc, RettoError)(err.value.decode("utf-8", "replace"))
+    try:
+        return C.string_at(out, ln.value).decode("utf-8").split("\n")
     finally:
         lib.rt_buffer_free(out)
 
@@ -452,8 +515,15 @@ class RettoSession:
             tp = C.POINTER(C.c_int32)()
             nt = lib.rt_results_rec_tokens(r, page, k, C.byref(tp))
             toks = np.ctypeslib.as_array(tp, (nt,)).copy() if nt else np.zeros(0, np.int32)
-            rec.append(RecProcessorSingleResult(lib.rt_results_rec_text(r, page, k).decode("utf-8"), float(rs[k]), toks))
+            words = self._words(r, page, k) if self.config.rec_processor_config.return_word_box else None
+            rec.append(RecProcessorSingleResult(lib.rt_results_rec_text(r, page, k).decode("utf-8"), float(rs[k]), toks, words))
         return RettoWorkerResult(det, cls, rec)
+
+    def _words(self, r, page: int, line: int) -> List[RecWord]:
+        lib = self._hd.lib
+        wp = C.POINTER(_lib.Word)()
+        nw = lib.rt_results_rec_words(r, page, line, C.byref(wp))
+        return [_rec_word(wp[j], lib.rt_results_rec_word_text(r, page, line, j).decode("utf-8")) for j in range(nw)]
 
     def run_batch(self, pages: Sequence[np.ndarray], det_map_override=None) -> List[RettoWorkerResult]:
         pages = [np.ascontiguousarray(p, np.uint8) for p in pages]

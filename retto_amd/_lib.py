@@ -36,8 +36,13 @@ class Config(C.Structure):
         ("cls_image_shape", C.c_int32 * 3), ("cls_batch_num", C.c_int32), ("cls_thresh", C.c_float),
         ("rec_image_shape", C.c_int32 * 3), ("rec_batch_num", C.c_int32),
         ("max_boxes_per_page", C.c_int32), ("det_sub_batch", C.c_int32), ("lanes", C.c_int32), ("dtype", C.c_int32),
-        ("det_score_mode", C.c_int32),
+        ("det_score_mode", C.c_int32), ("rec_return_word_box", C.c_int32),
     ]
+
+
+class Word(C.Structure):   # rt_word
+    _fields_ = [("quad", C.c_float * 8), ("first_token", C.c_int32), ("n_tokens", C.c_int32), ("first_col", C.c_int32),
+                ("last_col", C.c_int32), ("kind", C.c_int32)]
 
 
 # every symbol include/retto_hip.h declares (tests check that each is exported)
@@ -49,7 +54,7 @@ EXPORTS = [
     "rt_ctc_decode",
     "rt_run_batch", "rt_run_batch_stream", "rt_submit_batch", "rt_wait_batch", "rt_host_cpu_budget", "rt_results_free", "rt_results_pages", "rt_results_count", "rt_results_boxes",
     "rt_results_det_scores", "rt_results_cls_labels", "rt_results_cls_scores", "rt_results_rec_scores",
-    "rt_results_rec_tokens", "rt_results_rec_text", "rt_results_det_checksum", "rt_results_json",
+    "rt_results_rec_tokens", "rt_results_rec_text", "rt_results_rec_words", "rt_results_rec_word_text", "rt_debug_word_boxes", "rt_results_det_checksum", "rt_results_json",
     "rt_device_malloc", "rt_device_free", "rt_memcpy_h2d", "rt_memcpy_d2h", "rt_synchronize",
     "rt_set_lanes", "rt_profile_enable", "rt_profile_get",
     "rt_onnx_to_rtwb", "rt_buffer_free", "rt_model_manifest", "rt_decode_image", "rt_run_encoded_batch",
@@ -157,5 +162,11 @@ def load():
     lib.rt_debug_jpeg_reconstruct.argtypes = [C.c_char_p, C.c_size_t, P(C.c_void_p), P(C.c_int), P(C.c_int), P(C.c_int),
                                               C.c_char_p, C.c_size_t]
     lib.rt_model_manifest.restype = C.c_size_t
+    lib.rt_parse_dictionary.argtypes = [C.c_char_p, C.c_size_t, P(C.c_void_p), P(C.c_size_t), P(C.c_int), C.c_char_p, C.c_size_t]
+    lib.rt_results_rec_words.argtypes = [C.c_void_p, C.c_int, C.c_int, P(P(Word))]
+    lib.rt_results_rec_word_text.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int]
+    lib.rt_results_rec_word_text.restype = C.c_char_p
+    lib.rt_debug_word_boxes.argtypes = [C.c_char_p, C.c_size_t, P(C.c_int32), P(C.c_int32), C.c_int, C.c_int, C.c_int, C.c_int,
+                                        P(C.c_float), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, P(Word), P(C.c_int)]
     _lib = lib
     return lib

@@ -33,6 +33,8 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--json", default=None, help="write one JSON object per image (det/cls/rec stage results)")
     ap.add_argument("--det-score-mode", choices=["Fast", "Slow"], default="Fast",
                     help="DetProcessorConfig.score_mode: box score over the min-area rect (Fast) or the contour's own polygon (Slow)")
+    ap.add_argument("--rec-return-word-box", action="store_true",
+                    help="RecProcessorConfig.return_word_box: per-word boxes; each --json line gains a \"words\" array (per line)")
     return ap
 
 
@@ -59,6 +61,7 @@ def main(argv=None) -> int:
             det=S.Path(a.det_model_path), rec=S.Path(a.rec_model_path), cls=S.Path(a.cls_model_path)))
         cfg.rec_processor_config.character_source = S.Path(a.rec_keys_path)
     cfg.det_processor_config.score_mode = a.det_score_mode
+    cfg.rec_processor_config.return_word_box = a.rec_return_word_box
     session = retto_amd.RettoSession(cfg)
     files = walk_files(a.images)
     log.info("Found %d files, processing...", len(files))
@@ -75,12 +78,17 @@ def main(argv=None) -> int:
         n += len(results)
         if out:
             for path, r in zip(chunk, results):
-                out.write(json.dumps({
+                rec = {
                     "file": path,
                     "det": [{"boxes": {"inner": [{"x": p.x, "y": p.y} for p in d.boxes.inner]}, "score": d.score} for d in r.det_result],
                     "cls": [{"label": {"label": c.label.label, "score": c.label.score}} for c in r.cls_result],
                     "rec": [{"text": t.text, "score": None if np.isnan(t.score) else t.score} for t in r.rec_result],
-                }, ensure_ascii=False) + "\n")
+                }
+                if a.rec_return_word_box:   # one list of words per line, in line order
+                    rec["words"] = [[{"text": w.text, "kind": w.kind, "boxes": {"inner": [{"x": p.x, "y": p.y} for p in w.box.inner]},
+                                      "first_token": w.first_token, "n_tokens": w.n_tokens, "first_col": w.first_col,
+                                      "last_col": w.last_col} for w in t.words] for t in r.rec_result]
+                out.write(json.dumps(rec, ensure_ascii=False) + "\n")
     dur = time.perf_counter() - start
     if out:
         out.close()

@@ -100,6 +100,7 @@ void rt_config_default(rt_config* c) {
   c->rec_batch_num = 6;
   c->max_boxes_per_page = 0; c->det_sub_batch = 0; c->lanes = 0; c->dtype = RT_DTYPE_F32;
   c->det_score_mode = 0;
+  c->rec_return_word_box = 0;
 }
 
 int rt_create(const rt_config* cfg, rt_session** out) {
@@ -116,6 +117,8 @@ int rt_create(const rt_config* cfg, rt_session** out) {
   RT_REQUIRE(cfg->max_boxes_per_page >= 0 && cfg->max_boxes_per_page <= 65536, (rt_session*)nullptr,
              "max_boxes_per_page must be in [0, 65536]");
   RT_REQUIRE(cfg->det_score_mode == 0 || cfg->det_score_mode == 1, (rt_session*)nullptr, "det_score_mode must be 0 (Fast) or 1 (Slow)");
+  RT_REQUIRE(cfg->rec_return_word_box == 0 || cfg->rec_return_word_box == 1, (rt_session*)nullptr,
+             "rec_return_word_box must be 0 (off) or 1 (on)");
   capture_variant_defaults();
   return guarded(nullptr, [&] { *out = rt_session_create(cfg); });
 }
@@ -136,6 +139,7 @@ void rt_destroy(rt_session* s) {
   s->free_stage();
   s->det.reset(); s->cls.reset(); s->rec.reset();
   if (s->d_flags) (void)hipFree(s->d_flags);
+  if (s->d_word_raw) (void)hipFree(s->d_word_raw);
   if (s->ev_block) (void)hipEventDestroy(s->ev_block);
   if (s->st_part) { rt::forget_stream(s->st_part); (void)hipStreamDestroy(s->st_part); }
   if (s->st_full) (void)hipStreamDestroy(s->st_full);
@@ -446,6 +450,55 @@ const char* rt_results_rec_text(const rt_results* r, int page, int line) {
   auto* p = RT_PAGE(r, page);
   if (!p || line < 0 || (size_t)line >= p->text.size()) return nullptr;
   return p->text[(size_t)line].c_str();
+}
+static_assert(sizeof(rt_word) == sizeof(wb::Word) && offsetof(rt_word, kind) == offsetof(wb::Word, kind),
+              "rt_word and wb::Word must share one layout");
+int rt_results_rec_words(const rt_results* r, int page, int line, const rt_word** words) {
+  auto* p = RT_PAGE(r, page);
+  if (!p || line < 0 || (size_t)line >= p->words.size()) return 0;
+  if (words) *words = reinterpret_cast<const rt_word*>(p->words[(size_t)line].data());
+  return (int)p->words[(size_t)line].size();
+}
+const char* rt_results_rec_word_text(rt_results* r, int page, int line, int word) {
+  auto* p = RT_PAGE(r, page);
+  if (!p || line < 0 || (size_t)line >= p->word_text.size()) return nullptr;
+  const auto& wt = p->word_text[(size_t)line];
+  if (word < 0 || (size_t)word >= wt.size()) return nullptr;
+  return wt[(size_t)word].c_str();
+}
+int rt_debug_word_boxes(const void* dict, size_t dict_len, const int32_t* tokens, const int32_t* cols, int n, int T, int W,
+                        int resized_w, const float* box8_after, int rot180, int after_w, int after_h, int ori_w, int ori_h,
+                        rt_word* out, int* n_words) {
+  if ((!dict && dict_len) || !box8_after || !n_words || n < 0 || (n > 0 && (!tokens || !cols || !out))) return RT_ERR_INVALID;
+  if (T <= 0 || W <= 0 || after_w <= 0 || after_h <= 0 || ori_w <= 0 || ori_h <= 0) return RT_ERR_INVALID;
+  *n_words = 0;
+  try {
+    std::vector<uint8_t> bytes((const uint8_t*)dict, (const uint8_t*)dict + dict_len);
+    const std::vector<std::string> d = rt::load_dictionary(bytes);
+    std::vector<uint8_t> raw(d.size());
+    for (size_t i = 0; i < d.size(); i++) raw[i] = wb::raw_class(d[i].data(), d[i].size());
+    for (int k = 0; k < n; k++) {
+      if (tokens[k] < 0 || (size_t)tokens[k] >= d.size()) return RT_ERR_INVALID;
+      if (cols[k] < 0 || cols[k] >= T || (k > 0 && cols[k] <= cols[k - 1])) return RT_ERR_INVALID;
+    }
+    // the crop as plan_crops (session.cpp) derives it
+    const gm::CropDims cd = gm::crop_dims(box8_after);
+    if (cd.w <= 0 || cd.h <= 0) return RT_ERR_IMAGE;
+    wb::WordGeom g;
+    if (!gm::projection_inverse(box8_after, cd.cw, cd.ch, g.inv)) return RT_ERR_IMAGE;
+    g.T = T; g.W = W; g.resized_w = resized_w;
+    g.w_c = cd.rot ? cd.h : cd.w; g.h_c = cd.rot ? cd.w : cd.h;
+    g.rot270 = cd.rot; g.w = cd.w; g.h = cd.h; g.cw = cd.cw; g.ch = cd.ch;
+    wb::Word* o = reinterpret_cast<wb::Word*>(out);
+    const int nw = wb::line_words(raw.data(), tokens, cols, n, g, rot180 ? 1 : 0, o);
+    for (int j = 0; j < nw; j++) gm::scale_and_clip(o[j].quad, (double)after_w, (double)after_h, (double)ori_w, (double)ori_h);
+    *n_words = nw;
+    return RT_OK;
+  } catch (const RtError& e) {
+    return e.code;
+  } catch (const std::exception&) {
+    return RT_ERR_BACKEND;
+  }
 }
 double rt_results_det_checksum(const rt_results* r) { return r ? r->det_checksum : 0.0; }
 const char* rt_results_json(rt_results* r, int page, int stage) {

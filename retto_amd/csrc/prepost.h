@@ -4,6 +4,7 @@
 #pragma once
 #include "nn.h"
 #include "common.h"
+#include "word_boxes.h"
 
 namespace rt {
 namespace pp {
@@ -68,6 +69,15 @@ void resize_norm(hipStream_t st, const LineDesc* lines, int n, int img_h, int ma
 // tok_off[i] = first row of line i, T[i] rows; tokens written compacted at the same offsets.
 void ctc_decode(hipStream_t st, const int* idx, const float* prob, const ImgGeom* lines, int n, int* tokens,
                 int* n_tokens, float* score);
+
+// rt_config.rec_return_word_box: the words of n lines of one rec group (word_boxes.h), one wave64 per line.  idx: the group's
+// argmax rows; tokens / n_tokens: what ctc_decode wrote for the same lines; label / cls_score: the lines' cls results (the
+// rotate180 predicate of cls_post_rotate); raw_of_id: the session's class table.  Per line i: word count -> n_words[i], words
+// -> words[tok_off ...] (a line has at most as many words as kept tokens); cols: scratch of the group's token count.
+struct WordLineDesc { long long tok_off; wb::WordGeom g; };   // tok_off: first argmax row of the line inside the group
+void word_boxes(hipStream_t st, const int* idx, const int* tokens, const int* n_tokens, const int* label, const float* cls_score,
+                float cls_thresh, const uint8_t* raw_of_id, const WordLineDesc* lines, int n, int* cols, int* n_words,
+                wb::Word* words);
 
 // sum of a float buffer into per-block doubles (partials has ceil(n/65536) entries)
 int sum_blocks(long long n);

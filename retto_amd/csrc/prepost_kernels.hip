@@ -294,6 +294,41 @@ void ctc_decode(hipStream_t st, const int* idx, const float* prob, const ImgGeom
   RT_LAUNCH(k_ctc_decode, dim3((n + 63) / 64), dim3(64), 0, st, idx, prob, lines, n, tokens, n_tokens, score);
 }
 
+// rt_config.rec_return_word_box (word_boxes.h).  One wave64 per line: the kept columns (the selection k_ctc_decode makes) are
+// compacted 64 time steps at a time with a ballot and a popcount prefix; then lane 0 runs the header's segmentation and
+// geometry, which is serial in token order (the CJK pitch is an f32 sum in run order).
+__global__ __launch_bounds__(64) void k_word_boxes(const int* __restrict__ idx, const int* __restrict__ tokens,
+                                                   const int* __restrict__ n_tokens, const int* __restrict__ label,
+                                                   const float* __restrict__ cls_score, float thresh,
+                                                   const u8* __restrict__ raw_of_id, const WordLineDesc* __restrict__ lines,
+                                                   int* __restrict__ cols, int* __restrict__ n_words, wb::Word* __restrict__ words) {
+  const int line = blockIdx.x, lane = threadIdx.x;
+  const WordLineDesc d = lines[line];
+  const int* id = idx + d.tok_off;
+  int* col = cols + d.tok_off;
+  int kept = 0;
+  for (int t0 = 0; t0 < d.g.T; t0 += 64) {
+    const int t = t0 + lane;
+    bool sel = false;
+    if (t < d.g.T) { const int v = id[t]; sel = v != 0 && (t == 0 || v != id[t - 1]); }
+    const unsigned long long m = __ballot(sel);
+    if (sel) col[kept + __popcll(m & ((1ull << lane) - 1ull))] = t;
+    kept += __popcll(m);
+  }
+  __syncthreads();   // the columns other lanes wrote, for lane 0
+  if (lane != 0) return;
+  const int n = min(kept, n_tokens[line]);   // (equal: the same selection)
+  const int rot180 = (label[line] == 1 && cls_score[line] >= thresh) ? 1 : 0;
+  n_words[line] = wb::line_words(raw_of_id, tokens + d.tok_off, col, n, d.g, rot180, words + d.tok_off);
+}
+void word_boxes(hipStream_t st, const int* idx, const int* tokens, const int* n_tokens, const int* label, const float* cls_score,
+                float cls_thresh, const uint8_t* raw_of_id, const WordLineDesc* lines, int n, int* cols, int* n_words,
+                wb::Word* words) {
+  if (n <= 0) return;
+  RT_LAUNCH(k_word_boxes, dim3(n), dim3(64), 0, st, idx, tokens, n_tokens, label, cls_score, cls_thresh, raw_of_id, lines, cols,
+            n_words, words);
+}
+
 // ===========================================================================
 // (round 5: 8192 values per block, 16-byte loads -- was 65536 per block, scalar: one 960 x 960 map ran on 15 workgroups for 77 us,
 //  6 % of the C2 call)

@@ -135,11 +135,18 @@ rt_session* rt_session_create(const rt_config* cfg) {
   RT_HIP_CHECK(hipMalloc((void**)&s->d_flags, 64));
   RT_HIP_CHECK(hipMemset(s->d_flags, 0, 64));
   RT_HIP_CHECK(hipEventCreateWithFlags(&s->ev_block, hipEventBlockingSync | hipEventDisableTiming));
+  if (cfg->rec_return_word_box) {   // the class table of k_word_boxes, once per session
+    std::vector<uint8_t> raw(s->dict.size());
+    for (size_t i = 0; i < raw.size(); i++) raw[i] = rt::wb::raw_class(s->dict[i].data(), s->dict[i].size());
+    RT_HIP_CHECK(hipMalloc((void**)&s->d_word_raw, raw.size()));
+    RT_HIP_CHECK(hipMemcpy(s->d_word_raw, raw.data(), raw.size(), hipMemcpyHostToDevice));
+  }
   const int lanes = cfg->lanes > 0 ? cfg->lanes : 3;  // measured on C3: 1 -> 640, 2 -> 681, 3 -> 700, 4 -> 652 images/s
   for (int l = 1; l < lanes; l++) {
     std::unique_ptr<rt_session> h(new rt_session());
     h->cfg = s->cfg; h->device = s->device;
     h->det = s->det; h->cls = s->cls; h->rec = s->rec; h->dict = s->dict; h->model_info = s->model_info;
+    h->d_word_raw = s->d_word_raw;
     RT_HIP_CHECK(hipStreamCreateWithFlags(&h->st_full, hipStreamNonBlocking));
     h->st = h->st_full;
     RT_HIP_CHECK(hipMalloc((void**)&h->d_flags, 64));
@@ -387,6 +394,7 @@ void rt_session::det_postprocess(const float* pred, int h, int w, int ori_h, int
 struct CropPlan {
   std::vector<pp::CropDesc> descs;
   std::vector<pp::CropRef> refs;
+  std::vector<gm::CropDims> dims;   // per crop: what the word boxes map back through (cw, ch)
   size_t pool_bytes = 0;
   int max_pix = 0;
 };
@@ -402,7 +410,7 @@ static void plan_crops(CropPlan& plan, const uint8_t* src, int sh, int sw, const
       throw RtError(RT_ERR_IMAGE, "singular crop homography (Projection::from_control_points -> None; the reference unwraps)");
     cd.out_off = (long long)plan.pool_bytes;
     pp::CropRef r; r.off = cd.out_off; r.h = d.rot ? d.w : d.h; r.w = d.rot ? d.h : d.w; r.pad_ = 0;
-    plan.descs.push_back(cd); plan.refs.push_back(r);
+    plan.descs.push_back(cd); plan.refs.push_back(r); plan.dims.push_back(d);
     plan.pool_bytes += ((size_t)d.w * d.h * 3 + 63) & ~(size_t)63;
     plan.max_pix = std::max(plan.max_pix, d.w * d.h);
   }
@@ -724,6 +732,8 @@ rt_results* rt_session::run_pages(const uint8_t* const* rgb, const int* hs, cons
   const int* h_label = h_meta; const float* h_cscore = reinterpret_cast<const float*>(h_meta + NLp);
   const int* h_ntok = h_meta + 2 * NLp; const float* h_rscore = reinterpret_cast<const float*>(h_meta + 3 * NLp);
   const int* h_tokens = nullptr; std::vector<long long> tok_off((size_t)NL + 1, 0);
+  const bool words_on = cfg.rec_return_word_box != 0;
+  const int* h_wcount = nullptr; const wb::Word* h_words = nullptr;   // rec_return_word_box
   if (NL > 0) {
     uint8_t* pool = arena.alloc<uint8_t>(plan.pool_bytes + 64);
     pp::CropDesc* d_desc = arena.alloc<pp::CropDesc>(NL);
@@ -818,6 +828,13 @@ rt_results* rt_session::run_pages(const uint8_t* const* rgb, const int* hs, cons
     int* d_idx = arena.alloc<int>(std::max<long long>(total_tok, 1));
     float* d_prob = arena.alloc<float>(std::max<long long>(total_tok, 1));
     int* d_tok = arena.alloc<int>(std::max<long long>(total_tok, 1));
+    // rec_return_word_box: word count per line, words at the lines' token offsets, the kept columns (k_word_boxes' scratch)
+    int* d_wcount = nullptr; wb::Word* d_words = nullptr; int* d_wcol = nullptr;
+    if (words_on) {
+      d_wcount = arena.alloc<int>(NLp);
+      d_words = arena.alloc<wb::Word>(std::max<long long>(total_tok, 1));
+      d_wcol = arena.alloc<int>(std::max<long long>(total_tok, 1));
+    }
     static const long long REC_GROUP_PX = getenv("RT_REC_GROUP_PX") ? atoll(getenv("RT_REC_GROUP_PX")) : (long long)24000000;  // measured sweet spot (profiles/README.md)
     for (int l0 = 0; l0 < NL;) {
       int l1 = l0; long long px = 0;
@@ -847,6 +864,25 @@ rt_results* rt_session::run_pages(const uint8_t* const* rgb, const int* hs, cons
       if (Lt.total != tok_off[l1] - tok_off[l0]) throw RtError(RT_ERR_SHAPE, "token count mismatch");
       { ProfScope ps(&prof, st, "ctc_decode");
         pp::ctc_decode(st, d_idx + tok_off[l0], d_prob + tok_off[l0], Lt.d, ln, d_tok + tok_off[l0], d_ntok + l0, d_rscore + l0); }
+      if (words_on) {
+        pp::WordLineDesc* hw = pinned.alloc<pp::WordLineDesc>(ln);
+        for (int k = 0; k < ln; k++) {
+          const int li = l0 + k;
+          const pp::CropRef& r = plan.refs[li];
+          const pp::CropDesc& cd = plan.descs[li];
+          pp::WordLineDesc& D = hw[k];
+          D.tok_off = tok_off[li] - tok_off[l0];
+          D.g.T = (int)(tok_off[li + 1] - tok_off[li]); D.g.W = line_W[li]; D.g.resized_w = lines[li].resized_w;
+          D.g.w_c = r.w; D.g.h_c = r.h; D.g.rot270 = cd.rot; D.g.w = cd.w; D.g.h = cd.h;
+          D.g.cw = plan.dims[li].cw; D.g.ch = plan.dims[li].ch;
+          memcpy(D.g.inv, cd.inv, sizeof D.g.inv);
+        }
+        pp::WordLineDesc* dw = scratch.alloc<pp::WordLineDesc>(ln);
+        RT_HIP_CHECK(hipMemcpyAsync(dw, hw, (size_t)ln * sizeof(pp::WordLineDesc), hipMemcpyHostToDevice, st));
+        ProfScope ps(&prof, st, "word_boxes");
+        pp::word_boxes(st, d_idx + tok_off[l0], d_tok + tok_off[l0], d_ntok + l0, d_label + l0, d_cscore + l0, cfg.cls_thresh,
+                       d_word_raw, dw, ln, d_wcol + tok_off[l0], d_wcount + l0, d_words + tok_off[l0]);
+      }
       l0 = l1;
     }
     tick.lap("rec enqueue");
@@ -855,6 +891,13 @@ rt_results* rt_session::run_pages(const uint8_t* const* rgb, const int* hs, cons
     h_tokens = h_tok;
     RT_HIP_CHECK(hipMemcpyAsync(h_meta, d_meta, (size_t)4 * NLp * sizeof(int), hipMemcpyDeviceToHost, st));
     if (total_tok > 0) RT_HIP_CHECK(hipMemcpyAsync(h_tok, d_tok, (size_t)total_tok * 4, hipMemcpyDeviceToHost, st));
+    if (words_on) {   // (the words ride with the tokens: same round trip)
+      int* hc = pinned.alloc<int>(NLp);
+      wb::Word* hwd = pinned.alloc<wb::Word>((size_t)std::max<long long>(total_tok, 1));
+      RT_HIP_CHECK(hipMemcpyAsync(hc, d_wcount, (size_t)NL * sizeof(int), hipMemcpyDeviceToHost, st));
+      if (total_tok > 0) RT_HIP_CHECK(hipMemcpyAsync(hwd, d_words, (size_t)total_tok * sizeof(wb::Word), hipMemcpyDeviceToHost, st));
+      h_wcount = hc; h_words = hwd;
+    }
     sync(); check_flags();
   }
 
@@ -879,6 +922,21 @@ rt_results* rt_session::run_pages(const uint8_t* const* rgb, const int* hs, cons
       std::string& t = P.text[k];
       t.reserve(P.tokens[k].size() * 3);  // CJK dictionary entries are 3 UTF-8 bytes
       for (int id : P.tokens[k]) t += dict[(size_t)id];
+    }
+    if (words_on) {   // word quads to original-image coordinates, word texts from the dictionary
+      P.words.resize(nb); P.word_text.resize(nb);
+      for (int k = 0; k < nb; k++) {
+        const int li = p.first_line + k;
+        const int nw = std::min(std::max(h_wcount[li], 0), h_ntok[li]);
+        std::vector<wb::Word>& W = P.words[k];
+        W.assign(h_words + tok_off[li], h_words + tok_off[li] + nw);
+        P.word_text[k].resize((size_t)nw);
+        for (int j = 0; j < nw; j++) {
+          gm::scale_and_clip(W[j].quad, (double)p.after_w, (double)p.after_h, (double)p.ori_w, (double)p.ori_h);
+          std::string& t = P.word_text[k][(size_t)j];
+          for (int q = W[j].first_token; q < W[j].first_token + W[j].n_tokens; q++) t += dict[(size_t)P.tokens[k][(size_t)q]];
+        }
+      }
     }
   }
   if (stage_cb)

@@ -30,6 +30,9 @@ struct rt_results {
     std::vector<float> rec_scores;
     std::vector<std::vector<int32_t>> tokens;
     std::vector<std::string> text;
+    // rt_config.rec_return_word_box: per line its words (quads in original-image coordinates) and their texts; empty when off
+    std::vector<std::vector<rt::wb::Word>> words;
+    std::vector<std::vector<std::string>> word_text;
     std::string json[3];
   };
   std::vector<Page> pages;
@@ -111,6 +114,7 @@ struct rt_session {
   std::vector<std::unique_ptr<rt_session>> helpers;
   int active_lanes = 1 << 30;  // rt_set_lanes: upper bound on the lanes rt_run_batch uses
   std::vector<std::string> dict;  // RecCharacter (rec_processor.rs:29-46)
+  uint8_t* d_word_raw = nullptr;  // rec_return_word_box: wb::raw_class of every dictionary entry (device; owned by the main lane)
   std::string last_error;
   int* d_flags = nullptr;         // [0] thumbnail/resize error flag
   // run_stream (session.rs:133-143): stage results are handed to the callback as soon as the stage is complete --
