@@ -365,21 +365,29 @@ static pp::DbParams db_params(const rt_config& c) {
 }
 static int max_boxes_of(const rt_config& c) { return c.max_boxes_per_page > 0 ? c.max_boxes_per_page : 8192; }
 
+// a5 (det_processor.rs:279-335) enqueued for n pages with shared launches: page i's boxes go to boxes[i * max_boxes_of ...],
+// its count and overflow flag to counts[2 i], counts[2 i + 1]
+static void db_post_enqueue(rt_session& s, int n, const pp::DbPageIn* in, pp::DbBox* boxes, int* counts) {
+  const int mb = max_boxes_of(s.cfg);
+  std::vector<void*> wsp((size_t)n); std::vector<pp::DbBox*> bo((size_t)n); std::vector<int*> co((size_t)n);
+  for (int i = 0; i < n; i++) {
+    wsp[i] = s.dbws.alloc_bytes(pp::db_workspace_bytes(in[i].H, in[i].W, mb, s.cfg.det_score_mode));
+    bo[i] = boxes + (size_t)i * mb; co[i] = counts + 2 * i;
+  }
+  void* hd = s.pinned.alloc_bytes((size_t)n * pp::db_page_desc_bytes());
+  void* dd = s.arena.alloc_bytes((size_t)n * pp::db_page_desc_bytes());
+  pp::db_postprocess_batch(s.st, n, in, db_params(s.cfg), wsp.data(), mb, bo.data(), co.data(), hd, dd);
+}
+
 void rt_session::det_postprocess(const float* pred, int h, int w, int ori_h, int ori_w, float* boxes, float* scores,
                                  int max_out, int* n_out) {
   begin_call();
   float* d = arena.alloc<float>((size_t)h * w);
   RT_HIP_CHECK(hipMemcpyAsync(d, pred, (size_t)h * w * 4, hipMemcpyHostToDevice, st));
-  const int mb = max_boxes_of(cfg);
-  void* ws = dbws.alloc_bytes(pp::db_workspace_bytes(h, w, mb, cfg.det_score_mode));
-  pp::DbBox* db = arena.alloc<pp::DbBox>(mb);
+  pp::DbBox* db = arena.alloc<pp::DbBox>(max_boxes_of(cfg));
   int* cnt = arena.alloc<int>(2);
-  {
-    pp::DbPageIn in{d, h, w, ori_h, ori_w};
-    void* hd = pinned.alloc_bytes(pp::db_page_desc_bytes());
-    void* dd = arena.alloc_bytes(pp::db_page_desc_bytes());
-    pp::db_postprocess_batch(st, 1, &in, db_params(cfg), &ws, mb, &db, &cnt, hd, dd);
-  }
+  const pp::DbPageIn in{d, h, w, ori_h, ori_w};
+  db_post_enqueue(*this, 1, &in, db, cnt);
   int hc[2];
   RT_HIP_CHECK(hipMemcpyAsync(hc, cnt, 8, hipMemcpyDeviceToHost, st));
   sync();
@@ -398,22 +406,36 @@ struct CropPlan {
   size_t pool_bytes = 0;
   int max_pix = 0;
 };
-// image_helper.rs:223-249 planning for the boxes of one page (src = device page after resize_both)
-static void plan_crops(CropPlan& plan, const uint8_t* src, int sh, int sw, const float* boxes, int n) {
-  for (int i = 0; i < n; i++) {
-    const float* b = boxes + 8 * i;
-    gm::CropDims d = gm::crop_dims(b);
-    if (d.w <= 0 || d.h <= 0) throw RtError(RT_ERR_IMAGE, "zero-sized crop");
-    pp::CropDesc cd;
-    cd.src = src; cd.sh = sh; cd.sw = sw; cd.w = d.w; cd.h = d.h; cd.rot = d.rot;
-    if (!gm::projection_inverse(b, d.cw, d.ch, cd.inv))
-      throw RtError(RT_ERR_IMAGE, "singular crop homography (Projection::from_control_points -> None; the reference unwraps)");
-    cd.out_off = (long long)plan.pool_bytes;
-    pp::CropRef r; r.off = cd.out_off; r.h = d.rot ? d.w : d.h; r.w = d.rot ? d.h : d.w; r.pad_ = 0;
-    plan.descs.push_back(cd); plan.refs.push_back(r); plan.dims.push_back(d);
-    plan.pool_bytes += ((size_t)d.w * d.h * 3 + 63) & ~(size_t)63;
-    plan.max_pix = std::max(plan.max_pix, d.w * d.h);
-  }
+// image_helper.rs:223-249 planning for one box b[8] of a page (src = device page after resize_both)
+static void plan_crop(CropPlan& plan, const uint8_t* src, int sh, int sw, const float* b) {
+  gm::CropDims d = gm::crop_dims(b);
+  if (d.w <= 0 || d.h <= 0) throw RtError(RT_ERR_IMAGE, "zero-sized crop");
+  pp::CropDesc cd;
+  cd.src = src; cd.sh = sh; cd.sw = sw; cd.w = d.w; cd.h = d.h; cd.rot = d.rot;
+  if (!gm::projection_inverse(b, d.cw, d.ch, cd.inv))
+    throw RtError(RT_ERR_IMAGE, "singular crop homography (Projection::from_control_points -> None; the reference unwraps)");
+  cd.out_off = (long long)plan.pool_bytes;
+  pp::CropRef r; r.off = cd.out_off; r.h = d.rot ? d.w : d.h; r.w = d.rot ? d.h : d.w; r.pad_ = 0;
+  plan.descs.push_back(cd); plan.refs.push_back(r); plan.dims.push_back(d);
+  plan.pool_bytes += ((size_t)d.w * d.h * 3 + 63) & ~(size_t)63;
+  plan.max_pix = std::max(plan.max_pix, d.w * d.h);
+}
+// a6: the plan's descriptors and crop refs to the device through pinned staging, then every crop warped into one pool (returned;
+// *d_refs: the refs on the device, what cls_post_rotate reads).  The plan holds at least one crop.
+static uint8_t* warp_planned_crops(rt_session& s, const CropPlan& plan, pp::CropRef** d_refs) {
+  const int n = (int)plan.descs.size();
+  uint8_t* pool = s.arena.alloc<uint8_t>(plan.pool_bytes + 64);
+  pp::CropDesc* d_desc = s.arena.alloc<pp::CropDesc>(n);
+  *d_refs = s.arena.alloc<pp::CropRef>(n);
+  pp::CropDesc* hd = s.pinned.alloc<pp::CropDesc>(n);
+  pp::CropRef* hr = s.pinned.alloc<pp::CropRef>(n);
+  memcpy(hd, plan.descs.data(), (size_t)n * sizeof(pp::CropDesc));
+  memcpy(hr, plan.refs.data(), (size_t)n * sizeof(pp::CropRef));
+  RT_HIP_CHECK(hipMemcpyAsync(d_desc, hd, (size_t)n * sizeof(pp::CropDesc), hipMemcpyHostToDevice, s.st));
+  RT_HIP_CHECK(hipMemcpyAsync(*d_refs, hr, (size_t)n * sizeof(pp::CropRef), hipMemcpyHostToDevice, s.st));
+  ProfScope ps(&s.prof, s.st, "warp_crops");
+  pp::warp_crops(s.st, d_desc, n, plan.max_pix, pool);
+  return pool;
 }
 
 void rt_session::crop_images(const uint8_t* rgb, int h, int w, const float* boxes, int n, uint8_t* out, size_t out_cap) {
@@ -421,21 +443,26 @@ void rt_session::crop_images(const uint8_t* rgb, int h, int w, const float* boxe
   uint8_t* d = arena.alloc<uint8_t>((size_t)h * w * 3);
   RT_HIP_CHECK(hipMemcpyAsync(d, rgb, (size_t)h * w * 3, hipMemcpyHostToDevice, st));
   CropPlan plan;
-  plan_crops(plan, d, h, w, boxes, n);
+  for (int i = 0; i < n; i++) plan_crop(plan, d, h, w, boxes + 8 * i);
   size_t need = 0;
   for (auto& r : plan.refs) need += (size_t)r.h * r.w * 3;
   if (need > out_cap) throw RtError(RT_ERR_INVALID, "crop_images: output buffer too small");
-  uint8_t* pool = arena.alloc<uint8_t>(std::max<size_t>(plan.pool_bytes, 64));
-  pp::CropDesc* dd = arena.alloc<pp::CropDesc>(std::max(n, 1));
-  if (n > 0) RT_HIP_CHECK(hipMemcpyAsync(dd, plan.descs.data(), (size_t)n * sizeof(pp::CropDesc), hipMemcpyHostToDevice, st));
-  pp::warp_crops(st, dd, n, plan.max_pix, pool);
-  size_t o = 0;
-  for (int i = 0; i < n; i++) {
-    size_t bytes = (size_t)plan.refs[i].h * plan.refs[i].w * 3;
-    RT_HIP_CHECK(hipMemcpyAsync(out + o, pool + plan.refs[i].off, bytes, hipMemcpyDeviceToHost, st));
-    o += bytes;
+  if (n > 0) {
+    pp::CropRef* d_refs;
+    const uint8_t* pool = warp_planned_crops(*this, plan, &d_refs);
+    for (const pp::CropRef& r : plan.refs) {
+      const size_t bytes = (size_t)r.h * r.w * 3;
+      RT_HIP_CHECK(hipMemcpyAsync(out, pool + r.off, bytes, hipMemcpyDeviceToHost, st));
+      out += bytes;
+    }
   }
   sync();
+}
+
+// image_helper.rs:176-209: the line of crop r resized to height img_h and padded to width W; the resized width follows the
+// crop's original dims ori_h x ori_w (inside the pipeline: the crop's own dims)
+static pp::LineDesc line_desc(const pp::CropRef& r, int ori_h, int ori_w, int img_h, int W) {
+  return pp::LineDesc{r.off, r.h, r.w, gm::resize_norm_resized_w(img_h, W, ori_h, ori_w), W, 0};
 }
 
 void rt_session::resize_norm_image(const uint8_t* crop, int h, int w, int ori_h, int ori_w, int img_h, int img_w,
@@ -443,16 +470,14 @@ void rt_session::resize_norm_image(const uint8_t* crop, int h, int w, int ori_h,
   begin_call();
   uint8_t* d = arena.alloc<uint8_t>(std::max<size_t>((size_t)h * w * 3, 4));
   RT_HIP_CHECK(hipMemcpyAsync(d, crop, (size_t)h * w * 3, hipMemcpyHostToDevice, st));
-  pp::LineDesc L;
-  L.crop_off = 0; L.h = h; L.w = w;
-  L.W = gm::resize_norm_width(img_h, img_w, ratio);
-  L.resized_w = gm::resize_norm_resized_w(img_h, L.W, ori_h, ori_w);
-  L.out_off = 0;
+  pp::LineDesc* hl = pinned.alloc<pp::LineDesc>(1);
+  const int W = gm::resize_norm_width(img_h, img_w, ratio);
+  *hl = line_desc(pp::CropRef{0, h, w, 0}, ori_h, ori_w, img_h, W);
   pp::LineDesc* dl = arena.alloc<pp::LineDesc>(1);
-  RT_HIP_CHECK(hipMemcpyAsync(dl, &L, sizeof(L), hipMemcpyHostToDevice, st));
-  float* o = arena.alloc<float>((size_t)3 * img_h * std::max(L.W, 1));
-  pp::resize_norm(st, dl, 1, img_h, L.W, d, 1, o, d_flags);
-  RT_HIP_CHECK(hipMemcpyAsync(out, o, (size_t)3 * img_h * L.W * 4, hipMemcpyDeviceToHost, st));
+  RT_HIP_CHECK(hipMemcpyAsync(dl, hl, sizeof(pp::LineDesc), hipMemcpyHostToDevice, st));
+  float* o = arena.alloc<float>((size_t)3 * img_h * std::max(W, 1));
+  pp::resize_norm(st, dl, 1, img_h, W, d, 1, o, d_flags);
+  RT_HIP_CHECK(hipMemcpyAsync(out, o, (size_t)3 * img_h * W * 4, hipMemcpyDeviceToHost, st));
   sync(); check_flags();
 }
 
@@ -478,19 +503,7 @@ void rt_session::ctc_decode(const float* probs, int n, int t, int c, int32_t* id
   sync();
 }
 
-// ---------------------------------------------------------------------------
-// L2: process_pipeline over a batch of pages
-// ---------------------------------------------------------------------------
 namespace {
-struct PageState {
-  int ori_h, ori_w, after_h, after_w, det_h, det_w;
-  const uint8_t* img;  // device, after resize_both
-  const float* map;    // device det map used for boxes
-  pp::DbBox* d_boxes; int* d_count;
-  int n_boxes = 0; int first_line = 0;
-  std::vector<pp::DbBox> boxes;
-};
-
 std::string json_escape(const std::string& s) {
   std::string o;
   for (char ch : s) {
@@ -541,6 +554,356 @@ std::string fnum(float v) {
   }
   return o;
 }
+
+// ---------------------------------------------------------------------------
+// L2: process_pipeline over a batch of pages, one function per stage over the call's state
+// ---------------------------------------------------------------------------
+struct PageState {
+  int ori_h, ori_w, after_h, after_w, det_h, det_w;
+  const uint8_t* img;      // device, after resize_both
+  const uint8_t* det_img;  // device, det input size (RGB8: the det stem normalises it)
+  const float* map;        // device det map used for boxes
+  int n_boxes = 0; int first_line = 0;
+  const pp::DbBox* boxes = nullptr;  // pinned: the page's part of round trip #1
+};
+// per-line results: views of one [4][NLp] block of 32-bit words (label first), so that one copy brings them to the host
+struct LineMeta {
+  int* label = nullptr; float* cscore = nullptr; int* ntok = nullptr; float* rscore = nullptr;
+  void view(int* m, int NLp) { label = m; cscore = reinterpret_cast<float*>(m + NLp); ntok = m + 2 * NLp; rscore = reinterpret_cast<float*>(m + 3 * NLp); }
+};
+// the state of one run_pages call; device and pinned buffers live until the next begin_call
+struct Pipeline {
+  int n_pages, mem; const float* const* det_map_override;
+  std::vector<PageState> pg;
+  std::vector<double*> sum_parts; std::vector<int> sum_counts;   // det map checksum partials per det group (device)
+  int* d_counts = nullptr;                  // [n_pages][2]: box count, overflow flag
+  pp::DbBox* d_boxes_packed = nullptr;      // every page's boxes, packed in page order
+  int NL = 0, NLp = 1;                      // lines of the call; NLp = max(NL, 1) sizes the per-line buffers
+  CropPlan plan; uint8_t* pool = nullptr; pp::CropRef* d_refs = nullptr;   // the crops: their plan, pool and refs (device)
+  LineMeta h_meta, d_meta;
+  std::vector<pp::LineDesc> lines; std::vector<int> line_W;  // rec: per line its resize_norm descriptor and width
+  std::vector<long long> tok_off;           // [NL + 1]: first token of every line
+  int* d_tok = nullptr; int* h_tokens = nullptr;   // CTC tokens at tok_off
+  int* d_wcount = nullptr; wb::Word* d_words = nullptr; int* h_wcount = nullptr; wb::Word* h_words = nullptr;   // rec_return_word_box
+};
+
+// Launch groups: items [g0, end) where the group always takes its first item; with max_items > 0 it takes up to max_items items,
+// otherwise items while their pixels px_of(i) sum to at most budget_px.
+template <class PxOf>
+int group_end(int g0, int n, int max_items, long long budget_px, PxOf px_of) {
+  int g1 = g0; long long px = 0;
+  while (g1 < n) {
+    const long long add = px_of(g1);
+    if (g1 > g0 && (max_items > 0 ? g1 - g0 >= max_items : px + add > budget_px)) break;
+    px += add; g1++;
+  }
+  return g1;
+}
+// a page's boxes (after_* coordinates) to original-image corners, and their scores (session.rs:94-105)
+void page_boxes(const PageState& p, rt_results::Page& P) {
+  P.boxes.resize((size_t)p.n_boxes * 8); P.det_scores.resize((size_t)p.n_boxes);
+  for (int k = 0; k < p.n_boxes; k++) {
+    memcpy(&P.boxes[8 * k], p.boxes[k].pts, 32);
+    gm::scale_and_clip(&P.boxes[8 * k], (double)p.after_w, (double)p.after_h, (double)p.ori_w, (double)p.ori_h);
+    P.det_scores[k] = p.boxes[k].score;
+  }
+}
+// ---- a2 + a3: size limits, det resize (the normalise is folded into the det stem) ----
+void page_sizes(rt_session& s, Pipeline& P, const uint8_t* const* rgb, const int* hs, const int* ws) {
+  for (int i = 0; i < P.n_pages; i++) {
+    PageState& p = P.pg[i];
+    p.ori_h = hs[i]; p.ori_w = ws[i];
+    if (hs[i] <= 0 || ws[i] <= 0 || rgb[i] == nullptr) throw RtError(RT_ERR_IMAGE, "empty page");
+    const uint8_t* raw = rgb[i];
+    if (P.mem == RT_MEM_HOST || P.mem == RT_MEM_HOST_MAPS_DEVICE) {   // the pages cross PCIe here (a submitted batch staged them already)
+      uint8_t* d = s.arena.alloc<uint8_t>((size_t)hs[i] * ws[i] * 3);
+      RT_HIP_CHECK(hipMemcpyAsync(d, rgb[i], (size_t)hs[i] * ws[i] * 3, hipMemcpyHostToDevice, s.st));
+      raw = d;
+    }
+    p.img = dev_resize_both(&s, raw, hs[i], ws[i], &p.after_h, &p.after_w);
+    if (p.after_h <= 0 || p.after_w <= 0) throw RtError(RT_ERR_SHAPE, "page collapses to zero size in resize_both");
+    gm::resize_either_dims(p.after_h, p.after_w, s.cfg.det_limit_type, s.cfg.det_limit_side_len, &p.det_h, &p.det_w);
+    if (p.det_h <= 0 || p.det_w <= 0) throw RtError(RT_ERR_SHAPE, "det input collapses to zero size");
+    if (p.det_h == p.after_h && p.det_w == p.after_w) p.det_img = p.img;  // thumbnail at ratio 1 is the identity
+    else {
+      uint8_t* d = s.arena.alloc<uint8_t>((size_t)p.det_h * p.det_w * 3);
+      ProfScope ps(&s.prof, s.st, "thumbnail");
+      pp::thumbnail_rgb8(s.st, p.img, p.after_h, p.after_w, d, p.det_h, p.det_w, s.d_flags);
+      p.det_img = d;
+    }
+  }
+}
+// ---- a4: det network in launch groups ----------------------------------------------
+void det_groups(rt_session& s, Pipeline& P) {
+  const long long group_px = (long long)32 * 960 * 960;  // measured: larger launch groups win (launch-bound small layers)
+  for (int g0 = 0; g0 < P.n_pages;) {
+    const int g1 = group_end(g0, P.n_pages, s.cfg.det_sub_batch, group_px,
+                             [&](int i) { return (long long)P.pg[i].det_h * P.pg[i].det_w; });
+    const int gn = g1 - g0;
+    std::vector<std::pair<int, int>> hw;
+    for (int i = g0; i < g1; i++) hw.push_back({P.pg[i].det_h, P.pg[i].det_w});
+    Level L0 = make_level(hw);
+    s.scratch.rewind();
+    // the pages stay RGB8 until the first conv reads them (DetNet::run_u8)
+    nn::U8Page* hd = s.pinned.alloc<nn::U8Page>((size_t)gn);
+    nn::U8Page* dd = s.scratch.alloc<nn::U8Page>((size_t)gn);
+    for (int i = g0; i < g1; i++)
+      hd[i - g0] = nn::U8Page{P.pg[i].det_img, (long long)P.pg[i].det_h * P.pg[i].det_w, L0.h[i - g0].off};
+    RT_HIP_CHECK(hipMemcpyAsync(dd, hd, (size_t)gn * sizeof(nn::U8Page), hipMemcpyHostToDevice, s.st));
+    RunCtx c = s.ctx(&s.scratch);
+    float* map;
+    { ProfOuter po(&s.prof, s.st, "net/det"); map = s.det->run_u8(c, dd, s.cfg.det_scale, s.cfg.det_mean, s.cfg.det_std, L0); }
+    // keep the maps beyond the next group's scratch rewind; the last group's map is consumed by the DB post-processing
+    // (same stream) before the classifier reuses the scratch arena, so it stays where the network left it
+    float* keep = map;
+    if (g1 < P.n_pages) {
+      keep = s.arena.alloc<float>((size_t)L0.total);
+      RT_HIP_CHECK(hipMemcpyAsync(keep, map, (size_t)L0.total * 4, hipMemcpyDeviceToDevice, s.st));
+    }
+    for (int i = g0; i < g1; i++) P.pg[i].map = keep + L0.h[i - g0].off;
+    int nb = pp::sum_blocks(L0.total);
+    double* parts = s.arena.alloc<double>(nb);
+    pp::sum_partial(s.st, keep, L0.total, parts);
+    P.sum_parts.push_back(parts); P.sum_counts.push_back(nb);
+    g0 = g1;
+  }
+}
+// ---- a5: DB post-processing of every page (on device; stream-ordered workspace reuse) ----
+void db_post(rt_session& s, Pipeline& P) {
+  const int n = P.n_pages, mb = max_boxes_of(s.cfg);
+  // box lists and counts of all pages are contiguous: one pack launch + two copies bring them to the host
+  pp::DbBox* d_boxes = s.arena.alloc<pp::DbBox>((size_t)mb * n);
+  P.d_counts = s.arena.alloc<int>((size_t)2 * n);
+  P.d_boxes_packed = s.arena.alloc<pp::DbBox>((size_t)mb * n);
+  std::vector<pp::DbPageIn> in((size_t)n);
+  for (int i = 0; i < n; i++) {
+    const PageState& p = P.pg[i];
+    const float* pred = p.map;
+    if (P.det_map_override && P.det_map_override[i]) {
+      if (P.mem == RT_MEM_HOST || P.mem == RT_MEM_STAGED_MAPS_HOST) {
+        float* d = s.arena.alloc<float>((size_t)p.det_h * p.det_w);
+        RT_HIP_CHECK(hipMemcpyAsync(d, P.det_map_override[i], (size_t)p.det_h * p.det_w * 4, hipMemcpyHostToDevice, s.st));
+        pred = d;
+      } else pred = P.det_map_override[i];
+    }
+    in[i] = pp::DbPageIn{pred, p.det_h, p.det_w, p.after_h, p.after_w};
+  }
+  ProfScope ps(&s.prof, s.st, "db_postprocess");
+  db_post_enqueue(s, n, in.data(), d_boxes, P.d_counts);
+  pp::pack_boxes(s.st, n, d_boxes, P.d_counts, mb, P.d_boxes_packed);
+}
+// ---- metadata round trip #1: box lists (a few KB per page); pixels and tensors stay on the device ----
+void box_round_trip(rt_session& s, Pipeline& P, rt_results& res) {
+  const int n = P.n_pages;
+  int* h_counts = s.pinned.alloc<int>((size_t)2 * n);
+  RT_HIP_CHECK(hipMemcpyAsync(h_counts, P.d_counts, (size_t)2 * n * sizeof(int), hipMemcpyDeviceToHost, s.st));
+  // (the map checksum partials ride to pinned memory with the box counts)
+  std::vector<double*> h_sum(P.sum_parts.size());
+  for (size_t g = 0; g < P.sum_parts.size(); g++) {
+    h_sum[g] = s.pinned.alloc<double>((size_t)P.sum_counts[g]);
+    RT_HIP_CHECK(hipMemcpyAsync(h_sum[g], P.sum_parts[g], (size_t)P.sum_counts[g] * 8, hipMemcpyDeviceToHost, s.st));
+  }
+  s.sync(); s.check_flags();
+  int total_lines = 0;
+  for (int i = 0; i < n; i++) {
+    if (h_counts[2 * i + 1]) throw RtError(RT_ERR_CAPACITY, "DB post-processing work list overflow (raise max_boxes_per_page)");
+    PageState& p = P.pg[i];
+    p.n_boxes = std::min(std::max(h_counts[2 * i], 0), max_boxes_of(s.cfg)); p.first_line = total_lines; total_lines += p.n_boxes;
+  }
+  if (total_lines > 0) {
+    pp::DbBox* h_boxes = s.pinned.alloc<pp::DbBox>((size_t)total_lines);
+    RT_HIP_CHECK(hipMemcpyAsync(h_boxes, P.d_boxes_packed, (size_t)total_lines * sizeof(pp::DbBox), hipMemcpyDeviceToHost, s.st));
+    s.sync();
+    for (PageState& p : P.pg) p.boxes = h_boxes + p.first_line;
+  }
+  for (size_t g = 0; g < P.sum_parts.size(); g++)
+    for (int i = 0; i < P.sum_counts[g]; i++) res.det_checksum += h_sum[g][i];
+  P.NL = total_lines; P.NLp = std::max(total_lines, 1);
+  P.tok_off.assign((size_t)P.NL + 1, 0);
+  if (s.stage_cb)  // run_stream: the Det stage is complete here (session.rs:98)
+    for (int i = 0; i < n; i++) { rt_results::Page page; page_boxes(P.pg[i], page); s.emit_stage(i, 0, page); }
+}
+// ---- a6: crop plan over every page's boxes, the crops warped when there are any ----
+void crop_stage(rt_session& s, Pipeline& P) {
+  for (const PageState& p : P.pg)
+    for (int k = 0; k < p.n_boxes; k++) plan_crop(P.plan, p.img, p.after_h, p.after_w, p.boxes[k].pts);
+  if (P.NL > 0) P.pool = warp_planned_crops(s, P.plan, &P.d_refs);
+}
+// ---- a8 + a9: angle classifier over every crop --------------------------------------
+// (cls_processor.rs:127-172: batches of 6 sorted by aspect; the classifier is per-crop independent, so batch composition does
+//  not change any value)
+void cls_stage(rt_session& s, Pipeline& P) {
+  const int ch = s.cfg.cls_image_shape[1], cw = s.cfg.cls_image_shape[2];
+  P.d_meta.view(s.arena.alloc<int>((size_t)4 * P.NLp), P.NLp);
+  const int CG = 2048;
+  for (int c0 = 0; c0 < P.NL; c0 += CG) {
+    int cn = std::min(CG, P.NL - c0);
+    s.scratch.rewind();
+    pp::LineDesc* hl = s.pinned.alloc<pp::LineDesc>(cn);
+    int* hrow = s.pinned.alloc<int>(cn);
+    for (int k = 0; k < cn; k++) {
+      const pp::CropRef& r = P.plan.refs[c0 + k];
+      hl[k] = line_desc(r, r.h, r.w, ch, cw); hl[k].out_off = (long long)k * ch * cw * 4;
+      hrow[k] = c0 + k;
+    }
+    pp::LineDesc* dl = s.scratch.alloc<pp::LineDesc>(cn);
+    int* drow = s.scratch.alloc<int>(cn);
+    RT_HIP_CHECK(hipMemcpyAsync(dl, hl, (size_t)cn * sizeof(pp::LineDesc), hipMemcpyHostToDevice, s.st));
+    RT_HIP_CHECK(hipMemcpyAsync(drow, hrow, (size_t)cn * 4, hipMemcpyHostToDevice, s.st));
+    float* x = s.scratch.alloc<float>((size_t)cn * ch * cw * 4);
+    { ProfScope ps(&s.prof, s.st, "resize_norm");
+      pp::resize_norm(s.st, dl, cn, ch, cw, P.pool, 0, x, s.d_flags); }
+    Level L0 = make_level(uniform_hw(cn, ch, cw));
+    RunCtx c = s.ctx(&s.scratch);
+    float* probs;
+    { ProfOuter po(&s.prof, s.st, "net/cls"); probs = s.cls->run(c, x, L0); }
+    ProfScope ps(&s.prof, s.st, "cls_post_rotate");
+    pp::cls_post_rotate(s.st, probs, drow, cn, s.cfg.cls_thresh, P.d_refs, P.pool, P.plan.max_pix, P.d_meta.label, P.d_meta.cscore);
+  }
+}
+// ---- a10: rec plan: per page, order by h/w descending (stable), chunks of batch_num, running max_wh_ratio ----
+void rec_plan(rt_session& s, Pipeline& P) {
+  const int rh = s.cfg.rec_image_shape[1], rw = s.cfg.rec_image_shape[2];
+  const std::vector<pp::CropRef>& refs = P.plan.refs;
+  P.lines.resize((size_t)P.NL); P.line_W.resize((size_t)P.NL);
+  for (const PageState& p : P.pg) {
+    int nb = p.n_boxes, f = p.first_line;
+    std::vector<int> order((size_t)nb);
+    std::iota(order.begin(), order.end(), 0);
+    std::stable_sort(order.begin(), order.end(), [&](int a, int b) {
+      double ra = (double)refs[f + a].h / (double)refs[f + a].w;
+      double rb = (double)refs[f + b].h / (double)refs[f + b].w;
+      return ra > rb;  // Reverse(OrderedFloat(ori_ratio))
+    });
+    float max_wh_ratio = (float)rw / (float)rh;
+    for (int s0 = 0; s0 < nb; s0 += s.cfg.rec_batch_num) {
+      int s1 = std::min(nb, s0 + s.cfg.rec_batch_num);
+      for (int k = s0; k < s1; k++) {
+        const pp::CropRef& r = refs[f + order[k]];
+        float wh = (float)r.w / (float)r.h;
+        if (wh > max_wh_ratio) max_wh_ratio = wh;
+      }
+      int W = gm::resize_norm_width(rh, rw, max_wh_ratio);
+      for (int k = s0; k < s1; k++) {
+        int li = f + order[k];
+        const pp::CropRef& r = refs[li];
+        P.lines[li] = line_desc(r, r.h, r.w, rh, W); P.line_W[li] = W;
+      }
+    }
+  }
+  for (int l = 0; l < P.NL; l++) P.tok_off[l + 1] = P.tok_off[l] + RecNet::tokens_for_width(P.line_W[l]);
+}
+// ---- a11 + a12: rec network + CTC decode in launch groups (+ word boxes) --------------
+void rec_groups(rt_session& s, Pipeline& P) {
+  const int rh = s.cfg.rec_image_shape[1];
+  const size_t ntok = (size_t)std::max<long long>(P.tok_off[P.NL], 1);
+  int* d_idx = s.arena.alloc<int>(ntok); float* d_prob = s.arena.alloc<float>(ntok); P.d_tok = s.arena.alloc<int>(ntok);
+  // rec_return_word_box: word count per line, words at the lines' token offsets, the kept columns (k_word_boxes' scratch)
+  int* d_wcol = nullptr;
+  if (s.cfg.rec_return_word_box) {
+    P.d_wcount = s.arena.alloc<int>(P.NLp); P.d_words = s.arena.alloc<wb::Word>(ntok); d_wcol = s.arena.alloc<int>(ntok);
+  }
+  static const long long REC_GROUP_PX = getenv("RT_REC_GROUP_PX") ? atoll(getenv("RT_REC_GROUP_PX")) : (long long)24000000;  // measured sweet spot (profiles/README.md)
+  for (int l0 = 0; l0 < P.NL;) {
+    const int l1 = group_end(l0, P.NL, 0, REC_GROUP_PX, [&](int l) { return (long long)rh * P.line_W[l]; });
+    const int ln = l1 - l0;
+    s.scratch.rewind();
+    std::vector<std::pair<int, int>> hw;
+    pp::LineDesc* hl = s.pinned.alloc<pp::LineDesc>(ln);
+    long long off = 0; int maxW = 0;
+    for (int k = 0; k < ln; k++) {
+      hl[k] = P.lines[l0 + k];
+      hl[k].out_off = off * 4;
+      off += (long long)rh * P.line_W[l0 + k];
+      hw.push_back({rh, P.line_W[l0 + k]}); maxW = std::max(maxW, P.line_W[l0 + k]);
+    }
+    pp::LineDesc* dl = s.scratch.alloc<pp::LineDesc>(ln);
+    RT_HIP_CHECK(hipMemcpyAsync(dl, hl, (size_t)ln * sizeof(pp::LineDesc), hipMemcpyHostToDevice, s.st));
+    float* x = s.scratch.alloc<float>((size_t)off * 4);
+    { ProfScope ps(&s.prof, s.st, "resize_norm");
+      pp::resize_norm(s.st, dl, ln, rh, maxW, P.pool, 0, x, s.d_flags); }
+    Level L0 = make_level(hw), Lt;
+    RunCtx c = s.ctx(&s.scratch);
+    // (the token count per line only depends on the widths, so the offsets are known before the net runs)
+    const long long t0 = P.tok_off[l0];
+    { ProfOuter po(&s.prof, s.st, "net/rec");
+      s.rec->run(c, x, L0, Lt, d_idx + t0, d_prob + t0); }  // fused CTC head: logits never reach HBM
+    if (Lt.total != P.tok_off[l1] - t0) throw RtError(RT_ERR_SHAPE, "token count mismatch");
+    { ProfScope ps(&s.prof, s.st, "ctc_decode");
+      pp::ctc_decode(s.st, d_idx + t0, d_prob + t0, Lt.d, ln, P.d_tok + t0, P.d_meta.ntok + l0, P.d_meta.rscore + l0); }
+    if (s.cfg.rec_return_word_box) {
+      pp::WordLineDesc* hwl = s.pinned.alloc<pp::WordLineDesc>(ln);
+      for (int k = 0; k < ln; k++) {
+        const int li = l0 + k;
+        const pp::CropRef& r = P.plan.refs[li];
+        const pp::CropDesc& cd = P.plan.descs[li];
+        pp::WordLineDesc& D = hwl[k];
+        D.tok_off = P.tok_off[li] - t0;
+        D.g.T = (int)(P.tok_off[li + 1] - P.tok_off[li]); D.g.W = P.line_W[li]; D.g.resized_w = P.lines[li].resized_w;
+        D.g.w_c = r.w; D.g.h_c = r.h; D.g.rot270 = cd.rot; D.g.w = cd.w; D.g.h = cd.h;
+        D.g.cw = P.plan.dims[li].cw; D.g.ch = P.plan.dims[li].ch;
+        memcpy(D.g.inv, cd.inv, sizeof D.g.inv);
+      }
+      pp::WordLineDesc* dw = s.scratch.alloc<pp::WordLineDesc>(ln);
+      RT_HIP_CHECK(hipMemcpyAsync(dw, hwl, (size_t)ln * sizeof(pp::WordLineDesc), hipMemcpyHostToDevice, s.st));
+      ProfScope ps(&s.prof, s.st, "word_boxes");
+      pp::word_boxes(s.st, d_idx + t0, P.d_tok + t0, P.d_meta.ntok + l0, P.d_meta.label + l0, P.d_meta.cscore + l0, s.cfg.cls_thresh,
+                     s.d_word_raw, dw, ln, d_wcol + t0, P.d_wcount + l0, P.d_words + t0);
+    }
+    l0 = l1;
+  }
+}
+// ---- metadata round trip #2: labels, scores, token ids (and the words) ---------------
+void line_round_trip(rt_session& s, Pipeline& P) {
+  const long long total_tok = P.tok_off[P.NL];
+  // per-line results come back in two copies into pinned memory: the metadata block and the tokens
+  P.h_meta.view(s.pinned.alloc<int>((size_t)4 * P.NLp), P.NLp);
+  P.h_tokens = s.pinned.alloc<int>((size_t)std::max<long long>(total_tok, 1));
+  RT_HIP_CHECK(hipMemcpyAsync(P.h_meta.label, P.d_meta.label, (size_t)4 * P.NLp * sizeof(int), hipMemcpyDeviceToHost, s.st));
+  if (total_tok > 0) RT_HIP_CHECK(hipMemcpyAsync(P.h_tokens, P.d_tok, (size_t)total_tok * 4, hipMemcpyDeviceToHost, s.st));
+  if (s.cfg.rec_return_word_box) {   // (the words ride with the tokens: same round trip)
+    P.h_wcount = s.pinned.alloc<int>(P.NLp);
+    P.h_words = s.pinned.alloc<wb::Word>((size_t)std::max<long long>(total_tok, 1));
+    RT_HIP_CHECK(hipMemcpyAsync(P.h_wcount, P.d_wcount, (size_t)P.NL * sizeof(int), hipMemcpyDeviceToHost, s.st));
+    if (total_tok > 0) RT_HIP_CHECK(hipMemcpyAsync(P.h_words, P.d_words, (size_t)total_tok * sizeof(wb::Word), hipMemcpyDeviceToHost, s.st));
+  }
+  s.sync(); s.check_flags();
+}
+// ---- results (session.rs:94-105) ----------------------------------------------------
+void results(const rt_session& s, const Pipeline& P, rt_results& res) {
+  static const uint16_t LABELS[2] = {0, 180};
+  const LineMeta& m = P.h_meta;
+  for (int i = 0; i < P.n_pages; i++) {
+    rt_results::Page& R = res.pages[i];
+    const PageState& p = P.pg[i];
+    int nb = p.n_boxes;
+    page_boxes(p, R);
+    R.cls_labels.resize(nb); R.cls_scores.resize(nb); R.rec_scores.resize(nb); R.tokens.resize(nb); R.text.resize(nb);
+    for (int k = 0; k < nb; k++) {
+      int li = p.first_line + k;
+      R.cls_labels[k] = LABELS[m.label[li] ? 1 : 0]; R.cls_scores[k] = m.cscore[li]; R.rec_scores[k] = m.rscore[li];
+      R.tokens[k].assign(P.h_tokens + P.tok_off[li], P.h_tokens + P.tok_off[li] + m.ntok[li]);
+      std::string& t = R.text[k];
+      t.reserve(R.tokens[k].size() * 3);  // CJK dictionary entries are 3 UTF-8 bytes
+      for (int id : R.tokens[k]) t += s.dict[(size_t)id];
+    }
+    if (s.cfg.rec_return_word_box) {   // word quads to original-image coordinates, word texts from the dictionary
+      R.words.resize(nb); R.word_text.resize(nb);
+      for (int k = 0; k < nb; k++) {
+        const int li = p.first_line + k;
+        const int nw = std::min(std::max(P.h_wcount[li], 0), m.ntok[li]);
+        std::vector<wb::Word>& W = R.words[k];
+        W.assign(P.h_words + P.tok_off[li], P.h_words + P.tok_off[li] + nw);
+        R.word_text[k].resize((size_t)nw);
+        for (int j = 0; j < nw; j++) {
+          gm::scale_and_clip(W[j].quad, (double)p.after_w, (double)p.after_h, (double)p.ori_w, (double)p.ori_h);
+          std::string& t = R.word_text[k][(size_t)j];
+          for (int q = W[j].first_token; q < W[j].first_token + W[j].n_tokens; q++) t += s.dict[(size_t)R.tokens[k][(size_t)q]];
+        }
+      }
+    }
+  }
+}
 }  // namespace
 std::string rt_format_f32_impl(float v) { return fnum(v); }
 
@@ -559,386 +922,22 @@ rt_results* rt_session::run_pages(const uint8_t* const* rgb, const int* hs, cons
   std::unique_ptr<rt_results> res(new rt_results());
   res->pages.resize((size_t)n_pages);
   if (n_pages == 0) return res.release();
-  std::vector<PageState> pg((size_t)n_pages);
-  const int mb = max_boxes_of(cfg);
-  pp::DbBox *d_boxes_all = nullptr, *d_boxes_packed = nullptr;
-  int* d_counts_all = nullptr;
-
-  // ---- a2 + a3: size limits, det resize, normalise ---------------------------------
-  std::vector<std::pair<int, int>> det_hw;
-  std::vector<const uint8_t*> det_img((size_t)n_pages);
-  for (int i = 0; i < n_pages; i++) {
-    PageState& p = pg[i];
-    p.ori_h = hs[i]; p.ori_w = ws[i];
-    if (hs[i] <= 0 || ws[i] <= 0 || rgb[i] == nullptr) throw RtError(RT_ERR_IMAGE, "empty page");
-    const uint8_t* raw = rgb[i];
-    if (mem == RT_MEM_HOST || mem == RT_MEM_HOST_MAPS_DEVICE) {   // the pages cross PCIe here (a submitted batch staged them already)
-      uint8_t* d = arena.alloc<uint8_t>((size_t)hs[i] * ws[i] * 3);
-      RT_HIP_CHECK(hipMemcpyAsync(d, rgb[i], (size_t)hs[i] * ws[i] * 3, hipMemcpyHostToDevice, st));
-      raw = d;
-    }
-    p.img = dev_resize_both(this, raw, hs[i], ws[i], &p.after_h, &p.after_w);
-    if (p.after_h <= 0 || p.after_w <= 0) throw RtError(RT_ERR_SHAPE, "page collapses to zero size in resize_both");
-    gm::resize_either_dims(p.after_h, p.after_w, cfg.det_limit_type, cfg.det_limit_side_len, &p.det_h, &p.det_w);
-    if (p.det_h <= 0 || p.det_w <= 0) throw RtError(RT_ERR_SHAPE, "det input collapses to zero size");
-    if (p.det_h == p.after_h && p.det_w == p.after_w) det_img[i] = p.img;  // thumbnail at ratio 1 is the identity
-    else {
-      uint8_t* d = arena.alloc<uint8_t>((size_t)p.det_h * p.det_w * 3);
-      ProfScope ps(&prof, st, "thumbnail");
-      pp::thumbnail_rgb8(st, p.img, p.after_h, p.after_w, d, p.det_h, p.det_w, d_flags);
-      det_img[i] = d;
-    }
-    det_hw.push_back({p.det_h, p.det_w});
-  }
-
-  HostTick tick;
-  tick.lap("pre (resize, upload)");
-  // ---- a4: det network in launch groups -------------------------------------------
-  long long group_px = cfg.det_sub_batch > 0 ? 0 : (long long)32 * 960 * 960;  // measured: larger launch groups win (launch-bound small layers)
-  std::vector<double*> sum_parts; std::vector<int> sum_counts;
-  for (int g0 = 0; g0 < n_pages;) {
-    int g1 = g0; long long px = 0;
-    while (g1 < n_pages) {
-      long long add = (long long)det_hw[g1].first * det_hw[g1].second;
-      if (g1 > g0 && ((cfg.det_sub_batch > 0 && g1 - g0 >= cfg.det_sub_batch) || (cfg.det_sub_batch <= 0 && px + add > group_px))) break;
-      px += add; g1++;
-    }
-    std::vector<std::pair<int, int>> hw(det_hw.begin() + g0, det_hw.begin() + g1);
-    Level L0 = make_level(hw);
-    scratch.rewind();
-    // a3 normalise is folded into the det stem (DetNet::run_u8): the pages stay RGB8 until the first conv reads them
-    const int gn = g1 - g0;
-    pp::NormDesc* hd = pinned.alloc<pp::NormDesc>((size_t)gn);
-    pp::NormDesc* dd = scratch.alloc<pp::NormDesc>((size_t)gn);
-    for (int i = g0; i < g1; i++)
-      hd[i - g0] = pp::NormDesc{det_img[i], (long long)pg[i].det_h * pg[i].det_w, L0.h[i - g0].off};
-    RT_HIP_CHECK(hipMemcpyAsync(dd, hd, (size_t)gn * sizeof(pp::NormDesc), hipMemcpyHostToDevice, st));
-    RunCtx c = ctx(&scratch);
-    float* map;
-    static const bool f32_input = getenv("RT_DET_F32_INPUT") != nullptr;  // A/B: build the normalised tensor first
-    if (f32_input) {
-      float* x = scratch.alloc<float>((size_t)L0.total * 4);
-      long long max_pix = 0;
-      for (int i = 0; i < gn; i++) max_pix = std::max(max_pix, hd[i].npix);
-      { ProfScope ps(&prof, st, "det_normalize");
-        pp::det_normalize_batch(st, dd, gn, max_pix, cfg.det_scale, cfg.det_mean, cfg.det_std, x); }
-      ProfOuter po(&prof, st, "net/det"); map = det->run(c, x, L0);
-    } else {
-      ProfOuter po(&prof, st, "net/det"); map = det->run_u8(c, dd, cfg.det_scale, cfg.det_mean, cfg.det_std, L0);
-    }
-    // keep the maps beyond the next group's scratch rewind; the last group's map is consumed by the DB post-processing
-    // (same stream) before the classifier reuses the scratch arena, so it stays where the network left it
-    float* keep = map;
-    if (g1 < n_pages) {
-      keep = arena.alloc<float>((size_t)L0.total);
-      RT_HIP_CHECK(hipMemcpyAsync(keep, map, (size_t)L0.total * 4, hipMemcpyDeviceToDevice, st));
-    }
-    for (int i = g0; i < g1; i++) pg[i].map = keep + L0.h[i - g0].off;
-    int nb = pp::sum_blocks(L0.total);
-    double* parts = arena.alloc<double>(nb);
-    pp::sum_partial(st, keep, L0.total, parts);
-    sum_parts.push_back(parts); sum_counts.push_back(nb);
-    g0 = g1;
-  }
-
-  tick.lap("det enqueue");
-  // ---- a5: DB post-processing per page (on device; stream-ordered workspace reuse) --
-  {
-    std::vector<pp::DbPageIn> in((size_t)n_pages);
-    std::vector<void*> wsp((size_t)n_pages);
-    std::vector<pp::DbBox*> bo((size_t)n_pages);
-    std::vector<int*> co((size_t)n_pages);
-    // box lists and counts of all pages are contiguous: one pack launch + two copies bring them to the host
-    d_boxes_all = arena.alloc<pp::DbBox>((size_t)mb * std::max(n_pages, 1));
-    d_counts_all = arena.alloc<int>((size_t)2 * std::max(n_pages, 1));
-    d_boxes_packed = arena.alloc<pp::DbBox>((size_t)mb * std::max(n_pages, 1));
-    for (int i = 0; i < n_pages; i++) {
-      PageState& p = pg[i];
-      const float* pred = p.map;
-      if (det_map_override && det_map_override[i]) {
-        if (mem == RT_MEM_HOST || mem == RT_MEM_STAGED_MAPS_HOST) {
-          float* d = arena.alloc<float>((size_t)p.det_h * p.det_w);
-          RT_HIP_CHECK(hipMemcpyAsync(d, det_map_override[i], (size_t)p.det_h * p.det_w * 4, hipMemcpyHostToDevice, st));
-          pred = d;
-        } else pred = det_map_override[i];
-      }
-      p.d_boxes = d_boxes_all + (size_t)i * mb;
-      p.d_count = d_counts_all + 2 * i;
-      in[i] = pp::DbPageIn{pred, p.det_h, p.det_w, p.after_h, p.after_w};
-      wsp[i] = dbws.alloc_bytes(pp::db_workspace_bytes(p.det_h, p.det_w, mb, cfg.det_score_mode));
-      bo[i] = p.d_boxes; co[i] = p.d_count;
-    }
-    void* hd = pinned.alloc_bytes((size_t)n_pages * pp::db_page_desc_bytes());
-    void* dd = arena.alloc_bytes((size_t)n_pages * pp::db_page_desc_bytes());
-    ProfScope ps(&prof, st, "db_postprocess");
-    pp::db_postprocess_batch(st, n_pages, in.data(), db_params(cfg), wsp.data(), mb, bo.data(), co.data(), hd, dd);
-    pp::pack_boxes(st, n_pages, d_boxes_all, d_counts_all, mb, d_boxes_packed);
-  }
-  tick.lap("dbpost enqueue");
-  // metadata round trip #1: box lists (a few KB per page); pixels and tensors stay on the device
-  int* h_counts = pinned.alloc<int>((size_t)2 * std::max(n_pages, 1));
-  if (n_pages > 0) RT_HIP_CHECK(hipMemcpyAsync(h_counts, d_counts_all, (size_t)2 * n_pages * sizeof(int), hipMemcpyDeviceToHost, st));
-  // (the map checksum partials ride to pinned memory with the box counts)
-  std::vector<double*> h_sum(sum_parts.size());
-  for (size_t g = 0; g < sum_parts.size(); g++) {
-    h_sum[g] = pinned.alloc<double>((size_t)sum_counts[g]);
-    RT_HIP_CHECK(hipMemcpyAsync(h_sum[g], sum_parts[g], (size_t)sum_counts[g] * 8, hipMemcpyDeviceToHost, st));
-  }
-  sync(); check_flags();
-  int total_lines = 0;
-  for (int i = 0; i < n_pages; i++) {
-    if (h_counts[2 * i + 1]) throw RtError(RT_ERR_CAPACITY, "DB post-processing work list overflow (raise max_boxes_per_page)");
-    pg[i].n_boxes = std::min(std::max(h_counts[2 * i], 0), mb);
-    pg[i].first_line = total_lines;
-    total_lines += pg[i].n_boxes;
-  }
-  pp::DbBox* h_boxes = nullptr;
-  if (total_lines > 0) {
-    h_boxes = pinned.alloc<pp::DbBox>((size_t)total_lines);
-    RT_HIP_CHECK(hipMemcpyAsync(h_boxes, d_boxes_packed, (size_t)total_lines * sizeof(pp::DbBox), hipMemcpyDeviceToHost, st));
-  }
-  if (total_lines > 0) sync();
-  if (total_lines > 0)
-    for (int i = 0; i < n_pages; i++) pg[i].boxes.assign(h_boxes + pg[i].first_line, h_boxes + pg[i].first_line + pg[i].n_boxes);
-  for (size_t g = 0; g < sum_parts.size(); g++)
-    for (int i = 0; i < sum_counts[g]; i++) res->det_checksum += h_sum[g][i];
-
-  if (stage_cb) {  // run_stream: the Det stage is complete here (session.rs:98)
-    for (int i = 0; i < n_pages; i++) {
-      rt_results::Page P;
-      P.boxes.resize((size_t)pg[i].n_boxes * 8); P.det_scores.resize((size_t)pg[i].n_boxes);
-      for (int k = 0; k < pg[i].n_boxes; k++) {
-        float b[8]; memcpy(b, pg[i].boxes[k].pts, 32);
-        gm::scale_and_clip(b, (double)pg[i].after_w, (double)pg[i].after_h, (double)pg[i].ori_w, (double)pg[i].ori_h);
-        memcpy(&P.boxes[8 * k], b, 32);
-        P.det_scores[k] = pg[i].boxes[k].score;
-      }
-      emit_stage(i, 0, P);
-    }
-  }
-  tick.lap("sync #1 + box D2H");
-  // ---- a6: crops --------------------------------------------------------------------
-  CropPlan plan;
-  for (int i = 0; i < n_pages; i++) {
-    std::vector<float> b((size_t)pg[i].n_boxes * 8);
-    for (int k = 0; k < pg[i].n_boxes; k++) memcpy(&b[8 * k], pg[i].boxes[k].pts, 32);
-    plan_crops(plan, pg[i].img, pg[i].after_h, pg[i].after_w, b.data(), pg[i].n_boxes);
-  }
-  const int NL = total_lines;
-  // per-line results come back in two copies into pinned memory: {label, cls score, token count, rec score} and the tokens
-  const int NLp = std::max(NL, 1);
-  int* h_meta = pinned.alloc<int>((size_t)4 * NLp);
-  memset(h_meta, 0, (size_t)4 * NLp * sizeof(int));
-  const int* h_label = h_meta; const float* h_cscore = reinterpret_cast<const float*>(h_meta + NLp);
-  const int* h_ntok = h_meta + 2 * NLp; const float* h_rscore = reinterpret_cast<const float*>(h_meta + 3 * NLp);
-  const int* h_tokens = nullptr; std::vector<long long> tok_off((size_t)NL + 1, 0);
-  const bool words_on = cfg.rec_return_word_box != 0;
-  const int* h_wcount = nullptr; const wb::Word* h_words = nullptr;   // rec_return_word_box
-  if (NL > 0) {
-    uint8_t* pool = arena.alloc<uint8_t>(plan.pool_bytes + 64);
-    pp::CropDesc* d_desc = arena.alloc<pp::CropDesc>(NL);
-    pp::CropRef* d_refs = arena.alloc<pp::CropRef>(NL);
-    {
-      pp::CropDesc* hd = pinned.alloc<pp::CropDesc>(NL);
-      pp::CropRef* hr = pinned.alloc<pp::CropRef>(NL);
-      memcpy(hd, plan.descs.data(), (size_t)NL * sizeof(pp::CropDesc));
-      memcpy(hr, plan.refs.data(), (size_t)NL * sizeof(pp::CropRef));
-      RT_HIP_CHECK(hipMemcpyAsync(d_desc, hd, (size_t)NL * sizeof(pp::CropDesc), hipMemcpyHostToDevice, st));
-      RT_HIP_CHECK(hipMemcpyAsync(d_refs, hr, (size_t)NL * sizeof(pp::CropRef), hipMemcpyHostToDevice, st));
-    }
-    { ProfScope ps(&prof, st, "warp_crops");
-      pp::warp_crops(st, d_desc, NL, plan.max_pix, pool); }
-
+  Pipeline P{n_pages, mem, det_map_override, std::vector<PageState>((size_t)n_pages)};
+  page_sizes(*this, P, rgb, hs, ws);
+  HostTick tick; tick.lap("pre (resize, upload)");
+  det_groups(*this, P); tick.lap("det enqueue");
+  db_post(*this, P); tick.lap("dbpost enqueue");
+  box_round_trip(*this, P, *res); tick.lap("sync #1 + box D2H");
+  crop_stage(*this, P);
+  if (P.NL > 0) {
     tick.lap("crop plan + warp enqueue");
-    // ---- a8 + a9: angle classifier over every crop -------------------------------
-    // (cls_processor.rs:127-172: batches of 6 sorted by aspect; the classifier is
-    //  per-crop independent, so batch composition does not change any value)
-    const int ch = cfg.cls_image_shape[1], cw = cfg.cls_image_shape[2];
-    int* d_meta = arena.alloc<int>((size_t)4 * NLp);
-    int* d_label = d_meta; float* d_cscore = reinterpret_cast<float*>(d_meta + NLp);
-    int* d_ntok = d_meta + 2 * NLp; float* d_rscore = reinterpret_cast<float*>(d_meta + 3 * NLp);
-    {
-      const int CG = 2048;
-      for (int c0 = 0; c0 < NL; c0 += CG) {
-        int cn = std::min(CG, NL - c0);
-        scratch.rewind();
-        pp::LineDesc* hl = pinned.alloc<pp::LineDesc>(cn);
-        int* hrow = pinned.alloc<int>(cn);
-        for (int k = 0; k < cn; k++) {
-          const pp::CropRef& r = plan.refs[c0 + k];
-          pp::LineDesc L;
-          L.crop_off = r.off; L.h = r.h; L.w = r.w; L.W = cw;
-          L.resized_w = gm::resize_norm_resized_w(ch, cw, r.h, r.w);
-          L.out_off = (long long)k * ch * cw * 4;
-          hl[k] = L; hrow[k] = c0 + k;
-        }
-        pp::LineDesc* dl = scratch.alloc<pp::LineDesc>(cn);
-        int* drow = scratch.alloc<int>(cn);
-        RT_HIP_CHECK(hipMemcpyAsync(dl, hl, (size_t)cn * sizeof(pp::LineDesc), hipMemcpyHostToDevice, st));
-        RT_HIP_CHECK(hipMemcpyAsync(drow, hrow, (size_t)cn * 4, hipMemcpyHostToDevice, st));
-        float* x = scratch.alloc<float>((size_t)cn * ch * cw * 4);
-        { ProfScope ps(&prof, st, "resize_norm");
-          pp::resize_norm(st, dl, cn, ch, cw, pool, 0, x, d_flags); }
-        Level L0 = make_level(uniform_hw(cn, ch, cw));
-        RunCtx c = ctx(&scratch);
-        float* probs;
-        { ProfOuter po(&prof, st, "net/cls"); probs = cls->run(c, x, L0); }
-        ProfScope ps(&prof, st, "cls_post_rotate");
-        pp::cls_post_rotate(st, probs, drow, cn, cfg.cls_thresh, d_refs, pool, plan.max_pix, d_label, d_cscore);
-      }
-    }
-
-    tick.lap("cls enqueue");
-    // ---- a10 + a11 + a12: recognition ----------------------------------------------
-    // per page: order by h/w descending (stable), chunks of batch_num, running max_wh_ratio
-    const int rh = cfg.rec_image_shape[1], rw = cfg.rec_image_shape[2];
-    std::vector<pp::LineDesc> lines((size_t)NL);
-    std::vector<int> line_W((size_t)NL);
-    for (int i = 0; i < n_pages; i++) {
-      int nb = pg[i].n_boxes, f = pg[i].first_line;
-      std::vector<int> order((size_t)nb);
-      std::iota(order.begin(), order.end(), 0);
-      std::stable_sort(order.begin(), order.end(), [&](int a, int b) {
-        double ra = (double)plan.refs[f + a].h / (double)plan.refs[f + a].w;
-        double rb = (double)plan.refs[f + b].h / (double)plan.refs[f + b].w;
-        return ra > rb;  // Reverse(OrderedFloat(ori_ratio))
-      });
-      float max_wh_ratio = (float)rw / (float)rh;
-      for (int s0 = 0; s0 < nb; s0 += cfg.rec_batch_num) {
-        int s1 = std::min(nb, s0 + cfg.rec_batch_num);
-        for (int k = s0; k < s1; k++) {
-          const pp::CropRef& r = plan.refs[f + order[k]];
-          float wh = (float)r.w / (float)r.h;
-          if (wh > max_wh_ratio) max_wh_ratio = wh;
-        }
-        int W = gm::resize_norm_width(rh, rw, max_wh_ratio);
-        for (int k = s0; k < s1; k++) {
-          int li = f + order[k];
-          const pp::CropRef& r = plan.refs[li];
-          pp::LineDesc L;
-          L.crop_off = r.off; L.h = r.h; L.w = r.w; L.W = W;
-          L.resized_w = gm::resize_norm_resized_w(rh, W, r.h, r.w);
-          L.out_off = 0;
-          lines[li] = L; line_W[li] = W;
-        }
-      }
-    }
-    for (int l = 0; l < NL; l++) tok_off[l + 1] = tok_off[l] + RecNet::tokens_for_width(line_W[l]);
-    const long long total_tok = tok_off[NL];
-    int* d_idx = arena.alloc<int>(std::max<long long>(total_tok, 1));
-    float* d_prob = arena.alloc<float>(std::max<long long>(total_tok, 1));
-    int* d_tok = arena.alloc<int>(std::max<long long>(total_tok, 1));
-    // rec_return_word_box: word count per line, words at the lines' token offsets, the kept columns (k_word_boxes' scratch)
-    int* d_wcount = nullptr; wb::Word* d_words = nullptr; int* d_wcol = nullptr;
-    if (words_on) {
-      d_wcount = arena.alloc<int>(NLp);
-      d_words = arena.alloc<wb::Word>(std::max<long long>(total_tok, 1));
-      d_wcol = arena.alloc<int>(std::max<long long>(total_tok, 1));
-    }
-    static const long long REC_GROUP_PX = getenv("RT_REC_GROUP_PX") ? atoll(getenv("RT_REC_GROUP_PX")) : (long long)24000000;  // measured sweet spot (profiles/README.md)
-    for (int l0 = 0; l0 < NL;) {
-      int l1 = l0; long long px = 0;
-      while (l1 < NL) { long long add = (long long)rh * line_W[l1]; if (l1 > l0 && px + add > REC_GROUP_PX) break; px += add; l1++; }
-      int ln = l1 - l0;
-      scratch.rewind();
-      std::vector<std::pair<int, int>> hw;
-      pp::LineDesc* hl = pinned.alloc<pp::LineDesc>(ln);
-      long long off = 0;
-      for (int k = 0; k < ln; k++) {
-        hl[k] = lines[l0 + k];
-        hl[k].out_off = off * 4;
-        off += (long long)rh * line_W[l0 + k];
-        hw.push_back({rh, line_W[l0 + k]});
-      }
-      pp::LineDesc* dl = scratch.alloc<pp::LineDesc>(ln);
-      RT_HIP_CHECK(hipMemcpyAsync(dl, hl, (size_t)ln * sizeof(pp::LineDesc), hipMemcpyHostToDevice, st));
-      float* x = scratch.alloc<float>((size_t)off * 4);
-      int maxW = 0; for (auto& p : hw) maxW = std::max(maxW, p.second);
-      { ProfScope ps(&prof, st, "resize_norm");
-        pp::resize_norm(st, dl, ln, rh, maxW, pool, 0, x, d_flags); }
-      Level L0 = make_level(hw), Lt;
-      RunCtx c = ctx(&scratch);
-      // (the token count per line only depends on the widths, so the offsets are known before the net runs)
-      { ProfOuter po(&prof, st, "net/rec");
-        rec->run(c, x, L0, Lt, d_idx + tok_off[l0], d_prob + tok_off[l0]); }  // fused CTC head: logits never reach HBM
-      if (Lt.total != tok_off[l1] - tok_off[l0]) throw RtError(RT_ERR_SHAPE, "token count mismatch");
-      { ProfScope ps(&prof, st, "ctc_decode");
-        pp::ctc_decode(st, d_idx + tok_off[l0], d_prob + tok_off[l0], Lt.d, ln, d_tok + tok_off[l0], d_ntok + l0, d_rscore + l0); }
-      if (words_on) {
-        pp::WordLineDesc* hw = pinned.alloc<pp::WordLineDesc>(ln);
-        for (int k = 0; k < ln; k++) {
-          const int li = l0 + k;
-          const pp::CropRef& r = plan.refs[li];
-          const pp::CropDesc& cd = plan.descs[li];
-          pp::WordLineDesc& D = hw[k];
-          D.tok_off = tok_off[li] - tok_off[l0];
-          D.g.T = (int)(tok_off[li + 1] - tok_off[li]); D.g.W = line_W[li]; D.g.resized_w = lines[li].resized_w;
-          D.g.w_c = r.w; D.g.h_c = r.h; D.g.rot270 = cd.rot; D.g.w = cd.w; D.g.h = cd.h;
-          D.g.cw = plan.dims[li].cw; D.g.ch = plan.dims[li].ch;
-          memcpy(D.g.inv, cd.inv, sizeof D.g.inv);
-        }
-        pp::WordLineDesc* dw = scratch.alloc<pp::WordLineDesc>(ln);
-        RT_HIP_CHECK(hipMemcpyAsync(dw, hw, (size_t)ln * sizeof(pp::WordLineDesc), hipMemcpyHostToDevice, st));
-        ProfScope ps(&prof, st, "word_boxes");
-        pp::word_boxes(st, d_idx + tok_off[l0], d_tok + tok_off[l0], d_ntok + l0, d_label + l0, d_cscore + l0, cfg.cls_thresh,
-                       d_word_raw, dw, ln, d_wcol + tok_off[l0], d_wcount + l0, d_words + tok_off[l0]);
-      }
-      l0 = l1;
-    }
-    tick.lap("rec enqueue");
-    // metadata round trip #2: labels, scores, token ids
-    int* h_tok = pinned.alloc<int>((size_t)std::max<long long>(total_tok, 1));
-    h_tokens = h_tok;
-    RT_HIP_CHECK(hipMemcpyAsync(h_meta, d_meta, (size_t)4 * NLp * sizeof(int), hipMemcpyDeviceToHost, st));
-    if (total_tok > 0) RT_HIP_CHECK(hipMemcpyAsync(h_tok, d_tok, (size_t)total_tok * 4, hipMemcpyDeviceToHost, st));
-    if (words_on) {   // (the words ride with the tokens: same round trip)
-      int* hc = pinned.alloc<int>(NLp);
-      wb::Word* hwd = pinned.alloc<wb::Word>((size_t)std::max<long long>(total_tok, 1));
-      RT_HIP_CHECK(hipMemcpyAsync(hc, d_wcount, (size_t)NL * sizeof(int), hipMemcpyDeviceToHost, st));
-      if (total_tok > 0) RT_HIP_CHECK(hipMemcpyAsync(hwd, d_words, (size_t)total_tok * sizeof(wb::Word), hipMemcpyDeviceToHost, st));
-      h_wcount = hc; h_words = hwd;
-    }
-    sync(); check_flags();
+    cls_stage(*this, P); tick.lap("cls enqueue");
+    rec_plan(*this, P);
+    rec_groups(*this, P); tick.lap("rec enqueue");
+    line_round_trip(*this, P);
   }
-
   tick.lap("sync #2 + D2H");
-  // ---- results (session.rs:94-105) ---------------------------------------------------
-  static const uint16_t LABELS[2] = {0, 180};
-  for (int i = 0; i < n_pages; i++) {
-    rt_results::Page& P = res->pages[i];
-    const PageState& p = pg[i];
-    int nb = p.n_boxes;
-    P.boxes.resize((size_t)nb * 8); P.det_scores.resize(nb); P.cls_labels.resize(nb); P.cls_scores.resize(nb);
-    P.rec_scores.resize(nb); P.tokens.resize(nb); P.text.resize(nb);
-    for (int k = 0; k < nb; k++) {
-      float b[8]; memcpy(b, p.boxes[k].pts, 32);
-      gm::scale_and_clip(b, (double)p.after_w, (double)p.after_h, (double)p.ori_w, (double)p.ori_h);
-      memcpy(&P.boxes[8 * k], b, 32);
-      P.det_scores[k] = p.boxes[k].score;
-      int li = p.first_line + k;
-      P.cls_labels[k] = LABELS[h_label[li] ? 1 : 0]; P.cls_scores[k] = h_cscore[li];
-      P.rec_scores[k] = h_rscore[li];
-      P.tokens[k].assign(h_tokens + tok_off[li], h_tokens + tok_off[li] + h_ntok[li]);
-      std::string& t = P.text[k];
-      t.reserve(P.tokens[k].size() * 3);  // CJK dictionary entries are 3 UTF-8 bytes
-      for (int id : P.tokens[k]) t += dict[(size_t)id];
-    }
-    if (words_on) {   // word quads to original-image coordinates, word texts from the dictionary
-      P.words.resize(nb); P.word_text.resize(nb);
-      for (int k = 0; k < nb; k++) {
-        const int li = p.first_line + k;
-        const int nw = std::min(std::max(h_wcount[li], 0), h_ntok[li]);
-        std::vector<wb::Word>& W = P.words[k];
-        W.assign(h_words + tok_off[li], h_words + tok_off[li] + nw);
-        P.word_text[k].resize((size_t)nw);
-        for (int j = 0; j < nw; j++) {
-          gm::scale_and_clip(W[j].quad, (double)p.after_w, (double)p.after_h, (double)p.ori_w, (double)p.ori_h);
-          std::string& t = P.word_text[k][(size_t)j];
-          for (int q = W[j].first_token; q < W[j].first_token + W[j].n_tokens; q++) t += dict[(size_t)P.tokens[k][(size_t)q]];
-        }
-      }
-    }
-  }
+  results(*this, P, *res);
   if (stage_cb)
     for (int i = 0; i < n_pages; i++) { emit_stage(i, 1, res->pages[i]); emit_stage(i, 2, res->pages[i]); }
   tick.lap("results");

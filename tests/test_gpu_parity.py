@@ -469,6 +469,34 @@ def test_pipeline_mixed_sizes_c4(hip_session, oracle_session):
                           np.stack([d.boxes.as_array() for d in res[1].det_result]))
 
 
+def test_det_sub_batch_groups_equal_the_default_grouping():
+    """det_sub_batch > 0 cuts the det launch groups by page count instead of by pixel budget: five pages of mixed sizes on one
+    lane run the det network as 2 + 2 + 1 pages (one "net/det" scope per launch group) where the default budget takes all five
+    in one group, and give the same boxes, scores, labels and token ids, and the same det checksum to fp32 rounding (the det
+    maps of a page in different groups come from different kernel shapes)."""
+    specs = [(640, 640, 6, 61), (720, 1280, 5, 62), (416, 608, 3, 63), (960, 960, 4, 64), (2100, 1500, 7, 65)]
+    pages, maps = zip(*[_planted_for(h, w, L, s) for h, w, L, s in specs])
+    got = []
+    for sub, groups in ((0, 1), (2, 3)):
+        s = retto_amd.RettoSession(retto_amd.synthetic_session_config(0, det_sub_batch=sub, lanes=1))
+        try:
+            s.profile_enable()
+            got.append((s.run_batch(list(pages), det_map_override=list(maps)), s.last_det_checksum))
+            assert s.profile_get()["net/det"][1] == groups, (sub, s.profile_get()["net/det"])
+        finally:
+            s.close()
+    (ref, cs_ref), (res, cs) = got
+    for a, b in zip(ref, res):
+        assert len(a.det_result) == len(b.det_result) > 0
+        assert np.array_equal(np.stack([d.boxes.as_array() for d in a.det_result]), np.stack([d.boxes.as_array() for d in b.det_result]))
+        assert [d.score for d in a.det_result] == [d.score for d in b.det_result]
+        assert [(c.label.label, c.label.score) for c in a.cls_result] == [(c.label.label, c.label.score) for c in b.cls_result]
+        for x, y in zip(a.rec_result, b.rec_result):
+            assert np.array_equal(x.tokens, y.tokens)
+            assert x.score == y.score or (np.isnan(x.score) and np.isnan(y.score))
+    assert abs(cs - cs_ref) <= 1e-6 * abs(cs_ref)
+
+
 def test_pipeline_empty_and_border_pages(hip_session, oracle_session):
     blank = np.zeros((320, 320, 3), np.uint8)
     m_blank = np.full((736, 736), 0.01, np.float32)
