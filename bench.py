@@ -13,10 +13,13 @@ Other workloads (never substituted for the C3 headline; `config.workload` names 
                   (retto_amd.dist.shard_pages), results are gathered in input order and checked for rank invariance
   --workload c5   PP-OCRv4 server det+rec in fp16 (BASELINE config 5), own roofline against the fp16 MFMA peak
 
-Prints ONE JSON line on rank 0 (driver contract) with `roofline` for the dominant kernel family (HIP-event
-times measured live on the session's stream) and `cpu_baseline` (rank 0, N=1 only).  `--dump-outputs DIR` also writes
-what the last timed step returned on rank 0 (boxes, scores, labels, token ids, det checksum) as DIR/<name>.npy; inputs
-and weights are seeded, so two builds run with the same arguments can be compared output for output.
+Prints ONE JSON line on rank 0 (driver contract).  A plain run does only what its headline needs: set-up, warm-up, the timed
+steps, `--dump-outputs` and the line.  `--full` adds everything else after the timed region: the repeat, synchronous-call,
+host-fed and split-bf16 legs, `roofline` for the dominant kernel family (HIP-event times measured live on the session's stream),
+`roofline_e2e`, `networks`, `cpu_baseline` (rank 0, N=1 only), `host`, the page-0 self-check, the C5 leg and the global batch's
+gather and rank-invariance check.  `--dump-outputs DIR` also writes what the last timed step returned on rank 0 (boxes, scores,
+labels, token ids, det checksum) as DIR/<name>.npy; inputs and weights are seeded, so two builds run with the same arguments can
+be compared output for output.
 """
 from __future__ import annotations
 
@@ -85,9 +88,14 @@ def parse():
     ap.add_argument("--repeat", type=int, default=2, help="extra repetitions of the K timed steps after the timed region (spread, reported in `repeat`)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed region, write what the last timed step returned (rank 0's pages) as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region, also run every other leg, pass and check (see the module docstring); the options "
+                         "that shape those (--repeat, --no-cpu-baseline, --no-c5, --no-split-leg, --profile-all ...) act only with it")
     a = ap.parse_args()
     if a.steps is not None and a.steps < 1:
         ap.error("--steps must be at least 1")
+    if a.profile_all and not a.full:
+        ap.error("--profile-all needs --full (the per-family table comes from its profile pass)")
     if a.workload == "c5":
         a.dtype = a.dtype or "f16"; a.models = a.models or "server"
         a.pages = a.pages or 128; a.steps = a.steps or 3; a.warmup = a.warmup if a.warmup is not None else 3   # (the arenas of the 3 lanes settle after 3 calls)
@@ -229,9 +237,9 @@ def launch_ranks(n):
 
 def c5_leg(a):
     """BASELINE config 5 on this GPU, driver-visible: a short `--workload c5` run of this script in a child process after the
-    C3 measurement (32 pages per step so that it stays well inside the default run's minutes), its line condensed."""
+    C3 measurement of a --full run (32 pages per step so that it stays well inside that run's minutes), its line condensed."""
     cmd = [sys.executable, os.path.abspath(__file__), "--workload", "c5", "--pages", str(a.c5_pages), "--steps", str(a.c5_steps),
-           "--warmup", "3", "--no-cpu-baseline", "--no-c5"]
+           "--warmup", "3", "--no-cpu-baseline", "--no-c5", "--full"]
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "LOCAL_WORLD_SIZE")}
     t0 = time.perf_counter()
     try:
@@ -449,14 +457,16 @@ def main():
         except Exception:
             pass
         return out
-    th0 = thread_cpu()
-    ru0 = resource.getrusage(resource.RUSAGE_SELF)
+    if a.full:
+        th0 = thread_cpu()
+        ru0 = resource.getrusage(resource.RUSAGE_SELF)
     t0 = time.perf_counter()
     last_outs = run_steps(a.steps, on_host, keep_last=bool(a.dump_outputs) and rank == 0)
     barrier()
     elapsed = time.perf_counter() - t0
-    ru1 = resource.getrusage(resource.RUSAGE_SELF)
-    th1 = thread_cpu()
+    if a.full:
+        ru1 = resource.getrusage(resource.RUSAGE_SELF)
+        th1 = thread_cpu()
     dumped = None
     if last_outs is not None:
         try:
@@ -464,25 +474,26 @@ def main():
         finally:
             for r, _n in last_outs:
                 lib.rt_results_free(r)
-    per_thread = sorted(((th1[t][1] - th0.get(t, (None, 0.0))[1], th1[t][0]) for t in th1), reverse=True)[:6]
-    # host budget of one rank: CPU time (user + system, all threads) per step and the threads it keeps -- eight ranks share the
-    # node's CPUs (the pod on the MI355X box: 16), so a rank that needs more than cpus / 8 of a core-second per second is the limit
-    host_cpu_ms = 1000.0 * ((ru1.ru_utime - ru0.ru_utime) + (ru1.ru_stime - ru0.ru_stime)) / a.steps
-    try:
-        host_threads = int([ln for ln in open("/proc/self/status") if ln.startswith("Threads:")][0].split()[1])
-    except Exception:
-        host_threads = None
-    # spread: the same K steps again, `--repeat` more times (each bracketed like the timed region); `value` stays the FIRST region
-    rep_ms = [1000.0 * elapsed / a.steps]
-    for _ in range(max(0, a.repeat)):
-        barrier()
-        tr = time.perf_counter()
-        run_steps(a.steps, on_host)
-        barrier()
-        rep_ms.append(1000.0 * (time.perf_counter() - tr) / a.steps)
+    if a.full:
+        per_thread = sorted(((th1[t][1] - th0.get(t, (None, 0.0))[1], th1[t][0]) for t in th1), reverse=True)[:6]
+        # host budget of one rank: CPU time (user + system, all threads) per step and the threads it keeps -- eight ranks share the
+        # node's CPUs (16, say), so a rank that needs more than cpus / 8 of a core-second per second is the limit
+        host_cpu_ms = 1000.0 * ((ru1.ru_utime - ru0.ru_utime) + (ru1.ru_stime - ru0.ru_stime)) / a.steps
+        try:
+            host_threads = int([ln for ln in open("/proc/self/status") if ln.startswith("Threads:")][0].split()[1])
+        except Exception:
+            host_threads = None
+        # spread: the same K steps again, `--repeat` more times (each bracketed like the timed region); `value` stays the FIRST region
+        rep_ms = [1000.0 * elapsed / a.steps]
+        for _ in range(max(0, a.repeat)):
+            barrier()
+            tr = time.perf_counter()
+            run_steps(a.steps, on_host)
+            barrier()
+            rep_ms.append(1000.0 * (time.perf_counter() - tr) / a.steps)
     # the same K steps as synchronous calls (one rt_run_batch per step, nothing submitted ahead): what rounds 1-3 reported
     sync_ms = None
-    if a.inflight > 1 and not global_mode:
+    if a.full and a.inflight > 1 and not global_mode:
         barrier()
         tr = time.perf_counter()
         for _ in range(a.steps):
@@ -494,7 +505,7 @@ def main():
     # benchmark scaffolding and stay in HBM (RT_MEM_HOST_MAPS_DEVICE); the leg has its own warm-up and at least 20
     # steps whatever --steps says (the first host-fed calls size the staging; 5 steps after one cold call measured that).
     other_rate = None
-    if not global_mode:
+    if a.full and not global_mode:
         ks_all = list(range(n_my))
 
         def host_steps(k):
@@ -526,7 +537,7 @@ def main():
     # accumulation (error against an fp64 product measured BELOW the fp32-MFMA kernel's: tests/test_gpu_parity.py
     # test_split_bf16_gemm_error_against_fp64, tools/bench_gemm_split.py).  Same steps, same batches in flight.
     split_leg = None
-    if a.workload == "c3" and a.dtype == "f32" and not global_mode and not on_host and not a.no_split_leg:
+    if a.full and a.workload == "c3" and a.dtype == "f32" and not global_mode and not on_host and not a.no_split_leg:
         vv = [int(v) for v in a.variants.split(',')] if a.variants else [0, 0, 0]
         lib.rt_debug_set_variants(vv[0], vv[1], vv[2] | 4096)
         try:
@@ -547,7 +558,7 @@ def main():
             lib.rt_debug_set_variants(vv[0], vv[1], vv[2])
     # ---- global mode: gather every page's digest in INPUT order; rank invariance is checked on rank 0 below -------
     gathered = None
-    if global_mode:   # every rank ends with every page's digest in input order (retto_amd.dist.run_global_batch)
+    if global_mode and a.full:   # every rank ends with every page's digest in input order (retto_amd.dist.run_global_batch)
         digs = run_global_batch(all_sizes, rank, world if dist_on else 1, lambda ids: run_ids(ids, False, "digest"),
                                 est_lines=[a.lines] * a.global_batch, chunk=chunk)
         gathered = [(gid,) + tuple(d) for gid, d in enumerate(digs)]
@@ -555,7 +566,7 @@ def main():
     # events around every launch.  Concurrent lanes share the GPU and stretch each other's
     # kernels, so a kernel's own duration can only be read from a serial pass.
     prof, prof_nets, serial_ms = {}, {}, None
-    if rank == 0:
+    if a.full and rank == 0:
         lib.rt_set_lanes(h, 1)
         for _ in range(2):  # lane 0's arenas re-size for the whole batch
             step()
@@ -614,6 +625,48 @@ def main():
 
     value = pages_total * a.steps / elapsed
     ms_per_step = 1000.0 * elapsed / a.steps
+
+    names = {"c2": "C2: PP-OCRv4 %s det only (DBNet + DB post, no text lines), one %dx%d page per call (batch 1), " % (a.models, S, S),
+             "c3": "C3: PP-OCRv4 %s det+cls+rec full pipeline, batch=%d pages of %dx%d per GPU, " % (a.models, n_my, S, S),
+             "c4": ("C4: PP-OCRv4 %s det+cls+rec full pipeline, ONE global batch of %d mixed-size pages (640x640 .. 2480x3508) sharded over "
+                    "%d rank(s) by estimated work (LPT), results gathered in input order, " % (a.models, a.global_batch, world)) if global_mode else
+                   "C4: PP-OCRv4 %s det+cls+rec full pipeline, batch=%d mixed-size pages per GPU (640x640 .. 2480x3508), " % (a.models, n_my),
+             "c5": "C5: PP-OCRv4 SERVER det (PPHGNet_small + LKPAN + PFHeadLocal) + mobile cls + SERVER rec (PPHGNet_small + SVTR/CTC), "
+                   "fp16 MFMA, batch=%d pages of %dx%d per GPU, " % (n_my, S, S)}
+    wl = names[a.workload] + ("%d planted lines/page (planted DB map drives box extraction; det net fully executed, checksum %.6g); "
+                               "pages %s when the timed region starts" % (
+                                   a.lines, checksum, "resident in HBM" if not on_host else "in host memory (H2D inside the timed region)"))
+    out = {
+        "metric": "images/sec end-to-end PP-OCRv4 det+rec @960x960",
+        "value": round(value, 3), "unit": "images/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
+        "ms_per_step": round(ms_per_step, 3), "higher_is_better": True, "scaling": "strong" if global_mode else "weak",
+        "vs_baseline": None, "dtype": a.dtype, "data": "synthetic",
+        "config": {"workload": wl, "pages_per_gpu_per_step": n_my, "lines_per_step_all_gpus": n_lines_total,
+                   "weights": "seeded synthetic, PP-OCRv4 %s shapes" % a.models, "networks": model_info,
+                   "parallelism": "dp%d (pages sharded, no per-step collective)" % world,
+                   "batches_in_flight": 1 if global_mode else max(1, a.inflight)},
+        "full": a.full,
+    }
+    if dist_on:
+        out["rccl_ranks"] = rccl_ranks
+        out["bcast_ms"] = round(bcast_ms, 2)
+    if dumped:
+        out["dump_outputs"] = dumped
+
+    def emit(out, sess):
+        if sess is not None:
+            sess.close()
+        if dist_on:
+            dist.destroy_process_group()
+        _flush_c_stdio()
+        sys.stdout.flush()
+        print(json.dumps(out), flush=True)  # the ONE line of the contract, last thing on stdout
+
+    if not a.full:   # a plain run reports the headline and ends here
+        emit(out, sess)
+        return
+
+    # ---- everything below: --full only ---------------------------------------------------------------------------------
 
     # ---- rank invariance of the global batch: pages that other ranks processed, re-run here one by one ---------------
     rank_invariance = None
@@ -834,31 +887,8 @@ def main():
         raise RuntimeError("bench self-check failed: page 0 differs between the batch and a run of its own")
     selfcheck = {"batch_invariance_page0": True, "lines": int(len(in_batch[2]))}
 
-    names = {"c2": "C2: PP-OCRv4 %s det only (DBNet + DB post, no text lines), one %dx%d page per call (batch 1), " % (a.models, S, S),
-             "c3": "C3: PP-OCRv4 %s det+cls+rec full pipeline, batch=%d pages of %dx%d per GPU, " % (a.models, n_my, S, S),
-             "c4": ("C4: PP-OCRv4 %s det+cls+rec full pipeline, ONE global batch of %d mixed-size pages (640x640 .. 2480x3508) sharded over "
-                    "%d rank(s) by estimated work (LPT), results gathered in input order, " % (a.models, a.global_batch, world)) if global_mode else
-                   "C4: PP-OCRv4 %s det+cls+rec full pipeline, batch=%d mixed-size pages per GPU (640x640 .. 2480x3508), " % (a.models, n_my),
-             "c5": "C5: PP-OCRv4 SERVER det (PPHGNet_small + LKPAN + PFHeadLocal) + mobile cls + SERVER rec (PPHGNet_small + SVTR/CTC), "
-                   "fp16 MFMA, batch=%d pages of %dx%d per GPU, " % (n_my, S, S)}
-    wl = names[a.workload] + ("%d planted lines/page (planted DB map drives box extraction; det net fully executed, checksum %.6g); "
-                               "pages %s when the timed region starts" % (
-                                   a.lines, checksum, "resident in HBM" if not on_host else "in host memory (H2D inside the timed region)"))
-    out = {
-        "metric": "images/sec end-to-end PP-OCRv4 det+rec @960x960",
-        "value": round(value, 3), "unit": "images/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
-        "ms_per_step": round(ms_per_step, 3), "higher_is_better": True, "scaling": "strong" if global_mode else "weak",
-        "vs_baseline": None, "dtype": a.dtype, "data": "synthetic",
-        "config": {"workload": wl, "pages_per_gpu_per_step": n_my, "lines_per_step_all_gpus": n_lines_total,
-                   "weights": "seeded synthetic, PP-OCRv4 %s shapes" % a.models, "networks": model_info,
-                   "parallelism": "dp%d (pages sharded, no per-step collective)" % world,
-                   "batches_in_flight": 1 if global_mode else max(1, a.inflight)},
-        "roofline": roofline,
-        "roofline_e2e": roofline_e2e,
-        "cpu_baseline": cpu_baseline,
-        "networks": networks,
-        "selfcheck": selfcheck,
-    }
+    out.update({"roofline": roofline, "roofline_e2e": roofline_e2e, "cpu_baseline": cpu_baseline, "networks": networks,
+                "selfcheck": selfcheck})
     out["repeat"] = {"ms_per_step": [round(x, 3) for x in rep_ms], "min": round(min(rep_ms), 3), "median": round(float(np.median(rep_ms)), 3),
                      "note": "the timed region (first entry, = ms_per_step) and %d more regions of %d steps on this rank" % (len(rep_ms) - 1, a.steps)}
     out["host"] = {"cpu_ms_per_step": round(host_cpu_ms, 2), "cpu_cores_busy": round(host_cpu_ms / ms_per_step, 2), "threads": host_threads,
@@ -872,9 +902,6 @@ def main():
                                     "note": "the same %d steps on this rank as one synchronous rt_run_batch per step (nothing submitted ahead: what rounds "
                                             "1-3 reported); `value` is timed with %d batches in flight through rt_submit_batch / rt_wait_batch -- every "
                                             "step still runs its whole batch, the host-side result assembly of step i overlaps step i + 1" % (a.steps, a.inflight)}
-    if dist_on:
-        out["rccl_ranks"] = rccl_ranks
-        out["bcast_ms"] = round(bcast_ms, 2)
     if a.workload == "c3" and world == 1 and not a.no_c5 and a.dtype == "f32" and a.models == "mobile":
         sess.close(); sess = None
         out["c5"] = c5_leg(a)
@@ -890,15 +917,7 @@ def main():
         out["c2"] = c2
     if rank_invariance:
         out["rank_invariance"] = rank_invariance
-    if dumped:
-        out["dump_outputs"] = dumped
-    if sess is not None:
-        sess.close()
-    if dist_on:
-        dist.destroy_process_group()
-    _flush_c_stdio()
-    sys.stdout.flush()
-    print(json.dumps(out), flush=True)  # the ONE line of the contract, last thing on stdout
+    emit(out, sess)
 
 
 if __name__ == "__main__":

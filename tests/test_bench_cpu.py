@@ -15,6 +15,17 @@ def test_steps_below_one_is_refused():
     assert r.returncode == 2 and "--steps must be at least 1" in r.stderr, r.stderr[-1500:]
 
 
+def test_full_is_opt_in(monkeypatch):
+    """A plain run leaves every leg beyond the headline to --full; --profile-all prints a table of --full's profile pass."""
+    import bench
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "20", "--warmup", "5"])
+    assert bench.parse().full is False
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--profile-all"])
+    assert bench.parse().full is True
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--profile-all"], capture_output=True, text=True, cwd=ROOT, timeout=120)
+    assert r.returncode == 2 and "--profile-all needs --full" in r.stderr, r.stderr[-1500:]
+
+
 class _FakeResults:
     """The rt_results_* accessors bench.dump_outputs calls, over numpy arrays: handle r, page i, line k."""
 

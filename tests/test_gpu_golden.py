@@ -355,7 +355,7 @@ def test_bench_runs_the_cabi_broadcast_every_round():
     env = dict(os.environ, RT_BENCH_FORCE_DIST="1", MASTER_ADDR="127.0.0.1", MASTER_PORT="29547", RANK="0", LOCAL_RANK="0",
                WORLD_SIZE="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--bcast", "cabi", "--steps", "2", "--warmup", "1",
-                          "--pages", "3", "--size", "480", "--lines", "4", "--no-c5", "--no-cpu-baseline", "--repeat", "0"],
+                          "--pages", "3", "--size", "480", "--lines", "4", "--full", "--no-c5", "--no-cpu-baseline", "--repeat", "0"],
                          capture_output=True, text=True, timeout=900, env=env, cwd=root)
     assert out.returncode == 0, out.stderr[-3000:]
     line = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])

@@ -5,7 +5,7 @@
 #   gpurun -- 'bash tools/c2_kernel_trace.sh [rows] [bench args]'      default: 30 rows, "--workload c2" (one 960 x 960 page per call);
 #   e.g. 'bash tools/c2_kernel_trace.sh 40 --pages 1' = one page with its 32 text lines through det + cls + rec
 rows=${1:-30}; shift
-args=${*:---workload c2}
+args="${*:---workload c2} --full"   # (--full: the `networks` figures printed below and the serial profile passes among the calls)
 steps=200; calls=$((steps + 20 + 2 * steps + 3))
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 rm -rf gpurun_out/c2_trace
