@@ -381,6 +381,23 @@ RT_API int rt_bench_gemm(rt_session* s, long long M, int K, int N, int variant, 
  * rms err, max |ref|, rms ref} over `rows` rows from the start, the middle and the end of the M rows.  variant 1 = narrow fp32-MFMA
  * kernel, 30 = k_gemm32p (fp32 MFMA), 40 = split-bf16 (three bf16 planes per operand, six bf16 MFMAs per product, fp32 accumulate). */
 RT_API int rt_bench_gemm_err(rt_session* s, long long M, int K, int N, int variant, int rows, int act, unsigned seed, double* out4);
+/* One nn::gemm launch on host arrays, for the numerics tests: out[:, coff ..] = epi(A x W + bias) (+ residual), as the networks
+ * call it.  A [M][lda] (channels K .. lda zero), W [K][N] (packed as pack_linear packs a linear layer), bias [N] or NULL, act
+ * (as rt_debug_conv16), LAB (has_lab, lab_a, lab_c), residual [M][ld_res] or NULL.  Squeeze-excite: se_scale [n_img][ld_scale]
+ * (NULL: none) over img_rows[n_img] consecutive images of M rows in all; se_rows = the row-block table's form (0 = what the
+ * networks ask for, 128 or 256).  variant: 0 = production rule, else as rt_bench_gemm.  ctc = -1: the plain GEMM; 0 / 1 / 2: the
+ * CTC head with that argmax form (idx_out / prob_out [M]: argmax and its softmax probability per row).  out [(M + 64) * ldc] is
+ * filled with RT_DEBUG_CANARY before the launch and returned whole.  plan_out[5] = {GemmKernel value (gemm_plan.h), nt, kg, se,
+ * bf} of the plan that ran. */
+#define RT_DEBUG_CANARY 0x7FA5C3E1u
+RT_API int rt_debug_gemm(rt_session* s, const float* A, long long M, int K, int lda, const float* W, int N, const float* bias,
+                         int act, int has_lab, float lab_a, float lab_c, const float* residual, int ld_res, const float* se_scale,
+                         int ld_scale, const long long* img_rows, int n_img, int se_rows, int ldc, int coff, int variant, int ctc,
+                         float* out, int* idx_out, float* prob_out, int* plan_out);
+/* One nn::attention launch (head dim 15) on host arrays: qkv [rows][3 * heads * 15] (q | k | v, as the neck's qkv GEMM writes
+ * it), lines of tokens[i] consecutive rows (sum = rows) -> out [rows][heads * 15], with the geometry SvtrCore::mixer passes. */
+RT_API int rt_debug_attention(rt_session* s, const float* qkv, long long rows, const int* tokens, int n_lines, int heads,
+                              float* out);
 /* times the fused thin LCNetV3 block (3x3 depthwise -> 1x1 conv; n images of h x w, random data).  form: 0 = k_lc_thin
  * (workgroup-staged; the unfused depthwise + GEMM pair where it has no instance), 1 = k_lc_wave (direct loads, stride 1 only),
  * 3 = k_lc_lds (production).  stride: 1, 2, or 21 = (2, 1).  Returns the average ms and the max |diff| against form 0. */

@@ -778,6 +778,114 @@ RT_API int rt_bench_gemm_err(rt_session* s, long long M, int K, int N, int varia
   });
 }
 
+// One nn::gemm launch on host arrays (tests/test_gpu_ops.py compares it with an fp64 product): the weights packed by the networks'
+// pack_linear, the squeeze-excite table built by their se_row_table, the plan of gemm_plan() -- returned with the whole output
+// buffer, whose 64 rows past M and columns outside [coff, coff + round_up(N, 4)) must keep the canary.
+RT_API int rt_debug_gemm(rt_session* s, const float* A, long long M, int K, int lda, const float* W, int N, const float* bias,
+                         int act, int has_lab, float lab_a, float lab_c, const float* residual, int ld_res, const float* se_scale,
+                         int ld_scale, const long long* img_rows, int n_img, int se_rows, int ldc, int coff, int variant, int ctc,
+                         float* out, int* idx_out, float* prob_out, int* plan_out) {
+  RT_REQUIRE(s && A && W && out && plan_out, s, "rt_debug_gemm: null argument");
+  RT_REQUIRE(M > 0 && M < (1ll << 30) && K > 0 && N > 0 && lda >= round_up(K, 4) && lda % 4 == 0 && coff >= 0 &&
+                 ldc >= coff + round_up(N, 4) && act >= ACT_NONE && act <= ACT_SIGMOID,
+             s, "rt_debug_gemm: bad shape");
+  RT_REQUIRE(!residual || ld_res >= N, s, "rt_debug_gemm: ld_res < N");
+  RT_REQUIRE(!se_scale || (img_rows && n_img > 0 && ld_scale >= round_up(K, 4) && (se_rows == 0 || se_rows == 128 || se_rows == 256)),
+             s, "rt_debug_gemm: bad squeeze-excite arguments");
+  RT_REQUIRE(ctc >= -1 && ctc <= 2 && (ctc < 0 || (idx_out && prob_out)), s, "rt_debug_gemm: bad ctc arguments");
+  long long img_total = 0, min_pix = M;
+  for (int i = 0; se_scale && i < n_img; i++) {
+    RT_REQUIRE(img_rows[i] > 0, s, "rt_debug_gemm: empty image");
+    img_total += img_rows[i]; min_pix = std::min(min_pix, img_rows[i]);
+  }
+  RT_REQUIRE(!se_scale || img_total == M, s, "rt_debug_gemm: the images' rows do not add up to M");
+  return guarded(s, [&] {
+    RT_HIP_CHECK(hipSetDevice(s->device));
+    WeightStore ws;   // (frees the pack, and the split planes derived from it, on every way out)
+    const PackedDense pw = pack_linear(ws, W, bias, K, N);
+    DevBufs bufs;
+    RestoreInt keep_variant(nn::g_gemm_variant), keep_argmax(nn::g_argmax_wide);
+    nn::g_gemm_variant = variant;
+    const size_t a_rows = (size_t)M + 256;   // (zero rows past M: a tile's loads stay inside the allocation whatever it reads)
+    float* dA = bufs.alloc<float>(a_rows * lda);
+    RT_HIP_CHECK(hipMemset(dA, 0, a_rows * lda * sizeof(float)));
+    RT_HIP_CHECK(hipMemcpy(dA, A, (size_t)M * lda * sizeof(float), hipMemcpyHostToDevice));
+    float* dres = nullptr;
+    if (residual) {
+      dres = bufs.alloc<float>((size_t)M * ld_res);
+      RT_HIP_CHECK(hipMemcpy(dres, residual, (size_t)M * ld_res * sizeof(float), hipMemcpyHostToDevice));
+    }
+    const Lab lab{has_lab, lab_a, lab_c};
+    Epilogue e = make_epi(pw, act, &lab, dres, ld_res);
+    if (se_scale) {   // as run_lc: the table form the layer asks for (or the one forced), built over consecutive images
+      const int tile_rows = se_rows ? se_rows : nn::gemm_se_rows(lda, M, pw.K, N, pw.Npad, act, min_pix);
+      if (!tile_rows) throw RtError(RT_ERR_INVALID, "rt_debug_gemm: the layer has no fused squeeze-excite form (gemm_se_rows() == 0)");
+      std::vector<ImgGeom> imgs;
+      long long off = 0;
+      for (int i = 0; i < n_img; i++) { imgs.push_back(ImgGeom{off, 1, (int)img_rows[i], 0}); off += img_rows[i]; }
+      std::vector<int> tab(se_row_table_len(M, tile_rows));
+      se_row_table(imgs, M, tile_rows, tab.data());
+      int* dtab = bufs.alloc<int>(tab.size());
+      float* dscale = bufs.alloc<float>((size_t)n_img * ld_scale);
+      RT_HIP_CHECK(hipMemcpy(dtab, tab.data(), tab.size() * sizeof(int), hipMemcpyHostToDevice));
+      RT_HIP_CHECK(hipMemcpy(dscale, se_scale, (size_t)n_img * ld_scale * sizeof(float), hipMemcpyHostToDevice));
+      e.a_scale = dscale; e.ld_scale = ld_scale; e.a_tab = dtab; e.a_tab_stride = tile_rows == 256 ? 3 : 2; e.n_img = n_img;
+    }
+    int* didx = nullptr;
+    float* dprob = nullptr;
+    if (ctc >= 0) {   // CTC head: per-tile softmax statistics, folded by argmax_merge (SvtrCore::head)
+      nn::g_argmax_wide = ctc;
+      e.am_tiles = nn::gemm_argmax_tiles(pw.Npad);
+      e.am_max = bufs.alloc<float>((size_t)M * e.am_tiles); e.am_idx = bufs.alloc<int>((size_t)M * e.am_tiles);
+      e.am_sum = bufs.alloc<float>((size_t)M * e.am_tiles);
+      didx = bufs.alloc<int>(M); dprob = bufs.alloc<float>(M);
+    }
+    const size_t out_n = (size_t)(M + 64) * ldc;
+    float* dC = bufs.alloc<float>(out_n);
+    RT_HIP_CHECK(hipMemsetD32Async((hipDeviceptr_t)dC, (int)RT_DEBUG_CANARY, out_n, s->st));
+    const nn::GemmPlan plan = nn::gemm_plan(lda, M, pw.K, N, pw.Npad, ldc, coff, e, stream_cus(s->st));
+    nn::gemm(s->st, plan, dA, lda, M, pw.K, pw.w, N, pw.Npad, dC, ldc, coff, e);
+    if (ctc >= 0) nn::argmax_merge(s->st, e.am_max, e.am_idx, e.am_sum, e.am_tiles, M, didx, dprob);
+    RT_HIP_CHECK(hipStreamSynchronize(s->st));
+    RT_HIP_CHECK(hipMemcpy(out, dC, out_n * sizeof(float), hipMemcpyDeviceToHost));
+    if (ctc >= 0) {
+      RT_HIP_CHECK(hipMemcpy(idx_out, didx, (size_t)M * sizeof(int), hipMemcpyDeviceToHost));
+      RT_HIP_CHECK(hipMemcpy(prob_out, dprob, (size_t)M * sizeof(float), hipMemcpyDeviceToHost));
+    }
+    plan_out[0] = (int)plan.kernel; plan_out[1] = plan.nt; plan_out[2] = plan.kg; plan_out[3] = plan.se; plan_out[4] = plan.bf;
+  });
+}
+
+// One nn::attention launch on host arrays: one ImgGeom{off, 1, T} per line, as SvtrCore::mixer passes its token level.
+RT_API int rt_debug_attention(rt_session* s, const float* qkv, long long rows, const int* tokens, int n_lines, int heads, float* out) {
+  RT_REQUIRE(s && qkv && tokens && out, s, "rt_debug_attention: null argument");
+  RT_REQUIRE(rows > 0 && rows < (1ll << 30) && n_lines > 0 && heads > 0 && heads <= 64, s, "rt_debug_attention: bad shape");
+  long long total = 0;
+  int maxT = 0;
+  for (int i = 0; i < n_lines; i++) {
+    RT_REQUIRE(tokens[i] > 0, s, "rt_debug_attention: a line without tokens");
+    total += tokens[i]; maxT = std::max(maxT, tokens[i]);
+  }
+  RT_REQUIRE(total == rows, s, "rt_debug_attention: the lines' tokens do not add up to rows");
+  return guarded(s, [&] {
+    RT_HIP_CHECK(hipSetDevice(s->device));
+    const int hd = 15, C = heads * hd;
+    std::vector<ImgGeom> geom;
+    long long off = 0;
+    for (int i = 0; i < n_lines; i++) { geom.push_back(ImgGeom{off, 1, tokens[i], 0}); off += tokens[i]; }
+    DevBufs bufs;
+    float* dq = bufs.alloc<float>((size_t)rows * 3 * C);
+    float* dout = bufs.alloc<float>((size_t)rows * C);
+    ImgGeom* dg = bufs.alloc<ImgGeom>(n_lines);
+    RT_HIP_CHECK(hipMemcpy(dq, qkv, (size_t)rows * 3 * C * sizeof(float), hipMemcpyHostToDevice));
+    RT_HIP_CHECK(hipMemcpy(dg, geom.data(), geom.size() * sizeof(ImgGeom), hipMemcpyHostToDevice));
+    RT_HIP_CHECK(hipMemset(dout, 0, (size_t)rows * C * sizeof(float)));
+    nn::attention(s->st, dq, dg, n_lines, maxT, heads, hd, dout);
+    RT_HIP_CHECK(hipStreamSynchronize(s->st));
+    RT_HIP_CHECK(hipMemcpy(out, dout, (size_t)rows * C * sizeof(float), hipMemcpyDeviceToHost));
+  });
+}
+
 // Kernel micro-benchmark: the fused thin LCNetV3 block (3x3 depthwise -> pointwise) on n images of h x w pixels, random data.
 // form = nn::g_lc_wave for the timed launches: 0 = k_lc_thin (workgroup-staged; the unfused depthwise + GEMM pair where it has no
 // instance), 1 = k_lc_wave (direct loads, stride 1), 3 = k_lc_lds (production); stride 21 means (2, 1).  maxdiff compares with

@@ -114,18 +114,21 @@ PackedDense pack_conv(WeightStore& ws, const Blob& b, const std::string& name, i
 PackedDense pack_linear(WeightStore& ws, const Blob& b, const std::string& name, int cin, int cout) {
   const BlobTensor& w = b.get(name + ".w");
   expect_dims(w, {cin, cout}, name + ".w");
+  const BlobTensor& bt = b.get(name + ".b");
+  expect_dims(bt, {cout}, name + ".b");
+  return pack_linear(ws, w.data, bt.data, cin, cout);
+}
+PackedDense pack_linear(WeightStore& ws, const float* w, const float* bias_in, int cin, int cout) {
   PackedDense p;
   p.K = round_up(cin, 4); p.N = cout; p.Npad = round_up(cout, 16);
   const int nkc = (p.K + nn::KC - 1) / nn::KC;
   std::vector<float> host((size_t)nkc * p.Npad * nn::KC, 0.f);
   for (int k = 0; k < cin; k++)
     for (int n = 0; n < cout; n++)
-      host[((size_t)(k / nn::KC) * p.Npad + n) * nn::KC + (k % nn::KC)] = w.data[(size_t)k * cout + n];
+      host[((size_t)(k / nn::KC) * p.Npad + n) * nn::KC + (k % nn::KC)] = w[(size_t)k * cout + n];
   p.w = ws.upload(host);
   std::vector<float> bias(p.Npad, 0.f);
-  const BlobTensor& bt = b.get(name + ".b");
-  expect_dims(bt, {cout}, name + ".b");
-  memcpy(bias.data(), bt.data, cout * sizeof(float));
+  if (bias_in) memcpy(bias.data(), bias_in, cout * sizeof(float));
   p.b = ws.upload(bias);
   return p;
 }
@@ -207,6 +210,22 @@ Epilogue make_epi(const PackedDense& p, int act, const Lab* lab, const float* re
   return e;
 }
 
+size_t se_row_table_len(long long total, int tile_rows) {
+  return (size_t)((total + tile_rows - 1) / tile_rows) * (tile_rows == 256 ? 3 : 2);
+}
+void se_row_table(const std::vector<ImgGeom>& imgs, long long total, int tile_rows, int* htab) {
+  const int stride = tile_rows == 256 ? 3 : 2;   // per row block: image of its first row, first row of the next image (, of the one after)
+  const long long tiles = (total + tile_rows - 1) / tile_rows;
+  size_t img = 0;
+  for (long long t = 0; t < tiles; t++) {
+    const long long m0 = t * tile_rows;
+    while (img + 1 < imgs.size() && imgs[img + 1].off <= m0) img++;
+    htab[stride * t] = (int)img;
+    htab[stride * t + 1] = img + 1 < imgs.size() ? (int)imgs[img + 1].off : 0x7fffffff;  // no next image: never crossed
+    if (stride == 3) htab[stride * t + 2] = img + 2 < imgs.size() ? (int)imgs[img + 2].off : 0x7fffffff;
+  }
+}
+
 // Squeeze-excite scales of x ([image][Cp]); with apply the tensor is rescaled in place, otherwise the
 // caller folds the returned factors into the kernel that consumes x.
 static float* run_se(RunCtx& c, float* x, const Level& L, const SeW& se, float slope, int residual, bool apply = true) {
@@ -265,20 +284,13 @@ static float* run_lc(RunCtx& c, const LcBlock& b, const float* x, const Level& L
       nn::se_fc_from_dw(c.st, pool, Lout.d, Lout.n(), chunks, strip_R, strips_pb, b.sew.C, b.dw.Cp, b.sew.w1, b.sew.b1, b.sew.w2,
                         b.sew.b2, b.sew.Cr, HSIG_LCNET, 0, scale); }
     const int*& dtab = Lout.a_tabs[tile_rows];
-    const int stride = tile_rows == 256 ? 3 : 2;   // per row block: image of its first row, first row of the next image (, of the one after)
+    const int stride = tile_rows == 256 ? 3 : 2;
     if (!dtab) {
-      const long long tiles = (Lout.total + tile_rows - 1) / tile_rows;
-      int* htab = c.pinned->alloc<int>((size_t)tiles * stride);
-      int* dt = c.arena->alloc<int>((size_t)tiles * stride);
-      size_t img = 0;
-      for (long long t = 0; t < tiles; t++) {
-        const long long m0 = t * tile_rows;
-        while (img + 1 < Lout.h.size() && Lout.h[img + 1].off <= m0) img++;
-        htab[stride * t] = (int)img;
-        htab[stride * t + 1] = img + 1 < Lout.h.size() ? (int)Lout.h[img + 1].off : 0x7fffffff;  // no next image: never crossed
-        if (stride == 3) htab[stride * t + 2] = img + 2 < Lout.h.size() ? (int)Lout.h[img + 2].off : 0x7fffffff;
-      }
-      RT_HIP_CHECK(hipMemcpyAsync(dt, htab, (size_t)tiles * stride * sizeof(int), hipMemcpyHostToDevice, c.st));
+      const size_t len = se_row_table_len(Lout.total, tile_rows);
+      int* htab = c.pinned->alloc<int>(len);
+      int* dt = c.arena->alloc<int>(len);
+      se_row_table(Lout.h, Lout.total, tile_rows, htab);
+      RT_HIP_CHECK(hipMemcpyAsync(dt, htab, len * sizeof(int), hipMemcpyHostToDevice, c.st));
       dtab = dt;
     }
     epi.a_scale = scale; epi.ld_scale = b.dw.Cp; epi.a_tab = dtab; epi.a_tab_stride = stride; epi.n_img = Lout.n();

@@ -61,7 +61,12 @@ class WeightStore {  // owns one device allocation per network
 
 PackedDense pack_conv(WeightStore& ws, const Blob& b, const std::string& name, int cout, int cin, int kh, int kw);
 PackedDense pack_linear(WeightStore& ws, const Blob& b, const std::string& name, int cin, int cout);
+PackedDense pack_linear(WeightStore& ws, const float* w, const float* bias, int cin, int cout);   // host w [cin][cout], bias [cout] or null
 float* upload_raw(WeightStore& ws, const Blob& b, const std::string& name, size_t expect_numel);
+// Row-block table of the squeeze-excite-scaled GEMMs (Epilogue::a_tab) over the images of a level, for blocks of tile_rows = 128
+// (2 ints per block) or 256 (3 ints per block, k_gemm32p): se_row_table_len(total, tile_rows) ints.
+size_t se_row_table_len(long long total, int tile_rows);
+void se_row_table(const std::vector<ImgGeom>& imgs, long long total, int tile_rows, int* tab);
 Epilogue make_epi(const PackedDense& p, int act, const Lab* lab = nullptr, const float* residual = nullptr, int ld_res = 0);
 
 struct LcBlock {

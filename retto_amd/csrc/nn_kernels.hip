@@ -2357,7 +2357,8 @@ __global__ __launch_bounds__(64) void k_attention(const float* __restrict__ qkv,
 // contiguous bytes), re-laid per head into 16-float LDS rows, and a thread owns one (query, head) pair: a key costs 8
 // ds_read_b128 (lanes of a wave are consecutive queries of one head: broadcast reads) instead of 30 ds_read_b32.  Same keys in
 // the same order through the same online-softmax recurrence; exp by v_exp_f32 (__expf) where k_attention calls expf: equal to
-// ~2 ulp of the exponentials, NOT bit-identical.
+// ~2 ulp of the exponentials, NOT bit-identical.  Lines of <= ATT_MFMA_MAX_T tokens are k_attention_mfma's (attention()).
+constexpr int ATT_MFMA_MAX_T = 128;
 template <int HD>
 __global__ __launch_bounds__(256) void k_attention_line(const float* __restrict__ qkv, const ImgGeom* __restrict__ geom,
                                                         int heads, float* __restrict__ out) {
@@ -2365,7 +2366,7 @@ __global__ __launch_bounds__(256) void k_attention_line(const float* __restrict_
   extern __shared__ __attribute__((aligned(16))) float att_lds[];
   const ImgGeom g = geom[blockIdx.x];
   const int T = g.H * g.W, C = heads * HD;
-  if (T <= 0) return;
+  if (T <= ATT_MFMA_MAX_T) return;           // (k_attention_mfma's line)
   float* ks = att_lds;                       // [64 keys][heads][16]
   float* vs = att_lds + 64 * heads * 16;
   const int tid = threadIdx.x;
@@ -2448,7 +2449,7 @@ __global__ __launch_bounds__(512) void k_attention_mfma(const float* __restrict_
   extern __shared__ __attribute__((aligned(16))) float att_lds[];
   const ImgGeom g = geom[blockIdx.x];
   const int T = g.H * g.W, C = heads * HD;
-  if (T <= 0) return;
+  if (T <= 0 || T > ATT_MFMA_MAX_T) return;   // (longer lines: k_attention_line)
   const int Tp = (T + 15) & ~15;
   // [Tp keys][4 heads x 16 floats + 4 pad]: 68 floats per key (padding the key rows to 68 floats against the fragment reads' bank conflicts measured
   // slower: 0.069 vs 0.061 ms per launch)
@@ -2551,16 +2552,19 @@ void attention(hipStream_t st, const float* qkv, const ImgGeom* geom, int n_img,
                float* out) {
   if (n_img <= 0) return;
   if (hd != 15) throw RtError(8, "attention: head dim must be 15");
-  if (maxT <= 128 && heads <= 8) {
-    const size_t lds = (size_t)2 * ((maxT + 15) & ~15) * 64 * 4;   // K and V of four heads: 64 KB at 128 tokens
+  // The kernel is chosen per line, so that a line's result does not depend on the lines launched with it (the two forms are not
+  // bit-identical): every line of <= 128 tokens is k_attention_mfma's, every longer one k_attention_line's.  Both stage whole
+  // 16-byte chunks of a token's projections: C a multiple of 4.
+  if ((heads * hd) % 4 == 0 && heads <= 8) {
+    const int tm = min(maxT, ATT_MFMA_MAX_T);
+    const size_t lds = (size_t)2 * ((tm + 15) & ~15) * 64 * 4;   // K and V of four heads: 64 KB at 128 tokens
     allow_big_lds((const void*)k_attention_mfma<15>, 64 * 1024);
     RT_LAUNCH(k_attention_mfma<15>, dim3((unsigned)n_img), dim3(512), lds, st, qkv, geom, heads, out);
-    return;
-  }
-  if ((heads * hd) % 4 == 0 && heads <= 8) {
-    const size_t lds = (size_t)2 * 64 * heads * 16 * 4;   // 64 KB at 8 heads
-    allow_big_lds((const void*)k_attention_line<15>, 64 * 1024);
-    RT_LAUNCH(k_attention_line<15>, dim3((unsigned)n_img), dim3(256), lds, st, qkv, geom, heads, out);
+    if (maxT > ATT_MFMA_MAX_T) {
+      const size_t lds_line = (size_t)2 * 64 * heads * 16 * 4;   // 64 KB at 8 heads
+      allow_big_lds((const void*)k_attention_line<15>, 64 * 1024);
+      RT_LAUNCH(k_attention_line<15>, dim3((unsigned)n_img), dim3(256), lds_line, st, qkv, geom, heads, out);
+    }
     return;
   }
   RT_LAUNCH(k_attention<15>, dim3((maxT + 63) / 64, heads, n_img), dim3(64), 0, st, qkv, geom, heads, out);
