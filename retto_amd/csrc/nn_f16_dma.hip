@@ -1,6 +1,7 @@
 // fp16 convolution kernels staged by LDS-DMA (global_load_lds) for gfx950: k_conv16v2 (3x3 / 1x3 / 3x1 layers) and k_gemm16p
 // (1x1 layers over a flat pixel list).  Same fragment maps, K order and epilogue as k_conv16 (nn_f16.hip).
 #include "nn_f16_dev.h"
+#include "lds_asm.h"
 
 #include <algorithm>
 #include <cstdlib>
@@ -23,61 +24,6 @@ namespace nh {
 //     16-byte chunk index with bits 2-3 of the row, applied to the per-lane SOURCE address and again on the fragment reads.
 // Same fragment maps, K order and epilogue as k_conv16: results are bit-identical.
 // ---------------------------------------------------------------------------------------------------------------------
-// The LDS-DMA request is written as inline asm: with the builtin (__builtin_amdgcn_global_load_lds) in a loop hipcc's
-// wait-count pass treats the LDS counter as out of order and emits lgkmcnt(0) before every MFMA group -- which also waits
-// for the fragment reads just issued for the NEXT k-step (checked on a reduced kernel: counted lgkmcnt(5/4/1) without the
-// DMA or with this form, lgkmcnt(0) everywhere with the builtin).  M0 = wave-uniform LDS byte address; lane i writes
-// 16 bytes at M0 + 16 i.  The kernel counts vmcnt for these requests by hand (nothing else loads inside the loop).
-#pragma clang diagnostic push
-#pragma clang diagnostic ignored "-Winline-asm"   // M0 is named as clobbered on purpose: nothing else in these kernels uses it
-__device__ __forceinline__ void glds16(const void* g, void* l) {
-  const unsigned la = __builtin_amdgcn_readfirstlane((unsigned)(size_t)(__attribute__((address_space(3))) char*)l);
-  asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off" ::"v"(g), "s"(la) : "memory", "m0");
-}
-#pragma clang diagnostic pop
-#define RT_GLDS16(gp, lp) glds16((gp), (lp))
-
-// Fragment reads and their waits by hand (k_gemm16p): inside a loop whose body holds branches (the counted-vmcnt switch,
-// the conditional DMA request) hipcc falls back to lgkmcnt(0) before each MFMA group even for plain ds_reads, which waits
-// for the prefetch issued just before.  As inline asm the reads are invisible to its wait-count pass; lds_wait<N>() leaves
-// the newest N reads in flight and pins the order (sched_barrier: an MFMA has no memory operand, so a "memory" clobber
-// alone does not keep it behind the wait).
-__device__ __forceinline__ unsigned lds_addr(const void* p) { return (unsigned)(size_t)(__attribute__((address_space(3))) const char*)p; }
-__device__ __forceinline__ h8 lds_read16(unsigned byte_addr) {
-  h8 v;
-  asm volatile("ds_read_b128 %0, %1" : "=v"(v) : "v"(byte_addr));
-  return v;
-}
-template <int OFF>
-__device__ __forceinline__ h8 lds_read16_imm(unsigned byte_addr) {   // address + compile-time offset in the instruction
-  static_assert(OFF >= 0 && OFF < 65536, "16-bit offset field");
-  h8 v;
-  asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(v) : "v"(byte_addr), "n"(OFF));
-  return v;
-}
-// DMA request with the LDS address already in an SGPR (uniform by construction: no readfirstlane per request)
-#pragma clang diagnostic push
-#pragma clang diagnostic ignored "-Winline-asm"
-__device__ __forceinline__ void glds16_s(unsigned long long gaddr, unsigned lds_sgpr) {
-  asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off" ::"v"(gaddr), "s"(lds_sgpr) : "memory", "m0");
-}
-#pragma clang diagnostic pop
-// LDS-DMA request through a buffer resource (round 5): lane i writes 16 bytes at M0 + 16 i; source = resource base + per-lane
-// byte offset + scalar offset; a lane whose offset is out of range (0x80000000) writes ZEROS -- the padding pixels / rows cost no
-// select, and the per-slab / per-row advance is one scalar operand instead of a 64-bit add per lane and request.
-#pragma clang diagnostic push
-#pragma clang diagnostic ignored "-Winline-asm"
-__device__ __forceinline__ void blds16(unsigned voff, __amdgpu_buffer_rsrc_t rs, unsigned lds_sgpr, unsigned soff) {
-  asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tbuffer_load_dwordx4 %0, %1, %3 offen lds" ::"v"(voff), "s"(rs), "s"(lds_sgpr), "s"(soff) : "memory", "m0");
-}
-#pragma clang diagnostic pop
-template <int N>
-__device__ __forceinline__ void lds_wait() {
-  static_assert(N >= 0 && N <= 15, "lgkmcnt is a 4-bit counter");
-  asm volatile("s_waitcnt lgkmcnt(%0)" ::"n"(N) : "memory");
-  __builtin_amdgcn_sched_barrier(0);
-}
-
 // Halo rows un-swizzled since round 5 (make EXTRA=-DRT_V2_HSWZ=1 restores the XOR swizzle of the chunk index with bits 2-3 of the
 // pixel): the swizzle made the pixel-fragment reads conflict-free at ~4 address instructions per read, and the main loop is bound
 // by instruction issue, not by the LDS (24 % busy): without it the reads are 2-way conflicting and the server det network runs
@@ -171,6 +117,7 @@ __global__ __launch_bounds__(64 * NW, 2) void k_conv16v2(const ConvArgs2 c2) {
   const unsigned lds0 = __builtin_amdgcn_readfirstlane(lds_addr(smem2));
   const unsigned wring_b = lds0 + (unsigned)c2.hbufs * (unsigned)c2.hbuf_halves * 2u + (unsigned)__builtin_amdgcn_readfirstlane(wid) * 1024u;   // this wave's slots of ring slot 0
   const unsigned hbuf_b = lds0 + (unsigned)__builtin_amdgcn_readfirstlane(wid) * 1024u;
+  // (the requests of both streams are unguarded: the s_nop 4 measured slower than the run-to-run spread, lds_asm.h)
   auto dma_wrow = [&](int rr) {         // kernel row rr -> ring slot rr % wslots
     if (bdma) {
       const unsigned dstb = __builtin_amdgcn_readfirstlane(wring_b + (unsigned)(rr % wslots) * (unsigned)(wbuf_halves * 2));
@@ -178,7 +125,7 @@ __global__ __launch_bounds__(64 * NW, 2) void k_conv16v2(const ConvArgs2 c2) {
 #pragma unroll
       for (int i = 0; i < WI; i++) {
         if (i * NTHR >= wchunks) break;   // (uniform)
-        blds16(wsrc[i] >= 0 ? (unsigned)wsrc[i] * 2u : 0x80000000u, wrs, dstb + (unsigned)i * (NTHR * 16), soff);
+        blds16_unguarded(wsrc[i] >= 0 ? (unsigned)wsrc[i] * 2u : 0x80000000u, wrs, dstb + (unsigned)i * (NTHR * 16), soff);
       }
       return;
     }
@@ -188,7 +135,7 @@ __global__ __launch_bounds__(64 * NW, 2) void k_conv16v2(const ConvArgs2 c2) {
     for (int i = 0; i < WI; i++) {
       if (i * NTHR >= wchunks) break;   // (uniform)
       const half_t* src = wsrc[i] >= 0 ? wg + wsrc[i] : c2.zeros;
-      RT_GLDS16(src, dst + (size_t)i * NTHR * 8 + wave_slot);
+      glds16((unsigned long long)src, __builtin_amdgcn_readfirstlane(lds_addr(dst + (size_t)i * NTHR * 8 + wave_slot)));
     }
   };
   // prologue, ordered so that the requests are in flight while the rest of the index arithmetic runs: weight rows first
@@ -216,7 +163,7 @@ __global__ __launch_bounds__(64 * NW, 2) void k_conv16v2(const ConvArgs2 c2) {
 #pragma unroll
       for (int i = 0; i < V2_HMAX; i++) {
         if (i * NTHR >= hchunks) break;   // (uniform)
-        blds16(hsrc[i] >= 0 ? (unsigned)(hsrc[i] & 0x0fffffff) * 2u : 0x80000000u, xrs, dstb + (unsigned)i * (NTHR * 16), soff);
+        blds16_unguarded(hsrc[i] >= 0 ? (unsigned)(hsrc[i] & 0x0fffffff) * 2u : 0x80000000u, xrs, dstb + (unsigned)i * (NTHR * 16), soff);
       }
       return;
     }
@@ -227,7 +174,7 @@ __global__ __launch_bounds__(64 * NW, 2) void k_conv16v2(const ConvArgs2 c2) {
       if (i * NTHR >= hchunks) break;   // (uniform)
       const bool ok = hsrc[i] >= 0 && (hsrc[i] >> 28) * 8 < cvalid;
       const half_t* src = ok ? xtile + (hsrc[i] & 0x0fffffff) + s * KS : c2.zeros;
-      RT_GLDS16(src, dst + (size_t)i * NTHR * 8 + wave_slot);
+      glds16((unsigned long long)src, __builtin_amdgcn_readfirstlane(lds_addr(dst + (size_t)i * NTHR * 8 + wave_slot)));
     }
   };
   dma_halo(0);
@@ -253,7 +200,7 @@ __global__ __launch_bounds__(64 * NW, 2) void k_conv16v2(const ConvArgs2 c2) {
       for (int e = 0; e < 16; e++) acc[i][j][e] = 0.f;
 
   if (kstamp) a.stamps[4001] = __builtin_amdgcn_s_memtime();
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  vm_wait<0>();
   __builtin_amdgcn_s_barrier();
   if (kstamp) a.stamps[4002] = __builtin_amdgcn_s_memtime();
   const int nw = (wchunks + NTHR - 1) / NTHR, nh = (hchunks + NTHR - 1) / NTHR;   // DMA instructions per row / per halo, per thread
@@ -329,11 +276,11 @@ __global__ __launch_bounds__(64 * NW, 2) void k_conv16v2(const ConvArgs2 c2) {
     if (D == 0 || (c2.hbufs == 1 && ndy == 0)) {
       // single halo buffer / single weight buffer: every wave is done with the old contents only after the barrier; request and
       // wait here (exposed; with NW = 4 the CU's other workgroup multiplies meanwhile)
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      vm_wait<0>();
       __builtin_amdgcn_s_barrier();
       if (D == 0) dma_wrow(rr + 1);
       if (c2.hbufs == 1 && ndy == 0) dma_halo(ns);
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      vm_wait<0>();
       __builtin_amdgcn_s_barrier();
       continue;
     }
@@ -343,18 +290,7 @@ __global__ __launch_bounds__(64 * NW, 2) void k_conv16v2(const ConvArgs2 c2) {
     // (ring of 2: row rr + 1 itself was requested in this iteration, before the halo: only that halo may stay in flight)
     const int keep = (halo_now && ndy == 0) ? 0 : ((D > 1 && rr + 2 < nrows) ? nw : 0) + (halo_now ? nh : 0);
     // (a halo requested in an earlier iteration of this slab is older than row rr + 1's weights and therefore retired with them)
-    switch (keep) {
-      case 0: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
-      case 1: asm volatile("s_waitcnt vmcnt(1)" ::: "memory"); break;
-      case 2: asm volatile("s_waitcnt vmcnt(2)" ::: "memory"); break;
-      case 3: asm volatile("s_waitcnt vmcnt(3)" ::: "memory"); break;
-      case 4: asm volatile("s_waitcnt vmcnt(4)" ::: "memory"); break;
-      case 5: asm volatile("s_waitcnt vmcnt(5)" ::: "memory"); break;
-      case 6: asm volatile("s_waitcnt vmcnt(6)" ::: "memory"); break;
-      case 7: asm volatile("s_waitcnt vmcnt(7)" ::: "memory"); break;
-      case 8: asm volatile("s_waitcnt vmcnt(8)" ::: "memory"); break;
-      default: asm volatile("s_waitcnt vmcnt(9)" ::: "memory"); break;
-    }
+    vm_wait<9>(keep);   // (capped at 9, the form the kernel was measured with)
     if (stamp) a.stamps[rr * 5 + 3] = __builtin_amdgcn_s_memtime();
     __builtin_amdgcn_s_barrier();
     if (stamp) a.stamps[rr * 5 + 4] = __builtin_amdgcn_s_memtime();
@@ -369,7 +305,7 @@ __global__ __launch_bounds__(64 * NW, 2) void k_conv16v2(const ConvArgs2 c2) {
   if (kstamp) a.stamps[4005] = __builtin_amdgcn_s_memtime();
   store_tile16<NTN, NTP>(a, acc, reinterpret_cast<half_t*>(smem2) + (size_t)wid * epi_scratch_halves<NTN>(), lane, nb0, oys, oxs, go);
   if (kstamp) a.stamps[4006] = __builtin_amdgcn_s_memtime();
-  if (kstamp) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); a.stamps[4004] = __builtin_amdgcn_s_memtime(); }
+  if (kstamp) { vm_wait<0>(); a.stamps[4004] = __builtin_amdgcn_s_memtime(); }
 }
 
 static const half_t* zero_page16() {   // per device: DMA source of padding (one allocation per process and device)
@@ -464,30 +400,19 @@ __global__ __launch_bounds__(512, 1) void k_gemm16p(const GemmArgs16 g) {
     const bool tail = krem && issued == nst - 1;
 #pragma unroll
     for (int i = 0; i < XCH; i++) {
-      glds16_s((tail && xk[i] >= krem) ? zaddr : xcur[i], issue_b + i * (NTHR * 16));
+      glds16((tail && xk[i] >= krem) ? zaddr : xcur[i], issue_b + i * (NTHR * 16));
       xcur[i] += xstep[i];
     }
 #pragma unroll
     for (int i = 0; i < WCH; i++) {
-      glds16_s(wcur[i], issue_b + XHALVES * 2 + i * (NTHR * 16));
+      glds16(wcur[i], issue_b + XHALVES * 2 + i * (NTHR * 16));
       wcur[i] += wstep[i];
     }
     issued++;
     issue_b = (issue_b + STAGE_B == slot_b + R * STAGE_B) ? slot_b : issue_b + STAGE_B;
     __builtin_amdgcn_sched_barrier(0);
   };
-  auto wait_keep = [&](int slabs) {   // leave the newest `slabs` slabs in flight
-    switch (slabs * PER) {
-      case 0: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
-      case 3: asm volatile("s_waitcnt vmcnt(3)" ::: "memory"); break;
-      case 4: asm volatile("s_waitcnt vmcnt(4)" ::: "memory"); break;
-      case 6: asm volatile("s_waitcnt vmcnt(6)" ::: "memory"); break;
-      case 8: asm volatile("s_waitcnt vmcnt(8)" ::: "memory"); break;
-      case 9: asm volatile("s_waitcnt vmcnt(9)" ::: "memory"); break;
-      case 12: asm volatile("s_waitcnt vmcnt(12)" ::: "memory"); break;
-      default: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
-    }
-  };
+  auto wait_keep = [&](int slabs) { vm_wait<2 * PER>(slabs * PER); };   // leave the newest `slabs` slabs in flight
   // prologue: slabs 0 .. R - 2 requested, slab 0 landed and visible
 #pragma unroll
   for (int s = 0; s < R - 1; s++)
@@ -511,12 +436,12 @@ __global__ __launch_bounds__(512, 1) void k_gemm16p(const GemmArgs16 g) {
   constexpr int FR = 32 * ROW * 2;   // bytes between fragments (32 rows)
   auto frags = [&](unsigned buf_b, int ks, h8 (&A)[NTN], h8 (&B)[NTP]) {
     const unsigned xa = buf_b + (ks ? xo1 : xo0), wa = buf_b + (ks ? wo1 : wo0);
-    B[0] = lds_read16_imm<0>(xa);
-    B[1] = lds_read16_imm<FR>(xa);
-    A[0] = lds_read16_imm<0>(wa);
-    if (NTN > 1) A[NTN > 1 ? 1 : 0] = lds_read16_imm<FR>(wa);
-    if (NTN > 2) A[NTN > 2 ? 2 : 0] = lds_read16_imm<2 * FR>(wa);
-    if (NTN > 3) A[NTN > 3 ? 3 : 0] = lds_read16_imm<3 * FR>(wa);
+    B[0] = lds_read16<h8>(xa);
+    B[1] = lds_read16<h8, FR>(xa);
+    A[0] = lds_read16<h8>(wa);
+    if (NTN > 1) A[NTN > 1 ? 1 : 0] = lds_read16<h8, FR>(wa);
+    if (NTN > 2) A[NTN > 2 ? 2 : 0] = lds_read16<h8, 2 * FR>(wa);
+    if (NTN > 3) A[NTN > 3 ? 3 : 0] = lds_read16<h8, 3 * FR>(wa);
   };
   auto mfmas = [&](const h8 (&A)[NTN], const h8 (&B)[NTP]) {
 #pragma unroll
@@ -533,22 +458,15 @@ __global__ __launch_bounds__(512, 1) void k_gemm16p(const GemmArgs16 g) {
     constexpr bool STEADY = decltype(steady)::value;
     const unsigned nxt_b = (cur_b + STAGE_B == lds_b + R * STAGE_B) ? lds_b : cur_b + STAGE_B;
     frags(cur_b, 1, A1, B1);
-    lds_wait<NR>();                                          // step 0's fragments are back, step 1's stay in flight
+    lgkm_wait<NR>();                                          // step 0's fragments are back, step 1's stay in flight
     mfmas(A0, B0);
-    if (STEADY) {
-      if (PER * (R - 3) == 4) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-      else if (PER * (R - 3) == 3) asm volatile("s_waitcnt vmcnt(3)" ::: "memory");
-      else if (PER * (R - 3) == 8) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-      else if (PER * (R - 3) == 6) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-      else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    } else {
-      wait_keep(max(0, min(nst - 1, s + R - 2) - (s + 1)));   // slab s + 1 has landed (this wave's requests)
-    }
+    if (STEADY) vm_wait<PER * (R - 3)>();
+    else wait_keep(max(0, min(nst - 1, s + R - 2) - (s + 1)));   // slab s + 1 has landed (this wave's requests)
     __builtin_amdgcn_s_barrier();                            // ... and everybody's; every wave is done with slab s - 1
     if (STEADY) dma_slab();
     __builtin_amdgcn_sched_barrier(0);
     frags(nxt_b, 0, A0, B0);
-    lds_wait<NR>();
+    lgkm_wait<NR>();
     mfmas(A1, B1);
     cur_b = nxt_b;
   };
@@ -556,9 +474,9 @@ __global__ __launch_bounds__(512, 1) void k_gemm16p(const GemmArgs16 g) {
   for (; s + R - 1 < nst; s++) stage(s, std::true_type{});
   for (; s + 1 < nst; s++) stage(s, std::false_type{});
   frags(cur_b, 1, A1, B1);
-  lds_wait<NR>();
+  lgkm_wait<NR>();
   mfmas(A0, B0);
-  lds_wait<0>();
+  lgkm_wait<0>();
   mfmas(A1, B1);
   __builtin_amdgcn_s_barrier();   // every wave is done with the ring: it becomes the transpose scratch
   int oys[NTP], oxs[NTP];

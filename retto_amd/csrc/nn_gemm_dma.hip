@@ -16,6 +16,7 @@
 //     tile t + 1 (counted vmcnt: the first wait after an epilogue leaves exactly those stores in flight).
 #include "nn.h"
 #include "nn_dev.h"
+#include "lds_asm.h"
 
 #include <algorithm>
 #include <cstdio>
@@ -28,41 +29,9 @@
 namespace rt {
 namespace nn {
 
-namespace {
-
-#pragma clang diagnostic push
-#pragma clang diagnostic ignored "-Winline-asm"   // M0 is named as clobbered on purpose: nothing else in this kernel uses it
-// LDS-DMA request: lane i writes 16 bytes at M0 + 16 i; source = 64-bit scalar base + 32-bit per-lane byte offset.
-// Inline asm, not the builtin: with the builtin in a loop hipcc waits lgkmcnt(0) before every MFMA group (nn_f16_dma.hip).
-__device__ __forceinline__ void glds16_so(unsigned voff, const void* sbase, unsigned lds_sgpr) {
-  asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(voff), "s"(sbase), "s"(lds_sgpr) : "memory", "m0");
-}
-// The same through a buffer resource (round 5): source = resource base + per-lane byte offset + scalar offset; a lane whose offset
-// is beyond the resource's range writes zeros.
-__device__ __forceinline__ void blds16(unsigned voff, __amdgpu_buffer_rsrc_t rs, unsigned lds_sgpr, unsigned soff) {
-  asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tbuffer_load_dwordx4 %0, %1, %3 offen lds" ::"v"(voff), "s"(rs), "s"(lds_sgpr), "s"(soff) : "memory", "m0");
-}
-#pragma clang diagnostic pop
 #ifndef RT_G32P_BUF
 #define RT_G32P_BUF 1   // 0 (make EXTRA=-DRT_G32P_BUF=0): the round-4 request form, per-lane offsets re-derived at every request
 #endif
-__device__ __forceinline__ unsigned lds_addr32(const void* p) { return (unsigned)(size_t)(__attribute__((address_space(3))) const char*)p; }
-template <int OFF>
-__device__ __forceinline__ f32x4 lds_read16f(unsigned byte_addr) {   // address + compile-time offset in the instruction
-  static_assert(OFF >= 0 && OFF < 65536, "16-bit offset field");
-  f32x4 v;
-  asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(v) : "v"(byte_addr), "n"(OFF));
-  return v;
-}
-__device__ __forceinline__ int lane_id() { return (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)); }
-template <int N>
-__device__ __forceinline__ void lgkm_wait() {   // leaves the newest N LDS reads in flight and pins the order around it
-  static_assert(N >= 0 && N <= 15, "lgkmcnt is a 4-bit counter");
-  asm volatile("s_waitcnt lgkmcnt(%0)" ::"n"(N) : "memory");
-  __builtin_amdgcn_sched_barrier(0);
-}
-
-}  // namespace
 
 struct GemmPArgs {
   const float* A; const float* Wp; float* C;
@@ -94,7 +63,7 @@ __global__ __launch_bounds__(P_NTHR, 1) void k_gemm32p(const GemmPArgs g) {
   const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);   // (SGPR: everything derived from it stays scalar)
   const int r = lane & 15, q = lane >> 4;
   const int wm = wid / WN, wn = wid - wm * WN;
-  const unsigned lds_b = __builtin_amdgcn_readfirstlane(lds_addr32(smem32p));
+  const unsigned lds_b = __builtin_amdgcn_readfirstlane(lds_addr(smem32p));
   float* bias_l = reinterpret_cast<float*>(smem32p + 2 * P_STAGE);
   const int nkc = (g.K + KC - 1) / KC;
   const int G = gridDim.x;
@@ -168,13 +137,14 @@ __global__ __launch_bounds__(P_NTHR, 1) void k_gemm32p(const GemmPArgs g) {
           req_a = (unsigned)(ln_ >> 3) * pitch + ch_; req_w = (unsigned)((ln_ >> 3) * 128) + ch_;
           swk += (unsigned)wid * 1024u;
         }
-        blds16(req_a, ars, dst, sa);
-        blds16(req_a + 96u * pitch, ars, dst + 1 * (P_NW * 1024), sa);
-        if (p2_is_a) blds16(req_a + 192u * pitch, ars, dst + 2 * (P_NW * 1024), sa);
-        else blds16(req_w, wrs, dst + 2 * (P_NW * 1024), swk);
-        blds16(req_w, wrs, dst + 3 * (P_NW * 1024), swk + 12 * 1024);
-        blds16(req_w, wrs, dst + 4 * (P_NW * 1024), swk + 24 * 1024);
-        if (wid + 5 * P_NW < P_AJ + P_WJ) blds16(req_w, wrs, dst + 5 * (P_NW * 1024), swk + 36 * 1024);
+        // (unguarded: the s_nop 4 measured slower than the run-to-run spread, lds_asm.h)
+        blds16_unguarded(req_a, ars, dst, sa);
+        blds16_unguarded(req_a + 96u * pitch, ars, dst + 1 * (P_NW * 1024), sa);
+        if (p2_is_a) blds16_unguarded(req_a + 192u * pitch, ars, dst + 2 * (P_NW * 1024), sa);
+        else blds16_unguarded(req_w, wrs, dst + 2 * (P_NW * 1024), swk);
+        blds16_unguarded(req_w, wrs, dst + 3 * (P_NW * 1024), swk + 12 * 1024);
+        blds16_unguarded(req_w, wrs, dst + 4 * (P_NW * 1024), swk + 24 * 1024);
+        if (wid + 5 * P_NW < P_AJ + P_WJ) blds16_unguarded(req_w, wrs, dst + 5 * (P_NW * 1024), swk + 36 * 1024);
       }
       int ln = 0;
       if (ASC) { ln = lane_id(); asm volatile("" : "+v"(ln)); }
@@ -230,8 +200,8 @@ __global__ __launch_bounds__(P_NTHR, 1) void k_gemm32p(const GemmPArgs g) {
   const unsigned wo0 = P_ABYTES + (unsigned)((wn * NT * 16 + r) * 128) + (((unsigned)q ^ sw) << 4);
   constexpr int FR = 16 * 128;   // bytes between 16-row fragments
   f32x4 acc[MT][NT], A0[MT], A1[MT], B[NT];   // (every tile's first five steps start their accumulators from zero)
-#define RT_RDA(addr, a) do { a[0] = lds_read16f<0>(addr); a[1] = lds_read16f<FR>(addr); a[2] = lds_read16f<2 * FR>(addr); a[3] = lds_read16f<3 * FR>(addr); } while (0)
-#define RT_RDB(addr, nt) B[nt] = lds_read16f<(nt) * FR>(addr)
+#define RT_RDA(addr, a) do { a[0] = lds_read16<f32x4>(addr); a[1] = lds_read16<f32x4, FR>(addr); a[2] = lds_read16<f32x4, 2 * FR>(addr); a[3] = lds_read16<f32x4, 3 * FR>(addr); } while (0)
+#define RT_RDB(addr, nt) B[nt] = lds_read16<f32x4, (nt) * FR>(addr)
   // 16 MFMAs of one weight fragment (16 output channels) against the wave's 64 pixels
   // ... starting the accumulators of that column tile from zero (first group of a tile: C = 0 in the first k step, so the
   // accumulator registers are dead between the previous tile's epilogue chunk and here)
@@ -247,7 +217,7 @@ __global__ __launch_bounds__(P_NTHR, 1) void k_gemm32p(const GemmPArgs g) {
   // ---- prologue: slabs 0 and 1 requested, landed and visible; the first fragments requested ------------------------------
   dma_issue();
   dma_issue();
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  vm_wait<0>();
   __syncthreads();   // (also publishes the bias)
   unsigned cur_b = lds_b;
   if (HALF) RT_RDA(cur_b + xo0, A1); else RT_RDA(cur_b + xo0, A0);
@@ -265,8 +235,8 @@ __global__ __launch_bounds__(P_NTHR, 1) void k_gemm32p(const GemmPArgs g) {
   // here 2.55 M, at the start of the next slab 2.58 M -- the placement is not what the requests cost.
   // fetched / pub: wave 0, lane 0 holds the counter value an atomic issued at the start of this slab returns (tile id - G)
   auto handover = [&](unsigned fetched, bool pub) __attribute__((always_inline)) {
-    if (after_epi) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(P_NSTORE) : "memory");
-    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    if (after_epi) vm_wait<P_NSTORE>();
+    else vm_wait<0>();
     after_epi = false;
     if (pub) {   // (the atomic was issued eight steps ago: the wait above covered it)
       if (wid == 0 && lane_id() == 0) tileq[pub_slot] = G + (int)fetched;
@@ -353,7 +323,7 @@ __global__ __launch_bounds__(P_NTHR, 1) void k_gemm32p(const GemmPArgs g) {
     bool pub = false;
     if (!EPI && fetch_now) {
       if (wid == 0 && lane_id() == 0)
-        asm volatile("s_nop 4\n\tglobal_atomic_add %0, %1, %2, %3 sc0" : "=v"(fetched) : "v"(0u), "v"(1u), "s"(g.sched) : "memory");
+        fetched = tile_queue_fetch(g.sched);
       fetch_now = false; pub = true;
       __builtin_amdgcn_sched_barrier(0);
     }
@@ -498,7 +468,7 @@ __global__ __launch_bounds__(W_NTHR, 1) void k_gemm32w(const GemmWArgs g) {
   const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int r = lane & 15, q = lane >> 4;
   const int wm = wid >> 1, wn = wid & 1;
-  const unsigned lds_b = __builtin_amdgcn_readfirstlane(lds_addr32(smem32w));
+  const unsigned lds_b = __builtin_amdgcn_readfirstlane(lds_addr(smem32w));
   float* bias_l = reinterpret_cast<float*>(smem32w + W_WBYTES + 2 * W_ABYTES);
   if (tid < 128) bias_l[tid] = g.epi.bias ? g.epi.bias[tid] : 0.f;
   const int G = gridDim.x;
@@ -527,7 +497,7 @@ __global__ __launch_bounds__(W_NTHR, 1) void k_gemm32w(const GemmWArgs g) {
   };
   int t = blockIdx.x;
   issue_a(t, 0u);
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  vm_wait<0>();
   __syncthreads();
   // fragment addresses: lane (r, q) reads row (16-row tile base + r), logical chunk 4 grp + q; group 1 = byte address ^ 64
   const unsigned sw = (unsigned)((r >> 1) & 7);
@@ -574,8 +544,8 @@ __global__ __launch_bounds__(W_NTHR, 1) void k_gemm32w(const GemmWArgs g) {
       // the next tile has landed (this wave's requests; the 4 stores behind them may stay in flight -- a partial tile's
       // stores may be skipped by whole waves: then nothing is assumed)
       if (more) {
-        if (full) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        if (full) vm_wait<4>();
+        else vm_wait<0>();
       }
       __syncthreads();   // ... and everybody's; every wave is done with this tile's buffer
     }

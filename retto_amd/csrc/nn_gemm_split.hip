@@ -29,6 +29,7 @@
 //     MFMA steps, one 16-channel tile at a time (its accumulators restart from zero there).
 #include "nn.h"
 #include "nn_dev.h"
+#include "lds_asm.h"
 
 #include <algorithm>
 #include <cstdio>
@@ -46,38 +47,6 @@ typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
-#pragma clang diagnostic push
-#pragma clang diagnostic ignored "-Winline-asm"
-// LDS-DMA through a buffer resource: lane i writes 16 bytes at M0 + 16 i; source = base + per-lane offset + scalar offset; a
-// lane whose per-lane offset is beyond the resource's range writes zeros.
-// s_nop 4 first: this kernel spills scalar registers to VGPR lanes, and a descriptor word restored by v_readlane (a VALU write
-// of an SGPR) right in front of the asm block needs 5 wait states before a VMEM instruction reads it -- the hazard recogniser
-// does not see the buffer_load inside the block.  Without it: stale descriptor words, memory faults that came and went with
-// the register allocation.
-__device__ __forceinline__ void blds16(unsigned voff, __amdgpu_buffer_rsrc_t rs, unsigned lds_sgpr, unsigned soff) {
-  asm volatile("s_nop 4\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tbuffer_load_dwordx4 %0, %1, %3 offen lds" ::"v"(voff), "s"(rs), "s"(lds_sgpr), "s"(soff) : "memory", "m0");
-}
-#pragma clang diagnostic pop
-// 4-byte form: lane i writes one dword at M0 + 4 i (the squeeze-excite scale vectors of a slab: 2 images x 32 channels per instruction)
-__device__ __forceinline__ void blds4(unsigned voff, __amdgpu_buffer_rsrc_t rs, unsigned lds_sgpr) {
-  asm volatile("s_nop 4\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tbuffer_load_dword %0, %1, 0 offen lds" ::"v"(voff), "s"(rs), "s"(lds_sgpr) : "memory", "m0");
-}
-__device__ __forceinline__ unsigned lds_addr32(const void* p) { return (unsigned)(size_t)(__attribute__((address_space(3))) const char*)p; }
-#pragma clang diagnostic pop
-template <int OFF>
-__device__ __forceinline__ u32x4 lds_read16u(unsigned byte_addr) {   // address + compile-time offset in the instruction
-  static_assert(OFF >= 0 && OFF < 65536, "16-bit offset field");
-  u32x4 v;
-  asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(v) : "v"(byte_addr), "n"(OFF));
-  return v;
-}
-template <int N>
-__device__ __forceinline__ void lgkm_wait() {   // leaves the newest N LDS operations in flight and pins the order around it
-  asm volatile("s_waitcnt lgkmcnt(%0)" ::"n"(N) : "memory");
-  __builtin_amdgcn_sched_barrier(0);
-}
-__device__ __forceinline__ int lane_id() { return (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)); }
 
 __device__ __forceinline__ unsigned cvt_pk_bf16(float a, float b) {   // v_cvt_pk_bf16_f32: a -> low half, b -> high half (RNE)
   const f32x2 v = {a, b};
@@ -162,7 +131,7 @@ __global__ __launch_bounds__(S_NTHR, 2) void k_gemm_split(const GemmSArgs g) {
   const int tid = threadIdx.x, lane = tid & 63;
   const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int r = lane & 15, q = lane >> 4;
-  const unsigned lds_b = __builtin_amdgcn_readfirstlane(lds_addr32(smem_s));
+  const unsigned lds_b = __builtin_amdgcn_readfirstlane(lds_addr(smem_s));
   float* bias_l = reinterpret_cast<float*>(smem_s + S_OFF_BIAS);
   // (the bias of the column block whose epilogue is pending; restaged between two barriers of a tile's last slab when the
   //  next tile's column block differs)
@@ -298,23 +267,14 @@ __global__ __launch_bounds__(S_NTHR, 2) void k_gemm_split(const GemmSArgs g) {
   };
   auto a_issue = [&]() __attribute__((always_inline)) { a_piece(IntTag<0>{}); a_piece(IntTag<1>{}); a_piece(IntTag<2>{}); a_piece(IntTag<3>{}); };
   auto w_issue = [&]() __attribute__((always_inline)) { w_piece(IntTag<0>{}); w_piece(IntTag<1>{}); w_piece(IntTag<2>{}); w_piece(IntTag<3>{}); };
-  // s_waitcnt vmcnt(n), n at run time (the instruction takes an immediate; a smaller n only waits for more)
-  auto vm_wait_n = [&](int n) __attribute__((always_inline)) {
-#define RT_VW(N) case N: asm volatile("s_waitcnt vmcnt(" #N ")" ::: "memory"); break;
-    switch (min(n, 47)) {
-      RT_VW(0) RT_VW(1) RT_VW(2) RT_VW(3) RT_VW(4) RT_VW(5) RT_VW(6) RT_VW(7) RT_VW(8) RT_VW(9) RT_VW(10) RT_VW(11) RT_VW(12) RT_VW(13) RT_VW(14) RT_VW(15)
-      RT_VW(16) RT_VW(17) RT_VW(18) RT_VW(19) RT_VW(20) RT_VW(21) RT_VW(22) RT_VW(23) RT_VW(24) RT_VW(25) RT_VW(26) RT_VW(27) RT_VW(28) RT_VW(29) RT_VW(30) RT_VW(31)
-      RT_VW(32) RT_VW(33) RT_VW(34) RT_VW(35) RT_VW(36) RT_VW(37) RT_VW(38) RT_VW(39) RT_VW(40) RT_VW(41) RT_VW(42) RT_VW(43) RT_VW(44) RT_VW(45) RT_VW(46) RT_VW(47)
-    }
-#undef RT_VW
-    __builtin_amdgcn_sched_barrier(0);
-  };
+  // s_waitcnt vmcnt(n), n at run time, capped at 47 (a smaller n only waits for more)
+  auto vm_wait_n = [&](int n) __attribute__((always_inline)) { vm_wait<47>(n); __builtin_amdgcn_sched_barrier(0); };
   // the wait that closes a weight group: everything issued after the last piece of the group it needs may stay in flight.  EXPECT =
   // the count of the steady state at that site (one compare instead of the switch's tree)
-  auto vm_wait = [&](auto expect_tag) __attribute__((always_inline)) {
+  auto group_wait = [&](auto expect_tag) __attribute__((always_inline)) {
     constexpr int EXPECT = decltype(expect_tag)::value;
     const int n = vc_ops - vs_next;
-    if (n == EXPECT) { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(EXPECT) : "memory"); __builtin_amdgcn_sched_barrier(0); }
+    if (n == EXPECT) { vm_wait<EXPECT>(); __builtin_amdgcn_sched_barrier(0); }
     else vm_wait_n(n);
     vs_next = vs_later;
   };
@@ -342,9 +302,9 @@ __global__ __launch_bounds__(S_NTHR, 2) void k_gemm_split(const GemmSArgs g) {
   //  freed them -- 4 MFMAs before their first use; every wait that follows leaves exactly the newest three reads in flight)
   auto read_b = [&](auto slot_tag, auto off_tag, unsigned wf) __attribute__((always_inline)) {   // wf: w_fr + ring buffer of the half
     constexpr int SL = decltype(slot_tag)::value, OFF = decltype(off_tag)::value;
-    Bf[SL][0] = lds_read16u<OFF>(wf);
-    Bf[SL][1] = lds_read16u<OFF + 1024>(wf);
-    Bf[SL][2] = lds_read16u<OFF + 2048>(wf);
+    Bf[SL][0] = lds_read16<u32x4, OFF>(wf);
+    Bf[SL][1] = lds_read16<u32x4, OFF + 1024>(wf);
+    Bf[SL][2] = lds_read16<u32x4, OFF + 2048>(wf);
   };
 
   // ---- epilogue of the previous tile, one 16-channel tile at a time ------------------------------------------------------------
@@ -396,7 +356,7 @@ __global__ __launch_bounds__(S_NTHR, 2) void k_gemm_split(const GemmSArgs g) {
   a_issue();
   a_issue();
   vs_next = vs_later = vc_ops;
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  vm_wait<0>();
   __syncthreads();
   const float* sc_lds = reinterpret_cast<const float*>(smem_s + S_OFF_SC);
   auto split_into = [&](int mt, u32x4& h, u32x4& m, u32x4& l, int slot) __attribute__((always_inline)) {
@@ -443,10 +403,10 @@ __global__ __launch_bounds__(S_NTHR, 2) void k_gemm_split(const GemmSArgs g) {
       __builtin_amdgcn_sched_barrier(0); } while (0)
 #define RT_STEP(SL, nt, NOFF, REQ) RT_STEP_V(SL, nt, NOFF, REQ, (void)0)
     // last step of a group: this tile's fragments are in registers; the next group's weights have landed (this wave's pieces:
-    // vm_wait; everybody's: the barrier), its first fragments are requested, then the 12 MFMAs
+    // group_wait; everybody's: the barrier), its first fragments are requested, then the 12 MFMAs
 #define RT_LAST(SL, nt, REQ, WORK, VME) do { \
       lgkm_wait<0>(); \
-      vm_wait(IntTag<VME>{}); \
+      group_wait(IntTag<VME>{}); \
       __builtin_amdgcn_s_barrier(); \
       __builtin_amdgcn_sched_barrier(0); \
       wb = wb == 2 ? 0 : wb + 1; \
@@ -468,7 +428,7 @@ __global__ __launch_bounds__(S_NTHR, 2) void k_gemm_split(const GemmSArgs g) {
     unsigned fetched = 0;
     if (EPI) {
       if (wid == 0) {
-        if (lane_id() == 0) asm volatile("s_nop 4\n\tglobal_atomic_add %0, %1, %2, %3 sc0" : "=v"(fetched) : "v"(0u), "v"(1u), "s"(g.sched) : "memory");
+        if (lane_id() == 0) fetched = tile_queue_fetch(g.sched);
         vm_note(1); vs_at = vc_ops;
       }
       __builtin_amdgcn_sched_barrier(0);
