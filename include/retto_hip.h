@@ -110,11 +110,16 @@ typedef struct rt_config {
                                  scores a box by the mean over the contour's own polygon (its full point chain) instead of its
                                  min-area rect, as the field's doc comment specifies; the reference itself never reads the field
                                  and computes Fast either way.  rt_create rejects other values with RT_ERR_INVALID. */
+  int32_t rec_return_candidates; /* 0 = off (default); K = 1 .. RT_MAX_CANDIDATES: per kept token its time step, its own
+                                 probability and the K - 1 next best classes (rt_results_rec_candidates).  The reference has no
+                                 counterpart (rec_processor.rs:155 `// TODO: word_results`).  Off: no extra launch, no extra
+                                 workspace.  rt_create rejects other values with RT_ERR_INVALID. */
   int32_t rec_return_word_box; /* 0 = off (default), 1 = word boxes (rt_results_rec_words): RecCharacter::decode's
                                  `return_word_box` (rec_processor.rs:48-56), which the reference declares but never implements
                                  (its only caller passes false, :199-206).  Off: no extra launch and no extra workspace.
                                  rt_create rejects other values with RT_ERR_INVALID. */
 } rt_config;
+#define RT_MAX_CANDIDATES 8
 typedef enum rt_dtype { RT_DTYPE_F32 = 0, RT_DTYPE_F16 = 1 } rt_dtype;
 
 typedef struct rt_session rt_session;
@@ -250,6 +255,36 @@ RT_API const char* rt_results_rec_word_text(rt_results* r, int page, int line, i
 RT_API int rt_debug_word_boxes(const void* dict, size_t dict_len, const int32_t* tokens, const int32_t* cols, int n, int T, int W,
                                int resized_w, const float* box8_after, int rot180, int after_w, int after_h, int ori_w, int ori_h,
                                rt_word* out, int* n_words);
+/* ---- token candidates (rt_config.rec_return_candidates = K) ------------------------------------------------------------------
+ * Per kept CTC token of a line: its time step and K (class id, probability) pairs.  retto_amd/csrc/ctc_candidates.h states the
+ * rule; in short, for token j kept at time step cols[j]:
+ *   - rank 0 is the decode's own choice: (token id, the fused CTC head's probability at that step), bit for bit what the line's
+ *     rec score averages;
+ *   - ranks 1 .. K-1 are the other classes (the blank 0 included) with the largest logits, recomputed in fp32 from the head's
+ *     input features for the kept rows only, ordered by logit descending, then id ascending; their probabilities are the softmax
+ *     over every class of the recomputed logits;
+ *   - (-1, 0.0f) fills the row when the model has fewer than K classes.
+ * Near ties: the recomputed logits come from another GEMM launch than the fused head's, so a runner-up's probability may exceed
+ * rank 0's by rounding; rank 0 stays the decode's choice.  K = 1 recomputes nothing (confidences and time steps only).  Ranks
+ * >= 1 are repeatable run to run and equal across rt_run_batch, submit / wait and the encoded entry points on the same batch;
+ * they are NOT promised bit-identical when the batch around a line changes (the logits GEMM's plan may depend on the number of
+ * kept rows).  Everything else the session returns is bit-identical to K = 0. */
+typedef struct rt_candidate { int32_t id; float prob; } rt_candidate;
+/* returns K (0 when the option is off or page / line are out of range).  *cands: [n_tokens][K] row-major, *cols: [n_tokens],
+ * n_tokens = what rt_results_rec_tokens returns for the line; either pointer may be NULL.  Library-owned until rt_results_free. */
+RT_API int rt_results_rec_candidates(const rt_results* r, int page, int line, const rt_candidate** cands, const int32_t** cols);
+/* The device path of the option on host arrays (k_ctc_kept_rows, row gather, the CTC FC GEMM, k_ctc_topk; chunk_rows kept rows
+ * per GEMM, 0 = the production chunk).  z5 [rows][120]: head input features; W [120][N], bias [N] (or NULL): the CTC FC; idx /
+ * prob [rows]: the fused head's argmax and probability per time step; tokens_per_line [n_lines]: time steps per line (sum =
+ * rows).  Kept token j of a line whose first row is o: cols_out[o + j], cands_out[(o + j) * K .. + K); entries past a line's
+ * token count keep what the caller put there.  n_tokens_out [n_lines]: kept tokens per line.  z5 may be NULL when K = 1. */
+RT_API int rt_debug_ctc_candidates(rt_session* s, const float* z5, const float* W, const float* bias, int N, const int32_t* idx,
+                                   const float* prob, const int32_t* tokens_per_line, int n_lines, int K, int chunk_rows,
+                                   rt_candidate* cands_out, int32_t* cols_out, int32_t* n_tokens_out);
+/* The same rule on the CPU in plain fp32 loops (ctc_candidates.h), GPU-free and sessionless; same layout. */
+RT_API int rt_debug_ctc_candidates_host(const float* z5, const float* W, const float* bias, int N, const int32_t* idx,
+                                        const float* prob, const int32_t* tokens_per_line, int n_lines, int K,
+                                        rt_candidate* cands_out, int32_t* cols_out, int32_t* n_tokens_out);
 /* f32 sum of every det probability map produced in the call (keeps the network's
  * output observable when det_map_override is used) */
 RT_API double rt_results_det_checksum(const rt_results* r);

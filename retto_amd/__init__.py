@@ -13,7 +13,7 @@ from __future__ import annotations
 import ctypes as C
 import io
 from dataclasses import dataclass, field
-from typing import Callable, List, Optional, Sequence, Union
+from typing import Callable, List, Optional, Sequence, Tuple, Union
 
 import numpy as np
 
@@ -107,6 +107,9 @@ class RecProcessorConfig:  # rec_processor.rs:102-136
     # RecCharacter::decode's return_word_box (rec_processor.rs:48-56; the reference never implements it): per-word boxes in
     # RecProcessorSingleResult.words (include/retto_hip.h "word boxes" for the rule)
     return_word_box: bool = False
+    # rt_config.rec_return_candidates: 0 = off, K = 1..8: per kept token its time step (RecProcessorSingleResult.token_cols) and K
+    # candidates (.candidates): the token itself, then the K - 1 next best classes (include/retto_hip.h "token candidates")
+    return_candidates: int = 0
 
 
 @dataclass
@@ -179,6 +182,11 @@ class RecProcessorSingleResult:
     score: float
     tokens: np.ndarray = None  # kept CTC token ids (not in the reference struct; exposed for parity checks)
     words: Optional[List[RecWord]] = None  # RecProcessorConfig.return_word_box; None when off
+    # RecProcessorConfig.return_candidates = K; None when off.  candidates: per kept token a list of K (id, text, prob), rank 0 the
+    # token itself with the probability the score averages, then the next best classes (id -1, text "" where the model has fewer
+    # than K classes); token_cols: the tokens' time steps
+    candidates: Optional[List[List[Tuple[int, str, float]]]] = None
+    token_cols: Optional[np.ndarray] = None
 
 
 @dataclass
@@ -245,6 +253,7 @@ class _Handle:
         c.cls_batch_num, c.cls_thresh = cl.batch_num, cl.thresh
         c.rec_batch_num = rc.batch_num
         c.rec_return_word_box = 1 if rc.return_word_box else 0
+        c.rec_return_candidates = int(rc.return_candidates)
         if tuple(cl.label) != (0, 180):
             raise InvalidArgument("cls label set other than [0, 180] is not supported")
         c.max_boxes_per_page = cfg.max_boxes_per_page; c.det_sub_batch = cfg.det_sub_batch; c.lanes = cfg.lanes
@@ -377,6 +386,12 @@ def debug_word_boxes(dict_bytes: bytes, tokens, cols, T: int, W: int, resized_w:
     ents = parse_dictionary(dict_bytes)
     return [_rec_word(out[j], "".join(ents[int(t)] for t in tok[out[j].first_token:out[j].first_token + out[j].n_tokens]))
             for j in range(nw.value)]
+
+
+def _candidate_lists(cands, K: int, n_tokens: int, entries: Sequence[str]) -> List[List[Tuple[int, str, float]]]:
+    """rt_candidate [n_tokens][K] -> per token its K (id, text, prob); text from the dictionary entries, "" for the fill id -1."""
+    return [[(int(c.id), entries[c.id] if c.id >= 0 else "", float(c.prob)) for c in (cands[j * K + q] for q in range(K))]
+            for j in range(n_tokens)]
 
 
 def parse_dictionary(data: bytes) -> List[str]:
@@ -516,8 +531,25 @@ class RettoSession:
             nt = lib.rt_results_rec_tokens(r, page, k, C.byref(tp))
             toks = np.ctypeslib.as_array(tp, (nt,)).copy() if nt else np.zeros(0, np.int32)
             words = self._words(r, page, k) if self.config.rec_processor_config.return_word_box else None
-            rec.append(RecProcessorSingleResult(lib.rt_results_rec_text(r, page, k).decode("utf-8"), float(rs[k]), toks, words))
+            cands, cols = self._candidates(r, page, k, nt)
+            rec.append(RecProcessorSingleResult(lib.rt_results_rec_text(r, page, k).decode("utf-8"), float(rs[k]), toks, words,
+                                                cands, cols))
         return RettoWorkerResult(det, cls, rec)
+
+    def _dictionary(self) -> List[str]:
+        if getattr(self, "_dict", None) is None:
+            src = self.config.rec_processor_config.character_source
+            data = src.blob if src.path is None else open(src.path, "rb").read()
+            self._dict = parse_dictionary(data)
+        return self._dict
+
+    def _candidates(self, r, page: int, line: int, n_tokens: int):
+        if not self.config.rec_processor_config.return_candidates:
+            return None, None
+        cp = C.POINTER(_lib.Candidate)(); colp = C.POINTER(C.c_int32)()
+        K = self._hd.lib.rt_results_rec_candidates(r, page, line, C.byref(cp), C.byref(colp))
+        return _candidate_lists(cp, K, n_tokens, self._dictionary()), \
+            (np.ctypeslib.as_array(colp, (n_tokens,)).copy() if n_tokens else np.zeros(0, np.int32))
 
     def _words(self, r, page: int, line: int) -> List[RecWord]:
         lib = self._hd.lib

@@ -36,7 +36,7 @@ class Config(C.Structure):
         ("cls_image_shape", C.c_int32 * 3), ("cls_batch_num", C.c_int32), ("cls_thresh", C.c_float),
         ("rec_image_shape", C.c_int32 * 3), ("rec_batch_num", C.c_int32),
         ("max_boxes_per_page", C.c_int32), ("det_sub_batch", C.c_int32), ("lanes", C.c_int32), ("dtype", C.c_int32),
-        ("det_score_mode", C.c_int32), ("rec_return_word_box", C.c_int32),
+        ("det_score_mode", C.c_int32), ("rec_return_candidates", C.c_int32), ("rec_return_word_box", C.c_int32),
     ]
 
 
@@ -44,6 +44,12 @@ class Word(C.Structure):   # rt_word
     _fields_ = [("quad", C.c_float * 8), ("first_token", C.c_int32), ("n_tokens", C.c_int32), ("first_col", C.c_int32),
                 ("last_col", C.c_int32), ("kind", C.c_int32)]
 
+
+class Candidate(C.Structure):   # rt_candidate
+    _fields_ = [("id", C.c_int32), ("prob", C.c_float)]
+
+
+MAX_CANDIDATES = 8   # RT_MAX_CANDIDATES
 
 # every symbol include/retto_hip.h declares (tests check that each is exported)
 EXPORTS = [
@@ -54,7 +60,8 @@ EXPORTS = [
     "rt_ctc_decode",
     "rt_run_batch", "rt_run_batch_stream", "rt_submit_batch", "rt_wait_batch", "rt_host_cpu_budget", "rt_results_free", "rt_results_pages", "rt_results_count", "rt_results_boxes",
     "rt_results_det_scores", "rt_results_cls_labels", "rt_results_cls_scores", "rt_results_rec_scores",
-    "rt_results_rec_tokens", "rt_results_rec_text", "rt_results_rec_words", "rt_results_rec_word_text", "rt_debug_word_boxes", "rt_results_det_checksum", "rt_results_json",
+    "rt_results_rec_tokens", "rt_results_rec_text", "rt_results_rec_words", "rt_results_rec_word_text", "rt_debug_word_boxes", "rt_results_rec_candidates",
+    "rt_debug_ctc_candidates", "rt_debug_ctc_candidates_host", "rt_results_det_checksum", "rt_results_json",
     "rt_device_malloc", "rt_device_free", "rt_memcpy_h2d", "rt_memcpy_d2h", "rt_synchronize",
     "rt_set_lanes", "rt_profile_enable", "rt_profile_get",
     "rt_onnx_to_rtwb", "rt_buffer_free", "rt_model_manifest", "rt_decode_image", "rt_run_encoded_batch",
@@ -173,5 +180,10 @@ def load():
                                   C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.rt_debug_attention.argtypes = [C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+    lib.rt_results_rec_candidates.argtypes = [C.c_void_p, C.c_int, C.c_int, P(P(Candidate)), P(P(C.c_int32))]
+    lib.rt_debug_ctc_candidates.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                            C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.rt_debug_ctc_candidates_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                                 C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
     _lib = lib
     return lib

@@ -35,6 +35,9 @@ def build_parser() -> argparse.ArgumentParser:
                     help="DetProcessorConfig.score_mode: box score over the min-area rect (Fast) or the contour's own polygon (Slow)")
     ap.add_argument("--rec-return-word-box", action="store_true",
                     help="RecProcessorConfig.return_word_box: per-word boxes; each --json line gains a \"words\" array (per line)")
+    ap.add_argument("--rec-candidates", type=int, default=0, metavar="K",
+                    help="RecProcessorConfig.return_candidates: K = 1..8 candidates per token; each --json line gains "
+                         "\"candidates\" and \"token_cols\" arrays (per line)")
     return ap
 
 
@@ -62,6 +65,7 @@ def main(argv=None) -> int:
         cfg.rec_processor_config.character_source = S.Path(a.rec_keys_path)
     cfg.det_processor_config.score_mode = a.det_score_mode
     cfg.rec_processor_config.return_word_box = a.rec_return_word_box
+    cfg.rec_processor_config.return_candidates = a.rec_candidates
     session = retto_amd.RettoSession(cfg)
     files = walk_files(a.images)
     log.info("Found %d files, processing...", len(files))
@@ -88,6 +92,10 @@ def main(argv=None) -> int:
                     rec["words"] = [[{"text": w.text, "kind": w.kind, "boxes": {"inner": [{"x": p.x, "y": p.y} for p in w.box.inner]},
                                       "first_token": w.first_token, "n_tokens": w.n_tokens, "first_col": w.first_col,
                                       "last_col": w.last_col} for w in t.words] for t in r.rec_result]
+                if a.rec_candidates:   # per line: one list of K {id, text, prob} per token, and the tokens' time steps
+                    rec["candidates"] = [[[{"id": i, "text": s, "prob": p} for i, s, p in tok] for tok in t.candidates]
+                                         for t in r.rec_result]
+                    rec["token_cols"] = [[int(c) for c in t.token_cols] for t in r.rec_result]
                 out.write(json.dumps(rec, ensure_ascii=False) + "\n")
     dur = time.perf_counter() - start
     if out:

@@ -101,6 +101,7 @@ void rt_config_default(rt_config* c) {
   c->max_boxes_per_page = 0; c->det_sub_batch = 0; c->lanes = 0; c->dtype = RT_DTYPE_F32;
   c->det_score_mode = 0;
   c->rec_return_word_box = 0;
+  c->rec_return_candidates = 0;
 }
 
 int rt_create(const rt_config* cfg, rt_session** out) {
@@ -119,6 +120,8 @@ int rt_create(const rt_config* cfg, rt_session** out) {
   RT_REQUIRE(cfg->det_score_mode == 0 || cfg->det_score_mode == 1, (rt_session*)nullptr, "det_score_mode must be 0 (Fast) or 1 (Slow)");
   RT_REQUIRE(cfg->rec_return_word_box == 0 || cfg->rec_return_word_box == 1, (rt_session*)nullptr,
              "rec_return_word_box must be 0 (off) or 1 (on)");
+  RT_REQUIRE(cfg->rec_return_candidates >= 0 && cfg->rec_return_candidates <= RT_MAX_CANDIDATES, (rt_session*)nullptr,
+             "rec_return_candidates must be in [0, 8] (0 = off, K = 1 .. RT_MAX_CANDIDATES)");
   capture_variant_defaults();
   return guarded(nullptr, [&] { *out = rt_session_create(cfg); });
 }
@@ -496,6 +499,58 @@ int rt_debug_word_boxes(const void* dict, size_t dict_len, const int32_t* tokens
     return RT_OK;
   } catch (const RtError& e) {
     return e.code;
+  } catch (const std::exception&) {
+    return RT_ERR_BACKEND;
+  }
+}
+static_assert(sizeof(rt_candidate) == sizeof(cc::Cand) && offsetof(rt_candidate, prob) == offsetof(cc::Cand, prob) &&
+                  RT_MAX_CANDIDATES == cc::MAX_K, "rt_candidate and cc::Cand must share one layout");
+int rt_results_rec_candidates(const rt_results* r, int page, int line, const rt_candidate** cands, const int32_t** cols) {
+  auto* p = RT_PAGE(r, page);
+  if (!p || p->cand_k <= 0 || line < 0 || (size_t)line + 1 >= p->cand_off.size()) return 0;
+  const size_t o = p->cand_off[(size_t)line];
+  if (cands) *cands = reinterpret_cast<const rt_candidate*>(p->cands.data()) + o * (size_t)p->cand_k;
+  if (cols) *cols = p->cand_cols.data() + o;
+  return p->cand_k;
+}
+// what both rt_debug_ctc_candidates forms require of their arguments; *rows_out = the lines' time steps
+static bool cand_args_ok(const float* z5, const float* W, int N, const int32_t* idx, const float* prob, const int32_t* tokens_per_line,
+                         int n_lines, int K, const rt_candidate* cands_out, const int32_t* cols_out, const int32_t* n_tokens_out,
+                         long long* rows_out) {
+  if (!idx || !prob || !tokens_per_line || !cands_out || !cols_out || !n_tokens_out) return false;
+  if (n_lines <= 0 || K < 1 || K > RT_MAX_CANDIDATES || N <= 0 || (K > 1 && (!z5 || !W))) return false;
+  long long rows = 0;
+  for (int i = 0; i < n_lines; i++) {
+    if (tokens_per_line[i] < 0) return false;
+    rows += tokens_per_line[i];
+  }
+  if (rows >= (1ll << 30)) return false;
+  for (long long r = 0; r < rows; r++)
+    if (idx[r] < 0 || idx[r] >= N) return false;
+  *rows_out = rows;
+  return true;
+}
+int rt_debug_ctc_candidates_host(const float* z5, const float* W, const float* bias, int N, const int32_t* idx, const float* prob,
+                                 const int32_t* tokens_per_line, int n_lines, int K, rt_candidate* cands_out, int32_t* cols_out,
+                                 int32_t* n_tokens_out) {
+  long long rows = 0;
+  if (!cand_args_ok(z5, W, N, idx, prob, tokens_per_line, n_lines, K, cands_out, cols_out, n_tokens_out, &rows)) return RT_ERR_INVALID;
+  try {
+    const int D = 120;
+    std::vector<float> logits((size_t)N);
+    cc::Cand* out = reinterpret_cast<cc::Cand*>(cands_out);
+    long long o = 0;
+    for (int i = 0; i < n_lines; i++) {
+      const int T = tokens_per_line[i];
+      const int n = cc::line_kept(idx + o, prob + o, T, K, cols_out + o, out + o * K);
+      n_tokens_out[i] = n;
+      for (int j = 0; K > 1 && j < n; j++) {
+        cc::Cand* c = out + (o + j) * K;
+        cc::row_candidates(z5 + (size_t)(o + cols_out[o + j]) * D, D, W, bias, N, c[0].id, K, c, logits.data());
+      }
+      o += T;
+    }
+    return RT_OK;
   } catch (const std::exception&) {
     return RT_ERR_BACKEND;
   }
@@ -883,6 +938,50 @@ RT_API int rt_debug_attention(rt_session* s, const float* qkv, long long rows, c
     nn::attention(s->st, dq, dg, n_lines, maxT, heads, hd, dout);
     RT_HIP_CHECK(hipStreamSynchronize(s->st));
     RT_HIP_CHECK(hipMemcpy(out, dout, (size_t)rows * C * sizeof(float), hipMemcpyDeviceToHost));
+  });
+}
+
+// rt_config.rec_return_candidates' device path (rt_session::ctc_candidates, what rec_groups runs per group) on host arrays: the
+// lines' geometry as the token level gives it, pp::ctc_decode for the token counts, an FC packed by pack_linear.
+RT_API int rt_debug_ctc_candidates(rt_session* s, const float* z5, const float* W, const float* bias, int N, const int32_t* idx,
+                                   const float* prob, const int32_t* tokens_per_line, int n_lines, int K, int chunk_rows,
+                                   rt_candidate* cands_out, int32_t* cols_out, int32_t* n_tokens_out) {
+  long long rows = 0;
+  RT_REQUIRE(s, s, "rt_debug_ctc_candidates: null session");
+  RT_REQUIRE(cand_args_ok(z5, W, N, idx, prob, tokens_per_line, n_lines, K, cands_out, cols_out, n_tokens_out, &rows) && chunk_rows >= 0,
+             s, "rt_debug_ctc_candidates: bad argument");
+  return guarded(s, [&] {
+    s->begin_call();
+    const size_t nr = (size_t)std::max<long long>(rows, 1);
+    WeightStore ws;
+    SvtrCore core;
+    core.classes = N;
+    if (K > 1) core.fc = pack_linear(ws, W, bias, core.D, N);
+    std::vector<ImgGeom> geom;
+    long long off = 0;
+    for (int i = 0; i < n_lines; i++) { geom.push_back(ImgGeom{off, 1, tokens_per_line[i], 0}); off += tokens_per_line[i]; }
+    DevBufs bufs;
+    float* dz = nullptr;
+    if (K > 1) {   // (the features sit inside a larger allocation, as z5 does inside the scratch arena)
+      dz = bufs.alloc<float>((nr + 256) * core.D);
+      RT_HIP_CHECK(hipMemset(dz, 0, (nr + 256) * core.D * sizeof(float)));
+      RT_HIP_CHECK(hipMemcpy(dz, z5, (size_t)rows * core.D * sizeof(float), hipMemcpyHostToDevice));
+    }
+    int* didx = bufs.alloc<int>(nr); float* dprob = bufs.alloc<float>(nr); int* dtok = bufs.alloc<int>(nr);
+    int* dntok = bufs.alloc<int>(n_lines); float* dscore = bufs.alloc<float>(n_lines);
+    ImgGeom* dg = bufs.alloc<ImgGeom>(n_lines);
+    int* dcols = bufs.alloc<int>(nr); cc::Cand* dcands = bufs.alloc<cc::Cand>(nr * K);
+    RT_HIP_CHECK(hipMemcpy(didx, idx, (size_t)rows * sizeof(int), hipMemcpyHostToDevice));
+    RT_HIP_CHECK(hipMemcpy(dprob, prob, (size_t)rows * sizeof(float), hipMemcpyHostToDevice));
+    RT_HIP_CHECK(hipMemcpy(dg, geom.data(), geom.size() * sizeof(ImgGeom), hipMemcpyHostToDevice));
+    RT_HIP_CHECK(hipMemcpy(dcols, cols_out, (size_t)rows * sizeof(int), hipMemcpyHostToDevice));
+    RT_HIP_CHECK(hipMemcpy(dcands, cands_out, (size_t)rows * K * sizeof(cc::Cand), hipMemcpyHostToDevice));
+    pp::ctc_decode(s->st, didx, dprob, dg, n_lines, dtok, dntok, dscore);
+    s->ctc_candidates(core, dz, didx, dprob, dg, dntok, n_lines, rows, K, chunk_rows, dcols, dcands);
+    RT_HIP_CHECK(hipStreamSynchronize(s->st));
+    RT_HIP_CHECK(hipMemcpy(n_tokens_out, dntok, (size_t)n_lines * sizeof(int), hipMemcpyDeviceToHost));
+    RT_HIP_CHECK(hipMemcpy(cols_out, dcols, (size_t)rows * sizeof(int), hipMemcpyDeviceToHost));
+    RT_HIP_CHECK(hipMemcpy(cands_out, dcands, (size_t)rows * K * sizeof(cc::Cand), hipMemcpyDeviceToHost));
   });
 }
 

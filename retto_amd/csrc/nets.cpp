@@ -562,7 +562,7 @@ int RecNet::tokens_for_width(int w) {
   return wc >= 2 ? (wc - 2) / 2 + 1 : 0;
 }
 
-float* RecNet::run(RunCtx& c, const float* x, Level& L0, Level& Lt, int* idx_out, float* prob_out) {
+float* RecNet::run(RunCtx& c, const float* x, Level& L0, Level& Lt, int* idx_out, float* prob_out, const float** z5_out) {
   for (auto& g : L0.h) if (g.H != 48 || g.W < 8) throw RtError(3, "rec input must be 48 high and at least 8 wide");
   Level La = down_level(L0, 2, 2);
   std::vector<Level> lv; lv.reserve(16);
@@ -613,6 +613,7 @@ float* RecNet::run(RunCtx& c, const float* x, Level& L0, Level& Lt, int* idx_out
   float* z5 = c.arena->alloc<float>((size_t)rows * D);
   { ProfScope ps(c.prof, c.st, "gemm_neck");
     nn::gemm(c.st, z4, 60, rows, conv1x1_.K, conv1x1_.w, D, conv1x1_.Npad, z5, D, 0, make_epi(conv1x1_, ACT_SWISH)); }
+  if (z5_out) *z5_out = z5;
   return core_.head(c, z5, rows, idx_out, prob_out);
 }
 
@@ -686,6 +687,10 @@ float* SvtrCore::head(RunCtx& c, const float* z5, long long rows, int* idx_out, 
   { ProfScope ps(c.prof, c.st, "gemm_ctc_fc", shape_str(rows, fc.K, classes, 0));
     nn::gemm(c.st, z5, D, rows, fc.K, fc.w, classes, fc.Npad, logits, ld, 0, make_epi(fc, ACT_NONE)); }
   return logits;
+}
+void SvtrCore::logits_rows(RunCtx& c, const float* z_rows, long long m, float* out) const {
+  ProfScope ps(c.prof, c.st, "gemm_cand_fc", shape_str(m, fc.K, classes, 0));
+  nn::gemm(c.st, z_rows, D, m, fc.K, fc.w, classes, fc.Npad, out, round_up(classes, 4), 0, make_epi(fc, ACT_NONE));
 }
 
 // ---------------------------------------------------------------------------

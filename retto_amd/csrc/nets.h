@@ -98,6 +98,7 @@ class ClsModel {
   virtual float* run(RunCtx& c, const float* x, Level& L0) = 0;
   virtual const char* dtype() const = 0;
 };
+struct SvtrCore;
 class RecModel {
  public:
   virtual ~RecModel() {}
@@ -106,7 +107,10 @@ class RecModel {
   // x: f32 NHWC pitch-4 (R,G,B,0), level L0 = lines of height 48; Lt (out) is the token level (H=1, W=T_i).
   // Returns the logits [Lt.total, logits_ld()], or -- with idx_out / prob_out (Lt.total each) -- runs the fused
   // CTC head (argmax + softmax probability of the argmax per time step, no logits in HBM) and returns nullptr.
-  virtual float* run(RunCtx& c, const float* x, Level& L0, Level& Lt, int* idx_out = nullptr, float* prob_out = nullptr) = 0;
+  // z5_out (rec_return_candidates): receives the head's input features [Lt.total, SvtrCore::D] (arena memory of this pass).
+  virtual float* run(RunCtx& c, const float* x, Level& L0, Level& Lt, int* idx_out = nullptr, float* prob_out = nullptr,
+                     const float** z5_out = nullptr) = 0;
+  virtual const SvtrCore& core() const = 0;   // the head every variant shares (its CTC FC recomputes logits of chosen rows)
   virtual const char* arch() const = 0;
   virtual const char* dtype() const = 0;
   virtual size_t weight_bytes() const = 0;
@@ -124,6 +128,9 @@ struct SvtrCore {
   float* mixer(RunCtx& c, float* z, const Level& Lt) const;
   // z5 [rows, D] -> fused argmax (idx_out / prob_out) and nullptr, or the logits [rows, round_up(classes, 4)]
   float* head(RunCtx& c, const float* z5, long long rows, int* idx_out, float* prob_out) const;
+  // The CTC FC alone over m chosen rows (rec_return_candidates): z_rows [m, D], followed by the zero slack rows every nn::gemm
+  // input has, -> out [m, round_up(classes, 4)].  The non-fused GEMM of head(), under a profile family of its own.
+  void logits_rows(RunCtx& c, const float* z_rows, long long m, float* out) const;
 };
 
 class DetNet : public DetModel {
@@ -156,7 +163,9 @@ class RecNet : public RecModel {
  public:
   explicit RecNet(const Blob& b);
   int classes() const override { return core_.classes; }
-  float* run(RunCtx& c, const float* x, Level& L0, Level& Lt, int* idx_out = nullptr, float* prob_out = nullptr) override;
+  float* run(RunCtx& c, const float* x, Level& L0, Level& Lt, int* idx_out = nullptr, float* prob_out = nullptr,
+             const float** z5_out = nullptr) override;
+  const SvtrCore& core() const override { return core_; }
   const char* arch() const override { return "mobile"; }
   const char* dtype() const override { return "f32"; }
   size_t weight_bytes() const override { return ws_.bytes(); }

@@ -417,7 +417,8 @@ void RecNeck16::load(WeightStore& ws, const Blob& b, const std::string& prefix, 
   core.load(ws, b, prefix);
 }
 
-float* RecNeck16::run(RunCtx& c, H16 t, const Level& Lb, Level& Lt, const Level& LtFlat, int* idx_out, float* prob_out) const {
+float* RecNeck16::run(RunCtx& c, H16 t, const Level& Lb, Level& Lt, const Level& LtFlat, int* idx_out, float* prob_out,
+                      const float** z5_out) const {
   const long long rows = Lt.total;
   const int D = 120;
   H16 cat; cat.C = 2 * C; cat.ld = 2 * C;
@@ -444,6 +445,7 @@ float* RecNeck16::run(RunCtx& c, H16 t, const Level& Lb, Level& Lt, const Level&
   float* z5f = c.arena->alloc<float>((size_t)std::max<long long>(rows, 1) * D);
   { ProfScope ps(c.prof, c.st, "f16_to_f32");
     nh::h_to_f32(c.st, z5.p, z5.ld, rows, D, z5f, D, 0); }
+  if (z5_out) *z5_out = z5f;
   return core.head(c, z5f, rows, idx_out, prob_out);
 }
 
@@ -456,7 +458,7 @@ RecNetH::RecNetH(const Blob& b) {
   neck_.load(ws_, b, "rec", 480);
 }
 
-float* RecNetH::run(RunCtx& c, const float* x4, Level& L0, Level& Lt, int* idx_out, float* prob_out) {
+float* RecNetH::run(RunCtx& c, const float* x4, Level& L0, Level& Lt, int* idx_out, float* prob_out, const float** z5_out) {
   for (auto& g : L0.h) if (g.H != 48 || g.W < 8) throw RtError(3, "rec input must be 48 high and at least 8 wide");
   std::vector<Level> lv; lv.reserve(16);
   lv.push_back(down_level(L0, 2, 2));
@@ -473,7 +475,7 @@ float* RecNetH::run(RunCtx& c, const float* x4, Level& L0, Level& Lt, int* idx_o
   H16 t = alloc16(c, lv[0], 16);
   conv_sp16(c, stem_, x, L0, lv[0], 2, 2, t, 0, epi16(stem_, ACT_NONE));
   for (size_t i = 0; i < blocks_.size(); i++) t = run_lc16(c, blocks_[i], t, lv[i], lv[i + 1], fl[i + 1]);
-  return neck_.run(c, t, lv.back(), Lt, LtF, idx_out, prob_out);
+  return neck_.run(c, t, lv.back(), Lt, LtF, idx_out, prob_out, z5_out);
 }
 
 // ---------------------------------------------------------------------------
@@ -743,7 +745,7 @@ RecServerH::RecServerH(const Blob& b) {
   neck_.load(ws_, b, "srec", 1024);
 }
 
-float* RecServerH::run(RunCtx& c, const float* x4, Level& L0, Level& Lt, int* idx_out, float* prob_out) {
+float* RecServerH::run(RunCtx& c, const float* x4, Level& L0, Level& Lt, int* idx_out, float* prob_out, const float** z5_out) {
   for (auto& g : L0.h) if (g.H != 48 || g.W < 8) throw RtError(3, "rec input must be 48 high and at least 8 wide");
   Level Ls = down_level(L0, 2, 2);
   Level S1 = down_level(Ls, 2, 1), S2 = down_level(S1, 1, 2), S3 = down_level(S2, 2, 1), S4 = down_level(S3, 2, 1);
@@ -752,7 +754,7 @@ float* RecServerH::run(RunCtx& c, const float* x4, Level& L0, Level& Lt, int* id
   upload_levels(c, {&L0, &Ls, &S1, &S2, &S3, &S4, &Lt, &F1, &F2, &F3, &F4, &LtF});
   H16 x = input_f32(c, x4, L0);
   HgRun bb = run_hgnet(c, bb_, x, L0, Ls, nullptr, {&S1, &S2, &S3, &S4}, {&F1, &F2, &F3, &F4});
-  return neck_.run(c, bb.feat[3], S4, Lt, LtF, idx_out, prob_out);
+  return neck_.run(c, bb.feat[3], S4, Lt, LtF, idx_out, prob_out, z5_out);
 }
 
 }  // namespace rt

@@ -65,14 +65,17 @@ struct RecNeck16 {
   int C = 0;  // backbone channels (480 mobile, 1024 server)
   void load(WeightStore& ws, const Blob& b, const std::string& prefix, int C);
   // t: backbone output at level Lb (H = 3 rows); pools to Lt and runs neck + head
-  float* run(RunCtx& c, H16 t, const Level& Lb, Level& Lt, const Level& LtFlat, int* idx_out, float* prob_out) const;
+  float* run(RunCtx& c, H16 t, const Level& Lb, Level& Lt, const Level& LtFlat, int* idx_out, float* prob_out,
+             const float** z5_out = nullptr) const;
 };
 
 class RecNetH : public RecModel {  // PP-OCRv4 mobile rec, fp16
  public:
   explicit RecNetH(const Blob& b);
   int classes() const override { return neck_.core.classes; }
-  float* run(RunCtx& c, const float* x, Level& L0, Level& Lt, int* idx_out = nullptr, float* prob_out = nullptr) override;
+  float* run(RunCtx& c, const float* x, Level& L0, Level& Lt, int* idx_out = nullptr, float* prob_out = nullptr,
+             const float** z5_out = nullptr) override;
+  const SvtrCore& core() const override { return neck_.core; }
   const char* arch() const override { return "mobile"; }
   const char* dtype() const override { return "f16"; }
   size_t weight_bytes() const override { return ws_.bytes(); }
@@ -115,7 +118,9 @@ class RecServerH : public RecModel {  // PP-OCRv4 server rec: PPHGNet_small + SV
  public:
   explicit RecServerH(const Blob& b);
   int classes() const override { return neck_.core.classes; }
-  float* run(RunCtx& c, const float* x, Level& L0, Level& Lt, int* idx_out = nullptr, float* prob_out = nullptr) override;
+  float* run(RunCtx& c, const float* x, Level& L0, Level& Lt, int* idx_out = nullptr, float* prob_out = nullptr,
+             const float** z5_out = nullptr) override;
+  const SvtrCore& core() const override { return neck_.core; }
   const char* arch() const override { return "server"; }
   const char* dtype() const override { return "f16"; }
   size_t weight_bytes() const override { return ws_.bytes(); }

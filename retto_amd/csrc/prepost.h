@@ -5,6 +5,7 @@
 #include "nn.h"
 #include "common.h"
 #include "word_boxes.h"
+#include "ctc_candidates.h"
 
 namespace rt {
 namespace pp {
@@ -75,6 +76,19 @@ struct WordLineDesc { long long tok_off; wb::WordGeom g; };   // tok_off: first 
 void word_boxes(hipStream_t st, const int* idx, const int* tokens, const int* n_tokens, const int* label, const float* cls_score,
                 float cls_thresh, const uint8_t* raw_of_id, const WordLineDesc* lines, int n, int* cols, int* n_words,
                 wb::Word* words);
+
+// rt_config.rec_return_candidates (ctc_candidates.h) over the n lines of one rec group; lines[i] = {first row, 1, T_i}, what
+// ctc_decode got.  kept_rows: one wave64 per line writes, at the line's row offset, the kept time steps -> cols and rank 0
+// (idx, prob at the step) -> cands[slot * K]; with kept_row / kept_slot (K > 1) also the group's compact list of kept rows and
+// their token slots, in line order (line i starts at the sum of n_tokens[0..i), ctc_decode's counts), and the list's length ->
+// *n_kept.
+void ctc_kept_rows(hipStream_t st, const int* idx, const float* prob, const ImgGeom* lines, const int* n_tokens, int n, int K,
+                   int* cols, cc::Cand* cands, int* kept_row, int* kept_slot, int* n_kept);
+// rows kept_row[0..m) of z [.][ld] (ld a multiple of 4) -> out [m][ld]
+void ctc_gather_rows(hipStream_t st, const float* z, int ld, const int* kept_row, int m, float* out);
+// one wave64 per row i < m of logits [m][ld]: ranks 1..K-1 over the columns [0, classes) other than cands[kept_slot[i] * K].id
+// -> cands[kept_slot[i] * K + 1 ...]
+void ctc_topk(hipStream_t st, const float* logits, int ld, int classes, const int* kept_slot, int m, int K, cc::Cand* cands);
 
 // sum of a float buffer into per-block doubles (partials has ceil(n/65536) entries)
 int sum_blocks(long long n);

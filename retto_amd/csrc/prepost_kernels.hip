@@ -309,6 +309,122 @@ void word_boxes(hipStream_t st, const int* idx, const int* tokens, const int* n_
             n_words, words);
 }
 
+// rt_config.rec_return_candidates (ctc_candidates.h).  One wave64 per line, the ballot / popcount-prefix compaction of
+// k_word_boxes: kept token j of the line gets its time step and rank 0 at slot (line's first row + j).  With kept_row the line
+// also appends its kept rows to the group's compact list, from the sum of the earlier lines' token counts (line order, so the
+// list -- and with it every chunk of the logits recompute -- is the same on every run).
+__global__ __launch_bounds__(64) void k_ctc_kept_rows(const int* __restrict__ idx, const float* __restrict__ prob,
+                                                      const ImgGeom* __restrict__ lines, const int* __restrict__ n_tokens, int n,
+                                                      int K, int* __restrict__ cols, cc::Cand* __restrict__ cands,
+                                                      int* __restrict__ kept_row, int* __restrict__ kept_slot,
+                                                      int* __restrict__ n_kept) {
+  const int line = blockIdx.x, lane = threadIdx.x;
+  const ImgGeom g = lines[line];
+  const int T = g.H * g.W;
+  int base = 0;
+  if (kept_row) {
+    for (int i = lane; i < line; i += 64) base += n_tokens[i];
+    for (int o = 32; o >= 1; o >>= 1) base += __shfl_xor(base, o);
+  }
+  const int* id = idx + g.off;
+  int cnt = 0;
+  for (int t0 = 0; t0 < T; t0 += 64) {
+    const int t = t0 + lane;
+    bool sel = false; int v = 0;
+    if (t < T) { v = id[t]; sel = cc::kept(v, t > 0 ? id[t - 1] : 0, t == 0); }
+    const unsigned long long m = __ballot(sel);
+    if (sel) {
+      const int j = cnt + __popcll(m & ((1ull << lane) - 1ull));
+      const long long slot = g.off + j;
+      cols[slot] = t;
+      cands[slot * K] = cc::Cand{v, prob[g.off + t]};
+      if (kept_row) { kept_row[base + j] = (int)(g.off + t); kept_slot[base + j] = (int)slot; }
+    }
+    cnt += __popcll(m);
+  }
+  if (kept_row && line == n - 1 && lane == 0) *n_kept = base + cnt;
+}
+void ctc_kept_rows(hipStream_t st, const int* idx, const float* prob, const ImgGeom* lines, const int* n_tokens, int n, int K,
+                   int* cols, cc::Cand* cands, int* kept_row, int* kept_slot, int* n_kept) {
+  if (n <= 0) return;
+  RT_LAUNCH(k_ctc_kept_rows, dim3(n), dim3(64), 0, st, idx, prob, lines, n_tokens, n, K, cols, cands, kept_row, kept_slot, n_kept);
+}
+
+__global__ __launch_bounds__(256) void k_ctc_gather_rows(const float4* __restrict__ z, int ld4, const int* __restrict__ kept_row,
+                                                         int m, float4* __restrict__ out) {
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= (long long)m * ld4) return;
+  const int r = (int)(i / ld4), c = (int)(i % ld4);
+  out[i] = z[(long long)kept_row[r] * ld4 + c];
+}
+void ctc_gather_rows(hipStream_t st, const float* z, int ld, const int* kept_row, int m, float* out) {
+  if (m <= 0) return;
+  const long long n = (long long)m * (ld / 4);
+  RT_LAUNCH(k_ctc_gather_rows, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, reinterpret_cast<const float4*>(z), ld / 4,
+            kept_row, m, reinterpret_cast<float4*>(out));
+}
+
+// One wave64 per kept row.  Pass 1: the lanes stream the row's logits as float4 (coalesced; the row pitch is a multiple of 4 and
+// the GEMM's pad columns >= classes are masked out), each keeping its own best-first list of MAX_K - 1 classes other than the
+// greedy one, and the row maximum.  Pass 2: sum(exp(l - max)) over every class (the row is 26 KB: it comes back from L2).  Then
+// K - 1 rounds of a wave arg-max over the lanes' list heads (ties to the lower id); the lane that owned the winner pops it, lane r
+// keeps round r's winner and writes rank r + 1.
+__global__ __launch_bounds__(64) void k_ctc_topk(const float* __restrict__ logits, int ld, int classes,
+                                                 const int* __restrict__ kept_slot, int m, int K, cc::Cand* __restrict__ cands) {
+  constexpr int N = cc::MAX_K - 1;
+  const int row = blockIdx.x, lane = threadIdx.x;
+  if (row >= m) return;
+  cc::Cand* out = cands + (long long)kept_slot[row] * K;
+  const int tok = out[0].id;
+  const float4* x = reinterpret_cast<const float4*>(logits + (long long)row * ld);
+  const int nv = (classes + 3) / 4;
+  float L[N]; int I[N];
+#pragma unroll
+  for (int j = 0; j < N; j++) { L[j] = -INFINITY; I[j] = cc::EMPTY_ID; }
+  float mx = -INFINITY;
+  for (int v = lane; v < nv; v += 64) {
+    const float4 q = x[v];
+    const float e[4] = {q.x, q.y, q.z, q.w};
+#pragma unroll
+    for (int u = 0; u < 4; u++) {
+      const int c = 4 * v + u;
+      if (c < classes) {
+        mx = fmaxf(mx, e[u]);
+        if (c != tok) cc::list_insert(L, I, e[u], c);
+      }
+    }
+  }
+  for (int o = 32; o >= 1; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o));
+  float sum = 0.0f;
+  for (int v = lane; v < nv; v += 64) {
+    const float4 q = x[v];
+    const float e[4] = {q.x, q.y, q.z, q.w};
+#pragma unroll
+    for (int u = 0; u < 4; u++)
+      if (4 * v + u < classes) sum = sum + expf(e[u] - mx);
+  }
+  for (int o = 32; o >= 1; o >>= 1) sum = sum + __shfl_xor(sum, o);   // (a butterfly: every lane adds in the same order)
+  float ol = 0.0f; int oi = cc::EMPTY_ID;
+  for (int r = 0; r < K - 1; r++) {
+    float wl = L[0]; int wi = I[0];
+    for (int o = 32; o >= 1; o >>= 1) {
+      const float l2 = __shfl_xor(wl, o); const int i2 = __shfl_xor(wi, o);
+      if (cc::better(l2, i2, wl, wi)) { wl = l2; wi = i2; }
+    }
+    if (lane == r) { ol = wl; oi = wi; }
+    if (wi != cc::EMPTY_ID && I[0] == wi) {
+#pragma unroll
+      for (int j = 0; j + 1 < N; j++) { L[j] = L[j + 1]; I[j] = I[j + 1]; }
+      L[N - 1] = -INFINITY; I[N - 1] = cc::EMPTY_ID;
+    }
+  }
+  if (lane < K - 1) out[1 + lane] = oi == cc::EMPTY_ID ? cc::Cand{-1, 0.0f} : cc::Cand{oi, cc::prob_of(ol, mx, sum)};
+}
+void ctc_topk(hipStream_t st, const float* logits, int ld, int classes, const int* kept_slot, int m, int K, cc::Cand* cands) {
+  if (m <= 0 || K <= 1) return;
+  RT_LAUNCH(k_ctc_topk, dim3(m), dim3(64), 0, st, logits, ld, classes, kept_slot, m, K, cands);
+}
+
 // ===========================================================================
 // (round 5: 8192 values per block, 16-byte loads -- was 65536 per block, scalar: one 960 x 960 map ran on 15 workgroups for 77 us,
 //  6 % of the C2 call)

@@ -311,6 +311,36 @@ void rt_session::rec_forward_ragged(const float* nchw, int n, const int* widths,
   sync();
 }
 
+void rt_session::ctc_candidates(const SvtrCore& core, const float* z5, const int* idx, const float* prob, const ImgGeom* lines,
+                                const int* n_tokens, int n_lines, long long rows, int K, int chunk_rows, int* cols, cc::Cand* cands) {
+  if (n_lines <= 0 || rows <= 0) return;
+  int *kept_row = nullptr, *kept_slot = nullptr, *d_kept = nullptr;
+  if (K > 1) { kept_row = scratch.alloc<int>((size_t)rows); kept_slot = scratch.alloc<int>((size_t)rows); d_kept = scratch.alloc<int>(1); }
+  { ProfScope ps(&prof, st, "ctc_kept_rows");
+    pp::ctc_kept_rows(st, idx, prob, lines, n_tokens, n_lines, K, cols, cands, kept_row, kept_slot, d_kept); }
+  if (K <= 1) return;
+  // the only host wait of the option: the logits GEMMs are sized by the number of kept rows (about a tenth of the time steps)
+  int* h_kept = pinned.alloc<int>(1);
+  RT_HIP_CHECK(hipMemcpyAsync(h_kept, d_kept, sizeof(int), hipMemcpyDeviceToHost, st));
+  sync();
+  const int kept = (int)std::min<long long>(std::max(*h_kept, 0), rows);
+  if (kept == 0) return;
+  const int chunk = chunk_rows > 0 ? chunk_rows : cc::CAND_CHUNK, cap = std::min(chunk, kept), ld = round_up(core.classes, 4);
+  const size_t zc_n = ((size_t)cap + 256) * core.D;   // (zero rows past the chunk: a GEMM tile's loads stay inside the allocation)
+  float* zc = scratch.alloc<float>(zc_n);
+  float* logits = scratch.alloc<float>((size_t)cap * ld);
+  RT_HIP_CHECK(hipMemsetAsync(zc, 0, zc_n * sizeof(float), st));
+  RunCtx c = ctx(&scratch);
+  for (int c0 = 0; c0 < kept; c0 += chunk) {   // (stream order lets the chunks share zc and logits)
+    const int m = std::min(chunk, kept - c0);
+    { ProfScope ps(&prof, st, "ctc_gather_rows");
+      pp::ctc_gather_rows(st, z5, core.D, kept_row + c0, m, zc); }
+    core.logits_rows(c, zc, m, logits);
+    ProfScope ps(&prof, st, "ctc_topk");
+    pp::ctc_topk(st, logits, ld, core.classes, kept_slot + c0, m, K, cands);
+  }
+}
+
 // ---------------------------------------------------------------------------
 // stage functions
 // ---------------------------------------------------------------------------
@@ -585,6 +615,7 @@ struct Pipeline {
   std::vector<long long> tok_off;           // [NL + 1]: first token of every line
   int* d_tok = nullptr; int* h_tokens = nullptr;   // CTC tokens at tok_off
   int* d_wcount = nullptr; wb::Word* d_words = nullptr; int* h_wcount = nullptr; wb::Word* h_words = nullptr;   // rec_return_word_box
+  int* d_ccol = nullptr; cc::Cand* d_cands = nullptr; int* h_ccol = nullptr; cc::Cand* h_cands = nullptr;       // rec_return_candidates
 };
 
 // Launch groups: items [g0, end) where the group always takes its first item; with max_items > 0 it takes up to max_items items,
@@ -797,7 +828,12 @@ void rec_plan(rt_session& s, Pipeline& P) {
 void rec_groups(rt_session& s, Pipeline& P) {
   const int rh = s.cfg.rec_image_shape[1];
   const size_t ntok = (size_t)std::max<long long>(P.tok_off[P.NL], 1);
-  int* d_idx = s.arena.alloc<int>(ntok); float* d_prob = s.arena.alloc<float>(ntok); P.d_tok = s.arena.alloc<int>(ntok);
+  int* d_idx = s.arena.alloc<int>(ntok); float* d_prob = s.arena.alloc<float>(ntok);
+  // rec_return_candidates = K: per token slot its time step and K candidates, in one block behind the tokens ([ntok] tokens |
+  // [ntok] time steps | [ntok][K] candidates), so that the one copy that brings the tokens home brings them too
+  const int cand_k = s.cfg.rec_return_candidates;
+  P.d_tok = s.arena.alloc<int>(ntok * (cand_k > 0 ? 2 + 2 * (size_t)cand_k : 1));
+  if (cand_k > 0) { P.d_ccol = P.d_tok + ntok; P.d_cands = reinterpret_cast<cc::Cand*>(P.d_ccol + ntok); }
   // rec_return_word_box: word count per line, words at the lines' token offsets, the kept columns (k_word_boxes' scratch)
   int* d_wcol = nullptr;
   if (s.cfg.rec_return_word_box) {
@@ -826,8 +862,9 @@ void rec_groups(rt_session& s, Pipeline& P) {
     RunCtx c = s.ctx(&s.scratch);
     // (the token count per line only depends on the widths, so the offsets are known before the net runs)
     const long long t0 = P.tok_off[l0];
+    const float* z5 = nullptr;   // the head's input, for the candidates' logits
     { ProfOuter po(&s.prof, s.st, "net/rec");
-      s.rec->run(c, x, L0, Lt, d_idx + t0, d_prob + t0); }  // fused CTC head: logits never reach HBM
+      s.rec->run(c, x, L0, Lt, d_idx + t0, d_prob + t0, cand_k > 1 ? &z5 : nullptr); }  // fused CTC head: logits never reach HBM
     if (Lt.total != P.tok_off[l1] - t0) throw RtError(RT_ERR_SHAPE, "token count mismatch");
     { ProfScope ps(&s.prof, s.st, "ctc_decode");
       pp::ctc_decode(s.st, d_idx + t0, d_prob + t0, Lt.d, ln, P.d_tok + t0, P.d_meta.ntok + l0, P.d_meta.rscore + l0); }
@@ -850,6 +887,9 @@ void rec_groups(rt_session& s, Pipeline& P) {
       pp::word_boxes(s.st, d_idx + t0, P.d_tok + t0, P.d_meta.ntok + l0, P.d_meta.label + l0, P.d_meta.cscore + l0, s.cfg.cls_thresh,
                      s.d_word_raw, dw, ln, d_wcol + t0, P.d_wcount + l0, P.d_words + t0);
     }
+    if (cand_k > 0)   // (before the next group rewinds the scratch arena z5 lives in)
+      s.ctc_candidates(s.rec->core(), z5, d_idx + t0, d_prob + t0, Lt.d, P.d_meta.ntok + l0, ln, Lt.total, cand_k, 0,
+                       P.d_ccol + t0, P.d_cands + t0 * cand_k);
     l0 = l1;
   }
 }
@@ -858,9 +898,13 @@ void line_round_trip(rt_session& s, Pipeline& P) {
   const long long total_tok = P.tok_off[P.NL];
   // per-line results come back in two copies into pinned memory: the metadata block and the tokens
   P.h_meta.view(s.pinned.alloc<int>((size_t)4 * P.NLp), P.NLp);
-  P.h_tokens = s.pinned.alloc<int>((size_t)std::max<long long>(total_tok, 1));
+  // (with rec_return_candidates = K the tokens' block also holds their time steps and candidates: rec_groups)
+  const size_t nt = (size_t)std::max<long long>(total_tok, 1), K = (size_t)s.cfg.rec_return_candidates;
+  const size_t tok_words = nt * (K > 0 ? 2 + 2 * K : 1);
+  P.h_tokens = s.pinned.alloc<int>(tok_words);
+  if (K > 0) { P.h_ccol = P.h_tokens + nt; P.h_cands = reinterpret_cast<cc::Cand*>(P.h_ccol + nt); }
   RT_HIP_CHECK(hipMemcpyAsync(P.h_meta.label, P.d_meta.label, (size_t)4 * P.NLp * sizeof(int), hipMemcpyDeviceToHost, s.st));
-  if (total_tok > 0) RT_HIP_CHECK(hipMemcpyAsync(P.h_tokens, P.d_tok, (size_t)total_tok * 4, hipMemcpyDeviceToHost, s.st));
+  if (total_tok > 0) RT_HIP_CHECK(hipMemcpyAsync(P.h_tokens, P.d_tok, tok_words * 4, hipMemcpyDeviceToHost, s.st));
   if (s.cfg.rec_return_word_box) {   // (the words ride with the tokens: same round trip)
     P.h_wcount = s.pinned.alloc<int>(P.NLp);
     P.h_words = s.pinned.alloc<wb::Word>((size_t)std::max<long long>(total_tok, 1));
@@ -886,6 +930,18 @@ void results(const rt_session& s, const Pipeline& P, rt_results& res) {
       std::string& t = R.text[k];
       t.reserve(R.tokens[k].size() * 3);  // CJK dictionary entries are 3 UTF-8 bytes
       for (int id : R.tokens[k]) t += s.dict[(size_t)id];
+    }
+    if (const int K = s.cfg.rec_return_candidates) {
+      R.cand_k = K; R.cand_off.assign((size_t)nb + 1, 0);
+      for (int k = 0; k < nb; k++) R.cand_off[k + 1] = R.cand_off[k] + (uint32_t)m.ntok[p.first_line + k];
+      R.cand_cols.resize(R.cand_off[nb]); R.cands.resize((size_t)R.cand_off[nb] * K);
+      for (int k = 0; k < nb; k++) {
+        const long long o = P.tok_off[p.first_line + k];
+        const size_t n = (size_t)m.ntok[p.first_line + k];
+        if (n == 0) continue;
+        memcpy(&R.cand_cols[R.cand_off[k]], P.h_ccol + o, n * sizeof(int32_t));
+        memcpy(&R.cands[(size_t)R.cand_off[k] * K], P.h_cands + o * K, n * K * sizeof(cc::Cand));
+      }
     }
     if (s.cfg.rec_return_word_box) {   // word quads to original-image coordinates, word texts from the dictionary
       R.words.resize(nb); R.word_text.resize(nb);

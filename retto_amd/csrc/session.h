@@ -33,6 +33,12 @@ struct rt_results {
     // rt_config.rec_return_word_box: per line its words (quads in original-image coordinates) and their texts; empty when off
     std::vector<std::vector<rt::wb::Word>> words;
     std::vector<std::vector<std::string>> word_text;
+    // rt_config.rec_return_candidates = cand_k > 0 (ctc_candidates.h): the page's kept tokens in line order, line k's from
+    // cand_off[k] (one array per page, not per line: two allocations); their time steps and [cand_k] candidates each.  Empty when off
+    int cand_k = 0;
+    std::vector<uint32_t> cand_off;   // [lines + 1]
+    std::vector<int32_t> cand_cols;
+    std::vector<rt::cc::Cand> cands;
     std::string json[3];
   };
   std::vector<Page> pages;
@@ -148,6 +154,12 @@ struct rt_session {
                          float* out);
   void ctc_decode(const float* probs, int n, int t, int c, int32_t* idx, float* prob, int32_t* tokens,
                   int32_t* n_tokens, float* scores);
+  // rec_return_candidates = K over the n_lines lines of one rec group (ctc_candidates.h): lines / n_tokens as pp::ctc_decode got
+  // and left them, rows = the group's time steps, z5 [rows, core.D] the head's input (only read when K > 1).  Kept token j of a
+  // line at first row o gets cols[o + j] and cands[(o + j) * K ...].  K > 1 waits for the stream once (the kept-row count sizes
+  // the logits GEMMs) and recomputes in chunks of chunk_rows kept rows (0: cc::CAND_CHUNK); the workspace comes from `scratch`.
+  void ctc_candidates(const rt::SvtrCore& core, const float* z5, const int* idx, const float* prob, const rt::ImgGeom* lines,
+                      const int* n_tokens, int n_lines, long long rows, int K, int chunk_rows, int* cols, rt::cc::Cand* cands);
   // L2
   // persistent lane threads (index 0 = this session's own lane) and the number of submitted, not yet waited batches
   std::vector<std::unique_ptr<LaneWorker>> workers;
