@@ -429,6 +429,17 @@ RT_API int rt_debug_gemm(rt_session* s, const float* A, long long M, int K, int 
                          int act, int has_lab, float lab_a, float lab_c, const float* residual, int ld_res, const float* se_scale,
                          int ld_scale, const long long* img_rows, int n_img, int se_rows, int ldc, int coff, int variant, int ctc,
                          float* out, int* idx_out, float* prob_out, int* plan_out);
+/* One depthwise conv layer (K = 3 or 5, stride (sh, sw) in {1, 2}, "same" padding) on host arrays, for the numerics tests: n_img
+ * images of heights[i] x widths[i] pixels, consecutive in x [sum h w][Cp] (channels C .. Cp zero); w [K * K][Cp] (tap dy * K + dx),
+ * bias [Cp]; act / LAB as rt_debug_gemm.  form: 0 = the row-strip kernel, 1 = the column-sweep kernel where the layer has an
+ * instance (info_out[3] tells).  out [(sum ho wo + 64) * Cp], filled with RT_DEBUG_CANARY before the launch and returned whole.
+ * pooled != 0: the kernel also leaves the squeeze-excite partial sums, returned as they lie in memory in partial_out
+ * [n_img][chunks][Cp] (canary where nothing was written; partial_cap = floats available) and, in mean_out [n_img][Cp], as the
+ * channel means the squeeze-excite FC reads from them.  info_out[4] = {chunks, strip rows, strips per block, sweep ran}. */
+RT_API int rt_debug_dwconv(rt_session* s, const float* x, const int* heights, const int* widths, int n_img, int C, int Cp, int K,
+                           int sh, int sw, const float* w, const float* bias, int act, int has_lab, float lab_a, float lab_c,
+                           int pooled, int form, float* out, float* partial_out, long long partial_cap, float* mean_out,
+                           int* info_out);
 /* One nn::attention launch (head dim 15) on host arrays: qkv [rows][3 * heads * 15] (q | k | v, as the neck's qkv GEMM writes
  * it), lines of tokens[i] consecutive rows (sum = rows) -> out [rows][heads * 15], with the geometry SvtrCore::mixer passes. */
 RT_API int rt_debug_attention(rt_session* s, const float* qkv, long long rows, const int* tokens, int n_lines, int heads,

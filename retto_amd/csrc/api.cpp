@@ -911,6 +911,66 @@ RT_API int rt_debug_gemm(rt_session* s, const float* A, long long M, int K, int 
   });
 }
 
+// One nn::dwconv launch on host arrays (tests/test_gpu_dwconv_sweep.py): ragged images as the networks' levels lay them out, the
+// pooled partial sums in the layout dwconv_pool_layout gives run_lc, and the channel means k_se_fc makes of them (its walk over
+// the partials, without the FCs).  form 0 = k_dwconv_rows, 1 = k_dwconv_sweep where the layer has an instance.
+RT_API int rt_debug_dwconv(rt_session* s, const float* x, const int* heights, const int* widths, int n_img, int C, int Cp, int K,
+                           int sh, int sw, const float* w, const float* bias, int act, int has_lab, float lab_a, float lab_c,
+                           int pooled, int form, float* out, float* partial_out, long long partial_cap, float* mean_out,
+                           int* info_out) {
+  RT_REQUIRE(s && x && heights && widths && w && bias && out && info_out, s, "rt_debug_dwconv: null argument");
+  RT_REQUIRE(n_img > 0 && C > 0 && Cp >= C && Cp % 4 == 0 && (K == 3 || K == 5) && sh >= 1 && sh <= 2 && sw >= 1 && sw <= 2 &&
+                 act >= ACT_NONE && act <= ACT_SIGMOID && (form == 0 || form == 1),
+             s, "rt_debug_dwconv: bad shape");
+  RT_REQUIRE(!pooled || (partial_out && mean_out), s, "rt_debug_dwconv: pooled without buffers for the sums");
+  std::vector<ImgGeom> gi(n_img), go(n_img);
+  long long pin = 0, pout = 0;
+  int maxHo = 0, maxWo = 0;
+  for (int i = 0; i < n_img; i++) {
+    RT_REQUIRE(heights[i] > 0 && widths[i] > 0, s, "rt_debug_dwconv: empty image");
+    const int ho = (heights[i] + sh - 1) / sh, wo = (widths[i] + sw - 1) / sw;
+    gi[i] = ImgGeom{pin, heights[i], widths[i], 0}; go[i] = ImgGeom{pout, ho, wo, 0};
+    pin += (long long)heights[i] * widths[i]; pout += (long long)ho * wo;
+    maxHo = std::max(maxHo, ho); maxWo = std::max(maxWo, wo);
+  }
+  RT_REQUIRE(pin * Cp < (1ll << 30), s, "rt_debug_dwconv: too large");
+  int chunks = 0, strip_R = 0, spb = 0;
+  if (pooled) nn::dwconv_pool_layout(K, sh, sw, Cp, maxHo, maxWo, &chunks, &strip_R, &spb);
+  const size_t npart = (size_t)n_img * chunks * Cp;
+  RT_REQUIRE(!pooled || (long long)npart <= partial_cap, s, "rt_debug_dwconv: partial_out is too small");
+  return guarded(s, [&] {
+    RT_HIP_CHECK(hipSetDevice(s->device));
+    DevBufs bufs;
+    RestoreInt keep_form(nn::g_dw_sweep);
+    nn::g_dw_sweep = form ? 4 : 0;
+    const size_t nin = (size_t)pin * Cp, nout = (size_t)(pout + 64) * Cp;
+    float *dx = bufs.alloc<float>(nin), *dw = bufs.alloc<float>((size_t)K * K * Cp), *db = bufs.alloc<float>(Cp), *dy = bufs.alloc<float>(nout);
+    ImgGeom *dgi = bufs.alloc<ImgGeom>(n_img), *dgo = bufs.alloc<ImgGeom>(n_img);
+    float *dpart = nullptr, *dmean = nullptr;
+    RT_HIP_CHECK(hipMemcpy(dx, x, nin * sizeof(float), hipMemcpyHostToDevice));
+    RT_HIP_CHECK(hipMemcpy(dw, w, (size_t)K * K * Cp * sizeof(float), hipMemcpyHostToDevice));
+    RT_HIP_CHECK(hipMemcpy(db, bias, (size_t)Cp * sizeof(float), hipMemcpyHostToDevice));
+    RT_HIP_CHECK(hipMemcpy(dgi, gi.data(), n_img * sizeof(ImgGeom), hipMemcpyHostToDevice));
+    RT_HIP_CHECK(hipMemcpy(dgo, go.data(), n_img * sizeof(ImgGeom), hipMemcpyHostToDevice));
+    RT_HIP_CHECK(hipMemsetD32Async((hipDeviceptr_t)dy, (int)RT_DEBUG_CANARY, nout, s->st));
+    if (pooled) {
+      dpart = bufs.alloc<float>(npart); dmean = bufs.alloc<float>((size_t)n_img * Cp);
+      RT_HIP_CHECK(hipMemsetD32Async((hipDeviceptr_t)dpart, (int)RT_DEBUG_CANARY, npart, s->st));
+    }
+    nn::dwconv(s->st, K, sh, sw, dx, dgi, dgo, n_img, maxHo, maxWo, Cp, C, dw, db, act, has_lab, lab_a, lab_c, dy, dpart);
+    if (pooled)
+      nn::se_fc_from_dw(s->st, dpart, dgo, n_img, chunks, strip_R, spb, C, Cp, nullptr, nullptr, nullptr, nullptr, 0, 0.f, 0, dmean);
+    RT_HIP_CHECK(hipStreamSynchronize(s->st));
+    RT_HIP_CHECK(hipMemcpy(out, dy, nout * sizeof(float), hipMemcpyDeviceToHost));
+    if (pooled) {
+      RT_HIP_CHECK(hipMemcpy(partial_out, dpart, npart * sizeof(float), hipMemcpyDeviceToHost));
+      RT_HIP_CHECK(hipMemcpy(mean_out, dmean, (size_t)n_img * Cp * sizeof(float), hipMemcpyDeviceToHost));
+    }
+    info_out[0] = chunks; info_out[1] = strip_R; info_out[2] = spb;
+    info_out[3] = nn::dwconv_sweeps(K, sh, sw, Cp, maxHo, pooled != 0) ? 1 : 0;
+  });
+}
+
 // One nn::attention launch on host arrays: one ImgGeom{off, 1, T} per line, as SvtrCore::mixer passes its token level.
 RT_API int rt_debug_attention(rt_session* s, const float* qkv, long long rows, const int* tokens, int n_lines, int heads, float* out) {
   RT_REQUIRE(s && qkv && tokens && out, s, "rt_debug_attention: null argument");

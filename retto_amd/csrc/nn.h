@@ -44,6 +44,7 @@ void conv_sp(hipStream_t st, int KH, int KW, const float* x, int ldx, const ImgG
 void dwconv(hipStream_t st, int K, int sh, int sw, const float* x, const ImgGeom* gin, const ImgGeom* gout, int n_img,
             int maxHo, int maxWo, int Cp, int C, const float* Wd, const float* bias, int act, int has_lab,
             float lab_a, float lab_c, float* y, float* pool = nullptr);  // Cp = channel pitch (chan_pitch), C = real channels
+bool dwconv_sweeps(int K, int sh, int sw, int Cp, int maxHo, bool pool);   // the layer runs on k_dwconv_sweep (g_dw_sweep and its shape)
 // Fused squeeze-excite pooling: with `pool` (n_img * chunks * Cp floats, dwconv_pool_layout) the depthwise
 // kernel also writes per-block channel sums of its output; se_fc_from_dw turns them into the scales.
 void dwconv_pool_layout(int K, int sh, int sw, int Cp, int maxHo, int maxWo, int* chunks, int* strip_R, int* strips_per_block);

@@ -1223,8 +1223,8 @@ void conv_sp(hipStream_t st, int KH, int KW, const float* x, int ldx, const ImgG
 // instead of re-reading HBM.  Accumulation order per output: bias, then taps in (dy, dx) order.
 // 128 VGPRs (4 waves/SIMD): +15 % over 3 waves at C = 480.  Measured and rejected: lane groups
 // spanning whole pixels with all the weights in LDS (1.2-1.5x slower), one-row-ahead register
-// prefetch (hipcc hoists every load: spills).  On short maps (<= 24 rows, no pooling) the 5x5 stride-1 layers run on
-// k_dwconv_sweep below instead (every input row fetched once).
+// prefetch (hipcc hoists every load: spills).  The recognition net's short maps (<= 24 input rows, 64-channel slabs) run on
+// k_dwconv_sweep below instead (every input row fetched once): its 5x5 and 3x3 layers, strided and squeeze-excite ones included.
 template <int K, int R, int SH, int SW, int POOL, int LP = 8>  // LP lanes (16 bytes each) side by side on a pixel: 32- or 64-channel slabs
 __global__ __launch_bounds__(256, 4) void k_dwconv_rows(const float* __restrict__ x, const ImgGeom* __restrict__ gin,
                                                      const ImgGeom* __restrict__ gout, int Cp, int C,
@@ -1346,27 +1346,54 @@ __global__ __launch_bounds__(256, 4) void k_dwconv_rows(const float* __restrict_
 }
 
 // ---------------------------------------------------------------------------
-// Column-sweep depthwise conv (stride 1) for short, wide maps (the recognition net's 12- / 6-row stages): a thread owns a
-// PX-pixel x 4-channel column of the WHOLE image and streams the input rows top to bottom once, holding the K output rows
-// an input row feeds in a rotating window of accumulators (slot = output row % K, compile time: rows walked in groups of
-// K); an output row is stored and its slot restarted from the bias as soon as its last input row has gone through.
-// k_dwconv_rows re-reads the K - 1 rows that vertically adjacent strips share -- 20 row reads for 12 rows, 1.63x the output
-// bytes at the fabric (PMC), which is what bounds it (4.1 TB/s algorithmic = 6.7 TB/s of fetches).  Same accumulation
+// Column-sweep depthwise conv for short, wide maps (the recognition net's 24- / 12- / 6-row stages): a thread owns a
+// PX-pixel x 4-channel column of the WHOLE output image and streams the input rows top to bottom once, holding the output rows
+// an input row feeds in a rotating window of NS = ceil(K / SH) accumulator rows (slot = output row % NS, compile time: input rows
+// walked in groups of NS * SH); an output row is stored and its slot restarted from the bias as soon as its last input row has
+// gone through.  k_dwconv_rows re-reads the rows that vertically adjacent strips share -- 20 row reads for 12 rows, 1.63x the
+// output bytes at the fabric (PMC), which is what bounds it (4.1 TB/s algorithmic = 6.7 TB/s of fetches).  Same accumulation
 // order per output (bias, taps in (dy, dx) order): bit-identical.  Measured on the 1.23 M-pixel 256-channel maps (k_dwconv_rows
 // 0.621 ms): PX = 4 at 3 waves / SIMD 0.543 ms (4.64 TB/s), PX = 2 at 4 waves / SIMD 0.567; a first form that loaded the
 // columns one tap column ahead (dx-outer loop) ran 0.674 -- the eight loads of a row must be in flight together.
 // Round 6: buffer-descriptor addressing (below) 0.533 -> 0.519 ms; PX = 4 at 4 waves / SIMD still spills (300 bytes of scratch).
+// Strides (SH, SW) in {1, 2}: input row i feeds output row (i + P - dy) / SH through the tap rows dy of its parity; the input
+// columns of a row are (PX - 1) * SW + K loads as in k_dwconv_rows.
+// Measured on the recognition net's strided / squeeze-excite layers of the C3 workload (per launch: k_dwconv_rows -> this kernel;
+// fetched bytes at the fabric over the layer's input, PMC; profiles/README.md, "Rec depthwise ..."):
+//   5x5 (1,1) pooled, 480 ch, 6 rows      <5,16,4,3,1,1,3>  0.613 -> 0.498 ms, fetch 1.23 x -> 1.05 x, 4.76 TB/s of real traffic
+//   5x5 (2,1), 480 ch, 6 -> 3 rows        <5,16,4,4,2,1,0>  0.442 -> 0.352 ms, fetch 1.36 x -> 1.05 x, 5.20 TB/s
+//   5x5 (2,1) pooled, pitch 256, 12 -> 6  <5,16,4,3,2,1,3>  0.422 -> 0.389 ms, fetch 1.26 x -> 1.05 x, 5.03 TB/s
+//   3x3 (1,2), 128 ch, 12 rows            <3,16,4,4,1,2,0>  0.389 -> 0.391 ms, fetch 1.35 x -> 1.01 x, 4.88 TB/s: the time did not
+//     move -- the row kernel's 2.32 GB per launch went by at 5.95 TB/s, more than a copy reaches, so its re-read rows were served
+//     short of the HBM; the launch stays here for the 0.42 GB it no longer asks the fabric for.
+// Waves per SIMD: the pooled instances run at 3 -- at 4 (128 VGPRs) <5,..,2,1,3> spills one VGPR (8 bytes of scratch) and
+// <5,..,1,1,3> 160 bytes (its unpooled form: 300); at 3 they use 131 and 158 VGPRs.  The unpooled strided forms fit 4 (118 and
+// 117 VGPRs, no scratch), and 3 measured the same there: 0.352 against 0.353 ms per launch (one run of three at 0.317) on the 5x5,
+// 0.390 against 0.391 on the 3x3.
+// PR > 0: squeeze-excite pooling with the partial sums of k_dwconv_rows<K, PR, SH, SW, 1, LP> -- same layout, same values, bit for
+// bit.  There a thread sums its PR x 4 outputs in (row, pixel) order, the 4 strips of a wave are added by two xor shuffles
+// ((s0 + s1) + (s2 + s3)), the 4 waves in order, one partial per block of 16 column-major strips.  Here a thread meets the same
+// strips one after the other on its way down (same order of additions inside a strip) and leaves each strip's sum in LDS under
+// the strip's number; the 16 columns of a block hold exactly the strips of go.H / PR consecutive blocks of the row kernel,
+// which are then added in that kernel's order.
 // ---------------------------------------------------------------------------
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-template <int K, int LP, int PX, int WAVES>
+constexpr int DW_SWEEP_POOL_STRIPS = 4;   // strips of PR rows a pooled column may cross (LDS: 4 KB each)
+template <int K, int LP, int PX, int WAVES, int SH = 1, int SW = 1, int PR = 0>
 __global__ __launch_bounds__(256, WAVES) void k_dwconv_sweep(const float* __restrict__ x, const ImgGeom* __restrict__ gin,
                                                            const ImgGeom* __restrict__ gout, int Cp, int C,
                                                            const float* __restrict__ Wd, const float* __restrict__ bias, int act,
-                                                           int has_lab, float lab_a, float lab_c, float* __restrict__ y) {
-  constexpr int NV = PX - 1 + K, P = K / 2, SPB = 256 / LP;
+                                                           int has_lab, float lab_a, float lab_c, float* __restrict__ y,
+                                                           float* __restrict__ pool, int pool_pitch) {
+  constexpr int NV = (PX - 1) * SW + K, P = K / 2, SPB = 256 / LP;
+  constexpr int NS = (K + SH - 1) / SH, G = NS * SH;   // live output rows; input rows per turn of the window
+  constexpr int PRD = PR ? PR : 1;                     // (divisor that is never 0)
+  static_assert(PR == 0 || (PX == 4 && LP == 16), "pooled partials follow k_dwconv_rows<.., 16>: 4-pixel strips, 4 strips per wave");
   __shared__ __attribute__((aligned(16))) float wl[K * K * LP * 4];
+  __shared__ __attribute__((aligned(16))) float psl[PR ? DW_SWEEP_POOL_STRIPS * 256 * 4 : 4];   // [strip of the block][lane] x 4 channels
   const ImgGeom gi = gin[blockIdx.y], go = gout[blockIdx.y];
   const int strips_x = (go.W + PX - 1) / PX;
+  const int strips_y = PR ? (go.H + PRD - 1) / PRD : 1;   // <= DW_SWEEP_POOL_STRIPS: go.H <= maxHo, which dwconv() checks
   if ((int)blockIdx.x * SPB >= strips_x) return;
   const int cbase = blockIdx.z * LP * 4;
   const int tid = threadIdx.x;
@@ -1376,98 +1403,151 @@ __global__ __launch_bounds__(256, WAVES) void k_dwconv_sweep(const float* __rest
     if (cbase + cc * 4 < Cp) v = *reinterpret_cast<const f32x4*>(Wd + t * Cp + cbase + cc * 4);
     *reinterpret_cast<f32x4*>(wl + i * 4) = v;
   }
-  __syncthreads();
   const int c4 = tid % LP, ch = cbase + c4 * 4;
   const int strip = (int)blockIdx.x * SPB + tid / LP;
-  if (ch >= Cp || strip >= strips_x) return;
-  const int ox0 = strip * PX, H = gi.H;   // (stride 1: output and input maps have the same size)
-  const f32x4 b = *reinterpret_cast<const f32x4*>(bias + ch);
-  f32x4 acc[K][PX];
+  if (PR) {   // strips of columns past the image or of channel lanes past Cp count as zeros, as the idle threads of the row kernel do
+    for (int sy = 0; sy < strips_y; sy++) *reinterpret_cast<f32x4*>(psl + (((tid / LP) * strips_y + sy) * LP + c4) * 4) = f32x4{0.f, 0.f, 0.f, 0.f};
+  }
+  __syncthreads();
+  const bool active = ch < Cp && strip < strips_x;
+  if (!PR && !active) return;
+  if (active) {
+    const int ox0 = strip * PX, Hi = gi.H, Ho = go.H;
+    const f32x4 b = *reinterpret_cast<const f32x4*>(bias + ch);
+    f32x4 acc[NS][PX];
 #pragma unroll
-  for (int r = 0; r < K; r++)
+    for (int r = 0; r < NS; r++)
 #pragma unroll
-    for (int j = 0; j < PX; j++) acc[r][j] = b;
-  // Addresses: one buffer descriptor per ROW (its base is uniform: scalar registers; num_records = the row's bytes) + a 32-bit
-  // per-lane byte offset that does not depend on the row.  Columns right of the map are out of the descriptor's range -- loads
-  // return zeros, stores are dropped -- and columns left of it carry the out-of-range mark: no per-load test or branch is left.
-  // (The first form kept 64-bit per-lane pointers and laundered the running column pointer through an asm operand to keep hipcc
-  // from precomputing and spilling the 64-bit column addresses of every row; a pointer that went through an asm operand loses its
-  // address space, so every load was a flat_load -- counted in lgkmcnt as well, which made the waits for the taps' LDS reads wait
-  // for the row in flight.)
-  unsigned loff[NV];   // column ox0 - P + j, this lane's 4 channels
+      for (int j = 0; j < PX; j++) acc[r][j] = b;
+    // Addresses: one buffer descriptor per ROW (its base is uniform: scalar registers; num_records = the row's bytes) + a 32-bit
+    // per-lane byte offset that does not depend on the row.  Columns right of the map are out of the descriptor's range -- loads
+    // return zeros, stores are dropped -- and columns left of it carry the out-of-range mark: no per-load test or branch is left.
+    // (The first form kept 64-bit per-lane pointers and laundered the running column pointer through an asm operand to keep hipcc
+    // from precomputing and spilling the 64-bit column addresses of every row; a pointer that went through an asm operand loses its
+    // address space, so every load was a flat_load -- counted in lgkmcnt as well, which made the waits for the taps' LDS reads wait
+    // for the row in flight.)
+    unsigned loff[NV];   // input column ox0 * SW - P + j, this lane's 4 channels
 #pragma unroll
-  for (int j = 0; j < NV; j++) loff[j] = ox0 - P + j >= 0 ? (unsigned)((ox0 - P + j) * Cp + ch) * 4u : 0x80000000u;
-  auto uni_ptr = [](const float* p_) {   // (the image geometry comes from a load indexed by blockIdx: made scalar explicitly)
-    const unsigned long long v = (unsigned long long)p_;
-    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)v), hi = __builtin_amdgcn_readfirstlane((unsigned)(v >> 32));
-    return (float*)(((unsigned long long)hi << 32) | lo);
-  };
-  const float* xim = uni_ptr(x + gi.off * Cp);
-  float* yim = uni_ptr(y + go.off * Cp);
-  const unsigned row_bytes = (unsigned)__builtin_amdgcn_readfirstlane(gi.W * Cp * 4);
-  act_dispatch(act, has_lab, false, [&](auto at, auto lt, auto) {
-    constexpr int A = decltype(at)::value, L = decltype(lt)::value;
-    auto store_row = [&](int oy, f32x4 (&a)[PX]) __attribute__((always_inline)) {
-      const __amdgpu_buffer_rsrc_t yrs = __builtin_amdgcn_make_buffer_rsrc(yim + (long long)oy * go.W * Cp, 0, row_bytes, 0x00020000);
-#pragma unroll
-      for (int j = 0; j < PX; j++) {
-        f32x4 o;
-#pragma unroll
-        for (int e = 0; e < 4; e++) {
-          const float t = epi_val<A, L>(a[j][e], act, has_lab, lab_a, lab_c);
-          o[e] = (ch + e < C) ? t : 0.f;  // pitch padding (chan_pitch) holds zeros whatever the input padding held
-        }
-        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, o), yrs, loff[j + P], 0, 0);
-        a[j] = b;
-      }
+    for (int j = 0; j < NV; j++) loff[j] = ox0 * SW - P + j >= 0 ? (unsigned)((ox0 * SW - P + j) * Cp + ch) * 4u : 0x80000000u;
+    const unsigned ooff0 = (unsigned)(ox0 * Cp + ch) * 4u, opix = (unsigned)Cp * 4u;   // output pixel ox0 + j: ooff0 + j * opix
+    auto uni_ptr = [](const float* p_) {   // (the image geometry comes from a load indexed by blockIdx: made scalar explicitly)
+      const unsigned long long v = (unsigned long long)p_;
+      const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)v), hi = __builtin_amdgcn_readfirstlane((unsigned)(v >> 32));
+      return (float*)(((unsigned long long)hi << 32) | lo);
     };
-    for (int i0 = 0; i0 < H; i0 += K) {
+    const float* xim = uni_ptr(x + gi.off * Cp);
+    float* yim = uni_ptr(y + go.off * Cp);
+    const unsigned row_bytes = (unsigned)__builtin_amdgcn_readfirstlane(gi.W * Cp * 4);
+    const unsigned orow_bytes = (unsigned)__builtin_amdgcn_readfirstlane(go.W * Cp * 4);
+    f32x4 ps = {0.f, 0.f, 0.f, 0.f};   // pooling: the sum of the strip of PR output rows this thread is in
+    act_dispatch(act, has_lab, false, [&](auto at, auto lt, auto) {
+      constexpr int A = decltype(at)::value, L = decltype(lt)::value;
+      auto store_row = [&](int oy, f32x4 (&a)[PX]) __attribute__((always_inline)) {
+        const __amdgpu_buffer_rsrc_t yrs = __builtin_amdgcn_make_buffer_rsrc(yim + (long long)oy * go.W * Cp, 0, orow_bytes, 0x00020000);
 #pragma unroll
-      for (int u = 0; u < K; u++) {
-        const int i = i0 + u;   // input row; feeds output rows i - P .. i + P through tap rows dy = K - 1 .. 0
-        if (i < H) {
-          const __amdgpu_buffer_rsrc_t xrs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(xim) + (long long)i * gi.W * Cp, 0, row_bytes, 0x00020000);
-          f32x4 v[NV];
+        for (int j = 0; j < PX; j++) {
+          f32x4 o;
 #pragma unroll
-          for (int j = 0; j < NV; j++) v[j] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(xrs, loff[j], 0, 0));
+          for (int e = 0; e < 4; e++) {
+            const float t = epi_val<A, L>(a[j][e], act, has_lab, lab_a, lab_c);
+            o[e] = (ch + e < C) ? t : 0.f;  // pitch padding (chan_pitch) holds zeros whatever the input padding held
+          }
+          __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, o), yrs, SW == 1 ? loff[j + P] : ooff0 + j * opix, 0, 0);
+          if (PR && ox0 + j < go.W) ps += o;
+          a[j] = b;
+        }
+        if (PR) {
+          if (oy == Ho - 1 || (oy + 1) % PRD == 0) {   // last row of its strip
+            *reinterpret_cast<f32x4*>(psl + (((tid / LP) * strips_y + oy / PRD) * LP + c4) * 4) = ps;
+            ps = f32x4{0.f, 0.f, 0.f, 0.f};
+          }
+        }
+      };
+      for (int i0 = 0; i0 < Hi; i0 += G) {
 #pragma unroll
-          for (int dy = 0; dy < K; dy++) {
-            const int r = i + P - dy;                  // output row fed through tap row dy
-            const int slot = (u + P - dy + K) % K;     // == r mod K (i0 is a multiple of K): compile time
-            if (r >= 0 && r < H) {
+        for (int u = 0; u < G; u++) {
+          const int i = i0 + u;   // input row; feeds output rows (i + P - dy) / SH through the tap rows dy with i + P - dy a multiple of SH
+          if (i < Hi) {
+            const __amdgpu_buffer_rsrc_t xrs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(xim) + (long long)i * gi.W * Cp, 0, row_bytes, 0x00020000);
+            f32x4 v[NV];
 #pragma unroll
-              for (int dx = 0; dx < K; dx++) {
-                const f32x4 w = *reinterpret_cast<const f32x4*>(wl + ((dy * K + dx) * LP + c4) * 4);
+            for (int j = 0; j < NV; j++) v[j] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(xrs, loff[j], 0, 0));
 #pragma unroll
-                for (int j = 0; j < PX; j++)
+            for (int dy = 0; dy < K; dy++) {
+              if ((u + P - dy + G) % SH != 0) continue;      // (i0 is a multiple of SH)
+              const int r = i0 / SH + (u + P - dy + G) / SH - NS;   // output row fed through tap row dy
+              const int slot = ((u + P - dy + G) / SH) % NS;        // == r mod NS (i0 / SH is a multiple of NS): compile time
+              if (r >= 0 && r < Ho) {
 #pragma unroll
-                  for (int e = 0; e < 4; e++) acc[slot][j][e] = fmaf(v[j + dx][e], w[e], acc[slot][j][e]);
+                for (int dx = 0; dx < K; dx++) {
+                  const f32x4 w = *reinterpret_cast<const f32x4*>(wl + ((dy * K + dx) * LP + c4) * 4);
+#pragma unroll
+                  for (int j = 0; j < PX; j++)
+#pragma unroll
+                    for (int e = 0; e < 4; e++) acc[slot][j][e] = fmaf(v[j * SW + dx][e], w[e], acc[slot][j][e]);
+                }
               }
             }
+            if ((u - P + G) % SH == 0) {   // output row (i - P) / SH has seen its last input row
+              const int r = i0 / SH + (u - P + G) / SH - NS;
+              if (r >= 0 && r < Ho) store_row(r, acc[((u - P + G) / SH) % NS]);
+            }
           }
-          if (i - P >= 0) store_row(i - P, acc[(u - P + K) % K]);   // output row i - P has seen its last input row
         }
       }
-    }
+      const int r0 = Hi - 1 - P >= 0 ? (Hi - 1 - P) / SH + 1 : 0;   // rows stored above: those with r * SH + P <= Hi - 1
 #pragma unroll
-    for (int t = 0; t < P; t++) {   // the last P output rows end at the bottom padding
-      const int r = H - P + t;
-      if (r >= 0) {
+      for (int t = 0; t < P; t++) {   // the last output rows end at the bottom padding
+        const int r = r0 + t;
+        if (r < Ho) {
 #pragma unroll
-        for (int sl = 0; sl < K; sl++)
-          if (r % K == sl) store_row(r, acc[sl]);
+          for (int sl = 0; sl < NS; sl++)
+            if (r % NS == sl) store_row(r, acc[sl]);
+        }
       }
+    });
+  }
+  if (PR) {   // block k of the row kernel = strips 16 k .. 16 k + 15 of the image, column-major; this block holds strips_y of them
+    __syncthreads();
+    const int k = tid / LP;
+    const long long blk = (long long)blockIdx.x * strips_y + k;
+    if (k < strips_y && blk * SPB < (long long)strips_x * strips_y && cbase + c4 * 4 < Cp) {
+      const f32x4* p = reinterpret_cast<const f32x4*>(psl) + k * SPB * LP + c4;   // strip s of the block: p[s * LP]
+      f32x4 t = (p[0] + p[LP]) + (p[2 * LP] + p[3 * LP]);
+#pragma unroll
+      for (int w = 1; w < 4; w++) t += (p[(4 * w) * LP] + p[(4 * w + 1) * LP]) + (p[(4 * w + 2) * LP] + p[(4 * w + 3) * LP]);
+      *reinterpret_cast<f32x4*>(pool + ((long long)blockIdx.y * pool_pitch + blk) * Cp + cbase + c4 * 4) = t;
     }
-  });
+  }
 }
 
 static int dw_lanes_per_pixel(int K, int sh, int sw, int R, int Cp, bool pool);
 int g_dw_sweep = getenv("RT_DW_SWEEP") ? atoi(getenv("RT_DW_SWEEP")) : 4;   // column-sweep kernels on short maps (0: off)
 // Output rows per thread of k_dwconv_rows: 4 (stride 1) or 2 (stride 2); 3 for the 3- and 6-row maps of the
 // recognition net's last stages, where 4-row (2-row) strips would leave a quarter of the lanes' rows empty.
+// It is also the strip height of the squeeze-excite partial sums (dwconv_pool_layout), whichever kernel writes them: the pooled
+// k_dwconv_sweep instances add the outputs strip by strip in this kernel's order, so the value stays part of the results.
+// (Measured with those instances: the 3-row strips' layers, 6-row maps, were the ones that re-read most -- 10 row reads for 6
+// rows at stride 1, 18 for 12 at stride (2, 1): 1.23-1.36 x their input at the fabric, 1.05 x on the sweep.)
 static int dw_strip_rows(int sh, int maxHo) {
   if (maxHo == 6 || (maxHo == 3 && sh == 1)) return 3;  // (stride 2 onto 3 rows: 2-row strips measured faster)
   return sh == 1 ? 4 : 2;
+}
+
+// Which k_dwconv_sweep instance runs the layer (0: none, k_dwconv_rows does).  The one place that decides it.
+static int dw_sweep_form(int K, int sh, int sw, int R, int lp, int maxHo, bool pool) {
+  if (!g_dw_sweep || lp != 16 || maxHo * sh > 24) return 0;
+  const bool pool3 = pool && R == 3 && (maxHo + 2) / 3 <= DW_SWEEP_POOL_STRIPS;
+  if (K == 5 && sh == 1 && sw == 1 && maxHo >= 5) return !pool ? 1 : pool3 ? 3 : 0;
+  if (K == 3 && sh == 1 && sw == 1 && maxHo >= 3 && !pool) return 2;
+  if (K == 5 && sh == 2 && sw == 1 && maxHo >= 3) return !pool ? 4 : pool3 ? 5 : 0;
+  if (K == 3 && sh == 1 && sw == 2 && maxHo >= 3 && !pool) return 6;
+  return 0;
+}
+bool dwconv_sweeps(int K, int sh, int sw, int Cp, int maxHo, bool pool) {
+  if ((K != 3 && K != 5) || sh < 1 || sh > 2 || sw < 1 || sw > 2) return false;
+  const int R = dw_strip_rows(sh, maxHo);
+  return dw_sweep_form(K, sh, sw, R, dw_lanes_per_pixel(K, sh, sw, R, Cp, pool), maxHo, pool) != 0;
 }
 
 void dwconv(hipStream_t st, int K, int sh, int sw, const float* x, const ImgGeom* gin, const ImgGeom* gout, int n_img,
@@ -1480,19 +1560,25 @@ void dwconv(hipStream_t st, int K, int sh, int sw, const float* x, const ImgGeom
     // 64-channel slabs (256 contiguous bytes per pixel and load) for wide tensors: the 5x5 kernel on 256 channels goes from
     // 2.9 to 4.1 TB/s with them; 32-channel slabs otherwise
     const int lp = dw_lanes_per_pixel(K, sh, sw, R, Cp, pool != nullptr);
-    // short, wide maps: one thread column sweeps the whole height (RT_DW_SWEEP=0: off)
-    if (g_dw_sweep && K == 5 && sh == 1 && sw == 1 && !pool && lp == 16 && maxHo >= 5 && maxHo <= 24) {
+    // short, wide maps: one thread column sweeps the whole height, every input row fetched once (RT_DW_SWEEP=0: off).  The 5x5
+    // stride-1 layers of the 12-row maps, the 3x3 stride-1 layer of the 128-channel maps (k_dwconv_rows fetched 1.33x its output
+    // there: 6-row patches of 4-row strips, PMC), and the recognition net's strided and squeeze-excite layers, whose pooled partial
+    // sums keep the layout and the values of the row kernel's (dwconv_pool_layout: 3-row strips).
+    if (const int form = dw_sweep_form(K, sh, sw, R, lp, maxHo, pool != nullptr)) {
       const int spb = 256 / 16;
       dim3 grids((unsigned)(((maxWo + 3) / 4 + spb - 1) / spb), n_img, (Cp + 63) / 64);
-      RT_LAUNCH((k_dwconv_sweep<5, 16, 4, 3>), grids, dim3(256), 0, st, x, gin, gout, Cp, C, Wd, bias, act, has_lab, lab_a, lab_c, y);
-      return;
-    }
-    // (round 4) the same sweep for the 3x3 stride-1 layer on the 12-row, 128-channel maps of the recognition net: k_dwconv_rows
-    // fetched 1.33x its output there (6-row patches of 4-row strips, PMC)
-    if (g_dw_sweep && K == 3 && sh == 1 && sw == 1 && !pool && lp == 16 && maxHo >= 3 && maxHo <= 24) {
-      const int spb = 256 / 16;
-      dim3 grids((unsigned)(((maxWo + 3) / 4 + spb - 1) / spb), n_img, (Cp + 63) / 64);
-      RT_LAUNCH((k_dwconv_sweep<3, 16, 4, 4>), grids, dim3(256), 0, st, x, gin, gout, Cp, C, Wd, bias, act, has_lab, lab_a, lab_c, y);
+      const int pitch = (int)((strips + spb - 1) / spb);   // pooled partials per image: the row kernel's blocks
+      if (pool && (maxHo + R - 1) / R > DW_SWEEP_POOL_STRIPS) throw RtError(8, "dwconv: pooled sweep on a map of more strips than its LDS holds");
+#define RT_DWS(KK, WV, SH_, SW_, PR_) RT_LAUNCH((k_dwconv_sweep<KK, 16, 4, WV, SH_, SW_, PR_>), grids, dim3(256), 0, st, x, gin, gout, Cp, C, Wd, bias, act, has_lab, lab_a, lab_c, y, pool, pitch)
+      switch (form) {
+        case 1: RT_DWS(5, 3, 1, 1, 0); break;
+        case 2: RT_DWS(3, 4, 1, 1, 0); break;
+        case 3: RT_DWS(5, 3, 1, 1, 3); break;
+        case 4: RT_DWS(5, 4, 2, 1, 0); break;
+        case 5: RT_DWS(5, 3, 2, 1, 3); break;   // (waves per SIMD of each instance: see the kernel's header)
+        default: RT_DWS(3, 4, 1, 2, 0); break;
+      }
+#undef RT_DWS
       return;
     }
     if (lp == 16) {
