@@ -444,6 +444,30 @@ RT_API int rt_debug_dwconv(rt_session* s, const float* x, const int* heights, co
  * it), lines of tokens[i] consecutive rows (sum = rows) -> out [rows][heads * 15], with the geometry SvtrCore::mixer passes. */
 RT_API int rt_debug_attention(rt_session* s, const float* qkv, long long rows, const int* tokens, int n_lines, int heads,
                               float* out);
+/* One fused thin LCNetV3 block (3x3 depthwise, stride (sh, sw), "same" padding -> 1x1 conv + hardswish) as one nn::lc_thin launch on
+ * host arrays, for the numerics tests: n_img images of heights[i] x widths[i] pixels, consecutive in x [sum h w][Cp] with Cp =
+ * cin rounded up to 4 (32 from 128 channels on; channels cin .. Cp zero), laid out as the networks' levels are.  dw_w [cin][3][3]
+ * (torch depthwise layout) and dw_bias [cin], pw_w [cout][cin] and pw_bias [cout], packed by the networks' own packers; dw_act and
+ * the two LABs (has, a, c) as rt_debug_gemm.  form (the thin blocks' A/B switch): 0 = k_lc_thin, or the depthwise + GEMM pair where
+ * it has no instance, 1 = k_lc_wave, 3 = k_lc_lds (production).  out [(sum ho wo + 64) * ldy], ho = ceil(h / sh), wo = ceil(w / sw),
+ * ldy = cout's channel pitch, filled with RT_DEBUG_CANARY before the launch and returned whole.  info_out[0] = the route that ran:
+ * 0 the unfused pair, 1 k_lc_thin, 2 k_lc_wave, 3 k_lc_lds. */
+RT_API int rt_debug_lc_block(rt_session* s, const float* x, const int* heights, const int* widths, int n_img, int cin, int cout,
+                             int sh, int sw, const float* dw_w, const float* dw_bias, const float* pw_w, const float* pw_bias,
+                             int dw_act, int dw_has_lab, float dw_a, float dw_c, int pw_has_lab, float pw_a, float pw_c, int form,
+                             float* out, int* info_out);
+/* One 1x3 conv over lines of tokens (the SVTR neck's) on host arrays: x [rows][ldx] (channels 0 .. cin read), lines of
+ * tokens_per_line[i] consecutive rows (sum = rows), w [cout][cin][1][3], bias [cout] or NULL, zero padding at both ends of every
+ * line, act as rt_debug_gemm.  form 0 = nn::conv_sp on one 1 x T image per line, 1 = nn::conv13_flat over the flat token list with
+ * the line-boundary flags the recognition net builds.  out [(rows + 64) * ldy], ldy = cout's channel pitch, filled with
+ * RT_DEBUG_CANARY before the launch and returned whole.  info_out[2] = {column tiles per workgroup conv13_flat chose (0 for form
+ * 0), the CU count it chose them for}. */
+RT_API int rt_debug_conv13(rt_session* s, const float* x, long long rows, int ldx, const int* tokens_per_line, int n_lines, int cin,
+                           const float* w, int cout, const float* bias, int act, int form, float* out, int* info_out);
+/* One nn::add_layernorm launch on host arrays: out = LayerNorm(x + r) over the C channels of each row (r NULL: of x), x, r
+ * [rows][C], g, beta [C].  out [(rows + 64) * C], filled with RT_DEBUG_CANARY before the launch and returned whole. */
+RT_API int rt_debug_layernorm(rt_session* s, const float* x, const float* r, long long rows, int C, const float* g,
+                              const float* beta, float eps, float* out);
 /* times the fused thin LCNetV3 block (3x3 depthwise -> 1x1 conv; n images of h x w, random data).  form: 0 = k_lc_thin
  * (workgroup-staged; the unfused depthwise + GEMM pair where it has no instance), 1 = k_lc_wave (direct loads, stride 1 only),
  * 3 = k_lc_lds (production).  stride: 1, 2, or 21 = (2, 1).  Returns the average ms and the max |diff| against form 0. */

@@ -1045,6 +1045,134 @@ RT_API int rt_debug_ctc_candidates(rt_session* s, const float* z5, const float* 
   });
 }
 
+// One nn::lc_thin launch on host arrays (tests/test_gpu_rec_kernels.py compares it with an fp64 block): a ragged batch laid out as
+// the networks' levels are, the weights packed by the networks' pack_dw / pack_conv, the route named by nn::lc_route -- what
+// lc_thin() itself dispatches on.  form = nn::g_lc_wave for the launch; where no fused form has an instance the block runs as
+// run_lc runs it: nn::dwconv + nn::gemm.
+RT_API int rt_debug_lc_block(rt_session* s, const float* x, const int* heights, const int* widths, int n_img, int cin, int cout,
+                             int sh, int sw, const float* dw_w, const float* dw_bias, const float* pw_w, const float* pw_bias,
+                             int dw_act, int dw_has_lab, float dw_a, float dw_c, int pw_has_lab, float pw_a, float pw_c, int form,
+                             float* out, int* info_out) {
+  RT_REQUIRE(s && x && heights && widths && dw_w && dw_bias && pw_w && pw_bias && out && info_out, s, "rt_debug_lc_block: null argument");
+  RT_REQUIRE(n_img > 0 && n_img <= RT_MAX_GRID_Y && cin > 0 && cout > 0 && chan_pitch(cin) == round_up(cin, 4) && sh >= 1 && sh <= 2 &&
+                 sw >= 1 && sw <= 2 && dw_act >= ACT_NONE && dw_act <= ACT_SIGMOID && (form == 0 || form == 1 || form == 3),
+             s, "rt_debug_lc_block: bad shape");
+  const int Cp = chan_pitch(cin), ldy = chan_pitch(cout);
+  std::vector<ImgGeom> gi(n_img), go(n_img);
+  long long pin = 0, pout = 0;
+  int maxHo = 0, maxWo = 0;
+  for (int i = 0; i < n_img; i++) {
+    RT_REQUIRE(heights[i] > 0 && widths[i] > 0, s, "rt_debug_lc_block: empty image");
+    const int ho = (heights[i] + sh - 1) / sh, wo = (widths[i] + sw - 1) / sw;
+    gi[i] = ImgGeom{pin, heights[i], widths[i], 0}; go[i] = ImgGeom{pout, ho, wo, 0};
+    pin += (long long)heights[i] * widths[i]; pout += (long long)ho * wo;
+    maxHo = std::max(maxHo, ho); maxWo = std::max(maxWo, wo);
+  }
+  RT_REQUIRE(pin * Cp < (1ll << 30) && pout * ldy < (1ll << 30), s, "rt_debug_lc_block: too large");
+  return guarded(s, [&] {
+    RT_HIP_CHECK(hipSetDevice(s->device));
+    WeightStore ws;
+    const PackedDw dw = pack_dw(ws, dw_w, dw_bias, cin, 3);
+    const PackedDense pw = pack_conv(ws, pw_w, pw_bias, cout, cin, 1, 1);
+    const Lab lab{pw_has_lab, pw_a, pw_c};
+    const Epilogue e = make_epi(pw, ACT_HSWISH, &lab);
+    DevBufs bufs;
+    RestoreInt keep_form(nn::g_lc_wave);
+    nn::g_lc_wave = form;
+    const size_t nin = (size_t)pin * Cp, nout = (size_t)(pout + 64) * ldy;
+    float *dx = bufs.alloc<float>(nin), *dy = bufs.alloc<float>(nout);
+    ImgGeom *dgi = bufs.alloc<ImgGeom>(n_img), *dgo = bufs.alloc<ImgGeom>(n_img);
+    RT_HIP_CHECK(hipMemcpy(dx, x, nin * sizeof(float), hipMemcpyHostToDevice));
+    RT_HIP_CHECK(hipMemcpy(dgi, gi.data(), n_img * sizeof(ImgGeom), hipMemcpyHostToDevice));
+    RT_HIP_CHECK(hipMemcpy(dgo, go.data(), n_img * sizeof(ImgGeom), hipMemcpyHostToDevice));
+    RT_HIP_CHECK(hipMemsetD32Async((hipDeviceptr_t)dy, (int)RT_DEBUG_CANARY, nout, s->st));
+    const nn::LcRoute route = nn::lc_route(3, sh, sw, dw.Cp, dw.C, pw.N, pw.Npad, dw_act, dw_has_lab, e, maxHo, maxWo, ldy);
+    if (route == nn::LC_UNFUSED) {   // no fused instance: depthwise + GEMM
+      const size_t nmid = (size_t)(pout + 256) * Cp;   // (zero rows past the last pixel: a GEMM tile's loads stay inside the allocation)
+      float* dy1 = bufs.alloc<float>(nmid);
+      RT_HIP_CHECK(hipMemsetAsync(dy1, 0, nmid * sizeof(float), s->st));
+      nn::dwconv(s->st, 3, sh, sw, dx, dgi, dgo, n_img, maxHo, maxWo, dw.Cp, dw.C, dw.w, dw.b, dw_act, dw_has_lab, dw_a, dw_c, dy1, nullptr);
+      nn::gemm(s->st, dy1, dw.Cp, pout, pw.K, pw.w, pw.N, pw.Npad, dy, ldy, 0, e);
+    } else {
+      nn::lc_thin(s->st, sh, sw, dx, dgi, dgo, n_img, maxHo, maxWo, dw.Cp, dw.C, dw.w, dw.b, dw_act, dw_has_lab, dw_a, dw_c, pw.w, pw.N,
+                  pw.Npad, dy, ldy, e);
+    }
+    RT_HIP_CHECK(hipStreamSynchronize(s->st));
+    RT_HIP_CHECK(hipMemcpy(out, dy, nout * sizeof(float), hipMemcpyDeviceToHost));
+    info_out[0] = (int)route;
+  });
+}
+
+// One 1x3 token conv on host arrays: form 0 = nn::conv_sp on one ImgGeom{off, 1, T} per line (the fallback of RecNet::run), form 1 =
+// nn::conv13_flat over the flat list with RecNet's token_line_flags; the weights through pack_conv.
+RT_API int rt_debug_conv13(rt_session* s, const float* x, long long rows, int ldx, const int* tokens_per_line, int n_lines, int cin,
+                           const float* w, int cout, const float* bias, int act, int form, float* out, int* info_out) {
+  RT_REQUIRE(s && x && tokens_per_line && w && out && info_out, s, "rt_debug_conv13: null argument");
+  RT_REQUIRE(rows > 0 && rows < (1ll << 24) && n_lines > 0 && n_lines <= RT_MAX_GRID_Y && cin > 0 && cin % 4 == 0 && ldx >= cin &&
+                 ldx % 4 == 0 && cout > 0 && cout <= 64 && act >= ACT_NONE && act <= ACT_SIGMOID && (form == 0 || form == 1),
+             s, "rt_debug_conv13: bad shape");
+  RT_REQUIRE(rows * ldx < (1ll << 30), s, "rt_debug_conv13: too large");
+  std::vector<ImgGeom> geom;
+  long long total = 0;
+  int maxT = 0;
+  for (int i = 0; i < n_lines; i++) {
+    RT_REQUIRE(tokens_per_line[i] > 0, s, "rt_debug_conv13: a line without tokens");
+    geom.push_back(ImgGeom{total, 1, tokens_per_line[i], 0});
+    total += tokens_per_line[i]; maxT = std::max(maxT, tokens_per_line[i]);
+  }
+  RT_REQUIRE(total == rows, s, "rt_debug_conv13: the lines' tokens do not add up to rows");
+  return guarded(s, [&] {
+    RT_HIP_CHECK(hipSetDevice(s->device));
+    WeightStore ws;
+    const PackedDense pw = pack_conv(ws, w, bias, cout, cin, 1, 3);
+    if (form == 1 && !nn::conv13_flat_supported(cout, pw.Npad)) throw RtError(RT_ERR_INVALID, "rt_debug_conv13: conv13_flat has no instance for the layer");
+    const Epilogue e = make_epi(pw, act);
+    const int ldy = chan_pitch(cout);
+    DevBufs bufs;
+    const size_t nin = (size_t)rows * ldx, nout = (size_t)(rows + 64) * ldy;
+    float *dx = bufs.alloc<float>(nin), *dy = bufs.alloc<float>(nout);
+    RT_HIP_CHECK(hipMemcpy(dx, x, nin * sizeof(float), hipMemcpyHostToDevice));
+    RT_HIP_CHECK(hipMemsetD32Async((hipDeviceptr_t)dy, (int)RT_DEBUG_CANARY, nout, s->st));
+    info_out[0] = 0; info_out[1] = stream_cus(s->st);
+    if (form == 1) {
+      std::vector<unsigned char> hf((size_t)rows);
+      token_line_flags(geom, rows, hf.data());
+      unsigned char* df = bufs.alloc<unsigned char>((size_t)rows);
+      RT_HIP_CHECK(hipMemcpy(df, hf.data(), (size_t)rows, hipMemcpyHostToDevice));
+      info_out[0] = nn::conv13_flat_nt(rows, pw.Npad, info_out[1]);
+      nn::conv13_flat(s->st, dx, ldx, rows, df, cin, pw.w, cout, pw.Npad, dy, ldy, e);
+    } else {
+      ImgGeom* dg = bufs.alloc<ImgGeom>(n_lines);
+      RT_HIP_CHECK(hipMemcpy(dg, geom.data(), geom.size() * sizeof(ImgGeom), hipMemcpyHostToDevice));
+      nn::conv_sp(s->st, 1, 3, dx, ldx, dg, n_lines, 1, maxT, cin, pw.w, cout, pw.Npad, dy, ldy, e);
+    }
+    RT_HIP_CHECK(hipStreamSynchronize(s->st));
+    RT_HIP_CHECK(hipMemcpy(out, dy, nout * sizeof(float), hipMemcpyDeviceToHost));
+  });
+}
+
+// One nn::add_layernorm launch on host arrays.
+RT_API int rt_debug_layernorm(rt_session* s, const float* x, const float* r, long long rows, int C, const float* g,
+                              const float* beta, float eps, float* out) {
+  RT_REQUIRE(s && x && g && beta && out, s, "rt_debug_layernorm: null argument");
+  RT_REQUIRE(rows > 0 && rows < (1ll << 22) && C > 0 && C <= 256 && eps > 0.f, s, "rt_debug_layernorm: bad shape");
+  return guarded(s, [&] {
+    RT_HIP_CHECK(hipSetDevice(s->device));
+    DevBufs bufs;
+    const size_t nin = (size_t)rows * C, nout = (size_t)(rows + 64) * C;
+    float *dx = bufs.alloc<float>(nin), *dr = r ? bufs.alloc<float>(nin) : nullptr, *dg = bufs.alloc<float>(C), *db = bufs.alloc<float>(C),
+          *dy = bufs.alloc<float>(nout);
+    RT_HIP_CHECK(hipMemcpy(dx, x, nin * sizeof(float), hipMemcpyHostToDevice));
+    if (r) RT_HIP_CHECK(hipMemcpy(dr, r, nin * sizeof(float), hipMemcpyHostToDevice));
+    RT_HIP_CHECK(hipMemcpy(dg, g, (size_t)C * sizeof(float), hipMemcpyHostToDevice));
+    RT_HIP_CHECK(hipMemcpy(db, beta, (size_t)C * sizeof(float), hipMemcpyHostToDevice));
+    RT_HIP_CHECK(hipMemsetD32Async((hipDeviceptr_t)dy, (int)RT_DEBUG_CANARY, nout, s->st));
+    nn::add_layernorm(s->st, dx, dr, rows, C, dg, db, eps, dy);
+    RT_HIP_CHECK(hipStreamSynchronize(s->st));
+    RT_HIP_CHECK(hipMemcpy(out, dy, nout * sizeof(float), hipMemcpyDeviceToHost));
+  });
+}
+
 // Kernel micro-benchmark: the fused thin LCNetV3 block (3x3 depthwise -> pointwise) on n images of h x w pixels, random data.
 // form = nn::g_lc_wave for the timed launches: 0 = k_lc_thin (workgroup-staged; the unfused depthwise + GEMM pair where it has no
 // instance), 1 = k_lc_wave (direct loads, stride 1), 3 = k_lc_lds (production); stride 21 means (2, 1).  maxdiff compares with
@@ -1059,12 +1187,14 @@ RT_API int rt_bench_lc(rt_session* s, int n, int h, int w, int cin, int cout, in
     std::vector<ImgGeom> gi(n), go(n);
     for (int i = 0; i < n; i++) { gi[i] = ImgGeom{(long long)i * h * w, h, w, 0}; go[i] = ImgGeom{(long long)i * ho * wo, ho, wo, 0}; }
     const size_t nin = (size_t)n * h * w * Cp, nout = (size_t)n * ho * wo * ldy;
-    std::vector<float> hx(nin), hwd(9 * Cp), hbd(Cp, 0.05f), hw((size_t)nkc * Np * nn::KC, 0.f), hb(Np, 0.1f);
+    std::vector<float> hx(nin), hwd(9 * Cp), hbd(Cp, 0.f), hw((size_t)nkc * Np * nn::KC, 0.f), hb(Np, 0.f);
     uint32_t st = 777;
     auto rnd = [&]() { st = st * 1664525u + 1013904223u; return ((st >> 8) & 0xffff) / 32768.0f - 1.0f; };
     for (auto& v : hx) v = rnd();
     for (auto& v : hwd) v = rnd() * 0.3f;
     for (int k = 0; k < cin; k++) for (int c = 0; c < cout; c++) hw[((size_t)(k / nn::KC) * Np + c) * nn::KC + k % nn::KC] = rnd() * 0.1f;
+    for (int k = 0; k < cin; k++) hbd[k] = rnd() * 0.1f;    // (a bias per channel: a constant one would hide an indexing error)
+    for (int c = 0; c < cout; c++) hb[c] = rnd() * 0.2f;
     DevBufs bufs;
     RestoreInt keep_form(nn::g_lc_wave);
     float *dx = bufs.alloc<float>(nin), *dwd = bufs.alloc<float>(hwd.size()), *dbd = bufs.alloc<float>(hbd.size()), *dw = bufs.alloc<float>(hw.size()),

@@ -90,6 +90,15 @@ static void expect_dims(const BlobTensor& t, std::initializer_list<int> d, const
 PackedDense pack_conv(WeightStore& ws, const Blob& b, const std::string& name, int cout, int cin, int kh, int kw) {
   const BlobTensor& w = b.get(name + ".w");
   expect_dims(w, {cout, cin, kh, kw}, name + ".w");
+  const float* bias = nullptr;
+  if (b.has(name + ".b")) {
+    const BlobTensor& bt = b.get(name + ".b");
+    expect_dims(bt, {cout}, name + ".b");
+    bias = bt.data;
+  }
+  return pack_conv(ws, w.data, bias, cout, cin, kh, kw);
+}
+PackedDense pack_conv(WeightStore& ws, const float* w, const float* bias_in, int cout, int cin, int kh, int kw) {
   PackedDense p;
   p.K = round_up(cin, 4); p.N = cout; p.Npad = round_up(cout, 16); p.kh = kh; p.kw = kw;
   const int taps = kh * kw, nkc = (p.K + nn::KC - 1) / nn::KC;
@@ -98,15 +107,11 @@ PackedDense pack_conv(WeightStore& ws, const Blob& b, const std::string& name, i
     for (int k = 0; k < cin; k++)
       for (int t = 0; t < taps; t++) {
         int kc = k / nn::KC, kk = k % nn::KC;
-        host[(((size_t)kc * taps + t) * p.Npad + n) * nn::KC + kk] = w.data[((size_t)n * cin + k) * taps + t];
+        host[(((size_t)kc * taps + t) * p.Npad + n) * nn::KC + kk] = w[((size_t)n * cin + k) * taps + t];
       }
   p.w = ws.upload(host);
   std::vector<float> bias(p.Npad, 0.f);
-  if (b.has(name + ".b")) {
-    const BlobTensor& bt = b.get(name + ".b");
-    expect_dims(bt, {cout}, name + ".b");
-    memcpy(bias.data(), bt.data, cout * sizeof(float));
-  }
+  if (bias_in) memcpy(bias.data(), bias_in, cout * sizeof(float));
   p.b = ws.upload(bias);
   return p;
 }
@@ -135,13 +140,16 @@ PackedDense pack_linear(WeightStore& ws, const float* w, const float* bias_in, i
 static PackedDw pack_dw(WeightStore& ws, const Blob& b, const std::string& name, int C, int k) {
   const BlobTensor& w = b.get(name + ".w");
   expect_dims(w, {C, 1, k, k}, name + ".w");
+  const BlobTensor& bt = b.get(name + ".b");
+  expect_dims(bt, {C}, name + ".b");
+  return pack_dw(ws, w.data, bt.data, C, k);
+}
+PackedDw pack_dw(WeightStore& ws, const float* w, const float* bias_in, int C, int k) {
   PackedDw p; p.k = k; p.C = C; p.Cp = chan_pitch(C);
   std::vector<float> host((size_t)k * k * p.Cp, 0.f), bias(p.Cp, 0.f);
   for (int c = 0; c < C; c++)
-    for (int t = 0; t < k * k; t++) host[(size_t)t * p.Cp + c] = w.data[(size_t)c * k * k + t];
-  const BlobTensor& bt = b.get(name + ".b");
-  expect_dims(bt, {C}, name + ".b");
-  memcpy(bias.data(), bt.data, C * sizeof(float));
+    for (int t = 0; t < k * k; t++) host[(size_t)t * p.Cp + c] = w[(size_t)c * k * k + t];
+  memcpy(bias.data(), bias_in, C * sizeof(float));
   p.w = ws.upload(host); p.b = ws.upload(bias);
   return p;
 }
@@ -557,6 +565,12 @@ RecNet::RecNet(const Blob& b) {
   core_.load(ws_, b, "rec");
 }
 
+void token_line_flags(const std::vector<ImgGeom>& lines, long long rows, unsigned char* flags) {
+  memset(flags, 0, (size_t)rows);
+  for (const ImgGeom& g : lines)
+    if (g.H == 1 && g.W > 0) { flags[g.off] |= 1; flags[g.off + g.W - 1] |= 2; }
+}
+
 int RecNet::tokens_for_width(int w) {
   int wa = (w - 1) / 2 + 1, wc = (wa - 1) / 2 + 1;
   return wc >= 2 ? (wc - 2) / 2 + 1 : 0;
@@ -587,9 +601,7 @@ float* RecNet::run(RunCtx& c, const float* x, Level& L0, Level& Lt, int* idx_out
   unsigned char* tok_flags = nullptr;
   if (nn::conv13_flat_supported(60, conv1_.Npad) && Lt.maxH == 1 && rows > 0) {
     unsigned char* hf = c.pinned->alloc<unsigned char>((size_t)rows);
-    memset(hf, 0, (size_t)rows);
-    for (const ImgGeom& g : Lt.h)
-      if (g.H == 1 && g.W > 0) { hf[g.off] |= 1; hf[g.off + g.W - 1] |= 2; }
+    token_line_flags(Lt.h, rows, hf);
     tok_flags = c.arena->alloc<unsigned char>((size_t)rows);
     RT_HIP_CHECK(hipMemcpyAsync(tok_flags, hf, (size_t)rows, hipMemcpyHostToDevice, c.st));
   }

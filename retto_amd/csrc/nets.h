@@ -60,6 +60,8 @@ class WeightStore {  // owns one device allocation per network
 };
 
 PackedDense pack_conv(WeightStore& ws, const Blob& b, const std::string& name, int cout, int cin, int kh, int kw);
+PackedDense pack_conv(WeightStore& ws, const float* w, const float* bias, int cout, int cin, int kh, int kw);   // host w [cout][cin][kh][kw], bias [cout] or null
+PackedDw pack_dw(WeightStore& ws, const float* w, const float* bias, int C, int k);   // host w [C][k][k] (torch depthwise layout), bias [C]
 PackedDense pack_linear(WeightStore& ws, const Blob& b, const std::string& name, int cin, int cout);
 PackedDense pack_linear(WeightStore& ws, const float* w, const float* bias, int cin, int cout);   // host w [cin][cout], bias [cout] or null
 float* upload_raw(WeightStore& ws, const Blob& b, const std::string& name, size_t expect_numel);
@@ -67,6 +69,9 @@ float* upload_raw(WeightStore& ws, const Blob& b, const std::string& name, size_
 // (2 ints per block) or 256 (3 ints per block, k_gemm32p): se_row_table_len(total, tile_rows) ints.
 size_t se_row_table_len(long long total, int tile_rows);
 void se_row_table(const std::vector<ImgGeom>& imgs, long long total, int tile_rows, int* tab);
+// Line-boundary flags of the flat token list nn::conv13_flat runs over: flags[rows], bit 0 = first token of its line, bit 1 = last
+// (lines = the H = 1 images of a token level; a line without tokens sets nothing).
+void token_line_flags(const std::vector<ImgGeom>& lines, long long rows, unsigned char* flags);
 Epilogue make_epi(const PackedDense& p, int act, const Lab* lab = nullptr, const float* residual = nullptr, int ld_res = 0);
 
 struct LcBlock {

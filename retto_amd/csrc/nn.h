@@ -37,6 +37,7 @@ extern int g_dw_sweep;      // A/B: column-sweep depthwise kernels on short maps
 bool conv13_flat_supported(int N, int Npad16);
 void conv13_flat(hipStream_t st, const float* x, int ldx, long long rows, const unsigned char* flags, int Cin, const float* Wp, int N,
                  int Npad16, float* y, int ldy, const Epilogue& epi);
+int conv13_flat_nt(long long rows, int Npad16, int cus);   // column tiles (16 channels each) per workgroup conv13_flat() picks on `cus` CUs
 void conv_sp(hipStream_t st, int KH, int KW, const float* x, int ldx, const ImgGeom* geom, int n_img, int maxH,
              int maxW, int Cin, const float* Wp, int N, int Npad16, float* y, int ldy, const Epilogue& epi);
 
@@ -73,6 +74,12 @@ void lc_thin(hipStream_t st, int sh, int sw, const float* x, const ImgGeom* gin,
              const float* Wp, int N, int Npad16, float* y, int ldy, const Epilogue& epi);
 // one-wave-per-tile form of the same block (nn_lcwave.hip): activations never touch LDS; bit-identical to lc_thin
 extern int g_lc_wave;
+// the kernel lc_thin() runs for a block under the current g_lc_wave (LC_UNFUSED: no fused form has an instance; lc_thin() throws and
+// the caller runs nn::dwconv + nn::gemm).  lc_thin() dispatches on it, rt_debug_lc_block reports it.
+enum LcRoute { LC_UNFUSED = 0, LC_THIN = 1, LC_WAVE = 2, LC_LDS = 3 };
+LcRoute lc_route(int K, int sh, int sw, int Cp, int C, int N, int Npad16, int dw_act, int dw_has_lab, const Epilogue& epi, int maxHo,
+                 int maxWo, int ldy);
+bool lc_wave_runs_lds(int sh, int sw, int Cp, int Npad16);   // lc_wave() launches k_lc_lds (else k_lc_wave) for a block it supports
 // either form has an instance for the block (what run_lc asks before it takes the fused path)
 bool lc_block_supported(int K, int sh, int sw, int Cp, int C, int N, int Npad16, int dw_act, int dw_has_lab, const Epilogue& epi,
                         int maxHo, int maxWo);

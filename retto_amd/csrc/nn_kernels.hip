@@ -49,6 +49,30 @@ __device__ __forceinline__ void mma_chunk(const float* __restrict__ xs0, const f
   }
 }
 
+// The 1x3 token convs sum 3 * Cin = 1440 / 2880 products per output.  In ONE fp32 accumulator chain the rounding error grows with
+// the root of the chain's length (measured against fp64: rms 2.8 x / 3.8 x that of a blocked float32 GEMM on the CPU, where the
+// GEMM routes' chains of <= 480 terms stay within 1.1 x), so k_conv_sp<1, 3> and k_conv13_flat close a partial sum every
+// LONGK_SLABS slabs (3 * 32 * LONGK_SLABS products) and add it to a running total: chains of 192 terms, then <= 15 additions.
+constexpr int LONGK_SLABS = 2;
+template <int NT>
+__device__ __forceinline__ void longk_flush(f32x4 (&tot)[2][NT], f32x4 (&acc)[2][NT]) {
+#pragma unroll
+  for (int i = 0; i < 2; i++)
+#pragma unroll
+    for (int j = 0; j < NT; j++) {
+      tot[i][j] += acc[i][j];
+      acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+    }
+}
+// the open partial sum joins the total, which goes on to the epilogue in `acc`
+template <int NT>
+__device__ __forceinline__ void longk_finish(f32x4 (&tot)[2][NT], f32x4 (&acc)[2][NT]) {
+#pragma unroll
+  for (int i = 0; i < 2; i++)
+#pragma unroll
+    for (int j = 0; j < NT; j++) acc[i][j] = tot[i][j] + acc[i][j];
+}
+
 template <int NT>
 __device__ __forceinline__ void epilogue_store(f32x4 (&acc)[2][NT], int nt_valid, const Epilogue& epi, int n0, int N,
                                                int nstore, float* __restrict__ yrow0, float* __restrict__ yrow1,
@@ -691,18 +715,23 @@ static bool lc_wave_fits(int maxHo, int maxWo, int sh, int sw, int Cp, int ldy) 
   const long long in_bytes = (long long)(maxHo * sh + 2) * (maxWo * sw + 2) * Cp * 4, out_bytes = (long long)maxHo * maxWo * ldy * 4;
   return in_bytes < (1ll << 30) && out_bytes < (1ll << 30);
 }
+LcRoute lc_route(int K, int sh, int sw, int Cp, int C, int N, int Npad16, int dw_act, int dw_has_lab, const Epilogue& epi, int maxHo,
+                 int maxWo, int ldy) {
+  if (g_lc_wave && lc_wave_supported(K, sh, sw, Cp, C, N, Npad16, dw_act, dw_has_lab, epi) && lc_wave_fits(maxHo, maxWo, sh, sw, Cp, ldy))
+    return lc_wave_runs_lds(sh, sw, Cp, Npad16) ? LC_LDS : LC_WAVE;
+  return lc_thin_supported(K, sh, sw, Cp, C, Npad16) ? LC_THIN : LC_UNFUSED;
+}
 bool lc_block_supported(int K, int sh, int sw, int Cp, int C, int N, int Npad16, int dw_act, int dw_has_lab, const Epilogue& epi,
                         int maxHo, int maxWo) {
-  if (lc_thin_supported(K, sh, sw, Cp, C, Npad16)) return true;
-  return g_lc_wave && lc_wave_supported(K, sh, sw, Cp, C, N, Npad16, dw_act, dw_has_lab, epi) &&
-         lc_wave_fits(maxHo, maxWo, sh, sw, Cp, chan_pitch(N));
+  return lc_route(K, sh, sw, Cp, C, N, Npad16, dw_act, dw_has_lab, epi, maxHo, maxWo, chan_pitch(N)) != LC_UNFUSED;
 }
 void lc_thin(hipStream_t st, int sh, int sw, const float* x, const ImgGeom* gin, const ImgGeom* gout, int n_img, int maxHo,
              int maxWo, int Cp, int C, const float* Wd, const float* bd, int dw_act, int dw_has_lab, float dw_a, float dw_c,
              const float* Wp, int N, int Npad16, float* y, int ldy, const Epilogue& epi) {
   if (n_img <= 0) return;
   if (epi.residual || epi.a_scale) throw RtError(8, "lc_thin: residual / a_scale epilogues are not supported");
-  if (g_lc_wave && lc_wave_supported(3, sh, sw, Cp, C, N, Npad16, dw_act, dw_has_lab, epi) && lc_wave_fits(maxHo, maxWo, sh, sw, Cp, ldy)) {
+  const LcRoute route = lc_route(3, sh, sw, Cp, C, N, Npad16, dw_act, dw_has_lab, epi, maxHo, maxWo, ldy);
+  if (route == LC_WAVE || route == LC_LDS) {
     lc_wave(st, sh, sw, x, gin, gout, n_img, maxHo, maxWo, Cp, C, Wd, bd, dw_act, dw_has_lab, dw_a, dw_c, Wp, N, Npad16, y, ldy, epi);
     return;
   }
@@ -824,6 +853,14 @@ __global__ __launch_bounds__(256) void k_conv_sp(const float* __restrict__ x, in
   for (int i = 0; i < 2; i++)
 #pragma unroll
     for (int j = 0; j < NT; j++) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+  constexpr bool LONGK = KH == 1 && KW == 3;   // the token convs: partial sums (longk_flush), in k_conv13_flat's order
+  f32x4 tot[2][NT];
+  if constexpr (LONGK) {
+#pragma unroll
+    for (int i = 0; i < 2; i++)
+#pragma unroll
+      for (int j = 0; j < NT; j++) tot[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+  }
   // this lane's two pixels (tile-local)
   const int p0 = wave * 32 + r, p1 = p0 + 16;
   const int py0 = p0 / TW, px0 = p0 % TW, py1 = p1 / TW, px1 = p1 % TW;
@@ -882,8 +919,10 @@ __global__ __launch_bounds__(256) void k_conv_sp(const float* __restrict__ x, in
       for (int dx = 0; dx < KW; dx++)
         mma_chunk<NT>(xs + ((py0 + dy) * HW + px0 + dx) * LROW, xs + ((py1 + dy) * HW + px1 + dx) * LROW,
                       ws + (dy * KW + dx) * 16 * NT * LROW, nt_valid, acc, r, q);
+    if constexpr (LONGK) { if (kc % LONGK_SLABS == LONGK_SLABS - 1) longk_flush<NT>(tot, acc); }
     __syncthreads();
   }
+  if constexpr (LONGK) longk_finish<NT>(tot, acc);
   const int oy0 = ty * TH + py0, ox0 = tx * TW + px0, oy1 = ty * TH + py1, ox1 = tx * TW + px1;
   const bool v0 = oy0 < g.H && ox0 < g.W, v1 = oy1 < g.H && ox1 < g.W;
   const long long pa = g.off + (long long)oy0 * g.W + ox0, pb = g.off + (long long)oy1 * g.W + ox1;
@@ -1063,8 +1102,8 @@ void conv3_fpn_fused(hipStream_t st, const float* p5, const float* p4, const flo
 // 0.76 busy at 0.20 / 0.41 ms per launch for 8.8 / 17.7 GFLOP), and five ways of shrinking the tiles did not help (DESIGN.md
 // 5.4).  Here a tile is 128 CONSECUTIVE tokens whatever lines they belong to; `flags` (one byte per token: 1 = first of its
 // line, 2 = last) zero the left / right tap's operand where the neighbour belongs to another line.  Halo rows are contiguous
-// (130 rows of the activation matrix), every tile but the last is full.  Same slab / tap / (q, s) -> k order per accumulator as
-// k_conv_sp and exact zeros for the masked taps: bit-identical.
+// (130 rows of the activation matrix), every tile but the last is full.  Same slab / tap / (q, s) -> k order per accumulator and
+// the same partial sums (longk_flush) as k_conv_sp<1, 3>, and exact zeros for the masked taps: bit-identical.
 // ---------------------------------------------------------------------------
 template <int NT>
 __global__ __launch_bounds__(256) void k_conv13_flat(const float* __restrict__ x, int ldx, long long rows, const unsigned char* __restrict__ flags,
@@ -1083,6 +1122,11 @@ __global__ __launch_bounds__(256) void k_conv13_flat(const float* __restrict__ x
   for (int i = 0; i < 2; i++)
 #pragma unroll
     for (int j = 0; j < NT; j++) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+  f32x4 tot[2][NT];   // the closed partial sums (longk_flush)
+#pragma unroll
+  for (int i = 0; i < 2; i++)
+#pragma unroll
+    for (int j = 0; j < NT; j++) tot[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
   const int p0 = wave * 32 + r, p1 = p0 + 16;
   const long long t0 = P0 + p0, t1 = P0 + p1;
   const unsigned f0 = t0 < rows ? flags[t0] : 3u, f1 = t1 < rows ? flags[t1] : 3u;
@@ -1151,22 +1195,27 @@ __global__ __launch_bounds__(256) void k_conv13_flat(const float* __restrict__ x
         }
       }
     }
+    if (kc % LONGK_SLABS == LONGK_SLABS - 1) longk_flush<NT>(tot, acc);
     __syncthreads();
   }
+  longk_finish<NT>(tot, acc);
   const int nstore = (N + 3) & ~3;
   epilogue_store<NT>(acc, nt_valid, epi, n0, N, nstore, y + t0 * ldy, y + t1 * ldy, t0 < rows, t1 < rows,
                      epi.residual ? epi.residual + t0 * epi.ld_res : nullptr, epi.residual ? epi.residual + t1 * epi.ld_res : nullptr, q);
 }
 bool conv13_flat_supported(int N, int Npad16) { return Npad16 <= 64 && N > 0; }
-void conv13_flat(hipStream_t st, const float* x, int ldx, long long rows, const unsigned char* flags, int Cin, const float* Wp, int N,
-                 int Npad16, float* y, int ldy, const Epilogue& epi) {
-  if (rows <= 0) return;
+int conv13_flat_nt(long long rows, int Npad16, int cus) {
   const int ntiles = Npad16 / 16;
   int NT = ntiles >= 4 ? 4 : ntiles;
   // few tokens (one page: 13 tiles of 128 tokens walking 45 slabs each, 96 us): a column tile per workgroup until there is a
   // workgroup per CU -- the column tiles are independent: same bits (as the narrow GEMM's launch rule)
-  const int cus13 = stream_cus(st);
-  while (NT > 1 && (rows + 127) / 128 * ((ntiles + NT - 1) / NT) < cus13) NT = (NT + 1) / 2;
+  while (NT > 1 && (rows + 127) / 128 * ((ntiles + NT - 1) / NT) < cus) NT = (NT + 1) / 2;
+  return NT;
+}
+void conv13_flat(hipStream_t st, const float* x, int ldx, long long rows, const unsigned char* flags, int Cin, const float* Wp, int N,
+                 int Npad16, float* y, int ldy, const Epilogue& epi) {
+  if (rows <= 0) return;
+  const int ntiles = Npad16 / 16, NT = conv13_flat_nt(rows, Npad16, stream_cus(st));
   dim3 grid((unsigned)((rows + 127) / 128), (unsigned)((ntiles + NT - 1) / NT));
   switch (NT) {
     case 1: RT_LAUNCH((k_conv13_flat<1>), grid, dim3(256), 0, st, x, ldx, rows, flags, Cin, Wp, N, Npad16, y, ldy, epi); break;
@@ -2354,7 +2403,9 @@ void maxpool_2x2(hipStream_t st, const float* x, const ImgGeom* gin, const ImgGe
 // ---------------------------------------------------------------------------
 // SVTR pieces
 // ---------------------------------------------------------------------------
-// one wavefront per row; wave-shuffle reductions (two-pass mean / variance like F.layer_norm)
+// one wavefront per row; wave-shuffle reductions.  Corrected two-pass mean / variance: the fp32 mean is off by a few roundings
+// of itself, which at |mean| >> sigma is the whole error of the output (mean 10, sigma 1: 4e-7); the sum of the centred values
+// measures that offset, and taking it out of the centred values and of the variance leaves roundings of sigma's size only.
 __global__ __launch_bounds__(256) void k_add_layernorm(const float* __restrict__ x, const float* __restrict__ r,
                                                        long long rows, int C, const float* __restrict__ g,
                                                        const float* __restrict__ beta, float eps,
@@ -2373,15 +2424,20 @@ __global__ __launch_bounds__(256) void k_add_layernorm(const float* __restrict__
   }
   for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
   float mean = s / (float)C;
+  float ds = 0.f;
+#pragma unroll
+  for (int i = 0; i < 4; i++) { int c = lane + 64 * i; v[i] = c < C ? v[i] - mean : 0.f; ds += v[i]; }
+  for (int o = 32; o > 0; o >>= 1) ds += __shfl_xor(ds, o);
+  const float corr = ds / (float)C;   // what the rounded mean is off by
   float ss = 0.f;
 #pragma unroll
-  for (int i = 0; i < 4; i++) { int c = lane + 64 * i; if (c < C) { float d = v[i] - mean; ss = fmaf(d, d, ss); } }
+  for (int i = 0; i < 4; i++) { int c = lane + 64 * i; if (c < C) { v[i] -= corr; ss = fmaf(v[i], v[i], ss); } }
   for (int o = 32; o > 0; o >>= 1) ss += __shfl_xor(ss, o);
   float rstd = 1.0f / sqrtf(ss / (float)C + eps);
 #pragma unroll
   for (int i = 0; i < 4; i++) {
     int c = lane + 64 * i;
-    if (c < C) y[row * C + c] = fmaf((v[i] - mean) * rstd, g[c], beta[c]);
+    if (c < C) y[row * C + c] = fmaf(v[i] * rstd, g[c], beta[c]);
   }
 }
 void add_layernorm(hipStream_t st, const float* x, const float* r, long long rows, int C, const float* g,

@@ -75,7 +75,7 @@ struct LcwArgs {   // (compact: the kernel keeps its scalars in SGPRs; a spilled
 };
 
 // DWA: the depthwise half ends in hardswish + LAB (stride 1) or in nothing (stride 2).  The pointwise half always ends in
-// hardswish + LAB (a block without LAB passes a = 1, c = 0).  C_in = 16 G and N = 16 NT exactly: no channel masks.
+// hardswish + LAB (lc_wave_supported() leaves a block without it to k_lc_thin).  C_in = 16 G and N = 16 NT exactly: no channel masks.
 template <int G, int NT, int MT, bool DWA>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) void k_lc_wave(LcwArgs p) {
   constexpr int CP = G * 16, NKC = (CP + KC - 1) / KC, NCOL = NT * 16;
@@ -444,10 +444,16 @@ static int lc_wave_code(int sh, int sw, int Cp, int Npad16) {
 bool lc_wave_supported(int K, int sh, int sw, int Cp, int C, int N, int Npad16, int dw_act, int dw_has_lab, const Epilogue& epi) {
   if (K != 3 || Cp != C || N != Npad16 || lc_wave_code(sh, sw, Cp, Npad16) == 0) return false;
   if (epi.residual || epi.a_scale || epi.am_max || !epi.bias || epi.act != ACT_HSWISH) return false;
+  // the pointwise half always ends in the LAB's fma: with a = 1, c = 0 it would turn the -0 hardswish gives below -3 into +0, one
+  // bit away from k_lc_thin and the unfused pair (tests/test_gpu_rec_kernels.py); every block of the two backbones has the LAB
+  if (!epi.has_lab) return false;
   // depthwise tail: hardswish + LAB (LearnableRepLayer at stride 1) or nothing (stride 2)
   // depthwise tail (LearnableRepLayer: the activation is skipped when stride == 2; the rec net's (2, 1) is not 2)
   return (sh == 2 && sw == 2) ? (dw_act == ACT_NONE && !dw_has_lab) : (dw_act == ACT_HSWISH && dw_has_lab);
 }
+
+// (the direct-load form is kept for the stride-1 blocks only: A/B, RT_LC_WAVE=1)
+bool lc_wave_runs_lds(int sh, int sw, int Cp, int Npad16) { return g_lc_wave >= 3 || lc_wave_code(sh, sw, Cp, Npad16) >= 6; }
 
 void lc_wave(hipStream_t st, int sh, int sw, const float* x, const ImgGeom* gin, const ImgGeom* gout, int n_img, int maxHo,
              int maxWo, int Cp, int C, const float* Wd, const float* bd, int dw_act, int dw_has_lab, float dw_a, float dw_c,
@@ -456,7 +462,7 @@ void lc_wave(hipStream_t st, int sh, int sw, const float* x, const ImgGeom* gin,
   if (!lc_wave_supported(3, sh, sw, Cp, C, N, Npad16, dw_act, dw_has_lab, epi)) throw RtError(8, "lc_wave: unsupported block (check lc_wave_supported)");
   const int code = lc_wave_code(sh, sw, Cp, Npad16);
   const int tpw = 4;   // tiles per wave
-  if (g_lc_wave >= 3 || code >= 6) {   // (the direct-load form below is kept for the stride-1 blocks only: A/B, RT_LC_WAVE=1)
+  if (lc_wave_runs_lds(sh, sw, Cp, Npad16)) {
     // LDS-staged form: 4-row tiles at stride 1 (2 waves per SIMD), 2-row tiles at stride 2
     const int mtl = sh == 1 ? 4 : 2;
     const int tiles = ((maxWo + 15) / 16) * ((maxHo + mtl - 1) / mtl);
