@@ -114,6 +114,19 @@ typedef struct rt_config {
                                  probability and the K - 1 next best classes (rt_results_rec_candidates).  The reference has no
                                  counterpart (rec_processor.rs:155 `// TODO: word_results`).  Off: no extra launch, no extra
                                  workspace.  rt_create rejects other values with RT_ERR_INVALID. */
+  int32_t crop_source;        /* where the text lines are cut from.  0 = Resized (default): from the page after resize_both, as the
+                                 reference does (session.rs:75-106, image_helper.rs:223-249).  1 = Original: line k of a page is
+                                 get_crop_img(the caller's page, rt_results_boxes(page)[k]) -- the page as handed in (or decoded) at
+                                 ori_h x ori_w, and the quad the results report, i.e. after scale_and_clip.  The crop size, the
+                                 rotate270 decision, the homography, the cls / rec ordering by aspect and the running max_wh_ratio
+                                 are all computed from that quad by unchanged arithmetic; detection, DB post-processing, the
+                                 reported boxes and their scores are untouched; word boxes map back through the same homography
+                                 and are scale_and_clip'd with the original size on both sides.  A page resize_both leaves as it
+                                 is gives bit-identical results in both modes.  The crops are warped by a launch over the flat
+                                 list of output pixels (crop area grows with the square of the resize ratio, and differs by
+                                 orders of magnitude between lines).  No reference counterpart (PaddleOCR crops from the image it
+                                 was given).  Applies to every entry point that runs the pipeline.  rt_create rejects other values
+                                 with RT_ERR_INVALID. */
   int32_t rec_return_word_box; /* 0 = off (default), 1 = word boxes (rt_results_rec_words): RecCharacter::decode's
                                  `return_word_box` (rec_processor.rs:48-56), which the reference declares but never implements
                                  (its only caller passes false, :199-206).  Off: no extra launch and no extra workspace.
@@ -164,6 +177,11 @@ RT_API int rt_det_postprocess(rt_session* s, const float* pred, int h, int w, in
 RT_API int rt_crop_dims(const float* boxes, int n, int* ws, int* hs);
 RT_API int rt_crop_images(rt_session* s, const uint8_t* rgb, int h, int w, const float* boxes, int n,
                           uint8_t* out, size_t out_cap);
+/* rt_crop_images with the launch form chosen: form 0 = one grid row per crop, each as long as the largest crop (what
+ * rt_crop_images and crop_source = Resized run), form 1 = the flat list of output pixels (crop_source = Original,
+ * rt_run_regions).  Both run the same per-pixel code: the outputs are equal byte for byte. */
+RT_API int rt_debug_warp_crops(rt_session* s, const uint8_t* rgb, int h, int w, const float* boxes, int n, int form,
+                               uint8_t* out, size_t out_cap);
 RT_API int rt_scale_and_clip(float* boxes, int n, double bitmap_w, double bitmap_h, double ori_w, double ori_h);
 /* a8/a10: one crop -> f32 [3,img_h,W]; W = img_w when max_wh_ratio <= 0 else (int)(img_h*max_wh_ratio). */
 RT_API int rt_resize_norm_width(int img_h, int img_w, float max_wh_ratio);
@@ -214,6 +232,20 @@ typedef struct rt_ticket rt_ticket;
 RT_API int rt_submit_batch(rt_session* s, const uint8_t* const* rgb, const int* hs, const int* ws, int n_pages, int mem,
                            const float* const* det_map_override, rt_ticket** out);
 RT_API int rt_wait_batch(rt_session* s, rt_ticket* ticket, rt_results** out);
+/* The pipeline over regions the caller already knows (form fields, subtitles, corrected boxes, another detector's boxes):
+ * quads[i] = n_quads[i] x 8 floats in host memory, TL, TR, BR, BL of each region in original-page coordinates; mem
+ * (RT_MEM_HOST or RT_MEM_DEVICE) says where the pages live.  Every coordinate is clamped to [0, ori - 1] (no rounding); line k
+ * of page i is get_crop_img(page i, clamped quad k), cut from the page as handed in, whatever rt_config.crop_source says.
+ * resize_both, the det network and DB post-processing do not run; the crop plan, the flat warp, cls, the rec plan, rec and
+ * CTC (word boxes and candidates when configured) are the pipeline's own stages.  Pages are split over the lanes as by
+ * rt_run_batch.  The results object is rt_run_batch's: lines keep the caller's order, rt_results_boxes returns the clamped
+ * quads, rt_results_det_scores is 1.0f for every line, rt_results_det_checksum is 0.
+ * RT_ERR_INVALID, with a message naming the page and the region, and nothing queued: a non-finite coordinate, a clamped quad
+ * whose crop is less than one pixel wide or high, a singular homography, a negative count, NULL quads[i] with n_quads[i] > 0.
+ * Fails like every other call while tickets are in flight.  A crop of more than 2^31 - 1 pixels is RT_ERR_IMAGE, here and in
+ * every other call that plans crops (its pixel count used to overflow the plan's 32-bit arithmetic). */
+RT_API int rt_run_regions(rt_session* s, const uint8_t* const* rgb, const int* hs, const int* ws, int n_pages, int mem,
+                          const float* const* quads, const int* n_quads, rt_results** out);
 RT_API void rt_results_free(rt_results* r);
 RT_API int rt_results_pages(const rt_results* r);
 RT_API int rt_results_count(const rt_results* r, int page);

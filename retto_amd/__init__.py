@@ -124,6 +124,9 @@ class RettoSessionConfig:  # session.rs:17-40
     det_sub_batch: int = 0
     lanes: int = 0
     dtype: str = "f32"   # "f32" (the reference's arithmetic) or "f16" (fp16 storage / MFMA, fp32 accumulation)
+    # rt_config.crop_source: "Resized" (the reference: lines are cut from the page after resize_both) or "Original" (from the page
+    # as handed in, by the boxes the results report; include/retto_hip.h states the rule)
+    crop_source: str = "Resized"
 
 
 # ---- result types (points.rs, processor/*.rs) ---------------------------------------------
@@ -260,6 +263,9 @@ class _Handle:
         if cfg.dtype not in ("f32", "f16"):
             raise InvalidArgument("dtype must be 'f32' or 'f16'")
         c.dtype = 1 if cfg.dtype == "f16" else 0
+        if cfg.crop_source not in ("Resized", "Original"):
+            raise InvalidArgument("crop_source must be 'Resized' or 'Original'")
+        c.crop_source = 1 if cfg.crop_source == "Original" else 0
         h = C.c_void_p()
         _check(lib.rt_create(C.byref(c), C.byref(h)), None)
         self.lib, self.h = lib, h
@@ -442,14 +448,20 @@ class RettoSession:
                                                scores.ctypes.data, max_out, C.byref(n)), self._hd.h)
         return boxes[:n.value].reshape(-1, 4, 2).copy(), scores[:n.value].copy()
 
-    def crop_images(self, img: np.ndarray, boxes: np.ndarray) -> List[np.ndarray]:
+    def crop_images(self, img: np.ndarray, boxes: np.ndarray, form: Optional[int] = None) -> List[np.ndarray]:
+        """rt_crop_images; with form = 0 / 1 rt_debug_warp_crops: the same crops through the launch chosen -- 0 = one grid row
+        per crop (k_warp_crops, what rt_crop_images runs), 1 = the flat pixel list (k_warp_crops_flat)."""
         img = np.ascontiguousarray(img, np.uint8); h, w = img.shape[:2]
         b = np.ascontiguousarray(boxes, np.float32).reshape(-1, 8); n = len(b)
         ws = np.zeros(max(n, 1), np.int32); hs = np.zeros(max(n, 1), np.int32)
         _check(self._hd.lib.rt_crop_dims(b.ctypes.data, n, ws.ctypes.data, hs.ctypes.data), self._hd.h)
         total = int(sum(int(ws[i]) * int(hs[i]) * 3 for i in range(n)))
         out = np.zeros(max(total, 1), np.uint8)
-        _check(self._hd.lib.rt_crop_images(self._hd.h, img.ctypes.data, h, w, b.ctypes.data, n, out.ctypes.data, total), self._hd.h)
+        if form is None:
+            rc = self._hd.lib.rt_crop_images(self._hd.h, img.ctypes.data, h, w, b.ctypes.data, n, out.ctypes.data, total)
+        else:
+            rc = self._hd.lib.rt_debug_warp_crops(self._hd.h, img.ctypes.data, h, w, b.ctypes.data, n, int(form), out.ctypes.data, total)
+        _check(rc, self._hd.h)
         res, o = [], 0
         for i in range(n):
             sz = int(ws[i]) * int(hs[i]) * 3
@@ -473,18 +485,25 @@ class RettoSession:
         return idx, pr, [tok[i, :tn[i]].copy() for i in range(n)], sc
 
     # -- pipeline ---------------------------------------------------------------------------
-    def run_batch_raw(self, pages, hs, ws, mem=RT_MEM_HOST, det_map_override=None, submit=False):
-        """pages: sequence of host arrays or device pointers (ints). Returns an opaque results handle."""
-        lib, h = self._hd.lib, self._hd.h
+    @staticmethod
+    def _page_arrays(pages, hs, ws, keep: list):
+        """the rgb / hs / ws argument arrays of the batch entry points; host arrays that must outlive the call go to keep"""
         n = len(pages)
         arr_p = (C.c_void_p * max(n, 1))(); arr_h = (C.c_int * max(n, 1))(); arr_w = (C.c_int * max(n, 1))()
-        keep = []
         for i, p in enumerate(pages):
             if isinstance(p, np.ndarray):
                 p = np.ascontiguousarray(p, np.uint8); keep.append(p); arr_p[i] = p.ctypes.data
             else:
                 arr_p[i] = int(p)
             arr_h[i], arr_w[i] = int(hs[i]), int(ws[i])
+        return arr_p, arr_h, arr_w
+
+    def run_batch_raw(self, pages, hs, ws, mem=RT_MEM_HOST, det_map_override=None, submit=False):
+        """pages: sequence of host arrays or device pointers (ints). Returns an opaque results handle."""
+        lib, h = self._hd.lib, self._hd.h
+        n = len(pages)
+        keep = []
+        arr_p, arr_h, arr_w = self._page_arrays(pages, hs, ws, keep)
         ov = None
         if det_map_override is not None:
             ov = (C.c_void_p * max(n, 1))()
@@ -561,6 +580,36 @@ class RettoSession:
         pages = [np.ascontiguousarray(p, np.uint8) for p in pages]
         r = self.run_batch_raw(pages, [p.shape[0] for p in pages], [p.shape[1] for p in pages], RT_MEM_HOST,
                                det_map_override)
+        try:
+            self.last_det_checksum = self._hd.lib.rt_results_det_checksum(r)
+            return [self._collect(r, i) for i in range(len(pages))]
+        finally:
+            self._hd.lib.rt_results_free(r)
+
+    def run_regions_raw(self, pages, hs, ws, quads, mem=RT_MEM_HOST):
+        """rt_run_regions.  pages: host arrays or device pointers (ints); quads[i]: the regions of page i, anything that
+        reshapes to [n_i, 8] floats (TL, TR, BR, BL in original-page coordinates).  Returns an opaque results handle."""
+        lib, h = self._hd.lib, self._hd.h
+        n = len(pages)
+        if len(quads) != n:
+            raise InvalidArgument("run_regions: one list of quads per page")
+        keep = []
+        arr_p, arr_h, arr_w = self._page_arrays(pages, hs, ws, keep)
+        arr_q = (C.c_void_p * max(n, 1))(); arr_n = (C.c_int * max(n, 1))()
+        for i in range(n):
+            q = np.ascontiguousarray(quads[i], np.float32).reshape(-1, 8); keep.append(q)
+            arr_q[i] = q.ctypes.data if len(q) else None
+            arr_n[i] = len(q)
+        out = C.c_void_p()
+        _check(lib.rt_run_regions(h, arr_p, arr_h, arr_w, n, mem, arr_q, arr_n, C.byref(out)), h)
+        return out
+
+    def run_regions(self, pages: Sequence[np.ndarray], quads) -> List[RettoWorkerResult]:
+        """The pipeline over regions the caller already knows (rt_run_regions): quads[i] = the [n_i, 4, 2] (or [n_i, 8]) quads
+        of page i in original-page coordinates, TL, TR, BR, BL.  No detector runs; line k of a page is cut from the page as it
+        is by quad k clamped to the page.  det_result holds the clamped quads with score 1.0."""
+        pages = [np.ascontiguousarray(p, np.uint8) for p in pages]
+        r = self.run_regions_raw(pages, [p.shape[0] for p in pages], [p.shape[1] for p in pages], quads)
         try:
             self.last_det_checksum = self._hd.lib.rt_results_det_checksum(r)
             return [self._collect(r, i) for i in range(len(pages))]

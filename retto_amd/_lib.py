@@ -36,7 +36,8 @@ class Config(C.Structure):
         ("cls_image_shape", C.c_int32 * 3), ("cls_batch_num", C.c_int32), ("cls_thresh", C.c_float),
         ("rec_image_shape", C.c_int32 * 3), ("rec_batch_num", C.c_int32),
         ("max_boxes_per_page", C.c_int32), ("det_sub_batch", C.c_int32), ("lanes", C.c_int32), ("dtype", C.c_int32),
-        ("det_score_mode", C.c_int32), ("rec_return_candidates", C.c_int32), ("rec_return_word_box", C.c_int32),
+        ("det_score_mode", C.c_int32), ("rec_return_candidates", C.c_int32), ("crop_source", C.c_int32),
+        ("rec_return_word_box", C.c_int32),
     ]
 
 
@@ -67,6 +68,7 @@ EXPORTS = [
     "rt_onnx_to_rtwb", "rt_buffer_free", "rt_model_manifest", "rt_decode_image", "rt_run_encoded_batch",
     "rt_submit_encoded_batch", "rt_decode_batch", "rt_debug_jpeg_reconstruct",
     "rt_debug_set_variants", "rt_bench_gemm", "rt_bench_gemm_err", "rt_bench_lc", "rt_debug_conv16", "rt_debug_gemm", "rt_debug_dwconv", "rt_debug_attention", "rt_debug_lc_block", "rt_debug_conv13", "rt_debug_layernorm", "rt_parse_dictionary", "rt_format_f32", "rt_rccl_unique_id", "rt_broadcast_blobs",
+    "rt_run_regions", "rt_debug_warp_crops",
 ]
 
 STAGE_CALLBACK = C.CFUNCTYPE(None, C.c_void_p, C.c_int, C.c_int, C.c_char_p)  # rt_stage_callback
@@ -154,6 +156,10 @@ def load():
                                  P(C.c_void_p)]
     lib.rt_submit_batch.argtypes = [C.c_void_p, P(C.c_void_p), P(C.c_int), P(C.c_int), C.c_int, C.c_int, P(C.c_void_p), P(C.c_void_p)]
     lib.rt_wait_batch.argtypes = [C.c_void_p, C.c_void_p, P(C.c_void_p)]
+    lib.rt_run_regions.argtypes = [C.c_void_p, P(C.c_void_p), P(C.c_int), P(C.c_int), C.c_int, C.c_int, P(C.c_void_p), P(C.c_int),
+                                   P(C.c_void_p)]
+    lib.rt_debug_warp_crops.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p,
+                                        C.c_size_t]
     lib.rt_run_batch_stream.argtypes = [C.c_void_p, P(C.c_void_p), P(C.c_int), P(C.c_int), C.c_int, C.c_int, P(C.c_void_p),
                                         STAGE_CALLBACK, C.c_void_p, P(C.c_void_p)]
     lib.rt_profile_get.argtypes = [C.c_void_p, P(P(C.c_char_p)), P(P(C.c_float)), P(P(C.c_int)), P(C.c_int)]

@@ -38,6 +38,9 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--rec-candidates", type=int, default=0, metavar="K",
                     help="RecProcessorConfig.return_candidates: K = 1..8 candidates per token; each --json line gains "
                          "\"candidates\" and \"token_cols\" arrays (per line)")
+    ap.add_argument("--crop-source", choices=["Resized", "Original"], default="Resized",
+                    help="RettoSessionConfig.crop_source: cut the text lines from the page after resize_both (Resized, the "
+                         "reference) or from the page as it was read (Original: small print on pages above max_side_len)")
     return ap
 
 
@@ -66,6 +69,7 @@ def main(argv=None) -> int:
     cfg.det_processor_config.score_mode = a.det_score_mode
     cfg.rec_processor_config.return_word_box = a.rec_return_word_box
     cfg.rec_processor_config.return_candidates = a.rec_candidates
+    cfg.crop_source = a.crop_source
     session = retto_amd.RettoSession(cfg)
     files = walk_files(a.images)
     log.info("Found %d files, processing...", len(files))

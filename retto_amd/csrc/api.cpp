@@ -102,6 +102,7 @@ void rt_config_default(rt_config* c) {
   c->det_score_mode = 0;
   c->rec_return_word_box = 0;
   c->rec_return_candidates = 0;
+  c->crop_source = 0;
 }
 
 int rt_create(const rt_config* cfg, rt_session** out) {
@@ -122,6 +123,7 @@ int rt_create(const rt_config* cfg, rt_session** out) {
              "rec_return_word_box must be 0 (off) or 1 (on)");
   RT_REQUIRE(cfg->rec_return_candidates >= 0 && cfg->rec_return_candidates <= RT_MAX_CANDIDATES, (rt_session*)nullptr,
              "rec_return_candidates must be in [0, 8] (0 = off, K = 1 .. RT_MAX_CANDIDATES)");
+  RT_REQUIRE(cfg->crop_source == 0 || cfg->crop_source == 1, (rt_session*)nullptr, "crop_source must be 0 (Resized) or 1 (Original)");
   capture_variant_defaults();
   return guarded(nullptr, [&] { *out = rt_session_create(cfg); });
 }
@@ -212,6 +214,11 @@ int rt_crop_images(rt_session* s, const uint8_t* rgb, int h, int w, const float*
   RT_REQUIRE(s && rgb && boxes && out && h > 0 && w > 0 && n >= 0, s, "rt_crop_images: bad argument");
   return guarded(s, [&] { s->crop_images(rgb, h, w, boxes, n, out, out_cap); });
 }
+int rt_debug_warp_crops(rt_session* s, const uint8_t* rgb, int h, int w, const float* boxes, int n, int form, uint8_t* out,
+                        size_t out_cap) {
+  RT_REQUIRE(s && rgb && boxes && out && h > 0 && w > 0 && n >= 0 && (form == 0 || form == 1), s, "rt_debug_warp_crops: bad argument");
+  return guarded(s, [&] { s->crop_images(rgb, h, w, boxes, n, out, out_cap, form); });
+}
 int rt_scale_and_clip(float* boxes, int n, double bitmap_w, double bitmap_h, double ori_w, double ori_h) {
   if (!boxes) return RT_ERR_INVALID;
   for (int i = 0; i < n; i++) gm::scale_and_clip(boxes + 8 * i, bitmap_w, bitmap_h, ori_w, ori_h);
@@ -242,6 +249,13 @@ int rt_run_batch_stream(rt_session* s, const uint8_t* const* rgb, const int* hs,
   RT_REQUIRE(mem == RT_MEM_HOST || mem == RT_MEM_DEVICE || mem == RT_MEM_HOST_MAPS_DEVICE, s, "rt_run_batch_stream: bad mem kind");
   *out = nullptr;
   return guarded(s, [&] { *out = s->run_batch(rgb, hs, ws, n_pages, mem, det_map_override, cb, user); });
+}
+int rt_run_regions(rt_session* s, const uint8_t* const* rgb, const int* hs, const int* ws, int n_pages, int mem,
+                   const float* const* quads, const int* n_quads, rt_results** out) {
+  RT_REQUIRE(s && out && n_pages >= 0 && (n_pages == 0 || (rgb && hs && ws && quads && n_quads)), s, "rt_run_regions: bad argument");
+  RT_REQUIRE(mem == RT_MEM_HOST || mem == RT_MEM_DEVICE, s, "rt_run_regions: mem must be RT_MEM_HOST or RT_MEM_DEVICE");
+  *out = nullptr;
+  return guarded(s, [&] { *out = s->run_regions(rgb, hs, ws, n_pages, mem, quads, n_quads); });
 }
 int rt_submit_batch(rt_session* s, const uint8_t* const* rgb, const int* hs, const int* ws, int n_pages, int mem,
                     const float* const* det_map_override, rt_ticket** out) {

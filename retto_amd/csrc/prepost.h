@@ -45,8 +45,14 @@ struct CropDesc {
   float inv[9];                     // output pixel -> source pixel
   int w, h, rot;                    // pre-rotation dims, rotate270 flag
   long long out_off;                // byte offset of this crop in the crop pool
+  long long pix_base;               // output pixels (w * h) of the crops before this one: warp_crops_flat's work list
 };
+// one grid row per crop, each as long as the largest crop (max_pix): the launch for crops of about one size
 void warp_crops(hipStream_t st, const CropDesc* descs, int n, int max_pix, uint8_t* pool);
+// the same crops, byte for byte, walked as one flat list of total_pix = sum of w * h output pixels: ceil(total_pix / 256)
+// workgroups, at most WARP_FLAT_MAX_BLOCKS, which stride over the rest.  A thread finds its crop by binary search over pix_base.
+constexpr int WARP_FLAT_MAX_BLOCKS = 16384;
+void warp_crops_flat(hipStream_t st, const CropDesc* descs, int n, long long total_pix, uint8_t* pool);
 
 // cls_processor.rs:108-121,163-166: argmax of [n,2]; rotate180 in place when label==180 && score>=thresh
 struct CropRef { long long off; int h, w; int pad_; };   // final (post-rotation) dims

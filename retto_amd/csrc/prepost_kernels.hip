@@ -148,10 +148,9 @@ __device__ __forceinline__ u8 clamp_u8_trunc(float x) {
 __device__ __forceinline__ float cubic(float p0, float p1, float p2, float p3, float x) {
   return p1 + 0.5f * x * (p2 - p0 + x * (2.0f * p0 - 5.0f * p1 + 4.0f * p2 - p3 + x * (3.0f * (p1 - p2) + p3 - p0)));
 }
-__global__ __launch_bounds__(256) void k_warp_crops(const CropDesc* __restrict__ descs, u8* __restrict__ pool) {
-  const CropDesc d = descs[blockIdx.y];
-  int p = blockIdx.x * 256 + threadIdx.x;
-  if (p >= d.w * d.h) return;
+// one output pixel p (row-major, pre-rotation dims) of crop d: the whole per-pixel rule -- bicubic taps, white outside the source,
+// clamp_u8_trunc, the rotate270 store.  k_warp_crops and k_warp_crops_flat differ only in how a thread finds (d, p).
+__device__ __forceinline__ void warp_pixel(const CropDesc& d, int p, u8* __restrict__ pool) {
   int y = p / d.w, x = p % d.w;
   float fx = (float)x, fy = (float)y;
   float dd = d.inv[6] * fx + d.inv[7] * fy + d.inv[8];
@@ -180,10 +179,43 @@ __global__ __launch_bounds__(256) void k_warp_crops(const CropDesc* __restrict__
   u8* q = pool + d.out_off + dst * 3;
   q[0] = o[0]; q[1] = o[1]; q[2] = o[2];
 }
+__global__ __launch_bounds__(256) void k_warp_crops(const CropDesc* __restrict__ descs, u8* __restrict__ pool) {
+  const CropDesc d = descs[blockIdx.y];
+  int p = blockIdx.x * 256 + threadIdx.x;
+  if (p >= d.w * d.h) return;
+  warp_pixel(d, p, pool);
+}
 void warp_crops(hipStream_t st, const CropDesc* descs, int n, int max_pix, uint8_t* pool) {
   if (n <= 0 || max_pix <= 0) return;
   for (int y0 = 0; y0 < n; y0 += RT_MAX_GRID_Y)  // one grid row per crop: chunked to the gridDim.y limit
     RT_LAUNCH(k_warp_crops, dim3((max_pix + 255) / 256, std::min(n - y0, RT_MAX_GRID_Y)), dim3(256), 0, st, descs + y0, pool);
+}
+
+// The same crops as one flat list of output pixels: pixel g of the call belongs to the last crop whose pix_base <= g (pix_base
+// is the host's prefix sum of w * h; every crop has at least one pixel, so the bases strictly increase).  The grid follows the
+// total, not n x the largest crop: crops cut from an unshrunk page differ in size by orders of magnitude.
+__device__ inline int find_crop(const CropDesc* descs, int n, long long g) {
+  int lo = 0, hi = n - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (descs[mid].pix_base <= g) lo = mid; else hi = mid - 1;
+  }
+  return lo;
+}
+__global__ __launch_bounds__(256) void k_warp_crops_flat(const CropDesc* __restrict__ descs, int n, long long total,
+                                                         u8* __restrict__ pool) {
+  for (long long g = (long long)blockIdx.x * 256 + threadIdx.x; g < total; g += (long long)gridDim.x * 256) {
+    const CropDesc& d = descs[find_crop(descs, n, g)];
+    const long long p = g - d.pix_base;
+    if (p >= (long long)d.w * d.h) continue;   // (a descriptor table whose bases do not match its sizes writes nothing)
+    warp_pixel(d, (int)p, pool);
+  }
+}
+void warp_crops_flat(hipStream_t st, const CropDesc* descs, int n, long long total_pix, uint8_t* pool) {
+  if (n <= 0 || total_pix <= 0) return;
+  const long long want = (total_pix + 255) / 256;
+  const int grid = (int)std::min<long long>(want, WARP_FLAT_MAX_BLOCKS);
+  RT_LAUNCH(k_warp_crops_flat, dim3(grid), dim3(256), 0, st, descs, n, total_pix, pool);
 }
 
 // cls_processor.rs:108-121 (first-max argmax) + :163-166 rotate_180_in_place

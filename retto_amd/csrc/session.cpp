@@ -435,24 +435,30 @@ struct CropPlan {
   std::vector<gm::CropDims> dims;   // per crop: what the word boxes map back through (cw, ch)
   size_t pool_bytes = 0;
   int max_pix = 0;
+  long long total_pix = 0;          // sum of w * h: the flat warp's work list (CropDesc::pix_base is its prefix sum)
 };
-// image_helper.rs:223-249 planning for one box b[8] of a page (src = device page after resize_both)
+// image_helper.rs:223-249 planning for one box b[8] of a page (src = the device page the crop is cut from: the page after
+// resize_both, or the caller's page with crop_source = Original and in rt_run_regions; b in that page's coordinates)
 static void plan_crop(CropPlan& plan, const uint8_t* src, int sh, int sw, const float* b) {
   gm::CropDims d = gm::crop_dims(b);
   if (d.w <= 0 || d.h <= 0) throw RtError(RT_ERR_IMAGE, "zero-sized crop");
+  if ((long long)d.w * d.h > 0x7fffffffLL) throw RtError(RT_ERR_IMAGE, "crop of more than 2^31 pixels");
   pp::CropDesc cd;
   cd.src = src; cd.sh = sh; cd.sw = sw; cd.w = d.w; cd.h = d.h; cd.rot = d.rot;
   if (!gm::projection_inverse(b, d.cw, d.ch, cd.inv))
     throw RtError(RT_ERR_IMAGE, "singular crop homography (Projection::from_control_points -> None; the reference unwraps)");
   cd.out_off = (long long)plan.pool_bytes;
+  cd.pix_base = plan.total_pix;
   pp::CropRef r; r.off = cd.out_off; r.h = d.rot ? d.w : d.h; r.w = d.rot ? d.h : d.w; r.pad_ = 0;
   plan.descs.push_back(cd); plan.refs.push_back(r); plan.dims.push_back(d);
   plan.pool_bytes += ((size_t)d.w * d.h * 3 + 63) & ~(size_t)63;
   plan.max_pix = std::max(plan.max_pix, d.w * d.h);
+  plan.total_pix += (long long)d.w * d.h;
 }
 // a6: the plan's descriptors and crop refs to the device through pinned staging, then every crop warped into one pool (returned;
-// *d_refs: the refs on the device, what cls_post_rotate reads).  The plan holds at least one crop.
-static uint8_t* warp_planned_crops(rt_session& s, const CropPlan& plan, pp::CropRef** d_refs) {
+// *d_refs: the refs on the device, what cls_post_rotate reads).  The plan holds at least one crop.  flat: the launch walks the
+// flat pixel list (crops of very different sizes: original-page crops, caller-supplied regions) instead of one grid row per crop.
+static uint8_t* warp_planned_crops(rt_session& s, const CropPlan& plan, pp::CropRef** d_refs, bool flat) {
   const int n = (int)plan.descs.size();
   uint8_t* pool = s.arena.alloc<uint8_t>(plan.pool_bytes + 64);
   pp::CropDesc* d_desc = s.arena.alloc<pp::CropDesc>(n);
@@ -464,11 +470,12 @@ static uint8_t* warp_planned_crops(rt_session& s, const CropPlan& plan, pp::Crop
   RT_HIP_CHECK(hipMemcpyAsync(d_desc, hd, (size_t)n * sizeof(pp::CropDesc), hipMemcpyHostToDevice, s.st));
   RT_HIP_CHECK(hipMemcpyAsync(*d_refs, hr, (size_t)n * sizeof(pp::CropRef), hipMemcpyHostToDevice, s.st));
   ProfScope ps(&s.prof, s.st, "warp_crops");
-  pp::warp_crops(s.st, d_desc, n, plan.max_pix, pool);
+  if (flat) pp::warp_crops_flat(s.st, d_desc, n, plan.total_pix, pool);
+  else pp::warp_crops(s.st, d_desc, n, plan.max_pix, pool);
   return pool;
 }
 
-void rt_session::crop_images(const uint8_t* rgb, int h, int w, const float* boxes, int n, uint8_t* out, size_t out_cap) {
+void rt_session::crop_images(const uint8_t* rgb, int h, int w, const float* boxes, int n, uint8_t* out, size_t out_cap, int form) {
   begin_call();
   uint8_t* d = arena.alloc<uint8_t>((size_t)h * w * 3);
   RT_HIP_CHECK(hipMemcpyAsync(d, rgb, (size_t)h * w * 3, hipMemcpyHostToDevice, st));
@@ -479,7 +486,7 @@ void rt_session::crop_images(const uint8_t* rgb, int h, int w, const float* boxe
   if (need > out_cap) throw RtError(RT_ERR_INVALID, "crop_images: output buffer too small");
   if (n > 0) {
     pp::CropRef* d_refs;
-    const uint8_t* pool = warp_planned_crops(*this, plan, &d_refs);
+    const uint8_t* pool = warp_planned_crops(*this, plan, &d_refs, form == 1);
     for (const pp::CropRef& r : plan.refs) {
       const size_t bytes = (size_t)r.h * r.w * 3;
       RT_HIP_CHECK(hipMemcpyAsync(out, pool + r.off, bytes, hipMemcpyDeviceToHost, st));
@@ -590,11 +597,12 @@ std::string fnum(float v) {
 // ---------------------------------------------------------------------------
 struct PageState {
   int ori_h, ori_w, after_h, after_w, det_h, det_w;
+  const uint8_t* raw;      // device, the caller's page (ori_h x ori_w): what crop_source = Original and the regions are cut from
   const uint8_t* img;      // device, after resize_both
   const uint8_t* det_img;  // device, det input size (RGB8: the det stem normalises it)
   const float* map;        // device det map used for boxes
   int n_boxes = 0; int first_line = 0;
-  const pp::DbBox* boxes = nullptr;  // pinned: the page's part of round trip #1
+  const pp::DbBox* boxes = nullptr;  // pinned: the page's part of round trip #1 (regions: the caller's clamped quads, host)
 };
 // per-line results: views of one [4][NLp] block of 32-bit words (label first), so that one copy brings them to the host
 struct LineMeta {
@@ -605,6 +613,9 @@ struct LineMeta {
 struct Pipeline {
   int n_pages, mem; const float* const* det_map_override;
   std::vector<PageState> pg;
+  const rt_session::Regions* regions = nullptr;   // rt_run_regions: the boxes are the caller's, in original-page coordinates
+  std::vector<pp::DbBox> region_boxes;            // ... as the stages read them (score 1)
+  bool crop_original = false;                     // crops are planned on PageState::raw (regions, or crop_source = Original)
   std::vector<double*> sum_parts; std::vector<int> sum_counts;   // det map checksum partials per det group (device)
   int* d_counts = nullptr;                  // [n_pages][2]: box count, overflow flag
   pp::DbBox* d_boxes_packed = nullptr;      // every page's boxes, packed in page order
@@ -631,26 +642,30 @@ int group_end(int g0, int n, int max_items, long long budget_px, PxOf px_of) {
   return g1;
 }
 // a page's boxes (after_* coordinates) to original-image corners, and their scores (session.rs:94-105)
-void page_boxes(const PageState& p, rt_results::Page& P) {
+// (regions: the quads are reported as they were clamped, unrounded)
+void page_boxes(const PageState& p, rt_results::Page& P, bool regions) {
   P.boxes.resize((size_t)p.n_boxes * 8); P.det_scores.resize((size_t)p.n_boxes);
   for (int k = 0; k < p.n_boxes; k++) {
     memcpy(&P.boxes[8 * k], p.boxes[k].pts, 32);
-    gm::scale_and_clip(&P.boxes[8 * k], (double)p.after_w, (double)p.after_h, (double)p.ori_w, (double)p.ori_h);
+    if (!regions) gm::scale_and_clip(&P.boxes[8 * k], (double)p.after_w, (double)p.after_h, (double)p.ori_w, (double)p.ori_h);
     P.det_scores[k] = p.boxes[k].score;
   }
+}
+// page i of the call in HBM: the caller's device pointer, or an upload
+const uint8_t* page_on_device(rt_session& s, const Pipeline& P, const uint8_t* const* rgb, const int* hs, const int* ws, int i) {
+  if (hs[i] <= 0 || ws[i] <= 0 || rgb[i] == nullptr) throw RtError(RT_ERR_IMAGE, "empty page");
+  if (P.mem != RT_MEM_HOST && P.mem != RT_MEM_HOST_MAPS_DEVICE) return rgb[i];
+  // the pages cross PCIe here (a submitted batch staged them already)
+  uint8_t* d = s.arena.alloc<uint8_t>((size_t)hs[i] * ws[i] * 3);
+  RT_HIP_CHECK(hipMemcpyAsync(d, rgb[i], (size_t)hs[i] * ws[i] * 3, hipMemcpyHostToDevice, s.st));
+  return d;
 }
 // ---- a2 + a3: size limits, det resize (the normalise is folded into the det stem) ----
 void page_sizes(rt_session& s, Pipeline& P, const uint8_t* const* rgb, const int* hs, const int* ws) {
   for (int i = 0; i < P.n_pages; i++) {
     PageState& p = P.pg[i];
     p.ori_h = hs[i]; p.ori_w = ws[i];
-    if (hs[i] <= 0 || ws[i] <= 0 || rgb[i] == nullptr) throw RtError(RT_ERR_IMAGE, "empty page");
-    const uint8_t* raw = rgb[i];
-    if (P.mem == RT_MEM_HOST || P.mem == RT_MEM_HOST_MAPS_DEVICE) {   // the pages cross PCIe here (a submitted batch staged them already)
-      uint8_t* d = s.arena.alloc<uint8_t>((size_t)hs[i] * ws[i] * 3);
-      RT_HIP_CHECK(hipMemcpyAsync(d, rgb[i], (size_t)hs[i] * ws[i] * 3, hipMemcpyHostToDevice, s.st));
-      raw = d;
-    }
+    const uint8_t* raw = p.raw = page_on_device(s, P, rgb, hs, ws, i);
     p.img = dev_resize_both(&s, raw, hs[i], ws[i], &p.after_h, &p.after_w);
     if (p.after_h <= 0 || p.after_w <= 0) throw RtError(RT_ERR_SHAPE, "page collapses to zero size in resize_both");
     gm::resize_either_dims(p.after_h, p.after_w, s.cfg.det_limit_type, s.cfg.det_limit_side_len, &p.det_h, &p.det_w);
@@ -752,13 +767,45 @@ void box_round_trip(rt_session& s, Pipeline& P, rt_results& res) {
   P.NL = total_lines; P.NLp = std::max(total_lines, 1);
   P.tok_off.assign((size_t)P.NL + 1, 0);
   if (s.stage_cb)  // run_stream: the Det stage is complete here (session.rs:98)
-    for (int i = 0; i < n; i++) { rt_results::Page page; page_boxes(P.pg[i], page); s.emit_stage(i, 0, page); }
+    for (int i = 0; i < n; i++) { rt_results::Page page; page_boxes(P.pg[i], page, false); s.emit_stage(i, 0, page); }
+}
+// ---- rt_run_regions: instead of a2 .. a5 and round trip #1 -- the pages as they are, the boxes from the caller ----
+void region_pages(rt_session& s, Pipeline& P, const uint8_t* const* rgb, const int* hs, const int* ws) {
+  int total_lines = 0;
+  for (int i = 0; i < P.n_pages; i++) total_lines += P.regions->n_quads[i];
+  P.region_boxes.resize((size_t)total_lines);
+  total_lines = 0;
+  for (int i = 0; i < P.n_pages; i++) {
+    PageState& p = P.pg[i];
+    p.ori_h = p.after_h = hs[i]; p.ori_w = p.after_w = ws[i]; p.det_h = p.det_w = 0;
+    p.n_boxes = P.regions->n_quads[i]; p.first_line = total_lines;
+    p.raw = p.img = p.n_boxes > 0 ? page_on_device(s, P, rgb, hs, ws, i) : nullptr;   // (a page without regions is never read)
+    p.det_img = nullptr; p.map = nullptr;
+    for (int k = 0; k < p.n_boxes; k++) {
+      pp::DbBox& b = P.region_boxes[(size_t)total_lines + k];
+      memcpy(b.pts, P.regions->quads[i] + 8 * k, 32); b.score = 1.0f; b.key = 0;
+    }
+    p.boxes = P.region_boxes.data() + total_lines;
+    total_lines += p.n_boxes;
+  }
+  P.NL = total_lines; P.NLp = std::max(total_lines, 1);
+  P.tok_off.assign((size_t)P.NL + 1, 0);
 }
 // ---- a6: crop plan over every page's boxes, the crops warped when there are any ----
+// Resized (the reference): box k in after-resize_both coordinates, cut from the resized page.  Original / regions: the quad the
+// results report (page_boxes: after scale_and_clip, or the caller's clamped quad), cut from the caller's page; everything
+// downstream reads the plan, so the crop size, rotate270, the homography and the cls / rec ordering follow that quad.
 void crop_stage(rt_session& s, Pipeline& P) {
-  for (const PageState& p : P.pg)
-    for (int k = 0; k < p.n_boxes; k++) plan_crop(P.plan, p.img, p.after_h, p.after_w, p.boxes[k].pts);
-  if (P.NL > 0) P.pool = warp_planned_crops(s, P.plan, &P.d_refs);
+  for (const PageState& p : P.pg) {
+    if (!P.crop_original) {
+      for (int k = 0; k < p.n_boxes; k++) plan_crop(P.plan, p.img, p.after_h, p.after_w, p.boxes[k].pts);
+      continue;
+    }
+    rt_results::Page B;
+    page_boxes(p, B, P.regions != nullptr);
+    for (int k = 0; k < p.n_boxes; k++) plan_crop(P.plan, p.raw, p.ori_h, p.ori_w, &B.boxes[8 * (size_t)k]);
+  }
+  if (P.NL > 0) P.pool = warp_planned_crops(s, P.plan, &P.d_refs, P.crop_original);
 }
 // ---- a8 + a9: angle classifier over every crop --------------------------------------
 // (cls_processor.rs:127-172: batches of 6 sorted by aspect; the classifier is per-crop independent, so batch composition does
@@ -921,7 +968,7 @@ void results(const rt_session& s, const Pipeline& P, rt_results& res) {
     rt_results::Page& R = res.pages[i];
     const PageState& p = P.pg[i];
     int nb = p.n_boxes;
-    page_boxes(p, R);
+    page_boxes(p, R, P.regions != nullptr);
     R.cls_labels.resize(nb); R.cls_scores.resize(nb); R.rec_scores.resize(nb); R.tokens.resize(nb); R.text.resize(nb);
     for (int k = 0; k < nb; k++) {
       int li = p.first_line + k;
@@ -951,8 +998,10 @@ void results(const rt_session& s, const Pipeline& P, rt_results& res) {
         std::vector<wb::Word>& W = R.words[k];
         W.assign(P.h_words + P.tok_off[li], P.h_words + P.tok_off[li] + nw);
         R.word_text[k].resize((size_t)nw);
+        // (crops planned on the original page: the homography already maps to original coordinates)
+        const double bw = P.crop_original ? (double)p.ori_w : (double)p.after_w, bh = P.crop_original ? (double)p.ori_h : (double)p.after_h;
         for (int j = 0; j < nw; j++) {
-          gm::scale_and_clip(W[j].quad, (double)p.after_w, (double)p.after_h, (double)p.ori_w, (double)p.ori_h);
+          gm::scale_and_clip(W[j].quad, bw, bh, (double)p.ori_w, (double)p.ori_h);
           std::string& t = R.word_text[k][(size_t)j];
           for (int q = W[j].first_token; q < W[j].first_token + W[j].n_tokens; q++) t += s.dict[(size_t)R.tokens[k][(size_t)q]];
         }
@@ -964,7 +1013,7 @@ void results(const rt_session& s, const Pipeline& P, rt_results& res) {
 std::string rt_format_f32_impl(float v) { return fnum(v); }
 
 rt_results* rt_session::run_pages(const uint8_t* const* rgb, const int* hs, const int* ws, int n_pages, int mem,
-                                  const float* const* det_map_override) {
+                                  const float* const* det_map_override, const Regions* regions) {
   if (g_trace) fprintf(stderr, "[rt host] %-28s %8.3f ms\n", "between calls", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - last_exit).count());
   HostTick tick0;
   // a one-page call is the reference's real mode (retto-cli/src/main.rs:80-86): it polls through its waits; a multi-page batch
@@ -979,11 +1028,17 @@ rt_results* rt_session::run_pages(const uint8_t* const* rgb, const int* hs, cons
   res->pages.resize((size_t)n_pages);
   if (n_pages == 0) return res.release();
   Pipeline P{n_pages, mem, det_map_override, std::vector<PageState>((size_t)n_pages)};
-  page_sizes(*this, P, rgb, hs, ws);
-  HostTick tick; tick.lap("pre (resize, upload)");
-  det_groups(*this, P); tick.lap("det enqueue");
-  db_post(*this, P); tick.lap("dbpost enqueue");
-  box_round_trip(*this, P, *res); tick.lap("sync #1 + box D2H");
+  P.regions = regions; P.crop_original = regions != nullptr || cfg.crop_source == 1;
+  HostTick tick;
+  if (regions) {   // the boxes are given: no resize_both, no detector, no DB post-processing, no first round trip
+    region_pages(*this, P, rgb, hs, ws); tick.lap("pre (upload, regions)");
+  } else {
+    page_sizes(*this, P, rgb, hs, ws);
+    tick.lap("pre (resize, upload)");
+    det_groups(*this, P); tick.lap("det enqueue");
+    db_post(*this, P); tick.lap("dbpost enqueue");
+    box_round_trip(*this, P, *res); tick.lap("sync #1 + box D2H");
+  }
   crop_stage(*this, P);
   if (P.NL > 0) {
     tick.lap("crop plan + warp enqueue");
@@ -1221,13 +1276,14 @@ void rt_session::free_stage() {
 
 rt_ticket* rt_session::submit_batch(const uint8_t* const* rgb, const int* hs, const int* ws, int n_pages, int mem,
                                     const float* const* det_map_override, rt_stage_callback cb, void* user,
-                                    std::vector<rt::EncodedPage>* enc) {
+                                    std::vector<rt::EncodedPage>* enc, const Regions* regions) {
   ensure_workers();
   std::unique_ptr<rt_ticket> t(new rt_ticket());
   const int nl = std::max(1, std::min<int>(std::min<int>((int)helpers.size() + 1, active_lanes), std::max(n_pages, 1)));
   t->nl = nl; t->n_pages = n_pages; t->mem = mem; t->cb = cb; t->user = user;
   t->rgb.assign(rgb, rgb + n_pages); t->hs.assign(hs, hs + n_pages); t->ws.assign(ws, ws + n_pages);
   if (det_map_override) t->maps.assign(det_map_override, det_map_override + n_pages);
+  if (regions) { t->quads.assign(regions->quads, regions->quads + n_pages); t->n_quads.assign(regions->n_quads, regions->n_quads + n_pages); }
   t->parts.assign((size_t)nl, nullptr); t->errs.resize((size_t)nl); t->first.assign((size_t)nl + 1, 0);
   {
     // contiguous ranges of about equal work: det pixels after the session size limit (a2) plus a constant per page
@@ -1277,8 +1333,10 @@ rt_ticket* rt_session::submit_batch(const uint8_t* const* rgb, const int* hs, co
       s->on_lane_worker = true;
       try {
         if (!tp->ev_up.empty()) RT_HIP_CHECK(hipStreamWaitEvent(s->st, tp->ev_up[(size_t)l], 0));
+        Regions rg{nullptr, nullptr};
+        if (!tp->quads.empty()) rg = Regions{tp->quads.data() + f0, tp->n_quads.data() + f0};
         tp->parts[l] = s->run_pages(tp->rgb.data() + f0, tp->hs.data() + f0, tp->ws.data() + f0, f1 - f0, tp->mem_lane,
-                                    tp->maps.empty() ? nullptr : tp->maps.data() + f0);
+                                    tp->maps.empty() ? nullptr : tp->maps.data() + f0, tp->quads.empty() ? nullptr : &rg);
       } catch (...) {
         tp->errs[l] = std::current_exception();
         s->failed = true;
@@ -1348,6 +1406,45 @@ rt_results* rt_session::run_batch(const uint8_t* const* rgb, const int* hs, cons
     } catch (...) { failed = true; throw; }
   }
   return wait_batch(submit_batch(rgb, hs, ws, n_pages, mem, det_map_override, cb, user));
+}
+
+// rt_run_regions.  A quad is clamped to the page, then held to what the crop plan needs: a crop of at least 1 x 1 pixels and an
+// invertible homography -- checked here, for every page, before anything is queued.
+rt_results* rt_session::run_regions(const uint8_t* const* rgb, const int* hs, const int* ws, int n_pages, int mem,
+                                    const float* const* quads, const int* n_quads) {
+  std::vector<std::vector<float>> clamped((size_t)n_pages);
+  std::vector<const float*> qp((size_t)n_pages, nullptr);
+  for (int i = 0; i < n_pages; i++) {
+    const std::string where = "rt_run_regions: page " + std::to_string(i);
+    if (hs[i] <= 0 || ws[i] <= 0 || rgb[i] == nullptr) throw RtError(RT_ERR_IMAGE, where + ": empty page");
+    if (n_quads[i] < 0) throw RtError(RT_ERR_INVALID, where + ": negative region count");
+    if (n_quads[i] > 0 && quads[i] == nullptr) throw RtError(RT_ERR_INVALID, where + ": NULL quads with a positive region count");
+    std::vector<float>& q = clamped[(size_t)i];
+    q.resize((size_t)n_quads[i] * 8);
+    const float mx = (float)(ws[i] - 1), my = (float)(hs[i] - 1);
+    for (int k = 0; k < n_quads[i]; k++) {
+      const std::string at = where + " region " + std::to_string(k);
+      float* b = q.data() + 8 * (size_t)k;
+      for (int j = 0; j < 8; j++) {
+        const float v = quads[i][8 * (size_t)k + j], hi = (j & 1) ? my : mx;
+        if (!std::isfinite(v)) throw RtError(RT_ERR_INVALID, at + ": non-finite coordinate");
+        b[j] = v < 0.0f ? 0.0f : (v > hi ? hi : v);
+      }
+      const gm::CropDims d = gm::crop_dims(b);
+      if (d.w < 1 || d.h < 1) throw RtError(RT_ERR_INVALID, at + ": the crop is smaller than one pixel");
+      float inv[9];
+      if (!gm::projection_inverse(b, d.cw, d.ch, inv)) throw RtError(RT_ERR_INVALID, at + ": singular homography (degenerate quad)");
+    }
+    qp[(size_t)i] = q.data();
+  }
+  const Regions rg{qp.data(), n_quads};
+  const int nl = std::max(1, std::min<int>(std::min<int>((int)helpers.size() + 1, active_lanes), std::max(n_pages, 1)));
+  if (nl <= 1) {   // one lane: on the caller's thread, as run_batch
+    try {
+      return run_pages(rgb, hs, ws, n_pages, mem, nullptr, &rg);
+    } catch (...) { failed = true; throw; }
+  }
+  return wait_batch(submit_batch(rgb, hs, ws, n_pages, mem, nullptr, nullptr, nullptr, nullptr, &rg));   // (clamped outlives the wait)
 }
 
 // RettoWorkerStageResult JSON (serde derive shapes; retto-wasm/fe/index.ts:5-42)

@@ -67,6 +67,10 @@ struct rt_ticket {
   std::vector<const uint8_t*> rgb;
   std::vector<int> hs, ws;
   std::vector<const float*> maps;   // empty: no override
+  // rt_run_regions: per page its quads (already validated and clamped, owned by the caller of submit_batch) and their number;
+  // empty: the detector finds the boxes
+  std::vector<const float*> quads;
+  std::vector<int> n_quads;
   std::vector<int> first;
   std::vector<rt_results*> parts;
   std::vector<std::exception_ptr> errs;
@@ -149,7 +153,8 @@ struct rt_session {
   void det_preprocess(const uint8_t* rgb, int h, int w, float* out);
   void det_postprocess(const float* pred, int h, int w, int ori_h, int ori_w, float* boxes, float* scores, int max_out,
                        int* n_out);
-  void crop_images(const uint8_t* rgb, int h, int w, const float* boxes, int n, uint8_t* out, size_t out_cap);
+  // form 0: pp::warp_crops (one grid row per crop), 1: pp::warp_crops_flat (rt_debug_warp_crops compares the two)
+  void crop_images(const uint8_t* rgb, int h, int w, const float* boxes, int n, uint8_t* out, size_t out_cap, int form = 0);
   void resize_norm_image(const uint8_t* crop, int h, int w, int ori_h, int ori_w, int img_h, int img_w, float ratio,
                          float* out);
   void ctc_decode(const float* probs, int n, int t, int c, int32_t* idx, float* prob, int32_t* tokens,
@@ -177,16 +182,22 @@ struct rt_session {
   void release_stage(rt_ticket* t);
   void free_stage();
   void ensure_workers();
+  // regions (rt_run_regions): quads[i] = n_quads[i] x 8 validated, clamped floats of page i, valid until the ticket is waited for
+  struct Regions { const float* const* quads; const int* n_quads; };
   rt_ticket* submit_batch(const uint8_t* const* rgb, const int* hs, const int* ws, int n_pages, int mem,
                           const float* const* det_map_override, rt_stage_callback cb = nullptr, void* user = nullptr,
-                          std::vector<rt::EncodedPage>* enc = nullptr);
+                          std::vector<rt::EncodedPage>* enc = nullptr, const Regions* regions = nullptr);
   // rt_decode_batch: pages through the host stage and the reconstruction kernels into out[i] (mem: RT_MEM_HOST / RT_MEM_DEVICE)
   void decode_batch(std::vector<rt::EncodedPage>& enc, uint8_t* const* out, int mem);
   rt_results* wait_batch(rt_ticket* t);   // consumes the ticket
   rt_results* run_batch(const uint8_t* const* rgb, const int* hs, const int* ws, int n_pages, int mem,
                         const float* const* det_map_override, rt_stage_callback cb = nullptr, void* user = nullptr);
   rt_results* run_pages(const uint8_t* const* rgb, const int* hs, const int* ws, int n_pages, int mem,
-                        const float* const* det_map_override);  // one lane
+                        const float* const* det_map_override, const Regions* regions = nullptr);  // one lane
+  // rt_run_regions: checks and clamps every quad (RT_ERR_INVALID naming page and region; nothing is queued then), then the
+  // pages go over the lanes as run_batch's do, from the crop plan on
+  rt_results* run_regions(const uint8_t* const* rgb, const int* hs, const int* ws, int n_pages, int mem,
+                          const float* const* quads, const int* n_quads);
 };
 
 rt_session* rt_session_create(const rt_config* cfg);
