@@ -500,6 +500,51 @@ RT_API int rt_debug_conv13(rt_session* s, const float* x, long long rows, int ld
  * [rows][C], g, beta [C].  out [(rows + 64) * C], filled with RT_DEBUG_CANARY before the launch and returned whole. */
 RT_API int rt_debug_layernorm(rt_session* s, const float* x, const float* r, long long rows, int C, const float* g,
                               const float* beta, float eps, float* out);
+/* One launch of a glue kernel of the fp16 family on host arrays, for the numerics tests.  n_img source images of src_h[i] x
+ * src_w[i] pixels and n_img destination images of dst_h[i] x dst_w[i] pixels, each list consecutive in its buffer as the
+ * networks' levels are.  All host arrays are float32 and hold whole buffers, row by row; the entry converts to and from fp16 (and to
+ * bytes for op 11) where the kernel's operand is one.  ip[0] = channels processed (C or Cp), ip[1] = source pitch, ip[2] = source
+ * channel offset, ip[3] = destination pitch, ip[4] = destination channel offset; ip[5 .. 11] and fp[0 .. 6] per op:
+ *    0 dwconv16          x [ps][ip1] -> out; ip5.. = K, sh, sw, act, has_lab; fp = lab_a, lab_c; tab = w [K * K][C] then bias [C]
+ *    1 global_mean16     x [ps][ip1] -> fp32 out [n_img][C] (ip3 = C)
+ *    2 gate16            fp32 x [n_img][ip1] -> fp32 out [n_img][ip3]; ip0 = C, ip3 = Cp, ip5 = residual; fp0 = slope (< 0: sigmoid)
+ *    3 scale_channels16  ip5 = the residual's pitch (0: none; x2 [ps][ip5]), ip6 = its channel offset, ip7 = in place (the output
+ *                        buffer starts as x and is also read); tab = scale [n_img][C]
+ *    4 upsample_add16    x = b [ps][C] (low resolution), x2 = a [pd][C]; ip5 = in place on a, ip6 = tab holds scale_a [n_img][C]
+ *    5 upsample_into16   ip5 = shift, ip6 = the scale table's pitch (0: no scale); tab = scale [n_img][ip6]
+ *    6 maxpool16         ip5.. = kh, kw, sh, sw, ph, pw
+ *    7 avgpool16         ip5.. = kh, kw (window = stride; dst * k <= src)
+ *    8 pixel_shuffle16   x [ps][ip1] holding 4 * C channels from ip2 on; dst <= 2 * src
+ *    9 deconv_to_map16   x = f [ps][ip1], tab = w [C][4], fp0 = b -> fp32 out [pd] (ip3 = 1); dst = 2 * src
+ *   10 map_window16      fp32 x = map [ps] (ip0 = 16, ip1 = 1), src = the map's images, dst = the feature images; 16 channels at ip4
+ *   11 u8_to_h8          x [ps][3] byte values (ip0 = 8, ip1 = 3, ip3 = 8); fp0 = scale, fp1..3 = mean, fp4..6 = std; page i is
+ *                        written from the first pixel of destination image i (dst pixels >= src pixels)
+ *   12 f32x4_to_h8       fp32 x [ps][4] -> out [ps][8] (ip0 = 8, ip1 = 4, ip3 = 8)
+ *   13 h_to_f32, 14 f32_to_h   x [ps][ip1] -> out [ps][ip3] at channel offset ip4, C = ip0 channels
+ * ps / pd = the pixels of all source / destination images.  out [(rows + 64) * pitch] (rows = pd, or ps / n_img as above) is
+ * filled with RT_DEBUG_CANARY before the launch and returned whole; for fp16 outputs every 32-bit canary word is two halves,
+ * returned converted like the rest.  x_len, x2_len, tab_len, out_len = the arrays' lengths in floats: everything the kernel
+ * can address is checked against them before any device work. */
+RT_API int rt_debug_glue16(rt_session* s, int op, const int* ip, const float* fp, const int* src_h, const int* src_w,
+                           const int* dst_h, const int* dst_w, int n_img, const float* x, long long x_len, const float* x2,
+                           long long x2_len, const float* tab, long long tab_len, float* out, long long out_len);
+/* One nh::conv16 launch as the fp16 networks issue it, on host arrays, for the numerics tests.  n_img images of heights[i] x
+ * widths[i] pixels, consecutive in x as a level is; the output images follow the networks' rule (ceil(side / stride); the input
+ * geometry for the 2x2 phase convs).  ip[20] = cin, ldx, xoff (the input is channels [xoff, xoff + cin) of rows of pitch ldx),
+ * cout, ldy, coff (the output goes to channels [coff, coff + pitch8(cout)) of rows of pitch ldy), kh, kw, sh, sw, pt, pl (-1 = k / 2),
+ * flat (1: one image of 1 x total pixels, as the 1x1 layers are launched), act, has_lab, ld_res, res_off (the residual is
+ * res [pixels][ld_res] from channel res_off on; res may be NULL), in_place (the output buffer starts as x and is the input
+ * too; ldx == ldy), dot_py, dot_px.  fp[3] = lab_a, lab_c, dot_b.  wt [cout][cin][kh][kw], bias [cout] or NULL.  All host arrays
+ * are float32; fp16 operands are converted.  out [(pixels_out + 64) * ldy] is filled with RT_DEBUG_CANARY (two halves a word)
+ * before the launch and returned whole.  With dot_w [cout] (the PFHeadLocal phase convs: 2x2, pads 0 / 1, 33 .. 64 output
+ * channels) nothing is stored: out [4 * pixels + 64] holds the fp32 map at twice the resolution on entry (its 64 spare floats
+ * are overwritten with the canary), map[(2y + dot_py, 2x + dot_px)] = 0.5 * (map + sigmoid(dot_b + sum_n act(conv)[n] dot_w[n]))
+ * is applied and the map is returned whole.  route_out receives the kernel that ran: 1 = k_conv16, 2 = k_conv16v2, 3 = k_gemm16p,
+ * + 8 for an instance with the dot epilogue.  The two fp16 entries check their arguments before they look at the session, so
+ * that each check answers with its own message (rt_last_error(NULL)) even where no session can be created. */
+RT_API int rt_debug_conv16x(rt_session* s, const int* ip, const float* fp, const int* heights, const int* widths, int n_img,
+                            const float* x, long long x_len, const float* wt, long long wt_len, const float* bias, const float* res,
+                            long long res_len, const float* dot_w, float* out, long long out_len, int* route_out);
 /* times the fused thin LCNetV3 block (3x3 depthwise -> 1x1 conv; n images of h x w, random data).  form: 0 = k_lc_thin
  * (workgroup-staged; the unfused depthwise + GEMM pair where it has no instance), 1 = k_lc_wave (direct loads, stride 1 only),
  * 3 = k_lc_lds (production).  stride: 1, 2, or 21 = (2, 1).  Returns the average ms and the max |diff| against form 0. */

@@ -77,6 +77,14 @@ struct DevBufs {
   template <typename T> T* alloc(size_t n) { void* q = nullptr; RT_HIP_CHECK(hipMalloc(&q, std::max<size_t>(n, 1) * sizeof(T))); p.push_back(q); return (T*)q; }
   ~DevBufs() { for (void* q : p) (void)hipFree(q); }
 };
+// a host float array on the device as T (the debug entries take float32 and convert)
+template <typename T> T* upload_as(DevBufs& bufs, const float* src, size_t n) {
+  std::vector<T> h(std::max<size_t>(n, 1));
+  for (size_t i = 0; i < n; i++) h[i] = (T)src[i];
+  T* d = bufs.alloc<T>(n);
+  RT_HIP_CHECK(hipMemcpy(d, h.data(), n * sizeof(T), hipMemcpyHostToDevice));
+  return d;
+}
 struct ForgetSplit { const float* w; ~ForgetSplit() { nn::gemm_split_forget(w); } };
 struct Events { hipEvent_t a = nullptr, b = nullptr; ~Events() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); } };
 }  // namespace
@@ -1184,6 +1192,271 @@ RT_API int rt_debug_layernorm(rt_session* s, const float* x, const float* r, lon
     nn::add_layernorm(s->st, dx, dr, rows, C, dg, db, eps, dy);
     RT_HIP_CHECK(hipStreamSynchronize(s->st));
     RT_HIP_CHECK(hipMemcpy(out, dy, nout * sizeof(float), hipMemcpyDeviceToHost));
+  });
+}
+
+// One launch of a glue kernel of the fp16 family (nn_f16.hip) on host arrays, for tests/test_gpu_f16_kernels.py: ragged source
+// and destination image lists laid out as the networks' levels are, operands given as the rows of the buffers the networks
+// pass (so views into concat buffers are a pitch and a channel offset), the output buffer canary-filled with 64 spare rows.
+// Everything a kernel may address is checked against the lengths the caller gives before any device work.
+namespace {
+enum Glue16Op { G16_DWCONV = 0, G16_GLOBAL_MEAN, G16_GATE, G16_SCALE_CHANNELS, G16_UPSAMPLE_ADD, G16_UPSAMPLE_INTO, G16_MAXPOOL,
+                G16_AVGPOOL, G16_PIXEL_SHUFFLE, G16_DECONV_TO_MAP, G16_MAP_WINDOW, G16_U8_TO_H8, G16_F32X4_TO_H8, G16_H_TO_F32,
+                G16_F32_TO_H, G16_COUNT };
+}  // namespace
+RT_API int rt_debug_glue16(rt_session* s, int op, const int* ip, const float* fp, const int* src_h, const int* src_w,
+                           const int* dst_h, const int* dst_w, int n_img, const float* x, long long x_len, const float* x2,
+                           long long x2_len, const float* tab, long long tab_len, float* out, long long out_len) {
+  using nh::half_t;
+  // (the session is looked at last: without a device there is none, and the argument checks can still be told apart by their messages)
+  RT_REQUIRE(ip && fp && src_h && src_w && dst_h && dst_w && x && out, s, "rt_debug_glue16: null argument");
+  RT_REQUIRE(op >= 0 && op < G16_COUNT && n_img > 0 && n_img <= 4096, s, "rt_debug_glue16: bad op or image count");
+  const int C = ip[0], ldx = ip[1], xoff = ip[2], ldy = ip[3], yoff = ip[4];
+  RT_REQUIRE(C > 0 && C <= 4096 && ldx > 0 && ldx <= 8192 && ldy > 0 && ldy <= 8192 && xoff >= 0 && yoff >= 0, s, "rt_debug_glue16: bad channel counts");
+  std::vector<ImgGeom> gs(n_img), gd(n_img);
+  long long ps = 0, pd = 0, max_s = 0, max_d = 0;
+  int maxHd = 0, maxWd = 0;
+  for (int i = 0; i < n_img; i++) {
+    RT_REQUIRE(src_h[i] > 0 && src_w[i] > 0 && dst_h[i] > 0 && dst_w[i] > 0 && src_h[i] < 32768 && src_w[i] < 32768 && dst_h[i] < 32768 && dst_w[i] < 32768,
+               s, "rt_debug_glue16: empty or oversized image");
+    gs[i] = ImgGeom{ps, src_h[i], src_w[i], 0}; gd[i] = ImgGeom{pd, dst_h[i], dst_w[i], 0};
+    const long long a = (long long)src_h[i] * src_w[i], b = (long long)dst_h[i] * dst_w[i];
+    ps += a; pd += b; max_s = std::max(max_s, a); max_d = std::max(max_d, b);
+    maxHd = std::max(maxHd, dst_h[i]); maxWd = std::max(maxWd, dst_w[i]);
+  }
+  RT_REQUIRE(ps * ldx < (1ll << 28) && pd * ldy < (1ll << 28), s, "rt_debug_glue16: too large");
+  // what the op reads and writes: x / x2 / tab lengths in floats, the output's rows, pitch and type
+  const bool vec = op != G16_GATE && op != G16_H_TO_F32 && op != G16_F32_TO_H;   // 16-byte vectors of 8 halves
+  bool x_half = true, out_half = true, in_place = false;
+  long long x_need = ps * ldx, x2_need = 0, tab_need = 0, out_rows = pd;
+  int out_ld = ldy, c_read = C, c_write = C;
+  bool ok = true;
+  switch (op) {
+    case G16_DWCONV: {
+      const int K = ip[5], sh = ip[6], sw = ip[7];
+      ok = (K == 3 || K == 5) && sh >= 1 && sh <= 2 && sw >= 1 && sw <= 2 && ip[8] >= ACT_NONE && ip[8] <= ACT_SIGMOID;
+      for (int i = 0; ok && i < n_img; i++) ok = dst_h[i] == (src_h[i] + sh - 1) / sh && dst_w[i] == (src_w[i] + sw - 1) / sw;
+      tab_need = ok ? (long long)(K * K + 1) * C : 0;
+    } break;
+    case G16_GLOBAL_MEAN: out_half = false; out_rows = n_img; ok = ldy == C && yoff == 0; break;
+    case G16_GATE: x_half = false; out_half = false; x_need = (long long)n_img * ldx; out_rows = n_img; c_write = ldy; ok = ldy >= C && yoff == 0 && (ip[5] == 0 || ip[5] == 1); break;
+    case G16_SCALE_CHANNELS:
+      in_place = ip[7] != 0; tab_need = (long long)n_img * C;
+      ok = ip[5] >= 0 && ip[5] <= 8192 && ip[5] % 8 == 0 && ip[6] >= 0 && ip[6] % 8 == 0 && (ip[5] == 0 || ip[6] + C <= ip[5]) && (!in_place || ldx == ldy);
+      for (int i = 0; ok && i < n_img; i++) ok = dst_h[i] == src_h[i] && dst_w[i] == src_w[i];
+      x2_need = ps * ip[5];
+      break;
+    case G16_UPSAMPLE_ADD:
+      in_place = ip[5] != 0; tab_need = ip[6] ? (long long)n_img * C : 0; x2_need = pd * C;
+      ok = ldx == C && ldy == C && xoff == 0 && yoff == 0;
+      break;
+    case G16_UPSAMPLE_INTO: ok = ip[5] >= 0 && ip[5] <= 3 && (ip[6] == 0 || (ip[6] >= C && ip[6] <= 8192)); tab_need = (long long)n_img * ip[6]; break;
+    case G16_MAXPOOL:
+      ok = ip[5] >= 1 && ip[5] <= 5 && ip[6] >= 1 && ip[6] <= 5 && ip[7] >= 1 && ip[7] <= 4 && ip[8] >= 1 && ip[8] <= 4 && ip[9] >= 0 && ip[9] < ip[5] && ip[10] >= 0 && ip[10] < ip[6];
+      break;
+    case G16_AVGPOOL:   // (window = stride, no padding: the kernel reads every tap unchecked)
+      ok = ip[5] >= 1 && ip[5] <= 8 && ip[6] >= 1 && ip[6] <= 8;
+      for (int i = 0; ok && i < n_img; i++) ok = (long long)dst_h[i] * ip[5] <= src_h[i] && (long long)dst_w[i] * ip[6] <= src_w[i];
+      break;
+    case G16_PIXEL_SHUFFLE:
+      c_read = 4 * C;
+      for (int i = 0; ok && i < n_img; i++) ok = dst_h[i] <= 2 * src_h[i] && dst_w[i] <= 2 * src_w[i];
+      break;
+    case G16_DECONV_TO_MAP:
+      out_half = false; out_ld = 1; c_write = 1; tab_need = 4ll * C; ok = ldy == 1 && yoff == 0;
+      for (int i = 0; ok && i < n_img; i++) ok = dst_h[i] == 2 * src_h[i] && dst_w[i] == 2 * src_w[i];
+      break;
+    case G16_MAP_WINDOW: x_half = false; x_need = ps; c_read = 1; c_write = 16; ok = ldx == 1 && xoff == 0 && C == 16; break;
+    case G16_U8_TO_H8:
+      x_half = false; x_need = ps * 3; c_read = 3; c_write = 8; ok = ldx == 3 && xoff == 0 && ldy == 8 && yoff == 0 && C == 8;
+      for (int i = 0; ok && i < n_img; i++) ok = (long long)dst_h[i] * dst_w[i] >= (long long)src_h[i] * src_w[i];
+      break;
+    case G16_F32X4_TO_H8: x_half = false; x_need = ps * 4; c_read = 4; c_write = 8; out_rows = ps; ok = ldx == 4 && xoff == 0 && ldy == 8 && yoff == 0 && C == 8; break;
+    case G16_H_TO_F32: out_half = false; out_rows = ps; break;
+    case G16_F32_TO_H: x_half = false; out_rows = ps; break;
+  }
+  RT_REQUIRE(ok, s, "rt_debug_glue16: bad parameters for the op");
+  RT_REQUIRE(xoff + c_read <= ldx && yoff + c_write <= out_ld, s, "rt_debug_glue16: the channel window leaves the row");
+  RT_REQUIRE(!vec || ((!x_half || (ldx % 8 == 0 && xoff % 8 == 0)) && (!out_half || (out_ld % 8 == 0 && yoff % 8 == 0)) && C % 8 == 0),
+             s, "rt_debug_glue16: channel counts, pitches and offsets must be multiples of 8");
+  const long long out_n = (out_rows + 64) * out_ld;
+  RT_REQUIRE(x_len >= x_need && out_len == out_n, s, "rt_debug_glue16: x is too short or out has the wrong length");
+  RT_REQUIRE((x2_need == 0 || (x2 && x2_len >= x2_need)) && (tab_need == 0 || (tab && tab_len >= tab_need)), s, "rt_debug_glue16: x2 or tab is missing or too short");
+  RT_REQUIRE(s, s, "rt_debug_glue16: null session");
+  return guarded(s, [&] {
+    RT_HIP_CHECK(hipSetDevice(s->device));
+    DevBufs bufs;
+    hipStream_t st = s->st;
+    ImgGeom *dgs = bufs.alloc<ImgGeom>(n_img), *dgd = bufs.alloc<ImgGeom>(n_img);
+    RT_HIP_CHECK(hipMemcpy(dgs, gs.data(), n_img * sizeof(ImgGeom), hipMemcpyHostToDevice));
+    RT_HIP_CHECK(hipMemcpy(dgd, gd.data(), n_img * sizeof(ImgGeom), hipMemcpyHostToDevice));
+    void* dout = out_half ? (void*)bufs.alloc<half_t>((size_t)out_n + 1) : (void*)bufs.alloc<float>((size_t)out_n);
+    RT_HIP_CHECK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(dout), (int)RT_DEBUG_CANARY, out_half ? (size_t)(out_n + 1) / 2 : (size_t)out_n, st));
+    RT_HIP_CHECK(hipStreamSynchronize(st));   // (the copies below are not ordered with the stream)
+    half_t* yh = (half_t*)dout; float* yf = (float*)dout;
+    const float* first = in_place ? (op == G16_UPSAMPLE_ADD ? x2 : x) : nullptr;   // the operand that is also the output
+    if (first) {
+      const size_t n = (size_t)(op == G16_UPSAMPLE_ADD ? x2_need : x_need);
+      std::vector<half_t> h(n);
+      for (size_t i = 0; i < n; i++) h[i] = (half_t)first[i];
+      RT_HIP_CHECK(hipMemcpy(dout, h.data(), n * sizeof(half_t), hipMemcpyHostToDevice));
+    }
+    const half_t* xh = nullptr; const float* xf = nullptr;
+    if (op == G16_U8_TO_H8) {}
+    else if (in_place && op == G16_SCALE_CHANNELS) xh = yh;
+    else if (x_half) xh = upload_as<half_t>(bufs, x, (size_t)x_need);
+    else xf = upload_as<float>(bufs, x, (size_t)x_need);
+    const half_t* x2h = nullptr;
+    if (x2_need) x2h = (in_place && op == G16_UPSAMPLE_ADD) ? yh : upload_as<half_t>(bufs, x2, (size_t)x2_need);
+    const float* dtab = (tab_need && op != G16_DWCONV) ? upload_as<float>(bufs, tab, (size_t)tab_need) : nullptr;
+    switch (op) {
+      case G16_DWCONV: {
+        const int K = ip[5];
+        const half_t* dw = upload_as<half_t>(bufs, tab, (size_t)K * K * C);
+        const float* db = upload_as<float>(bufs, tab + (size_t)K * K * C, (size_t)C);
+        nh::dwconv16(st, K, ip[6], ip[7], xh + xoff, ldx, dgs, dgd, n_img, maxHd, maxWd, C, dw, db, ip[8], ip[9], fp[0], fp[1], yh + yoff, ldy);
+      } break;
+      case G16_GLOBAL_MEAN: {
+        float* partial = bufs.alloc<float>((size_t)n_img * nh::pool_chunks16(max_s) * C);
+        nh::global_mean16(st, xh + xoff, ldx, dgs, n_img, max_s, C, partial, yf);
+      } break;
+      case G16_GATE: nh::gate16(st, xf + xoff, ldx, n_img, C, ldy, fp[0], ip[5], yf); break;
+      case G16_SCALE_CHANNELS:
+        nh::scale_channels16(st, xh + xoff, ldx, dgs, n_img, max_s, C, dtab, ip[5] ? x2h + ip[6] : nullptr, ip[5], yh + yoff, ldy);
+        break;
+      case G16_UPSAMPLE_ADD: nh::upsample_add16(st, x2h, xh, dgd, dgs, n_img, max_d, C, yh, ip[6] ? dtab : nullptr); break;
+      case G16_UPSAMPLE_INTO: nh::upsample_into16(st, xh + xoff, ldx, dgs, dgd, n_img, max_d, C, ip[5], yh, ldy, yoff, ip[6] ? dtab : nullptr, ip[6]); break;
+      case G16_MAXPOOL: nh::maxpool16(st, xh + xoff, ldx, dgs, dgd, n_img, max_d, C, ip[5], ip[6], ip[7], ip[8], ip[9], ip[10], yh + yoff, ldy); break;
+      case G16_AVGPOOL: nh::avgpool16(st, xh + xoff, ldx, dgs, dgd, n_img, max_d, C, ip[5], ip[6], yh + yoff, ldy); break;
+      case G16_PIXEL_SHUFFLE: nh::pixel_shuffle16(st, xh + xoff, ldx, dgs, dgd, n_img, max_d, C, yh, ldy, yoff); break;
+      case G16_DECONV_TO_MAP: nh::deconv_to_map16(st, xh + xoff, ldx, dgs, dgd, n_img, max_s, C, dtab, fp[0], yf); break;
+      case G16_MAP_WINDOW: nh::map_window16(st, xf, dgs, dgd, n_img, max_d, yh, ldy, yoff); break;
+      case G16_U8_TO_H8: {
+        const uint8_t* d8 = upload_as<uint8_t>(bufs, x, (size_t)x_need);
+        std::vector<nh::U8Page16> pages(n_img);
+        for (int i = 0; i < n_img; i++) pages[i] = nh::U8Page16{d8 + gs[i].off * 3, (long long)gs[i].H * gs[i].W, gd[i].off};
+        nh::U8Page16* dp = bufs.alloc<nh::U8Page16>(n_img);
+        RT_HIP_CHECK(hipMemcpy(dp, pages.data(), n_img * sizeof(nh::U8Page16), hipMemcpyHostToDevice));
+        nh::u8_to_h8(st, dp, n_img, max_s, fp[0], fp + 1, fp + 4, yh);
+      } break;
+      case G16_F32X4_TO_H8: nh::f32x4_to_h8(st, xf, ps, yh); break;
+      case G16_H_TO_F32: nh::h_to_f32(st, xh + xoff, ldx, ps, C, yf, ldy, yoff); break;
+      case G16_F32_TO_H: nh::f32_to_h(st, xf + xoff, ldx, ps, C, yh, ldy, yoff); break;
+    }
+    RT_HIP_CHECK(hipStreamSynchronize(st));
+    if (out_half) {
+      std::vector<half_t> h((size_t)out_n);
+      RT_HIP_CHECK(hipMemcpy(h.data(), dout, (size_t)out_n * sizeof(half_t), hipMemcpyDeviceToHost));
+      for (size_t i = 0; i < (size_t)out_n; i++) out[i] = (float)h[i];
+    } else {
+      RT_HIP_CHECK(hipMemcpy(out, dout, (size_t)out_n * sizeof(float), hipMemcpyDeviceToHost));
+    }
+  });
+}
+
+// One nh::conv16 launch as the fp16 networks issue it, on host arrays, for tests/test_gpu_f16_kernels.py: a ragged image list
+// (or its flat view, one image of 1 x total pixels, as conv_pw16 launches the 1x1 layers), the input as the channel window
+// [xoff, xoff + cin) of rows of pitch ldx, the output at (ldy, coff) of a canary-filled buffer with 64 spare rows -- the same
+// buffer as the input when in_place, as run_hg_block reads and writes one concat -- and the whole epilogue: bias, activation,
+// LAB, a residual with its own pitch, or the dot epilogue of the PFHeadLocal phase convs, which updates the fp32 map `out` holds
+// on entry.  route_out receives the nh::Conv16Route of the launch.  Like rt_debug_glue16 it looks at its session last.
+//   ip[20]: cin, ldx, xoff, cout, ldy, coff, kh, kw, sh, sw, pt, pl (-1 = k / 2), flat, act, has_lab, ld_res, res_off, in_place,
+//           dot_py, dot_px;  fp[3]: lab_a, lab_c, dot_b;  wt [cout][cin][kh][kw];  bias [cout] or NULL;  dot_w [cout] or NULL
+RT_API int rt_debug_conv16x(rt_session* s, const int* ip, const float* fp, const int* heights, const int* widths, int n_img,
+                            const float* x, long long x_len, const float* wt, long long wt_len, const float* bias, const float* res,
+                            long long res_len, const float* dot_w, float* out, long long out_len, int* route_out) {
+  using nh::half_t;
+  RT_REQUIRE(ip && fp && heights && widths && x && wt && out && route_out, s, "rt_debug_conv16x: null argument");
+  RT_REQUIRE(n_img > 0 && n_img <= 4096, s, "rt_debug_conv16x: bad image count");
+  const int cin = ip[0], ldx = ip[1], xoff = ip[2], cout = ip[3], ldy = ip[4], coff = ip[5], kh = ip[6], kw = ip[7], sh = ip[8], sw = ip[9];
+  const int flat = ip[12], act = ip[13], has_lab = ip[14], ld_res = ip[15], res_off = ip[16], in_place = ip[17], py = ip[18], px = ip[19];
+  const bool dot = dot_w != nullptr, k22 = kh == 2 && kw == 2;
+  RT_REQUIRE(cin > 0 && cin <= 4096 && cout > 0 && cout <= 4096 && ldx > 0 && ldx <= 8192 && xoff >= 0 && xoff + cin <= ldx, s,
+             "rt_debug_conv16x: bad channel counts");
+  RT_REQUIRE(cin % 8 == 0 && ldx % 8 == 0 && xoff % 8 == 0, s, "rt_debug_conv16x: input channels, pitch and offset must be multiples of 8");
+  const int cop = nh::pitch8(cout), npad = round_up(cout, 32);
+  RT_REQUIRE(dot || (ldy > 0 && ldy <= 8192 && coff >= 0 && ldy % 8 == 0 && coff % 8 == 0 && coff + cop <= ldy), s,
+             "rt_debug_conv16x: the output window must be 8-aligned and lie within its row");
+  // the kernel forms the networks launch: odd kernels with "same" padding and strides 1 / 2, 1x1 over the flat view, and the
+  // 2x2 phase convs (stride 1, pads 0 / 1, dot epilogue on the instance that holds all 64 channels)
+  const int pt = ip[10] < 0 ? kh / 2 : ip[10], pl = ip[11] < 0 ? kw / 2 : ip[11];
+  bool ok = sh >= 1 && sh <= 2 && sw >= 1 && sw <= 2 && act >= ACT_NONE && act <= ACT_SIGMOID && (flat == 0 || flat == 1) &&
+            (in_place == 0 || in_place == 1) && (has_lab == 0 || has_lab == 1);
+  if (k22) ok = ok && dot && sh == 1 && sw == 1 && pt >= 0 && pt <= 1 && pl >= 0 && pl <= 1 && npad == 64 && cin >= 32 && !flat && (py == 0 || py == 1) && (px == 0 || px == 1);
+  else ok = ok && !dot && kh >= 1 && kh <= 9 && kw >= 1 && kw <= 9 && (kh & 1) && (kw & 1) && pt == kh / 2 && pl == kw / 2;
+  if (flat) ok = ok && kh == 1 && kw == 1 && sh == 1 && sw == 1;
+  RT_REQUIRE(ok, s, "rt_debug_conv16x: no such launch in the fp16 networks");
+  std::vector<ImgGeom> gi(n_img), go(n_img), gm(n_img);
+  long long pin = 0, pout = 0, pmap = 0;
+  int maxHo = 0, maxWo = 0;
+  for (int i = 0; i < n_img; i++) {
+    RT_REQUIRE(heights[i] > 0 && widths[i] > 0 && heights[i] < 16384 && widths[i] < 16384, s, "rt_debug_conv16x: empty or oversized image");
+    const int ho = k22 ? heights[i] : (heights[i] - 1) / sh + 1, wo = k22 ? widths[i] : (widths[i] - 1) / sw + 1;
+    gi[i] = ImgGeom{pin, heights[i], widths[i], 0}; go[i] = ImgGeom{pout, ho, wo, 0}; gm[i] = ImgGeom{pmap, 2 * ho, 2 * wo, 0};
+    pin += (long long)heights[i] * widths[i]; pout += (long long)ho * wo; pmap += 4ll * ho * wo;
+    maxHo = std::max(maxHo, ho); maxWo = std::max(maxWo, wo);
+  }
+  RT_REQUIRE(pin * ldx < (1ll << 28) && pout * std::max(ldy, 1) < (1ll << 28) && pin < (1ll << 24), s, "rt_debug_conv16x: too large");
+  int n_launch = n_img;
+  if (flat) { gi.assign(1, ImgGeom{0, 1, (int)pin, 0}); go = gi; n_launch = 1; maxHo = 1; maxWo = (int)pin; }
+  RT_REQUIRE(!in_place || (!dot && ldx == ldy && pin == pout), s, "rt_debug_conv16x: in place needs one pitch and one geometry");
+  const long long out_n = dot ? pmap + 64 : (pout + 64) * ldy;
+  RT_REQUIRE(x_len >= pin * ldx && wt_len == (long long)cout * cin * kh * kw && out_len == out_n, s,
+             "rt_debug_conv16x: x is too short, or wt or out has the wrong length");
+  RT_REQUIRE(!res || (!dot && ld_res > 0 && ld_res <= 8192 && ld_res % 8 == 0 && res_off >= 0 && res_off % 8 == 0 && res_off + cop <= ld_res &&
+                      res_len >= pout * ld_res), s, "rt_debug_conv16x: the residual is misaligned, leaves its row or is too short");
+  RT_REQUIRE(s, s, "rt_debug_conv16x: null session");
+  return guarded(s, [&] {
+    RT_HIP_CHECK(hipSetDevice(s->device));
+    DevBufs bufs;
+    hipStream_t st = s->st;
+    ImgGeom *dgi = bufs.alloc<ImgGeom>(gi.size()), *dgo = bufs.alloc<ImgGeom>(go.size()), *dgm = bufs.alloc<ImgGeom>(gm.size());
+    RT_HIP_CHECK(hipMemcpy(dgi, gi.data(), gi.size() * sizeof(ImgGeom), hipMemcpyHostToDevice));
+    RT_HIP_CHECK(hipMemcpy(dgo, go.data(), go.size() * sizeof(ImgGeom), hipMemcpyHostToDevice));
+    RT_HIP_CHECK(hipMemcpy(dgm, gm.data(), gm.size() * sizeof(ImgGeom), hipMemcpyHostToDevice));
+    // weights as upload_conv16 packs them: [ceil(cin / 32)][kh][kw][npad][32] halves; bias and dot weights zero beyond cout
+    const int nslab = (cin + nh::KS - 1) / nh::KS;
+    std::vector<half_t> hw((size_t)nslab * kh * kw * npad * nh::KS, (half_t)0.f);
+    for (int n = 0; n < cout; n++)
+      for (int k = 0; k < cin; k++)
+        for (int t = 0; t < kh * kw; t++)
+          hw[(((size_t)(k / nh::KS) * kh * kw + t) * npad + n) * nh::KS + k % nh::KS] = (half_t)wt[((size_t)n * cin + k) * kh * kw + t];
+    half_t* dw = bufs.alloc<half_t>(hw.size());
+    RT_HIP_CHECK(hipMemcpy(dw, hw.data(), hw.size() * sizeof(half_t), hipMemcpyHostToDevice));
+    std::vector<float> hb(npad, 0.f), hd(npad, 0.f);
+    if (bias) memcpy(hb.data(), bias, (size_t)cout * sizeof(float));
+    if (dot) memcpy(hd.data(), dot_w, (size_t)cout * sizeof(float));
+    const float *db = upload_as<float>(bufs, hb.data(), hb.size()), *dd = upload_as<float>(bufs, hd.data(), hd.size());
+    void* dout = dot ? (void*)bufs.alloc<float>((size_t)out_n) : (void*)bufs.alloc<half_t>((size_t)out_n + 1);
+    RT_HIP_CHECK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(dout), (int)RT_DEBUG_CANARY, dot ? (size_t)out_n : (size_t)(out_n + 1) / 2, st));
+    RT_HIP_CHECK(hipStreamSynchronize(st));   // (the copies below are not ordered with the stream)
+    half_t* yh = (half_t*)dout;
+    const half_t* xh;
+    if (in_place) {
+      std::vector<half_t> h((size_t)(pin * ldx));
+      for (size_t i = 0; i < h.size(); i++) h[i] = (half_t)x[i];
+      RT_HIP_CHECK(hipMemcpy(dout, h.data(), h.size() * sizeof(half_t), hipMemcpyHostToDevice));
+      xh = yh;
+    } else {
+      xh = upload_as<half_t>(bufs, x, (size_t)(pin * ldx));
+    }
+    if (dot) RT_HIP_CHECK(hipMemcpy(dout, out, (size_t)pmap * sizeof(float), hipMemcpyHostToDevice));
+    nh::Epi16 e; e.bias = db; e.act = act; e.has_lab = has_lab;
+    if (has_lab) { e.lab_a = fp[0]; e.lab_c = fp[1]; }
+    if (res) { e.residual = upload_as<half_t>(bufs, res, (size_t)(pout * ld_res)) + res_off; e.ld_res = ld_res; }
+    if (dot) { e.dot_w = dd; e.dot_b = fp[2]; e.dot_map = (float*)dout; e.gmap = dgm; e.dot_py = py; e.dot_px = px; }
+    nh::g_conv16_route = nh::CONV16_ROUTE_NONE;
+    nh::conv16(st, xh + xoff, ldx, dgi, dgo, n_launch, maxHo, maxWo, cin, kh, kw, sh, sw, pt, pl, dw, cout, npad, dot ? nullptr : yh + 0,
+               dot ? 8 : ldy, dot ? 0 : coff, e);
+    *route_out = nh::g_conv16_route;
+    RT_HIP_CHECK(hipStreamSynchronize(st));
+    if (dot) {
+      RT_HIP_CHECK(hipMemcpy(out, dout, (size_t)out_n * sizeof(float), hipMemcpyDeviceToHost));
+    } else {
+      std::vector<half_t> h((size_t)out_n);
+      RT_HIP_CHECK(hipMemcpy(h.data(), dout, (size_t)out_n * sizeof(half_t), hipMemcpyDeviceToHost));
+      for (size_t i = 0; i < (size_t)out_n; i++) out[i] = (float)h[i];
+    }
   });
 }
 

@@ -307,7 +307,7 @@ float* DetNetH::forward(RunCtx& c, H16 x, Level& L0) {
     conv_sp16(c, inp_[j], in[j], *tap_lv[j], *tap_lv[j], 1, 1, p, 0, epi16(inp_[j], ACT_NONE));
     float* sc = se16(c, inp_se_[j], p, *tap_lv[j], HSIG_MBV3, 1);
     ProfScope ps(c.prof, c.st, "fpn_concat16");
-    nh::upsample_into16(c.st, p.p, p.ld, tap_lv[j]->d, L4.d, L4.n(), L4.maxPix, 24, j, fuse.p, fuse.ld, (3 - j) * 24, sc);  // order p5, p4, p3, p2
+    nh::upsample_into16(c.st, p.p, p.ld, tap_lv[j]->d, L4.d, L4.n(), L4.maxPix, 24, j, fuse.p, fuse.ld, (3 - j) * 24, sc, pitch8(24));  // order p5, p4, p3, p2
   }
   H16 h1 = alloc16(c, L4, 24);
   conv_sp16(c, head_conv1_, fuse, L4, L4, 1, 1, h1, 0, epi16(head_conv1_, ACT_RELU));
@@ -709,7 +709,7 @@ float* DetServerH::forward(RunCtx& c, H16 x, Level& L0) {
       H16 q = alloc16(c, L, 64);
       conv_pw16(c, I.ret, r1, *fl[j], q, 0, epi16(I.ret, ACT_RELU, nullptr, p.p, p.ld));
       ProfScope ps(c.prof, c.st, "fpn_concat16");
-      nh::upsample_into16(c.st, q.p, q.ld, L.d, L4.d, L4.n(), L4.maxPix, 64, j, fuse.p, fuse.ld, (3 - j) * 64, nullptr);  // order p5, p4, p3, p2
+      nh::upsample_into16(c.st, q.p, q.ld, L.d, L4.d, L4.n(), L4.maxPix, 64, j, fuse.p, fuse.ld, (3 - j) * 64, nullptr, pitch8(64));  // order p5, p4, p3, p2
     }
   }
   // ---- PFHeadLocal ----

@@ -50,6 +50,9 @@ void conv16(hipStream_t st, const half_t* x, int ldx, const ImgGeom* gin, const 
 const char* conv16_label(int KH, int KW, int N, int Cin = 32);
 bool conv_stamps_compiled();   // true in a `make STAMPS=1` build
 extern long long* g_conv_stamps;  // diagnostics: when set, one workgroup of every conv16 launch records s_memtime per stage
+// diagnostics: the kernel the last conv16 call launched (host side, written by conv16 / conv16_dma, read by rt_debug_conv16x)
+enum Conv16Route { CONV16_ROUTE_NONE = 0, CONV16_ROUTE_CONV16 = 1, CONV16_ROUTE_CONV16V2 = 2, CONV16_ROUTE_GEMM16P = 3, CONV16_ROUTE_DOT = 8 };
+extern int g_conv16_route;   // one of the first four, | CONV16_ROUTE_DOT for an instance with the dot epilogue
 
 // Depthwise KxK (K odd), stride (sh, sw), pad K/2.  Wd packed [K*K][Cp] halves, bias fp32 [Cp].
 void dwconv16(hipStream_t st, int K, int sh, int sw, const half_t* x, int ldx, const ImgGeom* gin, const ImgGeom* gout, int n_img,
@@ -69,19 +72,14 @@ void h_to_f32(hipStream_t st, const half_t* src, int lds, long long rows, int C,
 void f32_to_h(hipStream_t st, const float* src, int lds, long long rows, int C, half_t* dst, int ldd, int coff);
 
 // ---- squeeze-excite / ESE -------------------------------------------------------------------------------------------
-// Deterministic two-stage spatial mean, then: hid = relu(w1t . mean + b1) (skipped when w1t == null: hid = mean, Cr = C),
-// s = w2t . hid + b2, gate = hardsigmoid(slope) or sigmoid (slope < 0), + 1 when residual.  w1t [C][Cr], w2t [Cr][C]
-// (transposed so that consecutive threads read consecutive floats).  scale: fp32 [n_img][Cp].
+// (the FCs between the mean and the gate run as nn::gemm over all images of a level: rows = images)
 int pool_chunks16(long long max_pix);
-void se_scale16(hipStream_t st, const half_t* x, int ldx, const ImgGeom* geom, int n_img, long long max_pix, int C, int Cp, const float* w1t,
-                const float* b1, const float* w2t, const float* b2, int Cr, float slope, int residual, float* partial,
-                float* scale);
 // gate of a squeeze-excite: scale[img][c] = hardsigmoid(slope) or sigmoid (slope < 0) of s[img][c] (pitch lds), + 1 when residual
 void gate16(hipStream_t st, const float* s, int lds, int n_img, int C, int Cp, float slope, int residual, float* scale);
 // y = x * scale[image] (+ res); in place allowed; x / res / y have their own channel pitches (views into concat buffers)
 void scale_channels16(hipStream_t st, const half_t* x, int ldx, const ImgGeom* geom, int n_img, long long max_pix, int Cp, const float* scale,
                       const half_t* res, int ldr, half_t* y, int ldy);
-// global mean only: out fp32 [n_img][Cp]
+// deterministic two-stage spatial mean: out fp32 [n_img][Cp]; partial: fp32 [n_img][pool_chunks16(max_pix)][Cp] of scratch
 void global_mean16(hipStream_t st, const half_t* x, int ldx, const ImgGeom* geom, int n_img, long long max_pix, int Cp, float* partial,
                    float* out);
 
@@ -89,18 +87,15 @@ void global_mean16(hipStream_t st, const half_t* x, int ldx, const ImgGeom* geom
 // out = a * scale_a[image] + nearest_up2(b)   (scale_a optional; in place on a allowed)
 void upsample_add16(hipStream_t st, const half_t* a, const half_t* b, const ImgGeom* ga, const ImgGeom* gb, int n_img,
                     long long max_pix, int Cp, half_t* out, const float* scale_a);
-// dst[pix][coff .. coff + C) = src[pix >> shift][0 .. C) * scale[image]   (nearest upsample by 1 << shift into a concat)
+// dst[pix][coff .. coff + C) = src[pix >> shift][0 .. C) * scale[image]   (nearest upsample by 1 << shift into a concat);
+// scale: fp32 [n_img][ld_scale] or null
 void upsample_into16(hipStream_t st, const half_t* src, int lds, const ImgGeom* gsrc, const ImgGeom* gdst, int n_img,
-                     long long max_pix, int C, int shift, half_t* dst, int ldd, int coff, const float* scale);
-// out = a + b (same geometry, pitch Cp)
-void add16(hipStream_t st, const half_t* a, const half_t* b, long long n_halves, half_t* out);
+                     long long max_pix, int C, int shift, half_t* dst, int ldd, int coff, const float* scale, int ld_scale);
 // max / average pooling, window (kh, kw), stride (sh, sw), pad (ph, pw) (max: -inf padding; avg: no padding allowed)
 void maxpool16(hipStream_t st, const half_t* x, int ldx, const ImgGeom* gin, const ImgGeom* gout, int n_img, long long max_pix, int Cp,
                int kh, int kw, int sh, int sw, int ph, int pw, half_t* y, int ldy);
 void avgpool16(hipStream_t st, const half_t* x, int ldx, const ImgGeom* gin, const ImgGeom* gout, int n_img, long long max_pix, int Cp,
                int kh, int kw, half_t* y, int ldy);   // window = stride, no padding
-void avgpool16_to_f32(hipStream_t st, const half_t* x, const ImgGeom* gin, const ImgGeom* gout, int n_img, long long max_pix, int C,
-                      int Cp, int kh, int kw, float* y, int ldy);
 // ConvTranspose 2x2 stride 2 = 1x1 conv to 4 * C channels (conv16, columns ordered (dy, dx, c)) + this pixel shuffle:
 // dst[(2y+dy, 2x+dx)][coff + c] = src[(y, x)][(dy * 2 + dx) * C + c]
 void pixel_shuffle16(hipStream_t st, const half_t* src, int lds, const ImgGeom* gsrc, const ImgGeom* gdst, int n_img,

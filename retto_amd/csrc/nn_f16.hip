@@ -186,6 +186,7 @@ __global__ __launch_bounds__(64 * WN * WP, 2) void k_conv16(const ConvArgs a) {
 int g_conv16_v2 = 1;   // 1 = LDS-DMA kernels where they apply (default); 0 = register-staged k_conv16 everywhere (A/B)
 
 long long* g_conv_stamps = nullptr;  // diagnostics: device buffer for stage time stamps (rt_debug_conv16 with RT_CONV_STAMPS)
+int g_conv16_route = CONV16_ROUTE_NONE;  // diagnostics: the kernel the last conv16 call launched
 bool conv_stamps_compiled() {
 #ifdef RT_CONV_STAMPS_BUILD
   return true;
@@ -266,6 +267,7 @@ void conv16(hipStream_t st, const half_t* x, int ldx, const ImgGeom* gin, const 
   const long long tiles = (long long)((maxWo + a.TW - 1) / a.TW) * ((maxHo + a.TH - 1) / a.TH);
   if (n_img > RT_MAX_GRID_Y) throw RtError(8, "conv16: too many images in one launch");
   dim3 grid((unsigned)(tiles * a.nzb), (unsigned)n_img);
+  g_conv16_route = CONV16_ROUTE_CONV16 | (dot ? CONV16_ROUTE_DOT : 0);
   switch (bn / 32) {
     case 1: dot ? launch_conv16<1, 1>(st, a, grid, lds) : launch_conv16<1, 0>(st, a, grid, lds); break;
     case 2: dot ? launch_conv16<2, 1>(st, a, grid, lds) : launch_conv16<2, 0>(st, a, grid, lds); break;
@@ -461,18 +463,10 @@ __global__ __launch_bounds__(256) void k_pool_partial16(const half_t* __restrict
   }
 }
 
-// block per group of IPB images: mean -> [fc1 -> relu] -> fc2 -> gate.  The FC weights are read once per block and applied to
-// all of its images (the recognition net's ESE layers have C x C weights of up to 4 MB and ~1000 images per launch: one
-// block per image re-read them from L2 a thousand times).
+// block per group of IPB images: the chunk sums of k_pool_partial16, added in chunk order, times 1 / pixels
 constexpr int SE_IPB = 8;
-__global__ __launch_bounds__(256) void k_se_fc16(const float* __restrict__ partial, const ImgGeom* __restrict__ geom, int n_img,
-                                                 int chunks_alloc, int C, int Cp, const float* __restrict__ w1t,
-                                                 const float* __restrict__ b1, const float* __restrict__ w2t,
-                                                 const float* __restrict__ b2, int Cr, float slope, int residual,
-                                                 float* __restrict__ scale) {
-  extern __shared__ float sm16[];  // mean[IPB][Cp] + hid[IPB][Cr]
-  float* mean = sm16;
-  float* hid = sm16 + SE_IPB * Cp;
+__global__ __launch_bounds__(256) void k_pool_mean16(const float* __restrict__ partial, const ImgGeom* __restrict__ geom, int n_img,
+                                                     int chunks_alloc, int Cp, float* __restrict__ out) {
   const int img0 = blockIdx.x * SE_IPB, ni = min(SE_IPB, n_img - img0);
   for (int i = 0; i < ni; i++) {
     const ImgGeom g = geom[img0 + i];
@@ -482,67 +476,20 @@ __global__ __launch_bounds__(256) void k_se_fc16(const float* __restrict__ parti
     for (int c = threadIdx.x; c < Cp; c += 256) {
       float s = 0.f;
       for (int k = 0; k < chunks; k++) s += partial[((long long)(img0 + i) * chunks_alloc + k) * Cp + c];
-      mean[i * Cp + c] = s * inv;
-    }
-  }
-  __syncthreads();
-  if (w2t == nullptr) {  // plain global mean
-    for (int i = 0; i < ni; i++)
-      for (int c = threadIdx.x; c < Cp; c += 256) scale[(long long)(img0 + i) * Cp + c] = mean[i * Cp + c];
-    return;
-  }
-  const float* hin = mean;
-  int hpitch = Cp;
-  if (w1t) {
-    for (int j = threadIdx.x; j < Cr; j += 256) {  // w1t [C][Cr]
-      float s[SE_IPB];
-#pragma unroll
-      for (int i = 0; i < SE_IPB; i++) s[i] = b1[j];
-      for (int c = 0; c < C; c++) {
-        const float w = w1t[(size_t)c * Cr + j];
-#pragma unroll
-        for (int i = 0; i < SE_IPB; i++) s[i] = fmaf(mean[i * Cp + c], w, s[i]);
-      }
-#pragma unroll
-      for (int i = 0; i < SE_IPB; i++) hid[i * Cr + j] = fmaxf(s[i], 0.f);
-    }
-    __syncthreads();
-    hin = hid; hpitch = Cr;
-  }
-  for (int c = threadIdx.x; c < Cp; c += 256) {  // w2t [Cr][C]
-    float s[SE_IPB];
-#pragma unroll
-    for (int i = 0; i < SE_IPB; i++) s[i] = c < C ? b2[c] : 0.f;
-    if (c < C)
-      for (int j = 0; j < Cr; j++) {
-        const float w = w2t[(size_t)j * C + c];
-#pragma unroll
-        for (int i = 0; i < SE_IPB; i++) s[i] = fmaf(hin[i * hpitch + j], w, s[i]);
-      }
-    for (int i = 0; i < ni; i++) {
-      float o = 0.f;
-      if (c < C) {
-        o = slope < 0.f ? 1.f / (1.f + __expf(-s[i])) : fminf(fmaxf(fmaf(s[i], slope, 0.5f), 0.f), 1.f);
-        if (residual) o += 1.0f;
-      }
-      scale[(long long)(img0 + i) * Cp + c] = o;
+      out[(long long)(img0 + i) * Cp + c] = s * inv;
     }
   }
 }
 
-void se_scale16(hipStream_t st, const half_t* x, int ldx, const ImgGeom* geom, int n_img, long long max_pix, int C, int Cp, const float* w1t,
-                const float* b1, const float* w2t, const float* b2, int Cr, float slope, int residual, float* partial,
-                float* scale) {
+void global_mean16(hipStream_t st, const half_t* x, int ldx, const ImgGeom* geom, int n_img, long long max_pix, int Cp, float* partial,
+                   float* out) {
   if (n_img <= 0) return;
   const int chunks = pool_chunks16(max_pix);
   for (int y0 = 0; y0 < n_img; y0 += RT_MAX_GRID_Y) {
     const int ny = std::min(n_img - y0, RT_MAX_GRID_Y);
     RT_LAUNCH(k_pool_partial16, dim3(chunks, ny), dim3(256), 0, st, x, ldx, geom + y0, Cp, chunks, partial + (size_t)y0 * chunks * Cp);
   }
-  const size_t lds = (size_t)SE_IPB * (Cp + Cr + 4) * sizeof(float);
-  allow_big_lds(reinterpret_cast<const void*>(k_se_fc16), 96 * 1024);
-  RT_LAUNCH(k_se_fc16, dim3((n_img + SE_IPB - 1) / SE_IPB), dim3(256), lds, st, partial, geom, n_img, chunks, C, Cp, w1t, b1, w2t,
-            b2, Cr, slope, residual, scale);
+  RT_LAUNCH(k_pool_mean16, dim3((n_img + SE_IPB - 1) / SE_IPB), dim3(256), 0, st, partial, geom, n_img, chunks, Cp, out);
 }
 // scale[img][c] = gate(s[img][c]) (+1 when residual), 0 on the pad channels
 __global__ __launch_bounds__(256) void k_gate16(const float* __restrict__ sv, int lds_, int n_img, int C, int Cp, float slope, int residual,
@@ -561,10 +508,6 @@ __global__ __launch_bounds__(256) void k_gate16(const float* __restrict__ sv, in
 void gate16(hipStream_t st, const float* s, int lds_, int n_img, int C, int Cp, float slope, int residual, float* scale) {
   if (n_img <= 0) return;
   RT_LAUNCH(k_gate16, dim3((unsigned)((n_img * Cp + 255) / 256)), dim3(256), 0, st, s, lds_, n_img, C, Cp, slope, residual, scale);
-}
-void global_mean16(hipStream_t st, const half_t* x, int ldx, const ImgGeom* geom, int n_img, long long max_pix, int Cp, float* partial,
-                   float* out) {
-  se_scale16(st, x, ldx, geom, n_img, max_pix, Cp, Cp, nullptr, nullptr, nullptr, nullptr, 0, 0.f, 0, partial, out);
 }
 
 __global__ __launch_bounds__(256) void k_scale_channels16(const half_t* __restrict__ x, int ldx, const ImgGeom* __restrict__ geom, int Cp,
@@ -634,7 +577,7 @@ void upsample_add16(hipStream_t st, const half_t* a, const half_t* b, const ImgG
 
 __global__ __launch_bounds__(256) void k_upsample_into16(const half_t* __restrict__ src, int lds, const ImgGeom* __restrict__ gsrc,
                                                          const ImgGeom* __restrict__ gdst, int C, int shift, half_t* __restrict__ dst,
-                                                         int ldd, int coff, const float* __restrict__ scale) {
+                                                         int ldd, int coff, const float* __restrict__ scale, int ld_scale) {
   const ImgGeom S = gsrc[blockIdx.y], D = gdst[blockIdx.y];
   const int C8 = C >> 3;
   const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
@@ -645,35 +588,20 @@ __global__ __launch_bounds__(256) void k_upsample_into16(const half_t* __restric
   const int sy = min(y >> shift, S.H - 1), sx = min(x >> shift, S.W - 1);
   h8 v = *reinterpret_cast<const h8*>(src + (S.off + (long long)sy * S.W + sx) * lds + c8 * 8);
   if (scale) {
-    const float* s = scale + (long long)blockIdx.y * lds + c8 * 8;
+    const float* s = scale + (long long)blockIdx.y * ld_scale + c8 * 8;
 #pragma unroll
     for (int t = 0; t < 8; t++) v[t] = (half_t)((float)v[t] * s[t]);
   }
   *reinterpret_cast<h8*>(dst + (D.off + p) * ldd + coff + c8 * 8) = v;
 }
 void upsample_into16(hipStream_t st, const half_t* src, int lds, const ImgGeom* gsrc, const ImgGeom* gdst, int n_img,
-                     long long max_pix, int C, int shift, half_t* dst, int ldd, int coff, const float* scale) {
+                     long long max_pix, int C, int shift, half_t* dst, int ldd, int coff, const float* scale, int ld_scale) {
   if (n_img <= 0) return;
   if (C % 8 || coff % 8 || ldd % 8 || lds % 8) throw RtError(8, "upsample_into16: channels must be multiples of 8");
+  if (scale && ld_scale < C) throw RtError(8, "upsample_into16: the scale table's pitch is below C");
   const long long total = max_pix * (C / 8);
   RT_LAUNCH(k_upsample_into16, dim3((unsigned)((total + 255) / 256), n_img), dim3(256), 0, st, src, lds, gsrc, gdst, C, shift, dst,
-            ldd, coff, scale);
-}
-
-__global__ __launch_bounds__(256) void k_add16(const half_t* __restrict__ a, const half_t* __restrict__ b, long long n8,
-                                               half_t* __restrict__ out) {
-  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-  if (i >= n8) return;
-  const h8 va = reinterpret_cast<const h8*>(a)[i], vb = reinterpret_cast<const h8*>(b)[i];
-  h8 o;
-#pragma unroll
-  for (int t = 0; t < 8; t++) o[t] = (half_t)((float)va[t] + (float)vb[t]);
-  reinterpret_cast<h8*>(out)[i] = o;
-}
-void add16(hipStream_t st, const half_t* a, const half_t* b, long long n_halves, half_t* out) {
-  if (n_halves <= 0) return;
-  const long long n8 = n_halves / 8;
-  RT_LAUNCH(k_add16, dim3((unsigned)((n8 + 255) / 256)), dim3(256), 0, st, a, b, n8, out);
+            ldd, coff, scale, ld_scale);
 }
 
 __global__ __launch_bounds__(256) void k_maxpool16(const half_t* __restrict__ x, int ldx, const ImgGeom* __restrict__ gin,
@@ -712,29 +640,6 @@ void maxpool16(hipStream_t st, const half_t* x, int ldx, const ImgGeom* gin, con
   for (int y0 = 0; y0 < n_img; y0 += RT_MAX_GRID_Y)
     RT_LAUNCH(k_maxpool16, dim3((unsigned)((total + 255) / 256), std::min(n_img - y0, RT_MAX_GRID_Y)), dim3(256), 0, st, x, ldx,
               gin + y0, gout + y0, Cp, kh, kw, sh, sw, ph, pw, y, ldy);
-}
-
-__global__ __launch_bounds__(256) void k_avgpool16_to_f32(const half_t* __restrict__ x, const ImgGeom* __restrict__ gin,
-                                                          const ImgGeom* __restrict__ gout, int C, int Cp, int kh, int kw,
-                                                          float* __restrict__ y, int ldy) {
-  const ImgGeom gi = gin[blockIdx.y], go = gout[blockIdx.y];
-  const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
-  if (idx >= (long long)go.H * go.W * C) return;
-  const int c = (int)(idx % C);
-  const long long p = idx / C;
-  const int oy = (int)(p / go.W), ox = (int)(p - (long long)oy * go.W);
-  float s = 0.f;
-  for (int dy = 0; dy < kh; dy++)
-    for (int dx = 0; dx < kw; dx++) s += (float)x[(gi.off + (long long)(oy * kh + dy) * gi.W + ox * kw + dx) * Cp + c];
-  y[(go.off + p) * ldy + c] = s / (float)(kh * kw);
-}
-void avgpool16_to_f32(hipStream_t st, const half_t* x, const ImgGeom* gin, const ImgGeom* gout, int n_img, long long max_pix, int C,
-                      int Cp, int kh, int kw, float* y, int ldy) {
-  if (n_img <= 0 || max_pix <= 0) return;
-  const long long total = max_pix * C;
-  for (int y0 = 0; y0 < n_img; y0 += RT_MAX_GRID_Y)
-    RT_LAUNCH(k_avgpool16_to_f32, dim3((unsigned)((total + 255) / 256), std::min(n_img - y0, RT_MAX_GRID_Y)), dim3(256), 0, st, x,
-              gin + y0, gout + y0, C, Cp, kh, kw, y, ldy);
 }
 
 __global__ __launch_bounds__(256) void k_avgpool16(const half_t* __restrict__ x, int ldx, const ImgGeom* __restrict__ gin,

@@ -515,6 +515,7 @@ bool conv16_dma(hipStream_t st, const ConvArgs& a0, int n_img, int maxHo, int ma
       g.a = a0; g.a.nzb = (Npad + bn - 1) / bn; g.zeros = zero_page16();
       const long long mtiles = ((long long)maxWo + 255) / 256;
       if (mtiles * g.a.nzb < (1ll << 31)) {
+        g_conv16_route = CONV16_ROUTE_GEMM16P;
         switch (bn / 64) { case 4: launch_gemm16p<4, 4>(st, g, mtiles); break; case 3: launch_gemm16p<3, 4>(st, g, mtiles); break;
                            case 2: launch_gemm16p<2, 4>(st, g, mtiles); break; default: launch_gemm16p<1, 4>(st, g, mtiles); break; }
         return true;
@@ -615,6 +616,7 @@ bool conv16_dma(hipStream_t st, const ConvArgs& a0, int n_img, int maxHo, int ma
   // whose 80 input channels are not whole slabs); a layer with a partial last slab or an image beyond the 2-GB offset range takes
   // the register-staged kernel.  (A/B of the two forms on C5, same box: 444 / 444 vs 452-460 images/s.)
   if (!k22 && ((Cin % KS) != 0 || !c2.bdma)) return false;
+  g_conv16_route = CONV16_ROUTE_CONV16V2 | (k22 ? CONV16_ROUTE_DOT : 0);
 #define RT_V2_ONE(NT, KWV, KWRV, DOTV, NWV, BDV) do { allow_big_lds((const void*)k_conv16v2<NT, KWV, KWRV, DOTV, NWV, BDV>, (NWV) == 8 ? 160 * 1024 : 80 * 1024); \
                                                       RT_LAUNCH((k_conv16v2<NT, KWV, KWRV, DOTV, NWV, BDV>), grid2, dim3(64 * (NWV)), lds2, st, c2); } while (0)
 #define RT_V2_GO(NT, KWV, KWRV) do { if (nw == 4) RT_V2_ONE(NT, KWV, KWRV, 0, 4, true); else RT_V2_ONE(NT, KWV, KWRV, 0, 8, true); } while (0)

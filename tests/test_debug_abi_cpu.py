@@ -1,6 +1,7 @@
 """The kernel-level debug entry points rt_debug_gemm / rt_debug_attention (tests/test_gpu_ops.py drives them on the GPU) and
-rt_debug_lc_block / rt_debug_conv13 / rt_debug_layernorm (tests/test_gpu_rec_kernels.py): declared, exported, and null or bad
-arguments rejected with RT_ERR_INVALID before any device work."""
+rt_debug_lc_block / rt_debug_conv13 / rt_debug_layernorm (tests/test_gpu_rec_kernels.py) and rt_debug_glue16 / rt_debug_conv16x
+(tests/test_gpu_f16_kernels.py): declared, exported, and null or bad arguments rejected with RT_ERR_INVALID before any device
+work."""
 import ctypes as C
 import os
 
@@ -15,7 +16,8 @@ RT_ERR_INVALID = 8
 def test_debug_symbols_are_declared_and_exported():
     header = open(os.path.join(ROOT, "include", "retto_hip.h")).read()
     lib = _lib.load()
-    for name in ("rt_debug_gemm", "rt_debug_attention", "rt_debug_lc_block", "rt_debug_conv13", "rt_debug_layernorm"):
+    for name in ("rt_debug_gemm", "rt_debug_attention", "rt_debug_lc_block", "rt_debug_conv13", "rt_debug_layernorm",
+                 "rt_debug_glue16", "rt_debug_conv16x"):
         assert "RT_API int %s(" % name in header
         assert name in _lib.EXPORTS
         assert hasattr(lib, name)
@@ -81,3 +83,114 @@ def test_rec_kernel_entries_reject_null_and_bad_arguments_without_a_device():
         assert _conv13(lib, **kw) == RT_ERR_INVALID, kw
     for kw in ({}, {"x": False}, {"g": False}, {"beta": False}, {"out": False}, {"rows": 0}, {"c": 0}, {"c": 257}, {"eps": 0.0}):
         assert _ln(lib, **kw) == RT_ERR_INVALID, kw
+
+
+def _glue(lib, s=None, op=3, ip=(24, 24, 0, 48, 24, 24, 0, 0), fp=True, ipp=True, sh=True, sw=True, dh=True, dw=True, n_img=2, x=True, x_len=None,
+          x2=True, x2_len=None, tab=True, tab_len=None, out=True, out_len=None, hs=(3, 1), ws=(2, 1)):
+    """scale_channels16 with a residual on two images of 6 and 1 pixels, unless the arguments say otherwise"""
+    i = np.zeros(12, np.int32); i[:len(ip)] = ip   # noqa: E702
+    f = np.zeros(8, np.float32)
+    h, w = np.array(hs, np.int32), np.array(ws, np.int32)
+    pix = 7
+    xs, x2s, t, o = np.zeros(pix * 64, np.float32), np.zeros(pix * 64, np.float32), np.zeros(256, np.float32), np.zeros((pix + 64) * 64, np.float32)
+    p = lambda arr, on: arr.ctypes.data if on else None   # noqa: E731
+    d = lambda v, dflt: dflt if v is None else v          # noqa: E731
+    return lib.rt_debug_glue16(s, op, p(i, ipp), p(f, fp), p(h, sh), p(w, sw), p(h, dh), p(w, dw), n_img, p(xs, x), d(x_len, pix * max(int(i[1]), 1)),
+                               p(x2s, x2), d(x2_len, pix * max(int(i[5]), 0)), p(t, tab), d(tab_len, 2 * max(int(i[0]), 0)), p(o, out),
+                               d(out_len, (pix + 64) * max(int(i[3]), 1)))
+
+
+def test_glue16_rejects_null_and_bad_arguments_without_a_device():
+    """rt_debug_glue16 looks at its session last, so without a device every argument check still answers with its own message
+    (rt_last_error(NULL) holds it): a check that was skipped would show as "null session"."""
+    lib = _lib.load()
+    null, op, chan, pitch8, window, params, lens, aux, img = (
+        "null argument", "bad op or image count", "bad channel counts", "multiples of 8", "leaves the row", "bad parameters for the op",
+        "x is too short or out has the wrong length", "x2 or tab is missing or too short", "empty or oversized image")
+    sc = lambda *tail: (24, 24, 0, 48, 24) + tail   # noqa: E731  scale_channels16: x pitch 24 -> y pitch 48 at 24; tail = ldr, roff, in place
+    cases = [({}, "null session"),
+             ({"ipp": False}, null), ({"fp": False}, null), ({"sh": False}, null), ({"sw": False}, null), ({"dh": False}, null),
+             ({"dw": False}, null), ({"x": False}, null), ({"out": False}, null), ({"x2": False}, aux), ({"tab": False}, aux),
+             ({"n_img": 0}, op), ({"op": -1}, op), ({"op": 15}, op), ({"hs": (3, 0)}, img), ({"ws": (0, 1)}, img),
+             ({"ip": (0, 24, 0, 48, 24, 24, 0, 0)}, chan),           # no channels
+             ({"ip": (24, 0, 0, 48, 24, 24, 0, 0)}, chan),           # no source pitch
+             ({"ip": (24, 16, 0, 48, 24, 24, 0, 0)}, window),        # source pitch below C
+             ({"ip": (24, 28, 0, 48, 24, 24, 0, 0)}, pitch8),        # source pitch no multiple of 8
+             ({"ip": (24, 24, 0, 52, 24, 24, 0, 0)}, pitch8),        # destination pitch no multiple of 8
+             ({"ip": (24, 24, 0, 48, 20, 24, 0, 0)}, pitch8),        # destination offset no multiple of 8
+             ({"ip": (24, 24, 0, 48, 32, 24, 0, 0)}, window),        # the window leaves the row
+             ({"ip": sc(20, 0, 0)}, params),                         # residual pitch misaligned
+             ({"ip": sc(24, 8, 0)}, params),                         # the residual's window leaves its row
+             ({"ip": sc(24, 0, 1)}, params),                         # in place with different pitches
+             ({"x_len": 7 * 24 - 1}, lens), ({"x2_len": 7 * 24 - 1}, aux), ({"tab_len": 47}, aux), ({"out_len": (7 + 64) * 48 - 1}, lens),
+             ({"out_len": 0}, lens),
+             # per-op parameter blocks: a geometry the kernel would read or write out of bounds with, a parameter it has no instance for
+             ({"op": 0, "ip": (24, 24, 0, 24, 0, 4, 1, 1, 0, 0)}, params),      # dwconv16: K = 4
+             ({"op": 0, "ip": (24, 24, 0, 24, 0, 3, 2, 2, 0, 0)}, params),      # dwconv16: destination is not ceil(source / stride)
+             ({"op": 7, "ip": (24, 24, 0, 24, 0, 3, 2)}, params),               # avgpool16: the windows leave the source
+             ({"op": 8, "ip": (24, 48, 0, 24, 0)}, window),                     # pixel_shuffle16: 4 C channels do not fit the source pitch
+             ({"op": 9, "ip": (24, 24, 0, 1, 0)}, params),                      # deconv_to_map16: the map is not 2 x the features
+             ({"op": 5, "ip": (24, 24, 0, 48, 24, 4, 0)}, params),              # upsample_into16: shift 4
+             ({"op": 5, "ip": (24, 24, 0, 48, 24, 1, 16)}, params),             # upsample_into16: scale pitch below C
+             ({"op": 6, "ip": (24, 24, 0, 24, 0, 2, 2, 2, 2, 2, 0)}, params),   # maxpool16: pad >= window
+             ({"op": 10, "ip": (16, 1, 0, 24, 16)}, window),                    # map_window16: 16 channels from 16 leave a pitch of 24
+             ({"op": 2, "ip": (24, 24, 0, 16, 0, 0)}, params),                  # gate16: Cp < C
+             ({"op": 13, "ip": (24, 16, 0, 24, 0)}, window)]                    # h_to_f32: C above the source pitch
+    lib.rt_last_error.restype = C.c_char_p
+    for kw, why in cases:
+        assert _glue(lib, **kw) == RT_ERR_INVALID, kw
+        assert why in lib.rt_last_error(None).decode(), (kw, lib.rt_last_error(None))
+
+
+
+def _conv16x(lib, s=None, ip=None, ipp=True, fp=True, hh=True, ww=True, n_img=2, x=True, x_len=None, wt=True, wt_len=None, res=False,
+             res_len=None, dot=False, out=True, out_len=None, route=True, hs=(3, 1), ws=(2, 1), **named):
+    """3x3 32 -> 24 relu on two images of 6 and 1 pixels, channels 8 .. 39 of pitch 48 into channels 8 .. 31 of pitch 40, unless
+    the arguments say otherwise; named = single ip entries by name"""
+    names = ("cin", "ldx", "xoff", "cout", "ldy", "coff", "kh", "kw", "sh", "sw", "pt", "pl", "flat", "act", "has_lab", "ld_res", "res_off",
+             "in_place", "dot_py", "dot_px")
+    i = np.array(ip if ip is not None else (32, 48, 8, 24, 40, 8, 3, 3, 1, 1, -1, -1, 0, 1, 0, 0, 0, 0, 0, 0), np.int32)
+    for k, v in named.items():
+        i[names.index(k)] = v
+    f = np.zeros(3, np.float32)
+    h, w = np.array(hs, np.int32), np.array(ws, np.int32)
+    pix = 7
+    xs, wts, rs, dws, o = (np.zeros(n, np.float32) for n in (pix * 128, 64 * 128 * 9, pix * 128, 64, (4 * pix + 64) * 128))
+    r = (C.c_int * 1)()
+    p = lambda arr, on: arr.ctypes.data if on else None   # noqa: E731
+    d = lambda v, dflt: dflt if v is None else v          # noqa: E731
+    return lib.rt_debug_conv16x(s, p(i, ipp), p(f, fp), p(h, hh), p(w, ww), n_img, p(xs, x), d(x_len, pix * max(int(i[1]), 1)),
+                                p(wts, wt), d(wt_len, int(i[3]) * int(i[0]) * int(i[6]) * int(i[7])), None, p(rs, res),
+                                d(res_len, pix * max(int(i[15]), 0)), p(dws, dot), p(o, out),
+                                d(out_len, 4 * pix + 64 if dot else (pix + 64) * max(int(i[4]), 1)), r if route else None)
+
+
+def test_conv16x_rejects_null_and_bad_arguments_without_a_device():
+    """as rt_debug_glue16: the session is looked at last, so every argument check answers with its own message"""
+    lib = _lib.load()
+    null, count, chan, in8, outw, launch, img, place, lens, resid = (
+        "null argument", "bad image count", "bad channel counts", "input channels, pitch and offset", "output window", "no such launch",
+        "empty or oversized image", "in place needs", "x is too short, or wt or out", "the residual is")
+    phase = (80, 80, 0, 64, 8, 0, 2, 2, 1, 1, 1, 0, 0, 1, 0, 0, 0, 0, 0, 1)   # a PFHeadLocal phase conv (dot=True goes with it)
+    cases = [({}, "null session"), ({"dot": True, "ip": phase}, "null session"), ({"res": True, "ld_res": 32, "res_off": 8}, "null session"),
+             ({"ipp": False}, null), ({"fp": False}, null), ({"hh": False}, null), ({"ww": False}, null), ({"x": False}, null),
+             ({"wt": False}, null), ({"out": False}, null), ({"route": False}, null),
+             ({"n_img": 0}, count), ({"hs": (3, 0)}, img), ({"ws": (0, 1)}, img),
+             ({"cin": 0}, chan), ({"cout": 0}, chan), ({"ldx": 0}, chan), ({"ldx": 32}, chan),     # (the window 8 .. 39 leaves a pitch of 32)
+             ({"cin": 36}, in8), ({"ldx": 52}, in8), ({"xoff": 4}, in8),
+             ({"ldy": 0}, outw), ({"ldy": 44}, outw), ({"coff": 4}, outw), ({"coff": 24}, outw),    # (24 + pitch8(24) > 40)
+             ({"cout": 34}, outw),                                                                   # (pad channels 34 .. 39 leave the row)
+             ({"kh": 2}, launch), ({"kh": 2, "kw": 2}, launch),                                      # (2x2 without the dot epilogue)
+             ({"dot": True}, launch),                                                                # (the dot epilogue on a 3x3)
+             ({"dot": True, "ip": phase, "cout": 96}, launch), ({"dot": True, "ip": phase, "pt": 2}, launch),
+             ({"dot": True, "ip": phase, "dot_py": 2}, launch), ({"dot": True, "ip": phase, "cin": 24, "ldx": 24}, launch),
+             ({"sh": 3}, launch), ({"sw": 0}, launch), ({"pt": 0}, launch), ({"act": 5}, launch), ({"flat": 1}, launch), ({"kw": 11}, launch),
+             ({"in_place": 1}, place), ({"in_place": 1, "ldy": 48, "sh": 2}, place),
+             ({"x_len": 7 * 48 - 1}, lens), ({"wt_len": 24 * 32 * 9 - 1}, lens), ({"out_len": (7 + 64) * 40 - 1}, lens), ({"out_len": 0}, lens),
+             ({"dot": True, "ip": phase, "out_len": 4 * 7 + 63}, lens),
+             ({"res": True, "ld_res": 0}, resid), ({"res": True, "ld_res": 28}, resid), ({"res": True, "ld_res": 32, "res_off": 4}, resid),
+             ({"res": True, "ld_res": 32, "res_off": 16}, resid), ({"res": True, "ld_res": 32, "res_len": 7 * 32 - 1}, resid)]
+    lib.rt_last_error.restype = C.c_char_p
+    for kw, why in cases:
+        assert _conv16x(lib, **kw) == RT_ERR_INVALID, kw
+        assert why in lib.rt_last_error(None).decode(), (kw, lib.rt_last_error(None))
