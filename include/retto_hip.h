@@ -476,7 +476,7 @@ RT_API int rt_debug_dwconv(rt_session* s, const float* x, const int* heights, co
  * it), lines of tokens[i] consecutive rows (sum = rows) -> out [rows][heads * 15], with the geometry SvtrCore::mixer passes. */
 RT_API int rt_debug_attention(rt_session* s, const float* qkv, long long rows, const int* tokens, int n_lines, int heads,
                               float* out);
-/* One fused thin LCNetV3 block (3x3 depthwise, stride (sh, sw), "same" padding -> 1x1 conv + hardswish) as one nn::lc_thin launch on
+/* One fused thin LCNetV3 block (3x3 depthwise, stride (sh, sw), "same" padding -> 1x1 conv + hardswish) through the networks' run_lc on
  * host arrays, for the numerics tests: n_img images of heights[i] x widths[i] pixels, consecutive in x [sum h w][Cp] with Cp =
  * cin rounded up to 4 (32 from 128 channels on; channels cin .. Cp zero), laid out as the networks' levels are.  dw_w [cin][3][3]
  * (torch depthwise layout) and dw_bias [cin], pw_w [cout][cin] and pw_bias [cout], packed by the networks' own packers; dw_act and

@@ -934,7 +934,7 @@ RT_API int rt_debug_gemm(rt_session* s, const float* A, long long M, int K, int 
 }
 
 // One nn::dwconv launch on host arrays (tests/test_gpu_dwconv_sweep.py): ragged images as the networks' levels lay them out, the
-// pooled partial sums in the layout dwconv_pool_layout gives run_lc, and the channel means k_se_fc makes of them (its walk over
+// pooled partial sums in the layout nn::dw_plan gives run_lc, and the channel means k_se_fc makes of them (its walk over
 // the partials, without the FCs).  form 0 = k_dwconv_rows, 1 = k_dwconv_sweep where the layer has an instance.
 RT_API int rt_debug_dwconv(rt_session* s, const float* x, const int* heights, const int* widths, int n_img, int C, int Cp, int K,
                            int sh, int sw, const float* w, const float* bias, int act, int has_lab, float lab_a, float lab_c,
@@ -956,15 +956,15 @@ RT_API int rt_debug_dwconv(rt_session* s, const float* x, const int* heights, co
     maxHo = std::max(maxHo, ho); maxWo = std::max(maxWo, wo);
   }
   RT_REQUIRE(pin * Cp < (1ll << 30), s, "rt_debug_dwconv: too large");
-  int chunks = 0, strip_R = 0, spb = 0;
-  if (pooled) nn::dwconv_pool_layout(K, sh, sw, Cp, maxHo, maxWo, &chunks, &strip_R, &spb);
+  RestoreInt keep_form(nn::g_dw_sweep);
+  nn::g_dw_sweep = form ? 4 : 0;
+  const nn::DwPlan plan = nn::dw_plan(K, sh, sw, Cp, maxHo, maxWo, pooled != 0);
+  const int chunks = pooled ? plan.chunks : 0, strip_R = pooled ? plan.R : 0, spb = pooled ? plan.spb : 0;
   const size_t npart = (size_t)n_img * chunks * Cp;
   RT_REQUIRE(!pooled || (long long)npart <= partial_cap, s, "rt_debug_dwconv: partial_out is too small");
   return guarded(s, [&] {
     RT_HIP_CHECK(hipSetDevice(s->device));
     DevBufs bufs;
-    RestoreInt keep_form(nn::g_dw_sweep);
-    nn::g_dw_sweep = form ? 4 : 0;
     const size_t nin = (size_t)pin * Cp, nout = (size_t)(pout + 64) * Cp;
     float *dx = bufs.alloc<float>(nin), *dw = bufs.alloc<float>((size_t)K * K * Cp), *db = bufs.alloc<float>(Cp), *dy = bufs.alloc<float>(nout);
     ImgGeom *dgi = bufs.alloc<ImgGeom>(n_img), *dgo = bufs.alloc<ImgGeom>(n_img);
@@ -979,7 +979,7 @@ RT_API int rt_debug_dwconv(rt_session* s, const float* x, const int* heights, co
       dpart = bufs.alloc<float>(npart); dmean = bufs.alloc<float>((size_t)n_img * Cp);
       RT_HIP_CHECK(hipMemsetD32Async((hipDeviceptr_t)dpart, (int)RT_DEBUG_CANARY, npart, s->st));
     }
-    nn::dwconv(s->st, K, sh, sw, dx, dgi, dgo, n_img, maxHo, maxWo, Cp, C, dw, db, act, has_lab, lab_a, lab_c, dy, dpart);
+    nn::dwconv(s->st, plan, dx, dgi, dgo, n_img, Cp, C, dw, db, act, has_lab, lab_a, lab_c, dy, dpart);
     if (pooled)
       nn::se_fc_from_dw(s->st, dpart, dgo, n_img, chunks, strip_R, spb, C, Cp, nullptr, nullptr, nullptr, nullptr, 0, 0.f, 0, dmean);
     RT_HIP_CHECK(hipStreamSynchronize(s->st));
@@ -989,7 +989,7 @@ RT_API int rt_debug_dwconv(rt_session* s, const float* x, const int* heights, co
       RT_HIP_CHECK(hipMemcpy(mean_out, dmean, (size_t)n_img * Cp * sizeof(float), hipMemcpyDeviceToHost));
     }
     info_out[0] = chunks; info_out[1] = strip_R; info_out[2] = spb;
-    info_out[3] = nn::dwconv_sweeps(K, sh, sw, Cp, maxHo, pooled != 0) ? 1 : 0;
+    info_out[3] = plan.kernel == nn::DwKernel::sweep ? 1 : 0;
   });
 }
 
@@ -1067,10 +1067,28 @@ RT_API int rt_debug_ctc_candidates(rt_session* s, const float* z5, const float* 
   });
 }
 
-// One nn::lc_thin launch on host arrays (tests/test_gpu_rec_kernels.py compares it with an fp64 block): a ragged batch laid out as
-// the networks' levels are, the weights packed by the networks' pack_dw / pack_conv, the route named by nn::lc_route -- what
-// lc_thin() itself dispatches on.  form = nn::g_lc_wave for the launch; where no fused form has an instance the block runs as
-// run_lc runs it: nn::dwconv + nn::gemm.
+// The LCNetV3 block of given host weights: packed by the networks' pack_dw / pack_conv (no squeeze-excite, hardswish pointwise tail)
+static LcBlock debug_lc_block(WeightStore& ws, int cin, int cout, int sh, int sw, const float* dw_w, const float* dw_bias, const float* pw_w,
+                              const float* pw_bias, int dw_act, const Lab& dw_lab, const Lab& pw_lab) {
+  LcBlock b;
+  b.dw = pack_dw(ws, dw_w, dw_bias, cin, 3); b.dw_lab = dw_lab; b.dw_act = dw_act;
+  b.pw = pack_conv(ws, pw_w, pw_bias, cout, cin, 1, 1); b.pw_lab = pw_lab;
+  b.sh = sh; b.sw = sw; b.cin = cin; b.cout = cout;
+  return b;
+}
+// The depthwise output buffer run_lc needs from a caller that supplies its own (the unfused route only): zero rows past the last
+// pixel, so that a GEMM tile's loads stay inside the allocation (the arena does not clear what it hands out)
+static float* debug_lc_mid(DevBufs& bufs, hipStream_t st, const LcBlock& b, const Level& Lo) {
+  if (lc_block_plan(b, Lo).route != nn::LC_UNFUSED) return nullptr;
+  const size_t nmid = (size_t)(Lo.total + 256) * b.dw.Cp;
+  float* dy1 = bufs.alloc<float>(nmid);
+  RT_HIP_CHECK(hipMemsetAsync(dy1, 0, nmid * sizeof(float), st));
+  return dy1;
+}
+
+// One block through the networks' run_lc on host arrays (tests/test_gpu_rec_kernels.py compares it with an fp64 block): a ragged
+// batch on the networks' levels, the weights packed by their pack_dw / pack_conv, the kernels of their plan (lc_block_plan, whose
+// route is returned).  form = nn::g_lc_wave for the launch.
 RT_API int rt_debug_lc_block(rt_session* s, const float* x, const int* heights, const int* widths, int n_img, int cin, int cout,
                              int sh, int sw, const float* dw_w, const float* dw_bias, const float* pw_w, const float* pw_bias,
                              int dw_act, int dw_has_lab, float dw_a, float dw_c, int pw_has_lab, float pw_a, float pw_c, int form,
@@ -1080,48 +1098,30 @@ RT_API int rt_debug_lc_block(rt_session* s, const float* x, const int* heights, 
                  sw >= 1 && sw <= 2 && dw_act >= ACT_NONE && dw_act <= ACT_SIGMOID && (form == 0 || form == 1 || form == 3),
              s, "rt_debug_lc_block: bad shape");
   const int Cp = chan_pitch(cin), ldy = chan_pitch(cout);
-  std::vector<ImgGeom> gi(n_img), go(n_img);
-  long long pin = 0, pout = 0;
-  int maxHo = 0, maxWo = 0;
+  std::vector<std::pair<int, int>> hw;
   for (int i = 0; i < n_img; i++) {
     RT_REQUIRE(heights[i] > 0 && widths[i] > 0, s, "rt_debug_lc_block: empty image");
-    const int ho = (heights[i] + sh - 1) / sh, wo = (widths[i] + sw - 1) / sw;
-    gi[i] = ImgGeom{pin, heights[i], widths[i], 0}; go[i] = ImgGeom{pout, ho, wo, 0};
-    pin += (long long)heights[i] * widths[i]; pout += (long long)ho * wo;
-    maxHo = std::max(maxHo, ho); maxWo = std::max(maxWo, wo);
+    hw.push_back({heights[i], widths[i]});
   }
-  RT_REQUIRE(pin * Cp < (1ll << 30) && pout * ldy < (1ll << 30), s, "rt_debug_lc_block: too large");
+  Level Li = make_level(hw), Lo = down_level(Li, sh, sw);
+  RT_REQUIRE(Li.total * Cp < (1ll << 30) && Lo.total * ldy < (1ll << 30), s, "rt_debug_lc_block: too large");
   return guarded(s, [&] {
-    RT_HIP_CHECK(hipSetDevice(s->device));
+    s->begin_call();
     WeightStore ws;
-    const PackedDw dw = pack_dw(ws, dw_w, dw_bias, cin, 3);
-    const PackedDense pw = pack_conv(ws, pw_w, pw_bias, cout, cin, 1, 1);
-    const Lab lab{pw_has_lab, pw_a, pw_c};
-    const Epilogue e = make_epi(pw, ACT_HSWISH, &lab);
+    const LcBlock b = debug_lc_block(ws, cin, cout, sh, sw, dw_w, dw_bias, pw_w, pw_bias, dw_act, Lab{dw_has_lab, dw_a, dw_c}, Lab{pw_has_lab, pw_a, pw_c});
     DevBufs bufs;
     RestoreInt keep_form(nn::g_lc_wave);
     nn::g_lc_wave = form;
-    const size_t nin = (size_t)pin * Cp, nout = (size_t)(pout + 64) * ldy;
+    RunCtx c = s->ctx(&s->arena);
+    upload_levels(c, {&Li, &Lo});
+    const size_t nin = (size_t)Li.total * Cp, nout = (size_t)(Lo.total + 64) * ldy;   // (64 canary rows past the last image)
     float *dx = bufs.alloc<float>(nin), *dy = bufs.alloc<float>(nout);
-    ImgGeom *dgi = bufs.alloc<ImgGeom>(n_img), *dgo = bufs.alloc<ImgGeom>(n_img);
     RT_HIP_CHECK(hipMemcpy(dx, x, nin * sizeof(float), hipMemcpyHostToDevice));
-    RT_HIP_CHECK(hipMemcpy(dgi, gi.data(), n_img * sizeof(ImgGeom), hipMemcpyHostToDevice));
-    RT_HIP_CHECK(hipMemcpy(dgo, go.data(), n_img * sizeof(ImgGeom), hipMemcpyHostToDevice));
     RT_HIP_CHECK(hipMemsetD32Async((hipDeviceptr_t)dy, (int)RT_DEBUG_CANARY, nout, s->st));
-    const nn::LcRoute route = nn::lc_route(3, sh, sw, dw.Cp, dw.C, pw.N, pw.Npad, dw_act, dw_has_lab, e, maxHo, maxWo, ldy);
-    if (route == nn::LC_UNFUSED) {   // no fused instance: depthwise + GEMM
-      const size_t nmid = (size_t)(pout + 256) * Cp;   // (zero rows past the last pixel: a GEMM tile's loads stay inside the allocation)
-      float* dy1 = bufs.alloc<float>(nmid);
-      RT_HIP_CHECK(hipMemsetAsync(dy1, 0, nmid * sizeof(float), s->st));
-      nn::dwconv(s->st, 3, sh, sw, dx, dgi, dgo, n_img, maxHo, maxWo, dw.Cp, dw.C, dw.w, dw.b, dw_act, dw_has_lab, dw_a, dw_c, dy1, nullptr);
-      nn::gemm(s->st, dy1, dw.Cp, pout, pw.K, pw.w, pw.N, pw.Npad, dy, ldy, 0, e);
-    } else {
-      nn::lc_thin(s->st, sh, sw, dx, dgi, dgo, n_img, maxHo, maxWo, dw.Cp, dw.C, dw.w, dw.b, dw_act, dw_has_lab, dw_a, dw_c, pw.w, pw.N,
-                  pw.Npad, dy, ldy, e);
-    }
+    run_lc(c, b, dx, Li, Lo, dy, debug_lc_mid(bufs, s->st, b, Lo));
     RT_HIP_CHECK(hipStreamSynchronize(s->st));
     RT_HIP_CHECK(hipMemcpy(out, dy, nout * sizeof(float), hipMemcpyDeviceToHost));
-    info_out[0] = (int)route;
+    info_out[0] = (int)lc_block_plan(b, Lo).route;
   });
 }
 
@@ -1460,49 +1460,41 @@ RT_API int rt_debug_conv16x(rt_session* s, const int* ip, const float* fp, const
   });
 }
 
-// Kernel micro-benchmark: the fused thin LCNetV3 block (3x3 depthwise -> pointwise) on n images of h x w pixels, random data.
-// form = nn::g_lc_wave for the timed launches: 0 = k_lc_thin (workgroup-staged; the unfused depthwise + GEMM pair where it has no
-// instance), 1 = k_lc_wave (direct loads, stride 1), 3 = k_lc_lds (production); stride 21 means (2, 1).  maxdiff compares with
-// form 0.
+// Kernel micro-benchmark: one LCNetV3 block (3x3 depthwise -> pointwise) through the networks' run_lc on n images of h x w pixels,
+// random data.  form = nn::g_lc_wave for the timed launches: 0 = k_lc_thin (workgroup-staged; the unfused depthwise + GEMM pair where
+// it has no instance), 1 = k_lc_wave (direct loads, stride 1), 3 = k_lc_lds (production); stride 21 means (2, 1).  maxdiff compares
+// with form 0.
 RT_API int rt_bench_lc(rt_session* s, int n, int h, int w, int cin, int cout, int stride, int form, int iters, float* ms_out, float* maxdiff_out) {
-  RT_REQUIRE(s && ms_out && n > 0 && h > 0 && w > 0 && (stride == 1 || stride == 2 || stride == 21), s, "rt_bench_lc: bad argument");
+  RT_REQUIRE(s && ms_out && n > 0 && h > 0 && w > 0 && cin > 0 && cout > 0 && (stride == 1 || stride == 2 || stride == 21), s, "rt_bench_lc: bad argument");
   return guarded(s, [&] {
-    RT_HIP_CHECK(hipSetDevice(s->device));
-    const int Cp = round_up(cin, 4), Np = round_up(cout, 16), ldy = chan_pitch(cout), nkc = (Cp + nn::KC - 1) / nn::KC;
+    s->begin_call();
     const int sh = stride == 21 ? 2 : stride, sw = stride == 21 ? 1 : stride;   // 21: stride (2, 1)
-    const int ho = (h + sh - 1) / sh, wo = (w + sw - 1) / sw;
-    std::vector<ImgGeom> gi(n), go(n);
-    for (int i = 0; i < n; i++) { gi[i] = ImgGeom{(long long)i * h * w, h, w, 0}; go[i] = ImgGeom{(long long)i * ho * wo, ho, wo, 0}; }
-    const size_t nin = (size_t)n * h * w * Cp, nout = (size_t)n * ho * wo * ldy;
-    std::vector<float> hx(nin), hwd(9 * Cp), hbd(Cp, 0.f), hw((size_t)nkc * Np * nn::KC, 0.f), hb(Np, 0.f);
+    std::vector<float> hwd((size_t)cin * 9), hbd(cin), hw((size_t)cout * cin), hb(cout);
     uint32_t st = 777;
     auto rnd = [&]() { st = st * 1664525u + 1013904223u; return ((st >> 8) & 0xffff) / 32768.0f - 1.0f; };
-    for (auto& v : hx) v = rnd();
     for (auto& v : hwd) v = rnd() * 0.3f;
-    for (int k = 0; k < cin; k++) for (int c = 0; c < cout; c++) hw[((size_t)(k / nn::KC) * Np + c) * nn::KC + k % nn::KC] = rnd() * 0.1f;
-    for (int k = 0; k < cin; k++) hbd[k] = rnd() * 0.1f;    // (a bias per channel: a constant one would hide an indexing error)
-    for (int c = 0; c < cout; c++) hb[c] = rnd() * 0.2f;
+    for (auto& v : hw) v = rnd() * 0.1f;
+    for (auto& v : hbd) v = rnd() * 0.1f;    // (a bias per channel: a constant one would hide an indexing error)
+    for (auto& v : hb) v = rnd() * 0.2f;
+    const bool plain_tail = sh == 2 && sw == 2;   // (depthwise tail as in the LCNetV3 blocks)
+    WeightStore ws;
+    const LcBlock blk = debug_lc_block(ws, cin, cout, sh, sw, hwd.data(), hbd.data(), hw.data(), hb.data(), plain_tail ? ACT_NONE : ACT_HSWISH,
+                                     Lab{!plain_tail, 0.99f, 0.01f}, Lab{1, 1.01f, 0.02f});
+    Level Li = make_level(std::vector<std::pair<int, int>>((size_t)n, {h, w})), Lo = down_level(Li, sh, sw);
+    RunCtx c = s->ctx(&s->arena);
+    upload_levels(c, {&Li, &Lo});
+    const size_t nin = (size_t)Li.total * blk.dw.Cp, nout = (size_t)Lo.total * chan_pitch(cout);
+    std::vector<float> hx(nin, 0.f);
+    for (size_t p = 0; p < (size_t)Li.total; p++) for (int k = 0; k < cin; k++) hx[p * blk.dw.Cp + k] = rnd();
     DevBufs bufs;
     RestoreInt keep_form(nn::g_lc_wave);
-    float *dx = bufs.alloc<float>(nin), *dwd = bufs.alloc<float>(hwd.size()), *dbd = bufs.alloc<float>(hbd.size()), *dw = bufs.alloc<float>(hw.size()),
-          *db = bufs.alloc<float>(hb.size()), *dy = bufs.alloc<float>(nout), *dy0 = bufs.alloc<float>(nout);
-    ImgGeom *dgi = bufs.alloc<ImgGeom>(n), *dgo = bufs.alloc<ImgGeom>(n);
+    float *dx = bufs.alloc<float>(nin), *dy = bufs.alloc<float>(nout), *dy0 = bufs.alloc<float>(nout);
     RT_HIP_CHECK(hipMemset(dy, 0, nout * 4)); RT_HIP_CHECK(hipMemset(dy0, 0, nout * 4));
-    RT_HIP_CHECK(hipMemcpy(dx, hx.data(), nin * 4, hipMemcpyHostToDevice)); RT_HIP_CHECK(hipMemcpy(dwd, hwd.data(), hwd.size() * 4, hipMemcpyHostToDevice));
-    RT_HIP_CHECK(hipMemcpy(dbd, hbd.data(), hbd.size() * 4, hipMemcpyHostToDevice)); RT_HIP_CHECK(hipMemcpy(dw, hw.data(), hw.size() * 4, hipMemcpyHostToDevice));
-    RT_HIP_CHECK(hipMemcpy(db, hb.data(), hb.size() * 4, hipMemcpyHostToDevice));
-    RT_HIP_CHECK(hipMemcpy(dgi, gi.data(), n * sizeof(ImgGeom), hipMemcpyHostToDevice)); RT_HIP_CHECK(hipMemcpy(dgo, go.data(), n * sizeof(ImgGeom), hipMemcpyHostToDevice));
-    Epilogue e; e.bias = db; e.act = ACT_HSWISH; e.has_lab = 1; e.lab_a = 1.01f; e.lab_c = 0.02f;
-    const int dw_act = (sh == 2 && sw == 2) ? ACT_NONE : ACT_HSWISH, dw_lab = !(sh == 2 && sw == 2);   // (depthwise tail as in the LCNetV3 blocks)
-    float* dy1 = nullptr;   // unfused reference: depthwise output
+    RT_HIP_CHECK(hipMemcpy(dx, hx.data(), nin * 4, hipMemcpyHostToDevice));
+    float* dy1 = nullptr;   // depthwise output of the unfused route
     auto run = [&](float* out) {
-      if (nn::g_lc_wave == 0 && !nn::lc_thin_supported(3, sh, sw, Cp, cin, Np)) {   // no k_lc_thin instance: depthwise + GEMM
-        if (!dy1) dy1 = bufs.alloc<float>((size_t)n * ho * wo * Cp);
-        nn::dwconv(s->st, 3, sh, sw, dx, dgi, dgo, n, ho, wo, Cp, cin, dwd, dbd, dw_act, dw_lab, 0.99f, 0.01f, dy1, nullptr);
-        nn::gemm(s->st, dy1, Cp, (long long)n * ho * wo, Cp, dw, cout, Np, out, ldy, 0, e);
-        return;
-      }
-      nn::lc_thin(s->st, sh, sw, dx, dgi, dgo, n, ho, wo, Cp, cin, dwd, dbd, dw_act, dw_lab, 0.99f, 0.01f, dw, cout, Np, out, ldy, e);
+      if (!dy1) dy1 = debug_lc_mid(bufs, s->st, blk, Lo);
+      run_lc(c, blk, dx, Li, Lo, out, dy1);
     };
     nn::g_lc_wave = 0; run(dy0);
     nn::g_lc_wave = form; run(dy);

@@ -9,7 +9,7 @@
 namespace rt {
 namespace nn {
 
-static int env_int(const char* name, int def) {
+int env_int(const char* name, int def) {
   const char* v = getenv(name);
   return v ? atoi(v) : def;
 }

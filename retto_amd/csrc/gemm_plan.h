@@ -14,6 +14,8 @@ extern int g_gemm_dma;      // A/B: persistent LDS-DMA wide GEMM on (default) / 
 extern int g_gemm_split;    // opt-in: split-bf16 form of the wide layers (RT_GEMM_SPLIT=1, rt_debug_set_variants flag bit 12)
 extern int g_argmax_wide;   // CTC head: 0 = narrow kernel with 128-column blocks; 2 = 128 x 128 wide tile; 1 = 256 x 240 tile
 
+int env_int(const char* name, int def);   // an integer switch of the environment, or its default
+
 // tile sizes the size predicates of the persistent kernels depend on
 constexpr int P_BM = 256, P_BN = 240;   // k_gemm32p (nn_gemm_dma.hip)
 constexpr int P_BIAS_MAX = 960;         // k_gemm32p: bias vector kept in LDS (N <= 960)

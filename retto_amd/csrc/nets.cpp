@@ -165,7 +165,7 @@ static void pack_stem(WeightStore& ws, const Blob& b, const std::string& name, i
   memcpy(bias.data(), bt.data, cout * sizeof(float));
   *w_out = ws.upload(host); *b_out = ws.upload(bias);
 }
-static Lab get_lab(const Blob& b, const std::string& name) {
+Lab get_lab(const Blob& b, const std::string& name) {
   Lab l;
   if (b.has(name + ".a")) { l.has = 1; l.a = b.get(name + ".a").data[0]; l.c = b.get(name + ".c").data[0]; }
   return l;
@@ -181,20 +181,6 @@ static SeW get_se(WeightStore& ws, const Blob& b, const std::string& name, int C
   s.w2 = upload_raw(ws, b, name + ".fc2.w", (size_t)s.Cr * C); s.b2 = upload_raw(ws, b, name + ".fc2.b", C);
   return s;
 }
-
-struct LcSpec { const char* name; int k, cin, cout, sh, sw; bool se; };
-static const LcSpec DET_SPEC[] = {
-    {"s2.0", 3, 16, 32, 1, 1, false}, {"s3.0", 3, 32, 48, 2, 2, false}, {"s3.1", 3, 48, 48, 1, 1, false},
-    {"s4.0", 3, 48, 96, 2, 2, false}, {"s4.1", 3, 96, 96, 1, 1, false}, {"s5.0", 3, 96, 192, 2, 2, false},
-    {"s5.1", 5, 192, 192, 1, 1, false}, {"s5.2", 5, 192, 192, 1, 1, false}, {"s5.3", 5, 192, 192, 1, 1, false},
-    {"s5.4", 5, 192, 192, 1, 1, false}, {"s6.0", 5, 192, 384, 2, 2, true}, {"s6.1", 5, 384, 384, 1, 1, true},
-    {"s6.2", 5, 384, 384, 1, 1, false}, {"s6.3", 5, 384, 384, 1, 1, false}};
-static const LcSpec REC_SPEC[] = {
-    {"s2.0", 3, 16, 32, 1, 1, false}, {"s3.0", 3, 32, 64, 1, 1, false}, {"s3.1", 3, 64, 64, 1, 1, false},
-    {"s4.0", 3, 64, 128, 2, 1, false}, {"s4.1", 3, 128, 128, 1, 1, false}, {"s5.0", 3, 128, 240, 1, 2, false},
-    {"s5.1", 5, 240, 240, 1, 1, false}, {"s5.2", 5, 240, 240, 1, 1, false}, {"s5.3", 5, 240, 240, 1, 1, false},
-    {"s5.4", 5, 240, 240, 1, 1, false}, {"s6.0", 5, 240, 480, 2, 1, true}, {"s6.1", 5, 480, 480, 1, 1, true},
-    {"s6.2", 5, 480, 480, 2, 1, false}, {"s6.3", 5, 480, 480, 1, 1, false}};
 
 static LcBlock build_lc(WeightStore& ws, const Blob& b, const std::string& prefix, const LcSpec& s) {
   LcBlock blk;
@@ -256,40 +242,37 @@ static std::string shape_str(long long a, long long b, long long c, long long d)
 static const float HSIG_LCNET = 0.1666667f;  // paddle nn.Hardsigmoid
 static const float HSIG_MBV3 = 0.2f;         // F.hardsigmoid(slope=0.2, offset=0.5)
 
-static float* run_lc(RunCtx& c, const LcBlock& b, const float* x, const Level& Lin, const Level& Lout) {
-  if (!b.se && b.pw.K == b.dw.Cp &&
-      nn::lc_block_supported(b.dw.k, b.sh, b.sw, b.dw.Cp, b.dw.C, b.pw.N, b.pw.Npad, b.dw_act, b.dw_lab.has, make_epi(b.pw, ACT_HSWISH, &b.pw_lab),
-                             Lout.maxH, Lout.maxW)) {
-    int Cpo = chan_pitch(b.cout);
-    float* y2 = c.arena->alloc<float>((size_t)Lout.total * Cpo);
+nn::LcPlan lc_block_plan(const LcBlock& b, const Level& Lout) {
+  nn::LcShape s;
+  s.K = b.dw.k; s.sh = b.sh; s.sw = b.sw; s.Cp = b.dw.Cp; s.C = b.dw.C; s.N = b.pw.N; s.Npad16 = b.pw.Npad;
+  s.dw_act = b.dw_act; s.dw_has_lab = b.dw_lab.has; s.se = b.se;
+  s.maxHo = Lout.maxH; s.maxWo = Lout.maxW; s.ldy = chan_pitch(b.cout); s.rows = Lout.total;
+  s.min_pix = Lout.maxPix;   // (a squeeze-excite row tile spans at most two images when every image has >= tile rows)
+  for (const ImgGeom& g : Lout.h) s.min_pix = std::min<long long>(s.min_pix, (long long)g.H * g.W);
+  return nn::lc_plan(s, make_epi(b.pw, ACT_HSWISH, &b.pw_lab));
+}
+
+float* run_lc(RunCtx& c, const LcBlock& b, const float* x, const Level& Lin, const Level& Lout, float* y2, float* y1) {
+  const nn::LcPlan plan = lc_block_plan(b, Lout);
+  const int Cpo = chan_pitch(b.cout);
+  Epilogue epi = make_epi(b.pw, ACT_HSWISH, &b.pw_lab);
+  if (plan.route != nn::LC_UNFUSED) {
+    if (!y2) y2 = c.arena->alloc<float>((size_t)Lout.total * Cpo);
     ProfScope ps(c.prof, c.st, "lc_thin", shape_str(Lout.total, b.dw.Cp, b.pw.N, b.sh * 10 + b.sw));
-    nn::lc_thin(c.st, b.sh, b.sw, x, Lin.d, Lout.d, Lout.n(), Lout.maxH, Lout.maxW, b.dw.Cp, b.dw.C, b.dw.w, b.dw.b, b.dw_act,
-                b.dw_lab.has, b.dw_lab.a, b.dw_lab.c, b.pw.w, b.pw.N, b.pw.Npad, y2, Cpo, make_epi(b.pw, ACT_HSWISH, &b.pw_lab));
+    (plan.route == nn::LC_THIN ? nn::lc_thin : nn::lc_wave)(c.st, plan, x, Lin.d, Lout.d, Lout.n(), b.dw.C, b.dw.w, b.dw.b, b.dw_act,
+                                                            b.dw_lab.has, b.dw_lab.a, b.dw_lab.c, b.pw.w, b.pw.N, b.pw.Npad, y2, Cpo, epi);
     return y2;
   }
-  float* y1 = c.arena->alloc<float>((size_t)Lout.total * b.dw.Cp);
-  // Squeeze-excite without extra passes over y1: the depthwise kernel leaves per-block channel sums,
-  // the FC turns them into scales, and the pointwise GEMM multiplies them in while staging its A
-  // rows (a row tile spans at most two images when every image has >= tile rows).
-  long long min_pix = Lout.maxPix;
-  for (const ImgGeom& g : Lout.h) min_pix = std::min<long long>(min_pix, (long long)g.H * g.W);
-  // 256: k_gemm32p (3-int table entries), 128: register-staged wide tiles (2-int entries), 0: no fused form
-  const int tile_rows = b.se ? nn::gemm_se_rows(b.dw.Cp, Lout.total, b.pw.K, b.pw.N, b.pw.Npad, ACT_HSWISH, min_pix) : 0;
-  static const bool no_se_fusion = getenv("RT_NO_SE_FUSION") != nullptr;  // A/B switch
-  const bool fuse_se = tile_rows > 0 && (b.dw.k == 3 || b.dw.k == 5) && !no_se_fusion;
-  float* pool = nullptr; int chunks = 0, strip_R = 0, strips_pb = 32;
-  if (fuse_se) {
-    nn::dwconv_pool_layout(b.dw.k, b.sh, b.sw, b.dw.Cp, Lout.maxH, Lout.maxW, &chunks, &strip_R, &strips_pb);
-    pool = c.arena->alloc<float>((size_t)Lout.n() * chunks * b.dw.Cp);
-  }
+  if (!y1) y1 = c.arena->alloc<float>((size_t)Lout.total * b.dw.Cp);
+  const nn::DwPlan& dw = plan.dw;
+  const int tile_rows = plan.se_rows;   // squeeze-excite folded into the GEMM: 256: k_gemm32p (3-int table entries), 128: register-staged wide tiles (2-int entries)
+  float* pool = tile_rows ? c.arena->alloc<float>((size_t)Lout.n() * dw.chunks * b.dw.Cp) : nullptr;
   { ProfScope ps(c.prof, c.st, b.dw.k == 3 ? "dwconv3" : "dwconv5", shape_str(Lin.total, Lout.total, b.dw.Cp, b.sh * 10 + b.sw));
-    nn::dwconv(c.st, b.dw.k, b.sh, b.sw, x, Lin.d, Lout.d, Lout.n(), Lout.maxH, Lout.maxW, b.dw.Cp, b.dw.C, b.dw.w, b.dw.b,
-               b.dw_act, b.dw_lab.has, b.dw_lab.a, b.dw_lab.c, y1, pool); }
-  Epilogue epi = make_epi(b.pw, ACT_HSWISH, &b.pw_lab);
-  if (fuse_se) {
+    nn::dwconv(c.st, dw, x, Lin.d, Lout.d, Lout.n(), b.dw.Cp, b.dw.C, b.dw.w, b.dw.b, b.dw_act, b.dw_lab.has, b.dw_lab.a, b.dw_lab.c, y1, pool); }
+  if (tile_rows) {
     float* scale = c.arena->alloc<float>((size_t)Lout.n() * b.dw.Cp);
     { ProfScope ps(c.prof, c.st, "se_pool_fc");
-      nn::se_fc_from_dw(c.st, pool, Lout.d, Lout.n(), chunks, strip_R, strips_pb, b.sew.C, b.dw.Cp, b.sew.w1, b.sew.b1, b.sew.w2,
+      nn::se_fc_from_dw(c.st, pool, Lout.d, Lout.n(), dw.chunks, dw.R, dw.spb, b.sew.C, b.dw.Cp, b.sew.w1, b.sew.b1, b.sew.w2,
                         b.sew.b2, b.sew.Cr, HSIG_LCNET, 0, scale); }
     const int*& dtab = Lout.a_tabs[tile_rows];
     const int stride = tile_rows == 256 ? 3 : 2;
@@ -305,11 +288,10 @@ static float* run_lc(RunCtx& c, const LcBlock& b, const float* x, const Level& L
   } else if (b.se) {
     run_se(c, y1, Lout, b.sew, HSIG_LCNET, 0);
   }
-  int Cpo = chan_pitch(b.cout);
-  float* y2 = c.arena->alloc<float>((size_t)Lout.total * Cpo);
-  const nn::GemmPlan plan = nn::gemm_plan(b.dw.Cp, Lout.total, b.pw.K, b.pw.N, b.pw.Npad, Cpo, 0, epi, stream_cus(c.st));
-  { ProfScope ps(c.prof, c.st, plan.label, shape_str(Lout.total, b.pw.K, b.pw.N, 0));
-    nn::gemm(c.st, plan, y1, b.dw.Cp, Lout.total, b.pw.K, b.pw.w, b.pw.N, b.pw.Npad, y2, Cpo, 0, epi); }
+  if (!y2) y2 = c.arena->alloc<float>((size_t)Lout.total * Cpo);
+  const nn::GemmPlan gp = nn::gemm_plan(b.dw.Cp, Lout.total, b.pw.K, b.pw.N, b.pw.Npad, Cpo, 0, epi, stream_cus(c.st));
+  { ProfScope ps(c.prof, c.st, gp.label, shape_str(Lout.total, b.pw.K, b.pw.N, 0));
+    nn::gemm(c.st, gp, y1, b.dw.Cp, Lout.total, b.pw.K, b.pw.w, b.pw.N, b.pw.Npad, y2, Cpo, 0, epi); }
   return y2;
 }
 
@@ -708,13 +690,6 @@ void SvtrCore::logits_rows(RunCtx& c, const float* z_rows, long long m, float* o
 // ---------------------------------------------------------------------------
 // ClsNet
 // ---------------------------------------------------------------------------
-struct ClsSpec { int k, mid, cout; bool se; int act, sh, sw; };
-static const ClsSpec CLS_SPEC[] = {
-    {3, 8, 8, true, ACT_RELU, 2, 1},      {3, 24, 8, false, ACT_RELU, 2, 1},    {3, 32, 8, false, ACT_RELU, 1, 1},
-    {5, 32, 16, true, ACT_HSWISH, 2, 1},  {5, 88, 16, true, ACT_HSWISH, 1, 1},  {5, 88, 16, true, ACT_HSWISH, 1, 1},
-    {5, 40, 16, true, ACT_HSWISH, 1, 1},  {5, 48, 16, true, ACT_HSWISH, 1, 1},  {5, 104, 32, true, ACT_HSWISH, 2, 1},
-    {5, 200, 32, true, ACT_HSWISH, 1, 1}, {5, 200, 32, true, ACT_HSWISH, 1, 1}};
-
 ClsNet::ClsNet(const Blob& b) {
   pack_stem(ws_, b, "cls.stem", 8, &stem_w_, &stem_b_);
   int cin = 8, i = 0;

@@ -81,6 +81,34 @@ struct LcBlock {
   int sh = 1, sw = 1, cin = 0, cout = 0;
 };
 
+// The block on the kernels of its plan (nn::lc_plan for its shape on level Lout): x at Lin -> the block's output at Lout, pitch
+// chan_pitch(b.cout).  y = null: arena memory; y1: the depthwise output where the plan's route is nn::LC_UNFUSED (null: arena
+// memory; a GEMM tile reads rows past its end, which a caller's buffer must hold).
+nn::LcPlan lc_block_plan(const LcBlock& b, const Level& Lout);
+float* run_lc(RunCtx& c, const LcBlock& b, const float* x, const Level& Lin, const Level& Lout, float* y = nullptr, float* y1 = nullptr);
+
+// The blocks of the three mobile networks (fp32 and fp16 builds of the same graphs)
+struct LcSpec { const char* name; int k, cin, cout, sh, sw; bool se; };
+inline constexpr LcSpec DET_SPEC[] = {
+    {"s2.0", 3, 16, 32, 1, 1, false}, {"s3.0", 3, 32, 48, 2, 2, false}, {"s3.1", 3, 48, 48, 1, 1, false},
+    {"s4.0", 3, 48, 96, 2, 2, false}, {"s4.1", 3, 96, 96, 1, 1, false}, {"s5.0", 3, 96, 192, 2, 2, false},
+    {"s5.1", 5, 192, 192, 1, 1, false}, {"s5.2", 5, 192, 192, 1, 1, false}, {"s5.3", 5, 192, 192, 1, 1, false},
+    {"s5.4", 5, 192, 192, 1, 1, false}, {"s6.0", 5, 192, 384, 2, 2, true}, {"s6.1", 5, 384, 384, 1, 1, true},
+    {"s6.2", 5, 384, 384, 1, 1, false}, {"s6.3", 5, 384, 384, 1, 1, false}};
+inline constexpr LcSpec REC_SPEC[] = {
+    {"s2.0", 3, 16, 32, 1, 1, false}, {"s3.0", 3, 32, 64, 1, 1, false}, {"s3.1", 3, 64, 64, 1, 1, false},
+    {"s4.0", 3, 64, 128, 2, 1, false}, {"s4.1", 3, 128, 128, 1, 1, false}, {"s5.0", 3, 128, 240, 1, 2, false},
+    {"s5.1", 5, 240, 240, 1, 1, false}, {"s5.2", 5, 240, 240, 1, 1, false}, {"s5.3", 5, 240, 240, 1, 1, false},
+    {"s5.4", 5, 240, 240, 1, 1, false}, {"s6.0", 5, 240, 480, 2, 1, true}, {"s6.1", 5, 480, 480, 1, 1, true},
+    {"s6.2", 5, 480, 480, 2, 1, false}, {"s6.3", 5, 480, 480, 1, 1, false}};
+struct ClsSpec { int k, mid, cout; bool se; int act, sh, sw; };
+inline constexpr ClsSpec CLS_SPEC[] = {
+    {3, 8, 8, true, ACT_RELU, 2, 1},      {3, 24, 8, false, ACT_RELU, 2, 1},    {3, 32, 8, false, ACT_RELU, 1, 1},
+    {5, 32, 16, true, ACT_HSWISH, 2, 1},  {5, 88, 16, true, ACT_HSWISH, 1, 1},  {5, 88, 16, true, ACT_HSWISH, 1, 1},
+    {5, 40, 16, true, ACT_HSWISH, 1, 1},  {5, 48, 16, true, ACT_HSWISH, 1, 1},  {5, 104, 32, true, ACT_HSWISH, 2, 1},
+    {5, 200, 32, true, ACT_HSWISH, 1, 1}, {5, 200, 32, true, ACT_HSWISH, 1, 1}};
+Lab get_lab(const Blob& b, const std::string& name);   // the LearnableAffineBlock <name>.a / .c of a blob, where it has one
+
 // The three worker functions as interfaces (RettoInnerWorker::{det,cls,rec}, worker.rs:69-73): the fp32 mobile
 // networks below and the fp16 mobile / server networks of nets_f16.h implement them; the session only sees these.
 class DetModel {

@@ -109,12 +109,6 @@ static Se16 get_ese16(WeightStore& ws, const Blob& b, const std::string& name, i
   s.fc2 = pack_fc32(ws, w, C, C, b.get(name + ".b").data);
   return s;
 }
-static Lab get_lab16(const Blob& b, const std::string& name) {
-  Lab l;
-  if (b.has(name + ".a")) { l.has = 1; l.a = b.get(name + ".a").data[0]; l.c = b.get(name + ".c").data[0]; }
-  return l;
-}
-
 // ---------------------------------------------------------------------------
 // run helpers
 // ---------------------------------------------------------------------------
@@ -181,12 +175,12 @@ static void scale16(RunCtx& c, H16 x, const Level& L, const float* scale, const 
 static LcBlock16 build_lc16(WeightStore& ws, const Blob& b, const std::string& p, int k, int cin, int cout, int sh, int sw, bool se) {
   LcBlock16 blk;
   blk.dw = pack_dw16(ws, b, p + ".dw", cin, k);
-  blk.dw_lab = get_lab16(b, p + ".dw");
+  blk.dw_lab = get_lab(b, p + ".dw");
   blk.dw_act = blk.dw_lab.has ? ACT_HSWISH : ACT_NONE;  // LearnableRepLayer: act only when stride != 2
   blk.se = se;
   if (se) blk.sew = get_se16(ws, b, p + ".se", cin);
   blk.pw = pack_conv16(ws, b, p + ".pw", cout, cin, 1, 1);
-  blk.pw_lab = get_lab16(b, p + ".pw");
+  blk.pw_lab = get_lab(b, p + ".pw");
   blk.sh = sh; blk.sw = sw; blk.cin = cin; blk.cout = cout;
   return blk;
 }
@@ -202,20 +196,6 @@ static H16 run_lc16(RunCtx& c, const LcBlock16& b, H16 x, const Level& Lin, cons
   conv_pw16(c, b.pw, y1, Fout, y2, 0, epi16(b.pw, ACT_HSWISH, &b.pw_lab));
   return y2;
 }
-
-struct LcSpec16 { const char* name; int k, cin, cout, sh, sw; bool se; };
-static const LcSpec16 DET_SPEC16[] = {
-    {"s2.0", 3, 16, 32, 1, 1, false}, {"s3.0", 3, 32, 48, 2, 2, false}, {"s3.1", 3, 48, 48, 1, 1, false},
-    {"s4.0", 3, 48, 96, 2, 2, false}, {"s4.1", 3, 96, 96, 1, 1, false}, {"s5.0", 3, 96, 192, 2, 2, false},
-    {"s5.1", 5, 192, 192, 1, 1, false}, {"s5.2", 5, 192, 192, 1, 1, false}, {"s5.3", 5, 192, 192, 1, 1, false},
-    {"s5.4", 5, 192, 192, 1, 1, false}, {"s6.0", 5, 192, 384, 2, 2, true}, {"s6.1", 5, 384, 384, 1, 1, true},
-    {"s6.2", 5, 384, 384, 1, 1, false}, {"s6.3", 5, 384, 384, 1, 1, false}};
-static const LcSpec16 REC_SPEC16[] = {
-    {"s2.0", 3, 16, 32, 1, 1, false}, {"s3.0", 3, 32, 64, 1, 1, false}, {"s3.1", 3, 64, 64, 1, 1, false},
-    {"s4.0", 3, 64, 128, 2, 1, false}, {"s4.1", 3, 128, 128, 1, 1, false}, {"s5.0", 3, 128, 240, 1, 2, false},
-    {"s5.1", 5, 240, 240, 1, 1, false}, {"s5.2", 5, 240, 240, 1, 1, false}, {"s5.3", 5, 240, 240, 1, 1, false},
-    {"s5.4", 5, 240, 240, 1, 1, false}, {"s6.0", 5, 240, 480, 2, 1, true}, {"s6.1", 5, 480, 480, 1, 1, true},
-    {"s6.2", 5, 480, 480, 2, 1, false}, {"s6.3", 5, 480, 480, 1, 1, false}};
 
 // det input: RGB8 pages -> [pix][8] halves (B, G, R, 0...), or the f32 NHWC-4 tensor of the L1 entry point
 static H16 det_input_u8(RunCtx& c, const nn::U8Page* pages, float scale, const float* mean3, const float* std3, const Level& L0) {
@@ -239,7 +219,7 @@ static H16 input_f32(RunCtx& c, const float* x4, const Level& L0) {
 // ---------------------------------------------------------------------------
 DetNetH::DetNetH(const Blob& b) {
   stem_ = pack_conv16(ws_, b, "det.stem", 16, 3, 3, 3);
-  for (const LcSpec16& s : DET_SPEC16) blocks_.push_back(build_lc16(ws_, b, std::string("det.") + s.name, s.k, s.cin, s.cout, s.sh, s.sw, s.se));
+  for (const LcSpec& s : DET_SPEC) blocks_.push_back(build_lc16(ws_, b, std::string("det.") + s.name, s.k, s.cin, s.cout, s.sh, s.sw, s.se));
   tap_after_[0] = 2; tap_after_[1] = 4; tap_after_[2] = 9; tap_after_[3] = 13;
   const int tap_c[4] = {48, 96, 192, 384}, out_c[4] = {12, 18, 42, 360};
   for (int j = 0; j < 4; j++) {
@@ -325,17 +305,10 @@ float* DetNetH::forward(RunCtx& c, H16 x, Level& L0) {
 // ---------------------------------------------------------------------------
 // ClsNetH
 // ---------------------------------------------------------------------------
-struct ClsSpec16 { int k, mid, cout; bool se; int act, sh, sw; };
-static const ClsSpec16 CLS_SPEC16[] = {
-    {3, 8, 8, true, ACT_RELU, 2, 1},      {3, 24, 8, false, ACT_RELU, 2, 1},    {3, 32, 8, false, ACT_RELU, 1, 1},
-    {5, 32, 16, true, ACT_HSWISH, 2, 1},  {5, 88, 16, true, ACT_HSWISH, 1, 1},  {5, 88, 16, true, ACT_HSWISH, 1, 1},
-    {5, 40, 16, true, ACT_HSWISH, 1, 1},  {5, 48, 16, true, ACT_HSWISH, 1, 1},  {5, 104, 32, true, ACT_HSWISH, 2, 1},
-    {5, 200, 32, true, ACT_HSWISH, 1, 1}, {5, 200, 32, true, ACT_HSWISH, 1, 1}};
-
 ClsNetH::ClsNetH(const Blob& b) {
   stem_ = pack_conv16(ws_, b, "cls.stem", 8, 3, 3, 3);
   int cin = 8, i = 0;
-  for (const ClsSpec16& s : CLS_SPEC16) {
+  for (const ClsSpec& s : CLS_SPEC) {
     const std::string p = "cls.b" + std::to_string(i++);
     B blk;
     blk.expand = pack_conv16(ws_, b, p + ".expand", s.mid, cin, 1, 1);
@@ -454,7 +427,7 @@ float* RecNeck16::run(RunCtx& c, H16 t, const Level& Lb, Level& Lt, const Level&
 // ---------------------------------------------------------------------------
 RecNetH::RecNetH(const Blob& b) {
   stem_ = pack_conv16(ws_, b, "rec.stem", 16, 3, 3, 3);
-  for (const LcSpec16& s : REC_SPEC16) blocks_.push_back(build_lc16(ws_, b, std::string("rec.") + s.name, s.k, s.cin, s.cout, s.sh, s.sw, s.se));
+  for (const LcSpec& s : REC_SPEC) blocks_.push_back(build_lc16(ws_, b, std::string("rec.") + s.name, s.k, s.cin, s.cout, s.sh, s.sw, s.se));
   neck_.load(ws_, b, "rec", 480);
 }
 

@@ -4,6 +4,7 @@
 #pragma once
 #include "common.h"
 #include "gemm_plan.h"
+#include "lc_plan.h"
 
 namespace rt {
 namespace nn {
@@ -28,7 +29,6 @@ void gemm_dma(hipStream_t st, const float* A, int lda, long long M, int K, const
 void gemm_split(hipStream_t st, const float* A, int lda, long long M, int K, const float* Wp, int N, int Npad16, float* C,
                 int ldc, int coff, const Epilogue& epi);
 void gemm_split_forget(const float* Wp);   // drops the cached split planes of a weight pack (before its memory is freed / reused)
-extern int g_dw_sweep;      // A/B: column-sweep depthwise kernels on short maps (0: off; rt_debug_set_variants bit 9)
 
 // Dense stride-1 "same" convolution, kernel (KH,KW) in {(3,3),(1,3)}; W packed as
 // [ceil(Cin/KC)][KH*KW][Npad16][KC].
@@ -41,14 +41,15 @@ int conv13_flat_nt(long long rows, int Npad16, int cus);   // column tiles (16 c
 void conv_sp(hipStream_t st, int KH, int KW, const float* x, int ldx, const ImgGeom* geom, int n_img, int maxH,
              int maxW, int Cin, const float* Wp, int N, int Npad16, float* y, int ldy, const Epilogue& epi);
 
-// Depthwise KxK (K in {3,5}), stride (sh,sw), pad K/2.  Wd packed [K*K][Cp].
+// Depthwise KxK (K in {3,5}), stride (sh,sw), pad K/2.  Wd packed [K*K][Cp]: the kernel of dw_plan() (lc_plan.h).
 void dwconv(hipStream_t st, int K, int sh, int sw, const float* x, const ImgGeom* gin, const ImgGeom* gout, int n_img,
             int maxHo, int maxWo, int Cp, int C, const float* Wd, const float* bias, int act, int has_lab,
             float lab_a, float lab_c, float* y, float* pool = nullptr);  // Cp = channel pitch (chan_pitch), C = real channels
-bool dwconv_sweeps(int K, int sh, int sw, int Cp, int maxHo, bool pool);   // the layer runs on k_dwconv_sweep (g_dw_sweep and its shape)
-// Fused squeeze-excite pooling: with `pool` (n_img * chunks * Cp floats, dwconv_pool_layout) the depthwise
-// kernel also writes per-block channel sums of its output; se_fc_from_dw turns them into the scales.
-void dwconv_pool_layout(int K, int sh, int sw, int Cp, int maxHo, int maxWo, int* chunks, int* strip_R, int* strips_per_block);
+// ... with the plan already made (p = dw_plan() of the same shape, pooled = pool != nullptr; callers that also need its layout).
+// Fused squeeze-excite pooling: with `pool` (n_img * p.chunks * Cp floats) the depthwise kernel also writes per-block channel
+// sums of its output; se_fc_from_dw turns them into the scales (chunks, strip_R = p.R, strips_per_block = p.spb).
+void dwconv(hipStream_t st, const DwPlan& p, const float* x, const ImgGeom* gin, const ImgGeom* gout, int n_img, int Cp, int C,
+            const float* Wd, const float* bias, int act, int has_lab, float lab_a, float lab_c, float* y, float* pool = nullptr);
 void se_fc_from_dw(hipStream_t st, const float* partial, const ImgGeom* geom, int n_img, int chunks, int strip_R,
                    int strips_per_block, int C, int Cp, const float* w1, const float* b1, const float* w2, const float* b2,
                    int Cr, float slope, int residual, float* scale);
@@ -67,26 +68,15 @@ void cls_block(hipStream_t st, int k, int sh, bool se, int act, const float* x, 
                int maxH_in, int maxW, int max_pix_out, int cin, int mid, int mid_cp, int cout, const float* Wexp, const float* bexp,
                const float* Wdw, const float* bdw, const float* w1, const float* b1, const float* w2, const float* b2, int cr, float slope,
                const float* Wlin, const float* blin, bool shortcut, float* y, float* dscr);   // dscr: n_pixels_out x round_up(mid, 16) floats when se
-// Fused thin LCNetV3 block (3x3 depthwise -> 1x1 conv, C_in <= 64, no SE): see k_lc_thin.
-bool lc_thin_supported(int K, int sh, int sw, int Cp, int C, int Npad16);
-void lc_thin(hipStream_t st, int sh, int sw, const float* x, const ImgGeom* gin, const ImgGeom* gout, int n_img, int maxHo,
-             int maxWo, int Cp, int C, const float* Wd, const float* bd, int dw_act, int dw_has_lab, float dw_a, float dw_c,
-             const float* Wp, int N, int Npad16, float* y, int ldy, const Epilogue& epi);
-// one-wave-per-tile form of the same block (nn_lcwave.hip): activations never touch LDS; bit-identical to lc_thin
-extern int g_lc_wave;
-// the kernel lc_thin() runs for a block under the current g_lc_wave (LC_UNFUSED: no fused form has an instance; lc_thin() throws and
-// the caller runs nn::dwconv + nn::gemm).  lc_thin() dispatches on it, rt_debug_lc_block reports it.
-enum LcRoute { LC_UNFUSED = 0, LC_THIN = 1, LC_WAVE = 2, LC_LDS = 3 };
-LcRoute lc_route(int K, int sh, int sw, int Cp, int C, int N, int Npad16, int dw_act, int dw_has_lab, const Epilogue& epi, int maxHo,
-                 int maxWo, int ldy);
-bool lc_wave_runs_lds(int sh, int sw, int Cp, int Npad16);   // lc_wave() launches k_lc_lds (else k_lc_wave) for a block it supports
-// either form has an instance for the block (what run_lc asks before it takes the fused path)
-bool lc_block_supported(int K, int sh, int sw, int Cp, int C, int N, int Npad16, int dw_act, int dw_has_lab, const Epilogue& epi,
-                        int maxHo, int maxWo);
-bool lc_wave_supported(int K, int sh, int sw, int Cp, int C, int N, int Npad16, int dw_act, int dw_has_lab, const Epilogue& epi);
-void lc_wave(hipStream_t st, int sh, int sw, const float* x, const ImgGeom* gin, const ImgGeom* gout, int n_img, int maxHo,
-             int maxWo, int Cp, int C, const float* Wd, const float* bd, int dw_act, int dw_has_lab, float dw_a, float dw_c,
-             const float* Wp, int N, int Npad16, float* y, int ldy, const Epilogue& epi);
+// Fused thin LCNetV3 block (3x3 depthwise -> 1x1 conv, C_in <= 64, no SE) on the kernel lc_plan() names (lc_plan.h): lc_thin() for
+// LcPlan::route == LC_THIN (k_lc_thin, workgroup-staged), lc_wave() for LC_WAVE / LC_LDS (nn_lcwave.hip: one wave per tile, the
+// activations never touch LDS / staged in wave-private LDS).  Bit-identical to each other and to the unfused pair.
+void lc_thin(hipStream_t st, const LcPlan& p, const float* x, const ImgGeom* gin, const ImgGeom* gout, int n_img, int C,
+             const float* Wd, const float* bd, int dw_act, int dw_has_lab, float dw_a, float dw_c, const float* Wp, int N, int Npad16,
+             float* y, int ldy, const Epilogue& epi);
+void lc_wave(hipStream_t st, const LcPlan& p, const float* x, const ImgGeom* gin, const ImgGeom* gout, int n_img, int C,
+             const float* Wd, const float* bd, int dw_act, int dw_has_lab, float dw_a, float dw_c, const float* Wp, int N, int Npad16,
+             float* y, int ldy, const Epilogue& epi);
 
 // 3x3 stride-2 stem on a 3(+1 pad)-channel f32 NHWC input. Ws packed [27][COUT]. COUT in {8,16}.
 // One RGB8 page of a det launch group (device pointer; npix = H*W; out_pix = its pixel offset in the group).

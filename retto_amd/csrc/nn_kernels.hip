@@ -693,62 +693,22 @@ __global__ __launch_bounds__(64 * TH) void k_lc_thin(const float* __restrict__ x
   }
 }
 
-int g_lc_wave = getenv("RT_LC_WAVE") ? atoi(getenv("RT_LC_WAVE")) : 3;   // 3 = wave-private LDS form for the stride-1 blocks (nn_lcwave.hip, default); 1 = direct-load form, every shape (A/B); 0 = k_lc_thin
-static int lc_thin_code(int sh, int sw, int Cp, int Npad16) {  // instantiated (stride, C_in/4, column tiles) combinations
-  const int c4 = Cp / 4, nt = (Npad16 + 31) / 32;
-  if (sh == 1 && sw == 1) {
-    if (c4 == 4 && nt == 1) return 1;
-    if (c4 == 8 && nt == 2) return 2;
-    if (c4 == 12 && nt == 2) return 3;
-    if (c4 == 16 && nt == 2) return 4;
-  } else if (sh == 2 && sw == 2) {  // ((2,1) 64 -> 128 of the rec net measured slower fused: 1.37 vs 1.05 ms)
-    if (c4 == 8 && nt == 2) return 6;   // det s3.0: 32 -> 48
-    if (c4 == 12 && nt == 3) return 7;  // det s4.0: 48 -> 96
-  }
-  return 0;
-}
-bool lc_thin_supported(int K, int sh, int sw, int Cp, int C, int Npad16) {
-  return K == 3 && Cp == round_up(C, 4) && lc_thin_code(sh, sw, Cp, Npad16) != 0;
-}
-// (k_lc_lds / k_lc_wave address an image through a 32-bit buffer offset, out-of-range marker 0x80000000: images up to 1 GB)
-static bool lc_wave_fits(int maxHo, int maxWo, int sh, int sw, int Cp, int ldy) {
-  const long long in_bytes = (long long)(maxHo * sh + 2) * (maxWo * sw + 2) * Cp * 4, out_bytes = (long long)maxHo * maxWo * ldy * 4;
-  return in_bytes < (1ll << 30) && out_bytes < (1ll << 30);
-}
-LcRoute lc_route(int K, int sh, int sw, int Cp, int C, int N, int Npad16, int dw_act, int dw_has_lab, const Epilogue& epi, int maxHo,
-                 int maxWo, int ldy) {
-  if (g_lc_wave && lc_wave_supported(K, sh, sw, Cp, C, N, Npad16, dw_act, dw_has_lab, epi) && lc_wave_fits(maxHo, maxWo, sh, sw, Cp, ldy))
-    return lc_wave_runs_lds(sh, sw, Cp, Npad16) ? LC_LDS : LC_WAVE;
-  return lc_thin_supported(K, sh, sw, Cp, C, Npad16) ? LC_THIN : LC_UNFUSED;
-}
-bool lc_block_supported(int K, int sh, int sw, int Cp, int C, int N, int Npad16, int dw_act, int dw_has_lab, const Epilogue& epi,
-                        int maxHo, int maxWo) {
-  return lc_route(K, sh, sw, Cp, C, N, Npad16, dw_act, dw_has_lab, epi, maxHo, maxWo, chan_pitch(N)) != LC_UNFUSED;
-}
-void lc_thin(hipStream_t st, int sh, int sw, const float* x, const ImgGeom* gin, const ImgGeom* gout, int n_img, int maxHo,
-             int maxWo, int Cp, int C, const float* Wd, const float* bd, int dw_act, int dw_has_lab, float dw_a, float dw_c,
-             const float* Wp, int N, int Npad16, float* y, int ldy, const Epilogue& epi) {
+// k_lc_thin on the instance and grid lc_plan() chose (p.route == LC_THIN)
+void lc_thin(hipStream_t st, const LcPlan& p, const float* x, const ImgGeom* gin, const ImgGeom* gout, int n_img, int C,
+             const float* Wd, const float* bd, int dw_act, int dw_has_lab, float dw_a, float dw_c, const float* Wp, int N, int Npad16,
+             float* y, int ldy, const Epilogue& epi) {
   if (n_img <= 0) return;
   if (epi.residual || epi.a_scale) throw RtError(8, "lc_thin: residual / a_scale epilogues are not supported");
-  const LcRoute route = lc_route(3, sh, sw, Cp, C, N, Npad16, dw_act, dw_has_lab, epi, maxHo, maxWo, ldy);
-  if (route == LC_WAVE || route == LC_LDS) {
-    lc_wave(st, sh, sw, x, gin, gout, n_img, maxHo, maxWo, Cp, C, Wd, bd, dw_act, dw_has_lab, dw_a, dw_c, Wp, N, Npad16, y, ldy, epi);
-    return;
-  }
-  // measured per shape: 64-pixel tiles (TH = 4: more workgroups per CU) win from 48 channels up, 128-pixel tiles below
-  const int code = lc_thin_code(sh, sw, Cp, Npad16);
-  const int TH = code >= 6 || Cp >= 48 ? 4 : 8, tpb = 8;
-  const int tiles = ((maxWo + 15) / 16) * ((maxHo + TH - 1) / TH);
-  dim3 grid((tiles + tpb - 1) / tpb, n_img);
-#define RT_LCT(CC, NN, TT, S1, S2) RT_LAUNCH((k_lc_thin<CC, NN, TT, S1, S2>), grid, dim3(64 * TT), 0, st, x, gin, gout, C, Wd, bd, dw_act, dw_has_lab, dw_a, dw_c, Wp, N, Npad16, y, ldy, epi, tpb)
-  switch (code) {
+  const dim3 grid(p.grid_x, n_img);
+#define RT_LCT(CC, NN, TT, S1, S2) RT_LAUNCH((k_lc_thin<CC, NN, TT, S1, S2>), grid, dim3(64 * TT), 0, st, x, gin, gout, C, Wd, bd, dw_act, dw_has_lab, dw_a, dw_c, Wp, N, Npad16, y, ldy, epi, LC_THIN_TPB)
+  switch (p.route == LC_THIN ? p.inst : 0) {
     case 1: RT_LCT(4, 1, 8, 1, 1); break;
     case 2: RT_LCT(8, 2, 8, 1, 1); break;
     case 3: RT_LCT(12, 2, 4, 1, 1); break;
     case 4: RT_LCT(16, 2, 4, 1, 1); break;
     case 6: RT_LCT(8, 2, 4, 2, 2); break;
     case 7: RT_LCT(12, 3, 4, 2, 2); break;
-    default: throw RtError(8, "lc_thin: unsupported shape (check lc_thin_supported)");
+    default: throw RtError(8, "lc_thin: the plan names no k_lc_thin instance");
   }
 #undef RT_LCT
 }
@@ -1427,7 +1387,6 @@ __global__ __launch_bounds__(256, 4) void k_dwconv_rows(const float* __restrict_
 // which are then added in that kernel's order.
 // ---------------------------------------------------------------------------
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-constexpr int DW_SWEEP_POOL_STRIPS = 4;   // strips of PR rows a pooled column may cross (LDS: 4 KB each)
 template <int K, int LP, int PX, int WAVES, int SH = 1, int SW = 1, int PR = 0>
 __global__ __launch_bounds__(256, WAVES) void k_dwconv_sweep(const float* __restrict__ x, const ImgGeom* __restrict__ gin,
                                                            const ImgGeom* __restrict__ gout, int Cp, int C,
@@ -1442,7 +1401,7 @@ __global__ __launch_bounds__(256, WAVES) void k_dwconv_sweep(const float* __rest
   __shared__ __attribute__((aligned(16))) float psl[PR ? DW_SWEEP_POOL_STRIPS * 256 * 4 : 4];   // [strip of the block][lane] x 4 channels
   const ImgGeom gi = gin[blockIdx.y], go = gout[blockIdx.y];
   const int strips_x = (go.W + PX - 1) / PX;
-  const int strips_y = PR ? (go.H + PRD - 1) / PRD : 1;   // <= DW_SWEEP_POOL_STRIPS: go.H <= maxHo, which dwconv() checks
+  const int strips_y = PR ? (go.H + PRD - 1) / PRD : 1;   // <= DW_SWEEP_POOL_STRIPS: go.H <= maxHo, which dw_plan() bounds
   if ((int)blockIdx.x * SPB >= strips_x) return;
   const int cbase = blockIdx.z * LP * 4;
   const int tid = threadIdx.x;
@@ -1570,103 +1529,42 @@ __global__ __launch_bounds__(256, WAVES) void k_dwconv_sweep(const float* __rest
   }
 }
 
-static int dw_lanes_per_pixel(int K, int sh, int sw, int R, int Cp, bool pool);
-int g_dw_sweep = getenv("RT_DW_SWEEP") ? atoi(getenv("RT_DW_SWEEP")) : 4;   // column-sweep kernels on short maps (0: off)
-// Output rows per thread of k_dwconv_rows: 4 (stride 1) or 2 (stride 2); 3 for the 3- and 6-row maps of the
-// recognition net's last stages, where 4-row (2-row) strips would leave a quarter of the lanes' rows empty.
-// It is also the strip height of the squeeze-excite partial sums (dwconv_pool_layout), whichever kernel writes them: the pooled
-// k_dwconv_sweep instances add the outputs strip by strip in this kernel's order, so the value stays part of the results.
-// (Measured with those instances: the 3-row strips' layers, 6-row maps, were the ones that re-read most -- 10 row reads for 6
-// rows at stride 1, 18 for 12 at stride (2, 1): 1.23-1.36 x their input at the fabric, 1.05 x on the sweep.)
-static int dw_strip_rows(int sh, int maxHo) {
-  if (maxHo == 6 || (maxHo == 3 && sh == 1)) return 3;  // (stride 2 onto 3 rows: 2-row strips measured faster)
-  return sh == 1 ? 4 : 2;
-}
-
-// Which k_dwconv_sweep instance runs the layer (0: none, k_dwconv_rows does).  The one place that decides it.
-static int dw_sweep_form(int K, int sh, int sw, int R, int lp, int maxHo, bool pool) {
-  if (!g_dw_sweep || lp != 16 || maxHo * sh > 24) return 0;
-  const bool pool3 = pool && R == 3 && (maxHo + 2) / 3 <= DW_SWEEP_POOL_STRIPS;
-  if (K == 5 && sh == 1 && sw == 1 && maxHo >= 5) return !pool ? 1 : pool3 ? 3 : 0;
-  if (K == 3 && sh == 1 && sw == 1 && maxHo >= 3 && !pool) return 2;
-  if (K == 5 && sh == 2 && sw == 1 && maxHo >= 3) return !pool ? 4 : pool3 ? 5 : 0;
-  if (K == 3 && sh == 1 && sw == 2 && maxHo >= 3 && !pool) return 6;
-  return 0;
-}
-bool dwconv_sweeps(int K, int sh, int sw, int Cp, int maxHo, bool pool) {
-  if ((K != 3 && K != 5) || sh < 1 || sh > 2 || sw < 1 || sw > 2) return false;
-  const int R = dw_strip_rows(sh, maxHo);
-  return dw_sweep_form(K, sh, sw, R, dw_lanes_per_pixel(K, sh, sw, R, Cp, pool), maxHo, pool) != 0;
-}
-
 void dwconv(hipStream_t st, int K, int sh, int sw, const float* x, const ImgGeom* gin, const ImgGeom* gout, int n_img,
             int maxHo, int maxWo, int Cp, int C, const float* Wd, const float* bias, int act, int has_lab, float lab_a,
             float lab_c, float* y, float* pool) {
+  dwconv(st, dw_plan(K, sh, sw, Cp, maxHo, maxWo, pool != nullptr), x, gin, gout, n_img, Cp, C, Wd, bias, act, has_lab, lab_a, lab_c, y, pool);
+}
+
+void dwconv(hipStream_t st, const DwPlan& p, const float* x, const ImgGeom* gin, const ImgGeom* gout, int n_img, int Cp, int C,
+            const float* Wd, const float* bias, int act, int has_lab, float lab_a, float lab_c, float* y, float* pool) {
   if (n_img <= 0) return;
-  if ((K == 3 || K == 5) && sh >= 1 && sh <= 2 && sw >= 1 && sw <= 2) {
-    const int R = dw_strip_rows(sh, maxHo);  // input rows streamed: stride 1 -> R+K-1, stride 2 -> 2R+K-2
-    long long strips = (long long)((maxWo + 3) / 4) * ((maxHo + R - 1) / R);
-    // 64-channel slabs (256 contiguous bytes per pixel and load) for wide tensors: the 5x5 kernel on 256 channels goes from
-    // 2.9 to 4.1 TB/s with them; 32-channel slabs otherwise
-    const int lp = dw_lanes_per_pixel(K, sh, sw, R, Cp, pool != nullptr);
-    // short, wide maps: one thread column sweeps the whole height, every input row fetched once (RT_DW_SWEEP=0: off).  The 5x5
-    // stride-1 layers of the 12-row maps, the 3x3 stride-1 layer of the 128-channel maps (k_dwconv_rows fetched 1.33x its output
-    // there: 6-row patches of 4-row strips, PMC), and the recognition net's strided and squeeze-excite layers, whose pooled partial
-    // sums keep the layout and the values of the row kernel's (dwconv_pool_layout: 3-row strips).
-    if (const int form = dw_sweep_form(K, sh, sw, R, lp, maxHo, pool != nullptr)) {
-      const int spb = 256 / 16;
-      dim3 grids((unsigned)(((maxWo + 3) / 4 + spb - 1) / spb), n_img, (Cp + 63) / 64);
-      const int pitch = (int)((strips + spb - 1) / spb);   // pooled partials per image: the row kernel's blocks
-      if (pool && (maxHo + R - 1) / R > DW_SWEEP_POOL_STRIPS) throw RtError(8, "dwconv: pooled sweep on a map of more strips than its LDS holds");
-#define RT_DWS(KK, WV, SH_, SW_, PR_) RT_LAUNCH((k_dwconv_sweep<KK, 16, 4, WV, SH_, SW_, PR_>), grids, dim3(256), 0, st, x, gin, gout, Cp, C, Wd, bias, act, has_lab, lab_a, lab_c, y, pool, pitch)
-      switch (form) {
-        case 1: RT_DWS(5, 3, 1, 1, 0); break;
-        case 2: RT_DWS(3, 4, 1, 1, 0); break;
-        case 3: RT_DWS(5, 3, 1, 1, 3); break;
-        case 4: RT_DWS(5, 4, 2, 1, 0); break;
-        case 5: RT_DWS(5, 3, 2, 1, 3); break;   // (waves per SIMD of each instance: see the kernel's header)
-        default: RT_DWS(3, 4, 1, 2, 0); break;
-      }
-#undef RT_DWS
-      return;
-    }
-    if (lp == 16) {
-      const int spb = 256 / 16;
-      dim3 gridw((unsigned)((strips + spb - 1) / spb), n_img, (Cp + 63) / 64);
-#define RT_DWW(KK, RR, SH_, SW_)                                                                                             \
-  do {                                                                                                                       \
-    if (pool) RT_LAUNCH((k_dwconv_rows<KK, RR, SH_, SW_, 1, 16>), gridw, dim3(256), 0, st, x, gin, gout, Cp, C, Wd, bias, act, has_lab, lab_a, lab_c, y, pool); \
-    else RT_LAUNCH((k_dwconv_rows<KK, RR, SH_, SW_, 0, 16>), gridw, dim3(256), 0, st, x, gin, gout, Cp, C, Wd, bias, act, has_lab, lab_a, lab_c, y, pool); \
-  } while (0)
-      if (K == 5 && sh == 1 && sw == 1 && R == 4) { RT_DWW(5, 4, 1, 1); return; }
-      if (K == 5 && sh == 1 && sw == 1 && R == 3) { RT_DWW(5, 3, 1, 1); return; }
-      if (K == 5 && sh == 2 && sw == 1 && R == 2) { RT_DWW(5, 2, 2, 1); return; }
-      if (K == 5 && sh == 2 && sw == 1 && R == 3) { RT_DWW(5, 3, 2, 1); return; }
-      if (K == 5 && sh == 2 && sw == 2 && R == 2) { RT_DWW(5, 2, 2, 2); return; }
-      if (K == 3 && sh == 1 && sw == 1 && R == 4 && !pool) { RT_DWW(3, 4, 1, 1); return; }
-      if (K == 3 && sh == 1 && sw == 2 && R == 4 && !pool) { RT_DWW(3, 4, 1, 2); return; }
-#undef RT_DWW
-      throw RtError(8, "dwconv: no wide-slab instantiation for a shape dw_lanes_per_pixel() lists");
-    }
-    dim3 grid((unsigned)((strips + 31) / 32), n_img, (Cp + 31) / 32);
-#define RT_DWR(KK, RR, SH_, SW_)                                                                                              \
-  do {                                                                                                                       \
-    if (pool) RT_LAUNCH((k_dwconv_rows<KK, RR, SH_, SW_, 1>), grid, dim3(256), 0, st, x, gin, gout, Cp, C, Wd, bias, act, has_lab, lab_a, lab_c, y, pool); \
-    else RT_LAUNCH((k_dwconv_rows<KK, RR, SH_, SW_, 0>), grid, dim3(256), 0, st, x, gin, gout, Cp, C, Wd, bias, act, has_lab, lab_a, lab_c, y, pool); \
-  } while (0)
-    const int code = (K == 5 ? 4 : 0) + (sh == 2 ? 2 : 0) + (sw == 2 ? 1 : 0);
-#define RT_DWR_R(KK, SH_, SW_, RBIG) do { if (R == 3) RT_DWR(KK, 3, SH_, SW_); else RT_DWR(KK, RBIG, SH_, SW_); } while (0)
-    switch (code) {
-      case 0: RT_DWR_R(3, 1, 1, 4); break; case 1: RT_DWR_R(3, 1, 2, 4); break;
-      case 2: RT_DWR_R(3, 2, 1, 2); break; case 3: RT_DWR_R(3, 2, 2, 2); break;
-      case 4: RT_DWR_R(5, 1, 1, 4); break; case 5: RT_DWR_R(5, 1, 2, 4); break;
-      case 6: RT_DWR_R(5, 2, 1, 2); break; default: RT_DWR_R(5, 2, 2, 2); break;
-    }
+  if (p.kernel == DwKernel::invalid) throw RtError(8, "dwconv: unsupported kernel size / stride");
+  const dim3 grid(p.grid_x, n_img, p.grid_z);
+#define RT_DW_ARGS x, gin, gout, Cp, C, Wd, bias, act, has_lab, lab_a, lab_c, y, pool
+  // (pooled sweep: the partials per image are the row kernel's blocks, p.chunks)
+#define RT_DWS(INST, KK, WV, SH_, SW_, PR_) \
+  case INST: RT_LAUNCH((k_dwconv_sweep<KK, 16, 4, WV, SH_, SW_, PR_>), grid, dim3(256), 0, st, RT_DW_ARGS, p.chunks); return;
+#define RT_DWR1(LP, KK, RR, SH_, SW_) \
+  case dw_rows_inst(LP, KK, RR, SH_, SW_): RT_LAUNCH((k_dwconv_rows<KK, RR, SH_, SW_, 0, LP>), grid, dim3(256), 0, st, RT_DW_ARGS); return;
+#define RT_DWR(LP, KK, RR, SH_, SW_)                                                                                  \
+  case dw_rows_inst(LP, KK, RR, SH_, SW_):                                                                            \
+    if (pool) RT_LAUNCH((k_dwconv_rows<KK, RR, SH_, SW_, 1, LP>), grid, dim3(256), 0, st, RT_DW_ARGS);                \
+    else RT_LAUNCH((k_dwconv_rows<KK, RR, SH_, SW_, 0, LP>), grid, dim3(256), 0, st, RT_DW_ARGS);                     \
+    return;
+#define RT_DWR_R(LP, KK, SH_, SW_, RBIG) RT_DWR(LP, KK, 3, SH_, SW_) RT_DWR(LP, KK, RBIG, SH_, SW_)
+  switch (p.inst) {
+    RT_DWS(1, 5, 3, 1, 1, 0) RT_DWS(2, 3, 4, 1, 1, 0) RT_DWS(3, 5, 3, 1, 1, 3)   // (waves per SIMD of each instance: see the kernel's header)
+    RT_DWS(4, 5, 4, 2, 1, 0) RT_DWS(5, 5, 3, 2, 1, 3) RT_DWS(6, 3, 4, 1, 2, 0)
+    RT_DWR_R(16, 5, 1, 1, 4) RT_DWR_R(16, 5, 2, 1, 2) RT_DWR(16, 5, 2, 2, 2) RT_DWR1(16, 3, 4, 1, 1) RT_DWR1(16, 3, 4, 1, 2)
+    RT_DWR_R(8, 3, 1, 1, 4) RT_DWR_R(8, 3, 1, 2, 4) RT_DWR_R(8, 3, 2, 1, 2) RT_DWR_R(8, 3, 2, 2, 2)
+    RT_DWR_R(8, 5, 1, 1, 4) RT_DWR_R(8, 5, 1, 2, 4) RT_DWR_R(8, 5, 2, 1, 2) RT_DWR_R(8, 5, 2, 2, 2)
+  }
 #undef RT_DWR_R
 #undef RT_DWR
-    return;
-  }
-  throw RtError(8, "dwconv: unsupported kernel size / stride");
+#undef RT_DWR1
+#undef RT_DWS
+#undef RT_DW_ARGS
+  throw RtError(8, "dwconv: the plan names no kernel instance");
 }
 
 // ---------------------------------------------------------------------------
@@ -2103,25 +2001,6 @@ void se_scale_projected(hipStream_t st, const float* x_in, const ImgGeom* geom, 
   const int nt = se_fc_threads(Cp, Cin_p);
   RT_LAUNCH(k_se_fc, dim3(n_img), dim3(nt), se_fc_lds(Cp, Cr, Cin_p, true, nt), st, partial, geom, chunks, C, Cp,
                      w1, b1, w2, b2, Cr, slope, residual, scale, 0, 32, Wlin, Cin, Cin_p);
-}
-// Lanes side by side on a pixel in k_dwconv_rows for this layer: 16 / 32 (64- / 128-channel slabs) where the tensor is
-// wide AND a wide instantiation exists for the shape, else 8 (32-channel slabs).  The one place that decides it: the
-// launch (dwconv) and the layout of the fused pooling partials (dwconv_pool_layout -> k_se_fc) must agree.
-static int dw_lanes_per_pixel(int K, int sh, int sw, int R, int Cp, bool pool) {
-  // 64-channel slabs from 192 channels (5x5) / 128 channels (3x3) up, for the shapes with a wide-slab instantiation
-  if (K == 5 && Cp >= 192) {
-    if (sh == 1 && sw == 1 && (R == 4 || R == 3)) return 16;
-    if (sh == 2 && sw == 1 && (R == 2 || R == 3)) return 16;
-    if (sh == 2 && sw == 2 && R == 2) return 16;
-  } else if (K == 3 && Cp >= 128) {
-    if (sh == 1 && (sw == 1 || sw == 2) && R == 4 && !pool) return 16;
-  }
-  return 8;
-}
-void dwconv_pool_layout(int K, int sh, int sw, int Cp, int maxHo, int maxWo, int* chunks, int* strip_R, int* strips_per_block) {
-  const int R = dw_strip_rows(sh, maxHo), spb = 256 / dw_lanes_per_pixel(K, sh, sw, R, Cp, true);
-  *strip_R = R; *strips_per_block = spb;
-  *chunks = (int)(((long long)((maxWo + 3) / 4) * ((maxHo + R - 1) / R) + spb - 1) / spb);
 }
 void se_fc_from_dw(hipStream_t st, const float* partial, const ImgGeom* geom, int n_img, int chunks, int strip_R,
                    int strips_per_block, int C, int Cp, const float* w1, const float* b1, const float* w2, const float* b2,

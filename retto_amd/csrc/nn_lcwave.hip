@@ -75,7 +75,7 @@ struct LcwArgs {   // (compact: the kernel keeps its scalars in SGPRs; a spilled
 };
 
 // DWA: the depthwise half ends in hardswish + LAB (stride 1) or in nothing (stride 2).  The pointwise half always ends in
-// hardswish + LAB (lc_wave_supported() leaves a block without it to k_lc_thin).  C_in = 16 G and N = 16 NT exactly: no channel masks.
+// hardswish + LAB (lc_plan() leaves a block without it to k_lc_thin).  C_in = 16 G and N = 16 NT exactly: no channel masks.
 template <int G, int NT, int MT, bool DWA>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) void k_lc_wave(LcwArgs p) {
   constexpr int CP = G * 16, NKC = (CP + KC - 1) / KC, NCOL = NT * 16;
@@ -424,75 +424,23 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE, WPE)))
   }
 }
 
-// instantiated (stride, C_in / 16, N / 16): the thin blocks of the two LCNetV3 backbones
-static int lc_wave_code(int sh, int sw, int Cp, int Npad16) {
-  const int gq = Cp / 16, nt = Npad16 / 16;
-  if (Cp % 16 || Npad16 % 16) return 0;
-  if (sh == 1 && sw == 1) {
-    if (gq == 1 && nt == 2) return 1;   // 16 -> 32
-    if (gq == 2 && nt == 4) return 2;   // 32 -> 64
-    if (gq == 3 && nt == 3) return 3;   // 48 -> 48
-    if (gq == 4 && nt == 4) return 4;   // 64 -> 64
-  } else if (sh == 2 && sw == 2) {
-    if (gq == 2 && nt == 3) return 6;   // 32 -> 48
-    if (gq == 3 && nt == 6) return 7;   // 48 -> 96
-  } else if (sh == 2 && sw == 1) {
-    if (gq == 4 && nt == 8) return 8;   // 64 -> 128 (rec s4.0; k_lc_lds only)
-  }
-  return 0;
-}
-bool lc_wave_supported(int K, int sh, int sw, int Cp, int C, int N, int Npad16, int dw_act, int dw_has_lab, const Epilogue& epi) {
-  if (K != 3 || Cp != C || N != Npad16 || lc_wave_code(sh, sw, Cp, Npad16) == 0) return false;
-  if (epi.residual || epi.a_scale || epi.am_max || !epi.bias || epi.act != ACT_HSWISH) return false;
-  // the pointwise half always ends in the LAB's fma: with a = 1, c = 0 it would turn the -0 hardswish gives below -3 into +0, one
-  // bit away from k_lc_thin and the unfused pair (tests/test_gpu_rec_kernels.py); every block of the two backbones has the LAB
-  if (!epi.has_lab) return false;
-  // depthwise tail: hardswish + LAB (LearnableRepLayer at stride 1) or nothing (stride 2)
-  // depthwise tail (LearnableRepLayer: the activation is skipped when stride == 2; the rec net's (2, 1) is not 2)
-  return (sh == 2 && sw == 2) ? (dw_act == ACT_NONE && !dw_has_lab) : (dw_act == ACT_HSWISH && dw_has_lab);
-}
-
-// (the direct-load form is kept for the stride-1 blocks only: A/B, RT_LC_WAVE=1)
-bool lc_wave_runs_lds(int sh, int sw, int Cp, int Npad16) { return g_lc_wave >= 3 || lc_wave_code(sh, sw, Cp, Npad16) >= 6; }
-
-void lc_wave(hipStream_t st, int sh, int sw, const float* x, const ImgGeom* gin, const ImgGeom* gout, int n_img, int maxHo,
-             int maxWo, int Cp, int C, const float* Wd, const float* bd, int dw_act, int dw_has_lab, float dw_a, float dw_c,
-             const float* Wp, int N, int Npad16, float* y, int ldy, const Epilogue& epi) {
+// k_lc_lds (p.route == LC_LDS) or k_lc_wave (LC_WAVE) on the instance, tile height and grid lc_plan() chose
+void lc_wave(hipStream_t st, const LcPlan& p, const float* x, const ImgGeom* gin, const ImgGeom* gout, int n_img, int C,
+             const float* Wd, const float* bd, int dw_act, int dw_has_lab, float dw_a, float dw_c, const float* Wp, int N, int Npad16,
+             float* y, int ldy, const Epilogue& epi) {
   if (n_img <= 0) return;
-  if (!lc_wave_supported(3, sh, sw, Cp, C, N, Npad16, dw_act, dw_has_lab, epi)) throw RtError(8, "lc_wave: unsupported block (check lc_wave_supported)");
-  const int code = lc_wave_code(sh, sw, Cp, Npad16);
-  const int tpw = 4;   // tiles per wave
-  if (lc_wave_runs_lds(sh, sw, Cp, Npad16)) {
-    // LDS-staged form: 4-row tiles at stride 1 (2 waves per SIMD), 2-row tiles at stride 2
-    const int mtl = sh == 1 ? 4 : 2;
-    const int tiles = ((maxWo + 15) / 16) * ((maxHo + mtl - 1) / mtl);
-    dim3 grid((tiles + 4 * tpw - 1) / (4 * tpw), n_img);
-    LcwArgs a{x, gin, gout, Wd, bd, Wp, epi.bias, y, dw_a, dw_c, epi.has_lab ? epi.lab_a : 1.f, epi.has_lab ? epi.lab_c : 0.f, Npad16, ldy, tpw};
-#define RT_LCL(GG, NN) RT_LAUNCH((k_lc_lds<GG, NN, 4, 1, 1, true, 2>), grid, dim3(256), 0, st, a)
-    switch (code) {
-      case 1: RT_LCL(1, 2); break;
-      case 2: RT_LCL(2, 4); break;
-      case 3: RT_LCL(3, 3); break;
-      case 4: RT_LCL(4, 4); break;
-      case 6: RT_LAUNCH((k_lc_lds<2, 3, 2, 2, 2, false, 2>), grid, dim3(256), 0, st, a); break;
-      case 7: RT_LAUNCH((k_lc_lds<3, 6, 2, 2, 2, false, 2>), grid, dim3(256), 0, st, a); break;
-      default: RT_LAUNCH((k_lc_lds<4, 8, 2, 2, 1, true, 2>), grid, dim3(256), 0, st, a); break;
-    }
-#undef RT_LCL
-    return;
-  }
-  const int tiles = ((maxWo + 15) / 16) * ((maxHo + 1) / 2);   // 2-row tiles
-  dim3 grid((tiles + 4 * tpw - 1) / (4 * tpw), n_img);
-  LcwArgs a{x, gin, gout, Wd, bd, Wp, epi.bias, y, dw_a, dw_c, epi.has_lab ? epi.lab_a : 1.f, epi.has_lab ? epi.lab_c : 0.f, Npad16, ldy, tpw};
-#define RT_LCW(GG, NN) RT_LAUNCH((k_lc_wave<GG, NN, 2, true>), grid, dim3(256), 0, st, a)
-  switch (code) {
-    case 1: RT_LCW(1, 2); break;
-    case 2: RT_LCW(2, 4); break;
-    case 3: RT_LCW(3, 3); break;
-    case 4: RT_LCW(4, 4); break;
-    default: throw RtError(8, "lc_wave: unsupported shape (check lc_wave_supported)");
+  const dim3 grid(p.grid_x, n_img);
+  const LcwArgs a{x, gin, gout, Wd, bd, Wp, epi.bias, y, dw_a, dw_c, epi.has_lab ? epi.lab_a : 1.f, epi.has_lab ? epi.lab_c : 0.f, Npad16, ldy, LC_WAVE_TPW};
+#define RT_LCL(INST, GG, NN, MT, S1, S2, DWA) case 10 * LC_LDS + INST: RT_LAUNCH((k_lc_lds<GG, NN, MT, S1, S2, DWA, 2>), grid, dim3(256), 0, st, a); return;
+#define RT_LCW(INST, GG, NN) case 10 * LC_WAVE + INST: RT_LAUNCH((k_lc_wave<GG, NN, 2, true>), grid, dim3(256), 0, st, a); return;
+  switch (10 * p.route + p.inst) {
+    RT_LCL(1, 1, 2, 4, 1, 1, true) RT_LCL(2, 2, 4, 4, 1, 1, true) RT_LCL(3, 3, 3, 4, 1, 1, true) RT_LCL(4, 4, 4, 4, 1, 1, true)
+    RT_LCL(6, 2, 3, 2, 2, 2, false) RT_LCL(7, 3, 6, 2, 2, 2, false) RT_LCL(8, 4, 8, 2, 2, 1, true)
+    RT_LCW(1, 1, 2) RT_LCW(2, 2, 4) RT_LCW(3, 3, 3) RT_LCW(4, 4, 4)
   }
 #undef RT_LCW
+#undef RT_LCL
+  throw RtError(8, "lc_wave: the plan names no k_lc_lds / k_lc_wave instance");
 }
 
 }  // namespace nn

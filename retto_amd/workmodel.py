@@ -59,8 +59,9 @@ def gemm_pw_label(M: int, K: int, N: int, se: bool = False, min_pix: int = 1 << 
 
 
 def lc_thin_fused(k: int, sh: int, sw: int, cin: int, cout: int, se: bool) -> bool:
-    """Mirror of nn::lc_block_supported: thin 3x3 blocks run as ONE kernel (k_lc_lds, nn_lcwave.hip; k_lc_thin with
-    RT_LC_WAVE=0), whose algorithmic traffic is the block's input + output (the depthwise result never reaches HBM)."""
+    """Mirror of the route of nn::lc_plan() (retto_amd/csrc/lc_plan.cpp; held to it by tests/test_lc_plan_cpu.py): thin 3x3 blocks
+    run as ONE kernel (k_lc_lds, nn_lcwave.hip; k_lc_thin with RT_LC_WAVE=0), whose algorithmic traffic is the block's input +
+    output (the depthwise result never reaches HBM)."""
     if se or k != 3 or cin % 16 or cout % 16:
         return False
     g, nt = cin // 16, cout // 16

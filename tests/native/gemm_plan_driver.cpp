@@ -1,9 +1,16 @@
-// Host-only driver of nn::gemm_plan() / nn::gemm_se_rows() (retto_amd/csrc/gemm_plan.cpp) for tests/test_gemm_plan_cpu.py.
+// Host-only driver of nn::gemm_plan() / nn::gemm_se_rows() (retto_amd/csrc/gemm_plan.cpp) and nn::dw_plan() / nn::lc_plan()
+// (lc_plan.cpp) for tests/test_gemm_plan_cpu.py and tests/test_lc_plan_cpu.py.
 // One query per stdin line, one answer per stdout line:
 //   plan <variant> <dma> <split> <argmax_wide> <cus> <lda> <M> <K> <N> <Npad16> <ldc> <coff>
 //        <am_max> <residual> <a_scale> <a_tab_stride> <act> <has_lab> <n_img> <ld_scale>
 //     -> <kernel> <nt> <kg> <bf> <se> <grid_x> <grid_y> <label, or the error of an invalid plan>
 //   se_rows <variant> <dma> <split> <lda> <M> <K> <N> <Npad16> <act> <min_pix>  ->  <rows>
+//   dw <dw_sweep> <K> <sh> <sw> <Cp> <maxHo> <maxWo> <pooled>
+//     -> <kernel> <sweep instance, or 0> <R> <lanes> <strips per block> <chunks> <grid_x> <grid_z>
+//   lc <lc_wave> <dw_sweep> <K> <sh> <sw> <Cp> <C> <N> <Npad16> <dw_act> <dw_has_lab> <se> <maxHo> <maxWo> <rows> <min_pix>
+//      <pw_act> <pw_has_lab> <pw_bias>          (the output pitch is chan_pitch(N), as run_lc's)
+//     (lc_wave / dw_sweep -1: what the environment selected when the driver started)
+//     -> thin | wave | lds <instance> <tile rows> <grid_x>    or    unfused <se_rows> <the block's dw answer>
 // (am_max != 0 sets the CTC-head statistics with am_tiles = gemm_argmax_tiles(Npad16); a_scale != 0 sets a scale and a row table)
 #include "nn.h"
 
@@ -33,9 +40,15 @@ static const char* kernel_name(nn::GemmKernel k) {
   return "?";
 }
 
+static void print_dw(const nn::DwPlan& p) {
+  static const char* const names[] = {"invalid", "rows32", "rows64", "sweep"};
+  printf("%s %d %d %d %d %d %u %u\n", names[(int)p.kernel], p.kernel == nn::DwKernel::sweep ? p.inst : 0, p.R, p.lanes, p.spb, p.chunks, p.grid_x, p.grid_z);
+}
+
 int main() {
   static float dummy_f[4];
   static int dummy_i[4];
+  const int env_lc_wave = nn::g_lc_wave, env_dw_sweep = nn::g_dw_sweep;   // what RT_LC_WAVE / RT_DW_SWEEP selected
   std::string line;
   while (std::getline(std::cin, line)) {
     std::istringstream in(line);
@@ -60,6 +73,27 @@ int main() {
       in >> nn::g_gemm_variant >> nn::g_gemm_dma >> nn::g_gemm_split >> lda >> M >> K >> N >> Npad16 >> act >> min_pix;
       if (!in) { printf("bad query\n"); return 2; }
       printf("%d\n", nn::gemm_se_rows(lda, M, K, N, Npad16, act, min_pix));
+    } else if (op == "dw") {
+      int dw_sweep, K, sh, sw, Cp, maxHo, maxWo, pooled;
+      in >> dw_sweep >> K >> sh >> sw >> Cp >> maxHo >> maxWo >> pooled;
+      if (!in) { printf("bad query\n"); return 2; }
+      nn::g_dw_sweep = dw_sweep < 0 ? env_dw_sweep : dw_sweep;
+      print_dw(nn::dw_plan(K, sh, sw, Cp, maxHo, maxWo, pooled != 0));
+    } else if (op == "lc") {
+      nn::LcShape s;
+      Epilogue e;
+      int lc_wave, dw_sweep, se, bias;
+      in >> lc_wave >> dw_sweep >> s.K >> s.sh >> s.sw >> s.Cp >> s.C >> s.N >> s.Npad16 >> s.dw_act >> s.dw_has_lab >> se >> s.maxHo >>
+          s.maxWo >> s.rows >> s.min_pix >> e.act >> e.has_lab >> bias;
+      if (!in) { printf("bad query\n"); return 2; }
+      nn::g_lc_wave = lc_wave < 0 ? env_lc_wave : lc_wave;
+      nn::g_dw_sweep = dw_sweep < 0 ? env_dw_sweep : dw_sweep;
+      s.se = se != 0; s.ldy = chan_pitch(s.N);
+      if (bias) e.bias = dummy_f;
+      const nn::LcPlan p = nn::lc_plan(s, e);
+      static const char* const routes[] = {"unfused", "thin", "wave", "lds"};
+      if (p.route != nn::LC_UNFUSED) printf("%s %d %d %u\n", routes[p.route], p.inst, p.tile_h, p.grid_x);
+      else { printf("unfused %d ", p.se_rows); print_dw(p.dw); }
     } else if (!op.empty()) {
       printf("unknown query %s\n", op.c_str());
       return 2;

@@ -1,36 +1,19 @@
 """The fp32 GEMM kernel choice (retto_amd/csrc/gemm_plan.cpp) on the host: a pinned table of shapes -> (kernel, template choice,
 grid, label), read off the launch rules gemm() had before they moved into the plan, and the work model's label mirror
 (retto_amd/workmodel.py gemm_pw_label) against the plan for every pointwise GEMM of the C3 / C4 networks.  The plan is compiled
-with g++ into tests/native/gemm_plan_driver.cpp: no GPU, no HIP runtime."""
-import os
-import subprocess
-
+with g++ into tests/native/gemm_plan_driver.cpp (tests/plan_driver.py): no GPU, no HIP runtime."""
 import pytest
 
+import plan_driver
+from plan_driver import run as _run
 from retto_amd import workmodel
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "retto_amd", "csrc")
 HSWISH, RELU = 2, 1
 
 
 @pytest.fixture(scope="module")
 def driver(tmp_path_factory):
-    exe = str(tmp_path_factory.mktemp("gemm_plan") / "gemm_plan_driver")
-    cmd = ["g++", "-std=c++17", "-O1", "-Wall", "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include", "-I" + CSRC,
-           os.path.join(ROOT, "tests", "native", "gemm_plan_driver.cpp"), os.path.join(CSRC, "gemm_plan.cpp"), "-o", exe]
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    assert r.returncode == 0, "the plan driver does not build:\n" + r.stderr[-3000:]
-    return exe
-
-
-def _run(exe, queries, env=None):
-    r = subprocess.run([exe], input="".join(q + "\n" for q in queries), capture_output=True, text=True, timeout=120,
-                       env=dict(os.environ, **(env or {})))
-    assert r.returncode == 0, r.stdout[-500:] + r.stderr[-500:]
-    out = r.stdout.splitlines()
-    assert len(out) == len(queries)
-    return out
+    return plan_driver.build(tmp_path_factory)
 
 
 def _pitch(c):

@@ -24,7 +24,7 @@ inputs off by da (first term, through |Wp|), adds the error of its own K-term su
 Measured on an MI355X, worst err / bound over the batch (k_lc_lds; torch float32 on the CPU in brackets): 16->32 0.039 (0.043),
 32->64 0.031 (0.028), 48->48 0.023 (0.025), 64->64 0.020 (0.018), 32->48 /2 0.041 (0.043), 48->96 /2 0.035 (0.038), 64->128
 /(2, 1) 0.024 (0.020); rms error 1.00-1.05 x torch's.  Without the pointwise LAB the barrier-free kernels were one bit off form 0
-(+0 for the -0 hardswish gives below -3: their LAB fma ran with a = 1, c = 0); lc_wave_supported() now leaves such a block to
+(+0 for the -0 hardswish gives below -3: their LAB fma ran with a = 1, c = 0); lc_plan() leaves such a block to
 k_lc_thin / the unfused pair, and the routes asserted here say so.
 
 (b) 1x3 token convs, N = 60 with swish, cin = 480 (inside rows of pitch 960 whose upper half holds noise) and 960: form 1
