@@ -528,6 +528,46 @@ RT_API int rt_debug_layernorm(rt_session* s, const float* x, const float* r, lon
 RT_API int rt_debug_glue16(rt_session* s, int op, const int* ip, const float* fp, const int* src_h, const int* src_w,
                            const int* dst_h, const int* dst_w, int n_img, const float* x, long long x_len, const float* x2,
                            long long x2_len, const float* tab, long long tab_len, float* out, long long out_len);
+/* One launch of a kernel of the fp32 detector's neck or head (nn_fpn.hip and the FPN glue of nn_kernels.hip) on host arrays, through
+ * the launcher DetNet::run calls, for the numerics tests.  n_img images of fine_h[i] x fine_w[i] pixels are the op's finest
+ * level and coarse_h / coarse_w the next coarser one where the op has one (always passed; ignored otherwise); levels below that
+ * are derived by halving.  A coarse level that is not exactly half of its fine level is rejected: DetNet::run never passes one.
+ * in[10] / in_len[10] are the operand arrays (float32, whole buffers, lengths in floats; NULL / 0 where the op or its flags do not
+ * use a slot), out[3] / out_len[3] the outputs: each is filled with RT_DEBUG_CANARY before the launch, has 64 spare rows past its
+ * last one and is returned whole.  Weights arrive in torch layout and go through the packers of the networks (pack_conv,
+ * fpn_fine_weights, fpn_phase_weights, fpn_class_weights, fpn_lateral_weights, fpn_tap_weights); w = a 3x3 conv [24][96][3][3],
+ * lat = a bias-free lateral 1x1 conv [96][cin].  pf / pc = pixels of all fine / coarse images, cf = cin rounded up to 4.
+ *   op 0 phase         ip = {cin, cc, flags}: flags 1 bias, 2 pool, 4 relu, 8 G, 16 fine scale, 32 coarse scale, 64 compose first.
+ *                      in: 0 fine [pf][cf], 1 coarse [pc][cc], 2 w, 3 bias [24], 4 Wf [n_img][9][24][cf] (cin < 24 without
+ *                      compose), 5 lat, 6 lat scale [n_img][96] (compose: nn::fpn_compose runs first in the same call and its
+ *                      output is the launch's Wf), 7 fine scale [n_img][24], 8 coarse scale [n_img][24], 9 G [9][pc / 4][24].
+ *                      cin is 12, 18 or 24, nothing else.  cin = 24 is the head conv (cc = 24: fine = channels 72 .. 95 of w, coarse = 48 .. 71; scales and G only
+ *                      here), cin < 24 an inp conv (cc = 96: coarse = all of w).  out: 0 y [(pf + 64) * 24], 1 the per-tile
+ *                      pool sums [(n_img * tiles + 64) * 24] with tiles = those of the largest height x the largest width,
+ *                      2 the composed weights [(n_img * 216 + 64) * cf].  info_out[0] = the k_fpn_phase instance as
+ *                      CF4 * 100 + NS * 10 + HASG.
+ *   op 1 class         ip = {c0, flags}: c0 = first of the 24 input channels of w, flags 1 bias, 2 scale, 4 lower.  in: 0 z [pf][24],
+ *                      1 w, 2 bias, 3 scale [n_img][24], 4 lower [9][pc][24].  out: 0 V [(9 * pf + 64) * 24].
+ *   op 2 compose       ip = {cin}, 12 or 18.  in: 0 lat, 1 scale [n_img][96], 2 w.  out: 0 [(n_img * 216 + 64) * cf].
+ *   op 3 tail          nn::db_head_tail.  in: 0 x [pf][24], 1 deconv1 w [24][24][2][2], 2 its bias [24], 3 deconv2 w [24][1][2][2],
+ *                      4 its bias [1].  out: 0 the map at four times the fine sides [16 * pf + 1024].
+ *   op 4 lateral_add   ip = {cin, has b}.  in: 0 x [pf][cf], 1 lat, 2 scale [n_img][96], 3 b [pc][96].  out: 0 [(pf + 64) * 96].
+ *   op 5 upsample_add  ip = {in place, has scale}.  in: 0 a [pf][96], 1 b [pc][96], 2 scale [n_img][96].  out: 0 [(pf + 64) * 96]
+ *                      (in place: the buffer holds a before the launch and is both operand and output).
+ *   op 6 se_projected  ip = {cin, Cr, residual}, fp = {slope}.  in: 0 x [pf][cf], 1 lat, 2 fc1 w [Cr][96], 3 fc1 b, 4 fc2 w [96][Cr],
+ *                      5 fc2 b.  out: 0 the scales [(n_img + 64) * 96].
+ *   op 7 se_tiles      ip = {Cr, residual}, fp = {slope}.  in: 0 pool sums [n_img][tiles][24] as op 0 leaves them, 1 .. 4 the FCs for
+ *                      24 channels.  out: 0 the scales [(n_img + 64) * 24].
+ *   op 8 head_fused    nn::conv3_fpn_fused.  ip = {flags}: 1 / 2 / 4 / 8 scale of p5 / p4 / p3 / p2, 16 bias, 32 relu.  in: 0 .. 3
+ *                      p5, p4, p3, p2 [pixels of the level][24] (fine = p2's level, sides multiples of 8), 4 w, 5 bias, 6 .. 9 the
+ *                      scales [n_img][24].  out: 0 [(pf + 64) * 24].
+ *   op 9 conv3         nn::conv_sp(3, 3) at 96 -> 24.  ip = {flags}: 1 bias, 2 relu.  in: 0 x [pf][96], 1 w, 2 bias.  out: 0
+ *                      [(pf + 64) * 24].  info_out[0] = NG of the k_conv3_few<NG> instance that ran (0: k_conv_sp).
+ * Everything the kernel can address is checked against the lengths before any device work, and like the two fp16 entries this
+ * one looks at its session last. */
+RT_API int rt_debug_fpn(rt_session* s, int op, const int* ip, const float* fp, const int* fine_h, const int* fine_w,
+                        const int* coarse_h, const int* coarse_w, int n_img, const float* const* in, const long long* in_len,
+                        float* const* out, const long long* out_len, int* info_out);
 /* One nh::conv16 launch as the fp16 networks issue it, on host arrays, for the numerics tests.  n_img images of heights[i] x
  * widths[i] pixels, consecutive in x as a level is; the output images follow the networks' rule (ceil(side / stride); the input
  * geometry for the 2x2 phase convs).  ip[20] = cin, ldx, xoff (the input is channels [xoff, xoff + cin) of rows of pitch ldx),

@@ -67,7 +67,7 @@ EXPORTS = [
     "rt_set_lanes", "rt_profile_enable", "rt_profile_get",
     "rt_onnx_to_rtwb", "rt_buffer_free", "rt_model_manifest", "rt_decode_image", "rt_run_encoded_batch",
     "rt_submit_encoded_batch", "rt_decode_batch", "rt_debug_jpeg_reconstruct",
-    "rt_debug_set_variants", "rt_bench_gemm", "rt_bench_gemm_err", "rt_bench_lc", "rt_debug_conv16", "rt_debug_gemm", "rt_debug_dwconv", "rt_debug_attention", "rt_debug_lc_block", "rt_debug_conv13", "rt_debug_layernorm", "rt_debug_glue16", "rt_debug_conv16x", "rt_parse_dictionary", "rt_format_f32", "rt_rccl_unique_id", "rt_broadcast_blobs",
+    "rt_debug_set_variants", "rt_bench_gemm", "rt_bench_gemm_err", "rt_bench_lc", "rt_debug_conv16", "rt_debug_gemm", "rt_debug_dwconv", "rt_debug_attention", "rt_debug_lc_block", "rt_debug_conv13", "rt_debug_layernorm", "rt_debug_glue16", "rt_debug_conv16x", "rt_debug_fpn", "rt_parse_dictionary", "rt_format_f32", "rt_rccl_unique_id", "rt_broadcast_blobs",
     "rt_run_regions", "rt_debug_warp_crops",
 ]
 
@@ -199,6 +199,8 @@ def load():
     lib.rt_debug_glue16.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
                                     C.c_void_p, C.c_longlong, C.c_void_p, C.c_longlong, C.c_void_p, C.c_longlong, C.c_void_p,
                                     C.c_longlong]
+    lib.rt_debug_fpn.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.rt_debug_conv16x.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_longlong,
                                      C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p,
                                      C.c_longlong, C.c_void_p]

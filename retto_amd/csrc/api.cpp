@@ -677,7 +677,7 @@ RT_API void rt_debug_set_variants(int gemm_variant, int dw_variant, int flags) {
   nn::g_lc_wave = (flags & 128) ? 0 : lc_wave0;
   nn::g_gemm_dma = (flags & 256) ? 0 : gemm_dma0;
   nn::g_dw_sweep = (flags & 512) ? 0 : dw_sweep0;
-  nn::g_fpn_phase_off = (flags & 2048) ? 1 : 0;   // (bit 11: RSEFPN / DB-head convs as the round-3 launch series; equal to fp32 rounding, not bit-identical)
+  nn::g_fpn_phase_off = (flags & 2048) ? 1 : 0;   // (bit 11: RSEFPN / DB-head convs as the round-3 launch series; not bit-identical: both forms stand against fp64 in tests/test_gpu_fpn_kernels.py)
   nn::g_gemm_split = (flags & 4096) ? 1 : g_default_gemm_split;   // (bit 12: the split-bf16 form of the wide rec-net GEMMs, opt-in)
   nn::g_cls_fused = (flags & 1024) ? 0 : cls_fused0;   // (bit 10: the classifier's blocks as the unfused launch series; fp32-tolerance equal, not bit-identical)
 }
@@ -1351,6 +1351,244 @@ RT_API int rt_debug_glue16(rt_session* s, int op, const int* ip, const float* fp
     } else {
       RT_HIP_CHECK(hipMemcpy(out, dout, (size_t)out_n * sizeof(float), hipMemcpyDeviceToHost));
     }
+  });
+}
+
+// One launch of a kernel of the fp32 det neck / head on host arrays, for tests/test_gpu_fpn_kernels.py (include/retto_hip.h lists
+// the ops and their operand slots): the launchers of nn.h as DetNet::run issues them, the weights through the packers DetNet's
+// constructor calls.  Every address a kernel can form is checked against the callers' lengths first; the session is looked at last.
+namespace {
+enum FpnOp { FPN_PHASE = 0, FPN_CLASS, FPN_COMPOSE, FPN_TAIL, FPN_LATERAL_ADD, FPN_UPSAMPLE_ADD, FPN_SE_PROJECTED, FPN_SE_TILES,
+             FPN_HEAD_FUSED, FPN_CONV3, FPN_COUNT };
+constexpr int FPN_IN = 10, FPN_OUT = 3;
+}  // namespace
+RT_API int rt_debug_fpn(rt_session* s, int op, const int* ip, const float* fp, const int* fine_h, const int* fine_w,
+                        const int* coarse_h, const int* coarse_w, int n_img, const float* const* in, const long long* in_len,
+                        float* const* out, const long long* out_len, int* info_out) {
+  RT_REQUIRE(ip && fp && fine_h && fine_w && coarse_h && coarse_w && in && in_len && out && out_len && info_out, s, "rt_debug_fpn: null argument");
+  RT_REQUIRE(op >= 0 && op < FPN_COUNT && n_img > 0 && n_img <= 256, s, "rt_debug_fpn: bad op or image count");
+  // the levels: 0 = fine, 1 = coarse (given), 2 / 3 = half of the one before (derived, where the op reads them)
+  std::vector<ImgGeom> lv[4];
+  long long pix[4] = {0, 0, 0, 0}, max_pix[4] = {0, 0, 0, 0};
+  int maxH = 0, maxW = 0;
+  for (int i = 0; i < n_img; i++) {
+    RT_REQUIRE(fine_h[i] > 0 && fine_w[i] > 0 && coarse_h[i] > 0 && coarse_w[i] > 0 && fine_h[i] <= 4096 && fine_w[i] <= 4096 &&
+                   coarse_h[i] <= 4096 && coarse_w[i] <= 4096, s, "rt_debug_fpn: empty or oversized image");
+    maxH = std::max(maxH, fine_h[i]); maxW = std::max(maxW, fine_w[i]);
+  }
+  const bool has_coarse = op == FPN_PHASE || op == FPN_UPSAMPLE_ADD || op == FPN_HEAD_FUSED || (op == FPN_CLASS && (ip[1] & 4)) ||
+                          (op == FPN_LATERAL_ADD && ip[1]);
+  const int n_levels = op == FPN_HEAD_FUSED ? 4 : (op == FPN_PHASE && (ip[2] & 8)) ? 3 : has_coarse ? 2 : 1;
+  for (int l = 0; l < n_levels; l++)
+    for (int i = 0; i < n_img; i++) {
+      int h = fine_h[i], w = fine_w[i];
+      if (l >= 1) {
+        h = l == 1 ? coarse_h[i] : lv[l - 1][i].H / 2; w = l == 1 ? coarse_w[i] : lv[l - 1][i].W / 2;
+        RT_REQUIRE(h > 0 && w > 0 && lv[l - 1][i].H == 2 * h && lv[l - 1][i].W == 2 * w, s,
+                   "rt_debug_fpn: a level that is not exactly twice the next coarser one");
+      }
+      lv[l].push_back(ImgGeom{pix[l], h, w, 0});
+      pix[l] += (long long)h * w; max_pix[l] = std::max(max_pix[l], (long long)h * w);
+    }
+  RT_REQUIRE(pix[0] < (1ll << 20), s, "rt_debug_fpn: too large");
+  const long long pf = pix[0], pc = pix[1];
+  const int tiles = ((maxW + 15) / 16) * ((maxH + 15) / 16);
+  // what the op reads (floats per slot; 0 = unused) and writes (rows and pitch per output)
+  long long need[FPN_IN] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, out_rows[FPN_OUT] = {0, 0, 0};
+  int out_ld[FPN_OUT] = {0, 0, 0};
+  const long long W33 = 24ll * 96 * 9;
+  bool ok = true, inst = true;
+  int cin = 0, cf = 0, flags = 0;
+  switch (op) {
+    case FPN_PHASE: {
+      cin = ip[0]; cf = round_up(std::max(cin, 1), 4); flags = ip[2];
+      const int cc = ip[1];
+      const bool head = cin == 24;
+      ok = cin > 0 && cin <= 24 && cc > 0 && cc <= 96 && flags >= 0 && flags < 128 && !((flags & 8) && (flags & 1));
+      // (what DetNet::run passes: the tap tensors of 12 / 18 channels over a 96-channel level, the head's 24 over 24)
+      inst = ok && (cin == 12 || cin == 18 || cin == 24) && cc == (head ? 24 : 96) && nn::fpn_phase_instance(cin, cc, (flags & 8) != 0) != 0 &&
+             (head ? !(flags & 64) : !(flags & (8 | 16 | 32)));
+      if (!ok || !inst) break;
+      need[0] = pf * cf; need[1] = pc * cc; need[2] = W33; need[3] = (flags & 1) ? 24 : 0;
+      need[4] = (!head && !(flags & 64)) ? (long long)n_img * 216 * cf : 0;
+      need[5] = (flags & 64) ? 96ll * cin : 0; need[6] = (flags & 64) ? (long long)n_img * 96 : 0;
+      need[7] = (flags & 16) ? (long long)n_img * 24 : 0; need[8] = (flags & 32) ? (long long)n_img * 24 : 0;
+      need[9] = (flags & 8) ? 9 * pix[2] * 24 : 0;
+      out_rows[0] = pf; out_ld[0] = 24;
+      if (flags & 2) { out_rows[1] = (long long)n_img * tiles; out_ld[1] = 24; }
+      if (flags & 64) { out_rows[2] = (long long)n_img * 216; out_ld[2] = cf; }
+    } break;
+    case FPN_CLASS:
+      flags = ip[1];
+      ok = ip[0] >= 0 && ip[0] <= 72 && ip[0] % 24 == 0 && flags >= 0 && flags < 8;
+      need[0] = pf * 24; need[1] = W33; need[2] = (flags & 1) ? 24 : 0; need[3] = (flags & 2) ? (long long)n_img * 24 : 0;
+      need[4] = (flags & 4) ? 9 * pc * 24 : 0;
+      out_rows[0] = 9 * pf; out_ld[0] = 24;
+      break;
+    case FPN_COMPOSE:
+      cin = ip[0]; cf = round_up(std::max(cin, 1), 4);
+      ok = cin > 0 && cin <= 24;
+      inst = ok && (cin == 12 || cin == 18) && nn::fpn_phase_instance(cin, 96, false) != 0;
+      need[0] = 96ll * cin; need[1] = (long long)n_img * 96; need[2] = W33;
+      out_rows[0] = (long long)n_img * 216; out_ld[0] = cf;
+      break;
+    case FPN_TAIL:
+      need[0] = pf * 24; need[1] = 24 * 24 * 4; need[2] = 24; need[3] = 24 * 4; need[4] = 1;
+      out_rows[0] = 16 * pf; out_ld[0] = 1;
+      break;
+    case FPN_LATERAL_ADD:
+      cin = ip[0]; cf = round_up(std::max(cin, 1), 4);
+      ok = cin > 0 && cin <= 64 && (ip[1] == 0 || ip[1] == 1);
+      need[0] = pf * cf; need[1] = 96ll * cin; need[2] = (long long)n_img * 96; need[3] = ip[1] ? pc * 96 : 0;
+      out_rows[0] = pf; out_ld[0] = 96;
+      break;
+    case FPN_UPSAMPLE_ADD:
+      ok = (ip[0] == 0 || ip[0] == 1) && (ip[1] == 0 || ip[1] == 1);
+      need[0] = pf * 96; need[1] = pc * 96; need[2] = ip[1] ? (long long)n_img * 96 : 0;
+      out_rows[0] = pf; out_ld[0] = 96;
+      break;
+    case FPN_SE_PROJECTED:
+      cin = ip[0]; cf = round_up(std::max(cin, 1), 4);
+      ok = cin > 0 && cin <= 64 && ip[1] > 0 && ip[1] <= 96 && (ip[2] == 0 || ip[2] == 1) && fp[0] > 0.f && fp[0] <= 1.f;
+      need[0] = pf * cf; need[1] = 96ll * cin; need[2] = 96ll * ip[1]; need[3] = ip[1]; need[4] = 96ll * ip[1]; need[5] = 96;
+      out_rows[0] = n_img; out_ld[0] = 96;
+      break;
+    case FPN_SE_TILES:
+      ok = ip[0] > 0 && ip[0] <= 24 && (ip[1] == 0 || ip[1] == 1) && fp[0] > 0.f && fp[0] <= 1.f;
+      need[0] = (long long)n_img * tiles * 24; need[1] = 24ll * ip[0]; need[2] = ip[0]; need[3] = 24ll * ip[0]; need[4] = 24;
+      out_rows[0] = n_img; out_ld[0] = 24;
+      break;
+    case FPN_HEAD_FUSED:
+      flags = ip[0];
+      ok = flags >= 0 && flags < 64;
+      for (int l = 0; l < 4; l++) { need[l] = pix[3 - l] * 24; need[6 + l] = (flags & (1 << l)) ? (long long)n_img * 24 : 0; }
+      need[4] = W33; need[5] = (flags & 16) ? 24 : 0;
+      out_rows[0] = pf; out_ld[0] = 24;
+      break;
+    case FPN_CONV3:
+      flags = ip[0];
+      ok = flags >= 0 && flags < 4;
+      need[0] = pf * 96; need[1] = W33; need[2] = (flags & 1) ? 24 : 0;
+      out_rows[0] = pf; out_ld[0] = 24;
+      break;
+  }
+  RT_REQUIRE(ok, s, "rt_debug_fpn: bad parameters for the op");
+  RT_REQUIRE(inst, s, "rt_debug_fpn: no kernel instance for this channel split");
+  for (int i = 0; i < FPN_IN; i++)
+    RT_REQUIRE(need[i] == 0 || (in[i] && in_len[i] >= need[i]), s, "rt_debug_fpn: an operand is missing or too short");
+  long long out_n[FPN_OUT];
+  for (int i = 0; i < FPN_OUT; i++) {
+    out_n[i] = out_ld[i] ? (out_rows[i] + (op == FPN_TAIL ? 1024 : 64)) * out_ld[i] : 0;   // (the map: 64 spare 4 x 4 blocks)
+    RT_REQUIRE(out_n[i] == 0 || (out[i] && out_len[i] == out_n[i]), s, "rt_debug_fpn: an output is missing or has the wrong length");
+  }
+  RT_REQUIRE(s, s, "rt_debug_fpn: null session");
+  return guarded(s, [&] {
+    RT_HIP_CHECK(hipSetDevice(s->device));
+    DevBufs bufs;
+    WeightStore ws;
+    hipStream_t st = s->st;
+    const ImgGeom* dg[4] = {nullptr, nullptr, nullptr, nullptr};
+    for (int l = 0; l < n_levels; l++) {
+      ImgGeom* d = bufs.alloc<ImgGeom>(n_img);
+      RT_HIP_CHECK(hipMemcpy(d, lv[l].data(), n_img * sizeof(ImgGeom), hipMemcpyHostToDevice));
+      dg[l] = d;
+    }
+    float* dout[FPN_OUT] = {nullptr, nullptr, nullptr};
+    for (int i = 0; i < FPN_OUT; i++)
+      if (out_n[i]) {
+        dout[i] = bufs.alloc<float>((size_t)out_n[i]);
+        RT_HIP_CHECK(hipMemsetD32Async((hipDeviceptr_t)dout[i], (int)RT_DEBUG_CANARY, (size_t)out_n[i], st));
+      }
+    RT_HIP_CHECK(hipStreamSynchronize(st));   // (the copies below are not ordered with the stream)
+    const bool in_place = op == FPN_UPSAMPLE_ADD && ip[0];
+    auto raw = [&](int slot) -> const float* { return need[slot] ? upload_as<float>(bufs, in[slot], (size_t)need[slot]) : nullptr; };
+    info_out[0] = 0;
+    switch (op) {
+      case FPN_PHASE: {
+        const int cc = ip[1];
+        const bool head = cin == 24;
+        nn::FpnPhaseArgs a;
+        a.fine = raw(0); a.ld_fine = cf; a.coarse = raw(1); a.ld_coarse = cc;
+        if (head) {   // as DetNet's head conv: w = [p5 | p4 | p3 | p2], the fine level is p2, the coarse one p3
+          a.Wf = ws.upload(fpn_fine_weights(in[2], 96, 72, 24, 24)); a.wf_img = 0;
+          a.Wc = ws.upload(fpn_phase_weights(in[2], 96, 48, 24));
+        } else {
+          a.Wc = ws.upload(fpn_phase_weights(in[2], 96, 0, 96)); a.wf_img = (long long)216 * cf;
+          if (flags & 64) {
+            const float* lat = ws.upload(fpn_lateral_weights(in[5], cin, 96));
+            const float* wm = ws.upload(fpn_tap_weights(in[2], 96));
+            nn::fpn_compose(st, lat, cin, 96, raw(6), wm, cf, n_img, dout[2]);
+            a.Wf = dout[2];
+          } else {
+            a.Wf = raw(4);
+          }
+        }
+        a.fine_scale = raw(7); a.ld_fs = 24; a.coarse_scale = raw(8); a.ld_cs = 24;
+        if (flags & 8) { a.G = raw(9); a.gg = dg[2]; a.g_plane = pix[2]; }
+        a.bias = raw(3); a.y = dout[0]; a.ldy = 24;
+        if (flags & 2) { a.pool = dout[1]; a.pool_tiles = tiles; }
+        a.act = (flags & 4) ? ACT_RELU : ACT_NONE;
+        info_out[0] = nn::fpn_phase_instance(cin, cc, a.G != nullptr);
+        nn::fpn_phase(st, a, cin, cc, dg[0], dg[1], n_img, maxH, maxW);
+      } break;
+      case FPN_CLASS: {
+        const float* wcls = ws.upload(fpn_class_weights(in[1], 96, ip[0]));
+        const float* z = raw(0); const float* bias = raw(2); const float* scale = raw(3); const float* lower = raw(4);
+        nn::fpn_class(st, z, 24, scale, 24, dg[0], n_img, max_pix[0], wcls, bias, lower, lower ? dg[1] : nullptr, lower ? pc : 0, dout[0], pf);
+      } break;
+      case FPN_COMPOSE: {
+        const float* lat = ws.upload(fpn_lateral_weights(in[0], cin, 96));
+        const float* wm = ws.upload(fpn_tap_weights(in[2], 96));
+        nn::fpn_compose(st, lat, cin, 96, raw(1), wm, cf, n_img, dout[0]);
+      } break;
+      case FPN_TAIL: {
+        std::vector<ImgGeom> go(n_img);
+        long long o = 0;
+        for (int i = 0; i < n_img; i++) { go[i] = ImgGeom{o, 4 * lv[0][i].H, 4 * lv[0][i].W, 0}; o += 16ll * lv[0][i].H * lv[0][i].W; }
+        ImgGeom* dgo = bufs.alloc<ImgGeom>(n_img);
+        RT_HIP_CHECK(hipMemcpy(dgo, go.data(), n_img * sizeof(ImgGeom), hipMemcpyHostToDevice));
+        const float* x = raw(0); const float* w1 = raw(1); const float* b1 = raw(2); const float* w2 = raw(3); const float* b2 = raw(4);
+        nn::db_head_tail(st, x, dg[0], dgo, n_img, max_pix[0], w1, b1, w2, b2, dout[0]);
+      } break;
+      case FPN_LATERAL_ADD: {
+        const float* lat = ws.upload(fpn_lateral_weights(in[1], cin, 96));
+        const float* x = raw(0); const float* scale = raw(2); const float* b = raw(3);
+        nn::lateral_add(st, x, cin, cf, lat, 96, scale, b, dg[0], b ? dg[1] : dg[0], n_img, max_pix[0], dout[0]);
+      } break;
+      case FPN_UPSAMPLE_ADD: {
+        const float* a = nullptr;
+        if (in_place) { RT_HIP_CHECK(hipMemcpy(dout[0], in[0], (size_t)need[0] * sizeof(float), hipMemcpyHostToDevice)); a = dout[0]; }
+        else a = raw(0);
+        const float* b = raw(1); const float* scale = raw(2);
+        nn::upsample_add(st, a, b, dg[0], dg[1], n_img, max_pix[0], 96, dout[0], scale);
+      } break;
+      case FPN_SE_PROJECTED: {
+        const float* lat = ws.upload(fpn_lateral_weights(in[1], cin, 96));
+        float* partial = bufs.alloc<float>((size_t)n_img * nn::pool_chunks(max_pix[0]) * cf);
+        const float* x = raw(0); const float* w1 = raw(2); const float* b1 = raw(3); const float* w2 = raw(4); const float* b2 = raw(5);
+        nn::se_scale_projected(st, x, dg[0], n_img, max_pix[0], cin, cf, lat, 96, 96, w1, b1, w2, b2, ip[1], fp[0], ip[2], partial, dout[0]);
+      } break;
+      case FPN_SE_TILES: {
+        const float* pool = raw(0); const float* w1 = raw(1); const float* b1 = raw(2); const float* w2 = raw(3); const float* b2 = raw(4);
+        nn::se_fc_from_tiles(st, pool, dg[0], n_img, tiles, 24, 24, w1, b1, w2, b2, ip[0], fp[0], ip[1], dout[0]);
+      } break;
+      case FPN_HEAD_FUSED: {
+        const PackedDense pw = pack_conv(ws, in[4], (flags & 16) ? in[5] : nullptr, 24, 96, 3, 3);
+        const float* p[4]; const float* sc[4];
+        for (int l = 0; l < 4; l++) { p[l] = raw(l); sc[l] = raw(6 + l); }
+        nn::conv3_fpn_fused(st, p[0], p[1], p[2], p[3], dg[3], dg[2], dg[1], dg[0], n_img, maxH, maxW, 24, sc, pw.w, 24, pw.Npad, dout[0], 24,
+                            make_epi(pw, (flags & 32) ? ACT_RELU : ACT_NONE));
+      } break;
+      case FPN_CONV3: {
+        const PackedDense pw = pack_conv(ws, in[1], (flags & 1) ? in[2] : nullptr, 24, 96, 3, 3);
+        const Epilogue e = make_epi(pw, (flags & 2) ? ACT_RELU : ACT_NONE);
+        info_out[0] = nn::conv_sp_few_groups(3, 3, 24, 24, e);
+        nn::conv_sp(st, 3, 3, raw(0), 96, dg[0], n_img, maxH, maxW, 96, pw.w, 24, pw.Npad, dout[0], 24, e);
+      } break;
+    }
+    RT_HIP_CHECK(hipStreamSynchronize(st));
+    for (int i = 0; i < FPN_OUT; i++)
+      if (out_n[i]) RT_HIP_CHECK(hipMemcpy(out[i], dout[i], (size_t)out_n[i] * sizeof(float), hipMemcpyDeviceToHost));
   });
 }
 

@@ -301,7 +301,7 @@ float* run_lc(RunCtx& c, const LcBlock& b, const float* x, const Level& Lin, con
 // through tap dy = 2 only when py == s - 1, and row Y otherwise.
 // ---------------------------------------------------------------------------
 // [9 taps][24 n][cf] (cf >= cc: zero padded): the channels [c0, c0 + cc) that are convolved at their own resolution
-static std::vector<float> fpn_fine_weights(const float* w, int cin_total, int c0, int cc, int cf) {
+std::vector<float> fpn_fine_weights(const float* w, int cin_total, int c0, int cc, int cf) {
   std::vector<float> o((size_t)9 * 24 * cf, 0.f);
   for (int t = 0; t < 9; t++)
     for (int n = 0; n < 24; n++)
@@ -314,7 +314,7 @@ static void phase_taps(int ph, int t, int* lo, int* hi) {
   else { *lo = t == 0 ? 0 : 2; *hi = t == 0 ? 1 : 2; }
 }
 // [cc / 24 slabs][4 phases (py, px)][4 taps (ty, tx)][24 n][24 k]: conv3x3(up2(z)) as four 2 x 2 convs of z
-static std::vector<float> fpn_phase_weights(const float* w, int cin_total, int c0, int cc) {
+std::vector<float> fpn_phase_weights(const float* w, int cin_total, int c0, int cc) {
   const int ns = cc / 24;
   std::vector<float> o((size_t)ns * 16 * 576, 0.f);
   for (int s = 0; s < ns; s++)
@@ -336,7 +336,7 @@ static std::vector<float> fpn_phase_weights(const float* w, int cin_total, int c
 }
 // [9 classes (row class x 3 + column class)][9 taps (ry + 1, rx + 1)][24 n][24 k] for the 24 channels at c0: class 0 = first row /
 // column of an upsampling block, 1 = interior, 2 = last
-static std::vector<float> fpn_class_weights(const float* w, int cin_total, int c0) {
+std::vector<float> fpn_class_weights(const float* w, int cin_total, int c0) {
   auto span = [](int cls, int r, int* lo, int* hi) {   // taps of the 3-tap axis that land on relative row r (-1, 0, +1); empty: lo > hi
     *lo = 1; *hi = 0;
     if (cls == 0) { if (r == -1) { *lo = 0; *hi = 0; } else if (r == 0) { *lo = 1; *hi = 2; } }
@@ -361,6 +361,22 @@ static std::vector<float> fpn_class_weights(const float* w, int cin_total, int c
   return o;
 }
 
+// [cin][C]: a bias-free 1x1 lateral conv w [C][cin] with the input channel outermost (k_se_fc's projection, k_lateral_add, k_fpn_compose)
+std::vector<float> fpn_lateral_weights(const float* w, int cin, int C) {
+  std::vector<float> lin((size_t)cin * C);
+  for (int n = 0; n < C; n++)
+    for (int k = 0; k < cin; k++) lin[(size_t)k * C + n] = w[(size_t)n * cin + k];
+  return lin;
+}
+// [9 taps][24 n][C m]: the 3x3 conv w [24][C][3][3] tap-major, the operand k_fpn_compose contracts with the lateral matrix
+std::vector<float> fpn_tap_weights(const float* w, int C) {
+  std::vector<float> wm((size_t)9 * 24 * C);
+  for (int t = 0; t < 9; t++)
+    for (int n = 0; n < 24; n++)
+      for (int m = 0; m < C; m++) wm[((size_t)t * 24 + n) * C + m] = w[((size_t)n * C + m) * 9 + t];
+  return wm;
+}
+
 // ---------------------------------------------------------------------------
 // DetNet
 // ---------------------------------------------------------------------------
@@ -373,14 +389,9 @@ DetNet::DetNet(const Blob& b) {
     std::string js = std::to_string(j);
     out_[j] = pack_conv(ws_, b, "det.out" + js, out_c[j], tap_c[j], 1, 1);
     ins_[j] = pack_conv(ws_, b, "det.fpn.ins" + js, 96, out_c[j], 1, 1);
-    {  // the same weights as [cin][96] (bias-free conv: checked by the manifest)
-      const BlobTensor& w = b.get("det.fpn.ins" + js + ".w");
-      std::vector<float> lin((size_t)out_c[j] * 96);
-      for (int n = 0; n < 96; n++)
-        for (int k = 0; k < out_c[j]; k++) lin[(size_t)k * 96 + n] = w.data[(size_t)n * out_c[j] + k];
-      ins_lin_[j] = ws_.upload(lin);
-      has_bias_[j] = b.has("det.fpn.ins" + js + ".b");
-    }
+    // the same weights as [cin][96] (bias-free conv: checked by the manifest)
+    ins_lin_[j] = ws_.upload(fpn_lateral_weights(b.get("det.fpn.ins" + js + ".w").data, out_c[j], 96));
+    has_bias_[j] = b.has("det.fpn.ins" + js + ".b");
     ins_se_[j] = get_se(ws_, b, "det.fpn.ins" + js + ".se", 96);
     inp_[j] = pack_conv(ws_, b, "det.fpn.inp" + js, 24, 96, 3, 3);
     inp_se_[j] = get_se(ws_, b, "det.fpn.inp" + js + ".se", 24);
@@ -395,11 +406,7 @@ DetNet::DetNet(const Blob& b) {
     for (int j = 0; j < 2; j++) {
       const BlobTensor& iw = b.get("det.fpn.inp" + std::to_string(j) + ".w");   // [24][96][3][3]
       inp_wc_[j] = ws_.upload(fpn_phase_weights(iw.data, 96, 0, 96));
-      std::vector<float> wm((size_t)9 * 24 * 96);
-      for (int t = 0; t < 9; t++)
-        for (int n = 0; n < 24; n++)
-          for (int m = 0; m < 96; m++) wm[((size_t)t * 24 + n) * 96 + m] = iw.data[((size_t)n * 96 + m) * 9 + t];
-      inp_wm_[j] = ws_.upload(wm);
+      inp_wm_[j] = ws_.upload(fpn_tap_weights(iw.data, 96));
     }
   }
   dc1_w_ = upload_raw(ws_, b, "det.head.deconv1.w", 24 * 24 * 4); dc1_b_ = upload_raw(ws_, b, "det.head.deconv1.b", 24);

@@ -65,6 +65,13 @@ PackedDw pack_dw(WeightStore& ws, const float* w, const float* bias, int C, int 
 PackedDense pack_linear(WeightStore& ws, const Blob& b, const std::string& name, int cin, int cout);
 PackedDense pack_linear(WeightStore& ws, const float* w, const float* bias, int cin, int cout);   // host w [cin][cout], bias [cout] or null
 float* upload_raw(WeightStore& ws, const Blob& b, const std::string& name, size_t expect_numel);
+// Host-side operands of the upsampling-aware FPN convs (nn_fpn.hip) from a raw 3x3 conv weight w [24][cin_total][3][3]; DetNet's
+// constructor and rt_debug_fpn call the same functions (layouts: at their definitions in nets.cpp).
+std::vector<float> fpn_fine_weights(const float* w, int cin_total, int c0, int cc, int cf);   // [9 taps][24 n][cf]
+std::vector<float> fpn_phase_weights(const float* w, int cin_total, int c0, int cc);          // [cc / 24][4 phases][4 taps][24 n][24 k]
+std::vector<float> fpn_class_weights(const float* w, int cin_total, int c0);                  // [9 classes][9 taps][24 n][24 k]
+std::vector<float> fpn_lateral_weights(const float* w, int cin, int C);                       // 1x1 lateral w [C][cin] -> [cin][C]
+std::vector<float> fpn_tap_weights(const float* w, int C);                                    // w [24][C][3][3] -> [9 taps][24 n][C m]
 // Row-block table of the squeeze-excite-scaled GEMMs (Epilogue::a_tab) over the images of a level, for blocks of tile_rows = 128
 // (2 ints per block) or 256 (3 ints per block, k_gemm32p): se_row_table_len(total, tile_rows) ints.
 size_t se_row_table_len(long long total, int tile_rows);

@@ -38,6 +38,8 @@ bool conv13_flat_supported(int N, int Npad16);
 void conv13_flat(hipStream_t st, const float* x, int ldx, long long rows, const unsigned char* flags, int Cin, const float* Wp, int N,
                  int Npad16, float* y, int ldy, const Epilogue& epi);
 int conv13_flat_nt(long long rows, int Npad16, int cus);   // column tiles (16 channels each) per workgroup conv13_flat() picks on `cus` CUs
+// channel groups NG of the k_conv3_few<NG> instance conv_sp runs a layer on (few output channels: N = 24 -> 6), 0: k_conv_sp
+int conv_sp_few_groups(int KH, int KW, int N, int ldy, const Epilogue& epi);
 void conv_sp(hipStream_t st, int KH, int KW, const float* x, int ldx, const ImgGeom* geom, int n_img, int maxH,
              int maxW, int Cin, const float* Wp, int N, int Npad16, float* y, int ldy, const Epilogue& epi);
 
@@ -138,6 +140,8 @@ struct FpnPhaseArgs {
 };
 extern int g_fpn_phase_off;   // A/B (rt_debug_set_variants bit 11): 1 = the round-3 launch series
 bool fpn_phase_supported(int cf, int cc);
+// the k_fpn_phase<CF4, NS, HASG> instance fpn_phase launches, as CF4 * 100 + NS * 10 + HASG (0: none for this channel split)
+int fpn_phase_instance(int cf, int cc, bool has_g);
 void fpn_phase(hipStream_t st, const FpnPhaseArgs& a, int cf, int cc, const ImgGeom* gf, const ImgGeom* gc, int n_img, int maxH, int maxW);
 // V[9][pixel][24] (plane = pixels of the level) = class tensor of z (24 channels, x scale) for the head conv's up4 / up8 inputs; Wcls [9][9][24 n][24 k];
 // + bias, + lower[implied class][(y >> 1, x >> 1)] (the next coarser level's class tensor) when given.

@@ -930,9 +930,15 @@ __global__ __launch_bounds__(256, 2) void k_conv3_few(const float* __restrict__ 
   const int ty = blockIdx.x / tiles_x, tx = blockIdx.x % tiles_x;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int py = wave * 4 + (lane >> 4), px = lane & 15;   // this lane's pixel (tile-local)
-  f32x4 acc[NG];
+  // A partial sum is closed after every row of taps of every slab (3 * 32 products, FUSE 3 * 24) and added to a running total, as
+  // longk_flush does for the 1x3 convs: in ONE fp32 chain over the 9 * Cin = 864 products of the 96 -> 24 layers the rms error
+  // against fp64 was 3.15 x that of a blocked float32 conv on the CPU (tests/test_gpu_fpn_kernels.py; the suite's rule is 2 x),
+  // with the rows closed it is about 1.1 x.  Two workgroups per CU leave the registers for the second set, barely: NG = 6 takes 251
+  // (FUSE: 254) of 256 VGPRs without a spill -- after a compiler change look at -Rpass-analysis=kernel-resource-usage first.
+  // (All NG share the form; the shipped graphs reach NG = 6 only.)
+  f32x4 acc[NG], tot[NG];
 #pragma unroll
-  for (int i = 0; i < NG; i++) acc[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+  for (int i = 0; i < NG; i++) { acc[i] = f32x4{0.f, 0.f, 0.f, 0.f}; tot[i] = f32x4{0.f, 0.f, 0.f, 0.f}; }
   const int nkc = FUSE ? 4 : (Cin + KC - 1) / KC;
   constexpr int XLD = (HH * HW * CH4 + 255) / 256, WLD = (TAPS * NCH * CH4 + 255) / 256;
   f32x4 px_[XLD], pw_[WLD];
@@ -994,7 +1000,7 @@ __global__ __launch_bounds__(256, 2) void k_conv3_few(const float* __restrict__ 
     __syncthreads();
     if (kc + 1 < nkc) fetch(kc + 1);
 #pragma unroll
-    for (int dy = 0; dy < 3; dy++)
+    for (int dy = 0; dy < 3; dy++) {
 #pragma unroll
       for (int dx = 0; dx < 3; dx++) {
         const float* xr = xs + ((py + dy) * HW + px + dx) * LROW;
@@ -1017,6 +1023,9 @@ __global__ __launch_bounds__(256, 2) void k_conv3_few(const float* __restrict__ 
           }
         }
       }
+#pragma unroll
+      for (int i = 0; i < NG; i++) { tot[i] += acc[i]; acc[i] = f32x4{0.f, 0.f, 0.f, 0.f}; }
+    }
     __syncthreads();
   }
   const int oy = ty * TH + py, ox = tx * TW + px;
@@ -1031,7 +1040,7 @@ __global__ __launch_bounds__(256, 2) void k_conv3_few(const float* __restrict__ 
       f32x4 o;
 #pragma unroll
       for (int j = 0; j < 4; j++) {
-        const float t = epi_val<A, L>(acc[gi][j] + bias[j], epi.act, epi.has_lab, epi.lab_a, epi.lab_c);
+        const float t = epi_val<A, L>(tot[gi][j] + bias[j], epi.act, epi.has_lab, epi.lab_a, epi.lab_c);
         o[j] = (gi * 4 + j < N) ? t : 0.0f;
       }
       *reinterpret_cast<f32x4*>(yr + gi * 4) = o;
@@ -1185,14 +1194,20 @@ void conv13_flat(hipStream_t st, const float* x, int ldx, long long rows, const 
   }
 }
 
+// few output channels that do not fill 16-wide tiles (N = 24: a quarter of k_conv_sp's MFMA work would be padding)
+int conv_sp_few_groups(int KH, int KW, int N, int ldy, const Epilogue& epi) {
+  if (!(KH == 3 && KW == 3 && N % 16 != 0 && N <= 32 && !epi.residual && ldy >= round_up(N, 4))) return 0;
+  const int ng = (N + 3) / 4;
+  return ng == 1 || ng == 2 || ng == 3 || ng == 5 || ng == 6 ? ng : 0;
+}
+
 void conv_sp(hipStream_t st, int KH, int KW, const float* x, int ldx, const ImgGeom* geom, int n_img, int maxH,
              int maxW, int Cin, const float* Wp, int N, int Npad16, float* y, int ldy, const Epilogue& epi) {
   if (n_img <= 0) return;
   int ntiles = Npad16 / 16;
-  // few output channels that do not fill 16-wide tiles (N = 24: a quarter of k_conv_sp's MFMA work would be padding)
-  if (KH == 3 && KW == 3 && N % 16 != 0 && N <= 32 && !epi.residual && ldy >= round_up(N, 4)) {
+  if (const int ng = conv_sp_few_groups(KH, KW, N, ldy, epi)) {
     dim3 gridf(((maxW + 15) / 16) * ((maxH + 15) / 16), n_img);
-    switch ((N + 3) / 4) {
+    switch (ng) {
 #define RT_C3F(n) case n: RT_LAUNCH((k_conv3_few<n>), gridf, dim3(256), 0, st, x, ldx, geom, Cin, Wp, N, Npad16, y, ldy, epi, FpnSrc{}); return;
       RT_C3F(1) RT_C3F(2) RT_C3F(3) RT_C3F(5) RT_C3F(6)
 #undef RT_C3F

@@ -1,7 +1,7 @@
 """The kernel-level debug entry points rt_debug_gemm / rt_debug_attention (tests/test_gpu_ops.py drives them on the GPU) and
 rt_debug_lc_block / rt_debug_conv13 / rt_debug_layernorm (tests/test_gpu_rec_kernels.py) and rt_debug_glue16 / rt_debug_conv16x
-(tests/test_gpu_f16_kernels.py): declared, exported, and null or bad arguments rejected with RT_ERR_INVALID before any device
-work."""
+(tests/test_gpu_f16_kernels.py) and rt_debug_fpn (tests/test_gpu_fpn_kernels.py): declared, exported, and null or bad arguments
+rejected with RT_ERR_INVALID before any device work."""
 import ctypes as C
 import os
 
@@ -17,7 +17,7 @@ def test_debug_symbols_are_declared_and_exported():
     header = open(os.path.join(ROOT, "include", "retto_hip.h")).read()
     lib = _lib.load()
     for name in ("rt_debug_gemm", "rt_debug_attention", "rt_debug_lc_block", "rt_debug_conv13", "rt_debug_layernorm",
-                 "rt_debug_glue16", "rt_debug_conv16x"):
+                 "rt_debug_glue16", "rt_debug_conv16x", "rt_debug_fpn"):
         assert "RT_API int %s(" % name in header
         assert name in _lib.EXPORTS
         assert hasattr(lib, name)
@@ -193,4 +193,76 @@ def test_conv16x_rejects_null_and_bad_arguments_without_a_device():
     lib.rt_last_error.restype = C.c_char_p
     for kw, why in cases:
         assert _conv16x(lib, **kw) == RT_ERR_INVALID, kw
+        assert why in lib.rt_last_error(None).decode(), (kw, lib.rt_last_error(None))
+
+
+def _fpn(lib, s=None, op=0, ip=(12, 96, 1 | 2), fpv=(0.2,), fine=((8, 8), (4, 4)), coarse=((4, 4), (2, 2)), n_img=2, ipp=True, fpp=True,
+         fh=True, cw=True, inp=True, outp=True, info=True, lens=None, short=None, missing=None, out_short=None):
+    """the phase conv <3, 4, 0> with bias and pool on two images, unless the arguments say otherwise; lens = the operands' lengths by
+    slot (pf = 80, pc = 20 pixels), short / missing = a slot one float short / a NULL slot, out_short = an output slot one float short"""
+    i = np.zeros(8, np.int32); i[:len(ip)] = ip   # noqa: E702
+    f = np.zeros(4, np.float32); f[:len(fpv)] = fpv   # noqa: E702
+    g = [np.array(v, np.int32) for v in ([a for a, _ in fine], [b for _, b in fine], [a for a, _ in coarse], [b for _, b in coarse])]
+    if lens is None:
+        lens = {0: 80 * 12, 1: 20 * 96, 2: 24 * 96 * 9, 3: 24, 4: 2 * 216 * 12}
+    olens = {0: (80 + 64) * 24, 1: (2 * 1 + 64) * 24} if isinstance(outp, bool) else dict(outp)
+    arrs = [np.zeros(max(lens.get(k, 0) - (1 if k == short else 0), 1), np.float32) for k in range(10)]
+    ptrs = (C.c_void_p * 10)(*[a.ctypes.data if k in lens and k != missing else None for k, a in enumerate(arrs)])
+    ilen = (C.c_longlong * 10)(*[lens.get(k, 0) - (1 if k == short else 0) for k in range(10)])
+    outs = [np.zeros(max(olens.get(k, 0), 1), np.float32) for k in range(3)]
+    optrs = (C.c_void_p * 3)(*[a.ctypes.data if k in olens else None for k, a in enumerate(outs)])
+    olen = (C.c_longlong * 3)(*[olens.get(k, 0) - (1 if k == out_short else 0) for k in range(3)])
+    p = lambda arr, on: arr.ctypes.data if on else None   # noqa: E731
+    return lib.rt_debug_fpn(s, op, p(i, ipp), p(f, fpp), p(g[0], fh), g[1].ctypes.data, g[2].ctypes.data, p(g[3], cw), n_img,
+                            ptrs if inp else None, ilen, optrs if outp is not False else None, olen, (C.c_int * 1)() if info else None)
+
+
+def test_fpn_rejects_null_and_bad_arguments_without_a_device():
+    """as rt_debug_glue16: the session is looked at last, so every argument check answers with its own message"""
+    lib = _lib.load()
+    null, opn, img, twice, params, inst, operand, output = (
+        "null argument", "bad op or image count", "empty or oversized image", "not exactly twice", "bad parameters for the op",
+        "no kernel instance", "an operand is missing or too short", "an output is missing or has the wrong length")
+    W = 24 * 96 * 9
+    head = {0: 80 * 24, 1: 20 * 24, 2: W, 7: 48, 8: 48, 9: 9 * 5 * 24}        # the head conv with G and both scales
+    head_out = {0: (80 + 64) * 24}
+    cls = {0: 80 * 24, 1: W, 2: 24, 3: 48, 4: 9 * 20 * 24}
+    cases = [({}, "null session"),
+             ({"ip": (24, 24, 8 | 4 | 16 | 32), "lens": head, "outp": head_out}, "null session"),
+             ({"op": 1, "ip": (24, 7), "lens": cls, "outp": {0: (9 * 80 + 64) * 24}}, "null session"),
+             ({"op": 2, "ip": (18,), "lens": {0: 96 * 18, 1: 2 * 96, 2: W}, "outp": {0: (2 * 216 + 64) * 20}}, "null session"),
+             ({"op": 3, "lens": {0: 80 * 24, 1: 2304, 2: 24, 3: 96, 4: 1}, "outp": {0: 16 * 80 + 1024}}, "null session"),
+             ({"ipp": False}, null), ({"fpp": False}, null), ({"fh": False}, null), ({"cw": False}, null), ({"inp": False}, null),
+             ({"outp": False}, null), ({"info": False}, null),
+             ({"op": -1}, opn), ({"op": 10}, opn), ({"n_img": 0}, opn),
+             ({"fine": ((8, 8), (0, 4))}, img), ({"coarse": ((4, 4), (2, 0))}, img), ({"fine": ((8, 5000), (4, 4))}, img),
+             ({"coarse": ((4, 4), (2, 3))}, twice), ({"fine": ((8, 8), (5, 4))}, twice), ({"fine": ((9, 8), (4, 4)), "coarse": ((5, 4), (2, 2))}, twice),
+             # the head's class tensor lives at a quarter of the fine level: 4 x 4 -> 2 x 2 -> 1 x 1, but 6 x 4 -> 3 x 2 has no half
+             ({"ip": (24, 24, 8), "lens": head, "outp": head_out, "fine": ((8, 8), (6, 4)), "coarse": ((4, 4), (3, 2))}, twice),
+             ({"op": 1, "ip": (24, 7), "lens": cls, "outp": {0: (9 * 80 + 64) * 24}, "coarse": ((4, 4), (2, 1))}, twice),
+             ({"ip": (0, 96, 3)}, params), ({"ip": (12, 0, 3)}, params), ({"ip": (12, 96, 128)}, params), ({"ip": (24, 24, 8 | 1)}, params),
+             ({"op": 1, "ip": (12, 0), "lens": cls}, params), ({"op": 1, "ip": (96, 0), "lens": cls}, params), ({"op": 1, "ip": (0, 8), "lens": cls}, params),
+             ({"op": 2, "ip": (0,)}, params), ({"op": 4, "ip": (65, 0)}, params), ({"op": 5, "ip": (2, 0)}, params),
+             ({"op": 6, "ip": (12, 0, 1)}, params), ({"op": 6, "ip": (12, 24, 1), "fpv": (0.0,)}, params), ({"op": 7, "ip": (25, 1)}, params),
+             ({"op": 8, "ip": (64,), "fine": ((8, 8), (16, 8)), "coarse": ((4, 4), (8, 4))}, params),
+             ({"op": 8, "ip": (0,)}, twice),         # (the fused head reads four levels: 4 x 4 has no eighth)
+             ({"op": 9, "ip": (4,)}, params),
+             ({"ip": (12, 24, 3)}, inst), ({"ip": (16, 96, 3)}, inst), ({"ip": (24, 96, 3)}, inst), ({"ip": (8, 96, 3)}, inst),
+             ({"ip": (22, 24, 3)}, inst), ({"ip": (10, 96, 3)}, inst), ({"ip": (17, 96, 3)}, inst), ({"ip": (20, 96, 3)}, inst),   # an instance exists, the net has no such layer
+             ({"ip": (12, 96, 8)}, inst),            # G with an inp conv
+             ({"ip": (12, 96, 16)}, inst),           # a fine scale with an inp conv
+             ({"ip": (24, 24, 64)}, inst),           # compose with the head conv
+             ({"op": 2, "ip": (24,)}, inst), ({"op": 2, "ip": (16,)}, inst), ({"op": 2, "ip": (11,)}, inst), ({"op": 2, "ip": (20,)}, inst),
+             ({"short": 0}, operand), ({"short": 1}, operand), ({"short": 2}, operand), ({"short": 3}, operand), ({"short": 4}, operand),
+             ({"missing": 0}, operand), ({"missing": 3}, operand), ({"missing": 4}, operand),
+             ({"ip": (24, 24, 8 | 16 | 32), "lens": head, "outp": head_out, "short": 9}, operand),
+             ({"ip": (24, 24, 8 | 16 | 32), "lens": head, "outp": head_out, "short": 7}, operand),
+             ({"ip": (24, 24, 8 | 16 | 32), "lens": head, "outp": head_out, "missing": 8}, operand),
+             ({"ip": (12, 96, 3 | 64)}, operand),    # compose first without the lateral matrix and its scales
+             ({"op": 1, "ip": (24, 7), "lens": cls, "outp": {0: (9 * 80 + 64) * 24}, "short": 4}, operand),
+             ({"out_short": 0}, output), ({"out_short": 1}, output), ({"outp": {0: (80 + 64) * 24}}, output),
+             ({"op": 3, "lens": {0: 80 * 24, 1: 2304, 2: 24, 3: 96, 4: 1}, "outp": {0: 16 * 80 + 64}}, output)]
+    lib.rt_last_error.restype = C.c_char_p
+    for kw, why in cases:
+        assert _fpn(lib, **kw) == RT_ERR_INVALID, kw
         assert why in lib.rt_last_error(None).decode(), (kw, lib.rt_last_error(None))
