@@ -186,7 +186,7 @@ void rt_session::begin_call() {
   if (failed) { arena.abandon_pass(); scratch.abandon_pass(); dbws.abandon_pass(); failed = false; }
   arena.reset(); scratch.reset(); pinned.reset(); dbws.reset();   // (dbws too: its mark below must see the previous pass folded in)
   arena.mark_call(); scratch.mark_call(); dbws.mark_call();
-  // (last_error belongs to the API caller's thread -- api.cpp guarded(); lane threads run this function and never touch it)
+  // (last_error belongs to the API caller's thread -- api_internal.h guarded(); lane threads run this function and never touch it)
 }
 // Waiting for the lane's stream.  hipStreamSynchronize spins on the CPU (HIP's default scheduling when there are more CPUs than
 // GPUs): three lanes = three cores at 100 % per rank for the whole step (measured: 3.9 cores busy per rank), which eight ranks
