@@ -317,6 +317,60 @@ RT_API int rt_debug_ctc_candidates(rt_session* s, const float* z5, const float* 
 RT_API int rt_debug_ctc_candidates_host(const float* z5, const float* W, const float* bias, int N, const int32_t* idx,
                                         const float* prob, const int32_t* tokens_per_line, int n_lines, int K,
                                         rt_candidate* cands_out, int32_t* cols_out, int32_t* n_tokens_out);
+/* ---- rec charsets: a line's CTC decode restricted to the characters the caller allows ---------------------------------------
+ * For callers who know what a region can hold (digits in a form field, Latin capitals on a plate).  Filtering tokens afterwards
+ * cannot bring back a runner-up that WAS allowed, and rec_return_candidates only covers the time steps the unrestricted decode
+ * kept; a charset changes the decode itself.  retto_amd/csrc/ctc_charset.h states the rule; in short, for every time step of a
+ * line that carries charset S (a set of class ids that always holds the blank 0):
+ *   - the logits of the step are recomputed in fp32 from the head's input features, as for candidates;
+ *   - the step's class is the one of S with the largest logit (ties to the lower id), its probability the softmax over S only;
+ *   - these replace the fused head's values before the greedy decode: the keep rule, the line score, word boxes, candidates and
+ *     JSON run unchanged over them.  With rec_return_candidates = K ranks >= 1 name classes of S only, with probabilities over
+ *     S; (-1, 0.0f) fills the row when S has fewer than K classes.
+ * Lines without a charset, and every det / cls result, are bit-identical to a session that never created one.  The reference
+ * has no counterpart.  Results of a restricted line are repeatable run to run and equal across the entry points on one batch
+ * (ctc_charset.h says why, under today's GEMM plan, they do not depend on the rest of the batch either).
+ *
+ * rt_charset_create: S = the blank, every dictionary class whose WHOLE entry is one code point of utf8 [len bytes] (duplicate
+ * entries all join; U+0020 selects the appended " " class; a multi-code-point entry can only be named through ids), and ids
+ * [n_ids] (class ids, may be NULL with n_ids = 0).  *charset_out: the new id, 1-based, valid until rt_destroy; a session holds at
+ * most RT_MAX_CHARSETS.  Errors: a code point that matches no entry -> RT_ERR_INVALID naming it as U+XXXX; malformed UTF-8 ->
+ * RT_ERR_UTF8; an id outside [0, classes) -> RT_ERR_INVALID; the cap -> RT_ERR_CAPACITY.  Fails like every other call while
+ * tickets are in flight. */
+#define RT_MAX_CHARSETS 64
+RT_API int rt_charset_create(rt_session* s, const char* utf8, size_t len, const int32_t* ids, int n_ids, int* charset_out);
+/* |S| of a charset (0 for an unknown id); *ids (optional): its class ids in ascending order, library-owned until rt_destroy */
+RT_API int rt_charset_classes(const rt_session* s, int charset, const int32_t** ids);
+/* The session default: the charset of every line of every pipeline call that follows (rt_run_batch, _stream, rt_submit_batch,
+ * the encoded entry points, rt_run_regions); 0 = none (the initial state).  rt_submit_* takes the value as it is at the call. */
+RT_API int rt_set_rec_charset(rt_session* s, int charset);
+/* rt_run_regions with a charset per region: charsets[i][k] for region k of page i; -1 = the session default, 0 = unrestricted,
+ * >= 1 = that charset.  charsets == NULL or charsets[i] == NULL: -1 throughout.  An unknown id: RT_ERR_INVALID naming the page
+ * and the region, nothing queued. */
+RT_API int rt_run_regions_charsets(rt_session* s, const uint8_t* const* rgb, const int* hs, const int* ws, int n_pages, int mem,
+                                   const float* const* quads, const int* n_quads, const int32_t* const* charsets,
+                                   rt_results** out);
+/* What rt_charset_create compiles, GPU-free and sessionless: dict = dictionary file bytes (parsed as rt_parse_dictionary does);
+ * mask_out [mask_cap >= ceil(classes / 32)]: class c is bit (c & 31) of word c >> 5; *n_classes: the dictionary's class count.
+ * The same code, errors and messages as rt_charset_create (err: optional, err_cap bytes). */
+RT_API int rt_debug_charset_compile(const void* dict, size_t dict_len, const char* utf8, size_t len, const int32_t* ids, int n_ids,
+                                    uint32_t* mask_out, int mask_cap, int* n_classes, char* err, size_t err_cap);
+/* The device path of the charsets on host arrays (row gather, the CTC FC GEMM, k_ctc_charset_argmax; then the greedy decode
+ * and, with K > 0, the candidates path with the masks).  z5, W, bias, N, tokens_per_line, n_lines, K (0 .. RT_MAX_CANDIDATES),
+ * chunk_rows, cands_out, cols_out: as rt_debug_ctc_candidates (cands_out / cols_out may be NULL when K = 0).  line_set
+ * [n_lines]: 0 = none, s >= 1 = the set at masks[(s - 1) * ceil(N / 32) ...]; masks [n_sets][ceil(N / 32)] (the blank is allowed
+ * whatever bit 0 says).  idx / prob [rows] are in-out: the rows of restricted lines are replaced, the others come back untouched.
+ * tokens_out [rows]: line i's tokens from its first row on (entries past its count keep what the caller put there);
+ * n_tokens_out, scores_out [n_lines]: the decode's counts and scores (NaN for a line without tokens). */
+RT_API int rt_debug_ctc_charset(rt_session* s, const float* z5, const float* W, const float* bias, int N, int32_t* idx, float* prob,
+                                const int32_t* tokens_per_line, int n_lines, const int32_t* line_set, const uint32_t* masks,
+                                int n_sets, int K, int chunk_rows, int32_t* tokens_out, int32_t* n_tokens_out, float* scores_out,
+                                rt_candidate* cands_out, int32_t* cols_out);
+/* The same rule on the CPU in plain fp32 loops (ctc_charset.h), GPU-free and sessionless; same layout. */
+RT_API int rt_debug_ctc_charset_host(const float* z5, const float* W, const float* bias, int N, int32_t* idx, float* prob,
+                                     const int32_t* tokens_per_line, int n_lines, const int32_t* line_set, const uint32_t* masks,
+                                     int n_sets, int K, int32_t* tokens_out, int32_t* n_tokens_out, float* scores_out,
+                                     rt_candidate* cands_out, int32_t* cols_out);
 /* f32 sum of every det probability map produced in the call (keeps the network's
  * output observable when det_map_override is used) */
 RT_API double rt_results_det_checksum(const rt_results* r);

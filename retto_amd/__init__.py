@@ -400,6 +400,23 @@ def _candidate_lists(cands, K: int, n_tokens: int, entries: Sequence[str]) -> Li
             for j in range(n_tokens)]
 
 
+def debug_charset_compile(dict_bytes: bytes, text: str = "", ids: Sequence[int] = ()) -> np.ndarray:
+    """rt_debug_charset_compile: what RettoSession.create_charset compiles (retto_amd/csrc/ctc_charset.h), GPU-free: the mask
+    of the charset as uint32 words, class c at bit (c & 31) of word c >> 5.  text: str, or bytes to pass raw UTF-8."""
+    lib = _lib.load()
+    dict_bytes = bytes(dict_bytes)
+    raw = text.encode("utf-8") if isinstance(text, str) else bytes(text)
+    arr = (C.c_int32 * max(len(ids), 1))(*[int(i) for i in ids])
+    n = C.c_int(); err = C.create_string_buffer(256)
+    lib.rt_debug_charset_compile(dict_bytes, len(dict_bytes), raw, len(raw), arr, len(ids), None, 0, C.byref(n), err, len(err))
+    mask = np.zeros(max((n.value + 31) // 32, 1), np.uint32)
+    rc = lib.rt_debug_charset_compile(dict_bytes, len(dict_bytes), raw, len(raw), arr, len(ids), mask.ctypes.data, len(mask),
+                                      C.byref(n), err, len(err))
+    if rc != 0:
+        raise _ERRS.get(rc, RettoError)(err.value.decode("utf-8", "replace"))
+    return mask
+
+
 def parse_dictionary(data: bytes) -> List[str]:
     """rt_parse_dictionary: RecCharacter::new (rec_processor.rs:29-46) -- "blank", the file's trimmed lines, " "."""
     lib = _lib.load()
@@ -586,9 +603,31 @@ class RettoSession:
         finally:
             self._hd.lib.rt_results_free(r)
 
-    def run_regions_raw(self, pages, hs, ws, quads, mem=RT_MEM_HOST):
+    # -- rec charsets -----------------------------------------------------------------------
+    def create_charset(self, text: str = "", ids: Sequence[int] = ()) -> int:
+        """rt_charset_create: a set of classes a line's CTC decode may be restricted to -- the blank, every dictionary class
+        whose whole entry is one character of ``text``, and the class ids ``ids``.  Returns its id (1-based, valid for the
+        session's life; at most MAX_CHARSETS); see set_rec_charset and run_regions(charsets=...)."""
+        raw = text.encode("utf-8") if isinstance(text, str) else bytes(text)
+        arr = (C.c_int32 * max(len(ids), 1))(*[int(i) for i in ids])
+        out = C.c_int()
+        _check(self._hd.lib.rt_charset_create(self._hd.h, raw, len(raw), arr, len(ids), C.byref(out)), self._hd.h)
+        return out.value
+
+    def charset_classes(self, charset: int) -> np.ndarray:
+        """rt_charset_classes: the class ids of a charset in ascending order (empty for an unknown id)."""
+        p = C.POINTER(C.c_int32)()
+        n = self._hd.lib.rt_charset_classes(self._hd.h, int(charset), C.byref(p))
+        return np.ctypeslib.as_array(p, (n,)).copy() if n else np.zeros(0, np.int32)
+
+    def set_rec_charset(self, charset: int) -> None:
+        """rt_set_rec_charset: the charset of every line of the pipeline calls that follow; 0 = none."""
+        _check(self._hd.lib.rt_set_rec_charset(self._hd.h, int(charset)), self._hd.h)
+
+    def run_regions_raw(self, pages, hs, ws, quads, mem=RT_MEM_HOST, charsets=None):
         """rt_run_regions.  pages: host arrays or device pointers (ints); quads[i]: the regions of page i, anything that
-        reshapes to [n_i, 8] floats (TL, TR, BR, BL in original-page coordinates).  Returns an opaque results handle."""
+        reshapes to [n_i, 8] floats (TL, TR, BR, BL in original-page coordinates).  charsets (rt_run_regions_charsets): per
+        page None or one id per region (-1 = the session default, 0 = unrestricted).  Returns an opaque results handle."""
         lib, h = self._hd.lib, self._hd.h
         n = len(pages)
         if len(quads) != n:
@@ -601,15 +640,30 @@ class RettoSession:
             arr_q[i] = q.ctypes.data if len(q) else None
             arr_n[i] = len(q)
         out = C.c_void_p()
+        if charsets is not None:
+            if len(charsets) != n:
+                raise InvalidArgument("run_regions: one list of charset ids per page (or None)")
+            arr_c = (C.c_void_p * max(n, 1))()
+            for i in range(n):
+                if charsets[i] is None:
+                    arr_c[i] = None
+                    continue
+                c = np.ascontiguousarray(charsets[i], np.int32).reshape(-1); keep.append(c)
+                if len(c) != arr_n[i]:
+                    raise InvalidArgument("run_regions: page %d has %d regions but %d charset ids" % (i, arr_n[i], len(c)))
+                arr_c[i] = c.ctypes.data if len(c) else None
+            _check(lib.rt_run_regions_charsets(h, arr_p, arr_h, arr_w, n, mem, arr_q, arr_n, arr_c, C.byref(out)), h)
+            return out
         _check(lib.rt_run_regions(h, arr_p, arr_h, arr_w, n, mem, arr_q, arr_n, C.byref(out)), h)
         return out
 
-    def run_regions(self, pages: Sequence[np.ndarray], quads) -> List[RettoWorkerResult]:
+    def run_regions(self, pages: Sequence[np.ndarray], quads, charsets=None) -> List[RettoWorkerResult]:
         """The pipeline over regions the caller already knows (rt_run_regions): quads[i] = the [n_i, 4, 2] (or [n_i, 8]) quads
         of page i in original-page coordinates, TL, TR, BR, BL.  No detector runs; line k of a page is cut from the page as it
-        is by quad k clamped to the page.  det_result holds the clamped quads with score 1.0."""
+        is by quad k clamped to the page.  det_result holds the clamped quads with score 1.0.  charsets: per page None or one
+        charset id per region (create_charset; -1 = the session default, 0 = unrestricted)."""
         pages = [np.ascontiguousarray(p, np.uint8) for p in pages]
-        r = self.run_regions_raw(pages, [p.shape[0] for p in pages], [p.shape[1] for p in pages], quads)
+        r = self.run_regions_raw(pages, [p.shape[0] for p in pages], [p.shape[1] for p in pages], quads, charsets=charsets)
         try:
             self.last_det_checksum = self._hd.lib.rt_results_det_checksum(r)
             return [self._collect(r, i) for i in range(len(pages))]

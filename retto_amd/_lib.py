@@ -51,6 +51,7 @@ class Candidate(C.Structure):   # rt_candidate
 
 
 MAX_CANDIDATES = 8   # RT_MAX_CANDIDATES
+MAX_CHARSETS = 64    # RT_MAX_CHARSETS
 
 # every symbol include/retto_hip.h declares (tests check that each is exported)
 EXPORTS = [
@@ -69,6 +70,8 @@ EXPORTS = [
     "rt_submit_encoded_batch", "rt_decode_batch", "rt_debug_jpeg_reconstruct",
     "rt_debug_set_variants", "rt_bench_gemm", "rt_bench_gemm_err", "rt_bench_lc", "rt_debug_conv16", "rt_debug_gemm", "rt_debug_dwconv", "rt_debug_attention", "rt_debug_lc_block", "rt_debug_conv13", "rt_debug_layernorm", "rt_debug_glue16", "rt_debug_conv16x", "rt_debug_fpn", "rt_parse_dictionary", "rt_format_f32", "rt_rccl_unique_id", "rt_broadcast_blobs",
     "rt_run_regions", "rt_debug_warp_crops",
+    "rt_charset_create", "rt_charset_classes", "rt_set_rec_charset", "rt_run_regions_charsets", "rt_debug_charset_compile",
+    "rt_debug_ctc_charset", "rt_debug_ctc_charset_host",
 ]
 
 STAGE_CALLBACK = C.CFUNCTYPE(None, C.c_void_p, C.c_int, C.c_int, C.c_char_p)  # rt_stage_callback
@@ -209,5 +212,18 @@ def load():
                                             C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.rt_debug_ctc_candidates_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
                                                  C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.rt_charset_create.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t, P(C.c_int32), C.c_int, P(C.c_int)]
+    lib.rt_charset_classes.argtypes = [C.c_void_p, C.c_int, P(P(C.c_int32))]
+    lib.rt_set_rec_charset.argtypes = [C.c_void_p, C.c_int]
+    lib.rt_run_regions_charsets.argtypes = [C.c_void_p, P(C.c_void_p), P(C.c_int), P(C.c_int), C.c_int, C.c_int, P(C.c_void_p),
+                                            P(C.c_int), P(C.c_void_p), P(C.c_void_p)]
+    lib.rt_debug_charset_compile.argtypes = [C.c_char_p, C.c_size_t, C.c_char_p, C.c_size_t, P(C.c_int32), C.c_int, C.c_void_p,
+                                             C.c_int, P(C.c_int), C.c_char_p, C.c_size_t]
+    lib.rt_debug_ctc_charset.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                         C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                         C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.rt_debug_ctc_charset_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                              C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                              C.c_void_p, C.c_void_p, C.c_void_p]
     _lib = lib
     return lib

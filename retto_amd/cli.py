@@ -41,6 +41,9 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--crop-source", choices=["Resized", "Original"], default="Resized",
                     help="RettoSessionConfig.crop_source: cut the text lines from the page after resize_both (Resized, the "
                          "reference) or from the page as it was read (Original: small print on pages above max_side_len)")
+    ap.add_argument("--rec-charset", default=None, metavar="TEXT",
+                    help="restrict every line's CTC decode to these characters (one charset, made the session default): the "
+                         "dictionary classes whose whole entry is one character of TEXT, plus the blank")
     return ap
 
 
@@ -71,6 +74,8 @@ def main(argv=None) -> int:
     cfg.rec_processor_config.return_candidates = a.rec_candidates
     cfg.crop_source = a.crop_source
     session = retto_amd.RettoSession(cfg)
+    if a.rec_charset is not None:
+        session.set_rec_charset(session.create_charset(a.rec_charset))
     files = walk_files(a.images)
     log.info("Found %d files, processing...", len(files))
     out = open(a.json, "w") if a.json else None

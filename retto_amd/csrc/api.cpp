@@ -1,6 +1,6 @@
 // extern "C" surface of libretto_hip.so (include/retto_hip.h): sessions, the networks, the pipeline stages, batches, results,
 // parsers and device memory, with the feature-level debug hooks that are thin forwards into their features (rt_debug_warp_crops,
-// rt_debug_jpeg_reconstruct, rt_debug_word_boxes, rt_debug_ctc_candidates_host).  The kernel-level diagnostics (rt_debug_set_variants,
+// rt_debug_jpeg_reconstruct, rt_debug_word_boxes, rt_debug_ctc_candidates_host, rt_debug_charset_compile, rt_debug_ctc_charset_host).  The kernel-level diagnostics (rt_debug_set_variants,
 // rt_bench_*, and the rt_debug_* harnesses the kernel tests drive) are in api_debug.cpp; api_internal.h holds what both share.
 #include <thread>
 #include <sched.h>
@@ -30,6 +30,24 @@ bool rt::cand_args_ok(const float* z5, const float* W, int N, const int32_t* idx
   long long rows = 0;
   for (int i = 0; i < n_lines; i++) {
     if (tokens_per_line[i] < 0) return false;
+    rows += tokens_per_line[i];
+  }
+  if (rows >= (1ll << 30)) return false;
+  for (long long r = 0; r < rows; r++)
+    if (idx[r] < 0 || idx[r] >= N) return false;
+  *rows_out = rows;
+  return true;
+}
+bool rt::charset_args_ok(const float* z5, const float* W, int N, const int32_t* idx, const float* prob, const int32_t* tokens_per_line,
+                         int n_lines, const int32_t* line_set, const uint32_t* masks, int n_sets, int K, const int32_t* tokens_out,
+                         const int32_t* n_tokens_out, const float* scores_out, const rt_candidate* cands_out, const int32_t* cols_out,
+                         long long* rows_out) {
+  if (!z5 || !W || !idx || !prob || !tokens_per_line || !line_set || !tokens_out || !n_tokens_out || !scores_out) return false;
+  if (n_lines <= 0 || N <= 0 || K < 0 || K > RT_MAX_CANDIDATES || n_sets < 0 || n_sets > RT_MAX_CHARSETS || (n_sets > 0 && !masks)) return false;
+  if (K > 0 && (!cands_out || !cols_out)) return false;
+  long long rows = 0;
+  for (int i = 0; i < n_lines; i++) {
+    if (tokens_per_line[i] < 0 || line_set[i] < 0 || line_set[i] > n_sets) return false;
     rows += tokens_per_line[i];
   }
   if (rows >= (1ll << 30)) return false;
@@ -214,6 +232,32 @@ int rt_run_regions(rt_session* s, const uint8_t* const* rgb, const int* hs, cons
   RT_REQUIRE(mem == RT_MEM_HOST || mem == RT_MEM_DEVICE, s, "rt_run_regions: mem must be RT_MEM_HOST or RT_MEM_DEVICE");
   *out = nullptr;
   return guarded(s, [&] { *out = s->run_regions(rgb, hs, ws, n_pages, mem, quads, n_quads); });
+}
+int rt_run_regions_charsets(rt_session* s, const uint8_t* const* rgb, const int* hs, const int* ws, int n_pages, int mem,
+                            const float* const* quads, const int* n_quads, const int32_t* const* charsets, rt_results** out) {
+  RT_REQUIRE(s && out && n_pages >= 0 && (n_pages == 0 || (rgb && hs && ws && quads && n_quads)), s, "rt_run_regions_charsets: bad argument");
+  RT_REQUIRE(mem == RT_MEM_HOST || mem == RT_MEM_DEVICE, s, "rt_run_regions_charsets: mem must be RT_MEM_HOST or RT_MEM_DEVICE");
+  *out = nullptr;
+  return guarded(s, [&] { *out = s->run_regions(rgb, hs, ws, n_pages, mem, quads, n_quads, charsets); });
+}
+int rt_charset_create(rt_session* s, const char* utf8, size_t len, const int32_t* ids, int n_ids, int* charset_out) {
+  RT_REQUIRE(s && charset_out && (utf8 || !len) && n_ids >= 0 && (ids || !n_ids), s, "rt_charset_create: bad argument");
+  *charset_out = 0;
+  return guarded(s, [&] { *charset_out = s->charset_create(utf8, len, ids, n_ids); });
+}
+int rt_charset_classes(const rt_session* s, int charset, const int32_t** ids) {
+  if (!s || !s->charsets || charset < 1 || charset > (int)s->charsets->ids.size()) return 0;
+  const std::vector<int32_t>& v = s->charsets->ids[(size_t)charset - 1];
+  if (ids) *ids = v.data();
+  return (int)v.size();
+}
+int rt_set_rec_charset(rt_session* s, int charset) {
+  RT_REQUIRE(s, s, "rt_set_rec_charset: null session");
+  return guarded(s, [&] {
+    if (charset < 0 || charset > (int)s->charsets->ids.size())
+      throw RtError(RT_ERR_INVALID, "rt_set_rec_charset: unknown charset id " + std::to_string(charset));
+    s->rec_charset = charset;
+  });
 }
 int rt_submit_batch(rt_session* s, const uint8_t* const* rgb, const int* hs, const int* ws, int n_pages, int mem,
                     const float* const* det_map_override, rt_ticket** out) {
@@ -502,6 +546,72 @@ int rt_debug_ctc_candidates_host(const float* z5, const float* W, const float* b
       for (int j = 0; K > 1 && j < n; j++) {
         cc::Cand* c = out + (o + j) * K;
         cc::row_candidates(z5 + (size_t)(o + cols_out[o + j]) * D, D, W, bias, N, c[0].id, K, c, logits.data());
+      }
+      o += T;
+    }
+    return RT_OK;
+  } catch (const std::exception&) {
+    return RT_ERR_BACKEND;
+  }
+}
+static_assert(RT_MAX_CHARSETS == cs::MAX_SETS, "RT_MAX_CHARSETS and cs::MAX_SETS must agree");
+int rt_debug_charset_compile(const void* dict, size_t dict_len, const char* utf8, size_t len, const int32_t* ids, int n_ids,
+                             uint32_t* mask_out, int mask_cap, int* n_classes, char* err, size_t err_cap) {
+  if (err && err_cap) err[0] = 0;
+  if ((!dict && dict_len) || (!utf8 && len) || n_ids < 0 || (!ids && n_ids) || !n_classes || mask_cap < 0 || (!mask_out && mask_cap)) {
+    if (err && err_cap) snprintf(err, err_cap, "rt_debug_charset_compile: bad argument");
+    return RT_ERR_INVALID;
+  }
+  *n_classes = 0;
+  try {
+    std::vector<uint8_t> bytes((const uint8_t*)dict, (const uint8_t*)dict + dict_len);
+    const std::vector<std::string> d = rt::load_dictionary(bytes);
+    const std::vector<uint32_t> mask = rt::compile_charset(d, utf8, len, ids, n_ids);
+    *n_classes = (int)d.size();
+    if ((size_t)mask_cap < mask.size()) throw RtError(RT_ERR_INVALID, "rt_debug_charset_compile: the mask needs " + std::to_string(mask.size()) + " words");
+    memcpy(mask_out, mask.data(), mask.size() * sizeof(uint32_t));
+    return RT_OK;
+  } catch (const RtError& e) {
+    if (err && err_cap) snprintf(err, err_cap, "%s", e.what());
+    return e.code;
+  } catch (const std::exception& e) {
+    if (err && err_cap) snprintf(err, err_cap, "%s", e.what());
+    return RT_ERR_BACKEND;
+  }
+}
+int rt_debug_ctc_charset_host(const float* z5, const float* W, const float* bias, int N, int32_t* idx, float* prob,
+                              const int32_t* tokens_per_line, int n_lines, const int32_t* line_set, const uint32_t* masks,
+                              int n_sets, int K, int32_t* tokens_out, int32_t* n_tokens_out, float* scores_out,
+                              rt_candidate* cands_out, int32_t* cols_out) {
+  long long rows = 0;
+  if (!charset_args_ok(z5, W, N, idx, prob, tokens_per_line, n_lines, line_set, masks, n_sets, K, tokens_out, n_tokens_out,
+                       scores_out, cands_out, cols_out, &rows))
+    return RT_ERR_INVALID;
+  try {
+    const int D = 120, words = cs::mask_words(N);
+    std::vector<float> logits((size_t)N);
+    cc::Cand* out = reinterpret_cast<cc::Cand*>(cands_out);
+    long long o = 0;
+    for (int i = 0; i < n_lines; i++) {
+      const int T = tokens_per_line[i];
+      const uint32_t* m = line_set[i] > 0 ? masks + (size_t)(line_set[i] - 1) * words : nullptr;
+      for (int t = 0; m && t < T; t++) {   // the restricted rows' (idx, prob), before the decode
+        cs::row_logits(z5 + (size_t)(o + t) * D, D, W, bias, N, logits.data());
+        cs::row_argmax(logits.data(), N, m, idx + o + t, prob + o + t, nullptr, nullptr);
+      }
+      int cnt = 0; float acc = 0.0f;   // k_ctc_decode
+      for (int t = 0; t < T; t++)
+        if (cc::kept(idx[o + t], t > 0 ? idx[o + t - 1] : 0, t == 0)) { tokens_out[o + cnt] = idx[o + t]; acc = acc + prob[o + t]; cnt++; }
+      n_tokens_out[i] = cnt;
+      scores_out[i] = acc / (float)(unsigned)cnt;
+      if (K > 0) {
+        const int n = cc::line_kept(idx + o, prob + o, T, K, cols_out + o, out + o * K);
+        for (int j = 0; K > 1 && j < n; j++) {
+          cc::Cand* c = out + (o + j) * K;
+          const float* z = z5 + (size_t)(o + cols_out[o + j]) * D;
+          if (m) { cs::row_logits(z, D, W, bias, N, logits.data()); cs::row_candidates(logits.data(), N, m, c[0].id, K, c); }
+          else cc::row_candidates(z, D, W, bias, N, c[0].id, K, c, logits.data());
+        }
       }
       o += T;
     }

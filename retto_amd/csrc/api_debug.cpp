@@ -1,6 +1,6 @@
 // Kernel-level diagnostics of libretto_hip.so (include/retto_hip.h, diagnostics section): the A/B switches of tools/, the kernel
 // micro-benchmarks (rt_bench_*), and one harness per kernel family that runs a single launch on host arrays for the fp64 tests
-// (rt_debug_gemm, _dwconv, _attention, _ctc_candidates, _lc_block, _conv13, _layernorm, _conv16, _glue16, _fpn, _conv16x).
+// (rt_debug_gemm, _dwconv, _attention, _ctc_candidates, _ctc_charset, _lc_block, _conv13, _layernorm, _conv16, _glue16, _fpn, _conv16x).
 // None of it runs in production, and every kernel test depends on it.  A harness has one shape: check the arguments (each
 // failure with its own message, before any device work), lay the ragged lists out (Ragged), put the operands on the device
 // (DevBufs::upload / zeroed, upload_as), fill what the kernel writes with RT_DEBUG_CANARY and spare rows (DevBufs::canary),
@@ -409,6 +409,65 @@ RT_API int rt_debug_ctc_candidates(rt_session* s, const float* z5, const float* 
     RT_HIP_CHECK(hipStreamSynchronize(s->st));
     DevBufs::download(n_tokens_out, dntok, (size_t)n_lines); DevBufs::download(cols_out, dcols, (size_t)rows);
     DevBufs::download(reinterpret_cast<cc::Cand*>(cands_out), dcands, (size_t)rows * K);
+  });
+}
+
+// Rec charsets' device path (rt_session::ctc_charset, pp::ctc_decode and -- K > 0 -- rt_session::ctc_candidates with the masks: what
+// rec_groups runs per group) on host arrays; the rows of the restricted lines and the per-row set table are built as there.
+RT_API int rt_debug_ctc_charset(rt_session* s, const float* z5, const float* W, const float* bias, int N, int32_t* idx, float* prob,
+                                const int32_t* tokens_per_line, int n_lines, const int32_t* line_set, const uint32_t* masks,
+                                int n_sets, int K, int chunk_rows, int32_t* tokens_out, int32_t* n_tokens_out, float* scores_out,
+                                rt_candidate* cands_out, int32_t* cols_out) {
+  long long rows = 0;
+  RT_REQUIRE(s, s, "rt_debug_ctc_charset: null session");
+  RT_REQUIRE(charset_args_ok(z5, W, N, idx, prob, tokens_per_line, n_lines, line_set, masks, n_sets, K, tokens_out, n_tokens_out,
+                             scores_out, cands_out, cols_out, &rows) && chunk_rows >= 0,
+             s, "rt_debug_ctc_charset: bad argument");
+  return guarded(s, [&] {
+    s->begin_call();
+    const size_t nr = (size_t)std::max<long long>(rows, 1);
+    const int words = cs::mask_words(N);
+    WeightStore ws;
+    SvtrCore core;
+    core.classes = N;
+    core.fc = pack_linear(ws, W, bias, core.D, N);
+    DevBufs bufs;
+    // (the features sit inside a larger allocation, as z5 does inside the scratch arena)
+    float* dz = bufs.zeroed<float>((nr + 256) * core.D);
+    DevBufs::put(dz, z5, (size_t)rows * core.D);
+    std::vector<int> row_set(nr, 0), crows;
+    long long o = 0;
+    for (int i = 0; i < n_lines; i++) {
+      for (int t = 0; t < tokens_per_line[i]; t++) {
+        row_set[(size_t)(o + t)] = line_set[i];
+        if (line_set[i] > 0) crows.push_back((int)(o + t));
+      }
+      o += tokens_per_line[i];
+    }
+    int* didx = bufs.alloc<int>(nr); float* dprob = bufs.alloc<float>(nr); int* dtok = bufs.alloc<int>(nr);
+    DevBufs::put(didx, idx, (size_t)rows); DevBufs::put(dprob, prob, (size_t)rows); DevBufs::put(dtok, tokens_out, (size_t)rows);
+    int* dntok = bufs.alloc<int>(n_lines); float* dscore = bufs.alloc<float>(n_lines);
+    const ImgGeom* dg = Ragged(tokens_per_line, n_lines).upload(bufs);
+    const int* drow_set = bufs.upload(row_set.data(), nr);
+    const int* dcrows = crows.empty() ? nullptr : bufs.upload(crows.data(), crows.size());
+    const uint32_t* dmasks = n_sets > 0 ? bufs.upload(masks, (size_t)n_sets * words) : nullptr;
+    s->ctc_charset(core, dz, dcrows, (int)crows.size(), drow_set, dmasks, words, chunk_rows, didx, dprob);
+    pp::ctc_decode(s->st, didx, dprob, dg, n_lines, dtok, dntok, dscore);
+    int* dcols = nullptr; cc::Cand* dcands = nullptr;
+    if (K > 0) {
+      dcols = bufs.alloc<int>(nr); dcands = bufs.alloc<cc::Cand>(nr * K);
+      DevBufs::put(dcols, cols_out, (size_t)rows); DevBufs::put(dcands, reinterpret_cast<const cc::Cand*>(cands_out), (size_t)rows * K);
+      s->ctc_candidates(core, dz, didx, dprob, dg, dntok, n_lines, rows, K, chunk_rows, dcols, dcands,
+                        crows.empty() ? nullptr : drow_set, crows.empty() ? nullptr : dmasks, words);
+    }
+    RT_HIP_CHECK(hipStreamSynchronize(s->st));
+    DevBufs::download(idx, didx, (size_t)rows); DevBufs::download(prob, dprob, (size_t)rows);
+    DevBufs::download(tokens_out, dtok, (size_t)rows);
+    DevBufs::download(n_tokens_out, dntok, (size_t)n_lines); DevBufs::download(scores_out, dscore, (size_t)n_lines);
+    if (K > 0) {
+      DevBufs::download(cols_out, dcols, (size_t)rows);
+      DevBufs::download(reinterpret_cast<cc::Cand*>(cands_out), dcands, (size_t)rows * K);
+    }
   });
 }
 

@@ -18,6 +18,12 @@ bool cand_args_ok(const float* z5, const float* W, int N, const int32_t* idx, co
                   int n_lines, int K, const rt_candidate* cands_out, const int32_t* cols_out, const int32_t* n_tokens_out,
                   long long* rows_out);
 
+// what both rt_debug_ctc_charset forms require beyond cand_args_ok (K = 0 allowed there: cands / cols may then be NULL)
+bool charset_args_ok(const float* z5, const float* W, int N, const int32_t* idx, const float* prob, const int32_t* tokens_per_line,
+                     int n_lines, const int32_t* line_set, const uint32_t* masks, int n_sets, int K, const int32_t* tokens_out,
+                     const int32_t* n_tokens_out, const float* scores_out, const rt_candidate* cands_out, const int32_t* cols_out,
+                     long long* rows_out);
+
 // A call that fails after work was enqueued must not leave kernels or H2D copies in flight: the next
 // begin_call() rewinds the pinned staging and the arenas they read.  Errors of the drain itself are dropped
 // (the first failure is the one reported).

@@ -6,6 +6,7 @@
 #include "common.h"
 #include "word_boxes.h"
 #include "ctc_candidates.h"
+#include "ctc_charset.h"
 
 namespace rt {
 namespace pp {
@@ -93,8 +94,15 @@ void ctc_kept_rows(hipStream_t st, const int* idx, const float* prob, const ImgG
 // rows kept_row[0..m) of z [.][ld] (ld a multiple of 4) -> out [m][ld]
 void ctc_gather_rows(hipStream_t st, const float* z, int ld, const int* kept_row, int m, float* out);
 // one wave64 per row i < m of logits [m][ld]: ranks 1..K-1 over the columns [0, classes) other than cands[kept_slot[i] * K].id
-// -> cands[kept_slot[i] * K + 1 ...]
-void ctc_topk(hipStream_t st, const float* logits, int ld, int classes, const int* kept_slot, int m, int K, cc::Cand* cands);
+// -> cands[kept_slot[i] * K + 1 ...].  With kept_row / row_set / masks (rec charsets, ctc_charset.h): row i is time step
+// kept_row[i] of the group, and where row_set[kept_row[i]] = s >= 1 only the classes of masks[(s - 1) * words ...] take part.
+void ctc_topk(hipStream_t st, const float* logits, int ld, int classes, const int* kept_slot, int m, int K, cc::Cand* cands,
+              const int* kept_row = nullptr, const int* row_set = nullptr, const uint32_t* masks = nullptr, int words = 0);
+// Rec charsets (ctc_charset.h): one wave64 per row i < m of logits [m][ld], time step rows[i] of the group with charset
+// row_set[rows[i]] = s >= 1: the argmax and its probability over the classes of masks[(s - 1) * words ...] -> idx[rows[i]],
+// prob[rows[i]].  masks: [n_sets][words = cs::mask_words(classes)] on the device.
+void ctc_charset_argmax(hipStream_t st, const float* logits, int ld, int classes, const int* rows, const int* row_set,
+                        const uint32_t* masks, int words, int m, int* idx, float* prob);
 
 // sum of a float buffer into per-block doubles (partials has ceil(n/65536) entries)
 int sum_blocks(long long n);

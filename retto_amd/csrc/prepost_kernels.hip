@@ -401,8 +401,13 @@ void ctc_gather_rows(hipStream_t st, const float* z, int ld, const int* kept_row
 // greedy one, and the row maximum.  Pass 2: sum(exp(l - max)) over every class (the row is 26 KB: it comes back from L2).  Then
 // K - 1 rounds of a wave arg-max over the lanes' list heads (ties to the lower id); the lane that owned the winner pops it, lane r
 // keeps round r's winner and writes rank r + 1.
+// MASKED (ctc_charset.h): row i is time step kept_row[i] of the group, whose charset row_set[...] (0: none) limits the lists, the
+// maximum and the sum to its classes; a disallowed column is skipped, never lowered.  MASKED = false is the kernel as it was.
+template <bool MASKED>
 __global__ __launch_bounds__(64) void k_ctc_topk(const float* __restrict__ logits, int ld, int classes,
-                                                 const int* __restrict__ kept_slot, int m, int K, cc::Cand* __restrict__ cands) {
+                                                 const int* __restrict__ kept_slot, int m, int K, cc::Cand* __restrict__ cands,
+                                                 const int* __restrict__ kept_row, const int* __restrict__ row_set,
+                                                 const uint32_t* __restrict__ masks, int words) {
   constexpr int N = cc::MAX_K - 1;
   const int row = blockIdx.x, lane = threadIdx.x;
   if (row >= m) return;
@@ -410,6 +415,8 @@ __global__ __launch_bounds__(64) void k_ctc_topk(const float* __restrict__ logit
   const int tok = out[0].id;
   const float4* x = reinterpret_cast<const float4*>(logits + (long long)row * ld);
   const int nv = (classes + 3) / 4;
+  const uint32_t* mask = nullptr;
+  if (MASKED) { const int set = row_set[kept_row[row]]; if (set > 0) mask = masks + (long long)(set - 1) * words; }
   float L[N]; int I[N];
 #pragma unroll
   for (int j = 0; j < N; j++) { L[j] = -INFINITY; I[j] = cc::EMPTY_ID; }
@@ -417,10 +424,11 @@ __global__ __launch_bounds__(64) void k_ctc_topk(const float* __restrict__ logit
   for (int v = lane; v < nv; v += 64) {
     const float4 q = x[v];
     const float e[4] = {q.x, q.y, q.z, q.w};
+    const uint32_t bits = MASKED && mask ? cs::allowed4(mask, v) : 15u;
 #pragma unroll
     for (int u = 0; u < 4; u++) {
       const int c = 4 * v + u;
-      if (c < classes) {
+      if (c < classes && (!MASKED || ((bits >> u) & 1u))) {
         mx = fmaxf(mx, e[u]);
         if (c != tok) cc::list_insert(L, I, e[u], c);
       }
@@ -431,9 +439,10 @@ __global__ __launch_bounds__(64) void k_ctc_topk(const float* __restrict__ logit
   for (int v = lane; v < nv; v += 64) {
     const float4 q = x[v];
     const float e[4] = {q.x, q.y, q.z, q.w};
+    const uint32_t bits = MASKED && mask ? cs::allowed4(mask, v) : 15u;
 #pragma unroll
     for (int u = 0; u < 4; u++)
-      if (4 * v + u < classes) sum = sum + expf(e[u] - mx);
+      if (4 * v + u < classes && (!MASKED || ((bits >> u) & 1u))) sum = sum + expf(e[u] - mx);
   }
   for (int o = 32; o >= 1; o >>= 1) sum = sum + __shfl_xor(sum, o);   // (a butterfly: every lane adds in the same order)
   float ol = 0.0f; int oi = cc::EMPTY_ID;
@@ -452,9 +461,62 @@ __global__ __launch_bounds__(64) void k_ctc_topk(const float* __restrict__ logit
   }
   if (lane < K - 1) out[1 + lane] = oi == cc::EMPTY_ID ? cc::Cand{-1, 0.0f} : cc::Cand{oi, cc::prob_of(ol, mx, sum)};
 }
-void ctc_topk(hipStream_t st, const float* logits, int ld, int classes, const int* kept_slot, int m, int K, cc::Cand* cands) {
+void ctc_topk(hipStream_t st, const float* logits, int ld, int classes, const int* kept_slot, int m, int K, cc::Cand* cands,
+              const int* kept_row, const int* row_set, const uint32_t* masks, int words) {
   if (m <= 0 || K <= 1) return;
-  RT_LAUNCH(k_ctc_topk, dim3(m), dim3(64), 0, st, logits, ld, classes, kept_slot, m, K, cands);
+  if (masks && row_set && kept_row)
+    RT_LAUNCH(k_ctc_topk<true>, dim3(m), dim3(64), 0, st, logits, ld, classes, kept_slot, m, K, cands, kept_row, row_set, masks, words);
+  else
+    RT_LAUNCH(k_ctc_topk<false>, dim3(m), dim3(64), 0, st, logits, ld, classes, kept_slot, m, K, cands, nullptr, nullptr, nullptr, 0);
+}
+
+// Rec charsets (ctc_charset.h).  One wave64 per restricted row i < m of logits [m][ld]: time step rows[i] of the group, whose
+// charset is row_set[rows[i]] >= 1.  The lanes stream the row as float4; a lane's four columns lie in one mask word.  Pass 1: the
+// maximum and its class over the allowed columns < classes, then a butterfly over (logit, id) with the tie rule, after which every
+// lane holds the same pair.  Pass 2: sum(exp(l - max)) over the same columns (the row comes back from L2).  Lane 0 writes the
+// row's idx and prob.
+__global__ __launch_bounds__(64) void k_ctc_charset_argmax(const float* __restrict__ logits, int ld, int classes,
+                                                           const int* __restrict__ rows, const int* __restrict__ row_set,
+                                                           const uint32_t* __restrict__ masks, int words, int m,
+                                                           int* __restrict__ idx, float* __restrict__ prob) {
+  const int i = blockIdx.x, lane = threadIdx.x;
+  if (i >= m) return;
+  const int row = rows[i], set = row_set[row];
+  if (set <= 0) return;   // (never listed: a row of an unrestricted line keeps the fused head's values)
+  const uint32_t* mask = masks + (long long)(set - 1) * words;
+  const float4* x = reinterpret_cast<const float4*>(logits + (long long)i * ld);
+  const int nv = (classes + 3) / 4;
+  float bl = -INFINITY; int bi = cc::EMPTY_ID;
+  for (int v = lane; v < nv; v += 64) {
+    const float4 q = x[v];
+    const float e[4] = {q.x, q.y, q.z, q.w};
+    const uint32_t bits = cs::allowed4(mask, v);
+#pragma unroll
+    for (int u = 0; u < 4; u++) {
+      const int c = 4 * v + u;
+      if (c < classes && ((bits >> u) & 1u) && cc::better(e[u], c, bl, bi)) { bl = e[u]; bi = c; }
+    }
+  }
+  for (int o = 32; o >= 1; o >>= 1) {
+    const float l2 = __shfl_xor(bl, o); const int i2 = __shfl_xor(bi, o);
+    if (cc::better(l2, i2, bl, bi)) { bl = l2; bi = i2; }
+  }
+  float sum = 0.0f;
+  for (int v = lane; v < nv; v += 64) {
+    const float4 q = x[v];
+    const float e[4] = {q.x, q.y, q.z, q.w};
+    const uint32_t bits = cs::allowed4(mask, v);
+#pragma unroll
+    for (int u = 0; u < 4; u++)
+      if (4 * v + u < classes && ((bits >> u) & 1u)) sum = sum + expf(e[u] - bl);
+  }
+  for (int o = 32; o >= 1; o >>= 1) sum = sum + __shfl_xor(sum, o);   // (a butterfly: every lane adds in the same order)
+  if (lane == 0) { idx[row] = bi == cc::EMPTY_ID ? 0 : bi; prob[row] = cc::prob_of(bl, bl, sum); }   // (every allowed logit NaN: the blank)
+}
+void ctc_charset_argmax(hipStream_t st, const float* logits, int ld, int classes, const int* rows, const int* row_set,
+                        const uint32_t* masks, int words, int m, int* idx, float* prob) {
+  if (m <= 0) return;
+  RT_LAUNCH(k_ctc_charset_argmax, dim3(m), dim3(64), 0, st, logits, ld, classes, rows, row_set, masks, words, m, idx, prob);
 }
 
 // ===========================================================================

@@ -93,6 +93,34 @@ std::vector<std::string> load_dictionary(const std::vector<uint8_t>& bytes) {
   dict.push_back(" ");
   return dict;
 }
+std::vector<uint32_t> compile_charset(const std::vector<std::string>& dict, const char* utf8, size_t len, const int32_t* ids,
+                                      int n_ids) {
+  const int classes = (int)dict.size();
+  std::vector<uint32_t> mask((size_t)cs::mask_words(classes), 0u);
+  auto add = [&](int c) { mask[(size_t)c >> 5] |= 1u << (c & 31); };
+  add(0);
+  const unsigned char* p = (const unsigned char*)utf8;
+  for (size_t i = 0; i < len;) {
+    uint32_t cp;
+    const int k = utf8_decode_strict(p + i, len - i, &cp);
+    if (k == 0) throw RtError(RT_ERR_UTF8, "charset: the text is not valid UTF-8 (byte offset " + std::to_string(i) + ")");
+    bool any = false;
+    for (int c = 1; c < classes; c++)   // (class 0 is the blank, whatever its placeholder text)
+      if (dict[(size_t)c].size() == (size_t)k && memcmp(dict[(size_t)c].data(), p + i, (size_t)k) == 0) { add(c); any = true; }
+    if (!any) {
+      char b[64];
+      snprintf(b, sizeof b, "charset: U+%04X matches no dictionary entry", (unsigned)cp);
+      throw RtError(RT_ERR_INVALID, b);
+    }
+    i += (size_t)k;
+  }
+  for (int j = 0; j < n_ids; j++) {
+    if (ids[j] < 0 || ids[j] >= classes)
+      throw RtError(RT_ERR_INVALID, "charset: class id " + std::to_string(ids[j]) + " is outside [0, " + std::to_string(classes) + ")");
+    add(ids[j]);
+  }
+  return mask;
+}
 }  // namespace rt
 
 // ---------------------------------------------------------------------------
@@ -129,6 +157,7 @@ rt_session* rt_session_create(const rt_config* cfg) {
   if (srec) s->rec.reset(new RecServerH(br)); else if (f16) s->rec.reset(new RecNetH(br)); else s->rec.reset(new RecNet(br));
   s->model_info = std::string(s->det->arch()) + "/" + s->det->dtype() + " " + s->cls->dtype() + " " + s->rec->arch() + "/" + s->rec->dtype();
   s->dict = rt::load_dictionary(dict);
+  s->charsets = std::make_shared<rt_charsets>();
   if ((int)s->dict.size() != s->rec->classes())
     throw RtError(RT_ERR_SHAPE, "dictionary has " + std::to_string(s->dict.size()) + " entries but the rec head has " +
                                     std::to_string(s->rec->classes()) + " classes");
@@ -146,7 +175,7 @@ rt_session* rt_session_create(const rt_config* cfg) {
     std::unique_ptr<rt_session> h(new rt_session());
     h->cfg = s->cfg; h->device = s->device;
     h->det = s->det; h->cls = s->cls; h->rec = s->rec; h->dict = s->dict; h->model_info = s->model_info;
-    h->d_word_raw = s->d_word_raw;
+    h->d_word_raw = s->d_word_raw; h->charsets = s->charsets;
     RT_HIP_CHECK(hipStreamCreateWithFlags(&h->st_full, hipStreamNonBlocking));
     h->st = h->st_full;
     RT_HIP_CHECK(hipMalloc((void**)&h->d_flags, 64));
@@ -312,7 +341,8 @@ void rt_session::rec_forward_ragged(const float* nchw, int n, const int* widths,
 }
 
 void rt_session::ctc_candidates(const SvtrCore& core, const float* z5, const int* idx, const float* prob, const ImgGeom* lines,
-                                const int* n_tokens, int n_lines, long long rows, int K, int chunk_rows, int* cols, cc::Cand* cands) {
+                                const int* n_tokens, int n_lines, long long rows, int K, int chunk_rows, int* cols, cc::Cand* cands,
+                                const int* row_set, const uint32_t* masks, int words) {
   if (n_lines <= 0 || rows <= 0) return;
   int *kept_row = nullptr, *kept_slot = nullptr, *d_kept = nullptr;
   if (K > 1) { kept_row = scratch.alloc<int>((size_t)rows); kept_slot = scratch.alloc<int>((size_t)rows); d_kept = scratch.alloc<int>(1); }
@@ -337,8 +367,43 @@ void rt_session::ctc_candidates(const SvtrCore& core, const float* z5, const int
       pp::ctc_gather_rows(st, z5, core.D, kept_row + c0, m, zc); }
     core.logits_rows(c, zc, m, logits);
     ProfScope ps(&prof, st, "ctc_topk");
-    pp::ctc_topk(st, logits, ld, core.classes, kept_slot + c0, m, K, cands);
+    pp::ctc_topk(st, logits, ld, core.classes, kept_slot + c0, m, K, cands, kept_row + c0, row_set, masks, words);
   }
+}
+
+void rt_session::ctc_charset(const SvtrCore& core, const float* z5, const int* d_rows, int n_rows, const int* d_row_set,
+                             const uint32_t* masks, int words, int chunk_rows, int* idx, float* prob) {
+  if (n_rows <= 0) return;
+  const int chunk = chunk_rows > 0 ? chunk_rows : cc::CAND_CHUNK, cap = std::min(chunk, n_rows), ld = round_up(core.classes, 4);
+  const size_t zc_n = ((size_t)cap + 256) * core.D;   // (zero rows past the chunk: a GEMM tile's loads stay inside the allocation)
+  float* zc = scratch.alloc<float>(zc_n);
+  float* logits = scratch.alloc<float>((size_t)cap * ld);
+  RT_HIP_CHECK(hipMemsetAsync(zc, 0, zc_n * sizeof(float), st));
+  RunCtx c = ctx(&scratch);
+  for (int c0 = 0; c0 < n_rows; c0 += chunk) {   // (stream order lets the chunks share zc and logits)
+    const int m = std::min(chunk, n_rows - c0);
+    { ProfScope ps(&prof, st, "ctc_gather_rows");
+      pp::ctc_gather_rows(st, z5, core.D, d_rows + c0, m, zc); }
+    core.logits_rows(c, zc, m, logits);
+    ProfScope ps(&prof, st, "ctc_charset_argmax");
+    pp::ctc_charset_argmax(st, logits, ld, core.classes, d_rows + c0, d_row_set, masks, words, m, idx, prob);
+  }
+}
+
+int rt_session::charset_create(const char* utf8, size_t len, const int32_t* ids, int n_ids) {
+  rt_charsets& C = *charsets;
+  if ((int)C.ids.size() >= cs::MAX_SETS)
+    throw RtError(RT_ERR_CAPACITY, "rt_charset_create: the session holds RT_MAX_CHARSETS (" + std::to_string(cs::MAX_SETS) + ") charsets already");
+  const std::vector<uint32_t> mask = compile_charset(dict, utf8, len, ids, n_ids);
+  RT_HIP_CHECK(hipSetDevice(device));
+  C.words = (int)mask.size();
+  if (!C.d_masks) RT_HIP_CHECK(hipMalloc((void**)&C.d_masks, (size_t)cs::MAX_SETS * mask.size() * sizeof(uint32_t)));
+  // (a blocking copy; no lane has work queued: this is a guarded call and every pipeline call ends with its streams drained)
+  RT_HIP_CHECK(hipMemcpy(C.d_masks + C.ids.size() * mask.size(), mask.data(), mask.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+  std::vector<int32_t> members;
+  for (int c = 0; c < (int)dict.size(); c++) if (cs::allowed(mask.data(), c)) members.push_back(c);
+  C.ids.push_back(std::move(members));
+  return (int)C.ids.size();
 }
 
 // ---------------------------------------------------------------------------
@@ -627,6 +692,7 @@ struct Pipeline {
   int* d_tok = nullptr; int* h_tokens = nullptr;   // CTC tokens at tok_off
   int* d_wcount = nullptr; wb::Word* d_words = nullptr; int* h_wcount = nullptr; wb::Word* h_words = nullptr;   // rec_return_word_box
   int* d_ccol = nullptr; cc::Cand* d_cands = nullptr; int* h_ccol = nullptr; cc::Cand* h_cands = nullptr;       // rec_return_candidates
+  std::vector<int> line_set;                // rec charsets: per line its set (0: none); empty when no line of the call has one
 };
 
 // Launch groups: items [g0, end) where the group always takes its first item; with max_items > 0 it takes up to max_items items,
@@ -909,10 +975,30 @@ void rec_groups(rt_session& s, Pipeline& P) {
     RunCtx c = s.ctx(&s.scratch);
     // (the token count per line only depends on the widths, so the offsets are known before the net runs)
     const long long t0 = P.tok_off[l0];
-    const float* z5 = nullptr;   // the head's input, for the candidates' logits
+    // rec charsets (ctc_charset.h): the rows of the group's restricted lines in line order, and every row's set
+    int n_crows = 0; int *d_crows = nullptr, *d_row_set = nullptr;
+    if (!P.line_set.empty()) {
+      for (int li = l0; li < l1; li++) if (P.line_set[li] > 0) n_crows += (int)(P.tok_off[li + 1] - P.tok_off[li]);
+      if (n_crows > 0) {
+        const size_t rows = (size_t)(P.tok_off[l1] - t0);
+        int* h_row_set = s.pinned.alloc<int>(rows); int* h_crows = s.pinned.alloc<int>(n_crows);
+        int n = 0;
+        for (int li = l0; li < l1; li++)
+          for (long long r = P.tok_off[li] - t0; r < P.tok_off[li + 1] - t0; r++) {
+            h_row_set[r] = P.line_set[li];
+            if (P.line_set[li] > 0) h_crows[n++] = (int)r;
+          }
+        d_row_set = s.scratch.alloc<int>(rows); d_crows = s.scratch.alloc<int>(n_crows);
+        RT_HIP_CHECK(hipMemcpyAsync(d_row_set, h_row_set, rows * sizeof(int), hipMemcpyHostToDevice, s.st));
+        RT_HIP_CHECK(hipMemcpyAsync(d_crows, h_crows, (size_t)n_crows * sizeof(int), hipMemcpyHostToDevice, s.st));
+      }
+    }
+    const float* z5 = nullptr;   // the head's input, for the candidates' and the charsets' logits
     { ProfOuter po(&s.prof, s.st, "net/rec");
-      s.rec->run(c, x, L0, Lt, d_idx + t0, d_prob + t0, cand_k > 1 ? &z5 : nullptr); }  // fused CTC head: logits never reach HBM
+      s.rec->run(c, x, L0, Lt, d_idx + t0, d_prob + t0, cand_k > 1 || n_crows > 0 ? &z5 : nullptr); }  // fused CTC head: logits never reach HBM
     if (Lt.total != P.tok_off[l1] - t0) throw RtError(RT_ERR_SHAPE, "token count mismatch");
+    if (n_crows > 0)   // the restricted rows' (idx, prob) are replaced before anything reads them
+      s.ctc_charset(s.rec->core(), z5, d_crows, n_crows, d_row_set, s.charsets->d_masks, s.charsets->words, 0, d_idx + t0, d_prob + t0);
     { ProfScope ps(&s.prof, s.st, "ctc_decode");
       pp::ctc_decode(s.st, d_idx + t0, d_prob + t0, Lt.d, ln, P.d_tok + t0, P.d_meta.ntok + l0, P.d_meta.rscore + l0); }
     if (s.cfg.rec_return_word_box) {
@@ -936,7 +1022,7 @@ void rec_groups(rt_session& s, Pipeline& P) {
     }
     if (cand_k > 0)   // (before the next group rewinds the scratch arena z5 lives in)
       s.ctc_candidates(s.rec->core(), z5, d_idx + t0, d_prob + t0, Lt.d, P.d_meta.ntok + l0, ln, Lt.total, cand_k, 0,
-                       P.d_ccol + t0, P.d_cands + t0 * cand_k);
+                       P.d_ccol + t0, P.d_cands + t0 * cand_k, d_row_set, d_row_set ? s.charsets->d_masks : nullptr, s.charsets->words);
     l0 = l1;
   }
 }
@@ -1013,7 +1099,7 @@ void results(const rt_session& s, const Pipeline& P, rt_results& res) {
 std::string rt_format_f32_impl(float v) { return fnum(v); }
 
 rt_results* rt_session::run_pages(const uint8_t* const* rgb, const int* hs, const int* ws, int n_pages, int mem,
-                                  const float* const* det_map_override, const Regions* regions) {
+                                  const float* const* det_map_override, const Regions* regions, int rec_charset_default) {
   if (g_trace) fprintf(stderr, "[rt host] %-28s %8.3f ms\n", "between calls", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - last_exit).count());
   HostTick tick0;
   // a one-page call is the reference's real mode (retto-cli/src/main.rs:80-86): it polls through its waits; a multi-page batch
@@ -1039,6 +1125,21 @@ rt_results* rt_session::run_pages(const uint8_t* const* rgb, const int* hs, cons
     db_post(*this, P); tick.lap("dbpost enqueue");
     box_round_trip(*this, P, *res); tick.lap("sync #1 + box D2H");
   }
+  // rec charsets: line k of page i is line first_line + k of the crop plan (the rec plan reorders widths, never lines)
+  if (regions && regions->charsets) {
+    bool any = false;
+    for (int i = 0; i < n_pages; i++)
+      for (int k = 0; k < P.pg[i].n_boxes && regions->charsets[i]; k++) any |= regions->charsets[i][k] > 0;
+    if (any) {
+      P.line_set.assign((size_t)P.NL, 0);
+      for (int i = 0; i < n_pages; i++)
+        for (int k = 0; k < P.pg[i].n_boxes && regions->charsets[i]; k++) P.line_set[(size_t)P.pg[i].first_line + k] = regions->charsets[i][k];
+    }
+  } else if (rec_charset_default > 0 && P.NL > 0) {
+    P.line_set.assign((size_t)P.NL, rec_charset_default);
+  }
+  for (int v : P.line_set)
+    if (v < 0 || v > (int)charsets->ids.size()) throw RtError(RT_ERR_INVALID, "unknown rec charset id " + std::to_string(v));
   crop_stage(*this, P);
   if (P.NL > 0) {
     tick.lap("crop plan + warp enqueue");
@@ -1284,6 +1385,8 @@ rt_ticket* rt_session::submit_batch(const uint8_t* const* rgb, const int* hs, co
   t->rgb.assign(rgb, rgb + n_pages); t->hs.assign(hs, hs + n_pages); t->ws.assign(ws, ws + n_pages);
   if (det_map_override) t->maps.assign(det_map_override, det_map_override + n_pages);
   if (regions) { t->quads.assign(regions->quads, regions->quads + n_pages); t->n_quads.assign(regions->n_quads, regions->n_quads + n_pages); }
+  if (regions && regions->charsets) t->region_sets.assign(regions->charsets, regions->charsets + n_pages);
+  t->rec_charset = rec_charset;   // (the lanes run later: the default is the one of the submitting call)
   t->parts.assign((size_t)nl, nullptr); t->errs.resize((size_t)nl); t->first.assign((size_t)nl + 1, 0);
   {
     // contiguous ranges of about equal work: det pixels after the session size limit (a2) plus a constant per page
@@ -1334,9 +1437,9 @@ rt_ticket* rt_session::submit_batch(const uint8_t* const* rgb, const int* hs, co
       try {
         if (!tp->ev_up.empty()) RT_HIP_CHECK(hipStreamWaitEvent(s->st, tp->ev_up[(size_t)l], 0));
         Regions rg{nullptr, nullptr};
-        if (!tp->quads.empty()) rg = Regions{tp->quads.data() + f0, tp->n_quads.data() + f0};
+        if (!tp->quads.empty()) rg = Regions{tp->quads.data() + f0, tp->n_quads.data() + f0, tp->region_sets.empty() ? nullptr : tp->region_sets.data() + f0};
         tp->parts[l] = s->run_pages(tp->rgb.data() + f0, tp->hs.data() + f0, tp->ws.data() + f0, f1 - f0, tp->mem_lane,
-                                    tp->maps.empty() ? nullptr : tp->maps.data() + f0, tp->quads.empty() ? nullptr : &rg);
+                                    tp->maps.empty() ? nullptr : tp->maps.data() + f0, tp->quads.empty() ? nullptr : &rg, tp->rec_charset);
       } catch (...) {
         tp->errs[l] = std::current_exception();
         s->failed = true;
@@ -1402,7 +1505,7 @@ rt_results* rt_session::run_batch(const uint8_t* const* rgb, const int* hs, cons
     } disarm{this};
     stage_cb = cb; stage_user = user; stage_mu = &cb_mu; page_base = 0;
     try {
-      return run_pages(rgb, hs, ws, n_pages, mem, det_map_override);
+      return run_pages(rgb, hs, ws, n_pages, mem, det_map_override, nullptr, rec_charset);
     } catch (...) { failed = true; throw; }
   }
   return wait_batch(submit_batch(rgb, hs, ws, n_pages, mem, det_map_override, cb, user));
@@ -1411,9 +1514,12 @@ rt_results* rt_session::run_batch(const uint8_t* const* rgb, const int* hs, cons
 // rt_run_regions.  A quad is clamped to the page, then held to what the crop plan needs: a crop of at least 1 x 1 pixels and an
 // invertible homography -- checked here, for every page, before anything is queued.
 rt_results* rt_session::run_regions(const uint8_t* const* rgb, const int* hs, const int* ws, int n_pages, int mem,
-                                    const float* const* quads, const int* n_quads) {
+                                    const float* const* quads, const int* n_quads, const int* const* region_charsets) {
   std::vector<std::vector<float>> clamped((size_t)n_pages);
   std::vector<const float*> qp((size_t)n_pages, nullptr);
+  // the regions' charsets with -1 resolved to the session default of this call (rec charsets, ctc_charset.h)
+  std::vector<std::vector<int>> sets((size_t)n_pages);
+  std::vector<const int*> sp((size_t)n_pages, nullptr);
   for (int i = 0; i < n_pages; i++) {
     const std::string where = "rt_run_regions: page " + std::to_string(i);
     if (hs[i] <= 0 || ws[i] <= 0 || rgb[i] == nullptr) throw RtError(RT_ERR_IMAGE, where + ": empty page");
@@ -1436,15 +1542,23 @@ rt_results* rt_session::run_regions(const uint8_t* const* rgb, const int* hs, co
       if (!gm::projection_inverse(b, d.cw, d.ch, inv)) throw RtError(RT_ERR_INVALID, at + ": singular homography (degenerate quad)");
     }
     qp[(size_t)i] = q.data();
+    sets[(size_t)i].assign((size_t)n_quads[i], rec_charset);
+    for (int k = 0; k < n_quads[i] && region_charsets && region_charsets[i]; k++) {
+      const int v = region_charsets[i][k];
+      if (v < -1 || v > (int)charsets->ids.size())
+        throw RtError(RT_ERR_INVALID, where + " region " + std::to_string(k) + ": unknown charset id " + std::to_string(v));
+      if (v >= 0) sets[(size_t)i][(size_t)k] = v;
+    }
+    sp[(size_t)i] = sets[(size_t)i].data();
   }
-  const Regions rg{qp.data(), n_quads};
+  const Regions rg{qp.data(), n_quads, sp.data()};
   const int nl = std::max(1, std::min<int>(std::min<int>((int)helpers.size() + 1, active_lanes), std::max(n_pages, 1)));
   if (nl <= 1) {   // one lane: on the caller's thread, as run_batch
     try {
       return run_pages(rgb, hs, ws, n_pages, mem, nullptr, &rg);
     } catch (...) { failed = true; throw; }
   }
-  return wait_batch(submit_batch(rgb, hs, ws, n_pages, mem, nullptr, nullptr, nullptr, nullptr, &rg));   // (clamped outlives the wait)
+  return wait_batch(submit_batch(rgb, hs, ws, n_pages, mem, nullptr, nullptr, nullptr, nullptr, &rg));   // (clamped and sets outlive the wait)
 }
 
 // RettoWorkerStageResult JSON (serde derive shapes; retto-wasm/fe/index.ts:5-42)

@@ -71,6 +71,10 @@ struct rt_ticket {
   // empty: the detector finds the boxes
   std::vector<const float*> quads;
   std::vector<int> n_quads;
+  // rec charsets (ctc_charset.h): the session default as it was when the batch was submitted (the lanes run later), and with
+  // rt_run_regions_charsets per page the regions' resolved ids (owned by the caller of submit_batch); empty: the default
+  int rec_charset = 0;
+  std::vector<const int*> region_sets;
   std::vector<int> first;
   std::vector<rt_results*> parts;
   std::vector<std::exception_ptr> errs;
@@ -99,6 +103,16 @@ struct rt_ticket {
   std::vector<EncPart> enc_parts;   // per lane part
 };
 
+// The session's rec charsets (ctc_charset.h), shared with the helper lanes.  Set k (1-based, rt_charset_create's id) has its
+// sorted class ids in ids[k - 1] and its mask at d_masks + (k - 1) * words.  Only changed while no ticket is in flight and every
+// lane's stream is drained (rt_charset_create is a guarded call), with a blocking copy.
+struct rt_charsets {
+  int words = 0;
+  std::vector<std::vector<int32_t>> ids;
+  uint32_t* d_masks = nullptr;   // [rt::cs::MAX_SETS][words], allocated by the first rt_charset_create
+  ~rt_charsets() { if (d_masks) (void)hipFree(d_masks); }
+};
+
 // internal to the library (never accepted from a caller): pages already in HBM, det map overrides still host pointers
 #define RT_MEM_STAGED_MAPS_HOST 3
 
@@ -124,6 +138,8 @@ struct rt_session {
   std::vector<std::unique_ptr<rt_session>> helpers;
   int active_lanes = 1 << 30;  // rt_set_lanes: upper bound on the lanes rt_run_batch uses
   std::vector<std::string> dict;  // RecCharacter (rec_processor.rs:29-46)
+  std::shared_ptr<rt_charsets> charsets;   // rec charsets (shared with the helper lanes)
+  int rec_charset = 0;            // rt_set_rec_charset: the default of every line of the pipeline calls that follow (0: none)
   uint8_t* d_word_raw = nullptr;  // rec_return_word_box: wb::raw_class of every dictionary entry (device; owned by the main lane)
   std::string last_error;
   int* d_flags = nullptr;         // [0] thumbnail/resize error flag
@@ -163,8 +179,18 @@ struct rt_session {
   // and left them, rows = the group's time steps, z5 [rows, core.D] the head's input (only read when K > 1).  Kept token j of a
   // line at first row o gets cols[o + j] and cands[(o + j) * K ...].  K > 1 waits for the stream once (the kept-row count sizes
   // the logits GEMMs) and recomputes in chunks of chunk_rows kept rows (0: cc::CAND_CHUNK); the workspace comes from `scratch`.
+  // row_set / masks / words (rec charsets): a kept row r with row_set[r] = s >= 1 ranks the classes of set s only.
   void ctc_candidates(const rt::SvtrCore& core, const float* z5, const int* idx, const float* prob, const rt::ImgGeom* lines,
-                      const int* n_tokens, int n_lines, long long rows, int K, int chunk_rows, int* cols, rt::cc::Cand* cands);
+                      const int* n_tokens, int n_lines, long long rows, int K, int chunk_rows, int* cols, rt::cc::Cand* cands,
+                      const int* row_set = nullptr, const uint32_t* masks = nullptr, int words = 0);
+  // Rec charsets over one rec group (ctc_charset.h), between the net and pp::ctc_decode: d_rows [n_rows] = the time steps of the
+  // group's restricted lines in line order, d_row_set [the group's rows] = every row's set (0: none), both on the device; masks
+  // [.][words] on the device.  In chunks of chunk_rows rows (0: cc::CAND_CHUNK): row gather, the CTC FC, k_ctc_charset_argmax,
+  // which overwrites idx / prob of exactly those rows.  No host wait: the rows are known from the line widths.
+  void ctc_charset(const rt::SvtrCore& core, const float* z5, const int* d_rows, int n_rows, const int* d_row_set,
+                   const uint32_t* masks, int words, int chunk_rows, int* idx, float* prob);
+  // rt_charset_create: compiles the set (rt::compile_charset), stores it and returns its id
+  int charset_create(const char* utf8, size_t len, const int32_t* ids, int n_ids);
   // L2
   // persistent lane threads (index 0 = this session's own lane) and the number of submitted, not yet waited batches
   std::vector<std::unique_ptr<LaneWorker>> workers;
@@ -183,7 +209,8 @@ struct rt_session {
   void free_stage();
   void ensure_workers();
   // regions (rt_run_regions): quads[i] = n_quads[i] x 8 validated, clamped floats of page i, valid until the ticket is waited for
-  struct Regions { const float* const* quads; const int* n_quads; };
+  // charsets (rt_run_regions_charsets): per page the regions' charset ids, already resolved (>= 0) and checked; null: the default
+  struct Regions { const float* const* quads; const int* n_quads; const int* const* charsets = nullptr; };
   rt_ticket* submit_batch(const uint8_t* const* rgb, const int* hs, const int* ws, int n_pages, int mem,
                           const float* const* det_map_override, rt_stage_callback cb = nullptr, void* user = nullptr,
                           std::vector<rt::EncodedPage>* enc = nullptr, const Regions* regions = nullptr);
@@ -193,11 +220,13 @@ struct rt_session {
   rt_results* run_batch(const uint8_t* const* rgb, const int* hs, const int* ws, int n_pages, int mem,
                         const float* const* det_map_override, rt_stage_callback cb = nullptr, void* user = nullptr);
   rt_results* run_pages(const uint8_t* const* rgb, const int* hs, const int* ws, int n_pages, int mem,
-                        const float* const* det_map_override, const Regions* regions = nullptr);  // one lane
+                        const float* const* det_map_override, const Regions* regions = nullptr,
+                        int rec_charset_default = 0);  // one lane
   // rt_run_regions: checks and clamps every quad (RT_ERR_INVALID naming page and region; nothing is queued then), then the
   // pages go over the lanes as run_batch's do, from the crop plan on
+  // charsets (or null; entries may be null): per region -1 = the session default, 0 = none, >= 1 = that charset
   rt_results* run_regions(const uint8_t* const* rgb, const int* hs, const int* ws, int n_pages, int mem,
-                          const float* const* quads, const int* n_quads);
+                          const float* const* quads, const int* n_quads, const int* const* charsets = nullptr);
 };
 
 rt_session* rt_session_create(const rt_config* cfg);
@@ -205,4 +234,9 @@ std::string rt_format_f32_impl(float v);  // serde_json / ryu form of an f32
 namespace rt {
 // RecCharacter::new (rec_processor.rs:29-46) with Rust's from_utf8 / lines / trim semantics
 std::vector<std::string> load_dictionary(const std::vector<uint8_t>& bytes);
+// A rec charset (ctc_charset.h) as its mask of cs::mask_words(dict.size()) words: the blank, every dictionary class whose whole
+// entry is one code point of utf8 [len] (duplicates all join; U+0020 is the appended " "), and ids [n_ids].  Throws RT_ERR_UTF8
+// for malformed text, RT_ERR_INVALID for a code point that matches no entry ("U+XXXX") or an id outside [0, dict.size()).
+std::vector<uint32_t> compile_charset(const std::vector<std::string>& dict, const char* utf8, size_t len, const int32_t* ids,
+                                      int n_ids);
 }
