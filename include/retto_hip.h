@@ -371,6 +371,81 @@ RT_API int rt_debug_ctc_charset_host(const float* z5, const float* W, const floa
                                      const int32_t* tokens_per_line, int n_lines, const int32_t* line_set, const uint32_t* masks,
                                      int n_sets, int K, int32_t* tokens_out, int32_t* n_tokens_out, float* scores_out,
                                      rt_candidate* cands_out, int32_t* cols_out);
+/* ---- rec lexicons: a caller's word list ranked by CTC likelihood per line -----------------------------------------------------
+ * For the enumerated field: the region holds one of N known strings (a country, a product code, a station name).  A charset only
+ * narrows the alphabet, candidates only exist at the time steps the greedy decode kept, and matching the greedy text against the
+ * list afterwards throws the model's probabilities away.  retto_amd/csrc/ctc_lexicon.h states the rule; in short, for a line of T
+ * time steps that carries a lexicon:
+ *   - the logits of every step are recomputed in fp32 from the head's input features, as for candidates and charsets, and turned
+ *     into log-probabilities by the FULL softmax over every class (a charset on the same line does not change them);
+ *   - every entry's CTC forward log-likelihood is computed in the log domain in fp32; an entry that cannot fit into T steps
+ *     (T < its length + its number of equal neighbours) is infeasible and never reported;
+ *   - the line reports up to RT_LEXICON_MATCHES feasible entries, by loglik descending then entry index ascending, each with
+ *     posterior = exp(loglik - log-sum-exp over the line's feasible entries).
+ * One limit: the lexicon lines that one rec group takes (about 24 M crop pixels) may carry 2^26 entries between them (1024 lines
+ * of a 65536-entry lexicon); a call past it fails with RT_ERR_CAPACITY.
+ * The line's tokens, score, text, word boxes, candidates and JSON stay what they are without the lexicon, bit for bit; replacing
+ * the text by the winner and aligning it for word boxes are out of scope.  Lines without a lexicon cost nothing.  The reference
+ * has no counterpart.
+ *
+ * rt_lexicon_create: the entries are the lines of utf8 [len bytes] (split and trimmed as rt_parse_dictionary's lines; empty
+ * lines skipped), read code point by code point, each the LOWEST class id whose whole dictionary entry is that code point (U+0020
+ * is the appended " "); then n_id_entries entries given as class ids, entry_lens[i] ids each, consecutive in ids (may be NULL
+ * with n_id_entries = 0).  Entry numbers count from 0 in that order.  *lexicon_out: the new id, 1-based, valid until rt_destroy;
+ * a session holds at most RT_MAX_LEXICONS.  Errors: a code point that matches no entry -> RT_ERR_INVALID naming it as U+XXXX and
+ * the entry; malformed UTF-8 -> RT_ERR_UTF8; an id of 0 or outside [1, classes), an empty id entry, an entry of more than
+ * RT_LEXICON_MAX_LEN ids, no entry at all -> RT_ERR_INVALID; more than RT_LEXICON_MAX_ENTRIES entries, or the lexicon cap ->
+ * RT_ERR_CAPACITY.  Fails like every other call while tickets are in flight. */
+#define RT_MAX_LEXICONS 16
+#define RT_LEXICON_MAX_ENTRIES 65536
+#define RT_LEXICON_MAX_LEN 31
+#define RT_LEXICON_MATCHES 4
+typedef struct rt_lexicon_match { int32_t entry; float loglik; float posterior; } rt_lexicon_match;
+RT_API int rt_lexicon_create(rt_session* s, const char* utf8, size_t len, const int32_t* ids, const int32_t* entry_lens,
+                             int n_id_entries, int* lexicon_out);
+/* the number of entries of a lexicon (0 for an unknown id) */
+RT_API int rt_lexicon_entries(const rt_session* s, int lexicon);
+/* the length of an entry (0 for an unknown lexicon or entry); *ids (optional): its class ids, library-owned until rt_destroy */
+RT_API int rt_lexicon_entry(const rt_session* s, int lexicon, int entry, const int32_t** ids);
+/* an entry as UTF-8 (its classes' dictionary texts joined), library-owned until rt_destroy; NULL for an unknown lexicon or entry */
+RT_API const char* rt_lexicon_entry_text(const rt_session* s, int lexicon, int entry);
+/* The session default: the lexicon of every line of every pipeline call that follows; 0 = none (the initial state).
+ * rt_submit_* takes the value as it is at the call. */
+RT_API int rt_set_rec_lexicon(rt_session* s, int lexicon);
+/* rt_run_regions with a charset and a lexicon per region: charsets[i][k] / lexicons[i][k] for region k of page i; -1 = the
+ * session default, 0 = none, >= 1 = that charset / lexicon.  Either array, or an entry of it, may be NULL: -1 throughout.  An
+ * unknown id: RT_ERR_INVALID naming the page and the region, nothing queued. */
+RT_API int rt_run_regions_lexicons(rt_session* s, const uint8_t* const* rgb, const int* hs, const int* ws, int n_pages, int mem,
+                                   const float* const* quads, const int* n_quads, const int32_t* const* charsets,
+                                   const int32_t* const* lexicons, rt_results** out);
+/* the matches of a line: their number (0 when the line had no lexicon); *m (optional): the matches, best first */
+RT_API int rt_results_rec_lexicon(const rt_results* r, int page, int line, const rt_lexicon_match** m);
+/* the lexicon a line was scored against (0: none) */
+RT_API int rt_results_rec_lexicon_id(const rt_results* r, int page, int line);
+/* What rt_lexicon_create compiles, GPU-free and sessionless: dict = dictionary file bytes (parsed as rt_parse_dictionary does).
+ * ids_out [ids_cap] / lens_out [lens_cap]: the entries' class ids, entry after entry, and their lengths; *n_ids_out / *n_entries_out:
+ * how many there are (also when a cap was too small: RT_ERR_INVALID then, nothing copied); *n_classes: the dictionary's class
+ * count.  The same code, errors and messages as rt_lexicon_create (err: optional, err_cap bytes). */
+RT_API int rt_debug_lexicon_compile(const void* dict, size_t dict_len, const char* utf8, size_t len, const int32_t* ids,
+                                    const int32_t* entry_lens, int n_id_entries, int32_t* ids_out, int ids_cap, int32_t* lens_out,
+                                    int lens_cap, int* n_ids_out, int* n_entries_out, int* n_classes, char* err, size_t err_cap);
+/* The device path of the lexicons on host arrays (row gather in chunks of whole lines, the CTC FC GEMM, k_ctc_row_lse,
+ * k_ctc_lexicon_forward, k_ctc_lexicon_topk).  z5, W, bias, N, tokens_per_line, n_lines, chunk_rows: as rt_debug_ctc_charset.
+ * line_lex [n_lines]: 0 = none, k >= 1 = lexicon k, whose entries are [lex_first_entry[k - 1], lex_first_entry[k]) of the flat
+ * list: entry j has entry_lens[j] ids (1 .. RT_LEXICON_MAX_LEN, each in [1, N)), consecutive in entry_ids; lex_first_entry
+ * [n_lex + 1] ascends from 0, every lexicon has at least one entry.  loglik_out (optional): the full table, line after line, one
+ * float per entry of the line's lexicon (none for a line of lexicon 0), -inf where infeasible.  matches_out [n_lines]
+ * [RT_LEXICON_MATCHES], n_matches_out [n_lines]: slots past a line's count, and everything of a line of lexicon 0 but its count
+ * (0), keep what the caller put there. */
+RT_API int rt_debug_ctc_lexicon(rt_session* s, const float* z5, const float* W, const float* bias, int N,
+                                const int32_t* tokens_per_line, int n_lines, const int32_t* line_lex, const int32_t* entry_ids,
+                                const int32_t* entry_lens, const int32_t* lex_first_entry, int n_lex, int chunk_rows,
+                                float* loglik_out, rt_lexicon_match* matches_out, int32_t* n_matches_out);
+/* The same rule on the CPU in plain fp32 loops (ctc_lexicon.h), GPU-free and sessionless; same layout. */
+RT_API int rt_debug_ctc_lexicon_host(const float* z5, const float* W, const float* bias, int N, const int32_t* tokens_per_line,
+                                     int n_lines, const int32_t* line_lex, const int32_t* entry_ids, const int32_t* entry_lens,
+                                     const int32_t* lex_first_entry, int n_lex, float* loglik_out, rt_lexicon_match* matches_out,
+                                     int32_t* n_matches_out);
 /* f32 sum of every det probability map produced in the call (keeps the network's
  * output observable when det_map_override is used) */
 RT_API double rt_results_det_checksum(const rt_results* r);

@@ -190,6 +190,9 @@ class RecProcessorSingleResult:
     # than K classes); token_cols: the tokens' time steps
     candidates: Optional[List[List[Tuple[int, str, float]]]] = None
     token_cols: Optional[np.ndarray] = None
+    # rec lexicons (create_lexicon): None when the line carried no lexicon, else up to LEXICON_MATCHES (entry, text, loglik,
+    # posterior), best first: the lexicon's entries ranked by their CTC forward log-likelihood under the line's own distribution
+    lexicon_matches: Optional[List[Tuple[int, str, float, float]]] = None
 
 
 @dataclass
@@ -417,6 +420,37 @@ def debug_charset_compile(dict_bytes: bytes, text: str = "", ids: Sequence[int] 
     return mask
 
 
+def _lexicon_id_arrays(ids):
+    """entries given as class ids -> (flat ids, lengths, count) as ctypes arrays"""
+    ids = [[int(c) for c in e] for e in ids]
+    flat = [c for e in ids for c in e]
+    return (C.c_int32 * max(len(flat), 1))(*flat), (C.c_int32 * max(len(ids), 1))(*[len(e) for e in ids]), len(ids)
+
+
+def _lexicon_text(entries) -> bytes:
+    return entries if isinstance(entries, (bytes, bytearray)) else "\n".join(entries).encode("utf-8")
+
+
+def debug_lexicon_compile(dict_bytes: bytes, entries=(), ids=()) -> List[List[int]]:
+    """rt_debug_lexicon_compile: what RettoSession.create_lexicon compiles (retto_amd/csrc/ctc_lexicon.h), GPU-free: every
+    entry as its list of class ids.  entries: strings (one entry each), or bytes to pass raw UTF-8 lines; ids: entries given as
+    class ids, appended."""
+    lib = _lib.load()
+    dict_bytes = bytes(dict_bytes)
+    raw = bytes(_lexicon_text(entries))
+    arr, lens, n_id = _lexicon_id_arrays(ids)
+    ni, ne, nc = C.c_int(), C.c_int(), C.c_int()
+    err = C.create_string_buffer(256)
+    cap_i, cap_e = len(raw) + len(arr) + 1, raw.count(b"\n") + n_id + 2
+    out_i = np.zeros(cap_i, np.int32); out_e = np.zeros(cap_e, np.int32)
+    rc = lib.rt_debug_lexicon_compile(dict_bytes, len(dict_bytes), raw, len(raw), arr, lens, n_id, out_i.ctypes.data, cap_i,
+                                      out_e.ctypes.data, cap_e, C.byref(ni), C.byref(ne), C.byref(nc), err, len(err))
+    if rc != 0:
+        raise _ERRS.get(rc, RettoError)(err.value.decode("utf-8", "replace"))
+    offs = np.concatenate([[0], np.cumsum(out_e[:ne.value])])
+    return [out_i[offs[j]:offs[j + 1]].tolist() for j in range(ne.value)]
+
+
 def parse_dictionary(data: bytes) -> List[str]:
     """rt_parse_dictionary: RecCharacter::new (rec_processor.rs:29-46) -- "blank", the file's trimmed lines, " "."""
     lib = _lib.load()
@@ -569,7 +603,7 @@ class RettoSession:
             words = self._words(r, page, k) if self.config.rec_processor_config.return_word_box else None
             cands, cols = self._candidates(r, page, k, nt)
             rec.append(RecProcessorSingleResult(lib.rt_results_rec_text(r, page, k).decode("utf-8"), float(rs[k]), toks, words,
-                                                cands, cols))
+                                                cands, cols, self._lexicon_matches(r, page, k)))
         return RettoWorkerResult(det, cls, rec)
 
     def _dictionary(self) -> List[str]:
@@ -586,6 +620,16 @@ class RettoSession:
         K = self._hd.lib.rt_results_rec_candidates(r, page, line, C.byref(cp), C.byref(colp))
         return _candidate_lists(cp, K, n_tokens, self._dictionary()), \
             (np.ctypeslib.as_array(colp, (n_tokens,)).copy() if n_tokens else np.zeros(0, np.int32))
+
+    def _lexicon_matches(self, r, page: int, line: int):
+        lib = self._hd.lib
+        lex = lib.rt_results_rec_lexicon_id(r, page, line)
+        if lex <= 0:
+            return None
+        mp = C.POINTER(_lib.LexiconMatch)()
+        n = lib.rt_results_rec_lexicon(r, page, line, C.byref(mp))
+        return [(int(mp[j].entry), lib.rt_lexicon_entry_text(self._hd.h, lex, mp[j].entry).decode("utf-8"), float(mp[j].loglik),
+                 float(mp[j].posterior)) for j in range(n)]
 
     def _words(self, r, page: int, line: int) -> List[RecWord]:
         lib = self._hd.lib
@@ -624,10 +668,38 @@ class RettoSession:
         """rt_set_rec_charset: the charset of every line of the pipeline calls that follow; 0 = none."""
         _check(self._hd.lib.rt_set_rec_charset(self._hd.h, int(charset)), self._hd.h)
 
-    def run_regions_raw(self, pages, hs, ws, quads, mem=RT_MEM_HOST, charsets=None):
+    # -- rec lexicons -----------------------------------------------------------------------
+    def create_lexicon(self, entries=(), ids=()) -> int:
+        """rt_lexicon_create: a word list whose entries a line's result ranks by their CTC forward log-likelihood
+        (RecProcessorSingleResult.lexicon_matches).  entries: strings, one entry each, read character by character (each the
+        lowest class whose whole dictionary entry is that character); ids: entries given as lists of class ids, appended.
+        Returns the lexicon's id (1-based, valid for the session's life; at most MAX_LEXICONS); see set_rec_lexicon and
+        run_regions(lexicons=...)."""
+        raw = bytes(_lexicon_text(entries))
+        arr, lens, n_id = _lexicon_id_arrays(ids)
+        out = C.c_int()
+        _check(self._hd.lib.rt_lexicon_create(self._hd.h, raw, len(raw), arr, lens, n_id, C.byref(out)), self._hd.h)
+        return out.value
+
+    def lexicon_entries(self, lexicon: int) -> List[Tuple[List[int], str]]:
+        """rt_lexicon_entries / _entry / _entry_text: every entry of a lexicon as (class ids, text); empty for an unknown id."""
+        lib, h = self._hd.lib, self._hd.h
+        out = []
+        for e in range(lib.rt_lexicon_entries(h, int(lexicon))):
+            p = C.POINTER(C.c_int32)()
+            n = lib.rt_lexicon_entry(h, int(lexicon), e, C.byref(p))
+            out.append(([int(p[i]) for i in range(n)], lib.rt_lexicon_entry_text(h, int(lexicon), e).decode("utf-8")))
+        return out
+
+    def set_rec_lexicon(self, lexicon: int) -> None:
+        """rt_set_rec_lexicon: the lexicon of every line of the pipeline calls that follow; 0 = none."""
+        _check(self._hd.lib.rt_set_rec_lexicon(self._hd.h, int(lexicon)), self._hd.h)
+
+    def run_regions_raw(self, pages, hs, ws, quads, mem=RT_MEM_HOST, charsets=None, lexicons=None):
         """rt_run_regions.  pages: host arrays or device pointers (ints); quads[i]: the regions of page i, anything that
         reshapes to [n_i, 8] floats (TL, TR, BR, BL in original-page coordinates).  charsets (rt_run_regions_charsets): per
-        page None or one id per region (-1 = the session default, 0 = unrestricted).  Returns an opaque results handle."""
+        page None or one id per region (-1 = the session default, 0 = unrestricted); lexicons (rt_run_regions_lexicons): the same for
+        lexicon ids.  Returns an opaque results handle."""
         lib, h = self._hd.lib, self._hd.h
         n = len(pages)
         if len(quads) != n:
@@ -640,30 +712,42 @@ class RettoSession:
             arr_q[i] = q.ctypes.data if len(q) else None
             arr_n[i] = len(q)
         out = C.c_void_p()
-        if charsets is not None:
-            if len(charsets) != n:
-                raise InvalidArgument("run_regions: one list of charset ids per page (or None)")
+
+        def id_arrays(per_page, what):
+            if len(per_page) != n:
+                raise InvalidArgument("run_regions: one list of %s ids per page (or None)" % what)
             arr_c = (C.c_void_p * max(n, 1))()
             for i in range(n):
-                if charsets[i] is None:
+                if per_page[i] is None:
                     arr_c[i] = None
                     continue
-                c = np.ascontiguousarray(charsets[i], np.int32).reshape(-1); keep.append(c)
+                c = np.ascontiguousarray(per_page[i], np.int32).reshape(-1); keep.append(c)
                 if len(c) != arr_n[i]:
-                    raise InvalidArgument("run_regions: page %d has %d regions but %d charset ids" % (i, arr_n[i], len(c)))
+                    raise InvalidArgument("run_regions: page %d has %d regions but %d %s ids" % (i, arr_n[i], len(c), what))
                 arr_c[i] = c.ctypes.data if len(c) else None
-            _check(lib.rt_run_regions_charsets(h, arr_p, arr_h, arr_w, n, mem, arr_q, arr_n, arr_c, C.byref(out)), h)
+            return arr_c
+
+        if lexicons is not None:
+            arr_c = id_arrays(charsets, "charset") if charsets is not None else None
+            _check(lib.rt_run_regions_lexicons(h, arr_p, arr_h, arr_w, n, mem, arr_q, arr_n, arr_c, id_arrays(lexicons, "lexicon"),
+                                               C.byref(out)), h)
+            return out
+        if charsets is not None:
+            _check(lib.rt_run_regions_charsets(h, arr_p, arr_h, arr_w, n, mem, arr_q, arr_n, id_arrays(charsets, "charset"),
+                                               C.byref(out)), h)
             return out
         _check(lib.rt_run_regions(h, arr_p, arr_h, arr_w, n, mem, arr_q, arr_n, C.byref(out)), h)
         return out
 
-    def run_regions(self, pages: Sequence[np.ndarray], quads, charsets=None) -> List[RettoWorkerResult]:
+    def run_regions(self, pages: Sequence[np.ndarray], quads, charsets=None, lexicons=None) -> List[RettoWorkerResult]:
         """The pipeline over regions the caller already knows (rt_run_regions): quads[i] = the [n_i, 4, 2] (or [n_i, 8]) quads
         of page i in original-page coordinates, TL, TR, BR, BL.  No detector runs; line k of a page is cut from the page as it
         is by quad k clamped to the page.  det_result holds the clamped quads with score 1.0.  charsets: per page None or one
-        charset id per region (create_charset; -1 = the session default, 0 = unrestricted)."""
+        charset id per region (create_charset; -1 = the session default, 0 = unrestricted); lexicons: the same with lexicon
+        ids (create_lexicon; 0 = none)."""
         pages = [np.ascontiguousarray(p, np.uint8) for p in pages]
-        r = self.run_regions_raw(pages, [p.shape[0] for p in pages], [p.shape[1] for p in pages], quads, charsets=charsets)
+        r = self.run_regions_raw(pages, [p.shape[0] for p in pages], [p.shape[1] for p in pages], quads, charsets=charsets,
+                                 lexicons=lexicons)
         try:
             self.last_det_checksum = self._hd.lib.rt_results_det_checksum(r)
             return [self._collect(r, i) for i in range(len(pages))]

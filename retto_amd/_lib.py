@@ -53,6 +53,16 @@ class Candidate(C.Structure):   # rt_candidate
 MAX_CANDIDATES = 8   # RT_MAX_CANDIDATES
 MAX_CHARSETS = 64    # RT_MAX_CHARSETS
 
+
+class LexiconMatch(C.Structure):   # rt_lexicon_match
+    _fields_ = [("entry", C.c_int32), ("loglik", C.c_float), ("posterior", C.c_float)]
+
+
+MAX_LEXICONS = 16            # RT_MAX_LEXICONS
+LEXICON_MAX_ENTRIES = 65536  # RT_LEXICON_MAX_ENTRIES
+LEXICON_MAX_LEN = 31         # RT_LEXICON_MAX_LEN
+LEXICON_MATCHES = 4          # RT_LEXICON_MATCHES
+
 # every symbol include/retto_hip.h declares (tests check that each is exported)
 EXPORTS = [
     "rt_config_default", "rt_create", "rt_destroy", "rt_last_error", "rt_version",
@@ -72,6 +82,9 @@ EXPORTS = [
     "rt_run_regions", "rt_debug_warp_crops",
     "rt_charset_create", "rt_charset_classes", "rt_set_rec_charset", "rt_run_regions_charsets", "rt_debug_charset_compile",
     "rt_debug_ctc_charset", "rt_debug_ctc_charset_host",
+    "rt_lexicon_create", "rt_lexicon_entries", "rt_lexicon_entry", "rt_lexicon_entry_text", "rt_set_rec_lexicon",
+    "rt_run_regions_lexicons", "rt_results_rec_lexicon", "rt_results_rec_lexicon_id", "rt_debug_lexicon_compile",
+    "rt_debug_ctc_lexicon", "rt_debug_ctc_lexicon_host",
 ]
 
 STAGE_CALLBACK = C.CFUNCTYPE(None, C.c_void_p, C.c_int, C.c_int, C.c_char_p)  # rt_stage_callback
@@ -225,5 +238,22 @@ def load():
     lib.rt_debug_ctc_charset_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                               C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                               C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.rt_lexicon_create.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t, P(C.c_int32), P(C.c_int32), C.c_int, P(C.c_int)]
+    lib.rt_lexicon_entries.argtypes = [C.c_void_p, C.c_int]
+    lib.rt_lexicon_entry.argtypes = [C.c_void_p, C.c_int, C.c_int, P(P(C.c_int32))]
+    lib.rt_lexicon_entry_text.argtypes = [C.c_void_p, C.c_int, C.c_int]
+    lib.rt_lexicon_entry_text.restype = C.c_char_p
+    lib.rt_set_rec_lexicon.argtypes = [C.c_void_p, C.c_int]
+    lib.rt_run_regions_lexicons.argtypes = [C.c_void_p, P(C.c_void_p), P(C.c_int), P(C.c_int), C.c_int, C.c_int, P(C.c_void_p),
+                                            P(C.c_int), P(C.c_void_p), P(C.c_void_p), P(C.c_void_p)]
+    lib.rt_results_rec_lexicon.argtypes = [C.c_void_p, C.c_int, C.c_int, P(P(LexiconMatch))]
+    lib.rt_results_rec_lexicon_id.argtypes = [C.c_void_p, C.c_int, C.c_int]
+    lib.rt_debug_lexicon_compile.argtypes = [C.c_char_p, C.c_size_t, C.c_char_p, C.c_size_t, P(C.c_int32), P(C.c_int32), C.c_int,
+                                             C.c_void_p, C.c_int, C.c_void_p, C.c_int, P(C.c_int), P(C.c_int), P(C.c_int),
+                                             C.c_char_p, C.c_size_t]
+    lib.rt_debug_ctc_lexicon.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
+                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.rt_debug_ctc_lexicon_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
+                                              C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
     _lib = lib
     return lib

@@ -44,6 +44,9 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--rec-charset", default=None, metavar="TEXT",
                     help="restrict every line's CTC decode to these characters (one charset, made the session default): the "
                          "dictionary classes whose whole entry is one character of TEXT, plus the blank")
+    ap.add_argument("--rec-lexicon", default=None, metavar="FILE",
+                    help="a word list, one entry per line: every line's result also ranks these entries by their CTC forward "
+                         "log-likelihood (one lexicon, made the session default; the recognised text itself is unchanged)")
     return ap
 
 
@@ -76,6 +79,9 @@ def main(argv=None) -> int:
     session = retto_amd.RettoSession(cfg)
     if a.rec_charset is not None:
         session.set_rec_charset(session.create_charset(a.rec_charset))
+    if a.rec_lexicon is not None:
+        with open(a.rec_lexicon, "rb") as f:
+            session.set_rec_lexicon(session.create_lexicon(f.read()))
     files = walk_files(a.images)
     log.info("Found %d files, processing...", len(files))
     out = open(a.json, "w") if a.json else None
@@ -105,6 +111,9 @@ def main(argv=None) -> int:
                     rec["candidates"] = [[[{"id": i, "text": s, "prob": p} for i, s, p in tok] for tok in t.candidates]
                                          for t in r.rec_result]
                     rec["token_cols"] = [[int(c) for c in t.token_cols] for t in r.rec_result]
+                if a.rec_lexicon is not None:   # per line: up to 4 {entry, text, loglik, posterior}, best first
+                    rec["lexicon_matches"] = [[{"entry": e, "text": s, "loglik": ll, "posterior": p}
+                                               for e, s, ll, p in (t.lexicon_matches or [])] for t in r.rec_result]
                 out.write(json.dumps(rec, ensure_ascii=False) + "\n")
     dur = time.perf_counter() - start
     if out:

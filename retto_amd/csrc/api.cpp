@@ -1,6 +1,6 @@
 // extern "C" surface of libretto_hip.so (include/retto_hip.h): sessions, the networks, the pipeline stages, batches, results,
 // parsers and device memory, with the feature-level debug hooks that are thin forwards into their features (rt_debug_warp_crops,
-// rt_debug_jpeg_reconstruct, rt_debug_word_boxes, rt_debug_ctc_candidates_host, rt_debug_charset_compile, rt_debug_ctc_charset_host).  The kernel-level diagnostics (rt_debug_set_variants,
+// rt_debug_jpeg_reconstruct, rt_debug_word_boxes, rt_debug_ctc_candidates_host, rt_debug_charset_compile, rt_debug_ctc_charset_host, rt_debug_lexicon_compile, rt_debug_ctc_lexicon_host).  The kernel-level diagnostics (rt_debug_set_variants,
 // rt_bench_*, and the rt_debug_* harnesses the kernel tests drive) are in api_debug.cpp; api_internal.h holds what both share.
 #include <thread>
 #include <sched.h>
@@ -55,6 +55,42 @@ bool rt::charset_args_ok(const float* z5, const float* W, int N, const int32_t* 
     if (idx[r] < 0 || idx[r] >= N) return false;
   *rows_out = rows;
   return true;
+}
+std::string rt::lexicon_args_error(const float* z5, const float* W, int N, const int32_t* tokens_per_line, int n_lines,
+                                   const int32_t* line_lex, const int32_t* entry_ids, const int32_t* entry_lens,
+                                   const int32_t* lex_first_entry, int n_lex, const rt_lexicon_match* matches_out,
+                                   const int32_t* n_matches_out, long long* rows_out, long long* table_out) {
+  auto S = [](long long v) { return std::to_string(v); };
+  if (!z5 || !W || !tokens_per_line || !line_lex || !entry_ids || !entry_lens || !lex_first_entry || !matches_out || !n_matches_out)
+    return "a required pointer is null";
+  if (n_lines <= 0) return "n_lines must be positive";
+  if (N <= 1) return "N must be at least 2 (the blank and one class)";
+  if (n_lex < 1 || n_lex > RT_MAX_LEXICONS) return "n_lex = " + S(n_lex) + " is outside [1, RT_MAX_LEXICONS]";
+  if (lex_first_entry[0] != 0) return "lex_first_entry[0] must be 0";
+  for (int k = 0; k < n_lex; k++) {
+    const long long n = (long long)lex_first_entry[k + 1] - lex_first_entry[k];
+    if (n < 1 || n > RT_LEXICON_MAX_ENTRIES) return "lexicon " + S(k + 1) + " has " + S(n) + " entries, outside [1, RT_LEXICON_MAX_ENTRIES]";
+  }
+  long long o = 0;
+  for (int j = 0; j < lex_first_entry[n_lex]; j++) {
+    if (entry_lens[j] < 1 || entry_lens[j] > RT_LEXICON_MAX_LEN)
+      return "entry " + S(j) + " has " + S(entry_lens[j]) + " ids, outside [1, RT_LEXICON_MAX_LEN]";
+    for (int i = 0; i < entry_lens[j]; i++)
+      if (entry_ids[o + i] < 1 || entry_ids[o + i] >= N)
+        return "class id " + S(entry_ids[o + i]) + " in entry " + S(j) + " is outside [1, " + S(N) + ")";
+    o += entry_lens[j];
+  }
+  long long rows = 0, table = 0;
+  for (int i = 0; i < n_lines; i++) {
+    if (tokens_per_line[i] < 0) return "line " + S(i) + " has a negative number of time steps";
+    if (line_lex[i] < 0 || line_lex[i] > n_lex) return "line " + S(i) + " names lexicon " + S(line_lex[i]) + ", outside [0, " + S(n_lex) + "]";
+    rows += tokens_per_line[i];
+    if (line_lex[i] > 0) table += lex_first_entry[line_lex[i]] - lex_first_entry[line_lex[i] - 1];
+  }
+  if (rows >= (1ll << 30)) return "the lines have " + S(rows) + " time steps, 2^30 or more";
+  if (table >= (1ll << 30)) return "the loglik table has " + S(table) + " floats, 2^30 or more";
+  *rows_out = rows; *table_out = table;
+  return std::string();
 }
 
 extern "C" {
@@ -257,6 +293,48 @@ int rt_set_rec_charset(rt_session* s, int charset) {
     if (charset < 0 || charset > (int)s->charsets->ids.size())
       throw RtError(RT_ERR_INVALID, "rt_set_rec_charset: unknown charset id " + std::to_string(charset));
     s->rec_charset = charset;
+  });
+}
+int rt_run_regions_lexicons(rt_session* s, const uint8_t* const* rgb, const int* hs, const int* ws, int n_pages, int mem,
+                            const float* const* quads, const int* n_quads, const int32_t* const* charsets,
+                            const int32_t* const* lexicons, rt_results** out) {
+  RT_REQUIRE(s && out && n_pages >= 0 && (n_pages == 0 || (rgb && hs && ws && quads && n_quads)), s, "rt_run_regions_lexicons: bad argument");
+  RT_REQUIRE(mem == RT_MEM_HOST || mem == RT_MEM_DEVICE, s, "rt_run_regions_lexicons: mem must be RT_MEM_HOST or RT_MEM_DEVICE");
+  *out = nullptr;
+  return guarded(s, [&] { *out = s->run_regions(rgb, hs, ws, n_pages, mem, quads, n_quads, charsets, lexicons); });
+}
+int rt_lexicon_create(rt_session* s, const char* utf8, size_t len, const int32_t* ids, const int32_t* entry_lens, int n_id_entries,
+                      int* lexicon_out) {
+  RT_REQUIRE(s && lexicon_out && (utf8 || !len) && n_id_entries >= 0 && ((ids && entry_lens) || !n_id_entries), s,
+             "rt_lexicon_create: bad argument");
+  *lexicon_out = 0;
+  return guarded(s, [&] { *lexicon_out = s->lexicon_create(utf8, len, ids, entry_lens, n_id_entries); });
+}
+static const rt_lexicons::Host* lexicon_of(const rt_session* s, int lexicon) {
+  if (!s || !s->lexicons || lexicon < 1 || lexicon > (int)s->lexicons->host.size()) return nullptr;
+  return s->lexicons->host[(size_t)lexicon - 1].get();
+}
+int rt_lexicon_entries(const rt_session* s, int lexicon) {
+  const rt_lexicons::Host* h = lexicon_of(s, lexicon);
+  return h ? (int)h->lens.size() : 0;
+}
+int rt_lexicon_entry(const rt_session* s, int lexicon, int entry, const int32_t** ids) {
+  const rt_lexicons::Host* h = lexicon_of(s, lexicon);
+  if (!h || entry < 0 || entry >= (int)h->lens.size()) return 0;
+  if (ids) *ids = h->ids.data() + h->off[(size_t)entry];
+  return h->lens[(size_t)entry];
+}
+const char* rt_lexicon_entry_text(const rt_session* s, int lexicon, int entry) {
+  const rt_lexicons::Host* h = lexicon_of(s, lexicon);
+  if (!h || entry < 0 || entry >= (int)h->text.size()) return nullptr;
+  return h->text[(size_t)entry].c_str();
+}
+int rt_set_rec_lexicon(rt_session* s, int lexicon) {
+  RT_REQUIRE(s, s, "rt_set_rec_lexicon: null session");
+  return guarded(s, [&] {
+    if (lexicon < 0 || lexicon > (int)s->lexicons->host.size())
+      throw RtError(RT_ERR_INVALID, "rt_set_rec_lexicon: unknown lexicon id " + std::to_string(lexicon));
+    s->rec_lexicon = lexicon;
   });
 }
 int rt_submit_batch(rt_session* s, const uint8_t* const* rgb, const int* hs, const int* ws, int n_pages, int mem,
@@ -612,6 +690,93 @@ int rt_debug_ctc_charset_host(const float* z5, const float* W, const float* bias
           if (m) { cs::row_logits(z, D, W, bias, N, logits.data()); cs::row_candidates(logits.data(), N, m, c[0].id, K, c); }
           else cc::row_candidates(z, D, W, bias, N, c[0].id, K, c, logits.data());
         }
+      }
+      o += T;
+    }
+    return RT_OK;
+  } catch (const std::exception&) {
+    return RT_ERR_BACKEND;
+  }
+}
+static_assert(RT_MAX_LEXICONS == lx::MAX_LEXICONS && RT_LEXICON_MAX_ENTRIES == lx::MAX_ENTRIES && RT_LEXICON_MAX_LEN == lx::MAX_LEN &&
+                  RT_LEXICON_MATCHES == lx::MATCHES, "the RT_LEXICON_* limits and lx:: must agree");
+static_assert(sizeof(rt_lexicon_match) == sizeof(lx::Match) && offsetof(rt_lexicon_match, loglik) == offsetof(lx::Match, loglik) &&
+                  offsetof(rt_lexicon_match, posterior) == offsetof(lx::Match, posterior), "rt_lexicon_match and lx::Match must share one layout");
+int rt_results_rec_lexicon(const rt_results* r, int page, int line, const rt_lexicon_match** m) {
+  auto* p = RT_PAGE(r, page);
+  if (!p || line < 0 || (size_t)line >= p->lex_n.size()) return 0;
+  if (m) *m = reinterpret_cast<const rt_lexicon_match*>(p->lex_matches.data()) + (size_t)line * lx::MATCHES;
+  return p->lex_n[(size_t)line];
+}
+int rt_results_rec_lexicon_id(const rt_results* r, int page, int line) {
+  auto* p = RT_PAGE(r, page);
+  if (!p || line < 0 || (size_t)line >= p->lex_id.size()) return 0;
+  return p->lex_id[(size_t)line];
+}
+int rt_debug_lexicon_compile(const void* dict, size_t dict_len, const char* utf8, size_t len, const int32_t* ids,
+                             const int32_t* entry_lens, int n_id_entries, int32_t* ids_out, int ids_cap, int32_t* lens_out,
+                             int lens_cap, int* n_ids_out, int* n_entries_out, int* n_classes, char* err, size_t err_cap) {
+  if (err && err_cap) err[0] = 0;
+  if ((!dict && dict_len) || (!utf8 && len) || n_id_entries < 0 || ((!ids || !entry_lens) && n_id_entries) || !n_ids_out ||
+      !n_entries_out || !n_classes || ids_cap < 0 || lens_cap < 0 || (!ids_out && ids_cap) || (!lens_out && lens_cap)) {
+    if (err && err_cap) snprintf(err, err_cap, "rt_debug_lexicon_compile: bad argument");
+    return RT_ERR_INVALID;
+  }
+  *n_ids_out = 0; *n_entries_out = 0; *n_classes = 0;
+  try {
+    std::vector<uint8_t> bytes((const uint8_t*)dict, (const uint8_t*)dict + dict_len);
+    const std::vector<std::string> d = rt::load_dictionary(bytes);
+    *n_classes = (int)d.size();
+    std::vector<int32_t> vi, vl;
+    rt::compile_lexicon(d, utf8, len, ids, entry_lens, n_id_entries, vi, vl);
+    *n_ids_out = (int)vi.size(); *n_entries_out = (int)vl.size();
+    if ((size_t)ids_cap < vi.size() || (size_t)lens_cap < vl.size())
+      throw RtError(RT_ERR_INVALID, "rt_debug_lexicon_compile: the lexicon needs " + std::to_string(vi.size()) + " ids and " +
+                                        std::to_string(vl.size()) + " lengths");
+    memcpy(ids_out, vi.data(), vi.size() * sizeof(int32_t));
+    memcpy(lens_out, vl.data(), vl.size() * sizeof(int32_t));
+    return RT_OK;
+  } catch (const RtError& e) {
+    if (err && err_cap) snprintf(err, err_cap, "%s", e.what());
+    return e.code;
+  } catch (const std::exception& e) {
+    if (err && err_cap) snprintf(err, err_cap, "%s", e.what());
+    return RT_ERR_BACKEND;
+  }
+}
+int rt_debug_ctc_lexicon_host(const float* z5, const float* W, const float* bias, int N, const int32_t* tokens_per_line,
+                              int n_lines, const int32_t* line_lex, const int32_t* entry_ids, const int32_t* entry_lens,
+                              const int32_t* lex_first_entry, int n_lex, float* loglik_out, rt_lexicon_match* matches_out,
+                              int32_t* n_matches_out) {
+  long long rows = 0, table = 0;
+  const std::string bad = lexicon_args_error(z5, W, N, tokens_per_line, n_lines, line_lex, entry_ids, entry_lens, lex_first_entry, n_lex,
+                                             matches_out, n_matches_out, &rows, &table);
+  if (!bad.empty()) {
+    rt::create_error() = "rt_debug_ctc_lexicon_host: " + bad;
+    return RT_ERR_INVALID;
+  }
+  try {
+    const int D = 120;
+    std::vector<long long> id_off((size_t)lex_first_entry[n_lex] + 1, 0);
+    for (int j = 0; j < lex_first_entry[n_lex]; j++) id_off[(size_t)j + 1] = id_off[(size_t)j] + entry_lens[j];
+    std::vector<float> logits, lse, row;
+    long long o = 0, out = 0;
+    for (int i = 0; i < n_lines; i++) {
+      const int T = tokens_per_line[i];
+      n_matches_out[i] = 0;
+      if (line_lex[i] > 0) {
+        logits.assign((size_t)std::max(T, 1) * N, 0.0f); lse.assign((size_t)std::max(T, 1), 0.0f);
+        for (int t = 0; t < T; t++) {
+          cs::row_logits(z5 + (size_t)(o + t) * D, D, W, bias, N, logits.data() + (size_t)t * N);
+          lse[(size_t)t] = lx::row_lse(logits.data() + (size_t)t * N, N);
+        }
+        const int e0 = lex_first_entry[line_lex[i] - 1], n = lex_first_entry[line_lex[i]] - e0;
+        row.assign((size_t)n, 0.0f);
+        for (int e = 0; e < n; e++)
+          row[(size_t)e] = lx::entry_loglik(logits.data(), N, lse.data(), T, entry_ids + id_off[(size_t)(e0 + e)], entry_lens[e0 + e]);
+        n_matches_out[i] = lx::line_matches(row.data(), n, reinterpret_cast<lx::Match*>(matches_out) + (size_t)i * lx::MATCHES);
+        if (loglik_out) memcpy(loglik_out + out, row.data(), (size_t)n * sizeof(float));
+        out += n;
       }
       o += T;
     }

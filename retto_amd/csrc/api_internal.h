@@ -24,6 +24,14 @@ bool charset_args_ok(const float* z5, const float* W, int N, const int32_t* idx,
                      const int32_t* n_tokens_out, const float* scores_out, const rt_candidate* cands_out, const int32_t* cols_out,
                      long long* rows_out);
 
+// what both rt_debug_ctc_lexicon forms require of their arguments: the first requirement that fails, in words, or the empty
+// string; *rows_out = the lines' time steps, *table_out = the floats of the loglik table (one per entry of the lexicon of every
+// line that has one)
+std::string lexicon_args_error(const float* z5, const float* W, int N, const int32_t* tokens_per_line, int n_lines,
+                               const int32_t* line_lex, const int32_t* entry_ids, const int32_t* entry_lens,
+                               const int32_t* lex_first_entry, int n_lex, const rt_lexicon_match* matches_out,
+                               const int32_t* n_matches_out, long long* rows_out, long long* table_out);
+
 // A call that fails after work was enqueued must not leave kernels or H2D copies in flight: the next
 // begin_call() rewinds the pinned staging and the arenas they read.  Errors of the drain itself are dropped
 // (the first failure is the one reported).

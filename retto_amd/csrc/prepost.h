@@ -7,6 +7,7 @@
 #include "word_boxes.h"
 #include "ctc_candidates.h"
 #include "ctc_charset.h"
+#include "ctc_lexicon.h"
 
 namespace rt {
 namespace pp {
@@ -103,6 +104,19 @@ void ctc_topk(hipStream_t st, const float* logits, int ld, int classes, const in
 // prob[rows[i]].  masks: [n_sets][words = cs::mask_words(classes)] on the device.
 void ctc_charset_argmax(hipStream_t st, const float* logits, int ld, int classes, const int* rows, const int* row_set,
                         const uint32_t* masks, int words, int m, int* idx, float* prob);
+// Rec lexicons (ctc_lexicon.h): one wave64 per row i < m of logits [m][ld]: lse[i] = log-sum-exp over the columns < classes
+void ctc_row_lse(hipStream_t st, const float* logits, int ld, int classes, int m, float* lse);
+// The CTC forward log-likelihood of every entry of the lexicon of each of lines[0..n_lines) (one chunk: their rows are resident
+// in logits [.][ld] and lse, row r of the call's compact row list at r - chunk_row0) -> loglik[line.out + entry], -inf where the
+// entry is infeasible for the line's T.  max_waves: the largest lx::waves_of over the lexicons of these lines.  lex / entries /
+// order / ids: lx::Tables on the device.
+void ctc_lexicon_forward(hipStream_t st, const float* logits, int ld, const float* lse, const lx::Line* lines, int n_lines,
+                         int chunk_row0, int max_waves, const lx::Lex* lex, const lx::Entry* entries, const int* order,
+                         const int* ids, float* loglik);
+// one wave64 per line over its loglik row: up to lx::MATCHES matches -> matches[line.slot * lx::MATCHES ...], their number ->
+// counts[line.slot] (slots of a line's row past its count are not written)
+void ctc_lexicon_topk(hipStream_t st, const lx::Line* lines, int n_lines, const lx::Lex* lex, const float* loglik,
+                      lx::Match* matches, int* counts);
 
 // sum of a float buffer into per-block doubles (partials has ceil(n/65536) entries)
 int sum_blocks(long long n);

@@ -519,6 +519,152 @@ void ctc_charset_argmax(hipStream_t st, const float* logits, int ld, int classes
   RT_LAUNCH(k_ctc_charset_argmax, dim3(m), dim3(64), 0, st, logits, ld, classes, rows, row_set, masks, words, m, idx, prob);
 }
 
+// Rec lexicons (ctc_lexicon.h).  One wave64 per row i < m of logits [m][ld]: lse[i] over the columns < classes, in the two-pass
+// shape of k_ctc_charset_argmax (float4 streaming, pad columns skipped; the second pass comes back from L2).
+__global__ __launch_bounds__(64) void k_ctc_row_lse(const float* __restrict__ logits, int ld, int classes, int m,
+                                                    float* __restrict__ lse) {
+  const int i = blockIdx.x, lane = threadIdx.x;
+  if (i >= m) return;
+  const float4* x = reinterpret_cast<const float4*>(logits + (long long)i * ld);
+  const int nv = (classes + 3) / 4;
+  float mx = -INFINITY;
+  for (int v = lane; v < nv; v += 64) {
+    const float4 q = x[v];
+    const float e[4] = {q.x, q.y, q.z, q.w};
+#pragma unroll
+    for (int u = 0; u < 4; u++)
+      if (4 * v + u < classes) mx = fmaxf(mx, e[u]);
+  }
+  for (int o = 32; o >= 1; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o));
+  float sum = 0.0f;
+  for (int v = lane; v < nv; v += 64) {
+    const float4 q = x[v];
+    const float e[4] = {q.x, q.y, q.z, q.w};
+#pragma unroll
+    for (int u = 0; u < 4; u++)
+      if (4 * v + u < classes) sum = sum + expf(e[u] - mx);
+  }
+  for (int o = 32; o >= 1; o >>= 1) sum = sum + __shfl_xor(sum, o);   // (a butterfly: every lane adds in the same order)
+  if (lane == 0) lse[i] = lx::lse_of(mx, sum);
+}
+void ctc_row_lse(hipStream_t st, const float* logits, int ld, int classes, int m, float* lse) {
+  if (m <= 0) return;
+  RT_LAUNCH(k_ctc_row_lse, dim3(m), dim3(64), 0, st, logits, ld, classes, m, lse);
+}
+
+// The CTC forward recursion of a lexicon's entries over the lines of one chunk.  Workgroup (w, j) is one wave64: wave w of the
+// lexicon of chunk line j.  A lexicon's waves go through its three buckets in turn (lx::waves_of): 4 entries of 16 lanes, 2 of
+// 32, 1 of 64, each entry's states on the lanes of its group; waves past the lexicon's count (the grid is sized for the largest
+// lexicon of the call) leave at once.  alpha lives in one register per lane; the neighbours' values come from __shfl_up within
+// the group's width.  The T steps are a serial chain through expf / logf; the gathered logit l[t][cls(s)] and lse[t] do not
+// depend on alpha, so they are loaded AHEAD steps early into a register ring (static indices: the loop is unrolled by AHEAD) and
+// their latency hides behind the chain.  Every lane of the wave runs the same T steps -- a group without an entry (the partial
+// last wave of a bucket) and the lanes past an entry's S states carry -inf along and read column 0 of the line's own rows -- so
+// no shuffle is ever divergent; only lane 0 of a group that holds an entry writes, one float: loglik[line.out + entry].
+__global__ __launch_bounds__(64) void k_ctc_lexicon_forward(const float* __restrict__ logits, int ld, const float* __restrict__ lse,
+                                                            const lx::Line* __restrict__ lines, int chunk_row0,
+                                                            const lx::Lex* __restrict__ lex, const lx::Entry* __restrict__ entries,
+                                                            const int* __restrict__ order, const int* __restrict__ ids,
+                                                            float* __restrict__ loglik) {
+  constexpr int AHEAD = 4;
+  const int lane = threadIdx.x;
+  const lx::Line ln = lines[blockIdx.y];
+  const lx::Lex X = lex[ln.lex];
+  const int w16 = (X.n16 + 3) / 4, w32 = (X.n32 + 1) / 2, n64 = X.n - X.n16 - X.n32;
+  int w = blockIdx.x, width, k, bucket_n, bucket_first;
+  if (w < w16) { width = 16; k = 4 * w + (lane >> 4); bucket_n = X.n16; bucket_first = 0; }
+  else if ((w -= w16) < w32) { width = 32; k = 2 * w + (lane >> 5); bucket_n = X.n32; bucket_first = X.n16; }
+  else if ((w -= w32) < n64) { width = 64; k = w; bucket_n = n64; bucket_first = X.n16 + X.n32; }
+  else return;
+  const bool live = k < bucket_n;
+  const int e = live ? order[X.first + bucket_first + k] : 0;   // (lexicon-local entry index)
+  const lx::Entry E = live ? entries[X.first + e] : lx::Entry{0, 0, 0};
+  const int s = lane & (width - 1), S = 2 * E.len + 1, T = ln.T;
+  const bool mine = live && s < S;
+  const int cls = mine ? lx::cls_of(ids + E.off, s) : 0;
+  const bool skip = mine && lx::skip_of(ids + E.off, s);
+  const float* col = logits + (long long)(ln.row0 - chunk_row0) * ld + cls;
+  const float* ls = lse + (ln.row0 - chunk_row0);
+  float lq[AHEAD], eq[AHEAD];
+#pragma unroll
+  for (int j = 0; j < AHEAD; j++) { lq[j] = j < T ? col[(long long)j * ld] : 0.0f; eq[j] = j < T ? ls[j] : 0.0f; }
+  float a = -INFINITY;
+  for (int t0 = 0; t0 < T; t0 += AHEAD) {
+#pragma unroll
+    for (int j = 0; j < AHEAD; j++) {
+      const int t = t0 + j;
+      if (t < T) {   // (wave-uniform)
+        const float lp = lq[j] - eq[j];
+        if (t + AHEAD < T) { lq[j] = col[(long long)(t + AHEAD) * ld]; eq[j] = ls[t + AHEAD]; }
+        const float u1 = __shfl_up(a, 1, width), u2 = __shfl_up(a, 2, width);
+        const float a1 = s >= 1 ? u1 : -INFINITY, a2 = s >= 2 ? u2 : -INFINITY;
+        const float nx = t == 0 ? (s < 2 ? lp : -INFINITY) : lx::step(a, a1, a2, skip, lp);
+        a = mine ? nx : -INFINITY;
+      }
+    }
+  }
+  const float f1 = __shfl(a, S - 1, width), f2 = __shfl(a, S >= 2 ? S - 2 : 0, width);
+  if (live && s == 0) loglik[ln.out + e] = T >= E.need ? lx::lae(f1, f2, -INFINITY) : -INFINITY;
+}
+void ctc_lexicon_forward(hipStream_t st, const float* logits, int ld, const float* lse, const lx::Line* lines, int n_lines,
+                         int chunk_row0, int max_waves, const lx::Lex* lex, const lx::Entry* entries, const int* order,
+                         const int* ids, float* loglik) {
+  if (n_lines <= 0 || max_waves <= 0) return;
+  RT_LAUNCH(k_ctc_lexicon_forward, dim3(max_waves, n_lines), dim3(64), 0, st, logits, ld, lse, lines, chunk_row0, lex, entries,
+            order, ids, loglik);
+}
+
+// One wave64 per lexicon line over its loglik row: each lane keeps a best-first list of MATCHES feasible entries (an infeasible
+// entry, -inf, is skipped, never ranked) and the maximum; pass 2 sums exp(loglik - max) over the feasible entries, by the
+// butterfly of k_ctc_topk; then MATCHES rounds of a wave arg-max over the list heads (ties to the lower entry index), lane r
+// keeping round r's winner and writing match r.  Lane 0 writes the count.
+__global__ __launch_bounds__(64) void k_ctc_lexicon_topk(const lx::Line* __restrict__ lines, const lx::Lex* __restrict__ lex,
+                                                         const float* __restrict__ loglik, lx::Match* __restrict__ matches,
+                                                         int* __restrict__ counts) {
+  constexpr int N = lx::MATCHES;
+  const int lane = threadIdx.x;
+  const lx::Line ln = lines[blockIdx.x];
+  const int n = lex[ln.lex].n;
+  const float* x = loglik + ln.out;
+  float L[N]; int I[N];
+#pragma unroll
+  for (int j = 0; j < N; j++) { L[j] = -INFINITY; I[j] = cc::EMPTY_ID; }
+  float mx = -INFINITY;
+  for (int e = lane; e < n; e += 64) {
+    const float v = x[e];
+    if (v > -INFINITY) { mx = fmaxf(mx, v); cc::list_insert(L, I, v, e); }
+  }
+  for (int o = 32; o >= 1; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o));
+  float sum = 0.0f;
+  for (int e = lane; e < n; e += 64) {
+    const float v = x[e];
+    if (v > -INFINITY) sum = sum + expf(v - mx);
+  }
+  for (int o = 32; o >= 1; o >>= 1) sum = sum + __shfl_xor(sum, o);   // (a butterfly: every lane adds in the same order)
+  float ol = 0.0f; int oi = cc::EMPTY_ID, cnt = 0;
+  for (int r = 0; r < N; r++) {
+    float wl = L[0]; int wi = I[0];
+    for (int o = 32; o >= 1; o >>= 1) {
+      const float l2 = __shfl_xor(wl, o); const int i2 = __shfl_xor(wi, o);
+      if (cc::better(l2, i2, wl, wi)) { wl = l2; wi = i2; }
+    }
+    if (lane == r) { ol = wl; oi = wi; }
+    if (wi != cc::EMPTY_ID) cnt++;
+    if (wi != cc::EMPTY_ID && I[0] == wi) {
+#pragma unroll
+      for (int j = 0; j + 1 < N; j++) { L[j] = L[j + 1]; I[j] = I[j + 1]; }
+      L[N - 1] = -INFINITY; I[N - 1] = cc::EMPTY_ID;
+    }
+  }
+  if (lane < N && oi != cc::EMPTY_ID) matches[(long long)ln.slot * N + lane] = lx::Match{oi, ol, lx::posterior_of(ol, mx, sum)};
+  if (lane == 0) counts[ln.slot] = cnt;
+}
+void ctc_lexicon_topk(hipStream_t st, const lx::Line* lines, int n_lines, const lx::Lex* lex, const float* loglik,
+                      lx::Match* matches, int* counts) {
+  if (n_lines <= 0) return;
+  RT_LAUNCH(k_ctc_lexicon_topk, dim3(n_lines), dim3(64), 0, st, lines, lex, loglik, matches, counts);
+}
+
 // ===========================================================================
 // (round 5: 8192 values per block, 16-byte loads -- was 65536 per block, scalar: one 960 x 960 map ran on 15 workgroups for 77 us,
 //  6 % of the C2 call)

@@ -11,6 +11,7 @@
 #include <numeric>
 #include <sstream>
 #include <thread>
+#include <unordered_map>
 
 #include <chrono>
 
@@ -121,6 +122,74 @@ std::vector<uint32_t> compile_charset(const std::vector<std::string>& dict, cons
   }
   return mask;
 }
+void compile_lexicon(const std::vector<std::string>& dict, const char* utf8, size_t len, const int32_t* ids,
+                     const int32_t* entry_lens, int n_id_entries, std::vector<int32_t>& ids_out, std::vector<int32_t>& lens_out) {
+  const int classes = (int)dict.size();
+  ids_out.clear(); lens_out.clear();
+  // every class whose whole entry is one code point, under its bytes: the lowest id wins (class 0 is the blank, whatever its
+  // placeholder text)
+  std::unordered_map<std::string, int> one;
+  for (int c = classes - 1; c >= 1; c--) {
+    const std::string& d = dict[(size_t)c];
+    uint32_t cp;
+    if (!d.empty() && (size_t)utf8_decode_strict((const unsigned char*)d.data(), d.size(), &cp) == d.size()) one[d] = c;
+  }
+  auto entry_done = [&](int n) {
+    if (n > lx::MAX_LEN)
+      throw RtError(RT_ERR_INVALID, "lexicon: entry " + std::to_string(lens_out.size()) + " has " + std::to_string(n) +
+                                        " tokens, more than RT_LEXICON_MAX_LEN (" + std::to_string(lx::MAX_LEN) + ")");
+    if ((int)lens_out.size() >= lx::MAX_ENTRIES)
+      throw RtError(RT_ERR_CAPACITY, "lexicon: more than RT_LEXICON_MAX_ENTRIES (" + std::to_string(lx::MAX_ENTRIES) + ") entries");
+    lens_out.push_back(n);
+  };
+  const unsigned char* p = (const unsigned char*)utf8;
+  for (size_t pos = 0; pos < len;) {
+    size_t e = pos;
+    while (e < len && p[e] != '\n') e++;
+    size_t le = e;
+    if (e < len && le > pos && p[le - 1] == '\r') le--;
+    size_t first = std::string::npos, last_end = 0;   // (trimmed as a dictionary line is)
+    for (size_t i = pos; i < le;) {
+      uint32_t cp;
+      const int k = utf8_decode_strict(p + i, le - i, &cp);
+      if (k == 0) throw RtError(RT_ERR_UTF8, "lexicon: the text is not valid UTF-8 (byte offset " + std::to_string(i) + ")");
+      if (!is_rust_whitespace(cp)) { if (first == std::string::npos) first = i; last_end = i + (size_t)k; }
+      i += (size_t)k;
+    }
+    if (first != std::string::npos) {
+      int n = 0;
+      for (size_t i = first; i < last_end;) {
+        uint32_t cp;
+        const int k = utf8_decode_strict(p + i, last_end - i, &cp);
+        const auto it = one.find(std::string((const char*)p + i, (size_t)k));
+        if (it == one.end()) {
+          char b[96];
+          snprintf(b, sizeof b, "lexicon: U+%04X in entry %zu matches no dictionary entry", (unsigned)cp, lens_out.size());
+          throw RtError(RT_ERR_INVALID, b);
+        }
+        ids_out.push_back(it->second); n++;
+        i += (size_t)k;
+      }
+      entry_done(n);
+    }
+    pos = e + 1;
+  }
+  size_t o = 0;
+  for (int j = 0; j < n_id_entries; j++) {
+    const int n = entry_lens[j];
+    if (n <= 0) throw RtError(RT_ERR_INVALID, "lexicon: entry " + std::to_string(lens_out.size()) + " is empty");
+    for (int i = 0; i < n && i < lx::MAX_LEN; i++) {
+      const int c = ids[o + (size_t)i];
+      if (c < 1 || c >= classes)
+        throw RtError(RT_ERR_INVALID, "lexicon: class id " + std::to_string(c) + " in entry " + std::to_string(lens_out.size()) +
+                                          " is outside [1, " + std::to_string(classes) + ")");
+      ids_out.push_back(c);
+    }
+    entry_done(n);
+    o += (size_t)n;
+  }
+  if (lens_out.empty()) throw RtError(RT_ERR_INVALID, "lexicon: no entry");
+}
 }  // namespace rt
 
 // ---------------------------------------------------------------------------
@@ -158,6 +227,7 @@ rt_session* rt_session_create(const rt_config* cfg) {
   s->model_info = std::string(s->det->arch()) + "/" + s->det->dtype() + " " + s->cls->dtype() + " " + s->rec->arch() + "/" + s->rec->dtype();
   s->dict = rt::load_dictionary(dict);
   s->charsets = std::make_shared<rt_charsets>();
+  s->lexicons = std::make_shared<rt_lexicons>();
   if ((int)s->dict.size() != s->rec->classes())
     throw RtError(RT_ERR_SHAPE, "dictionary has " + std::to_string(s->dict.size()) + " entries but the rec head has " +
                                     std::to_string(s->rec->classes()) + " classes");
@@ -175,7 +245,7 @@ rt_session* rt_session_create(const rt_config* cfg) {
     std::unique_ptr<rt_session> h(new rt_session());
     h->cfg = s->cfg; h->device = s->device;
     h->det = s->det; h->cls = s->cls; h->rec = s->rec; h->dict = s->dict; h->model_info = s->model_info;
-    h->d_word_raw = s->d_word_raw; h->charsets = s->charsets;
+    h->d_word_raw = s->d_word_raw; h->charsets = s->charsets; h->lexicons = s->lexicons;
     RT_HIP_CHECK(hipStreamCreateWithFlags(&h->st_full, hipStreamNonBlocking));
     h->st = h->st_full;
     RT_HIP_CHECK(hipMalloc((void**)&h->d_flags, 64));
@@ -404,6 +474,84 @@ int rt_session::charset_create(const char* utf8, size_t len, const int32_t* ids,
   for (int c = 0; c < (int)dict.size(); c++) if (cs::allowed(mask.data(), c)) members.push_back(c);
   C.ids.push_back(std::move(members));
   return (int)C.ids.size();
+}
+
+void rt_session::ctc_lexicon(const SvtrCore& core, const float* z5, const lx::Line* h_lines, const lx::Line* d_lines, int n_lines,
+                             const int* d_rows, int n_rows, int max_waves, const lx::Lex* d_lex, const lx::Entry* d_entries,
+                             const int* d_order, const int* d_ids, int chunk_rows, float* loglik, lx::Match* matches, int* counts) {
+  if (n_lines <= 0) return;
+  const int chunk = chunk_rows > 0 ? chunk_rows : cc::CAND_CHUNK, ld = round_up(core.classes, 4);
+  // chunks of whole lines: [i0, i1) takes lines while their rows fit the chunk, and always its first line
+  auto chunk_end = [&](int i0) {
+    int i1 = i0 + 1, rows = h_lines[i0].T;
+    while (i1 < n_lines && i1 - i0 < lx::LINES_PER_CHUNK && rows + h_lines[i1].T <= chunk) rows += h_lines[i1++].T;
+    return i1;
+  };
+  int cap = 1;
+  for (int i0 = 0; i0 < n_lines;) {
+    const int i1 = chunk_end(i0);
+    cap = std::max(cap, h_lines[i1 - 1].row0 + h_lines[i1 - 1].T - h_lines[i0].row0);
+    i0 = i1;
+  }
+  const size_t zc_n = ((size_t)cap + 256) * core.D;   // (zero rows past the chunk: a GEMM tile's loads stay inside the allocation)
+  float* zc = scratch.alloc<float>(zc_n);
+  float* logits = scratch.alloc<float>((size_t)cap * ld);
+  float* lse = scratch.alloc<float>((size_t)cap);
+  RT_HIP_CHECK(hipMemsetAsync(zc, 0, zc_n * sizeof(float), st));
+  RunCtx c = ctx(&scratch);
+  for (int i0 = 0; i0 < n_lines;) {   // (stream order lets the chunks share zc, logits and lse)
+    const int i1 = chunk_end(i0), r0 = h_lines[i0].row0, m = h_lines[i1 - 1].row0 + h_lines[i1 - 1].T - r0;
+    if (r0 + m > n_rows) throw RtError(RT_ERR_SHAPE, "ctc_lexicon: the lines' rows exceed the row list");
+    if (m > 0) {
+      { ProfScope ps(&prof, st, "ctc_gather_rows");
+        pp::ctc_gather_rows(st, z5, core.D, d_rows + r0, m, zc); }
+      core.logits_rows(c, zc, m, logits);
+      { ProfScope ps(&prof, st, "ctc_row_lse");
+        pp::ctc_row_lse(st, logits, ld, core.classes, m, lse); }
+    }
+    { ProfScope ps(&prof, st, "ctc_lexicon_forward");
+      pp::ctc_lexicon_forward(st, logits, ld, lse, d_lines + i0, i1 - i0, r0, max_waves, d_lex, d_entries, d_order, d_ids, loglik); }
+    i0 = i1;
+  }
+  ProfScope ps(&prof, st, "ctc_lexicon_topk");
+  pp::ctc_lexicon_topk(st, d_lines, n_lines, d_lex, loglik, matches, counts);
+}
+
+int rt_session::lexicon_create(const char* utf8, size_t len, const int32_t* ids, const int32_t* entry_lens, int n_id_entries) {
+  rt_lexicons& X = *lexicons;
+  if ((int)X.host.size() >= lx::MAX_LEXICONS)
+    throw RtError(RT_ERR_CAPACITY, "rt_lexicon_create: the session holds RT_MAX_LEXICONS (" + std::to_string(lx::MAX_LEXICONS) + ") lexicons already");
+  std::unique_ptr<rt_lexicons::Host> h(new rt_lexicons::Host());
+  compile_lexicon(dict, utf8, len, ids, entry_lens, n_id_entries, h->ids, h->lens);
+  int o = 0;
+  for (int n : h->lens) {
+    h->off.push_back(o);
+    std::string t;
+    for (int i = 0; i < n; i++) t += dict[(size_t)h->ids[(size_t)(o + i)]];
+    h->text.push_back(std::move(t));
+    o += n;
+  }
+  lx::Tables tb = X.tb;
+  tb.add(h->ids.data(), h->lens.data(), (int)h->lens.size());
+  // the device tables are rebuilt whole (blocking copies; no lane has work queued: this is a guarded call and every pipeline
+  // call ends with its streams drained)
+  RT_HIP_CHECK(hipSetDevice(device));
+  int32_t* d_ids = nullptr; lx::Entry* d_entries = nullptr; int32_t* d_order = nullptr; lx::Lex* d_lex = nullptr;
+  auto up = [&](auto** d, const auto& v) {
+    RT_HIP_CHECK(hipMalloc((void**)d, v.size() * sizeof(v[0])));
+    RT_HIP_CHECK(hipMemcpy(*d, v.data(), v.size() * sizeof(v[0]), hipMemcpyHostToDevice));
+  };
+  try {
+    up(&d_ids, tb.ids); up(&d_entries, tb.entries); up(&d_order, tb.order); up(&d_lex, tb.lex);
+  } catch (...) {
+    if (d_ids) (void)hipFree(d_ids); if (d_entries) (void)hipFree(d_entries); if (d_order) (void)hipFree(d_order); if (d_lex) (void)hipFree(d_lex);
+    throw;
+  }
+  X.free_device();
+  X.d_ids = d_ids; X.d_entries = d_entries; X.d_order = d_order; X.d_lex = d_lex;
+  X.tb = std::move(tb);
+  X.host.push_back(std::move(h));
+  return (int)X.host.size();
 }
 
 // ---------------------------------------------------------------------------
@@ -693,6 +841,10 @@ struct Pipeline {
   int* d_wcount = nullptr; wb::Word* d_words = nullptr; int* h_wcount = nullptr; wb::Word* h_words = nullptr;   // rec_return_word_box
   int* d_ccol = nullptr; cc::Cand* d_cands = nullptr; int* h_ccol = nullptr; cc::Cand* h_cands = nullptr;       // rec_return_candidates
   std::vector<int> line_set;                // rec charsets: per line its set (0: none); empty when no line of the call has one
+  // rec lexicons: per line its lexicon (0: none), empty when no line of the call has one; then per line lx::MATCHES match slots
+  // and the number of matches (written for the lines that carry a lexicon only)
+  std::vector<int> line_lex;
+  lx::Match* d_lexm = nullptr; int* d_lexn = nullptr; lx::Match* h_lexm = nullptr; int* h_lexn = nullptr;
 };
 
 // Launch groups: items [g0, end) where the group always takes its first item; with max_items > 0 it takes up to max_items items,
@@ -952,6 +1104,7 @@ void rec_groups(rt_session& s, Pipeline& P) {
   if (s.cfg.rec_return_word_box) {
     P.d_wcount = s.arena.alloc<int>(P.NLp); P.d_words = s.arena.alloc<wb::Word>(ntok); d_wcol = s.arena.alloc<int>(ntok);
   }
+  if (!P.line_lex.empty()) { P.d_lexm = s.arena.alloc<lx::Match>((size_t)P.NLp * lx::MATCHES); P.d_lexn = s.arena.alloc<int>(P.NLp); }
   static const long long REC_GROUP_PX = getenv("RT_REC_GROUP_PX") ? atoll(getenv("RT_REC_GROUP_PX")) : (long long)24000000;  // measured sweet spot (profiles/README.md)
   for (int l0 = 0; l0 < P.NL;) {
     const int l1 = group_end(l0, P.NL, 0, REC_GROUP_PX, [&](int l) { return (long long)rh * P.line_W[l]; });
@@ -993,9 +1146,13 @@ void rec_groups(rt_session& s, Pipeline& P) {
         RT_HIP_CHECK(hipMemcpyAsync(d_crows, h_crows, (size_t)n_crows * sizeof(int), hipMemcpyHostToDevice, s.st));
       }
     }
-    const float* z5 = nullptr;   // the head's input, for the candidates' and the charsets' logits
+    int n_lrows = -1;   // rec lexicons: the rows of the group's lexicon lines (-1: the group has no such line)
+    if (!P.line_lex.empty())
+      for (int li = l0; li < l1; li++)
+        if (P.line_lex[li] > 0) n_lrows = std::max(n_lrows, 0) + (int)(P.tok_off[li + 1] - P.tok_off[li]);
+    const float* z5 = nullptr;   // the head's input, for the candidates', the charsets' and the lexicons' logits
     { ProfOuter po(&s.prof, s.st, "net/rec");
-      s.rec->run(c, x, L0, Lt, d_idx + t0, d_prob + t0, cand_k > 1 || n_crows > 0 ? &z5 : nullptr); }  // fused CTC head: logits never reach HBM
+      s.rec->run(c, x, L0, Lt, d_idx + t0, d_prob + t0, cand_k > 1 || n_crows > 0 || n_lrows >= 0 ? &z5 : nullptr); }  // fused CTC head: logits never reach HBM
     if (Lt.total != P.tok_off[l1] - t0) throw RtError(RT_ERR_SHAPE, "token count mismatch");
     if (n_crows > 0)   // the restricted rows' (idx, prob) are replaced before anything reads them
       s.ctc_charset(s.rec->core(), z5, d_crows, n_crows, d_row_set, s.charsets->d_masks, s.charsets->words, 0, d_idx + t0, d_prob + t0);
@@ -1020,6 +1177,31 @@ void rec_groups(rt_session& s, Pipeline& P) {
       pp::word_boxes(s.st, d_idx + t0, P.d_tok + t0, P.d_meta.ntok + l0, P.d_meta.label + l0, P.d_meta.cscore + l0, s.cfg.cls_thresh,
                      s.d_word_raw, dw, ln, d_wcol + t0, P.d_wcount + l0, P.d_words + t0);
     }
+    if (n_lrows >= 0) {   // rec lexicons (ctc_lexicon.h): the group's lexicon lines, their rows and their loglik rows
+      const rt_lexicons& X = *s.lexicons;
+      int nl = 0;
+      for (int li = l0; li < l1; li++) nl += P.line_lex[li] > 0 ? 1 : 0;
+      lx::Line* h_lines = s.pinned.alloc<lx::Line>(nl); int* h_rows = s.pinned.alloc<int>(std::max(n_lrows, 1));
+      int n = 0, r = 0, max_waves = 0; long long out = 0;
+      for (int li = l0; li < l1; li++) {
+        if (P.line_lex[li] <= 0) continue;
+        const int T = (int)(P.tok_off[li + 1] - P.tok_off[li]);
+        const lx::Lex& x = X.tb.lex[(size_t)P.line_lex[li] - 1];
+        h_lines[n++] = lx::Line{r, T, P.line_lex[li] - 1, li, out};
+        for (int t = 0; t < T; t++) h_rows[r++] = (int)(P.tok_off[li] - t0) + t;
+        out += x.n; max_waves = std::max(max_waves, lx::waves_of(x));
+      }
+      lx::Line* d_lines = s.scratch.alloc<lx::Line>(nl); int* d_rows = s.scratch.alloc<int>(std::max(n_lrows, 1));
+      if (out > lx::MAX_GROUP_TABLE)
+        throw RtError(RT_ERR_CAPACITY, "rec lexicons: " + std::to_string(nl) + " lines of one rec group carry lexicons of " + std::to_string(out) +
+                                           " entries in all, more than the " + std::to_string(lx::MAX_GROUP_TABLE) +
+                                           " likelihoods a group's table holds: use smaller lexicons or fewer lexicon lines per call");
+      float* loglik = s.scratch.alloc<float>((size_t)out);
+      RT_HIP_CHECK(hipMemcpyAsync(d_lines, h_lines, (size_t)nl * sizeof(lx::Line), hipMemcpyHostToDevice, s.st));
+      if (n_lrows > 0) RT_HIP_CHECK(hipMemcpyAsync(d_rows, h_rows, (size_t)n_lrows * sizeof(int), hipMemcpyHostToDevice, s.st));
+      s.ctc_lexicon(s.rec->core(), z5, h_lines, d_lines, nl, d_rows, n_lrows, max_waves, X.d_lex, X.d_entries, X.d_order, X.d_ids, 0,
+                    loglik, P.d_lexm, P.d_lexn);
+    }
     if (cand_k > 0)   // (before the next group rewinds the scratch arena z5 lives in)
       s.ctc_candidates(s.rec->core(), z5, d_idx + t0, d_prob + t0, Lt.d, P.d_meta.ntok + l0, ln, Lt.total, cand_k, 0,
                        P.d_ccol + t0, P.d_cands + t0 * cand_k, d_row_set, d_row_set ? s.charsets->d_masks : nullptr, s.charsets->words);
@@ -1043,6 +1225,11 @@ void line_round_trip(rt_session& s, Pipeline& P) {
     P.h_words = s.pinned.alloc<wb::Word>((size_t)std::max<long long>(total_tok, 1));
     RT_HIP_CHECK(hipMemcpyAsync(P.h_wcount, P.d_wcount, (size_t)P.NL * sizeof(int), hipMemcpyDeviceToHost, s.st));
     if (total_tok > 0) RT_HIP_CHECK(hipMemcpyAsync(P.h_words, P.d_words, (size_t)total_tok * sizeof(wb::Word), hipMemcpyDeviceToHost, s.st));
+  }
+  if (!P.line_lex.empty()) {   // (the lexicon matches too)
+    P.h_lexm = s.pinned.alloc<lx::Match>((size_t)P.NLp * lx::MATCHES); P.h_lexn = s.pinned.alloc<int>(P.NLp);
+    RT_HIP_CHECK(hipMemcpyAsync(P.h_lexm, P.d_lexm, (size_t)P.NLp * lx::MATCHES * sizeof(lx::Match), hipMemcpyDeviceToHost, s.st));
+    RT_HIP_CHECK(hipMemcpyAsync(P.h_lexn, P.d_lexn, (size_t)P.NLp * sizeof(int), hipMemcpyDeviceToHost, s.st));
   }
   s.sync(); s.check_flags();
 }
@@ -1076,6 +1263,16 @@ void results(const rt_session& s, const Pipeline& P, rt_results& res) {
         memcpy(&R.cands[(size_t)R.cand_off[k] * K], P.h_cands + o * K, n * K * sizeof(cc::Cand));
       }
     }
+    if (!P.line_lex.empty()) {   // rec lexicons: a line without one has 0 matches (its device slots were never written)
+      R.lex_id.assign((size_t)nb, 0); R.lex_n.assign((size_t)nb, 0); R.lex_matches.assign((size_t)nb * lx::MATCHES, lx::Match{0, 0.0f, 0.0f});
+      for (int k = 0; k < nb; k++) {
+        const int li = p.first_line + k;
+        if (P.line_lex[li] <= 0) continue;
+        R.lex_id[k] = P.line_lex[li];
+        R.lex_n[k] = std::min(std::max(P.h_lexn[li], 0), lx::MATCHES);
+        for (int j = 0; j < R.lex_n[k]; j++) R.lex_matches[(size_t)k * lx::MATCHES + j] = P.h_lexm[(size_t)li * lx::MATCHES + j];
+      }
+    }
     if (s.cfg.rec_return_word_box) {   // word quads to original-image coordinates, word texts from the dictionary
       R.words.resize(nb); R.word_text.resize(nb);
       for (int k = 0; k < nb; k++) {
@@ -1099,7 +1296,8 @@ void results(const rt_session& s, const Pipeline& P, rt_results& res) {
 std::string rt_format_f32_impl(float v) { return fnum(v); }
 
 rt_results* rt_session::run_pages(const uint8_t* const* rgb, const int* hs, const int* ws, int n_pages, int mem,
-                                  const float* const* det_map_override, const Regions* regions, int rec_charset_default) {
+                                  const float* const* det_map_override, const Regions* regions, int rec_charset_default,
+                                  int rec_lexicon_default) {
   if (g_trace) fprintf(stderr, "[rt host] %-28s %8.3f ms\n", "between calls", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - last_exit).count());
   HostTick tick0;
   // a one-page call is the reference's real mode (retto-cli/src/main.rs:80-86): it polls through its waits; a multi-page batch
@@ -1140,6 +1338,21 @@ rt_results* rt_session::run_pages(const uint8_t* const* rgb, const int* hs, cons
   }
   for (int v : P.line_set)
     if (v < 0 || v > (int)charsets->ids.size()) throw RtError(RT_ERR_INVALID, "unknown rec charset id " + std::to_string(v));
+  // rec lexicons: the same, per line
+  if (regions && regions->lexicons) {
+    bool any = false;
+    for (int i = 0; i < n_pages; i++)
+      for (int k = 0; k < P.pg[i].n_boxes && regions->lexicons[i]; k++) any |= regions->lexicons[i][k] > 0;
+    if (any) {
+      P.line_lex.assign((size_t)P.NL, 0);
+      for (int i = 0; i < n_pages; i++)
+        for (int k = 0; k < P.pg[i].n_boxes && regions->lexicons[i]; k++) P.line_lex[(size_t)P.pg[i].first_line + k] = regions->lexicons[i][k];
+    }
+  } else if (rec_lexicon_default > 0 && P.NL > 0) {
+    P.line_lex.assign((size_t)P.NL, rec_lexicon_default);
+  }
+  for (int v : P.line_lex)
+    if (v < 0 || v > (int)lexicons->host.size()) throw RtError(RT_ERR_INVALID, "unknown rec lexicon id " + std::to_string(v));
   crop_stage(*this, P);
   if (P.NL > 0) {
     tick.lap("crop plan + warp enqueue");
@@ -1386,7 +1599,9 @@ rt_ticket* rt_session::submit_batch(const uint8_t* const* rgb, const int* hs, co
   if (det_map_override) t->maps.assign(det_map_override, det_map_override + n_pages);
   if (regions) { t->quads.assign(regions->quads, regions->quads + n_pages); t->n_quads.assign(regions->n_quads, regions->n_quads + n_pages); }
   if (regions && regions->charsets) t->region_sets.assign(regions->charsets, regions->charsets + n_pages);
+  if (regions && regions->lexicons) t->region_lexicons.assign(regions->lexicons, regions->lexicons + n_pages);
   t->rec_charset = rec_charset;   // (the lanes run later: the default is the one of the submitting call)
+  t->rec_lexicon = rec_lexicon;
   t->parts.assign((size_t)nl, nullptr); t->errs.resize((size_t)nl); t->first.assign((size_t)nl + 1, 0);
   {
     // contiguous ranges of about equal work: det pixels after the session size limit (a2) plus a constant per page
@@ -1437,9 +1652,10 @@ rt_ticket* rt_session::submit_batch(const uint8_t* const* rgb, const int* hs, co
       try {
         if (!tp->ev_up.empty()) RT_HIP_CHECK(hipStreamWaitEvent(s->st, tp->ev_up[(size_t)l], 0));
         Regions rg{nullptr, nullptr};
-        if (!tp->quads.empty()) rg = Regions{tp->quads.data() + f0, tp->n_quads.data() + f0, tp->region_sets.empty() ? nullptr : tp->region_sets.data() + f0};
+        if (!tp->quads.empty()) rg = Regions{tp->quads.data() + f0, tp->n_quads.data() + f0, tp->region_sets.empty() ? nullptr : tp->region_sets.data() + f0,
+                                                  tp->region_lexicons.empty() ? nullptr : tp->region_lexicons.data() + f0};
         tp->parts[l] = s->run_pages(tp->rgb.data() + f0, tp->hs.data() + f0, tp->ws.data() + f0, f1 - f0, tp->mem_lane,
-                                    tp->maps.empty() ? nullptr : tp->maps.data() + f0, tp->quads.empty() ? nullptr : &rg, tp->rec_charset);
+                                    tp->maps.empty() ? nullptr : tp->maps.data() + f0, tp->quads.empty() ? nullptr : &rg, tp->rec_charset, tp->rec_lexicon);
       } catch (...) {
         tp->errs[l] = std::current_exception();
         s->failed = true;
@@ -1505,7 +1721,7 @@ rt_results* rt_session::run_batch(const uint8_t* const* rgb, const int* hs, cons
     } disarm{this};
     stage_cb = cb; stage_user = user; stage_mu = &cb_mu; page_base = 0;
     try {
-      return run_pages(rgb, hs, ws, n_pages, mem, det_map_override, nullptr, rec_charset);
+      return run_pages(rgb, hs, ws, n_pages, mem, det_map_override, nullptr, rec_charset, rec_lexicon);
     } catch (...) { failed = true; throw; }
   }
   return wait_batch(submit_batch(rgb, hs, ws, n_pages, mem, det_map_override, cb, user));
@@ -1514,12 +1730,15 @@ rt_results* rt_session::run_batch(const uint8_t* const* rgb, const int* hs, cons
 // rt_run_regions.  A quad is clamped to the page, then held to what the crop plan needs: a crop of at least 1 x 1 pixels and an
 // invertible homography -- checked here, for every page, before anything is queued.
 rt_results* rt_session::run_regions(const uint8_t* const* rgb, const int* hs, const int* ws, int n_pages, int mem,
-                                    const float* const* quads, const int* n_quads, const int* const* region_charsets) {
+                                    const float* const* quads, const int* n_quads, const int* const* region_charsets,
+                                    const int* const* region_lexicons) {
   std::vector<std::vector<float>> clamped((size_t)n_pages);
   std::vector<const float*> qp((size_t)n_pages, nullptr);
   // the regions' charsets with -1 resolved to the session default of this call (rec charsets, ctc_charset.h)
   std::vector<std::vector<int>> sets((size_t)n_pages);
   std::vector<const int*> sp((size_t)n_pages, nullptr);
+  std::vector<std::vector<int>> lexs((size_t)n_pages);   // (and their lexicons)
+  std::vector<const int*> lp((size_t)n_pages, nullptr);
   for (int i = 0; i < n_pages; i++) {
     const std::string where = "rt_run_regions: page " + std::to_string(i);
     if (hs[i] <= 0 || ws[i] <= 0 || rgb[i] == nullptr) throw RtError(RT_ERR_IMAGE, where + ": empty page");
@@ -1550,8 +1769,16 @@ rt_results* rt_session::run_regions(const uint8_t* const* rgb, const int* hs, co
       if (v >= 0) sets[(size_t)i][(size_t)k] = v;
     }
     sp[(size_t)i] = sets[(size_t)i].data();
+    lexs[(size_t)i].assign((size_t)n_quads[i], rec_lexicon);
+    for (int k = 0; k < n_quads[i] && region_lexicons && region_lexicons[i]; k++) {
+      const int v = region_lexicons[i][k];
+      if (v < -1 || v > (int)lexicons->host.size())
+        throw RtError(RT_ERR_INVALID, where + " region " + std::to_string(k) + ": unknown lexicon id " + std::to_string(v));
+      if (v >= 0) lexs[(size_t)i][(size_t)k] = v;
+    }
+    lp[(size_t)i] = lexs[(size_t)i].data();
   }
-  const Regions rg{qp.data(), n_quads, sp.data()};
+  const Regions rg{qp.data(), n_quads, sp.data(), lp.data()};
   const int nl = std::max(1, std::min<int>(std::min<int>((int)helpers.size() + 1, active_lanes), std::max(n_pages, 1)));
   if (nl <= 1) {   // one lane: on the caller's thread, as run_batch
     try {

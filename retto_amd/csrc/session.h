@@ -39,6 +39,10 @@ struct rt_results {
     std::vector<uint32_t> cand_off;   // [lines + 1]
     std::vector<int32_t> cand_cols;
     std::vector<rt::cc::Cand> cands;
+    // rec lexicons (ctc_lexicon.h): per line the lexicon it was scored against (0: none), its number of matches and
+    // [rt::lx::MATCHES] match slots.  Empty when no line of the call carried a lexicon
+    std::vector<int32_t> lex_id, lex_n;
+    std::vector<rt::lx::Match> lex_matches;
     std::string json[3];
   };
   std::vector<Page> pages;
@@ -75,6 +79,9 @@ struct rt_ticket {
   // rt_run_regions_charsets per page the regions' resolved ids (owned by the caller of submit_batch); empty: the default
   int rec_charset = 0;
   std::vector<const int*> region_sets;
+  // rec lexicons (ctc_lexicon.h): the same two for lexicons
+  int rec_lexicon = 0;
+  std::vector<const int*> region_lexicons;
   std::vector<int> first;
   std::vector<rt_results*> parts;
   std::vector<std::exception_ptr> errs;
@@ -113,6 +120,22 @@ struct rt_charsets {
   ~rt_charsets() { if (d_masks) (void)hipFree(d_masks); }
 };
 
+// The session's rec lexicons (ctc_lexicon.h), shared with the helper lanes.  Lexicon k (1-based, rt_lexicon_create's id) is
+// host[k - 1] on the host (stable addresses: rt_lexicon_entry / _entry_text hand them out) and lexicon k - 1 of `tb`, whose four
+// tables sit on the device as d_*.  Only changed while no ticket is in flight and every lane's stream is drained
+// (rt_lexicon_create is a guarded call): the tables are rebuilt and copied whole, with blocking copies.
+struct rt_lexicons {
+  struct Host { std::vector<int32_t> ids, lens, off; std::vector<std::string> text; };
+  std::vector<std::unique_ptr<Host>> host;
+  rt::lx::Tables tb;
+  int32_t* d_ids = nullptr; rt::lx::Entry* d_entries = nullptr; int32_t* d_order = nullptr; rt::lx::Lex* d_lex = nullptr;
+  void free_device() {
+    if (d_ids) (void)hipFree(d_ids); if (d_entries) (void)hipFree(d_entries); if (d_order) (void)hipFree(d_order); if (d_lex) (void)hipFree(d_lex);
+    d_ids = nullptr; d_entries = nullptr; d_order = nullptr; d_lex = nullptr;
+  }
+  ~rt_lexicons() { free_device(); }
+};
+
 // internal to the library (never accepted from a caller): pages already in HBM, det map overrides still host pointers
 #define RT_MEM_STAGED_MAPS_HOST 3
 
@@ -140,6 +163,8 @@ struct rt_session {
   std::vector<std::string> dict;  // RecCharacter (rec_processor.rs:29-46)
   std::shared_ptr<rt_charsets> charsets;   // rec charsets (shared with the helper lanes)
   int rec_charset = 0;            // rt_set_rec_charset: the default of every line of the pipeline calls that follow (0: none)
+  std::shared_ptr<rt_lexicons> lexicons;   // rec lexicons (shared with the helper lanes)
+  int rec_lexicon = 0;            // rt_set_rec_lexicon: likewise
   uint8_t* d_word_raw = nullptr;  // rec_return_word_box: wb::raw_class of every dictionary entry (device; owned by the main lane)
   std::string last_error;
   int* d_flags = nullptr;         // [0] thumbnail/resize error flag
@@ -191,6 +216,17 @@ struct rt_session {
                    const uint32_t* masks, int words, int chunk_rows, int* idx, float* prob);
   // rt_charset_create: compiles the set (rt::compile_charset), stores it and returns its id
   int charset_create(const char* utf8, size_t len, const int32_t* ids, int n_ids);
+  // Rec lexicons over the lexicon lines of one rec group (ctc_lexicon.h), after the net and before the scratch arena that z5
+  // lives in is rewound.  h_lines / d_lines [n_lines]: the lines in line order on the host and on the device (row0 = the sum of
+  // the earlier lines' T); d_rows [n_rows]: their time steps of the group, line after line.  In chunks of whole lines of about
+  // chunk_rows rows (0: cc::CAND_CHUNK; at least one line, so a line's T rows are resident together): row gather, the CTC FC,
+  // k_ctc_row_lse, k_ctc_lexicon_forward -> loglik; then one k_ctc_lexicon_topk over all lines -> matches / counts.  max_waves:
+  // the largest lx::waves_of over the lines' lexicons.  No host wait; the workspace comes from `scratch`.
+  void ctc_lexicon(const rt::SvtrCore& core, const float* z5, const rt::lx::Line* h_lines, const rt::lx::Line* d_lines, int n_lines,
+                   const int* d_rows, int n_rows, int max_waves, const rt::lx::Lex* d_lex, const rt::lx::Entry* d_entries,
+                   const int* d_order, const int* d_ids, int chunk_rows, float* loglik, rt::lx::Match* matches, int* counts);
+  // rt_lexicon_create: compiles the entries (rt::compile_lexicon), stores them and returns the lexicon's id
+  int lexicon_create(const char* utf8, size_t len, const int32_t* ids, const int32_t* entry_lens, int n_id_entries);
   // L2
   // persistent lane threads (index 0 = this session's own lane) and the number of submitted, not yet waited batches
   std::vector<std::unique_ptr<LaneWorker>> workers;
@@ -210,7 +246,8 @@ struct rt_session {
   void ensure_workers();
   // regions (rt_run_regions): quads[i] = n_quads[i] x 8 validated, clamped floats of page i, valid until the ticket is waited for
   // charsets (rt_run_regions_charsets): per page the regions' charset ids, already resolved (>= 0) and checked; null: the default
-  struct Regions { const float* const* quads; const int* n_quads; const int* const* charsets = nullptr; };
+  // lexicons (rt_run_regions_lexicons): the same for rec lexicons
+  struct Regions { const float* const* quads; const int* n_quads; const int* const* charsets = nullptr; const int* const* lexicons = nullptr; };
   rt_ticket* submit_batch(const uint8_t* const* rgb, const int* hs, const int* ws, int n_pages, int mem,
                           const float* const* det_map_override, rt_stage_callback cb = nullptr, void* user = nullptr,
                           std::vector<rt::EncodedPage>* enc = nullptr, const Regions* regions = nullptr);
@@ -221,12 +258,13 @@ struct rt_session {
                         const float* const* det_map_override, rt_stage_callback cb = nullptr, void* user = nullptr);
   rt_results* run_pages(const uint8_t* const* rgb, const int* hs, const int* ws, int n_pages, int mem,
                         const float* const* det_map_override, const Regions* regions = nullptr,
-                        int rec_charset_default = 0);  // one lane
+                        int rec_charset_default = 0, int rec_lexicon_default = 0);  // one lane
   // rt_run_regions: checks and clamps every quad (RT_ERR_INVALID naming page and region; nothing is queued then), then the
   // pages go over the lanes as run_batch's do, from the crop plan on
   // charsets (or null; entries may be null): per region -1 = the session default, 0 = none, >= 1 = that charset
   rt_results* run_regions(const uint8_t* const* rgb, const int* hs, const int* ws, int n_pages, int mem,
-                          const float* const* quads, const int* n_quads, const int* const* charsets = nullptr);
+                          const float* const* quads, const int* n_quads, const int* const* charsets = nullptr,
+                          const int* const* lexicons = nullptr);   // lexicons: the same convention for rec lexicons
 };
 
 rt_session* rt_session_create(const rt_config* cfg);
@@ -239,4 +277,11 @@ std::vector<std::string> load_dictionary(const std::vector<uint8_t>& bytes);
 // for malformed text, RT_ERR_INVALID for a code point that matches no entry ("U+XXXX") or an id outside [0, dict.size()).
 std::vector<uint32_t> compile_charset(const std::vector<std::string>& dict, const char* utf8, size_t len, const int32_t* ids,
                                       int n_ids);
+// A rec lexicon (ctc_lexicon.h) as flat class ids and one length per entry: the lines of utf8 [len] (split and trimmed as the
+// dictionary's lines are; empty lines skipped), each code point the LOWEST class id whose whole dictionary entry is that code
+// point (U+0020 is the appended " "), then n_id_entries entries of entry_lens[i] ids each, consecutive in ids.  Throws RT_ERR_UTF8
+// for malformed text; RT_ERR_INVALID for a code point that matches no entry ("U+XXXX", naming the entry), an id outside
+// [1, dict.size()), an empty id entry, an entry longer than lx::MAX_LEN, or no entry at all; RT_ERR_CAPACITY past lx::MAX_ENTRIES.
+void compile_lexicon(const std::vector<std::string>& dict, const char* utf8, size_t len, const int32_t* ids,
+                     const int32_t* entry_lens, int n_id_entries, std::vector<int32_t>& ids_out, std::vector<int32_t>& lens_out);
 }
