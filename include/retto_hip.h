@@ -714,6 +714,46 @@ RT_API int rt_debug_fpn(rt_session* s, int op, const int* ip, const float* fp, c
 RT_API int rt_debug_conv16x(rt_session* s, const int* ip, const float* fp, const int* heights, const int* widths, int n_img,
                             const float* x, long long x_len, const float* wt, long long wt_len, const float* bias, const float* res,
                             long long res_len, const float* dot_w, float* out, long long out_len, int* route_out);
+/* One MobileNetV3 inverted-residual block of the angle classifier (expand 1x1 -> depthwise k x k, stride (sh, 1) -> squeeze-excite
+ * -> linear 1x1 [+ x]) on host arrays, through the function ClsNet::run calls per block, for the numerics tests.  n crops of one
+ * H x W (the classifier never has ragged input), x [n H W][cin]; exp_w [mid][cin], exp_b [mid]; dw_w [mid][k][k] (torch depthwise
+ * layout), dw_b [mid]; se != 0: fc1_w [mid / 4][mid], fc1_b [mid / 4], fc2_w [mid][mid / 4], fc2_b [mid] (hard-sigmoid slope 0.2,
+ * offset 0.5); lin_w [cout][mid], lin_b [cout]; act = 1 relu / 2 hardswish on the expansion and the depthwise; the shortcut is
+ * taken where sh == 1 and cin == cout.  cin, mid, cout are multiples of 4.  form: 0 = the launch series (GEMM, depthwise,
+ * pooling + FCs, channel scaling, GEMM), 1 = the single k_cls_block launch where cls_block_supported() has an instance.
+ * out [(n Ho W + 64) * cout], Ho = ceil(H / sh), filled with RT_DEBUG_CANARY before the launch and returned whole.
+ * info_out[4] = {k_cls_block ran, its LDS slice has padded rows (0: XOR swizzle), row tiles per wave MAXU (9 or 5), LDS bytes};
+ * all 0 where the series ran. */
+RT_API int rt_debug_cls_block(rt_session* s, const float* x, int n, int H, int W, int cin, int mid, int cout, int k, int sh, int act,
+                              int se, const float* exp_w, const float* exp_b, const float* dw_w, const float* dw_b, const float* fc1_w,
+                              const float* fc1_b, const float* fc2_w, const float* fc2_b, const float* lin_w, const float* lin_b,
+                              int form, float* out, int* info_out);
+/* One stem launch (3x3 conv, stride 2, pad 1, 3 -> cout channels) on n_img images of heights[i] x widths[i] pixels, consecutive in
+ * their buffer.  Exactly one of x4 / rgb is given: x4 = float32 NHWC-4 [pixels][4] (channel 3 ignored) with cout 8 (k_stem<8>, the
+ * classifier's) or 16 (k_stem_mfma<0>, the rec net's); rgb = RGB8 pages [pixels][3] with cout 16 (k_stem_mfma<1>, the det net's:
+ * tensor channel c = (byte[2 - c] * scale - mean3[c]) / std3[c], three separately rounded float32 operations).  w [cout][3][3][3],
+ * bias [cout], act as rt_debug_gemm.  out [(sum ceil(h / 2) ceil(w / 2) + 64) * cout] (out_len floats), filled with
+ * RT_DEBUG_CANARY before the launch and returned whole. */
+RT_API int rt_debug_stem(rt_session* s, const float* x4, const unsigned char* rgb, const int* heights, const int* widths, int n_img,
+                         int cout, const float* w, const float* bias, int act, float scale, const float* mean3, const float* std3,
+                         float* out, long long out_len);
+/* One launch of a glue kernel of the fp32 family on host arrays, for the numerics tests.  Ops 0 - 3 work on n_img images of
+ * heights[i] x widths[i] pixels, consecutive in x [pixels][pitch]; ops 4 - 6 on n_img ROWS (heights / widths unused, may be NULL).
+ *    0 se_scale          ip = {C, Cr, residual, apply}, fp = {slope}; x [pixels][Cp], Cp = C's channel pitch (C rounded up to 4; to
+ *                        32 from 128 channels on); w[4] = fc1 w [Cr][C], fc1 b [Cr], fc2 w [C][Cr], fc2 b [C].  out = the scales
+ *                        [(n_img + 64) * Cp] (channels C .. Cp: +0); apply: nn::scale_channels then multiplies x in place, out2 =
+ *                        that buffer [(pixels + 64) * Cp]
+ *    1 global_mean       ip = {Cp}; x [pixels][Cp] -> out [(n_img + 64) * Cp]
+ *    2 maxpool_2x2       ip = {Cp}; images of at least 2 x 2 -> out [(sum floor(h / 2) floor(w / 2) + 64) * Cp]
+ *    3 avgpool_3x2       ip = {Cp, ldy}; images of at least 3 x 2 -> channels 0 .. Cp of out [(sum floor(h / 3) floor(w / 2) + 64) * ldy]
+ *    4 softmax_rows      ip = {C, ld}; x [rows][ld] -> out [(rows + 64) * C]
+ *    5 argmax_prob_rows  ip = {C, ld} -> idx_out [rows + 64] (the first argmax), out [rows + 64] (its softmax probability)
+ *    6 argmax_rows       ip = {C, ld} -> idx_out [rows + 64], out [rows + 64] (the maximum itself)
+ * out, out2 and idx_out are filled with RT_DEBUG_CANARY before the launch and returned whole; x_len, out_len, out2_len = the
+ * arrays' lengths in floats, checked before any device work.  The session is looked at last. */
+RT_API int rt_debug_glue32(rt_session* s, int op, const int* ip, const float* fp, const int* heights, const int* widths, int n_img,
+                           const float* x, long long x_len, const float* const* w, float* out, long long out_len, float* out2,
+                           long long out2_len, int* idx_out);
 /* times the fused thin LCNetV3 block (3x3 depthwise -> 1x1 conv; n images of h x w, random data).  form: 0 = k_lc_thin
  * (workgroup-staged; the unfused depthwise + GEMM pair where it has no instance), 1 = k_lc_wave (direct loads, stride 1 only),
  * 3 = k_lc_lds (production).  stride: 1, 2, or 21 = (2, 1).  Returns the average ms and the max |diff| against form 0. */

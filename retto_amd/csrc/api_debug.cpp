@@ -1,6 +1,6 @@
 // Kernel-level diagnostics of libretto_hip.so (include/retto_hip.h, diagnostics section): the A/B switches of tools/, the kernel
 // micro-benchmarks (rt_bench_*), and one harness per kernel family that runs a single launch on host arrays for the fp64 tests
-// (rt_debug_gemm, _dwconv, _attention, _ctc_candidates, _ctc_charset, _ctc_lexicon, _lc_block, _conv13, _layernorm, _conv16, _glue16, _fpn, _conv16x).
+// (rt_debug_gemm, _dwconv, _attention, _ctc_candidates, _ctc_charset, _ctc_lexicon, _lc_block, _conv13, _layernorm, _conv16, _glue16, _fpn, _conv16x, _cls_block, _stem, _glue32).
 // None of it runs in production, and every kernel test depends on it.  A harness has one shape: check the arguments (each
 // failure with its own message, before any device work), lay the ragged lists out (Ragged), put the operands on the device
 // (DevBufs::upload / zeroed, upload_as), fill what the kernel writes with RT_DEBUG_CANARY and spare rows (DevBufs::canary),
@@ -35,6 +35,7 @@ struct Ragged {
   int n() const { return (int)g.size(); }
   Ragged down(int sh, int sw) const { Ragged r; for (const ImgGeom& i : g) r.push((i.H + sh - 1) / sh, (i.W + sw - 1) / sw); return r; }   // a "same"-padded conv of stride (sh, sw)
   Ragged up(int k) const { Ragged r; for (const ImgGeom& i : g) r.push(k * i.H, k * i.W); return r; }
+  Ragged pool(int kh, int kw) const { Ragged r; for (const ImgGeom& i : g) r.push(i.H / kh, i.W / kw); return r; }   // window = stride, no padding (pool_level)
   Ragged flat() const { Ragged r; r.push(1, (int)total); return r; }   // one image of 1 x total pixels
   const ImgGeom* upload(DevBufs& bufs) const { return bufs.upload(g.data(), g.size()); }
 };
@@ -1071,6 +1072,187 @@ RT_API int rt_debug_conv16x(rt_session* s, const int* ip, const float* fp, const
     *route_out = nh::g_conv16_route;
     RT_HIP_CHECK(hipStreamSynchronize(st));
     if (dot) DevBufs::download(out, yf, (size_t)out_n); else DevBufs::download(out, yh, (size_t)out_n);
+  });
+}
+
+// One MobileNetV3 block of the angle classifier through the networks' run_cls_block on host arrays (tests/test_gpu_cls_kernels.py
+// compares it with an fp64 block): n crops of one H x W, as ClsNet has them (cls_block_supported() sees the maxima only), the weights
+// through the packers ClsNet's constructor calls, squeeze-excite on mid / 4 hidden units, the shortcut where ClsNet takes it
+// (stride 1 and cin == cout).  form = nn::g_cls_fused for the launch; what ran is reported, not recomputed: cls_block_fused() and
+// cls_block_shape() are what run_cls_block and nn::cls_block themselves ask.  The session is looked at last.
+RT_API int rt_debug_cls_block(rt_session* s, const float* x, int n, int H, int W, int cin, int mid, int cout, int k, int sh, int act,
+                              int se, const float* exp_w, const float* exp_b, const float* dw_w, const float* dw_b, const float* fc1_w,
+                              const float* fc1_b, const float* fc2_w, const float* fc2_b, const float* lin_w, const float* lin_b,
+                              int form, float* out, int* info_out) {
+  RT_REQUIRE(x && exp_w && exp_b && dw_w && dw_b && lin_w && lin_b && out && info_out, s, "rt_debug_cls_block: null argument");
+  RT_REQUIRE((se == 0 || se == 1) && (!se || (fc1_w && fc1_b && fc2_w && fc2_b)), s, "rt_debug_cls_block: a squeeze-excite block needs both FCs");
+  RT_REQUIRE(n > 0 && n <= 4096 && H > 0 && H <= 4096 && W > 0 && W <= 4096, s, "rt_debug_cls_block: bad crop count or extents");
+  RT_REQUIRE(cin > 0 && cin <= 64 && cin % 4 == 0 && cout > 0 && cout <= 64 && cout % 4 == 0 && mid >= 4 && mid <= 1024 && mid % 4 == 0,
+             s, "rt_debug_cls_block: channel counts must be multiples of 4 (cin, cout <= 64, mid <= 1024)");
+  RT_REQUIRE((k == 3 || k == 5) && (sh == 1 || sh == 2) && (act == ACT_RELU || act == ACT_HSWISH) && (form == 0 || form == 1), s,
+             "rt_debug_cls_block: no such block in the classifier");
+  RT_REQUIRE((long long)n * H * W * chan_pitch(mid) < (1ll << 27), s, "rt_debug_cls_block: too large");
+  RT_REQUIRE(s, s, "rt_debug_cls_block: null session");
+  return guarded(s, [&] {
+    s->begin_call();
+    WeightStore ws;
+    ClsBlock b;
+    b.expand = pack_conv(ws, exp_w, exp_b, mid, cin, 1, 1);
+    b.dw = pack_dw(ws, dw_w, dw_b, mid, k);
+    b.se = se != 0;
+    if (se) b.sew = get_se(ws, fc1_w, fc1_b, fc2_w, fc2_b, mid, mid / 4);
+    b.linear = pack_conv(ws, lin_w, lin_b, cout, mid, 1, 1);
+    b.act = act; b.sh = sh; b.sw = 1; b.cin = cin; b.shortcut = sh == 1 && cin == cout;
+    Level Li = make_level(std::vector<std::pair<int, int>>((size_t)n, {H, W})), Lo = down_level(Li, sh, 1);
+    DevBufs bufs;
+    RestoreInt keep_form(nn::g_cls_fused);
+    nn::g_cls_fused = form;
+    RunCtx c = s->ctx(&s->arena);
+    upload_levels(c, {&Li, &Lo});
+    const size_t nin = (size_t)Li.total * cin, nout = (size_t)(Lo.total + 64) * cout;
+    float* dx = bufs.zeroed<float>(nin + (size_t)256 * cin);   // (zero rows past the last crop: the series' GEMM tiles read them)
+    DevBufs::put(dx, x, nin);
+    float* dy = bufs.canary<float>(nout, s->st);
+    const bool fused = cls_block_fused(b, Li, Lo);
+    run_cls_block(c, b, dx, Li, Lo, dy);
+    RT_HIP_CHECK(hipStreamSynchronize(s->st));
+    DevBufs::download(out, dy, nout);
+    const nn::ClsBlockShape sp = nn::cls_block_shape(k, cin, mid, Li.maxH, Li.maxW, (int)Lo.maxPix);
+    info_out[0] = fused ? 1 : 0; info_out[1] = fused && sp.padrow ? 1 : 0; info_out[2] = fused ? sp.maxu : 0; info_out[3] = fused ? sp.lds : 0;
+  });
+}
+
+// One stem launch (3x3, stride 2, pad 1, 3 -> cout channels) on a ragged image list, as the three networks issue it: cout 8 =
+// nn::stem_conv -> k_stem<8> (the classifier's), cout 16 with x4 = nn::stem_conv -> k_stem_mfma<0> (the rec net's), cout 16 with
+// rgb = nn::stem_conv_u8 -> k_stem_mfma<1> over U8Page descriptors built on the uploaded pages, as det_groups builds them (the
+// det net's; scale / mean3 / std3 = the normalisation folded in).  Weights through pack_stem.  The session is looked at last.
+RT_API int rt_debug_stem(rt_session* s, const float* x4, const unsigned char* rgb, const int* heights, const int* widths, int n_img,
+                         int cout, const float* w, const float* bias, int act, float scale, const float* mean3, const float* std3,
+                         float* out, long long out_len) {
+  RT_REQUIRE(heights && widths && w && bias && out && ((x4 != nullptr) != (rgb != nullptr)), s, "rt_debug_stem: null argument (x4 or rgb, not both)");
+  RT_REQUIRE(n_img > 0 && n_img <= 4096 && (cout == 16 || (cout == 8 && x4)) && act >= ACT_NONE && act <= ACT_SIGMOID, s,
+             "rt_debug_stem: bad image count, activation or cout (8 or 16 from a tensor, 16 from pages)");
+  RT_REQUIRE(!rgb || (mean3 && std3 && std3[0] != 0.f && std3[1] != 0.f && std3[2] != 0.f), s, "rt_debug_stem: pages need mean3 and a non-zero std3");
+  for (int i = 0; i < n_img; i++)
+    RT_REQUIRE(heights[i] > 0 && widths[i] > 0 && heights[i] <= 4096 && widths[i] <= 4096, s, "rt_debug_stem: empty or oversized image");
+  const Ragged gi(heights, widths, n_img), go = gi.down(2, 2);
+  RT_REQUIRE(gi.total < (1ll << 24), s, "rt_debug_stem: too large");
+  const long long out_n = (go.total + 64) * cout;
+  RT_REQUIRE(out_len == out_n, s, "rt_debug_stem: out has the wrong length");
+  RT_REQUIRE(s, s, "rt_debug_stem: null session");
+  return guarded(s, [&] {
+    RT_HIP_CHECK(hipSetDevice(s->device));
+    WeightStore ws;
+    float *dw = nullptr, *db = nullptr;
+    pack_stem(ws, w, bias, cout, &dw, &db);
+    DevBufs bufs;
+    const ImgGeom *dgi = gi.upload(bufs), *dgo = go.upload(bufs);
+    float* dy = bufs.canary<float>((size_t)out_n, s->st);
+    if (rgb) {
+      const uint8_t* d8 = bufs.upload(rgb, (size_t)gi.total * 3);
+      std::vector<nn::U8Page> pages(n_img);
+      for (int i = 0; i < n_img; i++) pages[i] = nn::U8Page{d8 + gi.g[i].off * 3, (long long)gi.g[i].H * gi.g[i].W, gi.g[i].off};
+      nn::stem_conv_u8(s->st, bufs.upload(pages.data(), pages.size()), scale, mean3, std3, dgi, dgo, n_img, go.maxH, go.maxW, cout, dw, db, act, dy);
+    } else {
+      nn::stem_conv(s->st, bufs.upload(x4, (size_t)gi.total * 4), dgi, dgo, n_img, go.maxH, go.maxW, cout, dw, db, act, dy);
+    }
+    RT_HIP_CHECK(hipStreamSynchronize(s->st));
+    DevBufs::download(out, dy, (size_t)out_n);
+  });
+}
+
+// One launch (squeeze-excite: the launch pair, plus nn::scale_channels in place, as run_se issues them) of the fp32 glue around the
+// squeeze-excite blocks and the classifier's and rec net's tails, on host arrays, for tests/test_gpu_cls_kernels.py
+// (include/retto_hip.h lists the ops).  Every address a kernel can form is checked against the callers' lengths first; the session
+// is looked at last.
+namespace {
+enum Glue32Op { G32_SE_SCALE = 0, G32_GLOBAL_MEAN, G32_MAXPOOL, G32_AVGPOOL, G32_SOFTMAX, G32_ARGMAX_PROB, G32_ARGMAX, G32_COUNT };
+}  // namespace
+RT_API int rt_debug_glue32(rt_session* s, int op, const int* ip, const float* fp, const int* heights, const int* widths, int n_img,
+                           const float* x, long long x_len, const float* const* w, float* out, long long out_len, float* out2,
+                           long long out2_len, int* idx_out) {
+  RT_REQUIRE(ip && fp && x && out, s, "rt_debug_glue32: null argument");
+  RT_REQUIRE(op >= 0 && op < G32_COUNT && n_img > 0 && n_img <= 4096, s, "rt_debug_glue32: bad op or image / row count");
+  const bool rows_op = op >= G32_SOFTMAX;   // n_img = the rows; no geometry
+  RT_REQUIRE(rows_op || (heights && widths), s, "rt_debug_glue32: null geometry");
+  for (int i = 0; !rows_op && i < n_img; i++)
+    RT_REQUIRE(heights[i] > 0 && widths[i] > 0 && heights[i] <= 4096 && widths[i] <= 4096, s, "rt_debug_glue32: empty or oversized image");
+  const Ragged gi = rows_op ? Ragged() : Ragged(heights, widths, n_img);
+  Ragged go;
+  const int C = ip[0];
+  RT_REQUIRE(C > 0 && C <= 8192, s, "rt_debug_glue32: bad channel count");
+  int Cp = C, ldy = C, Cr = 0;
+  long long x_need = 0, out_rows = 0, out2_n = 0;
+  bool ok = true;
+  switch (op) {
+    case G32_SE_SCALE:   // ip = {C, Cr, residual, apply}; fp = {slope}
+      Cp = chan_pitch(C); Cr = ip[1]; ldy = Cp;
+      ok = C % 4 == 0 && Cr > 0 && Cr <= 1024 && (ip[2] == 0 || ip[2] == 1) && (ip[3] == 0 || ip[3] == 1) && fp[0] > 0.f && fp[0] <= 1.f &&
+           w && w[0] && w[1] && w[2] && w[3];
+      x_need = gi.total * Cp; out_rows = n_img; out2_n = ip[3] ? (gi.total + 64) * Cp : 0;
+      break;
+    case G32_GLOBAL_MEAN: ok = C % 4 == 0; x_need = gi.total * Cp; out_rows = n_img; break;
+    case G32_MAXPOOL:
+      ok = C % 4 == 0;
+      for (int i = 0; ok && i < n_img; i++) ok = heights[i] >= 2 && widths[i] >= 2;
+      if (ok) go = gi.pool(2, 2);
+      x_need = gi.total * Cp; out_rows = go.total;
+      break;
+    case G32_AVGPOOL:    // ip = {Cp, ldy}
+      ldy = ip[1];
+      ok = C % 4 == 0 && ldy >= C && ldy <= 16384 && ldy % 4 == 0;
+      for (int i = 0; ok && i < n_img; i++) ok = heights[i] >= 3 && widths[i] >= 2;
+      if (ok) go = gi.pool(3, 2);
+      x_need = gi.total * Cp; out_rows = go.total;
+      break;
+    case G32_SOFTMAX: case G32_ARGMAX_PROB: case G32_ARGMAX:   // ip = {C, ld}
+      ok = ip[1] >= C && ip[1] <= 16384 && (op == G32_SOFTMAX || idx_out);
+      x_need = (long long)n_img * ip[1]; out_rows = n_img; ldy = op == G32_SOFTMAX ? C : 1;
+      break;
+  }
+  RT_REQUIRE(ok, s, "rt_debug_glue32: bad parameters for the op");
+  RT_REQUIRE(x_need < (1ll << 28) && out_rows * ldy < (1ll << 28), s, "rt_debug_glue32: too large");
+  const long long out_n = (out_rows + 64) * ldy;
+  RT_REQUIRE(x_len >= x_need && out_len == out_n, s, "rt_debug_glue32: x is too short or out has the wrong length");
+  RT_REQUIRE(out2_n == 0 || (out2 && out2_len == out2_n), s, "rt_debug_glue32: out2 is missing or has the wrong length");
+  RT_REQUIRE(s, s, "rt_debug_glue32: null session");
+  return guarded(s, [&] {
+    RT_HIP_CHECK(hipSetDevice(s->device));
+    DevBufs bufs;
+    WeightStore ws;
+    hipStream_t st = s->st;
+    float* dout = bufs.canary<float>((size_t)out_n, st);
+    const ImgGeom* dgi = rows_op ? nullptr : gi.upload(bufs);
+    switch (op) {
+      case G32_SE_SCALE: {   // as run_se
+        const SeW se = get_se(ws, w[0], w[1], w[2], w[3], C, Cr);
+        float* dx = nullptr;
+        if (out2_n) { dx = bufs.canary<float>((size_t)out2_n, st); DevBufs::put(dx, x, (size_t)x_need); }
+        else dx = bufs.upload(x, (size_t)x_need);
+        float* partial = bufs.alloc<float>((size_t)n_img * nn::pool_chunks(gi.max_pix) * Cp);
+        nn::se_scale(st, dx, dgi, n_img, gi.max_pix, se.C, Cp, se.w1, se.b1, se.w2, se.b2, se.Cr, fp[0], ip[2], partial, dout);
+        if (out2_n) nn::scale_channels(st, dx, dgi, n_img, gi.max_pix, Cp, dout);
+        RT_HIP_CHECK(hipStreamSynchronize(st));
+        if (out2_n) DevBufs::download(out2, dx, (size_t)out2_n);
+      } break;
+      case G32_GLOBAL_MEAN: {
+        float* partial = bufs.alloc<float>((size_t)n_img * nn::pool_chunks(gi.max_pix) * Cp);
+        nn::global_mean(st, bufs.upload(x, (size_t)x_need), dgi, n_img, gi.max_pix, Cp, partial, dout);
+      } break;
+      case G32_MAXPOOL: nn::maxpool_2x2(st, bufs.upload(x, (size_t)x_need), dgi, go.upload(bufs), n_img, go.max_pix, Cp, dout); break;
+      case G32_AVGPOOL: nn::avgpool_3x2(st, bufs.upload(x, (size_t)x_need), dgi, go.upload(bufs), n_img, go.max_pix, Cp, dout, ldy); break;
+      case G32_SOFTMAX: nn::softmax_rows(st, bufs.upload(x, (size_t)x_need), ip[1], n_img, C, dout); break;
+      case G32_ARGMAX_PROB: case G32_ARGMAX: {
+        int* didx = bufs.canary<int>((size_t)out_n, st);
+        const float* dx = bufs.upload(x, (size_t)x_need);
+        if (op == G32_ARGMAX_PROB) nn::argmax_prob_rows(st, dx, ip[1], n_img, C, didx, dout);
+        else nn::argmax_rows(st, dx, ip[1], n_img, C, didx, dout);
+        RT_HIP_CHECK(hipStreamSynchronize(st));
+        DevBufs::download(idx_out, didx, (size_t)out_n);
+      } break;
+    }
+    RT_HIP_CHECK(hipStreamSynchronize(st));
+    DevBufs::download(out, dout, (size_t)out_n);
   });
 }
 

@@ -156,13 +156,16 @@ PackedDw pack_dw(WeightStore& ws, const float* w, const float* bias_in, int C, i
 static void pack_stem(WeightStore& ws, const Blob& b, const std::string& name, int cout, float** w_out, float** b_out) {
   const BlobTensor& w = b.get(name + ".w");
   expect_dims(w, {cout, 3, 3, 3}, name + ".w");
+  const BlobTensor& bt = b.get(name + ".b");
+  expect_dims(bt, {cout}, name + ".b");
+  pack_stem(ws, w.data, bt.data, cout, w_out, b_out);
+}
+void pack_stem(WeightStore& ws, const float* w, const float* bias_in, int cout, float** w_out, float** b_out) {
   std::vector<float> host(27 * cout), bias(cout);
   for (int n = 0; n < cout; n++)
     for (int ci = 0; ci < 3; ci++)
-      for (int t = 0; t < 9; t++) host[(t * 3 + ci) * cout + n] = w.data[(n * 3 + ci) * 9 + t];
-  const BlobTensor& bt = b.get(name + ".b");
-  expect_dims(bt, {cout}, name + ".b");
-  memcpy(bias.data(), bt.data, cout * sizeof(float));
+      for (int t = 0; t < 9; t++) host[(t * 3 + ci) * cout + n] = w[(n * 3 + ci) * 9 + t];
+  memcpy(bias.data(), bias_in, cout * sizeof(float));
   *w_out = ws.upload(host); *b_out = ws.upload(bias);
 }
 Lab get_lab(const Blob& b, const std::string& name) {
@@ -174,6 +177,12 @@ float* upload_raw(WeightStore& ws, const Blob& b, const std::string& name, size_
   const BlobTensor& t = b.get(name);
   if (t.numel() != expect_numel) throw RtError(3, "RTWB: unexpected size for " + name);
   return ws.upload(std::vector<float>(t.data, t.data + t.numel()));
+}
+SeW get_se(WeightStore& ws, const float* w1, const float* b1, const float* w2, const float* b2, int C, int Cr) {
+  SeW s; s.C = C; s.Cr = Cr;
+  s.w1 = ws.upload(std::vector<float>(w1, w1 + (size_t)Cr * C)); s.b1 = ws.upload(std::vector<float>(b1, b1 + Cr));
+  s.w2 = ws.upload(std::vector<float>(w2, w2 + (size_t)Cr * C)); s.b2 = ws.upload(std::vector<float>(b2, b2 + C));
+  return s;
 }
 static SeW get_se(WeightStore& ws, const Blob& b, const std::string& name, int C) {
   SeW s; s.C = C; s.Cr = C / 4;
@@ -702,13 +711,14 @@ ClsNet::ClsNet(const Blob& b) {
   int cin = 8, i = 0;
   for (const ClsSpec& s : CLS_SPEC) {
     std::string p = "cls.b" + std::to_string(i++);
-    B blk;
+    ClsBlock blk;
     blk.expand = pack_conv(ws_, b, p + ".expand", s.mid, cin, 1, 1);
     blk.dw = pack_dw(ws_, b, p + ".dw", s.mid, s.k);
     blk.se = s.se;
     if (s.se) blk.sew = get_se(ws_, b, p + ".se", s.mid);
     blk.linear = pack_conv(ws_, b, p + ".linear", s.cout, s.mid, 1, 1);
     blk.act = s.act; blk.sh = s.sh; blk.sw = s.sw;
+    blk.cin = cin;
     blk.shortcut = (s.sh == 1 && s.sw == 1 && cin == s.cout);
     blocks_.push_back(blk);
     cin = s.cout;
@@ -717,10 +727,42 @@ ClsNet::ClsNet(const Blob& b) {
   fc_ = pack_linear(ws_, b, "cls.head.fc", 200, 2);
 }
 
+bool cls_block_fused(const ClsBlock& b, const Level& Lin, const Level& Lout) {
+  return nn::g_cls_fused && nn::cls_block_supported(b.dw.k, b.sh, b.sw, b.cin, b.dw.C, b.linear.N, b.act, Lin.maxH, Lin.maxW, (int)Lout.maxPix);
+}
+float* run_cls_block(RunCtx& c, const ClsBlock& b, const float* t, const Level& Lin, const Level& Lout, float* y) {
+  const int cin = b.cin, co = b.linear.N;
+  if (cls_block_fused(b, Lin, Lout)) {
+    // the whole block in one launch, a workgroup per crop (nn_clsblock.hip)
+    if (!y) y = c.arena->alloc<float>((size_t)Lout.total * co);
+    float* dscr = b.se ? c.arena->alloc<float>((size_t)Lout.total * round_up(b.dw.C, 16)) : nullptr;
+    ProfScope ps(c.prof, c.st, "cls_block", shape_str(Lin.total, b.dw.C, co, cin * 1000 + b.dw.k * 100 + b.sh * 10 + (b.se ? 1 : 0)));
+    nn::cls_block(c.st, b.dw.k, b.sh, b.se, b.act, t, Lin.d, Lout.d, Lout.n(), Lin.maxH, Lin.maxW, (int)Lout.maxPix, cin, b.dw.C, b.dw.Cp, co, b.expand.w,
+                  b.expand.b, b.dw.w, b.dw.b, b.se ? b.sew.w1 : nullptr, b.se ? b.sew.b1 : nullptr, b.se ? b.sew.w2 : nullptr,
+                  b.se ? b.sew.b2 : nullptr, b.se ? b.sew.Cr : 0, HSIG_MBV3, b.linear.w, b.linear.b, b.shortcut, y, dscr);
+    return y;
+  }
+  const int mid = b.dw.Cp;
+  float* e = c.arena->alloc<float>((size_t)Lin.total * mid);
+  { ProfScope ps(c.prof, c.st, "gemm_cls");
+    nn::gemm(c.st, t, cin, Lin.total, b.expand.K, b.expand.w, b.expand.N, b.expand.Npad, e, mid, 0,
+             make_epi(b.expand, b.act)); }
+  float* d = c.arena->alloc<float>((size_t)Lout.total * mid);
+  { ProfScope ps(c.prof, c.st, b.dw.k == 3 ? "dwconv3" : "dwconv5");
+    nn::dwconv(c.st, b.dw.k, b.sh, b.sw, e, Lin.d, Lout.d, Lout.n(), Lout.maxH, Lout.maxW, mid, b.dw.C, b.dw.w, b.dw.b, b.act, 0,
+               1.f, 0.f, d); }
+  if (b.se) run_se(c, d, Lout, b.sew, HSIG_MBV3, 0);
+  if (!y) y = c.arena->alloc<float>((size_t)Lout.total * co);
+  { ProfScope ps(c.prof, c.st, "gemm_cls");
+    nn::gemm(c.st, d, mid, Lout.total, b.linear.K, b.linear.w, co, b.linear.Npad, y, co, 0,
+             make_epi(b.linear, ACT_NONE, nullptr, b.shortcut ? t : nullptr, cin)); }
+  return y;
+}
+
 float* ClsNet::run(RunCtx& c, const float* x, Level& L0) {
   std::vector<Level> lv; lv.reserve(16);
   lv.push_back(down_level(L0, 2, 2));
-  for (const B& b : blocks_) lv.push_back(down_level(lv.back(), b.sh, b.sw));
+  for (const ClsBlock& b : blocks_) lv.push_back(down_level(lv.back(), b.sh, b.sw));
   Level Lp = pool_level(lv.back(), 2, 2);
   std::vector<Level*> ups = {&L0};
   for (auto& l : lv) ups.push_back(&l);
@@ -729,39 +771,8 @@ float* ClsNet::run(RunCtx& c, const float* x, Level& L0) {
   float* t = c.arena->alloc<float>((size_t)lv[0].total * 8);
   { ProfScope ps(c.prof, c.st, "stem");
     nn::stem_conv(c.st, x, L0.d, lv[0].d, lv[0].n(), lv[0].maxH, lv[0].maxW, 8, stem_w_, stem_b_, ACT_HSWISH, t); }
-  int cin = 8;
-  for (size_t i = 0; i < blocks_.size(); i++) {
-    const B& b = blocks_[i];
-    const Level &Lin = lv[i], &Lout = lv[i + 1];
-    if (nn::g_cls_fused && nn::cls_block_supported(b.dw.k, b.sh, b.sw, cin, b.dw.C, b.linear.N, b.act, Lin.maxH, Lin.maxW, (int)Lout.maxPix)) {
-      // the whole block in one launch, a workgroup per crop (nn_clsblock.hip)
-      const int co = b.linear.N;
-      float* y = c.arena->alloc<float>((size_t)Lout.total * co);
-      float* dscr = b.se ? c.arena->alloc<float>((size_t)Lout.total * round_up(b.dw.C, 16)) : nullptr;
-      ProfScope ps(c.prof, c.st, "cls_block", shape_str(Lin.total, b.dw.C, co, cin * 1000 + b.dw.k * 100 + b.sh * 10 + (b.se ? 1 : 0)));
-      nn::cls_block(c.st, b.dw.k, b.sh, b.se, b.act, t, Lin.d, Lout.d, Lout.n(), Lin.maxH, Lin.maxW, (int)Lout.maxPix, cin, b.dw.C, b.dw.Cp, co, b.expand.w,
-                    b.expand.b, b.dw.w, b.dw.b, b.se ? b.sew.w1 : nullptr, b.se ? b.sew.b1 : nullptr, b.se ? b.sew.w2 : nullptr,
-                    b.se ? b.sew.b2 : nullptr, b.se ? b.sew.Cr : 0, HSIG_MBV3, b.linear.w, b.linear.b, b.shortcut, y, dscr);
-      t = y; cin = co;
-      continue;
-    }
-    int mid = b.dw.Cp;
-    float* e = c.arena->alloc<float>((size_t)Lin.total * mid);
-    { ProfScope ps(c.prof, c.st, "gemm_cls");
-      nn::gemm(c.st, t, cin, Lin.total, b.expand.K, b.expand.w, b.expand.N, b.expand.Npad, e, mid, 0,
-               make_epi(b.expand, b.act)); }
-    float* d = c.arena->alloc<float>((size_t)Lout.total * mid);
-    { ProfScope ps(c.prof, c.st, b.dw.k == 3 ? "dwconv3" : "dwconv5");
-      nn::dwconv(c.st, b.dw.k, b.sh, b.sw, e, Lin.d, Lout.d, Lout.n(), Lout.maxH, Lout.maxW, mid, b.dw.C, b.dw.w, b.dw.b, b.act, 0,
-                 1.f, 0.f, d); }
-    if (b.se) run_se(c, d, Lout, b.sew, HSIG_MBV3, 0);
-    int co = b.linear.N;
-    float* y = c.arena->alloc<float>((size_t)Lout.total * co);
-    { ProfScope ps(c.prof, c.st, "gemm_cls");
-      nn::gemm(c.st, d, mid, Lout.total, b.linear.K, b.linear.w, co, b.linear.Npad, y, co, 0,
-               make_epi(b.linear, ACT_NONE, nullptr, b.shortcut ? t : nullptr, cin)); }
-    t = y; cin = co;
-  }
+  for (size_t i = 0; i < blocks_.size(); i++) t = run_cls_block(c, blocks_[i], t, lv[i], lv[i + 1]);
+  const int cin = blocks_.back().linear.N;
   const Level& Ll = lv.back();
   float* f = c.arena->alloc<float>((size_t)Ll.total * 200);
   { ProfScope ps(c.prof, c.st, "gemm_cls");

@@ -65,6 +65,8 @@ PackedDw pack_dw(WeightStore& ws, const float* w, const float* bias, int C, int 
 PackedDense pack_linear(WeightStore& ws, const Blob& b, const std::string& name, int cin, int cout);
 PackedDense pack_linear(WeightStore& ws, const float* w, const float* bias, int cin, int cout);   // host w [cin][cout], bias [cout] or null
 float* upload_raw(WeightStore& ws, const Blob& b, const std::string& name, size_t expect_numel);
+void pack_stem(WeightStore& ws, const float* w, const float* bias, int cout, float** w_out, float** b_out);   // host w [cout][3][3][3], bias [cout] -> [27][cout], [cout]
+SeW get_se(WeightStore& ws, const float* w1, const float* b1, const float* w2, const float* b2, int C, int Cr);   // host fc1 w [Cr][C], b [Cr], fc2 w [C][Cr], b [C]
 // Host-side operands of the upsampling-aware FPN convs (nn_fpn.hip) from a raw 3x3 conv weight w [24][cin_total][3][3]; DetNet's
 // constructor and rt_debug_fpn call the same functions (layouts: at their definitions in nets.cpp).
 std::vector<float> fpn_fine_weights(const float* w, int cin_total, int c0, int cc, int cf);   // [9 taps][24 n][cf]
@@ -114,6 +116,12 @@ inline constexpr ClsSpec CLS_SPEC[] = {
     {5, 32, 16, true, ACT_HSWISH, 2, 1},  {5, 88, 16, true, ACT_HSWISH, 1, 1},  {5, 88, 16, true, ACT_HSWISH, 1, 1},
     {5, 40, 16, true, ACT_HSWISH, 1, 1},  {5, 48, 16, true, ACT_HSWISH, 1, 1},  {5, 104, 32, true, ACT_HSWISH, 2, 1},
     {5, 200, 32, true, ACT_HSWISH, 1, 1}, {5, 200, 32, true, ACT_HSWISH, 1, 1}};
+// One MobileNetV3 block of the angle classifier: x at Lin (pitch cin) -> the block's output at Lout (pitch linear.N; y = null: arena
+// memory).  One k_cls_block launch where cls_block_fused() says so (nn::g_cls_fused and nn::cls_block_supported), else the
+// launch series expand GEMM -> depthwise -> run_se -> linear GEMM, whose GEMMs read rows past the end of x.
+struct ClsBlock { PackedDense expand, linear; PackedDw dw; bool se = false; SeW sew; int act = ACT_RELU, sh = 1, sw = 1, cin = 0; bool shortcut = false; };
+bool cls_block_fused(const ClsBlock& b, const Level& Lin, const Level& Lout);
+float* run_cls_block(RunCtx& c, const ClsBlock& b, const float* x, const Level& Lin, const Level& Lout, float* y = nullptr);
 Lab get_lab(const Blob& b, const std::string& name);   // the LearnableAffineBlock <name>.a / .c of a blob, where it has one
 
 // The three worker functions as interfaces (RettoInnerWorker::{det,cls,rec}, worker.rs:69-73): the fp32 mobile
@@ -225,10 +233,9 @@ class ClsNet : public ClsModel {
   float* run(RunCtx& c, const float* x, Level& L0) override;
   const char* dtype() const override { return "f32"; }
  private:
-  struct B { PackedDense expand, linear; PackedDw dw; bool se; SeW sew; int act, sh, sw; bool shortcut; };
   WeightStore ws_;
   float* stem_w_; float* stem_b_;
-  std::vector<B> blocks_;
+  std::vector<ClsBlock> blocks_;
   PackedDense conv2_, fc_;
 };
 

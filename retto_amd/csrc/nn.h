@@ -66,6 +66,10 @@ void argmax_merge(hipStream_t st, const float* pm, const int* pi, const float* p
 // kernel, a workgroup per crop (nn_clsblock.hip).  Weights in the PackedDense / PackedDw layouts of nets.cpp.
 extern int g_cls_fused;
 bool cls_block_supported(int k, int sh, int sw, int cin, int mid, int cout, int act, int maxH_in, int maxW, int max_pix_out);
+// what cls_block() launches for a supported shape: the LDS layout of the expansion slice (padded rows of 80-byte pixels, or 64-byte
+// pixels with the XOR swizzle), the row tiles per wave MAXU (9 or 5) of the 8-wave workgroup, the slice's bytes and the launch's LDS
+struct ClsBlockShape { bool padrow = false; int maxu = 9, es_bytes = 0, lds = 0; };
+ClsBlockShape cls_block_shape(int k, int cin, int mid, int maxH_in, int maxW, int max_pix_out);
 void cls_block(hipStream_t st, int k, int sh, bool se, int act, const float* x, const ImgGeom* gin, const ImgGeom* gout, int n_img,
                int maxH_in, int maxW, int max_pix_out, int cin, int mid, int mid_cp, int cout, const float* Wexp, const float* bexp,
                const float* Wdw, const float* bdw, const float* w1, const float* b1, const float* w2, const float* b2, int cr, float slope,

@@ -50,8 +50,8 @@ int g_cls_fused = getenv("RT_CLS_FUSED") ? atoi(getenv("RT_CLS_FUSED")) : 1;   /
 // first block's 72 tiles, 8 x 5 for the later ones (fewer registers: more crops per CU; at 8 x 9 everywhere the 200-channel blocks
 // ran one crop per CU, 0.35 ms)
 // PADROW: the LDS slice is [row][W + 2 PAD pixels][80 bytes] with zero columns left and right (no column checks, no swizzle:
-// 80-byte pixels are conflict-free for the 16-byte reads of 8 neighbouring lanes) -- every block but the first, whose 24 x 96
-// input does not fit that way and keeps 64-byte pixels with the XOR swizzle and checked columns.
+// 80-byte pixels are conflict-free for the 16-byte reads of 8 neighbouring lanes) -- every block but the first two, whose 24 x 96
+// and 12 x 96 inputs do not fit that way (cls_block_shape) and keep 64-byte pixels with the XOR swizzle and checked columns.
 template <int KS, int SH, bool SE, int ACT, int NW, int MAXU, bool PADROW>
 __global__ __launch_bounds__(64 * NW) void k_cls_block(ClsBlkArgs p) {
   constexpr int CLS_MAXU = MAXU, NTHR = 64 * NW;
@@ -303,10 +303,26 @@ __global__ __launch_bounds__(64 * NW) void k_cls_block(ClsBlkArgs p) {
 bool cls_block_supported(int k, int sh, int sw, int cin, int mid, int cout, int act, int maxH_in, int maxW, int max_pix_out) {
   if (!(k == 3 || k == 5) || !(sh == 1 || sh == 2) || sw != 1) return false;
   if (!(act == ACT_RELU || act == ACT_HSWISH)) return false;
-  if (cin % 4 || cin > 32 || cout % 4 || cout > 32 || mid > 512) return false;
+  if (cin % 4 || cin > 32 || cout % 4 || cout > 32 || mid % 4 || mid > 512) return false;   // (mid % 4: FC1 reads w1's rows 16 bytes wide)
   if (maxW % 16 || maxW <= 0) return false;
   if ((max_pix_out + 15) / 16 > 8 * 9) return false;
   return (long long)maxH_in * maxW * 64 + (8 * 16 + 2 * round_up(mid, 16) + 128 + (k * k + 1) * 16) * 4 <= 160 * 1024;
+}
+
+// The workgroup shape and LDS layout of a block: 8 waves per crop everywhere (4 on the small maps measured 1.31 vs 1.11 ms for the
+// eleven blocks: a launch has only ~1-4 crops per CU, so a crop's latency chain, not the CU's wave slots, is what counts); 9 row
+// tiles per wave where needed, 5 otherwise; the padded-row layout wherever slice, small tables and the input copy fit 96 KB.
+ClsBlockShape cls_block_shape(int k, int cin, int mid, int maxH_in, int maxW, int max_pix_out) {
+  const int nt_out = (max_pix_out + 15) / 16, nw = 8;
+  const int small = (nw * 16 + 2 * round_up(mid, 16) + 128 + (k * k + 1) * 16) * 4;
+  const long long padded = (long long)maxH_in * (maxW + 2 * (k / 2)) * 80;
+  const long long xs_bytes = (long long)maxH_in * maxW * (cin + 4) * 4;
+  ClsBlockShape s;
+  s.padrow = padded + small + xs_bytes <= 96 * 1024;   // (the first block's 24 x 96 input: 188 KB that way)
+  s.maxu = (!s.padrow || nt_out > 40) ? 9 : 5;          // 8 waves x 9 tiles | 8 x 5 (the swizzled layout has the 8 x 9 instance only)
+  s.es_bytes = s.padrow ? (int)padded : maxH_in * maxW * 64;
+  s.lds = s.es_bytes + small + (s.padrow ? (int)xs_bytes : 0);
+  return s;
 }
 
 void cls_block(hipStream_t st, int k, int sh, bool se, int act, const float* x, const ImgGeom* gin, const ImgGeom* gout, int n_img,
@@ -317,17 +333,10 @@ void cls_block(hipStream_t st, int k, int sh, bool se, int act, const float* x, 
   if (se && !dscr) throw RtError(8, "cls_block: a squeeze-excite block needs the scratch tensor");
   ClsBlkArgs a{x, y, gin, gout, Wexp, bexp, Wdw, bdw, w1, b1, w2, b2, Wlin, blin, dscr,
                cin, mid, mid_cp, cout, round_up(mid, 16), round_up(cout, 16), cr, shortcut ? 1 : 0, maxH_in * maxW * 64, slope};
-  const int nt_out = (max_pix_out + 15) / 16;
-  // 8 waves per crop everywhere (4 on the small maps measured 1.31 vs 1.11 ms for the eleven blocks: a launch has only ~1-4
-  // crops per CU, so a crop's latency chain, not the CU's wave slots, is what counts); 9 row tiles per wave where needed
-  const int shape = nt_out > 40 ? 0 : 1;   // 8 waves x 9 tiles | 8 x 5
-  const int nw = 8;
-  const int small = (nw * 16 + 2 * a.npad_e + 128 + (k * k + 1) * 16) * 4;
-  const long long padded = (long long)maxH_in * (maxW + 2 * (k / 2)) * 80;
-  const long long xs_bytes = (long long)maxH_in * maxW * (cin + 4) * 4;
-  const bool padrow = padded + small + xs_bytes <= 96 * 1024;   // (the first block's 24 x 96 input: 188 KB that way)
-  if (padrow) a.es_bytes = (int)padded;
-  const int lds = a.es_bytes + small + (padrow ? (int)xs_bytes : 0);
+  const ClsBlockShape sp = cls_block_shape(k, cin, mid, maxH_in, maxW, max_pix_out);
+  const bool padrow = sp.padrow;
+  const int shape = sp.maxu == 9 ? 0 : 1, lds = sp.lds;
+  a.es_bytes = sp.es_bytes;
 #define RT_CB(KK, SS, EE, AA, NWW, MU, PP)                                                               \
   do {                                                                                                   \
     allow_big_lds((const void*)k_cls_block<KK, SS, EE, AA, NWW, MU, PP>, 160 * 1024);                    \

@@ -1,7 +1,8 @@
 """The kernel-level debug entry points rt_debug_gemm / rt_debug_attention (tests/test_gpu_ops.py drives them on the GPU) and
 rt_debug_lc_block / rt_debug_conv13 / rt_debug_layernorm (tests/test_gpu_rec_kernels.py) and rt_debug_glue16 / rt_debug_conv16x
-(tests/test_gpu_f16_kernels.py) and rt_debug_fpn (tests/test_gpu_fpn_kernels.py): declared, exported, and null or bad arguments
-rejected with RT_ERR_INVALID before any device work."""
+(tests/test_gpu_f16_kernels.py) and rt_debug_fpn (tests/test_gpu_fpn_kernels.py) and rt_debug_cls_block / rt_debug_stem /
+rt_debug_glue32 (tests/test_gpu_cls_kernels.py): declared, exported, and null or bad arguments rejected with RT_ERR_INVALID before
+any device work."""
 import ctypes as C
 import os
 
@@ -17,7 +18,7 @@ def test_debug_symbols_are_declared_and_exported():
     header = open(os.path.join(ROOT, "include", "retto_hip.h")).read()
     lib = _lib.load()
     for name in ("rt_debug_gemm", "rt_debug_attention", "rt_debug_lc_block", "rt_debug_conv13", "rt_debug_layernorm",
-                 "rt_debug_glue16", "rt_debug_conv16x", "rt_debug_fpn"):
+                 "rt_debug_glue16", "rt_debug_conv16x", "rt_debug_fpn", "rt_debug_cls_block", "rt_debug_stem", "rt_debug_glue32"):
         assert "RT_API int %s(" % name in header
         assert name in _lib.EXPORTS
         assert hasattr(lib, name)
@@ -266,3 +267,89 @@ def test_fpn_rejects_null_and_bad_arguments_without_a_device():
     for kw, why in cases:
         assert _fpn(lib, **kw) == RT_ERR_INVALID, kw
         assert why in lib.rt_last_error(None).decode(), (kw, lib.rt_last_error(None))
+
+
+def _cls(lib, s=None, n=2, H=3, W=16, cin=8, mid=16, cout=8, k=3, sh=1, act=1, se=1, form=1, null=None, info=True):
+    """a 3 x 16 block with squeeze-excite on two crops, unless the arguments say otherwise; null = the name of a NULL operand"""
+    a = lambda *shape: np.zeros([max(v, 1) for v in shape], np.float32)   # noqa: E731
+    arr = {"x": a(n * H * W, cin), "exp_w": a(mid, cin), "exp_b": a(mid), "dw_w": a(mid, 5, 5), "dw_b": a(mid), "fc1_w": a(mid, mid),
+           "fc1_b": a(mid), "fc2_w": a(mid, mid), "fc2_b": a(mid), "lin_w": a(cout, mid), "lin_b": a(cout), "out": a(n * H * W + 64, cout)}
+    p = {k_: (None if k_ == null else v.ctypes.data) for k_, v in arr.items()}
+    return lib.rt_debug_cls_block(s, p["x"], n, H, W, cin, mid, cout, k, sh, act, se, p["exp_w"], p["exp_b"], p["dw_w"], p["dw_b"], p["fc1_w"],
+                                  p["fc1_b"], p["fc2_w"], p["fc2_b"], p["lin_w"], p["lin_b"], form, p["out"], (C.c_int * 4)() if info else None)
+
+
+def _stem(lib, s=None, x4=True, rgb=False, hs=(3, 1), ws=(2, 1), hh=True, ww=True, n_img=2, cout=16, w=True, b=True, act=0, mean=True,
+          std=(0.5, 0.5, 0.5), out=True, out_len=None):
+    """the rec stem on two images of 6 and 1 pixels (outputs 2 x 1 and 1 x 1), unless the arguments say otherwise"""
+    h, wd = np.array(hs, np.int32), np.array(ws, np.int32)
+    xs, px, wt, bs, o = np.zeros((7, 4), np.float32), np.zeros((7, 3), np.uint8), np.zeros((16, 27), np.float32), np.zeros(16, np.float32), np.zeros((3 + 64) * 16, np.float32)
+    m, sd = np.full(3, 0.5, np.float32), np.array(std, np.float32)
+    p = lambda arr, on: arr.ctypes.data if on else None   # noqa: E731
+    return lib.rt_debug_stem(s, p(xs, x4), p(px, rgb), p(h, hh), p(wd, ww), n_img, cout, p(wt, w), p(bs, b), act, 1 / 255.0, p(m, mean),
+                             p(sd, True), p(o, out), (3 + 64) * max(cout, 1) if out_len is None else out_len)
+
+
+def _glue32(lib, s=None, op=0, ip=(8, 2, 0, 1), fpv=(0.2,), hs=(3, 1), ws=(2, 1), hh=True, ww=True, n_img=2, ipp=True, fpp=True, x=True,
+            x_len=None, w=True, w_null=None, out=True, out_len=None, out2=True, out2_len=None, idx=True):
+    """se_scale at C = 8 applied in place on two images of 6 and 1 pixels, unless the arguments say otherwise"""
+    i = np.zeros(8, np.int32); i[:len(ip)] = ip   # noqa: E702
+    f = np.zeros(4, np.float32); f[:len(fpv)] = fpv   # noqa: E702
+    h, wd = np.array(hs, np.int32), np.array(ws, np.int32)
+    xs, o, o2, ix = np.zeros(1 << 16, np.float32), np.zeros(1 << 16, np.float32), np.zeros(1 << 16, np.float32), np.zeros(1 << 12, np.int32)
+    wts = [np.zeros(64, np.float32) for _ in range(4)]
+    wp = (C.c_void_p * 4)(*[None if k == w_null else a.ctypes.data for k, a in enumerate(wts)])
+    p = lambda arr, on: arr.ctypes.data if on else None   # noqa: E731
+    d = lambda v, dflt: dflt if v is None else v          # noqa: E731
+    return lib.rt_debug_glue32(s, op, p(i, ipp), p(f, fpp), p(h, hh), p(wd, ww), n_img, p(xs, x), d(x_len, 7 * 8), wp if w else None,
+                               p(o, out), d(out_len, (2 + 64) * 8), p(o2, out2), d(out2_len, (7 + 64) * 8), p(ix, idx))
+
+
+def test_cls_kernel_entries_reject_null_and_bad_arguments_without_a_device():
+    """rt_debug_cls_block, rt_debug_stem and rt_debug_glue32 look at their session last, so every argument check answers with its
+    own message (rt_last_error(NULL) holds it): a check that was skipped would show as a null session"""
+    lib = _lib.load()
+    lib.rt_last_error.restype = C.c_char_p
+
+    def run(fn, cases):
+        for kw, why in cases:
+            assert fn(lib, **kw) == RT_ERR_INVALID, kw
+            assert why in lib.rt_last_error(None).decode(), (kw, lib.rt_last_error(None))
+
+    null, se, crops, chan, block = "null argument", "needs both FCs", "bad crop count or extents", "multiples of 4", "no such block"
+    run(_cls, [({}, "null session"), ({"se": 0, "null": "fc1_w"}, "null session"), ({"form": 0, "W": 24}, "null session")] +
+        [({"null": k}, null) for k in ("x", "exp_w", "exp_b", "dw_w", "dw_b", "lin_w", "lin_b", "out")] + [({"info": False}, null)] +
+        [({"null": k}, se) for k in ("fc1_w", "fc1_b", "fc2_w", "fc2_b")] + [({"se": 2}, se)] +
+        [({"n": 0}, crops), ({"H": 0}, crops), ({"W": 0}, crops), ({"W": 5000}, crops),
+         ({"cin": 0}, chan), ({"cin": 6}, chan), ({"cin": 68}, chan), ({"cout": 0}, chan), ({"cout": 10}, chan), ({"mid": 0}, chan), ({"mid": 18}, chan),
+         ({"mid": 1028}, chan), ({"k": 4}, block), ({"k": 7}, block), ({"sh": 0}, block), ({"sh": 3}, block), ({"act": 0}, block), ({"act": 3}, block),
+         ({"form": 2}, block), ({"form": -1}, block), ({"n": 4096, "H": 4096, "W": 16}, "too large")])
+    null, count, pages, img, length = "null argument", "bad image count, activation or cout", "pages need", "empty or oversized image", "out has the wrong length"
+    run(_stem, [({}, "null session"), ({"cout": 8, "act": 2, "out_len": (3 + 64) * 8}, "null session"), ({"x4": False, "rgb": True}, "null session"),
+                ({"x4": False}, null), ({"rgb": True}, null), ({"hh": False}, null), ({"ww": False}, null), ({"w": False}, null), ({"b": False}, null),
+                ({"out": False}, null), ({"n_img": 0}, count), ({"cout": 4}, count), ({"cout": 32}, count), ({"act": 5}, count), ({"act": -1}, count),
+                ({"x4": False, "rgb": True, "cout": 8}, count), ({"x4": False, "rgb": True, "mean": False}, pages),
+                ({"x4": False, "rgb": True, "std": (0.5, 0.0, 0.5)}, pages), ({"hs": (3, 0)}, img), ({"ws": (5000, 1)}, img),
+                ({"out_len": (3 + 64) * 16 - 1}, length), ({"out_len": 0}, length)])
+    null, opn, geom, img, chan, params, lens, second = (
+        "null argument", "bad op or image / row count", "null geometry", "empty or oversized image", "bad channel count", "bad parameters for the op",
+        "x is too short or out has the wrong length", "out2 is missing or has the wrong length")
+    soft = {"op": 4, "ip": (2, 4), "x_len": 2 * 4, "out_len": (2 + 64) * 2, "hh": False, "ww": False}
+    amax = {"op": 6, "ip": (5, 8), "x_len": 2 * 8, "out_len": 2 + 64}
+    run(_glue32, [({}, "null session"), (soft, "null session"), (amax, "null session"), ({"ip": (8, 2, 1, 0), "out2": False}, "null session"),
+                  ({"op": 3, "ip": (8, 16), "hs": (3, 6), "ws": (2, 5), "x_len": 36 * 8, "out_len": (5 + 64) * 16}, "null session"),
+                  ({"ipp": False}, null), ({"fpp": False}, null), ({"x": False}, null), ({"out": False}, null),
+                  ({"op": -1}, opn), ({"op": 7}, opn), ({"n_img": 0}, opn), ({"hh": False}, geom), ({"ww": False}, geom),
+                  ({"hs": (3, 0)}, img), ({"ws": (0, 1)}, img), ({"ip": (0, 2, 0, 1)}, chan),
+                  ({"ip": (6, 2, 0, 1)}, params), ({"ip": (8, 0, 0, 1)}, params), ({"ip": (8, 2, 2, 1)}, params), ({"ip": (8, 2, 0, 2)}, params),
+                  ({"fpv": (0.0,)}, params), ({"w": False}, params), ({"w_null": 2}, params),
+                  ({"op": 1, "ip": (6,)}, params),
+                  ({"op": 2, "ip": (8,)}, params),                                   # maxpool_2x2: an image below the window
+                  ({"op": 3, "ip": (8, 16), "hs": (2, 3), "ws": (2, 2)}, params),   # avgpool_3x2: an image below the window
+                  ({"op": 3, "ip": (8, 4), "hs": (3, 3), "ws": (2, 2)}, params),    # avgpool_3x2: ldy below Cp
+                  ({"op": 3, "ip": (8, 18), "hs": (3, 3), "ws": (2, 2)}, params),   # avgpool_3x2: ldy no multiple of 4
+                  (dict(soft, ip=(5, 4)), params),                                   # softmax_rows: ld below C
+                  (dict(amax, idx=False), params),                                   # argmax_rows without idx_out
+                  ({"x_len": 7 * 8 - 1}, lens), ({"out_len": (2 + 64) * 8 - 1}, lens), ({"out_len": 0}, lens),
+                  (dict(soft, x_len=7), lens), (dict(amax, out_len=2 + 63), lens),
+                  ({"out2": False}, second), ({"out2_len": (7 + 64) * 8 - 1}, second)])
