@@ -591,12 +591,13 @@ RT_API int rt_debug_gemm(rt_session* s, const float* A, long long M, int K, int 
                          int ld_scale, const long long* img_rows, int n_img, int se_rows, int ldc, int coff, int variant, int ctc,
                          float* out, int* idx_out, float* prob_out, int* plan_out);
 /* One depthwise conv layer (K = 3 or 5, stride (sh, sw) in {1, 2}, "same" padding) on host arrays, for the numerics tests: n_img
- * images of heights[i] x widths[i] pixels, consecutive in x [sum h w][Cp] (channels C .. Cp zero); w [K * K][Cp] (tap dy * K + dx),
+ * images of heights[i] x widths[i] pixels, consecutive in x [sum h w][Cp] (channels C .. Cp: anything, the output's are +0); w [K * K][Cp] (tap dy * K + dx),
  * bias [Cp]; act / LAB as rt_debug_gemm.  form: 0 = the row-strip kernel, 1 = the column-sweep kernel where the layer has an
  * instance (info_out[3] tells).  out [(sum ho wo + 64) * Cp], filled with RT_DEBUG_CANARY before the launch and returned whole.
  * pooled != 0: the kernel also leaves the squeeze-excite partial sums, returned as they lie in memory in partial_out
  * [n_img][chunks][Cp] (canary where nothing was written; partial_cap = floats available) and, in mean_out [n_img][Cp], as the
- * channel means the squeeze-excite FC reads from them.  info_out[4] = {chunks, strip rows, strips per block, sweep ran}. */
+ * channel means the squeeze-excite FC reads from them.  info_out[4] = {chunks, strip rows, strips per block, sweep ran}; the launch
+ * follows the plan rt_debug_dw_plan reports for the same arguments. */
 RT_API int rt_debug_dwconv(rt_session* s, const float* x, const int* heights, const int* widths, int n_img, int C, int Cp, int K,
                            int sh, int sw, const float* w, const float* bias, int act, int has_lab, float lab_a, float lab_c,
                            int pooled, int form, float* out, float* partial_out, long long partial_cap, float* mean_out,
@@ -617,6 +618,30 @@ RT_API int rt_debug_lc_block(rt_session* s, const float* x, const int* heights, 
                              int sh, int sw, const float* dw_w, const float* dw_bias, const float* pw_w, const float* pw_bias,
                              int dw_act, int dw_has_lab, float dw_a, float dw_c, int pw_has_lab, float pw_a, float pw_c, int form,
                              float* out, int* info_out);
+/* The plan rt_debug_dwconv launches by (nn::dw_plan under the depthwise form `form`: 0 = row strips only, 1 = the column sweep where
+ * the layer has an instance) for a K x K depthwise conv, stride (sh, sw), channel pitch Cp, onto images of at most maxHo x maxWo
+ * OUTPUT pixels; pooled != 0: with the squeeze-excite partial sums.  Host only: it takes no session and touches no device.
+ * plan_out[8] = {kernel (0 invalid, 1 k_dwconv_rows on 32-channel slabs, 2 on 64-channel slabs, 3 k_dwconv_sweep), instance (sweep:
+ * 1 - 6; rows: (((lanes * 8 + K) * 8 + R) * 4 + sh) * 4 + sw), strip rows R, lanes per pixel, strips per block, partial sums per image
+ * (chunks), grid x, grid z}; the grid's y is the image count. */
+RT_API int rt_debug_dw_plan(int K, int sh, int sw, int Cp, int maxHo, int maxWo, int pooled, int form, int* plan_out);
+/* One wide LCNetV3 block (K x K depthwise, K = 3 or 5, stride (sh, sw), "same" padding [-> squeeze-excite] -> 1x1 conv + hardswish)
+ * through the networks' run_lc on host arrays, for the numerics tests: the sibling of rt_debug_lc_block for the blocks that entry
+ * cannot express.  x [sum h w][Cp], Cp = cin's channel pitch; channels cin .. Cp may hold anything.  dw_w [cin][K][K], dw_bias
+ * [cin], pw_w [cout][cin], pw_bias [cout], the two LABs as rt_debug_lc_block.  Squeeze-excite: fc1_w [cin / 4][cin], fc1_b [cin / 4],
+ * fc2_w [cin][cin / 4], fc2_b [cin] (hard-sigmoid slope 1/6), all four or all NULL.  dw_form: the depthwise form as rt_debug_dwconv's;
+ * the GEMM runs under variant 0 (the production rule).  Three buffers come back whole, each filled with RT_DEBUG_CANARY before the
+ * launch and 64 rows longer than its data: out [(sum ho wo + 64) * ldy] (ldy = cout's channel pitch), y1_out [(sum ho wo + 64) * Cp]
+ * = the depthwise buffer handed to run_lc (unscaled where the squeeze-excite is folded into the GEMM, scaled in place otherwise),
+ * scale_out [(n_img + 64) * Cp] = the per-image scales (NULL and 0 without squeeze-excite).  info_out[16] = {route (as
+ * rt_debug_lc_block), then of the unfused route: depthwise kernel, instance, R, lanes, strips per block, chunks, grid x, grid z (as
+ * rt_debug_dw_plan), rows of the squeeze-excite table folded into the GEMM (0: not folded), GemmKernel value of the pointwise GEMM's
+ * plan, that plan's se flag, scales: 0 none, 1 folded, 2 applied in place; the rest 0}.  The session is looked at last. */
+RT_API int rt_debug_lc_wide(rt_session* s, const float* x, const int* heights, const int* widths, int n_img, int K, int cin, int cout,
+                            int sh, int sw, const float* dw_w, const float* dw_bias, const float* pw_w, const float* pw_bias, int dw_act,
+                            int dw_has_lab, float dw_a, float dw_c, int pw_has_lab, float pw_a, float pw_c, const float* fc1_w,
+                            const float* fc1_b, const float* fc2_w, const float* fc2_b, int dw_form, float* out, long long out_len,
+                            float* y1_out, long long y1_len, float* scale_out, long long scale_len, int* info_out);
 /* One 1x3 conv over lines of tokens (the SVTR neck's) on host arrays: x [rows][ldx] (channels 0 .. cin read), lines of
  * tokens_per_line[i] consecutive rows (sum = rows), w [cout][cin][1][3], bias [cout] or NULL, zero padding at both ends of every
  * line, act as rt_debug_gemm.  form 0 = nn::conv_sp on one 1 x T image per line, 1 = nn::conv13_flat over the flat token list with

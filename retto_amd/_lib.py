@@ -78,7 +78,7 @@ EXPORTS = [
     "rt_set_lanes", "rt_profile_enable", "rt_profile_get",
     "rt_onnx_to_rtwb", "rt_buffer_free", "rt_model_manifest", "rt_decode_image", "rt_run_encoded_batch",
     "rt_submit_encoded_batch", "rt_decode_batch", "rt_debug_jpeg_reconstruct",
-    "rt_debug_set_variants", "rt_bench_gemm", "rt_bench_gemm_err", "rt_bench_lc", "rt_debug_conv16", "rt_debug_gemm", "rt_debug_dwconv", "rt_debug_attention", "rt_debug_lc_block", "rt_debug_conv13", "rt_debug_layernorm", "rt_debug_glue16", "rt_debug_conv16x", "rt_debug_fpn", "rt_debug_cls_block", "rt_debug_stem", "rt_debug_glue32", "rt_parse_dictionary", "rt_format_f32", "rt_rccl_unique_id", "rt_broadcast_blobs",
+    "rt_debug_set_variants", "rt_bench_gemm", "rt_bench_gemm_err", "rt_bench_lc", "rt_debug_conv16", "rt_debug_gemm", "rt_debug_dwconv", "rt_debug_dw_plan", "rt_debug_attention", "rt_debug_lc_block", "rt_debug_lc_wide", "rt_debug_conv13", "rt_debug_layernorm", "rt_debug_glue16", "rt_debug_conv16x", "rt_debug_fpn", "rt_debug_cls_block", "rt_debug_stem", "rt_debug_glue32", "rt_parse_dictionary", "rt_format_f32", "rt_rccl_unique_id", "rt_broadcast_blobs",
     "rt_run_regions", "rt_debug_warp_crops",
     "rt_charset_create", "rt_charset_classes", "rt_set_rec_charset", "rt_run_regions_charsets", "rt_debug_charset_compile",
     "rt_debug_ctc_charset", "rt_debug_ctc_charset_host",
@@ -208,6 +208,9 @@ def load():
     lib.rt_debug_lc_block.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_float,
                                       C.c_int, C.c_float, C.c_float, C.c_int, C.c_void_p, C.c_void_p]
+    lib.rt_debug_dw_plan.argtypes = [C.c_int] * 8 + [C.c_void_p]
+    lib.rt_debug_lc_wide.argtypes = ([C.c_void_p] * 4 + [C.c_int] * 6 + [C.c_void_p] * 4 + [C.c_int, C.c_int, C.c_float, C.c_float, C.c_int,
+                                     C.c_float, C.c_float] + [C.c_void_p] * 4 + [C.c_int] + [C.c_void_p, C.c_longlong] * 3 + [C.c_void_p])
     lib.rt_debug_conv13.argtypes = [C.c_void_p, C.c_void_p, C.c_longlong, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int,
                                     C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
     lib.rt_debug_layernorm.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong, C.c_int, C.c_void_p, C.c_void_p, C.c_float,

@@ -1,6 +1,6 @@
 // Kernel-level diagnostics of libretto_hip.so (include/retto_hip.h, diagnostics section): the A/B switches of tools/, the kernel
 // micro-benchmarks (rt_bench_*), and one harness per kernel family that runs a single launch on host arrays for the fp64 tests
-// (rt_debug_gemm, _dwconv, _attention, _ctc_candidates, _ctc_charset, _ctc_lexicon, _lc_block, _conv13, _layernorm, _conv16, _glue16, _fpn, _conv16x, _cls_block, _stem, _glue32).
+// (rt_debug_gemm, _dwconv, _dw_plan, _attention, _ctc_candidates, _ctc_charset, _ctc_lexicon, _lc_block, _lc_wide, _conv13, _layernorm, _conv16, _glue16, _fpn, _conv16x, _cls_block, _stem, _glue32).
 // None of it runs in production, and every kernel test depends on it.  A harness has one shape: check the arguments (each
 // failure with its own message, before any device work), lay the ragged lists out (Ragged), put the operands on the device
 // (DevBufs::upload / zeroed, upload_as), fill what the kernel writes with RT_DEBUG_CANARY and spare rows (DevBufs::canary),
@@ -589,6 +589,89 @@ RT_API int rt_debug_lc_block(rt_session* s, const float* x, const int* heights, 
     RT_HIP_CHECK(hipStreamSynchronize(s->st));
     DevBufs::download(out, dy, nout);
     info_out[0] = (int)lc_block_plan(b, Lo).route;
+  });
+}
+
+// The fields of nn::dw_plan() for a K x K depthwise conv, stride (sh, sw), pitch Cp, onto images of at most maxHo x maxWo output
+// pixels, under g_dw_sweep = form ? 4 : 0 -- the plan rt_debug_dwconv launches by.  Host only: no session, no device.
+// plan_out[8] = {DwKernel value (lc_plan.h), inst, R, lanes, spb, chunks, grid_x, grid_z}.
+RT_API int rt_debug_dw_plan(int K, int sh, int sw, int Cp, int maxHo, int maxWo, int pooled, int form, int* plan_out) {
+  rt_session* const none = nullptr;
+  RT_REQUIRE(plan_out, none, "rt_debug_dw_plan: null argument");
+  RT_REQUIRE(Cp > 0 && Cp % 4 == 0 && maxHo > 0 && maxWo > 0 && (form == 0 || form == 1), none, "rt_debug_dw_plan: bad shape");
+  RestoreInt keep_form(nn::g_dw_sweep);
+  nn::g_dw_sweep = form ? 4 : 0;
+  const nn::DwPlan p = nn::dw_plan(K, sh, sw, Cp, maxHo, maxWo, pooled != 0);
+  const int f[8] = {(int)p.kernel, p.inst, p.R, p.lanes, p.spb, p.chunks, (int)p.grid_x, (int)p.grid_z};
+  memcpy(plan_out, f, sizeof f);
+  return RT_OK;
+}
+
+// One wide LCNetV3 block (K x K depthwise [-> squeeze-excite] -> 1x1 conv + hardswish) through the networks' run_lc on host arrays
+// (tests/test_gpu_dw_kernels.py compares it with an fp64 block): what rt_debug_lc_block cannot express -- K = 5, squeeze-excite
+// weights (the host-array get_se, b.se = true), the depthwise form (g_dw_sweep) under GEMM variant 0, and the depthwise buffer y1
+// handed to run_lc returned beside the output.  What ran is reported from run_lc's own plan and trace, not recomputed.  Every
+// argument is checked with its own message before any device work; the session is looked at last.
+RT_API int rt_debug_lc_wide(rt_session* s, const float* x, const int* heights, const int* widths, int n_img, int K, int cin, int cout,
+                            int sh, int sw, const float* dw_w, const float* dw_bias, const float* pw_w, const float* pw_bias, int dw_act,
+                            int dw_has_lab, float dw_a, float dw_c, int pw_has_lab, float pw_a, float pw_c, const float* fc1_w,
+                            const float* fc1_b, const float* fc2_w, const float* fc2_b, int dw_form, float* out, long long out_len,
+                            float* y1_out, long long y1_len, float* scale_out, long long scale_len, int* info_out) {
+  RT_REQUIRE(x && heights && widths && dw_w && dw_bias && pw_w && pw_bias && out && y1_out && info_out, s, "rt_debug_lc_wide: null argument");
+  const bool se = fc1_w || fc1_b || fc2_w || fc2_b;
+  RT_REQUIRE(!se || (fc1_w && fc1_b && fc2_w && fc2_b && scale_out), s, "rt_debug_lc_wide: a squeeze-excite block needs both FCs and scale_out");
+  RT_REQUIRE(n_img > 0 && n_img <= 4096, s, "rt_debug_lc_wide: bad image count");
+  RT_REQUIRE(cin > 0 && cin <= 512 && cin % 4 == 0 && cout > 0 && cout <= 960, s, "rt_debug_lc_wide: bad channel counts (cin a multiple of 4 up to 512, cout up to 960)");
+  RT_REQUIRE((K == 3 || K == 5) && sh >= 1 && sh <= 2 && sw >= 1 && sw <= 2 && dw_act >= ACT_NONE && dw_act <= ACT_SIGMOID &&
+                 (dw_form == 0 || dw_form == 1), s, "rt_debug_lc_wide: no such block (K 3 or 5, strides 1 or 2, dw_form 0 or 1)");
+  for (int i = 0; i < n_img; i++)
+    RT_REQUIRE(heights[i] > 0 && widths[i] > 0 && heights[i] <= 4096 && widths[i] <= 65536, s, "rt_debug_lc_wide: empty or oversized image");
+  const int Cp = chan_pitch(cin), ldy = chan_pitch(cout);
+  const Ragged gi(heights, widths, n_img), go = gi.down(sh, sw);
+  RT_REQUIRE(gi.total * Cp < (1ll << 28) && go.total * ldy < (1ll << 28), s, "rt_debug_lc_wide: too large");
+  const long long out_n = (go.total + 64) * ldy, y1_n = (go.total + 64) * Cp, scale_n = se ? (long long)(n_img + 64) * Cp : 0;
+  RT_REQUIRE(out_len == out_n && y1_len == y1_n, s, "rt_debug_lc_wide: out or y1_out has the wrong length");
+  RT_REQUIRE(scale_len == scale_n, s, "rt_debug_lc_wide: scale_out has the wrong length");
+  RT_REQUIRE(s, s, "rt_debug_lc_wide: null session");
+  return guarded(s, [&] {
+    s->begin_call();
+    WeightStore ws;
+    LcBlock b;
+    b.dw = pack_dw(ws, dw_w, dw_bias, cin, K); b.dw_lab = Lab{dw_has_lab, dw_a, dw_c}; b.dw_act = dw_act;
+    b.se = se;
+    if (se) b.sew = get_se(ws, fc1_w, fc1_b, fc2_w, fc2_b, cin, cin / 4);
+    b.pw = pack_conv(ws, pw_w, pw_bias, cout, cin, 1, 1); b.pw_lab = Lab{pw_has_lab, pw_a, pw_c};
+    b.sh = sh; b.sw = sw; b.cin = cin; b.cout = cout;
+    std::vector<std::pair<int, int>> hw;
+    for (int i = 0; i < n_img; i++) hw.push_back({heights[i], widths[i]});
+    Level Li = make_level(hw), Lo = down_level(Li, sh, sw);
+    DevBufs bufs;
+    RestoreInt keep_form(nn::g_dw_sweep), keep_variant(nn::g_gemm_variant);
+    nn::g_dw_sweep = dw_form ? 4 : 0;
+    nn::g_gemm_variant = 0;   // (a forced variant takes no folded squeeze-excite form)
+    RunCtx c = s->ctx(&s->arena);
+    upload_levels(c, {&Li, &Lo});
+    const float* dx = bufs.upload(x, (size_t)Li.total * Cp);
+    float* dy = bufs.canary<float>((size_t)out_n, s->st);
+    // y1: 256 rows past the last pixel, as a GEMM tile reads past the end of its A rows (rows are independent: what they hold
+    // reaches no stored output); the first 64 of them are returned and must keep the canary
+    float* dy1 = bufs.canary<float>((size_t)(Lo.total + 256) * Cp, s->st);
+    const nn::LcPlan plan = lc_block_plan(b, Lo);
+    LcTrace tr;
+    run_lc(c, b, dx, Li, Lo, dy, dy1, &tr);
+    RT_HIP_CHECK(hipStreamSynchronize(s->st));
+    DevBufs::download(out, dy, (size_t)out_n);
+    DevBufs::download(y1_out, dy1, (size_t)y1_n);
+    if (se) {   // the scales [n_img][Cp], then 64 rows of the canary as the other buffers have them
+      const uint32_t cw = RT_DEBUG_CANARY;
+      for (long long i = 0; i < scale_n; i++) memcpy(scale_out + i, &cw, 4);
+      if (tr.scale) DevBufs::download(scale_out, tr.scale, (size_t)n_img * Cp);
+    }
+    const bool unfused = plan.route == nn::LC_UNFUSED;
+    const int f[16] = {(int)plan.route, unfused ? (int)plan.dw.kernel : 0, unfused ? plan.dw.inst : plan.inst, plan.dw.R, plan.dw.lanes,
+                       plan.dw.spb, plan.dw.chunks, (int)plan.dw.grid_x, (int)plan.dw.grid_z, plan.se_rows,
+                       unfused ? (int)tr.gemm.kernel : 0, unfused && tr.gemm.se ? 1 : 0, tr.scale ? (tr.scaled_in_place ? 2 : 1) : 0, 0, 0, 0};
+    memcpy(info_out, f, sizeof f);
   });
 }
 

@@ -261,7 +261,7 @@ nn::LcPlan lc_block_plan(const LcBlock& b, const Level& Lout) {
   return nn::lc_plan(s, make_epi(b.pw, ACT_HSWISH, &b.pw_lab));
 }
 
-float* run_lc(RunCtx& c, const LcBlock& b, const float* x, const Level& Lin, const Level& Lout, float* y2, float* y1) {
+float* run_lc(RunCtx& c, const LcBlock& b, const float* x, const Level& Lin, const Level& Lout, float* y2, float* y1, LcTrace* trace) {
   const nn::LcPlan plan = lc_block_plan(b, Lout);
   const int Cpo = chan_pitch(b.cout);
   Epilogue epi = make_epi(b.pw, ACT_HSWISH, &b.pw_lab);
@@ -294,11 +294,14 @@ float* run_lc(RunCtx& c, const LcBlock& b, const float* x, const Level& Lin, con
       dtab = dt;
     }
     epi.a_scale = scale; epi.ld_scale = b.dw.Cp; epi.a_tab = dtab; epi.a_tab_stride = stride; epi.n_img = Lout.n();
+    if (trace) trace->scale = scale;
   } else if (b.se) {
-    run_se(c, y1, Lout, b.sew, HSIG_LCNET, 0);
+    const float* scale = run_se(c, y1, Lout, b.sew, HSIG_LCNET, 0);
+    if (trace) { trace->scale = scale; trace->scaled_in_place = true; }
   }
   if (!y2) y2 = c.arena->alloc<float>((size_t)Lout.total * Cpo);
   const nn::GemmPlan gp = nn::gemm_plan(b.dw.Cp, Lout.total, b.pw.K, b.pw.N, b.pw.Npad, Cpo, 0, epi, stream_cus(c.st));
+  if (trace) trace->gemm = gp;
   { ProfScope ps(c.prof, c.st, gp.label, shape_str(Lout.total, b.pw.K, b.pw.N, 0));
     nn::gemm(c.st, gp, y1, b.dw.Cp, Lout.total, b.pw.K, b.pw.w, b.pw.N, b.pw.Npad, y2, Cpo, 0, epi); }
   return y2;

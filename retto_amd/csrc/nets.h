@@ -93,8 +93,15 @@ struct LcBlock {
 // The block on the kernels of its plan (nn::lc_plan for its shape on level Lout): x at Lin -> the block's output at Lout, pitch
 // chan_pitch(b.cout).  y = null: arena memory; y1: the depthwise output where the plan's route is nn::LC_UNFUSED (null: arena
 // memory; a GEMM tile reads rows past its end, which a caller's buffer must hold).
+// trace (diagnostics, rt_debug_lc_wide): what the unfused route did -- nothing it launches or allocates depends on it.
+struct LcTrace {
+  const float* scale = nullptr;   // the squeeze-excite scales [image][Cp] (arena memory), where the block has them
+  bool scaled_in_place = false;   // run_se multiplied them into y1; false: folded into the GEMM (or no squeeze-excite)
+  nn::GemmPlan gemm;              // the pointwise GEMM's plan
+};
 nn::LcPlan lc_block_plan(const LcBlock& b, const Level& Lout);
-float* run_lc(RunCtx& c, const LcBlock& b, const float* x, const Level& Lin, const Level& Lout, float* y = nullptr, float* y1 = nullptr);
+float* run_lc(RunCtx& c, const LcBlock& b, const float* x, const Level& Lin, const Level& Lout, float* y = nullptr, float* y1 = nullptr,
+              LcTrace* trace = nullptr);
 
 // The blocks of the three mobile networks (fp32 and fp16 builds of the same graphs)
 struct LcSpec { const char* name; int k, cin, cout, sh, sw; bool se; };

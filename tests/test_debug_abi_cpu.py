@@ -1,7 +1,7 @@
 """The kernel-level debug entry points rt_debug_gemm / rt_debug_attention (tests/test_gpu_ops.py drives them on the GPU) and
 rt_debug_lc_block / rt_debug_conv13 / rt_debug_layernorm (tests/test_gpu_rec_kernels.py) and rt_debug_glue16 / rt_debug_conv16x
 (tests/test_gpu_f16_kernels.py) and rt_debug_fpn (tests/test_gpu_fpn_kernels.py) and rt_debug_cls_block / rt_debug_stem /
-rt_debug_glue32 (tests/test_gpu_cls_kernels.py): declared, exported, and null or bad arguments rejected with RT_ERR_INVALID before
+rt_debug_glue32 (tests/test_gpu_cls_kernels.py) and rt_debug_dw_plan / rt_debug_lc_wide (tests/test_gpu_dw_kernels.py): declared, exported, and null or bad arguments rejected with RT_ERR_INVALID before
 any device work."""
 import ctypes as C
 import os
@@ -18,7 +18,8 @@ def test_debug_symbols_are_declared_and_exported():
     header = open(os.path.join(ROOT, "include", "retto_hip.h")).read()
     lib = _lib.load()
     for name in ("rt_debug_gemm", "rt_debug_attention", "rt_debug_lc_block", "rt_debug_conv13", "rt_debug_layernorm",
-                 "rt_debug_glue16", "rt_debug_conv16x", "rt_debug_fpn", "rt_debug_cls_block", "rt_debug_stem", "rt_debug_glue32"):
+                 "rt_debug_glue16", "rt_debug_conv16x", "rt_debug_fpn", "rt_debug_cls_block", "rt_debug_stem", "rt_debug_glue32",
+                 "rt_debug_dw_plan", "rt_debug_lc_wide"):
         assert "RT_API int %s(" % name in header
         assert name in _lib.EXPORTS
         assert hasattr(lib, name)
@@ -353,3 +354,50 @@ def test_cls_kernel_entries_reject_null_and_bad_arguments_without_a_device():
                   ({"x_len": 7 * 8 - 1}, lens), ({"out_len": (2 + 64) * 8 - 1}, lens), ({"out_len": 0}, lens),
                   (dict(soft, x_len=7), lens), (dict(amax, out_len=2 + 63), lens),
                   ({"out2": False}, second), ({"out2_len": (7 + 64) * 8 - 1}, second)])
+
+
+def _wide(lib, s=None, hs=(3, 2), ws=(5, 1), n_img=2, K=5, cin=192, cout=384, sh=1, sw=1, dw_act=2, se=1, form=1, null=None, info=True,
+          out_len=None, y1_len=None, scale_len=None):
+    """a 5x5 192 -> 384 block with squeeze-excite on two images of 15 and 2 pixels, unless the arguments say otherwise; null = the
+    name of a NULL operand"""
+    a = lambda *shape: np.zeros([max(v, 1) for v in shape], np.float32)   # noqa: E731
+    arr = {"x": a(17, 512), "hs": np.array(hs, np.int32), "ws": np.array(ws, np.int32), "dw_w": a(cin, 5, 5), "dw_b": a(cin), "pw_w": a(cout, cin),
+           "pw_b": a(cout), "fc1_w": a(cin, cin), "fc1_b": a(cin), "fc2_w": a(cin, cin), "fc2_b": a(cin), "out": a(17 + 64, 1024),
+           "y1": a(17 + 64, 512), "scale": a(2 + 64, 512)}
+    p = {k_: (None if k_ == null or (not se and k_.startswith(("fc", "scale"))) else v.ctypes.data) for k_, v in arr.items()}
+    pitch = lambda c: (c + 31) // 32 * 32 if c >= 128 else (c + 3) // 4 * 4   # noqa: E731
+    d = lambda v, dflt: dflt if v is None else v                             # noqa: E731
+    return lib.rt_debug_lc_wide(s, p["x"], p["hs"], p["ws"], n_img, K, cin, cout, sh, sw, p["dw_w"], p["dw_b"], p["pw_w"], p["pw_b"], dw_act, 1,
+                                1.3, 0.07, 1, 0.8, -0.05, p["fc1_w"], p["fc1_b"], p["fc2_w"], p["fc2_b"], form, p["out"],
+                                d(out_len, (17 + 64) * pitch(max(cout, 1))), p["y1"], d(y1_len, (17 + 64) * pitch(max(cin, 1))), p["scale"],
+                                d(scale_len, (2 + 64) * pitch(max(cin, 1)) if se else 0), (C.c_int * 16)() if info else None)
+
+
+def test_dw_kernel_entries_reject_null_and_bad_arguments_without_a_device():
+    """rt_debug_lc_wide looks at its session last, so every argument check answers with its own message (rt_last_error(NULL) holds
+    it); rt_debug_dw_plan takes no session at all and answers on the host"""
+    lib = _lib.load()
+    lib.rt_last_error.restype = C.c_char_p
+    null, se, count, chan, block, img, lens, slen = (
+        "null argument", "needs both FCs and scale_out", "bad image count", "bad channel counts", "no such block", "empty or oversized image",
+        "out or y1_out has the wrong length", "scale_out has the wrong length")
+    cases = ([({}, "null session"), ({"se": 0}, "null session"), ({"K": 3, "cin": 96, "cout": 96, "form": 0}, "null session"),
+              ({"sh": 2, "sw": 2, "hs": (6, 4), "ws": (5, 2), "out_len": (11 + 64) * 384, "y1_len": (11 + 64) * 192}, "null session")] +
+             [({"null": k}, null) for k in ("x", "hs", "ws", "dw_w", "dw_b", "pw_w", "pw_b", "out", "y1")] + [({"info": False}, null)] +
+             [({"null": k}, se) for k in ("fc1_w", "fc1_b", "fc2_w", "fc2_b", "scale")] +
+             [({"n_img": 0}, count), ({"n_img": 5000}, count), ({"cin": 0}, chan), ({"cin": 190}, chan), ({"cin": 516}, chan), ({"cout": 0}, chan),
+              ({"cout": 964}, chan), ({"K": 4}, block), ({"K": 7}, block), ({"sh": 0}, block), ({"sw": 3}, block), ({"dw_act": 9}, block),
+              ({"form": 2}, block), ({"form": -1}, block), ({"hs": (3, 0)}, img), ({"ws": (0, 1)}, img), ({"hs": (5000, 2)}, img),
+              ({"out_len": (17 + 64) * 384 - 1}, lens), ({"y1_len": 0}, lens), ({"scale_len": 0}, slen), ({"se": 0, "scale_len": 4}, slen)])
+    for kw, why in cases:
+        assert _wide(lib, **kw) == RT_ERR_INVALID, kw
+        assert why in lib.rt_last_error(None).decode(), (kw, lib.rt_last_error(None))
+    plan = (C.c_int * 8)()
+    for args, why in (((5, 1, 1, 256, 12, 100, 0, 1, None), "null argument"), ((5, 1, 1, 250, 12, 100, 0, 1, plan), "bad shape"),
+                      ((5, 1, 1, 256, 0, 100, 0, 1, plan), "bad shape"), ((5, 1, 1, 256, 12, 100, 0, 2, plan), "bad shape")):
+        assert lib.rt_debug_dw_plan(*args) == RT_ERR_INVALID, args
+        assert why in lib.rt_last_error(None).decode(), args
+    # the plan itself, on the host: the rec net's 12-row 5x5 layer as the sweep and as row strips, and a kernel size without an instance
+    assert lib.rt_debug_dw_plan(5, 1, 1, 256, 12, 800, 0, 1, plan) == 0 and tuple(plan) == (3, 1, 4, 16, 16, 38, 13, 4)
+    assert lib.rt_debug_dw_plan(5, 1, 1, 256, 12, 800, 0, 0, plan) == 0 and tuple(plan) == (2, 17093, 4, 16, 16, 38, 38, 4)
+    assert lib.rt_debug_dw_plan(7, 1, 1, 256, 12, 800, 0, 1, plan) == 0 and tuple(plan)[:2] == (0, 0)
