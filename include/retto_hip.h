@@ -384,9 +384,9 @@ RT_API int rt_debug_ctc_charset_host(const float* z5, const float* W, const floa
  *     posterior = exp(loglik - log-sum-exp over the line's feasible entries).
  * One limit: the lexicon lines that one rec group takes (about 24 M crop pixels) may carry 2^26 entries between them (1024 lines
  * of a 65536-entry lexicon); a call past it fails with RT_ERR_CAPACITY.
- * The line's tokens, score, text, word boxes, candidates and JSON stay what they are without the lexicon, bit for bit; replacing
- * the text by the winner and aligning it for word boxes are out of scope.  Lines without a lexicon cost nothing.  The reference
- * has no counterpart.
+ * The line's tokens, score, text, word boxes, candidates and JSON stay what they are without the lexicon, bit for bit, unless the
+ * caller switches the lexicon's snap on (rt_lexicon_set_snap below).  Lines without a lexicon cost nothing.  The reference has no
+ * counterpart.
  *
  * rt_lexicon_create: the entries are the lines of utf8 [len bytes] (split and trimmed as rt_parse_dictionary's lines; empty
  * lines skipped), read code point by code point, each the LOWEST class id whose whole dictionary entry is that code point (U+0020
@@ -422,6 +422,26 @@ RT_API int rt_run_regions_lexicons(rt_session* s, const uint8_t* const* rgb, con
 RT_API int rt_results_rec_lexicon(const rt_results* r, int page, int line, const rt_lexicon_match** m);
 /* the lexicon a line was scored against (0: none) */
 RT_API int rt_results_rec_lexicon_id(const rt_results* r, int page, int line);
+/* Lexicon snap: replace a line's decode by its aligned best entry (retto_amd/csrc/ctc_lexicon_align.h states the rule).  Off by
+ * default, switched on per lexicon: a line that carries the lexicon snaps iff min_posterior > 0, the line has at least one match
+ * and matches[0].posterior >= min_posterior (an fp32 comparison; a NaN never snaps).  Match 0 -- the forward winner -- is then
+ * aligned to the line's time steps by a CTC Viterbi pass on the GPU (raw logits, fp32, ties to the earlier state: alignments
+ * pack to the left) and the path replaces the line's per-step (class, probability) rows before the CTC decode: the line's
+ * tokens are the entry's ids, its text the entry's text, a token's time step the first frame of its run, its probability the
+ * FULL softmax's at that frame, the score their mean; word boxes, candidates (rank 0 is that pair; ranks >= 1 as without snap)
+ * and the JSON follow from the same rows.  With a charset on the same line the charset decodes first and a snap that fires
+ * replaces its rows; where it does not fire the charset's decode stands.  A line that does not snap, a line of a lexicon with
+ * min_posterior = 0 and a line without a lexicon are bit-identical to a call without snap, and the rt_lexicon_match lists are
+ * the same for every line.  With no lexicon that has snap on, nothing new is launched or allocated.
+ * Out of scope: snapping on rt_rec and rt_ctc_decode, a per-region threshold, sharing the logits with the charset pass, and
+ * aligning entries other than match 0.
+ * rt_lexicon_set_snap: min_posterior in [0, 1], 0 = never snap (the initial state); an unknown lexicon id, a NaN or a value
+ * outside [0, 1] -> RT_ERR_INVALID.  May be changed between calls; fails like rt_lexicon_create while tickets are in flight. */
+RT_API int rt_lexicon_set_snap(rt_session* s, int lexicon, float min_posterior);
+/* a lexicon's current min_posterior (0 for an unknown id) */
+RT_API float rt_lexicon_snap(const rt_session* s, int lexicon);
+/* 1 where the line's decode is its aligned best entry, else 0 (also for out-of-range arguments, a line with no lexicon, NULL) */
+RT_API int rt_results_rec_lexicon_snapped(const rt_results* r, int page, int line);
 /* What rt_lexicon_create compiles, GPU-free and sessionless: dict = dictionary file bytes (parsed as rt_parse_dictionary does).
  * ids_out [ids_cap] / lens_out [lens_cap]: the entries' class ids, entry after entry, and their lengths; *n_ids_out / *n_entries_out:
  * how many there are (also when a cap was too small: RT_ERR_INVALID then, nothing copied); *n_classes: the dictionary's class
@@ -446,6 +466,23 @@ RT_API int rt_debug_ctc_lexicon_host(const float* z5, const float* W, const floa
                                      int n_lines, const int32_t* line_lex, const int32_t* entry_ids, const int32_t* entry_lens,
                                      const int32_t* lex_first_entry, int n_lex, float* loglik_out, rt_lexicon_match* matches_out,
                                      int32_t* n_matches_out);
+/* The device path of the lexicon snap on host arrays: rt_debug_ctc_lexicon's, with k_ctc_lexicon_topk per chunk and
+ * k_ctc_lexicon_align behind it.  rt_debug_ctc_lexicon's arguments, and lex_min_post [n_lex]: each lexicon's min_posterior, in
+ * [0, 1]; idx [rows] / prob [rows], in and out: the lines' per-step rows, overwritten by the aligned path for the lines that
+ * snap -- rows of every other line come back untouched; snapped_out [n_lines]: 0 / 1 for every line of a lexicon, the caller's
+ * value kept for lines of lexicon 0; vit_out [n_lines]: the end state's fp32 Viterbi value in the raw-logit domain, written for
+ * snapped lines only.  loglik_out, matches_out, n_matches_out: exactly what rt_debug_ctc_lexicon returns. */
+RT_API int rt_debug_ctc_lexicon_align(rt_session* s, const float* z5, const float* W, const float* bias, int N,
+                                      const int32_t* tokens_per_line, int n_lines, const int32_t* line_lex, const int32_t* entry_ids,
+                                      const int32_t* entry_lens, const int32_t* lex_first_entry, int n_lex, const float* lex_min_post,
+                                      int chunk_rows, int32_t* idx, float* prob, int32_t* snapped_out, float* vit_out,
+                                      float* loglik_out, rt_lexicon_match* matches_out, int32_t* n_matches_out);
+/* The same rule on the CPU in plain fp32 loops (ctc_lexicon_align.h), GPU-free and sessionless; same layout. */
+RT_API int rt_debug_ctc_lexicon_align_host(const float* z5, const float* W, const float* bias, int N, const int32_t* tokens_per_line,
+                                           int n_lines, const int32_t* line_lex, const int32_t* entry_ids, const int32_t* entry_lens,
+                                           const int32_t* lex_first_entry, int n_lex, const float* lex_min_post, int32_t* idx,
+                                           float* prob, int32_t* snapped_out, float* vit_out, float* loglik_out,
+                                           rt_lexicon_match* matches_out, int32_t* n_matches_out);
 /* f32 sum of every det probability map produced in the call (keeps the network's
  * output observable when det_map_override is used) */
 RT_API double rt_results_det_checksum(const rt_results* r);

@@ -193,6 +193,9 @@ class RecProcessorSingleResult:
     # rec lexicons (create_lexicon): None when the line carried no lexicon, else up to LEXICON_MATCHES (entry, text, loglik,
     # posterior), best first: the lexicon's entries ranked by their CTC forward log-likelihood under the line's own distribution
     lexicon_matches: Optional[List[Tuple[int, str, float, float]]] = None
+    # lexicon snap (set_lexicon_snap): None when the line carried no lexicon, else whether the line's text, tokens, score, words
+    # and candidates are those of its best entry (lexicon_matches[0]) aligned to the line, instead of the greedy decode
+    lexicon_snapped: Optional[bool] = None
 
 
 @dataclass
@@ -602,8 +605,10 @@ class RettoSession:
             toks = np.ctypeslib.as_array(tp, (nt,)).copy() if nt else np.zeros(0, np.int32)
             words = self._words(r, page, k) if self.config.rec_processor_config.return_word_box else None
             cands, cols = self._candidates(r, page, k, nt)
+            matches = self._lexicon_matches(r, page, k)
+            snapped = None if matches is None else bool(lib.rt_results_rec_lexicon_snapped(r, page, k))
             rec.append(RecProcessorSingleResult(lib.rt_results_rec_text(r, page, k).decode("utf-8"), float(rs[k]), toks, words,
-                                                cands, cols, self._lexicon_matches(r, page, k)))
+                                                cands, cols, matches, snapped))
         return RettoWorkerResult(det, cls, rec)
 
     def _dictionary(self) -> List[str]:
@@ -694,6 +699,16 @@ class RettoSession:
     def set_rec_lexicon(self, lexicon: int) -> None:
         """rt_set_rec_lexicon: the lexicon of every line of the pipeline calls that follow; 0 = none."""
         _check(self._hd.lib.rt_set_rec_lexicon(self._hd.h, int(lexicon)), self._hd.h)
+
+    def set_lexicon_snap(self, lexicon: int, min_posterior: float) -> None:
+        """rt_lexicon_set_snap: from the next call on, a line that carries this lexicon and whose best entry's posterior reaches
+        min_posterior takes that entry, aligned to its time steps, as its decode (RecProcessorSingleResult.lexicon_snapped;
+        retto_amd/csrc/ctc_lexicon_align.h).  min_posterior in [0, 1]; 0 (the initial state) never snaps."""
+        _check(self._hd.lib.rt_lexicon_set_snap(self._hd.h, int(lexicon), float(min_posterior)), self._hd.h)
+
+    def lexicon_snap(self, lexicon: int) -> float:
+        """rt_lexicon_snap: the lexicon's current min_posterior (0.0 for an unknown id)."""
+        return float(self._hd.lib.rt_lexicon_snap(self._hd.h, int(lexicon)))
 
     def run_regions_raw(self, pages, hs, ws, quads, mem=RT_MEM_HOST, charsets=None, lexicons=None):
         """rt_run_regions.  pages: host arrays or device pointers (ints); quads[i]: the regions of page i, anything that

@@ -85,6 +85,8 @@ EXPORTS = [
     "rt_lexicon_create", "rt_lexicon_entries", "rt_lexicon_entry", "rt_lexicon_entry_text", "rt_set_rec_lexicon",
     "rt_run_regions_lexicons", "rt_results_rec_lexicon", "rt_results_rec_lexicon_id", "rt_debug_lexicon_compile",
     "rt_debug_ctc_lexicon", "rt_debug_ctc_lexicon_host",
+    "rt_lexicon_set_snap", "rt_lexicon_snap", "rt_results_rec_lexicon_snapped", "rt_debug_ctc_lexicon_align",
+    "rt_debug_ctc_lexicon_align_host",
 ]
 
 STAGE_CALLBACK = C.CFUNCTYPE(None, C.c_void_p, C.c_int, C.c_int, C.c_char_p)  # rt_stage_callback
@@ -263,5 +265,15 @@ def load():
                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.rt_debug_ctc_lexicon_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
                                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.rt_lexicon_set_snap.argtypes = [C.c_void_p, C.c_int, C.c_float]
+    lib.rt_lexicon_snap.argtypes = [C.c_void_p, C.c_int]
+    lib.rt_lexicon_snap.restype = C.c_float
+    lib.rt_results_rec_lexicon_snapped.argtypes = [C.c_void_p, C.c_int, C.c_int]
+    lib.rt_debug_ctc_lexicon_align.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int,
+                                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int,
+                                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.rt_debug_ctc_lexicon_align_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
+                                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     _lib = lib
     return lib

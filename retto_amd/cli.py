@@ -46,7 +46,10 @@ def build_parser() -> argparse.ArgumentParser:
                          "dictionary classes whose whole entry is one character of TEXT, plus the blank")
     ap.add_argument("--rec-lexicon", default=None, metavar="FILE",
                     help="a word list, one entry per line: every line's result also ranks these entries by their CTC forward "
-                         "log-likelihood (one lexicon, made the session default; the recognised text itself is unchanged)")
+                         "log-likelihood (one lexicon, made the session default; the recognised text itself is unchanged unless --rec-lexicon-snap is given)")
+    ap.add_argument("--rec-lexicon-snap", type=float, default=None, metavar="P",
+                    help="with --rec-lexicon: a line whose best entry's posterior reaches P (0 < P <= 1) takes that entry, "
+                         "aligned to its time steps, as its text, score, words and candidates (\"lexicon_snapped\" per line)")
     return ap
 
 
@@ -81,7 +84,12 @@ def main(argv=None) -> int:
         session.set_rec_charset(session.create_charset(a.rec_charset))
     if a.rec_lexicon is not None:
         with open(a.rec_lexicon, "rb") as f:
-            session.set_rec_lexicon(session.create_lexicon(f.read()))
+            lexicon = session.create_lexicon(f.read())
+        if a.rec_lexicon_snap is not None:
+            session.set_lexicon_snap(lexicon, a.rec_lexicon_snap)
+        session.set_rec_lexicon(lexicon)
+    elif a.rec_lexicon_snap is not None:
+        raise SystemExit("--rec-lexicon-snap needs --rec-lexicon")
     files = walk_files(a.images)
     log.info("Found %d files, processing...", len(files))
     out = open(a.json, "w") if a.json else None
@@ -114,6 +122,8 @@ def main(argv=None) -> int:
                 if a.rec_lexicon is not None:   # per line: up to 4 {entry, text, loglik, posterior}, best first
                     rec["lexicon_matches"] = [[{"entry": e, "text": s, "loglik": ll, "posterior": p}
                                                for e, s, ll, p in (t.lexicon_matches or [])] for t in r.rec_result]
+                    if a.rec_lexicon_snap is not None:   # per line: whether its text is its aligned best entry
+                        rec["lexicon_snapped"] = [bool(t.lexicon_snapped) for t in r.rec_result]
                 out.write(json.dumps(rec, ensure_ascii=False) + "\n")
     dur = time.perf_counter() - start
     if out:

@@ -1,6 +1,6 @@
 // extern "C" surface of libretto_hip.so (include/retto_hip.h): sessions, the networks, the pipeline stages, batches, results,
 // parsers and device memory, with the feature-level debug hooks that are thin forwards into their features (rt_debug_warp_crops,
-// rt_debug_jpeg_reconstruct, rt_debug_word_boxes, rt_debug_ctc_candidates_host, rt_debug_charset_compile, rt_debug_ctc_charset_host, rt_debug_lexicon_compile, rt_debug_ctc_lexicon_host).  The kernel-level diagnostics (rt_debug_set_variants,
+// rt_debug_jpeg_reconstruct, rt_debug_word_boxes, rt_debug_ctc_candidates_host, rt_debug_charset_compile, rt_debug_ctc_charset_host, rt_debug_lexicon_compile, rt_debug_ctc_lexicon_host, rt_debug_ctc_lexicon_align_host).  The kernel-level diagnostics (rt_debug_set_variants,
 // rt_bench_*, and the rt_debug_* harnesses the kernel tests drive) are in api_debug.cpp; api_internal.h holds what both share.
 #include <thread>
 #include <sched.h>
@@ -90,6 +90,14 @@ std::string rt::lexicon_args_error(const float* z5, const float* W, int N, const
   if (rows >= (1ll << 30)) return "the lines have " + S(rows) + " time steps, 2^30 or more";
   if (table >= (1ll << 30)) return "the loglik table has " + S(table) + " floats, 2^30 or more";
   *rows_out = rows; *table_out = table;
+  return std::string();
+}
+std::string rt::lexicon_align_args_error(const float* lex_min_post, int n_lex, const int32_t* idx, const float* prob,
+                                         const int32_t* snapped_out, const float* vit_out) {
+  if (!lex_min_post || !idx || !prob || !snapped_out || !vit_out) return "a required pointer is null";
+  for (int k = 0; k < n_lex; k++)
+    if (!(lex_min_post[k] >= 0.0f && lex_min_post[k] <= 1.0f))
+      return "lex_min_post[" + std::to_string(k) + "] = " + std::to_string(lex_min_post[k]) + " is outside [0, 1]";
   return std::string();
 }
 
@@ -336,6 +344,13 @@ int rt_set_rec_lexicon(rt_session* s, int lexicon) {
       throw RtError(RT_ERR_INVALID, "rt_set_rec_lexicon: unknown lexicon id " + std::to_string(lexicon));
     s->rec_lexicon = lexicon;
   });
+}
+int rt_lexicon_set_snap(rt_session* s, int lexicon, float min_posterior) {
+  RT_REQUIRE(s, s, "rt_lexicon_set_snap: null session");
+  return guarded(s, [&] { s->lexicon_set_snap(lexicon, min_posterior); });
+}
+float rt_lexicon_snap(const rt_session* s, int lexicon) {
+  return lexicon_of(s, lexicon) ? s->lexicons->snap[lexicon - 1] : 0.0f;
 }
 int rt_submit_batch(rt_session* s, const uint8_t* const* rgb, const int* hs, const int* ws, int n_pages, int mem,
                     const float* const* det_map_override, rt_ticket** out) {
@@ -713,6 +728,11 @@ int rt_results_rec_lexicon_id(const rt_results* r, int page, int line) {
   if (!p || line < 0 || (size_t)line >= p->lex_id.size()) return 0;
   return p->lex_id[(size_t)line];
 }
+int rt_results_rec_lexicon_snapped(const rt_results* r, int page, int line) {
+  auto* p = RT_PAGE(r, page);
+  if (!p || line < 0 || (size_t)line >= p->lex_snapped.size()) return 0;
+  return p->lex_snapped[(size_t)line];
+}
 int rt_debug_lexicon_compile(const void* dict, size_t dict_len, const char* utf8, size_t len, const int32_t* ids,
                              const int32_t* entry_lens, int n_id_entries, int32_t* ids_out, int ids_cap, int32_t* lens_out,
                              int lens_cap, int* n_ids_out, int* n_entries_out, int* n_classes, char* err, size_t err_cap) {
@@ -744,17 +764,11 @@ int rt_debug_lexicon_compile(const void* dict, size_t dict_len, const char* utf8
     return RT_ERR_BACKEND;
   }
 }
-int rt_debug_ctc_lexicon_host(const float* z5, const float* W, const float* bias, int N, const int32_t* tokens_per_line,
-                              int n_lines, const int32_t* line_lex, const int32_t* entry_ids, const int32_t* entry_lens,
-                              const int32_t* lex_first_entry, int n_lex, float* loglik_out, rt_lexicon_match* matches_out,
-                              int32_t* n_matches_out) {
-  long long rows = 0, table = 0;
-  const std::string bad = lexicon_args_error(z5, W, N, tokens_per_line, n_lines, line_lex, entry_ids, entry_lens, lex_first_entry, n_lex,
-                                             matches_out, n_matches_out, &rows, &table);
-  if (!bad.empty()) {
-    rt::create_error() = "rt_debug_ctc_lexicon_host: " + bad;
-    return RT_ERR_INVALID;
-  }
+// both rt_debug_ctc_lexicon*_host forms, arguments already checked; lex_min_post null: the lexicon rule alone
+static int lexicon_host(const float* z5, const float* W, const float* bias, int N, const int32_t* tokens_per_line, int n_lines,
+                        const int32_t* line_lex, const int32_t* entry_ids, const int32_t* entry_lens, const int32_t* lex_first_entry,
+                        int n_lex, float* loglik_out, rt_lexicon_match* matches_out, int32_t* n_matches_out,
+                        const float* lex_min_post, int32_t* idx, float* prob, int32_t* snapped_out, float* vit_out) {
   try {
     const int D = 120;
     std::vector<long long> id_off((size_t)lex_first_entry[n_lex] + 1, 0);
@@ -774,9 +788,17 @@ int rt_debug_ctc_lexicon_host(const float* z5, const float* W, const float* bias
         row.assign((size_t)n, 0.0f);
         for (int e = 0; e < n; e++)
           row[(size_t)e] = lx::entry_loglik(logits.data(), N, lse.data(), T, entry_ids + id_off[(size_t)(e0 + e)], entry_lens[e0 + e]);
+        const lx::Match* m = reinterpret_cast<lx::Match*>(matches_out) + (size_t)i * lx::MATCHES;
         n_matches_out[i] = lx::line_matches(row.data(), n, reinterpret_cast<lx::Match*>(matches_out) + (size_t)i * lx::MATCHES);
         if (loglik_out) memcpy(loglik_out + out, row.data(), (size_t)n * sizeof(float));
         out += n;
+        if (lex_min_post) {   // lexicon snap (ctc_lexicon_align.h); m[0] is read only where the line has a match
+          const bool fire = la::snaps(lex_min_post[line_lex[i] - 1], n_matches_out[i], n_matches_out[i] >= 1 ? m[0].posterior : 0.0f);
+          snapped_out[i] = fire ? 1 : 0;
+          if (fire)
+            vit_out[i] = la::align_line(logits.data(), N, lse.data(), T, entry_ids + id_off[(size_t)(e0 + m[0].entry)],
+                                        entry_lens[e0 + m[0].entry], idx + o, prob + o);
+        }
       }
       o += T;
     }
@@ -784,6 +806,36 @@ int rt_debug_ctc_lexicon_host(const float* z5, const float* W, const float* bias
   } catch (const std::exception&) {
     return RT_ERR_BACKEND;
   }
+}
+int rt_debug_ctc_lexicon_host(const float* z5, const float* W, const float* bias, int N, const int32_t* tokens_per_line,
+                              int n_lines, const int32_t* line_lex, const int32_t* entry_ids, const int32_t* entry_lens,
+                              const int32_t* lex_first_entry, int n_lex, float* loglik_out, rt_lexicon_match* matches_out,
+                              int32_t* n_matches_out) {
+  long long rows = 0, table = 0;
+  const std::string bad = lexicon_args_error(z5, W, N, tokens_per_line, n_lines, line_lex, entry_ids, entry_lens, lex_first_entry, n_lex,
+                                             matches_out, n_matches_out, &rows, &table);
+  if (!bad.empty()) {
+    rt::create_error() = "rt_debug_ctc_lexicon_host: " + bad;
+    return RT_ERR_INVALID;
+  }
+  return lexicon_host(z5, W, bias, N, tokens_per_line, n_lines, line_lex, entry_ids, entry_lens, lex_first_entry, n_lex, loglik_out,
+                      matches_out, n_matches_out, nullptr, nullptr, nullptr, nullptr, nullptr);
+}
+int rt_debug_ctc_lexicon_align_host(const float* z5, const float* W, const float* bias, int N, const int32_t* tokens_per_line,
+                                    int n_lines, const int32_t* line_lex, const int32_t* entry_ids, const int32_t* entry_lens,
+                                    const int32_t* lex_first_entry, int n_lex, const float* lex_min_post, int32_t* idx, float* prob,
+                                    int32_t* snapped_out, float* vit_out, float* loglik_out, rt_lexicon_match* matches_out,
+                                    int32_t* n_matches_out) {
+  long long rows = 0, table = 0;
+  std::string bad = lexicon_args_error(z5, W, N, tokens_per_line, n_lines, line_lex, entry_ids, entry_lens, lex_first_entry, n_lex,
+                                       matches_out, n_matches_out, &rows, &table);
+  if (bad.empty()) bad = lexicon_align_args_error(lex_min_post, n_lex, idx, prob, snapped_out, vit_out);
+  if (!bad.empty()) {
+    rt::create_error() = "rt_debug_ctc_lexicon_align_host: " + bad;
+    return RT_ERR_INVALID;
+  }
+  return lexicon_host(z5, W, bias, N, tokens_per_line, n_lines, line_lex, entry_ids, entry_lens, lex_first_entry, n_lex, loglik_out,
+                      matches_out, n_matches_out, lex_min_post, idx, prob, snapped_out, vit_out);
 }
 double rt_results_det_checksum(const rt_results* r) { return r ? r->det_checksum : 0.0; }
 const char* rt_results_json(rt_results* r, int page, int stage) {

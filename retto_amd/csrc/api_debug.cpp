@@ -1,6 +1,6 @@
 // Kernel-level diagnostics of libretto_hip.so (include/retto_hip.h, diagnostics section): the A/B switches of tools/, the kernel
 // micro-benchmarks (rt_bench_*), and one harness per kernel family that runs a single launch on host arrays for the fp64 tests
-// (rt_debug_gemm, _dwconv, _dw_plan, _attention, _ctc_candidates, _ctc_charset, _ctc_lexicon, _lc_block, _lc_wide, _conv13, _layernorm, _conv16, _glue16, _fpn, _conv16x, _cls_block, _stem, _glue32).
+// (rt_debug_gemm, _dwconv, _dw_plan, _attention, _ctc_candidates, _ctc_charset, _ctc_lexicon, _ctc_lexicon_align, _lc_block, _lc_wide, _conv13, _layernorm, _conv16, _glue16, _fpn, _conv16x, _cls_block, _stem, _glue32).
 // None of it runs in production, and every kernel test depends on it.  A harness has one shape: check the arguments (each
 // failure with its own message, before any device work), lay the ragged lists out (Ragged), put the operands on the device
 // (DevBufs::upload / zeroed, upload_as), fill what the kernel writes with RT_DEBUG_CANARY and spare rows (DevBufs::canary),
@@ -473,7 +473,77 @@ RT_API int rt_debug_ctc_charset(rt_session* s, const float* z5, const float* W, 
 }
 
 // Rec lexicons' device path (rt_session::ctc_lexicon: what rec_groups runs per group) on host arrays; the lines, their rows and
-// the lexicon tables are built as there and by rt_lexicon_create (lx::Tables).
+// the lexicon tables are built as there and by rt_lexicon_create (lx::Tables).  With lex_min_post (lexicon snap,
+// ctc_lexicon_align.h) also the caller's idx / prob rows, in and out, the flags and the Viterbi values; a threshold above 0 on
+// the lexicon of some line takes ctc_lexicon's snap path (top-K per chunk, k_ctc_lexicon_align), as rec_groups does.
+static void debug_ctc_lexicon(rt_session* s, const float* z5, const float* W, const float* bias, int N, const int32_t* tokens_per_line,
+                              int n_lines, const int32_t* line_lex, const int32_t* entry_ids, const int32_t* entry_lens,
+                              const int32_t* lex_first_entry, int n_lex, int chunk_rows, long long rows, long long table,
+                              float* loglik_out, rt_lexicon_match* matches_out, int32_t* n_matches_out, const float* lex_min_post,
+                              int32_t* idx, float* prob, int32_t* snapped_out, float* vit_out) {
+  s->begin_call();
+  const size_t nr = (size_t)std::max<long long>(rows, 1);
+  WeightStore ws;
+  SvtrCore core;
+  core.classes = N;
+  core.fc = pack_linear(ws, W, bias, core.D, N);
+  DevBufs bufs;
+  // (the features sit inside a larger allocation, as z5 does inside the scratch arena)
+  float* dz = bufs.zeroed<float>((nr + 256) * core.D);
+  DevBufs::put(dz, z5, (size_t)rows * core.D);
+  lx::Tables tb;
+  long long io = 0;
+  for (int k = 0; k < n_lex; k++) {
+    const int e0 = lex_first_entry[k], n = lex_first_entry[k + 1] - e0;
+    tb.add(entry_ids + io, entry_lens + e0, n);
+    for (int j = 0; j < n; j++) io += entry_lens[e0 + j];
+  }
+  std::vector<lx::Line> lines; std::vector<int> lrows;
+  long long o = 0, out = 0; int max_waves = 0; bool any_snap = false;
+  for (int i = 0; i < n_lines; i++) {
+    const int T = tokens_per_line[i];
+    if (line_lex[i] > 0) {
+      const lx::Lex& x = tb.lex[(size_t)line_lex[i] - 1];
+      lines.push_back(lx::Line{(int)lrows.size(), T, line_lex[i] - 1, i, out});
+      for (int t = 0; t < T; t++) lrows.push_back((int)(o + t));
+      out += x.n; max_waves = std::max(max_waves, lx::waves_of(x));
+      if (lex_min_post) {   // (the kernel, where it runs, writes every lexicon line's flag again)
+        any_snap |= lex_min_post[line_lex[i] - 1] > 0.0f;
+        snapped_out[i] = 0;
+      }
+    } else n_matches_out[i] = 0;
+    o += T;
+  }
+  if (lines.empty()) return;
+  const lx::Line* dlines = bufs.upload(lines.data(), lines.size());
+  const int* drows = lrows.empty() ? bufs.alloc<int>(1) : bufs.upload(lrows.data(), lrows.size());
+  const int32_t* dids = bufs.upload(tb.ids.data(), tb.ids.size());
+  const lx::Entry* dent = bufs.upload(tb.entries.data(), tb.entries.size());
+  const int32_t* dord = bufs.upload(tb.order.data(), tb.order.size());
+  const lx::Lex* dlex = bufs.upload(tb.lex.data(), tb.lex.size());
+  // (what the kernels write starts as the caller's values: a slot they leave alone comes back untouched)
+  float* dll = bufs.alloc<float>((size_t)table);
+  if (loglik_out) DevBufs::put(dll, loglik_out, (size_t)table);
+  lx::Match* dm = bufs.upload(reinterpret_cast<const lx::Match*>(matches_out), (size_t)n_lines * lx::MATCHES);
+  int* dn = bufs.upload(n_matches_out, (size_t)n_lines);
+  rt_session::LexSnap snap{nullptr, nullptr, nullptr, nullptr, nullptr};
+  if (any_snap) {
+    snap.d_min_post = bufs.upload(lex_min_post, (size_t)n_lex);
+    snap.idx = bufs.alloc<int>(nr); snap.prob = bufs.alloc<float>(nr);
+    DevBufs::put(snap.idx, idx, (size_t)rows); DevBufs::put(snap.prob, prob, (size_t)rows);
+    snap.snapped = bufs.upload(snapped_out, (size_t)n_lines); snap.vit = bufs.upload(vit_out, (size_t)n_lines);
+  }
+  s->ctc_lexicon(core, dz, lines.data(), dlines, (int)lines.size(), drows, (int)lrows.size(), max_waves, dlex, dent, dord, dids,
+                 chunk_rows, dll, dm, dn, any_snap ? &snap : nullptr);
+  RT_HIP_CHECK(hipStreamSynchronize(s->st));
+  if (loglik_out) DevBufs::download(loglik_out, dll, (size_t)table);
+  DevBufs::download(reinterpret_cast<lx::Match*>(matches_out), dm, (size_t)n_lines * lx::MATCHES);
+  DevBufs::download(n_matches_out, dn, (size_t)n_lines);
+  if (any_snap) {
+    DevBufs::download(idx, snap.idx, (size_t)rows); DevBufs::download(prob, snap.prob, (size_t)rows);
+    DevBufs::download(snapped_out, snap.snapped, (size_t)n_lines); DevBufs::download(vit_out, snap.vit, (size_t)n_lines);
+  }
+}
 RT_API int rt_debug_ctc_lexicon(rt_session* s, const float* z5, const float* W, const float* bias, int N,
                                 const int32_t* tokens_per_line, int n_lines, const int32_t* line_lex, const int32_t* entry_ids,
                                 const int32_t* entry_lens, const int32_t* lex_first_entry, int n_lex, int chunk_rows,
@@ -485,53 +555,25 @@ RT_API int rt_debug_ctc_lexicon(rt_session* s, const float* z5, const float* W, 
   RT_REQUIRE(bad.empty(), s, "rt_debug_ctc_lexicon: " + bad);
   RT_REQUIRE(chunk_rows >= 0, s, "rt_debug_ctc_lexicon: chunk_rows is negative");
   return guarded(s, [&] {
-    s->begin_call();
-    const size_t nr = (size_t)std::max<long long>(rows, 1);
-    WeightStore ws;
-    SvtrCore core;
-    core.classes = N;
-    core.fc = pack_linear(ws, W, bias, core.D, N);
-    DevBufs bufs;
-    // (the features sit inside a larger allocation, as z5 does inside the scratch arena)
-    float* dz = bufs.zeroed<float>((nr + 256) * core.D);
-    DevBufs::put(dz, z5, (size_t)rows * core.D);
-    lx::Tables tb;
-    long long io = 0;
-    for (int k = 0; k < n_lex; k++) {
-      const int e0 = lex_first_entry[k], n = lex_first_entry[k + 1] - e0;
-      tb.add(entry_ids + io, entry_lens + e0, n);
-      for (int j = 0; j < n; j++) io += entry_lens[e0 + j];
-    }
-    std::vector<lx::Line> lines; std::vector<int> lrows;
-    long long o = 0, out = 0; int max_waves = 0;
-    for (int i = 0; i < n_lines; i++) {
-      const int T = tokens_per_line[i];
-      if (line_lex[i] > 0) {
-        const lx::Lex& x = tb.lex[(size_t)line_lex[i] - 1];
-        lines.push_back(lx::Line{(int)lrows.size(), T, line_lex[i] - 1, i, out});
-        for (int t = 0; t < T; t++) lrows.push_back((int)(o + t));
-        out += x.n; max_waves = std::max(max_waves, lx::waves_of(x));
-      } else n_matches_out[i] = 0;
-      o += T;
-    }
-    if (lines.empty()) return;
-    const lx::Line* dlines = bufs.upload(lines.data(), lines.size());
-    const int* drows = lrows.empty() ? bufs.alloc<int>(1) : bufs.upload(lrows.data(), lrows.size());
-    const int32_t* dids = bufs.upload(tb.ids.data(), tb.ids.size());
-    const lx::Entry* dent = bufs.upload(tb.entries.data(), tb.entries.size());
-    const int32_t* dord = bufs.upload(tb.order.data(), tb.order.size());
-    const lx::Lex* dlex = bufs.upload(tb.lex.data(), tb.lex.size());
-    // (what the kernels write starts as the caller's values: a slot they leave alone comes back untouched)
-    float* dll = bufs.alloc<float>((size_t)table);
-    if (loglik_out) DevBufs::put(dll, loglik_out, (size_t)table);
-    lx::Match* dm = bufs.upload(reinterpret_cast<const lx::Match*>(matches_out), (size_t)n_lines * lx::MATCHES);
-    int* dn = bufs.upload(n_matches_out, (size_t)n_lines);
-    s->ctc_lexicon(core, dz, lines.data(), dlines, (int)lines.size(), drows, (int)lrows.size(), max_waves, dlex, dent, dord, dids,
-                   chunk_rows, dll, dm, dn);
-    RT_HIP_CHECK(hipStreamSynchronize(s->st));
-    if (loglik_out) DevBufs::download(loglik_out, dll, (size_t)table);
-    DevBufs::download(reinterpret_cast<lx::Match*>(matches_out), dm, (size_t)n_lines * lx::MATCHES);
-    DevBufs::download(n_matches_out, dn, (size_t)n_lines);
+    debug_ctc_lexicon(s, z5, W, bias, N, tokens_per_line, n_lines, line_lex, entry_ids, entry_lens, lex_first_entry, n_lex, chunk_rows,
+                      rows, table, loglik_out, matches_out, n_matches_out, nullptr, nullptr, nullptr, nullptr, nullptr);
+  });
+}
+RT_API int rt_debug_ctc_lexicon_align(rt_session* s, const float* z5, const float* W, const float* bias, int N,
+                                      const int32_t* tokens_per_line, int n_lines, const int32_t* line_lex, const int32_t* entry_ids,
+                                      const int32_t* entry_lens, const int32_t* lex_first_entry, int n_lex, const float* lex_min_post,
+                                      int chunk_rows, int32_t* idx, float* prob, int32_t* snapped_out, float* vit_out,
+                                      float* loglik_out, rt_lexicon_match* matches_out, int32_t* n_matches_out) {
+  long long rows = 0, table = 0;
+  RT_REQUIRE(s, s, "rt_debug_ctc_lexicon_align: null session");
+  std::string bad = lexicon_args_error(z5, W, N, tokens_per_line, n_lines, line_lex, entry_ids, entry_lens, lex_first_entry, n_lex,
+                                       matches_out, n_matches_out, &rows, &table);
+  if (bad.empty()) bad = lexicon_align_args_error(lex_min_post, n_lex, idx, prob, snapped_out, vit_out);
+  RT_REQUIRE(bad.empty(), s, "rt_debug_ctc_lexicon_align: " + bad);
+  RT_REQUIRE(chunk_rows >= 0, s, "rt_debug_ctc_lexicon_align: chunk_rows is negative");
+  return guarded(s, [&] {
+    debug_ctc_lexicon(s, z5, W, bias, N, tokens_per_line, n_lines, line_lex, entry_ids, entry_lens, lex_first_entry, n_lex, chunk_rows,
+                      rows, table, loglik_out, matches_out, n_matches_out, lex_min_post, idx, prob, snapped_out, vit_out);
   });
 }
 

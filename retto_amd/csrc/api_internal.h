@@ -31,6 +31,9 @@ std::string lexicon_args_error(const float* z5, const float* W, int N, const int
                                const int32_t* line_lex, const int32_t* entry_ids, const int32_t* entry_lens,
                                const int32_t* lex_first_entry, int n_lex, const rt_lexicon_match* matches_out,
                                const int32_t* n_matches_out, long long* rows_out, long long* table_out);
+// what both rt_debug_ctc_lexicon_align forms require beyond lexicon_args_error (n_lex already checked), likewise
+std::string lexicon_align_args_error(const float* lex_min_post, int n_lex, const int32_t* idx, const float* prob,
+                                     const int32_t* snapped_out, const float* vit_out);
 
 // A call that fails after work was enqueued must not leave kernels or H2D copies in flight: the next
 // begin_call() rewinds the pinned staging and the arenas they read.  Errors of the drain itself are dropped

@@ -24,9 +24,9 @@
 //             (entry, loglik, posterior), posterior = expf(loglik - LSE over the line's feasible entries) (posterior_of()).
 //             Fewer feasible entries give fewer matches, none gives 0.
 // Everything else of the line -- tokens, score, text, word boxes, candidates, JSON -- is what it is without the lexicon, bit for
-// bit: nothing here writes a value the decode reads.  Out of scope: replacing the line's text by the winner, and a Viterbi
-// alignment of the winner for word boxes.  Lines of lexicon 0 (none) take no part: no row of theirs is gathered, no launch sees
-// them, no value of theirs is written.
+// bit: nothing here writes a value the decode reads.  Out of scope here; the Viterbi alignment of the winner, and replacing the
+// line's decode by it where the caller switched that on (rt_lexicon_set_snap), live in ctc_lexicon_align.h.  Lines of lexicon 0
+// (none) take no part: no row of theirs is gathered, no launch sees them, no value of theirs is written.
 //
 // Device layout (Tables).  Entries of all lexicons sit in one flat list; lexicon k (0-based) owns entries [first, first + n).
 // At create time a lexicon's entries are bucketed by length into lane widths -- 16 lanes (L <= 7, S <= 15), 32 lanes (L <= 15),

@@ -8,6 +8,7 @@
 #include "ctc_candidates.h"
 #include "ctc_charset.h"
 #include "ctc_lexicon.h"
+#include "ctc_lexicon_align.h"
 
 namespace rt {
 namespace pp {
@@ -117,6 +118,15 @@ void ctc_lexicon_forward(hipStream_t st, const float* logits, int ld, const floa
 // counts[line.slot] (slots of a line's row past its count are not written)
 void ctc_lexicon_topk(hipStream_t st, const lx::Line* lines, int n_lines, const lx::Lex* lex, const float* loglik,
                       lx::Match* matches, int* counts);
+// Lexicon snap (ctc_lexicon_align.h): one wave64 per line of lines[0..n_lines) (one chunk, resident as for ctc_lexicon_forward,
+// after ctc_lexicon_topk over the same lines).  snapped[line.slot] <- 0 / 1 for every line; a line whose lexicon has
+// min_post[line.lex] > 0 and whose match 0 reaches it has its winner aligned (CTC Viterbi) and its rows rows[line.row0 ..
+// + T) of idx / prob overwritten by the path; vit (optional): the end state's Viterbi value -> vit[line.slot], snapped lines
+// only.  bp: 16 bytes per row of the chunk (16-byte aligned), the backpointers of the lines longer than la::TILE steps.
+void ctc_lexicon_align(hipStream_t st, const float* logits, int ld, const float* lse, const lx::Line* lines, int n_lines,
+                       int chunk_row0, const lx::Lex* lex, const lx::Entry* entries, const int* ids, const float* min_post,
+                       const lx::Match* matches, const int* counts, const int* rows, void* bp, int* idx, float* prob, int* snapped,
+                       float* vit);
 
 // sum of a float buffer into per-block doubles (partials has ceil(n/65536) entries)
 int sum_blocks(long long n);

@@ -665,6 +665,111 @@ void ctc_lexicon_topk(hipStream_t st, const lx::Line* lines, int n_lines, const 
   RT_LAUNCH(k_ctc_lexicon_topk, dim3(n_lines), dim3(64), 0, st, lines, lex, loglik, matches, counts);
 }
 
+// Lexicon snap (ctc_lexicon_align.h).  One wave64 per lexicon line of one chunk, after k_ctc_lexicon_topk has written the line's
+// matches: the wave applies the snap condition to match 0, writes snapped[slot] (0 or 1, for every line it sees) and leaves
+// unless the line snaps.  Then lane s owns state s of the winner (S <= 63) and the forward pass is k_ctc_lexicon_forward's
+// loop with la::best in place of lae: the same __shfl_up neighbours, the same register ring of l[t][cls(s)] loads AHEAD steps
+// early, no lse, expf or logf on the chain.  A step's backpointers (0, 1 or 2 per state) leave the wave as two 64-bit ballots,
+// 16 bytes per step, written by lane 0: into LDS when the line fits one tile (T <= la::TILE), otherwise into bp [2 * chunk
+// rows] at the line's rows -- T has no bound beyond the pipeline's own.  The backtrack is wave-uniform and serial in t; it
+// walks the line tile by tile from the end, each tile's ballots brought back coalesced (lane i loads steps i, i + 64, ...) into
+// LDS first, so the chain runs over LDS reads, never over dependent global loads.  The walk leaves s_t per step in LDS, and a
+// pass parallel over the tile's steps writes idx[rows[..]] = cls(s_t) and prob = expf(l - lse) through the chunk's row list.
+// A backpointer cannot leave [0, S) (ctc_lexicon_align.h), so every index below stays inside the line's own rows.
+// bp is deliberately NOT __restrict__: on the long-T path lane 0 writes it with plain stores and, after the __syncthreads()
+// behind the forward pass (a workgroup-scope release / acquire around the barrier; the block is this one wave, on one CU and
+// one L1), the other lanes read those very bytes.  Marking it __restrict__ would let the compiler treat the loads as
+// independent of the stores.
+__global__ __launch_bounds__(64) void k_ctc_lexicon_align(const float* __restrict__ logits, int ld, const float* __restrict__ lse,
+                                                          const lx::Line* __restrict__ lines, int chunk_row0,
+                                                          const lx::Lex* __restrict__ lex, const lx::Entry* __restrict__ entries,
+                                                          const int* __restrict__ ids, const float* __restrict__ min_post,
+                                                          const lx::Match* __restrict__ matches, const int* __restrict__ counts,
+                                                          const int* __restrict__ rows, ulonglong2* bp, int* __restrict__ idx,
+                                                          float* __restrict__ prob, int* __restrict__ snapped,
+                                                          float* __restrict__ vit) {
+  constexpr int AHEAD = 4, TILE = la::TILE;
+  __shared__ ulonglong2 s_bp[TILE];
+  __shared__ unsigned char s_state[TILE];
+  const int lane = threadIdx.x;
+  const lx::Line ln = lines[blockIdx.x];
+  const float mp = min_post[ln.lex];
+  bool fire = false; int e = 0;
+  if (mp > 0.0f) {   // (a match slot past the count was never written: read match 0 only where there is one)
+    const int cnt = counts[ln.slot];
+    if (cnt >= 1) {
+      const lx::Match m = matches[(long long)ln.slot * lx::MATCHES];
+      fire = la::snaps(mp, cnt, m.posterior); e = m.entry;
+    }
+  }
+  if (lane == 0) snapped[ln.slot] = fire ? 1 : 0;
+  if (!fire) return;   // (wave-uniform)
+  const lx::Entry E = entries[lex[ln.lex].first + e];
+  const int32_t* eid = ids + E.off;
+  const int s = lane, S = 2 * E.len + 1, T = ln.T;
+  const bool mine = s < S;
+  const int cls = mine ? lx::cls_of(eid, s) : 0;
+  const bool skip = mine && lx::skip_of(eid, s);
+  const long long r0 = ln.row0 - chunk_row0;
+  const float* col = logits + r0 * ld + cls;
+  const bool in_lds = T <= TILE;
+  ulonglong2* g = bp + r0;
+  float lq[AHEAD];
+#pragma unroll
+  for (int j = 0; j < AHEAD; j++) lq[j] = j < T ? col[(long long)j * ld] : 0.0f;
+  float v = -INFINITY;
+  for (int t0 = 0; t0 < T; t0 += AHEAD) {
+#pragma unroll
+    for (int j = 0; j < AHEAD; j++) {
+      const int t = t0 + j;
+      if (t < T) {   // (wave-uniform)
+        const float l = lq[j];
+        if (t + AHEAD < T) lq[j] = col[(long long)(t + AHEAD) * ld];
+        const float u1 = __shfl_up(v, 1), u2 = __shfl_up(v, 2);
+        int off;
+        const float b = la::best(v, s >= 1 ? u1 : -INFINITY, skip ? u2 : -INFINITY, &off);
+        const float nx = t == 0 ? (s < 2 ? l : -INFINITY) : b + l;
+        v = mine ? nx : -INFINITY;
+        if (t == 0 || !mine) off = 0;
+        const ulonglong2 q = make_ulonglong2(__ballot(off & 1), __ballot(off >> 1));
+        if (lane == 0) { if (in_lds) s_bp[t] = q; else g[t] = q; }
+      }
+    }
+  }
+  const float f1 = __shfl(v, S - 1), f2 = __shfl(v, S - 2);
+  int cur = __builtin_amdgcn_readfirstlane(la::end_of(f1, f2, S));
+  if (lane == 0 && vit) vit[ln.slot] = cur == S - 1 ? f1 : f2;
+  __syncthreads();   // (lane 0's ballots, in LDS or in bp, before any lane reads them)
+  for (int t1 = T; t1 > 0;) {
+    const int tb = in_lds ? 0 : ((t1 - 1) / TILE) * TILE, n = t1 - tb;   // the tile [tb, t1), n <= TILE
+    if (!in_lds) {
+      for (int i = lane; i < n; i += 64) s_bp[i] = g[tb + i];
+      __syncthreads();
+    }
+    for (int i = n - 1; i >= 0; i--) {
+      const ulonglong2 q = s_bp[i];
+      if (lane == 0) s_state[i] = (unsigned char)cur;
+      cur -= __builtin_amdgcn_readfirstlane((int)((q.x >> cur) & 1ull) | ((int)((q.y >> cur) & 1ull) << 1));
+    }
+    __syncthreads();
+    for (int i = lane; i < n; i += 64) {
+      const int c = lx::cls_of(eid, s_state[i]), row = rows[ln.row0 + tb + i];
+      idx[row] = c;
+      prob[row] = expf(logits[(r0 + tb + i) * ld + c] - lse[r0 + tb + i]);
+    }
+    __syncthreads();   // (the tile's states and ballots are read before the next tile overwrites them)
+    t1 = tb;
+  }
+}
+void ctc_lexicon_align(hipStream_t st, const float* logits, int ld, const float* lse, const lx::Line* lines, int n_lines,
+                       int chunk_row0, const lx::Lex* lex, const lx::Entry* entries, const int* ids, const float* min_post,
+                       const lx::Match* matches, const int* counts, const int* rows, void* bp, int* idx, float* prob, int* snapped,
+                       float* vit) {
+  if (n_lines <= 0) return;
+  RT_LAUNCH(k_ctc_lexicon_align, dim3(n_lines), dim3(64), 0, st, logits, ld, lse, lines, chunk_row0, lex, entries, ids, min_post,
+            matches, counts, rows, static_cast<ulonglong2*>(bp), idx, prob, snapped, vit);
+}
+
 // ===========================================================================
 // (round 5: 8192 values per block, 16-byte loads -- was 65536 per block, scalar: one 960 x 960 map ran on 15 workgroups for 77 us,
 //  6 % of the C2 call)

@@ -478,7 +478,8 @@ int rt_session::charset_create(const char* utf8, size_t len, const int32_t* ids,
 
 void rt_session::ctc_lexicon(const SvtrCore& core, const float* z5, const lx::Line* h_lines, const lx::Line* d_lines, int n_lines,
                              const int* d_rows, int n_rows, int max_waves, const lx::Lex* d_lex, const lx::Entry* d_entries,
-                             const int* d_order, const int* d_ids, int chunk_rows, float* loglik, lx::Match* matches, int* counts) {
+                             const int* d_order, const int* d_ids, int chunk_rows, float* loglik, lx::Match* matches, int* counts,
+                             const LexSnap* snap) {
   if (n_lines <= 0) return;
   const int chunk = chunk_rows > 0 ? chunk_rows : cc::CAND_CHUNK, ld = round_up(core.classes, 4);
   // chunks of whole lines: [i0, i1) takes lines while their rows fit the chunk, and always its first line
@@ -497,6 +498,8 @@ void rt_session::ctc_lexicon(const SvtrCore& core, const float* z5, const lx::Li
   float* zc = scratch.alloc<float>(zc_n);
   float* logits = scratch.alloc<float>((size_t)cap * ld);
   float* lse = scratch.alloc<float>((size_t)cap);
+  // (lexicon snap: the backpointers of a chunk's long lines, two 64-bit ballots per row)
+  void* bp = snap ? scratch.alloc_bytes((size_t)cap * 16) : nullptr;
   RT_HIP_CHECK(hipMemsetAsync(zc, 0, zc_n * sizeof(float), st));
   RunCtx c = ctx(&scratch);
   for (int i0 = 0; i0 < n_lines;) {   // (stream order lets the chunks share zc, logits and lse)
@@ -511,10 +514,19 @@ void rt_session::ctc_lexicon(const SvtrCore& core, const float* z5, const lx::Li
     }
     { ProfScope ps(&prof, st, "ctc_lexicon_forward");
       pp::ctc_lexicon_forward(st, logits, ld, lse, d_lines + i0, i1 - i0, r0, max_waves, d_lex, d_entries, d_order, d_ids, loglik); }
+    if (snap) {   // (a line never straddles chunks: its matches are complete, and its logits still resident, here)
+      { ProfScope ps(&prof, st, "ctc_lexicon_topk");
+        pp::ctc_lexicon_topk(st, d_lines + i0, i1 - i0, d_lex, loglik, matches, counts); }
+      ProfScope ps(&prof, st, "ctc_lexicon_align");
+      pp::ctc_lexicon_align(st, logits, ld, lse, d_lines + i0, i1 - i0, r0, d_lex, d_entries, d_ids, snap->d_min_post, matches, counts,
+                            d_rows, bp, snap->idx, snap->prob, snap->snapped, snap->vit);
+    }
     i0 = i1;
   }
-  ProfScope ps(&prof, st, "ctc_lexicon_topk");
-  pp::ctc_lexicon_topk(st, d_lines, n_lines, d_lex, loglik, matches, counts);
+  if (!snap) {   // (without snap: one top-K over all the group's lines)
+    ProfScope ps(&prof, st, "ctc_lexicon_topk");
+    pp::ctc_lexicon_topk(st, d_lines, n_lines, d_lex, loglik, matches, counts);
+  }
 }
 
 int rt_session::lexicon_create(const char* utf8, size_t len, const int32_t* ids, const int32_t* entry_lens, int n_id_entries) {
@@ -552,6 +564,22 @@ int rt_session::lexicon_create(const char* utf8, size_t len, const int32_t* ids,
   X.tb = std::move(tb);
   X.host.push_back(std::move(h));
   return (int)X.host.size();
+}
+
+void rt_session::lexicon_set_snap(int lexicon, float min_posterior) {
+  rt_lexicons& X = *lexicons;
+  if (lexicon < 1 || lexicon > (int)X.host.size())
+    throw RtError(RT_ERR_INVALID, "rt_lexicon_set_snap: unknown lexicon id " + std::to_string(lexicon));
+  if (!(min_posterior >= 0.0f && min_posterior <= 1.0f))   // (a NaN fails both)
+    throw RtError(RT_ERR_INVALID, "rt_lexicon_set_snap: min_posterior " + std::to_string(min_posterior) + " is outside [0, 1]");
+  // (blocking copies; no lane has work queued: this is a guarded call and every pipeline call ends with its streams drained)
+  RT_HIP_CHECK(hipSetDevice(device));
+  if (!X.d_snap) {
+    RT_HIP_CHECK(hipMalloc((void**)&X.d_snap, sizeof X.snap));
+    RT_HIP_CHECK(hipMemcpy(X.d_snap, X.snap, sizeof X.snap, hipMemcpyHostToDevice));
+  }
+  RT_HIP_CHECK(hipMemcpy(X.d_snap + (lexicon - 1), &min_posterior, sizeof(float), hipMemcpyHostToDevice));
+  X.snap[lexicon - 1] = min_posterior;
 }
 
 // ---------------------------------------------------------------------------
@@ -845,6 +873,8 @@ struct Pipeline {
   // and the number of matches (written for the lines that carry a lexicon only)
   std::vector<int> line_lex;
   lx::Match* d_lexm = nullptr; int* d_lexn = nullptr; lx::Match* h_lexm = nullptr; int* h_lexn = nullptr;
+  // lexicon snap (ctc_lexicon_align.h): per line 1 where it snapped; null unless a lexicon of the call's lines has snap on
+  int* d_lexs = nullptr; int* h_lexs = nullptr;
 };
 
 // Launch groups: items [g0, end) where the group always takes its first item; with max_items > 0 it takes up to max_items items,
@@ -1105,6 +1135,13 @@ void rec_groups(rt_session& s, Pipeline& P) {
     P.d_wcount = s.arena.alloc<int>(P.NLp); P.d_words = s.arena.alloc<wb::Word>(ntok); d_wcol = s.arena.alloc<int>(ntok);
   }
   if (!P.line_lex.empty()) { P.d_lexm = s.arena.alloc<lx::Match>((size_t)P.NLp * lx::MATCHES); P.d_lexn = s.arena.alloc<int>(P.NLp); }
+  // lexicon snap (ctc_lexicon_align.h): a line snaps only where its lexicon has min_posterior > 0
+  auto snap_on = [&](int li) { return P.line_lex[li] > 0 && s.lexicons->snap[P.line_lex[li] - 1] > 0.0f; };
+  for (int li = 0; li < P.NL && !P.line_lex.empty() && !P.d_lexs; li++)
+    if (snap_on(li)) {   // (zeroed: the lexicon lines of a group without a snap-enabled line are never written)
+      P.d_lexs = s.arena.alloc<int>(P.NLp);
+      RT_HIP_CHECK(hipMemsetAsync(P.d_lexs, 0, (size_t)P.NLp * sizeof(int), s.st));
+    }
   static const long long REC_GROUP_PX = getenv("RT_REC_GROUP_PX") ? atoll(getenv("RT_REC_GROUP_PX")) : (long long)24000000;  // measured sweet spot (profiles/README.md)
   for (int l0 = 0; l0 < P.NL;) {
     const int l1 = group_end(l0, P.NL, 0, REC_GROUP_PX, [&](int l) { return (long long)rh * P.line_W[l]; });
@@ -1156,28 +1193,11 @@ void rec_groups(rt_session& s, Pipeline& P) {
     if (Lt.total != P.tok_off[l1] - t0) throw RtError(RT_ERR_SHAPE, "token count mismatch");
     if (n_crows > 0)   // the restricted rows' (idx, prob) are replaced before anything reads them
       s.ctc_charset(s.rec->core(), z5, d_crows, n_crows, d_row_set, s.charsets->d_masks, s.charsets->words, 0, d_idx + t0, d_prob + t0);
-    { ProfScope ps(&s.prof, s.st, "ctc_decode");
-      pp::ctc_decode(s.st, d_idx + t0, d_prob + t0, Lt.d, ln, P.d_tok + t0, P.d_meta.ntok + l0, P.d_meta.rscore + l0); }
-    if (s.cfg.rec_return_word_box) {
-      pp::WordLineDesc* hwl = s.pinned.alloc<pp::WordLineDesc>(ln);
-      for (int k = 0; k < ln; k++) {
-        const int li = l0 + k;
-        const pp::CropRef& r = P.plan.refs[li];
-        const pp::CropDesc& cd = P.plan.descs[li];
-        pp::WordLineDesc& D = hwl[k];
-        D.tok_off = P.tok_off[li] - t0;
-        D.g.T = (int)(P.tok_off[li + 1] - P.tok_off[li]); D.g.W = P.line_W[li]; D.g.resized_w = P.lines[li].resized_w;
-        D.g.w_c = r.w; D.g.h_c = r.h; D.g.rot270 = cd.rot; D.g.w = cd.w; D.g.h = cd.h;
-        D.g.cw = P.plan.dims[li].cw; D.g.ch = P.plan.dims[li].ch;
-        memcpy(D.g.inv, cd.inv, sizeof D.g.inv);
-      }
-      pp::WordLineDesc* dw = s.scratch.alloc<pp::WordLineDesc>(ln);
-      RT_HIP_CHECK(hipMemcpyAsync(dw, hwl, (size_t)ln * sizeof(pp::WordLineDesc), hipMemcpyHostToDevice, s.st));
-      ProfScope ps(&s.prof, s.st, "word_boxes");
-      pp::word_boxes(s.st, d_idx + t0, P.d_tok + t0, P.d_meta.ntok + l0, P.d_meta.label + l0, P.d_meta.cscore + l0, s.cfg.cls_thresh,
-                     s.d_word_raw, dw, ln, d_wcol + t0, P.d_wcount + l0, P.d_words + t0);
-    }
-    if (n_lrows >= 0) {   // rec lexicons (ctc_lexicon.h): the group's lexicon lines, their rows and their loglik rows
+    // lexicon snap (ctc_lexicon_align.h): a group with a snap-enabled lexicon line runs its lexicons HERE, behind the charsets
+    // and in front of the decode, which then reads the snapped lines' aligned rows.  Any other group keeps the order below
+    bool snap_group = false;
+    for (int li = l0; li < l1 && P.d_lexs && !snap_group; li++) snap_group = snap_on(li);
+    auto run_lexicons = [&] {   // rec lexicons (ctc_lexicon.h): the group's lexicon lines, their rows and their loglik rows
       const rt_lexicons& X = *s.lexicons;
       int nl = 0;
       for (int li = l0; li < l1; li++) nl += P.line_lex[li] > 0 ? 1 : 0;
@@ -1199,9 +1219,33 @@ void rec_groups(rt_session& s, Pipeline& P) {
       float* loglik = s.scratch.alloc<float>((size_t)out);
       RT_HIP_CHECK(hipMemcpyAsync(d_lines, h_lines, (size_t)nl * sizeof(lx::Line), hipMemcpyHostToDevice, s.st));
       if (n_lrows > 0) RT_HIP_CHECK(hipMemcpyAsync(d_rows, h_rows, (size_t)n_lrows * sizeof(int), hipMemcpyHostToDevice, s.st));
+      const rt_session::LexSnap snap{X.d_snap, d_idx + t0, d_prob + t0, P.d_lexs, nullptr};
       s.ctc_lexicon(s.rec->core(), z5, h_lines, d_lines, nl, d_rows, n_lrows, max_waves, X.d_lex, X.d_entries, X.d_order, X.d_ids, 0,
-                    loglik, P.d_lexm, P.d_lexn);
+                    loglik, P.d_lexm, P.d_lexn, snap_group ? &snap : nullptr);
+    };
+    if (snap_group) run_lexicons();
+    { ProfScope ps(&s.prof, s.st, "ctc_decode");
+      pp::ctc_decode(s.st, d_idx + t0, d_prob + t0, Lt.d, ln, P.d_tok + t0, P.d_meta.ntok + l0, P.d_meta.rscore + l0); }
+    if (s.cfg.rec_return_word_box) {
+      pp::WordLineDesc* hwl = s.pinned.alloc<pp::WordLineDesc>(ln);
+      for (int k = 0; k < ln; k++) {
+        const int li = l0 + k;
+        const pp::CropRef& r = P.plan.refs[li];
+        const pp::CropDesc& cd = P.plan.descs[li];
+        pp::WordLineDesc& D = hwl[k];
+        D.tok_off = P.tok_off[li] - t0;
+        D.g.T = (int)(P.tok_off[li + 1] - P.tok_off[li]); D.g.W = P.line_W[li]; D.g.resized_w = P.lines[li].resized_w;
+        D.g.w_c = r.w; D.g.h_c = r.h; D.g.rot270 = cd.rot; D.g.w = cd.w; D.g.h = cd.h;
+        D.g.cw = P.plan.dims[li].cw; D.g.ch = P.plan.dims[li].ch;
+        memcpy(D.g.inv, cd.inv, sizeof D.g.inv);
+      }
+      pp::WordLineDesc* dw = s.scratch.alloc<pp::WordLineDesc>(ln);
+      RT_HIP_CHECK(hipMemcpyAsync(dw, hwl, (size_t)ln * sizeof(pp::WordLineDesc), hipMemcpyHostToDevice, s.st));
+      ProfScope ps(&s.prof, s.st, "word_boxes");
+      pp::word_boxes(s.st, d_idx + t0, P.d_tok + t0, P.d_meta.ntok + l0, P.d_meta.label + l0, P.d_meta.cscore + l0, s.cfg.cls_thresh,
+                     s.d_word_raw, dw, ln, d_wcol + t0, P.d_wcount + l0, P.d_words + t0);
     }
+    if (n_lrows >= 0 && !snap_group) run_lexicons();
     if (cand_k > 0)   // (before the next group rewinds the scratch arena z5 lives in)
       s.ctc_candidates(s.rec->core(), z5, d_idx + t0, d_prob + t0, Lt.d, P.d_meta.ntok + l0, ln, Lt.total, cand_k, 0,
                        P.d_ccol + t0, P.d_cands + t0 * cand_k, d_row_set, d_row_set ? s.charsets->d_masks : nullptr, s.charsets->words);
@@ -1230,6 +1274,10 @@ void line_round_trip(rt_session& s, Pipeline& P) {
     P.h_lexm = s.pinned.alloc<lx::Match>((size_t)P.NLp * lx::MATCHES); P.h_lexn = s.pinned.alloc<int>(P.NLp);
     RT_HIP_CHECK(hipMemcpyAsync(P.h_lexm, P.d_lexm, (size_t)P.NLp * lx::MATCHES * sizeof(lx::Match), hipMemcpyDeviceToHost, s.st));
     RT_HIP_CHECK(hipMemcpyAsync(P.h_lexn, P.d_lexn, (size_t)P.NLp * sizeof(int), hipMemcpyDeviceToHost, s.st));
+    if (P.d_lexs) {   // (and, with snap on, which lines snapped)
+      P.h_lexs = s.pinned.alloc<int>(P.NLp);
+      RT_HIP_CHECK(hipMemcpyAsync(P.h_lexs, P.d_lexs, (size_t)P.NLp * sizeof(int), hipMemcpyDeviceToHost, s.st));
+    }
   }
   s.sync(); s.check_flags();
 }
@@ -1265,9 +1313,11 @@ void results(const rt_session& s, const Pipeline& P, rt_results& res) {
     }
     if (!P.line_lex.empty()) {   // rec lexicons: a line without one has 0 matches (its device slots were never written)
       R.lex_id.assign((size_t)nb, 0); R.lex_n.assign((size_t)nb, 0); R.lex_matches.assign((size_t)nb * lx::MATCHES, lx::Match{0, 0.0f, 0.0f});
+      if (P.h_lexs) R.lex_snapped.assign((size_t)nb, 0);
       for (int k = 0; k < nb; k++) {
         const int li = p.first_line + k;
         if (P.line_lex[li] <= 0) continue;
+        if (P.h_lexs) R.lex_snapped[k] = P.h_lexs[li] == 1 ? 1 : 0;
         R.lex_id[k] = P.line_lex[li];
         R.lex_n[k] = std::min(std::max(P.h_lexn[li], 0), lx::MATCHES);
         for (int j = 0; j < R.lex_n[k]; j++) R.lex_matches[(size_t)k * lx::MATCHES + j] = P.h_lexm[(size_t)li * lx::MATCHES + j];

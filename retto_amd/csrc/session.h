@@ -43,6 +43,9 @@ struct rt_results {
     // [rt::lx::MATCHES] match slots.  Empty when no line of the call carried a lexicon
     std::vector<int32_t> lex_id, lex_n;
     std::vector<rt::lx::Match> lex_matches;
+    // lexicon snap (ctc_lexicon_align.h): per line 1 where its decode is its aligned best entry.  Empty when no lexicon of the
+    // call's lines had snap on
+    std::vector<uint8_t> lex_snapped;
     std::string json[3];
   };
   std::vector<Page> pages;
@@ -129,11 +132,15 @@ struct rt_lexicons {
   std::vector<std::unique_ptr<Host>> host;
   rt::lx::Tables tb;
   int32_t* d_ids = nullptr; rt::lx::Entry* d_entries = nullptr; int32_t* d_order = nullptr; rt::lx::Lex* d_lex = nullptr;
+  // lexicon snap (ctc_lexicon_align.h, rt_lexicon_set_snap): min_posterior per lexicon, 0 = never snap; d_snap [MAX_LEXICONS]
+  // is allocated by the first rt_lexicon_set_snap and changed under the same guard, with a blocking copy
+  float snap[rt::lx::MAX_LEXICONS] = {};
+  float* d_snap = nullptr;
   void free_device() {
     if (d_ids) (void)hipFree(d_ids); if (d_entries) (void)hipFree(d_entries); if (d_order) (void)hipFree(d_order); if (d_lex) (void)hipFree(d_lex);
     d_ids = nullptr; d_entries = nullptr; d_order = nullptr; d_lex = nullptr;
   }
-  ~rt_lexicons() { free_device(); }
+  ~rt_lexicons() { free_device(); if (d_snap) (void)hipFree(d_snap); }
 };
 
 // internal to the library (never accepted from a caller): pages already in HBM, det map overrides still host pointers
@@ -222,11 +229,19 @@ struct rt_session {
   // chunk_rows rows (0: cc::CAND_CHUNK; at least one line, so a line's T rows are resident together): row gather, the CTC FC,
   // k_ctc_row_lse, k_ctc_lexicon_forward -> loglik; then one k_ctc_lexicon_topk over all lines -> matches / counts.  max_waves:
   // the largest lx::waves_of over the lines' lexicons.  No host wait; the workspace comes from `scratch`.
+  // snap (ctc_lexicon_align.h; null: off, today's launches in today's order): at least one of the lines' lexicons has
+  // min_posterior > 0.  Then k_ctc_lexicon_topk runs per chunk, over the chunk's lines, followed by k_ctc_lexicon_align while
+  // the chunk's logits are resident; it overwrites the snapped lines' rows of snap->idx / prob (the group's, indexed by d_rows)
+  // and writes snap->snapped[slot] for every line.  The caller runs pp::ctc_decode afterwards.
+  struct LexSnap { const float* d_min_post; int* idx; float* prob; int* snapped; float* vit; };
   void ctc_lexicon(const rt::SvtrCore& core, const float* z5, const rt::lx::Line* h_lines, const rt::lx::Line* d_lines, int n_lines,
                    const int* d_rows, int n_rows, int max_waves, const rt::lx::Lex* d_lex, const rt::lx::Entry* d_entries,
-                   const int* d_order, const int* d_ids, int chunk_rows, float* loglik, rt::lx::Match* matches, int* counts);
+                   const int* d_order, const int* d_ids, int chunk_rows, float* loglik, rt::lx::Match* matches, int* counts,
+                   const LexSnap* snap = nullptr);
   // rt_lexicon_create: compiles the entries (rt::compile_lexicon), stores them and returns the lexicon's id
   int lexicon_create(const char* utf8, size_t len, const int32_t* ids, const int32_t* entry_lens, int n_id_entries);
+  // rt_lexicon_set_snap: the lexicon's min_posterior (ctc_lexicon_align.h), on the host and in the device table
+  void lexicon_set_snap(int lexicon, float min_posterior);
   // L2
   // persistent lane threads (index 0 = this session's own lane) and the number of submitted, not yet waited batches
   std::vector<std::unique_ptr<LaneWorker>> workers;

@@ -7,7 +7,11 @@ times: median and spread) and, from a serial profiled pass (one lane, per-launch
 lexicons' launch families (`ctc_gather_rows`, `gemm_cand_fc`, `ctc_row_lse`, `ctc_lexicon_forward`, `ctc_lexicon_topk`) next to
 `ctc_decode` and `net/rec`.
 
-    python tools/bench_lexicon.py --steps 10 --warmup 2 --repeats 3
+--snap adds a third leg, the lexicon snap (rt_lexicon_set_snap, ctc_lexicon_align.h): the same lines and the same lexicon with a
+threshold every line meets, next to the 100 % leg with snap off in the same run; its profile shows `ctc_lexicon_topk` once per
+chunk instead of once per group, and `ctc_lexicon_align`.
+
+    python tools/bench_lexicon.py --steps 10 --warmup 2 --repeats 3 [--snap]
 """
 import argparse
 import ctypes as C
@@ -24,8 +28,9 @@ import numpy as np  # noqa: E402
 import retto_amd  # noqa: E402
 from retto_amd import workload  # noqa: E402
 
-FAMILIES = ("ctc_gather_rows", "gemm_cand_fc", "ctc_row_lse", "ctc_lexicon_forward", "ctc_lexicon_topk")
+FAMILIES = ("ctc_gather_rows", "gemm_cand_fc", "ctc_row_lse", "ctc_lexicon_forward", "ctc_lexicon_topk", "ctc_lexicon_align")
 SHARES = (0, 100)
+SNAP_MIN_POSTERIOR = 1e-30   # (--snap: reached by every line that has a match)
 
 
 def upload(lib, h, arr):
@@ -44,6 +49,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--profile-steps", type=int, default=3)
+    ap.add_argument("--snap", action="store_true", help="add the leg with lexicon snap on for every line")
     a = ap.parse_args()
     if a.steps < 1 or a.repeats < 1 or a.profile_steps < 1 or a.entries < 1:
         ap.error("--steps, --repeats, --profile-steps and --entries must be at least 1")
@@ -66,23 +72,28 @@ def main():
         lid = sess.create_lexicon(ids=[rng.integers(1, n, int(rng.integers(3, 13))).tolist() for _ in range(a.entries)])
         ids = {share: [np.full(len(q), lid if share else 0, np.int32) for q in quads] for share in SHARES}
 
-        def run(share):
+        legs = [("%d%%" % share, share, 0.0) for share in SHARES] + ([("100%+snap", 100, SNAP_MIN_POSTERIOR)] if a.snap else [])
+
+        def run(leg):
+            name, share, snap = leg
+            if sess.lexicon_snap(lid) != np.float32(snap):   # (a guarded call: every earlier call has drained its streams)
+                sess.set_lexicon_snap(lid, snap)
             return sess.run_regions_raw(d_pages, [960] * a.pages, [960] * a.pages, quads, retto_amd.RT_MEM_DEVICE, lexicons=ids[share])
 
-        def step_ms(share, steps):
+        def step_ms(leg, steps):
             lib.rt_synchronize(h)
             t0 = time.perf_counter()
             for _ in range(steps):
-                lib.rt_results_free(run(share))
+                lib.rt_results_free(run(leg))
             return (time.perf_counter() - t0) * 1e3 / steps
 
-        def profile(share):
+        def profile(leg):
             lib.rt_set_lanes(h, 1)
             for _ in range(2):
-                lib.rt_results_free(run(share))
+                lib.rt_results_free(run(leg))
             sess.profile_enable(True)
             for _ in range(a.profile_steps):
-                lib.rt_results_free(run(share))
+                lib.rt_results_free(run(leg))
             prof = sess.profile_get()
             sess.profile_enable(False)
             lib.rt_set_lanes(h, 1 << 20)
@@ -92,17 +103,22 @@ def main():
 
         out = {"pages": a.pages, "lines_per_call": int(sum(len(q) for q in quads)), "steps": a.steps, "repeats": a.repeats,
                "lexicon_entries": len(sess.lexicon_entries(lid))}
-        for share in SHARES:
-            step_ms(share, a.warmup)
-        ms = {share: [] for share in SHARES}
+        for leg in legs:
+            step_ms(leg, a.warmup)
+        ms = {leg[0]: [] for leg in legs}
         for _ in range(a.repeats):
-            for share in SHARES:
-                ms[share].append(step_ms(share, a.steps))
-        for share in SHARES:
-            v = ms[share]
+            for leg in legs:
+                ms[leg[0]].append(step_ms(leg, a.steps))
+        for leg in legs:
+            v = ms[leg[0]]
             med = float(np.median(v))
-            out["%d%%" % share] = {"step_ms": {"median": med, "min": min(v), "max": max(v)}, "images_per_s": a.pages * 1e3 / med,
-                                   "lexicon_lines": sum(int(c) > 0 for per in ids[share] for c in per), "profile": profile(share)}
+            out[leg[0]] = {"step_ms": {"median": med, "min": min(v), "max": max(v)}, "images_per_s": a.pages * 1e3 / med,
+                           "lexicon_lines": sum(int(c) > 0 for per in ids[leg[1]] for c in per), "profile": profile(leg)}
+        if a.snap:   # how many of the lines took their winner
+            r = run(legs[-1])
+            out["100%+snap"]["snapped_lines"] = sum(lib.rt_results_rec_lexicon_snapped(r, i, k) for i, q in enumerate(quads) for k in range(len(q)))
+            lib.rt_results_free(r)
+            sess.set_lexicon_snap(lid, 0.0)
         out["new_families_when_unused"] = [f for f in FAMILIES if f in out["0%"]["profile"]]
         print(json.dumps(out))
     finally:
