@@ -9,6 +9,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <numeric>
 
 #include "api_internal.h"
 
@@ -377,8 +378,47 @@ RT_API int rt_debug_attention(rt_session* s, const float* qkv, long long rows, c
   });
 }
 
-// rt_config.rec_return_candidates' device path (rt_session::ctc_candidates, what rec_groups runs per group) on host arrays: the
-// lines' geometry as the token level gives it, pp::ctc_decode for the token counts, an FC packed by pack_linear.
+// One rec group on host arrays through rt_session::rec_tail, the tail rec_groups runs per group, on the plan of rec_tail_plan.h
+// over the caller's lines: the features inside a larger zeroed allocation, as z5 sits inside the scratch arena; an FC packed by
+// pack_linear; the lines' geometry as the token level gives it; idx / prob the caller's (null: zeros, the decode's results are
+// then thrown away).  An entry adds its own inputs and outputs to `t`, run()s, and downloads.
+struct TailHook {
+  rt_session* s; size_t nr;
+  WeightStore ws; SvtrCore core; DevBufs bufs;
+  RecTailPlan plan; rt_session::RecTail t{};
+  TailHook(rt_session* s_, const float* z5, const float* W, const float* bias, int N, long long rows, const int32_t* tokens_per_line,
+           int n_lines, const int32_t* line_set, const int32_t* line_lex, const lx::Tables& tb, const float* snap_min, const int32_t* idx,
+           const float* prob, int K, int chunk_rows) : s(s_), nr((size_t)std::max<long long>(rows, 1)) {
+    s->begin_call();
+    std::vector<long long> off((size_t)n_lines + 1, 0);
+    std::partial_sum(tokens_per_line, tokens_per_line + n_lines, off.begin() + 1);   // (below 2^30: the entries' own check)
+    plan = rec_tail_plan(off.data(), 0, n_lines, line_set, line_lex, tb, snap_min);
+    core.classes = N;
+    if (plan.needs_z5(K)) {
+      core.fc = pack_linear(ws, W, bias, core.D, N);
+      float* dz = bufs.zeroed<float>((nr + 256) * core.D);
+      DevBufs::put(dz, z5, (size_t)rows * core.D); t.z5 = dz;
+    }
+    const std::vector<int32_t> zeros(idx ? 0 : nr, 0);
+    t.idx = bufs.upload(idx ? idx : zeros.data(), idx ? (size_t)rows : nr);
+    t.prob = bufs.upload(prob ? prob : reinterpret_cast<const float*>(zeros.data()), prob ? (size_t)rows : nr);
+    t.lines = Ragged(tokens_per_line, n_lines).upload(bufs); t.n_lines = n_lines;
+    t.tok = bufs.alloc<int>(nr); t.ntok = bufs.alloc<int>(n_lines); t.rscore = bufs.alloc<float>(n_lines);
+    t.cand_k = K; t.chunk_rows = chunk_rows;
+  }
+  // rec_return_candidates: what the kernels write starts as the caller's values
+  void candidates(const int32_t* cols, const rt_candidate* cands) {
+    t.ccol = bufs.alloc<int>(nr); t.cands = bufs.alloc<cc::Cand>(nr * t.cand_k); DevBufs::put(t.ccol, cols, (size_t)plan.rows);
+    DevBufs::put(t.cands, reinterpret_cast<const cc::Cand*>(cands), (size_t)plan.rows * t.cand_k);
+  }
+  void run() { s->rec_tail(plan, core, t); RT_HIP_CHECK(hipStreamSynchronize(s->st)); }
+  void download_candidates(int32_t* cols, rt_candidate* cands) const {
+    DevBufs::download(cols, t.ccol, (size_t)plan.rows);
+    DevBufs::download(reinterpret_cast<cc::Cand*>(cands), t.cands, (size_t)plan.rows * t.cand_k);
+  }
+};
+
+// rt_config.rec_return_candidates' device path on host arrays: pp::ctc_decode for the token counts, then the candidates.
 RT_API int rt_debug_ctc_candidates(rt_session* s, const float* z5, const float* W, const float* bias, int N, const int32_t* idx,
                                    const float* prob, const int32_t* tokens_per_line, int n_lines, int K, int chunk_rows,
                                    rt_candidate* cands_out, int32_t* cols_out, int32_t* n_tokens_out) {
@@ -387,34 +427,15 @@ RT_API int rt_debug_ctc_candidates(rt_session* s, const float* z5, const float* 
   RT_REQUIRE(cand_args_ok(z5, W, N, idx, prob, tokens_per_line, n_lines, K, cands_out, cols_out, n_tokens_out, &rows) && chunk_rows >= 0,
              s, "rt_debug_ctc_candidates: bad argument");
   return guarded(s, [&] {
-    s->begin_call();
-    const size_t nr = (size_t)std::max<long long>(rows, 1);
-    WeightStore ws;
-    SvtrCore core;
-    core.classes = N;
-    if (K > 1) core.fc = pack_linear(ws, W, bias, core.D, N);
-    DevBufs bufs;
-    float* dz = nullptr;
-    if (K > 1) {   // (the features sit inside a larger allocation, as z5 does inside the scratch arena)
-      dz = bufs.zeroed<float>((nr + 256) * core.D);
-      DevBufs::put(dz, z5, (size_t)rows * core.D);
-    }
-    int* didx = bufs.alloc<int>(nr); float* dprob = bufs.alloc<float>(nr); int* dtok = bufs.alloc<int>(nr);
-    int* dntok = bufs.alloc<int>(n_lines); float* dscore = bufs.alloc<float>(n_lines);
-    const ImgGeom* dg = Ragged(tokens_per_line, n_lines).upload(bufs);
-    int* dcols = bufs.alloc<int>(nr); cc::Cand* dcands = bufs.alloc<cc::Cand>(nr * K);
-    DevBufs::put(didx, idx, (size_t)rows); DevBufs::put(dprob, prob, (size_t)rows);
-    DevBufs::put(dcols, cols_out, (size_t)rows); DevBufs::put(dcands, reinterpret_cast<const cc::Cand*>(cands_out), (size_t)rows * K);
-    pp::ctc_decode(s->st, didx, dprob, dg, n_lines, dtok, dntok, dscore);
-    s->ctc_candidates(core, dz, didx, dprob, dg, dntok, n_lines, rows, K, chunk_rows, dcols, dcands);
-    RT_HIP_CHECK(hipStreamSynchronize(s->st));
-    DevBufs::download(n_tokens_out, dntok, (size_t)n_lines); DevBufs::download(cols_out, dcols, (size_t)rows);
-    DevBufs::download(reinterpret_cast<cc::Cand*>(cands_out), dcands, (size_t)rows * K);
+    TailHook h(s, z5, W, bias, N, rows, tokens_per_line, n_lines, nullptr, nullptr, lx::Tables(), nullptr, idx, prob, K, chunk_rows);
+    h.candidates(cols_out, cands_out);
+    h.run();
+    DevBufs::download(n_tokens_out, h.t.ntok, (size_t)n_lines);
+    h.download_candidates(cols_out, cands_out);
   });
 }
 
-// Rec charsets' device path (rt_session::ctc_charset, pp::ctc_decode and -- K > 0 -- rt_session::ctc_candidates with the masks: what
-// rec_groups runs per group) on host arrays; the rows of the restricted lines and the per-row set table are built as there.
+// Rec charsets' device path on host arrays: the restricted rows' argmax, pp::ctc_decode and -- K > 0 -- the candidates with the masks.
 RT_API int rt_debug_ctc_charset(rt_session* s, const float* z5, const float* W, const float* bias, int N, int32_t* idx, float* prob,
                                 const int32_t* tokens_per_line, int n_lines, const int32_t* line_set, const uint32_t* masks,
                                 int n_sets, int K, int chunk_rows, int32_t* tokens_out, int32_t* n_tokens_out, float* scores_out,
@@ -425,72 +446,27 @@ RT_API int rt_debug_ctc_charset(rt_session* s, const float* z5, const float* W, 
                              scores_out, cands_out, cols_out, &rows) && chunk_rows >= 0,
              s, "rt_debug_ctc_charset: bad argument");
   return guarded(s, [&] {
-    s->begin_call();
-    const size_t nr = (size_t)std::max<long long>(rows, 1);
-    const int words = cs::mask_words(N);
-    WeightStore ws;
-    SvtrCore core;
-    core.classes = N;
-    core.fc = pack_linear(ws, W, bias, core.D, N);
-    DevBufs bufs;
-    // (the features sit inside a larger allocation, as z5 does inside the scratch arena)
-    float* dz = bufs.zeroed<float>((nr + 256) * core.D);
-    DevBufs::put(dz, z5, (size_t)rows * core.D);
-    std::vector<int> row_set(nr, 0), crows;
-    long long o = 0;
-    for (int i = 0; i < n_lines; i++) {
-      for (int t = 0; t < tokens_per_line[i]; t++) {
-        row_set[(size_t)(o + t)] = line_set[i];
-        if (line_set[i] > 0) crows.push_back((int)(o + t));
-      }
-      o += tokens_per_line[i];
-    }
-    int* didx = bufs.alloc<int>(nr); float* dprob = bufs.alloc<float>(nr); int* dtok = bufs.alloc<int>(nr);
-    DevBufs::put(didx, idx, (size_t)rows); DevBufs::put(dprob, prob, (size_t)rows); DevBufs::put(dtok, tokens_out, (size_t)rows);
-    int* dntok = bufs.alloc<int>(n_lines); float* dscore = bufs.alloc<float>(n_lines);
-    const ImgGeom* dg = Ragged(tokens_per_line, n_lines).upload(bufs);
-    const int* drow_set = bufs.upload(row_set.data(), nr);
-    const int* dcrows = crows.empty() ? nullptr : bufs.upload(crows.data(), crows.size());
-    const uint32_t* dmasks = n_sets > 0 ? bufs.upload(masks, (size_t)n_sets * words) : nullptr;
-    s->ctc_charset(core, dz, dcrows, (int)crows.size(), drow_set, dmasks, words, chunk_rows, didx, dprob);
-    pp::ctc_decode(s->st, didx, dprob, dg, n_lines, dtok, dntok, dscore);
-    int* dcols = nullptr; cc::Cand* dcands = nullptr;
-    if (K > 0) {
-      dcols = bufs.alloc<int>(nr); dcands = bufs.alloc<cc::Cand>(nr * K);
-      DevBufs::put(dcols, cols_out, (size_t)rows); DevBufs::put(dcands, reinterpret_cast<const cc::Cand*>(cands_out), (size_t)rows * K);
-      s->ctc_candidates(core, dz, didx, dprob, dg, dntok, n_lines, rows, K, chunk_rows, dcols, dcands,
-                        crows.empty() ? nullptr : drow_set, crows.empty() ? nullptr : dmasks, words);
-    }
-    RT_HIP_CHECK(hipStreamSynchronize(s->st));
-    DevBufs::download(idx, didx, (size_t)rows); DevBufs::download(prob, dprob, (size_t)rows);
-    DevBufs::download(tokens_out, dtok, (size_t)rows);
-    DevBufs::download(n_tokens_out, dntok, (size_t)n_lines); DevBufs::download(scores_out, dscore, (size_t)n_lines);
-    if (K > 0) {
-      DevBufs::download(cols_out, dcols, (size_t)rows);
-      DevBufs::download(reinterpret_cast<cc::Cand*>(cands_out), dcands, (size_t)rows * K);
-    }
+    TailHook h(s, z5, W, bias, N, rows, tokens_per_line, n_lines, line_set, nullptr, lx::Tables(), nullptr, idx, prob, K, chunk_rows);
+    h.t.words = cs::mask_words(N);
+    h.t.masks = n_sets > 0 ? h.bufs.upload(masks, (size_t)n_sets * h.t.words) : nullptr;
+    DevBufs::put(h.t.tok, tokens_out, (size_t)rows);
+    if (K > 0) h.candidates(cols_out, cands_out);
+    h.run();
+    DevBufs::download(idx, h.t.idx, (size_t)rows); DevBufs::download(prob, h.t.prob, (size_t)rows);
+    DevBufs::download(tokens_out, h.t.tok, (size_t)rows);
+    DevBufs::download(n_tokens_out, h.t.ntok, (size_t)n_lines); DevBufs::download(scores_out, h.t.rscore, (size_t)n_lines);
+    if (K > 0) h.download_candidates(cols_out, cands_out);
   });
 }
 
-// Rec lexicons' device path (rt_session::ctc_lexicon: what rec_groups runs per group) on host arrays; the lines, their rows and
-// the lexicon tables are built as there and by rt_lexicon_create (lx::Tables).  With lex_min_post (lexicon snap,
-// ctc_lexicon_align.h) also the caller's idx / prob rows, in and out, the flags and the Viterbi values; a threshold above 0 on
-// the lexicon of some line takes ctc_lexicon's snap path (top-K per chunk, k_ctc_lexicon_align), as rec_groups does.
+// Rec lexicons' device path on host arrays; the lexicon tables are built as rt_lexicon_create builds them (lx::Tables).  With
+// lex_min_post (lexicon snap, ctc_lexicon_align.h) also the caller's idx / prob rows, in and out, the flags and the Viterbi
+// values; a threshold above 0 on the lexicon of some line makes the group a snap group.
 static void debug_ctc_lexicon(rt_session* s, const float* z5, const float* W, const float* bias, int N, const int32_t* tokens_per_line,
                               int n_lines, const int32_t* line_lex, const int32_t* entry_ids, const int32_t* entry_lens,
-                              const int32_t* lex_first_entry, int n_lex, int chunk_rows, long long rows, long long table,
+                              const int32_t* lex_first_entry, int n_lex, int chunk_rows, long long rows,
                               float* loglik_out, rt_lexicon_match* matches_out, int32_t* n_matches_out, const float* lex_min_post,
                               int32_t* idx, float* prob, int32_t* snapped_out, float* vit_out) {
-  s->begin_call();
-  const size_t nr = (size_t)std::max<long long>(rows, 1);
-  WeightStore ws;
-  SvtrCore core;
-  core.classes = N;
-  core.fc = pack_linear(ws, W, bias, core.D, N);
-  DevBufs bufs;
-  // (the features sit inside a larger allocation, as z5 does inside the scratch arena)
-  float* dz = bufs.zeroed<float>((nr + 256) * core.D);
-  DevBufs::put(dz, z5, (size_t)rows * core.D);
   lx::Tables tb;
   long long io = 0;
   for (int k = 0; k < n_lex; k++) {
@@ -498,50 +474,32 @@ static void debug_ctc_lexicon(rt_session* s, const float* z5, const float* W, co
     tb.add(entry_ids + io, entry_lens + e0, n);
     for (int j = 0; j < n; j++) io += entry_lens[e0 + j];
   }
-  std::vector<lx::Line> lines; std::vector<int> lrows;
-  long long o = 0, out = 0; int max_waves = 0; bool any_snap = false;
-  for (int i = 0; i < n_lines; i++) {
-    const int T = tokens_per_line[i];
-    if (line_lex[i] > 0) {
-      const lx::Lex& x = tb.lex[(size_t)line_lex[i] - 1];
-      lines.push_back(lx::Line{(int)lrows.size(), T, line_lex[i] - 1, i, out});
-      for (int t = 0; t < T; t++) lrows.push_back((int)(o + t));
-      out += x.n; max_waves = std::max(max_waves, lx::waves_of(x));
-      if (lex_min_post) {   // (the kernel, where it runs, writes every lexicon line's flag again)
-        any_snap |= lex_min_post[line_lex[i] - 1] > 0.0f;
-        snapped_out[i] = 0;
-      }
-    } else n_matches_out[i] = 0;
-    o += T;
+  TailHook h(s, z5, W, bias, N, rows, tokens_per_line, n_lines, nullptr, line_lex, tb, lex_min_post, idx, prob, 0, chunk_rows);
+  for (int i = 0; i < n_lines; i++) {   // (a line without a lexicon has no match; the kernel, where it runs, writes every lexicon line's flag again)
+    if (line_lex[i] <= 0) n_matches_out[i] = 0;
+    else if (lex_min_post) snapped_out[i] = 0;
   }
-  if (lines.empty()) return;
-  const lx::Line* dlines = bufs.upload(lines.data(), lines.size());
-  const int* drows = lrows.empty() ? bufs.alloc<int>(1) : bufs.upload(lrows.data(), lrows.size());
-  const int32_t* dids = bufs.upload(tb.ids.data(), tb.ids.size());
-  const lx::Entry* dent = bufs.upload(tb.entries.data(), tb.entries.size());
-  const int32_t* dord = bufs.upload(tb.order.data(), tb.order.size());
-  const lx::Lex* dlex = bufs.upload(tb.lex.data(), tb.lex.size());
+  rt_session::RecTail& t = h.t;
+  t.d_ids = h.bufs.upload(tb.ids.data(), tb.ids.size());
+  t.d_entries = h.bufs.upload(tb.entries.data(), tb.entries.size());
+  t.d_order = h.bufs.upload(tb.order.data(), tb.order.size());
+  t.d_lex = h.bufs.upload(tb.lex.data(), tb.lex.size());
   // (what the kernels write starts as the caller's values: a slot they leave alone comes back untouched)
-  float* dll = bufs.alloc<float>((size_t)table);
-  if (loglik_out) DevBufs::put(dll, loglik_out, (size_t)table);
-  lx::Match* dm = bufs.upload(reinterpret_cast<const lx::Match*>(matches_out), (size_t)n_lines * lx::MATCHES);
-  int* dn = bufs.upload(n_matches_out, (size_t)n_lines);
-  rt_session::LexSnap snap{nullptr, nullptr, nullptr, nullptr, nullptr};
-  if (any_snap) {
-    snap.d_min_post = bufs.upload(lex_min_post, (size_t)n_lex);
-    snap.idx = bufs.alloc<int>(nr); snap.prob = bufs.alloc<float>(nr);
-    DevBufs::put(snap.idx, idx, (size_t)rows); DevBufs::put(snap.prob, prob, (size_t)rows);
-    snap.snapped = bufs.upload(snapped_out, (size_t)n_lines); snap.vit = bufs.upload(vit_out, (size_t)n_lines);
+  t.loglik = h.bufs.alloc<float>((size_t)h.plan.table);
+  if (loglik_out) DevBufs::put(t.loglik, loglik_out, (size_t)h.plan.table);
+  t.lexm = h.bufs.upload(reinterpret_cast<const lx::Match*>(matches_out), (size_t)n_lines * lx::MATCHES);
+  t.lexn = h.bufs.upload(n_matches_out, (size_t)n_lines);
+  if (lex_min_post) {
+    t.d_min_post = h.bufs.upload(lex_min_post, (size_t)n_lex);
+    t.lexs = h.bufs.upload(snapped_out, (size_t)n_lines); t.vit = h.bufs.upload(vit_out, (size_t)n_lines);
   }
-  s->ctc_lexicon(core, dz, lines.data(), dlines, (int)lines.size(), drows, (int)lrows.size(), max_waves, dlex, dent, dord, dids,
-                 chunk_rows, dll, dm, dn, any_snap ? &snap : nullptr);
-  RT_HIP_CHECK(hipStreamSynchronize(s->st));
-  if (loglik_out) DevBufs::download(loglik_out, dll, (size_t)table);
-  DevBufs::download(reinterpret_cast<lx::Match*>(matches_out), dm, (size_t)n_lines * lx::MATCHES);
-  DevBufs::download(n_matches_out, dn, (size_t)n_lines);
-  if (any_snap) {
-    DevBufs::download(idx, snap.idx, (size_t)rows); DevBufs::download(prob, snap.prob, (size_t)rows);
-    DevBufs::download(snapped_out, snap.snapped, (size_t)n_lines); DevBufs::download(vit_out, snap.vit, (size_t)n_lines);
+  h.run();
+  if (loglik_out) DevBufs::download(loglik_out, t.loglik, (size_t)h.plan.table);
+  DevBufs::download(reinterpret_cast<lx::Match*>(matches_out), t.lexm, (size_t)n_lines * lx::MATCHES);
+  DevBufs::download(n_matches_out, t.lexn, (size_t)n_lines);
+  if (lex_min_post) {
+    DevBufs::download(idx, t.idx, (size_t)rows); DevBufs::download(prob, t.prob, (size_t)rows);
+    DevBufs::download(snapped_out, t.lexs, (size_t)n_lines); DevBufs::download(vit_out, t.vit, (size_t)n_lines);
   }
 }
 RT_API int rt_debug_ctc_lexicon(rt_session* s, const float* z5, const float* W, const float* bias, int N,
@@ -556,7 +514,7 @@ RT_API int rt_debug_ctc_lexicon(rt_session* s, const float* z5, const float* W, 
   RT_REQUIRE(chunk_rows >= 0, s, "rt_debug_ctc_lexicon: chunk_rows is negative");
   return guarded(s, [&] {
     debug_ctc_lexicon(s, z5, W, bias, N, tokens_per_line, n_lines, line_lex, entry_ids, entry_lens, lex_first_entry, n_lex, chunk_rows,
-                      rows, table, loglik_out, matches_out, n_matches_out, nullptr, nullptr, nullptr, nullptr, nullptr);
+                      rows, loglik_out, matches_out, n_matches_out, nullptr, nullptr, nullptr, nullptr, nullptr);
   });
 }
 RT_API int rt_debug_ctc_lexicon_align(rt_session* s, const float* z5, const float* W, const float* bias, int N,
@@ -573,7 +531,7 @@ RT_API int rt_debug_ctc_lexicon_align(rt_session* s, const float* z5, const floa
   RT_REQUIRE(chunk_rows >= 0, s, "rt_debug_ctc_lexicon_align: chunk_rows is negative");
   return guarded(s, [&] {
     debug_ctc_lexicon(s, z5, W, bias, N, tokens_per_line, n_lines, line_lex, entry_ids, entry_lens, lex_first_entry, n_lex, chunk_rows,
-                      rows, table, loglik_out, matches_out, n_matches_out, lex_min_post, idx, prob, snapped_out, vit_out);
+                      rows, loglik_out, matches_out, n_matches_out, lex_min_post, idx, prob, snapped_out, vit_out);
   });
 }
 

@@ -1,0 +1,59 @@
+// What the CTC tail of one rec group works on (rt_session::rec_tail, rec_tail.cpp), decided on the host in one place: the charset
+// row tables, the lexicon lines with their rows and table, and the three questions whose answers order the launches.  The
+// pipeline (rec_groups) and the debug hooks (rt_debug_ctc_*) both go through it.  Plain C++ as lc_plan.h: built and checked
+// without a GPU (tests/test_rec_tail_plan_cpu.py).
+#pragma once
+#include <algorithm>
+#include <vector>
+
+#include "ctc_lexicon.h"
+
+namespace rt {
+
+struct RecTailPlan {
+  long long rows = 0;              // the group's time steps; every row below counts from the group's first
+  // rec charsets (ctc_charset.h): every row's set (0: none) and the rows of the restricted lines in line order; both empty
+  // when no row of the group is restricted
+  std::vector<int> row_set, crows;
+  // rec lexicons (ctc_lexicon.h): the group's lexicon lines in line order (row0 = the sum of the earlier ones' T, slot = the
+  // line's index in the call, out = the sum of the earlier ones' lexicon sizes), their rows line after line, the floats of the
+  // loglik table (rec_groups refuses a group whose table does not fit) and the largest lx::waves_of over the lines' lexicons
+  std::vector<lx::Line> lines; std::vector<int> lrows;
+  long long table = 0; int max_waves = 0;
+  bool has_lex() const { return !lines.empty(); }   // (a lexicon line without a time step counts)
+  bool table_fits() const { return table <= lx::MAX_GROUP_TABLE; }
+  // lexicon snap (ctc_lexicon_align.h): a lexicon line of THIS group has min_posterior > 0; its lexicons then run before the decode
+  bool snap = false;
+  // the net must hand out the head's input: some logits are recomputed
+  bool needs_z5(int cand_k) const { return cand_k > 1 || !crows.empty() || has_lex(); }
+};
+
+// Lines [l0, l1) of a call: line li has the time steps [tok_off[li], tok_off[li + 1]), charset line_set[li] and lexicon
+// line_lex[li] (1-based, 0: none; either array may be null: no line has one), lexicon k is tb.lex[k - 1] and snaps where
+// snap_min[k - 1] > 0 (null: never).
+inline RecTailPlan rec_tail_plan(const long long* tok_off, int l0, int l1, const int* line_set, const int* line_lex,
+                                 const lx::Tables& tb, const float* snap_min) {
+  RecTailPlan p;
+  const long long t0 = tok_off[l0];
+  p.rows = tok_off[l1] - t0;
+  bool restricted = false;
+  for (int li = l0; li < l1 && line_set && !restricted; li++) restricted = line_set[li] > 0 && tok_off[li + 1] > tok_off[li];
+  if (restricted) p.row_set.resize((size_t)p.rows);
+  for (int li = l0; li < l1; li++) {
+    const int r0 = (int)(tok_off[li] - t0), T = (int)(tok_off[li + 1] - tok_off[li]);
+    for (int t = 0; restricted && t < T; t++) {
+      p.row_set[(size_t)(r0 + t)] = line_set[li];
+      if (line_set[li] > 0) p.crows.push_back(r0 + t);
+    }
+    if (!line_lex || line_lex[li] <= 0) continue;
+    const lx::Lex& x = tb.lex[(size_t)line_lex[li] - 1];
+    p.lines.push_back(lx::Line{(int)p.lrows.size(), T, line_lex[li] - 1, li, p.table});
+    for (int t = 0; t < T; t++) p.lrows.push_back(r0 + t);
+    p.table += x.n;
+    p.max_waves = std::max(p.max_waves, lx::waves_of(x));
+    p.snap = p.snap || (snap_min && snap_min[line_lex[li] - 1] > 0.0f);
+  }
+  return p;
+}
+
+}  // namespace rt

@@ -10,10 +10,8 @@
 #include <cstring>
 #include <numeric>
 #include <sstream>
-#include <thread>
-#include <unordered_map>
-
 #include <chrono>
+#include <thread>
 
 #include "geom_math.h"
 
@@ -29,168 +27,6 @@ struct HostTick {
     t = n;
   }
 };
-
-// ---------------------------------------------------------------------------
-// RecCharacter::new (rec_processor.rs:29-46): String::from_utf8(bytes)? -> lines().map(|l| l.trim()) -> push " "
-// -> insert "blank" at 0.  Rust semantics, restated exactly:
-//  * String::from_utf8 is strict: overlong forms, surrogates (U+D800-DFFF) and code points above U+10FFFF
-//    are errors (Utf8Error);
-//  * str::lines splits after every '\n', drops that '\n' and one '\r' in front of it; a trailing '\n' does not
-//    open a last empty line;
-//  * str::trim strips every char with the Unicode White_Space property (char::is_whitespace): U+0009-000D,
-//    U+0020, U+0085, U+00A0, U+1680, U+2000-200A, U+2028, U+2029, U+202F, U+205F, U+3000 -- a dictionary line
-//    that holds only U+3000 becomes the empty string.
-// ---------------------------------------------------------------------------
-namespace rt {
-static int utf8_decode_strict(const unsigned char* p, size_t n, uint32_t* cp) {  // bytes consumed, 0 = invalid
-  if (n == 0) return 0;
-  const unsigned char c = p[0];
-  if (c < 0x80) { *cp = c; return 1; }
-  auto cont = [&](size_t i) { return i < n && (p[i] & 0xC0) == 0x80; };
-  if (c >= 0xC2 && c <= 0xDF) { if (!cont(1)) return 0; *cp = ((c & 0x1F) << 6) | (p[1] & 0x3F); return 2; }
-  if (c >= 0xE0 && c <= 0xEF) {
-    if (!cont(1) || !cont(2)) return 0;
-    if (c == 0xE0 && p[1] < 0xA0) return 0;   // overlong
-    if (c == 0xED && p[1] >= 0xA0) return 0;  // surrogate
-    *cp = ((c & 0x0F) << 12) | ((p[1] & 0x3F) << 6) | (p[2] & 0x3F); return 3;
-  }
-  if (c >= 0xF0 && c <= 0xF4) {
-    if (!cont(1) || !cont(2) || !cont(3)) return 0;
-    if (c == 0xF0 && p[1] < 0x90) return 0;   // overlong
-    if (c == 0xF4 && p[1] >= 0x90) return 0;  // above U+10FFFF
-    *cp = ((c & 0x07) << 18) | ((p[1] & 0x3F) << 12) | ((p[2] & 0x3F) << 6) | (p[3] & 0x3F); return 4;
-  }
-  return 0;  // 0x80-0xC1 (continuation / overlong lead), 0xF5-0xFF
-}
-static bool is_rust_whitespace(uint32_t c) {
-  return (c >= 0x09 && c <= 0x0D) || c == 0x20 || c == 0x85 || c == 0xA0 || c == 0x1680 || (c >= 0x2000 && c <= 0x200A) ||
-         c == 0x2028 || c == 0x2029 || c == 0x202F || c == 0x205F || c == 0x3000;
-}
-std::vector<std::string> load_dictionary(const std::vector<uint8_t>& bytes) {
-  const unsigned char* p = bytes.data();
-  const size_t n = bytes.size();
-  std::vector<std::string> dict;
-  dict.push_back("blank");
-  size_t pos = 0;
-  while (pos < n) {
-    // one line: [pos, e) without its terminator
-    size_t e = pos;
-    while (e < n && p[e] != '\n') e++;
-    size_t le = e;
-    if (e < n && le > pos && p[le - 1] == '\r') le--;
-    // trim: first / last non-whitespace char, validating as we decode
-    size_t first = std::string::npos, last_end = 0;
-    for (size_t i = pos; i < le;) {
-      uint32_t cp;
-      int k = utf8_decode_strict(p + i, le - i, &cp);
-      if (k == 0) throw RtError(RT_ERR_UTF8, "dictionary is not valid UTF-8 (byte offset " + std::to_string(i) + ")");
-      if (!is_rust_whitespace(cp)) { if (first == std::string::npos) first = i; last_end = i + (size_t)k; }
-      i += (size_t)k;
-    }
-    dict.push_back(first == std::string::npos ? std::string() : std::string((const char*)p + first, last_end - first));
-    if (e >= n) break;
-    pos = e + 1;
-  }
-  dict.push_back(" ");
-  return dict;
-}
-std::vector<uint32_t> compile_charset(const std::vector<std::string>& dict, const char* utf8, size_t len, const int32_t* ids,
-                                      int n_ids) {
-  const int classes = (int)dict.size();
-  std::vector<uint32_t> mask((size_t)cs::mask_words(classes), 0u);
-  auto add = [&](int c) { mask[(size_t)c >> 5] |= 1u << (c & 31); };
-  add(0);
-  const unsigned char* p = (const unsigned char*)utf8;
-  for (size_t i = 0; i < len;) {
-    uint32_t cp;
-    const int k = utf8_decode_strict(p + i, len - i, &cp);
-    if (k == 0) throw RtError(RT_ERR_UTF8, "charset: the text is not valid UTF-8 (byte offset " + std::to_string(i) + ")");
-    bool any = false;
-    for (int c = 1; c < classes; c++)   // (class 0 is the blank, whatever its placeholder text)
-      if (dict[(size_t)c].size() == (size_t)k && memcmp(dict[(size_t)c].data(), p + i, (size_t)k) == 0) { add(c); any = true; }
-    if (!any) {
-      char b[64];
-      snprintf(b, sizeof b, "charset: U+%04X matches no dictionary entry", (unsigned)cp);
-      throw RtError(RT_ERR_INVALID, b);
-    }
-    i += (size_t)k;
-  }
-  for (int j = 0; j < n_ids; j++) {
-    if (ids[j] < 0 || ids[j] >= classes)
-      throw RtError(RT_ERR_INVALID, "charset: class id " + std::to_string(ids[j]) + " is outside [0, " + std::to_string(classes) + ")");
-    add(ids[j]);
-  }
-  return mask;
-}
-void compile_lexicon(const std::vector<std::string>& dict, const char* utf8, size_t len, const int32_t* ids,
-                     const int32_t* entry_lens, int n_id_entries, std::vector<int32_t>& ids_out, std::vector<int32_t>& lens_out) {
-  const int classes = (int)dict.size();
-  ids_out.clear(); lens_out.clear();
-  // every class whose whole entry is one code point, under its bytes: the lowest id wins (class 0 is the blank, whatever its
-  // placeholder text)
-  std::unordered_map<std::string, int> one;
-  for (int c = classes - 1; c >= 1; c--) {
-    const std::string& d = dict[(size_t)c];
-    uint32_t cp;
-    if (!d.empty() && (size_t)utf8_decode_strict((const unsigned char*)d.data(), d.size(), &cp) == d.size()) one[d] = c;
-  }
-  auto entry_done = [&](int n) {
-    if (n > lx::MAX_LEN)
-      throw RtError(RT_ERR_INVALID, "lexicon: entry " + std::to_string(lens_out.size()) + " has " + std::to_string(n) +
-                                        " tokens, more than RT_LEXICON_MAX_LEN (" + std::to_string(lx::MAX_LEN) + ")");
-    if ((int)lens_out.size() >= lx::MAX_ENTRIES)
-      throw RtError(RT_ERR_CAPACITY, "lexicon: more than RT_LEXICON_MAX_ENTRIES (" + std::to_string(lx::MAX_ENTRIES) + ") entries");
-    lens_out.push_back(n);
-  };
-  const unsigned char* p = (const unsigned char*)utf8;
-  for (size_t pos = 0; pos < len;) {
-    size_t e = pos;
-    while (e < len && p[e] != '\n') e++;
-    size_t le = e;
-    if (e < len && le > pos && p[le - 1] == '\r') le--;
-    size_t first = std::string::npos, last_end = 0;   // (trimmed as a dictionary line is)
-    for (size_t i = pos; i < le;) {
-      uint32_t cp;
-      const int k = utf8_decode_strict(p + i, le - i, &cp);
-      if (k == 0) throw RtError(RT_ERR_UTF8, "lexicon: the text is not valid UTF-8 (byte offset " + std::to_string(i) + ")");
-      if (!is_rust_whitespace(cp)) { if (first == std::string::npos) first = i; last_end = i + (size_t)k; }
-      i += (size_t)k;
-    }
-    if (first != std::string::npos) {
-      int n = 0;
-      for (size_t i = first; i < last_end;) {
-        uint32_t cp;
-        const int k = utf8_decode_strict(p + i, last_end - i, &cp);
-        const auto it = one.find(std::string((const char*)p + i, (size_t)k));
-        if (it == one.end()) {
-          char b[96];
-          snprintf(b, sizeof b, "lexicon: U+%04X in entry %zu matches no dictionary entry", (unsigned)cp, lens_out.size());
-          throw RtError(RT_ERR_INVALID, b);
-        }
-        ids_out.push_back(it->second); n++;
-        i += (size_t)k;
-      }
-      entry_done(n);
-    }
-    pos = e + 1;
-  }
-  size_t o = 0;
-  for (int j = 0; j < n_id_entries; j++) {
-    const int n = entry_lens[j];
-    if (n <= 0) throw RtError(RT_ERR_INVALID, "lexicon: entry " + std::to_string(lens_out.size()) + " is empty");
-    for (int i = 0; i < n && i < lx::MAX_LEN; i++) {
-      const int c = ids[o + (size_t)i];
-      if (c < 1 || c >= classes)
-        throw RtError(RT_ERR_INVALID, "lexicon: class id " + std::to_string(c) + " in entry " + std::to_string(lens_out.size()) +
-                                          " is outside [1, " + std::to_string(classes) + ")");
-      ids_out.push_back(c);
-    }
-    entry_done(n);
-    o += (size_t)n;
-  }
-  if (lens_out.empty()) throw RtError(RT_ERR_INVALID, "lexicon: no entry");
-}
-}  // namespace rt
 
 // ---------------------------------------------------------------------------
 // construction (RettoSession::new, session.rs:62-73; RettoWorker::new, worker.rs:91-98)
@@ -408,178 +244,6 @@ void rt_session::rec_forward_ragged(const float* nchw, int n, const int* widths,
   nn::softmax_rows(st, logits, rec->logits_ld(), Lt.total, C, probs);
   RT_HIP_CHECK(hipMemcpyAsync(out, probs, (size_t)Lt.total * C * 4, hipMemcpyDeviceToHost, st));
   sync();
-}
-
-void rt_session::ctc_candidates(const SvtrCore& core, const float* z5, const int* idx, const float* prob, const ImgGeom* lines,
-                                const int* n_tokens, int n_lines, long long rows, int K, int chunk_rows, int* cols, cc::Cand* cands,
-                                const int* row_set, const uint32_t* masks, int words) {
-  if (n_lines <= 0 || rows <= 0) return;
-  int *kept_row = nullptr, *kept_slot = nullptr, *d_kept = nullptr;
-  if (K > 1) { kept_row = scratch.alloc<int>((size_t)rows); kept_slot = scratch.alloc<int>((size_t)rows); d_kept = scratch.alloc<int>(1); }
-  { ProfScope ps(&prof, st, "ctc_kept_rows");
-    pp::ctc_kept_rows(st, idx, prob, lines, n_tokens, n_lines, K, cols, cands, kept_row, kept_slot, d_kept); }
-  if (K <= 1) return;
-  // the only host wait of the option: the logits GEMMs are sized by the number of kept rows (about a tenth of the time steps)
-  int* h_kept = pinned.alloc<int>(1);
-  RT_HIP_CHECK(hipMemcpyAsync(h_kept, d_kept, sizeof(int), hipMemcpyDeviceToHost, st));
-  sync();
-  const int kept = (int)std::min<long long>(std::max(*h_kept, 0), rows);
-  if (kept == 0) return;
-  const int chunk = chunk_rows > 0 ? chunk_rows : cc::CAND_CHUNK, cap = std::min(chunk, kept), ld = round_up(core.classes, 4);
-  const size_t zc_n = ((size_t)cap + 256) * core.D;   // (zero rows past the chunk: a GEMM tile's loads stay inside the allocation)
-  float* zc = scratch.alloc<float>(zc_n);
-  float* logits = scratch.alloc<float>((size_t)cap * ld);
-  RT_HIP_CHECK(hipMemsetAsync(zc, 0, zc_n * sizeof(float), st));
-  RunCtx c = ctx(&scratch);
-  for (int c0 = 0; c0 < kept; c0 += chunk) {   // (stream order lets the chunks share zc and logits)
-    const int m = std::min(chunk, kept - c0);
-    { ProfScope ps(&prof, st, "ctc_gather_rows");
-      pp::ctc_gather_rows(st, z5, core.D, kept_row + c0, m, zc); }
-    core.logits_rows(c, zc, m, logits);
-    ProfScope ps(&prof, st, "ctc_topk");
-    pp::ctc_topk(st, logits, ld, core.classes, kept_slot + c0, m, K, cands, kept_row + c0, row_set, masks, words);
-  }
-}
-
-void rt_session::ctc_charset(const SvtrCore& core, const float* z5, const int* d_rows, int n_rows, const int* d_row_set,
-                             const uint32_t* masks, int words, int chunk_rows, int* idx, float* prob) {
-  if (n_rows <= 0) return;
-  const int chunk = chunk_rows > 0 ? chunk_rows : cc::CAND_CHUNK, cap = std::min(chunk, n_rows), ld = round_up(core.classes, 4);
-  const size_t zc_n = ((size_t)cap + 256) * core.D;   // (zero rows past the chunk: a GEMM tile's loads stay inside the allocation)
-  float* zc = scratch.alloc<float>(zc_n);
-  float* logits = scratch.alloc<float>((size_t)cap * ld);
-  RT_HIP_CHECK(hipMemsetAsync(zc, 0, zc_n * sizeof(float), st));
-  RunCtx c = ctx(&scratch);
-  for (int c0 = 0; c0 < n_rows; c0 += chunk) {   // (stream order lets the chunks share zc and logits)
-    const int m = std::min(chunk, n_rows - c0);
-    { ProfScope ps(&prof, st, "ctc_gather_rows");
-      pp::ctc_gather_rows(st, z5, core.D, d_rows + c0, m, zc); }
-    core.logits_rows(c, zc, m, logits);
-    ProfScope ps(&prof, st, "ctc_charset_argmax");
-    pp::ctc_charset_argmax(st, logits, ld, core.classes, d_rows + c0, d_row_set, masks, words, m, idx, prob);
-  }
-}
-
-int rt_session::charset_create(const char* utf8, size_t len, const int32_t* ids, int n_ids) {
-  rt_charsets& C = *charsets;
-  if ((int)C.ids.size() >= cs::MAX_SETS)
-    throw RtError(RT_ERR_CAPACITY, "rt_charset_create: the session holds RT_MAX_CHARSETS (" + std::to_string(cs::MAX_SETS) + ") charsets already");
-  const std::vector<uint32_t> mask = compile_charset(dict, utf8, len, ids, n_ids);
-  RT_HIP_CHECK(hipSetDevice(device));
-  C.words = (int)mask.size();
-  if (!C.d_masks) RT_HIP_CHECK(hipMalloc((void**)&C.d_masks, (size_t)cs::MAX_SETS * mask.size() * sizeof(uint32_t)));
-  // (a blocking copy; no lane has work queued: this is a guarded call and every pipeline call ends with its streams drained)
-  RT_HIP_CHECK(hipMemcpy(C.d_masks + C.ids.size() * mask.size(), mask.data(), mask.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-  std::vector<int32_t> members;
-  for (int c = 0; c < (int)dict.size(); c++) if (cs::allowed(mask.data(), c)) members.push_back(c);
-  C.ids.push_back(std::move(members));
-  return (int)C.ids.size();
-}
-
-void rt_session::ctc_lexicon(const SvtrCore& core, const float* z5, const lx::Line* h_lines, const lx::Line* d_lines, int n_lines,
-                             const int* d_rows, int n_rows, int max_waves, const lx::Lex* d_lex, const lx::Entry* d_entries,
-                             const int* d_order, const int* d_ids, int chunk_rows, float* loglik, lx::Match* matches, int* counts,
-                             const LexSnap* snap) {
-  if (n_lines <= 0) return;
-  const int chunk = chunk_rows > 0 ? chunk_rows : cc::CAND_CHUNK, ld = round_up(core.classes, 4);
-  // chunks of whole lines: [i0, i1) takes lines while their rows fit the chunk, and always its first line
-  auto chunk_end = [&](int i0) {
-    int i1 = i0 + 1, rows = h_lines[i0].T;
-    while (i1 < n_lines && i1 - i0 < lx::LINES_PER_CHUNK && rows + h_lines[i1].T <= chunk) rows += h_lines[i1++].T;
-    return i1;
-  };
-  int cap = 1;
-  for (int i0 = 0; i0 < n_lines;) {
-    const int i1 = chunk_end(i0);
-    cap = std::max(cap, h_lines[i1 - 1].row0 + h_lines[i1 - 1].T - h_lines[i0].row0);
-    i0 = i1;
-  }
-  const size_t zc_n = ((size_t)cap + 256) * core.D;   // (zero rows past the chunk: a GEMM tile's loads stay inside the allocation)
-  float* zc = scratch.alloc<float>(zc_n);
-  float* logits = scratch.alloc<float>((size_t)cap * ld);
-  float* lse = scratch.alloc<float>((size_t)cap);
-  // (lexicon snap: the backpointers of a chunk's long lines, two 64-bit ballots per row)
-  void* bp = snap ? scratch.alloc_bytes((size_t)cap * 16) : nullptr;
-  RT_HIP_CHECK(hipMemsetAsync(zc, 0, zc_n * sizeof(float), st));
-  RunCtx c = ctx(&scratch);
-  for (int i0 = 0; i0 < n_lines;) {   // (stream order lets the chunks share zc, logits and lse)
-    const int i1 = chunk_end(i0), r0 = h_lines[i0].row0, m = h_lines[i1 - 1].row0 + h_lines[i1 - 1].T - r0;
-    if (r0 + m > n_rows) throw RtError(RT_ERR_SHAPE, "ctc_lexicon: the lines' rows exceed the row list");
-    if (m > 0) {
-      { ProfScope ps(&prof, st, "ctc_gather_rows");
-        pp::ctc_gather_rows(st, z5, core.D, d_rows + r0, m, zc); }
-      core.logits_rows(c, zc, m, logits);
-      { ProfScope ps(&prof, st, "ctc_row_lse");
-        pp::ctc_row_lse(st, logits, ld, core.classes, m, lse); }
-    }
-    { ProfScope ps(&prof, st, "ctc_lexicon_forward");
-      pp::ctc_lexicon_forward(st, logits, ld, lse, d_lines + i0, i1 - i0, r0, max_waves, d_lex, d_entries, d_order, d_ids, loglik); }
-    if (snap) {   // (a line never straddles chunks: its matches are complete, and its logits still resident, here)
-      { ProfScope ps(&prof, st, "ctc_lexicon_topk");
-        pp::ctc_lexicon_topk(st, d_lines + i0, i1 - i0, d_lex, loglik, matches, counts); }
-      ProfScope ps(&prof, st, "ctc_lexicon_align");
-      pp::ctc_lexicon_align(st, logits, ld, lse, d_lines + i0, i1 - i0, r0, d_lex, d_entries, d_ids, snap->d_min_post, matches, counts,
-                            d_rows, bp, snap->idx, snap->prob, snap->snapped, snap->vit);
-    }
-    i0 = i1;
-  }
-  if (!snap) {   // (without snap: one top-K over all the group's lines)
-    ProfScope ps(&prof, st, "ctc_lexicon_topk");
-    pp::ctc_lexicon_topk(st, d_lines, n_lines, d_lex, loglik, matches, counts);
-  }
-}
-
-int rt_session::lexicon_create(const char* utf8, size_t len, const int32_t* ids, const int32_t* entry_lens, int n_id_entries) {
-  rt_lexicons& X = *lexicons;
-  if ((int)X.host.size() >= lx::MAX_LEXICONS)
-    throw RtError(RT_ERR_CAPACITY, "rt_lexicon_create: the session holds RT_MAX_LEXICONS (" + std::to_string(lx::MAX_LEXICONS) + ") lexicons already");
-  std::unique_ptr<rt_lexicons::Host> h(new rt_lexicons::Host());
-  compile_lexicon(dict, utf8, len, ids, entry_lens, n_id_entries, h->ids, h->lens);
-  int o = 0;
-  for (int n : h->lens) {
-    h->off.push_back(o);
-    std::string t;
-    for (int i = 0; i < n; i++) t += dict[(size_t)h->ids[(size_t)(o + i)]];
-    h->text.push_back(std::move(t));
-    o += n;
-  }
-  lx::Tables tb = X.tb;
-  tb.add(h->ids.data(), h->lens.data(), (int)h->lens.size());
-  // the device tables are rebuilt whole (blocking copies; no lane has work queued: this is a guarded call and every pipeline
-  // call ends with its streams drained)
-  RT_HIP_CHECK(hipSetDevice(device));
-  int32_t* d_ids = nullptr; lx::Entry* d_entries = nullptr; int32_t* d_order = nullptr; lx::Lex* d_lex = nullptr;
-  auto up = [&](auto** d, const auto& v) {
-    RT_HIP_CHECK(hipMalloc((void**)d, v.size() * sizeof(v[0])));
-    RT_HIP_CHECK(hipMemcpy(*d, v.data(), v.size() * sizeof(v[0]), hipMemcpyHostToDevice));
-  };
-  try {
-    up(&d_ids, tb.ids); up(&d_entries, tb.entries); up(&d_order, tb.order); up(&d_lex, tb.lex);
-  } catch (...) {
-    if (d_ids) (void)hipFree(d_ids); if (d_entries) (void)hipFree(d_entries); if (d_order) (void)hipFree(d_order); if (d_lex) (void)hipFree(d_lex);
-    throw;
-  }
-  X.free_device();
-  X.d_ids = d_ids; X.d_entries = d_entries; X.d_order = d_order; X.d_lex = d_lex;
-  X.tb = std::move(tb);
-  X.host.push_back(std::move(h));
-  return (int)X.host.size();
-}
-
-void rt_session::lexicon_set_snap(int lexicon, float min_posterior) {
-  rt_lexicons& X = *lexicons;
-  if (lexicon < 1 || lexicon > (int)X.host.size())
-    throw RtError(RT_ERR_INVALID, "rt_lexicon_set_snap: unknown lexicon id " + std::to_string(lexicon));
-  if (!(min_posterior >= 0.0f && min_posterior <= 1.0f))   // (a NaN fails both)
-    throw RtError(RT_ERR_INVALID, "rt_lexicon_set_snap: min_posterior " + std::to_string(min_posterior) + " is outside [0, 1]");
-  // (blocking copies; no lane has work queued: this is a guarded call and every pipeline call ends with its streams drained)
-  RT_HIP_CHECK(hipSetDevice(device));
-  if (!X.d_snap) {
-    RT_HIP_CHECK(hipMalloc((void**)&X.d_snap, sizeof X.snap));
-    RT_HIP_CHECK(hipMemcpy(X.d_snap, X.snap, sizeof X.snap, hipMemcpyHostToDevice));
-  }
-  RT_HIP_CHECK(hipMemcpy(X.d_snap + (lexicon - 1), &min_posterior, sizeof(float), hipMemcpyHostToDevice));
-  X.snap[lexicon - 1] = min_posterior;
 }
 
 // ---------------------------------------------------------------------------
@@ -1136,12 +800,10 @@ void rec_groups(rt_session& s, Pipeline& P) {
   }
   if (!P.line_lex.empty()) { P.d_lexm = s.arena.alloc<lx::Match>((size_t)P.NLp * lx::MATCHES); P.d_lexn = s.arena.alloc<int>(P.NLp); }
   // lexicon snap (ctc_lexicon_align.h): a line snaps only where its lexicon has min_posterior > 0
-  auto snap_on = [&](int li) { return P.line_lex[li] > 0 && s.lexicons->snap[P.line_lex[li] - 1] > 0.0f; };
-  for (int li = 0; li < P.NL && !P.line_lex.empty() && !P.d_lexs; li++)
-    if (snap_on(li)) {   // (zeroed: the lexicon lines of a group without a snap-enabled line are never written)
-      P.d_lexs = s.arena.alloc<int>(P.NLp);
-      RT_HIP_CHECK(hipMemsetAsync(P.d_lexs, 0, (size_t)P.NLp * sizeof(int), s.st));
-    }
+  if (std::any_of(P.line_lex.begin(), P.line_lex.end(), [&](int k) { return k > 0 && s.lexicons->snap[k - 1] > 0.0f; })) {
+    P.d_lexs = s.arena.alloc<int>(P.NLp);   // (zeroed: the lexicon lines of a group without a snap-enabled line are never written)
+    RT_HIP_CHECK(hipMemsetAsync(P.d_lexs, 0, (size_t)P.NLp * sizeof(int), s.st));
+  }
   static const long long REC_GROUP_PX = getenv("RT_REC_GROUP_PX") ? atoll(getenv("RT_REC_GROUP_PX")) : (long long)24000000;  // measured sweet spot (profiles/README.md)
   for (int l0 = 0; l0 < P.NL;) {
     const int l1 = group_end(l0, P.NL, 0, REC_GROUP_PX, [&](int l) { return (long long)rh * P.line_W[l]; });
@@ -1165,67 +827,18 @@ void rec_groups(rt_session& s, Pipeline& P) {
     RunCtx c = s.ctx(&s.scratch);
     // (the token count per line only depends on the widths, so the offsets are known before the net runs)
     const long long t0 = P.tok_off[l0];
-    // rec charsets (ctc_charset.h): the rows of the group's restricted lines in line order, and every row's set
-    int n_crows = 0; int *d_crows = nullptr, *d_row_set = nullptr;
-    if (!P.line_set.empty()) {
-      for (int li = l0; li < l1; li++) if (P.line_set[li] > 0) n_crows += (int)(P.tok_off[li + 1] - P.tok_off[li]);
-      if (n_crows > 0) {
-        const size_t rows = (size_t)(P.tok_off[l1] - t0);
-        int* h_row_set = s.pinned.alloc<int>(rows); int* h_crows = s.pinned.alloc<int>(n_crows);
-        int n = 0;
-        for (int li = l0; li < l1; li++)
-          for (long long r = P.tok_off[li] - t0; r < P.tok_off[li + 1] - t0; r++) {
-            h_row_set[r] = P.line_set[li];
-            if (P.line_set[li] > 0) h_crows[n++] = (int)r;
-          }
-        d_row_set = s.scratch.alloc<int>(rows); d_crows = s.scratch.alloc<int>(n_crows);
-        RT_HIP_CHECK(hipMemcpyAsync(d_row_set, h_row_set, rows * sizeof(int), hipMemcpyHostToDevice, s.st));
-        RT_HIP_CHECK(hipMemcpyAsync(d_crows, h_crows, (size_t)n_crows * sizeof(int), hipMemcpyHostToDevice, s.st));
-      }
-    }
-    int n_lrows = -1;   // rec lexicons: the rows of the group's lexicon lines (-1: the group has no such line)
-    if (!P.line_lex.empty())
-      for (int li = l0; li < l1; li++)
-        if (P.line_lex[li] > 0) n_lrows = std::max(n_lrows, 0) + (int)(P.tok_off[li + 1] - P.tok_off[li]);
+    const rt_lexicons& X = *s.lexicons;
+    const RecTailPlan tail = rec_tail_plan(P.tok_off.data(), l0, l1, P.line_set.empty() ? nullptr : P.line_set.data(),
+                                           P.line_lex.empty() ? nullptr : P.line_lex.data(), X.tb, X.snap);
+    if (!tail.table_fits())
+      throw RtError(RT_ERR_CAPACITY, "rec lexicons: " + std::to_string(tail.lines.size()) + " lines of one rec group carry lexicons of " +
+                                         std::to_string(tail.table) + " entries in all, more than the " + std::to_string(lx::MAX_GROUP_TABLE) +
+                                         " likelihoods a group's table holds: use smaller lexicons or fewer lexicon lines per call");
     const float* z5 = nullptr;   // the head's input, for the candidates', the charsets' and the lexicons' logits
     { ProfOuter po(&s.prof, s.st, "net/rec");
-      s.rec->run(c, x, L0, Lt, d_idx + t0, d_prob + t0, cand_k > 1 || n_crows > 0 || n_lrows >= 0 ? &z5 : nullptr); }  // fused CTC head: logits never reach HBM
-    if (Lt.total != P.tok_off[l1] - t0) throw RtError(RT_ERR_SHAPE, "token count mismatch");
-    if (n_crows > 0)   // the restricted rows' (idx, prob) are replaced before anything reads them
-      s.ctc_charset(s.rec->core(), z5, d_crows, n_crows, d_row_set, s.charsets->d_masks, s.charsets->words, 0, d_idx + t0, d_prob + t0);
-    // lexicon snap (ctc_lexicon_align.h): a group with a snap-enabled lexicon line runs its lexicons HERE, behind the charsets
-    // and in front of the decode, which then reads the snapped lines' aligned rows.  Any other group keeps the order below
-    bool snap_group = false;
-    for (int li = l0; li < l1 && P.d_lexs && !snap_group; li++) snap_group = snap_on(li);
-    auto run_lexicons = [&] {   // rec lexicons (ctc_lexicon.h): the group's lexicon lines, their rows and their loglik rows
-      const rt_lexicons& X = *s.lexicons;
-      int nl = 0;
-      for (int li = l0; li < l1; li++) nl += P.line_lex[li] > 0 ? 1 : 0;
-      lx::Line* h_lines = s.pinned.alloc<lx::Line>(nl); int* h_rows = s.pinned.alloc<int>(std::max(n_lrows, 1));
-      int n = 0, r = 0, max_waves = 0; long long out = 0;
-      for (int li = l0; li < l1; li++) {
-        if (P.line_lex[li] <= 0) continue;
-        const int T = (int)(P.tok_off[li + 1] - P.tok_off[li]);
-        const lx::Lex& x = X.tb.lex[(size_t)P.line_lex[li] - 1];
-        h_lines[n++] = lx::Line{r, T, P.line_lex[li] - 1, li, out};
-        for (int t = 0; t < T; t++) h_rows[r++] = (int)(P.tok_off[li] - t0) + t;
-        out += x.n; max_waves = std::max(max_waves, lx::waves_of(x));
-      }
-      lx::Line* d_lines = s.scratch.alloc<lx::Line>(nl); int* d_rows = s.scratch.alloc<int>(std::max(n_lrows, 1));
-      if (out > lx::MAX_GROUP_TABLE)
-        throw RtError(RT_ERR_CAPACITY, "rec lexicons: " + std::to_string(nl) + " lines of one rec group carry lexicons of " + std::to_string(out) +
-                                           " entries in all, more than the " + std::to_string(lx::MAX_GROUP_TABLE) +
-                                           " likelihoods a group's table holds: use smaller lexicons or fewer lexicon lines per call");
-      float* loglik = s.scratch.alloc<float>((size_t)out);
-      RT_HIP_CHECK(hipMemcpyAsync(d_lines, h_lines, (size_t)nl * sizeof(lx::Line), hipMemcpyHostToDevice, s.st));
-      if (n_lrows > 0) RT_HIP_CHECK(hipMemcpyAsync(d_rows, h_rows, (size_t)n_lrows * sizeof(int), hipMemcpyHostToDevice, s.st));
-      const rt_session::LexSnap snap{X.d_snap, d_idx + t0, d_prob + t0, P.d_lexs, nullptr};
-      s.ctc_lexicon(s.rec->core(), z5, h_lines, d_lines, nl, d_rows, n_lrows, max_waves, X.d_lex, X.d_entries, X.d_order, X.d_ids, 0,
-                    loglik, P.d_lexm, P.d_lexn, snap_group ? &snap : nullptr);
-    };
-    if (snap_group) run_lexicons();
-    { ProfScope ps(&s.prof, s.st, "ctc_decode");
-      pp::ctc_decode(s.st, d_idx + t0, d_prob + t0, Lt.d, ln, P.d_tok + t0, P.d_meta.ntok + l0, P.d_meta.rscore + l0); }
+      s.rec->run(c, x, L0, Lt, d_idx + t0, d_prob + t0, tail.needs_z5(cand_k) ? &z5 : nullptr); }  // fused CTC head: logits never reach HBM
+    if (Lt.total != tail.rows) throw RtError(RT_ERR_SHAPE, "token count mismatch");
+    rt_session::WordBoxes words{};
     if (s.cfg.rec_return_word_box) {
       pp::WordLineDesc* hwl = s.pinned.alloc<pp::WordLineDesc>(ln);
       for (int k = 0; k < ln; k++) {
@@ -1239,16 +852,14 @@ void rec_groups(rt_session& s, Pipeline& P) {
         D.g.cw = P.plan.dims[li].cw; D.g.ch = P.plan.dims[li].ch;
         memcpy(D.g.inv, cd.inv, sizeof D.g.inv);
       }
-      pp::WordLineDesc* dw = s.scratch.alloc<pp::WordLineDesc>(ln);
-      RT_HIP_CHECK(hipMemcpyAsync(dw, hwl, (size_t)ln * sizeof(pp::WordLineDesc), hipMemcpyHostToDevice, s.st));
-      ProfScope ps(&s.prof, s.st, "word_boxes");
-      pp::word_boxes(s.st, d_idx + t0, P.d_tok + t0, P.d_meta.ntok + l0, P.d_meta.label + l0, P.d_meta.cscore + l0, s.cfg.cls_thresh,
-                     s.d_word_raw, dw, ln, d_wcol + t0, P.d_wcount + l0, P.d_words + t0);
+      words = {hwl, P.d_meta.label + l0, P.d_meta.cscore + l0, d_wcol + t0, P.d_wcount + l0, P.d_words + t0};
     }
-    if (n_lrows >= 0 && !snap_group) run_lexicons();
-    if (cand_k > 0)   // (before the next group rewinds the scratch arena z5 lives in)
-      s.ctc_candidates(s.rec->core(), z5, d_idx + t0, d_prob + t0, Lt.d, P.d_meta.ntok + l0, ln, Lt.total, cand_k, 0,
-                       P.d_ccol + t0, P.d_cands + t0 * cand_k, d_row_set, d_row_set ? s.charsets->d_masks : nullptr, s.charsets->words);
+    const rt_session::RecTail t{z5, d_idx + t0, d_prob + t0, Lt.d, ln, s.charsets->d_masks, s.charsets->words,
+                                X.d_lex, X.d_entries, X.d_order, X.d_ids, X.d_snap, cand_k, 0,
+                                P.d_tok + t0, P.d_meta.ntok + l0, P.d_meta.rscore + l0, nullptr, P.d_lexm, P.d_lexn, P.d_lexs, nullptr,
+                                P.d_ccol ? P.d_ccol + t0 : nullptr, P.d_cands ? P.d_cands + t0 * cand_k : nullptr,
+                                words.h_lines ? &words : nullptr};
+    s.rec_tail(tail, s.rec->core(), t);
     l0 = l1;
   }
 }
@@ -1342,6 +953,23 @@ void results(const rt_session& s, const Pipeline& P, rt_results& res) {
     }
   }
 }
+// A per-line option of the rec tail (rec charsets, rec lexicons): the regions' ids where the call gives them (line k of page i is
+// line first_line + k of the crop plan: the rec plan reorders widths, never lines), otherwise the session default on every line;
+// empty when no line has one.  Ids are 1-based in [1, n_ids], 0: none.
+std::vector<int> line_option(const Pipeline& P, const int* const* per_region, int dflt, int n_ids, const char* name) {
+  std::vector<int> v;
+  if (per_region) {
+    v.assign((size_t)P.NL, 0);
+    for (int i = 0; i < P.n_pages; i++)
+      for (int k = 0; k < P.pg[i].n_boxes && per_region[i]; k++) v[(size_t)P.pg[i].first_line + k] = per_region[i][k];
+    if (std::none_of(v.begin(), v.end(), [](int x) { return x > 0; })) v.clear();
+  } else if (dflt > 0 && P.NL > 0) {
+    v.assign((size_t)P.NL, dflt);
+  }
+  for (int x : v)
+    if (x < 0 || x > n_ids) throw RtError(RT_ERR_INVALID, std::string("unknown rec ") + name + " id " + std::to_string(x));
+  return v;
+}
 }  // namespace
 std::string rt_format_f32_impl(float v) { return fnum(v); }
 
@@ -1373,36 +1001,8 @@ rt_results* rt_session::run_pages(const uint8_t* const* rgb, const int* hs, cons
     db_post(*this, P); tick.lap("dbpost enqueue");
     box_round_trip(*this, P, *res); tick.lap("sync #1 + box D2H");
   }
-  // rec charsets: line k of page i is line first_line + k of the crop plan (the rec plan reorders widths, never lines)
-  if (regions && regions->charsets) {
-    bool any = false;
-    for (int i = 0; i < n_pages; i++)
-      for (int k = 0; k < P.pg[i].n_boxes && regions->charsets[i]; k++) any |= regions->charsets[i][k] > 0;
-    if (any) {
-      P.line_set.assign((size_t)P.NL, 0);
-      for (int i = 0; i < n_pages; i++)
-        for (int k = 0; k < P.pg[i].n_boxes && regions->charsets[i]; k++) P.line_set[(size_t)P.pg[i].first_line + k] = regions->charsets[i][k];
-    }
-  } else if (rec_charset_default > 0 && P.NL > 0) {
-    P.line_set.assign((size_t)P.NL, rec_charset_default);
-  }
-  for (int v : P.line_set)
-    if (v < 0 || v > (int)charsets->ids.size()) throw RtError(RT_ERR_INVALID, "unknown rec charset id " + std::to_string(v));
-  // rec lexicons: the same, per line
-  if (regions && regions->lexicons) {
-    bool any = false;
-    for (int i = 0; i < n_pages; i++)
-      for (int k = 0; k < P.pg[i].n_boxes && regions->lexicons[i]; k++) any |= regions->lexicons[i][k] > 0;
-    if (any) {
-      P.line_lex.assign((size_t)P.NL, 0);
-      for (int i = 0; i < n_pages; i++)
-        for (int k = 0; k < P.pg[i].n_boxes && regions->lexicons[i]; k++) P.line_lex[(size_t)P.pg[i].first_line + k] = regions->lexicons[i][k];
-    }
-  } else if (rec_lexicon_default > 0 && P.NL > 0) {
-    P.line_lex.assign((size_t)P.NL, rec_lexicon_default);
-  }
-  for (int v : P.line_lex)
-    if (v < 0 || v > (int)lexicons->host.size()) throw RtError(RT_ERR_INVALID, "unknown rec lexicon id " + std::to_string(v));
+  P.line_set = line_option(P, regions ? regions->charsets : nullptr, rec_charset_default, (int)charsets->ids.size(), "charset");
+  P.line_lex = line_option(P, regions ? regions->lexicons : nullptr, rec_lexicon_default, (int)lexicons->host.size(), "lexicon");
   crop_stage(*this, P);
   if (P.NL > 0) {
     tick.lap("crop plan + warp enqueue");

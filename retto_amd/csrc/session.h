@@ -19,6 +19,7 @@
 #include "nets.h"
 #include "nets_f16.h"
 #include "prepost.h"
+#include "rec_tail_plan.h"
 #include "runtime.h"
 
 struct rt_results {
@@ -207,37 +208,44 @@ struct rt_session {
                          float* out);
   void ctc_decode(const float* probs, int n, int t, int c, int32_t* idx, float* prob, int32_t* tokens,
                   int32_t* n_tokens, float* scores);
-  // rec_return_candidates = K over the n_lines lines of one rec group (ctc_candidates.h): lines / n_tokens as pp::ctc_decode got
-  // and left them, rows = the group's time steps, z5 [rows, core.D] the head's input (only read when K > 1).  Kept token j of a
-  // line at first row o gets cols[o + j] and cands[(o + j) * K ...].  K > 1 waits for the stream once (the kept-row count sizes
-  // the logits GEMMs) and recomputes in chunks of chunk_rows kept rows (0: cc::CAND_CHUNK); the workspace comes from `scratch`.
-  // row_set / masks / words (rec charsets): a kept row r with row_set[r] = s >= 1 ranks the classes of set s only.
-  void ctc_candidates(const rt::SvtrCore& core, const float* z5, const int* idx, const float* prob, const rt::ImgGeom* lines,
-                      const int* n_tokens, int n_lines, long long rows, int K, int chunk_rows, int* cols, rt::cc::Cand* cands,
-                      const int* row_set = nullptr, const uint32_t* masks = nullptr, int words = 0);
-  // Rec charsets over one rec group (ctc_charset.h), between the net and pp::ctc_decode: d_rows [n_rows] = the time steps of the
-  // group's restricted lines in line order, d_row_set [the group's rows] = every row's set (0: none), both on the device; masks
-  // [.][words] on the device.  In chunks of chunk_rows rows (0: cc::CAND_CHUNK): row gather, the CTC FC, k_ctc_charset_argmax,
-  // which overwrites idx / prob of exactly those rows.  No host wait: the rows are known from the line widths.
-  void ctc_charset(const rt::SvtrCore& core, const float* z5, const int* d_rows, int n_rows, const int* d_row_set,
-                   const uint32_t* masks, int words, int chunk_rows, int* idx, float* prob);
+  // ---- the rec network's CTC tail (rec_tail.cpp) ----
+  // What rec_tail reads and writes for ONE rec group, everything on the device.  Row and line arrays start at the group's first
+  // row / line; the lexicon outputs (lexm, lexn, lexs, vit) are indexed by lx::Line::slot, the line's index in the call.
+  // (rec_return_word_box, word_boxes.h: pp::word_boxes' arguments; h_lines: the group's descriptors in pinned memory)
+  struct WordBoxes { const rt::pp::WordLineDesc* h_lines; const int* label; const float* cscore; int* cols; int* n_words; rt::wb::Word* words; };
+  struct RecTail {
+    const float* z5;                          // [rows, core.D] the head's input, inside a larger allocation (RecTailPlan::needs_z5)
+    int* idx; float* prob;                    // [rows] the fused head's argmax rows, in and out
+    const rt::ImgGeom* lines; int n_lines;    // the token level: {first row, 1, T} per line
+    const uint32_t* masks; int words;         // rec charsets: [.][words]
+    // rec lexicons: the device tables (lx::Tables) and the per-lexicon min_posterior (read in a snap group only)
+    const rt::lx::Lex* d_lex; const rt::lx::Entry* d_entries; const int* d_order; const int* d_ids; const float* d_min_post;
+    int cand_k, chunk_rows;                   // rec_return_candidates; rows per logits recompute (0: cc::CAND_CHUNK)
+    int* tok; int* ntok; float* rscore;       // pp::ctc_decode's outputs
+    float* loglik;                            // [plan.table], or null: taken from `scratch`
+    rt::lx::Match* lexm; int* lexn; int* lexs; float* vit;   // (lexs: snap groups only; vit: optional)
+    int* ccol; rt::cc::Cand* cands;           // cand_k > 0: the kept tokens' time steps and [cand_k] candidates
+    const WordBoxes* wb;                      // or null
+  };
+  // The tail of one rec group behind the net, in the one order that is right: the charsets replace the restricted rows' (idx, prob)
+  // before anything reads them; a snap group's lexicons run next, so that the decode reads the snapped lines' aligned rows;
+  // pp::ctc_decode; the word boxes; any other group's lexicons; the candidates last, for their host wait.  The plan's tables go
+  // through `pinned` into `scratch`, where the workspace comes from too: the caller rewinds it per group, after this.
+  void rec_tail(const rt::RecTailPlan& plan, const rt::SvtrCore& core, const RecTail& t);
+  // rec_return_candidates = K (ctc_candidates.h): kept token j of a line at first row o gets ccol[o + j] and cands[(o + j) * K ...].
+  // K > 1 waits for the stream once (the kept-row count sizes the logits GEMMs) and recomputes in chunks of kept rows.  d_row_set
+  // (rec charsets, or null): a kept row r with d_row_set[r] = s >= 1 ranks the classes of set s only.
+  void ctc_candidates(const rt::SvtrCore& core, const RecTail& t, long long rows, const int* d_row_set);
+  // Rec charsets (ctc_charset.h): d_rows [n_rows] / d_row_set [rows] = the plan's crows / row_set.  In chunks of rows: row gather,
+  // the CTC FC, k_ctc_charset_argmax, which overwrites idx / prob of exactly those rows.  No host wait.
+  void ctc_charset(const rt::SvtrCore& core, const RecTail& t, const int* d_rows, int n_rows, const int* d_row_set);
+  // Rec lexicons (ctc_lexicon.h) over the plan's lexicon lines, in chunks of whole lines of about chunk_rows rows (at least one
+  // line, so a line's T rows are resident together): row gather, the CTC FC, k_ctc_row_lse, k_ctc_lexicon_forward -> loglik; then
+  // one k_ctc_lexicon_topk over all lines -> lexm / lexn.  No host wait.  A snap group (ctc_lexicon_align.h) runs the top-K per chunk,
+  // then k_ctc_lexicon_align on the resident logits: it overwrites the snapped lines' rows of idx / prob and writes every lexs[slot].
+  void ctc_lexicon(const rt::RecTailPlan& plan, const rt::SvtrCore& core, const RecTail& t);
   // rt_charset_create: compiles the set (rt::compile_charset), stores it and returns its id
   int charset_create(const char* utf8, size_t len, const int32_t* ids, int n_ids);
-  // Rec lexicons over the lexicon lines of one rec group (ctc_lexicon.h), after the net and before the scratch arena that z5
-  // lives in is rewound.  h_lines / d_lines [n_lines]: the lines in line order on the host and on the device (row0 = the sum of
-  // the earlier lines' T); d_rows [n_rows]: their time steps of the group, line after line.  In chunks of whole lines of about
-  // chunk_rows rows (0: cc::CAND_CHUNK; at least one line, so a line's T rows are resident together): row gather, the CTC FC,
-  // k_ctc_row_lse, k_ctc_lexicon_forward -> loglik; then one k_ctc_lexicon_topk over all lines -> matches / counts.  max_waves:
-  // the largest lx::waves_of over the lines' lexicons.  No host wait; the workspace comes from `scratch`.
-  // snap (ctc_lexicon_align.h; null: off, today's launches in today's order): at least one of the lines' lexicons has
-  // min_posterior > 0.  Then k_ctc_lexicon_topk runs per chunk, over the chunk's lines, followed by k_ctc_lexicon_align while
-  // the chunk's logits are resident; it overwrites the snapped lines' rows of snap->idx / prob (the group's, indexed by d_rows)
-  // and writes snap->snapped[slot] for every line.  The caller runs pp::ctc_decode afterwards.
-  struct LexSnap { const float* d_min_post; int* idx; float* prob; int* snapped; float* vit; };
-  void ctc_lexicon(const rt::SvtrCore& core, const float* z5, const rt::lx::Line* h_lines, const rt::lx::Line* d_lines, int n_lines,
-                   const int* d_rows, int n_rows, int max_waves, const rt::lx::Lex* d_lex, const rt::lx::Entry* d_entries,
-                   const int* d_order, const int* d_ids, int chunk_rows, float* loglik, rt::lx::Match* matches, int* counts,
-                   const LexSnap* snap = nullptr);
   // rt_lexicon_create: compiles the entries (rt::compile_lexicon), stores them and returns the lexicon's id
   int lexicon_create(const char* utf8, size_t len, const int32_t* ids, const int32_t* entry_lens, int n_id_entries);
   // rt_lexicon_set_snap: the lexicon's min_posterior (ctc_lexicon_align.h), on the host and in the device table
@@ -285,6 +293,7 @@ struct rt_session {
 rt_session* rt_session_create(const rt_config* cfg);
 std::string rt_format_f32_impl(float v);  // serde_json / ryu form of an f32
 namespace rt {
+// (the three below live in rec_tail.cpp)
 // RecCharacter::new (rec_processor.rs:29-46) with Rust's from_utf8 / lines / trim semantics
 std::vector<std::string> load_dictionary(const std::vector<uint8_t>& bytes);
 // A rec charset (ctc_charset.h) as its mask of cs::mask_words(dict.size()) words: the blank, every dictionary class whose whole

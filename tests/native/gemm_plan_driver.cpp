@@ -11,13 +11,19 @@
 //      <pw_act> <pw_has_lab> <pw_bias>          (the output pitch is chan_pitch(N), as run_lc's)
 //     (lc_wave / dw_sweep -1: what the environment selected when the driver started)
 //     -> thin | wave | lds <instance> <tile rows> <grid_x>    or    unfused <se_rows> <the block's dw answer>
+//   tail <l0> <l1> <cand_k> <NL> <T of each of the NL lines> <1 + NL charset ids, or 0> <1 + NL lexicon ids, or 0>
+//        <n_lex> <n16 n32 n64 of each lexicon: its entries of 1, 8 and 16 ids> <1 + n_lex snap thresholds, or 0>
+//     -> rec_tail_plan() (rec_tail_plan.h) of lines [l0, l1): rows=.. z5=.. has_lex=.. snap=.. table=.. fits=.. max_waves=..
+//        row_set=a,b,.. crows=.. lines=row0:T:lex:slot:out,.. lrows=..   (an empty list prints as -)
 // (am_max != 0 sets the CTC-head statistics with am_tiles = gemm_argmax_tiles(Npad16); a_scale != 0 sets a scale and a row table)
 #include "nn.h"
+#include "rec_tail_plan.h"
 
 #include <cstdio>
 #include <iostream>
 #include <sstream>
 #include <string>
+#include <vector>
 
 using namespace rt;
 
@@ -43,6 +49,20 @@ static const char* kernel_name(nn::GemmKernel k) {
 static void print_dw(const nn::DwPlan& p) {
   static const char* const names[] = {"invalid", "rows32", "rows64", "sweep"};
   printf("%s %d %d %d %d %d %u %u\n", names[(int)p.kernel], p.kernel == nn::DwKernel::sweep ? p.inst : 0, p.R, p.lanes, p.spb, p.chunks, p.grid_x, p.grid_z);
+}
+
+static void print_list(const char* name, const std::vector<int>& v) {
+  printf(" %s=%s", name, v.empty() ? "-" : "");
+  for (size_t i = 0; i < v.size(); i++) printf(i ? ",%d" : "%d", v[i]);
+}
+// an optional array of a query: a 0, or a 1 and n values
+template <typename T>
+static bool read_optional(std::istream& in, size_t n, std::vector<T>& v) {
+  int has = 0;
+  in >> has;
+  v.assign(has ? n : 0, T());
+  for (T& x : v) in >> x;
+  return has != 0;
 }
 
 int main() {
@@ -94,6 +114,41 @@ int main() {
       static const char* const routes[] = {"unfused", "thin", "wave", "lds"};
       if (p.route != nn::LC_UNFUSED) printf("%s %d %d %u\n", routes[p.route], p.inst, p.tile_h, p.grid_x);
       else { printf("unfused %d ", p.se_rows); print_dw(p.dw); }
+    } else if (op == "tail") {
+      int l0, l1, cand_k, NL, n_lex = 0;
+      in >> l0 >> l1 >> cand_k >> NL;
+      if (!in || NL < 0 || l0 < 0 || l0 > l1 || l1 > NL) { printf("bad query\n"); return 2; }
+      std::vector<long long> tok_off((size_t)NL + 1, 0);
+      for (int i = 0; i < NL; i++) { int T; in >> T; tok_off[(size_t)i + 1] = tok_off[(size_t)i] + T; }
+      std::vector<int> sets, lexs;
+      std::vector<float> snaps;
+      const bool has_set = read_optional(in, (size_t)NL, sets), has_lex = read_optional(in, (size_t)NL, lexs);
+      in >> n_lex;
+      lx::Tables tb;
+      for (int k = 0; k < n_lex && in; k++) {
+        int n16, n32, n64;
+        in >> n16 >> n32 >> n64;
+        if (!in || n16 < 0 || n32 < 0 || n64 < 0) break;
+        std::vector<int32_t> lens;
+        lens.insert(lens.end(), (size_t)n16, 1); lens.insert(lens.end(), (size_t)n32, 8); lens.insert(lens.end(), (size_t)n64, 16);
+        size_t n_ids = 0;
+        for (int32_t n : lens) n_ids += (size_t)n;
+        const std::vector<int32_t> ids(n_ids, 1);
+        tb.add(ids.data(), lens.data(), (int)lens.size());
+      }
+      const bool has_snap = read_optional(in, (size_t)n_lex, snaps);
+      if (!in) { printf("bad query\n"); return 2; }
+      for (int v : lexs) if (v < 0 || v > n_lex) { printf("bad query\n"); return 2; }
+      const RecTailPlan p = rec_tail_plan(tok_off.data(), l0, l1, has_set ? sets.data() : nullptr, has_lex ? lexs.data() : nullptr, tb,
+                                          has_snap ? snaps.data() : nullptr);
+      printf("rows=%lld z5=%d has_lex=%d snap=%d table=%lld fits=%d max_waves=%d", p.rows, (int)p.needs_z5(cand_k), (int)p.has_lex(),
+             (int)p.snap, p.table, (int)p.table_fits(), p.max_waves);
+      print_list("row_set", p.row_set); print_list("crows", p.crows);
+      printf(" lines=%s", p.lines.empty() ? "-" : "");
+      for (size_t i = 0; i < p.lines.size(); i++)
+        printf("%s%d:%d:%d:%d:%lld", i ? "," : "", p.lines[i].row0, p.lines[i].T, p.lines[i].lex, p.lines[i].slot, p.lines[i].out);
+      print_list("lrows", p.lrows);
+      printf("\n");
     } else if (!op.empty()) {
       printf("unknown query %s\n", op.c_str());
       return 2;
