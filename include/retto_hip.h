@@ -483,6 +483,64 @@ RT_API int rt_debug_ctc_lexicon_align_host(const float* z5, const float* W, cons
                                            const int32_t* lex_first_entry, int n_lex, const float* lex_min_post, int32_t* idx,
                                            float* prob, int32_t* snapped_out, float* vit_out, float* loglik_out,
                                            rt_lexicon_match* matches_out, int32_t* n_matches_out);
+/* ---- rec patterns (retto_amd/csrc/ctc_pattern.h): a line's CTC decode constrained to a regular expression ----
+ * The pattern language, the compiled form (a trimmed DFA over class groups), the Viterbi rule and its tie order are stated in that
+ * header.  For the field whose format is known ("[0-9]{4}-[0-9]{2}-[0-9]{2}"): a line that carries a pattern decodes to the best
+ * CTC path whose collapsed string the pattern accepts -- text, tokens, time steps, score, word boxes, candidates (rank 0 = the
+ * path's (id, prob)) and JSON all follow, as for a lexicon snap.  A line too short for the pattern (T < min_steps) is unmatched
+ * and keeps its decode (its charset's, if it has one: the charset writes first).  Lines without a pattern are bit-identical to a
+ * run without patterns.  A line may not carry both a pattern and a lexicon: RT_ERR_INVALID naming the page and the region (for
+ * the session defaults: at the call), nothing queued.
+ * RT_PATTERN_MAX_STATES counts the states of the automaton as built (subset construction of the position automaton, dead states
+ * removed, NOT minimised: "[ab]*" has two states); RT_PATTERN_MAX_PAIRS counts the (state entered, class) pairs.  Either limit, or
+ * repeats that write out to more than 4096 atoms, gives RT_ERR_CAPACITY; a wide set (".{8}" over a large dictionary) belongs
+ * into a charset. */
+#define RT_MAX_PATTERNS 16
+#define RT_PATTERN_MAX_STATES 64
+#define RT_PATTERN_MAX_PAIRS 4096
+#define RT_PATTERN_MAX_BYTES 1024
+typedef struct rt_pattern_result { int32_t pattern, matched; float logprob, free_logprob; } rt_pattern_result;
+/* compiles utf8 [len] over the session's dictionary; *pattern_out = its 1-based id, valid until rt_destroy.  RT_ERR_UTF8 /
+ * RT_ERR_INVALID / RT_ERR_CAPACITY with a message naming the byte offset.  Fails while tickets are in flight. */
+RT_API int rt_pattern_create(rt_session* s, const char* utf8, size_t len, int* pattern_out);
+/* a pattern's states, pairs and the fewest time steps a line needs to match it (each optional); RT_ERR_INVALID for an unknown id */
+RT_API int rt_pattern_info(const rt_session* s, int pattern, int* states, int* pairs, int* min_steps);
+/* the pattern's text as given (NULL for an unknown id); library-owned */
+RT_API const char* rt_pattern_text(const rt_session* s, int pattern);
+/* the pattern of every line of the pipeline calls that follow (rt_submit_* takes it as it is at the call); 0 = none */
+RT_API int rt_set_rec_pattern(rt_session* s, int pattern);
+/* rt_run_regions_lexicons with one pattern id per region as well: -1 = the session default, 0 = none, >= 1 = that pattern; each
+ * of the three arrays, and each page's entry, may be NULL */
+RT_API int rt_run_regions_patterns(rt_session* s, const uint8_t* const* rgb, const int* hs, const int* ws, int n_pages, int mem,
+                                   const float* const* quads, const int* n_quads, const int32_t* const* charsets,
+                                   const int32_t* const* lexicons, const int32_t* const* patterns, rt_results** out);
+/* 1 where the line carried a pattern (*out, optional: which, whether it matched, the path's log-probability and the unconstrained
+ * best path's: logprob - free_logprob <= 0 is what the format cost; an unmatched line reports logprob = -inf), else 0 */
+RT_API int rt_results_rec_pattern(const rt_results* r, int page, int line, rt_pattern_result* out);
+/* The pattern compiler, GPU-free and sessionless: dict = dictionary file bytes (parsed as rt_parse_dictionary does), utf8 [len]
+ * the pattern.  group_of_out [group_cap >= classes], delta_out [delta_cap >= S * G] (-1: no arc), accept_out [accept_cap >= S];
+ * *S_out, *G_out, *P_out, *min_steps_out, *n_classes are written also when a cap was too small (RT_ERR_INVALID then, nothing
+ * copied).  RT_ERR_UTF8 / RT_ERR_INVALID / RT_ERR_CAPACITY with a message naming the byte offset (err: optional, err_cap bytes). */
+RT_API int rt_debug_pattern_compile(const void* dict, size_t dict_len, const char* utf8, size_t len, int32_t* group_of_out,
+                                    int group_cap, int32_t* delta_out, int delta_cap, int32_t* accept_out, int accept_cap, int* S_out,
+                                    int* G_out, int* P_out, int* min_steps_out, int* n_classes, char* err, size_t err_cap);
+/* The device path of the patterns on host arrays (row gather in chunks of whole lines, the CTC FC GEMM, k_ctc_row_lse,
+ * k_ctc_row_max, k_ctc_pattern_viterbi).  z5, W, bias, N, tokens_per_line, n_lines, chunk_rows: as rt_debug_ctc_lexicon_align.
+ * line_pat [n_lines]: 0 = none, k >= 1 = pattern k of the n_pat given as flat compiled tables: pat_S [n_pat], pat_G [n_pat],
+ * group_of [n_pat][N], and pattern k's delta [S][G] and accept [S] behind pattern k - 1's -- so it runs at any N without a
+ * dictionary.  idx [rows] / prob [rows], in and out: overwritten by the path for the matched lines, rows of every other line come
+ * back untouched.  matched_out / vit_out / logprob_out / free_out [n_lines]: written for every line of a pattern (an unmatched
+ * one: 0, -inf, -inf and its free_logprob), the caller's values kept for lines of pattern 0. */
+RT_API int rt_debug_ctc_pattern(rt_session* s, const float* z5, const float* W, const float* bias, int N,
+                                const int32_t* tokens_per_line, int n_lines, const int32_t* line_pat, const int32_t* pat_S,
+                                const int32_t* pat_G, const int32_t* group_of, const int32_t* delta, const int32_t* accept, int n_pat,
+                                int chunk_rows, int32_t* idx, float* prob, int32_t* matched_out, float* vit_out, float* logprob_out,
+                                float* free_out);
+/* The same rule on the CPU in plain fp32 loops (ctc_pattern.h), GPU-free and sessionless; same layout. */
+RT_API int rt_debug_ctc_pattern_host(const float* z5, const float* W, const float* bias, int N, const int32_t* tokens_per_line,
+                                     int n_lines, const int32_t* line_pat, const int32_t* pat_S, const int32_t* pat_G,
+                                     const int32_t* group_of, const int32_t* delta, const int32_t* accept, int n_pat, int32_t* idx,
+                                     float* prob, int32_t* matched_out, float* vit_out, float* logprob_out, float* free_out);
 /* f32 sum of every det probability map produced in the call (keeps the network's
  * output observable when det_map_override is used) */
 RT_API double rt_results_det_checksum(const rt_results* r);

@@ -196,6 +196,10 @@ class RecProcessorSingleResult:
     # lexicon snap (set_lexicon_snap): None when the line carried no lexicon, else whether the line's text, tokens, score, words
     # and candidates are those of its best entry (lexicon_matches[0]) aligned to the line, instead of the greedy decode
     lexicon_snapped: Optional[bool] = None
+    # rec patterns (create_pattern): None when the line carried no pattern, else (matched, logprob, free_logprob): whether the
+    # line's decode is the best CTC path the pattern accepts, that path's log-probability (-inf where unmatched) and the
+    # unconstrained best path's; logprob - free_logprob <= 0 is what the format cost
+    pattern: Optional[Tuple[bool, float, float]] = None
 
 
 @dataclass
@@ -454,6 +458,28 @@ def debug_lexicon_compile(dict_bytes: bytes, entries=(), ids=()) -> List[List[in
     return [out_i[offs[j]:offs[j + 1]].tolist() for j in range(ne.value)]
 
 
+def debug_pattern_compile(dict_bytes: bytes, pattern) -> dict:
+    """rt_debug_pattern_compile: a rec pattern's compiled form (retto_amd/csrc/ctc_pattern.h), GPU-free: a dict with
+    group_of [classes], delta [S][G] (-1: no arc), accept [S] as int32 arrays and S, G, P, min_steps, classes.  pattern: a
+    string, or bytes to pass raw UTF-8."""
+    lib = _lib.load()
+    dict_bytes = bytes(dict_bytes)
+    raw = pattern.encode("utf-8") if isinstance(pattern, str) else bytes(pattern)
+    S, G, P, ms, nc = C.c_int(), C.c_int(), C.c_int(), C.c_int(), C.c_int()
+    err = C.create_string_buffer(384)
+    cap_g = dict_bytes.count(b"\n") + 3
+    group_of = np.zeros(cap_g, np.int32); delta = np.zeros(_lib.PATTERN_MAX_STATES * cap_g, np.int32)
+    accept = np.zeros(_lib.PATTERN_MAX_STATES, np.int32)
+    rc = lib.rt_debug_pattern_compile(dict_bytes, len(dict_bytes), raw, len(raw), group_of.ctypes.data, len(group_of),
+                                      delta.ctypes.data, len(delta), accept.ctypes.data, len(accept), C.byref(S), C.byref(G),
+                                      C.byref(P), C.byref(ms), C.byref(nc), err, len(err))
+    if rc != 0:
+        raise _ERRS.get(rc, RettoError)(err.value.decode("utf-8", "replace"))
+    return {"group_of": group_of[:nc.value].copy(), "delta": delta[:S.value * G.value].reshape(S.value, G.value).copy(),
+            "accept": accept[:S.value].copy(), "S": S.value, "G": G.value, "P": P.value, "min_steps": ms.value,
+            "classes": nc.value}
+
+
 def parse_dictionary(data: bytes) -> List[str]:
     """rt_parse_dictionary: RecCharacter::new (rec_processor.rs:29-46) -- "blank", the file's trimmed lines, " "."""
     lib = _lib.load()
@@ -608,7 +634,7 @@ class RettoSession:
             matches = self._lexicon_matches(r, page, k)
             snapped = None if matches is None else bool(lib.rt_results_rec_lexicon_snapped(r, page, k))
             rec.append(RecProcessorSingleResult(lib.rt_results_rec_text(r, page, k).decode("utf-8"), float(rs[k]), toks, words,
-                                                cands, cols, matches, snapped))
+                                                cands, cols, matches, snapped, self._pattern(r, page, k)))
         return RettoWorkerResult(det, cls, rec)
 
     def _dictionary(self) -> List[str]:
@@ -625,6 +651,12 @@ class RettoSession:
         K = self._hd.lib.rt_results_rec_candidates(r, page, line, C.byref(cp), C.byref(colp))
         return _candidate_lists(cp, K, n_tokens, self._dictionary()), \
             (np.ctypeslib.as_array(colp, (n_tokens,)).copy() if n_tokens else np.zeros(0, np.int32))
+
+    def _pattern(self, r, page: int, line: int):
+        out = _lib.PatternResult()
+        if not self._hd.lib.rt_results_rec_pattern(r, page, line, C.byref(out)):
+            return None
+        return bool(out.matched), float(out.logprob), float(out.free_logprob)
 
     def _lexicon_matches(self, r, page: int, line: int):
         lib = self._hd.lib
@@ -710,7 +742,30 @@ class RettoSession:
         """rt_lexicon_snap: the lexicon's current min_posterior (0.0 for an unknown id)."""
         return float(self._hd.lib.rt_lexicon_snap(self._hd.h, int(lexicon)))
 
-    def run_regions_raw(self, pages, hs, ws, quads, mem=RT_MEM_HOST, charsets=None, lexicons=None):
+    # -- rec patterns -----------------------------------------------------------------------
+    def create_pattern(self, pattern) -> int:
+        """rt_pattern_create: a regular expression over the dictionary (retto_amd/csrc/ctc_pattern.h) that constrains the decode
+        of the lines that carry it: "[0-9]{4}-[0-9]{2}-[0-9]{2}".  pattern: a string, or bytes to pass raw UTF-8.  Returns the
+        pattern's id (1-based, valid for the session's life; at most MAX_PATTERNS); see set_rec_pattern and
+        run_regions(patterns=...)."""
+        raw = pattern.encode("utf-8") if isinstance(pattern, str) else bytes(pattern)
+        out = C.c_int()
+        _check(self._hd.lib.rt_pattern_create(self._hd.h, raw, len(raw), C.byref(out)), self._hd.h)
+        return out.value
+
+    def pattern_info(self, pattern: int) -> Optional[dict]:
+        """rt_pattern_info / rt_pattern_text: {text, states, pairs, min_steps} of a pattern; None for an unknown id."""
+        S, P, ms = C.c_int(), C.c_int(), C.c_int()
+        if self._hd.lib.rt_pattern_info(self._hd.h, int(pattern), C.byref(S), C.byref(P), C.byref(ms)) != 0:
+            return None
+        return {"text": self._hd.lib.rt_pattern_text(self._hd.h, int(pattern)).decode("utf-8", "replace"), "states": S.value,
+                "pairs": P.value, "min_steps": ms.value}
+
+    def set_rec_pattern(self, pattern: int) -> None:
+        """rt_set_rec_pattern: the pattern of every line of the pipeline calls that follow; 0 = none."""
+        _check(self._hd.lib.rt_set_rec_pattern(self._hd.h, int(pattern)), self._hd.h)
+
+    def run_regions_raw(self, pages, hs, ws, quads, mem=RT_MEM_HOST, charsets=None, lexicons=None, patterns=None):
         """rt_run_regions.  pages: host arrays or device pointers (ints); quads[i]: the regions of page i, anything that
         reshapes to [n_i, 8] floats (TL, TR, BR, BL in original-page coordinates).  charsets (rt_run_regions_charsets): per
         page None or one id per region (-1 = the session default, 0 = unrestricted); lexicons (rt_run_regions_lexicons): the same for
@@ -742,6 +797,12 @@ class RettoSession:
                 arr_c[i] = c.ctypes.data if len(c) else None
             return arr_c
 
+        if patterns is not None:   # (rt_run_regions_patterns: any of the three may be missing)
+            arr_c = id_arrays(charsets, "charset") if charsets is not None else None
+            arr_l = id_arrays(lexicons, "lexicon") if lexicons is not None else None
+            _check(lib.rt_run_regions_patterns(h, arr_p, arr_h, arr_w, n, mem, arr_q, arr_n, arr_c, arr_l, id_arrays(patterns, "pattern"),
+                                               C.byref(out)), h)
+            return out
         if lexicons is not None:
             arr_c = id_arrays(charsets, "charset") if charsets is not None else None
             _check(lib.rt_run_regions_lexicons(h, arr_p, arr_h, arr_w, n, mem, arr_q, arr_n, arr_c, id_arrays(lexicons, "lexicon"),
@@ -754,15 +815,16 @@ class RettoSession:
         _check(lib.rt_run_regions(h, arr_p, arr_h, arr_w, n, mem, arr_q, arr_n, C.byref(out)), h)
         return out
 
-    def run_regions(self, pages: Sequence[np.ndarray], quads, charsets=None, lexicons=None) -> List[RettoWorkerResult]:
+    def run_regions(self, pages: Sequence[np.ndarray], quads, charsets=None, lexicons=None, patterns=None) -> List[RettoWorkerResult]:
         """The pipeline over regions the caller already knows (rt_run_regions): quads[i] = the [n_i, 4, 2] (or [n_i, 8]) quads
         of page i in original-page coordinates, TL, TR, BR, BL.  No detector runs; line k of a page is cut from the page as it
         is by quad k clamped to the page.  det_result holds the clamped quads with score 1.0.  charsets: per page None or one
         charset id per region (create_charset; -1 = the session default, 0 = unrestricted); lexicons: the same with lexicon
-        ids (create_lexicon; 0 = none)."""
+        ids (create_lexicon; 0 = none); patterns: the same with pattern ids (create_pattern; 0 = none; a region may not carry
+        both a pattern and a lexicon)."""
         pages = [np.ascontiguousarray(p, np.uint8) for p in pages]
         r = self.run_regions_raw(pages, [p.shape[0] for p in pages], [p.shape[1] for p in pages], quads, charsets=charsets,
-                                 lexicons=lexicons)
+                                 lexicons=lexicons, patterns=patterns)
         try:
             self.last_det_checksum = self._hd.lib.rt_results_det_checksum(r)
             return [self._collect(r, i) for i in range(len(pages))]

@@ -58,10 +58,18 @@ class LexiconMatch(C.Structure):   # rt_lexicon_match
     _fields_ = [("entry", C.c_int32), ("loglik", C.c_float), ("posterior", C.c_float)]
 
 
+class PatternResult(C.Structure):   # rt_pattern_result
+    _fields_ = [("pattern", C.c_int32), ("matched", C.c_int32), ("logprob", C.c_float), ("free_logprob", C.c_float)]
+
+
 MAX_LEXICONS = 16            # RT_MAX_LEXICONS
 LEXICON_MAX_ENTRIES = 65536  # RT_LEXICON_MAX_ENTRIES
 LEXICON_MAX_LEN = 31         # RT_LEXICON_MAX_LEN
 LEXICON_MATCHES = 4          # RT_LEXICON_MATCHES
+MAX_PATTERNS = 16            # RT_MAX_PATTERNS
+PATTERN_MAX_STATES = 64      # RT_PATTERN_MAX_STATES
+PATTERN_MAX_PAIRS = 4096     # RT_PATTERN_MAX_PAIRS
+PATTERN_MAX_BYTES = 1024     # RT_PATTERN_MAX_BYTES
 
 # every symbol include/retto_hip.h declares (tests check that each is exported)
 EXPORTS = [
@@ -87,6 +95,8 @@ EXPORTS = [
     "rt_debug_ctc_lexicon", "rt_debug_ctc_lexicon_host",
     "rt_lexicon_set_snap", "rt_lexicon_snap", "rt_results_rec_lexicon_snapped", "rt_debug_ctc_lexicon_align",
     "rt_debug_ctc_lexicon_align_host",
+    "rt_pattern_create", "rt_pattern_info", "rt_pattern_text", "rt_set_rec_pattern", "rt_run_regions_patterns", "rt_results_rec_pattern",
+    "rt_debug_pattern_compile", "rt_debug_ctc_pattern", "rt_debug_ctc_pattern_host",
 ]
 
 STAGE_CALLBACK = C.CFUNCTYPE(None, C.c_void_p, C.c_int, C.c_int, C.c_char_p)  # rt_stage_callback
@@ -275,5 +285,22 @@ def load():
     lib.rt_debug_ctc_lexicon_align_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
                                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.rt_pattern_create.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t, P(C.c_int)]
+    lib.rt_pattern_info.argtypes = [C.c_void_p, C.c_int, P(C.c_int), P(C.c_int), P(C.c_int)]
+    lib.rt_pattern_text.argtypes = [C.c_void_p, C.c_int]
+    lib.rt_pattern_text.restype = C.c_char_p
+    lib.rt_set_rec_pattern.argtypes = [C.c_void_p, C.c_int]
+    lib.rt_run_regions_patterns.argtypes = [C.c_void_p, P(C.c_void_p), P(C.c_int), P(C.c_int), C.c_int, C.c_int, P(C.c_void_p),
+                                            P(C.c_int), P(C.c_void_p), P(C.c_void_p), P(C.c_void_p), P(C.c_void_p)]
+    lib.rt_results_rec_pattern.argtypes = [C.c_void_p, C.c_int, C.c_int, P(PatternResult)]
+    lib.rt_debug_pattern_compile.argtypes = [C.c_char_p, C.c_size_t, C.c_char_p, C.c_size_t, C.c_void_p, C.c_int, C.c_void_p, C.c_int,
+                                             C.c_void_p, C.c_int, P(C.c_int), P(C.c_int), P(C.c_int), P(C.c_int), P(C.c_int),
+                                             C.c_char_p, C.c_size_t]
+    lib.rt_debug_ctc_pattern.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
+                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
+                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.rt_debug_ctc_pattern_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
+                                              C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                                              C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     _lib = lib
     return lib

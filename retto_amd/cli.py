@@ -47,6 +47,9 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--rec-lexicon", default=None, metavar="FILE",
                     help="a word list, one entry per line: every line's result also ranks these entries by their CTC forward "
                          "log-likelihood (one lexicon, made the session default; the recognised text itself is unchanged unless --rec-lexicon-snap is given)")
+    ap.add_argument("--rec-pattern", default=None, metavar="TEXT",
+                    help="constrain every line's text to this regular expression over the dictionary, e.g. "
+                         "'[0-9]{4}-[0-9]{2}-[0-9]{2}' (one pattern, made the session default; not together with --rec-lexicon)")
     ap.add_argument("--rec-lexicon-snap", type=float, default=None, metavar="P",
                     help="with --rec-lexicon: a line whose best entry's posterior reaches P (0 < P <= 1) takes that entry, "
                          "aligned to its time steps, as its text, score, words and candidates (\"lexicon_snapped\" per line)")
@@ -90,6 +93,10 @@ def main(argv=None) -> int:
         session.set_rec_lexicon(lexicon)
     elif a.rec_lexicon_snap is not None:
         raise SystemExit("--rec-lexicon-snap needs --rec-lexicon")
+    if a.rec_pattern is not None:
+        if a.rec_lexicon is not None:
+            raise SystemExit("--rec-pattern and --rec-lexicon exclude each other")
+        session.set_rec_pattern(session.create_pattern(a.rec_pattern))
     files = walk_files(a.images)
     log.info("Found %d files, processing...", len(files))
     out = open(a.json, "w") if a.json else None
@@ -124,6 +131,10 @@ def main(argv=None) -> int:
                                                for e, s, ll, p in (t.lexicon_matches or [])] for t in r.rec_result]
                     if a.rec_lexicon_snap is not None:   # per line: whether its text is its aligned best entry
                         rec["lexicon_snapped"] = [bool(t.lexicon_snapped) for t in r.rec_result]
+                if a.rec_pattern is not None:   # per line: {matched, logprob, free_logprob} (logprob null where unmatched)
+                    rec["pattern"] = [None if t.pattern is None else
+                                      {"matched": t.pattern[0], "logprob": t.pattern[1] if t.pattern[0] else None,
+                                       "free_logprob": t.pattern[2]} for t in r.rec_result]
                 out.write(json.dumps(rec, ensure_ascii=False) + "\n")
     dur = time.perf_counter() - start
     if out:

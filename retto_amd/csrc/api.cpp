@@ -100,6 +100,37 @@ std::string rt::lexicon_align_args_error(const float* lex_min_post, int n_lex, c
       return "lex_min_post[" + std::to_string(k) + "] = " + std::to_string(lex_min_post[k]) + " is outside [0, 1]";
   return std::string();
 }
+std::string rt::pattern_args_error(const float* z5, const float* W, int N, const int32_t* tokens_per_line, int n_lines,
+                                   const int32_t* line_pat, const int32_t* pat_S, const int32_t* pat_G, const int32_t* group_of,
+                                   const int32_t* delta, const int32_t* accept, int n_pat, const int32_t* idx, const float* prob,
+                                   const int32_t* matched_out, const float* vit_out, const float* logprob_out, const float* free_out,
+                                   long long* rows_out, std::vector<pt::Rule>* rules_out) {
+  auto S = [](long long v) { return std::to_string(v); };
+  if (!z5 || !W || !tokens_per_line || !line_pat || !pat_S || !pat_G || !group_of || !delta || !accept || !idx || !prob ||
+      !matched_out || !vit_out || !logprob_out || !free_out)
+    return "a required pointer is null";
+  if (n_lines <= 0) return "n_lines must be positive";
+  if (N <= 1 || N > 65535) return "N must be in [2, 65535]";
+  if (n_pat < 1 || n_pat > RT_MAX_PATTERNS) return "n_pat = " + S(n_pat) + " is outside [1, RT_MAX_PATTERNS]";
+  rules_out->assign((size_t)n_pat, pt::Rule());
+  size_t od = 0, oa = 0;
+  for (int k = 0; k < n_pat; k++) {
+    if (pat_S[k] < 1 || pat_S[k] > RT_PATTERN_MAX_STATES) return "pattern " + S(k + 1) + ": S = " + S(pat_S[k]) + " is outside [1, RT_PATTERN_MAX_STATES]";
+    if (pat_G[k] < 1 || pat_G[k] > N) return "pattern " + S(k + 1) + ": G = " + S(pat_G[k]) + " is outside [1, N]";
+    const std::string bad = (*rules_out)[(size_t)k].build(N, pat_S[k], pat_G[k], group_of + (size_t)k * N, delta + od, accept + oa);
+    if (!bad.empty()) return "pattern " + S(k + 1) + ": " + bad;
+    od += (size_t)pat_S[k] * pat_G[k]; oa += (size_t)pat_S[k];
+  }
+  long long rows = 0;
+  for (int i = 0; i < n_lines; i++) {
+    if (tokens_per_line[i] < 0) return "line " + S(i) + " has a negative number of time steps";
+    if (line_pat[i] < 0 || line_pat[i] > n_pat) return "line " + S(i) + " names pattern " + S(line_pat[i]) + ", outside [0, " + S(n_pat) + "]";
+    rows += tokens_per_line[i];
+  }
+  if (rows >= (1ll << 30)) return "the lines have " + S(rows) + " time steps, 2^30 or more";
+  *rows_out = rows;
+  return std::string();
+}
 
 extern "C" {
 
@@ -336,6 +367,49 @@ const char* rt_lexicon_entry_text(const rt_session* s, int lexicon, int entry) {
   const rt_lexicons::Host* h = lexicon_of(s, lexicon);
   if (!h || entry < 0 || entry >= (int)h->text.size()) return nullptr;
   return h->text[(size_t)entry].c_str();
+}
+int rt_pattern_create(rt_session* s, const char* utf8, size_t len, int* pattern_out) {
+  RT_REQUIRE(s && pattern_out && (utf8 || len == 0), s, "rt_pattern_create: null argument");
+  return guarded(s, [&] { *pattern_out = s->pattern_create(utf8 ? utf8 : "", len); });
+}
+static const rt_patterns::Host* pattern_of(const rt_session* s, int pattern) {
+  if (!s || !s->patterns || pattern < 1 || pattern > (int)s->patterns->host.size()) return nullptr;
+  return s->patterns->host[(size_t)pattern - 1].get();
+}
+int rt_pattern_info(const rt_session* s, int pattern, int* states, int* pairs, int* min_steps) {
+  const rt_patterns::Host* h = pattern_of(s, pattern);
+  if (!h) return RT_ERR_INVALID;
+  if (states) *states = h->S;
+  if (pairs) *pairs = h->P;
+  if (min_steps) *min_steps = h->min_steps;
+  return RT_OK;
+}
+const char* rt_pattern_text(const rt_session* s, int pattern) {
+  const rt_patterns::Host* h = pattern_of(s, pattern);
+  return h ? h->text.c_str() : nullptr;
+}
+int rt_set_rec_pattern(rt_session* s, int pattern) {
+  RT_REQUIRE(s, s, "rt_set_rec_pattern: null session");
+  return guarded(s, [&] {
+    if (pattern < 0 || pattern > (int)s->patterns->host.size())
+      throw RtError(RT_ERR_INVALID, "rt_set_rec_pattern: unknown pattern id " + std::to_string(pattern));
+    s->rec_pattern = pattern;
+  });
+}
+int rt_run_regions_patterns(rt_session* s, const uint8_t* const* rgb, const int* hs, const int* ws, int n_pages, int mem,
+                            const float* const* quads, const int* n_quads, const int32_t* const* charsets,
+                            const int32_t* const* lexicons, const int32_t* const* patterns, rt_results** out) {
+  RT_REQUIRE(s && out && n_pages >= 0 && (n_pages == 0 || (rgb && hs && ws && quads && n_quads)), s, "rt_run_regions_patterns: bad argument");
+  RT_REQUIRE(mem == RT_MEM_HOST || mem == RT_MEM_DEVICE, s, "rt_run_regions_patterns: mem must be RT_MEM_HOST or RT_MEM_DEVICE");
+  *out = nullptr;
+  return guarded(s, [&] { *out = s->run_regions(rgb, hs, ws, n_pages, mem, quads, n_quads, charsets, lexicons, patterns); });
+}
+int rt_results_rec_pattern(const rt_results* r, int page, int line, rt_pattern_result* out) {
+  const rt_results::Page* p = r && page >= 0 && (size_t)page < r->pages.size() ? &r->pages[(size_t)page] : nullptr;
+  if (!p || line < 0 || (size_t)line >= p->pat_id.size() || p->pat_id[(size_t)line] <= 0) return 0;
+  const pt::LineResult& v = p->pat_res[(size_t)line];
+  if (out) *out = rt_pattern_result{p->pat_id[(size_t)line], v.matched, v.logprob, v.free_logprob};
+  return 1;
 }
 int rt_set_rec_lexicon(rt_session* s, int lexicon) {
   RT_REQUIRE(s, s, "rt_set_rec_lexicon: null session");
@@ -836,6 +910,78 @@ int rt_debug_ctc_lexicon_align_host(const float* z5, const float* W, const float
   }
   return lexicon_host(z5, W, bias, N, tokens_per_line, n_lines, line_lex, entry_ids, entry_lens, lex_first_entry, n_lex, loglik_out,
                       matches_out, n_matches_out, lex_min_post, idx, prob, snapped_out, vit_out);
+}
+static_assert(RT_MAX_PATTERNS == pt::MAX_PATTERNS && RT_PATTERN_MAX_STATES == pt::MAX_STATES && RT_PATTERN_MAX_PAIRS == pt::MAX_PAIRS &&
+                  RT_PATTERN_MAX_BYTES == pt::MAX_BYTES, "the RT_PATTERN_* limits and pt:: must agree");
+static_assert(RT_OK == pt::OK && RT_ERR_UTF8 == pt::ERR_UTF8 && RT_ERR_INVALID == pt::ERR_INVALID && RT_ERR_CAPACITY == pt::ERR_CAPACITY,
+              "the status codes of ctc_pattern.h are the RT_ERR_* ones");
+int rt_debug_pattern_compile(const void* dict, size_t dict_len, const char* utf8, size_t len, int32_t* group_of_out, int group_cap,
+                             int32_t* delta_out, int delta_cap, int32_t* accept_out, int accept_cap, int* S_out, int* G_out, int* P_out,
+                             int* min_steps_out, int* n_classes, char* err, size_t err_cap) {
+  if (err && err_cap) err[0] = 0;
+  if ((!dict && dict_len) || (!utf8 && len) || !S_out || !G_out || !P_out || !min_steps_out || !n_classes || group_cap < 0 ||
+      delta_cap < 0 || accept_cap < 0 || (!group_of_out && group_cap) || (!delta_out && delta_cap) || (!accept_out && accept_cap)) {
+    if (err && err_cap) snprintf(err, err_cap, "rt_debug_pattern_compile: bad argument");
+    return RT_ERR_INVALID;
+  }
+  *S_out = 0; *G_out = 0; *P_out = 0; *min_steps_out = 0; *n_classes = 0;
+  try {
+    std::vector<uint8_t> bytes((const uint8_t*)dict, (const uint8_t*)dict + dict_len);
+    const std::vector<std::string> d = rt::load_dictionary(bytes);
+    *n_classes = (int)d.size();
+    pt::Compiled c;
+    std::string msg;
+    const int rc = pt::compile(d, utf8, len, c, msg);
+    if (rc != pt::OK) throw RtError(rc, msg);
+    *S_out = c.S; *G_out = c.G; *P_out = c.P; *min_steps_out = c.min_steps;
+    if ((size_t)group_cap < c.group_of.size() || (size_t)delta_cap < c.delta.size() || (size_t)accept_cap < c.accept.size())
+      throw RtError(RT_ERR_INVALID, "rt_debug_pattern_compile: the pattern needs " + std::to_string(c.group_of.size()) + " groups' ids, " +
+                                        std::to_string(c.delta.size()) + " arcs and " + std::to_string(c.accept.size()) + " flags");
+    memcpy(group_of_out, c.group_of.data(), c.group_of.size() * sizeof(int32_t));
+    memcpy(delta_out, c.delta.data(), c.delta.size() * sizeof(int32_t));
+    memcpy(accept_out, c.accept.data(), c.accept.size() * sizeof(int32_t));
+    return RT_OK;
+  } catch (const RtError& e) {
+    if (err && err_cap) snprintf(err, err_cap, "%s", e.what());
+    return e.code;
+  } catch (const std::exception& e) {
+    if (err && err_cap) snprintf(err, err_cap, "%s", e.what());
+    return RT_ERR_BACKEND;
+  }
+}
+int rt_debug_ctc_pattern_host(const float* z5, const float* W, const float* bias, int N, const int32_t* tokens_per_line, int n_lines,
+                              const int32_t* line_pat, const int32_t* pat_S, const int32_t* pat_G, const int32_t* group_of,
+                              const int32_t* delta, const int32_t* accept, int n_pat, int32_t* idx, float* prob, int32_t* matched_out,
+                              float* vit_out, float* logprob_out, float* free_out) {
+  long long rows = 0;
+  std::vector<pt::Rule> rules;
+  try {
+    const std::string bad = pattern_args_error(z5, W, N, tokens_per_line, n_lines, line_pat, pat_S, pat_G, group_of, delta, accept, n_pat,
+                                               idx, prob, matched_out, vit_out, logprob_out, free_out, &rows, &rules);
+    if (!bad.empty()) {
+      rt::create_error() = "rt_debug_ctc_pattern_host: " + bad;
+      return RT_ERR_INVALID;
+    }
+    const int D = 120;
+    std::vector<float> logits, lse;
+    long long o = 0;
+    for (int i = 0; i < n_lines; i++) {
+      const int T = tokens_per_line[i];
+      if (line_pat[i] > 0) {
+        logits.assign((size_t)std::max(T, 1) * N, 0.0f); lse.assign((size_t)std::max(T, 1), 0.0f);
+        for (int t = 0; t < T; t++) {
+          cs::row_logits(z5 + (size_t)(o + t) * D, D, W, bias, N, logits.data() + (size_t)t * N);
+          lse[(size_t)t] = lx::row_lse(logits.data() + (size_t)t * N, N);
+        }
+        const pt::LineResult r = pt::viterbi_line(rules[(size_t)line_pat[i] - 1], logits.data(), N, lse.data(), T, idx + o, prob + o);
+        matched_out[i] = r.matched; vit_out[i] = r.vit; logprob_out[i] = r.logprob; free_out[i] = r.free_logprob;
+      }
+      o += T;
+    }
+    return RT_OK;
+  } catch (const std::exception&) {
+    return RT_ERR_BACKEND;
+  }
 }
 double rt_results_det_checksum(const rt_results* r) { return r ? r->det_checksum : 0.0; }
 const char* rt_results_json(rt_results* r, int page, int stage) {

@@ -1,6 +1,6 @@
 // Kernel-level diagnostics of libretto_hip.so (include/retto_hip.h, diagnostics section): the A/B switches of tools/, the kernel
 // micro-benchmarks (rt_bench_*), and one harness per kernel family that runs a single launch on host arrays for the fp64 tests
-// (rt_debug_gemm, _dwconv, _dw_plan, _attention, _ctc_candidates, _ctc_charset, _ctc_lexicon, _ctc_lexicon_align, _lc_block, _lc_wide, _conv13, _layernorm, _conv16, _glue16, _fpn, _conv16x, _cls_block, _stem, _glue32).
+// (rt_debug_gemm, _dwconv, _dw_plan, _attention, _ctc_candidates, _ctc_charset, _ctc_lexicon, _ctc_lexicon_align, _ctc_pattern, _lc_block, _lc_wide, _conv13, _layernorm, _conv16, _glue16, _fpn, _conv16x, _cls_block, _stem, _glue32).
 // None of it runs in production, and every kernel test depends on it.  A harness has one shape: check the arguments (each
 // failure with its own message, before any device work), lay the ragged lists out (Ragged), put the operands on the device
 // (DevBufs::upload / zeroed, upload_as), fill what the kernel writes with RT_DEBUG_CANARY and spare rows (DevBufs::canary),
@@ -388,11 +388,12 @@ struct TailHook {
   RecTailPlan plan; rt_session::RecTail t{};
   TailHook(rt_session* s_, const float* z5, const float* W, const float* bias, int N, long long rows, const int32_t* tokens_per_line,
            int n_lines, const int32_t* line_set, const int32_t* line_lex, const lx::Tables& tb, const float* snap_min, const int32_t* idx,
-           const float* prob, int K, int chunk_rows) : s(s_), nr((size_t)std::max<long long>(rows, 1)) {
+           const float* prob, int K, int chunk_rows, const int32_t* line_pat = nullptr, const pt::Tables* ptb = nullptr)
+      : s(s_), nr((size_t)std::max<long long>(rows, 1)) {
     s->begin_call();
     std::vector<long long> off((size_t)n_lines + 1, 0);
     std::partial_sum(tokens_per_line, tokens_per_line + n_lines, off.begin() + 1);   // (below 2^30: the entries' own check)
-    plan = rec_tail_plan(off.data(), 0, n_lines, line_set, line_lex, tb, snap_min);
+    plan = rec_tail_plan(off.data(), 0, n_lines, line_set, line_lex, tb, snap_min, line_pat, ptb);
     core.classes = N;
     if (plan.needs_z5(K)) {
       core.fc = pack_linear(ws, W, bias, core.D, N);
@@ -532,6 +533,38 @@ RT_API int rt_debug_ctc_lexicon_align(rt_session* s, const float* z5, const floa
   return guarded(s, [&] {
     debug_ctc_lexicon(s, z5, W, bias, N, tokens_per_line, n_lines, line_lex, entry_ids, entry_lens, lex_first_entry, n_lex, chunk_rows,
                       rows, loglik_out, matches_out, n_matches_out, lex_min_post, idx, prob, snapped_out, vit_out);
+  });
+}
+
+// Rec patterns' device path on host arrays (ctc_pattern.h); the pattern tables are built as a session's store would build them
+// (pt::Rule::build from the flat compiled tables, pt::Tables).
+RT_API int rt_debug_ctc_pattern(rt_session* s, const float* z5, const float* W, const float* bias, int N,
+                                const int32_t* tokens_per_line, int n_lines, const int32_t* line_pat, const int32_t* pat_S,
+                                const int32_t* pat_G, const int32_t* group_of, const int32_t* delta, const int32_t* accept, int n_pat,
+                                int chunk_rows, int32_t* idx, float* prob, int32_t* matched_out, float* vit_out, float* logprob_out,
+                                float* free_out) {
+  long long rows = 0;
+  std::vector<pt::Rule> rules;
+  RT_REQUIRE(s, s, "rt_debug_ctc_pattern: null session");
+  const std::string bad = pattern_args_error(z5, W, N, tokens_per_line, n_lines, line_pat, pat_S, pat_G, group_of, delta, accept, n_pat,
+                                             idx, prob, matched_out, vit_out, logprob_out, free_out, &rows, &rules);
+  RT_REQUIRE(bad.empty(), s, "rt_debug_ctc_pattern: " + bad);
+  RT_REQUIRE(chunk_rows >= 0, s, "rt_debug_ctc_pattern: chunk_rows is negative");
+  return guarded(s, [&] {
+    pt::Tables tb;
+    for (const pt::Rule& r : rules) tb.add(r);
+    TailHook h(s, z5, W, bias, N, rows, tokens_per_line, n_lines, nullptr, nullptr, lx::Tables(), nullptr, idx, prob, 0, chunk_rows, line_pat, &tb);
+    rt_session::RecTail& t = h.t;
+    t.d_pat = pt::DevTables{h.bufs.upload(tb.pats.data(), tb.pats.size()), h.bufs.upload(tb.pair_c.data(), tb.pair_c.size()),
+                            h.bufs.upload(tb.pair_pb.data(), tb.pair_pb.size()), h.bufs.upload(tb.pair_pe.data(), tb.pair_pe.size()),
+                            h.bufs.upload(tb.seg.data(), tb.seg.size()), h.bufs.upload(tb.preds.data(), tb.preds.size())};
+    // (what the kernel writes starts as the caller's values: a slot it leaves alone comes back untouched)
+    t.patm = h.bufs.upload(matched_out, (size_t)n_lines); t.patv = h.bufs.upload(vit_out, (size_t)n_lines);
+    t.patlp = h.bufs.upload(logprob_out, (size_t)n_lines); t.patfree = h.bufs.upload(free_out, (size_t)n_lines);
+    h.run();
+    DevBufs::download(idx, t.idx, (size_t)rows); DevBufs::download(prob, t.prob, (size_t)rows);
+    DevBufs::download(matched_out, t.patm, (size_t)n_lines); DevBufs::download(vit_out, t.patv, (size_t)n_lines);
+    DevBufs::download(logprob_out, t.patlp, (size_t)n_lines); DevBufs::download(free_out, t.patfree, (size_t)n_lines);
   });
 }
 

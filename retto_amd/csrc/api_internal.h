@@ -34,6 +34,13 @@ std::string lexicon_args_error(const float* z5, const float* W, int N, const int
 // what both rt_debug_ctc_lexicon_align forms require beyond lexicon_args_error (n_lex already checked), likewise
 std::string lexicon_align_args_error(const float* lex_min_post, int n_lex, const int32_t* idx, const float* prob,
                                      const int32_t* snapped_out, const float* vit_out);
+// what both rt_debug_ctc_pattern forms require of their arguments, likewise; rules_out: the n_pat patterns' tables (pt::Rule::build
+// checks the flat compiled tables: pattern k's group_of at [k][N], its delta [S[k]][G[k]] and accept [S[k]] behind pattern k - 1's)
+std::string pattern_args_error(const float* z5, const float* W, int N, const int32_t* tokens_per_line, int n_lines,
+                               const int32_t* line_pat, const int32_t* pat_S, const int32_t* pat_G, const int32_t* group_of,
+                               const int32_t* delta, const int32_t* accept, int n_pat, const int32_t* idx, const float* prob,
+                               const int32_t* matched_out, const float* vit_out, const float* logprob_out, const float* free_out,
+                               long long* rows_out, std::vector<pt::Rule>* rules_out);
 
 // A call that fails after work was enqueued must not leave kernels or H2D copies in flight: the next
 // begin_call() rewinds the pinned staging and the arenas they read.  Errors of the drain itself are dropped

@@ -9,6 +9,7 @@
 #include "ctc_charset.h"
 #include "ctc_lexicon.h"
 #include "ctc_lexicon_align.h"
+#include "ctc_pattern.h"
 
 namespace rt {
 namespace pp {
@@ -127,6 +128,15 @@ void ctc_lexicon_align(hipStream_t st, const float* logits, int ld, const float*
                        int chunk_row0, const lx::Lex* lex, const lx::Entry* entries, const int* ids, const float* min_post,
                        const lx::Match* matches, const int* counts, const int* rows, void* bp, int* idx, float* prob, int* snapped,
                        float* vit);
+// Rec patterns (ctc_pattern.h): one wave64 per row i < m of logits [m][ld]: rmax[i] = the largest logit of the columns < classes
+void ctc_row_max(hipStream_t st, const float* logits, int ld, int classes, int m, float* rmax);
+// The pattern Viterbi: one workgroup per line of lines[0..n_lines) (one chunk, resident as for ctc_lexicon_forward, with lse and
+// rmax of its rows).  Per line matched / vit / logprob / free_lp [line.slot]; a matched line's rows rows[line.row0 .. + T) of
+// idx / prob are overwritten by the path.  tb: pt::Tables on the device.  bp: the chunk's backpointer codes (16 bits each,
+// line.bp counts in codes), read and written only for lines with pt::bp_codes(T, P, S) > pt::BP_LDS.
+void ctc_pattern_viterbi(hipStream_t st, const float* logits, int ld, int classes, const float* lse, const float* rmax,
+                         const pt::Line* lines, int n_lines, int chunk_row0, const pt::DevTables& tb, const int* rows, void* bp,
+                         int* idx, float* prob, int* matched, float* vit, float* logprob, float* free_lp);
 
 // sum of a float buffer into per-block doubles (partials has ceil(n/65536) entries)
 int sum_blocks(long long n);

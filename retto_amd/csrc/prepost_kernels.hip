@@ -770,6 +770,193 @@ void ctc_lexicon_align(hipStream_t st, const float* logits, int ld, const float*
             matches, counts, rows, static_cast<ulonglong2*>(bp), idx, prob, snapped, vit);
 }
 
+// Rec patterns (ctc_pattern.h).  One wave64 per row i < m of logits [m][ld]: rmax[i] = the largest logit of the columns <
+// classes, k_ctc_row_lse's first pass (free_logprob needs it beside the lse; that kernel and its result stay as they are).
+__global__ __launch_bounds__(64) void k_ctc_row_max(const float* __restrict__ logits, int ld, int classes, int m,
+                                                    float* __restrict__ rmax) {
+  const int i = blockIdx.x, lane = threadIdx.x;
+  if (i >= m) return;
+  const float4* x = reinterpret_cast<const float4*>(logits + (long long)i * ld);
+  const int nv = (classes + 3) / 4;
+  float mx = -INFINITY;
+  for (int v = lane; v < nv; v += 64) {
+    const float4 q = x[v];
+    const float e[4] = {q.x, q.y, q.z, q.w};
+#pragma unroll
+    for (int u = 0; u < 4; u++)
+      if (4 * v + u < classes && e[u] > mx) mx = e[u];   // (pt::viterbi_line's comparison: a NaN never becomes the maximum)
+  }
+  for (int o = 32; o >= 1; o >>= 1) { const float w = __shfl_xor(mx, o); if (w > mx) mx = w; }
+  if (lane == 0) rmax[i] = mx;
+}
+void ctc_row_max(hipStream_t st, const float* logits, int ld, int classes, int m, float* rmax) {
+  if (m <= 0) return;
+  RT_LAUNCH(k_ctc_row_max, dim3(m), dim3(64), 0, st, logits, ld, classes, m, rmax);
+}
+
+// The pattern Viterbi of ctc_pattern.h.  One workgroup of 256 threads per pattern line of one chunk.  B and C of two steps live
+// in LDS (2 x (64 + 4096) floats at the caps), beside the pattern's pair classes (16 bits each), its seg table and -- when they
+// are at most PREDS_LDS bytes -- its predecessor lists.  A step has three parts between two barriers:
+//   1. top(q): wave w takes the states q = w, w + 4, ...; its lanes stride over the state's pairs, each keeping a pt::Top of
+//      the live values it saw, and an xor butterfly merges the 64 lists with pt::top_insert (the lists of the two halves are
+//      disjoint at every level, and the order (value, pair index) is total over live values, so the result is the serial scan's);
+//   2. thread i updates the pairs i, i + 256, ... over their predecessor lists (pt::into_of) and stores one 16-bit code each;
+//   3. lane q of wave 0 updates B[q].
+// l[t][c] of a thread's pairs and of the blank is loaded one step ahead into registers, right behind its use: the gather is
+// off the chain.  The codes of step t go to row t of the line's table, P + S codes wide: in LDS when T * (P + S) <= pt::BP_LDS,
+// otherwise at bp + line.bp in the chunk's scratch buffer; the same generic pointer serves both.  After the last step thread 0
+// picks the end node and walks the table back, serial in t, leaving each step's node in slot 0 of its row (a row's code is
+// read before its slot 0 is overwritten; row 0 holds no codes); meanwhile thread 64 adds up lse and rmax in t order.  The rows
+// are then written back in parallel.  No code outside [0, S) / [0, P) is ever stored or followed (ctc_pattern.h).
+// bp is not __restrict__: other threads read what a thread stored, across the barriers.
+constexpr int PREDS_LDS = 2048;   // a pattern's predecessor bytes (one per arc) that the kernel copies into LDS
+__global__ __launch_bounds__(256) void k_ctc_pattern_viterbi(const float* __restrict__ logits, int ld, const float* __restrict__ lse,
+                                                             const float* __restrict__ rmax, const pt::Line* __restrict__ lines,
+                                                             int chunk_row0, pt::DevTables tb, const int* __restrict__ rows,
+                                                             uint16_t* bp_mem, int* __restrict__ idx, float* __restrict__ prob,
+                                                             int* __restrict__ matched, float* __restrict__ vit,
+                                                             float* __restrict__ logprob, float* __restrict__ free_lp) {
+  constexpr int NT = 256, PER = pt::MAX_PAIRS / NT;
+  __shared__ float sB[2][pt::MAX_STATES];
+  __shared__ float sC[2][pt::MAX_PAIRS];
+  __shared__ float sV1[pt::MAX_STATES], sV2[pt::MAX_STATES];
+  __shared__ int sA1[pt::MAX_STATES], sA2[pt::MAX_STATES], sK1[pt::MAX_STATES], sSeg[pt::MAX_STATES + 1];
+  __shared__ uint16_t sPC[pt::MAX_PAIRS];
+  __shared__ uint16_t sBP[pt::BP_LDS];
+  __shared__ uint8_t sPreds[PREDS_LDS];
+  __shared__ float sSum[2];
+  __shared__ int sEnd;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const pt::Line ln = lines[blockIdx.x];
+  const pt::Pat pat = tb.pats[ln.pat];
+  const int S = pat.S, P = pat.P, T = ln.T, W = P + S;
+  if (T < 1) {   // (uniform)
+    if (tid == 0) { matched[ln.slot] = 0; vit[ln.slot] = -INFINITY; logprob[ln.slot] = -INFINITY; free_lp[ln.slot] = 0.0f; }
+    return;
+  }
+  const long long r0 = ln.row0 - chunk_row0;
+  const float* L = logits + r0 * ld;
+  uint16_t* bp = pt::bp_codes(T, P, S) <= pt::BP_LDS ? sBP : bp_mem + ln.bp;
+  const bool preds_in_lds = pat.n_pred <= PREDS_LDS;
+  const uint8_t* pr = preds_in_lds ? sPreds : tb.preds + pat.pred0;
+  for (int p = tid; p < P; p += NT) sPC[p] = (uint16_t)tb.pair_c[pat.pair0 + p];
+  for (int q = tid; q <= S; q += NT) sSeg[q] = tb.seg[pat.seg0 + q];
+  if (preds_in_lds) for (int j = tid; j < pat.n_pred; j += NT) sPreds[j] = tb.preds[pat.pred0 + j];
+  int pb[PER], pe[PER];
+  float lq[PER];
+#pragma unroll
+  for (int k = 0; k < PER; k++) {
+    const int p = tid + k * NT;
+    pb[k] = p < P ? tb.pair_pb[pat.pair0 + p] : 0; pe[k] = p < P ? tb.pair_pe[pat.pair0 + p] : 0;
+  }
+  __syncthreads();
+  // t = 0
+  if (tid < S) sB[0][tid] = tid == 0 ? L[0] : -INFINITY;
+  float lb = tid < S && T > 1 ? L[ld] : 0.0f;
+#pragma unroll
+  for (int k = 0; k < PER; k++) {
+    const int p = tid + k * NT;
+    lq[k] = 0.0f;
+    if (p < P) {
+      const int c = sPC[p];
+      sC[0][p] = pr[pb[k]] == 0 ? L[c] : -INFINITY;
+      if (T > 1) lq[k] = L[ld + c];
+    }
+  }
+  __syncthreads();
+  int cur = 0;
+  for (int t = 1; t <= T; t++) {   // (t == T: top() of the last step alone, for the end)
+    for (int q = wave; q < S; q += NT / 64) {
+      pt::Top tp = pt::top_empty();
+      for (int p = sSeg[q] + lane; p < sSeg[q + 1]; p += 64) { const float v = sC[cur][p]; if (v > -INFINITY) pt::top_insert(tp, v, p); }
+      for (int o = 32; o >= 1; o >>= 1) {
+        const float w1 = __shfl_xor(tp.v1, o), w2 = __shfl_xor(tp.v2, o);
+        const int b1 = __shfl_xor(tp.a1, o), b2 = __shfl_xor(tp.a2, o);
+        pt::top_insert(tp, w1, b1); pt::top_insert(tp, w2, b2);   // (an empty slot, (-inf, NONE), ranks before nothing)
+      }
+      if (lane == 0) { sV1[q] = tp.v1; sV2[q] = tp.v2; sA1[q] = tp.a1; sA2[q] = tp.a2; sK1[q] = tp.a1 == pt::NONE ? 0 : sPC[tp.a1]; }
+    }
+    __syncthreads();
+    if (t == T) break;
+    const int nxt = cur ^ 1;
+    uint16_t* row = bp + (long long)t * W;
+    const float* Ln = L + (long long)(t + 1) * ld;
+    const bool more = t + 1 < T;
+#pragma unroll
+    for (int k = 0; k < PER; k++) {
+      const int p = tid + k * NT;
+      if (p < P) {
+        const int c = sPC[p];
+        float best = sC[cur][p]; int code = pt::STAY;
+        for (int j = pb[k]; j < pe[k]; j++) {
+          const int q = pr[j];
+          int kc;
+          const float v = pt::into_of(sB[cur][q], q, pt::Top{sV1[q], sV2[q], sA1[q], sA2[q]}, sK1[q], c, &kc);
+          if (v > best) { best = v; code = kc; }
+        }
+        sC[nxt][p] = lq[k] + best;
+        row[p] = (uint16_t)code;
+        if (more) lq[k] = Ln[c];
+      }
+    }
+    if (tid < S) {
+      float best = sB[cur][tid]; int code = pt::STAY;
+      if (sV1[tid] > best) { best = sV1[tid]; code = sA1[tid]; }
+      sB[nxt][tid] = lb + best;
+      row[P + tid] = (uint16_t)code;
+      if (more) lb = Ln[0];
+    }
+    __syncthreads();
+    cur = nxt;
+  }
+  if (tid == 0) {
+    float best = -INFINITY; int node = pt::NONE;
+    for (int q = 0; q < S; q++) {
+      if (!((pat.accept >> q) & 1ull)) continue;
+      if (sB[cur][q] > best) { best = sB[cur][q]; node = pt::BLANK | q; }
+      if (sV1[q] > best) { best = sV1[q]; node = sA1[q]; }
+    }
+    sEnd = node;
+    sSum[0] = best;
+    if (node != pt::NONE) {
+      for (int t = T - 1; t >= 0; t--) {
+        const int here = node;
+        if (t > 0) {
+          const int k = bp[(long long)t * W + ((node & pt::BLANK) ? P + (node & ~pt::BLANK) : node)];
+          if (k != pt::STAY) node = k;
+        }
+        bp[(long long)t * W] = (uint16_t)here;
+      }
+    }
+  }
+  float sum_lse = 0.0f, fr = 0.0f;
+  if (tid == 64) {
+    for (int t = 0; t < T; t++) { fr = fr + (rmax[r0 + t] - lse[r0 + t]); sum_lse = sum_lse + lse[r0 + t]; }
+    sSum[1] = fr;
+  }
+  __syncthreads();
+  const bool hit = sEnd != pt::NONE;
+  if (tid == 64) {
+    matched[ln.slot] = hit ? 1 : 0; vit[ln.slot] = hit ? sSum[0] : -INFINITY; logprob[ln.slot] = hit ? sSum[0] - sum_lse : -INFINITY;
+    free_lp[ln.slot] = fr;
+  }
+  if (!hit) return;
+  for (int t = tid; t < T; t += NT) {
+    const int node = bp[(long long)t * W];
+    const int c = (node & pt::BLANK) ? 0 : sPC[node], r = rows[ln.row0 + t];
+    idx[r] = c;
+    prob[r] = expf(L[(long long)t * ld + c] - lse[r0 + t]);
+  }
+}
+void ctc_pattern_viterbi(hipStream_t st, const float* logits, int ld, int classes, const float* lse, const float* rmax,
+                         const pt::Line* lines, int n_lines, int chunk_row0, const pt::DevTables& tb, const int* rows, void* bp,
+                         int* idx, float* prob, int* matched, float* vit, float* logprob, float* free_lp) {
+  if (n_lines <= 0) return;
+  if (classes > 65535) throw RtError(4, "ctc_pattern_viterbi: more than 65535 classes");   // (pair classes are 16 bits in LDS)
+  RT_LAUNCH(k_ctc_pattern_viterbi, dim3(n_lines), dim3(256), 0, st, logits, ld, lse, rmax, lines, chunk_row0, tb, rows,
+            static_cast<uint16_t*>(bp), idx, prob, matched, vit, logprob, free_lp);
+}
+
 // ===========================================================================
 // (round 5: 8192 values per block, 16-byte loads -- was 65536 per block, scalar: one 960 x 960 map ran on 15 workgroups for 77 us,
 //  6 % of the C2 call)

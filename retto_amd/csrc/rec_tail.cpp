@@ -1,6 +1,6 @@
 // The rec network's CTC tail and what feeds it: the dictionary, charset and lexicon text compilers, the session's charset and
-// lexicon stores, and rt_session::rec_tail -- the one launch sequence behind the net that the pipeline (session.cpp rec_groups)
-// and the debug hooks (api_debug.cpp rt_debug_ctc_*) both run, on the tables of rec_tail_plan.h.
+// lexicon stores, the pattern pass (ctc_pattern.h), and rt_session::rec_tail -- the one launch sequence behind the net that the
+// pipeline (session.cpp rec_groups) and the debug hooks (api_debug.cpp rt_debug_ctc_*) both run, on the tables of rec_tail_plan.h.
 #include "session.h"
 
 #include <cstdio>
@@ -208,6 +208,7 @@ void rt_session::rec_tail(const RecTailPlan& p, const SvtrCore& core, const RecT
     ctc_charset(core, t, staged(*this, p.crows), (int)p.crows.size(), d_row_set);
   }
   if (p.snap) ctc_lexicon(p, core, t);
+  if (p.has_pat()) ctc_pattern(p, core, t);
   { ProfScope ps(&prof, st, "ctc_decode");
     pp::ctc_decode(st, t.idx, t.prob, t.lines, t.n_lines, t.tok, t.ntok, t.rscore); }
   if (t.wb) {
@@ -303,6 +304,43 @@ void rt_session::ctc_lexicon(const RecTailPlan& p, const SvtrCore& core, const R
   }
 }
 
+void rt_session::ctc_pattern(const RecTailPlan& p, const SvtrCore& core, const RecTail& t) {
+  const pt::Line* h_lines = p.plines.data(); const int n_lines = (int)p.plines.size();
+  if (n_lines <= 0) return;
+  const pt::Line* d_lines = staged(*this, p.plines); const int* d_rows = staged(*this, p.prows);
+  const int chunk = t.chunk_rows > 0 ? t.chunk_rows : cc::CAND_CHUNK;
+  // chunks of whole lines, as ctc_lexicon's: a line's T rows are resident together
+  auto chunk_end = [&](int i0) {
+    int i1 = i0 + 1, rows = h_lines[i0].T;
+    while (i1 < n_lines && i1 - i0 < lx::LINES_PER_CHUNK && rows + h_lines[i1].T <= chunk) rows += h_lines[i1++].T;
+    return i1;
+  };
+  int cap = 1;
+  for (int i0 = 0; i0 < n_lines;) {
+    const int i1 = chunk_end(i0);
+    cap = std::max(cap, h_lines[i1 - 1].row0 + h_lines[i1 - 1].T - h_lines[i0].row0);
+    i0 = i1;
+  }
+  LogitsChunk lc(*this, core, t.z5, cap);
+  float* lse = scratch.alloc<float>((size_t)cap); float* rmax = scratch.alloc<float>((size_t)cap);
+  // (the backpointer codes of the group's long lines, 16 bits each; every line has its own part: pt::Line::bp)
+  void* bp = scratch.alloc_bytes((size_t)std::max<long long>(p.bp_codes, 1) * sizeof(uint16_t));
+  for (int i0 = 0; i0 < n_lines;) {
+    const int i1 = chunk_end(i0), r0 = h_lines[i0].row0, m = h_lines[i1 - 1].row0 + h_lines[i1 - 1].T - r0;
+    if (m > 0) {
+      lc.run(d_rows + r0, m);
+      { ProfScope ps(&prof, st, "ctc_row_lse");
+        pp::ctc_row_lse(st, lc.logits, lc.ld, core.classes, m, lse); }
+      ProfScope ps(&prof, st, "ctc_row_max");
+      pp::ctc_row_max(st, lc.logits, lc.ld, core.classes, m, rmax);
+    }
+    ProfScope ps(&prof, st, "ctc_pattern_viterbi");
+    pp::ctc_pattern_viterbi(st, lc.logits, lc.ld, core.classes, lse, rmax, d_lines + i0, i1 - i0, r0, t.d_pat, d_rows, bp, t.idx, t.prob,
+                            t.patm, t.patv, t.patlp, t.patfree);
+    i0 = i1;
+  }
+}
+
 int rt_session::charset_create(const char* utf8, size_t len, const int32_t* ids, int n_ids) {
   rt_charsets& C = *charsets;
   if ((int)C.ids.size() >= cs::MAX_SETS)
@@ -353,6 +391,35 @@ int rt_session::lexicon_create(const char* utf8, size_t len, const int32_t* ids,
   X.d_ids = d_ids; X.d_entries = d_entries; X.d_order = d_order; X.d_lex = d_lex;
   X.tb = std::move(tb);
   X.host.push_back(std::move(h));
+  return (int)X.host.size();
+}
+
+int rt_session::pattern_create(const char* utf8, size_t len) {
+  rt_patterns& X = *patterns;
+  if ((int)X.host.size() >= pt::MAX_PATTERNS)
+    throw RtError(RT_ERR_CAPACITY, "rt_pattern_create: the session holds RT_MAX_PATTERNS (" + std::to_string(pt::MAX_PATTERNS) + ") patterns already");
+  pt::Compiled c;
+  std::string msg;
+  const int rc = pt::compile(dict, utf8, len, c, msg);
+  if (rc != pt::OK) throw RtError(rc, msg);
+  pt::Rule r;
+  const std::string bad = r.build(c.classes, c.S, c.G, c.group_of.data(), c.delta.data(), c.accept.data());
+  if (!bad.empty()) throw RtError(RT_ERR_INVALID, "pattern: " + bad);
+  pt::Tables tb = X.tb;
+  tb.add(r);
+  // the device tables are rebuilt whole (blocking copies; no lane has work queued: this is a guarded call and every pipeline
+  // call ends with its streams drained)
+  RT_HIP_CHECK(hipSetDevice(device));
+  rt_patterns fresh;   // (frees what it holds if a copy below throws)
+  auto up = [&](auto** d, const auto& v) {
+    RT_HIP_CHECK(hipMalloc((void**)d, std::max<size_t>(v.size(), 1) * sizeof(v[0])));
+    if (!v.empty()) RT_HIP_CHECK(hipMemcpy(const_cast<void*>((const void*)*d), v.data(), v.size() * sizeof(v[0]), hipMemcpyHostToDevice));
+  };
+  up(&fresh.d.pats, tb.pats); up(&fresh.d.pair_c, tb.pair_c); up(&fresh.d.pair_pb, tb.pair_pb); up(&fresh.d.pair_pe, tb.pair_pe);
+  up(&fresh.d.seg, tb.seg); up(&fresh.d.preds, tb.preds);
+  std::swap(X.d, fresh.d);   // (the old tables leave with `fresh`)
+  X.tb = std::move(tb);
+  X.host.emplace_back(new rt_patterns::Host{std::string(utf8, len), c.S, c.P, c.min_steps});
   return (int)X.host.size();
 }
 

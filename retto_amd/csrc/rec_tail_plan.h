@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "ctc_lexicon.h"
+#include "ctc_pattern.h"
 
 namespace rt {
 
@@ -24,15 +25,23 @@ struct RecTailPlan {
   bool table_fits() const { return table <= lx::MAX_GROUP_TABLE; }
   // lexicon snap (ctc_lexicon_align.h): a lexicon line of THIS group has min_posterior > 0; its lexicons then run before the decode
   bool snap = false;
+  // rec patterns (ctc_pattern.h): the group's pattern lines in line order (row0 = the sum of the earlier ones' T, slot = the
+  // line's index in the call, bp = the sum of the earlier ones' backpointer codes), their rows line after line, the largest P
+  // and S over the lines' patterns, and the backpointer codes the group's scratch buffer holds: pt::bp_codes() of every line
+  // whose codes do not fit the kernel's LDS (pt::BP_LDS)
+  std::vector<pt::Line> plines; std::vector<int> prows;
+  int max_P = 0, max_S = 0; long long bp_codes = 0;
+  bool has_pat() const { return !plines.empty(); }
   // the net must hand out the head's input: some logits are recomputed
-  bool needs_z5(int cand_k) const { return cand_k > 1 || !crows.empty() || has_lex(); }
+  bool needs_z5(int cand_k) const { return cand_k > 1 || !crows.empty() || has_lex() || has_pat(); }
 };
 
 // Lines [l0, l1) of a call: line li has the time steps [tok_off[li], tok_off[li + 1]), charset line_set[li] and lexicon
 // line_lex[li] (1-based, 0: none; either array may be null: no line has one), lexicon k is tb.lex[k - 1] and snaps where
-// snap_min[k - 1] > 0 (null: never).
+// snap_min[k - 1] > 0 (null: never); pattern line_pat[li] (the same convention; null: no line has one) is ptb->pats[k - 1].
 inline RecTailPlan rec_tail_plan(const long long* tok_off, int l0, int l1, const int* line_set, const int* line_lex,
-                                 const lx::Tables& tb, const float* snap_min) {
+                                 const lx::Tables& tb, const float* snap_min, const int* line_pat = nullptr,
+                                 const pt::Tables* ptb = nullptr) {
   RecTailPlan p;
   const long long t0 = tok_off[l0];
   p.rows = tok_off[l1] - t0;
@@ -44,6 +53,13 @@ inline RecTailPlan rec_tail_plan(const long long* tok_off, int l0, int l1, const
     for (int t = 0; restricted && t < T; t++) {
       p.row_set[(size_t)(r0 + t)] = line_set[li];
       if (line_set[li] > 0) p.crows.push_back(r0 + t);
+    }
+    if (line_pat && ptb && line_pat[li] > 0) {
+      const pt::Pat& a = ptb->pats[(size_t)line_pat[li] - 1];
+      p.plines.push_back(pt::Line{(int)p.prows.size(), T, line_pat[li] - 1, li, p.bp_codes});
+      for (int t = 0; t < T; t++) p.prows.push_back(r0 + t);
+      p.max_P = std::max(p.max_P, a.P); p.max_S = std::max(p.max_S, a.S);
+      if (pt::bp_codes(T, a.P, a.S) > pt::BP_LDS) p.bp_codes += pt::bp_codes(T, a.P, a.S);
     }
     if (!line_lex || line_lex[li] <= 0) continue;
     const lx::Lex& x = tb.lex[(size_t)line_lex[li] - 1];

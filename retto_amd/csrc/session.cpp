@@ -64,6 +64,7 @@ rt_session* rt_session_create(const rt_config* cfg) {
   s->dict = rt::load_dictionary(dict);
   s->charsets = std::make_shared<rt_charsets>();
   s->lexicons = std::make_shared<rt_lexicons>();
+  s->patterns = std::make_shared<rt_patterns>();
   if ((int)s->dict.size() != s->rec->classes())
     throw RtError(RT_ERR_SHAPE, "dictionary has " + std::to_string(s->dict.size()) + " entries but the rec head has " +
                                     std::to_string(s->rec->classes()) + " classes");
@@ -81,7 +82,7 @@ rt_session* rt_session_create(const rt_config* cfg) {
     std::unique_ptr<rt_session> h(new rt_session());
     h->cfg = s->cfg; h->device = s->device;
     h->det = s->det; h->cls = s->cls; h->rec = s->rec; h->dict = s->dict; h->model_info = s->model_info;
-    h->d_word_raw = s->d_word_raw; h->charsets = s->charsets; h->lexicons = s->lexicons;
+    h->d_word_raw = s->d_word_raw; h->charsets = s->charsets; h->lexicons = s->lexicons; h->patterns = s->patterns;
     RT_HIP_CHECK(hipStreamCreateWithFlags(&h->st_full, hipStreamNonBlocking));
     h->st = h->st_full;
     RT_HIP_CHECK(hipMalloc((void**)&h->d_flags, 64));
@@ -539,6 +540,10 @@ struct Pipeline {
   lx::Match* d_lexm = nullptr; int* d_lexn = nullptr; lx::Match* h_lexm = nullptr; int* h_lexn = nullptr;
   // lexicon snap (ctc_lexicon_align.h): per line 1 where it snapped; null unless a lexicon of the call's lines has snap on
   int* d_lexs = nullptr; int* h_lexs = nullptr;
+  // rec patterns (ctc_pattern.h): per line its pattern (0: none), empty when no line of the call has one; then per line
+  // matched | vit | logprob | free_logprob, one block of 4 NLp words (written for the lines that carry a pattern only)
+  std::vector<int> line_pat;
+  int* d_pat = nullptr; int* h_pat = nullptr;
 };
 
 // Launch groups: items [g0, end) where the group always takes its first item; with max_items > 0 it takes up to max_items items,
@@ -804,6 +809,7 @@ void rec_groups(rt_session& s, Pipeline& P) {
     P.d_lexs = s.arena.alloc<int>(P.NLp);   // (zeroed: the lexicon lines of a group without a snap-enabled line are never written)
     RT_HIP_CHECK(hipMemsetAsync(P.d_lexs, 0, (size_t)P.NLp * sizeof(int), s.st));
   }
+  if (!P.line_pat.empty()) P.d_pat = s.arena.alloc<int>((size_t)4 * P.NLp);
   static const long long REC_GROUP_PX = getenv("RT_REC_GROUP_PX") ? atoll(getenv("RT_REC_GROUP_PX")) : (long long)24000000;  // measured sweet spot (profiles/README.md)
   for (int l0 = 0; l0 < P.NL;) {
     const int l1 = group_end(l0, P.NL, 0, REC_GROUP_PX, [&](int l) { return (long long)rh * P.line_W[l]; });
@@ -829,7 +835,8 @@ void rec_groups(rt_session& s, Pipeline& P) {
     const long long t0 = P.tok_off[l0];
     const rt_lexicons& X = *s.lexicons;
     const RecTailPlan tail = rec_tail_plan(P.tok_off.data(), l0, l1, P.line_set.empty() ? nullptr : P.line_set.data(),
-                                           P.line_lex.empty() ? nullptr : P.line_lex.data(), X.tb, X.snap);
+                                           P.line_lex.empty() ? nullptr : P.line_lex.data(), X.tb, X.snap,
+                                           P.line_pat.empty() ? nullptr : P.line_pat.data(), &s.patterns->tb);
     if (!tail.table_fits())
       throw RtError(RT_ERR_CAPACITY, "rec lexicons: " + std::to_string(tail.lines.size()) + " lines of one rec group carry lexicons of " +
                                          std::to_string(tail.table) + " entries in all, more than the " + std::to_string(lx::MAX_GROUP_TABLE) +
@@ -854,11 +861,12 @@ void rec_groups(rt_session& s, Pipeline& P) {
       }
       words = {hwl, P.d_meta.label + l0, P.d_meta.cscore + l0, d_wcol + t0, P.d_wcount + l0, P.d_words + t0};
     }
+    auto patf = [&](int k) { return P.d_pat ? reinterpret_cast<float*>(P.d_pat + (size_t)k * P.NLp) : nullptr; };   // vit | logprob | free_logprob
     const rt_session::RecTail t{z5, d_idx + t0, d_prob + t0, Lt.d, ln, s.charsets->d_masks, s.charsets->words,
                                 X.d_lex, X.d_entries, X.d_order, X.d_ids, X.d_snap, cand_k, 0,
                                 P.d_tok + t0, P.d_meta.ntok + l0, P.d_meta.rscore + l0, nullptr, P.d_lexm, P.d_lexn, P.d_lexs, nullptr,
                                 P.d_ccol ? P.d_ccol + t0 : nullptr, P.d_cands ? P.d_cands + t0 * cand_k : nullptr,
-                                words.h_lines ? &words : nullptr};
+                                words.h_lines ? &words : nullptr, s.patterns->d, P.d_pat, patf(1), patf(2), patf(3)};
     s.rec_tail(tail, s.rec->core(), t);
     l0 = l1;
   }
@@ -889,6 +897,10 @@ void line_round_trip(rt_session& s, Pipeline& P) {
       P.h_lexs = s.pinned.alloc<int>(P.NLp);
       RT_HIP_CHECK(hipMemcpyAsync(P.h_lexs, P.d_lexs, (size_t)P.NLp * sizeof(int), hipMemcpyDeviceToHost, s.st));
     }
+  }
+  if (P.d_pat) {   // (and the pattern results)
+    P.h_pat = s.pinned.alloc<int>((size_t)4 * P.NLp);
+    RT_HIP_CHECK(hipMemcpyAsync(P.h_pat, P.d_pat, (size_t)4 * P.NLp * sizeof(int), hipMemcpyDeviceToHost, s.st));
   }
   s.sync(); s.check_flags();
 }
@@ -934,6 +946,16 @@ void results(const rt_session& s, const Pipeline& P, rt_results& res) {
         for (int j = 0; j < R.lex_n[k]; j++) R.lex_matches[(size_t)k * lx::MATCHES + j] = P.h_lexm[(size_t)li * lx::MATCHES + j];
       }
     }
+    if (P.h_pat) {   // rec patterns: a line without one reports pattern 0
+      R.pat_id.assign((size_t)nb, 0); R.pat_res.assign((size_t)nb, pt::LineResult{0, 0.0f, 0.0f, 0.0f});
+      const float* f = reinterpret_cast<const float*>(P.h_pat);
+      for (int k = 0; k < nb; k++) {
+        const int li = p.first_line + k;
+        if (P.line_pat[li] <= 0) continue;
+        R.pat_id[k] = P.line_pat[li];
+        R.pat_res[k] = pt::LineResult{P.h_pat[li] == 1 ? 1 : 0, f[P.NLp + li], f[2 * (size_t)P.NLp + li], f[3 * (size_t)P.NLp + li]};
+      }
+    }
     if (s.cfg.rec_return_word_box) {   // word quads to original-image coordinates, word texts from the dictionary
       R.words.resize(nb); R.word_text.resize(nb);
       for (int k = 0; k < nb; k++) {
@@ -975,7 +997,7 @@ std::string rt_format_f32_impl(float v) { return fnum(v); }
 
 rt_results* rt_session::run_pages(const uint8_t* const* rgb, const int* hs, const int* ws, int n_pages, int mem,
                                   const float* const* det_map_override, const Regions* regions, int rec_charset_default,
-                                  int rec_lexicon_default) {
+                                  int rec_lexicon_default, int rec_pattern_default) {
   if (g_trace) fprintf(stderr, "[rt host] %-28s %8.3f ms\n", "between calls", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - last_exit).count());
   HostTick tick0;
   // a one-page call is the reference's real mode (retto-cli/src/main.rs:80-86): it polls through its waits; a multi-page batch
@@ -1003,6 +1025,9 @@ rt_results* rt_session::run_pages(const uint8_t* const* rgb, const int* hs, cons
   }
   P.line_set = line_option(P, regions ? regions->charsets : nullptr, rec_charset_default, (int)charsets->ids.size(), "charset");
   P.line_lex = line_option(P, regions ? regions->lexicons : nullptr, rec_lexicon_default, (int)lexicons->host.size(), "lexicon");
+  P.line_pat = line_option(P, regions ? regions->patterns : nullptr, rec_pattern_default, (int)patterns->host.size(), "pattern");
+  for (size_t li = 0; li < P.line_pat.size() && !P.line_lex.empty(); li++)   // (the entry points refuse this before anything is queued)
+    if (P.line_pat[li] > 0 && P.line_lex[li] > 0) throw RtError(RT_ERR_INVALID, "line " + std::to_string(li) + " carries both a rec pattern and a rec lexicon");
   crop_stage(*this, P);
   if (P.NL > 0) {
     tick.lap("crop plan + warp enqueue");
@@ -1241,6 +1266,9 @@ void rt_session::free_stage() {
 rt_ticket* rt_session::submit_batch(const uint8_t* const* rgb, const int* hs, const int* ws, int n_pages, int mem,
                                     const float* const* det_map_override, rt_stage_callback cb, void* user,
                                     std::vector<rt::EncodedPage>* enc, const Regions* regions) {
+  if (!regions && rec_pattern > 0 && rec_lexicon > 0)
+    throw RtError(RT_ERR_INVALID, "the session defaults name both a rec pattern (" + std::to_string(rec_pattern) + ") and a rec lexicon (" +
+                                      std::to_string(rec_lexicon) + "): a line may not carry both");
   ensure_workers();
   std::unique_ptr<rt_ticket> t(new rt_ticket());
   const int nl = std::max(1, std::min<int>(std::min<int>((int)helpers.size() + 1, active_lanes), std::max(n_pages, 1)));
@@ -1252,6 +1280,8 @@ rt_ticket* rt_session::submit_batch(const uint8_t* const* rgb, const int* hs, co
   if (regions && regions->lexicons) t->region_lexicons.assign(regions->lexicons, regions->lexicons + n_pages);
   t->rec_charset = rec_charset;   // (the lanes run later: the default is the one of the submitting call)
   t->rec_lexicon = rec_lexicon;
+  if (regions && regions->patterns) t->region_patterns.assign(regions->patterns, regions->patterns + n_pages);
+  t->rec_pattern = rec_pattern;
   t->parts.assign((size_t)nl, nullptr); t->errs.resize((size_t)nl); t->first.assign((size_t)nl + 1, 0);
   {
     // contiguous ranges of about equal work: det pixels after the session size limit (a2) plus a constant per page
@@ -1303,9 +1333,10 @@ rt_ticket* rt_session::submit_batch(const uint8_t* const* rgb, const int* hs, co
         if (!tp->ev_up.empty()) RT_HIP_CHECK(hipStreamWaitEvent(s->st, tp->ev_up[(size_t)l], 0));
         Regions rg{nullptr, nullptr};
         if (!tp->quads.empty()) rg = Regions{tp->quads.data() + f0, tp->n_quads.data() + f0, tp->region_sets.empty() ? nullptr : tp->region_sets.data() + f0,
-                                                  tp->region_lexicons.empty() ? nullptr : tp->region_lexicons.data() + f0};
+                                                  tp->region_lexicons.empty() ? nullptr : tp->region_lexicons.data() + f0,
+                                                  tp->region_patterns.empty() ? nullptr : tp->region_patterns.data() + f0};
         tp->parts[l] = s->run_pages(tp->rgb.data() + f0, tp->hs.data() + f0, tp->ws.data() + f0, f1 - f0, tp->mem_lane,
-                                    tp->maps.empty() ? nullptr : tp->maps.data() + f0, tp->quads.empty() ? nullptr : &rg, tp->rec_charset, tp->rec_lexicon);
+                                    tp->maps.empty() ? nullptr : tp->maps.data() + f0, tp->quads.empty() ? nullptr : &rg, tp->rec_charset, tp->rec_lexicon, tp->rec_pattern);
       } catch (...) {
         tp->errs[l] = std::current_exception();
         s->failed = true;
@@ -1369,9 +1400,12 @@ rt_results* rt_session::run_batch(const uint8_t* const* rgb, const int* hs, cons
       rt_session* self;
       ~Disarm() { self->stage_cb = nullptr; self->stage_mu = nullptr; }
     } disarm{this};
+    if (rec_pattern > 0 && rec_lexicon > 0)
+      throw RtError(RT_ERR_INVALID, "the session defaults name both a rec pattern (" + std::to_string(rec_pattern) + ") and a rec lexicon (" +
+                                        std::to_string(rec_lexicon) + "): a line may not carry both");
     stage_cb = cb; stage_user = user; stage_mu = &cb_mu; page_base = 0;
     try {
-      return run_pages(rgb, hs, ws, n_pages, mem, det_map_override, nullptr, rec_charset, rec_lexicon);
+      return run_pages(rgb, hs, ws, n_pages, mem, det_map_override, nullptr, rec_charset, rec_lexicon, rec_pattern);
     } catch (...) { failed = true; throw; }
   }
   return wait_batch(submit_batch(rgb, hs, ws, n_pages, mem, det_map_override, cb, user));
@@ -1381,7 +1415,9 @@ rt_results* rt_session::run_batch(const uint8_t* const* rgb, const int* hs, cons
 // invertible homography -- checked here, for every page, before anything is queued.
 rt_results* rt_session::run_regions(const uint8_t* const* rgb, const int* hs, const int* ws, int n_pages, int mem,
                                     const float* const* quads, const int* n_quads, const int* const* region_charsets,
-                                    const int* const* region_lexicons) {
+                                    const int* const* region_lexicons, const int* const* region_patterns) {
+  std::vector<std::vector<int>> pats((size_t)n_pages);   // (and their patterns)
+  std::vector<const int*> pp_((size_t)n_pages, nullptr);
   std::vector<std::vector<float>> clamped((size_t)n_pages);
   std::vector<const float*> qp((size_t)n_pages, nullptr);
   // the regions' charsets with -1 resolved to the session default of this call (rec charsets, ctc_charset.h)
@@ -1427,8 +1463,19 @@ rt_results* rt_session::run_regions(const uint8_t* const* rgb, const int* hs, co
       if (v >= 0) lexs[(size_t)i][(size_t)k] = v;
     }
     lp[(size_t)i] = lexs[(size_t)i].data();
+    pats[(size_t)i].assign((size_t)n_quads[i], rec_pattern);
+    for (int k = 0; k < n_quads[i]; k++) {
+      const int v = region_patterns && region_patterns[i] ? region_patterns[i][k] : -1;
+      if (v < -1 || v > (int)patterns->host.size())
+        throw RtError(RT_ERR_INVALID, where + " region " + std::to_string(k) + ": unknown pattern id " + std::to_string(v));
+      if (v >= 0) pats[(size_t)i][(size_t)k] = v;
+      if (pats[(size_t)i][(size_t)k] > 0 && lexs[(size_t)i][(size_t)k] > 0)
+        throw RtError(RT_ERR_INVALID, where + " region " + std::to_string(k) + ": both a rec pattern (" + std::to_string(pats[(size_t)i][(size_t)k]) +
+                                          ") and a rec lexicon (" + std::to_string(lexs[(size_t)i][(size_t)k]) + "): a line may not carry both");
+    }
+    pp_[(size_t)i] = pats[(size_t)i].data();
   }
-  const Regions rg{qp.data(), n_quads, sp.data(), lp.data()};
+  const Regions rg{qp.data(), n_quads, sp.data(), lp.data(), pp_.data()};
   const int nl = std::max(1, std::min<int>(std::min<int>((int)helpers.size() + 1, active_lanes), std::max(n_pages, 1)));
   if (nl <= 1) {   // one lane: on the caller's thread, as run_batch
     try {

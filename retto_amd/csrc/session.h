@@ -47,6 +47,8 @@ struct rt_results {
     // lexicon snap (ctc_lexicon_align.h): per line 1 where its decode is its aligned best entry.  Empty when no lexicon of the
     // call's lines had snap on
     std::vector<uint8_t> lex_snapped;
+    // rec patterns (ctc_pattern.h): per line its pattern (0: none) and result; empty when no line of the call carried one
+    std::vector<int32_t> pat_id; std::vector<rt::pt::LineResult> pat_res;
     std::string json[3];
   };
   std::vector<Page> pages;
@@ -86,6 +88,8 @@ struct rt_ticket {
   // rec lexicons (ctc_lexicon.h): the same two for lexicons
   int rec_lexicon = 0;
   std::vector<const int*> region_lexicons;
+  int rec_pattern = 0;
+  std::vector<const int*> region_patterns;
   std::vector<int> first;
   std::vector<rt_results*> parts;
   std::vector<std::exception_ptr> errs;
@@ -144,6 +148,23 @@ struct rt_lexicons {
   ~rt_lexicons() { free_device(); if (d_snap) (void)hipFree(d_snap); }
 };
 
+// The session's rec patterns (ctc_pattern.h), shared with the helper lanes.  Pattern k (1-based, rt_pattern_create's id) is
+// host[k - 1] (stable addresses: rt_pattern_text hands the text out) and pattern k - 1 of `tb`, whose tables sit on the device as
+// `d`.  Only changed while no ticket is in flight and every lane's stream is drained (rt_pattern_create is a guarded call): the
+// tables are rebuilt and copied whole, with blocking copies.
+struct rt_patterns {
+  struct Host { std::string text; int S, P, min_steps; };
+  std::vector<std::unique_ptr<Host>> host;
+  rt::pt::Tables tb;
+  rt::pt::DevTables d{};
+  void free_device() {
+    const void* p[] = {d.pats, d.pair_c, d.pair_pb, d.pair_pe, d.seg, d.preds};
+    for (const void* q : p) if (q) (void)hipFree(const_cast<void*>(q));
+    d = rt::pt::DevTables{};
+  }
+  ~rt_patterns() { free_device(); }
+};
+
 // internal to the library (never accepted from a caller): pages already in HBM, det map overrides still host pointers
 #define RT_MEM_STAGED_MAPS_HOST 3
 
@@ -173,6 +194,8 @@ struct rt_session {
   int rec_charset = 0;            // rt_set_rec_charset: the default of every line of the pipeline calls that follow (0: none)
   std::shared_ptr<rt_lexicons> lexicons;   // rec lexicons (shared with the helper lanes)
   int rec_lexicon = 0;            // rt_set_rec_lexicon: likewise
+  std::shared_ptr<rt_patterns> patterns;   // rec patterns (shared with the helper lanes)
+  int rec_pattern = 0;            // rt_set_rec_pattern: likewise
   uint8_t* d_word_raw = nullptr;  // rec_return_word_box: wb::raw_class of every dictionary entry (device; owned by the main lane)
   std::string last_error;
   int* d_flags = nullptr;         // [0] thumbnail/resize error flag
@@ -226,10 +249,12 @@ struct rt_session {
     rt::lx::Match* lexm; int* lexn; int* lexs; float* vit;   // (lexs: snap groups only; vit: optional)
     int* ccol; rt::cc::Cand* cands;           // cand_k > 0: the kept tokens' time steps and [cand_k] candidates
     const WordBoxes* wb;                      // or null
+    // rec patterns (ctc_pattern.h): pt::Tables on the device and the per-line results, indexed by pt::Line::slot
+    rt::pt::DevTables d_pat; int* patm; float* patv; float* patlp; float* patfree;
   };
   // The tail of one rec group behind the net, in the one order that is right: the charsets replace the restricted rows' (idx, prob)
   // before anything reads them; a snap group's lexicons run next, so that the decode reads the snapped lines' aligned rows;
-  // pp::ctc_decode; the word boxes; any other group's lexicons; the candidates last, for their host wait.  The plan's tables go
+  // then the patterns, whose matched lines overwrite theirs; pp::ctc_decode; the word boxes; any other group's lexicons; the candidates last, for their host wait.  The plan's tables go
   // through `pinned` into `scratch`, where the workspace comes from too: the caller rewinds it per group, after this.
   void rec_tail(const rt::RecTailPlan& plan, const rt::SvtrCore& core, const RecTail& t);
   // rec_return_candidates = K (ctc_candidates.h): kept token j of a line at first row o gets ccol[o + j] and cands[(o + j) * K ...].
@@ -244,10 +269,16 @@ struct rt_session {
   // one k_ctc_lexicon_topk over all lines -> lexm / lexn.  No host wait.  A snap group (ctc_lexicon_align.h) runs the top-K per chunk,
   // then k_ctc_lexicon_align on the resident logits: it overwrites the snapped lines' rows of idx / prob and writes every lexs[slot].
   void ctc_lexicon(const rt::RecTailPlan& plan, const rt::SvtrCore& core, const RecTail& t);
+  // Rec patterns (ctc_pattern.h) over the plan's pattern lines, chunked as the lexicon lines are: row gather, the CTC FC,
+  // k_ctc_row_lse and k_ctc_row_max, then k_ctc_pattern_viterbi on the resident logits: it overwrites the matched lines' rows of
+  // idx / prob and writes every pattern line's patm / patv / patlp / patfree [slot].  No host wait.
+  void ctc_pattern(const rt::RecTailPlan& plan, const rt::SvtrCore& core, const RecTail& t);
   // rt_charset_create: compiles the set (rt::compile_charset), stores it and returns its id
   int charset_create(const char* utf8, size_t len, const int32_t* ids, int n_ids);
   // rt_lexicon_create: compiles the entries (rt::compile_lexicon), stores them and returns the lexicon's id
   int lexicon_create(const char* utf8, size_t len, const int32_t* ids, const int32_t* entry_lens, int n_id_entries);
+  // rt_pattern_create: compiles the pattern (rt::pt::compile), stores it and returns its id
+  int pattern_create(const char* utf8, size_t len);
   // rt_lexicon_set_snap: the lexicon's min_posterior (ctc_lexicon_align.h), on the host and in the device table
   void lexicon_set_snap(int lexicon, float min_posterior);
   // L2
@@ -270,7 +301,8 @@ struct rt_session {
   // regions (rt_run_regions): quads[i] = n_quads[i] x 8 validated, clamped floats of page i, valid until the ticket is waited for
   // charsets (rt_run_regions_charsets): per page the regions' charset ids, already resolved (>= 0) and checked; null: the default
   // lexicons (rt_run_regions_lexicons): the same for rec lexicons
-  struct Regions { const float* const* quads; const int* n_quads; const int* const* charsets = nullptr; const int* const* lexicons = nullptr; };
+  struct Regions { const float* const* quads; const int* n_quads; const int* const* charsets = nullptr; const int* const* lexicons = nullptr;
+                   const int* const* patterns = nullptr; };   // patterns (rt_run_regions_patterns): the same for rec patterns
   rt_ticket* submit_batch(const uint8_t* const* rgb, const int* hs, const int* ws, int n_pages, int mem,
                           const float* const* det_map_override, rt_stage_callback cb = nullptr, void* user = nullptr,
                           std::vector<rt::EncodedPage>* enc = nullptr, const Regions* regions = nullptr);
@@ -281,13 +313,14 @@ struct rt_session {
                         const float* const* det_map_override, rt_stage_callback cb = nullptr, void* user = nullptr);
   rt_results* run_pages(const uint8_t* const* rgb, const int* hs, const int* ws, int n_pages, int mem,
                         const float* const* det_map_override, const Regions* regions = nullptr,
-                        int rec_charset_default = 0, int rec_lexicon_default = 0);  // one lane
+                        int rec_charset_default = 0, int rec_lexicon_default = 0, int rec_pattern_default = 0);  // one lane
   // rt_run_regions: checks and clamps every quad (RT_ERR_INVALID naming page and region; nothing is queued then), then the
   // pages go over the lanes as run_batch's do, from the crop plan on
   // charsets (or null; entries may be null): per region -1 = the session default, 0 = none, >= 1 = that charset
   rt_results* run_regions(const uint8_t* const* rgb, const int* hs, const int* ws, int n_pages, int mem,
                           const float* const* quads, const int* n_quads, const int* const* charsets = nullptr,
-                          const int* const* lexicons = nullptr);   // lexicons: the same convention for rec lexicons
+                          const int* const* lexicons = nullptr,    // lexicons: the same convention for rec lexicons
+                          const int* const* patterns = nullptr);   // patterns: likewise; a region may not carry both a pattern and a lexicon
 };
 
 rt_session* rt_session_create(const rt_config* cfg);
