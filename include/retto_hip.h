@@ -232,6 +232,38 @@ typedef struct rt_ticket rt_ticket;
 RT_API int rt_submit_batch(rt_session* s, const uint8_t* const* rgb, const int* hs, const int* ws, int n_pages, int mem,
                            const float* const* det_map_override, rt_ticket** out);
 RT_API int rt_wait_batch(rt_session* s, rt_ticket* ticket, rt_results** out);
+/* Det tiles (retto_amd/csrc/det_tiles.h states the rule): large pages detected at their own resolution.  A caller who raises
+ * max_side_len (or det_limit_side_len) so that a 7680 x 4320 scan reaches the detector unshrunk would otherwise push one image
+ * of 33 Mpixel through the det network: every activation resident at once, squeeze-excite pooled over the whole scan, every
+ * layer at a shape nobody tuned.  With tiles on, a page whose det input is larger than `tile` in either direction is run through
+ * the det network as overlapping tiles of tile x tile pixels (a direction the page fits into keeps its length), and each tile's
+ * trusted part -- up to the middle of the overlap with its neighbour -- is copied into the ONE page probability map.  The copy
+ * is a selection, every page pixel comes from exactly one tile; DB post-processing, the boxes, the crops, cls, rec and every rec
+ * option run on that map unchanged, rt_results_det_checksum is taken over it, a det_map_override still has the page's det
+ * size.  The tiles of all pages of a call share the det launch groups (and rt_config.det_sub_batch) with the untiled pages.
+ * A page that fits into one tile takes the whole-page path bit for bit, and with tiles off (the default) nothing is launched
+ * that was not before.  rt_run_regions and rt_det never tile.
+ * tile = 0: off; otherwise a multiple of 32, at least 64.  overlap: a multiple of 32, 0 <= overlap <= tile / 2 (64 suits the
+ * default det graph).  Anything else: RT_ERR_INVALID naming the parameter.  The setting holds for the pipeline calls that follow
+ * on every lane (rt_submit_* takes it as it is at the call); fails like every other call while tickets are in flight.
+ * The largest det input, tiled or not, is RT_DET_MAX_PIXELS pixels (DB post-processing indexes a page's pixels, rows and hull
+ * points with int; 8192 x 32736, say): a page beyond it fails with RT_ERR_CAPACITY before anything is queued.
+ * rt_config.max_boxes_per_page stays the caller's knob for pages with many lines. */
+#define RT_DET_MAX_PIXELS 268434432
+RT_API int rt_set_det_tiles(rt_session* s, int tile, int overlap);
+/* the setting (each optional); RT_ERR_INVALID for a NULL session */
+RT_API int rt_det_tiles(const rt_session* s, int* tile, int* overlap);
+/* The tile plan of a det input of h x w (both multiples of 32), GPU-free and sessionless.  *n_rows x *n_cols tiles of *tile_h x
+ * *tile_w pixels, in row-major order; tile row i starts at row_origin[i] and owns the page rows [i ? row_bound[i - 1] : 0,
+ * row_bound[i]), likewise the columns.  Each output is optional; arrays are written when row_cap / col_cap hold the plan
+ * (RT_ERR_INVALID otherwise, the counts still written).  A page that is not tiled (tile = 0, or it fits) is one tile.  Bad
+ * parameters: RT_ERR_INVALID naming the parameter; more than RT_DET_MAX_PIXELS: RT_ERR_CAPACITY (rt_last_error(NULL)). */
+RT_API int rt_det_tile_plan(int h, int w, int tile, int overlap, int32_t* row_origin, int32_t* row_bound, int row_cap,
+                            int32_t* col_origin, int32_t* col_bound, int col_cap, int* n_rows, int* n_cols, int* tile_h, int* tile_w);
+/* The det stage of a one-page pipeline call on rgb_det, a host RGB8 image at det-input size h x w, under the session's det tiles:
+ * the pipeline's own function and launch groups.  tile_maps_out (optional): every tile's own map, tile_h x tile_w floats each,
+ * packed in plan order; page_map_out [h * w]: the stitched map (the network's map for a page that is not tiled). */
+RT_API int rt_debug_det_tiles(rt_session* s, const uint8_t* rgb_det, int h, int w, float* tile_maps_out, float* page_map_out);
 /* The pipeline over regions the caller already knows (form fields, subtitles, corrected boxes, another detector's boxes):
  * quads[i] = n_quads[i] x 8 floats in host memory, TL, TR, BR, BL of each region in original-page coordinates; mem
  * (RT_MEM_HOST or RT_MEM_DEVICE) says where the pages live.  Every coordinate is clamped to [0, ori - 1] (no rounding); line k
@@ -878,6 +910,11 @@ RT_API int rt_debug_glue32(rt_session* s, int op, const int* ip, const float* fp
  * (workgroup-staged; the unfused depthwise + GEMM pair where it has no instance), 1 = k_lc_wave (direct loads, stride 1 only),
  * 3 = k_lc_lds (production).  stride: 1, 2, or 21 = (2, 1).  Returns the average ms and the max |diff| against form 0. */
 RT_API int rt_bench_lc(rt_session* s, int n, int h, int w, int cin, int cout, int stride, int form, int iters, float* ms_out, float* maxdiff_out);
+/* The main lane's arenas (tools/bench_det_tiles.py): out3 = the largest pass so far, in bytes, of the call arena, of the scratch
+ * arena (network activations, rewound per launch group) and of the DB post-processing workspace. */
+RT_API int rt_debug_arena_high_water(rt_session* s, long long* out3);
+/* iters device-to-device hipMemcpyAsync of `bytes` bytes on the session's stream, timed with events: *ms_out = the mean per copy. */
+RT_API int rt_bench_memcpy_d2d(rt_session* s, size_t bytes, int iters, float* ms_out);
 
 #ifdef __cplusplus
 }

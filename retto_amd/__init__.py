@@ -480,6 +480,31 @@ def debug_pattern_compile(dict_bytes: bytes, pattern) -> dict:
             "classes": nc.value}
 
 
+_TILE_PLAN_BUFS = None   # the four output arrays of det_tile_plan, grown on demand (a plan grid asks a hundred thousand times)
+
+
+def det_tile_plan(h: int, w: int, tile: int, overlap: int = 64) -> dict:
+    """rt_det_tile_plan: the det tile plan (retto_amd/csrc/det_tiles.h) of a det input of h x w, GPU-free: a dict with tile_h,
+    tile_w, and per direction the tiles' origins and ownership bounds (tile i owns [bounds[i - 1], bounds[i]), from 0) as
+    lists: row_origins, row_bounds, col_origins, col_bounds.  Tiles are in row-major order."""
+    global _TILE_PLAN_BUFS
+    lib = _lib.load()
+    nr, nc, th, tw = C.c_int(), C.c_int(), C.c_int(), C.c_int()
+    cap = len(_TILE_PLAN_BUFS[0]) if _TILE_PLAN_BUFS else 64
+    while True:
+        if _TILE_PLAN_BUFS is None or len(_TILE_PLAN_BUFS[0]) < cap:
+            _TILE_PLAN_BUFS = [(C.c_int32 * cap)() for _ in range(4)]
+        ro, rb, co, cb = _TILE_PLAN_BUFS
+        rc = lib.rt_det_tile_plan(int(h), int(w), int(tile), int(overlap), ro, rb, cap, co, cb, cap, C.byref(nr), C.byref(nc),
+                                  C.byref(th), C.byref(tw))
+        if rc == 8 and max(nr.value, nc.value) > cap:
+            cap = 2 * max(nr.value, nc.value)
+            continue
+        _check(rc, None)
+        return {"tile_h": th.value, "tile_w": tw.value, "row_origins": ro[:nr.value], "row_bounds": rb[:nr.value],
+                "col_origins": co[:nc.value], "col_bounds": cb[:nc.value]}
+
+
 def parse_dictionary(data: bytes) -> List[str]:
     """rt_parse_dictionary: RecCharacter::new (rec_processor.rs:29-46) -- "blank", the file's trimmed lines, " "."""
     lib = _lib.load()
@@ -683,6 +708,32 @@ class RettoSession:
             return [self._collect(r, i) for i in range(len(pages))]
         finally:
             self._hd.lib.rt_results_free(r)
+
+    # -- det tiles --------------------------------------------------------------------------
+    def set_det_tiles(self, tile: int, overlap: int = 64) -> None:
+        """rt_set_det_tiles: pages whose det input is larger than ``tile`` either way are detected as overlapping tiles whose
+        trusted parts are stitched into the one page map (retto_amd/csrc/det_tiles.h); 0 = off, the default.  tile: a multiple
+        of 32, at least 64; overlap: a multiple of 32, at most tile / 2.  Holds for the pipeline calls that follow."""
+        _check(self._hd.lib.rt_set_det_tiles(self._hd.h, int(tile), int(overlap)), self._hd.h)
+
+    @property
+    def det_tiles(self) -> Tuple[int, int]:
+        """rt_det_tiles: (tile, overlap) as set; tile 0 = off."""
+        t, o = C.c_int(), C.c_int()
+        _check(self._hd.lib.rt_det_tiles(self._hd.h, C.byref(t), C.byref(o)), self._hd.h)
+        return t.value, o.value
+
+    def debug_det_tiles(self, rgb_det: np.ndarray):
+        """rt_debug_det_tiles: the det stage of a one-page call on an RGB8 image at det-input size (both dimensions multiples
+        of 32) under the session's det tiles.  Returns (tile_maps [n_rows * n_cols, tile_h, tile_w] in plan order, page_map
+        [h, w], plan) with plan = det_tile_plan(h, w, *self.det_tiles)."""
+        img = np.ascontiguousarray(rgb_det, np.uint8); h, w = img.shape[:2]
+        tile, overlap = self.det_tiles
+        plan = det_tile_plan(h, w, tile, overlap)
+        n = len(plan["row_origins"]) * len(plan["col_origins"])
+        tiles = np.empty((n, plan["tile_h"], plan["tile_w"]), np.float32); page = np.empty((h, w), np.float32)
+        _check(self._hd.lib.rt_debug_det_tiles(self._hd.h, img.ctypes.data, h, w, tiles.ctypes.data, page.ctypes.data), self._hd.h)
+        return tiles, page, plan
 
     # -- rec charsets -----------------------------------------------------------------------
     def create_charset(self, text: str = "", ids: Sequence[int] = ()) -> int:

@@ -97,6 +97,7 @@ EXPORTS = [
     "rt_debug_ctc_lexicon_align_host",
     "rt_pattern_create", "rt_pattern_info", "rt_pattern_text", "rt_set_rec_pattern", "rt_run_regions_patterns", "rt_results_rec_pattern",
     "rt_debug_pattern_compile", "rt_debug_ctc_pattern", "rt_debug_ctc_pattern_host",
+    "rt_set_det_tiles", "rt_det_tiles", "rt_det_tile_plan", "rt_debug_det_tiles", "rt_debug_arena_high_water", "rt_bench_memcpy_d2d",
 ]
 
 STAGE_CALLBACK = C.CFUNCTYPE(None, C.c_void_p, C.c_int, C.c_int, C.c_char_p)  # rt_stage_callback
@@ -302,5 +303,12 @@ def load():
     lib.rt_debug_ctc_pattern_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
                                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
                                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.rt_set_det_tiles.argtypes = [C.c_void_p, C.c_int, C.c_int]
+    lib.rt_det_tiles.argtypes = [C.c_void_p, P(C.c_int), P(C.c_int)]
+    lib.rt_det_tile_plan.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, P(C.c_int32), P(C.c_int32), C.c_int, P(C.c_int32), P(C.c_int32),
+                                     C.c_int, P(C.c_int), P(C.c_int), P(C.c_int), P(C.c_int)]
+    lib.rt_debug_det_tiles.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+    lib.rt_debug_arena_high_water.argtypes = [C.c_void_p, P(C.c_longlong)]
+    lib.rt_bench_memcpy_d2d.argtypes = [C.c_void_p, C.c_size_t, C.c_int, P(C.c_float)]
     _lib = lib
     return lib

@@ -53,6 +53,11 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--rec-lexicon-snap", type=float, default=None, metavar="P",
                     help="with --rec-lexicon: a line whose best entry's posterior reaches P (0 < P <= 1) takes that entry, "
                          "aligned to its time steps, as its text, score, words and candidates (\"lexicon_snapped\" per line)")
+    ap.add_argument("--det-tile", type=int, default=0, metavar="N",
+                    help="detect pages whose det input is larger than N pixels either way as overlapping N x N tiles, stitched "
+                         "into one page map (large scans at their own resolution); a multiple of 32, at least 64; 0 = off")
+    ap.add_argument("--det-tile-overlap", type=int, default=64, metavar="M",
+                    help="with --det-tile: the tiles' overlap, a multiple of 32, at most N / 2")
     return ap
 
 
@@ -83,6 +88,8 @@ def main(argv=None) -> int:
     cfg.rec_processor_config.return_candidates = a.rec_candidates
     cfg.crop_source = a.crop_source
     session = retto_amd.RettoSession(cfg)
+    if a.det_tile:
+        session.set_det_tiles(a.det_tile, a.det_tile_overlap)
     if a.rec_charset is not None:
         session.set_rec_charset(session.create_charset(a.rec_charset))
     if a.rec_lexicon is not None:

@@ -411,6 +411,40 @@ int rt_results_rec_pattern(const rt_results* r, int page, int line, rt_pattern_r
   if (out) *out = rt_pattern_result{p->pat_id[(size_t)line], v.matched, v.logprob, v.free_logprob};
   return 1;
 }
+static_assert(RT_DET_MAX_PIXELS == dt::MAX_DET_PIXELS, "the header's det input limit is det_tiles.h's");
+int rt_set_det_tiles(rt_session* s, int tile, int overlap) {
+  RT_REQUIRE(s, s, "rt_set_det_tiles: null session");
+  return guarded(s, [&] {
+    if (const char* why = dt::check_params(tile, overlap)) throw RtError(RT_ERR_INVALID, std::string("rt_set_det_tiles: ") + why);
+    s->det_tile = tile; s->det_overlap = overlap;
+    for (auto& h : s->helpers) { h->det_tile = tile; h->det_overlap = overlap; }
+  });
+}
+int rt_det_tiles(const rt_session* s, int* tile, int* overlap) {
+  if (!s) return RT_ERR_INVALID;
+  if (tile) *tile = s->det_tile;
+  if (overlap) *overlap = s->det_overlap;
+  return RT_OK;
+}
+int rt_det_tile_plan(int h, int w, int tile, int overlap, int32_t* row_origin, int32_t* row_bound, int row_cap, int32_t* col_origin,
+                     int32_t* col_bound, int col_cap, int* n_rows, int* n_cols, int* tile_h, int* tile_w) {
+  return guarded(nullptr, [&] {
+    if (const char* why = dt::check_params(tile, overlap)) throw RtError(RT_ERR_INVALID, std::string("rt_det_tile_plan: ") + why);
+    std::string why;
+    const int rc = dt::check_page(h, w, &why);
+    if (rc != dt::OK) throw RtError(rc, "rt_det_tile_plan: " + why);
+    // (an axis the tile covers is one tile of the axis' length, so a page that is not tiled comes out as one tile)
+    const dt::Axis R = dt::axis_plan(h, tile, overlap), C = dt::axis_plan(w, tile, overlap);
+    if (n_rows) *n_rows = R.n();
+    if (n_cols) *n_cols = C.n();
+    if (tile_h) *tile_h = R.len;
+    if (tile_w) *tile_w = C.len;
+    if ((row_origin || row_bound) && row_cap < R.n()) throw RtError(RT_ERR_INVALID, "rt_det_tile_plan: row_cap is smaller than the " + std::to_string(R.n()) + " tile rows");
+    if ((col_origin || col_bound) && col_cap < C.n()) throw RtError(RT_ERR_INVALID, "rt_det_tile_plan: col_cap is smaller than the " + std::to_string(C.n()) + " tile columns");
+    for (int i = 0; i < R.n(); i++) { if (row_origin) row_origin[i] = R.origin[(size_t)i]; if (row_bound) row_bound[i] = R.bound[(size_t)i]; }
+    for (int i = 0; i < C.n(); i++) { if (col_origin) col_origin[i] = C.origin[(size_t)i]; if (col_bound) col_bound[i] = C.bound[(size_t)i]; }
+  });
+}
 int rt_set_rec_lexicon(rt_session* s, int lexicon) {
   RT_REQUIRE(s, s, "rt_set_rec_lexicon: null session");
   return guarded(s, [&] {

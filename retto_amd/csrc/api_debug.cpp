@@ -1412,4 +1412,39 @@ RT_API int rt_bench_lc(rt_session* s, int n, int h, int w, int cin, int cout, in
   });
 }
 
+// The det stage of a one-page pipeline call on a host RGB8 image at det-input size, under the session's det tiles: det_groups itself
+// (rt_session::debug_det_tiles), for tests/test_gpu_det_tiles.py.
+RT_API int rt_debug_det_tiles(rt_session* s, const uint8_t* rgb_det, int h, int w, float* tile_maps_out, float* page_map_out) {
+  RT_REQUIRE(s && rgb_det && page_map_out, s, "rt_debug_det_tiles: null argument");
+  return guarded(s, [&] { s->debug_det_tiles(rgb_det, h, w, tile_maps_out, page_map_out); });
+}
+// The main lane's arenas, for tools/bench_det_tiles.py: the largest pass so far of the call arena, the scratch arena (network
+// activations, rewound per launch group) and the DB post-processing workspace, in bytes.
+RT_API int rt_debug_arena_high_water(rt_session* s, long long* out3) {
+  RT_REQUIRE(s && out3, s, "rt_debug_arena_high_water: null argument");
+  return guarded(s, [&] {
+    out3[0] = (long long)s->arena.high_water(); out3[1] = (long long)s->scratch.high_water(); out3[2] = (long long)s->dbws.high_water();
+  });
+}
+// iters device-to-device hipMemcpyAsync of `bytes` bytes on the session's stream between two buffers of their own, timed with
+// events: *ms_out = the mean per copy.  The yardstick tools/bench_det_tiles.py states the cut and stitch kernels against.
+RT_API int rt_bench_memcpy_d2d(rt_session* s, size_t bytes, int iters, float* ms_out) {
+  RT_REQUIRE(s && ms_out && bytes > 0 && iters > 0, s, "rt_bench_memcpy_d2d: bad argument");
+  return guarded(s, [&] {
+    RT_HIP_CHECK(hipSetDevice(s->device));
+    DevBufs bufs;
+    char* a = bufs.zeroed<char>(bytes); char* b = bufs.zeroed<char>(bytes);
+    Events ev;
+    RT_HIP_CHECK(hipEventCreate(&ev.a)); RT_HIP_CHECK(hipEventCreate(&ev.b));
+    RT_HIP_CHECK(hipMemcpyAsync(b, a, bytes, hipMemcpyDeviceToDevice, s->st));   // (warm-up)
+    RT_HIP_CHECK(hipEventRecord(ev.a, s->st));
+    for (int i = 0; i < iters; i++) RT_HIP_CHECK(hipMemcpyAsync(b, a, bytes, hipMemcpyDeviceToDevice, s->st));
+    RT_HIP_CHECK(hipEventRecord(ev.b, s->st));
+    RT_HIP_CHECK(hipStreamSynchronize(s->st));
+    float ms = 0.f;
+    RT_HIP_CHECK(hipEventElapsedTime(&ms, ev.a, ev.b));
+    *ms_out = ms / (float)iters;
+  });
+}
+
 }  // extern "C"

@@ -10,6 +10,7 @@
 #include "ctc_lexicon.h"
 #include "ctc_lexicon_align.h"
 #include "ctc_pattern.h"
+#include "det_tiles.h"
 
 namespace rt {
 namespace pp {
@@ -141,6 +142,12 @@ void ctc_pattern_viterbi(hipStream_t st, const float* logits, int ld, int classe
 // sum of a float buffer into per-block doubles (partials has ceil(n/65536) entries)
 int sum_blocks(long long n);
 void sum_partial(hipStream_t st, const float* x, long long n, double* partials);
+
+// det tiles (det_tiles.h), one launch per det group each over the group's n tiles (tiles: device; max_tile_pix: the largest
+// th * tw).  cut: every tile's pixels out of its page's RGB8 det image, contiguous at cut + cut_off (16-byte aligned), the form
+// DetModel::run_u8 reads.  stitch: every tile's owned rectangle from maps + map_off into its page map.
+void det_tile_cut(hipStream_t st, const dt::TileDesc* tiles, int n, long long max_tile_pix, uint8_t* cut);
+void det_tile_stitch(hipStream_t st, const dt::TileDesc* tiles, int n, long long max_tile_pix, const float* maps);
 
 }  // namespace pp
 }  // namespace rt

@@ -984,5 +984,58 @@ void sum_partial(hipStream_t st, const float* x, long long n, double* partials) 
   RT_LAUNCH(k_sum_partial, dim3(sum_blocks(n)), dim3(256), 0, st, x, n, partials);
 }
 
+// ---- det tiles (det_tiles.h): pure data movement, one launch per det group each, blockIdx.y = tile of the group -------------
+// Both walk a tile in 16-byte vectors, rows coalesced, with a grid-stride loop over at most DT_MAX_BLOCKS_X blocks a tile (a
+// 960 x 960 tile is 172 800 vectors to cut, up to 230 400 to stitch).  Everything is inside its buffers by the plan: a tile lies
+// inside its page, an owned rectangle inside its tile.
+#define DT_MAX_BLOCKS_X 256
+// cut: the tile's th rows of tw * 3 bytes -> contiguous at cut + cut_off.  tw, x0 and page_w are multiples of 32, so a row is
+// tw * 3 / 16 whole vectors and starts a multiple of 96 bytes from the page's first byte: with the page 16-byte aligned (every
+// page the session made itself; a caller's device page that was not resized need not be) loads and stores are 16 bytes wide,
+// otherwise the loads are bytes.
+__global__ __launch_bounds__(256) void k_det_tile_cut(const dt::TileDesc* __restrict__ tiles, u8* __restrict__ cut) {
+  const dt::TileDesc d = tiles[blockIdx.y];
+  const int vpr = d.tw * 3 / 16;
+  const long long total = (long long)d.th * vpr;
+  u8* dst = cut + d.cut_off;
+  const bool al = ((size_t)d.src & 15) == 0;
+  for (long long v = (long long)blockIdx.x * 256 + threadIdx.x; v < total; v += (long long)gridDim.x * 256) {
+    const int r = (int)(v / vpr), c = (int)(v - (long long)r * vpr);
+    const u8* s = d.src + ((long long)(d.y0 + r) * d.page_w + d.x0) * 3 + (long long)c * 16;
+    uint4 w;
+    if (al) w = *reinterpret_cast<const uint4*>(s);
+    else {
+      unsigned q[4];
+#pragma unroll
+      for (int k = 0; k < 4; k++) q[k] = (unsigned)s[4 * k] | ((unsigned)s[4 * k + 1] << 8) | ((unsigned)s[4 * k + 2] << 16) | ((unsigned)s[4 * k + 3] << 24);
+      w = make_uint4(q[0], q[1], q[2], q[3]);
+    }
+    *reinterpret_cast<uint4*>(dst + v * 16) = w;
+  }
+}
+void det_tile_cut(hipStream_t st, const dt::TileDesc* tiles, int n, long long max_tile_pix, uint8_t* cut) {
+  if (n <= 0 || max_tile_pix <= 0) return;
+  const long long want = (max_tile_pix * 3 / 16 + 255) / 256;
+  RT_LAUNCH(k_det_tile_cut, dim3((unsigned)std::min<long long>(want, DT_MAX_BLOCKS_X), n), dim3(256), 0, st, tiles, cut);
+}
+// stitch: the tile's owned rectangle, (ox1 - ox0) / 4 float4 a row (ownership bounds are multiples of 16), from its map into the
+// page map.  The owned rectangles of a page's tiles partition the page: every page pixel is written once over the call, plain stores.
+__global__ __launch_bounds__(256) void k_det_tile_stitch(const dt::TileDesc* __restrict__ tiles, const float* __restrict__ maps) {
+  const dt::TileDesc d = tiles[blockIdx.y];
+  const int vpr = (d.ox1 - d.ox0) / 4;
+  const long long total = (long long)(d.oy1 - d.oy0) * vpr;
+  const float* src = maps + d.map_off;
+  for (long long v = (long long)blockIdx.x * 256 + threadIdx.x; v < total; v += (long long)gridDim.x * 256) {
+    const int r = (int)(v / vpr), c = (int)(v - (long long)r * vpr);
+    const float4 w = *reinterpret_cast<const float4*>(src + (long long)(d.oy0 - d.y0 + r) * d.tw + (d.ox0 - d.x0) + 4 * c);
+    *reinterpret_cast<float4*>(d.page_map + (long long)(d.oy0 + r) * d.page_w + d.ox0 + 4 * c) = w;
+  }
+}
+void det_tile_stitch(hipStream_t st, const dt::TileDesc* tiles, int n, long long max_tile_pix, const float* maps) {
+  if (n <= 0 || max_tile_pix <= 0) return;
+  const long long want = (max_tile_pix / 4 + 255) / 256;
+  RT_LAUNCH(k_det_tile_stitch, dim3((unsigned)std::min<long long>(want, DT_MAX_BLOCKS_X), n), dim3(256), 0, st, tiles, maps);
+}
+
 }  // namespace pp
 }  // namespace rt

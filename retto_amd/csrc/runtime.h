@@ -74,6 +74,7 @@ class Arena {
   void mark_call() { need_mark_ = need_; }
   size_t used() const { return off_; }
   size_t peak() const { return need_; }
+  size_t high_water() const { return pass_ > need_ ? pass_ : need_; }   // largest pass so far, the current one included
   size_t capacity() const { return cap_; }
   template <typename T>
   T* alloc(size_t count) { return reinterpret_cast<T*>(alloc_bytes(count * sizeof(T))); }

@@ -522,7 +522,9 @@ struct Pipeline {
   const rt_session::Regions* regions = nullptr;   // rt_run_regions: the boxes are the caller's, in original-page coordinates
   std::vector<pp::DbBox> region_boxes;            // ... as the stages read them (score 1)
   bool crop_original = false;                     // crops are planned on PageState::raw (regions, or crop_source = Original)
-  std::vector<double*> sum_parts; std::vector<int> sum_counts;   // det map checksum partials per det group (device)
+  std::vector<double*> sum_parts; std::vector<int> sum_counts;   // det map checksum partials per det group or page map (device)
+  int det_tile = 0, det_overlap = 0;        // det tiles (det_tiles.h) of this call; 0 = off
+  float* tile_maps_out = nullptr;           // rt_debug_det_tiles: host, every tile's own map packed in plan order (one-page call)
   int* d_counts = nullptr;                  // [n_pages][2]: box count, overflow flag
   pp::DbBox* d_boxes_packed = nullptr;      // every page's boxes, packed in page order
   int NL = 0, NLp = 1;                      // lines of the call; NLp = max(NL, 1) sizes the per-line buffers
@@ -579,6 +581,17 @@ const uint8_t* page_on_device(rt_session& s, const Pipeline& P, const uint8_t* c
 }
 // ---- a2 + a3: size limits, det resize (the normalise is folded into the det stem) ----
 void page_sizes(rt_session& s, Pipeline& P, const uint8_t* const* rgb, const int* hs, const int* ws) {
+  // a det input beyond what DB post-processing indexes (det_tiles.h "The largest det input") is refused before anything is queued
+  for (int i = 0; i < P.n_pages; i++) {
+    if (hs[i] <= 0 || ws[i] <= 0) continue;   // (an empty page: page_on_device reports it)
+    int plan[4], ah = hs[i], aw = ws[i], dh = 0, dw = 0;
+    const int n = gm::resize_both_plan(hs[i], ws[i], s.cfg.max_side_len, s.cfg.min_side_len, plan);
+    if (n > 0) { ah = plan[2 * (n - 1)]; aw = plan[2 * (n - 1) + 1]; }
+    if (ah <= 0 || aw <= 0) continue;
+    gm::resize_either_dims(ah, aw, s.cfg.det_limit_type, s.cfg.det_limit_side_len, &dh, &dw);
+    std::string why;
+    if (dh > 0 && dw > 0 && dt::check_page(dh, dw, &why) == dt::ERR_CAPACITY) throw RtError(RT_ERR_CAPACITY, "page " + std::to_string(i) + ": " + why);
+  }
   for (int i = 0; i < P.n_pages; i++) {
     PageState& p = P.pg[i];
     p.ori_h = hs[i]; p.ori_w = ws[i];
@@ -597,38 +610,125 @@ void page_sizes(rt_session& s, Pipeline& P, const uint8_t* const* rgb, const int
   }
 }
 // ---- a4: det network in launch groups ----------------------------------------------
+// The items of the launch groups are UNITS: an untiled page, or one tile of a tiled page (det tiles, det_tiles.h: a page whose det
+// input is larger than the call's tile either way).  The units of all pages are mixed under the one pixel budget and the one
+// det_sub_batch rule.  A tiled page's map is an arena allocation of det_h * det_w floats; a group's tiles are cut out of their
+// pages (k_det_tile_cut) into the contiguous RGB8 form run_u8 reads, and after the group's network run their owned rectangles are
+// written into the page maps (k_det_tile_stitch), before the next group rewinds the scratch arena.  Without a tiled page in the
+// call every group is what it was before tiles existed: the same launches, the same bits.
+struct DetUnit { int page, ty, tx, h, w; };   // ty < 0: the whole page
 void det_groups(rt_session& s, Pipeline& P) {
   const long long group_px = (long long)32 * 960 * 960;  // measured: larger launch groups win (launch-bound small layers)
-  for (int g0 = 0; g0 < P.n_pages;) {
-    const int g1 = group_end(g0, P.n_pages, s.cfg.det_sub_batch, group_px,
-                             [&](int i) { return (long long)P.pg[i].det_h * P.pg[i].det_w; });
+  const int T = P.det_tile, O = P.det_overlap;
+  std::vector<DetUnit> units;
+  std::vector<dt::Axis> rows((size_t)P.n_pages), cols((size_t)P.n_pages);
+  std::vector<float*> page_map((size_t)P.n_pages, nullptr);
+  for (int i = 0; i < P.n_pages; i++) {
+    const PageState& p = P.pg[i];
+    if (!dt::page_tiled(p.det_h, p.det_w, T)) { units.push_back(DetUnit{i, -1, -1, p.det_h, p.det_w}); continue; }
+    rows[(size_t)i] = dt::axis_plan(p.det_h, T, O); cols[(size_t)i] = dt::axis_plan(p.det_w, T, O);
+    P.pg[i].map = page_map[(size_t)i] = s.arena.alloc<float>((size_t)p.det_h * p.det_w);
+    for (int ty = 0; ty < rows[(size_t)i].n(); ty++)
+      for (int tx = 0; tx < cols[(size_t)i].n(); tx++) units.push_back(DetUnit{i, ty, tx, rows[(size_t)i].len, cols[(size_t)i].len});
+  }
+  const int nu = (int)units.size();
+  for (int g0 = 0; g0 < nu;) {
+    const int g1 = group_end(g0, nu, s.cfg.det_sub_batch, group_px, [&](int i) { return (long long)units[(size_t)i].h * units[(size_t)i].w; });
     const int gn = g1 - g0;
     std::vector<std::pair<int, int>> hw;
-    for (int i = g0; i < g1; i++) hw.push_back({P.pg[i].det_h, P.pg[i].det_w});
+    int nt = 0;
+    for (int i = g0; i < g1; i++) { hw.push_back({units[(size_t)i].h, units[(size_t)i].w}); nt += units[(size_t)i].ty >= 0; }
     Level L0 = make_level(hw);
     s.scratch.rewind();
     // the pages stay RGB8 until the first conv reads them (DetNet::run_u8)
     nn::U8Page* hd = s.pinned.alloc<nn::U8Page>((size_t)gn);
     nn::U8Page* dd = s.scratch.alloc<nn::U8Page>((size_t)gn);
-    for (int i = g0; i < g1; i++)
-      hd[i - g0] = nn::U8Page{P.pg[i].det_img, (long long)P.pg[i].det_h * P.pg[i].det_w, L0.h[i - g0].off};
+    // the group's tiles: their descriptors through pinned into scratch, as the crop refs go, and the buffer they are cut into
+    dt::TileDesc* ht = nullptr; dt::TileDesc* d_tiles = nullptr;
+    long long max_tile_pix = 0;
+    if (nt > 0) {
+      ht = s.pinned.alloc<dt::TileDesc>((size_t)nt);
+      d_tiles = s.scratch.alloc<dt::TileDesc>((size_t)nt);
+      size_t cut_bytes = 0;
+      int k = 0;
+      for (int i = g0; i < g1; i++) {
+        const DetUnit& u = units[(size_t)i];
+        if (u.ty < 0) continue;
+        const dt::Axis& R = rows[(size_t)u.page]; const dt::Axis& C = cols[(size_t)u.page];
+        dt::TileDesc& t = ht[k++];
+        t.src = P.pg[u.page].det_img; t.page_map = page_map[(size_t)u.page]; t.page_w = P.pg[u.page].det_w;
+        t.cut_off = (long long)cut_bytes; t.map_off = L0.h[i - g0].off;
+        t.y0 = R.origin[(size_t)u.ty]; t.x0 = C.origin[(size_t)u.tx]; t.th = u.h; t.tw = u.w;
+        t.oy0 = R.own0(u.ty); t.oy1 = R.bound[(size_t)u.ty]; t.ox0 = C.own0(u.tx); t.ox1 = C.bound[(size_t)u.tx]; t.pad_ = 0;
+        cut_bytes += ((size_t)u.h * u.w * 3 + 255) & ~(size_t)255;
+        max_tile_pix = std::max(max_tile_pix, (long long)u.h * u.w);
+      }
+      uint8_t* cut = s.scratch.alloc<uint8_t>(cut_bytes);
+      k = 0;
+      for (int i = g0; i < g1; i++) {
+        const DetUnit& u = units[(size_t)i];
+        hd[i - g0] = u.ty < 0 ? nn::U8Page{P.pg[u.page].det_img, (long long)u.h * u.w, L0.h[i - g0].off}
+                              : nn::U8Page{cut + ht[k++].cut_off, (long long)u.h * u.w, L0.h[i - g0].off};
+      }
+      RT_HIP_CHECK(hipMemcpyAsync(d_tiles, ht, (size_t)nt * sizeof(dt::TileDesc), hipMemcpyHostToDevice, s.st));
+      ProfScope ps(&s.prof, s.st, "det_tile_cut");
+      pp::det_tile_cut(s.st, d_tiles, nt, max_tile_pix, cut);
+    } else {
+      for (int i = g0; i < g1; i++)
+        hd[i - g0] = nn::U8Page{P.pg[units[(size_t)i].page].det_img, (long long)units[(size_t)i].h * units[(size_t)i].w, L0.h[i - g0].off};
+    }
     RT_HIP_CHECK(hipMemcpyAsync(dd, hd, (size_t)gn * sizeof(nn::U8Page), hipMemcpyHostToDevice, s.st));
     RunCtx c = s.ctx(&s.scratch);
     float* map;
     { ProfOuter po(&s.prof, s.st, "net/det"); map = s.det->run_u8(c, dd, s.cfg.det_scale, s.cfg.det_mean, s.cfg.det_std, L0); }
-    // keep the maps beyond the next group's scratch rewind; the last group's map is consumed by the DB post-processing
-    // (same stream) before the classifier reuses the scratch arena, so it stays where the network left it
-    float* keep = map;
-    if (g1 < P.n_pages) {
-      keep = s.arena.alloc<float>((size_t)L0.total);
-      RT_HIP_CHECK(hipMemcpyAsync(keep, map, (size_t)L0.total * 4, hipMemcpyDeviceToDevice, s.st));
+    if (nt == 0) {
+      // keep the maps beyond the next group's scratch rewind; the last group's map is consumed by the DB post-processing
+      // (same stream) before the classifier reuses the scratch arena, so it stays where the network left it
+      float* keep = map;
+      if (g1 < nu) {
+        keep = s.arena.alloc<float>((size_t)L0.total);
+        RT_HIP_CHECK(hipMemcpyAsync(keep, map, (size_t)L0.total * 4, hipMemcpyDeviceToDevice, s.st));
+      }
+      for (int i = g0; i < g1; i++) P.pg[units[(size_t)i].page].map = keep + L0.h[i - g0].off;
+      int nb = pp::sum_blocks(L0.total);
+      double* parts = s.arena.alloc<double>(nb);
+      pp::sum_partial(s.st, keep, L0.total, parts);
+      P.sum_parts.push_back(parts); P.sum_counts.push_back(nb);
+    } else {
+      { ProfScope ps(&s.prof, s.st, "det_tile_stitch");
+        pp::det_tile_stitch(s.st, d_tiles, nt, max_tile_pix, map); }
+      for (int i = g0; i < g1; i++) {
+        const DetUnit& u = units[(size_t)i];
+        const long long px = (long long)u.h * u.w;
+        float* m = map + L0.h[i - g0].off;
+        if (u.ty >= 0) {   // (rt_debug_det_tiles: the tile's own map, at its place in plan order)
+          if (P.tile_maps_out)
+            RT_HIP_CHECK(hipMemcpyAsync(P.tile_maps_out + ((long long)u.ty * cols[(size_t)u.page].n() + u.tx) * px, m, (size_t)px * 4, hipMemcpyDeviceToHost, s.st));
+          continue;
+        }
+        // an untiled page of a group that holds tiles: its own copy (the last group's stays in scratch) and its own checksum
+        if (g1 < nu) {
+          float* keep = s.arena.alloc<float>((size_t)px);
+          RT_HIP_CHECK(hipMemcpyAsync(keep, m, (size_t)px * 4, hipMemcpyDeviceToDevice, s.st));
+          m = keep;
+        }
+        P.pg[u.page].map = m;
+        int nb = pp::sum_blocks(px);
+        double* parts = s.arena.alloc<double>(nb);
+        pp::sum_partial(s.st, m, px, parts);
+        P.sum_parts.push_back(parts); P.sum_counts.push_back(nb);
+      }
     }
-    for (int i = g0; i < g1; i++) P.pg[i].map = keep + L0.h[i - g0].off;
-    int nb = pp::sum_blocks(L0.total);
-    double* parts = s.arena.alloc<double>(nb);
-    pp::sum_partial(s.st, keep, L0.total, parts);
-    P.sum_parts.push_back(parts); P.sum_counts.push_back(nb);
     g0 = g1;
+  }
+  // the checksum is taken over the page maps: a tiled page's stitched map, never its tiles
+  for (int i = 0; i < P.n_pages; i++) {
+    if (!page_map[(size_t)i]) continue;
+    const long long px = (long long)P.pg[i].det_h * P.pg[i].det_w;
+    int nb = pp::sum_blocks(px);
+    double* parts = s.arena.alloc<double>(nb);
+    pp::sum_partial(s.st, page_map[(size_t)i], px, parts);
+    P.sum_parts.push_back(parts); P.sum_counts.push_back(nb);
   }
 }
 // ---- a5: DB post-processing of every page (on device; stream-ordered workspace reuse) ----
@@ -997,7 +1097,7 @@ std::string rt_format_f32_impl(float v) { return fnum(v); }
 
 rt_results* rt_session::run_pages(const uint8_t* const* rgb, const int* hs, const int* ws, int n_pages, int mem,
                                   const float* const* det_map_override, const Regions* regions, int rec_charset_default,
-                                  int rec_lexicon_default, int rec_pattern_default) {
+                                  int rec_lexicon_default, int rec_pattern_default, int det_tile_, int det_overlap_) {
   if (g_trace) fprintf(stderr, "[rt host] %-28s %8.3f ms\n", "between calls", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - last_exit).count());
   HostTick tick0;
   // a one-page call is the reference's real mode (retto-cli/src/main.rs:80-86): it polls through its waits; a multi-page batch
@@ -1013,6 +1113,7 @@ rt_results* rt_session::run_pages(const uint8_t* const* rgb, const int* hs, cons
   if (n_pages == 0) return res.release();
   Pipeline P{n_pages, mem, det_map_override, std::vector<PageState>((size_t)n_pages)};
   P.regions = regions; P.crop_original = regions != nullptr || cfg.crop_source == 1;
+  P.det_tile = det_tile_; P.det_overlap = det_overlap_;
   HostTick tick;
   if (regions) {   // the boxes are given: no resize_both, no detector, no DB post-processing, no first round trip
     region_pages(*this, P, rgb, hs, ws); tick.lap("pre (upload, regions)");
@@ -1043,6 +1144,27 @@ rt_results* rt_session::run_pages(const uint8_t* const* rgb, const int* hs, cons
   tick.lap("results");
   if (g_trace) last_exit = std::chrono::steady_clock::now();
   return res.release();
+}
+
+// rt_debug_det_tiles: the det stage of a one-page call whose det image is the caller's -- det_groups itself, under the session's
+// det tiles and det_sub_batch, so the launch groups are the pipeline's.  A page that is not tiled has one tile, its whole map.
+void rt_session::debug_det_tiles(const uint8_t* rgb_det, int h, int w, float* tile_maps_out, float* page_map_out) {
+  std::string why;
+  const int rc = dt::check_page(h, w, &why);
+  if (rc != dt::OK) throw RtError(rc, "rt_debug_det_tiles: " + why);
+  begin_call();
+  uint8_t* d = arena.alloc<uint8_t>((size_t)h * w * 3);
+  RT_HIP_CHECK(hipMemcpyAsync(d, rgb_det, (size_t)h * w * 3, hipMemcpyHostToDevice, st));
+  Pipeline P{1, RT_MEM_DEVICE, nullptr, std::vector<PageState>(1)};
+  PageState& p = P.pg[0];
+  p.ori_h = p.after_h = p.det_h = h; p.ori_w = p.after_w = p.det_w = w;
+  p.raw = p.img = p.det_img = d; p.map = nullptr;
+  P.det_tile = det_tile; P.det_overlap = det_overlap; P.tile_maps_out = tile_maps_out;
+  det_groups(*this, P);
+  RT_HIP_CHECK(hipMemcpyAsync(page_map_out, p.map, (size_t)h * w * 4, hipMemcpyDeviceToHost, st));
+  if (tile_maps_out && !dt::page_tiled(h, w, det_tile))
+    RT_HIP_CHECK(hipMemcpyAsync(tile_maps_out, p.map, (size_t)h * w * 4, hipMemcpyDeviceToHost, st));
+  sync();
 }
 
 // Splits the pages over the lanes (contiguous ranges, order preserved) and runs the lanes on
@@ -1282,6 +1404,7 @@ rt_ticket* rt_session::submit_batch(const uint8_t* const* rgb, const int* hs, co
   t->rec_lexicon = rec_lexicon;
   if (regions && regions->patterns) t->region_patterns.assign(regions->patterns, regions->patterns + n_pages);
   t->rec_pattern = rec_pattern;
+  t->det_tile = det_tile; t->det_overlap = det_overlap;
   t->parts.assign((size_t)nl, nullptr); t->errs.resize((size_t)nl); t->first.assign((size_t)nl + 1, 0);
   {
     // contiguous ranges of about equal work: det pixels after the session size limit (a2) plus a constant per page
@@ -1336,7 +1459,8 @@ rt_ticket* rt_session::submit_batch(const uint8_t* const* rgb, const int* hs, co
                                                   tp->region_lexicons.empty() ? nullptr : tp->region_lexicons.data() + f0,
                                                   tp->region_patterns.empty() ? nullptr : tp->region_patterns.data() + f0};
         tp->parts[l] = s->run_pages(tp->rgb.data() + f0, tp->hs.data() + f0, tp->ws.data() + f0, f1 - f0, tp->mem_lane,
-                                    tp->maps.empty() ? nullptr : tp->maps.data() + f0, tp->quads.empty() ? nullptr : &rg, tp->rec_charset, tp->rec_lexicon, tp->rec_pattern);
+                                    tp->maps.empty() ? nullptr : tp->maps.data() + f0, tp->quads.empty() ? nullptr : &rg, tp->rec_charset, tp->rec_lexicon, tp->rec_pattern,
+                                    tp->det_tile, tp->det_overlap);
       } catch (...) {
         tp->errs[l] = std::current_exception();
         s->failed = true;
@@ -1405,7 +1529,7 @@ rt_results* rt_session::run_batch(const uint8_t* const* rgb, const int* hs, cons
                                         std::to_string(rec_lexicon) + "): a line may not carry both");
     stage_cb = cb; stage_user = user; stage_mu = &cb_mu; page_base = 0;
     try {
-      return run_pages(rgb, hs, ws, n_pages, mem, det_map_override, nullptr, rec_charset, rec_lexicon, rec_pattern);
+      return run_pages(rgb, hs, ws, n_pages, mem, det_map_override, nullptr, rec_charset, rec_lexicon, rec_pattern, det_tile, det_overlap);
     } catch (...) { failed = true; throw; }
   }
   return wait_batch(submit_batch(rgb, hs, ws, n_pages, mem, det_map_override, cb, user));

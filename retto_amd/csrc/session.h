@@ -90,6 +90,7 @@ struct rt_ticket {
   std::vector<const int*> region_lexicons;
   int rec_pattern = 0;
   std::vector<const int*> region_patterns;
+  int det_tile = 0, det_overlap = 0;   // det tiles (det_tiles.h): the session's setting as it was when the batch was submitted
   std::vector<int> first;
   std::vector<rt_results*> parts;
   std::vector<std::exception_ptr> errs;
@@ -196,6 +197,9 @@ struct rt_session {
   int rec_lexicon = 0;            // rt_set_rec_lexicon: likewise
   std::shared_ptr<rt_patterns> patterns;   // rec patterns (shared with the helper lanes)
   int rec_pattern = 0;            // rt_set_rec_pattern: likewise
+  // rt_set_det_tiles (det_tiles.h): pages whose det input is larger than det_tile either way are detected in tiles; 0 = off.  A
+  // helper lane never reads its own copy: a batch carries the main lane's value (rt_ticket::det_tile) into run_pages
+  int det_tile = 0, det_overlap = 0;
   uint8_t* d_word_raw = nullptr;  // rec_return_word_box: wb::raw_class of every dictionary entry (device; owned by the main lane)
   std::string last_error;
   int* d_flags = nullptr;         // [0] thumbnail/resize error flag
@@ -313,7 +317,11 @@ struct rt_session {
                         const float* const* det_map_override, rt_stage_callback cb = nullptr, void* user = nullptr);
   rt_results* run_pages(const uint8_t* const* rgb, const int* hs, const int* ws, int n_pages, int mem,
                         const float* const* det_map_override, const Regions* regions = nullptr,
-                        int rec_charset_default = 0, int rec_lexicon_default = 0, int rec_pattern_default = 0);  // one lane
+                        int rec_charset_default = 0, int rec_lexicon_default = 0, int rec_pattern_default = 0,
+                        int det_tile_ = 0, int det_overlap_ = 0);  // one lane
+  // rt_debug_det_tiles: the det stage of a one-page call on a host RGB8 image at det-input size h x w, through the pipeline's own
+  // det_groups under the session's det tiles; tile_maps_out: every tile's own map packed in plan order, page_map_out [h * w]
+  void debug_det_tiles(const uint8_t* rgb_det, int h, int w, float* tile_maps_out, float* page_map_out);
   // rt_run_regions: checks and clamps every quad (RT_ERR_INVALID naming page and region; nothing is queued then), then the
   // pages go over the lanes as run_batch's do, from the crop plan on
   // charsets (or null; entries may be null): per region -1 = the session default, 0 = none, >= 1 = that charset
