@@ -301,20 +301,45 @@ int rt_run_batch_stream(rt_session* s, const uint8_t* const* rgb, const int* hs,
   *out = nullptr;
   return guarded(s, [&] { *out = s->run_batch(rgb, hs, ws, n_pages, mem, det_map_override, cb, user); });
 }
+// the four rt_run_regions* forms: `name` is the entry's own, an array it does not take is null
+static int run_regions(const char* name, rt_session* s, const uint8_t* const* rgb, const int* hs, const int* ws, int n_pages, int mem,
+                       const float* const* quads, const int* n_quads, const int32_t* const* charsets, const int32_t* const* lexicons,
+                       const int32_t* const* patterns, rt_results** out) {
+  RT_REQUIRE(s && out && n_pages >= 0 && (n_pages == 0 || (rgb && hs && ws && quads && n_quads)), s, std::string(name) + ": bad argument");
+  RT_REQUIRE(mem == RT_MEM_HOST || mem == RT_MEM_DEVICE, s, std::string(name) + ": mem must be RT_MEM_HOST or RT_MEM_DEVICE");
+  *out = nullptr;
+  return guarded(s, [&] { *out = s->run_regions(rgb, hs, ws, n_pages, mem, quads, n_quads, charsets, lexicons, patterns); });
+}
 int rt_run_regions(rt_session* s, const uint8_t* const* rgb, const int* hs, const int* ws, int n_pages, int mem,
                    const float* const* quads, const int* n_quads, rt_results** out) {
-  RT_REQUIRE(s && out && n_pages >= 0 && (n_pages == 0 || (rgb && hs && ws && quads && n_quads)), s, "rt_run_regions: bad argument");
-  RT_REQUIRE(mem == RT_MEM_HOST || mem == RT_MEM_DEVICE, s, "rt_run_regions: mem must be RT_MEM_HOST or RT_MEM_DEVICE");
-  *out = nullptr;
-  return guarded(s, [&] { *out = s->run_regions(rgb, hs, ws, n_pages, mem, quads, n_quads); });
+  return run_regions("rt_run_regions", s, rgb, hs, ws, n_pages, mem, quads, n_quads, nullptr, nullptr, nullptr, out);
 }
 int rt_run_regions_charsets(rt_session* s, const uint8_t* const* rgb, const int* hs, const int* ws, int n_pages, int mem,
                             const float* const* quads, const int* n_quads, const int32_t* const* charsets, rt_results** out) {
-  RT_REQUIRE(s && out && n_pages >= 0 && (n_pages == 0 || (rgb && hs && ws && quads && n_quads)), s, "rt_run_regions_charsets: bad argument");
-  RT_REQUIRE(mem == RT_MEM_HOST || mem == RT_MEM_DEVICE, s, "rt_run_regions_charsets: mem must be RT_MEM_HOST or RT_MEM_DEVICE");
-  *out = nullptr;
-  return guarded(s, [&] { *out = s->run_regions(rgb, hs, ws, n_pages, mem, quads, n_quads, charsets); });
+  return run_regions("rt_run_regions_charsets", s, rgb, hs, ws, n_pages, mem, quads, n_quads, charsets, nullptr, nullptr, out);
 }
+int rt_run_regions_lexicons(rt_session* s, const uint8_t* const* rgb, const int* hs, const int* ws, int n_pages, int mem,
+                            const float* const* quads, const int* n_quads, const int32_t* const* charsets,
+                            const int32_t* const* lexicons, rt_results** out) {
+  return run_regions("rt_run_regions_lexicons", s, rgb, hs, ws, n_pages, mem, quads, n_quads, charsets, lexicons, nullptr, out);
+}
+int rt_run_regions_patterns(rt_session* s, const uint8_t* const* rgb, const int* hs, const int* ws, int n_pages, int mem,
+                            const float* const* quads, const int* n_quads, const int32_t* const* charsets,
+                            const int32_t* const* lexicons, const int32_t* const* patterns, rt_results** out) {
+  return run_regions("rt_run_regions_patterns", s, rgb, hs, ws, n_pages, mem, quads, n_quads, charsets, lexicons, patterns, out);
+}
+// rt_set_rec_charset / _lexicon / _pattern: the session default of one kind (rec_line_opts.h)
+static int set_rec_default(rt_session* s, const RecKind& kind, int id) {
+  const std::string name = std::string("rt_set_rec_") + kind.noun;
+  RT_REQUIRE(s, s, name + ": null session");
+  return guarded(s, [&] {
+    if (id < 0 || id > s->rec_counts().*kind.id) throw RtError(RT_ERR_INVALID, name + ": unknown " + kind.noun + " id " + std::to_string(id));
+    s->rec_default.*kind.id = id;
+  });
+}
+int rt_set_rec_charset(rt_session* s, int charset) { return set_rec_default(s, REC_KINDS[0], charset); }
+int rt_set_rec_lexicon(rt_session* s, int lexicon) { return set_rec_default(s, REC_KINDS[1], lexicon); }
+int rt_set_rec_pattern(rt_session* s, int pattern) { return set_rec_default(s, REC_KINDS[2], pattern); }
 int rt_charset_create(rt_session* s, const char* utf8, size_t len, const int32_t* ids, int n_ids, int* charset_out) {
   RT_REQUIRE(s && charset_out && (utf8 || !len) && n_ids >= 0 && (ids || !n_ids), s, "rt_charset_create: bad argument");
   *charset_out = 0;
@@ -325,22 +350,6 @@ int rt_charset_classes(const rt_session* s, int charset, const int32_t** ids) {
   const std::vector<int32_t>& v = s->charsets->ids[(size_t)charset - 1];
   if (ids) *ids = v.data();
   return (int)v.size();
-}
-int rt_set_rec_charset(rt_session* s, int charset) {
-  RT_REQUIRE(s, s, "rt_set_rec_charset: null session");
-  return guarded(s, [&] {
-    if (charset < 0 || charset > (int)s->charsets->ids.size())
-      throw RtError(RT_ERR_INVALID, "rt_set_rec_charset: unknown charset id " + std::to_string(charset));
-    s->rec_charset = charset;
-  });
-}
-int rt_run_regions_lexicons(rt_session* s, const uint8_t* const* rgb, const int* hs, const int* ws, int n_pages, int mem,
-                            const float* const* quads, const int* n_quads, const int32_t* const* charsets,
-                            const int32_t* const* lexicons, rt_results** out) {
-  RT_REQUIRE(s && out && n_pages >= 0 && (n_pages == 0 || (rgb && hs && ws && quads && n_quads)), s, "rt_run_regions_lexicons: bad argument");
-  RT_REQUIRE(mem == RT_MEM_HOST || mem == RT_MEM_DEVICE, s, "rt_run_regions_lexicons: mem must be RT_MEM_HOST or RT_MEM_DEVICE");
-  *out = nullptr;
-  return guarded(s, [&] { *out = s->run_regions(rgb, hs, ws, n_pages, mem, quads, n_quads, charsets, lexicons); });
 }
 int rt_lexicon_create(rt_session* s, const char* utf8, size_t len, const int32_t* ids, const int32_t* entry_lens, int n_id_entries,
                       int* lexicon_out) {
@@ -388,22 +397,6 @@ const char* rt_pattern_text(const rt_session* s, int pattern) {
   const rt_patterns::Host* h = pattern_of(s, pattern);
   return h ? h->text.c_str() : nullptr;
 }
-int rt_set_rec_pattern(rt_session* s, int pattern) {
-  RT_REQUIRE(s, s, "rt_set_rec_pattern: null session");
-  return guarded(s, [&] {
-    if (pattern < 0 || pattern > (int)s->patterns->host.size())
-      throw RtError(RT_ERR_INVALID, "rt_set_rec_pattern: unknown pattern id " + std::to_string(pattern));
-    s->rec_pattern = pattern;
-  });
-}
-int rt_run_regions_patterns(rt_session* s, const uint8_t* const* rgb, const int* hs, const int* ws, int n_pages, int mem,
-                            const float* const* quads, const int* n_quads, const int32_t* const* charsets,
-                            const int32_t* const* lexicons, const int32_t* const* patterns, rt_results** out) {
-  RT_REQUIRE(s && out && n_pages >= 0 && (n_pages == 0 || (rgb && hs && ws && quads && n_quads)), s, "rt_run_regions_patterns: bad argument");
-  RT_REQUIRE(mem == RT_MEM_HOST || mem == RT_MEM_DEVICE, s, "rt_run_regions_patterns: mem must be RT_MEM_HOST or RT_MEM_DEVICE");
-  *out = nullptr;
-  return guarded(s, [&] { *out = s->run_regions(rgb, hs, ws, n_pages, mem, quads, n_quads, charsets, lexicons, patterns); });
-}
 int rt_results_rec_pattern(const rt_results* r, int page, int line, rt_pattern_result* out) {
   const rt_results::Page* p = r && page >= 0 && (size_t)page < r->pages.size() ? &r->pages[(size_t)page] : nullptr;
   if (!p || line < 0 || (size_t)line >= p->pat_id.size() || p->pat_id[(size_t)line] <= 0) return 0;
@@ -416,8 +409,7 @@ int rt_set_det_tiles(rt_session* s, int tile, int overlap) {
   RT_REQUIRE(s, s, "rt_set_det_tiles: null session");
   return guarded(s, [&] {
     if (const char* why = dt::check_params(tile, overlap)) throw RtError(RT_ERR_INVALID, std::string("rt_set_det_tiles: ") + why);
-    s->det_tile = tile; s->det_overlap = overlap;
-    for (auto& h : s->helpers) { h->det_tile = tile; h->det_overlap = overlap; }
+    s->det_tile = tile; s->det_overlap = overlap;   // (the helper lanes get it with every call: CallSettings)
   });
 }
 int rt_det_tiles(const rt_session* s, int* tile, int* overlap) {
@@ -443,14 +435,6 @@ int rt_det_tile_plan(int h, int w, int tile, int overlap, int32_t* row_origin, i
     if ((col_origin || col_bound) && col_cap < C.n()) throw RtError(RT_ERR_INVALID, "rt_det_tile_plan: col_cap is smaller than the " + std::to_string(C.n()) + " tile columns");
     for (int i = 0; i < R.n(); i++) { if (row_origin) row_origin[i] = R.origin[(size_t)i]; if (row_bound) row_bound[i] = R.bound[(size_t)i]; }
     for (int i = 0; i < C.n(); i++) { if (col_origin) col_origin[i] = C.origin[(size_t)i]; if (col_bound) col_bound[i] = C.bound[(size_t)i]; }
-  });
-}
-int rt_set_rec_lexicon(rt_session* s, int lexicon) {
-  RT_REQUIRE(s, s, "rt_set_rec_lexicon: null session");
-  return guarded(s, [&] {
-    if (lexicon < 0 || lexicon > (int)s->lexicons->host.size())
-      throw RtError(RT_ERR_INVALID, "rt_set_rec_lexicon: unknown lexicon id " + std::to_string(lexicon));
-    s->rec_lexicon = lexicon;
   });
 }
 int rt_lexicon_set_snap(rt_session* s, int lexicon, float min_posterior) {

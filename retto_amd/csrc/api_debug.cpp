@@ -481,10 +481,8 @@ static void debug_ctc_lexicon(rt_session* s, const float* z5, const float* W, co
     else if (lex_min_post) snapped_out[i] = 0;
   }
   rt_session::RecTail& t = h.t;
-  t.d_ids = h.bufs.upload(tb.ids.data(), tb.ids.size());
-  t.d_entries = h.bufs.upload(tb.entries.data(), tb.entries.size());
-  t.d_order = h.bufs.upload(tb.order.data(), tb.order.size());
-  t.d_lex = h.bufs.upload(tb.lex.data(), tb.lex.size());
+  t.d_lex = lx::DevTables{h.bufs.upload(tb.ids.data(), tb.ids.size()), h.bufs.upload(tb.entries.data(), tb.entries.size()),
+                          h.bufs.upload(tb.order.data(), tb.order.size()), h.bufs.upload(tb.lex.data(), tb.lex.size())};
   // (what the kernels write starts as the caller's values: a slot they leave alone comes back untouched)
   t.loglik = h.bufs.alloc<float>((size_t)h.plan.table);
   if (loglik_out) DevBufs::put(t.loglik, loglik_out, (size_t)h.plan.table);

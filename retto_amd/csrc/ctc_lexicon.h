@@ -105,6 +105,8 @@ struct Tables {
     lex.push_back(x);
   }
 };
+// the four tables on the device (pt::DevTables' counterpart)
+struct DevTables { const int32_t* ids; const Entry* entries; const int32_t* order; const Lex* lex; };
 
 // Host reference, plain fp32 loops: lse of one row of logits [N]
 inline float row_lse(const float* logits, int N) {

@@ -1,0 +1,80 @@
+// The per-line options of the rec network's CTC tail -- a rec charset, a rec lexicon, a rec pattern -- as ONE value, and the host
+// rules every road to the tail shares: which ids exist, "-1 means the session default", "a line may not carry both a pattern and
+// a lexicon", and how a call's regions or defaults become one entry per line.  A new option is a member of RecLineOpts and a row of
+// REC_KINDS.  Plain C++ as rec_tail_plan.h and det_tiles.h: no HIP, no RtError (a function returns its message, empty = fine, and
+// session.cpp / api.cpp wrap it in RT_ERR_INVALID); built and checked without a GPU (tests/test_rec_line_opts_cpu.py).
+#pragma once
+#include <algorithm>
+#include <string>
+#include <vector>
+
+namespace rt {
+
+// ids are 1-based (rt_charset_create / rt_lexicon_create / rt_pattern_create), 0: none.  Also used as the number of ids of each
+// kind a session holds (the largest valid id).
+struct RecLineOpts { int charset = 0, lexicon = 0, pattern = 0; };
+// per kind: some line of the call has one
+struct RecLineAny { bool charset = false, lexicon = false, pattern = false; };
+// the three kinds, in the order every check walks them
+struct RecKind { const char* noun; int RecLineOpts::*id; bool RecLineAny::*any; };
+constexpr RecKind REC_KINDS[3] = {{"charset", &RecLineOpts::charset, &RecLineAny::charset},
+                                  {"lexicon", &RecLineOpts::lexicon, &RecLineAny::lexicon},
+                                  {"pattern", &RecLineOpts::pattern, &RecLineAny::pattern}};
+
+// The pattern's Viterbi and the lexicon's snap would both rewrite the line's rows, so a line carries at most one of the two.
+inline bool carries_both(const RecLineOpts& o) { return o.pattern > 0 && o.lexicon > 0; }
+// ... in words: `where` names a region ("page 0 region 2"), empty: o is the session's defaults
+inline std::string rec_opts_conflict(const RecLineOpts& o, const std::string& where = std::string()) {
+  if (!carries_both(o)) return std::string();
+  return (where.empty() ? "the session defaults name both" : where + ": both") + " a rec pattern (" + std::to_string(o.pattern) +
+         ") and a rec lexicon (" + std::to_string(o.lexicon) + "): a line may not carry both";
+}
+
+// rt_run_regions*, pages [p0, p1) of a call: region k of page i gets ids[j][i][k] of kind REC_KINDS[j] (-1: the default `dflt`,
+// 0: none, up to counts: that id; ids[j] or ids[j][i] null: -1 throughout) -> out[i][k]; out has an entry per page of the call.
+// Returns the first error in words ("page 1 region 2: unknown charset id 99"): pages in order, inside a page the charsets of
+// all regions, then the lexicons, then the patterns, a region's conflict with its pattern.  (A range, so that run_regions can
+// report a page's options behind the checks of its quads and before the next page's.)
+inline std::string resolve_region_opts(int p0, int p1, const int* n_quads, const int* const* const ids[3], const RecLineOpts& dflt,
+                                       const RecLineOpts& counts, std::vector<std::vector<RecLineOpts>>& out) {
+  for (int i = p0; i < p1; i++) {
+    out[(size_t)i].assign((size_t)n_quads[i], dflt);
+    for (int j = 0; j < 3; j++) {
+      const RecKind& kind = REC_KINDS[j];
+      for (int k = 0; k < n_quads[i]; k++) {
+        RecLineOpts& o = out[(size_t)i][(size_t)k];
+        const std::string where = "page " + std::to_string(i) + " region " + std::to_string(k);
+        const int v = ids[j] && ids[j][i] ? ids[j][i][k] : -1;
+        if (v < -1 || v > counts.*kind.id) return where + ": unknown " + kind.noun + " id " + std::to_string(v);
+        if (v >= 0) o.*kind.id = v;
+        if (j == 2 && carries_both(o)) return rec_opts_conflict(o, where);   // (every id of the region is resolved now)
+      }
+    }
+  }
+  return std::string();
+}
+
+// One entry per line of a call: line k of page i is line pages[i].first_line + k of the NL lines (the rec plan reorders widths,
+// never lines) and gets page_opts[i][k], the regions' resolved options; page_opts null: every line gets `dflt`.  Page needs
+// first_line and n_boxes.  any: per kind whether some line has one -- what decides whether the kind's buffers and results exist.
+// Returns the first id outside [0, counts] or the first line that carries both a pattern and a lexicon, in words (the entry
+// points refuse both before anything is queued).
+template <class Page>
+std::string expand_line_opts(const Page* pages, int n_pages, int NL, const RecLineOpts* const* page_opts, const RecLineOpts& dflt,
+                             const RecLineOpts& counts, std::vector<RecLineOpts>& lines, RecLineAny& any) {
+  lines.assign((size_t)NL, page_opts ? RecLineOpts() : dflt);
+  for (int i = 0; i < n_pages && page_opts; i++)
+    std::copy(page_opts[i], page_opts[i] + pages[i].n_boxes, lines.begin() + pages[i].first_line);
+  any = RecLineAny();
+  for (const RecKind& kind : REC_KINDS)
+    for (const RecLineOpts& o : lines) {
+      const int v = o.*kind.id;
+      if (v < 0 || v > counts.*kind.id) return std::string("unknown rec ") + kind.noun + " id " + std::to_string(v);
+      any.*kind.any = any.*kind.any || v > 0;
+    }
+  for (size_t li = 0; li < lines.size(); li++)
+    if (carries_both(lines[li])) return "line " + std::to_string(li) + " carries both a rec pattern and a rec lexicon";
+  return std::string();
+}
+
+}  // namespace rt

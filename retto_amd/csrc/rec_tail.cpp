@@ -199,6 +199,30 @@ struct LogitsChunk {
     core.logits_rows(c, zc, m, logits);
   }
 };
+// one table of a store (rt_lexicons, rt_patterns) into a device allocation of its own, with a blocking copy (an empty one gets one
+// element and no copy); the store's holder frees it
+template <typename T>
+void upload_table(const T** d, const std::vector<T>& v) {
+  RT_HIP_CHECK(hipMalloc((void**)d, std::max<size_t>(v.size(), 1) * sizeof(T)));
+  if (!v.empty()) RT_HIP_CHECK(hipMemcpy(const_cast<T*>(*d), v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
+}
+// Chunks of whole lines (lx::Line or pt::Line), so that a line's T rows are resident together: a chunk takes lines while their
+// rows fit t.chunk_rows (0: cc::CAND_CHUNK) and they are at most lx::LINES_PER_CHUNK, and always its first line.  f(i0, i1, r0, m)
+// per chunk: lines [i0, i1), whose rows are [r0, r0 + m) of the plan's compact row list.  Returns the largest m, at least 1.
+template <typename Line, typename F>
+int line_chunks(const std::vector<Line>& lines, const rt_session::RecTail& t, F f) {
+  const int n = (int)lines.size(), chunk = t.chunk_rows > 0 ? t.chunk_rows : cc::CAND_CHUNK;
+  int cap = 1;
+  for (int i0 = 0, i1; i0 < n; i0 = i1) {
+    int rows = lines[i0].T;
+    for (i1 = i0 + 1; i1 < n && i1 - i0 < lx::LINES_PER_CHUNK && rows + lines[i1].T <= chunk; i1++) rows += lines[i1].T;
+    const int r0 = lines[i0].row0, m = lines[i1 - 1].row0 + lines[i1 - 1].T - r0;
+    f(i0, i1, r0, m);
+    cap = std::max(cap, m);
+  }
+  return cap;
+}
+const auto no_chunk_work = [](int, int, int, int) {};   // (a pass of line_chunks for its result alone)
 }  // namespace
 
 void rt_session::rec_tail(const RecTailPlan& p, const SvtrCore& core, const RecTail& t) {
@@ -259,74 +283,47 @@ void rt_session::ctc_charset(const SvtrCore& core, const RecTail& t, const int* 
 }
 
 void rt_session::ctc_lexicon(const RecTailPlan& p, const SvtrCore& core, const RecTail& t) {
-  const lx::Line* h_lines = p.lines.data(); const int n_lines = (int)p.lines.size();
+  const int n_lines = (int)p.lines.size();
   if (n_lines <= 0) return;
   const lx::Line* d_lines = staged(*this, p.lines); const int* d_rows = staged(*this, p.lrows);
   float* loglik = t.loglik ? t.loglik : scratch.alloc<float>((size_t)p.table);
-  const int chunk = t.chunk_rows > 0 ? t.chunk_rows : cc::CAND_CHUNK;
-  // chunks of whole lines: [i0, i1) takes lines while their rows fit the chunk, and always its first line
-  auto chunk_end = [&](int i0) {
-    int i1 = i0 + 1, rows = h_lines[i0].T;
-    while (i1 < n_lines && i1 - i0 < lx::LINES_PER_CHUNK && rows + h_lines[i1].T <= chunk) rows += h_lines[i1++].T;
-    return i1;
-  };
-  int cap = 1;
-  for (int i0 = 0; i0 < n_lines;) {
-    const int i1 = chunk_end(i0);
-    cap = std::max(cap, h_lines[i1 - 1].row0 + h_lines[i1 - 1].T - h_lines[i0].row0);
-    i0 = i1;
-  }
+  const lx::DevTables& X = t.d_lex;
+  const int cap = line_chunks(p.lines, t, no_chunk_work);
   LogitsChunk lc(*this, core, t.z5, cap);
   float* lse = scratch.alloc<float>((size_t)cap);
   // (lexicon snap: the backpointers of a chunk's long lines, two 64-bit ballots per row)
   void* bp = p.snap ? scratch.alloc_bytes((size_t)cap * 16) : nullptr;
-  for (int i0 = 0; i0 < n_lines;) {   // (the chunks share lse too)
-    const int i1 = chunk_end(i0), r0 = h_lines[i0].row0, m = h_lines[i1 - 1].row0 + h_lines[i1 - 1].T - r0;
+  line_chunks(p.lines, t, [&](int i0, int i1, int r0, int m) {   // (the chunks share lse too)
     if (m > 0) {
       lc.run(d_rows + r0, m);
       ProfScope ps(&prof, st, "ctc_row_lse");
       pp::ctc_row_lse(st, lc.logits, lc.ld, core.classes, m, lse);
     }
     { ProfScope ps(&prof, st, "ctc_lexicon_forward");
-      pp::ctc_lexicon_forward(st, lc.logits, lc.ld, lse, d_lines + i0, i1 - i0, r0, p.max_waves, t.d_lex, t.d_entries, t.d_order, t.d_ids, loglik); }
+      pp::ctc_lexicon_forward(st, lc.logits, lc.ld, lse, d_lines + i0, i1 - i0, r0, p.max_waves, X.lex, X.entries, X.order, X.ids, loglik); }
     if (p.snap) {   // (a line never straddles chunks: its matches are complete, and its logits still resident, here)
       { ProfScope ps(&prof, st, "ctc_lexicon_topk");
-        pp::ctc_lexicon_topk(st, d_lines + i0, i1 - i0, t.d_lex, loglik, t.lexm, t.lexn); }
+        pp::ctc_lexicon_topk(st, d_lines + i0, i1 - i0, X.lex, loglik, t.lexm, t.lexn); }
       ProfScope ps(&prof, st, "ctc_lexicon_align");
-      pp::ctc_lexicon_align(st, lc.logits, lc.ld, lse, d_lines + i0, i1 - i0, r0, t.d_lex, t.d_entries, t.d_ids, t.d_min_post, t.lexm, t.lexn,
+      pp::ctc_lexicon_align(st, lc.logits, lc.ld, lse, d_lines + i0, i1 - i0, r0, X.lex, X.entries, X.ids, t.d_min_post, t.lexm, t.lexn,
                             d_rows, bp, t.idx, t.prob, t.lexs, t.vit);
     }
-    i0 = i1;
-  }
+  });
   if (!p.snap) {   // (without snap: one top-K over all the group's lines)
     ProfScope ps(&prof, st, "ctc_lexicon_topk");
-    pp::ctc_lexicon_topk(st, d_lines, n_lines, t.d_lex, loglik, t.lexm, t.lexn);
+    pp::ctc_lexicon_topk(st, d_lines, n_lines, X.lex, loglik, t.lexm, t.lexn);
   }
 }
 
 void rt_session::ctc_pattern(const RecTailPlan& p, const SvtrCore& core, const RecTail& t) {
-  const pt::Line* h_lines = p.plines.data(); const int n_lines = (int)p.plines.size();
-  if (n_lines <= 0) return;
+  if (p.plines.empty()) return;
   const pt::Line* d_lines = staged(*this, p.plines); const int* d_rows = staged(*this, p.prows);
-  const int chunk = t.chunk_rows > 0 ? t.chunk_rows : cc::CAND_CHUNK;
-  // chunks of whole lines, as ctc_lexicon's: a line's T rows are resident together
-  auto chunk_end = [&](int i0) {
-    int i1 = i0 + 1, rows = h_lines[i0].T;
-    while (i1 < n_lines && i1 - i0 < lx::LINES_PER_CHUNK && rows + h_lines[i1].T <= chunk) rows += h_lines[i1++].T;
-    return i1;
-  };
-  int cap = 1;
-  for (int i0 = 0; i0 < n_lines;) {
-    const int i1 = chunk_end(i0);
-    cap = std::max(cap, h_lines[i1 - 1].row0 + h_lines[i1 - 1].T - h_lines[i0].row0);
-    i0 = i1;
-  }
+  const int cap = line_chunks(p.plines, t, no_chunk_work);
   LogitsChunk lc(*this, core, t.z5, cap);
   float* lse = scratch.alloc<float>((size_t)cap); float* rmax = scratch.alloc<float>((size_t)cap);
   // (the backpointer codes of the group's long lines, 16 bits each; every line has its own part: pt::Line::bp)
   void* bp = scratch.alloc_bytes((size_t)std::max<long long>(p.bp_codes, 1) * sizeof(uint16_t));
-  for (int i0 = 0; i0 < n_lines;) {
-    const int i1 = chunk_end(i0), r0 = h_lines[i0].row0, m = h_lines[i1 - 1].row0 + h_lines[i1 - 1].T - r0;
+  line_chunks(p.plines, t, [&](int i0, int i1, int r0, int m) {
     if (m > 0) {
       lc.run(d_rows + r0, m);
       { ProfScope ps(&prof, st, "ctc_row_lse");
@@ -337,8 +334,7 @@ void rt_session::ctc_pattern(const RecTailPlan& p, const SvtrCore& core, const R
     ProfScope ps(&prof, st, "ctc_pattern_viterbi");
     pp::ctc_pattern_viterbi(st, lc.logits, lc.ld, core.classes, lse, rmax, d_lines + i0, i1 - i0, r0, t.d_pat, d_rows, bp, t.idx, t.prob,
                             t.patm, t.patv, t.patlp, t.patfree);
-    i0 = i1;
-  }
+  });
 }
 
 int rt_session::charset_create(const char* utf8, size_t len, const int32_t* ids, int n_ids) {
@@ -376,19 +372,10 @@ int rt_session::lexicon_create(const char* utf8, size_t len, const int32_t* ids,
   // the device tables are rebuilt whole (blocking copies; no lane has work queued: this is a guarded call and every pipeline
   // call ends with its streams drained)
   RT_HIP_CHECK(hipSetDevice(device));
-  int32_t* d_ids = nullptr; lx::Entry* d_entries = nullptr; int32_t* d_order = nullptr; lx::Lex* d_lex = nullptr;
-  auto up = [&](auto** d, const auto& v) {
-    RT_HIP_CHECK(hipMalloc((void**)d, v.size() * sizeof(v[0])));
-    RT_HIP_CHECK(hipMemcpy(*d, v.data(), v.size() * sizeof(v[0]), hipMemcpyHostToDevice));
-  };
-  try {
-    up(&d_ids, tb.ids); up(&d_entries, tb.entries); up(&d_order, tb.order); up(&d_lex, tb.lex);
-  } catch (...) {
-    if (d_ids) (void)hipFree(d_ids); if (d_entries) (void)hipFree(d_entries); if (d_order) (void)hipFree(d_order); if (d_lex) (void)hipFree(d_lex);
-    throw;
-  }
-  X.free_device();
-  X.d_ids = d_ids; X.d_entries = d_entries; X.d_order = d_order; X.d_lex = d_lex;
+  rt_lexicons fresh;   // (frees what it holds if a copy below throws)
+  upload_table(&fresh.d.ids, tb.ids); upload_table(&fresh.d.entries, tb.entries); upload_table(&fresh.d.order, tb.order);
+  upload_table(&fresh.d.lex, tb.lex);
+  std::swap(X.d, fresh.d);   // (the old tables leave with `fresh`)
   X.tb = std::move(tb);
   X.host.push_back(std::move(h));
   return (int)X.host.size();
@@ -411,12 +398,8 @@ int rt_session::pattern_create(const char* utf8, size_t len) {
   // call ends with its streams drained)
   RT_HIP_CHECK(hipSetDevice(device));
   rt_patterns fresh;   // (frees what it holds if a copy below throws)
-  auto up = [&](auto** d, const auto& v) {
-    RT_HIP_CHECK(hipMalloc((void**)d, std::max<size_t>(v.size(), 1) * sizeof(v[0])));
-    if (!v.empty()) RT_HIP_CHECK(hipMemcpy(const_cast<void*>((const void*)*d), v.data(), v.size() * sizeof(v[0]), hipMemcpyHostToDevice));
-  };
-  up(&fresh.d.pats, tb.pats); up(&fresh.d.pair_c, tb.pair_c); up(&fresh.d.pair_pb, tb.pair_pb); up(&fresh.d.pair_pe, tb.pair_pe);
-  up(&fresh.d.seg, tb.seg); up(&fresh.d.preds, tb.preds);
+  upload_table(&fresh.d.pats, tb.pats); upload_table(&fresh.d.pair_c, tb.pair_c); upload_table(&fresh.d.pair_pb, tb.pair_pb);
+  upload_table(&fresh.d.pair_pe, tb.pair_pe); upload_table(&fresh.d.seg, tb.seg); upload_table(&fresh.d.preds, tb.preds);
   std::swap(X.d, fresh.d);   // (the old tables leave with `fresh`)
   X.tb = std::move(tb);
   X.host.emplace_back(new rt_patterns::Host{std::string(utf8, len), c.S, c.P, c.min_steps});

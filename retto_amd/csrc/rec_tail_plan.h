@@ -8,6 +8,7 @@
 
 #include "ctc_lexicon.h"
 #include "ctc_pattern.h"
+#include "rec_line_opts.h"
 
 namespace rt {
 
@@ -36,40 +37,49 @@ struct RecTailPlan {
   bool needs_z5(int cand_k) const { return cand_k > 1 || !crows.empty() || has_lex() || has_pat(); }
 };
 
-// Lines [l0, l1) of a call: line li has the time steps [tok_off[li], tok_off[li + 1]), charset line_set[li] and lexicon
-// line_lex[li] (1-based, 0: none; either array may be null: no line has one), lexicon k is tb.lex[k - 1] and snaps where
-// snap_min[k - 1] > 0 (null: never); pattern line_pat[li] (the same convention; null: no line has one) is ptb->pats[k - 1].
-inline RecTailPlan rec_tail_plan(const long long* tok_off, int l0, int l1, const int* line_set, const int* line_lex,
-                                 const lx::Tables& tb, const float* snap_min, const int* line_pat = nullptr,
-                                 const pt::Tables* ptb = nullptr) {
+// The session's stores the plan reads: lexicon k is lex.lex[k - 1] and snaps where snap_min[k - 1] > 0 (null: never); pattern k is
+// pat->pats[k - 1] (null: no line has one)
+struct RecStores { const lx::Tables& lex; const float* snap_min; const pt::Tables* pat; };
+
+// Lines [l0, l1) of a call: line li has the time steps [tok_off[li], tok_off[li + 1]) and the options line_opts[li] (rec_line_opts.h)
+inline RecTailPlan rec_tail_plan(const long long* tok_off, int l0, int l1, const RecLineOpts* line_opts, const RecStores& st) {
   RecTailPlan p;
   const long long t0 = tok_off[l0];
   p.rows = tok_off[l1] - t0;
   bool restricted = false;
-  for (int li = l0; li < l1 && line_set && !restricted; li++) restricted = line_set[li] > 0 && tok_off[li + 1] > tok_off[li];
+  for (int li = l0; li < l1 && !restricted; li++) restricted = line_opts[li].charset > 0 && tok_off[li + 1] > tok_off[li];
   if (restricted) p.row_set.resize((size_t)p.rows);
   for (int li = l0; li < l1; li++) {
     const int r0 = (int)(tok_off[li] - t0), T = (int)(tok_off[li + 1] - tok_off[li]);
+    const RecLineOpts& o = line_opts[li];
     for (int t = 0; restricted && t < T; t++) {
-      p.row_set[(size_t)(r0 + t)] = line_set[li];
-      if (line_set[li] > 0) p.crows.push_back(r0 + t);
+      p.row_set[(size_t)(r0 + t)] = o.charset;
+      if (o.charset > 0) p.crows.push_back(r0 + t);
     }
-    if (line_pat && ptb && line_pat[li] > 0) {
-      const pt::Pat& a = ptb->pats[(size_t)line_pat[li] - 1];
-      p.plines.push_back(pt::Line{(int)p.prows.size(), T, line_pat[li] - 1, li, p.bp_codes});
+    if (st.pat && o.pattern > 0) {
+      const pt::Pat& a = st.pat->pats[(size_t)o.pattern - 1];
+      p.plines.push_back(pt::Line{(int)p.prows.size(), T, o.pattern - 1, li, p.bp_codes});
       for (int t = 0; t < T; t++) p.prows.push_back(r0 + t);
       p.max_P = std::max(p.max_P, a.P); p.max_S = std::max(p.max_S, a.S);
       if (pt::bp_codes(T, a.P, a.S) > pt::BP_LDS) p.bp_codes += pt::bp_codes(T, a.P, a.S);
     }
-    if (!line_lex || line_lex[li] <= 0) continue;
-    const lx::Lex& x = tb.lex[(size_t)line_lex[li] - 1];
-    p.lines.push_back(lx::Line{(int)p.lrows.size(), T, line_lex[li] - 1, li, p.table});
+    if (o.lexicon <= 0) continue;
+    const lx::Lex& x = st.lex.lex[(size_t)o.lexicon - 1];
+    p.lines.push_back(lx::Line{(int)p.lrows.size(), T, o.lexicon - 1, li, p.table});
     for (int t = 0; t < T; t++) p.lrows.push_back(r0 + t);
     p.table += x.n;
     p.max_waves = std::max(p.max_waves, lx::waves_of(x));
-    p.snap = p.snap || (snap_min && snap_min[line_lex[li] - 1] > 0.0f);
+    p.snap = p.snap || (st.snap_min && st.snap_min[o.lexicon - 1] > 0.0f);
   }
   return p;
+}
+// The same from one optional id array per kind (null: no line has one), as the rt_debug_ctc_* hooks' ABI and the plan tests'
+// drivers hold them: lexicon k is tb.lex[k - 1], snap_min and ptb as RecStores'
+inline RecTailPlan rec_tail_plan(const long long* tok_off, int l0, int l1, const int* line_set, const int* line_lex, const lx::Tables& tb,
+                                 const float* snap_min, const int* line_pat = nullptr, const pt::Tables* ptb = nullptr) {
+  std::vector<RecLineOpts> opts((size_t)l1);
+  for (int li = l0; li < l1; li++) opts[(size_t)li] = {line_set ? line_set[li] : 0, line_lex ? line_lex[li] : 0, line_pat ? line_pat[li] : 0};
+  return rec_tail_plan(tok_off, l0, l1, opts.data(), RecStores{tb, snap_min, ptb});
 }
 
 }  // namespace rt

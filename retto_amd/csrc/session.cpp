@@ -535,16 +535,15 @@ struct Pipeline {
   int* d_tok = nullptr; int* h_tokens = nullptr;   // CTC tokens at tok_off
   int* d_wcount = nullptr; wb::Word* d_words = nullptr; int* h_wcount = nullptr; wb::Word* h_words = nullptr;   // rec_return_word_box
   int* d_ccol = nullptr; cc::Cand* d_cands = nullptr; int* h_ccol = nullptr; cc::Cand* h_cands = nullptr;       // rec_return_candidates
-  std::vector<int> line_set;                // rec charsets: per line its set (0: none); empty when no line of the call has one
-  // rec lexicons: per line its lexicon (0: none), empty when no line of the call has one; then per line lx::MATCHES match slots
-  // and the number of matches (written for the lines that carry a lexicon only)
-  std::vector<int> line_lex;
+  // per line its charset, lexicon and pattern (0: none), and per kind whether some line of the call has one (rec_line_opts.h)
+  std::vector<RecLineOpts> line_opts; RecLineAny any;
+  // rec lexicons (any.lexicon): per line lx::MATCHES match slots and the number of matches (written for the lines that carry a
+  // lexicon only)
   lx::Match* d_lexm = nullptr; int* d_lexn = nullptr; lx::Match* h_lexm = nullptr; int* h_lexn = nullptr;
   // lexicon snap (ctc_lexicon_align.h): per line 1 where it snapped; null unless a lexicon of the call's lines has snap on
   int* d_lexs = nullptr; int* h_lexs = nullptr;
-  // rec patterns (ctc_pattern.h): per line its pattern (0: none), empty when no line of the call has one; then per line
-  // matched | vit | logprob | free_logprob, one block of 4 NLp words (written for the lines that carry a pattern only)
-  std::vector<int> line_pat;
+  // rec patterns (ctc_pattern.h; any.pattern): per line matched | vit | logprob | free_logprob, one block of 4 NLp words (written
+  // for the lines that carry a pattern only)
   int* d_pat = nullptr; int* h_pat = nullptr;
 };
 
@@ -903,13 +902,13 @@ void rec_groups(rt_session& s, Pipeline& P) {
   if (s.cfg.rec_return_word_box) {
     P.d_wcount = s.arena.alloc<int>(P.NLp); P.d_words = s.arena.alloc<wb::Word>(ntok); d_wcol = s.arena.alloc<int>(ntok);
   }
-  if (!P.line_lex.empty()) { P.d_lexm = s.arena.alloc<lx::Match>((size_t)P.NLp * lx::MATCHES); P.d_lexn = s.arena.alloc<int>(P.NLp); }
+  if (P.any.lexicon) { P.d_lexm = s.arena.alloc<lx::Match>((size_t)P.NLp * lx::MATCHES); P.d_lexn = s.arena.alloc<int>(P.NLp); }
   // lexicon snap (ctc_lexicon_align.h): a line snaps only where its lexicon has min_posterior > 0
-  if (std::any_of(P.line_lex.begin(), P.line_lex.end(), [&](int k) { return k > 0 && s.lexicons->snap[k - 1] > 0.0f; })) {
+  if (std::any_of(P.line_opts.begin(), P.line_opts.end(), [&](const RecLineOpts& o) { return o.lexicon > 0 && s.lexicons->snap[o.lexicon - 1] > 0.0f; })) {
     P.d_lexs = s.arena.alloc<int>(P.NLp);   // (zeroed: the lexicon lines of a group without a snap-enabled line are never written)
     RT_HIP_CHECK(hipMemsetAsync(P.d_lexs, 0, (size_t)P.NLp * sizeof(int), s.st));
   }
-  if (!P.line_pat.empty()) P.d_pat = s.arena.alloc<int>((size_t)4 * P.NLp);
+  if (P.any.pattern) P.d_pat = s.arena.alloc<int>((size_t)4 * P.NLp);
   static const long long REC_GROUP_PX = getenv("RT_REC_GROUP_PX") ? atoll(getenv("RT_REC_GROUP_PX")) : (long long)24000000;  // measured sweet spot (profiles/README.md)
   for (int l0 = 0; l0 < P.NL;) {
     const int l1 = group_end(l0, P.NL, 0, REC_GROUP_PX, [&](int l) { return (long long)rh * P.line_W[l]; });
@@ -934,9 +933,7 @@ void rec_groups(rt_session& s, Pipeline& P) {
     // (the token count per line only depends on the widths, so the offsets are known before the net runs)
     const long long t0 = P.tok_off[l0];
     const rt_lexicons& X = *s.lexicons;
-    const RecTailPlan tail = rec_tail_plan(P.tok_off.data(), l0, l1, P.line_set.empty() ? nullptr : P.line_set.data(),
-                                           P.line_lex.empty() ? nullptr : P.line_lex.data(), X.tb, X.snap,
-                                           P.line_pat.empty() ? nullptr : P.line_pat.data(), &s.patterns->tb);
+    const RecTailPlan tail = rec_tail_plan(P.tok_off.data(), l0, l1, P.line_opts.data(), RecStores{X.tb, X.snap, &s.patterns->tb});
     if (!tail.table_fits())
       throw RtError(RT_ERR_CAPACITY, "rec lexicons: " + std::to_string(tail.lines.size()) + " lines of one rec group carry lexicons of " +
                                          std::to_string(tail.table) + " entries in all, more than the " + std::to_string(lx::MAX_GROUP_TABLE) +
@@ -963,7 +960,7 @@ void rec_groups(rt_session& s, Pipeline& P) {
     }
     auto patf = [&](int k) { return P.d_pat ? reinterpret_cast<float*>(P.d_pat + (size_t)k * P.NLp) : nullptr; };   // vit | logprob | free_logprob
     const rt_session::RecTail t{z5, d_idx + t0, d_prob + t0, Lt.d, ln, s.charsets->d_masks, s.charsets->words,
-                                X.d_lex, X.d_entries, X.d_order, X.d_ids, X.d_snap, cand_k, 0,
+                                X.d, X.d_snap, cand_k, 0,
                                 P.d_tok + t0, P.d_meta.ntok + l0, P.d_meta.rscore + l0, nullptr, P.d_lexm, P.d_lexn, P.d_lexs, nullptr,
                                 P.d_ccol ? P.d_ccol + t0 : nullptr, P.d_cands ? P.d_cands + t0 * cand_k : nullptr,
                                 words.h_lines ? &words : nullptr, s.patterns->d, P.d_pat, patf(1), patf(2), patf(3)};
@@ -989,7 +986,7 @@ void line_round_trip(rt_session& s, Pipeline& P) {
     RT_HIP_CHECK(hipMemcpyAsync(P.h_wcount, P.d_wcount, (size_t)P.NL * sizeof(int), hipMemcpyDeviceToHost, s.st));
     if (total_tok > 0) RT_HIP_CHECK(hipMemcpyAsync(P.h_words, P.d_words, (size_t)total_tok * sizeof(wb::Word), hipMemcpyDeviceToHost, s.st));
   }
-  if (!P.line_lex.empty()) {   // (the lexicon matches too)
+  if (P.any.lexicon) {   // (the lexicon matches too)
     P.h_lexm = s.pinned.alloc<lx::Match>((size_t)P.NLp * lx::MATCHES); P.h_lexn = s.pinned.alloc<int>(P.NLp);
     RT_HIP_CHECK(hipMemcpyAsync(P.h_lexm, P.d_lexm, (size_t)P.NLp * lx::MATCHES * sizeof(lx::Match), hipMemcpyDeviceToHost, s.st));
     RT_HIP_CHECK(hipMemcpyAsync(P.h_lexn, P.d_lexn, (size_t)P.NLp * sizeof(int), hipMemcpyDeviceToHost, s.st));
@@ -1034,14 +1031,14 @@ void results(const rt_session& s, const Pipeline& P, rt_results& res) {
         memcpy(&R.cands[(size_t)R.cand_off[k] * K], P.h_cands + o * K, n * K * sizeof(cc::Cand));
       }
     }
-    if (!P.line_lex.empty()) {   // rec lexicons: a line without one has 0 matches (its device slots were never written)
+    if (P.any.lexicon) {   // rec lexicons: a line without one has 0 matches (its device slots were never written)
       R.lex_id.assign((size_t)nb, 0); R.lex_n.assign((size_t)nb, 0); R.lex_matches.assign((size_t)nb * lx::MATCHES, lx::Match{0, 0.0f, 0.0f});
       if (P.h_lexs) R.lex_snapped.assign((size_t)nb, 0);
       for (int k = 0; k < nb; k++) {
         const int li = p.first_line + k;
-        if (P.line_lex[li] <= 0) continue;
+        if (P.line_opts[li].lexicon <= 0) continue;
         if (P.h_lexs) R.lex_snapped[k] = P.h_lexs[li] == 1 ? 1 : 0;
-        R.lex_id[k] = P.line_lex[li];
+        R.lex_id[k] = P.line_opts[li].lexicon;
         R.lex_n[k] = std::min(std::max(P.h_lexn[li], 0), lx::MATCHES);
         for (int j = 0; j < R.lex_n[k]; j++) R.lex_matches[(size_t)k * lx::MATCHES + j] = P.h_lexm[(size_t)li * lx::MATCHES + j];
       }
@@ -1051,8 +1048,8 @@ void results(const rt_session& s, const Pipeline& P, rt_results& res) {
       const float* f = reinterpret_cast<const float*>(P.h_pat);
       for (int k = 0; k < nb; k++) {
         const int li = p.first_line + k;
-        if (P.line_pat[li] <= 0) continue;
-        R.pat_id[k] = P.line_pat[li];
+        if (P.line_opts[li].pattern <= 0) continue;
+        R.pat_id[k] = P.line_opts[li].pattern;
         R.pat_res[k] = pt::LineResult{P.h_pat[li] == 1 ? 1 : 0, f[P.NLp + li], f[2 * (size_t)P.NLp + li], f[3 * (size_t)P.NLp + li]};
       }
     }
@@ -1075,29 +1072,13 @@ void results(const rt_session& s, const Pipeline& P, rt_results& res) {
     }
   }
 }
-// A per-line option of the rec tail (rec charsets, rec lexicons): the regions' ids where the call gives them (line k of page i is
-// line first_line + k of the crop plan: the rec plan reorders widths, never lines), otherwise the session default on every line;
-// empty when no line has one.  Ids are 1-based in [1, n_ids], 0: none.
-std::vector<int> line_option(const Pipeline& P, const int* const* per_region, int dflt, int n_ids, const char* name) {
-  std::vector<int> v;
-  if (per_region) {
-    v.assign((size_t)P.NL, 0);
-    for (int i = 0; i < P.n_pages; i++)
-      for (int k = 0; k < P.pg[i].n_boxes && per_region[i]; k++) v[(size_t)P.pg[i].first_line + k] = per_region[i][k];
-    if (std::none_of(v.begin(), v.end(), [](int x) { return x > 0; })) v.clear();
-  } else if (dflt > 0 && P.NL > 0) {
-    v.assign((size_t)P.NL, dflt);
-  }
-  for (int x : v)
-    if (x < 0 || x > n_ids) throw RtError(RT_ERR_INVALID, std::string("unknown rec ") + name + " id " + std::to_string(x));
-  return v;
-}
+// what a rule of rec_line_opts.h objects to, if anything
+void refuse(const std::string& why) { if (!why.empty()) throw RtError(RT_ERR_INVALID, why); }
 }  // namespace
 std::string rt_format_f32_impl(float v) { return fnum(v); }
 
 rt_results* rt_session::run_pages(const uint8_t* const* rgb, const int* hs, const int* ws, int n_pages, int mem,
-                                  const float* const* det_map_override, const Regions* regions, int rec_charset_default,
-                                  int rec_lexicon_default, int rec_pattern_default, int det_tile_, int det_overlap_) {
+                                  const float* const* det_map_override, const Regions* regions, const CallSettings& set) {
   if (g_trace) fprintf(stderr, "[rt host] %-28s %8.3f ms\n", "between calls", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - last_exit).count());
   HostTick tick0;
   // a one-page call is the reference's real mode (retto-cli/src/main.rs:80-86): it polls through its waits; a multi-page batch
@@ -1113,7 +1094,7 @@ rt_results* rt_session::run_pages(const uint8_t* const* rgb, const int* hs, cons
   if (n_pages == 0) return res.release();
   Pipeline P{n_pages, mem, det_map_override, std::vector<PageState>((size_t)n_pages)};
   P.regions = regions; P.crop_original = regions != nullptr || cfg.crop_source == 1;
-  P.det_tile = det_tile_; P.det_overlap = det_overlap_;
+  P.det_tile = set.det_tile; P.det_overlap = set.det_overlap;
   HostTick tick;
   if (regions) {   // the boxes are given: no resize_both, no detector, no DB post-processing, no first round trip
     region_pages(*this, P, rgb, hs, ws); tick.lap("pre (upload, regions)");
@@ -1124,11 +1105,7 @@ rt_results* rt_session::run_pages(const uint8_t* const* rgb, const int* hs, cons
     db_post(*this, P); tick.lap("dbpost enqueue");
     box_round_trip(*this, P, *res); tick.lap("sync #1 + box D2H");
   }
-  P.line_set = line_option(P, regions ? regions->charsets : nullptr, rec_charset_default, (int)charsets->ids.size(), "charset");
-  P.line_lex = line_option(P, regions ? regions->lexicons : nullptr, rec_lexicon_default, (int)lexicons->host.size(), "lexicon");
-  P.line_pat = line_option(P, regions ? regions->patterns : nullptr, rec_pattern_default, (int)patterns->host.size(), "pattern");
-  for (size_t li = 0; li < P.line_pat.size() && !P.line_lex.empty(); li++)   // (the entry points refuse this before anything is queued)
-    if (P.line_pat[li] > 0 && P.line_lex[li] > 0) throw RtError(RT_ERR_INVALID, "line " + std::to_string(li) + " carries both a rec pattern and a rec lexicon");
+  refuse(expand_line_opts(P.pg.data(), n_pages, P.NL, regions ? regions->opts : nullptr, set.rec, rec_counts(), P.line_opts, P.any));
   crop_stage(*this, P);
   if (P.NL > 0) {
     tick.lap("crop plan + warp enqueue");
@@ -1388,9 +1365,7 @@ void rt_session::free_stage() {
 rt_ticket* rt_session::submit_batch(const uint8_t* const* rgb, const int* hs, const int* ws, int n_pages, int mem,
                                     const float* const* det_map_override, rt_stage_callback cb, void* user,
                                     std::vector<rt::EncodedPage>* enc, const Regions* regions) {
-  if (!regions && rec_pattern > 0 && rec_lexicon > 0)
-    throw RtError(RT_ERR_INVALID, "the session defaults name both a rec pattern (" + std::to_string(rec_pattern) + ") and a rec lexicon (" +
-                                      std::to_string(rec_lexicon) + "): a line may not carry both");
+  if (!regions) refuse(rec_opts_conflict(rec_default));   // (regions: run_regions has checked every region's own options)
   ensure_workers();
   std::unique_ptr<rt_ticket> t(new rt_ticket());
   const int nl = std::max(1, std::min<int>(std::min<int>((int)helpers.size() + 1, active_lanes), std::max(n_pages, 1)));
@@ -1398,13 +1373,8 @@ rt_ticket* rt_session::submit_batch(const uint8_t* const* rgb, const int* hs, co
   t->rgb.assign(rgb, rgb + n_pages); t->hs.assign(hs, hs + n_pages); t->ws.assign(ws, ws + n_pages);
   if (det_map_override) t->maps.assign(det_map_override, det_map_override + n_pages);
   if (regions) { t->quads.assign(regions->quads, regions->quads + n_pages); t->n_quads.assign(regions->n_quads, regions->n_quads + n_pages); }
-  if (regions && regions->charsets) t->region_sets.assign(regions->charsets, regions->charsets + n_pages);
-  if (regions && regions->lexicons) t->region_lexicons.assign(regions->lexicons, regions->lexicons + n_pages);
-  t->rec_charset = rec_charset;   // (the lanes run later: the default is the one of the submitting call)
-  t->rec_lexicon = rec_lexicon;
-  if (regions && regions->patterns) t->region_patterns.assign(regions->patterns, regions->patterns + n_pages);
-  t->rec_pattern = rec_pattern;
-  t->det_tile = det_tile; t->det_overlap = det_overlap;
+  if (regions && regions->opts) t->region_opts.assign(regions->opts, regions->opts + n_pages);
+  t->set = settings();   // (the lanes run later: the settings are the ones of the submitting call)
   t->parts.assign((size_t)nl, nullptr); t->errs.resize((size_t)nl); t->first.assign((size_t)nl + 1, 0);
   {
     // contiguous ranges of about equal work: det pixels after the session size limit (a2) plus a constant per page
@@ -1455,12 +1425,9 @@ rt_ticket* rt_session::submit_batch(const uint8_t* const* rgb, const int* hs, co
       try {
         if (!tp->ev_up.empty()) RT_HIP_CHECK(hipStreamWaitEvent(s->st, tp->ev_up[(size_t)l], 0));
         Regions rg{nullptr, nullptr};
-        if (!tp->quads.empty()) rg = Regions{tp->quads.data() + f0, tp->n_quads.data() + f0, tp->region_sets.empty() ? nullptr : tp->region_sets.data() + f0,
-                                                  tp->region_lexicons.empty() ? nullptr : tp->region_lexicons.data() + f0,
-                                                  tp->region_patterns.empty() ? nullptr : tp->region_patterns.data() + f0};
+        if (!tp->quads.empty()) rg = Regions{tp->quads.data() + f0, tp->n_quads.data() + f0, tp->region_opts.empty() ? nullptr : tp->region_opts.data() + f0};
         tp->parts[l] = s->run_pages(tp->rgb.data() + f0, tp->hs.data() + f0, tp->ws.data() + f0, f1 - f0, tp->mem_lane,
-                                    tp->maps.empty() ? nullptr : tp->maps.data() + f0, tp->quads.empty() ? nullptr : &rg, tp->rec_charset, tp->rec_lexicon, tp->rec_pattern,
-                                    tp->det_tile, tp->det_overlap);
+                                    tp->maps.empty() ? nullptr : tp->maps.data() + f0, tp->quads.empty() ? nullptr : &rg, tp->set);
       } catch (...) {
         tp->errs[l] = std::current_exception();
         s->failed = true;
@@ -1524,12 +1491,10 @@ rt_results* rt_session::run_batch(const uint8_t* const* rgb, const int* hs, cons
       rt_session* self;
       ~Disarm() { self->stage_cb = nullptr; self->stage_mu = nullptr; }
     } disarm{this};
-    if (rec_pattern > 0 && rec_lexicon > 0)
-      throw RtError(RT_ERR_INVALID, "the session defaults name both a rec pattern (" + std::to_string(rec_pattern) + ") and a rec lexicon (" +
-                                        std::to_string(rec_lexicon) + "): a line may not carry both");
+    refuse(rec_opts_conflict(rec_default));
     stage_cb = cb; stage_user = user; stage_mu = &cb_mu; page_base = 0;
     try {
-      return run_pages(rgb, hs, ws, n_pages, mem, det_map_override, nullptr, rec_charset, rec_lexicon, rec_pattern, det_tile, det_overlap);
+      return run_pages(rgb, hs, ws, n_pages, mem, det_map_override, nullptr, settings());
     } catch (...) { failed = true; throw; }
   }
   return wait_batch(submit_batch(rgb, hs, ws, n_pages, mem, det_map_override, cb, user));
@@ -1540,15 +1505,12 @@ rt_results* rt_session::run_batch(const uint8_t* const* rgb, const int* hs, cons
 rt_results* rt_session::run_regions(const uint8_t* const* rgb, const int* hs, const int* ws, int n_pages, int mem,
                                     const float* const* quads, const int* n_quads, const int* const* region_charsets,
                                     const int* const* region_lexicons, const int* const* region_patterns) {
-  std::vector<std::vector<int>> pats((size_t)n_pages);   // (and their patterns)
-  std::vector<const int*> pp_((size_t)n_pages, nullptr);
   std::vector<std::vector<float>> clamped((size_t)n_pages);
   std::vector<const float*> qp((size_t)n_pages, nullptr);
-  // the regions' charsets with -1 resolved to the session default of this call (rec charsets, ctc_charset.h)
-  std::vector<std::vector<int>> sets((size_t)n_pages);
-  std::vector<const int*> sp((size_t)n_pages, nullptr);
-  std::vector<std::vector<int>> lexs((size_t)n_pages);   // (and their lexicons)
-  std::vector<const int*> lp((size_t)n_pages, nullptr);
+  // the regions' options with -1 resolved to the session defaults of this call (rec_line_opts.h)
+  std::vector<std::vector<RecLineOpts>> opts((size_t)n_pages);
+  std::vector<const RecLineOpts*> op((size_t)n_pages, nullptr);
+  const int* const* const ids[3] = {region_charsets, region_lexicons, region_patterns};
   for (int i = 0; i < n_pages; i++) {
     const std::string where = "rt_run_regions: page " + std::to_string(i);
     if (hs[i] <= 0 || ws[i] <= 0 || rgb[i] == nullptr) throw RtError(RT_ERR_IMAGE, where + ": empty page");
@@ -1571,42 +1533,19 @@ rt_results* rt_session::run_regions(const uint8_t* const* rgb, const int* hs, co
       if (!gm::projection_inverse(b, d.cw, d.ch, inv)) throw RtError(RT_ERR_INVALID, at + ": singular homography (degenerate quad)");
     }
     qp[(size_t)i] = q.data();
-    sets[(size_t)i].assign((size_t)n_quads[i], rec_charset);
-    for (int k = 0; k < n_quads[i] && region_charsets && region_charsets[i]; k++) {
-      const int v = region_charsets[i][k];
-      if (v < -1 || v > (int)charsets->ids.size())
-        throw RtError(RT_ERR_INVALID, where + " region " + std::to_string(k) + ": unknown charset id " + std::to_string(v));
-      if (v >= 0) sets[(size_t)i][(size_t)k] = v;
-    }
-    sp[(size_t)i] = sets[(size_t)i].data();
-    lexs[(size_t)i].assign((size_t)n_quads[i], rec_lexicon);
-    for (int k = 0; k < n_quads[i] && region_lexicons && region_lexicons[i]; k++) {
-      const int v = region_lexicons[i][k];
-      if (v < -1 || v > (int)lexicons->host.size())
-        throw RtError(RT_ERR_INVALID, where + " region " + std::to_string(k) + ": unknown lexicon id " + std::to_string(v));
-      if (v >= 0) lexs[(size_t)i][(size_t)k] = v;
-    }
-    lp[(size_t)i] = lexs[(size_t)i].data();
-    pats[(size_t)i].assign((size_t)n_quads[i], rec_pattern);
-    for (int k = 0; k < n_quads[i]; k++) {
-      const int v = region_patterns && region_patterns[i] ? region_patterns[i][k] : -1;
-      if (v < -1 || v > (int)patterns->host.size())
-        throw RtError(RT_ERR_INVALID, where + " region " + std::to_string(k) + ": unknown pattern id " + std::to_string(v));
-      if (v >= 0) pats[(size_t)i][(size_t)k] = v;
-      if (pats[(size_t)i][(size_t)k] > 0 && lexs[(size_t)i][(size_t)k] > 0)
-        throw RtError(RT_ERR_INVALID, where + " region " + std::to_string(k) + ": both a rec pattern (" + std::to_string(pats[(size_t)i][(size_t)k]) +
-                                          ") and a rec lexicon (" + std::to_string(lexs[(size_t)i][(size_t)k]) + "): a line may not carry both");
-    }
-    pp_[(size_t)i] = pats[(size_t)i].data();
+    // (a page's options behind the checks of its quads and before the next page's)
+    const std::string bad = resolve_region_opts(i, i + 1, n_quads, ids, rec_default, rec_counts(), opts);
+    if (!bad.empty()) throw RtError(RT_ERR_INVALID, "rt_run_regions: " + bad);
+    op[(size_t)i] = opts[(size_t)i].data();
   }
-  const Regions rg{qp.data(), n_quads, sp.data(), lp.data(), pp_.data()};
+  const Regions rg{qp.data(), n_quads, op.data()};
   const int nl = std::max(1, std::min<int>(std::min<int>((int)helpers.size() + 1, active_lanes), std::max(n_pages, 1)));
   if (nl <= 1) {   // one lane: on the caller's thread, as run_batch
     try {
-      return run_pages(rgb, hs, ws, n_pages, mem, nullptr, &rg);
+      return run_pages(rgb, hs, ws, n_pages, mem, nullptr, &rg, settings());
     } catch (...) { failed = true; throw; }
   }
-  return wait_batch(submit_batch(rgb, hs, ws, n_pages, mem, nullptr, nullptr, nullptr, nullptr, &rg));   // (clamped and sets outlive the wait)
+  return wait_batch(submit_batch(rgb, hs, ws, n_pages, mem, nullptr, nullptr, nullptr, nullptr, &rg));   // (clamped and opts outlive the wait)
 }
 
 // RettoWorkerStageResult JSON (serde derive shapes; retto-wasm/fe/index.ts:5-42)

@@ -19,6 +19,7 @@
 #include "nets.h"
 #include "nets_f16.h"
 #include "prepost.h"
+#include "rec_line_opts.h"
 #include "rec_tail_plan.h"
 #include "runtime.h"
 
@@ -70,6 +71,10 @@ struct LaneWorker {
   ~LaneWorker() { shutdown(); }
 };
 
+// What a pipeline call reads of the session's settings, as they were when the call was submitted: the default options of every
+// line (rt_set_rec_charset / _lexicon / _pattern, rec_line_opts.h) and the det tiles (rt_set_det_tiles, det_tiles.h; 0 = off)
+struct CallSettings { rt::RecLineOpts rec; int det_tile = 0, det_overlap = 0; };
+
 // One submitted batch (rt_submit_batch): the argument arrays are copied (the PAGES must stay valid until rt_wait_batch), the
 // pages are split over the lanes exactly as rt_run_batch splits them, each lane leaves its part here.
 struct rt_ticket {
@@ -81,16 +86,10 @@ struct rt_ticket {
   // empty: the detector finds the boxes
   std::vector<const float*> quads;
   std::vector<int> n_quads;
-  // rec charsets (ctc_charset.h): the session default as it was when the batch was submitted (the lanes run later), and with
-  // rt_run_regions_charsets per page the regions' resolved ids (owned by the caller of submit_batch); empty: the default
-  int rec_charset = 0;
-  std::vector<const int*> region_sets;
-  // rec lexicons (ctc_lexicon.h): the same two for lexicons
-  int rec_lexicon = 0;
-  std::vector<const int*> region_lexicons;
-  int rec_pattern = 0;
-  std::vector<const int*> region_patterns;
-  int det_tile = 0, det_overlap = 0;   // det tiles (det_tiles.h): the session's setting as it was when the batch was submitted
+  // the session's settings as they were when the batch was submitted (the lanes run later), and with rt_run_regions* per page
+  // the regions' resolved options (rec_line_opts.h; owned by the caller of submit_batch); empty: every line gets set.rec
+  CallSettings set;
+  std::vector<const rt::RecLineOpts*> region_opts;
   std::vector<int> first;
   std::vector<rt_results*> parts;
   std::vector<std::exception_ptr> errs;
@@ -131,20 +130,21 @@ struct rt_charsets {
 
 // The session's rec lexicons (ctc_lexicon.h), shared with the helper lanes.  Lexicon k (1-based, rt_lexicon_create's id) is
 // host[k - 1] on the host (stable addresses: rt_lexicon_entry / _entry_text hand them out) and lexicon k - 1 of `tb`, whose four
-// tables sit on the device as d_*.  Only changed while no ticket is in flight and every lane's stream is drained
+// tables sit on the device as `d`.  Only changed while no ticket is in flight and every lane's stream is drained
 // (rt_lexicon_create is a guarded call): the tables are rebuilt and copied whole, with blocking copies.
 struct rt_lexicons {
   struct Host { std::vector<int32_t> ids, lens, off; std::vector<std::string> text; };
   std::vector<std::unique_ptr<Host>> host;
   rt::lx::Tables tb;
-  int32_t* d_ids = nullptr; rt::lx::Entry* d_entries = nullptr; int32_t* d_order = nullptr; rt::lx::Lex* d_lex = nullptr;
+  rt::lx::DevTables d{};
   // lexicon snap (ctc_lexicon_align.h, rt_lexicon_set_snap): min_posterior per lexicon, 0 = never snap; d_snap [MAX_LEXICONS]
   // is allocated by the first rt_lexicon_set_snap and changed under the same guard, with a blocking copy
   float snap[rt::lx::MAX_LEXICONS] = {};
   float* d_snap = nullptr;
   void free_device() {
-    if (d_ids) (void)hipFree(d_ids); if (d_entries) (void)hipFree(d_entries); if (d_order) (void)hipFree(d_order); if (d_lex) (void)hipFree(d_lex);
-    d_ids = nullptr; d_entries = nullptr; d_order = nullptr; d_lex = nullptr;
+    const void* p[] = {d.ids, d.entries, d.order, d.lex};
+    for (const void* q : p) if (q) (void)hipFree(const_cast<void*>(q));
+    d = rt::lx::DevTables{};
   }
   ~rt_lexicons() { free_device(); if (d_snap) (void)hipFree(d_snap); }
 };
@@ -191,15 +191,18 @@ struct rt_session {
   std::vector<std::unique_ptr<rt_session>> helpers;
   int active_lanes = 1 << 30;  // rt_set_lanes: upper bound on the lanes rt_run_batch uses
   std::vector<std::string> dict;  // RecCharacter (rec_processor.rs:29-46)
-  std::shared_ptr<rt_charsets> charsets;   // rec charsets (shared with the helper lanes)
-  int rec_charset = 0;            // rt_set_rec_charset: the default of every line of the pipeline calls that follow (0: none)
-  std::shared_ptr<rt_lexicons> lexicons;   // rec lexicons (shared with the helper lanes)
-  int rec_lexicon = 0;            // rt_set_rec_lexicon: likewise
-  std::shared_ptr<rt_patterns> patterns;   // rec patterns (shared with the helper lanes)
-  int rec_pattern = 0;            // rt_set_rec_pattern: likewise
-  // rt_set_det_tiles (det_tiles.h): pages whose det input is larger than det_tile either way are detected in tiles; 0 = off.  A
-  // helper lane never reads its own copy: a batch carries the main lane's value (rt_ticket::det_tile) into run_pages
+  // the rec charsets, lexicons and patterns (shared with the helper lanes), and how many of each there are: the valid ids
+  std::shared_ptr<rt_charsets> charsets;
+  std::shared_ptr<rt_lexicons> lexicons;
+  std::shared_ptr<rt_patterns> patterns;
+  rt::RecLineOpts rec_counts() const { return {(int)charsets->ids.size(), (int)lexicons->host.size(), (int)patterns->host.size()}; }
+  // rt_set_rec_charset / _lexicon / _pattern: the options of every line of the pipeline calls that follow, unless a region names
+  // its own (0: none)
+  rt::RecLineOpts rec_default;
+  // rt_set_det_tiles (det_tiles.h): pages whose det input is larger than det_tile either way are detected in tiles; 0 = off
   int det_tile = 0, det_overlap = 0;
+  // A helper lane never reads its own rec_default / det_tile / det_overlap: a call carries the main lane's into run_pages
+  CallSettings settings() const { return {rec_default, det_tile, det_overlap}; }
   uint8_t* d_word_raw = nullptr;  // rec_return_word_box: wb::raw_class of every dictionary entry (device; owned by the main lane)
   std::string last_error;
   int* d_flags = nullptr;         // [0] thumbnail/resize error flag
@@ -246,7 +249,7 @@ struct rt_session {
     const rt::ImgGeom* lines; int n_lines;    // the token level: {first row, 1, T} per line
     const uint32_t* masks; int words;         // rec charsets: [.][words]
     // rec lexicons: the device tables (lx::Tables) and the per-lexicon min_posterior (read in a snap group only)
-    const rt::lx::Lex* d_lex; const rt::lx::Entry* d_entries; const int* d_order; const int* d_ids; const float* d_min_post;
+    rt::lx::DevTables d_lex; const float* d_min_post;
     int cand_k, chunk_rows;                   // rec_return_candidates; rows per logits recompute (0: cc::CAND_CHUNK)
     int* tok; int* ntok; float* rscore;       // pp::ctc_decode's outputs
     float* loglik;                            // [plan.table], or null: taken from `scratch`
@@ -303,10 +306,8 @@ struct rt_session {
   void free_stage();
   void ensure_workers();
   // regions (rt_run_regions): quads[i] = n_quads[i] x 8 validated, clamped floats of page i, valid until the ticket is waited for
-  // charsets (rt_run_regions_charsets): per page the regions' charset ids, already resolved (>= 0) and checked; null: the default
-  // lexicons (rt_run_regions_lexicons): the same for rec lexicons
-  struct Regions { const float* const* quads; const int* n_quads; const int* const* charsets = nullptr; const int* const* lexicons = nullptr;
-                   const int* const* patterns = nullptr; };   // patterns (rt_run_regions_patterns): the same for rec patterns
+  // opts: per page the regions' options, already resolved (no -1) and checked (rt::resolve_region_opts); null: the call's defaults
+  struct Regions { const float* const* quads; const int* n_quads; const rt::RecLineOpts* const* opts = nullptr; };
   rt_ticket* submit_batch(const uint8_t* const* rgb, const int* hs, const int* ws, int n_pages, int mem,
                           const float* const* det_map_override, rt_stage_callback cb = nullptr, void* user = nullptr,
                           std::vector<rt::EncodedPage>* enc = nullptr, const Regions* regions = nullptr);
@@ -316,19 +317,17 @@ struct rt_session {
   rt_results* run_batch(const uint8_t* const* rgb, const int* hs, const int* ws, int n_pages, int mem,
                         const float* const* det_map_override, rt_stage_callback cb = nullptr, void* user = nullptr);
   rt_results* run_pages(const uint8_t* const* rgb, const int* hs, const int* ws, int n_pages, int mem,
-                        const float* const* det_map_override, const Regions* regions = nullptr,
-                        int rec_charset_default = 0, int rec_lexicon_default = 0, int rec_pattern_default = 0,
-                        int det_tile_ = 0, int det_overlap_ = 0);  // one lane
+                        const float* const* det_map_override, const Regions* regions, const CallSettings& set);  // one lane
   // rt_debug_det_tiles: the det stage of a one-page call on a host RGB8 image at det-input size h x w, through the pipeline's own
   // det_groups under the session's det tiles; tile_maps_out: every tile's own map packed in plan order, page_map_out [h * w]
   void debug_det_tiles(const uint8_t* rgb_det, int h, int w, float* tile_maps_out, float* page_map_out);
   // rt_run_regions: checks and clamps every quad (RT_ERR_INVALID naming page and region; nothing is queued then), then the
   // pages go over the lanes as run_batch's do, from the crop plan on
-  // charsets (or null; entries may be null): per region -1 = the session default, 0 = none, >= 1 = that charset
+  // charsets, lexicons, patterns (each or null; entries may be null): per region -1 = the session default, 0 = none, >= 1 = that
+  // id (rt::resolve_region_opts); a region may not carry both a pattern and a lexicon
   rt_results* run_regions(const uint8_t* const* rgb, const int* hs, const int* ws, int n_pages, int mem,
-                          const float* const* quads, const int* n_quads, const int* const* charsets = nullptr,
-                          const int* const* lexicons = nullptr,    // lexicons: the same convention for rec lexicons
-                          const int* const* patterns = nullptr);   // patterns: likewise; a region may not carry both a pattern and a lexicon
+                          const float* const* quads, const int* n_quads, const int* const* charsets, const int* const* lexicons,
+                          const int* const* patterns);
 };
 
 rt_session* rt_session_create(const rt_config* cfg);

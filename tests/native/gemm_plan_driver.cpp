@@ -1,5 +1,6 @@
 // Host-only driver of nn::gemm_plan() / nn::gemm_se_rows() (retto_amd/csrc/gemm_plan.cpp) and nn::dw_plan() / nn::lc_plan()
-// (lc_plan.cpp) for tests/test_gemm_plan_cpu.py and tests/test_lc_plan_cpu.py.
+// (lc_plan.cpp) for tests/test_gemm_plan_cpu.py and tests/test_lc_plan_cpu.py, and of the host-only headers rec_tail_plan.h
+// (tests/test_rec_tail_plan_cpu.py) and rec_line_opts.h (tests/test_rec_line_opts_cpu.py).
 // One query per stdin line, one answer per stdout line:
 //   plan <variant> <dma> <split> <argmax_wide> <cus> <lda> <M> <K> <N> <Npad16> <ldc> <coff>
 //        <am_max> <residual> <a_scale> <a_tab_stride> <act> <has_lab> <n_img> <ld_scale>
@@ -15,6 +16,12 @@
 //        <n_lex> <n16 n32 n64 of each lexicon: its entries of 1, 8 and 16 ids> <1 + n_lex snap thresholds, or 0>
 //     -> rec_tail_plan() (rec_tail_plan.h) of lines [l0, l1): rows=.. z5=.. has_lex=.. snap=.. table=.. fits=.. max_waves=..
 //        row_set=a,b,.. crows=.. lines=row0:T:lex:slot:out,.. lrows=..   (an empty list prints as -)
+//   defaults <charset> <lexicon> <pattern>  ->  rec_opts_conflict() of session defaults: ok   or   error: <message>
+//   regions <default charset lexicon pattern> <count of charsets lexicons patterns> <n_pages> <regions of each page>
+//           then per kind (charsets, lexicons, patterns): 0 = no array, or 1 and per page: 0 = no entry, or 1 and the regions' ids
+//     -> resolve_region_opts() (rec_line_opts.h) of all pages: ok <per page charset:lexicon:pattern,.. or ->   or   error: <message>
+//   lines <defaults> <counts> <n_pages> <boxes of each page> then 0 = the defaults, or 1 and every box's charset lexicon pattern
+//     -> expand_line_opts() over pages whose first lines follow each other: any=c,l,p lines=charset:lexicon:pattern,..  or  error: ..
 // (am_max != 0 sets the CTC-head statistics with am_tiles = gemm_argmax_tiles(Npad16); a_scale != 0 sets a scale and a row table)
 #include "nn.h"
 #include "rec_tail_plan.h"
@@ -148,6 +155,68 @@ int main() {
       for (size_t i = 0; i < p.lines.size(); i++)
         printf("%s%d:%d:%d:%d:%lld", i ? "," : "", p.lines[i].row0, p.lines[i].T, p.lines[i].lex, p.lines[i].slot, p.lines[i].out);
       print_list("lrows", p.lrows);
+      printf("\n");
+    } else if (op == "defaults") {
+      RecLineOpts o;
+      in >> o.charset >> o.lexicon >> o.pattern;
+      if (!in) { printf("bad query\n"); return 2; }
+      const std::string bad = rec_opts_conflict(o);
+      printf("%s%s\n", bad.empty() ? "ok" : "error: ", bad.c_str());
+    } else if (op == "regions" || op == "lines") {
+      RecLineOpts dflt, counts;
+      int n_pages = 0;
+      in >> dflt.charset >> dflt.lexicon >> dflt.pattern >> counts.charset >> counts.lexicon >> counts.pattern >> n_pages;
+      if (!in || n_pages < 0) { printf("bad query\n"); return 2; }
+      std::vector<int> n((size_t)n_pages);
+      for (int& x : n) in >> x;
+      for (int x : n) if (!in || x < 0) { printf("bad query\n"); return 2; }
+      std::string bad;
+      if (op == "regions") {
+        std::vector<std::vector<int>> vals[3];
+        std::vector<const int*> ptrs[3];
+        const int* const* ids[3] = {nullptr, nullptr, nullptr};
+        for (int j = 0; j < 3; j++) {
+          int has = 0;
+          in >> has;
+          if (!has) continue;
+          vals[j].resize((size_t)n_pages); ptrs[j].assign((size_t)n_pages, nullptr);
+          for (int i = 0; i < n_pages; i++)
+            if (read_optional(in, (size_t)n[(size_t)i], vals[j][(size_t)i])) ptrs[j][(size_t)i] = vals[j][(size_t)i].data();
+          ids[j] = ptrs[j].data();
+        }
+        if (!in) { printf("bad query\n"); return 2; }
+        std::vector<std::vector<RecLineOpts>> out((size_t)n_pages);
+        bad = resolve_region_opts(0, n_pages, n.data(), ids, dflt, counts, out);
+        if (bad.empty()) {
+          printf("ok");
+          for (const auto& page : out) {
+            printf(" %s", page.empty() ? "-" : "");
+            for (size_t k = 0; k < page.size(); k++) printf("%s%d:%d:%d", k ? "," : "", page[k].charset, page[k].lexicon, page[k].pattern);
+          }
+        }
+      } else {
+        struct Page { int first_line, n_boxes; };
+        std::vector<Page> pages((size_t)n_pages);
+        int NL = 0, has = 0;
+        for (int i = 0; i < n_pages; i++) { pages[(size_t)i] = {NL, n[(size_t)i]}; NL += n[(size_t)i]; }
+        in >> has;
+        std::vector<std::vector<RecLineOpts>> vals((size_t)n_pages);
+        std::vector<const RecLineOpts*> ptrs;
+        for (int i = 0; has && i < n_pages; i++) {
+          vals[(size_t)i].resize((size_t)n[(size_t)i]);
+          for (RecLineOpts& o : vals[(size_t)i]) in >> o.charset >> o.lexicon >> o.pattern;
+          ptrs.push_back(vals[(size_t)i].data());
+        }
+        if (!in) { printf("bad query\n"); return 2; }
+        std::vector<RecLineOpts> lines;
+        RecLineAny any;
+        bad = expand_line_opts(pages.data(), n_pages, NL, has ? ptrs.data() : nullptr, dflt, counts, lines, any);
+        if (bad.empty()) {
+          printf("any=%d,%d,%d lines=%s", (int)any.charset, (int)any.lexicon, (int)any.pattern, lines.empty() ? "-" : "");
+          for (size_t k = 0; k < lines.size(); k++) printf("%s%d:%d:%d", k ? "," : "", lines[k].charset, lines[k].lexicon, lines[k].pattern);
+        }
+      }
+      if (!bad.empty()) printf("error: %s", bad.c_str());
       printf("\n");
     } else if (!op.empty()) {
       printf("unknown query %s\n", op.c_str());

@@ -162,6 +162,39 @@ def test_the_same_results_from_every_entry_point(session):
     assert CS.digest(after) == plain and all(g.pattern is None for g in after.rec_result)
 
 
+def test_a_kind_per_page_on_three_lanes(session):
+    """One run_regions call over three copies of the page, so that each of the three lanes gets one page and reads its own page's
+    entry of the call's one per-page option array: page 0's regions carry charsets only (-1 among them: the session default),
+    page 1's lexicons only, with no charset entry for the page (the default on every region), page 2's patterns only.  Every
+    page is, bit for bit, what it is run alone -- one page, one lane -- with the same options."""
+    s, c = session, session.case
+    page, B = c["page"], c["B"]
+    pe = c.get("pe") or s.create_pattern(exact_pattern(c["ref"].rec_result[c["exact"]].tokens))
+    rng = np.random.default_rng(77)
+    half, dflt = (s.create_charset(ids=np.flatnonzero(rng.random(c["N"]) < 0.5).tolist()) for _ in range(2))
+    lex = s.create_lexicon(ids=[[1], [2], [1, 2]])
+    cs0, lx1 = [half, 0, -1, half, -1, 0], [lex, 0, lex, 0, 0, lex]
+    pt2 = [pe if k == c["exact"] else 0 for k in range(6)]
+    alone = (dict(charsets=[cs0]), dict(lexicons=[lx1]), dict(charsets=[[0] * 6], patterns=[pt2]))
+    whole = lambda r: (CS.digest(r), pat_bits(r), [g.lexicon_matches and [(e, t, np.float32(ll).tobytes(), np.float32(p).tobytes())
+                                                                           for e, t, ll, p in g.lexicon_matches] for g in r.rec_result])
+    s.set_rec_charset(dflt)
+    try:
+        three = s.run_regions([page] * 3, [B] * 3, charsets=[cs0, None, [0] * 6], lexicons=[None, lx1, None], patterns=[None, None, pt2])
+        want = [s.run_regions([page], [B], **kw)[0] for kw in alone]
+    finally:
+        s.set_rec_charset(0)
+    for i in range(3):
+        assert whole(three[i]) == whole(want[i]), (i, CS.differing(CS.digest(three[i]), CS.digest(want[i])))
+    # each page carries its own kind and no other
+    assert [[g.pattern is not None for g in r.rec_result] for r in three] == [[False] * 6, [False] * 6, [p > 0 for p in pt2]]
+    assert [[g.lexicon_matches is not None for g in r.rec_result] for r in three] == [[False] * 6, [x > 0 for x in lx1], [False] * 6]
+    ref = CS.digest(c["ref"])
+    assert CS.digest(three[0]) != ref and CS.digest(three[1]) != ref and CS.digest(three[0]) != CS.digest(three[1])   # the charsets bite
+    assert three[2].rec_result[c["exact"]].pattern[0] is True
+    assert all(_line(CS.digest(three[2]), k) == _line(ref, k) for k in range(6) if k != c["exact"])   # (0 overrides the default charset)
+
+
 def test_a_pattern_and_a_charset_on_one_line(session):
     """the charset writes first; a match overwrites its rows, and where the line cannot match the charset's decode stands"""
     s, c = session, session.case
