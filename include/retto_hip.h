@@ -573,6 +573,75 @@ RT_API int rt_debug_ctc_pattern_host(const float* z5, const float* W, const floa
                                      int n_lines, const int32_t* line_pat, const int32_t* pat_S, const int32_t* pat_G,
                                      const int32_t* group_of, const int32_t* delta, const int32_t* accept, int n_pat, int32_t* idx,
                                      float* prob, int32_t* matched_out, float* vit_out, float* logprob_out, float* free_out);
+
+/* ---- rec keywords: a caller's keyword list spotted inside every line ----------------------------------------------------------
+ * For the page-level question "where does it say Total, Invoice No, this customer's name".  A lexicon ranks whole lines only, a
+ * pattern .*Total.* over the whole dictionary passes RT_PATTERN_MAX_PAIRS, and searching the decoded text afterwards loses the
+ * hit to one weak frame.  retto_amd/csrc/ctc_keyword.h states the rule; in short, for a line of T time steps that carries a list
+ * and each entry of the list:
+ *   score      the log-ratio of the best CTC path whose collapsed string CONTAINS the entry as a substring over the best
+ *              unconstrained path, from the line's recomputed fp32 logits; <= 0, and exactly 0 where the greedy path holds it;
+ *   span       first_col, last_col: the time steps that best occurrence covers (ties: the earliest start, then the earliest end);
+ *   hits       the entries that fit the line (T >= length + equal neighbours) with score >= the list's min_score, up to
+ *              RT_KEYWORD_HITS of them, by score descending, then entry number ascending;
+ *   quad       the span [first_col, last_col + 1) on the page, mapped exactly as a word of rt_config.rec_return_word_box is (it
+ *              needs no option: the quads are computed on the host for lines with hits only).
+ * One occurrence per (line, entry): the best.  Several occurrences, length normalisation and whole-word matching are out of scope.
+ * Keywords only read a line: they go with any charset, lexicon or pattern, and every other result -- boxes, tokens, text, scores,
+ * words, candidates, lexicon matches and snaps, pattern results, JSON -- is what it is without them, bit for bit.  The per-stage
+ * JSON stays as it is: keyword hits are not serialised.  With no list created nothing new is launched or allocated.  One limit,
+ * as for lexicons: the keyword lines one rec group takes may carry 2^26 entries between them; past it RT_ERR_CAPACITY.
+ *
+ * rt_keywords_create: rt_lexicon_create's arguments, errors and messages (the entries go through the same compiler; at most
+ * RT_LEXICON_MAX_ENTRIES entries of at most RT_LEXICON_MAX_LEN ids), and min_score <= 0, fixed for the list's life: -INFINITY
+ * reports the best hits whatever they score, 0 only exact-zero hits; a NaN or a value above 0 -> RT_ERR_INVALID; more than
+ * RT_MAX_KEYWORD_LISTS lists -> RT_ERR_CAPACITY.  *list_out: the new id, 1-based, valid until rt_destroy.  Fails like
+ * rt_lexicon_create while tickets are in flight. */
+#define RT_MAX_KEYWORD_LISTS 16
+#define RT_KEYWORD_HITS 8
+typedef struct rt_keyword_hit { int32_t entry; float score; int32_t first_col, last_col; float quad[8]; } rt_keyword_hit;
+RT_API int rt_keywords_create(rt_session* s, const char* utf8, size_t len, const int32_t* ids, const int32_t* entry_lens,
+                              int n_id_entries, float min_score, int* list_out);
+/* rt_lexicon_entries / _entry / _entry_text for a keyword list; rt_keywords_min_score: NaN for an unknown id */
+RT_API int rt_keywords_entries(const rt_session* s, int list);
+RT_API int rt_keywords_entry(const rt_session* s, int list, int entry, const int32_t** ids);
+RT_API const char* rt_keywords_entry_text(const rt_session* s, int list, int entry);
+RT_API float rt_keywords_min_score(const rt_session* s, int list);
+/* The session default: the keyword list of every line of every pipeline call that follows; 0 = none (the initial state). */
+RT_API int rt_set_rec_keywords(rt_session* s, int list);
+/* rt_run_regions_patterns with one keyword list id per region as well: -1 = the session default, 0 = none, >= 1 = that list;
+ * each array, or an entry of it, may be NULL: -1 throughout.  An unknown id -> RT_ERR_INVALID naming page and region; the
+ * keywords of a page are checked behind its charsets, lexicons and patterns. */
+RT_API int rt_run_regions_keywords(rt_session* s, const uint8_t* const* rgb, const int* hs, const int* ws, int n_pages, int mem,
+                                   const float* const* quads, const int* n_quads, const int32_t* const* charsets,
+                                   const int32_t* const* lexicons, const int32_t* const* patterns,
+                                   const int32_t* const* keywords, rt_results** out);
+/* the hits of a line: their number (0 when the line had no list); *hits (optional): the hits, best first */
+RT_API int rt_results_rec_keywords(const rt_results* r, int page, int line, const rt_keyword_hit** hits);
+/* the keyword list a line was searched for (0: none) */
+RT_API int rt_results_rec_keywords_id(const rt_results* r, int page, int line);
+/* The device path of the keywords on host arrays (row gather in chunks of whole lines, the CTC FC GEMM, k_ctc_row_max,
+ * k_ctc_keyword_spot, k_ctc_keyword_topk).  z5, W, bias, N, tokens_per_line, n_lines, chunk_rows: as rt_debug_ctc_lexicon.
+ * line_kw [n_lines]: 0 = none, k >= 1 = list k, whose entries are [kw_first_entry[k - 1], kw_first_entry[k]) of the flat entry
+ * list entry_lens, their ids consecutive in entry_ids; kw_first_entry [n_kw + 1] ascends from 0, every list has at least one
+ * entry; kw_min_score [n_kw]: each list's min_score.  score_out, span_out [.][2] (both optional): the full tables, line after
+ * line, one score and one (first_col, last_col) per entry of the line's list (none for a line of list 0); -inf and (-1, -1) where
+ * infeasible.  hits_out [n_lines][RT_KEYWORD_HITS], n_hits_out [n_lines]: slots past a line's count, every hit's quad, and
+ * everything of a line of list 0 but its count of 0, come back as the caller put them. */
+RT_API int rt_debug_ctc_keywords(rt_session* s, const float* z5, const float* W, const float* bias, int N,
+                                 const int32_t* tokens_per_line, int n_lines, const int32_t* line_kw, const int32_t* entry_ids,
+                                 const int32_t* entry_lens, const int32_t* kw_first_entry, int n_kw, const float* kw_min_score,
+                                 int chunk_rows, float* score_out, int32_t* span_out, rt_keyword_hit* hits_out, int32_t* n_hits_out);
+/* The same rule on the CPU in plain fp32 loops (ctc_keyword.h), GPU-free and sessionless; same layout. */
+RT_API int rt_debug_ctc_keywords_host(const float* z5, const float* W, const float* bias, int N, const int32_t* tokens_per_line,
+                                      int n_lines, const int32_t* line_kw, const int32_t* entry_ids, const int32_t* entry_lens,
+                                      const int32_t* kw_first_entry, int n_kw, const float* kw_min_score, float* score_out,
+                                      int32_t* span_out, rt_keyword_hit* hits_out, int32_t* n_hits_out);
+/* Host-only: the page quad of the span [first_col, last_col + 1) of a line, from rt_debug_word_boxes' geometry arguments (T, W,
+ * resized_w, the line's det box after resize_both, rot180, the page's sizes) -> quad8_out in original-image coordinates: what
+ * rt_results_rec_keywords reports for a hit with that span. */
+RT_API int rt_debug_span_quad(int T, int W, int resized_w, const float* box8_after, int rot180, int after_w, int after_h, int ori_w,
+                              int ori_h, int first_col, int last_col, float* quad8_out);
 /* f32 sum of every det probability map produced in the call (keeps the network's
  * output observable when det_map_override is used) */
 RT_API double rt_results_det_checksum(const rt_results* r);

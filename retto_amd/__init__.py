@@ -180,6 +180,16 @@ class RecWord:
 
 
 @dataclass
+class KeywordHit:   # rt_keyword_hit, with the entry's text
+    entry: int
+    text: str
+    score: float          # log-ratio of the best path that contains the entry to the best path; <= 0, 0: the greedy path holds it
+    first_col: int
+    last_col: int
+    box: np.ndarray       # [4, 2] the span's page quad, TL, TR, BR, BL in original-image coordinates
+
+
+@dataclass
 class RecProcessorSingleResult:
     text: str
     score: float
@@ -200,6 +210,9 @@ class RecProcessorSingleResult:
     # line's decode is the best CTC path the pattern accepts, that path's log-probability (-inf where unmatched) and the
     # unconstrained best path's; logprob - free_logprob <= 0 is what the format cost
     pattern: Optional[Tuple[bool, float, float]] = None
+    # rec keywords (create_keywords): None when the line carried no list, else up to KEYWORD_HITS hits, best first: the list's
+    # entries spotted inside the line (retto_amd/csrc/ctc_keyword.h)
+    keywords: Optional[List["KeywordHit"]] = None
 
 
 @dataclass
@@ -659,7 +672,8 @@ class RettoSession:
             matches = self._lexicon_matches(r, page, k)
             snapped = None if matches is None else bool(lib.rt_results_rec_lexicon_snapped(r, page, k))
             rec.append(RecProcessorSingleResult(lib.rt_results_rec_text(r, page, k).decode("utf-8"), float(rs[k]), toks, words,
-                                                cands, cols, matches, snapped, self._pattern(r, page, k)))
+                                                cands, cols, matches, snapped, self._pattern(r, page, k),
+                                                self._keywords(r, page, k)))
         return RettoWorkerResult(det, cls, rec)
 
     def _dictionary(self) -> List[str]:
@@ -682,6 +696,17 @@ class RettoSession:
         if not self._hd.lib.rt_results_rec_pattern(r, page, line, C.byref(out)):
             return None
         return bool(out.matched), float(out.logprob), float(out.free_logprob)
+
+    def _keywords(self, r, page: int, line: int):
+        lib = self._hd.lib
+        kw = lib.rt_results_rec_keywords_id(r, page, line)
+        if kw <= 0:
+            return None
+        hp = C.POINTER(_lib.KeywordHit)()
+        n = lib.rt_results_rec_keywords(r, page, line, C.byref(hp))
+        return [KeywordHit(int(hp[j].entry), lib.rt_keywords_entry_text(self._hd.h, kw, hp[j].entry).decode("utf-8"),
+                           float(hp[j].score), int(hp[j].first_col), int(hp[j].last_col),
+                           np.array(list(hp[j].quad), np.float32).reshape(4, 2)) for j in range(n)]
 
     def _lexicon_matches(self, r, page: int, line: int):
         lib = self._hd.lib
@@ -816,7 +841,38 @@ class RettoSession:
         """rt_set_rec_pattern: the pattern of every line of the pipeline calls that follow; 0 = none."""
         _check(self._hd.lib.rt_set_rec_pattern(self._hd.h, int(pattern)), self._hd.h)
 
-    def run_regions_raw(self, pages, hs, ws, quads, mem=RT_MEM_HOST, charsets=None, lexicons=None, patterns=None):
+    # -- rec keywords -----------------------------------------------------------------------
+    def create_keywords(self, entries=(), ids=(), min_score=float("-inf")) -> int:
+        """rt_keywords_create: a keyword list whose entries are spotted inside every line that carries it
+        (RecProcessorSingleResult.keywords; retto_amd/csrc/ctc_keyword.h).  entries / ids: as create_lexicon's.  min_score <= 0: a
+        hit must score at least this; -inf reports the best hits whatever they score, 0 only where the greedy path holds the
+        entry.  Returns the list's id (1-based, valid for the session's life; at most MAX_KEYWORD_LISTS); see set_rec_keywords
+        and run_regions(keywords=...)."""
+        raw = bytes(_lexicon_text(entries))
+        arr, lens, n_id = _lexicon_id_arrays(ids)
+        out = C.c_int(0)
+        _check(self._hd.lib.rt_keywords_create(self._hd.h, raw, len(raw), arr, lens, n_id, float(min_score), C.byref(out)), self._hd.h)
+        return out.value
+
+    def keywords_entries(self, keywords: int) -> List[Tuple[List[int], str]]:
+        """rt_keywords_entries / _entry / _entry_text: every entry of a keyword list as (class ids, text); empty for an unknown id."""
+        lib, h = self._hd.lib, self._hd.h
+        out = []
+        for e in range(lib.rt_keywords_entries(h, int(keywords))):
+            p = C.POINTER(C.c_int32)()
+            n = lib.rt_keywords_entry(h, int(keywords), e, C.byref(p))
+            out.append(([int(p[i]) for i in range(n)], lib.rt_keywords_entry_text(h, int(keywords), e).decode("utf-8")))
+        return out
+
+    def keywords_min_score(self, keywords: int) -> float:
+        """rt_keywords_min_score: the list's min_score (NaN for an unknown id)."""
+        return float(self._hd.lib.rt_keywords_min_score(self._hd.h, int(keywords)))
+
+    def set_rec_keywords(self, keywords: int) -> None:
+        """rt_set_rec_keywords: the keyword list of every line of the pipeline calls that follow; 0 = none."""
+        _check(self._hd.lib.rt_set_rec_keywords(self._hd.h, int(keywords)), self._hd.h)
+
+    def run_regions_raw(self, pages, hs, ws, quads, mem=RT_MEM_HOST, charsets=None, lexicons=None, patterns=None, keywords=None):
         """rt_run_regions.  pages: host arrays or device pointers (ints); quads[i]: the regions of page i, anything that
         reshapes to [n_i, 8] floats (TL, TR, BR, BL in original-page coordinates).  charsets (rt_run_regions_charsets): per
         page None or one id per region (-1 = the session default, 0 = unrestricted); lexicons (rt_run_regions_lexicons): the same for
@@ -848,6 +904,12 @@ class RettoSession:
                 arr_c[i] = c.ctypes.data if len(c) else None
             return arr_c
 
+        if keywords is not None:   # (rt_run_regions_keywords: any of the four may be missing)
+            arrs = [id_arrays(v, what) if v is not None else None
+                    for v, what in ((charsets, "charset"), (lexicons, "lexicon"), (patterns, "pattern"), (keywords, "keywords"))]
+            _check(lib.rt_run_regions_keywords(h, arr_p, arr_h, arr_w, n, mem, arr_q, arr_n, arrs[0], arrs[1], arrs[2], arrs[3],
+                                               C.byref(out)), h)
+            return out
         if patterns is not None:   # (rt_run_regions_patterns: any of the three may be missing)
             arr_c = id_arrays(charsets, "charset") if charsets is not None else None
             arr_l = id_arrays(lexicons, "lexicon") if lexicons is not None else None
@@ -866,16 +928,17 @@ class RettoSession:
         _check(lib.rt_run_regions(h, arr_p, arr_h, arr_w, n, mem, arr_q, arr_n, C.byref(out)), h)
         return out
 
-    def run_regions(self, pages: Sequence[np.ndarray], quads, charsets=None, lexicons=None, patterns=None) -> List[RettoWorkerResult]:
+    def run_regions(self, pages: Sequence[np.ndarray], quads, charsets=None, lexicons=None, patterns=None,
+                    keywords=None) -> List[RettoWorkerResult]:
         """The pipeline over regions the caller already knows (rt_run_regions): quads[i] = the [n_i, 4, 2] (or [n_i, 8]) quads
         of page i in original-page coordinates, TL, TR, BR, BL.  No detector runs; line k of a page is cut from the page as it
         is by quad k clamped to the page.  det_result holds the clamped quads with score 1.0.  charsets: per page None or one
         charset id per region (create_charset; -1 = the session default, 0 = unrestricted); lexicons: the same with lexicon
         ids (create_lexicon; 0 = none); patterns: the same with pattern ids (create_pattern; 0 = none; a region may not carry
-        both a pattern and a lexicon)."""
+        both a pattern and a lexicon); keywords: the same with keyword list ids (create_keywords; 0 = none; goes with anything)."""
         pages = [np.ascontiguousarray(p, np.uint8) for p in pages]
         r = self.run_regions_raw(pages, [p.shape[0] for p in pages], [p.shape[1] for p in pages], quads, charsets=charsets,
-                                 lexicons=lexicons, patterns=patterns)
+                                 lexicons=lexicons, patterns=patterns, keywords=keywords)
         try:
             self.last_det_checksum = self._hd.lib.rt_results_det_checksum(r)
             return [self._collect(r, i) for i in range(len(pages))]

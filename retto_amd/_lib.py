@@ -62,6 +62,12 @@ class PatternResult(C.Structure):   # rt_pattern_result
     _fields_ = [("pattern", C.c_int32), ("matched", C.c_int32), ("logprob", C.c_float), ("free_logprob", C.c_float)]
 
 
+class KeywordHit(C.Structure):   # rt_keyword_hit
+    _fields_ = [("entry", C.c_int32), ("score", C.c_float), ("first_col", C.c_int32), ("last_col", C.c_int32), ("quad", C.c_float * 8)]
+
+
+MAX_KEYWORD_LISTS = 16       # RT_MAX_KEYWORD_LISTS
+KEYWORD_HITS = 8             # RT_KEYWORD_HITS
 MAX_LEXICONS = 16            # RT_MAX_LEXICONS
 LEXICON_MAX_ENTRIES = 65536  # RT_LEXICON_MAX_ENTRIES
 LEXICON_MAX_LEN = 31         # RT_LEXICON_MAX_LEN
@@ -97,6 +103,9 @@ EXPORTS = [
     "rt_debug_ctc_lexicon_align_host",
     "rt_pattern_create", "rt_pattern_info", "rt_pattern_text", "rt_set_rec_pattern", "rt_run_regions_patterns", "rt_results_rec_pattern",
     "rt_debug_pattern_compile", "rt_debug_ctc_pattern", "rt_debug_ctc_pattern_host",
+    "rt_keywords_create", "rt_keywords_entries", "rt_keywords_entry", "rt_keywords_entry_text", "rt_keywords_min_score",
+    "rt_set_rec_keywords", "rt_run_regions_keywords", "rt_results_rec_keywords", "rt_results_rec_keywords_id", "rt_debug_ctc_keywords",
+    "rt_debug_ctc_keywords_host", "rt_debug_span_quad",
     "rt_set_det_tiles", "rt_det_tiles", "rt_det_tile_plan", "rt_debug_det_tiles", "rt_debug_arena_high_water", "rt_bench_memcpy_d2d",
 ]
 
@@ -303,6 +312,26 @@ def load():
     lib.rt_debug_ctc_pattern_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
                                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
                                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.rt_keywords_create.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t, P(C.c_int32), P(C.c_int32), C.c_int, C.c_float, P(C.c_int)]
+    lib.rt_keywords_entries.argtypes = [C.c_void_p, C.c_int]
+    lib.rt_keywords_entry.argtypes = [C.c_void_p, C.c_int, C.c_int, P(P(C.c_int32))]
+    lib.rt_keywords_entry_text.argtypes = [C.c_void_p, C.c_int, C.c_int]
+    lib.rt_keywords_entry_text.restype = C.c_char_p
+    lib.rt_keywords_min_score.argtypes = [C.c_void_p, C.c_int]
+    lib.rt_keywords_min_score.restype = C.c_float
+    lib.rt_set_rec_keywords.argtypes = [C.c_void_p, C.c_int]
+    lib.rt_run_regions_keywords.argtypes = [C.c_void_p, P(C.c_void_p), P(C.c_int), P(C.c_int), C.c_int, C.c_int, P(C.c_void_p),
+                                            P(C.c_int), P(C.c_void_p), P(C.c_void_p), P(C.c_void_p), P(C.c_void_p), P(C.c_void_p)]
+    lib.rt_results_rec_keywords.argtypes = [C.c_void_p, C.c_int, C.c_int, P(P(KeywordHit))]
+    lib.rt_results_rec_keywords_id.argtypes = [C.c_void_p, C.c_int, C.c_int]
+    lib.rt_debug_ctc_keywords.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
+                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                          C.c_void_p, C.c_void_p]
+    lib.rt_debug_ctc_keywords_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
+                                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                               C.c_void_p, C.c_void_p]
+    lib.rt_debug_span_quad.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                       C.c_int, C.c_void_p]
     lib.rt_set_det_tiles.argtypes = [C.c_void_p, C.c_int, C.c_int]
     lib.rt_det_tiles.argtypes = [C.c_void_p, P(C.c_int), P(C.c_int)]
     lib.rt_det_tile_plan.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, P(C.c_int32), P(C.c_int32), C.c_int, P(C.c_int32), P(C.c_int32),

@@ -1,6 +1,6 @@
 // extern "C" surface of libretto_hip.so (include/retto_hip.h): sessions, the networks, the pipeline stages, batches, results,
 // parsers and device memory, with the feature-level debug hooks that are thin forwards into their features (rt_debug_warp_crops,
-// rt_debug_jpeg_reconstruct, rt_debug_word_boxes, rt_debug_ctc_candidates_host, rt_debug_charset_compile, rt_debug_ctc_charset_host, rt_debug_lexicon_compile, rt_debug_ctc_lexicon_host, rt_debug_ctc_lexicon_align_host).  The kernel-level diagnostics (rt_debug_set_variants,
+// rt_debug_jpeg_reconstruct, rt_debug_word_boxes, rt_debug_ctc_candidates_host, rt_debug_charset_compile, rt_debug_ctc_charset_host, rt_debug_lexicon_compile, rt_debug_ctc_lexicon_host, rt_debug_ctc_lexicon_align_host, rt_debug_ctc_keywords_host, rt_debug_span_quad).  The kernel-level diagnostics (rt_debug_set_variants,
 // rt_bench_*, and the rt_debug_* harnesses the kernel tests drive) are in api_debug.cpp; api_internal.h holds what both share.
 #include <thread>
 #include <sched.h>
@@ -89,6 +89,43 @@ std::string rt::lexicon_args_error(const float* z5, const float* W, int N, const
   }
   if (rows >= (1ll << 30)) return "the lines have " + S(rows) + " time steps, 2^30 or more";
   if (table >= (1ll << 30)) return "the loglik table has " + S(table) + " floats, 2^30 or more";
+  *rows_out = rows; *table_out = table;
+  return std::string();
+}
+std::string rt::keywords_args_error(const float* z5, const float* W, int N, const int32_t* tokens_per_line, int n_lines,
+                                    const int32_t* line_kw, const int32_t* entry_ids, const int32_t* entry_lens,
+                                    const int32_t* kw_first_entry, int n_kw, const float* kw_min_score, const rt_keyword_hit* hits_out,
+                                    const int32_t* n_hits_out, long long* rows_out, long long* table_out) {
+  auto S = [](long long v) { return std::to_string(v); };
+  if (!z5 || !W || !tokens_per_line || !line_kw || !entry_ids || !entry_lens || !kw_first_entry || !kw_min_score || !hits_out || !n_hits_out)
+    return "a required pointer is null";
+  if (n_lines <= 0) return "n_lines must be positive";
+  if (N <= 1) return "N must be at least 2 (the blank and one class)";
+  if (n_kw < 1 || n_kw > RT_MAX_KEYWORD_LISTS) return "n_kw = " + S(n_kw) + " is outside [1, RT_MAX_KEYWORD_LISTS]";
+  if (kw_first_entry[0] != 0) return "kw_first_entry[0] must be 0";
+  for (int k = 0; k < n_kw; k++) {
+    const long long n = (long long)kw_first_entry[k + 1] - kw_first_entry[k];
+    if (n < 1 || n > RT_LEXICON_MAX_ENTRIES) return "list " + S(k + 1) + " has " + S(n) + " entries, outside [1, RT_LEXICON_MAX_ENTRIES]";
+    if (!(kw_min_score[k] <= 0.0f)) return "kw_min_score[" + S(k) + "] = " + std::to_string(kw_min_score[k]) + " is not a number at most 0";
+  }
+  long long o = 0;
+  for (int j = 0; j < kw_first_entry[n_kw]; j++) {
+    if (entry_lens[j] < 1 || entry_lens[j] > RT_LEXICON_MAX_LEN)
+      return "entry " + S(j) + " has " + S(entry_lens[j]) + " ids, outside [1, RT_LEXICON_MAX_LEN]";
+    for (int i = 0; i < entry_lens[j]; i++)
+      if (entry_ids[o + i] < 1 || entry_ids[o + i] >= N)
+        return "class id " + S(entry_ids[o + i]) + " in entry " + S(j) + " is outside [1, " + S(N) + ")";
+    o += entry_lens[j];
+  }
+  long long rows = 0, table = 0;
+  for (int i = 0; i < n_lines; i++) {
+    if (tokens_per_line[i] < 0) return "line " + S(i) + " has a negative number of time steps";
+    if (line_kw[i] < 0 || line_kw[i] > n_kw) return "line " + S(i) + " names list " + S(line_kw[i]) + ", outside [0, " + S(n_kw) + "]";
+    rows += tokens_per_line[i];
+    if (line_kw[i] > 0) table += kw_first_entry[line_kw[i]] - kw_first_entry[line_kw[i] - 1];
+  }
+  if (rows >= (1ll << 30)) return "the lines have " + S(rows) + " time steps, 2^30 or more";
+  if (table > lx::MAX_GROUP_TABLE) return "the score table has " + S(table) + " entries, more than a group's table holds";
   *rows_out = rows; *table_out = table;
   return std::string();
 }
@@ -301,14 +338,14 @@ int rt_run_batch_stream(rt_session* s, const uint8_t* const* rgb, const int* hs,
   *out = nullptr;
   return guarded(s, [&] { *out = s->run_batch(rgb, hs, ws, n_pages, mem, det_map_override, cb, user); });
 }
-// the four rt_run_regions* forms: `name` is the entry's own, an array it does not take is null
+// the five rt_run_regions* forms: `name` is the entry's own, an array it does not take is null
 static int run_regions(const char* name, rt_session* s, const uint8_t* const* rgb, const int* hs, const int* ws, int n_pages, int mem,
                        const float* const* quads, const int* n_quads, const int32_t* const* charsets, const int32_t* const* lexicons,
-                       const int32_t* const* patterns, rt_results** out) {
+                       const int32_t* const* patterns, rt_results** out, const int32_t* const* keywords = nullptr) {
   RT_REQUIRE(s && out && n_pages >= 0 && (n_pages == 0 || (rgb && hs && ws && quads && n_quads)), s, std::string(name) + ": bad argument");
   RT_REQUIRE(mem == RT_MEM_HOST || mem == RT_MEM_DEVICE, s, std::string(name) + ": mem must be RT_MEM_HOST or RT_MEM_DEVICE");
   *out = nullptr;
-  return guarded(s, [&] { *out = s->run_regions(rgb, hs, ws, n_pages, mem, quads, n_quads, charsets, lexicons, patterns); });
+  return guarded(s, [&] { *out = s->run_regions(rgb, hs, ws, n_pages, mem, quads, n_quads, charsets, lexicons, patterns, keywords); });
 }
 int rt_run_regions(rt_session* s, const uint8_t* const* rgb, const int* hs, const int* ws, int n_pages, int mem,
                    const float* const* quads, const int* n_quads, rt_results** out) {
@@ -328,7 +365,13 @@ int rt_run_regions_patterns(rt_session* s, const uint8_t* const* rgb, const int*
                             const int32_t* const* lexicons, const int32_t* const* patterns, rt_results** out) {
   return run_regions("rt_run_regions_patterns", s, rgb, hs, ws, n_pages, mem, quads, n_quads, charsets, lexicons, patterns, out);
 }
-// rt_set_rec_charset / _lexicon / _pattern: the session default of one kind (rec_line_opts.h)
+int rt_run_regions_keywords(rt_session* s, const uint8_t* const* rgb, const int* hs, const int* ws, int n_pages, int mem,
+                            const float* const* quads, const int* n_quads, const int32_t* const* charsets,
+                            const int32_t* const* lexicons, const int32_t* const* patterns, const int32_t* const* keywords,
+                            rt_results** out) {
+  return run_regions("rt_run_regions_keywords", s, rgb, hs, ws, n_pages, mem, quads, n_quads, charsets, lexicons, patterns, out, keywords);
+}
+// rt_set_rec_charset / _lexicon / _pattern / _keywords: the session default of one kind (rec_line_opts.h)
 static int set_rec_default(rt_session* s, const RecKind& kind, int id) {
   const std::string name = std::string("rt_set_rec_") + kind.noun;
   RT_REQUIRE(s, s, name + ": null session");
@@ -340,6 +383,7 @@ static int set_rec_default(rt_session* s, const RecKind& kind, int id) {
 int rt_set_rec_charset(rt_session* s, int charset) { return set_rec_default(s, REC_KINDS[0], charset); }
 int rt_set_rec_lexicon(rt_session* s, int lexicon) { return set_rec_default(s, REC_KINDS[1], lexicon); }
 int rt_set_rec_pattern(rt_session* s, int pattern) { return set_rec_default(s, REC_KINDS[2], pattern); }
+int rt_set_rec_keywords(rt_session* s, int list) { return set_rec_default(s, REC_KINDS[3], list); }
 int rt_charset_create(rt_session* s, const char* utf8, size_t len, const int32_t* ids, int n_ids, int* charset_out) {
   RT_REQUIRE(s && charset_out && (utf8 || !len) && n_ids >= 0 && (ids || !n_ids), s, "rt_charset_create: bad argument");
   *charset_out = 0;
@@ -376,6 +420,35 @@ const char* rt_lexicon_entry_text(const rt_session* s, int lexicon, int entry) {
   const rt_lexicons::Host* h = lexicon_of(s, lexicon);
   if (!h || entry < 0 || entry >= (int)h->text.size()) return nullptr;
   return h->text[(size_t)entry].c_str();
+}
+int rt_keywords_create(rt_session* s, const char* utf8, size_t len, const int32_t* ids, const int32_t* entry_lens, int n_id_entries,
+                       float min_score, int* list_out) {
+  RT_REQUIRE(s && list_out && (utf8 || !len) && n_id_entries >= 0 && ((ids && entry_lens) || !n_id_entries), s,
+             "rt_keywords_create: bad argument");
+  *list_out = 0;
+  return guarded(s, [&] { *list_out = s->keywords_create(utf8, len, ids, entry_lens, n_id_entries, min_score); });
+}
+static const rt_lexicons::Host* keywords_of(const rt_session* s, int list) {
+  if (!s || !s->keywords || list < 1 || list > (int)s->keywords->host.size()) return nullptr;
+  return s->keywords->host[(size_t)list - 1].get();
+}
+int rt_keywords_entries(const rt_session* s, int list) {
+  const rt_lexicons::Host* h = keywords_of(s, list);
+  return h ? (int)h->lens.size() : 0;
+}
+int rt_keywords_entry(const rt_session* s, int list, int entry, const int32_t** ids) {
+  const rt_lexicons::Host* h = keywords_of(s, list);
+  if (!h || entry < 0 || entry >= (int)h->lens.size()) return 0;
+  if (ids) *ids = h->ids.data() + h->off[(size_t)entry];
+  return h->lens[(size_t)entry];
+}
+const char* rt_keywords_entry_text(const rt_session* s, int list, int entry) {
+  const rt_lexicons::Host* h = keywords_of(s, list);
+  if (!h || entry < 0 || entry >= (int)h->text.size()) return nullptr;
+  return h->text[(size_t)entry].c_str();
+}
+float rt_keywords_min_score(const rt_session* s, int list) {
+  return keywords_of(s, list) ? s->keywords->min_score[(size_t)list - 1] : NAN;
 }
 int rt_pattern_create(rt_session* s, const char* utf8, size_t len, int* pattern_out) {
   RT_REQUIRE(s && pattern_out && (utf8 || len == 0), s, "rt_pattern_create: null argument");
@@ -928,6 +1001,83 @@ int rt_debug_ctc_lexicon_align_host(const float* z5, const float* W, const float
   }
   return lexicon_host(z5, W, bias, N, tokens_per_line, n_lines, line_lex, entry_ids, entry_lens, lex_first_entry, n_lex, loglik_out,
                       matches_out, n_matches_out, lex_min_post, idx, prob, snapped_out, vit_out);
+}
+static_assert(RT_MAX_KEYWORD_LISTS == kw::MAX_LISTS && RT_KEYWORD_HITS == kw::HITS, "the RT_KEYWORD_* limits and kw:: must agree");
+static_assert(sizeof(rt_keyword_hit) == sizeof(kw::Hit) && offsetof(rt_keyword_hit, score) == offsetof(kw::Hit, score) &&
+                  offsetof(rt_keyword_hit, first_col) == offsetof(kw::Hit, first_col) && offsetof(rt_keyword_hit, last_col) == offsetof(kw::Hit, last_col) &&
+                  offsetof(rt_keyword_hit, quad) == offsetof(kw::Hit, quad), "rt_keyword_hit and kw::Hit must share one layout");
+int rt_results_rec_keywords(const rt_results* r, int page, int line, const rt_keyword_hit** hits) {
+  auto* p = RT_PAGE(r, page);
+  if (!p || line < 0 || (size_t)line >= p->kw_n.size()) return 0;
+  if (hits) *hits = reinterpret_cast<const rt_keyword_hit*>(p->kw_hits.data()) + (size_t)line * kw::HITS;
+  return p->kw_n[(size_t)line];
+}
+int rt_results_rec_keywords_id(const rt_results* r, int page, int line) {
+  auto* p = RT_PAGE(r, page);
+  if (!p || line < 0 || (size_t)line >= p->kw_id.size()) return 0;
+  return p->kw_id[(size_t)line];
+}
+int rt_debug_ctc_keywords_host(const float* z5, const float* W, const float* bias, int N, const int32_t* tokens_per_line, int n_lines,
+                               const int32_t* line_kw, const int32_t* entry_ids, const int32_t* entry_lens,
+                               const int32_t* kw_first_entry, int n_kw, const float* kw_min_score, float* score_out, int32_t* span_out,
+                               rt_keyword_hit* hits_out, int32_t* n_hits_out) {
+  long long rows = 0, table = 0;
+  const std::string bad = keywords_args_error(z5, W, N, tokens_per_line, n_lines, line_kw, entry_ids, entry_lens, kw_first_entry, n_kw,
+                                              kw_min_score, hits_out, n_hits_out, &rows, &table);
+  if (!bad.empty()) {
+    rt::create_error() = "rt_debug_ctc_keywords_host: " + bad;
+    return RT_ERR_INVALID;
+  }
+  try {
+    const int D = 120;
+    std::vector<long long> id_off((size_t)kw_first_entry[n_kw] + 1, 0);
+    for (int j = 0; j < kw_first_entry[n_kw]; j++) id_off[(size_t)j + 1] = id_off[(size_t)j] + entry_lens[j];
+    std::vector<float> logits, rmax, row;
+    std::vector<int32_t> span;
+    long long o = 0, out = 0;
+    for (int i = 0; i < n_lines; i++) {
+      const int T = tokens_per_line[i];
+      n_hits_out[i] = 0;
+      if (line_kw[i] > 0) {
+        logits.assign((size_t)std::max(T, 1) * N, 0.0f); rmax.assign((size_t)std::max(T, 1), 0.0f);
+        for (int t = 0; t < T; t++) {
+          cs::row_logits(z5 + (size_t)(o + t) * D, D, W, bias, N, logits.data() + (size_t)t * N);
+          rmax[(size_t)t] = kw::row_max(logits.data() + (size_t)t * N, N);
+        }
+        const int e0 = kw_first_entry[line_kw[i] - 1], n = kw_first_entry[line_kw[i]] - e0;
+        row.assign((size_t)n, 0.0f); span.assign((size_t)2 * n, -1);
+        for (int e = 0; e < n; e++)
+          row[(size_t)e] = kw::entry_spot(logits.data(), N, rmax.data(), T, entry_ids + id_off[(size_t)(e0 + e)], entry_lens[e0 + e],
+                                          span.data() + 2 * (size_t)e);
+        n_hits_out[i] = kw::line_hits(row.data(), span.data(), n, kw_min_score[line_kw[i] - 1],
+                                      reinterpret_cast<kw::Hit*>(hits_out) + (size_t)i * kw::HITS);
+        if (score_out) memcpy(score_out + out, row.data(), (size_t)n * sizeof(float));
+        if (span_out) memcpy(span_out + 2 * out, span.data(), (size_t)2 * n * sizeof(int32_t));
+        out += n;
+      }
+      o += T;
+    }
+    return RT_OK;
+  } catch (const std::exception&) {
+    return RT_ERR_BACKEND;
+  }
+}
+int rt_debug_span_quad(int T, int W, int resized_w, const float* box8_after, int rot180, int after_w, int after_h, int ori_w, int ori_h,
+                       int first_col, int last_col, float* quad8_out) {
+  if (!box8_after || !quad8_out || T <= 0 || W <= 0 || resized_w <= 0 || after_w <= 0 || after_h <= 0 || ori_w <= 0 || ori_h <= 0)
+    return RT_ERR_INVALID;
+  if (first_col < 0 || last_col < first_col || last_col >= T) return RT_ERR_INVALID;
+  // the crop as plan_crops (session.cpp) derives it, as rt_debug_word_boxes
+  const gm::CropDims cd = gm::crop_dims(box8_after);
+  if (cd.w <= 0 || cd.h <= 0) return RT_ERR_IMAGE;
+  wb::WordGeom g;
+  if (!gm::projection_inverse(box8_after, cd.cw, cd.ch, g.inv)) return RT_ERR_IMAGE;
+  g.T = T; g.W = W; g.resized_w = resized_w;
+  g.w_c = cd.rot ? cd.h : cd.w; g.h_c = cd.rot ? cd.w : cd.h;
+  g.rot270 = cd.rot; g.w = cd.w; g.h = cd.h; g.cw = cd.cw; g.ch = cd.ch;
+  kw::span_quad(first_col, last_col, g, rot180 ? 1 : 0, quad8_out);
+  gm::scale_and_clip(quad8_out, (double)after_w, (double)after_h, (double)ori_w, (double)ori_h);
+  return RT_OK;
 }
 static_assert(RT_MAX_PATTERNS == pt::MAX_PATTERNS && RT_PATTERN_MAX_STATES == pt::MAX_STATES && RT_PATTERN_MAX_PAIRS == pt::MAX_PAIRS &&
                   RT_PATTERN_MAX_BYTES == pt::MAX_BYTES, "the RT_PATTERN_* limits and pt:: must agree");

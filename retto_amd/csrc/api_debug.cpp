@@ -388,12 +388,13 @@ struct TailHook {
   RecTailPlan plan; rt_session::RecTail t{};
   TailHook(rt_session* s_, const float* z5, const float* W, const float* bias, int N, long long rows, const int32_t* tokens_per_line,
            int n_lines, const int32_t* line_set, const int32_t* line_lex, const lx::Tables& tb, const float* snap_min, const int32_t* idx,
-           const float* prob, int K, int chunk_rows, const int32_t* line_pat = nullptr, const pt::Tables* ptb = nullptr)
+           const float* prob, int K, int chunk_rows, const int32_t* line_pat = nullptr, const pt::Tables* ptb = nullptr,
+           const int32_t* line_kw = nullptr, const lx::Tables* ktb = nullptr)
       : s(s_), nr((size_t)std::max<long long>(rows, 1)) {
     s->begin_call();
     std::vector<long long> off((size_t)n_lines + 1, 0);
     std::partial_sum(tokens_per_line, tokens_per_line + n_lines, off.begin() + 1);   // (below 2^30: the entries' own check)
-    plan = rec_tail_plan(off.data(), 0, n_lines, line_set, line_lex, tb, snap_min, line_pat, ptb);
+    plan = rec_tail_plan(off.data(), 0, n_lines, line_set, line_lex, tb, snap_min, line_pat, ptb, line_kw, ktb);
     core.classes = N;
     if (plan.needs_z5(K)) {
       core.fc = pack_linear(ws, W, bias, core.D, N);
@@ -563,6 +564,48 @@ RT_API int rt_debug_ctc_pattern(rt_session* s, const float* z5, const float* W, 
     DevBufs::download(idx, t.idx, (size_t)rows); DevBufs::download(prob, t.prob, (size_t)rows);
     DevBufs::download(matched_out, t.patm, (size_t)n_lines); DevBufs::download(vit_out, t.patv, (size_t)n_lines);
     DevBufs::download(logprob_out, t.patlp, (size_t)n_lines); DevBufs::download(free_out, t.patfree, (size_t)n_lines);
+  });
+}
+
+// Rec keywords' device path on host arrays (ctc_keyword.h); the list tables are built as rt_keywords_create builds them (lx::Tables).
+RT_API int rt_debug_ctc_keywords(rt_session* s, const float* z5, const float* W, const float* bias, int N,
+                                 const int32_t* tokens_per_line, int n_lines, const int32_t* line_kw, const int32_t* entry_ids,
+                                 const int32_t* entry_lens, const int32_t* kw_first_entry, int n_kw, const float* kw_min_score,
+                                 int chunk_rows, float* score_out, int32_t* span_out, rt_keyword_hit* hits_out, int32_t* n_hits_out) {
+  long long rows = 0, table = 0;
+  RT_REQUIRE(s, s, "rt_debug_ctc_keywords: null session");
+  const std::string bad = keywords_args_error(z5, W, N, tokens_per_line, n_lines, line_kw, entry_ids, entry_lens, kw_first_entry, n_kw,
+                                              kw_min_score, hits_out, n_hits_out, &rows, &table);
+  RT_REQUIRE(bad.empty(), s, "rt_debug_ctc_keywords: " + bad);
+  RT_REQUIRE(chunk_rows >= 0, s, "rt_debug_ctc_keywords: chunk_rows is negative");
+  return guarded(s, [&] {
+    lx::Tables tb;
+    long long io = 0;
+    for (int k = 0; k < n_kw; k++) {
+      const int e0 = kw_first_entry[k], n = kw_first_entry[k + 1] - e0;
+      tb.add(entry_ids + io, entry_lens + e0, n);
+      for (int j = 0; j < n; j++) io += entry_lens[e0 + j];
+    }
+    TailHook h(s, z5, W, bias, N, rows, tokens_per_line, n_lines, nullptr, nullptr, lx::Tables(), nullptr, nullptr, nullptr, 0, chunk_rows,
+               nullptr, nullptr, line_kw, &tb);
+    for (int i = 0; i < n_lines; i++)   // (a line without a list has no hit)
+      if (line_kw[i] <= 0) n_hits_out[i] = 0;
+    rt_session::RecTail& t = h.t;
+    t.d_kw = lx::DevTables{h.bufs.upload(tb.ids.data(), tb.ids.size()), h.bufs.upload(tb.entries.data(), tb.entries.size()),
+                           h.bufs.upload(tb.order.data(), tb.order.size()), h.bufs.upload(tb.lex.data(), tb.lex.size())};
+    t.d_kw_min = h.bufs.upload(kw_min_score, (size_t)n_kw);
+    // (what the kernels write starts as the caller's values: a slot they leave alone comes back untouched)
+    const size_t tn = (size_t)std::max<long long>(table, 1);
+    t.kwscore = h.bufs.alloc<float>(tn); t.kwspan = h.bufs.alloc<int>(2 * tn);
+    if (score_out) DevBufs::put(t.kwscore, score_out, (size_t)table);
+    if (span_out) DevBufs::put(t.kwspan, span_out, 2 * (size_t)table);
+    t.kwh = h.bufs.upload(reinterpret_cast<const kw::Hit*>(hits_out), (size_t)n_lines * kw::HITS);
+    t.kwn = h.bufs.upload(n_hits_out, (size_t)n_lines);
+    h.run();
+    if (score_out) DevBufs::download(score_out, t.kwscore, (size_t)table);
+    if (span_out) DevBufs::download(span_out, t.kwspan, 2 * (size_t)table);
+    DevBufs::download(reinterpret_cast<kw::Hit*>(hits_out), t.kwh, (size_t)n_lines * kw::HITS);
+    DevBufs::download(n_hits_out, t.kwn, (size_t)n_lines);
   });
 }
 

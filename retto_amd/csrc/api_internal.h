@@ -31,6 +31,11 @@ std::string lexicon_args_error(const float* z5, const float* W, int N, const int
                                const int32_t* line_lex, const int32_t* entry_ids, const int32_t* entry_lens,
                                const int32_t* lex_first_entry, int n_lex, const rt_lexicon_match* matches_out,
                                const int32_t* n_matches_out, long long* rows_out, long long* table_out);
+// what both rt_debug_ctc_keywords forms require of their arguments, likewise; *table_out = the entries of the score / span tables
+std::string keywords_args_error(const float* z5, const float* W, int N, const int32_t* tokens_per_line, int n_lines,
+                                const int32_t* line_kw, const int32_t* entry_ids, const int32_t* entry_lens,
+                                const int32_t* kw_first_entry, int n_kw, const float* kw_min_score, const rt_keyword_hit* hits_out,
+                                const int32_t* n_hits_out, long long* rows_out, long long* table_out);
 // what both rt_debug_ctc_lexicon_align forms require beyond lexicon_args_error (n_lex already checked), likewise
 std::string lexicon_align_args_error(const float* lex_min_post, int n_lex, const int32_t* idx, const float* prob,
                                      const int32_t* snapped_out, const float* vit_out);

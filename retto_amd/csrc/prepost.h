@@ -7,6 +7,7 @@
 #include "word_boxes.h"
 #include "ctc_candidates.h"
 #include "ctc_charset.h"
+#include "ctc_keyword.h"
 #include "ctc_lexicon.h"
 #include "ctc_lexicon_align.h"
 #include "ctc_pattern.h"
@@ -120,6 +121,17 @@ void ctc_lexicon_forward(hipStream_t st, const float* logits, int ld, const floa
 // counts[line.slot] (slots of a line's row past its count are not written)
 void ctc_lexicon_topk(hipStream_t st, const lx::Line* lines, int n_lines, const lx::Lex* lex, const float* loglik,
                       lx::Match* matches, int* counts);
+// Rec keywords (ctc_keyword.h): every entry of the keyword list of each of lines[0..n_lines) spotted inside the line (one chunk,
+// resident as for ctc_lexicon_forward, with rmax of its rows: ctc_row_max) -> score[line.out + entry] and span[2 * (line.out +
+// entry) ..] = its first and last column; -inf and (-1, -1) where the entry is infeasible for the line's T.  max_waves: the
+// largest lx::waves_of over the lists of these lines.  lex / entries / order / ids: the lists' lx::Tables on the device.
+void ctc_keyword_spot(hipStream_t st, const float* logits, int ld, const float* rmax, const kw::Line* lines, int n_lines,
+                      int chunk_row0, int max_waves, const lx::Lex* lex, const lx::Entry* entries, const int* order, const int* ids,
+                      float* score, int* span);
+// one wave64 per line over its score row: up to kw::HITS hits that pass min_score[line.lex] -> hits[line.slot * kw::HITS ...]
+// (entry, score, first_col, last_col; never the quad), their number -> counts[line.slot] (slots past the count are not written)
+void ctc_keyword_topk(hipStream_t st, const kw::Line* lines, int n_lines, const lx::Lex* lex, const float* min_score,
+                      const float* score, const int* span, kw::Hit* hits, int* counts);
 // Lexicon snap (ctc_lexicon_align.h): one wave64 per line of lines[0..n_lines) (one chunk, resident as for ctc_lexicon_forward,
 // after ctc_lexicon_topk over the same lines).  snapped[line.slot] <- 0 / 1 for every line; a line whose lexicon has
 // min_post[line.lex] > 0 and whose match 0 reaches it has its winner aligned (CTC Viterbi) and its rows rows[line.row0 ..

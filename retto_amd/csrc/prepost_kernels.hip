@@ -665,6 +665,122 @@ void ctc_lexicon_topk(hipStream_t st, const lx::Line* lines, int n_lines, const 
   RT_LAUNCH(k_ctc_lexicon_topk, dim3(n_lines), dim3(64), 0, st, lines, lex, loglik, matches, counts);
 }
 
+// Rec keywords (ctc_keyword.h): k_ctc_lexicon_forward's sibling.  Workgroup (w, j) is one wave64: wave w of the keyword list of
+// chunk line j, through the list's three buckets in turn (4 entries of 16 lanes, 2 of 32, 1 of 64; an entry of L ids has 2 L - 1
+// states, which fit the lexicon's widths); waves past the list's count leave at once.  One lane is one state: its (v, a) live in
+// two registers and the neighbours' come from __shfl_up within the group's width.  The chain has no expf or logf: a step is two
+// compares and one add; the gathered logit l[t][cls(s)] and rmax[t] do not depend on it and are loaded AHEAD steps early into a
+// register ring (static indices: the loop is unrolled by AHEAD).  Every lane of the wave runs the same T steps -- a group
+// without an entry and the lanes past an entry's states carry (-inf, -1) along and read column 0 of the line's own rows -- so
+// no shuffle is ever divergent.  Every lane keeps the running end of its own state; the one of state 2 L - 2 is the entry's,
+// and lane 0 of a group that holds an entry fetches it and writes score[line.out + entry] and the two int32 of its span.
+__global__ __launch_bounds__(64) void k_ctc_keyword_spot(const float* __restrict__ logits, int ld, const float* __restrict__ rmax,
+                                                         const kw::Line* __restrict__ lines, int chunk_row0,
+                                                         const lx::Lex* __restrict__ lex, const lx::Entry* __restrict__ entries,
+                                                         const int* __restrict__ order, const int* __restrict__ ids,
+                                                         float* __restrict__ score, int* __restrict__ span) {
+  constexpr int AHEAD = 4;
+  const int lane = threadIdx.x;
+  const kw::Line ln = lines[blockIdx.y];
+  const lx::Lex X = lex[ln.lex];
+  const int w16 = (X.n16 + 3) / 4, w32 = (X.n32 + 1) / 2, n64 = X.n - X.n16 - X.n32;
+  int w = blockIdx.x, width, k, bucket_n, bucket_first;
+  if (w < w16) { width = 16; k = 4 * w + (lane >> 4); bucket_n = X.n16; bucket_first = 0; }
+  else if ((w -= w16) < w32) { width = 32; k = 2 * w + (lane >> 5); bucket_n = X.n32; bucket_first = X.n16; }
+  else if ((w -= w32) < n64) { width = 64; k = w; bucket_n = n64; bucket_first = X.n16 + X.n32; }
+  else return;
+  const bool live = k < bucket_n;
+  const int e = live ? order[X.first + bucket_first + k] : 0;   // (list-local entry index)
+  const lx::Entry E = live ? entries[X.first + e] : lx::Entry{0, 1, 1};
+  const int s = lane & (width - 1), S = 2 * E.len - 1, T = ln.T;
+  const bool mine = live && s < S;
+  const int cls = mine ? kw::cls_of(ids + E.off, s) : 0;
+  const bool skip = mine && kw::skip_of(ids + E.off, s);
+  const float* col = logits + (long long)(ln.row0 - chunk_row0) * ld + cls;
+  const float* rm = rmax + (ln.row0 - chunk_row0);
+  float lq[AHEAD], mq[AHEAD];
+#pragma unroll
+  for (int j = 0; j < AHEAD; j++) { lq[j] = j < T ? col[(long long)j * ld] : 0.0f; mq[j] = j < T ? rm[j] : 0.0f; }
+  kw::Cell c{-INFINITY, -1};
+  float best = -INFINITY; int first = -1, last = -1;
+  for (int t0 = 0; t0 < T; t0 += AHEAD) {
+#pragma unroll
+    for (int j = 0; j < AHEAD; j++) {
+      const int t = t0 + j;
+      if (t < T) {   // (wave-uniform)
+        const float d = lq[j] - mq[j];
+        if (t + AHEAD < T) { lq[j] = col[(long long)(t + AHEAD) * ld]; mq[j] = rm[t + AHEAD]; }
+        const kw::Cell p1{__shfl_up(c.v, 1, width), __shfl_up(c.a, 1, width)}, p2{__shfl_up(c.v, 2, width), __shfl_up(c.a, 2, width)};
+        const kw::Cell nx = t == 0 ? (s == 0 ? kw::Cell{d, 0} : kw::Cell{-INFINITY, -1}) : kw::step(s, t, c, p1, p2, skip, d);
+        c = mine ? nx : kw::Cell{-INFINITY, -1};
+        if (c.v > best) { best = c.v; first = c.a; last = t; }
+      }
+    }
+  }
+  const float fs = __shfl(best, S - 1, width);
+  const int ff = __shfl(first, S - 1, width), fl = __shfl(last, S - 1, width);
+  if (live && s == 0) {
+    const bool feasible = T >= E.need;
+    score[ln.out + e] = feasible ? fs : -INFINITY;
+    span[2 * (ln.out + e)] = feasible ? ff : -1; span[2 * (ln.out + e) + 1] = feasible ? fl : -1;
+  }
+}
+void ctc_keyword_spot(hipStream_t st, const float* logits, int ld, const float* rmax, const kw::Line* lines, int n_lines,
+                      int chunk_row0, int max_waves, const lx::Lex* lex, const lx::Entry* entries, const int* order, const int* ids,
+                      float* score, int* span) {
+  if (n_lines <= 0 || max_waves <= 0) return;
+  RT_LAUNCH(k_ctc_keyword_spot, dim3(max_waves, n_lines), dim3(64), 0, st, logits, ld, rmax, lines, chunk_row0, lex, entries, order,
+            ids, score, span);
+}
+
+// One wave64 per keyword line over its score row: each lane keeps a best-first list of kw::HITS entries that pass the list's
+// min_score (kw::passes: never a -inf, never a NaN); then kw::HITS rounds of a wave arg-max over the list heads (ties to the
+// lower entry index), lane r keeping round r's winner and writing hit r: entry, score and the span's two columns, never the
+// quad.  Lane 0 writes the count.
+__global__ __launch_bounds__(64) void k_ctc_keyword_topk(const kw::Line* __restrict__ lines, const lx::Lex* __restrict__ lex,
+                                                         const float* __restrict__ min_score, const float* __restrict__ score,
+                                                         const int* __restrict__ span, kw::Hit* __restrict__ hits,
+                                                         int* __restrict__ counts) {
+  constexpr int N = kw::HITS;
+  const int lane = threadIdx.x;
+  const kw::Line ln = lines[blockIdx.x];
+  const int n = lex[ln.lex].n;
+  const float floor_ = min_score[ln.lex];
+  const float* x = score + ln.out;
+  float L[N]; int I[N];
+#pragma unroll
+  for (int j = 0; j < N; j++) { L[j] = -INFINITY; I[j] = cc::EMPTY_ID; }
+  for (int e = lane; e < n; e += 64) {
+    const float v = x[e];
+    if (kw::passes(v, floor_)) cc::list_insert(L, I, v, e);
+  }
+  float ol = 0.0f; int oi = cc::EMPTY_ID, cnt = 0;
+  for (int r = 0; r < N; r++) {
+    float wl = L[0]; int wi = I[0];
+    for (int o = 32; o >= 1; o >>= 1) {
+      const float l2 = __shfl_xor(wl, o); const int i2 = __shfl_xor(wi, o);
+      if (cc::better(l2, i2, wl, wi)) { wl = l2; wi = i2; }
+    }
+    if (lane == r) { ol = wl; oi = wi; }
+    if (wi != cc::EMPTY_ID) cnt++;
+    if (wi != cc::EMPTY_ID && I[0] == wi) {
+#pragma unroll
+      for (int j = 0; j + 1 < N; j++) { L[j] = L[j + 1]; I[j] = I[j + 1]; }
+      L[N - 1] = -INFINITY; I[N - 1] = cc::EMPTY_ID;
+    }
+  }
+  if (lane < N && oi != cc::EMPTY_ID) {
+    kw::Hit& h = hits[(long long)ln.slot * N + lane];
+    h.entry = oi; h.score = ol; h.first_col = span[2 * (ln.out + oi)]; h.last_col = span[2 * (ln.out + oi) + 1];
+  }
+  if (lane == 0) counts[ln.slot] = cnt;
+}
+void ctc_keyword_topk(hipStream_t st, const kw::Line* lines, int n_lines, const lx::Lex* lex, const float* min_score,
+                      const float* score, const int* span, kw::Hit* hits, int* counts) {
+  if (n_lines <= 0) return;
+  RT_LAUNCH(k_ctc_keyword_topk, dim3(n_lines), dim3(64), 0, st, lines, lex, min_score, score, span, hits, counts);
+}
+
 // Lexicon snap (ctc_lexicon_align.h).  One wave64 per lexicon line of one chunk, after k_ctc_lexicon_topk has written the line's
 // matches: the wave applies the snap condition to match 0, writes snapped[slot] (0 or 1, for every line it sees) and leaves
 // unless the line snaps.  Then lane s owns state s of the winner (S <= 63) and the forward pass is k_ctc_lexicon_forward's

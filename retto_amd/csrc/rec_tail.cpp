@@ -243,6 +243,7 @@ void rt_session::rec_tail(const RecTailPlan& p, const SvtrCore& core, const RecT
                    t.wb->n_words, t.wb->words);
   }
   if (!p.snap) ctc_lexicon(p, core, t);
+  if (p.has_kw()) ctc_keywords(p, core, t);
   if (t.cand_k > 0) ctc_candidates(core, t, p.rows, d_row_set);   // (before the caller rewinds the scratch arena z5 lives in)
 }
 
@@ -337,6 +338,30 @@ void rt_session::ctc_pattern(const RecTailPlan& p, const SvtrCore& core, const R
   });
 }
 
+void rt_session::ctc_keywords(const RecTailPlan& p, const SvtrCore& core, const RecTail& t) {
+  const int n_lines = (int)p.klines.size();
+  if (n_lines <= 0) return;
+  const kw::Line* d_lines = staged(*this, p.klines); const int* d_rows = staged(*this, p.krows);
+  const size_t table = (size_t)std::max<long long>(p.ktable, 1);
+  float* score = t.kwscore ? t.kwscore : scratch.alloc<float>(table);
+  int* span = t.kwspan ? t.kwspan : scratch.alloc<int>(2 * table);
+  const lx::DevTables& X = t.d_kw;
+  const int cap = line_chunks(p.klines, t, no_chunk_work);
+  LogitsChunk lc(*this, core, t.z5, cap);
+  float* rmax = scratch.alloc<float>((size_t)cap);
+  line_chunks(p.klines, t, [&](int i0, int i1, int r0, int m) {   // (the chunks share rmax too)
+    if (m > 0) {
+      lc.run(d_rows + r0, m);
+      ProfScope ps(&prof, st, "ctc_row_max");
+      pp::ctc_row_max(st, lc.logits, lc.ld, core.classes, m, rmax);
+    }
+    ProfScope ps(&prof, st, "ctc_keyword_spot");
+    pp::ctc_keyword_spot(st, lc.logits, lc.ld, rmax, d_lines + i0, i1 - i0, r0, p.kmax_waves, X.lex, X.entries, X.order, X.ids, score, span);
+  });
+  ProfScope ps(&prof, st, "ctc_keyword_topk");
+  pp::ctc_keyword_topk(st, d_lines, n_lines, X.lex, t.d_kw_min, score, span, t.kwh, t.kwn);
+}
+
 int rt_session::charset_create(const char* utf8, size_t len, const int32_t* ids, int n_ids) {
   rt_charsets& C = *charsets;
   if ((int)C.ids.size() >= cs::MAX_SETS)
@@ -377,6 +402,39 @@ int rt_session::lexicon_create(const char* utf8, size_t len, const int32_t* ids,
   upload_table(&fresh.d.lex, tb.lex);
   std::swap(X.d, fresh.d);   // (the old tables leave with `fresh`)
   X.tb = std::move(tb);
+  X.host.push_back(std::move(h));
+  return (int)X.host.size();
+}
+
+int rt_session::keywords_create(const char* utf8, size_t len, const int32_t* ids, const int32_t* entry_lens, int n_id_entries,
+                                float min_score) {
+  rt_keywords& X = *keywords;
+  if (!(min_score <= 0.0f))   // (a NaN fails)
+    throw RtError(RT_ERR_INVALID, "rt_keywords_create: min_score " + std::to_string(min_score) + " is not a number at most 0");
+  if ((int)X.host.size() >= kw::MAX_LISTS)
+    throw RtError(RT_ERR_CAPACITY, "rt_keywords_create: the session holds RT_MAX_KEYWORD_LISTS (" + std::to_string(kw::MAX_LISTS) + ") keyword lists already");
+  std::unique_ptr<rt_lexicons::Host> h(new rt_lexicons::Host());
+  compile_lexicon(dict, utf8, len, ids, entry_lens, n_id_entries, h->ids, h->lens);
+  int o = 0;
+  for (int n : h->lens) {
+    h->off.push_back(o);
+    std::string t;
+    for (int i = 0; i < n; i++) t += dict[(size_t)h->ids[(size_t)(o + i)]];
+    h->text.push_back(std::move(t));
+    o += n;
+  }
+  lx::Tables tb = X.tb;
+  tb.add(h->ids.data(), h->lens.data(), (int)h->lens.size());
+  std::vector<float> mins = X.min_score;
+  mins.push_back(min_score);
+  // the device tables are rebuilt whole (blocking copies; no lane has work queued: this is a guarded call and every pipeline
+  // call ends with its streams drained)
+  RT_HIP_CHECK(hipSetDevice(device));
+  rt_keywords fresh;   // (frees what it holds if a copy below throws)
+  upload_table(&fresh.d.ids, tb.ids); upload_table(&fresh.d.entries, tb.entries); upload_table(&fresh.d.order, tb.order);
+  upload_table(&fresh.d.lex, tb.lex); upload_table(&fresh.d_min, mins);
+  std::swap(X.d, fresh.d); std::swap(X.d_min, fresh.d_min);   // (the old tables leave with `fresh`)
+  X.tb = std::move(tb); X.min_score = std::move(mins);
   X.host.push_back(std::move(h));
   return (int)X.host.size();
 }

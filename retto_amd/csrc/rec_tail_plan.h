@@ -1,11 +1,12 @@
 // What the CTC tail of one rec group works on (rt_session::rec_tail, rec_tail.cpp), decided on the host in one place: the charset
-// row tables, the lexicon lines with their rows and table, and the three questions whose answers order the launches.  The
+// row tables, the lexicon, pattern and keyword lines with their rows and tables, and the questions whose answers order the launches.  The
 // pipeline (rec_groups) and the debug hooks (rt_debug_ctc_*) both go through it.  Plain C++ as lc_plan.h: built and checked
 // without a GPU (tests/test_rec_tail_plan_cpu.py).
 #pragma once
 #include <algorithm>
 #include <vector>
 
+#include "ctc_keyword.h"
 #include "ctc_lexicon.h"
 #include "ctc_pattern.h"
 #include "rec_line_opts.h"
@@ -33,13 +34,21 @@ struct RecTailPlan {
   std::vector<pt::Line> plines; std::vector<int> prows;
   int max_P = 0, max_S = 0; long long bp_codes = 0;
   bool has_pat() const { return !plines.empty(); }
+  // rec keywords (ctc_keyword.h): the group's keyword lines in line order (row0 = the sum of the earlier ones' T, lex = the
+  // 0-based list, slot = the line's index in the call, out = the sum of the earlier ones' list sizes), their rows line after
+  // line, the entries of the score / span table (rec_groups refuses a group whose table does not fit) and the largest
+  // lx::waves_of over the lines' lists
+  std::vector<kw::Line> klines; std::vector<int> krows;
+  long long ktable = 0; int kmax_waves = 0;
+  bool has_kw() const { return !klines.empty(); }   // (a keyword line without a time step counts)
+  bool ktable_fits() const { return ktable <= lx::MAX_GROUP_TABLE; }
   // the net must hand out the head's input: some logits are recomputed
-  bool needs_z5(int cand_k) const { return cand_k > 1 || !crows.empty() || has_lex() || has_pat(); }
+  bool needs_z5(int cand_k) const { return cand_k > 1 || !crows.empty() || has_lex() || has_pat() || has_kw(); }
 };
 
 // The session's stores the plan reads: lexicon k is lex.lex[k - 1] and snaps where snap_min[k - 1] > 0 (null: never); pattern k is
-// pat->pats[k - 1] (null: no line has one)
-struct RecStores { const lx::Tables& lex; const float* snap_min; const pt::Tables* pat; };
+// pat->pats[k - 1] (null: no line has one); keyword list k is kw->lex[k - 1] (null: no line has one)
+struct RecStores { const lx::Tables& lex; const float* snap_min; const pt::Tables* pat; const lx::Tables* kw = nullptr; };
 
 // Lines [l0, l1) of a call: line li has the time steps [tok_off[li], tok_off[li + 1]) and the options line_opts[li] (rec_line_opts.h)
 inline RecTailPlan rec_tail_plan(const long long* tok_off, int l0, int l1, const RecLineOpts* line_opts, const RecStores& st) {
@@ -63,6 +72,13 @@ inline RecTailPlan rec_tail_plan(const long long* tok_off, int l0, int l1, const
       p.max_P = std::max(p.max_P, a.P); p.max_S = std::max(p.max_S, a.S);
       if (pt::bp_codes(T, a.P, a.S) > pt::BP_LDS) p.bp_codes += pt::bp_codes(T, a.P, a.S);
     }
+    if (st.kw && o.keywords > 0) {
+      const lx::Lex& x = st.kw->lex[(size_t)o.keywords - 1];
+      p.klines.push_back(kw::Line{(int)p.krows.size(), T, o.keywords - 1, li, p.ktable});
+      for (int t = 0; t < T; t++) p.krows.push_back(r0 + t);
+      p.ktable += x.n;
+      p.kmax_waves = std::max(p.kmax_waves, lx::waves_of(x));
+    }
     if (o.lexicon <= 0) continue;
     const lx::Lex& x = st.lex.lex[(size_t)o.lexicon - 1];
     p.lines.push_back(lx::Line{(int)p.lrows.size(), T, o.lexicon - 1, li, p.table});
@@ -74,12 +90,14 @@ inline RecTailPlan rec_tail_plan(const long long* tok_off, int l0, int l1, const
   return p;
 }
 // The same from one optional id array per kind (null: no line has one), as the rt_debug_ctc_* hooks' ABI and the plan tests'
-// drivers hold them: lexicon k is tb.lex[k - 1], snap_min and ptb as RecStores'
+// drivers hold them: lexicon k is tb.lex[k - 1], snap_min, ptb and ktb as RecStores'
 inline RecTailPlan rec_tail_plan(const long long* tok_off, int l0, int l1, const int* line_set, const int* line_lex, const lx::Tables& tb,
-                                 const float* snap_min, const int* line_pat = nullptr, const pt::Tables* ptb = nullptr) {
+                                 const float* snap_min, const int* line_pat = nullptr, const pt::Tables* ptb = nullptr,
+                                 const int* line_kw = nullptr, const lx::Tables* ktb = nullptr) {
   std::vector<RecLineOpts> opts((size_t)l1);
-  for (int li = l0; li < l1; li++) opts[(size_t)li] = {line_set ? line_set[li] : 0, line_lex ? line_lex[li] : 0, line_pat ? line_pat[li] : 0};
-  return rec_tail_plan(tok_off, l0, l1, opts.data(), RecStores{tb, snap_min, ptb});
+  for (int li = l0; li < l1; li++)
+    opts[(size_t)li] = {line_set ? line_set[li] : 0, line_lex ? line_lex[li] : 0, line_pat ? line_pat[li] : 0, line_kw ? line_kw[li] : 0};
+  return rec_tail_plan(tok_off, l0, l1, opts.data(), RecStores{tb, snap_min, ptb, ktb});
 }
 
 }  // namespace rt

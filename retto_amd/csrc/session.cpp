@@ -65,6 +65,7 @@ rt_session* rt_session_create(const rt_config* cfg) {
   s->charsets = std::make_shared<rt_charsets>();
   s->lexicons = std::make_shared<rt_lexicons>();
   s->patterns = std::make_shared<rt_patterns>();
+  s->keywords = std::make_shared<rt_keywords>();
   if ((int)s->dict.size() != s->rec->classes())
     throw RtError(RT_ERR_SHAPE, "dictionary has " + std::to_string(s->dict.size()) + " entries but the rec head has " +
                                     std::to_string(s->rec->classes()) + " classes");
@@ -83,6 +84,7 @@ rt_session* rt_session_create(const rt_config* cfg) {
     h->cfg = s->cfg; h->device = s->device;
     h->det = s->det; h->cls = s->cls; h->rec = s->rec; h->dict = s->dict; h->model_info = s->model_info;
     h->d_word_raw = s->d_word_raw; h->charsets = s->charsets; h->lexicons = s->lexicons; h->patterns = s->patterns;
+    h->keywords = s->keywords;
     RT_HIP_CHECK(hipStreamCreateWithFlags(&h->st_full, hipStreamNonBlocking));
     h->st = h->st_full;
     RT_HIP_CHECK(hipMalloc((void**)&h->d_flags, 64));
@@ -545,6 +547,9 @@ struct Pipeline {
   // rec patterns (ctc_pattern.h; any.pattern): per line matched | vit | logprob | free_logprob, one block of 4 NLp words (written
   // for the lines that carry a pattern only)
   int* d_pat = nullptr; int* h_pat = nullptr;
+  // rec keywords (ctc_keyword.h; any.keywords): per line kw::HITS hit slots and the number of hits (written for the lines that
+  // carry a list only)
+  kw::Hit* d_kwh = nullptr; int* d_kwn = nullptr; kw::Hit* h_kwh = nullptr; int* h_kwn = nullptr;
 };
 
 // Launch groups: items [g0, end) where the group always takes its first item; with max_items > 0 it takes up to max_items items,
@@ -887,6 +892,17 @@ void rec_plan(rt_session& s, Pipeline& P) {
   }
   for (int l = 0; l < P.NL; l++) P.tok_off[l + 1] = P.tok_off[l] + RecNet::tokens_for_width(P.line_W[l]);
 }
+// line li as the rec network saw it (word_boxes.h): what k_word_boxes and the keyword spans' quads map columns through
+wb::WordGeom word_geom(const Pipeline& P, int li) {
+  const pp::CropRef& r = P.plan.refs[li];
+  const pp::CropDesc& cd = P.plan.descs[li];
+  wb::WordGeom g;
+  g.T = (int)(P.tok_off[li + 1] - P.tok_off[li]); g.W = P.line_W[li]; g.resized_w = P.lines[li].resized_w;
+  g.w_c = r.w; g.h_c = r.h; g.rot270 = cd.rot; g.w = cd.w; g.h = cd.h;
+  g.cw = P.plan.dims[li].cw; g.ch = P.plan.dims[li].ch;
+  memcpy(g.inv, cd.inv, sizeof g.inv);
+  return g;
+}
 // ---- a11 + a12: rec network + CTC decode in launch groups (+ word boxes) --------------
 void rec_groups(rt_session& s, Pipeline& P) {
   const int rh = s.cfg.rec_image_shape[1];
@@ -909,6 +925,7 @@ void rec_groups(rt_session& s, Pipeline& P) {
     RT_HIP_CHECK(hipMemsetAsync(P.d_lexs, 0, (size_t)P.NLp * sizeof(int), s.st));
   }
   if (P.any.pattern) P.d_pat = s.arena.alloc<int>((size_t)4 * P.NLp);
+  if (P.any.keywords) { P.d_kwh = s.arena.alloc<kw::Hit>((size_t)P.NLp * kw::HITS); P.d_kwn = s.arena.alloc<int>(P.NLp); }
   static const long long REC_GROUP_PX = getenv("RT_REC_GROUP_PX") ? atoll(getenv("RT_REC_GROUP_PX")) : (long long)24000000;  // measured sweet spot (profiles/README.md)
   for (int l0 = 0; l0 < P.NL;) {
     const int l1 = group_end(l0, P.NL, 0, REC_GROUP_PX, [&](int l) { return (long long)rh * P.line_W[l]; });
@@ -933,12 +950,17 @@ void rec_groups(rt_session& s, Pipeline& P) {
     // (the token count per line only depends on the widths, so the offsets are known before the net runs)
     const long long t0 = P.tok_off[l0];
     const rt_lexicons& X = *s.lexicons;
-    const RecTailPlan tail = rec_tail_plan(P.tok_off.data(), l0, l1, P.line_opts.data(), RecStores{X.tb, X.snap, &s.patterns->tb});
+    const rt_keywords& KW = *s.keywords;
+    const RecTailPlan tail = rec_tail_plan(P.tok_off.data(), l0, l1, P.line_opts.data(), RecStores{X.tb, X.snap, &s.patterns->tb, &KW.tb});
     if (!tail.table_fits())
       throw RtError(RT_ERR_CAPACITY, "rec lexicons: " + std::to_string(tail.lines.size()) + " lines of one rec group carry lexicons of " +
                                          std::to_string(tail.table) + " entries in all, more than the " + std::to_string(lx::MAX_GROUP_TABLE) +
                                          " likelihoods a group's table holds: use smaller lexicons or fewer lexicon lines per call");
-    const float* z5 = nullptr;   // the head's input, for the candidates', the charsets' and the lexicons' logits
+    if (!tail.ktable_fits())
+      throw RtError(RT_ERR_CAPACITY, "rec keywords: " + std::to_string(tail.klines.size()) + " lines of one rec group carry keyword lists of " +
+                                         std::to_string(tail.ktable) + " entries in all, more than the " + std::to_string(lx::MAX_GROUP_TABLE) +
+                                         " scores a group's table holds: use smaller keyword lists or fewer keyword lines per call");
+    const float* z5 = nullptr;   // the head's input, for the candidates', the charsets', the lexicons' and the keywords' logits
     { ProfOuter po(&s.prof, s.st, "net/rec");
       s.rec->run(c, x, L0, Lt, d_idx + t0, d_prob + t0, tail.needs_z5(cand_k) ? &z5 : nullptr); }  // fused CTC head: logits never reach HBM
     if (Lt.total != tail.rows) throw RtError(RT_ERR_SHAPE, "token count mismatch");
@@ -947,14 +969,8 @@ void rec_groups(rt_session& s, Pipeline& P) {
       pp::WordLineDesc* hwl = s.pinned.alloc<pp::WordLineDesc>(ln);
       for (int k = 0; k < ln; k++) {
         const int li = l0 + k;
-        const pp::CropRef& r = P.plan.refs[li];
-        const pp::CropDesc& cd = P.plan.descs[li];
-        pp::WordLineDesc& D = hwl[k];
-        D.tok_off = P.tok_off[li] - t0;
-        D.g.T = (int)(P.tok_off[li + 1] - P.tok_off[li]); D.g.W = P.line_W[li]; D.g.resized_w = P.lines[li].resized_w;
-        D.g.w_c = r.w; D.g.h_c = r.h; D.g.rot270 = cd.rot; D.g.w = cd.w; D.g.h = cd.h;
-        D.g.cw = P.plan.dims[li].cw; D.g.ch = P.plan.dims[li].ch;
-        memcpy(D.g.inv, cd.inv, sizeof D.g.inv);
+        hwl[k].tok_off = P.tok_off[li] - t0;
+        hwl[k].g = word_geom(P, li);
       }
       words = {hwl, P.d_meta.label + l0, P.d_meta.cscore + l0, d_wcol + t0, P.d_wcount + l0, P.d_words + t0};
     }
@@ -963,7 +979,8 @@ void rec_groups(rt_session& s, Pipeline& P) {
                                 X.d, X.d_snap, cand_k, 0,
                                 P.d_tok + t0, P.d_meta.ntok + l0, P.d_meta.rscore + l0, nullptr, P.d_lexm, P.d_lexn, P.d_lexs, nullptr,
                                 P.d_ccol ? P.d_ccol + t0 : nullptr, P.d_cands ? P.d_cands + t0 * cand_k : nullptr,
-                                words.h_lines ? &words : nullptr, s.patterns->d, P.d_pat, patf(1), patf(2), patf(3)};
+                                words.h_lines ? &words : nullptr, s.patterns->d, P.d_pat, patf(1), patf(2), patf(3),
+                                KW.d, KW.d_min, nullptr, nullptr, P.d_kwh, P.d_kwn};
     s.rec_tail(tail, s.rec->core(), t);
     l0 = l1;
   }
@@ -998,6 +1015,11 @@ void line_round_trip(rt_session& s, Pipeline& P) {
   if (P.d_pat) {   // (and the pattern results)
     P.h_pat = s.pinned.alloc<int>((size_t)4 * P.NLp);
     RT_HIP_CHECK(hipMemcpyAsync(P.h_pat, P.d_pat, (size_t)4 * P.NLp * sizeof(int), hipMemcpyDeviceToHost, s.st));
+  }
+  if (P.any.keywords) {   // (and the keyword hits)
+    P.h_kwh = s.pinned.alloc<kw::Hit>((size_t)P.NLp * kw::HITS); P.h_kwn = s.pinned.alloc<int>(P.NLp);
+    RT_HIP_CHECK(hipMemcpyAsync(P.h_kwh, P.d_kwh, (size_t)P.NLp * kw::HITS * sizeof(kw::Hit), hipMemcpyDeviceToHost, s.st));
+    RT_HIP_CHECK(hipMemcpyAsync(P.h_kwn, P.d_kwn, (size_t)P.NLp * sizeof(int), hipMemcpyDeviceToHost, s.st));
   }
   s.sync(); s.check_flags();
 }
@@ -1051,6 +1073,27 @@ void results(const rt_session& s, const Pipeline& P, rt_results& res) {
         if (P.line_opts[li].pattern <= 0) continue;
         R.pat_id[k] = P.line_opts[li].pattern;
         R.pat_res[k] = pt::LineResult{P.h_pat[li] == 1 ? 1 : 0, f[P.NLp + li], f[2 * (size_t)P.NLp + li], f[3 * (size_t)P.NLp + li]};
+      }
+    }
+    if (P.h_kwh) {   // rec keywords: a line without a list has 0 hits (its device slots were never written)
+      R.kw_id.assign((size_t)nb, 0); R.kw_n.assign((size_t)nb, 0); R.kw_hits.assign((size_t)nb * kw::HITS, kw::Hit{});
+      const double bw = P.crop_original ? (double)p.ori_w : (double)p.after_w, bh = P.crop_original ? (double)p.ori_h : (double)p.after_h;
+      for (int k = 0; k < nb; k++) {
+        const int li = p.first_line + k;
+        if (P.line_opts[li].keywords <= 0) continue;
+        R.kw_id[k] = P.line_opts[li].keywords;
+        R.kw_n[k] = std::min(std::max(P.h_kwn[li], 0), kw::HITS);
+        if (R.kw_n[k] == 0) continue;
+        // the span [first_col, last_col + 1) as an ALNUM word's (wb::line_words): crop pixels per column, the crop's homography,
+        // the classifier's rot180 as k_word_boxes takes it, then original-image coordinates
+        const wb::WordGeom g = word_geom(P, li);
+        const int rot180 = (m.label[li] == 1 && m.cscore[li] >= s.cfg.cls_thresh) ? 1 : 0;
+        for (int j = 0; j < R.kw_n[k]; j++) {
+          kw::Hit& h = R.kw_hits[(size_t)k * kw::HITS + j];
+          h = P.h_kwh[(size_t)li * kw::HITS + j];
+          kw::span_quad(h.first_col, h.last_col, g, rot180, h.quad);
+          gm::scale_and_clip(h.quad, bw, bh, (double)p.ori_w, (double)p.ori_h);
+        }
       }
     }
     if (s.cfg.rec_return_word_box) {   // word quads to original-image coordinates, word texts from the dictionary
@@ -1504,13 +1547,14 @@ rt_results* rt_session::run_batch(const uint8_t* const* rgb, const int* hs, cons
 // invertible homography -- checked here, for every page, before anything is queued.
 rt_results* rt_session::run_regions(const uint8_t* const* rgb, const int* hs, const int* ws, int n_pages, int mem,
                                     const float* const* quads, const int* n_quads, const int* const* region_charsets,
-                                    const int* const* region_lexicons, const int* const* region_patterns) {
+                                    const int* const* region_lexicons, const int* const* region_patterns,
+                                    const int* const* region_keywords) {
   std::vector<std::vector<float>> clamped((size_t)n_pages);
   std::vector<const float*> qp((size_t)n_pages, nullptr);
   // the regions' options with -1 resolved to the session defaults of this call (rec_line_opts.h)
   std::vector<std::vector<RecLineOpts>> opts((size_t)n_pages);
   std::vector<const RecLineOpts*> op((size_t)n_pages, nullptr);
-  const int* const* const ids[3] = {region_charsets, region_lexicons, region_patterns};
+  const int* const* const ids[REC_N_KINDS] = {region_charsets, region_lexicons, region_patterns, region_keywords};
   for (int i = 0; i < n_pages; i++) {
     const std::string where = "rt_run_regions: page " + std::to_string(i);
     if (hs[i] <= 0 || ws[i] <= 0 || rgb[i] == nullptr) throw RtError(RT_ERR_IMAGE, where + ": empty page");
@@ -1534,7 +1578,7 @@ rt_results* rt_session::run_regions(const uint8_t* const* rgb, const int* hs, co
     }
     qp[(size_t)i] = q.data();
     // (a page's options behind the checks of its quads and before the next page's)
-    const std::string bad = resolve_region_opts(i, i + 1, n_quads, ids, rec_default, rec_counts(), opts);
+    const std::string bad = resolve_region_opts(i, i + 1, n_quads, ids, REC_N_KINDS, rec_default, rec_counts(), opts);
     if (!bad.empty()) throw RtError(RT_ERR_INVALID, "rt_run_regions: " + bad);
     op[(size_t)i] = opts[(size_t)i].data();
   }

@@ -50,6 +50,10 @@ struct rt_results {
     std::vector<uint8_t> lex_snapped;
     // rec patterns (ctc_pattern.h): per line its pattern (0: none) and result; empty when no line of the call carried one
     std::vector<int32_t> pat_id; std::vector<rt::pt::LineResult> pat_res;
+    // rec keywords (ctc_keyword.h): per line its list (0: none), its number of hits and [rt::kw::HITS] hit slots, each with its
+    // page quad; empty when no line of the call carried a list
+    std::vector<int32_t> kw_id, kw_n;
+    std::vector<rt::kw::Hit> kw_hits;
     std::string json[3];
   };
   std::vector<Page> pages;
@@ -72,7 +76,7 @@ struct LaneWorker {
 };
 
 // What a pipeline call reads of the session's settings, as they were when the call was submitted: the default options of every
-// line (rt_set_rec_charset / _lexicon / _pattern, rec_line_opts.h) and the det tiles (rt_set_det_tiles, det_tiles.h; 0 = off)
+// line (rt_set_rec_charset / _lexicon / _pattern / _keywords, rec_line_opts.h) and the det tiles (rt_set_det_tiles, det_tiles.h; 0 = off)
 struct CallSettings { rt::RecLineOpts rec; int det_tile = 0, det_overlap = 0; };
 
 // One submitted batch (rt_submit_batch): the argument arrays are copied (the PAGES must stay valid until rt_wait_batch), the
@@ -166,6 +170,24 @@ struct rt_patterns {
   ~rt_patterns() { free_device(); }
 };
 
+// The session's rec keyword lists (ctc_keyword.h), shared with the helper lanes: rt_lexicons' shape.  List k (1-based,
+// rt_keywords_create's id) is host[k - 1] on the host (stable addresses) and list k - 1 of `tb`, whose four tables sit on the
+// device as `d` beside the lists' min_score [rt::kw::MAX_LISTS].  Only changed while no ticket is in flight and every lane's
+// stream is drained (rt_keywords_create is a guarded call): the tables are rebuilt and copied whole, with blocking copies.
+struct rt_keywords {
+  std::vector<std::unique_ptr<rt_lexicons::Host>> host;
+  rt::lx::Tables tb;
+  rt::lx::DevTables d{};
+  std::vector<float> min_score;
+  const float* d_min = nullptr;
+  void free_device() {
+    const void* p[] = {d.ids, d.entries, d.order, d.lex, d_min};
+    for (const void* q : p) if (q) (void)hipFree(const_cast<void*>(q));
+    d = rt::lx::DevTables{}; d_min = nullptr;
+  }
+  ~rt_keywords() { free_device(); }
+};
+
 // internal to the library (never accepted from a caller): pages already in HBM, det map overrides still host pointers
 #define RT_MEM_STAGED_MAPS_HOST 3
 
@@ -191,12 +213,16 @@ struct rt_session {
   std::vector<std::unique_ptr<rt_session>> helpers;
   int active_lanes = 1 << 30;  // rt_set_lanes: upper bound on the lanes rt_run_batch uses
   std::vector<std::string> dict;  // RecCharacter (rec_processor.rs:29-46)
-  // the rec charsets, lexicons and patterns (shared with the helper lanes), and how many of each there are: the valid ids
+  // the rec charsets, lexicons, patterns and keyword lists (shared with the helper lanes), and how many of each there are: the
+  // valid ids
   std::shared_ptr<rt_charsets> charsets;
   std::shared_ptr<rt_lexicons> lexicons;
   std::shared_ptr<rt_patterns> patterns;
-  rt::RecLineOpts rec_counts() const { return {(int)charsets->ids.size(), (int)lexicons->host.size(), (int)patterns->host.size()}; }
-  // rt_set_rec_charset / _lexicon / _pattern: the options of every line of the pipeline calls that follow, unless a region names
+  std::shared_ptr<rt_keywords> keywords;
+  rt::RecLineOpts rec_counts() const {
+    return {(int)charsets->ids.size(), (int)lexicons->host.size(), (int)patterns->host.size(), (int)keywords->host.size()};
+  }
+  // rt_set_rec_charset / _lexicon / _pattern / _keywords: the options of every line of the pipeline calls that follow, unless a region names
   // its own (0: none)
   rt::RecLineOpts rec_default;
   // rt_set_det_tiles (det_tiles.h): pages whose det input is larger than det_tile either way are detected in tiles; 0 = off
@@ -258,10 +284,13 @@ struct rt_session {
     const WordBoxes* wb;                      // or null
     // rec patterns (ctc_pattern.h): pt::Tables on the device and the per-line results, indexed by pt::Line::slot
     rt::pt::DevTables d_pat; int* patm; float* patv; float* patlp; float* patfree;
+    // rec keywords (ctc_keyword.h): the lists' lx::Tables and min_score on the device; kwscore [plan.ktable] and kwspan
+    // [plan.ktable][2], or null: taken from `scratch`; the per-line hits and counts, indexed by kw::Line::slot
+    rt::lx::DevTables d_kw; const float* d_kw_min; float* kwscore; int* kwspan; rt::kw::Hit* kwh; int* kwn;
   };
   // The tail of one rec group behind the net, in the one order that is right: the charsets replace the restricted rows' (idx, prob)
   // before anything reads them; a snap group's lexicons run next, so that the decode reads the snapped lines' aligned rows;
-  // then the patterns, whose matched lines overwrite theirs; pp::ctc_decode; the word boxes; any other group's lexicons; the candidates last, for their host wait.  The plan's tables go
+  // then the patterns, whose matched lines overwrite theirs; pp::ctc_decode; the word boxes; any other group's lexicons; the keywords, which read and write nothing of the others'; the candidates last, for their host wait.  The plan's tables go
   // through `pinned` into `scratch`, where the workspace comes from too: the caller rewinds it per group, after this.
   void rec_tail(const rt::RecTailPlan& plan, const rt::SvtrCore& core, const RecTail& t);
   // rec_return_candidates = K (ctc_candidates.h): kept token j of a line at first row o gets ccol[o + j] and cands[(o + j) * K ...].
@@ -280,10 +309,16 @@ struct rt_session {
   // k_ctc_row_lse and k_ctc_row_max, then k_ctc_pattern_viterbi on the resident logits: it overwrites the matched lines' rows of
   // idx / prob and writes every pattern line's patm / patv / patlp / patfree [slot].  No host wait.
   void ctc_pattern(const rt::RecTailPlan& plan, const rt::SvtrCore& core, const RecTail& t);
+  // Rec keywords (ctc_keyword.h) over the plan's keyword lines, chunked as the lexicon lines are: row gather, the CTC FC,
+  // k_ctc_row_max, k_ctc_keyword_spot -> kwscore / kwspan; then one k_ctc_keyword_topk over all lines -> kwh / kwn.  No host
+  // wait, and no value that anything else reads.
+  void ctc_keywords(const rt::RecTailPlan& plan, const rt::SvtrCore& core, const RecTail& t);
   // rt_charset_create: compiles the set (rt::compile_charset), stores it and returns its id
   int charset_create(const char* utf8, size_t len, const int32_t* ids, int n_ids);
   // rt_lexicon_create: compiles the entries (rt::compile_lexicon), stores them and returns the lexicon's id
   int lexicon_create(const char* utf8, size_t len, const int32_t* ids, const int32_t* entry_lens, int n_id_entries);
+  // rt_keywords_create: compiles the entries as a lexicon's (rt::compile_lexicon), stores them with min_score and returns the list's id
+  int keywords_create(const char* utf8, size_t len, const int32_t* ids, const int32_t* entry_lens, int n_id_entries, float min_score);
   // rt_pattern_create: compiles the pattern (rt::pt::compile), stores it and returns its id
   int pattern_create(const char* utf8, size_t len);
   // rt_lexicon_set_snap: the lexicon's min_posterior (ctc_lexicon_align.h), on the host and in the device table
@@ -323,11 +358,11 @@ struct rt_session {
   void debug_det_tiles(const uint8_t* rgb_det, int h, int w, float* tile_maps_out, float* page_map_out);
   // rt_run_regions: checks and clamps every quad (RT_ERR_INVALID naming page and region; nothing is queued then), then the
   // pages go over the lanes as run_batch's do, from the crop plan on
-  // charsets, lexicons, patterns (each or null; entries may be null): per region -1 = the session default, 0 = none, >= 1 = that
+  // charsets, lexicons, patterns, keywords (each or null; entries may be null): per region -1 = the session default, 0 = none, >= 1 = that
   // id (rt::resolve_region_opts); a region may not carry both a pattern and a lexicon
   rt_results* run_regions(const uint8_t* const* rgb, const int* hs, const int* ws, int n_pages, int mem,
                           const float* const* quads, const int* n_quads, const int* const* charsets, const int* const* lexicons,
-                          const int* const* patterns);
+                          const int* const* patterns, const int* const* keywords = nullptr);
 };
 
 rt_session* rt_session_create(const rt_config* cfg);
