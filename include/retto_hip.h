@@ -642,6 +642,49 @@ RT_API int rt_debug_ctc_keywords_host(const float* z5, const float* W, const flo
  * rt_results_rec_keywords reports for a hit with that span. */
 RT_API int rt_debug_span_quad(int T, int W, int resized_w, const float* box8_after, int rot180, int after_w, int after_h, int ori_w,
                               int ori_h, int first_col, int last_col, float* quad8_out);
+
+/* ---- rec beams: the N most probable strings of a line by CTC prefix beam search ------------------------------------------------
+ * The greedy decode is the best PATH; rec_return_candidates gives alternatives at the steps it kept; a lexicon ranks a given
+ * list; patterns and keywords are Viterbi searches.  A spell corrector, a language model or a validator that takes the first
+ * hypothesis that parses asks for the most probable STRINGS, each summed over its alignments, and how far apart they are.
+ * retto_amd/csrc/ctc_beam.h states the rule; in short, for a line of T time steps, beam width B and N hypotheses:
+ *   hypothesis  a string with the log-probabilities of its alignments that end in the blank (pb) and in a non-blank (pnb), from
+ *               the line's recomputed fp32 logits under the FULL softmax (a charset of the line is not applied);
+ *   step        every member stays (blank, or its last class again) and is extended by each of the step's 8 best non-blank
+ *               classes; an extension that IS another member's string is added to that member, never kept twice; the best B by
+ *               total log-probability survive (ties: stays before extensions, then beam order, then the class's rank);
+ *   result      the first N of the final beam, best first: tokens and logprob.  The empty string is a legitimate hypothesis with
+ *               0 tokens; fewer than N where the beam is smaller; none for a line without time steps.
+ * logprob sums the alignments that stayed inside the beam: never more than the string's full CTC likelihood, equal to it where
+ * the beam never overflowed.  Beams only read a line: they go with every charset, lexicon, pattern and keyword list, and every
+ * other result -- boxes, tokens, text, scores, words, candidates, matches, hits, JSON -- is what it is without them, bit for bit.
+ * The per-stage JSON stays as it is.  Off (the default): no launch, no workspace.
+ *
+ * rt_set_rec_beam: beam = 0 switches the option off; otherwise 1 <= beam <= RT_MAX_BEAM and 1 <= nbest <= min(beam, RT_MAX_NBEST),
+ * else RT_ERR_INVALID.  It applies to every pipeline call that follows, rt_run_regions* included; it fails like the other
+ * setters while tickets are in flight.  rt_rec_beam reads the two values back. */
+#define RT_MAX_BEAM 32
+#define RT_MAX_NBEST 8
+typedef struct rt_beam { float logprob; int32_t n_tokens; } rt_beam;
+RT_API int rt_set_rec_beam(rt_session* s, int beam, int nbest);
+RT_API int rt_rec_beam(const rt_session* s, int* beam, int* nbest);
+/* the hypotheses of a line: their number (0 when the option was off); *out (optional): their records, best first */
+RT_API int rt_results_rec_beams(const rt_results* r, int page, int line, const rt_beam** out);
+/* hypothesis k of a line: its number of tokens; *tokens (optional): its class ids in reading order */
+RT_API int rt_results_rec_beam_tokens(const rt_results* r, int page, int line, int k, const int32_t** tokens);
+/* hypothesis k of a line as UTF-8, built from the dictionary as rt_results_rec_text is (NULL for a k the line does not have) */
+RT_API const char* rt_results_rec_beam_text(const rt_results* r, int page, int line, int k);
+/* The device path of the beams on host arrays (row gather in chunks of whole lines, the CTC FC GEMM, k_ctc_row_lse,
+ * k_ctc_beam_topc, k_ctc_beam_search): every line carries the beam.  z5, W, bias, N, tokens_per_line, n_lines, chunk_rows: as
+ * rt_debug_ctc_keywords.  counts_out [n_lines]; beams_out [n_lines][nbest]; tokens_out: line after line [nbest][T], hypothesis k
+ * of a line at its k * T.  Record slots past a line's count and token slots past a hypothesis' n_tokens come back as the caller
+ * put them.  beam = 0 or n_lines = 0: nothing runs and nothing is written. */
+RT_API int rt_debug_ctc_beam(rt_session* s, const float* z5, const float* W, const float* bias, int N, const int32_t* tokens_per_line,
+                             int n_lines, int beam, int nbest, int chunk_rows, int32_t* counts_out, rt_beam* beams_out,
+                             int32_t* tokens_out);
+/* The same rule on the CPU in plain fp32 loops (ctc_beam.h), GPU-free and sessionless; same layout. */
+RT_API int rt_debug_ctc_beam_host(const float* z5, const float* W, const float* bias, int N, const int32_t* tokens_per_line,
+                                  int n_lines, int beam, int nbest, int32_t* counts_out, rt_beam* beams_out, int32_t* tokens_out);
 /* f32 sum of every det probability map produced in the call (keeps the network's
  * output observable when det_map_override is used) */
 RT_API double rt_results_det_checksum(const rt_results* r);

@@ -190,6 +190,13 @@ class KeywordHit:   # rt_keyword_hit, with the entry's text
 
 
 @dataclass
+class BeamHypothesis:   # rt_beam, with its tokens and text
+    tokens: np.ndarray    # int32 class ids in reading order; empty: the empty string
+    text: str
+    logprob: float        # log of the summed probability of the string's alignments that stayed inside the beam
+
+
+@dataclass
 class RecProcessorSingleResult:
     text: str
     score: float
@@ -213,6 +220,9 @@ class RecProcessorSingleResult:
     # rec keywords (create_keywords): None when the line carried no list, else up to KEYWORD_HITS hits, best first: the list's
     # entries spotted inside the line (retto_amd/csrc/ctc_keyword.h)
     keywords: Optional[List["KeywordHit"]] = None
+    # rec beams (set_rec_beam): None when the option is off, else the line's most probable strings by CTC prefix beam search,
+    # best first (retto_amd/csrc/ctc_beam.h)
+    beams: Optional[List["BeamHypothesis"]] = None
 
 
 @dataclass
@@ -660,6 +670,7 @@ class RettoSession:
         cs = np.ctypeslib.as_array(lib.rt_results_cls_scores(r, page), (n,)).copy() if n else np.zeros(0, np.float32)
         rs = np.ctypeslib.as_array(lib.rt_results_rec_scores(r, page), (n,)).copy() if n else np.zeros(0, np.float32)
         det, cls, rec = [], [], []
+        beam_on = self.rec_beam()[0] > 0   # (the setter is refused while a ticket is in flight: what the call ran under)
         for k in range(n):
             det.append(DetProcessorInnerResult(PointBox([Point(float(boxes[k, 2 * q]), float(boxes[k, 2 * q + 1]))
                                                          for q in range(4)]), float(ds[k])))
@@ -673,7 +684,7 @@ class RettoSession:
             snapped = None if matches is None else bool(lib.rt_results_rec_lexicon_snapped(r, page, k))
             rec.append(RecProcessorSingleResult(lib.rt_results_rec_text(r, page, k).decode("utf-8"), float(rs[k]), toks, words,
                                                 cands, cols, matches, snapped, self._pattern(r, page, k),
-                                                self._keywords(r, page, k)))
+                                                self._keywords(r, page, k), self._beams(r, page, k, beam_on)))
         return RettoWorkerResult(det, cls, rec)
 
     def _dictionary(self) -> List[str]:
@@ -708,6 +719,20 @@ class RettoSession:
                            float(hp[j].score), int(hp[j].first_col), int(hp[j].last_col),
                            np.array(list(hp[j].quad), np.float32).reshape(4, 2)) for j in range(n)]
 
+    def _beams(self, r, page: int, line: int, on: bool):
+        if not on:
+            return None
+        lib = self._hd.lib
+        bp = C.POINTER(_lib.Beam)()
+        n = lib.rt_results_rec_beams(r, page, line, C.byref(bp))
+        out = []
+        for k in range(n):
+            tp = C.POINTER(C.c_int32)()
+            nt = lib.rt_results_rec_beam_tokens(r, page, line, k, C.byref(tp))
+            out.append(BeamHypothesis(np.array([tp[i] for i in range(nt)], np.int32),
+                                      lib.rt_results_rec_beam_text(r, page, line, k).decode("utf-8"), float(bp[k].logprob)))
+        return out
+
     def _lexicon_matches(self, r, page: int, line: int):
         lib = self._hd.lib
         lex = lib.rt_results_rec_lexicon_id(r, page, line)
@@ -740,6 +765,20 @@ class RettoSession:
         trusted parts are stitched into the one page map (retto_amd/csrc/det_tiles.h); 0 = off, the default.  tile: a multiple
         of 32, at least 64; overlap: a multiple of 32, at most tile / 2.  Holds for the pipeline calls that follow."""
         _check(self._hd.lib.rt_set_det_tiles(self._hd.h, int(tile), int(overlap)), self._hd.h)
+
+    # -- rec beams --------------------------------------------------------------------------
+    def set_rec_beam(self, beam: int, nbest: int = 1) -> None:
+        """rt_set_rec_beam: every line of the pipeline calls that follow also reports its ``nbest`` most probable strings from a
+        CTC prefix beam search of width ``beam`` (RecProcessorSingleResult.beams; retto_amd/csrc/ctc_beam.h).  beam = 0: off, the
+        default; otherwise 1 <= beam <= MAX_BEAM and 1 <= nbest <= min(beam, MAX_NBEST).  It only reads a line: every other
+        result stays what it is."""
+        _check(self._hd.lib.rt_set_rec_beam(self._hd.h, int(beam), int(nbest)), self._hd.h)
+
+    def rec_beam(self) -> Tuple[int, int]:
+        """rt_rec_beam: (beam, nbest) as set; beam 0 = off."""
+        b, n = C.c_int(), C.c_int()
+        _check(self._hd.lib.rt_rec_beam(self._hd.h, C.byref(b), C.byref(n)), self._hd.h)
+        return b.value, n.value
 
     @property
     def det_tiles(self) -> Tuple[int, int]:

@@ -66,6 +66,12 @@ class KeywordHit(C.Structure):   # rt_keyword_hit
     _fields_ = [("entry", C.c_int32), ("score", C.c_float), ("first_col", C.c_int32), ("last_col", C.c_int32), ("quad", C.c_float * 8)]
 
 
+class Beam(C.Structure):   # rt_beam
+    _fields_ = [("logprob", C.c_float), ("n_tokens", C.c_int32)]
+
+
+MAX_BEAM = 32                # RT_MAX_BEAM
+MAX_NBEST = 8                # RT_MAX_NBEST
 MAX_KEYWORD_LISTS = 16       # RT_MAX_KEYWORD_LISTS
 KEYWORD_HITS = 8             # RT_KEYWORD_HITS
 MAX_LEXICONS = 16            # RT_MAX_LEXICONS
@@ -106,6 +112,8 @@ EXPORTS = [
     "rt_keywords_create", "rt_keywords_entries", "rt_keywords_entry", "rt_keywords_entry_text", "rt_keywords_min_score",
     "rt_set_rec_keywords", "rt_run_regions_keywords", "rt_results_rec_keywords", "rt_results_rec_keywords_id", "rt_debug_ctc_keywords",
     "rt_debug_ctc_keywords_host", "rt_debug_span_quad",
+    "rt_set_rec_beam", "rt_rec_beam", "rt_results_rec_beams", "rt_results_rec_beam_tokens", "rt_results_rec_beam_text",
+    "rt_debug_ctc_beam", "rt_debug_ctc_beam_host",
     "rt_set_det_tiles", "rt_det_tiles", "rt_det_tile_plan", "rt_debug_det_tiles", "rt_debug_arena_high_water", "rt_bench_memcpy_d2d",
 ]
 
@@ -332,6 +340,16 @@ def load():
                                                C.c_void_p, C.c_void_p]
     lib.rt_debug_span_quad.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                        C.c_int, C.c_void_p]
+    lib.rt_set_rec_beam.argtypes = [C.c_void_p, C.c_int, C.c_int]
+    lib.rt_rec_beam.argtypes = [C.c_void_p, P(C.c_int), P(C.c_int)]
+    lib.rt_results_rec_beams.argtypes = [C.c_void_p, C.c_int, C.c_int, P(P(Beam))]
+    lib.rt_results_rec_beam_tokens.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, P(P(C.c_int32))]
+    lib.rt_results_rec_beam_text.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int]
+    lib.rt_results_rec_beam_text.restype = C.c_char_p
+    lib.rt_debug_ctc_beam.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int,
+                                      C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.rt_debug_ctc_beam_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int,
+                                           C.c_void_p, C.c_void_p, C.c_void_p]
     lib.rt_set_det_tiles.argtypes = [C.c_void_p, C.c_int, C.c_int]
     lib.rt_det_tiles.argtypes = [C.c_void_p, P(C.c_int), P(C.c_int)]
     lib.rt_det_tile_plan.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, P(C.c_int32), P(C.c_int32), C.c_int, P(C.c_int32), P(C.c_int32),

@@ -1,6 +1,6 @@
 // extern "C" surface of libretto_hip.so (include/retto_hip.h): sessions, the networks, the pipeline stages, batches, results,
 // parsers and device memory, with the feature-level debug hooks that are thin forwards into their features (rt_debug_warp_crops,
-// rt_debug_jpeg_reconstruct, rt_debug_word_boxes, rt_debug_ctc_candidates_host, rt_debug_charset_compile, rt_debug_ctc_charset_host, rt_debug_lexicon_compile, rt_debug_ctc_lexicon_host, rt_debug_ctc_lexicon_align_host, rt_debug_ctc_keywords_host, rt_debug_span_quad).  The kernel-level diagnostics (rt_debug_set_variants,
+// rt_debug_jpeg_reconstruct, rt_debug_word_boxes, rt_debug_ctc_candidates_host, rt_debug_charset_compile, rt_debug_ctc_charset_host, rt_debug_lexicon_compile, rt_debug_ctc_lexicon_host, rt_debug_ctc_lexicon_align_host, rt_debug_ctc_keywords_host, rt_debug_span_quad, rt_debug_ctc_beam_host).  The kernel-level diagnostics (rt_debug_set_variants,
 // rt_bench_*, and the rt_debug_* harnesses the kernel tests drive) are in api_debug.cpp; api_internal.h holds what both share.
 #include <thread>
 #include <sched.h>
@@ -127,6 +127,26 @@ std::string rt::keywords_args_error(const float* z5, const float* W, int N, cons
   if (rows >= (1ll << 30)) return "the lines have " + S(rows) + " time steps, 2^30 or more";
   if (table > lx::MAX_GROUP_TABLE) return "the score table has " + S(table) + " entries, more than a group's table holds";
   *rows_out = rows; *table_out = table;
+  return std::string();
+}
+std::string rt::beam_args_error(const float* z5, const float* W, int N, const int32_t* tokens_per_line, int n_lines, int beam, int nbest,
+                                const int32_t* counts_out, const rt_beam* beams_out, const int32_t* tokens_out, long long* rows_out) {
+  auto S = [](long long v) { return std::to_string(v); };
+  if (!z5 || !W || !tokens_per_line || !counts_out || !beams_out || !tokens_out) return "a required pointer is null";
+  if (n_lines < 0) return "n_lines is negative";
+  if (N <= 1) return "N must be at least 2 (the blank and one class)";
+  if (beam < 0 || beam > RT_MAX_BEAM) return "beam = " + S(beam) + " is outside [0, RT_MAX_BEAM]";
+  if (beam > 0 && (nbest < 1 || nbest > std::min(beam, RT_MAX_NBEST)))
+    return "nbest = " + S(nbest) + " is outside [1, min(beam, RT_MAX_NBEST)]";
+  long long rows = 0;
+  for (int i = 0; i < n_lines; i++) {
+    if (tokens_per_line[i] < 0) return "line " + S(i) + " has a negative number of time steps";
+    rows += tokens_per_line[i];
+  }
+  if (rows >= (1ll << 30)) return "the lines have " + S(rows) + " time steps, 2^30 or more";
+  if (beam > 0 && n_lines + rows * beam > bm::MAX_GROUP_NODES)
+    return "the lines need " + S(n_lines + rows * beam) + " trie nodes, more than a group's trie holds";
+  *rows_out = rows;
   return std::string();
 }
 std::string rt::lexicon_align_args_error(const float* lex_min_post, int n_lex, const int32_t* idx, const float* prob,
@@ -489,6 +509,24 @@ int rt_det_tiles(const rt_session* s, int* tile, int* overlap) {
   if (!s) return RT_ERR_INVALID;
   if (tile) *tile = s->det_tile;
   if (overlap) *overlap = s->det_overlap;
+  return RT_OK;
+}
+static_assert(RT_MAX_BEAM == bm::MAX_BEAM && RT_MAX_NBEST == bm::MAX_NBEST, "the RT_MAX_BEAM / RT_MAX_NBEST limits and bm:: must agree");
+static_assert(sizeof(rt_beam) == sizeof(bm::Beam) && offsetof(rt_beam, logprob) == offsetof(bm::Beam, logprob) &&
+                  offsetof(rt_beam, n_tokens) == offsetof(bm::Beam, n_tokens), "rt_beam and bm::Beam must share one layout");
+int rt_set_rec_beam(rt_session* s, int beam, int nbest) {
+  RT_REQUIRE(s, s, "rt_set_rec_beam: null session");
+  return guarded(s, [&] {
+    if (beam == 0) { s->beam_b = s->beam_n = 0; return; }
+    if (const char* why = bm::check_params(beam, nbest))
+      throw RtError(RT_ERR_INVALID, "rt_set_rec_beam(" + std::to_string(beam) + ", " + std::to_string(nbest) + "): " + why);
+    s->beam_b = beam; s->beam_n = nbest;   // (the helper lanes get it with every call: CallSettings)
+  });
+}
+int rt_rec_beam(const rt_session* s, int* beam, int* nbest) {
+  if (!s) return RT_ERR_INVALID;
+  if (beam) *beam = s->beam_b;
+  if (nbest) *nbest = s->beam_n;
   return RT_OK;
 }
 int rt_det_tile_plan(int h, int w, int tile, int overlap, int32_t* row_origin, int32_t* row_bound, int row_cap, int32_t* col_origin,
@@ -1016,6 +1054,53 @@ int rt_results_rec_keywords_id(const rt_results* r, int page, int line) {
   auto* p = RT_PAGE(r, page);
   if (!p || line < 0 || (size_t)line >= p->kw_id.size()) return 0;
   return p->kw_id[(size_t)line];
+}
+int rt_results_rec_beams(const rt_results* r, int page, int line, const rt_beam** out) {
+  auto* p = RT_PAGE(r, page);
+  if (!p || p->beam_n <= 0 || line < 0 || (size_t)line >= p->bm_count.size()) return 0;
+  if (out) *out = reinterpret_cast<const rt_beam*>(p->bm_recs.data()) + (size_t)line * p->beam_n;
+  return p->bm_count[(size_t)line];
+}
+int rt_results_rec_beam_tokens(const rt_results* r, int page, int line, int k, const int32_t** tokens) {
+  auto* p = RT_PAGE(r, page);
+  if (!p || p->beam_n <= 0 || line < 0 || (size_t)line >= p->bm_count.size() || k < 0 || k >= p->bm_count[(size_t)line]) return 0;
+  const std::vector<int32_t>& t = p->bm_tokens[(size_t)line * p->beam_n + k];
+  if (tokens) *tokens = t.data();
+  return (int)t.size();
+}
+const char* rt_results_rec_beam_text(const rt_results* r, int page, int line, int k) {
+  auto* p = RT_PAGE(r, page);
+  if (!p || p->beam_n <= 0 || line < 0 || (size_t)line >= p->bm_count.size() || k < 0 || k >= p->bm_count[(size_t)line]) return nullptr;
+  return p->bm_text[(size_t)line * p->beam_n + k].c_str();
+}
+int rt_debug_ctc_beam_host(const float* z5, const float* W, const float* bias, int N, const int32_t* tokens_per_line, int n_lines,
+                           int beam, int nbest, int32_t* counts_out, rt_beam* beams_out, int32_t* tokens_out) {
+  long long rows = 0;
+  const std::string bad = beam_args_error(z5, W, N, tokens_per_line, n_lines, beam, nbest, counts_out, beams_out, tokens_out, &rows);
+  if (!bad.empty()) {
+    rt::create_error() = "rt_debug_ctc_beam_host: " + bad;
+    return RT_ERR_INVALID;
+  }
+  if (beam == 0) return RT_OK;
+  try {
+    const int D = 120;
+    std::vector<float> logits, lse;
+    long long o = 0;
+    for (int i = 0; i < n_lines; i++) {
+      const int T = tokens_per_line[i];
+      logits.assign((size_t)std::max(T, 1) * N, 0.0f); lse.assign((size_t)std::max(T, 1), 0.0f);
+      for (int t = 0; t < T; t++) {
+        cs::row_logits(z5 + (size_t)(o + t) * D, D, W, bias, N, logits.data() + (size_t)t * N);
+        lse[(size_t)t] = lx::row_lse(logits.data() + (size_t)t * N, N);
+      }
+      counts_out[i] = bm::line_beams(logits.data(), N, lse.data(), T, N, beam, nbest, reinterpret_cast<bm::Beam*>(beams_out) + (size_t)i * nbest,
+                                     tokens_out + o * nbest);
+      o += T;
+    }
+    return RT_OK;
+  } catch (const std::exception&) {
+    return RT_ERR_BACKEND;
+  }
 }
 int rt_debug_ctc_keywords_host(const float* z5, const float* W, const float* bias, int N, const int32_t* tokens_per_line, int n_lines,
                                const int32_t* line_kw, const int32_t* entry_ids, const int32_t* entry_lens,

@@ -389,12 +389,13 @@ struct TailHook {
   TailHook(rt_session* s_, const float* z5, const float* W, const float* bias, int N, long long rows, const int32_t* tokens_per_line,
            int n_lines, const int32_t* line_set, const int32_t* line_lex, const lx::Tables& tb, const float* snap_min, const int32_t* idx,
            const float* prob, int K, int chunk_rows, const int32_t* line_pat = nullptr, const pt::Tables* ptb = nullptr,
-           const int32_t* line_kw = nullptr, const lx::Tables* ktb = nullptr)
+           const int32_t* line_kw = nullptr, const lx::Tables* ktb = nullptr, int beam_b = 0, int beam_n = 0)
       : s(s_), nr((size_t)std::max<long long>(rows, 1)) {
     s->begin_call();
     std::vector<long long> off((size_t)n_lines + 1, 0);
     std::partial_sum(tokens_per_line, tokens_per_line + n_lines, off.begin() + 1);   // (below 2^30: the entries' own check)
-    plan = rec_tail_plan(off.data(), 0, n_lines, line_set, line_lex, tb, snap_min, line_pat, ptb, line_kw, ktb);
+    plan = rec_tail_plan(off.data(), 0, n_lines, line_set, line_lex, tb, snap_min, line_pat, ptb, line_kw, ktb, beam_b, beam_n);
+    t.beam_b = beam_b; t.beam_n = beam_n;
     core.classes = N;
     if (plan.needs_z5(K)) {
       core.fc = pack_linear(ws, W, bias, core.D, N);
@@ -606,6 +607,33 @@ RT_API int rt_debug_ctc_keywords(rt_session* s, const float* z5, const float* W,
     if (span_out) DevBufs::download(span_out, t.kwspan, 2 * (size_t)table);
     DevBufs::download(reinterpret_cast<kw::Hit*>(hits_out), t.kwh, (size_t)n_lines * kw::HITS);
     DevBufs::download(n_hits_out, t.kwn, (size_t)n_lines);
+  });
+}
+
+// Rec beams' device path on host arrays (ctc_beam.h): every line carries the beam, as in a pipeline call after rt_set_rec_beam.
+RT_API int rt_debug_ctc_beam(rt_session* s, const float* z5, const float* W, const float* bias, int N, const int32_t* tokens_per_line,
+                             int n_lines, int beam, int nbest, int chunk_rows, int32_t* counts_out, rt_beam* beams_out,
+                             int32_t* tokens_out) {
+  long long rows = 0;
+  RT_REQUIRE(s, s, "rt_debug_ctc_beam: null session");
+  const std::string bad = beam_args_error(z5, W, N, tokens_per_line, n_lines, beam, nbest, counts_out, beams_out, tokens_out, &rows);
+  RT_REQUIRE(bad.empty(), s, "rt_debug_ctc_beam: " + bad);
+  RT_REQUIRE(chunk_rows >= 0, s, "rt_debug_ctc_beam: chunk_rows is negative");
+  return guarded(s, [&] {
+    if (beam == 0 || n_lines == 0) return;   // (off, or no line: no launch, no write)
+    TailHook h(s, z5, W, bias, N, rows, tokens_per_line, n_lines, nullptr, nullptr, lx::Tables(), nullptr, nullptr, nullptr, 0, chunk_rows,
+               nullptr, nullptr, nullptr, nullptr, beam, nbest);
+    rt_session::RecTail& t = h.t;
+    // (what the kernels write starts as the caller's values: a slot they leave alone comes back untouched)
+    const size_t nt = (size_t)std::max<long long>(rows, 1) * nbest;
+    t.bmn = h.bufs.upload(counts_out, (size_t)n_lines);
+    t.bmrec = h.bufs.upload(reinterpret_cast<const bm::Beam*>(beams_out), (size_t)n_lines * nbest);
+    t.bmtok = h.bufs.alloc<int>(nt);
+    DevBufs::put(t.bmtok, tokens_out, (size_t)rows * nbest);
+    h.run();
+    DevBufs::download(counts_out, t.bmn, (size_t)n_lines);
+    DevBufs::download(reinterpret_cast<bm::Beam*>(beams_out), t.bmrec, (size_t)n_lines * nbest);
+    DevBufs::download(tokens_out, t.bmtok, (size_t)rows * nbest);
   });
 }
 

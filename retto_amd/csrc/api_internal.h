@@ -36,6 +36,10 @@ std::string keywords_args_error(const float* z5, const float* W, int N, const in
                                 const int32_t* line_kw, const int32_t* entry_ids, const int32_t* entry_lens,
                                 const int32_t* kw_first_entry, int n_kw, const float* kw_min_score, const rt_keyword_hit* hits_out,
                                 const int32_t* n_hits_out, long long* rows_out, long long* table_out);
+// what both rt_debug_ctc_beam forms require of their arguments, likewise (beam = 0, off, and n_lines = 0 pass: the entries then
+// do nothing); *rows_out = the lines' time steps
+std::string beam_args_error(const float* z5, const float* W, int N, const int32_t* tokens_per_line, int n_lines, int beam, int nbest,
+                            const int32_t* counts_out, const rt_beam* beams_out, const int32_t* tokens_out, long long* rows_out);
 // what both rt_debug_ctc_lexicon_align forms require beyond lexicon_args_error (n_lex already checked), likewise
 std::string lexicon_align_args_error(const float* lex_min_post, int n_lex, const int32_t* idx, const float* prob,
                                      const int32_t* snapped_out, const float* vit_out);

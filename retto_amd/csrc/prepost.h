@@ -5,6 +5,7 @@
 #include "nn.h"
 #include "common.h"
 #include "word_boxes.h"
+#include "ctc_beam.h"
 #include "ctc_candidates.h"
 #include "ctc_charset.h"
 #include "ctc_keyword.h"
@@ -132,6 +133,14 @@ void ctc_keyword_spot(hipStream_t st, const float* logits, int ld, const float* 
 // (entry, score, first_col, last_col; never the quad), their number -> counts[line.slot] (slots past the count are not written)
 void ctc_keyword_topk(hipStream_t st, const kw::Line* lines, int n_lines, const lx::Lex* lex, const float* min_score,
                       const float* score, const int* span, kw::Hit* hits, int* counts);
+// Rec beams (ctc_beam.h): K_t of every row i < m of logits [m][ld] -> topc[i]
+void ctc_beam_topc(hipStream_t st, const float* logits, int ld, int classes, int m, bm::TopC* topc);
+// the prefix beam search of lines[0..n_lines) (one chunk, resident as for ctc_lexicon_forward, with lse and topc of its rows:
+// ctc_row_lse, ctc_beam_topc), beam width B, nbest hypotheses: counts[line.slot] <- their number, beams[line.slot * nbest ...]
+// their records, tokens[line.out + k * T ...] hypothesis k's tokens (slots past a count or a length are not written).  nodes: the
+// group's trie, bm::nodes_of(T, B) nodes per line from line.lex on; needs no initialisation.
+void ctc_beam_search(hipStream_t st, const float* logits, int ld, const float* lse, const bm::TopC* topc, const bm::Line* lines,
+                     int n_lines, int chunk_row0, int B, int nbest, bm::Node* nodes, bm::Beam* beams, int* tokens, int* counts);
 // Lexicon snap (ctc_lexicon_align.h): one wave64 per line of lines[0..n_lines) (one chunk, resident as for ctc_lexicon_forward,
 // after ctc_lexicon_topk over the same lines).  snapped[line.slot] <- 0 / 1 for every line; a line whose lexicon has
 // min_post[line.lex] > 0 and whose match 0 reaches it has its winner aligned (CTC Viterbi) and its rows rows[line.row0 ..

@@ -781,6 +781,176 @@ void ctc_keyword_topk(hipStream_t st, const kw::Line* lines, int n_lines, const 
   RT_LAUNCH(k_ctc_keyword_topk, dim3(n_lines), dim3(64), 0, st, lines, lex, min_score, score, span, hits, counts);
 }
 
+// Rec beams (ctc_beam.h).  One wave64 per row i < m of logits [m][ld]: K_t, the up to bm::TOP_C non-blank classes with the largest
+// logits, in k_ctc_topk's shape -- the lanes stream the row once as float4 (pad columns and the blank skipped), each keeping a
+// best-first list of TOP_C; then TOP_C rounds of a wave arg-max over the list heads (ties to the lower id), lane r keeping round
+// r's winner and writing slot r: (cc::EMPTY_ID, -inf) past the row's count.  The beam kernel then never reads a whole row.
+__global__ __launch_bounds__(64) void k_ctc_beam_topc(const float* __restrict__ logits, int ld, int classes, int m,
+                                                      bm::TopC* __restrict__ topc) {
+  constexpr int N = bm::TOP_C;
+  const int i = blockIdx.x, lane = threadIdx.x;
+  if (i >= m) return;
+  const float4* x = reinterpret_cast<const float4*>(logits + (long long)i * ld);
+  const int nv = (classes + 3) / 4;
+  float L[N]; int I[N];
+#pragma unroll
+  for (int j = 0; j < N; j++) { L[j] = -INFINITY; I[j] = cc::EMPTY_ID; }
+  for (int v = lane; v < nv; v += 64) {
+    const float4 q = x[v];
+    const float e[4] = {q.x, q.y, q.z, q.w};
+#pragma unroll
+    for (int u = 0; u < 4; u++) {
+      const int c = 4 * v + u;
+      if (c >= 1 && c < classes) cc::list_insert(L, I, e[u], c);
+    }
+  }
+  float ol = -INFINITY; int oi = cc::EMPTY_ID;
+  for (int r = 0; r < N; r++) {
+    float wl = L[0]; int wi = I[0];
+    for (int o = 32; o >= 1; o >>= 1) {
+      const float l2 = __shfl_xor(wl, o); const int i2 = __shfl_xor(wi, o);
+      if (cc::better(l2, i2, wl, wi)) { wl = l2; wi = i2; }
+    }
+    if (lane == r) { ol = wl; oi = wi; }
+    if (wi != cc::EMPTY_ID && I[0] == wi) {
+#pragma unroll
+      for (int j = 0; j + 1 < N; j++) { L[j] = L[j + 1]; I[j] = I[j + 1]; }
+      L[N - 1] = -INFINITY; I[N - 1] = cc::EMPTY_ID;
+    }
+  }
+  if (lane < N) { topc[i].id[lane] = oi; topc[i].logit[lane] = oi == cc::EMPTY_ID ? -INFINITY : ol; }
+}
+void ctc_beam_topc(hipStream_t st, const float* logits, int ld, int classes, int m, bm::TopC* topc) {
+  if (m <= 0) return;
+  RT_LAUNCH(k_ctc_beam_topc, dim3(m), dim3(64), 0, st, logits, ld, classes, m, topc);
+}
+
+// The prefix beam search of one chunk's lines: one workgroup of MAX_BEAM * TOP_C = 256 threads per line, T steps in sequence.
+// The beam -- per member its trie node, that node's parent, its last class, its length, pb and pnb -- lives in LDS twice (this
+// step's and the next's); so do the members' totals, the stay values and the totals of the step's bm::CANDS candidates.  Thread
+// (j, r) = (tid / TOP_C, tid % TOP_C) owns ext_{j,r}; thread j < MAX_BEAM also owns stay_j.  A step, between barriers:
+//   A  thread j: total_j, stay_j's pb' and pnb' (one gathered logit: l[t][last_j]); every thread: its class of K_t;
+//   B  thread (j, r): its pnb'; a scan of the beam for the member that IS string_j + c (parent == node_j && last == c): found,
+//      it folds its value into that member's stay pnb' -- the only thread that can (ctc_beam.h "merge") -- and has no candidate;
+//   C  thread j: stay_j's total;
+//   D  every candidate counts the candidates that rank before it (cc::better over the totals in LDS, broadcast reads): that
+//      number is its place in the new beam, B or more: it is out.  No sort, no atomics, and the rule's total order to the bit.
+//      A surviving extension then looks its string up among its parent's children (read only);
+//   E  ... and, not found, creates node 1 + t B + place (no counter: the place is unique) and pushes it onto its parent's list
+//      with one atomic exchange of the head; the survivors write the next beam, whose size is the largest place + 1.
+// The trie is in global memory (ctc_beam.h "Device form"): what one step writes the next reads behind a barrier, within one
+// workgroup.  At the end thread k < N walks hypothesis k's nodes to the root and writes its tokens back to front.
+// Bounds: a row index is < the chunk's rows (a line's rows are resident together), a node id <= T B < bm::nodes_of(T, B), a
+// token slot < N T.
+__global__ __launch_bounds__(256) void k_ctc_beam_search(const float* __restrict__ logits, int ld, const float* __restrict__ lse,
+                                                         const bm::TopC* __restrict__ topc, const bm::Line* __restrict__ lines,
+                                                         int chunk_row0, int B, int nbest, bm::Node* nodes,
+                                                         bm::Beam* __restrict__ beams, int* __restrict__ tokens,
+                                                         int* __restrict__ counts) {
+  constexpr int MB = bm::MAX_BEAM, TC = bm::TOP_C;
+  static_assert(MB * TC == 256 && bm::CANDS == MB + 256, "one thread per extension");
+  __shared__ int s_node[2][MB], s_par[2][MB], s_last[2][MB], s_len[2][MB], s_n[2];
+  __shared__ float s_pb[2][MB], s_pnb[2][MB], s_tot[MB], s_spb[MB], s_spnb[MB], s_cand[bm::CANDS];
+  const int tid = threadIdx.x, j = tid / TC, r = tid % TC;
+  const bm::Line ln = lines[blockIdx.x];
+  const int T = ln.T;
+  if (T <= 0) { if (tid == 0) counts[ln.slot] = 0; return; }   // (block-uniform)
+  bm::Node* nd = nodes + ln.lex;
+  const int n_nodes = (int)bm::nodes_of(T, B);
+  const long long row0 = ln.row0 - chunk_row0;
+  if (tid == 0) {
+    nd[0] = bm::Node{-1, 0, -1, -1};
+    s_node[0][0] = 0; s_par[0][0] = -1; s_last[0][0] = 0; s_len[0][0] = 0; s_pb[0][0] = 0.0f; s_pnb[0][0] = -INFINITY; s_n[0] = 1;
+  }
+  __syncthreads();
+  int cur = 0;
+  for (int t = 0; t < T; t++) {
+    const int nxt = cur ^ 1, n = s_n[cur];
+    const float* l = logits + (row0 + t) * ld;
+    const float ls = lse[row0 + t];
+    const int c = topc[row0 + t].id[r];
+    const float lc = topc[row0 + t].logit[r];
+    // A
+    if (tid < n) {
+      const int last = s_last[cur][tid];
+      const float tot = bm::total_of(s_pb[cur][tid], s_pnb[cur][tid]);
+      s_tot[tid] = tot;
+      s_spb[tid] = bm::stay_pb(tot, l[0] - ls);
+      s_spnb[tid] = bm::stay_pnb(s_pnb[cur][tid], last, l[last] - ls);
+    }
+    if (tid == 0) s_n[nxt] = 0;
+    __syncthreads();
+    // B
+    const bool ext = j < n && c != cc::EMPTY_ID;
+    const int node = ext ? s_node[cur][j] : 0;
+    float v = -INFINITY; int target = -1;
+    if (ext) {
+      v = bm::ext_pnb(s_pb[cur][j], s_tot[j], c == s_last[cur][j], lc - ls);
+      for (int q = 0; q < n; q++)
+        if (s_par[cur][q] == node && s_last[cur][q] == c) target = q;
+      if (target >= 0) s_spnb[target] = bm::merged(s_spnb[target], v);
+    }
+    s_cand[MB + tid] = ext && target < 0 ? bm::total_of(-INFINITY, v) : -INFINITY;
+    __syncthreads();
+    // C
+    if (tid < MB) s_cand[tid] = tid < n ? bm::total_of(s_spb[tid], s_spnb[tid]) : -INFINITY;
+    __syncthreads();
+    // D
+    const float ev = s_cand[MB + tid], sv = tid < MB ? s_cand[tid] : -INFINITY;
+    int eplace = bm::CANDS, splace = bm::CANDS;
+    if (bm::alive(ev)) {
+      eplace = 0;
+      for (int k = 0; k < n; k++) eplace += cc::better(s_cand[k], k, ev, MB + tid) ? 1 : 0;
+      for (int k = MB; k < MB + n * TC; k++) eplace += cc::better(s_cand[k], k, ev, MB + tid) ? 1 : 0;
+    }
+    if (bm::alive(sv)) {
+      splace = 0;
+      for (int k = 0; k < n; k++) splace += cc::better(s_cand[k], k, sv, tid) ? 1 : 0;
+      for (int k = MB; k < MB + n * TC; k++) splace += cc::better(s_cand[k], k, sv, tid) ? 1 : 0;
+    }
+    int found = -1;
+    if (eplace < B)   // (a list's head is only ever changed by an atomic in L2: read it there; tok and next are written once)
+      for (int q = __hip_atomic_load(&nd[node].child, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), k = 0;
+           q >= 0 && q < n_nodes && k < n_nodes && found < 0; q = nd[q].next, k++)   // (the bounds: a list never leaves the line's nodes)
+        if (nd[q].tok == c) found = q;
+    __syncthreads();
+    // E
+    if (eplace < B) {
+      int id = found;
+      if (id < 0) {
+        id = 1 + t * B + eplace;
+        const int old = atomicExch(&nd[node].child, id);
+        nd[id] = bm::Node{node, c, -1, old};
+      }
+      s_node[nxt][eplace] = id; s_par[nxt][eplace] = node; s_last[nxt][eplace] = c; s_len[nxt][eplace] = s_len[cur][j] + 1;
+      s_pb[nxt][eplace] = -INFINITY; s_pnb[nxt][eplace] = v;
+      atomicMax(&s_n[nxt], eplace + 1);
+    }
+    if (splace < B) {
+      s_node[nxt][splace] = s_node[cur][tid]; s_par[nxt][splace] = s_par[cur][tid]; s_last[nxt][splace] = s_last[cur][tid];
+      s_len[nxt][splace] = s_len[cur][tid]; s_pb[nxt][splace] = s_spb[tid]; s_pnb[nxt][splace] = s_spnb[tid];
+      atomicMax(&s_n[nxt], splace + 1);
+    }
+    __syncthreads();
+    cur = nxt;
+  }
+  const int n = s_n[cur], count = n < nbest ? n : nbest;
+  if (tid == 0) counts[ln.slot] = count;
+  if (tid < count) {
+    const int len = s_len[cur][tid];
+    beams[(long long)ln.slot * nbest + tid] = bm::Beam{bm::total_of(s_pb[cur][tid], s_pnb[cur][tid]), len};
+    int* out = tokens + ln.out + (long long)tid * T;
+    int q = s_node[cur][tid];
+    for (int i = len - 1; i >= 0 && q > 0 && q < n_nodes; i--) { out[i] = nd[q].tok; q = nd[q].parent; }
+  }
+}
+void ctc_beam_search(hipStream_t st, const float* logits, int ld, const float* lse, const bm::TopC* topc, const bm::Line* lines,
+                     int n_lines, int chunk_row0, int B, int nbest, bm::Node* nodes, bm::Beam* beams, int* tokens, int* counts) {
+  if (n_lines <= 0) return;
+  RT_LAUNCH(k_ctc_beam_search, dim3(n_lines), dim3(256), 0, st, logits, ld, lse, topc, lines, chunk_row0, B, nbest, nodes, beams,
+            tokens, counts);
+}
+
 // Lexicon snap (ctc_lexicon_align.h).  One wave64 per lexicon line of one chunk, after k_ctc_lexicon_topk has written the line's
 // matches: the wave applies the snap condition to match 0, writes snapped[slot] (0 or 1, for every line it sees) and leaves
 // unless the line snaps.  Then lane s owns state s of the winner (S <= 63) and the forward pass is k_ctc_lexicon_forward's

@@ -244,6 +244,7 @@ void rt_session::rec_tail(const RecTailPlan& p, const SvtrCore& core, const RecT
   }
   if (!p.snap) ctc_lexicon(p, core, t);
   if (p.has_kw()) ctc_keywords(p, core, t);
+  if (p.has_beam()) ctc_beams(p, core, t);
   if (t.cand_k > 0) ctc_candidates(core, t, p.rows, d_row_set);   // (before the caller rewinds the scratch arena z5 lives in)
 }
 
@@ -360,6 +361,27 @@ void rt_session::ctc_keywords(const RecTailPlan& p, const SvtrCore& core, const 
   });
   ProfScope ps(&prof, st, "ctc_keyword_topk");
   pp::ctc_keyword_topk(st, d_lines, n_lines, X.lex, t.d_kw_min, score, span, t.kwh, t.kwn);
+}
+
+void rt_session::ctc_beams(const RecTailPlan& p, const SvtrCore& core, const RecTail& t) {
+  const int n_lines = (int)p.blines.size();
+  if (n_lines <= 0 || t.beam_b <= 0) return;
+  const bm::Line* d_lines = staged(*this, p.blines); const int* d_rows = staged(*this, p.brows);
+  bm::Node* nodes = scratch.alloc<bm::Node>((size_t)std::max<long long>(p.bnodes, 1));   // (the kernel initialises what it reads)
+  const int cap = line_chunks(p.blines, t, no_chunk_work);
+  LogitsChunk lc(*this, core, t.z5, cap);
+  float* lse = scratch.alloc<float>((size_t)cap); bm::TopC* topc = scratch.alloc<bm::TopC>((size_t)cap);
+  line_chunks(p.blines, t, [&](int i0, int i1, int r0, int m) {   // (the chunks share lse and topc too)
+    if (m > 0) {
+      lc.run(d_rows + r0, m);
+      { ProfScope ps(&prof, st, "ctc_row_lse");
+        pp::ctc_row_lse(st, lc.logits, lc.ld, core.classes, m, lse); }
+      ProfScope ps(&prof, st, "ctc_beam_topc");
+      pp::ctc_beam_topc(st, lc.logits, lc.ld, core.classes, m, topc);
+    }
+    ProfScope ps(&prof, st, "ctc_beam_search");
+    pp::ctc_beam_search(st, lc.logits, lc.ld, lse, topc, d_lines + i0, i1 - i0, r0, t.beam_b, t.beam_n, nodes, t.bmrec, t.bmtok, t.bmn);
+  });
 }
 
 int rt_session::charset_create(const char* utf8, size_t len, const int32_t* ids, int n_ids) {

@@ -1,11 +1,12 @@
 // What the CTC tail of one rec group works on (rt_session::rec_tail, rec_tail.cpp), decided on the host in one place: the charset
-// row tables, the lexicon, pattern and keyword lines with their rows and tables, and the questions whose answers order the launches.  The
+// row tables, the lexicon, pattern, keyword and beam lines with their rows and tables, and the questions whose answers order the launches.  The
 // pipeline (rec_groups) and the debug hooks (rt_debug_ctc_*) both go through it.  Plain C++ as lc_plan.h: built and checked
 // without a GPU (tests/test_rec_tail_plan_cpu.py).
 #pragma once
 #include <algorithm>
 #include <vector>
 
+#include "ctc_beam.h"
 #include "ctc_keyword.h"
 #include "ctc_lexicon.h"
 #include "ctc_pattern.h"
@@ -42,19 +43,30 @@ struct RecTailPlan {
   long long ktable = 0; int kmax_waves = 0;
   bool has_kw() const { return !klines.empty(); }   // (a keyword line without a time step counts)
   bool ktable_fits() const { return ktable <= lx::MAX_GROUP_TABLE; }
+  // rec beams (ctc_beam.h; a session option, so every line of the group or none): the lines in line order (row0 = the sum of the
+  // earlier ones' T, lex = the first of the line's trie nodes, slot = the line's index in the call, out = the first of its N T
+  // token slots), their rows line after line, and the trie nodes of the group, the sum of bm::nodes_of(T, B) (rec_groups refuses
+  // a group whose trie does not fit)
+  std::vector<bm::Line> blines; std::vector<int> brows;
+  long long bnodes = 0;
+  bool has_beam() const { return !blines.empty(); }   // (a line without a time step counts: it reports 0 hypotheses)
+  bool bnodes_fit() const { return bnodes <= bm::MAX_GROUP_NODES; }
   // the net must hand out the head's input: some logits are recomputed
-  bool needs_z5(int cand_k) const { return cand_k > 1 || !crows.empty() || has_lex() || has_pat() || has_kw(); }
+  bool needs_z5(int cand_k) const { return cand_k > 1 || !crows.empty() || has_lex() || has_pat() || has_kw() || has_beam(); }
 };
 
 // The session's stores the plan reads: lexicon k is lex.lex[k - 1] and snaps where snap_min[k - 1] > 0 (null: never); pattern k is
 // pat->pats[k - 1] (null: no line has one); keyword list k is kw->lex[k - 1] (null: no line has one)
 struct RecStores { const lx::Tables& lex; const float* snap_min; const pt::Tables* pat; const lx::Tables* kw = nullptr; };
 
-// Lines [l0, l1) of a call: line li has the time steps [tok_off[li], tok_off[li + 1]) and the options line_opts[li] (rec_line_opts.h)
-inline RecTailPlan rec_tail_plan(const long long* tok_off, int l0, int l1, const RecLineOpts* line_opts, const RecStores& st) {
+// Lines [l0, l1) of a call: line li has the time steps [tok_off[li], tok_off[li + 1]) and the options line_opts[li] (rec_line_opts.h);
+// beam_b > 0: the call's rec beam (rt_set_rec_beam: width and hypotheses per line)
+inline RecTailPlan rec_tail_plan(const long long* tok_off, int l0, int l1, const RecLineOpts* line_opts, const RecStores& st,
+                                 int beam_b = 0, int beam_n = 0) {
   RecTailPlan p;
   const long long t0 = tok_off[l0];
   p.rows = tok_off[l1] - t0;
+  long long btok = 0;
   bool restricted = false;
   for (int li = l0; li < l1 && !restricted; li++) restricted = line_opts[li].charset > 0 && tok_off[li + 1] > tok_off[li];
   if (restricted) p.row_set.resize((size_t)p.rows);
@@ -79,6 +91,12 @@ inline RecTailPlan rec_tail_plan(const long long* tok_off, int l0, int l1, const
       p.ktable += x.n;
       p.kmax_waves = std::max(p.kmax_waves, lx::waves_of(x));
     }
+    if (beam_b > 0) {
+      p.blines.push_back(bm::Line{(int)p.brows.size(), T, (int)p.bnodes, li, btok});
+      for (int t = 0; t < T; t++) p.brows.push_back(r0 + t);
+      p.bnodes += bm::nodes_of(T, beam_b);
+      btok += (long long)beam_n * T;
+    }
     if (o.lexicon <= 0) continue;
     const lx::Lex& x = st.lex.lex[(size_t)o.lexicon - 1];
     p.lines.push_back(lx::Line{(int)p.lrows.size(), T, o.lexicon - 1, li, p.table});
@@ -93,11 +111,11 @@ inline RecTailPlan rec_tail_plan(const long long* tok_off, int l0, int l1, const
 // drivers hold them: lexicon k is tb.lex[k - 1], snap_min, ptb and ktb as RecStores'
 inline RecTailPlan rec_tail_plan(const long long* tok_off, int l0, int l1, const int* line_set, const int* line_lex, const lx::Tables& tb,
                                  const float* snap_min, const int* line_pat = nullptr, const pt::Tables* ptb = nullptr,
-                                 const int* line_kw = nullptr, const lx::Tables* ktb = nullptr) {
+                                 const int* line_kw = nullptr, const lx::Tables* ktb = nullptr, int beam_b = 0, int beam_n = 0) {
   std::vector<RecLineOpts> opts((size_t)l1);
   for (int li = l0; li < l1; li++)
     opts[(size_t)li] = {line_set ? line_set[li] : 0, line_lex ? line_lex[li] : 0, line_pat ? line_pat[li] : 0, line_kw ? line_kw[li] : 0};
-  return rec_tail_plan(tok_off, l0, l1, opts.data(), RecStores{tb, snap_min, ptb, ktb});
+  return rec_tail_plan(tok_off, l0, l1, opts.data(), RecStores{tb, snap_min, ptb, ktb}, beam_b, beam_n);
 }
 
 }  // namespace rt

@@ -550,6 +550,11 @@ struct Pipeline {
   // rec keywords (ctc_keyword.h; any.keywords): per line kw::HITS hit slots and the number of hits (written for the lines that
   // carry a list only)
   kw::Hit* d_kwh = nullptr; int* d_kwn = nullptr; kw::Hit* h_kwh = nullptr; int* h_kwn = nullptr;
+  // rec beams (ctc_beam.h) of this call; beam_b = 0: off.  Per line its count and beam_n records; the token pool: line li's
+  // hypothesis k at [(tok_off[li] * beam_n) + k * T]
+  int beam_b = 0, beam_n = 0;
+  int* d_bmn = nullptr; bm::Beam* d_bmrec = nullptr; int* d_bmtok = nullptr;
+  int* h_bmn = nullptr; bm::Beam* h_bmrec = nullptr; int* h_bmtok = nullptr;
 };
 
 // Launch groups: items [g0, end) where the group always takes its first item; with max_items > 0 it takes up to max_items items,
@@ -926,6 +931,10 @@ void rec_groups(rt_session& s, Pipeline& P) {
   }
   if (P.any.pattern) P.d_pat = s.arena.alloc<int>((size_t)4 * P.NLp);
   if (P.any.keywords) { P.d_kwh = s.arena.alloc<kw::Hit>((size_t)P.NLp * kw::HITS); P.d_kwn = s.arena.alloc<int>(P.NLp); }
+  if (P.beam_b > 0) {
+    P.d_bmn = s.arena.alloc<int>(P.NLp); P.d_bmrec = s.arena.alloc<bm::Beam>((size_t)P.NLp * P.beam_n);
+    P.d_bmtok = s.arena.alloc<int>(ntok * (size_t)P.beam_n);
+  }
   static const long long REC_GROUP_PX = getenv("RT_REC_GROUP_PX") ? atoll(getenv("RT_REC_GROUP_PX")) : (long long)24000000;  // measured sweet spot (profiles/README.md)
   for (int l0 = 0; l0 < P.NL;) {
     const int l1 = group_end(l0, P.NL, 0, REC_GROUP_PX, [&](int l) { return (long long)rh * P.line_W[l]; });
@@ -951,7 +960,8 @@ void rec_groups(rt_session& s, Pipeline& P) {
     const long long t0 = P.tok_off[l0];
     const rt_lexicons& X = *s.lexicons;
     const rt_keywords& KW = *s.keywords;
-    const RecTailPlan tail = rec_tail_plan(P.tok_off.data(), l0, l1, P.line_opts.data(), RecStores{X.tb, X.snap, &s.patterns->tb, &KW.tb});
+    const RecTailPlan tail = rec_tail_plan(P.tok_off.data(), l0, l1, P.line_opts.data(), RecStores{X.tb, X.snap, &s.patterns->tb, &KW.tb},
+                                           P.beam_b, P.beam_n);
     if (!tail.table_fits())
       throw RtError(RT_ERR_CAPACITY, "rec lexicons: " + std::to_string(tail.lines.size()) + " lines of one rec group carry lexicons of " +
                                          std::to_string(tail.table) + " entries in all, more than the " + std::to_string(lx::MAX_GROUP_TABLE) +
@@ -960,7 +970,11 @@ void rec_groups(rt_session& s, Pipeline& P) {
       throw RtError(RT_ERR_CAPACITY, "rec keywords: " + std::to_string(tail.klines.size()) + " lines of one rec group carry keyword lists of " +
                                          std::to_string(tail.ktable) + " entries in all, more than the " + std::to_string(lx::MAX_GROUP_TABLE) +
                                          " scores a group's table holds: use smaller keyword lists or fewer keyword lines per call");
-    const float* z5 = nullptr;   // the head's input, for the candidates', the charsets', the lexicons' and the keywords' logits
+    if (!tail.bnodes_fit())
+      throw RtError(RT_ERR_CAPACITY, "rec beams: the " + std::to_string(tail.blines.size()) + " lines of one rec group need " +
+                                         std::to_string(tail.bnodes) + " trie nodes at beam " + std::to_string(P.beam_b) + ", more than the " +
+                                         std::to_string(bm::MAX_GROUP_NODES) + " a group's trie holds: use a narrower beam or fewer lines per call");
+    const float* z5 = nullptr;   // the head's input, for the candidates', the charsets', the lexicons', the keywords' and the beams' logits
     { ProfOuter po(&s.prof, s.st, "net/rec");
       s.rec->run(c, x, L0, Lt, d_idx + t0, d_prob + t0, tail.needs_z5(cand_k) ? &z5 : nullptr); }  // fused CTC head: logits never reach HBM
     if (Lt.total != tail.rows) throw RtError(RT_ERR_SHAPE, "token count mismatch");
@@ -980,7 +994,8 @@ void rec_groups(rt_session& s, Pipeline& P) {
                                 P.d_tok + t0, P.d_meta.ntok + l0, P.d_meta.rscore + l0, nullptr, P.d_lexm, P.d_lexn, P.d_lexs, nullptr,
                                 P.d_ccol ? P.d_ccol + t0 : nullptr, P.d_cands ? P.d_cands + t0 * cand_k : nullptr,
                                 words.h_lines ? &words : nullptr, s.patterns->d, P.d_pat, patf(1), patf(2), patf(3),
-                                KW.d, KW.d_min, nullptr, nullptr, P.d_kwh, P.d_kwn};
+                                KW.d, KW.d_min, nullptr, nullptr, P.d_kwh, P.d_kwn,
+                                P.beam_b, P.beam_n, P.d_bmn, P.d_bmrec, P.d_bmtok ? P.d_bmtok + t0 * P.beam_n : nullptr};
     s.rec_tail(tail, s.rec->core(), t);
     l0 = l1;
   }
@@ -1020,6 +1035,13 @@ void line_round_trip(rt_session& s, Pipeline& P) {
     P.h_kwh = s.pinned.alloc<kw::Hit>((size_t)P.NLp * kw::HITS); P.h_kwn = s.pinned.alloc<int>(P.NLp);
     RT_HIP_CHECK(hipMemcpyAsync(P.h_kwh, P.d_kwh, (size_t)P.NLp * kw::HITS * sizeof(kw::Hit), hipMemcpyDeviceToHost, s.st));
     RT_HIP_CHECK(hipMemcpyAsync(P.h_kwn, P.d_kwn, (size_t)P.NLp * sizeof(int), hipMemcpyDeviceToHost, s.st));
+  }
+  if (P.beam_b > 0) {   // (and the beams: counts, records, the token pool)
+    const size_t N = (size_t)P.beam_n;
+    P.h_bmn = s.pinned.alloc<int>(P.NLp); P.h_bmrec = s.pinned.alloc<bm::Beam>((size_t)P.NLp * N); P.h_bmtok = s.pinned.alloc<int>(nt * N);
+    RT_HIP_CHECK(hipMemcpyAsync(P.h_bmn, P.d_bmn, (size_t)P.NLp * sizeof(int), hipMemcpyDeviceToHost, s.st));
+    RT_HIP_CHECK(hipMemcpyAsync(P.h_bmrec, P.d_bmrec, (size_t)P.NLp * N * sizeof(bm::Beam), hipMemcpyDeviceToHost, s.st));
+    if (total_tok > 0) RT_HIP_CHECK(hipMemcpyAsync(P.h_bmtok, P.d_bmtok, (size_t)total_tok * N * sizeof(int), hipMemcpyDeviceToHost, s.st));
   }
   s.sync(); s.check_flags();
 }
@@ -1096,6 +1118,25 @@ void results(const rt_session& s, const Pipeline& P, rt_results& res) {
         }
       }
     }
+    if (P.h_bmn) {   // rec beams: per line its hypotheses, best first; a hypothesis' text from the dictionary as the line's own
+      const int N = P.beam_n;
+      R.beam_n = N; R.bm_count.assign((size_t)nb, 0); R.bm_recs.assign((size_t)nb * N, bm::Beam{0.0f, 0});
+      R.bm_tokens.assign((size_t)nb * N, std::vector<int32_t>()); R.bm_text.assign((size_t)nb * N, std::string());
+      for (int k = 0; k < nb; k++) {
+        const int li = p.first_line + k;
+        const long long T = P.tok_off[li + 1] - P.tok_off[li];
+        R.bm_count[k] = std::min(std::max(P.h_bmn[li], 0), N);
+        for (int q = 0; q < R.bm_count[k]; q++) {
+          bm::Beam& b = R.bm_recs[(size_t)k * N + q];
+          b = P.h_bmrec[(size_t)li * N + q];
+          b.n_tokens = (int32_t)std::min<long long>(std::max(b.n_tokens, 0), T);
+          const int* tk = P.h_bmtok + P.tok_off[li] * N + q * T;
+          R.bm_tokens[(size_t)k * N + q].assign(tk, tk + b.n_tokens);
+          std::string& t = R.bm_text[(size_t)k * N + q];
+          for (int i = 0; i < b.n_tokens; i++) t += s.dict[(size_t)std::min<long long>(std::max(tk[i], 0), (long long)s.dict.size() - 1)];
+        }
+      }
+    }
     if (s.cfg.rec_return_word_box) {   // word quads to original-image coordinates, word texts from the dictionary
       R.words.resize(nb); R.word_text.resize(nb);
       for (int k = 0; k < nb; k++) {
@@ -1138,6 +1179,7 @@ rt_results* rt_session::run_pages(const uint8_t* const* rgb, const int* hs, cons
   Pipeline P{n_pages, mem, det_map_override, std::vector<PageState>((size_t)n_pages)};
   P.regions = regions; P.crop_original = regions != nullptr || cfg.crop_source == 1;
   P.det_tile = set.det_tile; P.det_overlap = set.det_overlap;
+  P.beam_b = set.beam_b; P.beam_n = set.beam_n;
   HostTick tick;
   if (regions) {   // the boxes are given: no resize_both, no detector, no DB post-processing, no first round trip
     region_pages(*this, P, rgb, hs, ws); tick.lap("pre (upload, regions)");

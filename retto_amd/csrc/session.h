@@ -54,6 +54,13 @@ struct rt_results {
     // page quad; empty when no line of the call carried a list
     std::vector<int32_t> kw_id, kw_n;
     std::vector<rt::kw::Hit> kw_hits;
+    // rec beams (ctc_beam.h; rt_set_rec_beam): beam_n = the call's hypotheses per line (0: off, everything below empty); per line
+    // its count and [beam_n] record slots; hypothesis k of line l has its tokens and its text at [l * beam_n + k]
+    int beam_n = 0;
+    std::vector<int32_t> bm_count;
+    std::vector<rt::bm::Beam> bm_recs;
+    std::vector<std::vector<int32_t>> bm_tokens;
+    std::vector<std::string> bm_text;
     std::string json[3];
   };
   std::vector<Page> pages;
@@ -76,8 +83,9 @@ struct LaneWorker {
 };
 
 // What a pipeline call reads of the session's settings, as they were when the call was submitted: the default options of every
-// line (rt_set_rec_charset / _lexicon / _pattern / _keywords, rec_line_opts.h) and the det tiles (rt_set_det_tiles, det_tiles.h; 0 = off)
-struct CallSettings { rt::RecLineOpts rec; int det_tile = 0, det_overlap = 0; };
+// line (rt_set_rec_charset / _lexicon / _pattern / _keywords, rec_line_opts.h), the det tiles (rt_set_det_tiles, det_tiles.h; 0 = off)
+// and the rec beam (rt_set_rec_beam, ctc_beam.h; beam_b = 0: off)
+struct CallSettings { rt::RecLineOpts rec; int det_tile = 0, det_overlap = 0, beam_b = 0, beam_n = 0; };
 
 // One submitted batch (rt_submit_batch): the argument arrays are copied (the PAGES must stay valid until rt_wait_batch), the
 // pages are split over the lanes exactly as rt_run_batch splits them, each lane leaves its part here.
@@ -227,8 +235,11 @@ struct rt_session {
   rt::RecLineOpts rec_default;
   // rt_set_det_tiles (det_tiles.h): pages whose det input is larger than det_tile either way are detected in tiles; 0 = off
   int det_tile = 0, det_overlap = 0;
-  // A helper lane never reads its own rec_default / det_tile / det_overlap: a call carries the main lane's into run_pages
-  CallSettings settings() const { return {rec_default, det_tile, det_overlap}; }
+  // rt_set_rec_beam (ctc_beam.h): every line of the pipeline calls that follow also reports its beam_n most probable strings from
+  // a prefix beam search of width beam_b; 0 = off
+  int beam_b = 0, beam_n = 0;
+  // A helper lane never reads its own rec_default / det_tile / det_overlap / beam_b / beam_n: a call carries the main lane's into run_pages
+  CallSettings settings() const { return {rec_default, det_tile, det_overlap, beam_b, beam_n}; }
   uint8_t* d_word_raw = nullptr;  // rec_return_word_box: wb::raw_class of every dictionary entry (device; owned by the main lane)
   std::string last_error;
   int* d_flags = nullptr;         // [0] thumbnail/resize error flag
@@ -287,10 +298,13 @@ struct rt_session {
     // rec keywords (ctc_keyword.h): the lists' lx::Tables and min_score on the device; kwscore [plan.ktable] and kwspan
     // [plan.ktable][2], or null: taken from `scratch`; the per-line hits and counts, indexed by kw::Line::slot
     rt::lx::DevTables d_kw; const float* d_kw_min; float* kwscore; int* kwspan; rt::kw::Hit* kwh; int* kwn;
+    // rec beams (ctc_beam.h; beam_b > 0 where the plan has beam lines): the width and the hypotheses per line; the per-line counts
+    // [slot], records [slot][beam_n] and the token pool (bm::Line::out)
+    int beam_b = 0, beam_n = 0; int* bmn = nullptr; rt::bm::Beam* bmrec = nullptr; int* bmtok = nullptr;
   };
   // The tail of one rec group behind the net, in the one order that is right: the charsets replace the restricted rows' (idx, prob)
   // before anything reads them; a snap group's lexicons run next, so that the decode reads the snapped lines' aligned rows;
-  // then the patterns, whose matched lines overwrite theirs; pp::ctc_decode; the word boxes; any other group's lexicons; the keywords, which read and write nothing of the others'; the candidates last, for their host wait.  The plan's tables go
+  // then the patterns, whose matched lines overwrite theirs; pp::ctc_decode; the word boxes; any other group's lexicons; the keywords and the beams, which read and write nothing of the others'; the candidates last, for their host wait.  The plan's tables go
   // through `pinned` into `scratch`, where the workspace comes from too: the caller rewinds it per group, after this.
   void rec_tail(const rt::RecTailPlan& plan, const rt::SvtrCore& core, const RecTail& t);
   // rec_return_candidates = K (ctc_candidates.h): kept token j of a line at first row o gets ccol[o + j] and cands[(o + j) * K ...].
@@ -313,6 +327,10 @@ struct rt_session {
   // k_ctc_row_max, k_ctc_keyword_spot -> kwscore / kwspan; then one k_ctc_keyword_topk over all lines -> kwh / kwn.  No host
   // wait, and no value that anything else reads.
   void ctc_keywords(const rt::RecTailPlan& plan, const rt::SvtrCore& core, const RecTail& t);
+  // Rec beams (ctc_beam.h) over the plan's beam lines, chunked as the keyword lines are: row gather, the CTC FC, k_ctc_row_lse,
+  // k_ctc_beam_topc, then k_ctc_beam_search on the resident logits -> bmn / bmrec / bmtok.  The trie comes from `scratch`.  No
+  // host wait, and no value that anything else reads.
+  void ctc_beams(const rt::RecTailPlan& plan, const rt::SvtrCore& core, const RecTail& t);
   // rt_charset_create: compiles the set (rt::compile_charset), stores it and returns its id
   int charset_create(const char* utf8, size_t len, const int32_t* ids, int n_ids);
   // rt_lexicon_create: compiles the entries (rt::compile_lexicon), stores them and returns the lexicon's id
