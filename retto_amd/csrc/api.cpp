@@ -422,24 +422,13 @@ int rt_lexicon_create(rt_session* s, const char* utf8, size_t len, const int32_t
   *lexicon_out = 0;
   return guarded(s, [&] { *lexicon_out = s->lexicon_create(utf8, len, ids, entry_lens, n_id_entries); });
 }
-static const rt_lexicons::Host* lexicon_of(const rt_session* s, int lexicon) {
-  if (!s || !s->lexicons || lexicon < 1 || lexicon > (int)s->lexicons->host.size()) return nullptr;
-  return s->lexicons->host[(size_t)lexicon - 1].get();
-}
-int rt_lexicon_entries(const rt_session* s, int lexicon) {
-  const rt_lexicons::Host* h = lexicon_of(s, lexicon);
-  return h ? (int)h->lens.size() : 0;
-}
+static const rt_entry_store::Host* lexicon_of(const rt_session* s, int lexicon) { return s && s->lexicons ? s->lexicons->list(lexicon) : nullptr; }
+int rt_lexicon_entries(const rt_session* s, int lexicon) { return s && s->lexicons ? s->lexicons->entries(lexicon) : 0; }
 int rt_lexicon_entry(const rt_session* s, int lexicon, int entry, const int32_t** ids) {
-  const rt_lexicons::Host* h = lexicon_of(s, lexicon);
-  if (!h || entry < 0 || entry >= (int)h->lens.size()) return 0;
-  if (ids) *ids = h->ids.data() + h->off[(size_t)entry];
-  return h->lens[(size_t)entry];
+  return s && s->lexicons ? s->lexicons->entry(lexicon, entry, ids) : 0;
 }
 const char* rt_lexicon_entry_text(const rt_session* s, int lexicon, int entry) {
-  const rt_lexicons::Host* h = lexicon_of(s, lexicon);
-  if (!h || entry < 0 || entry >= (int)h->text.size()) return nullptr;
-  return h->text[(size_t)entry].c_str();
+  return s && s->lexicons ? s->lexicons->entry_text(lexicon, entry) : nullptr;
 }
 int rt_keywords_create(rt_session* s, const char* utf8, size_t len, const int32_t* ids, const int32_t* entry_lens, int n_id_entries,
                        float min_score, int* list_out) {
@@ -448,24 +437,13 @@ int rt_keywords_create(rt_session* s, const char* utf8, size_t len, const int32_
   *list_out = 0;
   return guarded(s, [&] { *list_out = s->keywords_create(utf8, len, ids, entry_lens, n_id_entries, min_score); });
 }
-static const rt_lexicons::Host* keywords_of(const rt_session* s, int list) {
-  if (!s || !s->keywords || list < 1 || list > (int)s->keywords->host.size()) return nullptr;
-  return s->keywords->host[(size_t)list - 1].get();
-}
-int rt_keywords_entries(const rt_session* s, int list) {
-  const rt_lexicons::Host* h = keywords_of(s, list);
-  return h ? (int)h->lens.size() : 0;
-}
+static const rt_entry_store::Host* keywords_of(const rt_session* s, int list) { return s && s->keywords ? s->keywords->list(list) : nullptr; }
+int rt_keywords_entries(const rt_session* s, int list) { return s && s->keywords ? s->keywords->entries(list) : 0; }
 int rt_keywords_entry(const rt_session* s, int list, int entry, const int32_t** ids) {
-  const rt_lexicons::Host* h = keywords_of(s, list);
-  if (!h || entry < 0 || entry >= (int)h->lens.size()) return 0;
-  if (ids) *ids = h->ids.data() + h->off[(size_t)entry];
-  return h->lens[(size_t)entry];
+  return s && s->keywords ? s->keywords->entry(list, entry, ids) : 0;
 }
 const char* rt_keywords_entry_text(const rt_session* s, int list, int entry) {
-  const rt_lexicons::Host* h = keywords_of(s, list);
-  if (!h || entry < 0 || entry >= (int)h->text.size()) return nullptr;
-  return h->text[(size_t)entry].c_str();
+  return s && s->keywords ? s->keywords->entry_text(list, entry) : nullptr;
 }
 float rt_keywords_min_score(const rt_session* s, int list) {
   return keywords_of(s, list) ? s->keywords->min_score[(size_t)list - 1] : NAN;

@@ -381,21 +381,21 @@ RT_API int rt_debug_attention(rt_session* s, const float* qkv, long long rows, c
 // One rec group on host arrays through rt_session::rec_tail, the tail rec_groups runs per group, on the plan of rec_tail_plan.h
 // over the caller's lines: the features inside a larger zeroed allocation, as z5 sits inside the scratch arena; an FC packed by
 // pack_linear; the lines' geometry as the token level gives it; idx / prob the caller's (null: zeros, the decode's results are
-// then thrown away).  An entry adds its own inputs and outputs to `t`, run()s, and downloads.
+// then thrown away); opts: the lines' options (lines_with), whose ids count into `stores`; beam_b > 0: every line carries the beam.
+// An entry adds its own kind's tables, inputs and outputs to `t`, run()s, and downloads.
 struct TailHook {
   rt_session* s; size_t nr;
   WeightStore ws; SvtrCore core; DevBufs bufs;
-  RecTailPlan plan; rt_session::RecTail t{};
+  RecTailPlan plan; rt_session::RecTail t;
   TailHook(rt_session* s_, const float* z5, const float* W, const float* bias, int N, long long rows, const int32_t* tokens_per_line,
-           int n_lines, const int32_t* line_set, const int32_t* line_lex, const lx::Tables& tb, const float* snap_min, const int32_t* idx,
-           const float* prob, int K, int chunk_rows, const int32_t* line_pat = nullptr, const pt::Tables* ptb = nullptr,
-           const int32_t* line_kw = nullptr, const lx::Tables* ktb = nullptr, int beam_b = 0, int beam_n = 0)
+           int n_lines, const int32_t* idx, const float* prob, int K, int chunk_rows, const std::vector<RecLineOpts>& opts,
+           const RecStores& stores, int beam_b = 0, int beam_n = 0)
       : s(s_), nr((size_t)std::max<long long>(rows, 1)) {
     s->begin_call();
     std::vector<long long> off((size_t)n_lines + 1, 0);
     std::partial_sum(tokens_per_line, tokens_per_line + n_lines, off.begin() + 1);   // (below 2^30: the entries' own check)
-    plan = rec_tail_plan(off.data(), 0, n_lines, line_set, line_lex, tb, snap_min, line_pat, ptb, line_kw, ktb, beam_b, beam_n);
-    t.beam_b = beam_b; t.beam_n = beam_n;
+    plan = rec_tail_plan(off.data(), 0, n_lines, opts.data(), stores, beam_b, beam_n);
+    t.beam.b = beam_b; t.beam.n = beam_n;
     core.classes = N;
     if (plan.needs_z5(K)) {
       core.fc = pack_linear(ws, W, bias, core.D, N);
@@ -407,19 +407,31 @@ struct TailHook {
     t.prob = bufs.upload(prob ? prob : reinterpret_cast<const float*>(zeros.data()), prob ? (size_t)rows : nr);
     t.lines = Ragged(tokens_per_line, n_lines).upload(bufs); t.n_lines = n_lines;
     t.tok = bufs.alloc<int>(nr); t.ntok = bufs.alloc<int>(n_lines); t.rscore = bufs.alloc<float>(n_lines);
-    t.cand_k = K; t.chunk_rows = chunk_rows;
+    t.cand.k = K; t.chunk_rows = chunk_rows;
   }
   // rec_return_candidates: what the kernels write starts as the caller's values
   void candidates(const int32_t* cols, const rt_candidate* cands) {
-    t.ccol = bufs.alloc<int>(nr); t.cands = bufs.alloc<cc::Cand>(nr * t.cand_k); DevBufs::put(t.ccol, cols, (size_t)plan.rows);
-    DevBufs::put(t.cands, reinterpret_cast<const cc::Cand*>(cands), (size_t)plan.rows * t.cand_k);
+    t.cand.col = bufs.alloc<int>(nr); t.cand.cands = bufs.alloc<cc::Cand>(nr * t.cand.k); DevBufs::put(t.cand.col, cols, (size_t)plan.rows);
+    DevBufs::put(t.cand.cands, reinterpret_cast<const cc::Cand*>(cands), (size_t)plan.rows * t.cand.k);
   }
   void run() { s->rec_tail(plan, core, t); RT_HIP_CHECK(hipStreamSynchronize(s->st)); }
   void download_candidates(int32_t* cols, rt_candidate* cands) const {
-    DevBufs::download(cols, t.ccol, (size_t)plan.rows);
-    DevBufs::download(reinterpret_cast<cc::Cand*>(cands), t.cands, (size_t)plan.rows * t.cand_k);
+    DevBufs::download(cols, t.cand.col, (size_t)plan.rows);
+    DevBufs::download(reinterpret_cast<cc::Cand*>(cands), t.cand.cands, (size_t)plan.rows * t.cand.k);
   }
 };
+// the lists of a lexicon or keyword entry as lx::Tables: list k has the entries [first_entry[k], first_entry[k + 1]), whose ids
+// follow each other in entry_ids
+static lx::Tables tables_of(const int32_t* entry_ids, const int32_t* entry_lens, const int32_t* first_entry, int n_lists) {
+  lx::Tables tb;
+  long long io = 0;
+  for (int k = 0; k < n_lists; k++) {
+    const int e0 = first_entry[k], n = first_entry[k + 1] - e0;
+    tb.add(entry_ids + io, entry_lens + e0, n);
+    for (int j = 0; j < n; j++) io += entry_lens[e0 + j];
+  }
+  return tb;
+}
 
 // rt_config.rec_return_candidates' device path on host arrays: pp::ctc_decode for the token counts, then the candidates.
 RT_API int rt_debug_ctc_candidates(rt_session* s, const float* z5, const float* W, const float* bias, int N, const int32_t* idx,
@@ -430,7 +442,7 @@ RT_API int rt_debug_ctc_candidates(rt_session* s, const float* z5, const float* 
   RT_REQUIRE(cand_args_ok(z5, W, N, idx, prob, tokens_per_line, n_lines, K, cands_out, cols_out, n_tokens_out, &rows) && chunk_rows >= 0,
              s, "rt_debug_ctc_candidates: bad argument");
   return guarded(s, [&] {
-    TailHook h(s, z5, W, bias, N, rows, tokens_per_line, n_lines, nullptr, nullptr, lx::Tables(), nullptr, idx, prob, K, chunk_rows);
+    TailHook h(s, z5, W, bias, N, rows, tokens_per_line, n_lines, idx, prob, K, chunk_rows, std::vector<RecLineOpts>((size_t)n_lines), RecStores{});
     h.candidates(cols_out, cands_out);
     h.run();
     DevBufs::download(n_tokens_out, h.t.ntok, (size_t)n_lines);
@@ -449,9 +461,10 @@ RT_API int rt_debug_ctc_charset(rt_session* s, const float* z5, const float* W, 
                              scores_out, cands_out, cols_out, &rows) && chunk_rows >= 0,
              s, "rt_debug_ctc_charset: bad argument");
   return guarded(s, [&] {
-    TailHook h(s, z5, W, bias, N, rows, tokens_per_line, n_lines, line_set, nullptr, lx::Tables(), nullptr, idx, prob, K, chunk_rows);
-    h.t.words = cs::mask_words(N);
-    h.t.masks = n_sets > 0 ? h.bufs.upload(masks, (size_t)n_sets * h.t.words) : nullptr;
+    TailHook h(s, z5, W, bias, N, rows, tokens_per_line, n_lines, idx, prob, K, chunk_rows, lines_with(n_lines, &RecLineOpts::charset, line_set),
+               RecStores{});
+    h.t.charsets.words = cs::mask_words(N);
+    h.t.charsets.masks = n_sets > 0 ? h.bufs.upload(masks, (size_t)n_sets * h.t.charsets.words) : nullptr;
     DevBufs::put(h.t.tok, tokens_out, (size_t)rows);
     if (K > 0) h.candidates(cols_out, cands_out);
     h.run();
@@ -470,37 +483,33 @@ static void debug_ctc_lexicon(rt_session* s, const float* z5, const float* W, co
                               const int32_t* lex_first_entry, int n_lex, int chunk_rows, long long rows,
                               float* loglik_out, rt_lexicon_match* matches_out, int32_t* n_matches_out, const float* lex_min_post,
                               int32_t* idx, float* prob, int32_t* snapped_out, float* vit_out) {
-  lx::Tables tb;
-  long long io = 0;
-  for (int k = 0; k < n_lex; k++) {
-    const int e0 = lex_first_entry[k], n = lex_first_entry[k + 1] - e0;
-    tb.add(entry_ids + io, entry_lens + e0, n);
-    for (int j = 0; j < n; j++) io += entry_lens[e0 + j];
-  }
-  TailHook h(s, z5, W, bias, N, rows, tokens_per_line, n_lines, nullptr, line_lex, tb, lex_min_post, idx, prob, 0, chunk_rows);
+  const lx::Tables tb = tables_of(entry_ids, entry_lens, lex_first_entry, n_lex);
+  TailHook h(s, z5, W, bias, N, rows, tokens_per_line, n_lines, idx, prob, 0, chunk_rows, lines_with(n_lines, &RecLineOpts::lexicon, line_lex),
+             RecStores{&tb, lex_min_post});
+  rt_entry_store X;   // (the tables on the device, freed on every way out)
+  X.set(tb);
   for (int i = 0; i < n_lines; i++) {   // (a line without a lexicon has no match; the kernel, where it runs, writes every lexicon line's flag again)
     if (line_lex[i] <= 0) n_matches_out[i] = 0;
     else if (lex_min_post) snapped_out[i] = 0;
   }
-  rt_session::RecTail& t = h.t;
-  t.d_lex = lx::DevTables{h.bufs.upload(tb.ids.data(), tb.ids.size()), h.bufs.upload(tb.entries.data(), tb.entries.size()),
-                          h.bufs.upload(tb.order.data(), tb.order.size()), h.bufs.upload(tb.lex.data(), tb.lex.size())};
+  rt_session::RecTail::Lexicon& t = h.t.lexicon;
+  t.d = X.d;
   // (what the kernels write starts as the caller's values: a slot they leave alone comes back untouched)
   t.loglik = h.bufs.alloc<float>((size_t)h.plan.table);
   if (loglik_out) DevBufs::put(t.loglik, loglik_out, (size_t)h.plan.table);
-  t.lexm = h.bufs.upload(reinterpret_cast<const lx::Match*>(matches_out), (size_t)n_lines * lx::MATCHES);
-  t.lexn = h.bufs.upload(n_matches_out, (size_t)n_lines);
+  t.matches = h.bufs.upload(reinterpret_cast<const lx::Match*>(matches_out), (size_t)n_lines * lx::MATCHES);
+  t.n = h.bufs.upload(n_matches_out, (size_t)n_lines);
   if (lex_min_post) {
     t.d_min_post = h.bufs.upload(lex_min_post, (size_t)n_lex);
-    t.lexs = h.bufs.upload(snapped_out, (size_t)n_lines); t.vit = h.bufs.upload(vit_out, (size_t)n_lines);
+    t.snapped = h.bufs.upload(snapped_out, (size_t)n_lines); t.vit = h.bufs.upload(vit_out, (size_t)n_lines);
   }
   h.run();
   if (loglik_out) DevBufs::download(loglik_out, t.loglik, (size_t)h.plan.table);
-  DevBufs::download(reinterpret_cast<lx::Match*>(matches_out), t.lexm, (size_t)n_lines * lx::MATCHES);
-  DevBufs::download(n_matches_out, t.lexn, (size_t)n_lines);
+  DevBufs::download(reinterpret_cast<lx::Match*>(matches_out), t.matches, (size_t)n_lines * lx::MATCHES);
+  DevBufs::download(n_matches_out, t.n, (size_t)n_lines);
   if (lex_min_post) {
-    DevBufs::download(idx, t.idx, (size_t)rows); DevBufs::download(prob, t.prob, (size_t)rows);
-    DevBufs::download(snapped_out, t.lexs, (size_t)n_lines); DevBufs::download(vit_out, t.vit, (size_t)n_lines);
+    DevBufs::download(idx, h.t.idx, (size_t)rows); DevBufs::download(prob, h.t.prob, (size_t)rows);
+    DevBufs::download(snapped_out, t.snapped, (size_t)n_lines); DevBufs::download(vit_out, t.vit, (size_t)n_lines);
   }
 }
 RT_API int rt_debug_ctc_lexicon(rt_session* s, const float* z5, const float* W, const float* bias, int N,
@@ -553,18 +562,19 @@ RT_API int rt_debug_ctc_pattern(rt_session* s, const float* z5, const float* W, 
   return guarded(s, [&] {
     pt::Tables tb;
     for (const pt::Rule& r : rules) tb.add(r);
-    TailHook h(s, z5, W, bias, N, rows, tokens_per_line, n_lines, nullptr, nullptr, lx::Tables(), nullptr, idx, prob, 0, chunk_rows, line_pat, &tb);
-    rt_session::RecTail& t = h.t;
-    t.d_pat = pt::DevTables{h.bufs.upload(tb.pats.data(), tb.pats.size()), h.bufs.upload(tb.pair_c.data(), tb.pair_c.size()),
-                            h.bufs.upload(tb.pair_pb.data(), tb.pair_pb.size()), h.bufs.upload(tb.pair_pe.data(), tb.pair_pe.size()),
-                            h.bufs.upload(tb.seg.data(), tb.seg.size()), h.bufs.upload(tb.preds.data(), tb.preds.size())};
+    TailHook h(s, z5, W, bias, N, rows, tokens_per_line, n_lines, idx, prob, 0, chunk_rows, lines_with(n_lines, &RecLineOpts::pattern, line_pat),
+               RecStores{nullptr, nullptr, &tb});
+    rt_session::RecTail::Pattern& t = h.t.pattern;
+    t.d = pt::DevTables{h.bufs.upload(tb.pats.data(), tb.pats.size()), h.bufs.upload(tb.pair_c.data(), tb.pair_c.size()),
+                        h.bufs.upload(tb.pair_pb.data(), tb.pair_pb.size()), h.bufs.upload(tb.pair_pe.data(), tb.pair_pe.size()),
+                        h.bufs.upload(tb.seg.data(), tb.seg.size()), h.bufs.upload(tb.preds.data(), tb.preds.size())};
     // (what the kernel writes starts as the caller's values: a slot it leaves alone comes back untouched)
-    t.patm = h.bufs.upload(matched_out, (size_t)n_lines); t.patv = h.bufs.upload(vit_out, (size_t)n_lines);
-    t.patlp = h.bufs.upload(logprob_out, (size_t)n_lines); t.patfree = h.bufs.upload(free_out, (size_t)n_lines);
+    t.matched = h.bufs.upload(matched_out, (size_t)n_lines); t.vit = h.bufs.upload(vit_out, (size_t)n_lines);
+    t.logprob = h.bufs.upload(logprob_out, (size_t)n_lines); t.free_logprob = h.bufs.upload(free_out, (size_t)n_lines);
     h.run();
-    DevBufs::download(idx, t.idx, (size_t)rows); DevBufs::download(prob, t.prob, (size_t)rows);
-    DevBufs::download(matched_out, t.patm, (size_t)n_lines); DevBufs::download(vit_out, t.patv, (size_t)n_lines);
-    DevBufs::download(logprob_out, t.patlp, (size_t)n_lines); DevBufs::download(free_out, t.patfree, (size_t)n_lines);
+    DevBufs::download(idx, h.t.idx, (size_t)rows); DevBufs::download(prob, h.t.prob, (size_t)rows);
+    DevBufs::download(matched_out, t.matched, (size_t)n_lines); DevBufs::download(vit_out, t.vit, (size_t)n_lines);
+    DevBufs::download(logprob_out, t.logprob, (size_t)n_lines); DevBufs::download(free_out, t.free_logprob, (size_t)n_lines);
   });
 }
 
@@ -580,33 +590,28 @@ RT_API int rt_debug_ctc_keywords(rt_session* s, const float* z5, const float* W,
   RT_REQUIRE(bad.empty(), s, "rt_debug_ctc_keywords: " + bad);
   RT_REQUIRE(chunk_rows >= 0, s, "rt_debug_ctc_keywords: chunk_rows is negative");
   return guarded(s, [&] {
-    lx::Tables tb;
-    long long io = 0;
-    for (int k = 0; k < n_kw; k++) {
-      const int e0 = kw_first_entry[k], n = kw_first_entry[k + 1] - e0;
-      tb.add(entry_ids + io, entry_lens + e0, n);
-      for (int j = 0; j < n; j++) io += entry_lens[e0 + j];
-    }
-    TailHook h(s, z5, W, bias, N, rows, tokens_per_line, n_lines, nullptr, nullptr, lx::Tables(), nullptr, nullptr, nullptr, 0, chunk_rows,
-               nullptr, nullptr, line_kw, &tb);
+    const lx::Tables tb = tables_of(entry_ids, entry_lens, kw_first_entry, n_kw);
+    TailHook h(s, z5, W, bias, N, rows, tokens_per_line, n_lines, nullptr, nullptr, 0, chunk_rows, lines_with(n_lines, &RecLineOpts::keywords, line_kw),
+               RecStores{nullptr, nullptr, nullptr, &tb});
+    rt_entry_store X;   // (the tables on the device, freed on every way out)
+    X.set(tb);
     for (int i = 0; i < n_lines; i++)   // (a line without a list has no hit)
       if (line_kw[i] <= 0) n_hits_out[i] = 0;
-    rt_session::RecTail& t = h.t;
-    t.d_kw = lx::DevTables{h.bufs.upload(tb.ids.data(), tb.ids.size()), h.bufs.upload(tb.entries.data(), tb.entries.size()),
-                           h.bufs.upload(tb.order.data(), tb.order.size()), h.bufs.upload(tb.lex.data(), tb.lex.size())};
-    t.d_kw_min = h.bufs.upload(kw_min_score, (size_t)n_kw);
+    rt_session::RecTail::Keywords& t = h.t.keywords;
+    t.d = X.d;
+    t.d_min = h.bufs.upload(kw_min_score, (size_t)n_kw);
     // (what the kernels write starts as the caller's values: a slot they leave alone comes back untouched)
     const size_t tn = (size_t)std::max<long long>(table, 1);
-    t.kwscore = h.bufs.alloc<float>(tn); t.kwspan = h.bufs.alloc<int>(2 * tn);
-    if (score_out) DevBufs::put(t.kwscore, score_out, (size_t)table);
-    if (span_out) DevBufs::put(t.kwspan, span_out, 2 * (size_t)table);
-    t.kwh = h.bufs.upload(reinterpret_cast<const kw::Hit*>(hits_out), (size_t)n_lines * kw::HITS);
-    t.kwn = h.bufs.upload(n_hits_out, (size_t)n_lines);
+    t.score = h.bufs.alloc<float>(tn); t.span = h.bufs.alloc<int>(2 * tn);
+    if (score_out) DevBufs::put(t.score, score_out, (size_t)table);
+    if (span_out) DevBufs::put(t.span, span_out, 2 * (size_t)table);
+    t.hits = h.bufs.upload(reinterpret_cast<const kw::Hit*>(hits_out), (size_t)n_lines * kw::HITS);
+    t.n = h.bufs.upload(n_hits_out, (size_t)n_lines);
     h.run();
-    if (score_out) DevBufs::download(score_out, t.kwscore, (size_t)table);
-    if (span_out) DevBufs::download(span_out, t.kwspan, 2 * (size_t)table);
-    DevBufs::download(reinterpret_cast<kw::Hit*>(hits_out), t.kwh, (size_t)n_lines * kw::HITS);
-    DevBufs::download(n_hits_out, t.kwn, (size_t)n_lines);
+    if (score_out) DevBufs::download(score_out, t.score, (size_t)table);
+    if (span_out) DevBufs::download(span_out, t.span, 2 * (size_t)table);
+    DevBufs::download(reinterpret_cast<kw::Hit*>(hits_out), t.hits, (size_t)n_lines * kw::HITS);
+    DevBufs::download(n_hits_out, t.n, (size_t)n_lines);
   });
 }
 
@@ -621,19 +626,19 @@ RT_API int rt_debug_ctc_beam(rt_session* s, const float* z5, const float* W, con
   RT_REQUIRE(chunk_rows >= 0, s, "rt_debug_ctc_beam: chunk_rows is negative");
   return guarded(s, [&] {
     if (beam == 0 || n_lines == 0) return;   // (off, or no line: no launch, no write)
-    TailHook h(s, z5, W, bias, N, rows, tokens_per_line, n_lines, nullptr, nullptr, lx::Tables(), nullptr, nullptr, nullptr, 0, chunk_rows,
-               nullptr, nullptr, nullptr, nullptr, beam, nbest);
-    rt_session::RecTail& t = h.t;
+    TailHook h(s, z5, W, bias, N, rows, tokens_per_line, n_lines, nullptr, nullptr, 0, chunk_rows, std::vector<RecLineOpts>((size_t)n_lines), RecStores{},
+               beam, nbest);
+    rt_session::RecTail::Beam& t = h.t.beam;
     // (what the kernels write starts as the caller's values: a slot they leave alone comes back untouched)
     const size_t nt = (size_t)std::max<long long>(rows, 1) * nbest;
-    t.bmn = h.bufs.upload(counts_out, (size_t)n_lines);
-    t.bmrec = h.bufs.upload(reinterpret_cast<const bm::Beam*>(beams_out), (size_t)n_lines * nbest);
-    t.bmtok = h.bufs.alloc<int>(nt);
-    DevBufs::put(t.bmtok, tokens_out, (size_t)rows * nbest);
+    t.count = h.bufs.upload(counts_out, (size_t)n_lines);
+    t.recs = h.bufs.upload(reinterpret_cast<const bm::Beam*>(beams_out), (size_t)n_lines * nbest);
+    t.tok = h.bufs.alloc<int>(nt);
+    DevBufs::put(t.tok, tokens_out, (size_t)rows * nbest);
     h.run();
-    DevBufs::download(counts_out, t.bmn, (size_t)n_lines);
-    DevBufs::download(reinterpret_cast<bm::Beam*>(beams_out), t.bmrec, (size_t)n_lines * nbest);
-    DevBufs::download(tokens_out, t.bmtok, (size_t)rows * nbest);
+    DevBufs::download(counts_out, t.count, (size_t)n_lines);
+    DevBufs::download(reinterpret_cast<bm::Beam*>(beams_out), t.recs, (size_t)n_lines * nbest);
+    DevBufs::download(tokens_out, t.tok, (size_t)rows * nbest);
   });
 }
 

@@ -25,6 +25,14 @@ constexpr RecKind REC_KINDS[REC_N_KINDS] = {{"charset", &RecLineOpts::charset, &
                                             {"pattern", &RecLineOpts::pattern, &RecLineAny::pattern},
                                             {"keywords", &RecLineOpts::keywords, &RecLineAny::keywords}};
 
+// n lines that carry ids[i] of one kind (null: none) and nothing else, as the rt_debug_ctc_* hooks' ABI and the plan tests'
+// drivers hold them
+inline std::vector<RecLineOpts> lines_with(int n, int RecLineOpts::*kind, const int* ids) {
+  std::vector<RecLineOpts> lines((size_t)n);
+  for (int i = 0; ids && i < n; i++) lines[(size_t)i].*kind = ids[i];
+  return lines;
+}
+
 // The pattern's Viterbi and the lexicon's snap would both rewrite the line's rows, so a line carries at most one of the two.
 inline bool carries_both(const RecLineOpts& o) { return o.pattern > 0 && o.lexicon > 0; }
 // ... in words: `where` names a region ("page 0 region 2"), empty: o is the session's defaults

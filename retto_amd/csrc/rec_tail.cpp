@@ -183,8 +183,9 @@ T* staged(rt_session& s, const std::vector<T>& v) {
   RT_HIP_CHECK(hipMemcpyAsync(d, h, v.size() * sizeof(T), hipMemcpyHostToDevice, s.st));
   return d;
 }
-// The logits recompute the candidates, the charsets and the lexicons share: up to `cap` rows of z5 gathered into zc, then the
-// CTC FC -> logits [cap][ld].  Stream order lets a consumer's chunks share the two buffers.
+int chunk_rows_of(const rt_session::RecTail& t) { return t.chunk_rows > 0 ? t.chunk_rows : cc::CAND_CHUNK; }
+// The logits recompute every kind shares: up to `cap` rows of z5 gathered into zc, then the CTC FC -> logits [cap][ld].  Stream
+// order lets a consumer's chunks share the two buffers.
 struct LogitsChunk {
   rt_session& s; const SvtrCore& core; const float* z5; int ld; float *zc, *logits;
   LogitsChunk(rt_session& s_, const SvtrCore& core_, const float* z5_, int cap) : s(s_), core(core_), z5(z5_), ld(round_up(core_.classes, 4)) {
@@ -199,30 +200,58 @@ struct LogitsChunk {
     core.logits_rows(c, zc, m, logits);
   }
 };
-// one table of a store (rt_lexicons, rt_patterns) into a device allocation of its own, with a blocking copy (an empty one gets one
-// element and no copy); the store's holder frees it
+// Chunks of whole lines, so that a line's T rows are resident together: a chunk takes lines while their rows fit `chunk` and they
+// are at most lx::LINES_PER_CHUNK, and always its first line.  Lines [i0, i1), whose rows are [r0, r0 + m) of the kind's row list;
+// cap: raised to the largest m.
+struct Chunk { int i0, i1, r0, m; };
+template <typename Line>
+std::vector<Chunk> line_chunks(const std::vector<Line>& lines, int chunk, int& cap) {
+  std::vector<Chunk> out;
+  const int n = (int)lines.size();
+  for (int i0 = 0, i1; i0 < n; i0 = i1) {
+    int rows = lines[i0].T;
+    for (i1 = i0 + 1; i1 < n && i1 - i0 < lx::LINES_PER_CHUNK && rows + lines[i1].T <= chunk; i1++) rows += lines[i1].T;
+    const int r0 = lines[i0].row0;
+    out.push_back(Chunk{i0, i1, r0, lines[i1 - 1].row0 + lines[i1 - 1].T - r0});
+    cap = std::max(cap, out.back().m);
+  }
+  return out;
+}
+// One pass over a kind's lines (session.h, above rec_tail): both tables staged, the logits and the row statistics the kind asks
+// for (`stats`) sized by the largest chunk, `cap` rows, and shared by the chunks.  run(f): per chunk the row gather, the CTC FC,
+// k_ctc_row_lse and k_ctc_row_max as asked, then f(the chunk's lines on the device, their number, r0, m) for the kind's own launches.
+enum { ROW_LSE = 1, ROW_MAX = 2 };
+template <typename Line>
+struct LinePass {
+  rt_session& s;
+  const Line* d_lines; const int* d_rows;
+  int cap; std::vector<Chunk> chunks;
+  LogitsChunk lc; float *lse, *rmax;
+  LinePass(rt_session& s_, const SvtrCore& core, const rt_session::RecTail& t, const std::vector<Line>& lines, const std::vector<int>& rows, int stats)
+      : s(s_), d_lines(staged(s_, lines)), d_rows(staged(s_, rows)), cap(1), chunks(line_chunks(lines, chunk_rows_of(t), cap)),
+        lc(s_, core, t.z5, cap), lse(stats & ROW_LSE ? s_.scratch.alloc<float>((size_t)cap) : nullptr),
+        rmax(stats & ROW_MAX ? s_.scratch.alloc<float>((size_t)cap) : nullptr) {}
+  template <typename F>
+  void run(F f) {
+    for (const Chunk& c : chunks) {
+      if (c.m > 0) {
+        lc.run(d_rows + c.r0, c.m);
+        if (lse) { ProfScope ps(&s.prof, s.st, "ctc_row_lse");
+                   pp::ctc_row_lse(s.st, lc.logits, lc.ld, lc.core.classes, c.m, lse); }
+        if (rmax) { ProfScope ps(&s.prof, s.st, "ctc_row_max");
+                    pp::ctc_row_max(s.st, lc.logits, lc.ld, lc.core.classes, c.m, rmax); }
+      }
+      f(d_lines + c.i0, c.i1 - c.i0, c.r0, c.m);
+    }
+  }
+};
+// one table of a store (rt_entry_store, rt_patterns) into a device allocation of its own, with a blocking copy (an empty one gets
+// one element and no copy); the store's holder frees it
 template <typename T>
 void upload_table(const T** d, const std::vector<T>& v) {
   RT_HIP_CHECK(hipMalloc((void**)d, std::max<size_t>(v.size(), 1) * sizeof(T)));
   if (!v.empty()) RT_HIP_CHECK(hipMemcpy(const_cast<T*>(*d), v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
 }
-// Chunks of whole lines (lx::Line or pt::Line), so that a line's T rows are resident together: a chunk takes lines while their
-// rows fit t.chunk_rows (0: cc::CAND_CHUNK) and they are at most lx::LINES_PER_CHUNK, and always its first line.  f(i0, i1, r0, m)
-// per chunk: lines [i0, i1), whose rows are [r0, r0 + m) of the plan's compact row list.  Returns the largest m, at least 1.
-template <typename Line, typename F>
-int line_chunks(const std::vector<Line>& lines, const rt_session::RecTail& t, F f) {
-  const int n = (int)lines.size(), chunk = t.chunk_rows > 0 ? t.chunk_rows : cc::CAND_CHUNK;
-  int cap = 1;
-  for (int i0 = 0, i1; i0 < n; i0 = i1) {
-    int rows = lines[i0].T;
-    for (i1 = i0 + 1; i1 < n && i1 - i0 < lx::LINES_PER_CHUNK && rows + lines[i1].T <= chunk; i1++) rows += lines[i1].T;
-    const int r0 = lines[i0].row0, m = lines[i1 - 1].row0 + lines[i1 - 1].T - r0;
-    f(i0, i1, r0, m);
-    cap = std::max(cap, m);
-  }
-  return cap;
-}
-const auto no_chunk_work = [](int, int, int, int) {};   // (a pass of line_chunks for its result alone)
 }  // namespace
 
 void rt_session::rec_tail(const RecTailPlan& p, const SvtrCore& core, const RecTail& t) {
@@ -242,19 +271,19 @@ void rt_session::rec_tail(const RecTailPlan& p, const SvtrCore& core, const RecT
     pp::word_boxes(st, t.idx, t.tok, t.ntok, t.wb->label, t.wb->cscore, cfg.cls_thresh, d_word_raw, dw, t.n_lines, t.wb->cols,
                    t.wb->n_words, t.wb->words);
   }
-  if (!p.snap) ctc_lexicon(p, core, t);
+  if (!p.snap && p.has_lex()) ctc_lexicon(p, core, t);
   if (p.has_kw()) ctc_keywords(p, core, t);
-  if (p.has_beam()) ctc_beams(p, core, t);
-  if (t.cand_k > 0) ctc_candidates(core, t, p.rows, d_row_set);   // (before the caller rewinds the scratch arena z5 lives in)
+  if (p.has_beam() && t.beam.b > 0) ctc_beams(p, core, t);
+  if (t.cand.k > 0) ctc_candidates(core, t, p.rows, d_row_set);   // (before the caller rewinds the scratch arena z5 lives in)
 }
 
 void rt_session::ctc_candidates(const SvtrCore& core, const RecTail& t, long long rows, const int* d_row_set) {
-  const int K = t.cand_k;
+  const int K = t.cand.k;
   if (t.n_lines <= 0 || rows <= 0) return;
   int *kept_row = nullptr, *kept_slot = nullptr, *d_kept = nullptr;
   if (K > 1) { kept_row = scratch.alloc<int>((size_t)rows); kept_slot = scratch.alloc<int>((size_t)rows); d_kept = scratch.alloc<int>(1); }
   { ProfScope ps(&prof, st, "ctc_kept_rows");
-    pp::ctc_kept_rows(st, t.idx, t.prob, t.lines, t.ntok, t.n_lines, K, t.ccol, t.cands, kept_row, kept_slot, d_kept); }
+    pp::ctc_kept_rows(st, t.idx, t.prob, t.lines, t.ntok, t.n_lines, K, t.cand.col, t.cand.cands, kept_row, kept_slot, d_kept); }
   if (K <= 1) return;
   // the only host wait of the option: the logits GEMMs are sized by the number of kept rows (about a tenth of the time steps)
   int* h_kept = pinned.alloc<int>(1);
@@ -262,125 +291,94 @@ void rt_session::ctc_candidates(const SvtrCore& core, const RecTail& t, long lon
   sync();
   const int kept = (int)std::min<long long>(std::max(*h_kept, 0), rows);
   if (kept == 0) return;
-  const int chunk = t.chunk_rows > 0 ? t.chunk_rows : cc::CAND_CHUNK;
+  const int chunk = chunk_rows_of(t);
   LogitsChunk lc(*this, core, t.z5, std::min(chunk, kept));
   for (int c0 = 0; c0 < kept; c0 += chunk) {
     const int m = std::min(chunk, kept - c0);
     lc.run(kept_row + c0, m);
     ProfScope ps(&prof, st, "ctc_topk");
-    pp::ctc_topk(st, lc.logits, lc.ld, core.classes, kept_slot + c0, m, K, t.cands, kept_row + c0, d_row_set, d_row_set ? t.masks : nullptr, t.words);
+    pp::ctc_topk(st, lc.logits, lc.ld, core.classes, kept_slot + c0, m, K, t.cand.cands, kept_row + c0, d_row_set,
+                 d_row_set ? t.charsets.masks : nullptr, t.charsets.words);
   }
 }
 
 void rt_session::ctc_charset(const SvtrCore& core, const RecTail& t, const int* d_rows, int n_rows, const int* d_row_set) {
   if (n_rows <= 0) return;
-  const int chunk = t.chunk_rows > 0 ? t.chunk_rows : cc::CAND_CHUNK;
+  const int chunk = chunk_rows_of(t);
   LogitsChunk lc(*this, core, t.z5, std::min(chunk, n_rows));
   for (int c0 = 0; c0 < n_rows; c0 += chunk) {
     const int m = std::min(chunk, n_rows - c0);
     lc.run(d_rows + c0, m);
     ProfScope ps(&prof, st, "ctc_charset_argmax");
-    pp::ctc_charset_argmax(st, lc.logits, lc.ld, core.classes, d_rows + c0, d_row_set, t.masks, t.words, m, t.idx, t.prob);
+    pp::ctc_charset_argmax(st, lc.logits, lc.ld, core.classes, d_rows + c0, d_row_set, t.charsets.masks, t.charsets.words, m, t.idx, t.prob);
   }
 }
 
 void rt_session::ctc_lexicon(const RecTailPlan& p, const SvtrCore& core, const RecTail& t) {
-  const int n_lines = (int)p.lines.size();
-  if (n_lines <= 0) return;
-  const lx::Line* d_lines = staged(*this, p.lines); const int* d_rows = staged(*this, p.lrows);
-  float* loglik = t.loglik ? t.loglik : scratch.alloc<float>((size_t)p.table);
-  const lx::DevTables& X = t.d_lex;
-  const int cap = line_chunks(p.lines, t, no_chunk_work);
-  LogitsChunk lc(*this, core, t.z5, cap);
-  float* lse = scratch.alloc<float>((size_t)cap);
+  const RecTail::Lexicon& o = t.lexicon;
+  LinePass<lx::Line> pass(*this, core, t, p.lines, p.lrows, ROW_LSE);
+  const LogitsChunk& lc = pass.lc;
+  float* loglik = o.loglik ? o.loglik : scratch.alloc<float>((size_t)p.table);
   // (lexicon snap: the backpointers of a chunk's long lines, two 64-bit ballots per row)
-  void* bp = p.snap ? scratch.alloc_bytes((size_t)cap * 16) : nullptr;
-  line_chunks(p.lines, t, [&](int i0, int i1, int r0, int m) {   // (the chunks share lse too)
-    if (m > 0) {
-      lc.run(d_rows + r0, m);
-      ProfScope ps(&prof, st, "ctc_row_lse");
-      pp::ctc_row_lse(st, lc.logits, lc.ld, core.classes, m, lse);
-    }
+  void* bp = p.snap ? scratch.alloc_bytes((size_t)pass.cap * 16) : nullptr;
+  pass.run([&](const lx::Line* d_lines, int n, int r0, int) {
     { ProfScope ps(&prof, st, "ctc_lexicon_forward");
-      pp::ctc_lexicon_forward(st, lc.logits, lc.ld, lse, d_lines + i0, i1 - i0, r0, p.max_waves, X.lex, X.entries, X.order, X.ids, loglik); }
+      pp::ctc_lexicon_forward(st, lc.logits, lc.ld, pass.lse, d_lines, n, r0, p.max_waves, o.d.lex, o.d.entries, o.d.order, o.d.ids, loglik); }
     if (p.snap) {   // (a line never straddles chunks: its matches are complete, and its logits still resident, here)
       { ProfScope ps(&prof, st, "ctc_lexicon_topk");
-        pp::ctc_lexicon_topk(st, d_lines + i0, i1 - i0, X.lex, loglik, t.lexm, t.lexn); }
+        pp::ctc_lexicon_topk(st, d_lines, n, o.d.lex, loglik, o.matches, o.n); }
       ProfScope ps(&prof, st, "ctc_lexicon_align");
-      pp::ctc_lexicon_align(st, lc.logits, lc.ld, lse, d_lines + i0, i1 - i0, r0, X.lex, X.entries, X.ids, t.d_min_post, t.lexm, t.lexn,
-                            d_rows, bp, t.idx, t.prob, t.lexs, t.vit);
+      pp::ctc_lexicon_align(st, lc.logits, lc.ld, pass.lse, d_lines, n, r0, o.d.lex, o.d.entries, o.d.ids, o.d_min_post, o.matches, o.n,
+                            pass.d_rows, bp, t.idx, t.prob, o.snapped, o.vit);
     }
   });
   if (!p.snap) {   // (without snap: one top-K over all the group's lines)
     ProfScope ps(&prof, st, "ctc_lexicon_topk");
-    pp::ctc_lexicon_topk(st, d_lines, n_lines, X.lex, loglik, t.lexm, t.lexn);
+    pp::ctc_lexicon_topk(st, pass.d_lines, (int)p.lines.size(), o.d.lex, loglik, o.matches, o.n);
   }
 }
 
 void rt_session::ctc_pattern(const RecTailPlan& p, const SvtrCore& core, const RecTail& t) {
-  if (p.plines.empty()) return;
-  const pt::Line* d_lines = staged(*this, p.plines); const int* d_rows = staged(*this, p.prows);
-  const int cap = line_chunks(p.plines, t, no_chunk_work);
-  LogitsChunk lc(*this, core, t.z5, cap);
-  float* lse = scratch.alloc<float>((size_t)cap); float* rmax = scratch.alloc<float>((size_t)cap);
+  const RecTail::Pattern& o = t.pattern;
+  LinePass<pt::Line> pass(*this, core, t, p.plines, p.prows, ROW_LSE | ROW_MAX);
+  const LogitsChunk& lc = pass.lc;
   // (the backpointer codes of the group's long lines, 16 bits each; every line has its own part: pt::Line::bp)
   void* bp = scratch.alloc_bytes((size_t)std::max<long long>(p.bp_codes, 1) * sizeof(uint16_t));
-  line_chunks(p.plines, t, [&](int i0, int i1, int r0, int m) {
-    if (m > 0) {
-      lc.run(d_rows + r0, m);
-      { ProfScope ps(&prof, st, "ctc_row_lse");
-        pp::ctc_row_lse(st, lc.logits, lc.ld, core.classes, m, lse); }
-      ProfScope ps(&prof, st, "ctc_row_max");
-      pp::ctc_row_max(st, lc.logits, lc.ld, core.classes, m, rmax);
-    }
+  pass.run([&](const pt::Line* d_lines, int n, int r0, int) {
     ProfScope ps(&prof, st, "ctc_pattern_viterbi");
-    pp::ctc_pattern_viterbi(st, lc.logits, lc.ld, core.classes, lse, rmax, d_lines + i0, i1 - i0, r0, t.d_pat, d_rows, bp, t.idx, t.prob,
-                            t.patm, t.patv, t.patlp, t.patfree);
+    pp::ctc_pattern_viterbi(st, lc.logits, lc.ld, core.classes, pass.lse, pass.rmax, d_lines, n, r0, o.d, pass.d_rows, bp, t.idx, t.prob,
+                            o.matched, o.vit, o.logprob, o.free_logprob);
   });
 }
 
 void rt_session::ctc_keywords(const RecTailPlan& p, const SvtrCore& core, const RecTail& t) {
-  const int n_lines = (int)p.klines.size();
-  if (n_lines <= 0) return;
-  const kw::Line* d_lines = staged(*this, p.klines); const int* d_rows = staged(*this, p.krows);
+  const RecTail::Keywords& o = t.keywords;
+  LinePass<kw::Line> pass(*this, core, t, p.klines, p.krows, ROW_MAX);
+  const LogitsChunk& lc = pass.lc;
   const size_t table = (size_t)std::max<long long>(p.ktable, 1);
-  float* score = t.kwscore ? t.kwscore : scratch.alloc<float>(table);
-  int* span = t.kwspan ? t.kwspan : scratch.alloc<int>(2 * table);
-  const lx::DevTables& X = t.d_kw;
-  const int cap = line_chunks(p.klines, t, no_chunk_work);
-  LogitsChunk lc(*this, core, t.z5, cap);
-  float* rmax = scratch.alloc<float>((size_t)cap);
-  line_chunks(p.klines, t, [&](int i0, int i1, int r0, int m) {   // (the chunks share rmax too)
-    if (m > 0) {
-      lc.run(d_rows + r0, m);
-      ProfScope ps(&prof, st, "ctc_row_max");
-      pp::ctc_row_max(st, lc.logits, lc.ld, core.classes, m, rmax);
-    }
+  float* score = o.score ? o.score : scratch.alloc<float>(table);
+  int* span = o.span ? o.span : scratch.alloc<int>(2 * table);
+  pass.run([&](const kw::Line* d_lines, int n, int r0, int) {
     ProfScope ps(&prof, st, "ctc_keyword_spot");
-    pp::ctc_keyword_spot(st, lc.logits, lc.ld, rmax, d_lines + i0, i1 - i0, r0, p.kmax_waves, X.lex, X.entries, X.order, X.ids, score, span);
+    pp::ctc_keyword_spot(st, lc.logits, lc.ld, pass.rmax, d_lines, n, r0, p.kmax_waves, o.d.lex, o.d.entries, o.d.order, o.d.ids, score, span);
   });
   ProfScope ps(&prof, st, "ctc_keyword_topk");
-  pp::ctc_keyword_topk(st, d_lines, n_lines, X.lex, t.d_kw_min, score, span, t.kwh, t.kwn);
+  pp::ctc_keyword_topk(st, pass.d_lines, (int)p.klines.size(), o.d.lex, o.d_min, score, span, o.hits, o.n);
 }
 
 void rt_session::ctc_beams(const RecTailPlan& p, const SvtrCore& core, const RecTail& t) {
-  const int n_lines = (int)p.blines.size();
-  if (n_lines <= 0 || t.beam_b <= 0) return;
-  const bm::Line* d_lines = staged(*this, p.blines); const int* d_rows = staged(*this, p.brows);
+  const RecTail::Beam& o = t.beam;
+  LinePass<bm::Line> pass(*this, core, t, p.blines, p.brows, ROW_LSE);
+  const LogitsChunk& lc = pass.lc;
   bm::Node* nodes = scratch.alloc<bm::Node>((size_t)std::max<long long>(p.bnodes, 1));   // (the kernel initialises what it reads)
-  const int cap = line_chunks(p.blines, t, no_chunk_work);
-  LogitsChunk lc(*this, core, t.z5, cap);
-  float* lse = scratch.alloc<float>((size_t)cap); bm::TopC* topc = scratch.alloc<bm::TopC>((size_t)cap);
-  line_chunks(p.blines, t, [&](int i0, int i1, int r0, int m) {   // (the chunks share lse and topc too)
+  bm::TopC* topc = scratch.alloc<bm::TopC>((size_t)pass.cap);   // (the chunks share it, as they share lse)
+  pass.run([&](const bm::Line* d_lines, int n, int r0, int m) {
     if (m > 0) {
-      lc.run(d_rows + r0, m);
-      { ProfScope ps(&prof, st, "ctc_row_lse");
-        pp::ctc_row_lse(st, lc.logits, lc.ld, core.classes, m, lse); }
       ProfScope ps(&prof, st, "ctc_beam_topc");
       pp::ctc_beam_topc(st, lc.logits, lc.ld, core.classes, m, topc);
     }
     ProfScope ps(&prof, st, "ctc_beam_search");
-    pp::ctc_beam_search(st, lc.logits, lc.ld, lse, topc, d_lines + i0, i1 - i0, r0, t.beam_b, t.beam_n, nodes, t.bmrec, t.bmtok, t.bmn);
+    pp::ctc_beam_search(st, lc.logits, lc.ld, pass.lse, topc, d_lines, n, r0, o.b, o.n, nodes, o.recs, o.tok, o.count);
   });
 }
 
@@ -400,32 +398,45 @@ int rt_session::charset_create(const char* utf8, size_t len, const int32_t* ids,
   return (int)C.ids.size();
 }
 
-int rt_session::lexicon_create(const char* utf8, size_t len, const int32_t* ids, const int32_t* entry_lens, int n_id_entries) {
-  rt_lexicons& X = *lexicons;
-  if ((int)X.host.size() >= lx::MAX_LEXICONS)
-    throw RtError(RT_ERR_CAPACITY, "rt_lexicon_create: the session holds RT_MAX_LEXICONS (" + std::to_string(lx::MAX_LEXICONS) + ") lexicons already");
-  std::unique_ptr<rt_lexicons::Host> h(new rt_lexicons::Host());
-  compile_lexicon(dict, utf8, len, ids, entry_lens, n_id_entries, h->ids, h->lens);
+// ---- the entry stores (session.h rt_entry_store) ----
+rt_entry_store::~rt_entry_store() {
+  const void* p[] = {d.ids, d.entries, d.order, d.lex};
+  for (const void* q : p) if (q) (void)hipFree(const_cast<void*>(q));
+}
+void rt_entry_store::set(lx::Tables fresh) {
+  // the device tables are rebuilt whole (blocking copies; in a session no lane has work queued: the create calls are guarded and
+  // every pipeline call ends with its streams drained)
+  rt_entry_store up;   // (frees what it holds if a copy below throws; the old tables leave with it)
+  upload_table(&up.d.ids, fresh.ids); upload_table(&up.d.entries, fresh.entries); upload_table(&up.d.order, fresh.order);
+  upload_table(&up.d.lex, fresh.lex);
+  std::swap(d, up.d);
+  tb = std::move(fresh);
+}
+int rt_entry_store::add(const std::vector<std::string>& dict, const char* utf8, size_t len, const int32_t* ids, const int32_t* entry_lens,
+                        int n) {
+  std::unique_ptr<Host> h(new Host());
+  compile_lexicon(dict, utf8, len, ids, entry_lens, n, h->ids, h->lens);
   int o = 0;
-  for (int n : h->lens) {
+  for (int m : h->lens) {
     h->off.push_back(o);
     std::string t;
-    for (int i = 0; i < n; i++) t += dict[(size_t)h->ids[(size_t)(o + i)]];
+    for (int i = 0; i < m; i++) t += dict[(size_t)h->ids[(size_t)(o + i)]];
     h->text.push_back(std::move(t));
-    o += n;
+    o += m;
   }
-  lx::Tables tb = X.tb;
-  tb.add(h->ids.data(), h->lens.data(), (int)h->lens.size());
-  // the device tables are rebuilt whole (blocking copies; no lane has work queued: this is a guarded call and every pipeline
-  // call ends with its streams drained)
+  lx::Tables fresh = tb;
+  fresh.add(h->ids.data(), h->lens.data(), (int)h->lens.size());
+  host.reserve(host.size() + 1);   // (so that nothing behind set() throws)
+  set(std::move(fresh));
+  host.push_back(std::move(h));
+  return (int)host.size();
+}
+
+int rt_session::lexicon_create(const char* utf8, size_t len, const int32_t* ids, const int32_t* entry_lens, int n_id_entries) {
+  if ((int)lexicons->host.size() >= lx::MAX_LEXICONS)
+    throw RtError(RT_ERR_CAPACITY, "rt_lexicon_create: the session holds RT_MAX_LEXICONS (" + std::to_string(lx::MAX_LEXICONS) + ") lexicons already");
   RT_HIP_CHECK(hipSetDevice(device));
-  rt_lexicons fresh;   // (frees what it holds if a copy below throws)
-  upload_table(&fresh.d.ids, tb.ids); upload_table(&fresh.d.entries, tb.entries); upload_table(&fresh.d.order, tb.order);
-  upload_table(&fresh.d.lex, tb.lex);
-  std::swap(X.d, fresh.d);   // (the old tables leave with `fresh`)
-  X.tb = std::move(tb);
-  X.host.push_back(std::move(h));
-  return (int)X.host.size();
+  return lexicons->add(dict, utf8, len, ids, entry_lens, n_id_entries);
 }
 
 int rt_session::keywords_create(const char* utf8, size_t len, const int32_t* ids, const int32_t* entry_lens, int n_id_entries,
@@ -435,30 +446,15 @@ int rt_session::keywords_create(const char* utf8, size_t len, const int32_t* ids
     throw RtError(RT_ERR_INVALID, "rt_keywords_create: min_score " + std::to_string(min_score) + " is not a number at most 0");
   if ((int)X.host.size() >= kw::MAX_LISTS)
     throw RtError(RT_ERR_CAPACITY, "rt_keywords_create: the session holds RT_MAX_KEYWORD_LISTS (" + std::to_string(kw::MAX_LISTS) + ") keyword lists already");
-  std::unique_ptr<rt_lexicons::Host> h(new rt_lexicons::Host());
-  compile_lexicon(dict, utf8, len, ids, entry_lens, n_id_entries, h->ids, h->lens);
-  int o = 0;
-  for (int n : h->lens) {
-    h->off.push_back(o);
-    std::string t;
-    for (int i = 0; i < n; i++) t += dict[(size_t)h->ids[(size_t)(o + i)]];
-    h->text.push_back(std::move(t));
-    o += n;
-  }
-  lx::Tables tb = X.tb;
-  tb.add(h->ids.data(), h->lens.data(), (int)h->lens.size());
   std::vector<float> mins = X.min_score;
   mins.push_back(min_score);
-  // the device tables are rebuilt whole (blocking copies; no lane has work queued: this is a guarded call and every pipeline
-  // call ends with its streams drained)
   RT_HIP_CHECK(hipSetDevice(device));
-  rt_keywords fresh;   // (frees what it holds if a copy below throws)
-  upload_table(&fresh.d.ids, tb.ids); upload_table(&fresh.d.entries, tb.entries); upload_table(&fresh.d.order, tb.order);
-  upload_table(&fresh.d.lex, tb.lex); upload_table(&fresh.d_min, mins);
-  std::swap(X.d, fresh.d); std::swap(X.d_min, fresh.d_min);   // (the old tables leave with `fresh`)
-  X.tb = std::move(tb); X.min_score = std::move(mins);
-  X.host.push_back(std::move(h));
-  return (int)X.host.size();
+  rt_keywords fresh;   // (holds the new min_score table until the entries are in, then leaves with the old one)
+  upload_table(&fresh.d_min, mins);
+  const int id = X.add(dict, utf8, len, ids, entry_lens, n_id_entries);
+  std::swap(X.d_min, fresh.d_min);
+  X.min_score = std::move(mins);
+  return id;
 }
 
 int rt_session::pattern_create(const char* utf8, size_t len) {

@@ -517,6 +517,14 @@ struct LineMeta {
   int* label = nullptr; float* cscore = nullptr; int* ntok = nullptr; float* rscore = nullptr;
   void view(int* m, int NLp) { label = m; cscore = reinterpret_cast<float*>(m + NLp); ntok = m + 2 * NLp; rscore = reinterpret_cast<float*>(m + 3 * NLp); }
 };
+// A per-call result array that the tail fills per line: [n] on the device (from `arena`) with its mirror in pinned memory, both
+// allocated at once so that one count sizes them; fetch() queues the copy home.  Null until allocated: the option is off.
+template <typename T>
+struct Mirror {
+  T* d = nullptr; T* h = nullptr; size_t n = 0;
+  void alloc(rt_session& s, size_t n_) { n = n_; d = s.arena.alloc<T>(n); h = s.pinned.alloc<T>(n); }
+  void fetch(hipStream_t st) const { if (d) RT_HIP_CHECK(hipMemcpyAsync(h, d, n * sizeof(T), hipMemcpyDeviceToHost, st)); }
+};
 // the state of one run_pages call; device and pinned buffers live until the next begin_call
 struct Pipeline {
   int n_pages, mem; const float* const* det_map_override;
@@ -541,20 +549,19 @@ struct Pipeline {
   std::vector<RecLineOpts> line_opts; RecLineAny any;
   // rec lexicons (any.lexicon): per line lx::MATCHES match slots and the number of matches (written for the lines that carry a
   // lexicon only)
-  lx::Match* d_lexm = nullptr; int* d_lexn = nullptr; lx::Match* h_lexm = nullptr; int* h_lexn = nullptr;
+  Mirror<lx::Match> lexm; Mirror<int> lexn;
   // lexicon snap (ctc_lexicon_align.h): per line 1 where it snapped; null unless a lexicon of the call's lines has snap on
-  int* d_lexs = nullptr; int* h_lexs = nullptr;
+  Mirror<int> lexs;
   // rec patterns (ctc_pattern.h; any.pattern): per line matched | vit | logprob | free_logprob, one block of 4 NLp words (written
   // for the lines that carry a pattern only)
-  int* d_pat = nullptr; int* h_pat = nullptr;
+  Mirror<int> pat;
   // rec keywords (ctc_keyword.h; any.keywords): per line kw::HITS hit slots and the number of hits (written for the lines that
   // carry a list only)
-  kw::Hit* d_kwh = nullptr; int* d_kwn = nullptr; kw::Hit* h_kwh = nullptr; int* h_kwn = nullptr;
+  Mirror<kw::Hit> kwh; Mirror<int> kwn;
   // rec beams (ctc_beam.h) of this call; beam_b = 0: off.  Per line its count and beam_n records; the token pool: line li's
   // hypothesis k at [(tok_off[li] * beam_n) + k * T]
   int beam_b = 0, beam_n = 0;
-  int* d_bmn = nullptr; bm::Beam* d_bmrec = nullptr; int* d_bmtok = nullptr;
-  int* h_bmn = nullptr; bm::Beam* h_bmrec = nullptr; int* h_bmtok = nullptr;
+  Mirror<int> bmn; Mirror<bm::Beam> bmrec; Mirror<int> bmtok;
 };
 
 // Launch groups: items [g0, end) where the group always takes its first item; with max_items > 0 it takes up to max_items items,
@@ -923,18 +930,15 @@ void rec_groups(rt_session& s, Pipeline& P) {
   if (s.cfg.rec_return_word_box) {
     P.d_wcount = s.arena.alloc<int>(P.NLp); P.d_words = s.arena.alloc<wb::Word>(ntok); d_wcol = s.arena.alloc<int>(ntok);
   }
-  if (P.any.lexicon) { P.d_lexm = s.arena.alloc<lx::Match>((size_t)P.NLp * lx::MATCHES); P.d_lexn = s.arena.alloc<int>(P.NLp); }
+  if (P.any.lexicon) { P.lexm.alloc(s, (size_t)P.NLp * lx::MATCHES); P.lexn.alloc(s, P.NLp); }
   // lexicon snap (ctc_lexicon_align.h): a line snaps only where its lexicon has min_posterior > 0
   if (std::any_of(P.line_opts.begin(), P.line_opts.end(), [&](const RecLineOpts& o) { return o.lexicon > 0 && s.lexicons->snap[o.lexicon - 1] > 0.0f; })) {
-    P.d_lexs = s.arena.alloc<int>(P.NLp);   // (zeroed: the lexicon lines of a group without a snap-enabled line are never written)
-    RT_HIP_CHECK(hipMemsetAsync(P.d_lexs, 0, (size_t)P.NLp * sizeof(int), s.st));
+    P.lexs.alloc(s, P.NLp);   // (zeroed: the lexicon lines of a group without a snap-enabled line are never written)
+    RT_HIP_CHECK(hipMemsetAsync(P.lexs.d, 0, (size_t)P.NLp * sizeof(int), s.st));
   }
-  if (P.any.pattern) P.d_pat = s.arena.alloc<int>((size_t)4 * P.NLp);
-  if (P.any.keywords) { P.d_kwh = s.arena.alloc<kw::Hit>((size_t)P.NLp * kw::HITS); P.d_kwn = s.arena.alloc<int>(P.NLp); }
-  if (P.beam_b > 0) {
-    P.d_bmn = s.arena.alloc<int>(P.NLp); P.d_bmrec = s.arena.alloc<bm::Beam>((size_t)P.NLp * P.beam_n);
-    P.d_bmtok = s.arena.alloc<int>(ntok * (size_t)P.beam_n);
-  }
+  if (P.any.pattern) P.pat.alloc(s, (size_t)4 * P.NLp);
+  if (P.any.keywords) { P.kwh.alloc(s, (size_t)P.NLp * kw::HITS); P.kwn.alloc(s, P.NLp); }
+  if (P.beam_b > 0) { P.bmn.alloc(s, P.NLp); P.bmrec.alloc(s, (size_t)P.NLp * P.beam_n); P.bmtok.alloc(s, ntok * (size_t)P.beam_n); }
   static const long long REC_GROUP_PX = getenv("RT_REC_GROUP_PX") ? atoll(getenv("RT_REC_GROUP_PX")) : (long long)24000000;  // measured sweet spot (profiles/README.md)
   for (int l0 = 0; l0 < P.NL;) {
     const int l1 = group_end(l0, P.NL, 0, REC_GROUP_PX, [&](int l) { return (long long)rh * P.line_W[l]; });
@@ -960,20 +964,10 @@ void rec_groups(rt_session& s, Pipeline& P) {
     const long long t0 = P.tok_off[l0];
     const rt_lexicons& X = *s.lexicons;
     const rt_keywords& KW = *s.keywords;
-    const RecTailPlan tail = rec_tail_plan(P.tok_off.data(), l0, l1, P.line_opts.data(), RecStores{X.tb, X.snap, &s.patterns->tb, &KW.tb},
+    const RecTailPlan tail = rec_tail_plan(P.tok_off.data(), l0, l1, P.line_opts.data(), RecStores{&X.tb, X.snap, &s.patterns->tb, &KW.tb},
                                            P.beam_b, P.beam_n);
-    if (!tail.table_fits())
-      throw RtError(RT_ERR_CAPACITY, "rec lexicons: " + std::to_string(tail.lines.size()) + " lines of one rec group carry lexicons of " +
-                                         std::to_string(tail.table) + " entries in all, more than the " + std::to_string(lx::MAX_GROUP_TABLE) +
-                                         " likelihoods a group's table holds: use smaller lexicons or fewer lexicon lines per call");
-    if (!tail.ktable_fits())
-      throw RtError(RT_ERR_CAPACITY, "rec keywords: " + std::to_string(tail.klines.size()) + " lines of one rec group carry keyword lists of " +
-                                         std::to_string(tail.ktable) + " entries in all, more than the " + std::to_string(lx::MAX_GROUP_TABLE) +
-                                         " scores a group's table holds: use smaller keyword lists or fewer keyword lines per call");
-    if (!tail.bnodes_fit())
-      throw RtError(RT_ERR_CAPACITY, "rec beams: the " + std::to_string(tail.blines.size()) + " lines of one rec group need " +
-                                         std::to_string(tail.bnodes) + " trie nodes at beam " + std::to_string(P.beam_b) + ", more than the " +
-                                         std::to_string(bm::MAX_GROUP_NODES) + " a group's trie holds: use a narrower beam or fewer lines per call");
+    const std::string refused = tail.refusal(P.beam_b);
+    if (!refused.empty()) throw RtError(RT_ERR_CAPACITY, refused);
     const float* z5 = nullptr;   // the head's input, for the candidates', the charsets', the lexicons', the keywords' and the beams' logits
     { ProfOuter po(&s.prof, s.st, "net/rec");
       s.rec->run(c, x, L0, Lt, d_idx + t0, d_prob + t0, tail.needs_z5(cand_k) ? &z5 : nullptr); }  // fused CTC head: logits never reach HBM
@@ -988,14 +982,22 @@ void rec_groups(rt_session& s, Pipeline& P) {
       }
       words = {hwl, P.d_meta.label + l0, P.d_meta.cscore + l0, d_wcol + t0, P.d_wcount + l0, P.d_words + t0};
     }
-    auto patf = [&](int k) { return P.d_pat ? reinterpret_cast<float*>(P.d_pat + (size_t)k * P.NLp) : nullptr; };   // vit | logprob | free_logprob
-    const rt_session::RecTail t{z5, d_idx + t0, d_prob + t0, Lt.d, ln, s.charsets->d_masks, s.charsets->words,
-                                X.d, X.d_snap, cand_k, 0,
-                                P.d_tok + t0, P.d_meta.ntok + l0, P.d_meta.rscore + l0, nullptr, P.d_lexm, P.d_lexn, P.d_lexs, nullptr,
-                                P.d_ccol ? P.d_ccol + t0 : nullptr, P.d_cands ? P.d_cands + t0 * cand_k : nullptr,
-                                words.h_lines ? &words : nullptr, s.patterns->d, P.d_pat, patf(1), patf(2), patf(3),
-                                KW.d, KW.d_min, nullptr, nullptr, P.d_kwh, P.d_kwn,
-                                P.beam_b, P.beam_n, P.d_bmn, P.d_bmrec, P.d_bmtok ? P.d_bmtok + t0 * P.beam_n : nullptr};
+    rt_session::RecTail t;
+    t.z5 = z5; t.idx = d_idx + t0; t.prob = d_prob + t0; t.lines = Lt.d; t.n_lines = ln;
+    t.tok = P.d_tok + t0; t.ntok = P.d_meta.ntok + l0; t.rscore = P.d_meta.rscore + l0;
+    if (words.h_lines) t.wb = &words;
+    t.charsets = {s.charsets->d_masks, s.charsets->words};
+    t.lexicon.d = X.d; t.lexicon.matches = P.lexm.d; t.lexicon.n = P.lexn.d; t.lexicon.d_min_post = X.d_snap; t.lexicon.snapped = P.lexs.d;
+    t.pattern.d = s.patterns->d;
+    if (P.pat.d) {   // matched | vit | logprob | free_logprob
+      float* f = reinterpret_cast<float*>(P.pat.d);
+      t.pattern.matched = P.pat.d; t.pattern.vit = f + P.NLp; t.pattern.logprob = f + 2 * (size_t)P.NLp; t.pattern.free_logprob = f + 3 * (size_t)P.NLp;
+    }
+    t.keywords.d = KW.d; t.keywords.d_min = KW.d_min; t.keywords.hits = P.kwh.d; t.keywords.n = P.kwn.d;
+    t.beam.b = P.beam_b; t.beam.n = P.beam_n; t.beam.count = P.bmn.d; t.beam.recs = P.bmrec.d;
+    if (P.bmtok.d) t.beam.tok = P.bmtok.d + t0 * P.beam_n;
+    t.cand.k = cand_k;
+    if (cand_k > 0) { t.cand.col = P.d_ccol + t0; t.cand.cands = P.d_cands + t0 * cand_k; }
     s.rec_tail(tail, s.rec->core(), t);
     l0 = l1;
   }
@@ -1018,31 +1020,9 @@ void line_round_trip(rt_session& s, Pipeline& P) {
     RT_HIP_CHECK(hipMemcpyAsync(P.h_wcount, P.d_wcount, (size_t)P.NL * sizeof(int), hipMemcpyDeviceToHost, s.st));
     if (total_tok > 0) RT_HIP_CHECK(hipMemcpyAsync(P.h_words, P.d_words, (size_t)total_tok * sizeof(wb::Word), hipMemcpyDeviceToHost, s.st));
   }
-  if (P.any.lexicon) {   // (the lexicon matches too)
-    P.h_lexm = s.pinned.alloc<lx::Match>((size_t)P.NLp * lx::MATCHES); P.h_lexn = s.pinned.alloc<int>(P.NLp);
-    RT_HIP_CHECK(hipMemcpyAsync(P.h_lexm, P.d_lexm, (size_t)P.NLp * lx::MATCHES * sizeof(lx::Match), hipMemcpyDeviceToHost, s.st));
-    RT_HIP_CHECK(hipMemcpyAsync(P.h_lexn, P.d_lexn, (size_t)P.NLp * sizeof(int), hipMemcpyDeviceToHost, s.st));
-    if (P.d_lexs) {   // (and, with snap on, which lines snapped)
-      P.h_lexs = s.pinned.alloc<int>(P.NLp);
-      RT_HIP_CHECK(hipMemcpyAsync(P.h_lexs, P.d_lexs, (size_t)P.NLp * sizeof(int), hipMemcpyDeviceToHost, s.st));
-    }
-  }
-  if (P.d_pat) {   // (and the pattern results)
-    P.h_pat = s.pinned.alloc<int>((size_t)4 * P.NLp);
-    RT_HIP_CHECK(hipMemcpyAsync(P.h_pat, P.d_pat, (size_t)4 * P.NLp * sizeof(int), hipMemcpyDeviceToHost, s.st));
-  }
-  if (P.any.keywords) {   // (and the keyword hits)
-    P.h_kwh = s.pinned.alloc<kw::Hit>((size_t)P.NLp * kw::HITS); P.h_kwn = s.pinned.alloc<int>(P.NLp);
-    RT_HIP_CHECK(hipMemcpyAsync(P.h_kwh, P.d_kwh, (size_t)P.NLp * kw::HITS * sizeof(kw::Hit), hipMemcpyDeviceToHost, s.st));
-    RT_HIP_CHECK(hipMemcpyAsync(P.h_kwn, P.d_kwn, (size_t)P.NLp * sizeof(int), hipMemcpyDeviceToHost, s.st));
-  }
-  if (P.beam_b > 0) {   // (and the beams: counts, records, the token pool)
-    const size_t N = (size_t)P.beam_n;
-    P.h_bmn = s.pinned.alloc<int>(P.NLp); P.h_bmrec = s.pinned.alloc<bm::Beam>((size_t)P.NLp * N); P.h_bmtok = s.pinned.alloc<int>(nt * N);
-    RT_HIP_CHECK(hipMemcpyAsync(P.h_bmn, P.d_bmn, (size_t)P.NLp * sizeof(int), hipMemcpyDeviceToHost, s.st));
-    RT_HIP_CHECK(hipMemcpyAsync(P.h_bmrec, P.d_bmrec, (size_t)P.NLp * N * sizeof(bm::Beam), hipMemcpyDeviceToHost, s.st));
-    if (total_tok > 0) RT_HIP_CHECK(hipMemcpyAsync(P.h_bmtok, P.d_bmtok, (size_t)total_tok * N * sizeof(int), hipMemcpyDeviceToHost, s.st));
-  }
+  // (and what the lexicons, the snap, the patterns, the keywords and the beams left, where the call has them)
+  P.lexm.fetch(s.st); P.lexn.fetch(s.st); P.lexs.fetch(s.st); P.pat.fetch(s.st); P.kwh.fetch(s.st); P.kwn.fetch(s.st);
+  P.bmn.fetch(s.st); P.bmrec.fetch(s.st); P.bmtok.fetch(s.st);
   s.sync(); s.check_flags();
 }
 // ---- results (session.rs:94-105) ----------------------------------------------------
@@ -1077,34 +1057,34 @@ void results(const rt_session& s, const Pipeline& P, rt_results& res) {
     }
     if (P.any.lexicon) {   // rec lexicons: a line without one has 0 matches (its device slots were never written)
       R.lex_id.assign((size_t)nb, 0); R.lex_n.assign((size_t)nb, 0); R.lex_matches.assign((size_t)nb * lx::MATCHES, lx::Match{0, 0.0f, 0.0f});
-      if (P.h_lexs) R.lex_snapped.assign((size_t)nb, 0);
+      if (P.lexs.h) R.lex_snapped.assign((size_t)nb, 0);
       for (int k = 0; k < nb; k++) {
         const int li = p.first_line + k;
         if (P.line_opts[li].lexicon <= 0) continue;
-        if (P.h_lexs) R.lex_snapped[k] = P.h_lexs[li] == 1 ? 1 : 0;
+        if (P.lexs.h) R.lex_snapped[k] = P.lexs.h[li] == 1 ? 1 : 0;
         R.lex_id[k] = P.line_opts[li].lexicon;
-        R.lex_n[k] = std::min(std::max(P.h_lexn[li], 0), lx::MATCHES);
-        for (int j = 0; j < R.lex_n[k]; j++) R.lex_matches[(size_t)k * lx::MATCHES + j] = P.h_lexm[(size_t)li * lx::MATCHES + j];
+        R.lex_n[k] = std::min(std::max(P.lexn.h[li], 0), lx::MATCHES);
+        for (int j = 0; j < R.lex_n[k]; j++) R.lex_matches[(size_t)k * lx::MATCHES + j] = P.lexm.h[(size_t)li * lx::MATCHES + j];
       }
     }
-    if (P.h_pat) {   // rec patterns: a line without one reports pattern 0
+    if (P.pat.h) {   // rec patterns: a line without one reports pattern 0
       R.pat_id.assign((size_t)nb, 0); R.pat_res.assign((size_t)nb, pt::LineResult{0, 0.0f, 0.0f, 0.0f});
-      const float* f = reinterpret_cast<const float*>(P.h_pat);
+      const float* f = reinterpret_cast<const float*>(P.pat.h);
       for (int k = 0; k < nb; k++) {
         const int li = p.first_line + k;
         if (P.line_opts[li].pattern <= 0) continue;
         R.pat_id[k] = P.line_opts[li].pattern;
-        R.pat_res[k] = pt::LineResult{P.h_pat[li] == 1 ? 1 : 0, f[P.NLp + li], f[2 * (size_t)P.NLp + li], f[3 * (size_t)P.NLp + li]};
+        R.pat_res[k] = pt::LineResult{P.pat.h[li] == 1 ? 1 : 0, f[P.NLp + li], f[2 * (size_t)P.NLp + li], f[3 * (size_t)P.NLp + li]};
       }
     }
-    if (P.h_kwh) {   // rec keywords: a line without a list has 0 hits (its device slots were never written)
+    if (P.kwh.h) {   // rec keywords: a line without a list has 0 hits (its device slots were never written)
       R.kw_id.assign((size_t)nb, 0); R.kw_n.assign((size_t)nb, 0); R.kw_hits.assign((size_t)nb * kw::HITS, kw::Hit{});
       const double bw = P.crop_original ? (double)p.ori_w : (double)p.after_w, bh = P.crop_original ? (double)p.ori_h : (double)p.after_h;
       for (int k = 0; k < nb; k++) {
         const int li = p.first_line + k;
         if (P.line_opts[li].keywords <= 0) continue;
         R.kw_id[k] = P.line_opts[li].keywords;
-        R.kw_n[k] = std::min(std::max(P.h_kwn[li], 0), kw::HITS);
+        R.kw_n[k] = std::min(std::max(P.kwn.h[li], 0), kw::HITS);
         if (R.kw_n[k] == 0) continue;
         // the span [first_col, last_col + 1) as an ALNUM word's (wb::line_words): crop pixels per column, the crop's homography,
         // the classifier's rot180 as k_word_boxes takes it, then original-image coordinates
@@ -1112,25 +1092,25 @@ void results(const rt_session& s, const Pipeline& P, rt_results& res) {
         const int rot180 = (m.label[li] == 1 && m.cscore[li] >= s.cfg.cls_thresh) ? 1 : 0;
         for (int j = 0; j < R.kw_n[k]; j++) {
           kw::Hit& h = R.kw_hits[(size_t)k * kw::HITS + j];
-          h = P.h_kwh[(size_t)li * kw::HITS + j];
+          h = P.kwh.h[(size_t)li * kw::HITS + j];
           kw::span_quad(h.first_col, h.last_col, g, rot180, h.quad);
           gm::scale_and_clip(h.quad, bw, bh, (double)p.ori_w, (double)p.ori_h);
         }
       }
     }
-    if (P.h_bmn) {   // rec beams: per line its hypotheses, best first; a hypothesis' text from the dictionary as the line's own
+    if (P.bmn.h) {   // rec beams: per line its hypotheses, best first; a hypothesis' text from the dictionary as the line's own
       const int N = P.beam_n;
       R.beam_n = N; R.bm_count.assign((size_t)nb, 0); R.bm_recs.assign((size_t)nb * N, bm::Beam{0.0f, 0});
       R.bm_tokens.assign((size_t)nb * N, std::vector<int32_t>()); R.bm_text.assign((size_t)nb * N, std::string());
       for (int k = 0; k < nb; k++) {
         const int li = p.first_line + k;
         const long long T = P.tok_off[li + 1] - P.tok_off[li];
-        R.bm_count[k] = std::min(std::max(P.h_bmn[li], 0), N);
+        R.bm_count[k] = std::min(std::max(P.bmn.h[li], 0), N);
         for (int q = 0; q < R.bm_count[k]; q++) {
           bm::Beam& b = R.bm_recs[(size_t)k * N + q];
-          b = P.h_bmrec[(size_t)li * N + q];
+          b = P.bmrec.h[(size_t)li * N + q];
           b.n_tokens = (int32_t)std::min<long long>(std::max(b.n_tokens, 0), T);
-          const int* tk = P.h_bmtok + P.tok_off[li] * N + q * T;
+          const int* tk = P.bmtok.h + P.tok_off[li] * N + q * T;
           R.bm_tokens[(size_t)k * N + q].assign(tk, tk + b.n_tokens);
           std::string& t = R.bm_text[(size_t)k * N + q];
           for (int i = 0; i < b.n_tokens; i++) t += s.dict[(size_t)std::min<long long>(std::max(tk[i], 0), (long long)s.dict.size() - 1)];

@@ -140,25 +140,41 @@ struct rt_charsets {
   ~rt_charsets() { if (d_masks) (void)hipFree(d_masks); }
 };
 
-// The session's rec lexicons (ctc_lexicon.h), shared with the helper lanes.  Lexicon k (1-based, rt_lexicon_create's id) is
-// host[k - 1] on the host (stable addresses: rt_lexicon_entry / _entry_text hand them out) and lexicon k - 1 of `tb`, whose four
-// tables sit on the device as `d`.  Only changed while no ticket is in flight and every lane's stream is drained
-// (rt_lexicon_create is a guarded call): the tables are rebuilt and copied whole, with blocking copies.
-struct rt_lexicons {
+// Lists of entries compiled by rt::compile_lexicon: what the rec lexicons and the rec keyword lists both are.  List k (1-based,
+// the id add() returns) is host[k - 1] on the host (stable addresses: the rt_*_entry / _entry_text calls hand them out) and list
+// k - 1 of `tb`, whose four tables sit on the device as `d`.
+struct rt_entry_store {
   struct Host { std::vector<int32_t> ids, lens, off; std::vector<std::string> text; };
   std::vector<std::unique_ptr<Host>> host;
   rt::lx::Tables tb;
   rt::lx::DevTables d{};
+  // what the rt_*_entries / _entry / _entry_text calls answer: list id (null: unknown), its number of entries, entry e's length
+  // and ids, its text (0 / null: no such list or entry)
+  const Host* list(int id) const { return id < 1 || id > (int)host.size() ? nullptr : host[(size_t)id - 1].get(); }
+  int entries(int id) const { return list(id) ? (int)list(id)->lens.size() : 0; }
+  int entry(int id, int e, const int32_t** ids_out) const {
+    if (e < 0 || e >= entries(id)) return 0;
+    if (ids_out) *ids_out = list(id)->ids.data() + list(id)->off[(size_t)e];
+    return list(id)->lens[(size_t)e];
+  }
+  const char* entry_text(int id, int e) const { return e < 0 || e >= entries(id) ? nullptr : list(id)->text[(size_t)e].c_str(); }
+  // Compiles the entries (rt::compile_lexicon over `dict`), builds their host record, rebuilds the tables whole and puts them
+  // on the current device with set(); returns the new list's id.  Whatever throws leaves the store as it was.
+  int add(const std::vector<std::string>& dict, const char* utf8, size_t len, const int32_t* ids, const int32_t* entry_lens, int n);
+  // `fresh` in four device allocations of its own in place of the tables there are, then tb = fresh: a throwing copy leaves the
+  // old ones.  (The rt_debug_ctc_* hooks put their tables on the device with it too.)
+  void set(rt::lx::Tables fresh);
+  ~rt_entry_store();   // (never copied: `host` cannot be)
+};
+
+// The session's rec lexicons (ctc_lexicon.h), shared with the helper lanes: the store and the snap thresholds.  Only changed
+// while no ticket is in flight and every lane's stream is drained (rt_lexicon_create is a guarded call), with blocking copies.
+struct rt_lexicons : rt_entry_store {
   // lexicon snap (ctc_lexicon_align.h, rt_lexicon_set_snap): min_posterior per lexicon, 0 = never snap; d_snap [MAX_LEXICONS]
   // is allocated by the first rt_lexicon_set_snap and changed under the same guard, with a blocking copy
   float snap[rt::lx::MAX_LEXICONS] = {};
   float* d_snap = nullptr;
-  void free_device() {
-    const void* p[] = {d.ids, d.entries, d.order, d.lex};
-    for (const void* q : p) if (q) (void)hipFree(const_cast<void*>(q));
-    d = rt::lx::DevTables{};
-  }
-  ~rt_lexicons() { free_device(); if (d_snap) (void)hipFree(d_snap); }
+  ~rt_lexicons() { if (d_snap) (void)hipFree(d_snap); }
 };
 
 // The session's rec patterns (ctc_pattern.h), shared with the helper lanes.  Pattern k (1-based, rt_pattern_create's id) is
@@ -178,22 +194,13 @@ struct rt_patterns {
   ~rt_patterns() { free_device(); }
 };
 
-// The session's rec keyword lists (ctc_keyword.h), shared with the helper lanes: rt_lexicons' shape.  List k (1-based,
-// rt_keywords_create's id) is host[k - 1] on the host (stable addresses) and list k - 1 of `tb`, whose four tables sit on the
-// device as `d` beside the lists' min_score [rt::kw::MAX_LISTS].  Only changed while no ticket is in flight and every lane's
-// stream is drained (rt_keywords_create is a guarded call): the tables are rebuilt and copied whole, with blocking copies.
-struct rt_keywords {
-  std::vector<std::unique_ptr<rt_lexicons::Host>> host;
-  rt::lx::Tables tb;
-  rt::lx::DevTables d{};
+// The session's rec keyword lists (ctc_keyword.h), shared with the helper lanes: the store and the lists' min_score, on the
+// device as d_min [lists].  Only changed while no ticket is in flight and every lane's stream is drained (rt_keywords_create is
+// a guarded call), with blocking copies.
+struct rt_keywords : rt_entry_store {
   std::vector<float> min_score;
   const float* d_min = nullptr;
-  void free_device() {
-    const void* p[] = {d.ids, d.entries, d.order, d.lex, d_min};
-    for (const void* q : p) if (q) (void)hipFree(const_cast<void*>(q));
-    d = rt::lx::DevTables{}; d_min = nullptr;
-  }
-  ~rt_keywords() { free_device(); }
+  ~rt_keywords() { if (d_min) (void)hipFree(const_cast<float*>(d_min)); }
 };
 
 // internal to the library (never accepted from a caller): pages already in HBM, det map overrides still host pointers
@@ -276,66 +283,74 @@ struct rt_session {
   void ctc_decode(const float* probs, int n, int t, int c, int32_t* idx, float* prob, int32_t* tokens,
                   int32_t* n_tokens, float* scores);
   // ---- the rec network's CTC tail (rec_tail.cpp) ----
-  // What rec_tail reads and writes for ONE rec group, everything on the device.  Row and line arrays start at the group's first
-  // row / line; the lexicon outputs (lexm, lexn, lexs, vit) are indexed by lx::Line::slot, the line's index in the call.
+  // What rec_tail reads and writes for ONE rec group, everything on the device: what every group has, then one member per kind,
+  // left as it is where the plan has nothing of the kind.  Row and line arrays start at the group's first row / line; a kind's
+  // per-line outputs are indexed by its Line::slot, the line's index in the call.
   // (rec_return_word_box, word_boxes.h: pp::word_boxes' arguments; h_lines: the group's descriptors in pinned memory)
   struct WordBoxes { const rt::pp::WordLineDesc* h_lines; const int* label; const float* cscore; int* cols; int* n_words; rt::wb::Word* words; };
   struct RecTail {
-    const float* z5;                          // [rows, core.D] the head's input, inside a larger allocation (RecTailPlan::needs_z5)
-    int* idx; float* prob;                    // [rows] the fused head's argmax rows, in and out
-    const rt::ImgGeom* lines; int n_lines;    // the token level: {first row, 1, T} per line
-    const uint32_t* masks; int words;         // rec charsets: [.][words]
-    // rec lexicons: the device tables (lx::Tables) and the per-lexicon min_posterior (read in a snap group only)
-    rt::lx::DevTables d_lex; const float* d_min_post;
-    int cand_k, chunk_rows;                   // rec_return_candidates; rows per logits recompute (0: cc::CAND_CHUNK)
-    int* tok; int* ntok; float* rscore;       // pp::ctc_decode's outputs
-    float* loglik;                            // [plan.table], or null: taken from `scratch`
-    rt::lx::Match* lexm; int* lexn; int* lexs; float* vit;   // (lexs: snap groups only; vit: optional)
-    int* ccol; rt::cc::Cand* cands;           // cand_k > 0: the kept tokens' time steps and [cand_k] candidates
-    const WordBoxes* wb;                      // or null
-    // rec patterns (ctc_pattern.h): pt::Tables on the device and the per-line results, indexed by pt::Line::slot
-    rt::pt::DevTables d_pat; int* patm; float* patv; float* patlp; float* patfree;
-    // rec keywords (ctc_keyword.h): the lists' lx::Tables and min_score on the device; kwscore [plan.ktable] and kwspan
-    // [plan.ktable][2], or null: taken from `scratch`; the per-line hits and counts, indexed by kw::Line::slot
-    rt::lx::DevTables d_kw; const float* d_kw_min; float* kwscore; int* kwspan; rt::kw::Hit* kwh; int* kwn;
-    // rec beams (ctc_beam.h; beam_b > 0 where the plan has beam lines): the width and the hypotheses per line; the per-line counts
-    // [slot], records [slot][beam_n] and the token pool (bm::Line::out)
-    int beam_b = 0, beam_n = 0; int* bmn = nullptr; rt::bm::Beam* bmrec = nullptr; int* bmtok = nullptr;
+    const float* z5 = nullptr;                // [rows, core.D] the head's input, inside a larger allocation (RecTailPlan::needs_z5)
+    int* idx = nullptr; float* prob = nullptr;   // [rows] the fused head's argmax rows, in and out
+    const rt::ImgGeom* lines = nullptr; int n_lines = 0;   // the token level: {first row, 1, T} per line
+    int chunk_rows = 0;                       // rows per logits recompute (0: cc::CAND_CHUNK)
+    int* tok = nullptr; int* ntok = nullptr; float* rscore = nullptr;   // pp::ctc_decode's outputs
+    const WordBoxes* wb = nullptr;            // or null
+    // rec charsets (ctc_charset.h): [.][words]
+    struct Charsets { const uint32_t* masks = nullptr; int words = 0; } charsets;
+    // rec lexicons (ctc_lexicon.h): lx::Tables on the device; loglik [plan.table], or null: taken from `scratch`; the per-line
+    // matches [slot][lx::MATCHES] and counts.  Lexicon snap: the per-lexicon min_posterior and the per-line flags (both read and
+    // written in a snap group only) and Viterbi values (optional)
+    struct Lexicon {
+      rt::lx::DevTables d{}; float* loglik = nullptr; rt::lx::Match* matches = nullptr; int* n = nullptr;
+      const float* d_min_post = nullptr; int* snapped = nullptr; float* vit = nullptr;
+    } lexicon;
+    // rec patterns (ctc_pattern.h): pt::Tables on the device and the per-line results
+    struct Pattern { rt::pt::DevTables d{}; int* matched = nullptr; float* vit = nullptr; float* logprob = nullptr; float* free_logprob = nullptr; } pattern;
+    // rec keywords (ctc_keyword.h): the lists' lx::Tables and min_score on the device; score [plan.ktable] and span
+    // [plan.ktable][2], or null: taken from `scratch`; the per-line hits [slot][kw::HITS] and counts
+    struct Keywords {
+      rt::lx::DevTables d{}; const float* d_min = nullptr; float* score = nullptr; int* span = nullptr; rt::kw::Hit* hits = nullptr; int* n = nullptr;
+    } keywords;
+    // rec beams (ctc_beam.h; b > 0 where the plan has beam lines): the width and the hypotheses per line; the per-line counts
+    // [slot], records [slot][n] and the token pool (bm::Line::out)
+    struct Beam { int b = 0, n = 0; int* count = nullptr; rt::bm::Beam* recs = nullptr; int* tok = nullptr; } beam;
+    // rec_return_candidates = k > 0 (ctc_candidates.h): the kept tokens' time steps and [k] candidates
+    struct Candidates { int k = 0; int* col = nullptr; rt::cc::Cand* cands = nullptr; } cand;
   };
   // The tail of one rec group behind the net, in the one order that is right: the charsets replace the restricted rows' (idx, prob)
   // before anything reads them; a snap group's lexicons run next, so that the decode reads the snapped lines' aligned rows;
-  // then the patterns, whose matched lines overwrite theirs; pp::ctc_decode; the word boxes; any other group's lexicons; the keywords and the beams, which read and write nothing of the others'; the candidates last, for their host wait.  The plan's tables go
-  // through `pinned` into `scratch`, where the workspace comes from too: the caller rewinds it per group, after this.
+  // then the patterns, whose matched lines overwrite theirs; pp::ctc_decode; the word boxes; any other group's lexicons; the
+  // keywords and the beams, which read and write nothing of the others'; the candidates last, for their host wait.  The four
+  // kinds of whole lines -- lexicons, patterns, keywords, beams -- share one pass (rec_tail.cpp LinePass): chunks of about
+  // chunk_rows rows of whole lines, per chunk the row gather, the CTC FC, the row statistics, then the kind's own launches.  The
+  // plan's tables go through `pinned` into `scratch`, where the workspace comes from too: the caller rewinds it per group, after this.
   void rec_tail(const rt::RecTailPlan& plan, const rt::SvtrCore& core, const RecTail& t);
-  // rec_return_candidates = K (ctc_candidates.h): kept token j of a line at first row o gets ccol[o + j] and cands[(o + j) * K ...].
+  // rec_return_candidates = K (ctc_candidates.h): kept token j of a line at first row o gets col[o + j] and cands[(o + j) * K ...].
   // K > 1 waits for the stream once (the kept-row count sizes the logits GEMMs) and recomputes in chunks of kept rows.  d_row_set
   // (rec charsets, or null): a kept row r with d_row_set[r] = s >= 1 ranks the classes of set s only.
   void ctc_candidates(const rt::SvtrCore& core, const RecTail& t, long long rows, const int* d_row_set);
   // Rec charsets (ctc_charset.h): d_rows [n_rows] / d_row_set [rows] = the plan's crows / row_set.  In chunks of rows: row gather,
   // the CTC FC, k_ctc_charset_argmax, which overwrites idx / prob of exactly those rows.  No host wait.
   void ctc_charset(const rt::SvtrCore& core, const RecTail& t, const int* d_rows, int n_rows, const int* d_row_set);
-  // Rec lexicons (ctc_lexicon.h) over the plan's lexicon lines, in chunks of whole lines of about chunk_rows rows (at least one
-  // line, so a line's T rows are resident together): row gather, the CTC FC, k_ctc_row_lse, k_ctc_lexicon_forward -> loglik; then
-  // one k_ctc_lexicon_topk over all lines -> lexm / lexn.  No host wait.  A snap group (ctc_lexicon_align.h) runs the top-K per chunk,
-  // then k_ctc_lexicon_align on the resident logits: it overwrites the snapped lines' rows of idx / prob and writes every lexs[slot].
+  // Rec lexicons (ctc_lexicon.h) over the plan's lexicon lines, with k_ctc_row_lse: per chunk k_ctc_lexicon_forward -> loglik; then
+  // one k_ctc_lexicon_topk over all lines -> matches / n.  No host wait.  A snap group (ctc_lexicon_align.h) runs the top-K per chunk,
+  // then k_ctc_lexicon_align on the resident logits: it overwrites the snapped lines' rows of idx / prob and writes every snapped[slot].
   void ctc_lexicon(const rt::RecTailPlan& plan, const rt::SvtrCore& core, const RecTail& t);
-  // Rec patterns (ctc_pattern.h) over the plan's pattern lines, chunked as the lexicon lines are: row gather, the CTC FC,
-  // k_ctc_row_lse and k_ctc_row_max, then k_ctc_pattern_viterbi on the resident logits: it overwrites the matched lines' rows of
-  // idx / prob and writes every pattern line's patm / patv / patlp / patfree [slot].  No host wait.
+  // Rec patterns (ctc_pattern.h) over the plan's pattern lines, with k_ctc_row_lse and k_ctc_row_max: per chunk
+  // k_ctc_pattern_viterbi, which overwrites the matched lines' rows of idx / prob and writes every pattern line's results [slot].
+  // No host wait.
   void ctc_pattern(const rt::RecTailPlan& plan, const rt::SvtrCore& core, const RecTail& t);
-  // Rec keywords (ctc_keyword.h) over the plan's keyword lines, chunked as the lexicon lines are: row gather, the CTC FC,
-  // k_ctc_row_max, k_ctc_keyword_spot -> kwscore / kwspan; then one k_ctc_keyword_topk over all lines -> kwh / kwn.  No host
-  // wait, and no value that anything else reads.
+  // Rec keywords (ctc_keyword.h) over the plan's keyword lines, with k_ctc_row_max: per chunk k_ctc_keyword_spot -> score / span;
+  // then one k_ctc_keyword_topk over all lines -> hits / n.  No host wait, and no value that anything else reads.
   void ctc_keywords(const rt::RecTailPlan& plan, const rt::SvtrCore& core, const RecTail& t);
-  // Rec beams (ctc_beam.h) over the plan's beam lines, chunked as the keyword lines are: row gather, the CTC FC, k_ctc_row_lse,
-  // k_ctc_beam_topc, then k_ctc_beam_search on the resident logits -> bmn / bmrec / bmtok.  The trie comes from `scratch`.  No
-  // host wait, and no value that anything else reads.
+  // Rec beams (ctc_beam.h) over the plan's beam lines, with k_ctc_row_lse: per chunk k_ctc_beam_topc, then k_ctc_beam_search on the
+  // resident logits -> count / recs / tok.  The trie comes from `scratch`.  No host wait, and no value that anything else reads.
   void ctc_beams(const rt::RecTailPlan& plan, const rt::SvtrCore& core, const RecTail& t);
   // rt_charset_create: compiles the set (rt::compile_charset), stores it and returns its id
   int charset_create(const char* utf8, size_t len, const int32_t* ids, int n_ids);
-  // rt_lexicon_create: compiles the entries (rt::compile_lexicon), stores them and returns the lexicon's id
+  // rt_lexicon_create: the entries into the lexicon store (rt_entry_store::add); returns the lexicon's id
   int lexicon_create(const char* utf8, size_t len, const int32_t* ids, const int32_t* entry_lens, int n_id_entries);
-  // rt_keywords_create: compiles the entries as a lexicon's (rt::compile_lexicon), stores them with min_score and returns the list's id
+  // rt_keywords_create: the entries into the keyword store (rt_entry_store::add) with min_score; returns the list's id
   int keywords_create(const char* utf8, size_t len, const int32_t* ids, const int32_t* entry_lens, int n_id_entries, float min_score);
   // rt_pattern_create: compiles the pattern (rt::pt::compile), stores it and returns its id
   int pattern_create(const char* utf8, size_t len);

@@ -16,6 +16,11 @@
 //        <n_lex> <n16 n32 n64 of each lexicon: its entries of 1, 8 and 16 ids> <1 + n_lex snap thresholds, or 0>
 //     -> rec_tail_plan() (rec_tail_plan.h) of lines [l0, l1): rows=.. z5=.. has_lex=.. snap=.. table=.. fits=.. max_waves=..
 //        row_set=a,b,.. crows=.. lines=row0:T:lex:slot:out,.. lrows=..   (an empty list prints as -)
+//   group <l0> <l1> <beam> <nbest> <NL> <T of each line> <n_lex> <n16 n32 n64 of each lexicon> <a snap threshold per lexicon>
+//         <n_kw> <n16 n32 n64 of each keyword list> <n_pat> <S P of each pattern> <charset lexicon pattern keywords of each line>
+//     -> rec_tail_plan() of lines [l0, l1) with every kind at once: row_set=.. crows=.. lines=.. lrows=.. plines=row0:T:pat:slot:bp,..
+//        prows=.. klines=row0:T:list:slot:out,.. krows=.. blines=row0:T:node0:slot:out,.. brows=..
+//   capacity <the arguments of group>  ->  RecTailPlan::refusal(beam) of that group, or -
 //   defaults <charset> <lexicon> <pattern>  ->  rec_opts_conflict() of session defaults: ok   or   error: <message>
 //   regions <default charset lexicon pattern> <count of charsets lexicons patterns> <n_pages> <regions of each page>
 //           then per kind (charsets, lexicons, patterns): 0 = no array, or 1 and per page: 0 = no entry, or 1 and the regions' ids
@@ -61,6 +66,28 @@ static void print_dw(const nn::DwPlan& p) {
 static void print_list(const char* name, const std::vector<int>& v) {
   printf(" %s=%s", name, v.empty() ? "-" : "");
   for (size_t i = 0; i < v.size(); i++) printf(i ? ",%d" : "%d", v[i]);
+}
+static void print_line(const lx::Line& l) { printf("%d:%d:%d:%d:%lld", l.row0, l.T, l.lex, l.slot, l.out); }
+static void print_line(const pt::Line& l) { printf("%d:%d:%d:%d:%lld", l.row0, l.T, l.pat, l.slot, l.bp); }
+template <typename Line>
+static void print_lines(const char* name, const char* rows_name, const std::vector<Line>& lines, const std::vector<int>& rows) {
+  printf(" %s=%s", name, lines.empty() ? "-" : "");
+  for (size_t i = 0; i < lines.size(); i++) { if (i) printf(","); print_line(lines[i]); }
+  print_list(rows_name, rows);
+}
+// n lists of a query as lx::Tables: n16 n32 n64 each, its entries of 1, 8 and 16 ids (class 1 throughout)
+static void read_lists(std::istream& in, int n, lx::Tables& tb) {
+  for (int k = 0; k < n && in; k++) {
+    int n16, n32, n64;
+    in >> n16 >> n32 >> n64;
+    if (!in || n16 < 0 || n32 < 0 || n64 < 0) { in.setstate(std::ios::failbit); break; }
+    std::vector<int32_t> lens;
+    lens.insert(lens.end(), (size_t)n16, 1); lens.insert(lens.end(), (size_t)n32, 8); lens.insert(lens.end(), (size_t)n64, 16);
+    size_t n_ids = 0;
+    for (int32_t m : lens) n_ids += (size_t)m;
+    const std::vector<int32_t> ids(n_ids, 1);
+    tb.add(ids.data(), lens.data(), (int)lens.size());
+  }
 }
 // an optional array of a query: a 0, or a 1 and n values
 template <typename T>
@@ -132,17 +159,7 @@ int main() {
       const bool has_set = read_optional(in, (size_t)NL, sets), has_lex = read_optional(in, (size_t)NL, lexs);
       in >> n_lex;
       lx::Tables tb;
-      for (int k = 0; k < n_lex && in; k++) {
-        int n16, n32, n64;
-        in >> n16 >> n32 >> n64;
-        if (!in || n16 < 0 || n32 < 0 || n64 < 0) break;
-        std::vector<int32_t> lens;
-        lens.insert(lens.end(), (size_t)n16, 1); lens.insert(lens.end(), (size_t)n32, 8); lens.insert(lens.end(), (size_t)n64, 16);
-        size_t n_ids = 0;
-        for (int32_t n : lens) n_ids += (size_t)n;
-        const std::vector<int32_t> ids(n_ids, 1);
-        tb.add(ids.data(), lens.data(), (int)lens.size());
-      }
+      read_lists(in, n_lex, tb);
       const bool has_snap = read_optional(in, (size_t)n_lex, snaps);
       if (!in) { printf("bad query\n"); return 2; }
       for (int v : lexs) if (v < 0 || v > n_lex) { printf("bad query\n"); return 2; }
@@ -151,11 +168,39 @@ int main() {
       printf("rows=%lld z5=%d has_lex=%d snap=%d table=%lld fits=%d max_waves=%d", p.rows, (int)p.needs_z5(cand_k), (int)p.has_lex(),
              (int)p.snap, p.table, (int)p.table_fits(), p.max_waves);
       print_list("row_set", p.row_set); print_list("crows", p.crows);
-      printf(" lines=%s", p.lines.empty() ? "-" : "");
-      for (size_t i = 0; i < p.lines.size(); i++)
-        printf("%s%d:%d:%d:%d:%lld", i ? "," : "", p.lines[i].row0, p.lines[i].T, p.lines[i].lex, p.lines[i].slot, p.lines[i].out);
-      print_list("lrows", p.lrows);
+      print_lines("lines", "lrows", p.lines, p.lrows);
       printf("\n");
+    } else if (op == "group" || op == "capacity") {
+      int l0, l1, beam, nbest, NL, n_lex = 0, n_kw = 0, n_pat = 0;
+      in >> l0 >> l1 >> beam >> nbest >> NL;
+      if (!in || NL < 0 || l0 < 0 || l0 > l1 || l1 > NL) { printf("bad query\n"); return 2; }
+      std::vector<long long> tok_off((size_t)NL + 1, 0);
+      for (int i = 0; i < NL; i++) { int T; in >> T; tok_off[(size_t)i + 1] = tok_off[(size_t)i] + T; }
+      lx::Tables tb, ktb;
+      pt::Tables ptb;
+      in >> n_lex;
+      read_lists(in, n_lex, tb);
+      std::vector<float> snaps((size_t)std::max(n_lex, 0));
+      for (float& v : snaps) in >> v;
+      in >> n_kw;
+      read_lists(in, n_kw, ktb);
+      in >> n_pat;
+      for (int k = 0; k < n_pat && in; k++) { int S, P; in >> S >> P; ptb.pats.push_back(pt::Pat{S, P, 0, 0, 0, 0, 0}); }
+      std::vector<RecLineOpts> opts((size_t)NL);
+      for (RecLineOpts& o : opts) in >> o.charset >> o.lexicon >> o.pattern >> o.keywords;
+      if (!in) { printf("bad query\n"); return 2; }
+      for (const RecLineOpts& o : opts)
+        if (o.lexicon < 0 || o.lexicon > n_lex || o.pattern < 0 || o.pattern > n_pat || o.keywords < 0 || o.keywords > n_kw) { printf("bad query\n"); return 2; }
+      const RecTailPlan p = rec_tail_plan(tok_off.data(), l0, l1, opts.data(), RecStores{&tb, snaps.data(), &ptb, &ktb}, beam, nbest);
+      if (op == "capacity") {
+        const std::string why = p.refusal(beam);
+        printf("%s\n", why.empty() ? "-" : why.c_str());
+      } else {
+        print_list("row_set", p.row_set); print_list("crows", p.crows);
+        print_lines("lines", "lrows", p.lines, p.lrows); print_lines("plines", "prows", p.plines, p.prows);
+        print_lines("klines", "krows", p.klines, p.krows); print_lines("blines", "brows", p.blines, p.brows);
+        printf("\n");
+      }
     } else if (op == "defaults") {
       RecLineOpts o;
       in >> o.charset >> o.lexicon >> o.pattern;

@@ -125,3 +125,112 @@ def test_table_capacity_edge(answers):
     assert "table=%d fits=1 " % MAX_GROUP_TABLE in at and "rows=1024 " in at
     assert "table=%d fits=0 " % (MAX_GROUP_TABLE + 1) in over and "rows=1025 " in over
     assert over.split(" lines=")[1].split(" ")[0].endswith(",1024:1:1:1025:%d" % MAX_GROUP_TABLE)
+
+
+# ---- every kind in one group, and the group's capacity (RecTailPlan::refusal) ----
+MAX_GROUP_NODES = 1 << 26
+BP_LDS = 8192                         # pt::BP_LDS: a pattern line's backpointer codes up to here stay in the kernel's LDS
+
+
+def group_query(op, T, l0, l1, opts, lexicons=(), snaps=(), lists=(), pats=(), beam=0, nbest=0):
+    """opts: per line (charset, lexicon, pattern, keywords); lexicons / lists: (n16, n32, n64) each; pats: (S, P) each"""
+    words = [op, l0, l1, beam, nbest, len(T)] + list(T) + [len(lexicons)]
+    for lex in lexicons:
+        words += list(lex)
+    words += ["%g" % v for v in (snaps or [0] * len(lexicons))] + [len(lists)]
+    for kw in lists:
+        words += list(kw)
+    words += [len(pats)]
+    for p in pats:
+        words += list(p)
+    for o in opts:
+        words += list(o)
+    return " ".join(str(w) for w in words)
+
+
+def group_expected(T, l0, l1, opts, lexicons=(), snaps=(), lists=(), pats=(), beam=0, nbest=0):
+    """The four line tables of the group from the rules, each kind on its own: a line is (first position in ITS kind's compact row
+    list, T, id 0-based or first trie node, line index in the call, its kind's running offset), and its T rows follow the kind's
+    earlier lines' rows.  The offsets: a lexicon's / a list's entries; a pattern line's T (P + S) codes where they exceed BP_LDS;
+    a beam line's 1 + T B trie nodes (the id) and N T token slots (the offset)."""
+    first = [sum(T[:i]) - sum(T[:l0]) for i in range(len(T) + 1)]
+    group = range(l0, l1)
+    crows = [first[i] + t for i in group for t in range(T[i]) if opts[i][0] > 0]
+    row_set = [opts[i][0] for i in group for _ in range(T[i])] if crows else []
+    kinds = {k: ([], []) for k in ("lex", "pat", "kw", "beam")}
+    table = bp = ktable = nodes = slots = 0
+
+    def add(kind, i, ident, out):
+        lines, rows = kinds[kind]
+        lines.append("%d:%d:%d:%d:%d" % (len(rows), T[i], ident, i, out))
+        rows += [first[i] + t for t in range(T[i])]
+    for i in group:
+        _, lex, pat, kw = opts[i]
+        if lex > 0:
+            add("lex", i, lex - 1, table)
+            table += sum(lexicons[lex - 1])
+        if pat > 0:
+            add("pat", i, pat - 1, bp)
+            S, P = pats[pat - 1]
+            bp += T[i] * (P + S) if T[i] * (P + S) > BP_LDS else 0
+        if kw > 0:
+            add("kw", i, kw - 1, ktable)
+            ktable += sum(lists[kw - 1])
+        if beam > 0:
+            add("beam", i, nodes, slots)
+            nodes += 1 + T[i] * beam
+            slots += nbest * T[i]
+
+    def lst(v):
+        return ",".join(str(x) for x in v) if v else "-"
+    out = " row_set=%s crows=%s" % (lst(row_set), lst(crows))
+    for kind, names in (("lex", "lines lrows"), ("pat", "plines prows"), ("kw", "klines krows"), ("beam", "blines brows")):
+        out += " %s=%s %s=%s" % (names.split()[0], lst(kinds[kind][0]), names.split()[1], lst(kinds[kind][1]))
+    return out
+
+
+# lines 1 .. 6 of the call are the group: a charset line, a snapping lexicon on a T = 0 line and on a T = 65 line (with keywords),
+# a pattern whose 65 (100 + 30) codes leave the LDS and the same pattern short, a keyword line with a charset; the beam on all
+COMBINED = dict(T=[2, 3, 0, 65, 65, 4, 1, 5], l0=1, l1=7,
+                opts=[(1, 1, 0, 1), (2, 0, 0, 0), (0, 2, 0, 0), (0, 2, 0, 2), (0, 0, 1, 1), (0, 0, 1, 0), (1, 1, 0, 2), (0, 2, 1, 0)],
+                lexicons=[A, B], snaps=[0, 0.5], lists=[(3, 0, 0), (2, 1, 0)], pats=[(30, 100)], beam=4, nbest=2)
+
+
+def test_every_kind_in_one_group(exe):
+    """The four kinds share one add(): every table keeps its own row positions and its own offsets."""
+    got, = plan_driver.run(exe, [group_query("group", **COMBINED)])
+    assert got == group_expected(**COMBINED)
+    # ... and by hand: the lexicon lines 2, 3, 6; the pattern lines 4 (8450 codes, past the LDS) and 5; the keyword lines 3, 4, 6;
+    # every line with the beam (1 + 4 T nodes, 2 T token slots)
+    r = lambda a, b: ",".join(str(v) for v in range(a, b))
+    assert got == (" row_set=" + ",".join(["2"] * 3 + ["0"] * 134 + ["1"]) + " crows=0,1,2,137"
+                   " lines=0:0:1:2:0,0:65:1:3:4,65:1:0:6:8 lrows=" + r(3, 68) + ",137"
+                   " plines=0:65:0:4:0,65:4:0:5:8450 prows=" + r(68, 137) +
+                   " klines=0:65:1:3:0,65:65:0:4:3,130:1:1:6:6 krows=" + r(3, 133) + ",137"
+                   " blines=0:3:0:1:0,3:0:13:2:6,3:65:14:3:6,68:65:275:4:136,133:4:536:5:266,137:1:553:6:274 brows=" + r(0, 138))
+
+
+LEX_REFUSAL = ("rec lexicons: 1025 lines of one rec group carry lexicons of 67108865 entries in all, more than the 67108864 likelihoods a "
+               "group's table holds: use smaller lexicons or fewer lexicon lines per call")
+KW_REFUSAL = ("rec keywords: 1025 lines of one rec group carry keyword lists of 67108865 entries in all, more than the 67108864 scores a "
+              "group's table holds: use smaller keyword lists or fewer keyword lines per call")
+BEAM_REFUSAL = ("rec beams: the 2048 lines of one rec group need 67108896 trie nodes at beam 32, more than the 67108864 a group's trie "
+                "holds: use a narrower beam or fewer lines per call")
+
+
+def test_capacity_refusals(exe):
+    """What rec_groups refuses a group with (RT_ERR_CAPACITY), in full: nothing exactly at each limit, the message one past it,
+    and the first in the order lexicons, keywords, beams where several are exceeded.  1024 lines of a 65536-entry list are
+    lx::MAX_GROUP_TABLE entries; 2047 lines of 1024 steps and one of 960 are bm::MAX_GROUP_NODES nodes at beam 32 (1 + 32 T each)."""
+    two = [FULL, (1, 0, 0)]
+    ones = lambda n, **kw: dict(T=[1] * n, l0=0, l1=n, **kw)
+    lex = lambda n: ones(n, opts=[(0, 1, 0, 0)] * 1024 + [(0, 2, 0, 0)] * (n - 1024), lexicons=two)
+    kws = lambda n: ones(n, opts=[(0, 0, 0, 1)] * 1024 + [(0, 0, 0, 2)] * (n - 1024), lists=two)
+    beams = lambda last, opts=None, **kw: dict(T=[1024] * 2047 + [last], l0=0, l1=2048, opts=opts or [(0, 0, 0, 0)] * 2048, beam=32, nbest=1, **kw)
+    assert 2047 * (1 + 32 * 1024) + 1 + 32 * 960 == MAX_GROUP_NODES
+    both = ones(1025, opts=[(0, 1, 0, 1)] * 1024 + [(0, 2, 0, 2)], lexicons=two, lists=two)
+    kw_and_beam = beams(961, opts=[(0, 0, 0, 1)] * 1024 + [(0, 0, 0, 2)] + [(0, 0, 0, 0)] * 1023, lists=two)
+    all_three = beams(961, opts=[(0, 1, 0, 1)] * 1024 + [(0, 2, 0, 2)] + [(0, 0, 0, 0)] * 1023, lexicons=two, lists=two)
+    cases = [lex(1024), lex(1025), kws(1024), kws(1025), beams(960), beams(961), both, kw_and_beam, all_three]
+    got = plan_driver.run(exe, [group_query("capacity", **c) for c in cases])
+    assert got == ["-", LEX_REFUSAL, "-", KW_REFUSAL, "-", BEAM_REFUSAL, LEX_REFUSAL, KW_REFUSAL, LEX_REFUSAL]
