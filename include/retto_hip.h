@@ -264,6 +264,40 @@ RT_API int rt_det_tile_plan(int h, int w, int tile, int overlap, int32_t* row_or
  * the pipeline's own function and launch groups.  tile_maps_out (optional): every tile's own map, tile_h x tile_w floats each,
  * packed in plan order; page_map_out [h * w]: the stitched map (the network's map for a page that is not tiled). */
 RT_API int rt_debug_det_tiles(rt_session* s, const uint8_t* rgb_det, int h, int w, float* tile_maps_out, float* page_map_out);
+/* Rec windows (retto_amd/csrc/rec_windows.h states the rule): long lines read at a familiar width.  Det tiles and crop_source = 1
+ * produce long lines: a text line across a 7680-pixel scan is a 48 x 3000 rec tensor with 400 time steps, which the recogniser
+ * would read as one image -- its attention over all 400 steps, every squeeze-excite block pooled over the whole line.  With
+ * windows on, a rec line at least 8 columns wider than `window` is run through the rec network as overlapping units of `window`
+ * columns (the last one up to 7 wider), and each unit's trusted time steps -- up to the middle of the overlap with its neighbour
+ * -- are copied into the ONE line's rows of per-step (index, probability) and head-input features.  The copy is a selection,
+ * every time step comes from exactly one unit; the line keeps its number of time steps and its geometry, so the greedy decode,
+ * word boxes, candidates, charsets, lexicons and snap, patterns, keywords and beams run on it unchanged.  The units of all lines
+ * of a rec launch group run in one pass of the network.  A line that is not windowed takes the whole-line path, a group without
+ * a windowed line launches nothing that it did not before, and with windows off (the default) nothing changes.  It applies to
+ * every pipeline entry point, rt_run_regions* included; rt_rec, rt_rec_ragged and rt_ctc_decode never window.
+ * window = 0: off; otherwise a multiple of 32, at least 128.  overlap: a multiple of 32, 0 <= overlap <= window / 2.  Anything
+ * else: RT_ERR_INVALID naming the parameter.  The setting holds for the pipeline calls that follow on every lane (rt_submit_*
+ * takes it as it is at the call); fails like every other call while tickets are in flight.
+ * What windows do to accuracy with trained PP-OCRv4 weights has NOT been measured; a multiple of the 320 base width is the
+ * familiar regime, nothing more is recommended. */
+RT_API int rt_set_rec_windows(rt_session* s, int window, int overlap);
+/* the setting (each optional); RT_ERR_INVALID for a NULL session */
+RT_API int rt_rec_windows(const rt_session* s, int* window, int* overlap);
+/* The window plan of a rec line of L >= 8 columns, GPU-free and sessionless.  *n units, *T = the line's time steps; unit i covers
+ * the columns [origin[i], origin[i] + width[i]), its time step k is the line's step origin[i] / 8 + k, and it owns the line's
+ * steps [i ? bound[i - 1] : 0, bound[i]).  Each output is optional; the arrays are written when cap holds the plan
+ * (RT_ERR_INVALID otherwise, the counts still written).  A line that is not windowed (window = 0, or L < window + 8) is one
+ * unit.  Bad parameters: RT_ERR_INVALID naming the parameter (rt_last_error(NULL)). */
+RT_API int rt_rec_window_plan(int L, int window, int overlap, int32_t* origin, int32_t* width, int32_t* bound, int cap, int* n, int* T);
+/* the number of units line `line` of page `page` was read in: 1 for a whole line, 0 out of range */
+RT_API int rt_results_rec_windows(const rt_results* r, int page, int line);
+/* n lines of [3, 48, widths[i]] (host, NCHW, concatenated, as rt_rec_ragged takes them) run as ONE rec group through the
+ * pipeline's own cut, network and stitch functions under the session's rec windows.  Every output is optional: every unit's rows
+ * in unit order, line after line (unit_idx_out / unit_prob_out: one per unit time step; unit_z5_out: 120 floats per step), and
+ * the stitched rows of every line (line_*_out, likewise, one row per line time step). */
+RT_API int rt_debug_rec_windows(rt_session* s, const float* nchw, int n, const int* widths, int32_t* unit_idx_out,
+                                float* unit_prob_out, float* unit_z5_out, int32_t* line_idx_out, float* line_prob_out,
+                                float* line_z5_out);
 /* The pipeline over regions the caller already knows (form fields, subtitles, corrected boxes, another detector's boxes):
  * quads[i] = n_quads[i] x 8 floats in host memory, TL, TR, BR, BL of each region in original-page coordinates; mem
  * (RT_MEM_HOST or RT_MEM_DEVICE) says where the pages live.  Every coordinate is clamped to [0, ori - 1] (no rounding); line k

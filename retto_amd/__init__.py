@@ -223,6 +223,8 @@ class RecProcessorSingleResult:
     # rec beams (set_rec_beam): None when the option is off, else the line's most probable strings by CTC prefix beam search,
     # best first (retto_amd/csrc/ctc_beam.h)
     beams: Optional[List["BeamHypothesis"]] = None
+    # rec windows (set_rec_windows): the number of units the line was read in, 1 for a whole line (retto_amd/csrc/rec_windows.h)
+    windows: int = 1
 
 
 @dataclass
@@ -528,6 +530,29 @@ def det_tile_plan(h: int, w: int, tile: int, overlap: int = 64) -> dict:
                 "col_origins": co[:nc.value], "col_bounds": cb[:nc.value]}
 
 
+_WINDOW_PLAN_BUFS = None   # the three output arrays of rec_window_plan, grown on demand, as det_tile_plan's
+
+
+def rec_window_plan(L: int, window: int, overlap: int = 0) -> dict:
+    """rt_rec_window_plan: the window plan (retto_amd/csrc/rec_windows.h) of a rec line of L columns, GPU-free: a dict with T,
+    the line's time steps, and per unit its origin, width and ownership bound as lists (unit i covers the columns [origins[i],
+    origins[i] + widths[i]) and owns the steps [bounds[i - 1], bounds[i]), from 0).  A line that is not windowed is one unit."""
+    global _WINDOW_PLAN_BUFS
+    lib = _lib.load()
+    n, T = C.c_int(), C.c_int()
+    cap = len(_WINDOW_PLAN_BUFS[0]) if _WINDOW_PLAN_BUFS else 64
+    while True:
+        if _WINDOW_PLAN_BUFS is None or len(_WINDOW_PLAN_BUFS[0]) < cap:
+            _WINDOW_PLAN_BUFS = [(C.c_int32 * cap)() for _ in range(3)]
+        o, w, b = _WINDOW_PLAN_BUFS
+        rc = lib.rt_rec_window_plan(int(L), int(window), int(overlap), o, w, b, cap, C.byref(n), C.byref(T))
+        if rc == 8 and n.value > cap:
+            cap = 2 * n.value
+            continue
+        _check(rc, None)
+        return {"T": T.value, "origins": o[:n.value], "widths": w[:n.value], "bounds": b[:n.value]}
+
+
 def parse_dictionary(data: bytes) -> List[str]:
     """rt_parse_dictionary: RecCharacter::new (rec_processor.rs:29-46) -- "blank", the file's trimmed lines, " "."""
     lib = _lib.load()
@@ -684,7 +709,8 @@ class RettoSession:
             snapped = None if matches is None else bool(lib.rt_results_rec_lexicon_snapped(r, page, k))
             rec.append(RecProcessorSingleResult(lib.rt_results_rec_text(r, page, k).decode("utf-8"), float(rs[k]), toks, words,
                                                 cands, cols, matches, snapped, self._pattern(r, page, k),
-                                                self._keywords(r, page, k), self._beams(r, page, k, beam_on)))
+                                                self._keywords(r, page, k), self._beams(r, page, k, beam_on),
+                                                int(lib.rt_results_rec_windows(r, page, k))))
         return RettoWorkerResult(det, cls, rec)
 
     def _dictionary(self) -> List[str]:
@@ -798,6 +824,50 @@ class RettoSession:
         tiles = np.empty((n, plan["tile_h"], plan["tile_w"]), np.float32); page = np.empty((h, w), np.float32)
         _check(self._hd.lib.rt_debug_det_tiles(self._hd.h, img.ctypes.data, h, w, tiles.ctypes.data, page.ctypes.data), self._hd.h)
         return tiles, page, plan
+
+    # -- rec windows ------------------------------------------------------------------------
+    def set_rec_windows(self, window: int, overlap: int = 0) -> None:
+        """rt_set_rec_windows: rec lines at least 8 columns wider than ``window`` are read as overlapping windows whose trusted
+        time steps are stitched into the one line's rows (retto_amd/csrc/rec_windows.h); 0 = off, the default.  window: a
+        multiple of 32, at least 128; overlap: a multiple of 32, at most window / 2.  Holds for the pipeline calls that follow.
+        The effect on accuracy with trained weights has not been measured."""
+        _check(self._hd.lib.rt_set_rec_windows(self._hd.h, int(window), int(overlap)), self._hd.h)
+
+    @property
+    def rec_windows(self) -> Tuple[int, int]:
+        """rt_rec_windows: (window, overlap) as set; window 0 = off."""
+        w, o = C.c_int(), C.c_int()
+        _check(self._hd.lib.rt_rec_windows(self._hd.h, C.byref(w), C.byref(o)), self._hd.h)
+        return w.value, o.value
+
+    def debug_rec_windows(self, lines: Sequence[np.ndarray]):
+        """rt_debug_rec_windows: the lines ([3, 48, W_i] float32 each) as ONE rec group through the pipeline's own cut, network
+        and stitch under the session's rec windows.  Returns (units, stitched, plans): units[i] = the list of line i's units as
+        (idx [Tu], prob [Tu], z5 [Tu, 120]) in plan order, stitched[i] = (idx [T], prob [T], z5 [T, 120]) of line i, plans[i] =
+        rec_window_plan(W_i, *self.rec_windows)."""
+        lib = _lib.load()
+        arrs = [np.ascontiguousarray(a, np.float32) for a in lines]
+        for a in arrs:
+            if a.ndim != 3 or a.shape[0] != 3 or a.shape[1] != 48:
+                raise ValueError("debug_rec_windows: every line is [3, 48, W]")
+        window, overlap = self.rec_windows
+        widths = np.array([a.shape[2] for a in arrs], np.int32)
+        plans = [rec_window_plan(int(w), window, overlap) for w in widths]
+        unit_T = [[rec_window_plan(int(w), 0, 0)["T"] for w in p["widths"]] for p in plans]   # (a unit's own time steps)
+        nu = sum(sum(t) for t in unit_T); nl = sum(p["T"] for p in plans)
+        flat = np.concatenate([a.ravel() for a in arrs])
+        u_idx = np.empty(max(nu, 1), np.int32); u_prob = np.empty(max(nu, 1), np.float32); u_z5 = np.empty((max(nu, 1), 120), np.float32)
+        l_idx = np.empty(max(nl, 1), np.int32); l_prob = np.empty(max(nl, 1), np.float32); l_z5 = np.empty((max(nl, 1), 120), np.float32)
+        _check(lib.rt_debug_rec_windows(self._hd.h, flat.ctypes.data, len(arrs), widths.ctypes.data, u_idx.ctypes.data, u_prob.ctypes.data,
+                                        u_z5.ctypes.data, l_idx.ctypes.data, l_prob.ctypes.data, l_z5.ctypes.data), self._hd.h)
+        units, stitched, uo, lo = [], [], 0, 0
+        for p, ts in zip(plans, unit_T):
+            us = []
+            for t in ts:
+                us.append((u_idx[uo:uo + t].copy(), u_prob[uo:uo + t].copy(), u_z5[uo:uo + t].copy())); uo += t
+            units.append(us)
+            stitched.append((l_idx[lo:lo + p["T"]].copy(), l_prob[lo:lo + p["T"]].copy(), l_z5[lo:lo + p["T"]].copy())); lo += p["T"]
+        return units, stitched, plans
 
     # -- rec charsets -----------------------------------------------------------------------
     def create_charset(self, text: str = "", ids: Sequence[int] = ()) -> int:

@@ -115,6 +115,7 @@ EXPORTS = [
     "rt_set_rec_beam", "rt_rec_beam", "rt_results_rec_beams", "rt_results_rec_beam_tokens", "rt_results_rec_beam_text",
     "rt_debug_ctc_beam", "rt_debug_ctc_beam_host",
     "rt_set_det_tiles", "rt_det_tiles", "rt_det_tile_plan", "rt_debug_det_tiles", "rt_debug_arena_high_water", "rt_bench_memcpy_d2d",
+    "rt_set_rec_windows", "rt_rec_windows", "rt_rec_window_plan", "rt_results_rec_windows", "rt_debug_rec_windows",
 ]
 
 STAGE_CALLBACK = C.CFUNCTYPE(None, C.c_void_p, C.c_int, C.c_int, C.c_char_p)  # rt_stage_callback
@@ -357,5 +358,11 @@ def load():
     lib.rt_debug_det_tiles.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
     lib.rt_debug_arena_high_water.argtypes = [C.c_void_p, P(C.c_longlong)]
     lib.rt_bench_memcpy_d2d.argtypes = [C.c_void_p, C.c_size_t, C.c_int, P(C.c_float)]
+    lib.rt_set_rec_windows.argtypes = [C.c_void_p, C.c_int, C.c_int]
+    lib.rt_rec_windows.argtypes = [C.c_void_p, P(C.c_int), P(C.c_int)]
+    lib.rt_rec_window_plan.argtypes = [C.c_int, C.c_int, C.c_int, P(C.c_int32), P(C.c_int32), P(C.c_int32), C.c_int, P(C.c_int), P(C.c_int)]
+    lib.rt_results_rec_windows.argtypes = [C.c_void_p, C.c_int, C.c_int]
+    lib.rt_debug_rec_windows.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                         C.c_void_p, C.c_void_p]
     _lib = lib
     return lib

@@ -58,6 +58,12 @@ def build_parser() -> argparse.ArgumentParser:
                          "into one page map (large scans at their own resolution); a multiple of 32, at least 64; 0 = off")
     ap.add_argument("--det-tile-overlap", type=int, default=64, metavar="M",
                     help="with --det-tile: the tiles' overlap, a multiple of 32, at most N / 2")
+    ap.add_argument("--rec-window", type=int, default=0, metavar="N",
+                    help="read rec lines at least 8 columns wider than N as overlapping windows of N columns, stitched into the "
+                         "one line (long lines at a familiar width; the effect on accuracy is not measured); a multiple of 32, "
+                         "at least 128; 0 = off")
+    ap.add_argument("--rec-window-overlap", type=int, default=0, metavar="M",
+                    help="with --rec-window: the windows' overlap, a multiple of 32, at most N / 2")
     return ap
 
 
@@ -90,6 +96,8 @@ def main(argv=None) -> int:
     session = retto_amd.RettoSession(cfg)
     if a.det_tile:
         session.set_det_tiles(a.det_tile, a.det_tile_overlap)
+    if a.rec_window:
+        session.set_rec_windows(a.rec_window, a.rec_window_overlap)
     if a.rec_charset is not None:
         session.set_rec_charset(session.create_charset(a.rec_charset))
     if a.rec_lexicon is not None:

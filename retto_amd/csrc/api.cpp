@@ -507,6 +507,40 @@ int rt_rec_beam(const rt_session* s, int* beam, int* nbest) {
   if (nbest) *nbest = s->beam_n;
   return RT_OK;
 }
+int rt_set_rec_windows(rt_session* s, int window, int overlap) {
+  RT_REQUIRE(s, s, "rt_set_rec_windows: null session");
+  return guarded(s, [&] {
+    if (const char* why = rw::check_params(window, overlap)) throw RtError(RT_ERR_INVALID, std::string("rt_set_rec_windows: ") + why);
+    s->rec_window = window; s->rec_overlap = overlap;   // (the helper lanes get it with every call: CallSettings)
+  });
+}
+int rt_rec_windows(const rt_session* s, int* window, int* overlap) {
+  if (!s) return RT_ERR_INVALID;
+  if (window) *window = s->rec_window;
+  if (overlap) *overlap = s->rec_overlap;
+  return RT_OK;
+}
+int rt_rec_window_plan(int L, int window, int overlap, int32_t* origin, int32_t* width, int32_t* bound, int cap, int* n, int* T) {
+  return guarded(nullptr, [&] {
+    if (const char* why = rw::check_params(window, overlap)) throw RtError(RT_ERR_INVALID, std::string("rt_rec_window_plan: ") + why);
+    if (L < rw::STEP) throw RtError(RT_ERR_INVALID, "rt_rec_window_plan: L must be at least 8, not " + std::to_string(L));
+    // (a line that is not windowed comes out as one unit [0, L) that owns all its steps)
+    const rw::Plan p = rw::plan(L, window, overlap);
+    if (n) *n = p.n();
+    if (T) *T = p.T;
+    if ((origin || width || bound) && cap < p.n()) throw RtError(RT_ERR_INVALID, "rt_rec_window_plan: cap is smaller than the " + std::to_string(p.n()) + " units");
+    for (int i = 0; i < p.n(); i++) {
+      if (origin) origin[i] = p.origin[(size_t)i];
+      if (width) width[i] = p.width[(size_t)i];
+      if (bound) bound[i] = p.bound[(size_t)i];
+    }
+  });
+}
+int rt_results_rec_windows(const rt_results* r, int page, int line) {
+  const rt_results::Page* p = r && page >= 0 && (size_t)page < r->pages.size() ? &r->pages[(size_t)page] : nullptr;
+  if (!p || line < 0 || (size_t)line >= p->rec_units.size()) return 0;
+  return p->rec_units[(size_t)line];
+}
 int rt_det_tile_plan(int h, int w, int tile, int overlap, int32_t* row_origin, int32_t* row_bound, int row_cap, int32_t* col_origin,
                      int32_t* col_bound, int col_cap, int* n_rows, int* n_cols, int* tile_h, int* tile_w) {
   return guarded(nullptr, [&] {

@@ -1492,6 +1492,15 @@ RT_API int rt_debug_det_tiles(rt_session* s, const uint8_t* rgb_det, int h, int 
   RT_REQUIRE(s && rgb_det && page_map_out, s, "rt_debug_det_tiles: null argument");
   return guarded(s, [&] { s->debug_det_tiles(rgb_det, h, w, tile_maps_out, page_map_out); });
 }
+// n lines of [3, 48, widths[i]] as ONE rec group through the pipeline's own cut, network and stitch, under the session's rec
+// windows (rt_session::debug_rec_windows), for tests/test_gpu_rec_windows.py.
+RT_API int rt_debug_rec_windows(rt_session* s, const float* nchw, int n, const int* widths, int32_t* unit_idx_out, float* unit_prob_out,
+                                float* unit_z5_out, int32_t* line_idx_out, float* line_prob_out, float* line_z5_out) {
+  RT_REQUIRE(s && nchw && widths && n > 0, s, "rt_debug_rec_windows: bad argument");
+  return guarded(s, [&] {
+    s->debug_rec_windows(nchw, n, widths, unit_idx_out, unit_prob_out, unit_z5_out, line_idx_out, line_prob_out, line_z5_out);
+  });
+}
 // The main lane's arenas, for tools/bench_det_tiles.py: the largest pass so far of the call arena, the scratch arena (network
 // activations, rewound per launch group) and the DB post-processing workspace, in bytes.
 RT_API int rt_debug_arena_high_water(rt_session* s, long long* out3) {

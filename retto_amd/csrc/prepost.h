@@ -13,6 +13,7 @@
 #include "ctc_lexicon_align.h"
 #include "ctc_pattern.h"
 #include "det_tiles.h"
+#include "rec_windows.h"
 
 namespace rt {
 namespace pp {
@@ -169,6 +170,14 @@ void sum_partial(hipStream_t st, const float* x, long long n, double* partials);
 // DetModel::run_u8 reads.  stitch: every tile's owned rectangle from maps + map_off into its page map.
 void det_tile_cut(hipStream_t st, const dt::TileDesc* tiles, int n, long long max_tile_pix, uint8_t* cut);
 void det_tile_stitch(hipStream_t st, const dt::TileDesc* tiles, int n, long long max_tile_pix, const float* maps);
+
+// rec windows (rec_windows.h), one launch per windowed rec group each over the group's n units (units: device; max_w: the widest
+// unit's columns, max_rows: the most steps a unit owns).  cut: lines = the group's line tensors as resize_norm wrote them, unit
+// = the ragged unit tensors, both NHWC-4 of h rows.  stitch: the owned rows of the units' idx / prob / z5 (z5 [rows][120], or
+// null with line_z5 null) into the line rows.
+void rec_window_cut(hipStream_t st, const rw::UnitDesc* units, int n, int h, int max_w, const float* lines, float* unit);
+void rec_window_stitch(hipStream_t st, const rw::UnitDesc* units, int n, int max_rows, const int* unit_idx, const float* unit_prob,
+                       const float* unit_z5, int* line_idx, float* line_prob, float* line_z5);
 
 }  // namespace pp
 }  // namespace rt

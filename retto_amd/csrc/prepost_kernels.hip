@@ -1323,5 +1323,55 @@ void det_tile_stitch(hipStream_t st, const dt::TileDesc* tiles, int n, long long
   RT_LAUNCH(k_det_tile_stitch, dim3((unsigned)std::min<long long>(want, DT_MAX_BLOCKS_X), n), dim3(256), 0, st, tiles, maps);
 }
 
+// ---- rec windows (rec_windows.h): pure data movement, one launch per windowed rec group each, blockIdx.y = unit of the group --
+// Both walk a unit in 16-byte vectors with a grid-stride loop over at most RW_MAX_BLOCKS_X blocks a unit (a 48 x 640 unit is
+// 30 720 vectors to cut; a unit that owns 64 steps is 2048 lanes to stitch).  Everything is inside its buffers by the plan: a
+// unit's columns lie inside its line, its owned steps inside its own rows and inside the line's.
+#define RW_MAX_BLOCKS_X 64
+// cut: the unit's h rows of w pixels (one float4 each: NHWC-4) out of the line's rows of line_w pixels -> contiguous at unit +
+// dst_off.  Consecutive threads read and write consecutive pixels of a row.
+__global__ __launch_bounds__(256) void k_rec_window_cut(const rw::UnitDesc* __restrict__ units, int h, const float4* __restrict__ lines,
+                                                        float4* __restrict__ unit) {
+  const rw::UnitDesc d = units[blockIdx.y];
+  const long long total = (long long)h * d.w;
+  const float4* src = lines + d.src_off + d.x0;
+  float4* dst = unit + d.dst_off;
+  for (long long v = (long long)blockIdx.x * 256 + threadIdx.x; v < total; v += (long long)gridDim.x * 256) {
+    const int r = (int)(v / d.w), c = (int)(v - (long long)r * d.w);
+    dst[v] = src[(long long)r * d.line_w + c];
+  }
+}
+void rec_window_cut(hipStream_t st, const rw::UnitDesc* units, int n, int h, int max_w, const float* lines, float* unit) {
+  if (n <= 0 || h <= 0 || max_w <= 0) return;
+  const long long want = ((long long)h * max_w + 255) / 256;
+  RT_LAUNCH(k_rec_window_cut, dim3((unsigned)std::min<long long>(want, RW_MAX_BLOCKS_X), n), dim3(256), 0, st, units, h,
+            reinterpret_cast<const float4*>(lines), reinterpret_cast<float4*>(unit));
+}
+// stitch: 32 lanes a row -- lanes 0..29 the row's 30 float4 of z5 (skipped without z5), lane 30 its idx, lane 31 its prob -- from
+// the unit's row t - m into the line's row t, for the steps [t0, t1) the unit owns.  The owned steps of a line's units partition
+// its rows: every line row is written once over the launch, plain stores.
+__global__ __launch_bounds__(256) void k_rec_window_stitch(const rw::UnitDesc* __restrict__ units, const int* __restrict__ unit_idx,
+                                                           const float* __restrict__ unit_prob, const float4* __restrict__ unit_z5,
+                                                           int* __restrict__ line_idx, float* __restrict__ line_prob,
+                                                           float4* __restrict__ line_z5) {
+  const rw::UnitDesc d = units[blockIdx.y];
+  const long long total = (long long)(d.t1 - d.t0) * 32;
+  for (long long v = (long long)blockIdx.x * 256 + threadIdx.x; v < total; v += (long long)gridDim.x * 256) {
+    const int t = d.t0 + (int)(v >> 5), lane = (int)(v & 31);
+    const long long s = d.unit_row + (t - d.m), o = d.line_row + t;
+    if (lane < rw::Z5_D / 4) { if (unit_z5) line_z5[o * (rw::Z5_D / 4) + lane] = unit_z5[s * (rw::Z5_D / 4) + lane]; }
+    else if (lane == 30) line_idx[o] = unit_idx[s];
+    else line_prob[o] = unit_prob[s];
+  }
+}
+void rec_window_stitch(hipStream_t st, const rw::UnitDesc* units, int n, int max_rows, const int* unit_idx, const float* unit_prob,
+                       const float* unit_z5, int* line_idx, float* line_prob, float* line_z5) {
+  if (n <= 0 || max_rows <= 0) return;
+  static_assert(rw::Z5_D / 4 == 30, "k_rec_window_stitch gives a z5 row 30 of its 32 lanes");
+  const long long want = ((long long)max_rows * 32 + 255) / 256;
+  RT_LAUNCH(k_rec_window_stitch, dim3((unsigned)std::min<long long>(want, RW_MAX_BLOCKS_X), n), dim3(256), 0, st, units, unit_idx,
+            unit_prob, reinterpret_cast<const float4*>(unit_z5), line_idx, line_prob, reinterpret_cast<float4*>(line_z5));
+}
+
 }  // namespace pp
 }  // namespace rt

@@ -562,6 +562,7 @@ struct Pipeline {
   // hypothesis k at [(tok_off[li] * beam_n) + k * T]
   int beam_b = 0, beam_n = 0;
   Mirror<int> bmn; Mirror<bm::Beam> bmrec; Mirror<int> bmtok;
+  int rec_window = 0, rec_overlap = 0;      // rec windows (rec_windows.h) of this call; 0 = off
 };
 
 // Launch groups: items [g0, end) where the group always takes its first item; with max_items > 0 it takes up to max_items items,
@@ -915,6 +916,81 @@ wb::WordGeom word_geom(const Pipeline& P, int li) {
   memcpy(g.inv, cd.inv, sizeof g.inv);
   return g;
 }
+// ---- the rec network over ONE rec group: whole lines, or windows (rec_windows.h) --------
+// x = the group's line tensors as resize_norm wrote them (NHWC-4, rh rows, W[k] columns, concatenated).  idx / prob receive the
+// lines' rows, *z5 (when asked for) their head-input rows, Lt their token level on the device: exactly what RecModel::run leaves.
+// A group without a windowed line IS RecModel::run on the lines, what it was before windows existed: the same launches, the same
+// bits, nothing allocated.  With one, every line becomes its units (a whole line: one unit that owns all its rows):
+// k_rec_window_cut copies the units' column ranges into ragged unit tensors, the network runs once over the units as its
+// "lines" with idx / prob / z5 in scratch, and k_rec_window_stitch gathers the owned rows into the line rows.
+// taps (rt_debug_rec_windows): host arrays that receive every unit's rows in unit order, each optional.
+struct RecWindowTaps { int32_t* unit_idx = nullptr; float* unit_prob = nullptr; float* unit_z5 = nullptr; };
+void rec_group_net(rt_session& s, const float* x, int rh, const int* W, int ln, int window, int overlap, int* idx, float* prob,
+                   const float** z5, Level& Lt, const RecWindowTaps* taps = nullptr) {
+  static_assert(rw::Z5_D == 120, "a z5 row is SvtrCore::D floats");
+  RunCtx c = s.ctx(&s.scratch);
+  const auto tap = [&](const int* d_idx, const float* d_prob, const float* d_z5, long long rows) {
+    if (!taps || rows <= 0) return;
+    if (taps->unit_idx) RT_HIP_CHECK(hipMemcpyAsync(taps->unit_idx, d_idx, (size_t)rows * 4, hipMemcpyDeviceToHost, s.st));
+    if (taps->unit_prob) RT_HIP_CHECK(hipMemcpyAsync(taps->unit_prob, d_prob, (size_t)rows * 4, hipMemcpyDeviceToHost, s.st));
+    if (taps->unit_z5 && d_z5) RT_HIP_CHECK(hipMemcpyAsync(taps->unit_z5, d_z5, (size_t)rows * rw::Z5_D * 4, hipMemcpyDeviceToHost, s.st));
+  };
+  std::vector<std::pair<int, int>> hw;
+  bool windowed = false;
+  for (int k = 0; k < ln; k++) { hw.push_back({rh, W[k]}); windowed = windowed || rw::line_windowed(W[k], window); }
+  if (!windowed) {
+    Level L0 = make_level(hw);
+    { ProfOuter po(&s.prof, s.st, "net/rec");
+      s.rec->run(c, x, L0, Lt, idx, prob, z5); }  // fused CTC head: logits never reach HBM
+    tap(idx, prob, z5 ? *z5 : nullptr, Lt.total);
+    return;
+  }
+  int nu = 0;
+  for (int k = 0; k < ln; k++) nu += rw::units(W[k], window, overlap);
+  // the units' descriptors through pinned into scratch, as the det tiles' go
+  rw::UnitDesc* hu = s.pinned.alloc<rw::UnitDesc>((size_t)nu);
+  rw::UnitDesc* du = s.scratch.alloc<rw::UnitDesc>((size_t)nu);
+  std::vector<std::pair<int, int>> uhw, thw;
+  long long line_px = 0, unit_px = 0, line_rows = 0, unit_rows = 0;
+  int max_w = 0, max_own = 0, u = 0;
+  for (int k = 0; k < ln; k++) {
+    const rw::Plan p = rw::plan(W[k], window, overlap);
+    if (p.T != RecNet::tokens_for_width(W[k])) throw RtError(RT_ERR_BACKEND, "rec windows: rw::tokens and RecNet::tokens_for_width disagree");
+    for (int i = 0; i < p.n(); i++) {
+      rw::UnitDesc& d = hu[u++];
+      d.src_off = line_px; d.dst_off = unit_px; d.unit_row = unit_rows; d.line_row = line_rows;
+      d.line_w = W[k]; d.x0 = p.origin[(size_t)i]; d.w = p.width[(size_t)i];
+      d.m = d.x0 / rw::STEP; d.t0 = p.own0(i); d.t1 = p.bound[(size_t)i];
+      const int Tu = RecNet::tokens_for_width(d.w);
+      // (what the kernels rely on: the unit's columns inside its line, its owned steps inside its own rows and the line's)
+      if (d.x0 < 0 || d.w < rw::STEP || d.x0 + d.w > W[k] || d.t0 < d.m || d.t1 < d.t0 || d.t1 - d.m > Tu || d.t1 > p.T)
+        throw RtError(RT_ERR_BACKEND, "rec windows: a unit lies outside its line");
+      uhw.push_back({rh, d.w});
+      unit_px += (long long)rh * d.w; unit_rows += Tu;
+      max_w = std::max(max_w, d.w); max_own = std::max(max_own, d.t1 - d.t0);
+    }
+    thw.push_back({1, p.T});
+    line_px += (long long)rh * W[k]; line_rows += p.T;
+  }
+  RT_HIP_CHECK(hipMemcpyAsync(du, hu, (size_t)nu * sizeof(rw::UnitDesc), hipMemcpyHostToDevice, s.st));
+  float* xu = s.scratch.alloc<float>((size_t)unit_px * 4);
+  { ProfScope ps(&s.prof, s.st, "rec_window_cut");
+    pp::rec_window_cut(s.st, du, nu, rh, max_w, x, xu); }
+  int* u_idx = s.scratch.alloc<int>((size_t)unit_rows); float* u_prob = s.scratch.alloc<float>((size_t)unit_rows);
+  float* l_z5 = z5 ? s.scratch.alloc<float>((size_t)line_rows * rw::Z5_D) : nullptr;
+  const float* u_z5 = nullptr;
+  Level Lu0 = make_level(uhw), Ltu;
+  { ProfOuter po(&s.prof, s.st, "net/rec");
+    s.rec->run(c, xu, Lu0, Ltu, u_idx, u_prob, z5 ? &u_z5 : nullptr); }
+  if (Ltu.total != unit_rows) throw RtError(RT_ERR_SHAPE, "token count mismatch");
+  { ProfScope ps(&s.prof, s.st, "rec_window_stitch");
+    pp::rec_window_stitch(s.st, du, nu, max_own, u_idx, u_prob, u_z5, idx, prob, l_z5); }
+  if (z5) *z5 = l_z5;
+  // the LINES' token level, as RecModel::run would have left it: {first row, 1, T} per line
+  Lt = make_level(thw);
+  upload_levels(c, {&Lt});
+  tap(u_idx, u_prob, u_z5, unit_rows);
+}
 // ---- a11 + a12: rec network + CTC decode in launch groups (+ word boxes) --------------
 void rec_groups(rt_session& s, Pipeline& P) {
   const int rh = s.cfg.rec_image_shape[1];
@@ -941,25 +1017,24 @@ void rec_groups(rt_session& s, Pipeline& P) {
   if (P.beam_b > 0) { P.bmn.alloc(s, P.NLp); P.bmrec.alloc(s, (size_t)P.NLp * P.beam_n); P.bmtok.alloc(s, ntok * (size_t)P.beam_n); }
   static const long long REC_GROUP_PX = getenv("RT_REC_GROUP_PX") ? atoll(getenv("RT_REC_GROUP_PX")) : (long long)24000000;  // measured sweet spot (profiles/README.md)
   for (int l0 = 0; l0 < P.NL;) {
-    const int l1 = group_end(l0, P.NL, 0, REC_GROUP_PX, [&](int l) { return (long long)rh * P.line_W[l]; });
+    // (a windowed line is charged with its units' pixels, rec_windows.h: what the network is run on)
+    const int l1 = group_end(l0, P.NL, 0, REC_GROUP_PX, [&](int l) { return (long long)rh * rw::unit_columns(P.line_W[l], P.rec_window, P.rec_overlap); });
     const int ln = l1 - l0;
     s.scratch.rewind();
-    std::vector<std::pair<int, int>> hw;
     pp::LineDesc* hl = s.pinned.alloc<pp::LineDesc>(ln);
     long long off = 0; int maxW = 0;
     for (int k = 0; k < ln; k++) {
       hl[k] = P.lines[l0 + k];
       hl[k].out_off = off * 4;
       off += (long long)rh * P.line_W[l0 + k];
-      hw.push_back({rh, P.line_W[l0 + k]}); maxW = std::max(maxW, P.line_W[l0 + k]);
+      maxW = std::max(maxW, P.line_W[l0 + k]);
     }
     pp::LineDesc* dl = s.scratch.alloc<pp::LineDesc>(ln);
     RT_HIP_CHECK(hipMemcpyAsync(dl, hl, (size_t)ln * sizeof(pp::LineDesc), hipMemcpyHostToDevice, s.st));
     float* x = s.scratch.alloc<float>((size_t)off * 4);
     { ProfScope ps(&s.prof, s.st, "resize_norm");
       pp::resize_norm(s.st, dl, ln, rh, maxW, P.pool, 0, x, s.d_flags); }
-    Level L0 = make_level(hw), Lt;
-    RunCtx c = s.ctx(&s.scratch);
+    Level Lt;
     // (the token count per line only depends on the widths, so the offsets are known before the net runs)
     const long long t0 = P.tok_off[l0];
     const rt_lexicons& X = *s.lexicons;
@@ -969,8 +1044,7 @@ void rec_groups(rt_session& s, Pipeline& P) {
     const std::string refused = tail.refusal(P.beam_b);
     if (!refused.empty()) throw RtError(RT_ERR_CAPACITY, refused);
     const float* z5 = nullptr;   // the head's input, for the candidates', the charsets', the lexicons', the keywords' and the beams' logits
-    { ProfOuter po(&s.prof, s.st, "net/rec");
-      s.rec->run(c, x, L0, Lt, d_idx + t0, d_prob + t0, tail.needs_z5(cand_k) ? &z5 : nullptr); }  // fused CTC head: logits never reach HBM
+    rec_group_net(s, x, rh, P.line_W.data() + l0, ln, P.rec_window, P.rec_overlap, d_idx + t0, d_prob + t0, tail.needs_z5(cand_k) ? &z5 : nullptr, Lt);
     if (Lt.total != tail.rows) throw RtError(RT_ERR_SHAPE, "token count mismatch");
     rt_session::WordBoxes words{};
     if (s.cfg.rec_return_word_box) {
@@ -1035,6 +1109,8 @@ void results(const rt_session& s, const Pipeline& P, rt_results& res) {
     int nb = p.n_boxes;
     page_boxes(p, R, P.regions != nullptr);
     R.cls_labels.resize(nb); R.cls_scores.resize(nb); R.rec_scores.resize(nb); R.tokens.resize(nb); R.text.resize(nb);
+    R.rec_units.resize(nb);
+    for (int k = 0; k < nb; k++) R.rec_units[k] = rw::units(P.line_W[p.first_line + k], P.rec_window, P.rec_overlap);
     for (int k = 0; k < nb; k++) {
       int li = p.first_line + k;
       R.cls_labels[k] = LABELS[m.label[li] ? 1 : 0]; R.cls_scores[k] = m.cscore[li]; R.rec_scores[k] = m.rscore[li];
@@ -1160,6 +1236,7 @@ rt_results* rt_session::run_pages(const uint8_t* const* rgb, const int* hs, cons
   P.regions = regions; P.crop_original = regions != nullptr || cfg.crop_source == 1;
   P.det_tile = set.det_tile; P.det_overlap = set.det_overlap;
   P.beam_b = set.beam_b; P.beam_n = set.beam_n;
+  P.rec_window = set.rec_window; P.rec_overlap = set.rec_overlap;
   HostTick tick;
   if (regions) {   // the boxes are given: no resize_both, no detector, no DB post-processing, no first round trip
     region_pages(*this, P, rgb, hs, ws); tick.lap("pre (upload, regions)");
@@ -1206,6 +1283,38 @@ void rt_session::debug_det_tiles(const uint8_t* rgb_det, int h, int w, float* ti
   RT_HIP_CHECK(hipMemcpyAsync(page_map_out, p.map, (size_t)h * w * 4, hipMemcpyDeviceToHost, st));
   if (tile_maps_out && !dt::page_tiled(h, w, det_tile))
     RT_HIP_CHECK(hipMemcpyAsync(tile_maps_out, p.map, (size_t)h * w * 4, hipMemcpyDeviceToHost, st));
+  sync();
+}
+
+// rt_debug_rec_windows: the lines as ONE rec group through rec_group_net, the function rec_groups runs per group, under the
+// session's rec windows.  Without a windowed line the units are the lines.
+void rt_session::debug_rec_windows(const float* nchw, int n, const int* widths, int32_t* unit_idx_out, float* unit_prob_out,
+                                   float* unit_z5_out, int32_t* line_idx_out, float* line_prob_out, float* line_z5_out) {
+  const int h = 48;
+  size_t ne = 0, nt = 0;
+  for (int i = 0; i < n; i++) {
+    if (widths[i] < 8) throw RtError(RT_ERR_SHAPE, "rt_debug_rec_windows: every line must be at least 8 wide");
+    ne += (size_t)3 * h * widths[i];
+    nt += (size_t)RecNet::tokens_for_width(widths[i]);
+  }
+  begin_call();
+  float* d_in = arena.alloc<float>(ne);
+  RT_HIP_CHECK(hipMemcpyAsync(d_in, nchw, ne * 4, hipMemcpyHostToDevice, st));
+  float* x = arena.alloc<float>(ne / 3 * 4);
+  size_t off = 0;
+  for (int i = 0; i < n; i++) {
+    nn::nchw3_to_nhwc4(st, d_in + off * 3, 1, h, widths[i], x + off * 4);
+    off += (size_t)h * widths[i];
+  }
+  int* d_idx = arena.alloc<int>(nt); float* d_prob = arena.alloc<float>(nt);
+  const float* z5 = nullptr;
+  Level Lt;
+  const RecWindowTaps taps{unit_idx_out, unit_prob_out, unit_z5_out};
+  rec_group_net(*this, x, h, widths, n, rec_window, rec_overlap, d_idx, d_prob, &z5, Lt, &taps);
+  if ((size_t)Lt.total != nt) throw RtError(RT_ERR_BACKEND, "rt_debug_rec_windows: token count mismatch");
+  if (line_idx_out) RT_HIP_CHECK(hipMemcpyAsync(line_idx_out, d_idx, nt * 4, hipMemcpyDeviceToHost, st));
+  if (line_prob_out) RT_HIP_CHECK(hipMemcpyAsync(line_prob_out, d_prob, nt * 4, hipMemcpyDeviceToHost, st));
+  if (line_z5_out) RT_HIP_CHECK(hipMemcpyAsync(line_z5_out, z5, nt * rw::Z5_D * 4, hipMemcpyDeviceToHost, st));
   sync();
 }
 

@@ -61,6 +61,8 @@ struct rt_results {
     std::vector<rt::bm::Beam> bm_recs;
     std::vector<std::vector<int32_t>> bm_tokens;
     std::vector<std::string> bm_text;
+    // rec windows (rec_windows.h; rt_set_rec_windows): per line the number of units it was read in, 1 for a whole line
+    std::vector<int32_t> rec_units;
     std::string json[3];
   };
   std::vector<Page> pages;
@@ -84,8 +86,8 @@ struct LaneWorker {
 
 // What a pipeline call reads of the session's settings, as they were when the call was submitted: the default options of every
 // line (rt_set_rec_charset / _lexicon / _pattern / _keywords, rec_line_opts.h), the det tiles (rt_set_det_tiles, det_tiles.h; 0 = off)
-// and the rec beam (rt_set_rec_beam, ctc_beam.h; beam_b = 0: off)
-struct CallSettings { rt::RecLineOpts rec; int det_tile = 0, det_overlap = 0, beam_b = 0, beam_n = 0; };
+// the rec beam (rt_set_rec_beam, ctc_beam.h; beam_b = 0: off) and the rec windows (rt_set_rec_windows, rec_windows.h; 0 = off)
+struct CallSettings { rt::RecLineOpts rec; int det_tile = 0, det_overlap = 0, beam_b = 0, beam_n = 0, rec_window = 0, rec_overlap = 0; };
 
 // One submitted batch (rt_submit_batch): the argument arrays are copied (the PAGES must stay valid until rt_wait_batch), the
 // pages are split over the lanes exactly as rt_run_batch splits them, each lane leaves its part here.
@@ -245,8 +247,12 @@ struct rt_session {
   // rt_set_rec_beam (ctc_beam.h): every line of the pipeline calls that follow also reports its beam_n most probable strings from
   // a prefix beam search of width beam_b; 0 = off
   int beam_b = 0, beam_n = 0;
-  // A helper lane never reads its own rec_default / det_tile / det_overlap / beam_b / beam_n: a call carries the main lane's into run_pages
-  CallSettings settings() const { return {rec_default, det_tile, det_overlap, beam_b, beam_n}; }
+  // rt_set_rec_windows (rec_windows.h): lines at least 8 columns wider than rec_window are read as overlapping windows whose
+  // trusted time steps are stitched into the line's rows; 0 = off
+  int rec_window = 0, rec_overlap = 0;
+  // A helper lane never reads its own rec_default / det_tile / det_overlap / beam_b / beam_n / rec_window / rec_overlap: a call
+  // carries the main lane's into run_pages
+  CallSettings settings() const { return {rec_default, det_tile, det_overlap, beam_b, beam_n, rec_window, rec_overlap}; }
   uint8_t* d_word_raw = nullptr;  // rec_return_word_box: wb::raw_class of every dictionary entry (device; owned by the main lane)
   std::string last_error;
   int* d_flags = nullptr;         // [0] thumbnail/resize error flag
@@ -389,6 +395,11 @@ struct rt_session {
   // rt_debug_det_tiles: the det stage of a one-page call on a host RGB8 image at det-input size h x w, through the pipeline's own
   // det_groups under the session's det tiles; tile_maps_out: every tile's own map packed in plan order, page_map_out [h * w]
   void debug_det_tiles(const uint8_t* rgb_det, int h, int w, float* tile_maps_out, float* page_map_out);
+  // rt_debug_rec_windows: n lines of [3, 48, widths[i]] (host, NCHW, concatenated) as ONE rec group through the pipeline's own
+  // cut, network and stitch (rec_group_net) under the session's rec windows.  Every output is optional and on the host: the
+  // units' rows in unit order, line after line (idx / prob [unit rows], z5 [unit rows][120]), and the lines' stitched rows
+  void debug_rec_windows(const float* nchw, int n, const int* widths, int32_t* unit_idx_out, float* unit_prob_out, float* unit_z5_out,
+                         int32_t* line_idx_out, float* line_prob_out, float* line_z5_out);
   // rt_run_regions: checks and clamps every quad (RT_ERR_INVALID naming page and region; nothing is queued then), then the
   // pages go over the lanes as run_batch's do, from the crop plan on
   // charsets, lexicons, patterns, keywords (each or null; entries may be null): per region -1 = the session default, 0 = none, >= 1 = that
