@@ -1,7 +1,10 @@
 // extern "C" surface of libretto_hip.so (include/retto_hip.h): sessions, the networks, the pipeline stages, batches, results,
-// parsers and device memory, with the feature-level debug hooks that are thin forwards into their features (rt_debug_warp_crops,
-// rt_debug_jpeg_reconstruct, rt_debug_word_boxes, rt_debug_ctc_candidates_host, rt_debug_charset_compile, rt_debug_ctc_charset_host, rt_debug_lexicon_compile, rt_debug_ctc_lexicon_host, rt_debug_ctc_lexicon_align_host, rt_debug_ctc_keywords_host, rt_debug_span_quad, rt_debug_ctc_beam_host).  The kernel-level diagnostics (rt_debug_set_variants,
-// rt_bench_*, and the rt_debug_* harnesses the kernel tests drive) are in api_debug.cpp; api_internal.h holds what both share.
+// parsers and device memory, with the four feature-level debug hooks that are thin forwards into their features
+// (rt_debug_warp_crops, rt_debug_jpeg_reconstruct, rt_debug_word_boxes, rt_debug_span_quad).  The debug entries of the rec CTC
+// tail's options (rt_debug_ctc_*, both forms, and rt_debug_*_compile) are in api_ctc.cpp, on the host references of
+// ctc_host_ref.h; it also asserts the layouts the rt_results_rec_* accessors here cast between.  The kernel-level diagnostics
+// (rt_debug_set_variants, rt_bench_*, and the rt_debug_* harnesses the kernel tests drive) are in api_debug.cpp; api_internal.h
+// holds what the three share.
 #include <thread>
 #include <sched.h>
 #include <atomic>
@@ -22,171 +25,12 @@ std::string& rt::create_error() {
   return e;
 }
 const char* rt_results_json_impl(rt_results* r, int page, int stage);
-bool rt::cand_args_ok(const float* z5, const float* W, int N, const int32_t* idx, const float* prob, const int32_t* tokens_per_line,
-                      int n_lines, int K, const rt_candidate* cands_out, const int32_t* cols_out, const int32_t* n_tokens_out,
-                      long long* rows_out) {
-  if (!idx || !prob || !tokens_per_line || !cands_out || !cols_out || !n_tokens_out) return false;
-  if (n_lines <= 0 || K < 1 || K > RT_MAX_CANDIDATES || N <= 0 || (K > 1 && (!z5 || !W))) return false;
-  long long rows = 0;
-  for (int i = 0; i < n_lines; i++) {
-    if (tokens_per_line[i] < 0) return false;
-    rows += tokens_per_line[i];
-  }
-  if (rows >= (1ll << 30)) return false;
-  for (long long r = 0; r < rows; r++)
-    if (idx[r] < 0 || idx[r] >= N) return false;
-  *rows_out = rows;
-  return true;
-}
-bool rt::charset_args_ok(const float* z5, const float* W, int N, const int32_t* idx, const float* prob, const int32_t* tokens_per_line,
-                         int n_lines, const int32_t* line_set, const uint32_t* masks, int n_sets, int K, const int32_t* tokens_out,
-                         const int32_t* n_tokens_out, const float* scores_out, const rt_candidate* cands_out, const int32_t* cols_out,
-                         long long* rows_out) {
-  if (!z5 || !W || !idx || !prob || !tokens_per_line || !line_set || !tokens_out || !n_tokens_out || !scores_out) return false;
-  if (n_lines <= 0 || N <= 0 || K < 0 || K > RT_MAX_CANDIDATES || n_sets < 0 || n_sets > RT_MAX_CHARSETS || (n_sets > 0 && !masks)) return false;
-  if (K > 0 && (!cands_out || !cols_out)) return false;
-  long long rows = 0;
-  for (int i = 0; i < n_lines; i++) {
-    if (tokens_per_line[i] < 0 || line_set[i] < 0 || line_set[i] > n_sets) return false;
-    rows += tokens_per_line[i];
-  }
-  if (rows >= (1ll << 30)) return false;
-  for (long long r = 0; r < rows; r++)
-    if (idx[r] < 0 || idx[r] >= N) return false;
-  *rows_out = rows;
-  return true;
-}
-std::string rt::lexicon_args_error(const float* z5, const float* W, int N, const int32_t* tokens_per_line, int n_lines,
-                                   const int32_t* line_lex, const int32_t* entry_ids, const int32_t* entry_lens,
-                                   const int32_t* lex_first_entry, int n_lex, const rt_lexicon_match* matches_out,
-                                   const int32_t* n_matches_out, long long* rows_out, long long* table_out) {
-  auto S = [](long long v) { return std::to_string(v); };
-  if (!z5 || !W || !tokens_per_line || !line_lex || !entry_ids || !entry_lens || !lex_first_entry || !matches_out || !n_matches_out)
-    return "a required pointer is null";
-  if (n_lines <= 0) return "n_lines must be positive";
-  if (N <= 1) return "N must be at least 2 (the blank and one class)";
-  if (n_lex < 1 || n_lex > RT_MAX_LEXICONS) return "n_lex = " + S(n_lex) + " is outside [1, RT_MAX_LEXICONS]";
-  if (lex_first_entry[0] != 0) return "lex_first_entry[0] must be 0";
-  for (int k = 0; k < n_lex; k++) {
-    const long long n = (long long)lex_first_entry[k + 1] - lex_first_entry[k];
-    if (n < 1 || n > RT_LEXICON_MAX_ENTRIES) return "lexicon " + S(k + 1) + " has " + S(n) + " entries, outside [1, RT_LEXICON_MAX_ENTRIES]";
-  }
-  long long o = 0;
-  for (int j = 0; j < lex_first_entry[n_lex]; j++) {
-    if (entry_lens[j] < 1 || entry_lens[j] > RT_LEXICON_MAX_LEN)
-      return "entry " + S(j) + " has " + S(entry_lens[j]) + " ids, outside [1, RT_LEXICON_MAX_LEN]";
-    for (int i = 0; i < entry_lens[j]; i++)
-      if (entry_ids[o + i] < 1 || entry_ids[o + i] >= N)
-        return "class id " + S(entry_ids[o + i]) + " in entry " + S(j) + " is outside [1, " + S(N) + ")";
-    o += entry_lens[j];
-  }
-  long long rows = 0, table = 0;
-  for (int i = 0; i < n_lines; i++) {
-    if (tokens_per_line[i] < 0) return "line " + S(i) + " has a negative number of time steps";
-    if (line_lex[i] < 0 || line_lex[i] > n_lex) return "line " + S(i) + " names lexicon " + S(line_lex[i]) + ", outside [0, " + S(n_lex) + "]";
-    rows += tokens_per_line[i];
-    if (line_lex[i] > 0) table += lex_first_entry[line_lex[i]] - lex_first_entry[line_lex[i] - 1];
-  }
-  if (rows >= (1ll << 30)) return "the lines have " + S(rows) + " time steps, 2^30 or more";
-  if (table >= (1ll << 30)) return "the loglik table has " + S(table) + " floats, 2^30 or more";
-  *rows_out = rows; *table_out = table;
-  return std::string();
-}
-std::string rt::keywords_args_error(const float* z5, const float* W, int N, const int32_t* tokens_per_line, int n_lines,
-                                    const int32_t* line_kw, const int32_t* entry_ids, const int32_t* entry_lens,
-                                    const int32_t* kw_first_entry, int n_kw, const float* kw_min_score, const rt_keyword_hit* hits_out,
-                                    const int32_t* n_hits_out, long long* rows_out, long long* table_out) {
-  auto S = [](long long v) { return std::to_string(v); };
-  if (!z5 || !W || !tokens_per_line || !line_kw || !entry_ids || !entry_lens || !kw_first_entry || !kw_min_score || !hits_out || !n_hits_out)
-    return "a required pointer is null";
-  if (n_lines <= 0) return "n_lines must be positive";
-  if (N <= 1) return "N must be at least 2 (the blank and one class)";
-  if (n_kw < 1 || n_kw > RT_MAX_KEYWORD_LISTS) return "n_kw = " + S(n_kw) + " is outside [1, RT_MAX_KEYWORD_LISTS]";
-  if (kw_first_entry[0] != 0) return "kw_first_entry[0] must be 0";
-  for (int k = 0; k < n_kw; k++) {
-    const long long n = (long long)kw_first_entry[k + 1] - kw_first_entry[k];
-    if (n < 1 || n > RT_LEXICON_MAX_ENTRIES) return "list " + S(k + 1) + " has " + S(n) + " entries, outside [1, RT_LEXICON_MAX_ENTRIES]";
-    if (!(kw_min_score[k] <= 0.0f)) return "kw_min_score[" + S(k) + "] = " + std::to_string(kw_min_score[k]) + " is not a number at most 0";
-  }
-  long long o = 0;
-  for (int j = 0; j < kw_first_entry[n_kw]; j++) {
-    if (entry_lens[j] < 1 || entry_lens[j] > RT_LEXICON_MAX_LEN)
-      return "entry " + S(j) + " has " + S(entry_lens[j]) + " ids, outside [1, RT_LEXICON_MAX_LEN]";
-    for (int i = 0; i < entry_lens[j]; i++)
-      if (entry_ids[o + i] < 1 || entry_ids[o + i] >= N)
-        return "class id " + S(entry_ids[o + i]) + " in entry " + S(j) + " is outside [1, " + S(N) + ")";
-    o += entry_lens[j];
-  }
-  long long rows = 0, table = 0;
-  for (int i = 0; i < n_lines; i++) {
-    if (tokens_per_line[i] < 0) return "line " + S(i) + " has a negative number of time steps";
-    if (line_kw[i] < 0 || line_kw[i] > n_kw) return "line " + S(i) + " names list " + S(line_kw[i]) + ", outside [0, " + S(n_kw) + "]";
-    rows += tokens_per_line[i];
-    if (line_kw[i] > 0) table += kw_first_entry[line_kw[i]] - kw_first_entry[line_kw[i] - 1];
-  }
-  if (rows >= (1ll << 30)) return "the lines have " + S(rows) + " time steps, 2^30 or more";
-  if (table > lx::MAX_GROUP_TABLE) return "the score table has " + S(table) + " entries, more than a group's table holds";
-  *rows_out = rows; *table_out = table;
-  return std::string();
-}
-std::string rt::beam_args_error(const float* z5, const float* W, int N, const int32_t* tokens_per_line, int n_lines, int beam, int nbest,
-                                const int32_t* counts_out, const rt_beam* beams_out, const int32_t* tokens_out, long long* rows_out) {
-  auto S = [](long long v) { return std::to_string(v); };
-  if (!z5 || !W || !tokens_per_line || !counts_out || !beams_out || !tokens_out) return "a required pointer is null";
-  if (n_lines < 0) return "n_lines is negative";
-  if (N <= 1) return "N must be at least 2 (the blank and one class)";
-  if (beam < 0 || beam > RT_MAX_BEAM) return "beam = " + S(beam) + " is outside [0, RT_MAX_BEAM]";
-  if (beam > 0 && (nbest < 1 || nbest > std::min(beam, RT_MAX_NBEST)))
-    return "nbest = " + S(nbest) + " is outside [1, min(beam, RT_MAX_NBEST)]";
-  long long rows = 0;
-  for (int i = 0; i < n_lines; i++) {
-    if (tokens_per_line[i] < 0) return "line " + S(i) + " has a negative number of time steps";
-    rows += tokens_per_line[i];
-  }
-  if (rows >= (1ll << 30)) return "the lines have " + S(rows) + " time steps, 2^30 or more";
-  if (beam > 0 && n_lines + rows * beam > bm::MAX_GROUP_NODES)
-    return "the lines need " + S(n_lines + rows * beam) + " trie nodes, more than a group's trie holds";
-  *rows_out = rows;
-  return std::string();
-}
-std::string rt::lexicon_align_args_error(const float* lex_min_post, int n_lex, const int32_t* idx, const float* prob,
-                                         const int32_t* snapped_out, const float* vit_out) {
-  if (!lex_min_post || !idx || !prob || !snapped_out || !vit_out) return "a required pointer is null";
-  for (int k = 0; k < n_lex; k++)
-    if (!(lex_min_post[k] >= 0.0f && lex_min_post[k] <= 1.0f))
-      return "lex_min_post[" + std::to_string(k) + "] = " + std::to_string(lex_min_post[k]) + " is outside [0, 1]";
-  return std::string();
-}
-std::string rt::pattern_args_error(const float* z5, const float* W, int N, const int32_t* tokens_per_line, int n_lines,
-                                   const int32_t* line_pat, const int32_t* pat_S, const int32_t* pat_G, const int32_t* group_of,
-                                   const int32_t* delta, const int32_t* accept, int n_pat, const int32_t* idx, const float* prob,
-                                   const int32_t* matched_out, const float* vit_out, const float* logprob_out, const float* free_out,
-                                   long long* rows_out, std::vector<pt::Rule>* rules_out) {
-  auto S = [](long long v) { return std::to_string(v); };
-  if (!z5 || !W || !tokens_per_line || !line_pat || !pat_S || !pat_G || !group_of || !delta || !accept || !idx || !prob ||
-      !matched_out || !vit_out || !logprob_out || !free_out)
-    return "a required pointer is null";
-  if (n_lines <= 0) return "n_lines must be positive";
-  if (N <= 1 || N > 65535) return "N must be in [2, 65535]";
-  if (n_pat < 1 || n_pat > RT_MAX_PATTERNS) return "n_pat = " + S(n_pat) + " is outside [1, RT_MAX_PATTERNS]";
-  rules_out->assign((size_t)n_pat, pt::Rule());
-  size_t od = 0, oa = 0;
-  for (int k = 0; k < n_pat; k++) {
-    if (pat_S[k] < 1 || pat_S[k] > RT_PATTERN_MAX_STATES) return "pattern " + S(k + 1) + ": S = " + S(pat_S[k]) + " is outside [1, RT_PATTERN_MAX_STATES]";
-    if (pat_G[k] < 1 || pat_G[k] > N) return "pattern " + S(k + 1) + ": G = " + S(pat_G[k]) + " is outside [1, N]";
-    const std::string bad = (*rules_out)[(size_t)k].build(N, pat_S[k], pat_G[k], group_of + (size_t)k * N, delta + od, accept + oa);
-    if (!bad.empty()) return "pattern " + S(k + 1) + ": " + bad;
-    od += (size_t)pat_S[k] * pat_G[k]; oa += (size_t)pat_S[k];
-  }
-  long long rows = 0;
-  for (int i = 0; i < n_lines; i++) {
-    if (tokens_per_line[i] < 0) return "line " + S(i) + " has a negative number of time steps";
-    if (line_pat[i] < 0 || line_pat[i] > n_pat) return "line " + S(i) + " names pattern " + S(line_pat[i]) + ", outside [0, " + S(n_pat) + "]";
-    rows += tokens_per_line[i];
-  }
-  if (rows >= (1ll << 30)) return "the lines have " + S(rows) + " time steps, 2^30 or more";
-  *rows_out = rows;
-  return std::string();
+#define RT_PAGE(r, page) ((r) && (page) >= 0 && (size_t)(page) < (r)->pages.size() ? &(r)->pages[(size_t)(page)] : nullptr)
+// the page of a per-line result of the rec options, where `line` is one of the lines `per_line` holds an element for (else null)
+template <class V>
+static const rt_results::Page* page_of_line(const rt_results* r, int page, int line, V rt_results::Page::*per_line) {
+  const rt_results::Page* p = RT_PAGE(r, page);
+  return p && line >= 0 && (size_t)line < (p->*per_line).size() ? p : nullptr;
 }
 
 extern "C" {
@@ -469,8 +313,8 @@ const char* rt_pattern_text(const rt_session* s, int pattern) {
   return h ? h->text.c_str() : nullptr;
 }
 int rt_results_rec_pattern(const rt_results* r, int page, int line, rt_pattern_result* out) {
-  const rt_results::Page* p = r && page >= 0 && (size_t)page < r->pages.size() ? &r->pages[(size_t)page] : nullptr;
-  if (!p || line < 0 || (size_t)line >= p->pat_id.size() || p->pat_id[(size_t)line] <= 0) return 0;
+  auto* p = page_of_line(r, page, line, &rt_results::Page::pat_id);
+  if (!p || p->pat_id[(size_t)line] <= 0) return 0;
   const pt::LineResult& v = p->pat_res[(size_t)line];
   if (out) *out = rt_pattern_result{p->pat_id[(size_t)line], v.matched, v.logprob, v.free_logprob};
   return 1;
@@ -489,9 +333,6 @@ int rt_det_tiles(const rt_session* s, int* tile, int* overlap) {
   if (overlap) *overlap = s->det_overlap;
   return RT_OK;
 }
-static_assert(RT_MAX_BEAM == bm::MAX_BEAM && RT_MAX_NBEST == bm::MAX_NBEST, "the RT_MAX_BEAM / RT_MAX_NBEST limits and bm:: must agree");
-static_assert(sizeof(rt_beam) == sizeof(bm::Beam) && offsetof(rt_beam, logprob) == offsetof(bm::Beam, logprob) &&
-                  offsetof(rt_beam, n_tokens) == offsetof(bm::Beam, n_tokens), "rt_beam and bm::Beam must share one layout");
 int rt_set_rec_beam(rt_session* s, int beam, int nbest) {
   RT_REQUIRE(s, s, "rt_set_rec_beam: null session");
   return guarded(s, [&] {
@@ -537,9 +378,8 @@ int rt_rec_window_plan(int L, int window, int overlap, int32_t* origin, int32_t*
   });
 }
 int rt_results_rec_windows(const rt_results* r, int page, int line) {
-  const rt_results::Page* p = r && page >= 0 && (size_t)page < r->pages.size() ? &r->pages[(size_t)page] : nullptr;
-  if (!p || line < 0 || (size_t)line >= p->rec_units.size()) return 0;
-  return p->rec_units[(size_t)line];
+  auto* p = page_of_line(r, page, line, &rt_results::Page::rec_units);
+  return p ? p->rec_units[(size_t)line] : 0;
 }
 int rt_det_tile_plan(int h, int w, int tile, int overlap, int32_t* row_origin, int32_t* row_bound, int row_cap, int32_t* col_origin,
                      int32_t* col_bound, int col_cap, int* n_rows, int* n_cols, int* tile_h, int* tile_w) {
@@ -760,7 +600,6 @@ int rt_debug_jpeg_reconstruct(const void* data, size_t len, uint8_t** rgb, int* 
 }
 void rt_results_free(rt_results* r) { delete r; }
 int rt_results_pages(const rt_results* r) { return r ? (int)r->pages.size() : 0; }
-#define RT_PAGE(r, page) ((r) && (page) >= 0 && (size_t)(page) < (r)->pages.size() ? &(r)->pages[(size_t)(page)] : nullptr)
 int rt_results_count(const rt_results* r, int page) { auto* p = RT_PAGE(r, page); return p ? (int)p->det_scores.size() : 0; }
 const float* rt_results_boxes(const rt_results* r, int page) { auto* p = RT_PAGE(r, page); return p ? p->boxes.data() : nullptr; }
 const float* rt_results_det_scores(const rt_results* r, int page) { auto* p = RT_PAGE(r, page); return p ? p->det_scores.data() : nullptr; }
@@ -827,8 +666,6 @@ int rt_debug_word_boxes(const void* dict, size_t dict_len, const int32_t* tokens
     return RT_ERR_BACKEND;
   }
 }
-static_assert(sizeof(rt_candidate) == sizeof(cc::Cand) && offsetof(rt_candidate, prob) == offsetof(cc::Cand, prob) &&
-                  RT_MAX_CANDIDATES == cc::MAX_K, "rt_candidate and cc::Cand must share one layout");
 int rt_results_rec_candidates(const rt_results* r, int page, int line, const rt_candidate** cands, const int32_t** cols) {
   auto* p = RT_PAGE(r, page);
   if (!p || p->cand_k <= 0 || line < 0 || (size_t)line + 1 >= p->cand_off.size()) return 0;
@@ -837,327 +674,47 @@ int rt_results_rec_candidates(const rt_results* r, int page, int line, const rt_
   if (cols) *cols = p->cand_cols.data() + o;
   return p->cand_k;
 }
-int rt_debug_ctc_candidates_host(const float* z5, const float* W, const float* bias, int N, const int32_t* idx, const float* prob,
-                                 const int32_t* tokens_per_line, int n_lines, int K, rt_candidate* cands_out, int32_t* cols_out,
-                                 int32_t* n_tokens_out) {
-  long long rows = 0;
-  if (!cand_args_ok(z5, W, N, idx, prob, tokens_per_line, n_lines, K, cands_out, cols_out, n_tokens_out, &rows)) return RT_ERR_INVALID;
-  try {
-    const int D = 120;
-    std::vector<float> logits((size_t)N);
-    cc::Cand* out = reinterpret_cast<cc::Cand*>(cands_out);
-    long long o = 0;
-    for (int i = 0; i < n_lines; i++) {
-      const int T = tokens_per_line[i];
-      const int n = cc::line_kept(idx + o, prob + o, T, K, cols_out + o, out + o * K);
-      n_tokens_out[i] = n;
-      for (int j = 0; K > 1 && j < n; j++) {
-        cc::Cand* c = out + (o + j) * K;
-        cc::row_candidates(z5 + (size_t)(o + cols_out[o + j]) * D, D, W, bias, N, c[0].id, K, c, logits.data());
-      }
-      o += T;
-    }
-    return RT_OK;
-  } catch (const std::exception&) {
-    return RT_ERR_BACKEND;
-  }
-}
-static_assert(RT_MAX_CHARSETS == cs::MAX_SETS, "RT_MAX_CHARSETS and cs::MAX_SETS must agree");
-int rt_debug_charset_compile(const void* dict, size_t dict_len, const char* utf8, size_t len, const int32_t* ids, int n_ids,
-                             uint32_t* mask_out, int mask_cap, int* n_classes, char* err, size_t err_cap) {
-  if (err && err_cap) err[0] = 0;
-  if ((!dict && dict_len) || (!utf8 && len) || n_ids < 0 || (!ids && n_ids) || !n_classes || mask_cap < 0 || (!mask_out && mask_cap)) {
-    if (err && err_cap) snprintf(err, err_cap, "rt_debug_charset_compile: bad argument");
-    return RT_ERR_INVALID;
-  }
-  *n_classes = 0;
-  try {
-    std::vector<uint8_t> bytes((const uint8_t*)dict, (const uint8_t*)dict + dict_len);
-    const std::vector<std::string> d = rt::load_dictionary(bytes);
-    const std::vector<uint32_t> mask = rt::compile_charset(d, utf8, len, ids, n_ids);
-    *n_classes = (int)d.size();
-    if ((size_t)mask_cap < mask.size()) throw RtError(RT_ERR_INVALID, "rt_debug_charset_compile: the mask needs " + std::to_string(mask.size()) + " words");
-    memcpy(mask_out, mask.data(), mask.size() * sizeof(uint32_t));
-    return RT_OK;
-  } catch (const RtError& e) {
-    if (err && err_cap) snprintf(err, err_cap, "%s", e.what());
-    return e.code;
-  } catch (const std::exception& e) {
-    if (err && err_cap) snprintf(err, err_cap, "%s", e.what());
-    return RT_ERR_BACKEND;
-  }
-}
-int rt_debug_ctc_charset_host(const float* z5, const float* W, const float* bias, int N, int32_t* idx, float* prob,
-                              const int32_t* tokens_per_line, int n_lines, const int32_t* line_set, const uint32_t* masks,
-                              int n_sets, int K, int32_t* tokens_out, int32_t* n_tokens_out, float* scores_out,
-                              rt_candidate* cands_out, int32_t* cols_out) {
-  long long rows = 0;
-  if (!charset_args_ok(z5, W, N, idx, prob, tokens_per_line, n_lines, line_set, masks, n_sets, K, tokens_out, n_tokens_out,
-                       scores_out, cands_out, cols_out, &rows))
-    return RT_ERR_INVALID;
-  try {
-    const int D = 120, words = cs::mask_words(N);
-    std::vector<float> logits((size_t)N);
-    cc::Cand* out = reinterpret_cast<cc::Cand*>(cands_out);
-    long long o = 0;
-    for (int i = 0; i < n_lines; i++) {
-      const int T = tokens_per_line[i];
-      const uint32_t* m = line_set[i] > 0 ? masks + (size_t)(line_set[i] - 1) * words : nullptr;
-      for (int t = 0; m && t < T; t++) {   // the restricted rows' (idx, prob), before the decode
-        cs::row_logits(z5 + (size_t)(o + t) * D, D, W, bias, N, logits.data());
-        cs::row_argmax(logits.data(), N, m, idx + o + t, prob + o + t, nullptr, nullptr);
-      }
-      int cnt = 0; float acc = 0.0f;   // k_ctc_decode
-      for (int t = 0; t < T; t++)
-        if (cc::kept(idx[o + t], t > 0 ? idx[o + t - 1] : 0, t == 0)) { tokens_out[o + cnt] = idx[o + t]; acc = acc + prob[o + t]; cnt++; }
-      n_tokens_out[i] = cnt;
-      scores_out[i] = acc / (float)(unsigned)cnt;
-      if (K > 0) {
-        const int n = cc::line_kept(idx + o, prob + o, T, K, cols_out + o, out + o * K);
-        for (int j = 0; K > 1 && j < n; j++) {
-          cc::Cand* c = out + (o + j) * K;
-          const float* z = z5 + (size_t)(o + cols_out[o + j]) * D;
-          if (m) { cs::row_logits(z, D, W, bias, N, logits.data()); cs::row_candidates(logits.data(), N, m, c[0].id, K, c); }
-          else cc::row_candidates(z, D, W, bias, N, c[0].id, K, c, logits.data());
-        }
-      }
-      o += T;
-    }
-    return RT_OK;
-  } catch (const std::exception&) {
-    return RT_ERR_BACKEND;
-  }
-}
-static_assert(RT_MAX_LEXICONS == lx::MAX_LEXICONS && RT_LEXICON_MAX_ENTRIES == lx::MAX_ENTRIES && RT_LEXICON_MAX_LEN == lx::MAX_LEN &&
-                  RT_LEXICON_MATCHES == lx::MATCHES, "the RT_LEXICON_* limits and lx:: must agree");
-static_assert(sizeof(rt_lexicon_match) == sizeof(lx::Match) && offsetof(rt_lexicon_match, loglik) == offsetof(lx::Match, loglik) &&
-                  offsetof(rt_lexicon_match, posterior) == offsetof(lx::Match, posterior), "rt_lexicon_match and lx::Match must share one layout");
 int rt_results_rec_lexicon(const rt_results* r, int page, int line, const rt_lexicon_match** m) {
-  auto* p = RT_PAGE(r, page);
-  if (!p || line < 0 || (size_t)line >= p->lex_n.size()) return 0;
+  auto* p = page_of_line(r, page, line, &rt_results::Page::lex_n);
+  if (!p) return 0;
   if (m) *m = reinterpret_cast<const rt_lexicon_match*>(p->lex_matches.data()) + (size_t)line * lx::MATCHES;
   return p->lex_n[(size_t)line];
 }
 int rt_results_rec_lexicon_id(const rt_results* r, int page, int line) {
-  auto* p = RT_PAGE(r, page);
-  if (!p || line < 0 || (size_t)line >= p->lex_id.size()) return 0;
-  return p->lex_id[(size_t)line];
+  auto* p = page_of_line(r, page, line, &rt_results::Page::lex_id);
+  return p ? p->lex_id[(size_t)line] : 0;
 }
 int rt_results_rec_lexicon_snapped(const rt_results* r, int page, int line) {
-  auto* p = RT_PAGE(r, page);
-  if (!p || line < 0 || (size_t)line >= p->lex_snapped.size()) return 0;
-  return p->lex_snapped[(size_t)line];
+  auto* p = page_of_line(r, page, line, &rt_results::Page::lex_snapped);
+  return p ? p->lex_snapped[(size_t)line] : 0;
 }
-int rt_debug_lexicon_compile(const void* dict, size_t dict_len, const char* utf8, size_t len, const int32_t* ids,
-                             const int32_t* entry_lens, int n_id_entries, int32_t* ids_out, int ids_cap, int32_t* lens_out,
-                             int lens_cap, int* n_ids_out, int* n_entries_out, int* n_classes, char* err, size_t err_cap) {
-  if (err && err_cap) err[0] = 0;
-  if ((!dict && dict_len) || (!utf8 && len) || n_id_entries < 0 || ((!ids || !entry_lens) && n_id_entries) || !n_ids_out ||
-      !n_entries_out || !n_classes || ids_cap < 0 || lens_cap < 0 || (!ids_out && ids_cap) || (!lens_out && lens_cap)) {
-    if (err && err_cap) snprintf(err, err_cap, "rt_debug_lexicon_compile: bad argument");
-    return RT_ERR_INVALID;
-  }
-  *n_ids_out = 0; *n_entries_out = 0; *n_classes = 0;
-  try {
-    std::vector<uint8_t> bytes((const uint8_t*)dict, (const uint8_t*)dict + dict_len);
-    const std::vector<std::string> d = rt::load_dictionary(bytes);
-    *n_classes = (int)d.size();
-    std::vector<int32_t> vi, vl;
-    rt::compile_lexicon(d, utf8, len, ids, entry_lens, n_id_entries, vi, vl);
-    *n_ids_out = (int)vi.size(); *n_entries_out = (int)vl.size();
-    if ((size_t)ids_cap < vi.size() || (size_t)lens_cap < vl.size())
-      throw RtError(RT_ERR_INVALID, "rt_debug_lexicon_compile: the lexicon needs " + std::to_string(vi.size()) + " ids and " +
-                                        std::to_string(vl.size()) + " lengths");
-    memcpy(ids_out, vi.data(), vi.size() * sizeof(int32_t));
-    memcpy(lens_out, vl.data(), vl.size() * sizeof(int32_t));
-    return RT_OK;
-  } catch (const RtError& e) {
-    if (err && err_cap) snprintf(err, err_cap, "%s", e.what());
-    return e.code;
-  } catch (const std::exception& e) {
-    if (err && err_cap) snprintf(err, err_cap, "%s", e.what());
-    return RT_ERR_BACKEND;
-  }
-}
-// both rt_debug_ctc_lexicon*_host forms, arguments already checked; lex_min_post null: the lexicon rule alone
-static int lexicon_host(const float* z5, const float* W, const float* bias, int N, const int32_t* tokens_per_line, int n_lines,
-                        const int32_t* line_lex, const int32_t* entry_ids, const int32_t* entry_lens, const int32_t* lex_first_entry,
-                        int n_lex, float* loglik_out, rt_lexicon_match* matches_out, int32_t* n_matches_out,
-                        const float* lex_min_post, int32_t* idx, float* prob, int32_t* snapped_out, float* vit_out) {
-  try {
-    const int D = 120;
-    std::vector<long long> id_off((size_t)lex_first_entry[n_lex] + 1, 0);
-    for (int j = 0; j < lex_first_entry[n_lex]; j++) id_off[(size_t)j + 1] = id_off[(size_t)j] + entry_lens[j];
-    std::vector<float> logits, lse, row;
-    long long o = 0, out = 0;
-    for (int i = 0; i < n_lines; i++) {
-      const int T = tokens_per_line[i];
-      n_matches_out[i] = 0;
-      if (line_lex[i] > 0) {
-        logits.assign((size_t)std::max(T, 1) * N, 0.0f); lse.assign((size_t)std::max(T, 1), 0.0f);
-        for (int t = 0; t < T; t++) {
-          cs::row_logits(z5 + (size_t)(o + t) * D, D, W, bias, N, logits.data() + (size_t)t * N);
-          lse[(size_t)t] = lx::row_lse(logits.data() + (size_t)t * N, N);
-        }
-        const int e0 = lex_first_entry[line_lex[i] - 1], n = lex_first_entry[line_lex[i]] - e0;
-        row.assign((size_t)n, 0.0f);
-        for (int e = 0; e < n; e++)
-          row[(size_t)e] = lx::entry_loglik(logits.data(), N, lse.data(), T, entry_ids + id_off[(size_t)(e0 + e)], entry_lens[e0 + e]);
-        const lx::Match* m = reinterpret_cast<lx::Match*>(matches_out) + (size_t)i * lx::MATCHES;
-        n_matches_out[i] = lx::line_matches(row.data(), n, reinterpret_cast<lx::Match*>(matches_out) + (size_t)i * lx::MATCHES);
-        if (loglik_out) memcpy(loglik_out + out, row.data(), (size_t)n * sizeof(float));
-        out += n;
-        if (lex_min_post) {   // lexicon snap (ctc_lexicon_align.h); m[0] is read only where the line has a match
-          const bool fire = la::snaps(lex_min_post[line_lex[i] - 1], n_matches_out[i], n_matches_out[i] >= 1 ? m[0].posterior : 0.0f);
-          snapped_out[i] = fire ? 1 : 0;
-          if (fire)
-            vit_out[i] = la::align_line(logits.data(), N, lse.data(), T, entry_ids + id_off[(size_t)(e0 + m[0].entry)],
-                                        entry_lens[e0 + m[0].entry], idx + o, prob + o);
-        }
-      }
-      o += T;
-    }
-    return RT_OK;
-  } catch (const std::exception&) {
-    return RT_ERR_BACKEND;
-  }
-}
-int rt_debug_ctc_lexicon_host(const float* z5, const float* W, const float* bias, int N, const int32_t* tokens_per_line,
-                              int n_lines, const int32_t* line_lex, const int32_t* entry_ids, const int32_t* entry_lens,
-                              const int32_t* lex_first_entry, int n_lex, float* loglik_out, rt_lexicon_match* matches_out,
-                              int32_t* n_matches_out) {
-  long long rows = 0, table = 0;
-  const std::string bad = lexicon_args_error(z5, W, N, tokens_per_line, n_lines, line_lex, entry_ids, entry_lens, lex_first_entry, n_lex,
-                                             matches_out, n_matches_out, &rows, &table);
-  if (!bad.empty()) {
-    rt::create_error() = "rt_debug_ctc_lexicon_host: " + bad;
-    return RT_ERR_INVALID;
-  }
-  return lexicon_host(z5, W, bias, N, tokens_per_line, n_lines, line_lex, entry_ids, entry_lens, lex_first_entry, n_lex, loglik_out,
-                      matches_out, n_matches_out, nullptr, nullptr, nullptr, nullptr, nullptr);
-}
-int rt_debug_ctc_lexicon_align_host(const float* z5, const float* W, const float* bias, int N, const int32_t* tokens_per_line,
-                                    int n_lines, const int32_t* line_lex, const int32_t* entry_ids, const int32_t* entry_lens,
-                                    const int32_t* lex_first_entry, int n_lex, const float* lex_min_post, int32_t* idx, float* prob,
-                                    int32_t* snapped_out, float* vit_out, float* loglik_out, rt_lexicon_match* matches_out,
-                                    int32_t* n_matches_out) {
-  long long rows = 0, table = 0;
-  std::string bad = lexicon_args_error(z5, W, N, tokens_per_line, n_lines, line_lex, entry_ids, entry_lens, lex_first_entry, n_lex,
-                                       matches_out, n_matches_out, &rows, &table);
-  if (bad.empty()) bad = lexicon_align_args_error(lex_min_post, n_lex, idx, prob, snapped_out, vit_out);
-  if (!bad.empty()) {
-    rt::create_error() = "rt_debug_ctc_lexicon_align_host: " + bad;
-    return RT_ERR_INVALID;
-  }
-  return lexicon_host(z5, W, bias, N, tokens_per_line, n_lines, line_lex, entry_ids, entry_lens, lex_first_entry, n_lex, loglik_out,
-                      matches_out, n_matches_out, lex_min_post, idx, prob, snapped_out, vit_out);
-}
-static_assert(RT_MAX_KEYWORD_LISTS == kw::MAX_LISTS && RT_KEYWORD_HITS == kw::HITS, "the RT_KEYWORD_* limits and kw:: must agree");
-static_assert(sizeof(rt_keyword_hit) == sizeof(kw::Hit) && offsetof(rt_keyword_hit, score) == offsetof(kw::Hit, score) &&
-                  offsetof(rt_keyword_hit, first_col) == offsetof(kw::Hit, first_col) && offsetof(rt_keyword_hit, last_col) == offsetof(kw::Hit, last_col) &&
-                  offsetof(rt_keyword_hit, quad) == offsetof(kw::Hit, quad), "rt_keyword_hit and kw::Hit must share one layout");
 int rt_results_rec_keywords(const rt_results* r, int page, int line, const rt_keyword_hit** hits) {
-  auto* p = RT_PAGE(r, page);
-  if (!p || line < 0 || (size_t)line >= p->kw_n.size()) return 0;
+  auto* p = page_of_line(r, page, line, &rt_results::Page::kw_n);
+  if (!p) return 0;
   if (hits) *hits = reinterpret_cast<const rt_keyword_hit*>(p->kw_hits.data()) + (size_t)line * kw::HITS;
   return p->kw_n[(size_t)line];
 }
 int rt_results_rec_keywords_id(const rt_results* r, int page, int line) {
-  auto* p = RT_PAGE(r, page);
-  if (!p || line < 0 || (size_t)line >= p->kw_id.size()) return 0;
-  return p->kw_id[(size_t)line];
+  auto* p = page_of_line(r, page, line, &rt_results::Page::kw_id);
+  return p ? p->kw_id[(size_t)line] : 0;
 }
 int rt_results_rec_beams(const rt_results* r, int page, int line, const rt_beam** out) {
-  auto* p = RT_PAGE(r, page);
-  if (!p || p->beam_n <= 0 || line < 0 || (size_t)line >= p->bm_count.size()) return 0;
+  auto* p = page_of_line(r, page, line, &rt_results::Page::bm_count);
+  if (!p || p->beam_n <= 0) return 0;
   if (out) *out = reinterpret_cast<const rt_beam*>(p->bm_recs.data()) + (size_t)line * p->beam_n;
   return p->bm_count[(size_t)line];
 }
 int rt_results_rec_beam_tokens(const rt_results* r, int page, int line, int k, const int32_t** tokens) {
-  auto* p = RT_PAGE(r, page);
-  if (!p || p->beam_n <= 0 || line < 0 || (size_t)line >= p->bm_count.size() || k < 0 || k >= p->bm_count[(size_t)line]) return 0;
+  auto* p = page_of_line(r, page, line, &rt_results::Page::bm_count);
+  if (!p || p->beam_n <= 0 || k < 0 || k >= p->bm_count[(size_t)line]) return 0;
   const std::vector<int32_t>& t = p->bm_tokens[(size_t)line * p->beam_n + k];
   if (tokens) *tokens = t.data();
   return (int)t.size();
 }
 const char* rt_results_rec_beam_text(const rt_results* r, int page, int line, int k) {
-  auto* p = RT_PAGE(r, page);
-  if (!p || p->beam_n <= 0 || line < 0 || (size_t)line >= p->bm_count.size() || k < 0 || k >= p->bm_count[(size_t)line]) return nullptr;
+  auto* p = page_of_line(r, page, line, &rt_results::Page::bm_count);
+  if (!p || p->beam_n <= 0 || k < 0 || k >= p->bm_count[(size_t)line]) return nullptr;
   return p->bm_text[(size_t)line * p->beam_n + k].c_str();
-}
-int rt_debug_ctc_beam_host(const float* z5, const float* W, const float* bias, int N, const int32_t* tokens_per_line, int n_lines,
-                           int beam, int nbest, int32_t* counts_out, rt_beam* beams_out, int32_t* tokens_out) {
-  long long rows = 0;
-  const std::string bad = beam_args_error(z5, W, N, tokens_per_line, n_lines, beam, nbest, counts_out, beams_out, tokens_out, &rows);
-  if (!bad.empty()) {
-    rt::create_error() = "rt_debug_ctc_beam_host: " + bad;
-    return RT_ERR_INVALID;
-  }
-  if (beam == 0) return RT_OK;
-  try {
-    const int D = 120;
-    std::vector<float> logits, lse;
-    long long o = 0;
-    for (int i = 0; i < n_lines; i++) {
-      const int T = tokens_per_line[i];
-      logits.assign((size_t)std::max(T, 1) * N, 0.0f); lse.assign((size_t)std::max(T, 1), 0.0f);
-      for (int t = 0; t < T; t++) {
-        cs::row_logits(z5 + (size_t)(o + t) * D, D, W, bias, N, logits.data() + (size_t)t * N);
-        lse[(size_t)t] = lx::row_lse(logits.data() + (size_t)t * N, N);
-      }
-      counts_out[i] = bm::line_beams(logits.data(), N, lse.data(), T, N, beam, nbest, reinterpret_cast<bm::Beam*>(beams_out) + (size_t)i * nbest,
-                                     tokens_out + o * nbest);
-      o += T;
-    }
-    return RT_OK;
-  } catch (const std::exception&) {
-    return RT_ERR_BACKEND;
-  }
-}
-int rt_debug_ctc_keywords_host(const float* z5, const float* W, const float* bias, int N, const int32_t* tokens_per_line, int n_lines,
-                               const int32_t* line_kw, const int32_t* entry_ids, const int32_t* entry_lens,
-                               const int32_t* kw_first_entry, int n_kw, const float* kw_min_score, float* score_out, int32_t* span_out,
-                               rt_keyword_hit* hits_out, int32_t* n_hits_out) {
-  long long rows = 0, table = 0;
-  const std::string bad = keywords_args_error(z5, W, N, tokens_per_line, n_lines, line_kw, entry_ids, entry_lens, kw_first_entry, n_kw,
-                                              kw_min_score, hits_out, n_hits_out, &rows, &table);
-  if (!bad.empty()) {
-    rt::create_error() = "rt_debug_ctc_keywords_host: " + bad;
-    return RT_ERR_INVALID;
-  }
-  try {
-    const int D = 120;
-    std::vector<long long> id_off((size_t)kw_first_entry[n_kw] + 1, 0);
-    for (int j = 0; j < kw_first_entry[n_kw]; j++) id_off[(size_t)j + 1] = id_off[(size_t)j] + entry_lens[j];
-    std::vector<float> logits, rmax, row;
-    std::vector<int32_t> span;
-    long long o = 0, out = 0;
-    for (int i = 0; i < n_lines; i++) {
-      const int T = tokens_per_line[i];
-      n_hits_out[i] = 0;
-      if (line_kw[i] > 0) {
-        logits.assign((size_t)std::max(T, 1) * N, 0.0f); rmax.assign((size_t)std::max(T, 1), 0.0f);
-        for (int t = 0; t < T; t++) {
-          cs::row_logits(z5 + (size_t)(o + t) * D, D, W, bias, N, logits.data() + (size_t)t * N);
-          rmax[(size_t)t] = kw::row_max(logits.data() + (size_t)t * N, N);
-        }
-        const int e0 = kw_first_entry[line_kw[i] - 1], n = kw_first_entry[line_kw[i]] - e0;
-        row.assign((size_t)n, 0.0f); span.assign((size_t)2 * n, -1);
-        for (int e = 0; e < n; e++)
-          row[(size_t)e] = kw::entry_spot(logits.data(), N, rmax.data(), T, entry_ids + id_off[(size_t)(e0 + e)], entry_lens[e0 + e],
-                                          span.data() + 2 * (size_t)e);
-        n_hits_out[i] = kw::line_hits(row.data(), span.data(), n, kw_min_score[line_kw[i] - 1],
-                                      reinterpret_cast<kw::Hit*>(hits_out) + (size_t)i * kw::HITS);
-        if (score_out) memcpy(score_out + out, row.data(), (size_t)n * sizeof(float));
-        if (span_out) memcpy(span_out + 2 * out, span.data(), (size_t)2 * n * sizeof(int32_t));
-        out += n;
-      }
-      o += T;
-    }
-    return RT_OK;
-  } catch (const std::exception&) {
-    return RT_ERR_BACKEND;
-  }
 }
 int rt_debug_span_quad(int T, int W, int resized_w, const float* box8_after, int rot180, int after_w, int after_h, int ori_w, int ori_h,
                        int first_col, int last_col, float* quad8_out) {
@@ -1175,78 +732,6 @@ int rt_debug_span_quad(int T, int W, int resized_w, const float* box8_after, int
   kw::span_quad(first_col, last_col, g, rot180 ? 1 : 0, quad8_out);
   gm::scale_and_clip(quad8_out, (double)after_w, (double)after_h, (double)ori_w, (double)ori_h);
   return RT_OK;
-}
-static_assert(RT_MAX_PATTERNS == pt::MAX_PATTERNS && RT_PATTERN_MAX_STATES == pt::MAX_STATES && RT_PATTERN_MAX_PAIRS == pt::MAX_PAIRS &&
-                  RT_PATTERN_MAX_BYTES == pt::MAX_BYTES, "the RT_PATTERN_* limits and pt:: must agree");
-static_assert(RT_OK == pt::OK && RT_ERR_UTF8 == pt::ERR_UTF8 && RT_ERR_INVALID == pt::ERR_INVALID && RT_ERR_CAPACITY == pt::ERR_CAPACITY,
-              "the status codes of ctc_pattern.h are the RT_ERR_* ones");
-int rt_debug_pattern_compile(const void* dict, size_t dict_len, const char* utf8, size_t len, int32_t* group_of_out, int group_cap,
-                             int32_t* delta_out, int delta_cap, int32_t* accept_out, int accept_cap, int* S_out, int* G_out, int* P_out,
-                             int* min_steps_out, int* n_classes, char* err, size_t err_cap) {
-  if (err && err_cap) err[0] = 0;
-  if ((!dict && dict_len) || (!utf8 && len) || !S_out || !G_out || !P_out || !min_steps_out || !n_classes || group_cap < 0 ||
-      delta_cap < 0 || accept_cap < 0 || (!group_of_out && group_cap) || (!delta_out && delta_cap) || (!accept_out && accept_cap)) {
-    if (err && err_cap) snprintf(err, err_cap, "rt_debug_pattern_compile: bad argument");
-    return RT_ERR_INVALID;
-  }
-  *S_out = 0; *G_out = 0; *P_out = 0; *min_steps_out = 0; *n_classes = 0;
-  try {
-    std::vector<uint8_t> bytes((const uint8_t*)dict, (const uint8_t*)dict + dict_len);
-    const std::vector<std::string> d = rt::load_dictionary(bytes);
-    *n_classes = (int)d.size();
-    pt::Compiled c;
-    std::string msg;
-    const int rc = pt::compile(d, utf8, len, c, msg);
-    if (rc != pt::OK) throw RtError(rc, msg);
-    *S_out = c.S; *G_out = c.G; *P_out = c.P; *min_steps_out = c.min_steps;
-    if ((size_t)group_cap < c.group_of.size() || (size_t)delta_cap < c.delta.size() || (size_t)accept_cap < c.accept.size())
-      throw RtError(RT_ERR_INVALID, "rt_debug_pattern_compile: the pattern needs " + std::to_string(c.group_of.size()) + " groups' ids, " +
-                                        std::to_string(c.delta.size()) + " arcs and " + std::to_string(c.accept.size()) + " flags");
-    memcpy(group_of_out, c.group_of.data(), c.group_of.size() * sizeof(int32_t));
-    memcpy(delta_out, c.delta.data(), c.delta.size() * sizeof(int32_t));
-    memcpy(accept_out, c.accept.data(), c.accept.size() * sizeof(int32_t));
-    return RT_OK;
-  } catch (const RtError& e) {
-    if (err && err_cap) snprintf(err, err_cap, "%s", e.what());
-    return e.code;
-  } catch (const std::exception& e) {
-    if (err && err_cap) snprintf(err, err_cap, "%s", e.what());
-    return RT_ERR_BACKEND;
-  }
-}
-int rt_debug_ctc_pattern_host(const float* z5, const float* W, const float* bias, int N, const int32_t* tokens_per_line, int n_lines,
-                              const int32_t* line_pat, const int32_t* pat_S, const int32_t* pat_G, const int32_t* group_of,
-                              const int32_t* delta, const int32_t* accept, int n_pat, int32_t* idx, float* prob, int32_t* matched_out,
-                              float* vit_out, float* logprob_out, float* free_out) {
-  long long rows = 0;
-  std::vector<pt::Rule> rules;
-  try {
-    const std::string bad = pattern_args_error(z5, W, N, tokens_per_line, n_lines, line_pat, pat_S, pat_G, group_of, delta, accept, n_pat,
-                                               idx, prob, matched_out, vit_out, logprob_out, free_out, &rows, &rules);
-    if (!bad.empty()) {
-      rt::create_error() = "rt_debug_ctc_pattern_host: " + bad;
-      return RT_ERR_INVALID;
-    }
-    const int D = 120;
-    std::vector<float> logits, lse;
-    long long o = 0;
-    for (int i = 0; i < n_lines; i++) {
-      const int T = tokens_per_line[i];
-      if (line_pat[i] > 0) {
-        logits.assign((size_t)std::max(T, 1) * N, 0.0f); lse.assign((size_t)std::max(T, 1), 0.0f);
-        for (int t = 0; t < T; t++) {
-          cs::row_logits(z5 + (size_t)(o + t) * D, D, W, bias, N, logits.data() + (size_t)t * N);
-          lse[(size_t)t] = lx::row_lse(logits.data() + (size_t)t * N, N);
-        }
-        const pt::LineResult r = pt::viterbi_line(rules[(size_t)line_pat[i] - 1], logits.data(), N, lse.data(), T, idx + o, prob + o);
-        matched_out[i] = r.matched; vit_out[i] = r.vit; logprob_out[i] = r.logprob; free_out[i] = r.free_logprob;
-      }
-      o += T;
-    }
-    return RT_OK;
-  } catch (const std::exception&) {
-    return RT_ERR_BACKEND;
-  }
 }
 double rt_results_det_checksum(const rt_results* r) { return r ? r->det_checksum : 0.0; }
 const char* rt_results_json(rt_results* r, int page, int stage) {

@@ -1,15 +1,14 @@
 // Kernel-level diagnostics of libretto_hip.so (include/retto_hip.h, diagnostics section): the A/B switches of tools/, the kernel
 // micro-benchmarks (rt_bench_*), and one harness per kernel family that runs a single launch on host arrays for the fp64 tests
-// (rt_debug_gemm, _dwconv, _dw_plan, _attention, _ctc_candidates, _ctc_charset, _ctc_lexicon, _ctc_lexicon_align, _ctc_pattern, _lc_block, _lc_wide, _conv13, _layernorm, _conv16, _glue16, _fpn, _conv16x, _cls_block, _stem, _glue32).
+// (rt_debug_gemm, _dwconv, _dw_plan, _attention, _lc_block, _lc_wide, _conv13, _layernorm, _conv16, _glue16, _fpn, _conv16x, _cls_block, _stem, _glue32).
 // None of it runs in production, and every kernel test depends on it.  A harness has one shape: check the arguments (each
-// failure with its own message, before any device work), lay the ragged lists out (Ragged), put the operands on the device
+// failure with its own message, before any device work), lay the ragged lists out (Ragged, api_internal.h), put the operands on the device
 // (DevBufs::upload / zeroed, upload_as), fill what the kernel writes with RT_DEBUG_CANARY and spare rows (DevBufs::canary),
 // launch as the networks do, synchronise the stream, DevBufs::download.  A new entry is a thin body on these helpers.
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <numeric>
 
 #include "api_internal.h"
 
@@ -17,29 +16,6 @@ using namespace rt;
 
 namespace {
 using nh::half_t;
-
-// A ragged list of images laid out back to back, as the networks' levels are: each image's offset in pixels, the total, the
-// largest extents.  It accumulates; what an entry accepts (empty, oversized) is the entry's own check, made before.
-struct Ragged {
-  std::vector<ImgGeom> g;
-  long long total = 0, max_pix = 0;
-  int maxH = 0, maxW = 0;
-  Ragged() = default;
-  Ragged(const int* hs, const int* ws, int n) { for (int i = 0; i < n; i++) push(hs[i], ws[i]); }
-  // token lines (or image row counts): one ImgGeom{off, 1, T} each, as SvtrCore passes its token level
-  template <typename I> Ragged(const I* tokens, int n) { for (int i = 0; i < n; i++) push(1, (int)tokens[i]); }
-  void push(int h, int w) {
-    g.push_back(ImgGeom{total, h, w, 0});
-    const long long pix = (long long)h * w;
-    total += pix; max_pix = std::max(max_pix, pix); maxH = std::max(maxH, h); maxW = std::max(maxW, w);
-  }
-  int n() const { return (int)g.size(); }
-  Ragged down(int sh, int sw) const { Ragged r; for (const ImgGeom& i : g) r.push((i.H + sh - 1) / sh, (i.W + sw - 1) / sw); return r; }   // a "same"-padded conv of stride (sh, sw)
-  Ragged up(int k) const { Ragged r; for (const ImgGeom& i : g) r.push(k * i.H, k * i.W); return r; }
-  Ragged pool(int kh, int kw) const { Ragged r; for (const ImgGeom& i : g) r.push(i.H / kh, i.W / kw); return r; }   // window = stride, no padding (pool_level)
-  Ragged flat() const { Ragged r; r.push(1, (int)total); return r; }   // one image of 1 x total pixels
-  const ImgGeom* upload(DevBufs& bufs) const { return bufs.upload(g.data(), g.size()); }
-};
 
 // fp16 conv weights [cout][cin][kh][kw] as upload_conv16 packs them: [ceil(cin_pad / 32)][kh][kw][npad][32] halves, zero where
 // no weight lands.  rt_debug_conv16 passes cin_pad = pitch8(cin), rt_debug_conv16x cin_pad = cin (a multiple of 8 there); the
@@ -375,270 +351,6 @@ RT_API int rt_debug_attention(rt_session* s, const float* qkv, long long rows, c
     nn::attention(s->st, dq, lines.upload(bufs), n_lines, lines.maxW, heads, hd, dout);
     RT_HIP_CHECK(hipStreamSynchronize(s->st));
     DevBufs::download(out, dout, (size_t)rows * C);
-  });
-}
-
-// One rec group on host arrays through rt_session::rec_tail, the tail rec_groups runs per group, on the plan of rec_tail_plan.h
-// over the caller's lines: the features inside a larger zeroed allocation, as z5 sits inside the scratch arena; an FC packed by
-// pack_linear; the lines' geometry as the token level gives it; idx / prob the caller's (null: zeros, the decode's results are
-// then thrown away); opts: the lines' options (lines_with), whose ids count into `stores`; beam_b > 0: every line carries the beam.
-// An entry adds its own kind's tables, inputs and outputs to `t`, run()s, and downloads.
-struct TailHook {
-  rt_session* s; size_t nr;
-  WeightStore ws; SvtrCore core; DevBufs bufs;
-  RecTailPlan plan; rt_session::RecTail t;
-  TailHook(rt_session* s_, const float* z5, const float* W, const float* bias, int N, long long rows, const int32_t* tokens_per_line,
-           int n_lines, const int32_t* idx, const float* prob, int K, int chunk_rows, const std::vector<RecLineOpts>& opts,
-           const RecStores& stores, int beam_b = 0, int beam_n = 0)
-      : s(s_), nr((size_t)std::max<long long>(rows, 1)) {
-    s->begin_call();
-    std::vector<long long> off((size_t)n_lines + 1, 0);
-    std::partial_sum(tokens_per_line, tokens_per_line + n_lines, off.begin() + 1);   // (below 2^30: the entries' own check)
-    plan = rec_tail_plan(off.data(), 0, n_lines, opts.data(), stores, beam_b, beam_n);
-    t.beam.b = beam_b; t.beam.n = beam_n;
-    core.classes = N;
-    if (plan.needs_z5(K)) {
-      core.fc = pack_linear(ws, W, bias, core.D, N);
-      float* dz = bufs.zeroed<float>((nr + 256) * core.D);
-      DevBufs::put(dz, z5, (size_t)rows * core.D); t.z5 = dz;
-    }
-    const std::vector<int32_t> zeros(idx ? 0 : nr, 0);
-    t.idx = bufs.upload(idx ? idx : zeros.data(), idx ? (size_t)rows : nr);
-    t.prob = bufs.upload(prob ? prob : reinterpret_cast<const float*>(zeros.data()), prob ? (size_t)rows : nr);
-    t.lines = Ragged(tokens_per_line, n_lines).upload(bufs); t.n_lines = n_lines;
-    t.tok = bufs.alloc<int>(nr); t.ntok = bufs.alloc<int>(n_lines); t.rscore = bufs.alloc<float>(n_lines);
-    t.cand.k = K; t.chunk_rows = chunk_rows;
-  }
-  // rec_return_candidates: what the kernels write starts as the caller's values
-  void candidates(const int32_t* cols, const rt_candidate* cands) {
-    t.cand.col = bufs.alloc<int>(nr); t.cand.cands = bufs.alloc<cc::Cand>(nr * t.cand.k); DevBufs::put(t.cand.col, cols, (size_t)plan.rows);
-    DevBufs::put(t.cand.cands, reinterpret_cast<const cc::Cand*>(cands), (size_t)plan.rows * t.cand.k);
-  }
-  void run() { s->rec_tail(plan, core, t); RT_HIP_CHECK(hipStreamSynchronize(s->st)); }
-  void download_candidates(int32_t* cols, rt_candidate* cands) const {
-    DevBufs::download(cols, t.cand.col, (size_t)plan.rows);
-    DevBufs::download(reinterpret_cast<cc::Cand*>(cands), t.cand.cands, (size_t)plan.rows * t.cand.k);
-  }
-};
-// the lists of a lexicon or keyword entry as lx::Tables: list k has the entries [first_entry[k], first_entry[k + 1]), whose ids
-// follow each other in entry_ids
-static lx::Tables tables_of(const int32_t* entry_ids, const int32_t* entry_lens, const int32_t* first_entry, int n_lists) {
-  lx::Tables tb;
-  long long io = 0;
-  for (int k = 0; k < n_lists; k++) {
-    const int e0 = first_entry[k], n = first_entry[k + 1] - e0;
-    tb.add(entry_ids + io, entry_lens + e0, n);
-    for (int j = 0; j < n; j++) io += entry_lens[e0 + j];
-  }
-  return tb;
-}
-
-// rt_config.rec_return_candidates' device path on host arrays: pp::ctc_decode for the token counts, then the candidates.
-RT_API int rt_debug_ctc_candidates(rt_session* s, const float* z5, const float* W, const float* bias, int N, const int32_t* idx,
-                                   const float* prob, const int32_t* tokens_per_line, int n_lines, int K, int chunk_rows,
-                                   rt_candidate* cands_out, int32_t* cols_out, int32_t* n_tokens_out) {
-  long long rows = 0;
-  RT_REQUIRE(s, s, "rt_debug_ctc_candidates: null session");
-  RT_REQUIRE(cand_args_ok(z5, W, N, idx, prob, tokens_per_line, n_lines, K, cands_out, cols_out, n_tokens_out, &rows) && chunk_rows >= 0,
-             s, "rt_debug_ctc_candidates: bad argument");
-  return guarded(s, [&] {
-    TailHook h(s, z5, W, bias, N, rows, tokens_per_line, n_lines, idx, prob, K, chunk_rows, std::vector<RecLineOpts>((size_t)n_lines), RecStores{});
-    h.candidates(cols_out, cands_out);
-    h.run();
-    DevBufs::download(n_tokens_out, h.t.ntok, (size_t)n_lines);
-    h.download_candidates(cols_out, cands_out);
-  });
-}
-
-// Rec charsets' device path on host arrays: the restricted rows' argmax, pp::ctc_decode and -- K > 0 -- the candidates with the masks.
-RT_API int rt_debug_ctc_charset(rt_session* s, const float* z5, const float* W, const float* bias, int N, int32_t* idx, float* prob,
-                                const int32_t* tokens_per_line, int n_lines, const int32_t* line_set, const uint32_t* masks,
-                                int n_sets, int K, int chunk_rows, int32_t* tokens_out, int32_t* n_tokens_out, float* scores_out,
-                                rt_candidate* cands_out, int32_t* cols_out) {
-  long long rows = 0;
-  RT_REQUIRE(s, s, "rt_debug_ctc_charset: null session");
-  RT_REQUIRE(charset_args_ok(z5, W, N, idx, prob, tokens_per_line, n_lines, line_set, masks, n_sets, K, tokens_out, n_tokens_out,
-                             scores_out, cands_out, cols_out, &rows) && chunk_rows >= 0,
-             s, "rt_debug_ctc_charset: bad argument");
-  return guarded(s, [&] {
-    TailHook h(s, z5, W, bias, N, rows, tokens_per_line, n_lines, idx, prob, K, chunk_rows, lines_with(n_lines, &RecLineOpts::charset, line_set),
-               RecStores{});
-    h.t.charsets.words = cs::mask_words(N);
-    h.t.charsets.masks = n_sets > 0 ? h.bufs.upload(masks, (size_t)n_sets * h.t.charsets.words) : nullptr;
-    DevBufs::put(h.t.tok, tokens_out, (size_t)rows);
-    if (K > 0) h.candidates(cols_out, cands_out);
-    h.run();
-    DevBufs::download(idx, h.t.idx, (size_t)rows); DevBufs::download(prob, h.t.prob, (size_t)rows);
-    DevBufs::download(tokens_out, h.t.tok, (size_t)rows);
-    DevBufs::download(n_tokens_out, h.t.ntok, (size_t)n_lines); DevBufs::download(scores_out, h.t.rscore, (size_t)n_lines);
-    if (K > 0) h.download_candidates(cols_out, cands_out);
-  });
-}
-
-// Rec lexicons' device path on host arrays; the lexicon tables are built as rt_lexicon_create builds them (lx::Tables).  With
-// lex_min_post (lexicon snap, ctc_lexicon_align.h) also the caller's idx / prob rows, in and out, the flags and the Viterbi
-// values; a threshold above 0 on the lexicon of some line makes the group a snap group.
-static void debug_ctc_lexicon(rt_session* s, const float* z5, const float* W, const float* bias, int N, const int32_t* tokens_per_line,
-                              int n_lines, const int32_t* line_lex, const int32_t* entry_ids, const int32_t* entry_lens,
-                              const int32_t* lex_first_entry, int n_lex, int chunk_rows, long long rows,
-                              float* loglik_out, rt_lexicon_match* matches_out, int32_t* n_matches_out, const float* lex_min_post,
-                              int32_t* idx, float* prob, int32_t* snapped_out, float* vit_out) {
-  const lx::Tables tb = tables_of(entry_ids, entry_lens, lex_first_entry, n_lex);
-  TailHook h(s, z5, W, bias, N, rows, tokens_per_line, n_lines, idx, prob, 0, chunk_rows, lines_with(n_lines, &RecLineOpts::lexicon, line_lex),
-             RecStores{&tb, lex_min_post});
-  rt_entry_store X;   // (the tables on the device, freed on every way out)
-  X.set(tb);
-  for (int i = 0; i < n_lines; i++) {   // (a line without a lexicon has no match; the kernel, where it runs, writes every lexicon line's flag again)
-    if (line_lex[i] <= 0) n_matches_out[i] = 0;
-    else if (lex_min_post) snapped_out[i] = 0;
-  }
-  rt_session::RecTail::Lexicon& t = h.t.lexicon;
-  t.d = X.d;
-  // (what the kernels write starts as the caller's values: a slot they leave alone comes back untouched)
-  t.loglik = h.bufs.alloc<float>((size_t)h.plan.table);
-  if (loglik_out) DevBufs::put(t.loglik, loglik_out, (size_t)h.plan.table);
-  t.matches = h.bufs.upload(reinterpret_cast<const lx::Match*>(matches_out), (size_t)n_lines * lx::MATCHES);
-  t.n = h.bufs.upload(n_matches_out, (size_t)n_lines);
-  if (lex_min_post) {
-    t.d_min_post = h.bufs.upload(lex_min_post, (size_t)n_lex);
-    t.snapped = h.bufs.upload(snapped_out, (size_t)n_lines); t.vit = h.bufs.upload(vit_out, (size_t)n_lines);
-  }
-  h.run();
-  if (loglik_out) DevBufs::download(loglik_out, t.loglik, (size_t)h.plan.table);
-  DevBufs::download(reinterpret_cast<lx::Match*>(matches_out), t.matches, (size_t)n_lines * lx::MATCHES);
-  DevBufs::download(n_matches_out, t.n, (size_t)n_lines);
-  if (lex_min_post) {
-    DevBufs::download(idx, h.t.idx, (size_t)rows); DevBufs::download(prob, h.t.prob, (size_t)rows);
-    DevBufs::download(snapped_out, t.snapped, (size_t)n_lines); DevBufs::download(vit_out, t.vit, (size_t)n_lines);
-  }
-}
-RT_API int rt_debug_ctc_lexicon(rt_session* s, const float* z5, const float* W, const float* bias, int N,
-                                const int32_t* tokens_per_line, int n_lines, const int32_t* line_lex, const int32_t* entry_ids,
-                                const int32_t* entry_lens, const int32_t* lex_first_entry, int n_lex, int chunk_rows,
-                                float* loglik_out, rt_lexicon_match* matches_out, int32_t* n_matches_out) {
-  long long rows = 0, table = 0;
-  RT_REQUIRE(s, s, "rt_debug_ctc_lexicon: null session");
-  const std::string bad = lexicon_args_error(z5, W, N, tokens_per_line, n_lines, line_lex, entry_ids, entry_lens, lex_first_entry, n_lex,
-                                             matches_out, n_matches_out, &rows, &table);
-  RT_REQUIRE(bad.empty(), s, "rt_debug_ctc_lexicon: " + bad);
-  RT_REQUIRE(chunk_rows >= 0, s, "rt_debug_ctc_lexicon: chunk_rows is negative");
-  return guarded(s, [&] {
-    debug_ctc_lexicon(s, z5, W, bias, N, tokens_per_line, n_lines, line_lex, entry_ids, entry_lens, lex_first_entry, n_lex, chunk_rows,
-                      rows, loglik_out, matches_out, n_matches_out, nullptr, nullptr, nullptr, nullptr, nullptr);
-  });
-}
-RT_API int rt_debug_ctc_lexicon_align(rt_session* s, const float* z5, const float* W, const float* bias, int N,
-                                      const int32_t* tokens_per_line, int n_lines, const int32_t* line_lex, const int32_t* entry_ids,
-                                      const int32_t* entry_lens, const int32_t* lex_first_entry, int n_lex, const float* lex_min_post,
-                                      int chunk_rows, int32_t* idx, float* prob, int32_t* snapped_out, float* vit_out,
-                                      float* loglik_out, rt_lexicon_match* matches_out, int32_t* n_matches_out) {
-  long long rows = 0, table = 0;
-  RT_REQUIRE(s, s, "rt_debug_ctc_lexicon_align: null session");
-  std::string bad = lexicon_args_error(z5, W, N, tokens_per_line, n_lines, line_lex, entry_ids, entry_lens, lex_first_entry, n_lex,
-                                       matches_out, n_matches_out, &rows, &table);
-  if (bad.empty()) bad = lexicon_align_args_error(lex_min_post, n_lex, idx, prob, snapped_out, vit_out);
-  RT_REQUIRE(bad.empty(), s, "rt_debug_ctc_lexicon_align: " + bad);
-  RT_REQUIRE(chunk_rows >= 0, s, "rt_debug_ctc_lexicon_align: chunk_rows is negative");
-  return guarded(s, [&] {
-    debug_ctc_lexicon(s, z5, W, bias, N, tokens_per_line, n_lines, line_lex, entry_ids, entry_lens, lex_first_entry, n_lex, chunk_rows,
-                      rows, loglik_out, matches_out, n_matches_out, lex_min_post, idx, prob, snapped_out, vit_out);
-  });
-}
-
-// Rec patterns' device path on host arrays (ctc_pattern.h); the pattern tables are built as a session's store would build them
-// (pt::Rule::build from the flat compiled tables, pt::Tables).
-RT_API int rt_debug_ctc_pattern(rt_session* s, const float* z5, const float* W, const float* bias, int N,
-                                const int32_t* tokens_per_line, int n_lines, const int32_t* line_pat, const int32_t* pat_S,
-                                const int32_t* pat_G, const int32_t* group_of, const int32_t* delta, const int32_t* accept, int n_pat,
-                                int chunk_rows, int32_t* idx, float* prob, int32_t* matched_out, float* vit_out, float* logprob_out,
-                                float* free_out) {
-  long long rows = 0;
-  std::vector<pt::Rule> rules;
-  RT_REQUIRE(s, s, "rt_debug_ctc_pattern: null session");
-  const std::string bad = pattern_args_error(z5, W, N, tokens_per_line, n_lines, line_pat, pat_S, pat_G, group_of, delta, accept, n_pat,
-                                             idx, prob, matched_out, vit_out, logprob_out, free_out, &rows, &rules);
-  RT_REQUIRE(bad.empty(), s, "rt_debug_ctc_pattern: " + bad);
-  RT_REQUIRE(chunk_rows >= 0, s, "rt_debug_ctc_pattern: chunk_rows is negative");
-  return guarded(s, [&] {
-    pt::Tables tb;
-    for (const pt::Rule& r : rules) tb.add(r);
-    TailHook h(s, z5, W, bias, N, rows, tokens_per_line, n_lines, idx, prob, 0, chunk_rows, lines_with(n_lines, &RecLineOpts::pattern, line_pat),
-               RecStores{nullptr, nullptr, &tb});
-    rt_session::RecTail::Pattern& t = h.t.pattern;
-    t.d = pt::DevTables{h.bufs.upload(tb.pats.data(), tb.pats.size()), h.bufs.upload(tb.pair_c.data(), tb.pair_c.size()),
-                        h.bufs.upload(tb.pair_pb.data(), tb.pair_pb.size()), h.bufs.upload(tb.pair_pe.data(), tb.pair_pe.size()),
-                        h.bufs.upload(tb.seg.data(), tb.seg.size()), h.bufs.upload(tb.preds.data(), tb.preds.size())};
-    // (what the kernel writes starts as the caller's values: a slot it leaves alone comes back untouched)
-    t.matched = h.bufs.upload(matched_out, (size_t)n_lines); t.vit = h.bufs.upload(vit_out, (size_t)n_lines);
-    t.logprob = h.bufs.upload(logprob_out, (size_t)n_lines); t.free_logprob = h.bufs.upload(free_out, (size_t)n_lines);
-    h.run();
-    DevBufs::download(idx, h.t.idx, (size_t)rows); DevBufs::download(prob, h.t.prob, (size_t)rows);
-    DevBufs::download(matched_out, t.matched, (size_t)n_lines); DevBufs::download(vit_out, t.vit, (size_t)n_lines);
-    DevBufs::download(logprob_out, t.logprob, (size_t)n_lines); DevBufs::download(free_out, t.free_logprob, (size_t)n_lines);
-  });
-}
-
-// Rec keywords' device path on host arrays (ctc_keyword.h); the list tables are built as rt_keywords_create builds them (lx::Tables).
-RT_API int rt_debug_ctc_keywords(rt_session* s, const float* z5, const float* W, const float* bias, int N,
-                                 const int32_t* tokens_per_line, int n_lines, const int32_t* line_kw, const int32_t* entry_ids,
-                                 const int32_t* entry_lens, const int32_t* kw_first_entry, int n_kw, const float* kw_min_score,
-                                 int chunk_rows, float* score_out, int32_t* span_out, rt_keyword_hit* hits_out, int32_t* n_hits_out) {
-  long long rows = 0, table = 0;
-  RT_REQUIRE(s, s, "rt_debug_ctc_keywords: null session");
-  const std::string bad = keywords_args_error(z5, W, N, tokens_per_line, n_lines, line_kw, entry_ids, entry_lens, kw_first_entry, n_kw,
-                                              kw_min_score, hits_out, n_hits_out, &rows, &table);
-  RT_REQUIRE(bad.empty(), s, "rt_debug_ctc_keywords: " + bad);
-  RT_REQUIRE(chunk_rows >= 0, s, "rt_debug_ctc_keywords: chunk_rows is negative");
-  return guarded(s, [&] {
-    const lx::Tables tb = tables_of(entry_ids, entry_lens, kw_first_entry, n_kw);
-    TailHook h(s, z5, W, bias, N, rows, tokens_per_line, n_lines, nullptr, nullptr, 0, chunk_rows, lines_with(n_lines, &RecLineOpts::keywords, line_kw),
-               RecStores{nullptr, nullptr, nullptr, &tb});
-    rt_entry_store X;   // (the tables on the device, freed on every way out)
-    X.set(tb);
-    for (int i = 0; i < n_lines; i++)   // (a line without a list has no hit)
-      if (line_kw[i] <= 0) n_hits_out[i] = 0;
-    rt_session::RecTail::Keywords& t = h.t.keywords;
-    t.d = X.d;
-    t.d_min = h.bufs.upload(kw_min_score, (size_t)n_kw);
-    // (what the kernels write starts as the caller's values: a slot they leave alone comes back untouched)
-    const size_t tn = (size_t)std::max<long long>(table, 1);
-    t.score = h.bufs.alloc<float>(tn); t.span = h.bufs.alloc<int>(2 * tn);
-    if (score_out) DevBufs::put(t.score, score_out, (size_t)table);
-    if (span_out) DevBufs::put(t.span, span_out, 2 * (size_t)table);
-    t.hits = h.bufs.upload(reinterpret_cast<const kw::Hit*>(hits_out), (size_t)n_lines * kw::HITS);
-    t.n = h.bufs.upload(n_hits_out, (size_t)n_lines);
-    h.run();
-    if (score_out) DevBufs::download(score_out, t.score, (size_t)table);
-    if (span_out) DevBufs::download(span_out, t.span, 2 * (size_t)table);
-    DevBufs::download(reinterpret_cast<kw::Hit*>(hits_out), t.hits, (size_t)n_lines * kw::HITS);
-    DevBufs::download(n_hits_out, t.n, (size_t)n_lines);
-  });
-}
-
-// Rec beams' device path on host arrays (ctc_beam.h): every line carries the beam, as in a pipeline call after rt_set_rec_beam.
-RT_API int rt_debug_ctc_beam(rt_session* s, const float* z5, const float* W, const float* bias, int N, const int32_t* tokens_per_line,
-                             int n_lines, int beam, int nbest, int chunk_rows, int32_t* counts_out, rt_beam* beams_out,
-                             int32_t* tokens_out) {
-  long long rows = 0;
-  RT_REQUIRE(s, s, "rt_debug_ctc_beam: null session");
-  const std::string bad = beam_args_error(z5, W, N, tokens_per_line, n_lines, beam, nbest, counts_out, beams_out, tokens_out, &rows);
-  RT_REQUIRE(bad.empty(), s, "rt_debug_ctc_beam: " + bad);
-  RT_REQUIRE(chunk_rows >= 0, s, "rt_debug_ctc_beam: chunk_rows is negative");
-  return guarded(s, [&] {
-    if (beam == 0 || n_lines == 0) return;   // (off, or no line: no launch, no write)
-    TailHook h(s, z5, W, bias, N, rows, tokens_per_line, n_lines, nullptr, nullptr, 0, chunk_rows, std::vector<RecLineOpts>((size_t)n_lines), RecStores{},
-               beam, nbest);
-    rt_session::RecTail::Beam& t = h.t.beam;
-    // (what the kernels write starts as the caller's values: a slot they leave alone comes back untouched)
-    const size_t nt = (size_t)std::max<long long>(rows, 1) * nbest;
-    t.count = h.bufs.upload(counts_out, (size_t)n_lines);
-    t.recs = h.bufs.upload(reinterpret_cast<const bm::Beam*>(beams_out), (size_t)n_lines * nbest);
-    t.tok = h.bufs.alloc<int>(nt);
-    DevBufs::put(t.tok, tokens_out, (size_t)rows * nbest);
-    h.run();
-    DevBufs::download(counts_out, t.count, (size_t)n_lines);
-    DevBufs::download(reinterpret_cast<bm::Beam*>(beams_out), t.recs, (size_t)n_lines * nbest);
-    DevBufs::download(tokens_out, t.tok, (size_t)rows * nbest);
   });
 }
 

@@ -1,5 +1,6 @@
-// What the extern "C" entry points of api.cpp (the library's surface) and api_debug.cpp (the kernel diagnostics) share: the
-// exception guard, the argument-check macro, and the RAII pieces of the diagnostic hooks.  Internal: nothing here is exported.
+// What the extern "C" entry points of api.cpp (the library's surface), api_ctc.cpp (the rec CTC tail's debug entries) and
+// api_debug.cpp (the kernel diagnostics) share: the exception guard, the argument-check macro, and the RAII pieces and ragged
+// layout of the diagnostic hooks.  Internal: nothing here is exported.
 #pragma once
 #include <algorithm>
 #include <new>
@@ -13,43 +14,6 @@ namespace rt {
 
 std::string& create_error();       // the calling thread's message for calls without a session: what rt_last_error(NULL) returns
 void capture_variant_defaults();   // the A/B switches' load-time values (rt_debug_set_variants restores to them)
-// what both rt_debug_ctc_candidates forms require of their arguments; *rows_out = the lines' time steps
-bool cand_args_ok(const float* z5, const float* W, int N, const int32_t* idx, const float* prob, const int32_t* tokens_per_line,
-                  int n_lines, int K, const rt_candidate* cands_out, const int32_t* cols_out, const int32_t* n_tokens_out,
-                  long long* rows_out);
-
-// what both rt_debug_ctc_charset forms require beyond cand_args_ok (K = 0 allowed there: cands / cols may then be NULL)
-bool charset_args_ok(const float* z5, const float* W, int N, const int32_t* idx, const float* prob, const int32_t* tokens_per_line,
-                     int n_lines, const int32_t* line_set, const uint32_t* masks, int n_sets, int K, const int32_t* tokens_out,
-                     const int32_t* n_tokens_out, const float* scores_out, const rt_candidate* cands_out, const int32_t* cols_out,
-                     long long* rows_out);
-
-// what both rt_debug_ctc_lexicon forms require of their arguments: the first requirement that fails, in words, or the empty
-// string; *rows_out = the lines' time steps, *table_out = the floats of the loglik table (one per entry of the lexicon of every
-// line that has one)
-std::string lexicon_args_error(const float* z5, const float* W, int N, const int32_t* tokens_per_line, int n_lines,
-                               const int32_t* line_lex, const int32_t* entry_ids, const int32_t* entry_lens,
-                               const int32_t* lex_first_entry, int n_lex, const rt_lexicon_match* matches_out,
-                               const int32_t* n_matches_out, long long* rows_out, long long* table_out);
-// what both rt_debug_ctc_keywords forms require of their arguments, likewise; *table_out = the entries of the score / span tables
-std::string keywords_args_error(const float* z5, const float* W, int N, const int32_t* tokens_per_line, int n_lines,
-                                const int32_t* line_kw, const int32_t* entry_ids, const int32_t* entry_lens,
-                                const int32_t* kw_first_entry, int n_kw, const float* kw_min_score, const rt_keyword_hit* hits_out,
-                                const int32_t* n_hits_out, long long* rows_out, long long* table_out);
-// what both rt_debug_ctc_beam forms require of their arguments, likewise (beam = 0, off, and n_lines = 0 pass: the entries then
-// do nothing); *rows_out = the lines' time steps
-std::string beam_args_error(const float* z5, const float* W, int N, const int32_t* tokens_per_line, int n_lines, int beam, int nbest,
-                            const int32_t* counts_out, const rt_beam* beams_out, const int32_t* tokens_out, long long* rows_out);
-// what both rt_debug_ctc_lexicon_align forms require beyond lexicon_args_error (n_lex already checked), likewise
-std::string lexicon_align_args_error(const float* lex_min_post, int n_lex, const int32_t* idx, const float* prob,
-                                     const int32_t* snapped_out, const float* vit_out);
-// what both rt_debug_ctc_pattern forms require of their arguments, likewise; rules_out: the n_pat patterns' tables (pt::Rule::build
-// checks the flat compiled tables: pattern k's group_of at [k][N], its delta [S[k]][G[k]] and accept [S[k]] behind pattern k - 1's)
-std::string pattern_args_error(const float* z5, const float* W, int N, const int32_t* tokens_per_line, int n_lines,
-                               const int32_t* line_pat, const int32_t* pat_S, const int32_t* pat_G, const int32_t* group_of,
-                               const int32_t* delta, const int32_t* accept, int n_pat, const int32_t* idx, const float* prob,
-                               const int32_t* matched_out, const float* vit_out, const float* logprob_out, const float* free_out,
-                               long long* rows_out, std::vector<pt::Rule>* rules_out);
 
 // A call that fails after work was enqueued must not leave kernels or H2D copies in flight: the next
 // begin_call() rewinds the pinned staging and the arenas they read.  Errors of the drain itself are dropped
@@ -142,5 +106,28 @@ template <typename T> void put_as(T* dev, const float* src, size_t n) {
   DevBufs::put(dev, h.data(), n);
 }
 template <typename T> T* upload_as(DevBufs& bufs, const float* src, size_t n) { T* d = bufs.alloc<T>(n); put_as(d, src, n); return d; }
+
+// A ragged list of images laid out back to back, as the networks' levels are: each image's offset in pixels, the total, the
+// largest extents.  It accumulates; what an entry accepts (empty, oversized) is the entry's own check, made before.
+struct Ragged {
+  std::vector<ImgGeom> g;
+  long long total = 0, max_pix = 0;
+  int maxH = 0, maxW = 0;
+  Ragged() = default;
+  Ragged(const int* hs, const int* ws, int n) { for (int i = 0; i < n; i++) push(hs[i], ws[i]); }
+  // token lines (or image row counts): one ImgGeom{off, 1, T} each, as SvtrCore passes its token level
+  template <typename I> Ragged(const I* tokens, int n) { for (int i = 0; i < n; i++) push(1, (int)tokens[i]); }
+  void push(int h, int w) {
+    g.push_back(ImgGeom{total, h, w, 0});
+    const long long pix = (long long)h * w;
+    total += pix; max_pix = std::max(max_pix, pix); maxH = std::max(maxH, h); maxW = std::max(maxW, w);
+  }
+  int n() const { return (int)g.size(); }
+  Ragged down(int sh, int sw) const { Ragged r; for (const ImgGeom& i : g) r.push((i.H + sh - 1) / sh, (i.W + sw - 1) / sw); return r; }   // a "same"-padded conv of stride (sh, sw)
+  Ragged up(int k) const { Ragged r; for (const ImgGeom& i : g) r.push(k * i.H, k * i.W); return r; }
+  Ragged pool(int kh, int kw) const { Ragged r; for (const ImgGeom& i : g) r.push(i.H / kh, i.W / kw); return r; }   // window = stride, no padding (pool_level)
+  Ragged flat() const { Ragged r; r.push(1, (int)total); return r; }   // one image of 1 x total pixels
+  const ImgGeom* upload(DevBufs& bufs) const { return bufs.upload(g.data(), g.size()); }
+};
 
 }  // namespace rt

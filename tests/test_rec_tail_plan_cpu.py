@@ -1,6 +1,6 @@
 """The plan of one rec group's CTC tail (retto_amd/csrc/rec_tail_plan.h: rt::rec_tail_plan) on the host: the charset row tables,
 the lexicon lines with their rows and table, and the answers that order the launches (a lexicon line at all, a snap group, z5
-needed).  rec_groups (session.cpp) and the rt_debug_ctc_* hooks (api_debug.cpp) both run rt_session::rec_tail on this plan, so
+needed).  rec_groups (session.cpp) and the rt_debug_ctc_* hooks (api_ctc.cpp) both run rt_session::rec_tail on this plan, so
 what test_gpu_charset.py, test_gpu_lexicon.py and test_gpu_lexicon_align.py certify is what a page runs through.  The expected
 tables are restated here (expected()), from the rules of ctc_charset.h / ctc_lexicon.h / ctc_lexicon_align.h, and a few are
 written out by hand.  Compiled with g++ into tests/native/gemm_plan_driver.cpp (tests/plan_driver.py): no GPU.
