@@ -4,7 +4,8 @@
 // tail's options (rt_debug_ctc_*, both forms, and rt_debug_*_compile) are in api_ctc.cpp, on the host references of
 // ctc_host_ref.h; it also asserts the layouts the rt_results_rec_* accessors here cast between.  The kernel-level diagnostics
 // (rt_debug_set_variants, rt_bench_*, and the rt_debug_* harnesses the kernel tests drive) are in api_debug.cpp; api_internal.h
-// holds what the three share.
+// holds what the three share.  A pipeline entry checks its arguments, makes the call a PageCall (rt_session::call_of) and hands it
+// to the session; rt_destroy releases in one order: lane threads, streams drained, lanes closed, staging, networks, the rest.
 #include <thread>
 #include <sched.h>
 #include <atomic>
@@ -31,6 +32,50 @@ template <class V>
 static const rt_results::Page* page_of_line(const rt_results* r, int page, int line, V rt_results::Page::*per_line) {
   const rt_results::Page* p = RT_PAGE(r, page);
   return p && line >= 0 && (size_t)line < (p->*per_line).size() ? p : nullptr;
+}
+
+// a line's geometry for rt_debug_word_boxes / rt_debug_span_quad: the crop of box8 as plan_crop (session.cpp) derives it; false:
+// an empty crop or a singular homography
+static bool crop_geom(const float* box8, int T, int W, int resized_w, wb::WordGeom& g) {
+  const gm::CropDims cd = gm::crop_dims(box8);
+  if (cd.w <= 0 || cd.h <= 0 || !gm::projection_inverse(box8, cd.cw, cd.ch, g.inv)) return false;
+  g.T = T; g.W = W; g.resized_w = resized_w;
+  g.w_c = cd.rot ? cd.h : cd.w; g.h_c = cd.rot ? cd.w : cd.h;
+  g.rot270 = cd.rot; g.w = cd.w; g.h = cd.h; g.cw = cd.cw; g.ch = cd.ch;
+  return true;
+}
+// The entries without a session report through the caller's buffer: f() under the exception guard, its message into err [err_cap]
+template <typename F>
+static int guarded_into(char* err, size_t err_cap, F f) {
+  try {
+    f();
+    return RT_OK;
+  } catch (const RtError& e) {
+    if (err && err_cap) snprintf(err, err_cap, "%s", e.what());
+    return e.code;
+  } catch (const std::exception& e) {
+    if (err && err_cap) snprintf(err, err_cap, "%s", e.what());
+    return RT_ERR_BACKEND;
+  }
+}
+// The host decode pool: fn(i) for every page i < n on the CPUs this PROCESS may use (affinity mask capped by the cgroup quota -- the
+// GPU box shows 256 logical CPUs to a pod that owns 16), shared among the ranks of the node (LOCAL_WORLD_SIZE: one process per
+// GPU), at most 16 threads.  Rethrows the first failing page's error in page order, like the reference's `?`.
+template <typename F>
+static void decode_pool(int n, F fn) {
+  std::vector<std::exception_ptr> errs((size_t)n);
+  std::atomic<int> next{0};
+  auto work = [&] {
+    for (int i; (i = next.fetch_add(1)) < n;) {
+      try { fn(i); } catch (...) { errs[(size_t)i] = std::current_exception(); }
+    }
+  };
+  const int nt = std::max(1, std::min<int>(n, std::min<int>(16, rt_host_cpu_budget())));
+  std::vector<std::thread> th;
+  for (int t = 1; t < nt; t++) th.emplace_back(work);
+  work();
+  for (auto& t : th) t.join();
+  for (auto& e : errs) if (e) std::rethrow_exception(e);
 }
 
 extern "C" {
@@ -84,23 +129,13 @@ void rt_destroy(rt_session* s) {
   (void)hipSetDevice(s->device);
   for (auto& w : s->workers) w->shutdown();   // lanes finish what was submitted (tickets never waited for are leaked, not raced)
   s->workers.clear();
-  if (s->st) { (void)hipStreamSynchronize(s->st); }
-  for (auto& h : s->helpers) {
-    if (h->st) (void)hipStreamSynchronize(h->st);
-    if (h->d_flags) (void)hipFree(h->d_flags);
-    if (h->ev_block) (void)hipEventDestroy(h->ev_block);
-    if (h->st_part) { rt::forget_stream(h->st_part); (void)hipStreamDestroy(h->st_part); }
-    if (h->st_full) (void)hipStreamDestroy(h->st_full);
-  }
+  quiesce(s);   // every lane's stream drained
+  for (int l = 0; l < s->n_lanes(); l++) s->lane(l)->close();
   s->helpers.clear();
   s->free_stage();
   s->det.reset(); s->cls.reset(); s->rec.reset();
-  if (s->d_flags) (void)hipFree(s->d_flags);
   if (s->d_word_raw) (void)hipFree(s->d_word_raw);
-  if (s->ev_block) (void)hipEventDestroy(s->ev_block);
-  if (s->st_part) { rt::forget_stream(s->st_part); (void)hipStreamDestroy(s->st_part); }
-  if (s->st_full) (void)hipStreamDestroy(s->st_full);
-  delete s;
+  delete s;   // (and with it the rec stores' device tables)
 }
 const char* rt_last_error(const rt_session* s) { return s ? s->last_error.c_str() : create_error().c_str(); }
 const char* rt_version(void) { return "retto_hip 0.1.0 (gfx950)"; }
@@ -193,47 +228,46 @@ int rt_run_batch(rt_session* s, const uint8_t* const* rgb, const int* hs, const 
   RT_REQUIRE(s && out && n_pages >= 0 && (n_pages == 0 || (rgb && hs && ws)), s, "rt_run_batch: bad argument");
   RT_REQUIRE(mem == RT_MEM_HOST || mem == RT_MEM_DEVICE || mem == RT_MEM_HOST_MAPS_DEVICE, s, "rt_run_batch: bad mem kind");
   *out = nullptr;
-  return guarded(s, [&] { *out = s->run_batch(rgb, hs, ws, n_pages, mem, det_map_override); });
+  return guarded(s, [&] { *out = s->run_batch(s->call_of(rgb, hs, ws, n_pages, mem, det_map_override)); });
 }
 int rt_run_batch_stream(rt_session* s, const uint8_t* const* rgb, const int* hs, const int* ws, int n_pages, int mem,
                         const float* const* det_map_override, rt_stage_callback cb, void* user, rt_results** out) {
   RT_REQUIRE(s && out && cb && n_pages >= 0 && (n_pages == 0 || (rgb && hs && ws)), s, "rt_run_batch_stream: bad argument");
   RT_REQUIRE(mem == RT_MEM_HOST || mem == RT_MEM_DEVICE || mem == RT_MEM_HOST_MAPS_DEVICE, s, "rt_run_batch_stream: bad mem kind");
   *out = nullptr;
-  return guarded(s, [&] { *out = s->run_batch(rgb, hs, ws, n_pages, mem, det_map_override, cb, user); });
+  return guarded(s, [&] { *out = s->run_batch(s->call_of(rgb, hs, ws, n_pages, mem, det_map_override, cb, user)); });
 }
-// the five rt_run_regions* forms: `name` is the entry's own, an array it does not take is null
+// the five rt_run_regions* forms: `name` is the entry's own, ids = {charsets, lexicons, patterns, keywords}: an array it does not take is null
 static int run_regions(const char* name, rt_session* s, const uint8_t* const* rgb, const int* hs, const int* ws, int n_pages, int mem,
-                       const float* const* quads, const int* n_quads, const int32_t* const* charsets, const int32_t* const* lexicons,
-                       const int32_t* const* patterns, rt_results** out, const int32_t* const* keywords = nullptr) {
+                       const float* const* quads, const int* n_quads, const int32_t* const* const (&ids)[REC_N_KINDS], rt_results** out) {
   RT_REQUIRE(s && out && n_pages >= 0 && (n_pages == 0 || (rgb && hs && ws && quads && n_quads)), s, std::string(name) + ": bad argument");
   RT_REQUIRE(mem == RT_MEM_HOST || mem == RT_MEM_DEVICE, s, std::string(name) + ": mem must be RT_MEM_HOST or RT_MEM_DEVICE");
   *out = nullptr;
-  return guarded(s, [&] { *out = s->run_regions(rgb, hs, ws, n_pages, mem, quads, n_quads, charsets, lexicons, patterns, keywords); });
+  return guarded(s, [&] { *out = s->run_regions(rgb, hs, ws, n_pages, mem, quads, n_quads, ids); });
 }
 int rt_run_regions(rt_session* s, const uint8_t* const* rgb, const int* hs, const int* ws, int n_pages, int mem,
                    const float* const* quads, const int* n_quads, rt_results** out) {
-  return run_regions("rt_run_regions", s, rgb, hs, ws, n_pages, mem, quads, n_quads, nullptr, nullptr, nullptr, out);
+  return run_regions("rt_run_regions", s, rgb, hs, ws, n_pages, mem, quads, n_quads, {nullptr, nullptr, nullptr, nullptr}, out);
 }
 int rt_run_regions_charsets(rt_session* s, const uint8_t* const* rgb, const int* hs, const int* ws, int n_pages, int mem,
                             const float* const* quads, const int* n_quads, const int32_t* const* charsets, rt_results** out) {
-  return run_regions("rt_run_regions_charsets", s, rgb, hs, ws, n_pages, mem, quads, n_quads, charsets, nullptr, nullptr, out);
+  return run_regions("rt_run_regions_charsets", s, rgb, hs, ws, n_pages, mem, quads, n_quads, {charsets, nullptr, nullptr, nullptr}, out);
 }
 int rt_run_regions_lexicons(rt_session* s, const uint8_t* const* rgb, const int* hs, const int* ws, int n_pages, int mem,
                             const float* const* quads, const int* n_quads, const int32_t* const* charsets,
                             const int32_t* const* lexicons, rt_results** out) {
-  return run_regions("rt_run_regions_lexicons", s, rgb, hs, ws, n_pages, mem, quads, n_quads, charsets, lexicons, nullptr, out);
+  return run_regions("rt_run_regions_lexicons", s, rgb, hs, ws, n_pages, mem, quads, n_quads, {charsets, lexicons, nullptr, nullptr}, out);
 }
 int rt_run_regions_patterns(rt_session* s, const uint8_t* const* rgb, const int* hs, const int* ws, int n_pages, int mem,
                             const float* const* quads, const int* n_quads, const int32_t* const* charsets,
                             const int32_t* const* lexicons, const int32_t* const* patterns, rt_results** out) {
-  return run_regions("rt_run_regions_patterns", s, rgb, hs, ws, n_pages, mem, quads, n_quads, charsets, lexicons, patterns, out);
+  return run_regions("rt_run_regions_patterns", s, rgb, hs, ws, n_pages, mem, quads, n_quads, {charsets, lexicons, patterns, nullptr}, out);
 }
 int rt_run_regions_keywords(rt_session* s, const uint8_t* const* rgb, const int* hs, const int* ws, int n_pages, int mem,
                             const float* const* quads, const int* n_quads, const int32_t* const* charsets,
                             const int32_t* const* lexicons, const int32_t* const* patterns, const int32_t* const* keywords,
                             rt_results** out) {
-  return run_regions("rt_run_regions_keywords", s, rgb, hs, ws, n_pages, mem, quads, n_quads, charsets, lexicons, patterns, out, keywords);
+  return run_regions("rt_run_regions_keywords", s, rgb, hs, ws, n_pages, mem, quads, n_quads, {charsets, lexicons, patterns, keywords}, out);
 }
 // rt_set_rec_charset / _lexicon / _pattern / _keywords: the session default of one kind (rec_line_opts.h)
 static int set_rec_default(rt_session* s, const RecKind& kind, int id) {
@@ -324,7 +358,7 @@ int rt_set_det_tiles(rt_session* s, int tile, int overlap) {
   RT_REQUIRE(s, s, "rt_set_det_tiles: null session");
   return guarded(s, [&] {
     if (const char* why = dt::check_params(tile, overlap)) throw RtError(RT_ERR_INVALID, std::string("rt_set_det_tiles: ") + why);
-    s->det_tile = tile; s->det_overlap = overlap;   // (the helper lanes get it with every call: CallSettings)
+    s->det_tile = tile; s->det_overlap = overlap;
   });
 }
 int rt_det_tiles(const rt_session* s, int* tile, int* overlap) {
@@ -339,7 +373,7 @@ int rt_set_rec_beam(rt_session* s, int beam, int nbest) {
     if (beam == 0) { s->beam_b = s->beam_n = 0; return; }
     if (const char* why = bm::check_params(beam, nbest))
       throw RtError(RT_ERR_INVALID, "rt_set_rec_beam(" + std::to_string(beam) + ", " + std::to_string(nbest) + "): " + why);
-    s->beam_b = beam; s->beam_n = nbest;   // (the helper lanes get it with every call: CallSettings)
+    s->beam_b = beam; s->beam_n = nbest;
   });
 }
 int rt_rec_beam(const rt_session* s, int* beam, int* nbest) {
@@ -352,7 +386,7 @@ int rt_set_rec_windows(rt_session* s, int window, int overlap) {
   RT_REQUIRE(s, s, "rt_set_rec_windows: null session");
   return guarded(s, [&] {
     if (const char* why = rw::check_params(window, overlap)) throw RtError(RT_ERR_INVALID, std::string("rt_set_rec_windows: ") + why);
-    s->rec_window = window; s->rec_overlap = overlap;   // (the helper lanes get it with every call: CallSettings)
+    s->rec_window = window; s->rec_overlap = overlap;
   });
 }
 int rt_rec_windows(const rt_session* s, int* window, int* overlap) {
@@ -413,7 +447,7 @@ int rt_submit_batch(rt_session* s, const uint8_t* const* rgb, const int* hs, con
   RT_REQUIRE(mem == RT_MEM_HOST || mem == RT_MEM_DEVICE || mem == RT_MEM_HOST_MAPS_DEVICE, s, "rt_submit_batch: bad mem kind");
   RT_REQUIRE(s->inflight.load() < RT_MAX_INFLIGHT, s, "rt_submit_batch: too many batches in flight (RT_MAX_INFLIGHT)");
   *out = nullptr;
-  return guarded<true>(s, [&] { *out = s->submit_batch(rgb, hs, ws, n_pages, mem, det_map_override); });
+  return guarded<true>(s, [&] { *out = s->submit_batch(s->call_of(rgb, hs, ws, n_pages, mem, det_map_override)); });
 }
 int rt_wait_batch(rt_session* s, rt_ticket* ticket, rt_results** out) {
   RT_REQUIRE(s && ticket && out, s, "rt_wait_batch: bad argument");
@@ -446,27 +480,20 @@ int rt_decode_image(const void* data, size_t len, uint8_t** rgb, int* h, int* w,
   if (err && err_cap) err[0] = 0;
   if (!data || !rgb || !h || !w) { if (err && err_cap) snprintf(err, err_cap, "rt_decode_image: null argument"); return RT_ERR_INVALID; }
   *rgb = nullptr;
-  try {
+  return guarded_into(err, err_cap, [&] {
     std::vector<uint8_t> px;
     rt::decode_image((const uint8_t*)data, len, &px, h, w);
     uint8_t* p = (uint8_t*)malloc(px.size());
     if (!p) throw RtError(RT_ERR_BACKEND, "out of memory");
     memcpy(p, px.data(), px.size());
     *rgb = p;
-    return RT_OK;
-  } catch (const RtError& e) {
-    if (err && err_cap) snprintf(err, err_cap, "%s", e.what());
-    return e.code;
-  } catch (const std::exception& e) {
-    if (err && err_cap) snprintf(err, err_cap, "%s", e.what());
-    return RT_ERR_BACKEND;
-  }
+  });
 }
 int rt_parse_dictionary(const void* data, size_t len, char** out, size_t* out_len, int* n_entries, char* err, size_t err_cap) {
   if (err && err_cap) err[0] = 0;
   if ((!data && len) || !out || !out_len || !n_entries) { if (err && err_cap) snprintf(err, err_cap, "rt_parse_dictionary: null argument"); return RT_ERR_INVALID; }
   *out = nullptr; *out_len = 0; *n_entries = 0;
-  try {
+  return guarded_into(err, err_cap, [&] {
     std::vector<uint8_t> bytes((const uint8_t*)data, (const uint8_t*)data + len);
     std::vector<std::string> d = rt::load_dictionary(bytes);
     std::string j;
@@ -475,14 +502,7 @@ int rt_parse_dictionary(const void* data, size_t len, char** out, size_t* out_le
     if (!p) throw RtError(RT_ERR_BACKEND, "out of memory");
     memcpy(p, j.data(), j.size()); p[j.size()] = 0;
     *out = p; *out_len = j.size(); *n_entries = (int)d.size();
-    return RT_OK;
-  } catch (const RtError& e) {
-    if (err && err_cap) snprintf(err, err_cap, "%s", e.what());
-    return e.code;
-  } catch (const std::exception& e) {
-    if (err && err_cap) snprintf(err, err_cap, "%s", e.what());
-    return RT_ERR_BACKEND;
-  }
+  });
 }
 int rt_format_f32(float v, char* buf, size_t cap) {
   std::string s = rt_format_f32_impl(v);
@@ -497,49 +517,23 @@ int rt_run_encoded_batch(rt_session* s, const void* const* files, const size_t* 
   return guarded(s, [&] {
     std::vector<std::vector<uint8_t>> px((size_t)n_pages);
     std::vector<int> hs((size_t)n_pages), ws((size_t)n_pages);
-    std::vector<std::exception_ptr> errs((size_t)n_pages);
-    std::atomic<int> next{0};
-    auto work = [&] {
-      for (int i; (i = next.fetch_add(1)) < n_pages;) {
-        try {
-          if (!files[i]) throw RtError(RT_ERR_IMAGE, "image decode: null input");
-          rt::decode_image((const uint8_t*)files[i], lens[i], &px[(size_t)i], &hs[(size_t)i], &ws[(size_t)i]);
-        } catch (...) { errs[(size_t)i] = std::current_exception(); }
-      }
-    };
-    // decode threads: the CPUs this PROCESS may use (affinity mask capped by the cgroup quota -- the GPU box shows 256 logical
-    // CPUs to a pod that owns 16), shared among the ranks of the node (LOCAL_WORLD_SIZE: one process per GPU), at most 16
-    const int nt = std::max(1, std::min<int>(n_pages, std::min<int>(16, rt_host_cpu_budget())));
-    std::vector<std::thread> th;
-    for (int t = 1; t < nt; t++) th.emplace_back(work);
-    work();
-    for (auto& t : th) t.join();
-    for (auto& e : errs) if (e) std::rethrow_exception(e);  // first failing page in page order, like the reference's `?`
+    decode_pool(n_pages, [&](int i) {
+      if (!files[i]) throw RtError(RT_ERR_IMAGE, "image decode: null input");
+      rt::decode_image((const uint8_t*)files[i], lens[i], &px[(size_t)i], &hs[(size_t)i], &ws[(size_t)i]);
+    });
     std::vector<const uint8_t*> ptrs((size_t)n_pages);
     for (int i = 0; i < n_pages; i++) ptrs[(size_t)i] = px[(size_t)i].data();
-    *out = s->run_batch(ptrs.data(), hs.data(), ws.data(), n_pages, RT_MEM_HOST, nullptr, cb, user);
+    *out = s->run_batch(s->call_of(ptrs.data(), hs.data(), ws.data(), n_pages, RT_MEM_HOST, nullptr, cb, user));
   });
 }
 // The host stage of the device decode path: every page parsed and entropy-decoded (JPEG) or decoded (anything else) on the
-// same thread pool as rt_run_encoded_batch; the first failing page in page order is reported.
+// decode pool
 static std::vector<rt::EncodedPage> host_stage(const void* const* files, const size_t* lens, int n_pages) {
   std::vector<rt::EncodedPage> enc((size_t)n_pages);
-  std::vector<std::exception_ptr> errs((size_t)n_pages);
-  std::atomic<int> next{0};
-  auto work = [&] {
-    for (int i; (i = next.fetch_add(1)) < n_pages;) {
-      try {
-        if (!files[i]) throw RtError(RT_ERR_IMAGE, "image decode: null input");
-        rt::decode_for_device((const uint8_t*)files[i], lens[i], &enc[(size_t)i]);
-      } catch (...) { errs[(size_t)i] = std::current_exception(); }
-    }
-  };
-  const int nt = std::max(1, std::min<int>(n_pages, std::min<int>(16, rt_host_cpu_budget())));
-  std::vector<std::thread> th;
-  for (int t = 1; t < nt; t++) th.emplace_back(work);
-  work();
-  for (auto& t : th) t.join();
-  for (auto& e : errs) if (e) std::rethrow_exception(e);
+  decode_pool(n_pages, [&](int i) {
+    if (!files[i]) throw RtError(RT_ERR_IMAGE, "image decode: null input");
+    rt::decode_for_device((const uint8_t*)files[i], lens[i], &enc[(size_t)i]);
+  });
   return enc;
 }
 int rt_submit_encoded_batch(rt_session* s, const void* const* files, const size_t* lens, int n_pages, rt_ticket** out) {
@@ -551,7 +545,7 @@ int rt_submit_encoded_batch(rt_session* s, const void* const* files, const size_
     std::vector<const uint8_t*> rgb((size_t)n_pages, nullptr);
     std::vector<int> hs((size_t)n_pages), ws((size_t)n_pages);
     for (int i = 0; i < n_pages; i++) { hs[(size_t)i] = enc[(size_t)i].h; ws[(size_t)i] = enc[(size_t)i].w; }
-    *out = s->submit_batch(rgb.data(), hs.data(), ws.data(), n_pages, RT_MEM_HOST, nullptr, nullptr, nullptr, &enc);
+    *out = s->submit_batch(s->call_of(rgb.data(), hs.data(), ws.data(), n_pages, RT_MEM_HOST), &enc);
   });
 }
 int rt_decode_batch(rt_session* s, const void* const* files, const size_t* lens, int n, int* hs, int* ws, uint8_t* const* out,
@@ -581,7 +575,7 @@ int rt_debug_jpeg_reconstruct(const void* data, size_t len, uint8_t** rgb, int* 
   if (err && err_cap) err[0] = 0;
   if (!data || !rgb || !h || !w || !on_device) { if (err && err_cap) snprintf(err, err_cap, "rt_debug_jpeg_reconstruct: null argument"); return RT_ERR_INVALID; }
   *rgb = nullptr;
-  try {
+  return guarded_into(err, err_cap, [&] {
     rt::EncodedPage e;
     rt::decode_for_device((const uint8_t*)data, len, &e);
     if (e.on_device) rt::reconstruct_host(e.jpeg, &e.rgb);
@@ -589,14 +583,7 @@ int rt_debug_jpeg_reconstruct(const void* data, size_t len, uint8_t** rgb, int* 
     if (!p) throw RtError(RT_ERR_BACKEND, "out of memory");
     memcpy(p, e.rgb.data(), e.rgb.size());
     *rgb = p; *h = e.h; *w = e.w; *on_device = e.on_device ? 1 : 0;
-    return RT_OK;
-  } catch (const RtError& e) {
-    if (err && err_cap) snprintf(err, err_cap, "%s", e.what());
-    return e.code;
-  } catch (const std::exception& e) {
-    if (err && err_cap) snprintf(err, err_cap, "%s", e.what());
-    return RT_ERR_BACKEND;
-  }
+  });
 }
 void rt_results_free(rt_results* r) { delete r; }
 int rt_results_pages(const rt_results* r) { return r ? (int)r->pages.size() : 0; }
@@ -647,14 +634,8 @@ int rt_debug_word_boxes(const void* dict, size_t dict_len, const int32_t* tokens
       if (tokens[k] < 0 || (size_t)tokens[k] >= d.size()) return RT_ERR_INVALID;
       if (cols[k] < 0 || cols[k] >= T || (k > 0 && cols[k] <= cols[k - 1])) return RT_ERR_INVALID;
     }
-    // the crop as plan_crops (session.cpp) derives it
-    const gm::CropDims cd = gm::crop_dims(box8_after);
-    if (cd.w <= 0 || cd.h <= 0) return RT_ERR_IMAGE;
     wb::WordGeom g;
-    if (!gm::projection_inverse(box8_after, cd.cw, cd.ch, g.inv)) return RT_ERR_IMAGE;
-    g.T = T; g.W = W; g.resized_w = resized_w;
-    g.w_c = cd.rot ? cd.h : cd.w; g.h_c = cd.rot ? cd.w : cd.h;
-    g.rot270 = cd.rot; g.w = cd.w; g.h = cd.h; g.cw = cd.cw; g.ch = cd.ch;
+    if (!crop_geom(box8_after, T, W, resized_w, g)) return RT_ERR_IMAGE;
     wb::Word* o = reinterpret_cast<wb::Word*>(out);
     const int nw = wb::line_words(raw.data(), tokens, cols, n, g, rot180 ? 1 : 0, o);
     for (int j = 0; j < nw; j++) gm::scale_and_clip(o[j].quad, (double)after_w, (double)after_h, (double)ori_w, (double)ori_h);
@@ -721,14 +702,8 @@ int rt_debug_span_quad(int T, int W, int resized_w, const float* box8_after, int
   if (!box8_after || !quad8_out || T <= 0 || W <= 0 || resized_w <= 0 || after_w <= 0 || after_h <= 0 || ori_w <= 0 || ori_h <= 0)
     return RT_ERR_INVALID;
   if (first_col < 0 || last_col < first_col || last_col >= T) return RT_ERR_INVALID;
-  // the crop as plan_crops (session.cpp) derives it, as rt_debug_word_boxes
-  const gm::CropDims cd = gm::crop_dims(box8_after);
-  if (cd.w <= 0 || cd.h <= 0) return RT_ERR_IMAGE;
   wb::WordGeom g;
-  if (!gm::projection_inverse(box8_after, cd.cw, cd.ch, g.inv)) return RT_ERR_IMAGE;
-  g.T = T; g.W = W; g.resized_w = resized_w;
-  g.w_c = cd.rot ? cd.h : cd.w; g.h_c = cd.rot ? cd.w : cd.h;
-  g.rot270 = cd.rot; g.w = cd.w; g.h = cd.h; g.cw = cd.cw; g.ch = cd.ch;
+  if (!crop_geom(box8_after, T, W, resized_w, g)) return RT_ERR_IMAGE;
   kw::span_quad(first_col, last_col, g, rot180 ? 1 : 0, quad8_out);
   gm::scale_and_clip(quad8_out, (double)after_w, (double)after_h, (double)ori_w, (double)ori_h);
   return RT_OK;
@@ -768,13 +743,12 @@ int rt_profile_enable(rt_session* s, int on) {
   RT_REQUIRE(s, s, "rt_profile_enable: null session");
   return guarded(s, [&] {
     const int mode = on == 2 ? 2 : (on != 0 ? 1 : 0);   // 2: the enclosing network scopes only
-    s->prof.clear(); s->prof.on = mode;
-    for (auto& h : s->helpers) { h->prof.clear(); h->prof.on = mode; }
+    for (int l = 0; l < s->n_lanes(); l++) { s->lane(l)->prof.clear(); s->lane(l)->prof.on = mode; }
   });
 }
 int rt_profile_get(rt_session* s, const char* const** names, const float** ms, const int** calls, int* n) {
   RT_REQUIRE(s && names && ms && calls && n, s, "rt_profile_get: null argument");
-  for (auto& h : s->helpers) s->prof.merge(h->prof);
+  for (int l = 1; l < s->n_lanes(); l++) s->prof.merge(s->lane(l)->prof);
   *names = s->prof.names.data(); *ms = s->prof.ms.data(); *calls = s->prof.calls.data(); *n = (int)s->prof.names.size();
   return RT_OK;
 }
@@ -782,20 +756,13 @@ int rt_profile_get(rt_session* s, const char* const** names, const float** ms, c
 int rt_onnx_to_rtwb(int which, const void* onnx, size_t len, void** out, size_t* out_len, char* err, size_t err_cap) {
   if (err && err_cap) err[0] = 0;
   if (!onnx || !len || !out || !out_len) { if (err && err_cap) snprintf(err, err_cap, "rt_onnx_to_rtwb: null argument"); return RT_ERR_INVALID; }
-  try {
+  return guarded_into(err, err_cap, [&] {
     std::vector<uint8_t> b = rt::onnx_to_rtwb(which, (const uint8_t*)onnx, len);
     void* p = malloc(b.size());
     if (!p) throw RtError(RT_ERR_BACKEND, "out of memory");
     memcpy(p, b.data(), b.size());
     *out = p; *out_len = b.size();
-    return RT_OK;
-  } catch (const RtError& e) {
-    if (err && err_cap) snprintf(err, err_cap, "%s", e.what());
-    return e.code;
-  } catch (const std::exception& e) {
-    if (err && err_cap) snprintf(err, err_cap, "%s", e.what());
-    return RT_ERR_BACKEND;
-  }
+  });
 }
 void rt_buffer_free(void* p) { free(p); }
 size_t rt_model_manifest(int which, char* buf, size_t cap) {

@@ -1,6 +1,7 @@
 // What the extern "C" entry points of api.cpp (the library's surface), api_ctc.cpp (the rec CTC tail's debug entries) and
-// api_debug.cpp (the kernel diagnostics) share: the exception guard, the argument-check macro, and the RAII pieces and ragged
-// layout of the diagnostic hooks.  Internal: nothing here is exported.
+// api_debug.cpp (the kernel diagnostics) share: the exception guard with the drain of every lane's stream, the argument-check
+// macro, and the RAII pieces and ragged layout of the diagnostic hooks.  The hooks take the session where they mean lane 0
+// (rt_session is an rt_lane).  Internal: nothing here is exported.
 #pragma once
 #include <algorithm>
 #include <new>
@@ -21,9 +22,8 @@ void capture_variant_defaults();   // the A/B switches' load-time values (rt_deb
 inline void quiesce(rt_session* s) {
   if (!s) return;
   (void)hipSetDevice(s->device);
-  if (s->st) (void)hipStreamSynchronize(s->st);
-  for (auto& h : s->helpers)
-    if (h->st) (void)hipStreamSynchronize(h->st);
+  for (int l = 0; l < s->n_lanes(); l++)
+    if (s->lane(l)->st) (void)hipStreamSynchronize(s->lane(l)->st);
   (void)hipGetLastError();
 }
 // ALLOW_INFLIGHT: only rt_submit_batch / rt_wait_batch may run while submitted batches are in flight -- every other entry point

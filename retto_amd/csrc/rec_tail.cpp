@@ -1,5 +1,5 @@
 // The rec network's CTC tail and what feeds it: the dictionary, charset and lexicon text compilers, the session's charset and
-// lexicon stores, the pattern pass (ctc_pattern.h), and rt_session::rec_tail -- the one launch sequence behind the net that the
+// lexicon stores, the pattern pass (ctc_pattern.h), and rt_lane::rec_tail -- the one launch sequence behind the net that the
 // pipeline (session.cpp rec_groups) and the debug hooks (api_debug.cpp rt_debug_ctc_*) both run, on the tables of rec_tail_plan.h.
 #include "session.h"
 
@@ -175,7 +175,7 @@ void compile_lexicon(const std::vector<std::string>& dict, const char* utf8, siz
 namespace {
 // a table of the plan through pinned staging into the scratch arena (an empty one gets one element and no copy)
 template <typename T>
-T* staged(rt_session& s, const std::vector<T>& v) {
+T* staged(rt_lane& s, const std::vector<T>& v) {
   const size_t n = std::max<size_t>(v.size(), 1);
   T* h = s.pinned.alloc<T>(n); T* d = s.scratch.alloc<T>(n);
   if (v.empty()) return d;
@@ -183,12 +183,12 @@ T* staged(rt_session& s, const std::vector<T>& v) {
   RT_HIP_CHECK(hipMemcpyAsync(d, h, v.size() * sizeof(T), hipMemcpyHostToDevice, s.st));
   return d;
 }
-int chunk_rows_of(const rt_session::RecTail& t) { return t.chunk_rows > 0 ? t.chunk_rows : cc::CAND_CHUNK; }
+int chunk_rows_of(const rt_lane::RecTail& t) { return t.chunk_rows > 0 ? t.chunk_rows : cc::CAND_CHUNK; }
 // The logits recompute every kind shares: up to `cap` rows of z5 gathered into zc, then the CTC FC -> logits [cap][ld].  Stream
 // order lets a consumer's chunks share the two buffers.
 struct LogitsChunk {
-  rt_session& s; const SvtrCore& core; const float* z5; int ld; float *zc, *logits;
-  LogitsChunk(rt_session& s_, const SvtrCore& core_, const float* z5_, int cap) : s(s_), core(core_), z5(z5_), ld(round_up(core_.classes, 4)) {
+  rt_lane& s; const SvtrCore& core; const float* z5; int ld; float *zc, *logits;
+  LogitsChunk(rt_lane& s_, const SvtrCore& core_, const float* z5_, int cap) : s(s_), core(core_), z5(z5_), ld(round_up(core_.classes, 4)) {
     const size_t zc_n = ((size_t)cap + 256) * core.D;   // (zero rows past the chunk: a GEMM tile's loads stay inside the allocation)
     zc = s.scratch.alloc<float>(zc_n); logits = s.scratch.alloc<float>((size_t)cap * ld);
     RT_HIP_CHECK(hipMemsetAsync(zc, 0, zc_n * sizeof(float), s.st));
@@ -223,11 +223,11 @@ std::vector<Chunk> line_chunks(const std::vector<Line>& lines, int chunk, int& c
 enum { ROW_LSE = 1, ROW_MAX = 2 };
 template <typename Line>
 struct LinePass {
-  rt_session& s;
+  rt_lane& s;
   const Line* d_lines; const int* d_rows;
   int cap; std::vector<Chunk> chunks;
   LogitsChunk lc; float *lse, *rmax;
-  LinePass(rt_session& s_, const SvtrCore& core, const rt_session::RecTail& t, const std::vector<Line>& lines, const std::vector<int>& rows, int stats)
+  LinePass(rt_lane& s_, const SvtrCore& core, const rt_lane::RecTail& t, const std::vector<Line>& lines, const std::vector<int>& rows, int stats)
       : s(s_), d_lines(staged(s_, lines)), d_rows(staged(s_, rows)), cap(1), chunks(line_chunks(lines, chunk_rows_of(t), cap)),
         lc(s_, core, t.z5, cap), lse(stats & ROW_LSE ? s_.scratch.alloc<float>((size_t)cap) : nullptr),
         rmax(stats & ROW_MAX ? s_.scratch.alloc<float>((size_t)cap) : nullptr) {}
@@ -254,7 +254,7 @@ void upload_table(const T** d, const std::vector<T>& v) {
 }
 }  // namespace
 
-void rt_session::rec_tail(const RecTailPlan& p, const SvtrCore& core, const RecTail& t) {
+void rt_lane::rec_tail(const RecTailPlan& p, const SvtrCore& core, const RecTail& t) {
   const int* d_row_set = nullptr;
   if (!p.crows.empty()) {
     d_row_set = staged(*this, p.row_set);
@@ -268,7 +268,7 @@ void rt_session::rec_tail(const RecTailPlan& p, const SvtrCore& core, const RecT
     pp::WordLineDesc* dw = scratch.alloc<pp::WordLineDesc>(t.n_lines);
     RT_HIP_CHECK(hipMemcpyAsync(dw, t.wb->h_lines, (size_t)t.n_lines * sizeof(pp::WordLineDesc), hipMemcpyHostToDevice, st));
     ProfScope ps(&prof, st, "word_boxes");
-    pp::word_boxes(st, t.idx, t.tok, t.ntok, t.wb->label, t.wb->cscore, cfg.cls_thresh, d_word_raw, dw, t.n_lines, t.wb->cols,
+    pp::word_boxes(st, t.idx, t.tok, t.ntok, t.wb->label, t.wb->cscore, sh->cfg.cls_thresh, sh->d_word_raw, dw, t.n_lines, t.wb->cols,
                    t.wb->n_words, t.wb->words);
   }
   if (!p.snap && p.has_lex()) ctc_lexicon(p, core, t);
@@ -277,7 +277,7 @@ void rt_session::rec_tail(const RecTailPlan& p, const SvtrCore& core, const RecT
   if (t.cand.k > 0) ctc_candidates(core, t, p.rows, d_row_set);   // (before the caller rewinds the scratch arena z5 lives in)
 }
 
-void rt_session::ctc_candidates(const SvtrCore& core, const RecTail& t, long long rows, const int* d_row_set) {
+void rt_lane::ctc_candidates(const SvtrCore& core, const RecTail& t, long long rows, const int* d_row_set) {
   const int K = t.cand.k;
   if (t.n_lines <= 0 || rows <= 0) return;
   int *kept_row = nullptr, *kept_slot = nullptr, *d_kept = nullptr;
@@ -302,7 +302,7 @@ void rt_session::ctc_candidates(const SvtrCore& core, const RecTail& t, long lon
   }
 }
 
-void rt_session::ctc_charset(const SvtrCore& core, const RecTail& t, const int* d_rows, int n_rows, const int* d_row_set) {
+void rt_lane::ctc_charset(const SvtrCore& core, const RecTail& t, const int* d_rows, int n_rows, const int* d_row_set) {
   if (n_rows <= 0) return;
   const int chunk = chunk_rows_of(t);
   LogitsChunk lc(*this, core, t.z5, std::min(chunk, n_rows));
@@ -314,7 +314,7 @@ void rt_session::ctc_charset(const SvtrCore& core, const RecTail& t, const int* 
   }
 }
 
-void rt_session::ctc_lexicon(const RecTailPlan& p, const SvtrCore& core, const RecTail& t) {
+void rt_lane::ctc_lexicon(const RecTailPlan& p, const SvtrCore& core, const RecTail& t) {
   const RecTail::Lexicon& o = t.lexicon;
   LinePass<lx::Line> pass(*this, core, t, p.lines, p.lrows, ROW_LSE);
   const LogitsChunk& lc = pass.lc;
@@ -338,7 +338,7 @@ void rt_session::ctc_lexicon(const RecTailPlan& p, const SvtrCore& core, const R
   }
 }
 
-void rt_session::ctc_pattern(const RecTailPlan& p, const SvtrCore& core, const RecTail& t) {
+void rt_lane::ctc_pattern(const RecTailPlan& p, const SvtrCore& core, const RecTail& t) {
   const RecTail::Pattern& o = t.pattern;
   LinePass<pt::Line> pass(*this, core, t, p.plines, p.prows, ROW_LSE | ROW_MAX);
   const LogitsChunk& lc = pass.lc;
@@ -351,7 +351,7 @@ void rt_session::ctc_pattern(const RecTailPlan& p, const SvtrCore& core, const R
   });
 }
 
-void rt_session::ctc_keywords(const RecTailPlan& p, const SvtrCore& core, const RecTail& t) {
+void rt_lane::ctc_keywords(const RecTailPlan& p, const SvtrCore& core, const RecTail& t) {
   const RecTail::Keywords& o = t.keywords;
   LinePass<kw::Line> pass(*this, core, t, p.klines, p.krows, ROW_MAX);
   const LogitsChunk& lc = pass.lc;
@@ -366,7 +366,7 @@ void rt_session::ctc_keywords(const RecTailPlan& p, const SvtrCore& core, const 
   pp::ctc_keyword_topk(st, pass.d_lines, (int)p.klines.size(), o.d.lex, o.d_min, score, span, o.hits, o.n);
 }
 
-void rt_session::ctc_beams(const RecTailPlan& p, const SvtrCore& core, const RecTail& t) {
+void rt_lane::ctc_beams(const RecTailPlan& p, const SvtrCore& core, const RecTail& t) {
   const RecTail::Beam& o = t.beam;
   LinePass<bm::Line> pass(*this, core, t, p.blines, p.brows, ROW_LSE);
   const LogitsChunk& lc = pass.lc;

@@ -1,3 +1,7 @@
+// Session construction (rt_session_create, rt_lane::open / close), the lane's stage-level entries (the networks and the
+// pre / post stages on host arrays), the page pipeline (rt_lane::run_pages: one function per stage over the call's Pipeline),
+// the results and their stage JSON, and the two debug entries that run a pipeline stage on its own.  How calls reach the lanes
+// is session_batch.cpp.
 #include "session.h"
 
 #include <charconv>
@@ -50,8 +54,7 @@ rt_session* rt_session_create(const rt_config* cfg) {
   Blob br = Blob::from_source(cfg->rec.path, cfg->rec.data, cfg->rec.len, "rec", MODEL_REC);
   std::vector<uint8_t> dict = read_source_bytes(cfg->dict.path, cfg->dict.data, cfg->dict.len, "dict");
   s->cfg.det = s->cfg.cls = s->cfg.rec = s->cfg.dict = rt_model_source{nullptr, nullptr, 0};
-  RT_HIP_CHECK(hipStreamCreateWithFlags(&s->st_full, hipStreamNonBlocking));
-  s->st = s->st_full;
+  s->open(s.get());
   // which graph a source holds is read off its tensor names; rt_config.dtype picks the arithmetic
   const bool f16 = cfg->dtype == RT_DTYPE_F16;
   const bool sdet = blob_is_server_det(bd), srec = blob_is_server_rec(br);
@@ -62,16 +65,13 @@ rt_session* rt_session_create(const rt_config* cfg) {
   if (srec) s->rec.reset(new RecServerH(br)); else if (f16) s->rec.reset(new RecNetH(br)); else s->rec.reset(new RecNet(br));
   s->model_info = std::string(s->det->arch()) + "/" + s->det->dtype() + " " + s->cls->dtype() + " " + s->rec->arch() + "/" + s->rec->dtype();
   s->dict = rt::load_dictionary(dict);
-  s->charsets = std::make_shared<rt_charsets>();
-  s->lexicons = std::make_shared<rt_lexicons>();
-  s->patterns = std::make_shared<rt_patterns>();
-  s->keywords = std::make_shared<rt_keywords>();
+  s->charsets.reset(new rt_charsets());
+  s->lexicons.reset(new rt_lexicons());
+  s->patterns.reset(new rt_patterns());
+  s->keywords.reset(new rt_keywords());
   if ((int)s->dict.size() != s->rec->classes())
     throw RtError(RT_ERR_SHAPE, "dictionary has " + std::to_string(s->dict.size()) + " entries but the rec head has " +
                                     std::to_string(s->rec->classes()) + " classes");
-  RT_HIP_CHECK(hipMalloc((void**)&s->d_flags, 64));
-  RT_HIP_CHECK(hipMemset(s->d_flags, 0, 64));
-  RT_HIP_CHECK(hipEventCreateWithFlags(&s->ev_block, hipEventBlockingSync | hipEventDisableTiming));
   if (cfg->rec_return_word_box) {   // the class table of k_word_boxes, once per session
     std::vector<uint8_t> raw(s->dict.size());
     for (size_t i = 0; i < raw.size(); i++) raw[i] = rt::wb::raw_class(s->dict[i].data(), s->dict[i].size());
@@ -80,17 +80,8 @@ rt_session* rt_session_create(const rt_config* cfg) {
   }
   const int lanes = cfg->lanes > 0 ? cfg->lanes : 3;  // measured on C3: 1 -> 640, 2 -> 681, 3 -> 700, 4 -> 652 images/s
   for (int l = 1; l < lanes; l++) {
-    std::unique_ptr<rt_session> h(new rt_session());
-    h->cfg = s->cfg; h->device = s->device;
-    h->det = s->det; h->cls = s->cls; h->rec = s->rec; h->dict = s->dict; h->model_info = s->model_info;
-    h->d_word_raw = s->d_word_raw; h->charsets = s->charsets; h->lexicons = s->lexicons; h->patterns = s->patterns;
-    h->keywords = s->keywords;
-    RT_HIP_CHECK(hipStreamCreateWithFlags(&h->st_full, hipStreamNonBlocking));
-    h->st = h->st_full;
-    RT_HIP_CHECK(hipMalloc((void**)&h->d_flags, 64));
-    RT_HIP_CHECK(hipMemset(h->d_flags, 0, 64));
-    RT_HIP_CHECK(hipEventCreateWithFlags(&h->ev_block, hipEventBlockingSync | hipEventDisableTiming));
-    s->helpers.push_back(std::move(h));
+    s->helpers.emplace_back(new rt_lane());
+    s->helpers.back()->open(s.get());
   }
   // CU partitions (RT_LANE_CUMASK=1, A/B only): every lane of a multi-lane session gets its own slice of every XCD.  Measured
   // slower than whole-device streams on C3 (runtime.h "CU partitions"), so the default keeps the lanes time-slicing the chip.
@@ -105,10 +96,7 @@ rt_session* rt_session_create(const rt_config* cfg) {
       for (int b = a + 1; b < lanes && ok; b++)
         for (unsigned v : ids[(size_t)a]) if (std::find(ids[(size_t)b].begin(), ids[(size_t)b].end(), v) != ids[(size_t)b].end()) { ok = false; break; }
     if (ok) {
-      for (int l = 0; l < lanes; l++) {
-        rt_session* ln = l == 0 ? s.get() : s->helpers[(size_t)l - 1].get();
-        ln->st_part = ps[(size_t)l]; ln->part_cus = pc[(size_t)l];
-      }
+      for (int l = 0; l < lanes; l++) { s->lane(l)->st_part = ps[(size_t)l]; s->lane(l)->part_cus = pc[(size_t)l]; }
     } else {
       for (hipStream_t p : ps) if (p) { rt::forget_stream(p); (void)hipStreamDestroy(p); }
       if (getenv("RT_TRACE")) fprintf(stderr, "[rt] CU partitions could not be verified on this device: lanes keep whole-device streams\n");
@@ -117,8 +105,24 @@ rt_session* rt_session_create(const rt_config* cfg) {
   return s.release();
 }
 
-void rt_session::begin_call() {
-  RT_HIP_CHECK(hipSetDevice(device));
+void rt_lane::open(const rt_session* session) {
+  sh = session;
+  RT_HIP_CHECK(hipStreamCreateWithFlags(&st_full, hipStreamNonBlocking));
+  st = st_full;
+  RT_HIP_CHECK(hipMalloc((void**)&d_flags, 64));
+  RT_HIP_CHECK(hipMemset(d_flags, 0, 64));
+  RT_HIP_CHECK(hipEventCreateWithFlags(&ev_block, hipEventBlockingSync | hipEventDisableTiming));
+}
+void rt_lane::close() {
+  if (d_flags) (void)hipFree(d_flags);
+  if (ev_block) (void)hipEventDestroy(ev_block);
+  if (st_part) { rt::forget_stream(st_part); (void)hipStreamDestroy(st_part); }
+  if (st_full) (void)hipStreamDestroy(st_full);
+  d_flags = nullptr; ev_block = nullptr; st = st_full = st_part = nullptr;
+}
+
+void rt_lane::begin_call() {
+  RT_HIP_CHECK(hipSetDevice(sh->device));
   (void)hipGetLastError();   // HIP's last error is sticky per host thread: a failure of the PREVIOUS call on this thread (a refused
                              // hipMalloc, say) must not be what the first RT_LAUNCH of this call reports
   if (failed) { arena.abandon_pass(); scratch.abandon_pass(); dbws.abandon_pass(); failed = false; }
@@ -132,7 +136,7 @@ void rt_session::begin_call() {
 // wait that ends within ~50 us -- single pages, metadata copies -- pays no sleep / wake-up), then polled every 100 us with the
 // thread asleep in between.  RT_SYNC_SPIN=1 restores hipStreamSynchronize.
 static const bool g_sync_spin = getenv("RT_SYNC_SPIN") && atoi(getenv("RT_SYNC_SPIN")) != 0;
-void rt_session::sync() {
+void rt_lane::sync() {
   if (g_sync_spin || !ev_block) {
     RT_HIP_CHECK(hipStreamSynchronize(st));
   } else {
@@ -151,7 +155,7 @@ void rt_session::sync() {
   }
   if (prof.on) prof.collect();
 }
-void rt_session::check_flags() {
+void rt_lane::check_flags() {
   int f[2] = {0, 0};
   RT_HIP_CHECK(hipMemcpy(f, d_flags, sizeof(f), hipMemcpyDeviceToHost));
   if (f[0]) {
@@ -167,48 +171,57 @@ static std::vector<std::pair<int, int>> uniform_hw(int n, int h, int w) {
 // ---------------------------------------------------------------------------
 // L1 worker functions
 // ---------------------------------------------------------------------------
-void rt_session::det_forward(const float* nchw, int n, int h, int w, float* out) {
-  begin_call();
+// n images of [3, h, w] (host, NCHW) into the arena as the networks read them: NHWC pitch-4
+static float* upload_nchw(rt_lane& s, const float* nchw, int n, int h, int w) {
   size_t ne = (size_t)n * 3 * h * w;
-  float* d_in = arena.alloc<float>(ne);
-  RT_HIP_CHECK(hipMemcpyAsync(d_in, nchw, ne * 4, hipMemcpyHostToDevice, st));
-  float* x = arena.alloc<float>((size_t)n * h * w * 4);
-  nn::nchw3_to_nhwc4(st, d_in, n, h, w, x);
+  float* d_in = s.arena.alloc<float>(ne);
+  RT_HIP_CHECK(hipMemcpyAsync(d_in, nchw, ne * 4, hipMemcpyHostToDevice, s.st));
+  float* x = s.arena.alloc<float>((size_t)n * h * w * 4);
+  nn::nchw3_to_nhwc4(s.st, d_in, n, h, w, x);
+  return x;
+}
+// ... n lines of [3, h, widths[i]], concatenated (ne floats in all)
+static float* upload_ragged(rt_lane& s, const float* nchw, size_t ne, int n, int h, const int* widths) {
+  float* d_in = s.arena.alloc<float>(ne);
+  RT_HIP_CHECK(hipMemcpyAsync(d_in, nchw, ne * 4, hipMemcpyHostToDevice, s.st));
+  float* x = s.arena.alloc<float>(ne / 3 * 4);
+  size_t off = 0;
+  for (int i = 0; i < n; i++) {
+    nn::nchw3_to_nhwc4(s.st, d_in + off * 3, 1, h, widths[i], x + off * 4);
+    off += (size_t)h * widths[i];
+  }
+  return x;
+}
+void rt_lane::det_forward(const float* nchw, int n, int h, int w, float* out) {
+  begin_call();
+  float* x = upload_nchw(*this, nchw, n, h, w);
   Level L0 = make_level(uniform_hw(n, h, w));
   RunCtx c = ctx(&scratch);
-  float* map = det->run(c, x, L0);
+  float* map = sh->det->run(c, x, L0);
   RT_HIP_CHECK(hipMemcpyAsync(out, map, (size_t)n * h * w * 4, hipMemcpyDeviceToHost, st));
   sync();
 }
-void rt_session::cls_forward(const float* nchw, int n, int h, int w, float* out) {
+void rt_lane::cls_forward(const float* nchw, int n, int h, int w, float* out) {
   begin_call();
-  size_t ne = (size_t)n * 3 * h * w;
-  float* d_in = arena.alloc<float>(ne);
-  RT_HIP_CHECK(hipMemcpyAsync(d_in, nchw, ne * 4, hipMemcpyHostToDevice, st));
-  float* x = arena.alloc<float>((size_t)n * h * w * 4);
-  nn::nchw3_to_nhwc4(st, d_in, n, h, w, x);
+  float* x = upload_nchw(*this, nchw, n, h, w);
   Level L0 = make_level(uniform_hw(n, h, w));
   RunCtx c = ctx(&scratch);
-  float* probs = cls->run(c, x, L0);
+  float* probs = sh->cls->run(c, x, L0);
   RT_HIP_CHECK(hipMemcpyAsync(out, probs, (size_t)n * 2 * 4, hipMemcpyDeviceToHost, st));
   sync();
 }
-void rt_session::rec_forward(const float* nchw, int n, int h, int w, float* out, int* t_out) {
+void rt_lane::rec_forward(const float* nchw, int n, int h, int w, float* out, int* t_out) {
   int T = RecNet::tokens_for_width(w);
   if (t_out) *t_out = T;
   if (!out) return;
   begin_call();
-  size_t ne = (size_t)n * 3 * h * w;
-  float* d_in = arena.alloc<float>(ne);
-  RT_HIP_CHECK(hipMemcpyAsync(d_in, nchw, ne * 4, hipMemcpyHostToDevice, st));
-  float* x = arena.alloc<float>((size_t)n * h * w * 4);
-  nn::nchw3_to_nhwc4(st, d_in, n, h, w, x);
+  float* x = upload_nchw(*this, nchw, n, h, w);
   Level L0 = make_level(uniform_hw(n, h, w)), Lt;
   RunCtx c = ctx(&scratch);
-  float* logits = rec->run(c, x, L0, Lt);
-  const int C = rec->classes();
+  float* logits = sh->rec->run(c, x, L0, Lt);
+  const int C = sh->rec->classes();
   float* probs = scratch.alloc<float>((size_t)Lt.total * C);
-  nn::softmax_rows(st, logits, rec->logits_ld(), Lt.total, C, probs);
+  nn::softmax_rows(st, logits, sh->rec->logits_ld(), Lt.total, C, probs);
   RT_HIP_CHECK(hipMemcpyAsync(out, probs, (size_t)Lt.total * C * 4, hipMemcpyDeviceToHost, st));
   sync();
 }
@@ -216,7 +229,7 @@ void rt_session::rec_forward(const float* nchw, int n, int h, int w, float* out,
 // Ragged form of rec_forward: line i is [3,48,widths[i]] (NCHW, lines concatenated), every line keeps its own width inside ONE
 // launch series -- what rt_run_batch's rec groups do (rec_processor.rs:214-270 gives each batch of 6 its width; the session
 // concatenates the batches).  out = the lines' [T_i, classes] probabilities concatenated, t_out[i] = T_i.
-void rt_session::rec_forward_ragged(const float* nchw, int n, const int* widths, float* out, int* t_out) {
+void rt_lane::rec_forward_ragged(const float* nchw, int n, const int* widths, float* out, int* t_out) {
   const int h = 48;
   size_t ne = 0, nt = 0;
   for (int i = 0; i < n; i++) {
@@ -228,23 +241,16 @@ void rt_session::rec_forward_ragged(const float* nchw, int n, const int* widths,
   }
   if (!out) return;
   begin_call();
-  float* d_in = arena.alloc<float>(ne);
-  RT_HIP_CHECK(hipMemcpyAsync(d_in, nchw, ne * 4, hipMemcpyHostToDevice, st));
-  float* x = arena.alloc<float>(ne / 3 * 4);
+  float* x = upload_ragged(*this, nchw, ne, n, h, widths);
   std::vector<std::pair<int, int>> hw;
-  size_t off = 0;
-  for (int i = 0; i < n; i++) {
-    nn::nchw3_to_nhwc4(st, d_in + off * 3, 1, h, widths[i], x + off * 4);
-    off += (size_t)h * widths[i];
-    hw.emplace_back(h, widths[i]);
-  }
+  for (int i = 0; i < n; i++) hw.emplace_back(h, widths[i]);
   Level L0 = make_level(hw), Lt;
   RunCtx c = ctx(&scratch);
-  float* logits = rec->run(c, x, L0, Lt);
+  float* logits = sh->rec->run(c, x, L0, Lt);
   if ((size_t)Lt.total != nt) throw RtError(RT_ERR_BACKEND, "rt_rec_ragged: token count mismatch");
-  const int C = rec->classes();
+  const int C = sh->rec->classes();
   float* probs = scratch.alloc<float>((size_t)Lt.total * C);
-  nn::softmax_rows(st, logits, rec->logits_ld(), Lt.total, C, probs);
+  nn::softmax_rows(st, logits, sh->rec->logits_ld(), Lt.total, C, probs);
   RT_HIP_CHECK(hipMemcpyAsync(out, probs, (size_t)Lt.total * C * 4, hipMemcpyDeviceToHost, st));
   sync();
 }
@@ -253,9 +259,9 @@ void rt_session::rec_forward_ragged(const float* nchw, int n, const int* widths,
 // stage functions
 // ---------------------------------------------------------------------------
 // image_helper.rs:106-148 on a device image; returns the (possibly new) device buffer
-static const uint8_t* dev_resize_both(rt_session* s, const uint8_t* img, int h, int w, int* oh, int* ow) {
+static const uint8_t* dev_resize_both(rt_lane* s, const uint8_t* img, int h, int w, int* oh, int* ow) {
   int plan[4];
-  int n = gm::resize_both_plan(h, w, s->cfg.max_side_len, s->cfg.min_side_len, plan);
+  int n = gm::resize_both_plan(h, w, s->sh->cfg.max_side_len, s->sh->cfg.min_side_len, plan);
   const uint8_t* cur = img; int ch = h, cw = w;
   for (int i = 0; i < n; i++) {
     int nh = plan[2 * i], nw = plan[2 * i + 1];
@@ -268,7 +274,7 @@ static const uint8_t* dev_resize_both(rt_session* s, const uint8_t* img, int h, 
   return cur;
 }
 
-void rt_session::resize_both(const uint8_t* rgb, int h, int w, uint8_t* out, int oh, int ow) {
+void rt_lane::resize_both(const uint8_t* rgb, int h, int w, uint8_t* out, int oh, int ow) {
   begin_call();
   uint8_t* d = arena.alloc<uint8_t>((size_t)h * w * 3);
   RT_HIP_CHECK(hipMemcpyAsync(d, rgb, (size_t)h * w * 3, hipMemcpyHostToDevice, st));
@@ -279,17 +285,17 @@ void rt_session::resize_both(const uint8_t* rgb, int h, int w, uint8_t* out, int
   sync(); check_flags();
 }
 
-void rt_session::det_preprocess(const uint8_t* rgb, int h, int w, float* out) {
+void rt_lane::det_preprocess(const uint8_t* rgb, int h, int w, float* out) {
   begin_call();
   uint8_t* d = arena.alloc<uint8_t>((size_t)h * w * 3);
   RT_HIP_CHECK(hipMemcpyAsync(d, rgb, (size_t)h * w * 3, hipMemcpyHostToDevice, st));
   int dh, dw;
-  gm::resize_either_dims(h, w, cfg.det_limit_type, cfg.det_limit_side_len, &dh, &dw);
+  gm::resize_either_dims(h, w, sh->cfg.det_limit_type, sh->cfg.det_limit_side_len, &dh, &dw);
   if (dh <= 0 || dw <= 0) throw RtError(RT_ERR_SHAPE, "det input collapses to zero size");
   uint8_t* r = arena.alloc<uint8_t>((size_t)dh * dw * 3);
   pp::thumbnail_rgb8(st, d, h, w, r, dh, dw, d_flags);
   float* o = arena.alloc<float>((size_t)dh * dw * 3);
-  pp::det_normalize(st, r, dh, dw, cfg.det_scale, cfg.det_mean, cfg.det_std, 1, o);
+  pp::det_normalize(st, r, dh, dw, sh->cfg.det_scale, sh->cfg.det_mean, sh->cfg.det_std, 1, o);
   RT_HIP_CHECK(hipMemcpyAsync(out, o, (size_t)dh * dw * 3 * 4, hipMemcpyDeviceToHost, st));
   sync(); check_flags();
 }
@@ -305,24 +311,24 @@ static int max_boxes_of(const rt_config& c) { return c.max_boxes_per_page > 0 ? 
 
 // a5 (det_processor.rs:279-335) enqueued for n pages with shared launches: page i's boxes go to boxes[i * max_boxes_of ...],
 // its count and overflow flag to counts[2 i], counts[2 i + 1]
-static void db_post_enqueue(rt_session& s, int n, const pp::DbPageIn* in, pp::DbBox* boxes, int* counts) {
-  const int mb = max_boxes_of(s.cfg);
+static void db_post_enqueue(rt_lane& s, int n, const pp::DbPageIn* in, pp::DbBox* boxes, int* counts) {
+  const int mb = max_boxes_of(s.sh->cfg);
   std::vector<void*> wsp((size_t)n); std::vector<pp::DbBox*> bo((size_t)n); std::vector<int*> co((size_t)n);
   for (int i = 0; i < n; i++) {
-    wsp[i] = s.dbws.alloc_bytes(pp::db_workspace_bytes(in[i].H, in[i].W, mb, s.cfg.det_score_mode));
+    wsp[i] = s.dbws.alloc_bytes(pp::db_workspace_bytes(in[i].H, in[i].W, mb, s.sh->cfg.det_score_mode));
     bo[i] = boxes + (size_t)i * mb; co[i] = counts + 2 * i;
   }
   void* hd = s.pinned.alloc_bytes((size_t)n * pp::db_page_desc_bytes());
   void* dd = s.arena.alloc_bytes((size_t)n * pp::db_page_desc_bytes());
-  pp::db_postprocess_batch(s.st, n, in, db_params(s.cfg), wsp.data(), mb, bo.data(), co.data(), hd, dd);
+  pp::db_postprocess_batch(s.st, n, in, db_params(s.sh->cfg), wsp.data(), mb, bo.data(), co.data(), hd, dd);
 }
 
-void rt_session::det_postprocess(const float* pred, int h, int w, int ori_h, int ori_w, float* boxes, float* scores,
+void rt_lane::det_postprocess(const float* pred, int h, int w, int ori_h, int ori_w, float* boxes, float* scores,
                                  int max_out, int* n_out) {
   begin_call();
   float* d = arena.alloc<float>((size_t)h * w);
   RT_HIP_CHECK(hipMemcpyAsync(d, pred, (size_t)h * w * 4, hipMemcpyHostToDevice, st));
-  pp::DbBox* db = arena.alloc<pp::DbBox>(max_boxes_of(cfg));
+  pp::DbBox* db = arena.alloc<pp::DbBox>(max_boxes_of(sh->cfg));
   int* cnt = arena.alloc<int>(2);
   const pp::DbPageIn in{d, h, w, ori_h, ori_w};
   db_post_enqueue(*this, 1, &in, db, cnt);
@@ -366,7 +372,7 @@ static void plan_crop(CropPlan& plan, const uint8_t* src, int sh, int sw, const 
 // a6: the plan's descriptors and crop refs to the device through pinned staging, then every crop warped into one pool (returned;
 // *d_refs: the refs on the device, what cls_post_rotate reads).  The plan holds at least one crop.  flat: the launch walks the
 // flat pixel list (crops of very different sizes: original-page crops, caller-supplied regions) instead of one grid row per crop.
-static uint8_t* warp_planned_crops(rt_session& s, const CropPlan& plan, pp::CropRef** d_refs, bool flat) {
+static uint8_t* warp_planned_crops(rt_lane& s, const CropPlan& plan, pp::CropRef** d_refs, bool flat) {
   const int n = (int)plan.descs.size();
   uint8_t* pool = s.arena.alloc<uint8_t>(plan.pool_bytes + 64);
   pp::CropDesc* d_desc = s.arena.alloc<pp::CropDesc>(n);
@@ -383,7 +389,7 @@ static uint8_t* warp_planned_crops(rt_session& s, const CropPlan& plan, pp::Crop
   return pool;
 }
 
-void rt_session::crop_images(const uint8_t* rgb, int h, int w, const float* boxes, int n, uint8_t* out, size_t out_cap, int form) {
+void rt_lane::crop_images(const uint8_t* rgb, int h, int w, const float* boxes, int n, uint8_t* out, size_t out_cap, int form) {
   begin_call();
   uint8_t* d = arena.alloc<uint8_t>((size_t)h * w * 3);
   RT_HIP_CHECK(hipMemcpyAsync(d, rgb, (size_t)h * w * 3, hipMemcpyHostToDevice, st));
@@ -410,7 +416,7 @@ static pp::LineDesc line_desc(const pp::CropRef& r, int ori_h, int ori_w, int im
   return pp::LineDesc{r.off, r.h, r.w, gm::resize_norm_resized_w(img_h, W, ori_h, ori_w), W, 0};
 }
 
-void rt_session::resize_norm_image(const uint8_t* crop, int h, int w, int ori_h, int ori_w, int img_h, int img_w,
+void rt_lane::resize_norm_image(const uint8_t* crop, int h, int w, int ori_h, int ori_w, int img_h, int img_w,
                                    float ratio, float* out) {
   begin_call();
   uint8_t* d = arena.alloc<uint8_t>(std::max<size_t>((size_t)h * w * 3, 4));
@@ -426,7 +432,7 @@ void rt_session::resize_norm_image(const uint8_t* crop, int h, int w, int ori_h,
   sync(); check_flags();
 }
 
-void rt_session::ctc_decode(const float* probs, int n, int t, int c, int32_t* idx, float* prob, int32_t* tokens,
+void rt_lane::ctc_decode(const float* probs, int n, int t, int c, int32_t* idx, float* prob, int32_t* tokens,
                             int32_t* n_tokens, float* scores) {
   begin_call();
   size_t rows = (size_t)n * t;
@@ -500,6 +506,39 @@ std::string fnum(float v) {
   return o;
 }
 
+// RettoWorkerStageResult JSON (serde derive shapes; retto-wasm/fe/index.ts:5-42)
+std::string stage_json(const rt_results::Page& P, int stage) {
+  std::ostringstream o;
+  size_t n = P.det_scores.size();
+  if (stage == 0) {
+    o << "[";
+    for (size_t k = 0; k < n; k++) {
+      if (k) o << ",";
+      o << "{\"boxes\":{\"inner\":[";
+      for (int q = 0; q < 4; q++) { if (q) o << ","; o << "{\"x\":" << fnum(P.boxes[8 * k + 2 * q]) << ",\"y\":" << fnum(P.boxes[8 * k + 2 * q + 1]) << "}"; }
+      o << "]},\"score\":" << fnum(P.det_scores[k]) << "}";
+    }
+    o << "]";
+  } else if (stage == 1) {
+    o << "[";
+    for (size_t k = 0; k < n; k++) { if (k) o << ","; o << "{\"label\":{\"label\":" << P.cls_labels[k] << ",\"score\":" << fnum(P.cls_scores[k]) << "}}"; }
+    o << "]";
+  } else {
+    o << "[";
+    for (size_t k = 0; k < n; k++) { if (k) o << ","; o << "{\"text\":\"" << json_escape(P.text[k]) << "\",\"score\":" << fnum(P.rec_scores[k]) << "}"; }
+    o << "]";
+  }
+  return o.str();
+}
+// run_stream: page `page` of the call has completed `stage` -- its JSON to the call's callback, under the call's mutex
+void emit_stage(const PageCall& call, int page, int stage, const rt_results::Page& P) {
+  if (!call.cb) return;
+  const std::string j = stage_json(P, stage);
+  std::unique_lock<std::mutex> lk;
+  if (call.cb_mu) lk = std::unique_lock<std::mutex>(*call.cb_mu);
+  call.cb(call.user, call.page_base + page, stage, j.c_str());
+}
+
 // ---------------------------------------------------------------------------
 // L2: process_pipeline over a batch of pages, one function per stage over the call's state
 // ---------------------------------------------------------------------------
@@ -522,18 +561,16 @@ struct LineMeta {
 template <typename T>
 struct Mirror {
   T* d = nullptr; T* h = nullptr; size_t n = 0;
-  void alloc(rt_session& s, size_t n_) { n = n_; d = s.arena.alloc<T>(n); h = s.pinned.alloc<T>(n); }
+  void alloc(rt_lane& s, size_t n_) { n = n_; d = s.arena.alloc<T>(n); h = s.pinned.alloc<T>(n); }
   void fetch(hipStream_t st) const { if (d) RT_HIP_CHECK(hipMemcpyAsync(h, d, n * sizeof(T), hipMemcpyDeviceToHost, st)); }
 };
 // the state of one run_pages call; device and pinned buffers live until the next begin_call
 struct Pipeline {
-  int n_pages, mem; const float* const* det_map_override;
+  const PageCall& call;
   std::vector<PageState> pg;
-  const rt_session::Regions* regions = nullptr;   // rt_run_regions: the boxes are the caller's, in original-page coordinates
-  std::vector<pp::DbBox> region_boxes;            // ... as the stages read them (score 1)
+  std::vector<pp::DbBox> region_boxes;            // rt_run_regions: the caller's boxes as the stages read them (score 1)
   bool crop_original = false;                     // crops are planned on PageState::raw (regions, or crop_source = Original)
   std::vector<double*> sum_parts; std::vector<int> sum_counts;   // det map checksum partials per det group or page map (device)
-  int det_tile = 0, det_overlap = 0;        // det tiles (det_tiles.h) of this call; 0 = off
   float* tile_maps_out = nullptr;           // rt_debug_det_tiles: host, every tile's own map packed in plan order (one-page call)
   int* d_counts = nullptr;                  // [n_pages][2]: box count, overflow flag
   pp::DbBox* d_boxes_packed = nullptr;      // every page's boxes, packed in page order
@@ -558,11 +595,9 @@ struct Pipeline {
   // rec keywords (ctc_keyword.h; any.keywords): per line kw::HITS hit slots and the number of hits (written for the lines that
   // carry a list only)
   Mirror<kw::Hit> kwh; Mirror<int> kwn;
-  // rec beams (ctc_beam.h) of this call; beam_b = 0: off.  Per line its count and beam_n records; the token pool: line li's
-  // hypothesis k at [(tok_off[li] * beam_n) + k * T]
-  int beam_b = 0, beam_n = 0;
+  // rec beams (ctc_beam.h; call.set.beam_b > 0).  Per line its count and beam_n records; the token pool: line li's hypothesis k
+  // at [(tok_off[li] * beam_n) + k * T]
   Mirror<int> bmn; Mirror<bm::Beam> bmrec; Mirror<int> bmtok;
-  int rec_window = 0, rec_overlap = 0;      // rec windows (rec_windows.h) of this call; 0 = off
 };
 
 // Launch groups: items [g0, end) where the group always takes its first item; with max_items > 0 it takes up to max_items items,
@@ -588,34 +623,36 @@ void page_boxes(const PageState& p, rt_results::Page& P, bool regions) {
   }
 }
 // page i of the call in HBM: the caller's device pointer, or an upload
-const uint8_t* page_on_device(rt_session& s, const Pipeline& P, const uint8_t* const* rgb, const int* hs, const int* ws, int i) {
+const uint8_t* page_on_device(rt_lane& s, const PageCall& c, int i) {
+  const uint8_t* const* rgb = c.rgb; const int* hs = c.hs; const int* ws = c.ws;
   if (hs[i] <= 0 || ws[i] <= 0 || rgb[i] == nullptr) throw RtError(RT_ERR_IMAGE, "empty page");
-  if (P.mem != RT_MEM_HOST && P.mem != RT_MEM_HOST_MAPS_DEVICE) return rgb[i];
+  if (c.mem != RT_MEM_HOST && c.mem != RT_MEM_HOST_MAPS_DEVICE) return rgb[i];
   // the pages cross PCIe here (a submitted batch staged them already)
   uint8_t* d = s.arena.alloc<uint8_t>((size_t)hs[i] * ws[i] * 3);
   RT_HIP_CHECK(hipMemcpyAsync(d, rgb[i], (size_t)hs[i] * ws[i] * 3, hipMemcpyHostToDevice, s.st));
   return d;
 }
 // ---- a2 + a3: size limits, det resize (the normalise is folded into the det stem) ----
-void page_sizes(rt_session& s, Pipeline& P, const uint8_t* const* rgb, const int* hs, const int* ws) {
+void page_sizes(rt_lane& s, Pipeline& P) {
+  const int* hs = P.call.hs; const int* ws = P.call.ws;
   // a det input beyond what DB post-processing indexes (det_tiles.h "The largest det input") is refused before anything is queued
-  for (int i = 0; i < P.n_pages; i++) {
+  for (int i = 0; i < P.call.n_pages; i++) {
     if (hs[i] <= 0 || ws[i] <= 0) continue;   // (an empty page: page_on_device reports it)
     int plan[4], ah = hs[i], aw = ws[i], dh = 0, dw = 0;
-    const int n = gm::resize_both_plan(hs[i], ws[i], s.cfg.max_side_len, s.cfg.min_side_len, plan);
+    const int n = gm::resize_both_plan(hs[i], ws[i], s.sh->cfg.max_side_len, s.sh->cfg.min_side_len, plan);
     if (n > 0) { ah = plan[2 * (n - 1)]; aw = plan[2 * (n - 1) + 1]; }
     if (ah <= 0 || aw <= 0) continue;
-    gm::resize_either_dims(ah, aw, s.cfg.det_limit_type, s.cfg.det_limit_side_len, &dh, &dw);
+    gm::resize_either_dims(ah, aw, s.sh->cfg.det_limit_type, s.sh->cfg.det_limit_side_len, &dh, &dw);
     std::string why;
     if (dh > 0 && dw > 0 && dt::check_page(dh, dw, &why) == dt::ERR_CAPACITY) throw RtError(RT_ERR_CAPACITY, "page " + std::to_string(i) + ": " + why);
   }
-  for (int i = 0; i < P.n_pages; i++) {
+  for (int i = 0; i < P.call.n_pages; i++) {
     PageState& p = P.pg[i];
     p.ori_h = hs[i]; p.ori_w = ws[i];
-    const uint8_t* raw = p.raw = page_on_device(s, P, rgb, hs, ws, i);
+    const uint8_t* raw = p.raw = page_on_device(s, P.call, i);
     p.img = dev_resize_both(&s, raw, hs[i], ws[i], &p.after_h, &p.after_w);
     if (p.after_h <= 0 || p.after_w <= 0) throw RtError(RT_ERR_SHAPE, "page collapses to zero size in resize_both");
-    gm::resize_either_dims(p.after_h, p.after_w, s.cfg.det_limit_type, s.cfg.det_limit_side_len, &p.det_h, &p.det_w);
+    gm::resize_either_dims(p.after_h, p.after_w, s.sh->cfg.det_limit_type, s.sh->cfg.det_limit_side_len, &p.det_h, &p.det_w);
     if (p.det_h <= 0 || p.det_w <= 0) throw RtError(RT_ERR_SHAPE, "det input collapses to zero size");
     if (p.det_h == p.after_h && p.det_w == p.after_w) p.det_img = p.img;  // thumbnail at ratio 1 is the identity
     else {
@@ -634,13 +671,13 @@ void page_sizes(rt_session& s, Pipeline& P, const uint8_t* const* rgb, const int
 // written into the page maps (k_det_tile_stitch), before the next group rewinds the scratch arena.  Without a tiled page in the
 // call every group is what it was before tiles existed: the same launches, the same bits.
 struct DetUnit { int page, ty, tx, h, w; };   // ty < 0: the whole page
-void det_groups(rt_session& s, Pipeline& P) {
+void det_groups(rt_lane& s, Pipeline& P) {
   const long long group_px = (long long)32 * 960 * 960;  // measured: larger launch groups win (launch-bound small layers)
-  const int T = P.det_tile, O = P.det_overlap;
+  const int T = P.call.set.det_tile, O = P.call.set.det_overlap;
   std::vector<DetUnit> units;
-  std::vector<dt::Axis> rows((size_t)P.n_pages), cols((size_t)P.n_pages);
-  std::vector<float*> page_map((size_t)P.n_pages, nullptr);
-  for (int i = 0; i < P.n_pages; i++) {
+  std::vector<dt::Axis> rows((size_t)P.call.n_pages), cols((size_t)P.call.n_pages);
+  std::vector<float*> page_map((size_t)P.call.n_pages, nullptr);
+  for (int i = 0; i < P.call.n_pages; i++) {
     const PageState& p = P.pg[i];
     if (!dt::page_tiled(p.det_h, p.det_w, T)) { units.push_back(DetUnit{i, -1, -1, p.det_h, p.det_w}); continue; }
     rows[(size_t)i] = dt::axis_plan(p.det_h, T, O); cols[(size_t)i] = dt::axis_plan(p.det_w, T, O);
@@ -648,9 +685,16 @@ void det_groups(rt_session& s, Pipeline& P) {
     for (int ty = 0; ty < rows[(size_t)i].n(); ty++)
       for (int tx = 0; tx < cols[(size_t)i].n(); tx++) units.push_back(DetUnit{i, ty, tx, rows[(size_t)i].len, cols[(size_t)i].len});
   }
+  // a map's checksum partials (device): they ride home with the box counts
+  const auto checksum = [&](const float* m, long long px) {
+    const int nb = pp::sum_blocks(px);
+    double* parts = s.arena.alloc<double>(nb);
+    pp::sum_partial(s.st, m, px, parts);
+    P.sum_parts.push_back(parts); P.sum_counts.push_back(nb);
+  };
   const int nu = (int)units.size();
   for (int g0 = 0; g0 < nu;) {
-    const int g1 = group_end(g0, nu, s.cfg.det_sub_batch, group_px, [&](int i) { return (long long)units[(size_t)i].h * units[(size_t)i].w; });
+    const int g1 = group_end(g0, nu, s.sh->cfg.det_sub_batch, group_px, [&](int i) { return (long long)units[(size_t)i].h * units[(size_t)i].w; });
     const int gn = g1 - g0;
     std::vector<std::pair<int, int>> hw;
     int nt = 0;
@@ -697,7 +741,7 @@ void det_groups(rt_session& s, Pipeline& P) {
     RT_HIP_CHECK(hipMemcpyAsync(dd, hd, (size_t)gn * sizeof(nn::U8Page), hipMemcpyHostToDevice, s.st));
     RunCtx c = s.ctx(&s.scratch);
     float* map;
-    { ProfOuter po(&s.prof, s.st, "net/det"); map = s.det->run_u8(c, dd, s.cfg.det_scale, s.cfg.det_mean, s.cfg.det_std, L0); }
+    { ProfOuter po(&s.prof, s.st, "net/det"); map = s.sh->det->run_u8(c, dd, s.sh->cfg.det_scale, s.sh->cfg.det_mean, s.sh->cfg.det_std, L0); }
     if (nt == 0) {
       // keep the maps beyond the next group's scratch rewind; the last group's map is consumed by the DB post-processing
       // (same stream) before the classifier reuses the scratch arena, so it stays where the network left it
@@ -707,10 +751,7 @@ void det_groups(rt_session& s, Pipeline& P) {
         RT_HIP_CHECK(hipMemcpyAsync(keep, map, (size_t)L0.total * 4, hipMemcpyDeviceToDevice, s.st));
       }
       for (int i = g0; i < g1; i++) P.pg[units[(size_t)i].page].map = keep + L0.h[i - g0].off;
-      int nb = pp::sum_blocks(L0.total);
-      double* parts = s.arena.alloc<double>(nb);
-      pp::sum_partial(s.st, keep, L0.total, parts);
-      P.sum_parts.push_back(parts); P.sum_counts.push_back(nb);
+      checksum(keep, L0.total);
     } else {
       { ProfScope ps(&s.prof, s.st, "det_tile_stitch");
         pp::det_tile_stitch(s.st, d_tiles, nt, max_tile_pix, map); }
@@ -730,27 +771,20 @@ void det_groups(rt_session& s, Pipeline& P) {
           m = keep;
         }
         P.pg[u.page].map = m;
-        int nb = pp::sum_blocks(px);
-        double* parts = s.arena.alloc<double>(nb);
-        pp::sum_partial(s.st, m, px, parts);
-        P.sum_parts.push_back(parts); P.sum_counts.push_back(nb);
+        checksum(m, px);
       }
     }
     g0 = g1;
   }
   // the checksum is taken over the page maps: a tiled page's stitched map, never its tiles
-  for (int i = 0; i < P.n_pages; i++) {
+  for (int i = 0; i < P.call.n_pages; i++) {
     if (!page_map[(size_t)i]) continue;
-    const long long px = (long long)P.pg[i].det_h * P.pg[i].det_w;
-    int nb = pp::sum_blocks(px);
-    double* parts = s.arena.alloc<double>(nb);
-    pp::sum_partial(s.st, page_map[(size_t)i], px, parts);
-    P.sum_parts.push_back(parts); P.sum_counts.push_back(nb);
+    checksum(page_map[(size_t)i], (long long)P.pg[i].det_h * P.pg[i].det_w);
   }
 }
 // ---- a5: DB post-processing of every page (on device; stream-ordered workspace reuse) ----
-void db_post(rt_session& s, Pipeline& P) {
-  const int n = P.n_pages, mb = max_boxes_of(s.cfg);
+void db_post(rt_lane& s, Pipeline& P) {
+  const int n = P.call.n_pages, mb = max_boxes_of(s.sh->cfg);
   // box lists and counts of all pages are contiguous: one pack launch + two copies bring them to the host
   pp::DbBox* d_boxes = s.arena.alloc<pp::DbBox>((size_t)mb * n);
   P.d_counts = s.arena.alloc<int>((size_t)2 * n);
@@ -759,12 +793,12 @@ void db_post(rt_session& s, Pipeline& P) {
   for (int i = 0; i < n; i++) {
     const PageState& p = P.pg[i];
     const float* pred = p.map;
-    if (P.det_map_override && P.det_map_override[i]) {
-      if (P.mem == RT_MEM_HOST || P.mem == RT_MEM_STAGED_MAPS_HOST) {
+    if (P.call.det_map_override && P.call.det_map_override[i]) {
+      if (P.call.mem == RT_MEM_HOST || P.call.mem == RT_MEM_STAGED_MAPS_HOST) {
         float* d = s.arena.alloc<float>((size_t)p.det_h * p.det_w);
-        RT_HIP_CHECK(hipMemcpyAsync(d, P.det_map_override[i], (size_t)p.det_h * p.det_w * 4, hipMemcpyHostToDevice, s.st));
+        RT_HIP_CHECK(hipMemcpyAsync(d, P.call.det_map_override[i], (size_t)p.det_h * p.det_w * 4, hipMemcpyHostToDevice, s.st));
         pred = d;
-      } else pred = P.det_map_override[i];
+      } else pred = P.call.det_map_override[i];
     }
     in[i] = pp::DbPageIn{pred, p.det_h, p.det_w, p.after_h, p.after_w};
   }
@@ -773,8 +807,8 @@ void db_post(rt_session& s, Pipeline& P) {
   pp::pack_boxes(s.st, n, d_boxes, P.d_counts, mb, P.d_boxes_packed);
 }
 // ---- metadata round trip #1: box lists (a few KB per page); pixels and tensors stay on the device ----
-void box_round_trip(rt_session& s, Pipeline& P, rt_results& res) {
-  const int n = P.n_pages;
+void box_round_trip(rt_lane& s, Pipeline& P, rt_results& res) {
+  const int n = P.call.n_pages;
   int* h_counts = s.pinned.alloc<int>((size_t)2 * n);
   RT_HIP_CHECK(hipMemcpyAsync(h_counts, P.d_counts, (size_t)2 * n * sizeof(int), hipMemcpyDeviceToHost, s.st));
   // (the map checksum partials ride to pinned memory with the box counts)
@@ -788,7 +822,7 @@ void box_round_trip(rt_session& s, Pipeline& P, rt_results& res) {
   for (int i = 0; i < n; i++) {
     if (h_counts[2 * i + 1]) throw RtError(RT_ERR_CAPACITY, "DB post-processing work list overflow (raise max_boxes_per_page)");
     PageState& p = P.pg[i];
-    p.n_boxes = std::min(std::max(h_counts[2 * i], 0), max_boxes_of(s.cfg)); p.first_line = total_lines; total_lines += p.n_boxes;
+    p.n_boxes = std::min(std::max(h_counts[2 * i], 0), max_boxes_of(s.sh->cfg)); p.first_line = total_lines; total_lines += p.n_boxes;
   }
   if (total_lines > 0) {
     pp::DbBox* h_boxes = s.pinned.alloc<pp::DbBox>((size_t)total_lines);
@@ -800,24 +834,25 @@ void box_round_trip(rt_session& s, Pipeline& P, rt_results& res) {
     for (int i = 0; i < P.sum_counts[g]; i++) res.det_checksum += h_sum[g][i];
   P.NL = total_lines; P.NLp = std::max(total_lines, 1);
   P.tok_off.assign((size_t)P.NL + 1, 0);
-  if (s.stage_cb)  // run_stream: the Det stage is complete here (session.rs:98)
-    for (int i = 0; i < n; i++) { rt_results::Page page; page_boxes(P.pg[i], page, false); s.emit_stage(i, 0, page); }
+  if (P.call.cb)  // run_stream: the Det stage is complete here (session.rs:98)
+    for (int i = 0; i < n; i++) { rt_results::Page page; page_boxes(P.pg[i], page, false); emit_stage(P.call, i, 0, page); }
 }
 // ---- rt_run_regions: instead of a2 .. a5 and round trip #1 -- the pages as they are, the boxes from the caller ----
-void region_pages(rt_session& s, Pipeline& P, const uint8_t* const* rgb, const int* hs, const int* ws) {
+void region_pages(rt_lane& s, Pipeline& P) {
+  const PageCall& c = P.call;
   int total_lines = 0;
-  for (int i = 0; i < P.n_pages; i++) total_lines += P.regions->n_quads[i];
+  for (int i = 0; i < c.n_pages; i++) total_lines += c.n_quads[i];
   P.region_boxes.resize((size_t)total_lines);
   total_lines = 0;
-  for (int i = 0; i < P.n_pages; i++) {
+  for (int i = 0; i < P.call.n_pages; i++) {
     PageState& p = P.pg[i];
-    p.ori_h = p.after_h = hs[i]; p.ori_w = p.after_w = ws[i]; p.det_h = p.det_w = 0;
-    p.n_boxes = P.regions->n_quads[i]; p.first_line = total_lines;
-    p.raw = p.img = p.n_boxes > 0 ? page_on_device(s, P, rgb, hs, ws, i) : nullptr;   // (a page without regions is never read)
+    p.ori_h = p.after_h = c.hs[i]; p.ori_w = p.after_w = c.ws[i]; p.det_h = p.det_w = 0;
+    p.n_boxes = c.n_quads[i]; p.first_line = total_lines;
+    p.raw = p.img = p.n_boxes > 0 ? page_on_device(s, c, i) : nullptr;   // (a page without regions is never read)
     p.det_img = nullptr; p.map = nullptr;
     for (int k = 0; k < p.n_boxes; k++) {
       pp::DbBox& b = P.region_boxes[(size_t)total_lines + k];
-      memcpy(b.pts, P.regions->quads[i] + 8 * k, 32); b.score = 1.0f; b.key = 0;
+      memcpy(b.pts, c.quads[i] + 8 * k, 32); b.score = 1.0f; b.key = 0;
     }
     p.boxes = P.region_boxes.data() + total_lines;
     total_lines += p.n_boxes;
@@ -829,14 +864,14 @@ void region_pages(rt_session& s, Pipeline& P, const uint8_t* const* rgb, const i
 // Resized (the reference): box k in after-resize_both coordinates, cut from the resized page.  Original / regions: the quad the
 // results report (page_boxes: after scale_and_clip, or the caller's clamped quad), cut from the caller's page; everything
 // downstream reads the plan, so the crop size, rotate270, the homography and the cls / rec ordering follow that quad.
-void crop_stage(rt_session& s, Pipeline& P) {
+void crop_stage(rt_lane& s, Pipeline& P) {
   for (const PageState& p : P.pg) {
     if (!P.crop_original) {
       for (int k = 0; k < p.n_boxes; k++) plan_crop(P.plan, p.img, p.after_h, p.after_w, p.boxes[k].pts);
       continue;
     }
     rt_results::Page B;
-    page_boxes(p, B, P.regions != nullptr);
+    page_boxes(p, B, P.call.regions());
     for (int k = 0; k < p.n_boxes; k++) plan_crop(P.plan, p.raw, p.ori_h, p.ori_w, &B.boxes[8 * (size_t)k]);
   }
   if (P.NL > 0) P.pool = warp_planned_crops(s, P.plan, &P.d_refs, P.crop_original);
@@ -844,8 +879,8 @@ void crop_stage(rt_session& s, Pipeline& P) {
 // ---- a8 + a9: angle classifier over every crop --------------------------------------
 // (cls_processor.rs:127-172: batches of 6 sorted by aspect; the classifier is per-crop independent, so batch composition does
 //  not change any value)
-void cls_stage(rt_session& s, Pipeline& P) {
-  const int ch = s.cfg.cls_image_shape[1], cw = s.cfg.cls_image_shape[2];
+void cls_stage(rt_lane& s, Pipeline& P) {
+  const int ch = s.sh->cfg.cls_image_shape[1], cw = s.sh->cfg.cls_image_shape[2];
   P.d_meta.view(s.arena.alloc<int>((size_t)4 * P.NLp), P.NLp);
   const int CG = 2048;
   for (int c0 = 0; c0 < P.NL; c0 += CG) {
@@ -868,14 +903,14 @@ void cls_stage(rt_session& s, Pipeline& P) {
     Level L0 = make_level(uniform_hw(cn, ch, cw));
     RunCtx c = s.ctx(&s.scratch);
     float* probs;
-    { ProfOuter po(&s.prof, s.st, "net/cls"); probs = s.cls->run(c, x, L0); }
+    { ProfOuter po(&s.prof, s.st, "net/cls"); probs = s.sh->cls->run(c, x, L0); }
     ProfScope ps(&s.prof, s.st, "cls_post_rotate");
-    pp::cls_post_rotate(s.st, probs, drow, cn, s.cfg.cls_thresh, P.d_refs, P.pool, P.plan.max_pix, P.d_meta.label, P.d_meta.cscore);
+    pp::cls_post_rotate(s.st, probs, drow, cn, s.sh->cfg.cls_thresh, P.d_refs, P.pool, P.plan.max_pix, P.d_meta.label, P.d_meta.cscore);
   }
 }
 // ---- a10: rec plan: per page, order by h/w descending (stable), chunks of batch_num, running max_wh_ratio ----
-void rec_plan(rt_session& s, Pipeline& P) {
-  const int rh = s.cfg.rec_image_shape[1], rw = s.cfg.rec_image_shape[2];
+void rec_plan(rt_lane& s, Pipeline& P) {
+  const int rh = s.sh->cfg.rec_image_shape[1], rw = s.sh->cfg.rec_image_shape[2];
   const std::vector<pp::CropRef>& refs = P.plan.refs;
   P.lines.resize((size_t)P.NL); P.line_W.resize((size_t)P.NL);
   for (const PageState& p : P.pg) {
@@ -888,8 +923,8 @@ void rec_plan(rt_session& s, Pipeline& P) {
       return ra > rb;  // Reverse(OrderedFloat(ori_ratio))
     });
     float max_wh_ratio = (float)rw / (float)rh;
-    for (int s0 = 0; s0 < nb; s0 += s.cfg.rec_batch_num) {
-      int s1 = std::min(nb, s0 + s.cfg.rec_batch_num);
+    for (int s0 = 0; s0 < nb; s0 += s.sh->cfg.rec_batch_num) {
+      int s1 = std::min(nb, s0 + s.sh->cfg.rec_batch_num);
       for (int k = s0; k < s1; k++) {
         const pp::CropRef& r = refs[f + order[k]];
         float wh = (float)r.w / (float)r.h;
@@ -925,7 +960,7 @@ wb::WordGeom word_geom(const Pipeline& P, int li) {
 // "lines" with idx / prob / z5 in scratch, and k_rec_window_stitch gathers the owned rows into the line rows.
 // taps (rt_debug_rec_windows): host arrays that receive every unit's rows in unit order, each optional.
 struct RecWindowTaps { int32_t* unit_idx = nullptr; float* unit_prob = nullptr; float* unit_z5 = nullptr; };
-void rec_group_net(rt_session& s, const float* x, int rh, const int* W, int ln, int window, int overlap, int* idx, float* prob,
+void rec_group_net(rt_lane& s, const float* x, int rh, const int* W, int ln, int window, int overlap, int* idx, float* prob,
                    const float** z5, Level& Lt, const RecWindowTaps* taps = nullptr) {
   static_assert(rw::Z5_D == 120, "a z5 row is SvtrCore::D floats");
   RunCtx c = s.ctx(&s.scratch);
@@ -941,7 +976,7 @@ void rec_group_net(rt_session& s, const float* x, int rh, const int* W, int ln, 
   if (!windowed) {
     Level L0 = make_level(hw);
     { ProfOuter po(&s.prof, s.st, "net/rec");
-      s.rec->run(c, x, L0, Lt, idx, prob, z5); }  // fused CTC head: logits never reach HBM
+      s.sh->rec->run(c, x, L0, Lt, idx, prob, z5); }  // fused CTC head: logits never reach HBM
     tap(idx, prob, z5 ? *z5 : nullptr, Lt.total);
     return;
   }
@@ -981,7 +1016,7 @@ void rec_group_net(rt_session& s, const float* x, int rh, const int* W, int ln, 
   const float* u_z5 = nullptr;
   Level Lu0 = make_level(uhw), Ltu;
   { ProfOuter po(&s.prof, s.st, "net/rec");
-    s.rec->run(c, xu, Lu0, Ltu, u_idx, u_prob, z5 ? &u_z5 : nullptr); }
+    s.sh->rec->run(c, xu, Lu0, Ltu, u_idx, u_prob, z5 ? &u_z5 : nullptr); }
   if (Ltu.total != unit_rows) throw RtError(RT_ERR_SHAPE, "token count mismatch");
   { ProfScope ps(&s.prof, s.st, "rec_window_stitch");
     pp::rec_window_stitch(s.st, du, nu, max_own, u_idx, u_prob, u_z5, idx, prob, l_z5); }
@@ -992,33 +1027,34 @@ void rec_group_net(rt_session& s, const float* x, int rh, const int* W, int ln, 
   tap(u_idx, u_prob, u_z5, unit_rows);
 }
 // ---- a11 + a12: rec network + CTC decode in launch groups (+ word boxes) --------------
-void rec_groups(rt_session& s, Pipeline& P) {
-  const int rh = s.cfg.rec_image_shape[1];
+void rec_groups(rt_lane& s, Pipeline& P) {
+  const CallSettings& set = P.call.set;
+  const int rh = s.sh->cfg.rec_image_shape[1];
   const size_t ntok = (size_t)std::max<long long>(P.tok_off[P.NL], 1);
   int* d_idx = s.arena.alloc<int>(ntok); float* d_prob = s.arena.alloc<float>(ntok);
   // rec_return_candidates = K: per token slot its time step and K candidates, in one block behind the tokens ([ntok] tokens |
   // [ntok] time steps | [ntok][K] candidates), so that the one copy that brings the tokens home brings them too
-  const int cand_k = s.cfg.rec_return_candidates;
+  const int cand_k = s.sh->cfg.rec_return_candidates;
   P.d_tok = s.arena.alloc<int>(ntok * (cand_k > 0 ? 2 + 2 * (size_t)cand_k : 1));
   if (cand_k > 0) { P.d_ccol = P.d_tok + ntok; P.d_cands = reinterpret_cast<cc::Cand*>(P.d_ccol + ntok); }
   // rec_return_word_box: word count per line, words at the lines' token offsets, the kept columns (k_word_boxes' scratch)
   int* d_wcol = nullptr;
-  if (s.cfg.rec_return_word_box) {
+  if (s.sh->cfg.rec_return_word_box) {
     P.d_wcount = s.arena.alloc<int>(P.NLp); P.d_words = s.arena.alloc<wb::Word>(ntok); d_wcol = s.arena.alloc<int>(ntok);
   }
   if (P.any.lexicon) { P.lexm.alloc(s, (size_t)P.NLp * lx::MATCHES); P.lexn.alloc(s, P.NLp); }
   // lexicon snap (ctc_lexicon_align.h): a line snaps only where its lexicon has min_posterior > 0
-  if (std::any_of(P.line_opts.begin(), P.line_opts.end(), [&](const RecLineOpts& o) { return o.lexicon > 0 && s.lexicons->snap[o.lexicon - 1] > 0.0f; })) {
+  if (std::any_of(P.line_opts.begin(), P.line_opts.end(), [&](const RecLineOpts& o) { return o.lexicon > 0 && s.sh->lexicons->snap[o.lexicon - 1] > 0.0f; })) {
     P.lexs.alloc(s, P.NLp);   // (zeroed: the lexicon lines of a group without a snap-enabled line are never written)
     RT_HIP_CHECK(hipMemsetAsync(P.lexs.d, 0, (size_t)P.NLp * sizeof(int), s.st));
   }
   if (P.any.pattern) P.pat.alloc(s, (size_t)4 * P.NLp);
   if (P.any.keywords) { P.kwh.alloc(s, (size_t)P.NLp * kw::HITS); P.kwn.alloc(s, P.NLp); }
-  if (P.beam_b > 0) { P.bmn.alloc(s, P.NLp); P.bmrec.alloc(s, (size_t)P.NLp * P.beam_n); P.bmtok.alloc(s, ntok * (size_t)P.beam_n); }
+  if (set.beam_b > 0) { P.bmn.alloc(s, P.NLp); P.bmrec.alloc(s, (size_t)P.NLp * set.beam_n); P.bmtok.alloc(s, ntok * (size_t)set.beam_n); }
   static const long long REC_GROUP_PX = getenv("RT_REC_GROUP_PX") ? atoll(getenv("RT_REC_GROUP_PX")) : (long long)24000000;  // measured sweet spot (profiles/README.md)
   for (int l0 = 0; l0 < P.NL;) {
     // (a windowed line is charged with its units' pixels, rec_windows.h: what the network is run on)
-    const int l1 = group_end(l0, P.NL, 0, REC_GROUP_PX, [&](int l) { return (long long)rh * rw::unit_columns(P.line_W[l], P.rec_window, P.rec_overlap); });
+    const int l1 = group_end(l0, P.NL, 0, REC_GROUP_PX, [&](int l) { return (long long)rh * rw::unit_columns(P.line_W[l], set.rec_window, set.rec_overlap); });
     const int ln = l1 - l0;
     s.scratch.rewind();
     pp::LineDesc* hl = s.pinned.alloc<pp::LineDesc>(ln);
@@ -1037,17 +1073,17 @@ void rec_groups(rt_session& s, Pipeline& P) {
     Level Lt;
     // (the token count per line only depends on the widths, so the offsets are known before the net runs)
     const long long t0 = P.tok_off[l0];
-    const rt_lexicons& X = *s.lexicons;
-    const rt_keywords& KW = *s.keywords;
-    const RecTailPlan tail = rec_tail_plan(P.tok_off.data(), l0, l1, P.line_opts.data(), RecStores{&X.tb, X.snap, &s.patterns->tb, &KW.tb},
-                                           P.beam_b, P.beam_n);
-    const std::string refused = tail.refusal(P.beam_b);
+    const rt_lexicons& X = *s.sh->lexicons;
+    const rt_keywords& KW = *s.sh->keywords;
+    const RecTailPlan tail = rec_tail_plan(P.tok_off.data(), l0, l1, P.line_opts.data(), RecStores{&X.tb, X.snap, &s.sh->patterns->tb, &KW.tb},
+                                           set.beam_b, set.beam_n);
+    const std::string refused = tail.refusal(set.beam_b);
     if (!refused.empty()) throw RtError(RT_ERR_CAPACITY, refused);
     const float* z5 = nullptr;   // the head's input, for the candidates', the charsets', the lexicons', the keywords' and the beams' logits
-    rec_group_net(s, x, rh, P.line_W.data() + l0, ln, P.rec_window, P.rec_overlap, d_idx + t0, d_prob + t0, tail.needs_z5(cand_k) ? &z5 : nullptr, Lt);
+    rec_group_net(s, x, rh, P.line_W.data() + l0, ln, set.rec_window, set.rec_overlap, d_idx + t0, d_prob + t0, tail.needs_z5(cand_k) ? &z5 : nullptr, Lt);
     if (Lt.total != tail.rows) throw RtError(RT_ERR_SHAPE, "token count mismatch");
-    rt_session::WordBoxes words{};
-    if (s.cfg.rec_return_word_box) {
+    rt_lane::WordBoxes words{};
+    if (s.sh->cfg.rec_return_word_box) {
       pp::WordLineDesc* hwl = s.pinned.alloc<pp::WordLineDesc>(ln);
       for (int k = 0; k < ln; k++) {
         const int li = l0 + k;
@@ -1056,39 +1092,39 @@ void rec_groups(rt_session& s, Pipeline& P) {
       }
       words = {hwl, P.d_meta.label + l0, P.d_meta.cscore + l0, d_wcol + t0, P.d_wcount + l0, P.d_words + t0};
     }
-    rt_session::RecTail t;
+    rt_lane::RecTail t;
     t.z5 = z5; t.idx = d_idx + t0; t.prob = d_prob + t0; t.lines = Lt.d; t.n_lines = ln;
     t.tok = P.d_tok + t0; t.ntok = P.d_meta.ntok + l0; t.rscore = P.d_meta.rscore + l0;
     if (words.h_lines) t.wb = &words;
-    t.charsets = {s.charsets->d_masks, s.charsets->words};
+    t.charsets = {s.sh->charsets->d_masks, s.sh->charsets->words};
     t.lexicon.d = X.d; t.lexicon.matches = P.lexm.d; t.lexicon.n = P.lexn.d; t.lexicon.d_min_post = X.d_snap; t.lexicon.snapped = P.lexs.d;
-    t.pattern.d = s.patterns->d;
+    t.pattern.d = s.sh->patterns->d;
     if (P.pat.d) {   // matched | vit | logprob | free_logprob
       float* f = reinterpret_cast<float*>(P.pat.d);
       t.pattern.matched = P.pat.d; t.pattern.vit = f + P.NLp; t.pattern.logprob = f + 2 * (size_t)P.NLp; t.pattern.free_logprob = f + 3 * (size_t)P.NLp;
     }
     t.keywords.d = KW.d; t.keywords.d_min = KW.d_min; t.keywords.hits = P.kwh.d; t.keywords.n = P.kwn.d;
-    t.beam.b = P.beam_b; t.beam.n = P.beam_n; t.beam.count = P.bmn.d; t.beam.recs = P.bmrec.d;
-    if (P.bmtok.d) t.beam.tok = P.bmtok.d + t0 * P.beam_n;
+    t.beam.b = set.beam_b; t.beam.n = set.beam_n; t.beam.count = P.bmn.d; t.beam.recs = P.bmrec.d;
+    if (P.bmtok.d) t.beam.tok = P.bmtok.d + t0 * set.beam_n;
     t.cand.k = cand_k;
     if (cand_k > 0) { t.cand.col = P.d_ccol + t0; t.cand.cands = P.d_cands + t0 * cand_k; }
-    s.rec_tail(tail, s.rec->core(), t);
+    s.rec_tail(tail, s.sh->rec->core(), t);
     l0 = l1;
   }
 }
 // ---- metadata round trip #2: labels, scores, token ids (and the words) ---------------
-void line_round_trip(rt_session& s, Pipeline& P) {
+void line_round_trip(rt_lane& s, Pipeline& P) {
   const long long total_tok = P.tok_off[P.NL];
   // per-line results come back in two copies into pinned memory: the metadata block and the tokens
   P.h_meta.view(s.pinned.alloc<int>((size_t)4 * P.NLp), P.NLp);
   // (with rec_return_candidates = K the tokens' block also holds their time steps and candidates: rec_groups)
-  const size_t nt = (size_t)std::max<long long>(total_tok, 1), K = (size_t)s.cfg.rec_return_candidates;
+  const size_t nt = (size_t)std::max<long long>(total_tok, 1), K = (size_t)s.sh->cfg.rec_return_candidates;
   const size_t tok_words = nt * (K > 0 ? 2 + 2 * K : 1);
   P.h_tokens = s.pinned.alloc<int>(tok_words);
   if (K > 0) { P.h_ccol = P.h_tokens + nt; P.h_cands = reinterpret_cast<cc::Cand*>(P.h_ccol + nt); }
   RT_HIP_CHECK(hipMemcpyAsync(P.h_meta.label, P.d_meta.label, (size_t)4 * P.NLp * sizeof(int), hipMemcpyDeviceToHost, s.st));
   if (total_tok > 0) RT_HIP_CHECK(hipMemcpyAsync(P.h_tokens, P.d_tok, tok_words * 4, hipMemcpyDeviceToHost, s.st));
-  if (s.cfg.rec_return_word_box) {   // (the words ride with the tokens: same round trip)
+  if (s.sh->cfg.rec_return_word_box) {   // (the words ride with the tokens: same round trip)
     P.h_wcount = s.pinned.alloc<int>(P.NLp);
     P.h_words = s.pinned.alloc<wb::Word>((size_t)std::max<long long>(total_tok, 1));
     RT_HIP_CHECK(hipMemcpyAsync(P.h_wcount, P.d_wcount, (size_t)P.NL * sizeof(int), hipMemcpyDeviceToHost, s.st));
@@ -1103,14 +1139,14 @@ void line_round_trip(rt_session& s, Pipeline& P) {
 void results(const rt_session& s, const Pipeline& P, rt_results& res) {
   static const uint16_t LABELS[2] = {0, 180};
   const LineMeta& m = P.h_meta;
-  for (int i = 0; i < P.n_pages; i++) {
+  for (int i = 0; i < P.call.n_pages; i++) {
     rt_results::Page& R = res.pages[i];
     const PageState& p = P.pg[i];
     int nb = p.n_boxes;
-    page_boxes(p, R, P.regions != nullptr);
+    page_boxes(p, R, P.call.regions());
     R.cls_labels.resize(nb); R.cls_scores.resize(nb); R.rec_scores.resize(nb); R.tokens.resize(nb); R.text.resize(nb);
     R.rec_units.resize(nb);
-    for (int k = 0; k < nb; k++) R.rec_units[k] = rw::units(P.line_W[p.first_line + k], P.rec_window, P.rec_overlap);
+    for (int k = 0; k < nb; k++) R.rec_units[k] = rw::units(P.line_W[p.first_line + k], P.call.set.rec_window, P.call.set.rec_overlap);
     for (int k = 0; k < nb; k++) {
       int li = p.first_line + k;
       R.cls_labels[k] = LABELS[m.label[li] ? 1 : 0]; R.cls_scores[k] = m.cscore[li]; R.rec_scores[k] = m.rscore[li];
@@ -1175,7 +1211,7 @@ void results(const rt_session& s, const Pipeline& P, rt_results& res) {
       }
     }
     if (P.bmn.h) {   // rec beams: per line its hypotheses, best first; a hypothesis' text from the dictionary as the line's own
-      const int N = P.beam_n;
+      const int N = P.call.set.beam_n;
       R.beam_n = N; R.bm_count.assign((size_t)nb, 0); R.bm_recs.assign((size_t)nb * N, bm::Beam{0.0f, 0});
       R.bm_tokens.assign((size_t)nb * N, std::vector<int32_t>()); R.bm_text.assign((size_t)nb * N, std::string());
       for (int k = 0; k < nb; k++) {
@@ -1212,13 +1248,11 @@ void results(const rt_session& s, const Pipeline& P, rt_results& res) {
     }
   }
 }
-// what a rule of rec_line_opts.h objects to, if anything
-void refuse(const std::string& why) { if (!why.empty()) throw RtError(RT_ERR_INVALID, why); }
 }  // namespace
 std::string rt_format_f32_impl(float v) { return fnum(v); }
 
-rt_results* rt_session::run_pages(const uint8_t* const* rgb, const int* hs, const int* ws, int n_pages, int mem,
-                                  const float* const* det_map_override, const Regions* regions, const CallSettings& set) {
+rt_results* rt_lane::run_pages(const PageCall& call) {
+  const int n_pages = call.n_pages;
   if (g_trace) fprintf(stderr, "[rt host] %-28s %8.3f ms\n", "between calls", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - last_exit).count());
   HostTick tick0;
   // a one-page call is the reference's real mode (retto-cli/src/main.rs:80-86): it polls through its waits; a multi-page batch
@@ -1226,28 +1260,25 @@ rt_results* rt_session::run_pages(const uint8_t* const* rgb, const int* hs, cons
   struct SpinScope { int& r; int old; ~SpinScope() { r = old; } } spin_scope{spin_us, spin_us};
   // (a lane worker's one-page part -- a batch of <= lanes pages, or several one-page submissions in flight -- is a throughput run
   //  too: it polls for a bounded 250 us per wait, not 5 ms)
-  spin_us = n_pages > 1 ? 50 : on_lane_worker ? 250 : 5000;
+  spin_us = n_pages > 1 ? 50 : call.on_lane_worker ? 250 : 5000;
   begin_call();
   tick0.lap("begin_call + arena reset");
   std::unique_ptr<rt_results> res(new rt_results());
   res->pages.resize((size_t)n_pages);
   if (n_pages == 0) return res.release();
-  Pipeline P{n_pages, mem, det_map_override, std::vector<PageState>((size_t)n_pages)};
-  P.regions = regions; P.crop_original = regions != nullptr || cfg.crop_source == 1;
-  P.det_tile = set.det_tile; P.det_overlap = set.det_overlap;
-  P.beam_b = set.beam_b; P.beam_n = set.beam_n;
-  P.rec_window = set.rec_window; P.rec_overlap = set.rec_overlap;
+  Pipeline P{call, std::vector<PageState>((size_t)n_pages)};
+  P.crop_original = call.regions() || sh->cfg.crop_source == 1;
   HostTick tick;
-  if (regions) {   // the boxes are given: no resize_both, no detector, no DB post-processing, no first round trip
-    region_pages(*this, P, rgb, hs, ws); tick.lap("pre (upload, regions)");
+  if (call.regions()) {   // the boxes are given: no resize_both, no detector, no DB post-processing, no first round trip
+    region_pages(*this, P); tick.lap("pre (upload, regions)");
   } else {
-    page_sizes(*this, P, rgb, hs, ws);
+    page_sizes(*this, P);
     tick.lap("pre (resize, upload)");
     det_groups(*this, P); tick.lap("det enqueue");
     db_post(*this, P); tick.lap("dbpost enqueue");
     box_round_trip(*this, P, *res); tick.lap("sync #1 + box D2H");
   }
-  refuse(expand_line_opts(P.pg.data(), n_pages, P.NL, regions ? regions->opts : nullptr, set.rec, rec_counts(), P.line_opts, P.any));
+  rt_refuse(expand_line_opts(P.pg.data(), n_pages, P.NL, call.regions() ? call.region_opts : nullptr, call.set.rec, sh->rec_counts(), P.line_opts, P.any));
   crop_stage(*this, P);
   if (P.NL > 0) {
     tick.lap("crop plan + warp enqueue");
@@ -1257,9 +1288,9 @@ rt_results* rt_session::run_pages(const uint8_t* const* rgb, const int* hs, cons
     line_round_trip(*this, P);
   }
   tick.lap("sync #2 + D2H");
-  results(*this, P, *res);
-  if (stage_cb)
-    for (int i = 0; i < n_pages; i++) { emit_stage(i, 1, res->pages[i]); emit_stage(i, 2, res->pages[i]); }
+  results(*sh, P, *res);
+  if (call.cb)
+    for (int i = 0; i < n_pages; i++) { emit_stage(call, i, 1, res->pages[i]); emit_stage(call, i, 2, res->pages[i]); }
   tick.lap("results");
   if (g_trace) last_exit = std::chrono::steady_clock::now();
   return res.release();
@@ -1274,11 +1305,13 @@ void rt_session::debug_det_tiles(const uint8_t* rgb_det, int h, int w, float* ti
   begin_call();
   uint8_t* d = arena.alloc<uint8_t>((size_t)h * w * 3);
   RT_HIP_CHECK(hipMemcpyAsync(d, rgb_det, (size_t)h * w * 3, hipMemcpyHostToDevice, st));
-  Pipeline P{1, RT_MEM_DEVICE, nullptr, std::vector<PageState>(1)};
+  PageCall call;
+  call.n_pages = 1; call.mem = RT_MEM_DEVICE; call.set = settings();
+  Pipeline P{call, std::vector<PageState>(1)};
   PageState& p = P.pg[0];
   p.ori_h = p.after_h = p.det_h = h; p.ori_w = p.after_w = p.det_w = w;
   p.raw = p.img = p.det_img = d; p.map = nullptr;
-  P.det_tile = det_tile; P.det_overlap = det_overlap; P.tile_maps_out = tile_maps_out;
+  P.tile_maps_out = tile_maps_out;
   det_groups(*this, P);
   RT_HIP_CHECK(hipMemcpyAsync(page_map_out, p.map, (size_t)h * w * 4, hipMemcpyDeviceToHost, st));
   if (tile_maps_out && !dt::page_tiled(h, w, det_tile))
@@ -1298,14 +1331,7 @@ void rt_session::debug_rec_windows(const float* nchw, int n, const int* widths, 
     nt += (size_t)RecNet::tokens_for_width(widths[i]);
   }
   begin_call();
-  float* d_in = arena.alloc<float>(ne);
-  RT_HIP_CHECK(hipMemcpyAsync(d_in, nchw, ne * 4, hipMemcpyHostToDevice, st));
-  float* x = arena.alloc<float>(ne / 3 * 4);
-  size_t off = 0;
-  for (int i = 0; i < n; i++) {
-    nn::nchw3_to_nhwc4(st, d_in + off * 3, 1, h, widths[i], x + off * 4);
-    off += (size_t)h * widths[i];
-  }
+  float* x = upload_ragged(*this, nchw, ne, n, h, widths);
   int* d_idx = arena.alloc<int>(nt); float* d_prob = arena.alloc<float>(nt);
   const float* z5 = nullptr;
   Level Lt;
@@ -1318,444 +1344,8 @@ void rt_session::debug_rec_windows(const float* nchw, int n, const int* widths, 
   sync();
 }
 
-// Splits the pages over the lanes (contiguous ranges, order preserved) and runs the lanes on
-// concurrent host threads; every lane is a full pipeline on its own stream, so one lane's
-// small kernels, launch gaps and host sync points overlap the other lanes' large kernels.
-// ---------------------------------------------------------------------------
-// Lanes.  rt_run_batch splits the pages over the lanes; round 4: the lanes' host threads are persistent (round 3 created and
-// joined them on every call) and batches can be SUBMITTED ahead (rt_submit_batch / rt_wait_batch, the counterpart of
-// RettoSession::run_stream's worker thread + channel, session.rs:108-143): a lane that has finished its part of batch i starts
-// on batch i + 1 at once, so the lanes drift apart in phase and the call boundary (result assembly on the host, descriptors of
-// the next call) no longer idles the GPU.
-// ---------------------------------------------------------------------------
-void LaneWorker::start(int device) {
-  th = std::thread([this, device] {
-    (void)hipSetDevice(device);
-    for (;;) {
-      std::function<void()> f;
-      {
-        std::unique_lock<std::mutex> lk(mu);
-        cv.wait(lk, [&] { return stop || !q.empty(); });
-        if (q.empty()) return;   // stop requested and nothing left
-        f = std::move(q.front()); q.pop_front();
-      }
-      f();
-    }
-  });
-}
-void LaneWorker::push(std::function<void()> f) {
-  { std::lock_guard<std::mutex> lk(mu); q.push_back(std::move(f)); }
-  cv.notify_one();
-}
-void LaneWorker::shutdown() {
-  { std::lock_guard<std::mutex> lk(mu); stop = true; }
-  cv.notify_all();
-  if (th.joinable()) th.join();
-}
-void rt_session::ensure_workers() {
-  while (workers.size() < helpers.size() + 1) {
-    std::unique_ptr<LaneWorker> w(new LaneWorker());
-    w->start(device);
-    workers.push_back(std::move(w));
-  }
-}
-
-// ---- page staging ----------------------------------------------------------------------------------------------------------
-// A lane that uploads its own pages blocks its host thread in hipMemcpyAsync (pageable memory: the call returns when the copy is
-// done) with nothing queued on its stream: about 3 ms per 11-page part.  rt_submit_batch therefore copies the host pages of the
-// whole batch itself, on a copy stream, into a slot of HBM the session keeps per batch in flight; the lanes' streams wait for the
-// slot's event.  With one batch submitted ahead the copy of batch i+1 runs on the DMA engines under the kernels of batch i.
-int rt_session::acquire_slot(size_t total, int nl) {
-  RT_HIP_CHECK(hipSetDevice(device));   // (the caller's thread: nothing else has chosen the device on the submit path)
-  int slot = -1;
-  for (size_t k = 0; k < stage_slots.size(); k++) if (!stage_slots[k].busy) { slot = (int)k; break; }
-  if (slot < 0) { stage_slots.emplace_back(); slot = (int)stage_slots.size() - 1; }
-  StageSlot& S = stage_slots[(size_t)slot];
-  if (!st_copy) RT_HIP_CHECK(hipStreamCreateWithFlags(&st_copy, hipStreamNonBlocking));
-  while ((int)S.ev.size() < nl) {
-    hipEvent_t e = nullptr;
-    RT_HIP_CHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    S.ev.push_back(e);
-  }
-  if (S.cap < total) {
-    if (S.p) { (void)hipFree(S.p); S.p = nullptr; S.cap = 0; }
-    if (hipMalloc((void**)&S.p, total) != hipSuccess) { (void)hipGetLastError(); S.p = nullptr; return -1; }
-    S.cap = total;
-  }
-  return slot;
-}
-
-// ---- encoded pages (rt_submit_encoded_batch, rt_decode_batch) -----------------------------------------------------------------
-// Layout of pages [i0, i1) inside a slot from byte `at`: each page's RGB8 result, then for a page the kernels reconstruct its
-// MCU-padded component planes and int16 coefficients, then the part's DevComp / DevPage tables.  Returns the end offset.
-static size_t al256(size_t v) { return (v + 255) & ~(size_t)255; }
-static size_t enc_layout(const std::vector<rt::EncodedPage>& enc, int i0, int i1, size_t at, std::vector<size_t>& rgb_off,
-                         rt_ticket::EncPart& P) {
-  int64_t blocks = 0;
-  for (int i = i0; i < i1; i++) {
-    const rt::EncodedPage& e = enc[(size_t)i];
-    rgb_off[(size_t)i] = at;
-    at += al256((size_t)e.h * e.w * 3);
-    if (!e.on_device) continue;
-    const rt::JpegCoefs& J = e.jpeg;
-    rt::jpeg::DevPage dp{};
-    dp.rgb_off = rgb_off[(size_t)i]; dp.pix_base = P.pixels; dp.W = J.W; dp.H = J.H; dp.nc = J.nc; dp.is_rgb = J.is_rgb;
-    for (int k = 0; k < J.nc; k++) {
-      const rt::JpegCoefs::Comp& C = J.c[k];
-      rt::jpeg::DevComp dc{};
-      dc.plane_off = at; at += al256((size_t)C.stride * C.rows);
-      dc.coef_off = at; at += al256(C.coef.size() * sizeof(int16_t));
-      dc.blocks_w = C.stride / 8; dc.nblocks = (C.stride / 8) * (C.rows / 8); dc.block_base = (int)blocks;
-      blocks += dc.nblocks;
-      if (blocks > 0x7fffffff || C.coef.size() != (size_t)dc.nblocks * 64) throw RtError(RT_ERR_BACKEND, "encoded batch: too many JPEG blocks in one part");
-      dc.stride = C.stride; dc.cw = C.cw; dc.ch = C.ch; dc.fh = J.hmax / C.hs; dc.fv = J.vmax / C.vs;
-      memcpy(dc.q, C.q, sizeof(dc.q));
-      dp.comp[k] = (int)P.comps.size();
-      P.comps.push_back(dc);
-    }
-    P.pixels += (int64_t)J.W * J.H;
-    P.pages.push_back(dp);
-  }
-  P.blocks = (int)blocks;
-  P.comps_off = at; at += al256(P.comps.size() * sizeof(rt::jpeg::DevComp));
-  P.pages_off = at; at += al256(P.pages.size() * sizeof(rt::jpeg::DevPage));
-  return at;
-}
-// uploads pages [i0, i1) (coefficients of the device pages, pixels of the others) and the tables, then reconstructs on `st`
-static void enc_upload(uint8_t* base, const std::vector<rt::EncodedPage>& enc, int i0, int i1, const std::vector<size_t>& rgb_off,
-                       const rt_ticket::EncPart& P, hipStream_t st) {
-  size_t c = 0;
-  for (int i = i0; i < i1; i++) {
-    const rt::EncodedPage& e = enc[(size_t)i];
-    if (!e.on_device) {
-      RT_HIP_CHECK(hipMemcpyAsync(base + rgb_off[(size_t)i], e.rgb.data(), e.rgb.size(), hipMemcpyHostToDevice, st));
-      continue;
-    }
-    for (int k = 0; k < e.jpeg.nc; k++, c++) {
-      const std::vector<int16_t>& q = e.jpeg.c[k].coef;
-      RT_HIP_CHECK(hipMemcpyAsync(base + P.comps[c].coef_off, q.data(), q.size() * sizeof(int16_t), hipMemcpyHostToDevice, st));
-    }
-  }
-  if (P.pages.empty()) return;
-  RT_HIP_CHECK(hipMemcpyAsync(base + P.comps_off, P.comps.data(), P.comps.size() * sizeof(rt::jpeg::DevComp), hipMemcpyHostToDevice, st));
-  RT_HIP_CHECK(hipMemcpyAsync(base + P.pages_off, P.pages.data(), P.pages.size() * sizeof(rt::jpeg::DevPage), hipMemcpyHostToDevice, st));
-  const auto* comps = (const rt::jpeg::DevComp*)(base + P.comps_off);
-  rt::launch_jpeg_idct(base, comps, (int)P.comps.size(), P.blocks, st);
-  rt::launch_jpeg_color(base, comps, (const rt::jpeg::DevPage*)(base + P.pages_off), (int)P.pages.size(), P.pixels, st);
-}
-// an encoded ticket: every part in one slot, laid out part after part (staging is not optional here: the lanes need pixels)
-static void stage_encoded_layout(rt_ticket* t, size_t* total) {
-  t->enc_parts.assign((size_t)t->nl, rt_ticket::EncPart());
-  t->stage_off.assign((size_t)t->n_pages, (size_t)-1);
-  size_t at = 0;
-  for (int l = 0; l < t->nl; l++) at = enc_layout(t->enc, t->first[l], t->first[l + 1], at, t->stage_off, t->enc_parts[(size_t)l]);
-  *total = at;
-}
-void rt_session::decode_batch(std::vector<rt::EncodedPage>& enc, uint8_t* const* out, int mem) {
-  const int n = (int)enc.size();
-  std::vector<size_t> off((size_t)n, 0);
-  rt_ticket::EncPart P;
-  const size_t total = enc_layout(enc, 0, n, 0, off, P);
-  bool any_dev = false;
-  for (auto& e : enc) any_dev |= e.on_device || mem == RT_MEM_DEVICE;
-  if (!any_dev) {   // host pages into host memory: nothing to do on the device
-    for (int i = 0; i < n; i++) memcpy(out[i], enc[(size_t)i].rgb.data(), enc[(size_t)i].rgb.size());
-    return;
-  }
-  const int slot = acquire_slot(std::max<size_t>(total, 256), 1);
-  if (slot < 0) throw RtError(RT_ERR_BACKEND, "rt_decode_batch: out of device memory for the pages");
-  uint8_t* base = stage_slots[(size_t)slot].p;
-  enc_upload(base, enc, 0, n, off, P, st_copy);
-  for (int i = 0; i < n; i++) {
-    const rt::EncodedPage& e = enc[(size_t)i];
-    const size_t bytes = (size_t)e.h * e.w * 3;
-    if (mem == RT_MEM_DEVICE) RT_HIP_CHECK(hipMemcpyAsync(out[i], base + off[(size_t)i], bytes, hipMemcpyDeviceToDevice, st_copy));
-    else if (e.on_device) RT_HIP_CHECK(hipMemcpyAsync(out[i], base + off[(size_t)i], bytes, hipMemcpyDeviceToHost, st_copy));
-    else memcpy(out[i], e.rgb.data(), bytes);
-  }
-  RT_HIP_CHECK(hipStreamSynchronize(st_copy));
-}
-
-void rt_session::stage_pages(rt_ticket* t) {
-  if (!t->enc.empty()) {
-    size_t total = 0;
-    stage_encoded_layout(t, &total);
-    const int slot = acquire_slot(std::max<size_t>(total, 256), t->nl);
-    if (slot < 0) throw RtError(RT_ERR_BACKEND, "rt_submit_encoded_batch: out of device memory for the pages");
-    StageSlot& S = stage_slots[(size_t)slot];
-    S.busy = true;
-    t->stage_slot = slot;
-    t->ev_up.assign(S.ev.begin(), S.ev.begin() + t->nl);
-    for (int i = 0; i < t->n_pages; i++) t->rgb[(size_t)i] = S.p + t->stage_off[(size_t)i];
-    t->mem_lane = RT_MEM_STAGED_MAPS_HOST;
-    return;
-  }
-  if (t->mem != RT_MEM_HOST && t->mem != RT_MEM_HOST_MAPS_DEVICE) return;
-  size_t total = 0;
-  std::vector<size_t> off((size_t)t->n_pages, (size_t)-1);
-  for (int i = 0; i < t->n_pages; i++) {
-    if (t->hs[i] <= 0 || t->ws[i] <= 0 || !t->rgb[i]) continue;   // left to the lane, which reports it as the reference does
-    off[(size_t)i] = total;
-    total += ((size_t)t->hs[i] * t->ws[i] * 3 + 255) & ~(size_t)255;
-  }
-  if (!total) return;
-  const int slot = acquire_slot(total, t->nl);
-  if (slot < 0) return;   // out of device memory: the lanes copy, as before
-  StageSlot& S = stage_slots[(size_t)slot];
-  S.busy = true;
-  t->stage_slot = slot;
-  t->stage_off = std::move(off);
-  t->ev_up.assign(S.ev.begin(), S.ev.begin() + t->nl);
-  t->mem_lane = t->mem == RT_MEM_HOST ? RT_MEM_STAGED_MAPS_HOST : RT_MEM_DEVICE;
-}
-// the part's pages go up right before its lane job is queued: the first lane starts after its own pages, not after the batch's
-void rt_session::stage_part(rt_ticket* t, int l) {
-  if (t->stage_slot < 0) return;
-  StageSlot& S = stage_slots[(size_t)t->stage_slot];
-  if (!t->enc.empty()) {
-    enc_upload(S.p, t->enc, t->first[l], t->first[l + 1], t->stage_off, t->enc_parts[(size_t)l], st_copy);
-    RT_HIP_CHECK(hipEventRecord(t->ev_up[(size_t)l], st_copy));
-    return;
-  }
-  for (int i = t->first[l]; i < t->first[l + 1]; i++) {
-    const size_t o = t->stage_off[(size_t)i];
-    if (o == (size_t)-1) continue;
-    RT_HIP_CHECK(hipMemcpyAsync(S.p + o, t->rgb[i], (size_t)t->hs[i] * t->ws[i] * 3, hipMemcpyHostToDevice, st_copy));
-    t->rgb[i] = S.p + o;
-  }
-  RT_HIP_CHECK(hipEventRecord(t->ev_up[(size_t)l], st_copy));
-}
-void rt_session::release_stage(rt_ticket* t) {
-  if (t->stage_slot >= 0) stage_slots[(size_t)t->stage_slot].busy = false;
-  t->stage_slot = -1;
-}
-void rt_session::free_stage() {
-  if (st_copy) (void)hipStreamSynchronize(st_copy);
-  for (auto& S : stage_slots) { if (S.p) (void)hipFree(S.p); for (hipEvent_t e : S.ev) (void)hipEventDestroy(e); }
-  stage_slots.clear();
-  if (st_copy) { (void)hipStreamDestroy(st_copy); st_copy = nullptr; }
-}
-
-rt_ticket* rt_session::submit_batch(const uint8_t* const* rgb, const int* hs, const int* ws, int n_pages, int mem,
-                                    const float* const* det_map_override, rt_stage_callback cb, void* user,
-                                    std::vector<rt::EncodedPage>* enc, const Regions* regions) {
-  if (!regions) refuse(rec_opts_conflict(rec_default));   // (regions: run_regions has checked every region's own options)
-  ensure_workers();
-  std::unique_ptr<rt_ticket> t(new rt_ticket());
-  const int nl = std::max(1, std::min<int>(std::min<int>((int)helpers.size() + 1, active_lanes), std::max(n_pages, 1)));
-  t->nl = nl; t->n_pages = n_pages; t->mem = mem; t->cb = cb; t->user = user;
-  t->rgb.assign(rgb, rgb + n_pages); t->hs.assign(hs, hs + n_pages); t->ws.assign(ws, ws + n_pages);
-  if (det_map_override) t->maps.assign(det_map_override, det_map_override + n_pages);
-  if (regions) { t->quads.assign(regions->quads, regions->quads + n_pages); t->n_quads.assign(regions->n_quads, regions->n_quads + n_pages); }
-  if (regions && regions->opts) t->region_opts.assign(regions->opts, regions->opts + n_pages);
-  t->set = settings();   // (the lanes run later: the settings are the ones of the submitting call)
-  t->parts.assign((size_t)nl, nullptr); t->errs.resize((size_t)nl); t->first.assign((size_t)nl + 1, 0);
-  {
-    // contiguous ranges of about equal work: det pixels after the session size limit (a2) plus a constant per page
-    // for its lines; equal page counts when the pages are all one size
-    std::vector<double> cost((size_t)n_pages);
-    double total = 0;
-    for (int i = 0; i < n_pages; i++) {
-      const double h = std::max(hs[i], 1), w = std::max(ws[i], 1);
-      const double r = std::min(1.0, (double)cfg.max_side_len / std::max(h, w));
-      total += cost[(size_t)i] = h * w * r * r + 250000.0;
-    }
-    double acc = 0;
-    int l = 1;
-    for (int i = 0; i < n_pages && l < nl; i++) {
-      acc += cost[(size_t)i];
-      // close range l-1 after page i once its share is reached, leaving at least one page for each later lane
-      if (acc >= total * l / nl - 1e-6 || n_pages - (i + 1) <= nl - l) t->first[l++] = i + 1;  // one range per page: none empty
-    }
-    for (; l <= nl; l++) t->first[l] = n_pages;
-    for (int k = 1; k <= nl; k++) t->first[k] = std::max(t->first[k], t->first[k - 1]);
-  }
-  t->remaining = nl;
-  t->mem_lane = mem;
-  rt_ticket* tp = t.get();
-  static const bool no_stage = getenv("RT_NO_STAGE") && atoi(getenv("RT_NO_STAGE"));   // (A/B switch of the measurement in DESIGN.md)
-  if (enc) tp->enc = std::move(*enc);
-  if (!no_stage || !tp->enc.empty()) stage_pages(tp);
-  // parts go to consecutive lanes starting behind the previous batch's last one: batches that fill fewer lanes than the session
-  // has (single pages: one lane each) run side by side instead of queueing on lane 0
-  const int total_lanes = (int)helpers.size() + 1;
-  // (with rt_set_lanes below the session's lane count the partitions would leave CUs unused: whole-device streams then)
-  const bool use_parts = active_lanes >= total_lanes;
-  const int base = next_lane;
-  next_lane = (next_lane + nl) % total_lanes;
-  int queued = 0;
-  try {
-  for (int l = 0; l < nl; l++) {
-    const int li = (base + l) % total_lanes;
-    rt_session* s = li == 0 ? this : helpers[(size_t)li - 1].get();
-    stage_part(tp, l);
-    workers[(size_t)li]->push([tp, s, l, use_parts] {
-      const int f0 = tp->first[l], f1 = tp->first[l + 1];
-      s->stage_cb = tp->cb; s->stage_user = tp->user; s->stage_mu = &tp->cb_mu; s->page_base = f0;
-      // a lane inside a submitted batch works on its own CU partition (every call ends with its stream drained, so the lane's
-      // arenas and pinned staging can change streams between calls)
-      s->st = (s->st_part && use_parts) ? s->st_part : s->st_full;
-      s->on_lane_worker = true;
-      try {
-        if (!tp->ev_up.empty()) RT_HIP_CHECK(hipStreamWaitEvent(s->st, tp->ev_up[(size_t)l], 0));
-        Regions rg{nullptr, nullptr};
-        if (!tp->quads.empty()) rg = Regions{tp->quads.data() + f0, tp->n_quads.data() + f0, tp->region_opts.empty() ? nullptr : tp->region_opts.data() + f0};
-        tp->parts[l] = s->run_pages(tp->rgb.data() + f0, tp->hs.data() + f0, tp->ws.data() + f0, f1 - f0, tp->mem_lane,
-                                    tp->maps.empty() ? nullptr : tp->maps.data() + f0, tp->quads.empty() ? nullptr : &rg, tp->set);
-      } catch (...) {
-        tp->errs[l] = std::current_exception();
-        s->failed = true;
-        // work of the failed part may still be queued on the lane's stream: drain it before the lane's next job rewinds the
-        // arenas and the pinned staging it reads
-        if (s->st) (void)hipStreamSynchronize(s->st);
-        (void)hipGetLastError();
-      }
-      s->stage_cb = nullptr; s->stage_mu = nullptr;   // the callback never outlives the batch
-      s->st = s->st_full; s->on_lane_worker = false;
-      // notify while holding the mutex: rt_wait_batch owns the ticket and deletes it as soon as it sees remaining == 0, so
-      // nothing of *tp may be touched once the decrement is visible outside the lock
-      { std::lock_guard<std::mutex> lk(tp->mu); tp->remaining--; tp->cv.notify_all(); }
-    });
-    queued++;
-  }
-  } catch (...) {
-    // a push that threw (bad_alloc): the parts already queued hold tp -- take the un-queued ones off the count, wait for the
-    // queued ones, and leave the session as it was (inflight is only counted once every part is queued)
-    {
-      std::unique_lock<std::mutex> lk(tp->mu);
-      tp->remaining -= nl - queued;
-      tp->cv.wait(lk, [&] { return tp->remaining == 0; });
-    }
-    for (auto* r : tp->parts) delete r;
-    release_stage(tp);
-    throw;
-  }
-  inflight.fetch_add(1);
-  return t.release();
-}
-
-rt_results* rt_session::wait_batch(rt_ticket* tp) {
-  std::unique_ptr<rt_ticket> t(tp);
-  {
-    std::unique_lock<std::mutex> lk(t->mu);
-    t->cv.wait(lk, [&] { return t->remaining == 0; });
-  }
-  inflight.fetch_sub(1);
-  release_stage(t.get());   // (every lane has drained its stream: nothing reads the slot any more)
-  std::unique_ptr<rt_results> res(new rt_results());
-  std::exception_ptr err;
-  for (int l = 0; l < t->nl; l++) {
-    if (t->errs[l] && !err) err = t->errs[l];
-    if (t->parts[l]) {
-      for (auto& p : t->parts[l]->pages) res->pages.push_back(std::move(p));
-      res->det_checksum += t->parts[l]->det_checksum;
-      delete t->parts[l];
-    }
-  }
-  if (err) std::rethrow_exception(err);
-  return res.release();
-}
-
-rt_results* rt_session::run_batch(const uint8_t* const* rgb, const int* hs, const int* ws, int n_pages, int mem,
-                                  const float* const* det_map_override, rt_stage_callback cb, void* user) {
-  const int nl = std::max(1, std::min<int>(std::min<int>((int)helpers.size() + 1, active_lanes), std::max(n_pages, 1)));
-  if (nl <= 1) {   // one lane: on the caller's thread (no hand-over in the single-page latency path)
-    std::mutex cb_mu;
-    struct Disarm {  // the callback never outlives the call
-      rt_session* self;
-      ~Disarm() { self->stage_cb = nullptr; self->stage_mu = nullptr; }
-    } disarm{this};
-    refuse(rec_opts_conflict(rec_default));
-    stage_cb = cb; stage_user = user; stage_mu = &cb_mu; page_base = 0;
-    try {
-      return run_pages(rgb, hs, ws, n_pages, mem, det_map_override, nullptr, settings());
-    } catch (...) { failed = true; throw; }
-  }
-  return wait_batch(submit_batch(rgb, hs, ws, n_pages, mem, det_map_override, cb, user));
-}
-
-// rt_run_regions.  A quad is clamped to the page, then held to what the crop plan needs: a crop of at least 1 x 1 pixels and an
-// invertible homography -- checked here, for every page, before anything is queued.
-rt_results* rt_session::run_regions(const uint8_t* const* rgb, const int* hs, const int* ws, int n_pages, int mem,
-                                    const float* const* quads, const int* n_quads, const int* const* region_charsets,
-                                    const int* const* region_lexicons, const int* const* region_patterns,
-                                    const int* const* region_keywords) {
-  std::vector<std::vector<float>> clamped((size_t)n_pages);
-  std::vector<const float*> qp((size_t)n_pages, nullptr);
-  // the regions' options with -1 resolved to the session defaults of this call (rec_line_opts.h)
-  std::vector<std::vector<RecLineOpts>> opts((size_t)n_pages);
-  std::vector<const RecLineOpts*> op((size_t)n_pages, nullptr);
-  const int* const* const ids[REC_N_KINDS] = {region_charsets, region_lexicons, region_patterns, region_keywords};
-  for (int i = 0; i < n_pages; i++) {
-    const std::string where = "rt_run_regions: page " + std::to_string(i);
-    if (hs[i] <= 0 || ws[i] <= 0 || rgb[i] == nullptr) throw RtError(RT_ERR_IMAGE, where + ": empty page");
-    if (n_quads[i] < 0) throw RtError(RT_ERR_INVALID, where + ": negative region count");
-    if (n_quads[i] > 0 && quads[i] == nullptr) throw RtError(RT_ERR_INVALID, where + ": NULL quads with a positive region count");
-    std::vector<float>& q = clamped[(size_t)i];
-    q.resize((size_t)n_quads[i] * 8);
-    const float mx = (float)(ws[i] - 1), my = (float)(hs[i] - 1);
-    for (int k = 0; k < n_quads[i]; k++) {
-      const std::string at = where + " region " + std::to_string(k);
-      float* b = q.data() + 8 * (size_t)k;
-      for (int j = 0; j < 8; j++) {
-        const float v = quads[i][8 * (size_t)k + j], hi = (j & 1) ? my : mx;
-        if (!std::isfinite(v)) throw RtError(RT_ERR_INVALID, at + ": non-finite coordinate");
-        b[j] = v < 0.0f ? 0.0f : (v > hi ? hi : v);
-      }
-      const gm::CropDims d = gm::crop_dims(b);
-      if (d.w < 1 || d.h < 1) throw RtError(RT_ERR_INVALID, at + ": the crop is smaller than one pixel");
-      float inv[9];
-      if (!gm::projection_inverse(b, d.cw, d.ch, inv)) throw RtError(RT_ERR_INVALID, at + ": singular homography (degenerate quad)");
-    }
-    qp[(size_t)i] = q.data();
-    // (a page's options behind the checks of its quads and before the next page's)
-    const std::string bad = resolve_region_opts(i, i + 1, n_quads, ids, REC_N_KINDS, rec_default, rec_counts(), opts);
-    if (!bad.empty()) throw RtError(RT_ERR_INVALID, "rt_run_regions: " + bad);
-    op[(size_t)i] = opts[(size_t)i].data();
-  }
-  const Regions rg{qp.data(), n_quads, op.data()};
-  const int nl = std::max(1, std::min<int>(std::min<int>((int)helpers.size() + 1, active_lanes), std::max(n_pages, 1)));
-  if (nl <= 1) {   // one lane: on the caller's thread, as run_batch
-    try {
-      return run_pages(rgb, hs, ws, n_pages, mem, nullptr, &rg, settings());
-    } catch (...) { failed = true; throw; }
-  }
-  return wait_batch(submit_batch(rgb, hs, ws, n_pages, mem, nullptr, nullptr, nullptr, nullptr, &rg));   // (clamped and opts outlive the wait)
-}
-
-// RettoWorkerStageResult JSON (serde derive shapes; retto-wasm/fe/index.ts:5-42)
-static std::string stage_json(const rt_results::Page& P, int stage) {
-  std::ostringstream o;
-  size_t n = P.det_scores.size();
-  if (stage == 0) {
-    o << "[";
-    for (size_t k = 0; k < n; k++) {
-      if (k) o << ",";
-      o << "{\"boxes\":{\"inner\":[";
-      for (int q = 0; q < 4; q++) { if (q) o << ","; o << "{\"x\":" << fnum(P.boxes[8 * k + 2 * q]) << ",\"y\":" << fnum(P.boxes[8 * k + 2 * q + 1]) << "}"; }
-      o << "]},\"score\":" << fnum(P.det_scores[k]) << "}";
-    }
-    o << "]";
-  } else if (stage == 1) {
-    o << "[";
-    for (size_t k = 0; k < n; k++) { if (k) o << ","; o << "{\"label\":{\"label\":" << P.cls_labels[k] << ",\"score\":" << fnum(P.cls_scores[k]) << "}}"; }
-    o << "]";
-  } else {
-    o << "[";
-    for (size_t k = 0; k < n; k++) { if (k) o << ","; o << "{\"text\":\"" << json_escape(P.text[k]) << "\",\"score\":" << fnum(P.rec_scores[k]) << "}"; }
-    o << "]";
-  }
-  return o.str();
-}
 const char* rt_results_json_impl(rt_results* r, int page, int stage) {
   rt_results::Page& P = r->pages[(size_t)page];
   P.json[stage] = stage_json(P, stage);
   return P.json[stage].c_str();
-}
-void rt_session::emit_stage(int page, int stage, const rt_results::Page& P) {
-  if (!stage_cb) return;
-  const std::string j = stage_json(P, stage);
-  std::unique_lock<std::mutex> lk;
-  if (stage_mu) lk = std::unique_lock<std::mutex>(*stage_mu);
-  stage_cb(stage_user, page_base + page, stage, j.c_str());
 }

@@ -1,6 +1,9 @@
-// Host scheduler: the MI355X counterpart of RettoSession::process_pipeline
-// (/root/reference/retto-core/src/session.rs:75-106) over a batch of pages, plus the
-// tensor-level worker entry points (worker.rs:69-73) and the stage functions.
+// Host scheduler: the MI355X counterpart of RettoSession::process_pipeline (retto-core/src/session.rs:75-106) over a batch of
+// pages, plus the tensor-level worker entry points (worker.rs:69-73) and the stage functions.  A pipeline call travels as one
+// value, PageCall; what runs it is a lane, rt_lane (stream, arenas, pinned staging, profile and the functions on that stream);
+// the session, rt_session, is lane 0 plus what exists once: config, networks, dictionary, rec stores, the setters' defaults, the
+// helper lanes with their threads, tickets and staging.  session.cpp: construction, the stage-level entries, the page pipeline;
+// session_batch.cpp: lanes at work, tickets, staging, encoded pages; rec_tail.cpp: the rec CTC tail and the stores' create calls.
 #pragma once
 #include <atomic>
 #include <chrono>
@@ -16,6 +19,7 @@
 #include "../../include/retto_hip.h"
 #include "image_decode.h"
 #include "jpeg_recon.h"
+#include "lane_split.h"
 #include "nets.h"
 #include "nets_f16.h"
 #include "prepost.h"
@@ -89,34 +93,61 @@ struct LaneWorker {
 // the rec beam (rt_set_rec_beam, ctc_beam.h; beam_b = 0: off) and the rec windows (rt_set_rec_windows, rec_windows.h; 0 = off)
 struct CallSettings { rt::RecLineOpts rec; int det_tile = 0, det_overlap = 0, beam_b = 0, beam_n = 0, rec_window = 0, rec_overlap = 0; };
 
+// One pipeline call over some pages: what rt_lane::run_pages runs, whoever asked for it (rt_run_batch, rt_submit_batch,
+// rt_run_regions*, a lane's part of a ticket).  Non-owning: every array has n_pages entries and belongs to the caller or the ticket.
+struct PageCall {
+  int n_pages = 0, mem = RT_MEM_HOST;
+  const uint8_t* const* rgb = nullptr;
+  const int* hs = nullptr;
+  const int* ws = nullptr;
+  const float* const* det_map_override = nullptr;   // or null
+  // rt_run_regions*: per page its quads (n_quads[i] x 8 floats, validated and clamped), their number and the regions' options,
+  // resolved (no -1) and checked (rt::resolve_region_opts); n_quads null: the detector finds the boxes; opts null: every line set.rec
+  const float* const* quads = nullptr;
+  const int* n_quads = nullptr;
+  const rt::RecLineOpts* const* region_opts = nullptr;
+  CallSettings set;
+  // run_stream (session.rs:133-143): stage results are handed to the callback as soon as the stage is complete -- Det after the
+  // box round trip (before any crop is classified or read), Cls and Rec when the call ends.  cb_mu (or null) serialises the
+  // callbacks of concurrent lanes; page_base = the global index of the call's first page
+  rt_stage_callback cb = nullptr;
+  void* user = nullptr;
+  std::mutex* cb_mu = nullptr;
+  int page_base = 0;
+  bool on_lane_worker = false;   // the call runs on a lane's worker thread (a submitted batch): only the spin window reads it
+  bool regions() const { return n_quads != nullptr; }
+  // the sub-call over pages [f0, f1)
+  PageCall part(int f0, int f1) const {
+    PageCall c = *this;
+    c.n_pages = f1 - f0; c.rgb += f0; c.hs += f0; c.ws += f0; c.page_base += f0;
+    if (det_map_override) c.det_map_override += f0;
+    if (quads) c.quads += f0;
+    if (n_quads) c.n_quads += f0;
+    if (region_opts) c.region_opts += f0;
+    return c;
+  }
+};
+
 // One submitted batch (rt_submit_batch): the argument arrays are copied (the PAGES must stay valid until rt_wait_batch), the
 // pages are split over the lanes exactly as rt_run_batch splits them, each lane leaves its part here.
 struct rt_ticket {
-  int nl = 0, n_pages = 0, mem = 0;
+  int nl = 0;
+  // what must outlive the submitting call, and the call over it as the lanes run it: on a lane's thread, with mem = pages on the
+  // device once they are staged (the regions' arrays stay the caller's: rt_run_regions* waits)
   std::vector<const uint8_t*> rgb;
   std::vector<int> hs, ws;
   std::vector<const float*> maps;   // empty: no override
-  // rt_run_regions: per page its quads (already validated and clamped, owned by the caller of submit_batch) and their number;
-  // empty: the detector finds the boxes
-  std::vector<const float*> quads;
-  std::vector<int> n_quads;
-  // the session's settings as they were when the batch was submitted (the lanes run later), and with rt_run_regions* per page
-  // the regions' resolved options (rec_line_opts.h; owned by the caller of submit_batch); empty: every line gets set.rec
-  CallSettings set;
-  std::vector<const rt::RecLineOpts*> region_opts;
+  PageCall call;
   std::vector<int> first;
   std::vector<rt_results*> parts;
   std::vector<std::exception_ptr> errs;
-  rt_stage_callback cb = nullptr;
-  void* user = nullptr;
   std::mutex cb_mu;                 // callbacks of concurrent lanes are serialised
   std::mutex mu;
   std::condition_variable cv;
   int remaining = 0;
-  // host pages staged by rt_submit_batch itself (session.cpp "page staging"): rgb[] then holds device addresses inside the
+  // host pages staged by rt_submit_batch itself (session_batch.cpp "page staging"): rgb[] then holds device addresses inside the
   // session's staging slot `stage_slot`, and the lanes wait for `ev_up` on their streams instead of copying
   int stage_slot = -1;
-  int mem_lane = 0;                 // what the lanes are told: mem, or pages-on-device once staged
   std::vector<size_t> stage_off;    // per page: offset inside the slot, (size_t)-1 = not staged (empty page)
   std::vector<hipEvent_t> ev_up;    // per lane part; owned by the staging slot
   // rt_submit_encoded_batch: the ticket owns the host-decoded pages (coefficients or pixels); stage_part uploads lane part l and
@@ -208,66 +239,32 @@ struct rt_keywords : rt_entry_store {
 // internal to the library (never accepted from a caller): pages already in HBM, det map overrides still host pointers
 #define RT_MEM_STAGED_MAPS_HOST 3
 
-struct rt_session {
-  rt_config cfg{};
-  int device = 0;
+// One lane of a session: a stream with the arenas, pinned staging and profile of the calls that run on it, and the functions that
+// run on that stream.  Lane 0 is the session itself (rt_session derives from rt_lane: the entry points and the debug hooks use
+// s->st, s->arena ...); the others are the session's helper lanes, which rt_run_batch / rt_submit_batch give parts of a batch on
+// concurrent host threads.  What every lane reads and none owns -- config, networks, dictionary, rec stores -- is the session's.
+struct rt_session;
+struct rt_lane {
+  const rt_session* sh = nullptr;  // the session's shared state
   hipStream_t st = nullptr;        // the stream the lane's current call runs on: st_full, or st_part inside a multi-lane batch
   hipStream_t st_full = nullptr;   // whole device
   hipStream_t st_part = nullptr;   // this lane's CU partition (runtime.h "CU partitions"); nullptr: not partitioned
   int part_cus = 0;
   hipEvent_t ev_block = nullptr;   // blocking-sync event behind sync(): the lane's host thread sleeps instead of spinning
+  int* d_flags = nullptr;          // [0] thumbnail/resize error flag
   rt::Arena arena;      // lives for one API call: pages, maps, crops, descriptors, outputs
   rt::Arena scratch;    // network activations; rewound per launch group
   rt::Arena dbws;       // DB post-processing workspace (stream-ordered reuse across pages)
   rt::Pinned pinned;
   rt::Profiler prof;
-  std::shared_ptr<rt::DetModel> det;   // weights are shared with the helper lanes
-  std::shared_ptr<rt::ClsModel> cls;
-  std::shared_ptr<rt::RecModel> rec;
-  std::string model_info;
-  // extra lanes: same networks and config, own stream / arenas; rt_run_batch splits the pages
-  // over the lanes and runs them on concurrent host threads
-  std::vector<std::unique_ptr<rt_session>> helpers;
-  int active_lanes = 1 << 30;  // rt_set_lanes: upper bound on the lanes rt_run_batch uses
-  std::vector<std::string> dict;  // RecCharacter (rec_processor.rs:29-46)
-  // the rec charsets, lexicons, patterns and keyword lists (shared with the helper lanes), and how many of each there are: the
-  // valid ids
-  std::shared_ptr<rt_charsets> charsets;
-  std::shared_ptr<rt_lexicons> lexicons;
-  std::shared_ptr<rt_patterns> patterns;
-  std::shared_ptr<rt_keywords> keywords;
-  rt::RecLineOpts rec_counts() const {
-    return {(int)charsets->ids.size(), (int)lexicons->host.size(), (int)patterns->host.size(), (int)keywords->host.size()};
-  }
-  // rt_set_rec_charset / _lexicon / _pattern / _keywords: the options of every line of the pipeline calls that follow, unless a region names
-  // its own (0: none)
-  rt::RecLineOpts rec_default;
-  // rt_set_det_tiles (det_tiles.h): pages whose det input is larger than det_tile either way are detected in tiles; 0 = off
-  int det_tile = 0, det_overlap = 0;
-  // rt_set_rec_beam (ctc_beam.h): every line of the pipeline calls that follow also reports its beam_n most probable strings from
-  // a prefix beam search of width beam_b; 0 = off
-  int beam_b = 0, beam_n = 0;
-  // rt_set_rec_windows (rec_windows.h): lines at least 8 columns wider than rec_window are read as overlapping windows whose
-  // trusted time steps are stitched into the line's rows; 0 = off
-  int rec_window = 0, rec_overlap = 0;
-  // A helper lane never reads its own rec_default / det_tile / det_overlap / beam_b / beam_n / rec_window / rec_overlap: a call
-  // carries the main lane's into run_pages
-  CallSettings settings() const { return {rec_default, det_tile, det_overlap, beam_b, beam_n, rec_window, rec_overlap}; }
-  uint8_t* d_word_raw = nullptr;  // rec_return_word_box: wb::raw_class of every dictionary entry (device; owned by the main lane)
-  std::string last_error;
-  int* d_flags = nullptr;         // [0] thumbnail/resize error flag
-  // run_stream (session.rs:133-143): stage results are handed to the callback as soon as the stage is complete --
-  // Det after the box round trip (before any crop is classified or read), Cls and Rec when the call ends.
-  rt_stage_callback stage_cb = nullptr;
-  void* stage_user = nullptr;
-  std::mutex* stage_mu = nullptr;  // callbacks of concurrent lanes are serialised
-  int page_base = 0;               // global index of this lane's first page
+  int spin_us = 5000;              // sync(): how long to poll before sleeping; run_pages chooses it per call
+  bool failed = false;             // the lane's previous call threw: its arena statistics are discarded at the next begin_call
   std::chrono::steady_clock::time_point last_exit = std::chrono::steady_clock::now();  // RT_TRACE only
-  void emit_stage(int page, int stage, const rt_results::Page& P);
+  // the lane's stream, flag word and blocking event on the session's device (which is current), and their release
+  void open(const rt_session* session);
+  void close();
 
   rt::RunCtx ctx(rt::Arena* a) { return rt::RunCtx{st, a, &pinned, &prof}; }
-  bool on_lane_worker = false;    // set by a lane's worker thread around run_pages (submitted batches): bounded polling there
-  int spin_us = 5000;              // sync(): how long to poll before sleeping; run_pages drops it to 50 for multi-page batches
   void begin_call();
   void sync();
   void check_flags();
@@ -352,6 +349,45 @@ struct rt_session {
   // Rec beams (ctc_beam.h) over the plan's beam lines, with k_ctc_row_lse: per chunk k_ctc_beam_topc, then k_ctc_beam_search on the
   // resident logits -> count / recs / tok.  The trie comes from `scratch`.  No host wait, and no value that anything else reads.
   void ctc_beams(const rt::RecTailPlan& plan, const rt::SvtrCore& core, const RecTail& t);
+  // L2: one pipeline call over its pages, on this lane
+  rt_results* run_pages(const PageCall& call);
+};
+
+// what a rule of rec_line_opts.h objects to, if anything
+inline void rt_refuse(const std::string& why) { if (!why.empty()) throw rt::RtError(RT_ERR_INVALID, why); }
+
+// The session: lane 0, and what the session owns once -- what every lane reads (config, device, networks, dictionary, rec
+// stores), the defaults the setters write, the helper lanes with their host threads, the staging slots and the last error.
+struct rt_session : rt_lane {
+  rt_config cfg{};
+  int device = 0;
+  std::unique_ptr<rt::DetModel> det;
+  std::unique_ptr<rt::ClsModel> cls;
+  std::unique_ptr<rt::RecModel> rec;
+  std::string model_info;
+  std::vector<std::string> dict;  // RecCharacter (rec_processor.rs:29-46)
+  // the rec charsets, lexicons, patterns and keyword lists, and how many of each there are: the valid ids
+  std::unique_ptr<rt_charsets> charsets;
+  std::unique_ptr<rt_lexicons> lexicons;
+  std::unique_ptr<rt_patterns> patterns;
+  std::unique_ptr<rt_keywords> keywords;
+  rt::RecLineOpts rec_counts() const {
+    return {(int)charsets->ids.size(), (int)lexicons->host.size(), (int)patterns->host.size(), (int)keywords->host.size()};
+  }
+  uint8_t* d_word_raw = nullptr;  // rec_return_word_box: wb::raw_class of every dictionary entry (device)
+  // rt_set_rec_charset / _lexicon / _pattern / _keywords: the options of every line of the pipeline calls that follow, unless a region names
+  // its own (0: none)
+  rt::RecLineOpts rec_default;
+  // rt_set_det_tiles (det_tiles.h): pages whose det input is larger than det_tile either way are detected in tiles; 0 = off
+  int det_tile = 0, det_overlap = 0;
+  // rt_set_rec_beam (ctc_beam.h): every line of the pipeline calls that follow also reports its beam_n most probable strings from
+  // a prefix beam search of width beam_b; 0 = off
+  int beam_b = 0, beam_n = 0;
+  // rt_set_rec_windows (rec_windows.h): lines at least 8 columns wider than rec_window are read as overlapping windows whose
+  // trusted time steps are stitched into the line's rows; 0 = off
+  int rec_window = 0, rec_overlap = 0;
+  CallSettings settings() const { return {rec_default, det_tile, det_overlap, beam_b, beam_n, rec_window, rec_overlap}; }
+  std::string last_error;
   // rt_charset_create: compiles the set (rt::compile_charset), stores it and returns its id
   int charset_create(const char* utf8, size_t len, const int32_t* ids, int n_ids);
   // rt_lexicon_create: the entries into the lexicon store (rt_entry_store::add); returns the lexicon's id
@@ -362,12 +398,26 @@ struct rt_session {
   int pattern_create(const char* utf8, size_t len);
   // rt_lexicon_set_snap: the lexicon's min_posterior (ctc_lexicon_align.h), on the host and in the device table
   void lexicon_set_snap(int lexicon, float min_posterior);
-  // L2
-  // persistent lane threads (index 0 = this session's own lane) and the number of submitted, not yet waited batches
+  // rt_debug_det_tiles: the det stage of a one-page call on a host RGB8 image at det-input size h x w, through the pipeline's own
+  // det_groups under the session's det tiles; tile_maps_out: every tile's own map packed in plan order, page_map_out [h * w]
+  void debug_det_tiles(const uint8_t* rgb_det, int h, int w, float* tile_maps_out, float* page_map_out);
+  // rt_debug_rec_windows: n lines of [3, 48, widths[i]] (host, NCHW, concatenated) as ONE rec group through the pipeline's own
+  // cut, network and stitch (rec_group_net) under the session's rec windows.  Every output is optional and on the host: the
+  // units' rows in unit order, line after line (idx / prob [unit rows], z5 [unit rows][120]), and the lines' stitched rows
+  void debug_rec_windows(const float* nchw, int n, const int* widths, int32_t* unit_idx_out, float* unit_prob_out, float* unit_z5_out,
+                         int32_t* line_idx_out, float* line_prob_out, float* line_z5_out);
+
+  // ---- lanes, tickets, staging (session_batch.cpp) ----
+  // extra lanes: own stream / arenas; rt_run_batch splits the pages over the lanes and runs them on concurrent host threads
+  std::vector<std::unique_ptr<rt_lane>> helpers;
+  int n_lanes() const { return (int)helpers.size() + 1; }
+  rt_lane* lane(int l) { return l == 0 ? this : helpers[(size_t)l - 1].get(); }
+  int active_lanes = 1 << 30;  // rt_set_lanes: upper bound on the lanes rt_run_batch uses
+  int lanes_for(int n_pages) const { return rt::lanes_for(n_lanes(), active_lanes, n_pages); }
+  // persistent lane threads (one per lane) and the number of submitted, not yet waited batches
   std::vector<std::unique_ptr<LaneWorker>> workers;
   std::atomic<int> inflight{0};
   int next_lane = 0;               // first lane of the next submitted batch
-  bool failed = false;             // the lane's previous call threw: its arena statistics are discarded at the next begin_call
   // page staging: host pages of a submitted batch are copied to HBM by the submitting thread on a copy stream of their own, one
   // batch ahead of the lanes that read them (slots are reused; one per batch in flight)
   struct StageSlot { uint8_t* p = nullptr; size_t cap = 0; std::vector<hipEvent_t> ev; bool busy = false; };
@@ -379,34 +429,25 @@ struct rt_session {
   void release_stage(rt_ticket* t);
   void free_stage();
   void ensure_workers();
-  // regions (rt_run_regions): quads[i] = n_quads[i] x 8 validated, clamped floats of page i, valid until the ticket is waited for
-  // opts: per page the regions' options, already resolved (no -1) and checked (rt::resolve_region_opts); null: the call's defaults
-  struct Regions { const float* const* quads; const int* n_quads; const rt::RecLineOpts* const* opts = nullptr; };
-  rt_ticket* submit_batch(const uint8_t* const* rgb, const int* hs, const int* ws, int n_pages, int mem,
-                          const float* const* det_map_override, rt_stage_callback cb = nullptr, void* user = nullptr,
-                          std::vector<rt::EncodedPage>* enc = nullptr, const Regions* regions = nullptr);
+  // a pipeline call over the caller's arrays under the session's settings as they are now
+  PageCall call_of(const uint8_t* const* rgb, const int* hs, const int* ws, int n_pages, int mem, const float* const* det_map_override = nullptr,
+                   rt_stage_callback cb = nullptr, void* user = nullptr) const {
+    return PageCall{n_pages, mem, rgb, hs, ws, det_map_override, nullptr, nullptr, nullptr, settings(), cb, user};
+  }
+  // the call's pages split over the lanes and queued on their threads; enc: the call's pages are these, still encoded
+  rt_ticket* submit_batch(const PageCall& call, std::vector<rt::EncodedPage>* enc = nullptr);
+  rt_results* wait_batch(rt_ticket* t);   // consumes the ticket
+  // a call that takes one lane: on the caller's thread, lane 0 (no hand-over in the single-page latency path)
+  rt_results* run_on_caller(const PageCall& call);
+  rt_results* run_batch(const PageCall& call);
   // rt_decode_batch: pages through the host stage and the reconstruction kernels into out[i] (mem: RT_MEM_HOST / RT_MEM_DEVICE)
   void decode_batch(std::vector<rt::EncodedPage>& enc, uint8_t* const* out, int mem);
-  rt_results* wait_batch(rt_ticket* t);   // consumes the ticket
-  rt_results* run_batch(const uint8_t* const* rgb, const int* hs, const int* ws, int n_pages, int mem,
-                        const float* const* det_map_override, rt_stage_callback cb = nullptr, void* user = nullptr);
-  rt_results* run_pages(const uint8_t* const* rgb, const int* hs, const int* ws, int n_pages, int mem,
-                        const float* const* det_map_override, const Regions* regions, const CallSettings& set);  // one lane
-  // rt_debug_det_tiles: the det stage of a one-page call on a host RGB8 image at det-input size h x w, through the pipeline's own
-  // det_groups under the session's det tiles; tile_maps_out: every tile's own map packed in plan order, page_map_out [h * w]
-  void debug_det_tiles(const uint8_t* rgb_det, int h, int w, float* tile_maps_out, float* page_map_out);
-  // rt_debug_rec_windows: n lines of [3, 48, widths[i]] (host, NCHW, concatenated) as ONE rec group through the pipeline's own
-  // cut, network and stitch (rec_group_net) under the session's rec windows.  Every output is optional and on the host: the
-  // units' rows in unit order, line after line (idx / prob [unit rows], z5 [unit rows][120]), and the lines' stitched rows
-  void debug_rec_windows(const float* nchw, int n, const int* widths, int32_t* unit_idx_out, float* unit_prob_out, float* unit_z5_out,
-                         int32_t* line_idx_out, float* line_prob_out, float* line_z5_out);
   // rt_run_regions: checks and clamps every quad (RT_ERR_INVALID naming page and region; nothing is queued then), then the
   // pages go over the lanes as run_batch's do, from the crop plan on
-  // charsets, lexicons, patterns, keywords (each or null; entries may be null): per region -1 = the session default, 0 = none, >= 1 = that
-  // id (rt::resolve_region_opts); a region may not carry both a pattern and a lexicon
+  // ids[j] (the kinds of rec_line_opts.h: charsets, lexicons, patterns, keywords; each or null; entries may be null): per region
+  // -1 = the session default, 0 = none, >= 1 = that id (rt::resolve_region_opts); a region may not carry both a pattern and a lexicon
   rt_results* run_regions(const uint8_t* const* rgb, const int* hs, const int* ws, int n_pages, int mem,
-                          const float* const* quads, const int* n_quads, const int* const* charsets, const int* const* lexicons,
-                          const int* const* patterns, const int* const* keywords = nullptr);
+                          const float* const* quads, const int* n_quads, const int* const* const ids[rt::REC_N_KINDS]);
 };
 
 rt_session* rt_session_create(const rt_config* cfg);

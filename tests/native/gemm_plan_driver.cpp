@@ -1,6 +1,6 @@
 // Host-only driver of nn::gemm_plan() / nn::gemm_se_rows() (retto_amd/csrc/gemm_plan.cpp) and nn::dw_plan() / nn::lc_plan()
 // (lc_plan.cpp) for tests/test_gemm_plan_cpu.py and tests/test_lc_plan_cpu.py, and of the host-only headers rec_tail_plan.h
-// (tests/test_rec_tail_plan_cpu.py) and rec_line_opts.h (tests/test_rec_line_opts_cpu.py).
+// (tests/test_rec_tail_plan_cpu.py), rec_line_opts.h (tests/test_rec_line_opts_cpu.py) and lane_split.h (tests/test_lane_split_cpu.py).
 // One query per stdin line, one answer per stdout line:
 //   plan <variant> <dma> <split> <argmax_wide> <cus> <lda> <M> <K> <N> <Npad16> <ldc> <coff>
 //        <am_max> <residual> <a_scale> <a_tab_stride> <act> <has_lab> <n_img> <ld_scale>
@@ -27,7 +27,10 @@
 //     -> resolve_region_opts() (rec_line_opts.h) of all pages: ok <per page charset:lexicon:pattern,.. or ->   or   error: <message>
 //   lines <defaults> <counts> <n_pages> <boxes of each page> then 0 = the defaults, or 1 and every box's charset lexicon pattern
 //     -> expand_line_opts() over pages whose first lines follow each other: any=c,l,p lines=charset:lexicon:pattern,..  or  error: ..
+//   split <lanes> <active> <max_side_len> <nl> <n_pages> <h w of each page>
+//     -> lanes_for(lanes, active, n_pages) then lane_split() of the pages over nl lanes (lane_split.h): <lanes_for> <first[0..nl]>
 // (am_max != 0 sets the CTC-head statistics with am_tiles = gemm_argmax_tiles(Npad16); a_scale != 0 sets a scale and a row table)
+#include "lane_split.h"
 #include "nn.h"
 #include "rec_tail_plan.h"
 
@@ -262,6 +265,16 @@ int main() {
         }
       }
       if (!bad.empty()) printf("error: %s", bad.c_str());
+      printf("\n");
+    } else if (op == "split") {
+      int lanes, active, max_side_len, nl, n_pages = 0;
+      in >> lanes >> active >> max_side_len >> nl >> n_pages;
+      if (!in || nl < 1 || n_pages < 0) { printf("bad query\n"); return 2; }
+      std::vector<int> hs((size_t)n_pages), ws((size_t)n_pages);
+      for (int i = 0; i < n_pages; i++) in >> hs[(size_t)i] >> ws[(size_t)i];
+      if (!in) { printf("bad query\n"); return 2; }
+      printf("%d", lanes_for(lanes, active, n_pages));
+      for (int f : lane_split(hs.data(), ws.data(), n_pages, max_side_len, nl)) printf(" %d", f);
       printf("\n");
     } else if (!op.empty()) {
       printf("unknown query %s\n", op.c_str());

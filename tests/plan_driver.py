@@ -1,6 +1,6 @@
 """The host-only plan driver (tests/native/gemm_plan_driver.cpp + the plan sources of retto_amd/csrc, compiled with g++: no GPU,
 no HIP runtime), built once per test session and shared by test_gemm_plan_cpu.py, test_lc_plan_cpu.py,
-test_rec_tail_plan_cpu.py and test_rec_line_opts_cpu.py."""
+test_rec_tail_plan_cpu.py, test_rec_line_opts_cpu.py and test_lane_split_cpu.py."""
 import os
 import subprocess
 
