@@ -719,6 +719,71 @@ RT_API int rt_debug_ctc_beam(rt_session* s, const float* z5, const float* W, con
 /* The same rule on the CPU in plain fp32 loops (ctc_beam.h), GPU-free and sessionless; same layout. */
 RT_API int rt_debug_ctc_beam_host(const float* z5, const float* W, const float* bias, int N, const int32_t* tokens_per_line,
                                   int n_lines, int beam, int nbest, int32_t* counts_out, rt_beam* beams_out, int32_t* tokens_out);
+
+/* ---- rec language model: a character n-gram fused into the beam search -----------------------------------------------------------
+ * The standard companion of a CTC prefix beam search.  Re-ranking the N-best list afterwards is not the same thing: a string that
+ * was pruned at step t cannot come back, so the model acts inside every step's selection.  retto_amd/csrc/ctc_lm.h states the
+ * rule; in short:
+ *   model    a back-off n-gram over the recogniser's classes, order 1 .. RT_MAX_LM_ORDER, at most RT_MAX_LM_NGRAMS n-grams, given
+ *            as ARPA text ("\data\", "ngram k=count", "\k-grams:" sections of "log10 p <tab> tokens [<tab> log10 backoff]",
+ *            "\end\").  A token is the UTF-8 text of one dictionary entry, "<sp>" the entry that is U+0020, "<s>" the line start.
+ *            An n-gram with "</s>" or with a token the dictionary lacks is dropped and counted; "<unk>"'s unigram, if present,
+ *            gives the out-of-vocabulary log-probability, else oov_log10 does (finite, at most 0);
+ *   lm       of a string: the sum over its tokens, in reading order from the start state, of the model's log-probability (natural
+ *            log, fp32) of the token after its context, backing off as ARPA models do; 0 for the empty string;
+ *   fused    score = logprob + (alpha * lm + beta * n_tokens); alpha >= 0, both finite;
+ *   step     the beam's rule with one change: the best B candidates are the best by fused score (ties as before).
+ * rt_beam.logprob stays the CTC total, never above the string's full likelihood; the hypotheses come in fused order.  Everything
+ * else of a call -- and, with no model attached, the hypotheses too -- is what it is without it, bit for bit; the per-stage JSON
+ * stays as it is.  What the model does to accuracy with the real PP-OCRv4 weights has not been measured.
+ *
+ * rt_lm_create: compiles arpa [len] over the session's dictionary and puts its tables on the device; *lm_out = its handle, 0-based,
+ * valid until rt_destroy; a session holds at most RT_MAX_LMS.  RT_ERR_INVALID with a message that names the line for a number that
+ * is not finite, an n-gram that is there twice, an n-gram whose context (its first k - 1 tokens) is not an n-gram, an order above
+ * RT_MAX_LM_ORDER, more than RT_MAX_LM_NGRAMS kept n-grams, a malformed line or a file without its end mark; RT_ERR_CAPACITY past
+ * RT_MAX_LMS.  Fails like every other call while tickets are in flight.
+ * rt_lm_info: the model's order, its kept and dropped n-grams and its states (each optional); RT_ERR_INVALID for an unknown handle.
+ * rt_set_rec_beam_lm: lm = -1 switches fusion off; otherwise a handle, alpha >= 0 and both weights finite, else RT_ERR_INVALID.
+ * Legal while beam = 0, and without effect until rt_set_rec_beam sets one; it applies to every pipeline call that follows and
+ * fails like the other setters while tickets are in flight.  rt_rec_beam_lm reads the three values back (each optional). */
+#define RT_MAX_LM_ORDER 5
+#define RT_MAX_LM_NGRAMS (1 << 22)
+#define RT_MAX_LMS 4
+typedef struct rt_beam_lm { float lm; float score; } rt_beam_lm;
+RT_API int rt_lm_create(rt_session* s, const char* arpa, size_t len, float oov_log10, int* lm_out);
+RT_API int rt_lm_info(const rt_session* s, int lm, int* order, int* ngrams, int* dropped, int* states);
+RT_API int rt_set_rec_beam_lm(rt_session* s, int lm, float alpha, float beta);
+RT_API int rt_rec_beam_lm(const rt_session* s, int* lm, float* alpha, float* beta);
+/* the lm and fused score of a line's hypotheses, beside rt_results_rec_beams' records: their number, and 0 with nothing written
+ * when fusion was off; *out (optional): the records, best first */
+RT_API int rt_results_rec_beam_lm(const rt_results* r, int page, int line, const rt_beam_lm** out);
+/* The ARPA compiler without a session: dict [dict_len] as rt_config.dict, arpa [len], oov_log10 -> the id form: n-gram i has
+ * ngram_lens_out[i] ids, one n-gram after the other in ngram_ids_out (<s> = *n_classes), with logp_out[i] and backoff_out[i] as
+ * NATURAL logs.  *n_out, *n_ids_out: how many n-grams and ids there are (also when a cap was too small: RT_ERR_INVALID then,
+ * nothing copied); *order_out, *dropped_out, *states_out: as rt_lm_info; *oov_out: the out-of-vocabulary log-probability, natural. */
+RT_API int rt_debug_lm_compile(const void* dict, size_t dict_len, const char* arpa, size_t len, float oov_log10, int32_t* ngram_ids_out,
+                               int ids_cap, int32_t* ngram_lens_out, float* logp_out, float* backoff_out, int n_cap, int* n_ids_out,
+                               int* n_out, int* order_out, int* dropped_out, int* states_out, float* oov_out, int* n_classes,
+                               char* err, size_t err_cap);
+/* A model in its id form over `classes` classes (oov: natural log) compiled and walked on the host: string i has string_lens[i]
+ * ids of [1, classes), one string after the other in strings; lm_out[i]: its lm; state_out[i]: the state it ends in (0: the empty
+ * context; k + 1: the k-th n-gram of the id form among those shorter than the order).  Refusals as rt_lm_create's, naming the
+ * n-gram's index. */
+RT_API int rt_debug_lm_score(int classes, const int32_t* ngram_ids, const int32_t* ngram_lens, const float* logp, const float* backoff,
+                             int n, float oov, const int32_t* strings, const int32_t* string_lens, int n_strings, float* lm_out,
+                             int32_t* state_out, char* err, size_t err_cap);
+/* rt_debug_ctc_beam with a model in its id form over the head's N classes and the weights: the device path with
+ * k_ctc_beam_search's fused variant.  lm_out [n_lines][nbest] beside beams_out; slots past a line's count come back as the caller
+ * put them.  A bad model or weight is refused before any launch. */
+RT_API int rt_debug_ctc_beam_lm(rt_session* s, const float* z5, const float* W, const float* bias, int N, const int32_t* tokens_per_line,
+                                int n_lines, int beam, int nbest, int chunk_rows, const int32_t* ngram_ids, const int32_t* ngram_lens,
+                                const float* logp, const float* backoff, int n, float oov, float alpha, float beta,
+                                int32_t* counts_out, rt_beam* beams_out, int32_t* tokens_out, rt_beam_lm* lm_out);
+/* The same rule on the CPU in plain fp32 loops (ctc_beam.h, ctc_lm.h), GPU-free and sessionless; same layout. */
+RT_API int rt_debug_ctc_beam_lm_host(const float* z5, const float* W, const float* bias, int N, const int32_t* tokens_per_line,
+                                     int n_lines, int beam, int nbest, const int32_t* ngram_ids, const int32_t* ngram_lens,
+                                     const float* logp, const float* backoff, int n, float oov, float alpha, float beta,
+                                     int32_t* counts_out, rt_beam* beams_out, int32_t* tokens_out, rt_beam_lm* lm_out);
 /* f32 sum of every det probability map produced in the call (keeps the network's
  * output observable when det_map_override is used) */
 RT_API double rt_results_det_checksum(const rt_results* r);

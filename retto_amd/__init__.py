@@ -194,6 +194,10 @@ class BeamHypothesis:   # rt_beam, with its tokens and text
     tokens: np.ndarray    # int32 class ids in reading order; empty: the empty string
     text: str
     logprob: float        # log of the summed probability of the string's alignments that stayed inside the beam
+    # rec language model (set_rec_beam_lm; rt_beam_lm): None when fusion was off, else the model's sum over the string (natural
+    # log) and the fused score logprob + (alpha * lm_logprob + beta * len(tokens)) the hypotheses are ordered by
+    lm_logprob: Optional[float] = None
+    lm_score: Optional[float] = None
 
 
 @dataclass
@@ -751,12 +755,15 @@ class RettoSession:
         lib = self._hd.lib
         bp = C.POINTER(_lib.Beam)()
         n = lib.rt_results_rec_beams(r, page, line, C.byref(bp))
+        lp = C.POINTER(_lib.BeamLm)()
+        fused = lib.rt_results_rec_beam_lm(r, page, line, C.byref(lp)) == n and bool(lp)
         out = []
         for k in range(n):
             tp = C.POINTER(C.c_int32)()
             nt = lib.rt_results_rec_beam_tokens(r, page, line, k, C.byref(tp))
             out.append(BeamHypothesis(np.array([tp[i] for i in range(nt)], np.int32),
-                                      lib.rt_results_rec_beam_text(r, page, line, k).decode("utf-8"), float(bp[k].logprob)))
+                                      lib.rt_results_rec_beam_text(r, page, line, k).decode("utf-8"), float(bp[k].logprob),
+                                      float(lp[k].lm) if fused else None, float(lp[k].score) if fused else None))
         return out
 
     def _lexicon_matches(self, r, page: int, line: int):
@@ -805,6 +812,36 @@ class RettoSession:
         b, n = C.c_int(), C.c_int()
         _check(self._hd.lib.rt_rec_beam(self._hd.h, C.byref(b), C.byref(n)), self._hd.h)
         return b.value, n.value
+
+    # -- rec language model ------------------------------------------------------------------
+    def create_lm(self, data, oov_log10: float = -7.0) -> int:
+        """rt_lm_create: a character n-gram language model in ARPA text (str or bytes) over the session's dictionary
+        (retto_amd/csrc/ctc_lm.h): a token is one dictionary entry, "<sp>" the space, "<s>" the line start.  oov_log10: the
+        log10 probability of a class the model has no unigram for, unless the file has an "<unk>" unigram.  Returns the model's
+        handle (0-based, valid for the session's life; at most MAX_LMS); see set_rec_beam_lm."""
+        raw = data.encode("utf-8") if isinstance(data, str) else bytes(data)
+        out = C.c_int()
+        _check(self._hd.lib.rt_lm_create(self._hd.h, raw, len(raw), float(oov_log10), C.byref(out)), self._hd.h)
+        return out.value
+
+    def lm_info(self, lm: int) -> Optional[dict]:
+        """rt_lm_info: {order, ngrams, dropped, states} of a language model; None for an unknown handle."""
+        o, n, d, s = C.c_int(), C.c_int(), C.c_int(), C.c_int()
+        if self._hd.lib.rt_lm_info(self._hd.h, int(lm), C.byref(o), C.byref(n), C.byref(d), C.byref(s)) != 0:
+            return None
+        return {"order": o.value, "ngrams": n.value, "dropped": d.value, "states": s.value}
+
+    def set_rec_beam_lm(self, lm: int, alpha: float = 1.0, beta: float = 0.0) -> None:
+        """rt_set_rec_beam_lm: the beam search of the pipeline calls that follow keeps, at every step, the candidates with the
+        best logprob + (alpha * lm + beta * length) under model ``lm`` (BeamHypothesis.lm_logprob / lm_score); lm = -1: off, the
+        default.  Without effect until set_rec_beam sets a beam.  alpha >= 0; both finite."""
+        _check(self._hd.lib.rt_set_rec_beam_lm(self._hd.h, int(lm), float(alpha), float(beta)), self._hd.h)
+
+    def rec_beam_lm(self) -> Tuple[int, float, float]:
+        """rt_rec_beam_lm: (lm, alpha, beta) as set; lm -1 = off."""
+        m, a, b = C.c_int(), C.c_float(), C.c_float()
+        _check(self._hd.lib.rt_rec_beam_lm(self._hd.h, C.byref(m), C.byref(a), C.byref(b)), self._hd.h)
+        return m.value, a.value, b.value
 
     @property
     def det_tiles(self) -> Tuple[int, int]:

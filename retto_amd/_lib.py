@@ -70,7 +70,14 @@ class Beam(C.Structure):   # rt_beam
     _fields_ = [("logprob", C.c_float), ("n_tokens", C.c_int32)]
 
 
+class BeamLm(C.Structure):   # rt_beam_lm
+    _fields_ = [("lm", C.c_float), ("score", C.c_float)]
+
+
 MAX_BEAM = 32                # RT_MAX_BEAM
+MAX_LM_ORDER = 5             # RT_MAX_LM_ORDER
+MAX_LM_NGRAMS = 1 << 22      # RT_MAX_LM_NGRAMS
+MAX_LMS = 4                  # RT_MAX_LMS
 MAX_NBEST = 8                # RT_MAX_NBEST
 MAX_KEYWORD_LISTS = 16       # RT_MAX_KEYWORD_LISTS
 KEYWORD_HITS = 8             # RT_KEYWORD_HITS
@@ -114,6 +121,8 @@ EXPORTS = [
     "rt_debug_ctc_keywords_host", "rt_debug_span_quad",
     "rt_set_rec_beam", "rt_rec_beam", "rt_results_rec_beams", "rt_results_rec_beam_tokens", "rt_results_rec_beam_text",
     "rt_debug_ctc_beam", "rt_debug_ctc_beam_host",
+    "rt_lm_create", "rt_lm_info", "rt_set_rec_beam_lm", "rt_rec_beam_lm", "rt_results_rec_beam_lm", "rt_debug_lm_compile",
+    "rt_debug_lm_score", "rt_debug_ctc_beam_lm", "rt_debug_ctc_beam_lm_host",
     "rt_set_det_tiles", "rt_det_tiles", "rt_det_tile_plan", "rt_debug_det_tiles", "rt_debug_arena_high_water", "rt_bench_memcpy_d2d",
     "rt_set_rec_windows", "rt_rec_windows", "rt_rec_window_plan", "rt_results_rec_windows", "rt_debug_rec_windows",
 ]
@@ -351,6 +360,22 @@ def load():
                                       C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.rt_debug_ctc_beam_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int,
                                            C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.rt_lm_create.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t, C.c_float, P(C.c_int)]
+    lib.rt_lm_info.argtypes = [C.c_void_p, C.c_int, P(C.c_int), P(C.c_int), P(C.c_int), P(C.c_int)]
+    lib.rt_set_rec_beam_lm.argtypes = [C.c_void_p, C.c_int, C.c_float, C.c_float]
+    lib.rt_rec_beam_lm.argtypes = [C.c_void_p, P(C.c_int), P(C.c_float), P(C.c_float)]
+    lib.rt_results_rec_beam_lm.argtypes = [C.c_void_p, C.c_int, C.c_int, P(P(BeamLm))]
+    lib.rt_debug_lm_compile.argtypes = [C.c_char_p, C.c_size_t, C.c_char_p, C.c_size_t, C.c_float, C.c_void_p, C.c_int, C.c_void_p,
+                                        C.c_void_p, C.c_void_p, C.c_int, P(C.c_int), P(C.c_int), P(C.c_int), P(C.c_int), P(C.c_int),
+                                        P(C.c_float), P(C.c_int), C.c_char_p, C.c_size_t]
+    lib.rt_debug_lm_score.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_void_p,
+                                      C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_char_p, C.c_size_t]
+    lib.rt_debug_ctc_beam_lm.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int,
+                                         C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_float,
+                                         C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.rt_debug_ctc_beam_lm_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int,
+                                              C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_float, C.c_float,
+                                              C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.rt_set_det_tiles.argtypes = [C.c_void_p, C.c_int, C.c_int]
     lib.rt_det_tiles.argtypes = [C.c_void_p, P(C.c_int), P(C.c_int)]
     lib.rt_det_tile_plan.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, P(C.c_int32), P(C.c_int32), C.c_int, P(C.c_int32), P(C.c_int32),

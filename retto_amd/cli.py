@@ -64,7 +64,33 @@ def build_parser() -> argparse.ArgumentParser:
                          "at least 128; 0 = off")
     ap.add_argument("--rec-window-overlap", type=int, default=0, metavar="M",
                     help="with --rec-window: the windows' overlap, a multiple of 32, at most N / 2")
+    ap.add_argument("--rec-beam", default=None, metavar="B[,N]",
+                    help="rec beams: every line also reports its N (default 1) most probable strings from a CTC prefix beam "
+                         "search of width B (1..32; N up to min(B, 8)); each --json line gains a \"beams\" array (per line)")
+    ap.add_argument("--rec-lm", default=None, metavar="FILE",
+                    help="with --rec-beam: a character n-gram language model in ARPA text over the dictionary (tokens: one "
+                         "dictionary entry each, <sp> the space, <s> the line start), fused into the beam search; the "
+                         "hypotheses gain \"lm_logprob\" and \"lm_score\" (the effect on accuracy is not measured)")
+    ap.add_argument("--rec-lm-weights", default="1.0,0.0", metavar="ALPHA,BETA",
+                    help="with --rec-lm: the beam keeps the candidates with the best logprob + ALPHA * lm + BETA * length")
     return ap
+
+
+def parse_beam(text: str):
+    """--rec-beam's "B" or "B,N" -> (B, N)"""
+    parts = text.split(",")
+    if len(parts) not in (1, 2) or not all(p.strip().lstrip("+").isdigit() for p in parts):
+        raise SystemExit("--rec-beam takes B or B,N")
+    return int(parts[0]), int(parts[1]) if len(parts) == 2 else 1
+
+
+def parse_weights(text: str):
+    """--rec-lm-weights' "ALPHA,BETA" -> (alpha, beta)"""
+    try:
+        alpha, beta = (float(p) for p in text.split(","))
+    except ValueError:
+        raise SystemExit("--rec-lm-weights takes ALPHA,BETA")
+    return alpha, beta
 
 
 def walk_files(root: str):
@@ -112,6 +138,13 @@ def main(argv=None) -> int:
         if a.rec_lexicon is not None:
             raise SystemExit("--rec-pattern and --rec-lexicon exclude each other")
         session.set_rec_pattern(session.create_pattern(a.rec_pattern))
+    if a.rec_beam is not None:
+        session.set_rec_beam(*parse_beam(a.rec_beam))
+    if a.rec_lm is not None:
+        if a.rec_beam is None:
+            raise SystemExit("--rec-lm needs --rec-beam")
+        with open(a.rec_lm, "rb") as f:
+            session.set_rec_beam_lm(session.create_lm(f.read()), *parse_weights(a.rec_lm_weights))
     files = walk_files(a.images)
     log.info("Found %d files, processing...", len(files))
     out = open(a.json, "w") if a.json else None
@@ -150,6 +183,10 @@ def main(argv=None) -> int:
                     rec["pattern"] = [None if t.pattern is None else
                                       {"matched": t.pattern[0], "logprob": t.pattern[1] if t.pattern[0] else None,
                                        "free_logprob": t.pattern[2]} for t in r.rec_result]
+                if a.rec_beam is not None:   # per line: its hypotheses, best first; lm_logprob / lm_score with --rec-lm
+                    rec["beams"] = [[dict({"text": h.text, "tokens": [int(c) for c in h.tokens], "logprob": h.logprob},
+                                          **({} if h.lm_score is None else {"lm_logprob": h.lm_logprob, "lm_score": h.lm_score}))
+                                     for h in (t.beams or [])] for t in r.rec_result]
                 out.write(json.dumps(rec, ensure_ascii=False) + "\n")
     dur = time.perf_counter() - start
     if out:

@@ -382,6 +382,37 @@ int rt_rec_beam(const rt_session* s, int* beam, int* nbest) {
   if (nbest) *nbest = s->beam_n;
   return RT_OK;
 }
+int rt_lm_create(rt_session* s, const char* arpa, size_t len, float oov_log10, int* lm_out) {
+  RT_REQUIRE(s && lm_out && (arpa || !len), s, "rt_lm_create: bad argument");
+  *lm_out = -1;
+  return guarded(s, [&] { *lm_out = s->lm_create(arpa, len, oov_log10); });
+}
+int rt_lm_info(const rt_session* s, int lm, int* order, int* ngrams, int* dropped, int* states) {
+  if (!s || !s->lms || lm < 0 || lm >= (int)s->lms->host.size()) return RT_ERR_INVALID;
+  const lm::Model& m = *s->lms->host[(size_t)lm];
+  if (order) *order = m.order;
+  if (ngrams) *ngrams = m.n_ngrams;
+  if (dropped) *dropped = m.dropped;
+  if (states) *states = (int)m.states.size();
+  return RT_OK;
+}
+int rt_set_rec_beam_lm(rt_session* s, int lm, float alpha, float beta) {
+  RT_REQUIRE(s, s, "rt_set_rec_beam_lm: null session");
+  return guarded(s, [&] {
+    if (lm == -1) { s->beam_lm = -1; s->lm_alpha = s->lm_beta = 0.0f; return; }
+    if (lm < 0 || lm >= (int)s->lms->host.size())
+      throw RtError(RT_ERR_INVALID, "rt_set_rec_beam_lm: " + std::to_string(lm) + " is not a language model of this session");
+    if (const char* why = lm::check_weights(alpha, beta)) throw RtError(RT_ERR_INVALID, std::string("rt_set_rec_beam_lm: ") + why);
+    s->beam_lm = lm; s->lm_alpha = alpha; s->lm_beta = beta;
+  });
+}
+int rt_rec_beam_lm(const rt_session* s, int* lm, float* alpha, float* beta) {
+  if (!s) return RT_ERR_INVALID;
+  if (lm) *lm = s->beam_lm;
+  if (alpha) *alpha = s->lm_alpha;
+  if (beta) *beta = s->lm_beta;
+  return RT_OK;
+}
 int rt_set_rec_windows(rt_session* s, int window, int overlap) {
   RT_REQUIRE(s, s, "rt_set_rec_windows: null session");
   return guarded(s, [&] {
@@ -683,6 +714,12 @@ int rt_results_rec_beams(const rt_results* r, int page, int line, const rt_beam*
   auto* p = page_of_line(r, page, line, &rt_results::Page::bm_count);
   if (!p || p->beam_n <= 0) return 0;
   if (out) *out = reinterpret_cast<const rt_beam*>(p->bm_recs.data()) + (size_t)line * p->beam_n;
+  return p->bm_count[(size_t)line];
+}
+int rt_results_rec_beam_lm(const rt_results* r, int page, int line, const rt_beam_lm** out) {
+  auto* p = page_of_line(r, page, line, &rt_results::Page::bm_count);
+  if (!p || p->beam_n <= 0 || p->bm_lm.empty()) return 0;
+  if (out) *out = reinterpret_cast<const rt_beam_lm*>(p->bm_lm.data()) + (size_t)line * p->beam_n;
   return p->bm_count[(size_t)line];
 }
 int rt_results_rec_beam_tokens(const rt_results* r, int page, int line, int k, const int32_t** tokens) {

@@ -25,6 +25,10 @@ static_assert(sizeof(rt_keyword_hit) == sizeof(kw::Hit) && offsetof(rt_keyword_h
 static_assert(RT_MAX_BEAM == bm::MAX_BEAM && RT_MAX_NBEST == bm::MAX_NBEST, "the RT_MAX_BEAM / RT_MAX_NBEST limits and bm:: must agree");
 static_assert(sizeof(rt_beam) == sizeof(bm::Beam) && offsetof(rt_beam, logprob) == offsetof(bm::Beam, logprob) &&
                   offsetof(rt_beam, n_tokens) == offsetof(bm::Beam, n_tokens), "rt_beam and bm::Beam must share one layout");
+static_assert(RT_MAX_LM_ORDER == lm::MAX_ORDER && RT_MAX_LM_NGRAMS == lm::MAX_NGRAMS && RT_MAX_LMS == lm::MAX_LMS, "the RT_MAX_LM* limits and lm:: must agree");
+static_assert(sizeof(rt_beam_lm) == sizeof(lm::BeamLm) && offsetof(rt_beam_lm, lm) == offsetof(lm::BeamLm, lm) &&
+                  offsetof(rt_beam_lm, score) == offsetof(lm::BeamLm, score), "rt_beam_lm and lm::BeamLm must share one layout");
+static_assert(RT_OK == lm::OK && RT_ERR_INVALID == lm::ERR_INVALID, "the status codes of ctc_lm.h are the RT_ERR_* ones");
 static_assert(RT_MAX_PATTERNS == pt::MAX_PATTERNS && RT_PATTERN_MAX_STATES == pt::MAX_STATES && RT_PATTERN_MAX_PAIRS == pt::MAX_PAIRS &&
                   RT_PATTERN_MAX_BYTES == pt::MAX_BYTES, "the RT_PATTERN_* limits and pt:: must agree");
 static_assert(RT_OK == pt::OK && RT_ERR_UTF8 == pt::ERR_UTF8 && RT_ERR_INVALID == pt::ERR_INVALID && RT_ERR_CAPACITY == pt::ERR_CAPACITY,
@@ -438,6 +442,104 @@ RT_API int rt_debug_ctc_beam(rt_session* s, const float* z5, const float* W, con
     h.run();
     DevBufs::download(counts_out, t.count, (size_t)n_lines);
     DevBufs::download(reinterpret_cast<bm::Beam*>(beams_out), t.recs, (size_t)n_lines * nbest);
+    DevBufs::download(tokens_out, t.tok, (size_t)a.rows * nbest);
+  });
+}
+
+// ---- beams with language-model fusion (ctc_lm.h): the model in its id form, compiled by the check; its tables go to the device
+// as rt_lm_create puts them
+int rt_debug_lm_compile(const void* dict, size_t dict_len, const char* arpa, size_t len, float oov_log10, int32_t* ngram_ids_out,
+                        int ids_cap, int32_t* ngram_lens_out, float* logp_out, float* backoff_out, int n_cap, int* n_ids_out, int* n_out,
+                        int* order_out, int* dropped_out, int* states_out, float* oov_out, int* n_classes, char* err, size_t err_cap) {
+  const bool bad = (!dict && dict_len) || (!arpa && len) || !n_ids_out || !n_out || !order_out || !dropped_out || !states_out || !oov_out ||
+                   !n_classes || ids_cap < 0 || n_cap < 0 || (!ngram_ids_out && ids_cap) || ((!ngram_lens_out || !logp_out || !backoff_out) && n_cap);
+  if (!bad) { *n_ids_out = 0; *n_out = 0; *order_out = 0; *dropped_out = 0; *states_out = 0; *oov_out = 0.0f; }
+  return compile_hook("rt_debug_lm_compile", bad, dict, dict_len, n_classes, err, err_cap, [&](const std::vector<std::string>& d) {
+    lm::Ids f; lm::Model m; std::string msg;
+    const int rc = lm::compile_arpa(d, arpa, len, oov_log10, f, m, msg);
+    if (rc != lm::OK) throw RtError(rc, msg);
+    *n_ids_out = (int)f.ids.size(); *n_out = f.n(); *order_out = m.order; *dropped_out = m.dropped; *states_out = (int)m.states.size(); *oov_out = m.oov;
+    if ((size_t)ids_cap < f.ids.size() || n_cap < f.n())
+      throw RtError(RT_ERR_INVALID, "rt_debug_lm_compile: the model needs " + std::to_string(f.ids.size()) + " ids and " + std::to_string(f.n()) + " n-grams");
+    memcpy(ngram_ids_out, f.ids.data(), f.ids.size() * sizeof(int32_t));
+    memcpy(ngram_lens_out, f.lens.data(), f.lens.size() * sizeof(int32_t));
+    memcpy(logp_out, f.logp.data(), f.logp.size() * sizeof(float));
+    memcpy(backoff_out, f.backoff.data(), f.backoff.size() * sizeof(float));
+  });
+}
+int rt_debug_lm_score(int classes, const int32_t* ngram_ids, const int32_t* ngram_lens, const float* logp, const float* backoff, int n,
+                      float oov, const int32_t* strings, const int32_t* string_lens, int n_strings, float* lm_out, int32_t* state_out,
+                      char* err, size_t err_cap) {
+  if (err && err_cap) err[0] = 0;
+  auto refuse = [&](const std::string& why) {
+    if (err && err_cap) snprintf(err, err_cap, "rt_debug_lm_score: %s", why.c_str());
+    return RT_ERR_INVALID;
+  };
+  if (n_strings < 0 || (n_strings > 0 && (!strings || !string_lens || !lm_out || !state_out))) return refuse("bad argument");
+  try {
+    lm::Model m;
+    const std::string bad = hr::IdModel{ngram_ids, ngram_lens, logp, backoff, n, oov}.compile(classes, m);
+    if (!bad.empty()) return refuse(bad);
+    long long o = 0;
+    for (int i = 0; i < n_strings; i++) {
+      if (string_lens[i] < 0) return refuse("string " + std::to_string(i) + " has a negative length");
+      for (int k = 0; k < string_lens[i]; k++)
+        if (strings[o + k] < 1 || strings[o + k] >= classes)
+          return refuse("class id " + std::to_string(strings[o + k]) + " in string " + std::to_string(i) + " is outside [1, " + std::to_string(classes) + ")");
+      o += string_lens[i];
+    }
+    const lm::View v = m.view();
+    o = 0;
+    for (int i = 0; i < n_strings; i++) {
+      const lm::Step x = lm::walk(v, strings + o, string_lens[i]);
+      lm_out[i] = x.score; state_out[i] = x.next;
+      o += string_lens[i];
+    }
+    return RT_OK;
+  } catch (const std::exception& e) {
+    if (err && err_cap) snprintf(err, err_cap, "%s", e.what());
+    return RT_ERR_BACKEND;
+  }
+}
+int rt_debug_ctc_beam_lm_host(const float* z5, const float* W, const float* bias, int N, const int32_t* tokens_per_line, int n_lines,
+                              int beam, int nbest, const int32_t* ngram_ids, const int32_t* ngram_lens, const float* logp,
+                              const float* backoff, int n, float oov, float alpha, float beta, int32_t* counts_out, rt_beam* beams_out,
+                              int32_t* tokens_out, rt_beam_lm* lm_out) {
+  hr::BeamLmArgs a;
+  static_cast<hr::Head&>(a) = hr::Head{z5, W, bias, N, tokens_per_line, n_lines};
+  a.beam = beam; a.nbest = nbest; a.counts_out = counts_out; a.beams_out = beams_out; a.tokens_out = tokens_out;
+  a.ids = {ngram_ids, ngram_lens, logp, backoff, n, oov}; a.alpha = alpha; a.beta = beta; a.lm_out = lm_out;
+  return host_entry("rt_debug_ctc_beam_lm_host", a, hr::beam_lm_ref);
+}
+RT_API int rt_debug_ctc_beam_lm(rt_session* s, const float* z5, const float* W, const float* bias, int N, const int32_t* tokens_per_line,
+                                int n_lines, int beam, int nbest, int chunk_rows, const int32_t* ngram_ids, const int32_t* ngram_lens,
+                                const float* logp, const float* backoff, int n, float oov, float alpha, float beta, int32_t* counts_out,
+                                rt_beam* beams_out, int32_t* tokens_out, rt_beam_lm* lm_out) {
+  hr::BeamLmArgs a;
+  static_cast<hr::Head&>(a) = hr::Head{z5, W, bias, N, tokens_per_line, n_lines};
+  a.beam = beam; a.nbest = nbest; a.counts_out = counts_out; a.beams_out = beams_out; a.tokens_out = tokens_out;
+  a.ids = {ngram_ids, ngram_lens, logp, backoff, n, oov}; a.alpha = alpha; a.beta = beta; a.lm_out = lm_out;
+  if (const int rc = device_check(s, "rt_debug_ctc_beam_lm", a, chunk_rows)) return rc;
+  return guarded(s, [&] {
+    if (beam == 0 || n_lines == 0) return;   // (off, or no line: no launch, no write)
+    TailHook h(s, a, {nullptr, nullptr, 0, chunk_rows, beam, nbest}, std::vector<RecLineOpts>((size_t)n_lines), RecStores{});
+    rt_session::RecTail::Beam& t = h.t.beam;
+    // (what the kernels write starts as the caller's values: a slot they leave alone comes back untouched)
+    const size_t nt = (size_t)std::max<long long>(a.rows, 1) * nbest;
+    t.count = h.bufs.upload(counts_out, (size_t)n_lines);
+    t.recs = h.bufs.upload(reinterpret_cast<const bm::Beam*>(beams_out), (size_t)n_lines * nbest);
+    t.lms = h.bufs.upload(reinterpret_cast<const lm::BeamLm*>(lm_out), (size_t)n_lines * nbest);
+    t.tok = h.bufs.alloc<int>(nt);
+    DevBufs::put(t.tok, tokens_out, (size_t)a.rows * nbest);
+    const lm::Model& m = a.model;
+    t.fused = true;
+    t.fu = lm::Fusion{lm::View{h.bufs.upload(m.uni.data(), m.uni.size()), h.bufs.upload(m.states.data(), m.states.size()),
+                               h.bufs.upload(m.arcs.data(), m.arcs.size()), m.classes, (int32_t)m.states.size(), (int32_t)m.arcs.size(), m.start},
+                      alpha, beta};
+    h.run();
+    DevBufs::download(counts_out, t.count, (size_t)n_lines);
+    DevBufs::download(reinterpret_cast<bm::Beam*>(beams_out), t.recs, (size_t)n_lines * nbest);
+    DevBufs::download(reinterpret_cast<lm::BeamLm*>(lm_out), t.lms, (size_t)n_lines * nbest);
     DevBufs::download(tokens_out, t.tok, (size_t)a.rows * nbest);
   });
 }

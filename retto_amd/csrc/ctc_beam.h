@@ -31,8 +31,10 @@
 //              the beam is smaller.  The empty string is a legitimate hypothesis with 0 tokens.  T = 0: no hypothesis.
 // Identity is by string and exact: one string is never twice in a beam.  A hypothesis' logprob sums a subset of its string's
 // alignments -- those that stayed inside the beam -- so it never exceeds the string's full CTC forward log-likelihood; with a beam
-// that never overflows it IS that likelihood.  Out of scope: a charset- or pattern-restricted beam, language-model fusion,
-// per-region widths, time steps or word boxes of the alternatives.
+// that never overflows it IS that likelihood.  Language-model fusion (rt_set_rec_beam_lm) is ctc_lm.h's: with a lm::Fusion
+// every member also carries the model's sum over its string and its model state, and "selection" orders by lm::key_of() -- the
+// fused score -- in place of the total; everything else above, logprob included, stays.  Out of scope: a charset- or
+// pattern-restricted beam, per-region widths or models, time steps or word boxes of the alternatives.
 //
 // Device form.  Strings live in a per-line trie of (parent, token) nodes with find-or-create, so that one string always has one
 // node: "member j' is string_j + c" is then parent(j') == node_j && last_j' == c.  Only the at most B survivors of a step need
@@ -45,6 +47,7 @@
 #include <vector>
 
 #include "ctc_lexicon.h"
+#include "ctc_lm.h"
 
 namespace rt {
 namespace bm {
@@ -93,12 +96,14 @@ inline void row_topc(const float* logits, int N, TopC* out) {
   for (int j = 0; j < TOP_C; j++) { out->id[j] = I[j]; out->logit[j] = I[j] == cc::EMPTY_ID ? -INFINITY : L[j]; }
 }
 // Host reference: the hypotheses of one line from its logits [T][ld] (N classes) and lse [T] -> out[0 .. count) and hypothesis k's
-// tokens at tokens[k * T ...]; returns the count.  Strings are plain vectors here: identity is comparison
-inline int line_beams(const float* logits, int ld, const float* lse, int T, int N, int B, int nbest, Beam* out, int32_t* tokens) {
+// tokens at tokens[k * T ...]; returns the count.  Strings are plain vectors here: identity is comparison.  f (with lm_out
+// [nbest]): language-model fusion (ctc_lm.h); null: a candidate's key is its total
+inline int line_beams(const float* logits, int ld, const float* lse, int T, int N, int B, int nbest, Beam* out, int32_t* tokens,
+                      const lm::Fusion* f = nullptr, lm::BeamLm* lm_out = nullptr) {
   if (T <= 0) return 0;
-  struct Hyp { std::vector<int32_t> s; float pb, pnb; };
-  struct Cand { float total, pb, pnb; int index, j, c; };
-  std::vector<Hyp> beam(1, Hyp{{}, 0.0f, -INFINITY}), next;
+  struct Hyp { std::vector<int32_t> s; float pb, pnb, lm; int state; };
+  struct Cand { float total, pb, pnb; int index, j, c; float key, lm; int state; };
+  std::vector<Hyp> beam(1, Hyp{{}, 0.0f, -INFINITY, 0.0f, f ? f->m.start : 0}), next;
   std::vector<Cand> cands;
   for (int t = 0; t < T; t++) {
     const float* l = logits + (size_t)t * ld;
@@ -126,16 +131,30 @@ inline int line_beams(const float* logits, int ld, const float* lse, int T, int 
           if (s.size() == h.s.size() + 1 && s.back() == c && std::equal(h.s.begin(), h.s.end(), s.begin())) target = q;
         }
         if (target >= 0) spnb[target] = merged(spnb[target], v);
-        else cands.push_back(Cand{total_of(-INFINITY, v), -INFINITY, v, ext_index(j, r), j, c});
+        else {
+          Cand a{total_of(-INFINITY, v), -INFINITY, v, ext_index(j, r), j, c, 0.0f, 0.0f, 0};
+          a.key = a.total;
+          if (f) {
+            const lm::Step x = lm::step(f->m, h.state, c);
+            a.lm = h.lm + x.score; a.state = x.next;
+            a.key = lm::key_of(a.total, a.lm, (int)h.s.size() + 1, f->alpha, f->beta);
+          }
+          cands.push_back(a);
+        }
       }
     }
-    for (int j = 0; j < n; j++) cands.push_back(Cand{total_of(spb[j], spnb[j]), spb[j], spnb[j], j, j, 0});
+    for (int j = 0; j < n; j++) {
+      const Hyp& h = beam[(size_t)j];
+      Cand a{total_of(spb[j], spnb[j]), spb[j], spnb[j], j, j, 0, 0.0f, h.lm, h.state};
+      a.key = f ? lm::key_of(a.total, a.lm, (int)h.s.size(), f->alpha, f->beta) : a.total;
+      cands.push_back(a);
+    }
     cands.erase(std::remove_if(cands.begin(), cands.end(), [](const Cand& a) { return !alive(a.total); }), cands.end());
-    std::sort(cands.begin(), cands.end(), [](const Cand& a, const Cand& b) { return cc::better(a.total, a.index, b.total, b.index); });
+    std::sort(cands.begin(), cands.end(), [](const Cand& a, const Cand& b) { return cc::better(a.key, a.index, b.key, b.index); });
     next.clear();
     for (size_t i = 0; i < cands.size() && (int)i < B; i++) {
       const Cand& a = cands[i];
-      Hyp h{beam[(size_t)a.j].s, a.pb, a.pnb};
+      Hyp h{beam[(size_t)a.j].s, a.pb, a.pnb, a.lm, a.state};
       if (a.index >= MAX_BEAM) h.s.push_back(a.c);
       next.push_back(std::move(h));
     }
@@ -145,6 +164,7 @@ inline int line_beams(const float* logits, int ld, const float* lse, int T, int 
   for (int k = 0; k < count; k++) {
     const Hyp& h = beam[(size_t)k];
     out[k] = Beam{total_of(h.pb, h.pnb), (int32_t)h.s.size()};
+    if (f && lm_out) lm_out[k] = lm::BeamLm{h.lm, lm::fused_of(out[k].logprob, h.lm, out[k].n_tokens, f->alpha, f->beta)};
     for (size_t i = 0; i < h.s.size(); i++) tokens[(size_t)k * T + i] = h.s[i];
   }
   return count;

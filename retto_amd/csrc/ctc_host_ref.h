@@ -358,5 +358,38 @@ inline void beam_ref(const BeamArgs& a) {
   });
 }
 
+// ---- beams with language-model fusion (ctc_lm.h): the beam's arguments, the model in its id form over the head's N classes
+// (<s> = N), oov as a natural log, the weights; the check compiles the model.  lm_out [n_lines][nbest] beside beams_out
+struct IdModel {
+  const int32_t* ngram_ids = nullptr; const int32_t* ngram_lens = nullptr; const float* logp = nullptr; const float* backoff = nullptr;
+  int n = 0; float oov = 0.0f;
+  // the first requirement that fails, or the empty string with the model compiled into m
+  std::string compile(int classes, lm::Model& m) const {
+    if (n < 0 || (n > 0 && (!ngram_ids || !ngram_lens || !logp || !backoff))) return "the model's arrays are null or n is negative";
+    std::string msg;
+    return lm::compile(classes, ngram_ids, ngram_lens, logp, backoff, n, nullptr, oov, m, msg) == lm::OK ? std::string() : msg;
+  }
+};
+struct BeamLmArgs : BeamArgs {
+  IdModel ids; float alpha = 0.0f, beta = 0.0f;
+  rt_beam_lm* lm_out = nullptr;
+  lm::Model model;
+  std::string error() {
+    if (!lm_out) return "a required pointer is null";
+    const std::string bad = BeamArgs::error();
+    if (!bad.empty()) return bad;
+    if (const char* why = lm::check_weights(alpha, beta)) return why;
+    return ids.compile(N, model);
+  }
+};
+inline void beam_lm_ref(const BeamLmArgs& a) {
+  if (a.beam == 0) return;
+  const lm::Fusion f{a.model.view(), a.alpha, a.beta};
+  walk_lines(a, lx::row_lse, [](int) { return true; }, [&](int i, long long o, int T, const float* logits, const float* lse) {
+    a.counts_out[i] = bm::line_beams(logits, a.N, lse, T, a.N, a.beam, a.nbest, reinterpret_cast<bm::Beam*>(a.beams_out) + (size_t)i * a.nbest,
+                                     a.tokens_out + o * a.nbest, &f, reinterpret_cast<lm::BeamLm*>(a.lm_out) + (size_t)i * a.nbest);
+  });
+}
+
 }  // namespace hr
 }  // namespace rt

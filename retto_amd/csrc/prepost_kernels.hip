@@ -842,15 +842,26 @@ void ctc_beam_topc(hipStream_t st, const float* logits, int ld, int classes, int
 // workgroup.  At the end thread k < N walks hypothesis k's nodes to the root and writes its tokens back to front.
 // Bounds: a row index is < the chunk's rows (a line's rows are resident together), a node id <= T B < bm::nodes_of(T, B), a
 // token slot < N T.
+// LM: language-model fusion (ctc_lm.h), a compile-time variant; LM = false is the kernel as it was, to the bit.  A member's model
+// state and lm live in LDS twice, like pb and pnb; the candidates' keys (lm::key_of) beside their totals.  In B thread (j, r),
+// where its extension is a candidate, looks its class up from state_j (lm::step): at the unigram level one indexed load of the
+// dense table, above it one binary search per back-off level; the tables are read-only global memory.  D ranks by the key, E
+// writes the survivors' state and lm; the trie is untouched.  Bounds: lm::step reads state s only for 0 < s < n_states (anything
+// else is the empty context), cuts a state's arc slice to [0, n_arcs) and searches inside it in at most lm::ARC_STEPS halvings,
+// walks at most lm::MAX_ORDER levels, and reads uni[c] only for 1 <= c < classes; a record slot < n_lines nbest as beams'.
+template <bool LM>
 __global__ __launch_bounds__(256) void k_ctc_beam_search(const float* __restrict__ logits, int ld, const float* __restrict__ lse,
                                                          const bm::TopC* __restrict__ topc, const bm::Line* __restrict__ lines,
                                                          int chunk_row0, int B, int nbest, bm::Node* nodes,
                                                          bm::Beam* __restrict__ beams, int* __restrict__ tokens,
-                                                         int* __restrict__ counts) {
+                                                         int* __restrict__ counts, lm::Fusion fu, lm::BeamLm* __restrict__ lms) {
   constexpr int MB = bm::MAX_BEAM, TC = bm::TOP_C;
   static_assert(MB * TC == 256 && bm::CANDS == MB + 256, "one thread per extension");
   __shared__ int s_node[2][MB], s_par[2][MB], s_last[2][MB], s_len[2][MB], s_n[2];
   __shared__ float s_pb[2][MB], s_pnb[2][MB], s_tot[MB], s_spb[MB], s_spnb[MB], s_cand[bm::CANDS];
+  __shared__ int s_state[2][LM ? MB : 1];
+  __shared__ float s_lm[2][LM ? MB : 1], s_key[LM ? bm::CANDS : 1];
+  const float* rank = LM ? s_key : s_cand;   // what D orders by
   const int tid = threadIdx.x, j = tid / TC, r = tid % TC;
   const bm::Line ln = lines[blockIdx.x];
   const int T = ln.T;
@@ -861,6 +872,7 @@ __global__ __launch_bounds__(256) void k_ctc_beam_search(const float* __restrict
   if (tid == 0) {
     nd[0] = bm::Node{-1, 0, -1, -1};
     s_node[0][0] = 0; s_par[0][0] = -1; s_last[0][0] = 0; s_len[0][0] = 0; s_pb[0][0] = 0.0f; s_pnb[0][0] = -INFINITY; s_n[0] = 1;
+    if (LM) { s_state[0][0] = fu.m.start; s_lm[0][0] = 0.0f; }
   }
   __syncthreads();
   int cur = 0;
@@ -891,22 +903,35 @@ __global__ __launch_bounds__(256) void k_ctc_beam_search(const float* __restrict
       if (target >= 0) s_spnb[target] = bm::merged(s_spnb[target], v);
     }
     s_cand[MB + tid] = ext && target < 0 ? bm::total_of(-INFINITY, v) : -INFINITY;
+    float elm = 0.0f; int estate = 0;
+    if (LM) {
+      float key = -INFINITY;
+      if (ext && target < 0) {
+        const lm::Step x = lm::step(fu.m, s_state[cur][j], c);
+        elm = s_lm[cur][j] + x.score; estate = x.next;
+        key = lm::key_of(s_cand[MB + tid], elm, s_len[cur][j] + 1, fu.alpha, fu.beta);
+      }
+      s_key[MB + tid] = key;
+    }
     __syncthreads();
     // C
-    if (tid < MB) s_cand[tid] = tid < n ? bm::total_of(s_spb[tid], s_spnb[tid]) : -INFINITY;
+    if (tid < MB) {
+      s_cand[tid] = tid < n ? bm::total_of(s_spb[tid], s_spnb[tid]) : -INFINITY;
+      if (LM) s_key[tid] = tid < n ? lm::key_of(s_cand[tid], s_lm[cur][tid], s_len[cur][tid], fu.alpha, fu.beta) : -INFINITY;
+    }
     __syncthreads();
-    // D
-    const float ev = s_cand[MB + tid], sv = tid < MB ? s_cand[tid] : -INFINITY;
+    // D  (a dead candidate's key is -inf and a live one's is above it: lm::key_of)
+    const float ev = rank[MB + tid], sv = tid < MB ? rank[tid] : -INFINITY;
     int eplace = bm::CANDS, splace = bm::CANDS;
     if (bm::alive(ev)) {
       eplace = 0;
-      for (int k = 0; k < n; k++) eplace += cc::better(s_cand[k], k, ev, MB + tid) ? 1 : 0;
-      for (int k = MB; k < MB + n * TC; k++) eplace += cc::better(s_cand[k], k, ev, MB + tid) ? 1 : 0;
+      for (int k = 0; k < n; k++) eplace += cc::better(rank[k], k, ev, MB + tid) ? 1 : 0;
+      for (int k = MB; k < MB + n * TC; k++) eplace += cc::better(rank[k], k, ev, MB + tid) ? 1 : 0;
     }
     if (bm::alive(sv)) {
       splace = 0;
-      for (int k = 0; k < n; k++) splace += cc::better(s_cand[k], k, sv, tid) ? 1 : 0;
-      for (int k = MB; k < MB + n * TC; k++) splace += cc::better(s_cand[k], k, sv, tid) ? 1 : 0;
+      for (int k = 0; k < n; k++) splace += cc::better(rank[k], k, sv, tid) ? 1 : 0;
+      for (int k = MB; k < MB + n * TC; k++) splace += cc::better(rank[k], k, sv, tid) ? 1 : 0;
     }
     int found = -1;
     if (eplace < B)   // (a list's head is only ever changed by an atomic in L2: read it there; tok and next are written once)
@@ -924,11 +949,13 @@ __global__ __launch_bounds__(256) void k_ctc_beam_search(const float* __restrict
       }
       s_node[nxt][eplace] = id; s_par[nxt][eplace] = node; s_last[nxt][eplace] = c; s_len[nxt][eplace] = s_len[cur][j] + 1;
       s_pb[nxt][eplace] = -INFINITY; s_pnb[nxt][eplace] = v;
+      if (LM) { s_state[nxt][eplace] = estate; s_lm[nxt][eplace] = elm; }
       atomicMax(&s_n[nxt], eplace + 1);
     }
     if (splace < B) {
       s_node[nxt][splace] = s_node[cur][tid]; s_par[nxt][splace] = s_par[cur][tid]; s_last[nxt][splace] = s_last[cur][tid];
       s_len[nxt][splace] = s_len[cur][tid]; s_pb[nxt][splace] = s_spb[tid]; s_pnb[nxt][splace] = s_spnb[tid];
+      if (LM) { s_state[nxt][splace] = s_state[cur][tid]; s_lm[nxt][splace] = s_lm[cur][tid]; }
       atomicMax(&s_n[nxt], splace + 1);
     }
     __syncthreads();
@@ -938,17 +965,24 @@ __global__ __launch_bounds__(256) void k_ctc_beam_search(const float* __restrict
   if (tid == 0) counts[ln.slot] = count;
   if (tid < count) {
     const int len = s_len[cur][tid];
-    beams[(long long)ln.slot * nbest + tid] = bm::Beam{bm::total_of(s_pb[cur][tid], s_pnb[cur][tid]), len};
+    const float total = bm::total_of(s_pb[cur][tid], s_pnb[cur][tid]);
+    beams[(long long)ln.slot * nbest + tid] = bm::Beam{total, len};
+    if (LM) lms[(long long)ln.slot * nbest + tid] = lm::BeamLm{s_lm[cur][tid], lm::fused_of(total, s_lm[cur][tid], len, fu.alpha, fu.beta)};
     int* out = tokens + ln.out + (long long)tid * T;
     int q = s_node[cur][tid];
     for (int i = len - 1; i >= 0 && q > 0 && q < n_nodes; i--) { out[i] = nd[q].tok; q = nd[q].parent; }
   }
 }
 void ctc_beam_search(hipStream_t st, const float* logits, int ld, const float* lse, const bm::TopC* topc, const bm::Line* lines,
-                     int n_lines, int chunk_row0, int B, int nbest, bm::Node* nodes, bm::Beam* beams, int* tokens, int* counts) {
+                     int n_lines, int chunk_row0, int B, int nbest, bm::Node* nodes, bm::Beam* beams, int* tokens, int* counts,
+                     const lm::Fusion* fu, lm::BeamLm* lms) {
   if (n_lines <= 0) return;
-  RT_LAUNCH(k_ctc_beam_search, dim3(n_lines), dim3(256), 0, st, logits, ld, lse, topc, lines, chunk_row0, B, nbest, nodes, beams,
-            tokens, counts);
+  if (fu)
+    RT_LAUNCH(k_ctc_beam_search<true>, dim3(n_lines), dim3(256), 0, st, logits, ld, lse, topc, lines, chunk_row0, B, nbest, nodes,
+              beams, tokens, counts, *fu, lms);
+  else
+    RT_LAUNCH(k_ctc_beam_search<false>, dim3(n_lines), dim3(256), 0, st, logits, ld, lse, topc, lines, chunk_row0, B, nbest, nodes,
+              beams, tokens, counts, lm::Fusion{}, nullptr);
 }
 
 // Lexicon snap (ctc_lexicon_align.h).  One wave64 per lexicon line of one chunk, after k_ctc_lexicon_topk has written the line's

@@ -377,8 +377,10 @@ void rt_lane::ctc_beams(const RecTailPlan& p, const SvtrCore& core, const RecTai
       ProfScope ps(&prof, st, "ctc_beam_topc");
       pp::ctc_beam_topc(st, lc.logits, lc.ld, core.classes, m, topc);
     }
-    ProfScope ps(&prof, st, "ctc_beam_search");
-    pp::ctc_beam_search(st, lc.logits, lc.ld, pass.lse, topc, d_lines, n, r0, o.b, o.n, nodes, o.recs, o.tok, o.count);
+    // (with a language model the search is its own profile family: its cost is then read off apart from the plain beam's)
+    ProfScope ps(&prof, st, o.fused ? "ctc_beam_search_lm" : "ctc_beam_search");
+    pp::ctc_beam_search(st, lc.logits, lc.ld, pass.lse, topc, d_lines, n, r0, o.b, o.n, nodes, o.recs, o.tok, o.count,
+                        o.fused ? &o.fu : nullptr, o.lms);
   });
 }
 
@@ -455,6 +457,35 @@ int rt_session::keywords_create(const char* utf8, size_t len, const int32_t* ids
   std::swap(X.d_min, fresh.d_min);
   X.min_score = std::move(mins);
   return id;
+}
+
+// ---- the language models (session.h rt_lms) ----
+namespace {
+void free_view(const lm::View& v) {
+  const void* p[] = {v.uni, v.states, v.arcs};
+  for (const void* q : p) if (q) (void)hipFree(const_cast<void*>(q));
+}
+}  // namespace
+rt_lms::~rt_lms() { for (const lm::View& v : dev) free_view(v); }
+int rt_lms::add(lm::Model m) {
+  host.reserve(host.size() + 1); dev.reserve(dev.size() + 1);   // (so that nothing behind the copies throws)
+  std::unique_ptr<lm::Model> h(new lm::Model(std::move(m)));
+  lm::View v = h->view();
+  v.uni = nullptr; v.states = nullptr; v.arcs = nullptr;
+  try {
+    upload_table(&v.uni, h->uni); upload_table(&v.states, h->states); upload_table(&v.arcs, h->arcs);
+  } catch (...) { free_view(v); throw; }
+  host.push_back(std::move(h)); dev.push_back(v);
+  return (int)host.size() - 1;
+}
+int rt_session::lm_create(const char* arpa, size_t len, float oov_log10) {
+  if ((int)lms->host.size() >= lm::MAX_LMS)
+    throw RtError(RT_ERR_CAPACITY, "rt_lm_create: the session holds RT_MAX_LMS (" + std::to_string(lm::MAX_LMS) + ") language models already");
+  lm::Ids ids; lm::Model m; std::string msg;
+  const int rc = lm::compile_arpa(dict, arpa, len, oov_log10, ids, m, msg);
+  if (rc != lm::OK) throw RtError(rc, "rt_lm_create: " + msg);
+  RT_HIP_CHECK(hipSetDevice(device));
+  return lms->add(std::move(m));
 }
 
 int rt_session::pattern_create(const char* utf8, size_t len) {

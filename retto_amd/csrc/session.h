@@ -65,6 +65,8 @@ struct rt_results {
     std::vector<rt::bm::Beam> bm_recs;
     std::vector<std::vector<int32_t>> bm_tokens;
     std::vector<std::string> bm_text;
+    // rec language model (ctc_lm.h; rt_set_rec_beam_lm): per record slot the hypothesis' lm and fused score; empty when fusion was off
+    std::vector<rt::lm::BeamLm> bm_lm;
     // rec windows (rec_windows.h; rt_set_rec_windows): per line the number of units it was read in, 1 for a whole line
     std::vector<int32_t> rec_units;
     std::string json[3];
@@ -90,8 +92,13 @@ struct LaneWorker {
 
 // What a pipeline call reads of the session's settings, as they were when the call was submitted: the default options of every
 // line (rt_set_rec_charset / _lexicon / _pattern / _keywords, rec_line_opts.h), the det tiles (rt_set_det_tiles, det_tiles.h; 0 = off)
-// the rec beam (rt_set_rec_beam, ctc_beam.h; beam_b = 0: off) and the rec windows (rt_set_rec_windows, rec_windows.h; 0 = off)
-struct CallSettings { rt::RecLineOpts rec; int det_tile = 0, det_overlap = 0, beam_b = 0, beam_n = 0, rec_window = 0, rec_overlap = 0; };
+// the rec beam (rt_set_rec_beam, ctc_beam.h; beam_b = 0: off), the rec windows (rt_set_rec_windows, rec_windows.h; 0 = off) and
+// the beam's language model (rt_set_rec_beam_lm, ctc_lm.h; lm = -1: off, and without effect while beam_b = 0)
+struct CallSettings {
+  rt::RecLineOpts rec; int det_tile = 0, det_overlap = 0, beam_b = 0, beam_n = 0, rec_window = 0, rec_overlap = 0;
+  int lm = -1; float lm_alpha = 0.0f, lm_beta = 0.0f;
+  bool fused() const { return beam_b > 0 && lm >= 0; }
+};
 
 // One pipeline call over some pages: what rt_lane::run_pages runs, whoever asked for it (rt_run_batch, rt_submit_batch,
 // rt_run_regions*, a lane's part of a ticket).  Non-owning: every array has n_pages entries and belongs to the caller or the ticket.
@@ -236,6 +243,17 @@ struct rt_keywords : rt_entry_store {
   ~rt_keywords() { if (d_min) (void)hipFree(const_cast<float*>(d_min)); }
 };
 
+// The session's rec language models (ctc_lm.h), shared with the helper lanes.  Model k (0-based, rt_lm_create's handle) is
+// host[k], whose three tables sit on the device as dev[k], uploaded once at creation and kept until the session goes.  Only
+// changed while no ticket is in flight (rt_lm_create is a guarded call), with blocking copies.
+struct rt_lms {
+  std::vector<std::unique_ptr<rt::lm::Model>> host;
+  std::vector<rt::lm::View> dev;
+  // the model's tables onto the current device; returns its handle.  Whatever throws leaves the store as it was.
+  int add(rt::lm::Model m);
+  ~rt_lms();
+};
+
 // internal to the library (never accepted from a caller): pages already in HBM, det map overrides still host pointers
 #define RT_MEM_STAGED_MAPS_HOST 3
 
@@ -316,7 +334,11 @@ struct rt_lane {
     } keywords;
     // rec beams (ctc_beam.h; b > 0 where the plan has beam lines): the width and the hypotheses per line; the per-line counts
     // [slot], records [slot][n] and the token pool (bm::Line::out)
-    struct Beam { int b = 0, n = 0; int* count = nullptr; rt::bm::Beam* recs = nullptr; int* tok = nullptr; } beam;
+    // fused: language-model fusion (ctc_lm.h) with fu, whose tables are on the device, and the records' lm / fused score [slot][n]
+    struct Beam {
+      int b = 0, n = 0; int* count = nullptr; rt::bm::Beam* recs = nullptr; int* tok = nullptr;
+      bool fused = false; rt::lm::Fusion fu{}; rt::lm::BeamLm* lms = nullptr;
+    } beam;
     // rec_return_candidates = k > 0 (ctc_candidates.h): the kept tokens' time steps and [k] candidates
     struct Candidates { int k = 0; int* col = nullptr; rt::cc::Cand* cands = nullptr; } cand;
   };
@@ -371,6 +393,7 @@ struct rt_session : rt_lane {
   std::unique_ptr<rt_lexicons> lexicons;
   std::unique_ptr<rt_patterns> patterns;
   std::unique_ptr<rt_keywords> keywords;
+  std::unique_ptr<rt_lms> lms;
   rt::RecLineOpts rec_counts() const {
     return {(int)charsets->ids.size(), (int)lexicons->host.size(), (int)patterns->host.size(), (int)keywords->host.size()};
   }
@@ -383,10 +406,13 @@ struct rt_session : rt_lane {
   // rt_set_rec_beam (ctc_beam.h): every line of the pipeline calls that follow also reports its beam_n most probable strings from
   // a prefix beam search of width beam_b; 0 = off
   int beam_b = 0, beam_n = 0;
+  // rt_set_rec_beam_lm (ctc_lm.h): the beam search of the calls that follow ranks by total + (alpha * lm + beta * len) under
+  // model beam_lm; -1 = off.  Without effect while beam_b = 0
+  int beam_lm = -1; float lm_alpha = 0.0f, lm_beta = 0.0f;
   // rt_set_rec_windows (rec_windows.h): lines at least 8 columns wider than rec_window are read as overlapping windows whose
   // trusted time steps are stitched into the line's rows; 0 = off
   int rec_window = 0, rec_overlap = 0;
-  CallSettings settings() const { return {rec_default, det_tile, det_overlap, beam_b, beam_n, rec_window, rec_overlap}; }
+  CallSettings settings() const { return {rec_default, det_tile, det_overlap, beam_b, beam_n, rec_window, rec_overlap, beam_lm, lm_alpha, lm_beta}; }
   std::string last_error;
   // rt_charset_create: compiles the set (rt::compile_charset), stores it and returns its id
   int charset_create(const char* utf8, size_t len, const int32_t* ids, int n_ids);
@@ -394,6 +420,8 @@ struct rt_session : rt_lane {
   int lexicon_create(const char* utf8, size_t len, const int32_t* ids, const int32_t* entry_lens, int n_id_entries);
   // rt_keywords_create: the entries into the keyword store (rt_entry_store::add) with min_score; returns the list's id
   int keywords_create(const char* utf8, size_t len, const int32_t* ids, const int32_t* entry_lens, int n_id_entries, float min_score);
+  // rt_lm_create: compiles the ARPA text (rt::lm::compile_arpa over the dictionary), stores the model and returns its handle
+  int lm_create(const char* arpa, size_t len, float oov_log10);
   // rt_pattern_create: compiles the pattern (rt::pt::compile), stores it and returns its id
   int pattern_create(const char* utf8, size_t len);
   // rt_lexicon_set_snap: the lexicon's min_posterior (ctc_lexicon_align.h), on the host and in the device table
