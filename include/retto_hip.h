@@ -784,6 +784,82 @@ RT_API int rt_debug_ctc_beam_lm_host(const float* z5, const float* W, const floa
                                      int n_lines, int beam, int nbest, const int32_t* ngram_ids, const int32_t* ngram_lens,
                                      const float* logp, const float* backoff, int n, float oov, float alpha, float beta,
                                      int32_t* counts_out, rt_beam* beams_out, int32_t* tokens_out, rt_beam_lm* lm_out);
+
+/* ---- rec vocabulary: a word-list constraint fused into the beam search ------------------------------------------------------------
+ * "This is running text, and its words should be words of this list": a language's word list, a product catalogue, a customer's
+ * field vocabulary.  A character n-gram cannot tell `recieve` from `receive`, a lexicon ranks whole lines, and re-ranking the
+ * N-best list afterwards cannot bring back a string that was pruned on the way, so the list acts inside every step's selection,
+ * beside the language model where one is attached.  retto_amd/csrc/ctc_vocab.h states the rule; in short:
+ *   words      1 .. RT_VOCAB_MAX_LEN class ids each, at most RT_VOCAB_MAX_WORDS; a word given twice is one word;
+ *   classes    the classes that occur in some word are WORD classes; every other class (digits, punctuation, the space, as far
+ *              as the list does not spell with them) is a SEPARATOR: it passes freely and ends a word;
+ *   oov_words  of a string: its maximal runs of word classes that are not words of the list.  While the search runs, a last run
+ *              still open counts only once it is no prefix of a word any more; the line end closes it;
+ *   score      logprob (with a model: rt_beam_lm.score) - gamma * oov_words; gamma >= 0, finite;
+ *   step       the beam's rule with one change: the best B candidates are the best by that score over the count so far (ties as
+ *              before); after the last step the final beam is ranked once more by the score over the closed count.
+ * The constraint is soft: a line is never left without hypotheses.  rt_beam.logprob stays the CTC total and rt_beam_lm what it
+ * is (its score holds no gamma).  gamma = 0 gives the bytes of the search without a vocabulary.  Everything else of a call --
+ * and, with no vocabulary attached, the hypotheses too -- is what it is without it, bit for bit; the per-stage JSON stays as it
+ * is.  What the option does to accuracy with the real PP-OCRv4 weights has not been measured.
+ *
+ * rt_vocab_create: the words are the lines of utf8 [len] (may be NULL with len 0), split, trimmed and mapped code point by code
+ * point to the lowest class exactly as rt_lexicon_create maps its entries, then n_id_words words of word_lens[i] ids each,
+ * consecutive in ids.  flags & RT_VOCAB_CASE_VARIANTS: every UTF-8 word is also inserted with its first ASCII letter upper-cased
+ * and with all its ASCII letters upper-cased; a variant with a code point the dictionary lacks is not inserted, and is counted.
+ * *vocab_out = its handle, 0-based, valid until rt_destroy; a session holds at most RT_MAX_VOCABS.  RT_ERR_UTF8 for malformed
+ * text; RT_ERR_INVALID with a message that names the word for a code point that matches no dictionary entry ("U+XXXX"), the
+ * blank or an id outside [1, classes), an empty or over-long word, no word at all, unknown flag bits; RT_ERR_CAPACITY past
+ * RT_VOCAB_MAX_WORDS or RT_MAX_VOCABS.  Fails like every other call while tickets are in flight.
+ * rt_vocab_info: the vocabulary's words, trie nodes (the root included), word classes and dropped case variants (each
+ * optional); RT_ERR_INVALID for an unknown handle.
+ * rt_set_rec_beam_vocab: vocab = -1 switches the constraint off; otherwise a handle and gamma >= 0, finite, else RT_ERR_INVALID.
+ * Legal while beam = 0, and without effect until rt_set_rec_beam sets one; it applies to every pipeline call that follows and
+ * fails like the other setters while tickets are in flight.  rt_rec_beam_vocab reads the two values back (each optional). */
+#define RT_VOCAB_MAX_LEN 63
+#define RT_VOCAB_MAX_WORDS (1 << 20)
+#define RT_MAX_VOCABS 4
+#define RT_VOCAB_CASE_VARIANTS 1
+typedef struct rt_beam_vocab { int32_t oov_words; float score; } rt_beam_vocab;
+RT_API int rt_vocab_create(rt_session* s, const char* utf8, size_t len, const int32_t* ids, const int32_t* word_lens, int n_id_words,
+                           int flags, int* vocab_out);
+RT_API int rt_vocab_info(const rt_session* s, int vocab, int* words, int* nodes, int* word_classes, int* variants_dropped);
+RT_API int rt_set_rec_beam_vocab(rt_session* s, int vocab, float gamma);
+RT_API int rt_rec_beam_vocab(const rt_session* s, int* vocab, float* gamma);
+/* the closed count and the score of a line's hypotheses, beside rt_results_rec_beams' records: their number, and 0 with nothing
+ * written when no vocabulary was attached; *out (optional): the records, best first */
+RT_API int rt_results_rec_beam_vocab(const rt_results* r, int page, int line, const rt_beam_vocab** out);
+/* The vocabulary compiler without a session: dict [dict_len] as rt_config.dict, utf8 [len], flags -> the id form: word i has
+ * word_lens_out[i] ids, one word after the other in word_ids_out, each word once, in order of first occurrence.  *n_out,
+ * *n_ids_out: how many words and ids there are (also when a cap was too small: RT_ERR_INVALID then, nothing copied); *words_out,
+ * *nodes_out, *word_classes_out, *variants_dropped_out: as rt_vocab_info. */
+RT_API int rt_debug_vocab_compile(const void* dict, size_t dict_len, const char* utf8, size_t len, int flags, int32_t* word_ids_out,
+                                  int ids_cap, int32_t* word_lens_out, int n_cap, int* n_ids_out, int* n_out, int* words_out,
+                                  int* nodes_out, int* word_classes_out, int* variants_dropped_out, int* n_classes, char* err,
+                                  size_t err_cap);
+/* A vocabulary in its id form over `classes` classes compiled and walked on the host: string i has string_lens[i] ids of
+ * [1, classes), one string after the other in strings; open_out[i]: the count while the string's last word is open, closed_out[i]:
+ * the count with the line end, state_out[i]: the trie node it ends in (0: the root; -1: inside a word that left the trie).
+ * Refusals as rt_vocab_create's, naming the word's index. */
+RT_API int rt_debug_vocab_walk(int classes, const int32_t* word_ids, const int32_t* word_lens, int n_words, const int32_t* strings,
+                               const int32_t* string_lens, int n_strings, int32_t* open_out, int32_t* closed_out, int32_t* state_out,
+                               char* err, size_t err_cap);
+/* rt_debug_ctc_beam_lm with a vocabulary in its id form over the head's N classes and gamma: the device path with
+ * k_ctc_beam_search's vocabulary variants.  n = 0 n-grams with alpha = beta = 0 means no model, and lm_out may be NULL then.
+ * vocab_out [n_lines][nbest] beside beams_out; slots past a line's count come back as the caller put them.  Anything bad is
+ * refused before any launch. */
+RT_API int rt_debug_ctc_beam_vocab(rt_session* s, const float* z5, const float* W, const float* bias, int N, const int32_t* tokens_per_line,
+                                   int n_lines, int beam, int nbest, int chunk_rows, const int32_t* ngram_ids, const int32_t* ngram_lens,
+                                   const float* logp, const float* backoff, int n, float oov, float alpha, float beta,
+                                   const int32_t* word_ids, const int32_t* word_lens, int n_words, float gamma, int32_t* counts_out,
+                                   rt_beam* beams_out, int32_t* tokens_out, rt_beam_lm* lm_out, rt_beam_vocab* vocab_out);
+/* The same rule on the CPU in plain fp32 loops (ctc_beam.h, ctc_lm.h, ctc_vocab.h), GPU-free and sessionless; same layout. */
+RT_API int rt_debug_ctc_beam_vocab_host(const float* z5, const float* W, const float* bias, int N, const int32_t* tokens_per_line,
+                                        int n_lines, int beam, int nbest, const int32_t* ngram_ids, const int32_t* ngram_lens,
+                                        const float* logp, const float* backoff, int n, float oov, float alpha, float beta,
+                                        const int32_t* word_ids, const int32_t* word_lens, int n_words, float gamma,
+                                        int32_t* counts_out, rt_beam* beams_out, int32_t* tokens_out, rt_beam_lm* lm_out,
+                                        rt_beam_vocab* vocab_out);
 /* f32 sum of every det probability map produced in the call (keeps the network's
  * output observable when det_map_override is used) */
 RT_API double rt_results_det_checksum(const rt_results* r);

@@ -198,6 +198,11 @@ class BeamHypothesis:   # rt_beam, with its tokens and text
     # log) and the fused score logprob + (alpha * lm_logprob + beta * len(tokens)) the hypotheses are ordered by
     lm_logprob: Optional[float] = None
     lm_score: Optional[float] = None
+    # rec vocabulary (set_rec_beam_vocab; rt_beam_vocab): None when no vocabulary was attached, else the string's words that are
+    # not in the list (the line end closing the last one) and the score -- logprob, or lm_score with a model, minus gamma per
+    # such word -- the hypotheses are ordered by
+    oov_words: Optional[int] = None
+    vocab_score: Optional[float] = None
 
 
 @dataclass
@@ -757,13 +762,16 @@ class RettoSession:
         n = lib.rt_results_rec_beams(r, page, line, C.byref(bp))
         lp = C.POINTER(_lib.BeamLm)()
         fused = lib.rt_results_rec_beam_lm(r, page, line, C.byref(lp)) == n and bool(lp)
+        vp = C.POINTER(_lib.BeamVocab)()
+        worded = lib.rt_results_rec_beam_vocab(r, page, line, C.byref(vp)) == n and bool(vp)
         out = []
         for k in range(n):
             tp = C.POINTER(C.c_int32)()
             nt = lib.rt_results_rec_beam_tokens(r, page, line, k, C.byref(tp))
             out.append(BeamHypothesis(np.array([tp[i] for i in range(nt)], np.int32),
                                       lib.rt_results_rec_beam_text(r, page, line, k).decode("utf-8"), float(bp[k].logprob),
-                                      float(lp[k].lm) if fused else None, float(lp[k].score) if fused else None))
+                                      float(lp[k].lm) if fused else None, float(lp[k].score) if fused else None,
+                                      int(vp[k].oov_words) if worded else None, float(vp[k].score) if worded else None))
         return out
 
     def _lexicon_matches(self, r, page: int, line: int):
@@ -842,6 +850,45 @@ class RettoSession:
         m, a, b = C.c_int(), C.c_float(), C.c_float()
         _check(self._hd.lib.rt_rec_beam_lm(self._hd.h, C.byref(m), C.byref(a), C.byref(b)), self._hd.h)
         return m.value, a.value, b.value
+
+    # -- rec vocabulary ----------------------------------------------------------------------
+    def create_vocab(self, words=(), ids=(), case_variants: bool = False) -> int:
+        """rt_vocab_create: a word list for the beam search (retto_amd/csrc/ctc_vocab.h).  words: an iterable of str (each mapped
+        code point by code point to the dictionary, as a lexicon's entries are) or one str / bytes of newline-separated words;
+        ids: an iterable of class-id sequences that follow them.  case_variants: every text word also Capitalised and in UPPER
+        CASE.  Returns the vocabulary's handle (0-based, valid for the session's life; at most MAX_VOCABS); see
+        set_rec_beam_vocab."""
+        if isinstance(words, (bytes, bytearray)):
+            raw = bytes(words)
+        else:
+            raw = (words if isinstance(words, str) else "\n".join(words)).encode("utf-8")
+        seqs = [np.asarray(w, np.int32).ravel() for w in ids]
+        flat = np.ascontiguousarray(np.concatenate(seqs) if seqs else np.zeros(0, np.int32), np.int32)
+        lens = np.ascontiguousarray([len(w) for w in seqs], np.int32)
+        out = C.c_int()
+        _check(self._hd.lib.rt_vocab_create(self._hd.h, raw, len(raw), flat.ctypes.data_as(C.c_void_p), lens.ctypes.data_as(C.c_void_p),
+                                            len(seqs), _lib.VOCAB_CASE_VARIANTS if case_variants else 0, C.byref(out)), self._hd.h)
+        return out.value
+
+    def vocab_info(self, vocab: int) -> Optional[dict]:
+        """rt_vocab_info: {words, nodes, word_classes, variants_dropped} of a vocabulary; None for an unknown handle."""
+        w, n, c, d = C.c_int(), C.c_int(), C.c_int(), C.c_int()
+        if self._hd.lib.rt_vocab_info(self._hd.h, int(vocab), C.byref(w), C.byref(n), C.byref(c), C.byref(d)) != 0:
+            return None
+        return {"words": w.value, "nodes": n.value, "word_classes": c.value, "variants_dropped": d.value}
+
+    def set_rec_beam_vocab(self, vocab: int, gamma: float = 4.0) -> None:
+        """rt_set_rec_beam_vocab: the beam search of the pipeline calls that follow charges every word of a hypothesis that is
+        not in vocabulary ``vocab`` with ``gamma`` (BeamHypothesis.oov_words / vocab_score); characters the list does not spell
+        with pass freely and separate words.  vocab = -1: off, the default.  Without effect until set_rec_beam sets a beam.
+        gamma >= 0, finite.  The effect on accuracy with the real weights is not measured."""
+        _check(self._hd.lib.rt_set_rec_beam_vocab(self._hd.h, int(vocab), float(gamma)), self._hd.h)
+
+    def rec_beam_vocab(self) -> Tuple[int, float]:
+        """rt_rec_beam_vocab: (vocab, gamma) as set; vocab -1 = off."""
+        v, g = C.c_int(), C.c_float()
+        _check(self._hd.lib.rt_rec_beam_vocab(self._hd.h, C.byref(v), C.byref(g)), self._hd.h)
+        return v.value, g.value
 
     @property
     def det_tiles(self) -> Tuple[int, int]:

@@ -74,7 +74,15 @@ class BeamLm(C.Structure):   # rt_beam_lm
     _fields_ = [("lm", C.c_float), ("score", C.c_float)]
 
 
+class BeamVocab(C.Structure):   # rt_beam_vocab
+    _fields_ = [("oov_words", C.c_int32), ("score", C.c_float)]
+
+
 MAX_BEAM = 32                # RT_MAX_BEAM
+VOCAB_MAX_LEN = 63           # RT_VOCAB_MAX_LEN
+VOCAB_MAX_WORDS = 1 << 20    # RT_VOCAB_MAX_WORDS
+MAX_VOCABS = 4               # RT_MAX_VOCABS
+VOCAB_CASE_VARIANTS = 1      # RT_VOCAB_CASE_VARIANTS
 MAX_LM_ORDER = 5             # RT_MAX_LM_ORDER
 MAX_LM_NGRAMS = 1 << 22      # RT_MAX_LM_NGRAMS
 MAX_LMS = 4                  # RT_MAX_LMS
@@ -123,6 +131,8 @@ EXPORTS = [
     "rt_debug_ctc_beam", "rt_debug_ctc_beam_host",
     "rt_lm_create", "rt_lm_info", "rt_set_rec_beam_lm", "rt_rec_beam_lm", "rt_results_rec_beam_lm", "rt_debug_lm_compile",
     "rt_debug_lm_score", "rt_debug_ctc_beam_lm", "rt_debug_ctc_beam_lm_host",
+    "rt_vocab_create", "rt_vocab_info", "rt_set_rec_beam_vocab", "rt_rec_beam_vocab", "rt_results_rec_beam_vocab",
+    "rt_debug_vocab_compile", "rt_debug_vocab_walk", "rt_debug_ctc_beam_vocab", "rt_debug_ctc_beam_vocab_host",
     "rt_set_det_tiles", "rt_det_tiles", "rt_det_tile_plan", "rt_debug_det_tiles", "rt_debug_arena_high_water", "rt_bench_memcpy_d2d",
     "rt_set_rec_windows", "rt_rec_windows", "rt_rec_window_plan", "rt_results_rec_windows", "rt_debug_rec_windows",
 ]
@@ -376,6 +386,24 @@ def load():
     lib.rt_debug_ctc_beam_lm_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int,
                                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_float, C.c_float,
                                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.rt_vocab_create.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_int, C.c_int, P(C.c_int)]
+    lib.rt_vocab_info.argtypes = [C.c_void_p, C.c_int, P(C.c_int), P(C.c_int), P(C.c_int), P(C.c_int)]
+    lib.rt_set_rec_beam_vocab.argtypes = [C.c_void_p, C.c_int, C.c_float]
+    lib.rt_rec_beam_vocab.argtypes = [C.c_void_p, P(C.c_int), P(C.c_float)]
+    lib.rt_results_rec_beam_vocab.argtypes = [C.c_void_p, C.c_int, C.c_int, P(P(BeamVocab))]
+    lib.rt_debug_vocab_compile.argtypes = [C.c_char_p, C.c_size_t, C.c_char_p, C.c_size_t, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
+                                           C.c_int, P(C.c_int), P(C.c_int), P(C.c_int), P(C.c_int), P(C.c_int), P(C.c_int), P(C.c_int),
+                                           C.c_char_p, C.c_size_t]
+    lib.rt_debug_vocab_walk.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                        C.c_void_p, C.c_char_p, C.c_size_t]
+    lib.rt_debug_ctc_beam_vocab.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int,
+                                            C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_float,
+                                            C.c_float, C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p,
+                                            C.c_void_p, C.c_void_p]
+    lib.rt_debug_ctc_beam_vocab_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int,
+                                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_float, C.c_float,
+                                                 C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                 C.c_void_p, C.c_void_p]
     lib.rt_set_det_tiles.argtypes = [C.c_void_p, C.c_int, C.c_int]
     lib.rt_det_tiles.argtypes = [C.c_void_p, P(C.c_int), P(C.c_int)]
     lib.rt_det_tile_plan.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, P(C.c_int32), P(C.c_int32), C.c_int, P(C.c_int32), P(C.c_int32),

@@ -73,6 +73,15 @@ def build_parser() -> argparse.ArgumentParser:
                          "hypotheses gain \"lm_logprob\" and \"lm_score\" (the effect on accuracy is not measured)")
     ap.add_argument("--rec-lm-weights", default="1.0,0.0", metavar="ALPHA,BETA",
                     help="with --rec-lm: the beam keeps the candidates with the best logprob + ALPHA * lm + BETA * length")
+    ap.add_argument("--rec-vocab", default=None, metavar="FILE",
+                    help="with --rec-beam: a word list, one word per line in UTF-8 over the dictionary, fused into the beam search: "
+                         "every word of a hypothesis that is not in the list costs G; characters the list does not spell with "
+                         "(digits, punctuation, the space) pass freely and separate words; the hypotheses gain \"oov_words\" and "
+                         "\"vocab_score\" (the effect on accuracy is not measured)")
+    ap.add_argument("--rec-vocab-gamma", type=float, default=4.0, metavar="G",
+                    help="with --rec-vocab: the cost of a word that is not in the list, in nats (default 4.0)")
+    ap.add_argument("--rec-vocab-case-variants", action="store_true",
+                    help="with --rec-vocab: every word also Capitalised and in UPPER CASE")
     return ap
 
 
@@ -145,6 +154,11 @@ def main(argv=None) -> int:
             raise SystemExit("--rec-lm needs --rec-beam")
         with open(a.rec_lm, "rb") as f:
             session.set_rec_beam_lm(session.create_lm(f.read()), *parse_weights(a.rec_lm_weights))
+    if a.rec_vocab is not None:
+        if a.rec_beam is None:
+            raise SystemExit("--rec-vocab needs --rec-beam")
+        with open(a.rec_vocab, "rb") as f:
+            session.set_rec_beam_vocab(session.create_vocab(f.read(), case_variants=a.rec_vocab_case_variants), a.rec_vocab_gamma)
     files = walk_files(a.images)
     log.info("Found %d files, processing...", len(files))
     out = open(a.json, "w") if a.json else None
@@ -185,7 +199,8 @@ def main(argv=None) -> int:
                                        "free_logprob": t.pattern[2]} for t in r.rec_result]
                 if a.rec_beam is not None:   # per line: its hypotheses, best first; lm_logprob / lm_score with --rec-lm
                     rec["beams"] = [[dict({"text": h.text, "tokens": [int(c) for c in h.tokens], "logprob": h.logprob},
-                                          **({} if h.lm_score is None else {"lm_logprob": h.lm_logprob, "lm_score": h.lm_score}))
+                                          **({} if h.lm_score is None else {"lm_logprob": h.lm_logprob, "lm_score": h.lm_score}),
+                                          **({} if h.vocab_score is None else {"oov_words": h.oov_words, "vocab_score": h.vocab_score}))
                                      for h in (t.beams or [])] for t in r.rec_result]
                 out.write(json.dumps(rec, ensure_ascii=False) + "\n")
     dur = time.perf_counter() - start

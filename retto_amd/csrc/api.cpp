@@ -413,6 +413,37 @@ int rt_rec_beam_lm(const rt_session* s, int* lm, float* alpha, float* beta) {
   if (beta) *beta = s->lm_beta;
   return RT_OK;
 }
+int rt_vocab_create(rt_session* s, const char* utf8, size_t len, const int32_t* ids, const int32_t* word_lens, int n_id_words, int flags,
+                    int* vocab_out) {
+  RT_REQUIRE(s && vocab_out && (utf8 || !len) && n_id_words >= 0 && ((ids && word_lens) || !n_id_words), s, "rt_vocab_create: bad argument");
+  *vocab_out = -1;
+  return guarded(s, [&] { *vocab_out = s->vocab_create(utf8, len, ids, word_lens, n_id_words, flags); });
+}
+int rt_vocab_info(const rt_session* s, int vocab, int* words, int* nodes, int* word_classes, int* variants_dropped) {
+  if (!s || !s->vocabs || vocab < 0 || vocab >= (int)s->vocabs->host.size()) return RT_ERR_INVALID;
+  const vc::Vocab& m = *s->vocabs->host[(size_t)vocab];
+  if (words) *words = m.n_words;
+  if (nodes) *nodes = (int)m.nodes.size();
+  if (word_classes) *word_classes = m.n_word_classes;
+  if (variants_dropped) *variants_dropped = m.variants_dropped;
+  return RT_OK;
+}
+int rt_set_rec_beam_vocab(rt_session* s, int vocab, float gamma) {
+  RT_REQUIRE(s, s, "rt_set_rec_beam_vocab: null session");
+  return guarded(s, [&] {
+    if (vocab == -1) { s->beam_vocab = -1; s->vocab_gamma = 0.0f; return; }
+    if (vocab < 0 || vocab >= (int)s->vocabs->host.size())
+      throw RtError(RT_ERR_INVALID, "rt_set_rec_beam_vocab: " + std::to_string(vocab) + " is not a vocabulary of this session");
+    if (const char* why = vc::check_gamma(gamma)) throw RtError(RT_ERR_INVALID, std::string("rt_set_rec_beam_vocab: ") + why);
+    s->beam_vocab = vocab; s->vocab_gamma = gamma;
+  });
+}
+int rt_rec_beam_vocab(const rt_session* s, int* vocab, float* gamma) {
+  if (!s) return RT_ERR_INVALID;
+  if (vocab) *vocab = s->beam_vocab;
+  if (gamma) *gamma = s->vocab_gamma;
+  return RT_OK;
+}
 int rt_set_rec_windows(rt_session* s, int window, int overlap) {
   RT_REQUIRE(s, s, "rt_set_rec_windows: null session");
   return guarded(s, [&] {
@@ -720,6 +751,12 @@ int rt_results_rec_beam_lm(const rt_results* r, int page, int line, const rt_bea
   auto* p = page_of_line(r, page, line, &rt_results::Page::bm_count);
   if (!p || p->beam_n <= 0 || p->bm_lm.empty()) return 0;
   if (out) *out = reinterpret_cast<const rt_beam_lm*>(p->bm_lm.data()) + (size_t)line * p->beam_n;
+  return p->bm_count[(size_t)line];
+}
+int rt_results_rec_beam_vocab(const rt_results* r, int page, int line, const rt_beam_vocab** out) {
+  auto* p = page_of_line(r, page, line, &rt_results::Page::bm_count);
+  if (!p || p->beam_n <= 0 || p->bm_vocab.empty()) return 0;
+  if (out) *out = reinterpret_cast<const rt_beam_vocab*>(p->bm_vocab.data()) + (size_t)line * p->beam_n;
   return p->bm_count[(size_t)line];
 }
 int rt_results_rec_beam_tokens(const rt_results* r, int page, int line, int k, const int32_t** tokens) {

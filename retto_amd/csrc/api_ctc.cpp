@@ -29,6 +29,11 @@ static_assert(RT_MAX_LM_ORDER == lm::MAX_ORDER && RT_MAX_LM_NGRAMS == lm::MAX_NG
 static_assert(sizeof(rt_beam_lm) == sizeof(lm::BeamLm) && offsetof(rt_beam_lm, lm) == offsetof(lm::BeamLm, lm) &&
                   offsetof(rt_beam_lm, score) == offsetof(lm::BeamLm, score), "rt_beam_lm and lm::BeamLm must share one layout");
 static_assert(RT_OK == lm::OK && RT_ERR_INVALID == lm::ERR_INVALID, "the status codes of ctc_lm.h are the RT_ERR_* ones");
+static_assert(RT_VOCAB_MAX_LEN == vc::MAX_LEN && RT_VOCAB_MAX_WORDS == vc::MAX_WORDS && RT_MAX_VOCABS == vc::MAX_VOCABS &&
+                  RT_VOCAB_CASE_VARIANTS == vc::CASE_VARIANTS, "the RT_VOCAB_* limits and vc:: must agree");
+static_assert(sizeof(rt_beam_vocab) == sizeof(vc::BeamVocab) && offsetof(rt_beam_vocab, oov_words) == offsetof(vc::BeamVocab, oov_words) &&
+                  offsetof(rt_beam_vocab, score) == offsetof(vc::BeamVocab, score), "rt_beam_vocab and vc::BeamVocab must share one layout");
+static_assert(RT_OK == vc::OK && RT_ERR_INVALID == vc::ERR_INVALID && RT_ERR_CAPACITY == vc::ERR_CAPACITY, "the status codes of ctc_vocab.h are the RT_ERR_* ones");
 static_assert(RT_MAX_PATTERNS == pt::MAX_PATTERNS && RT_PATTERN_MAX_STATES == pt::MAX_STATES && RT_PATTERN_MAX_PAIRS == pt::MAX_PAIRS &&
                   RT_PATTERN_MAX_BYTES == pt::MAX_BYTES, "the RT_PATTERN_* limits and pt:: must agree");
 static_assert(RT_OK == pt::OK && RT_ERR_UTF8 == pt::ERR_UTF8 && RT_ERR_INVALID == pt::ERR_INVALID && RT_ERR_CAPACITY == pt::ERR_CAPACITY,
@@ -540,6 +545,125 @@ RT_API int rt_debug_ctc_beam_lm(rt_session* s, const float* z5, const float* W, 
     DevBufs::download(counts_out, t.count, (size_t)n_lines);
     DevBufs::download(reinterpret_cast<bm::Beam*>(beams_out), t.recs, (size_t)n_lines * nbest);
     DevBufs::download(reinterpret_cast<lm::BeamLm*>(lm_out), t.lms, (size_t)n_lines * nbest);
+    DevBufs::download(tokens_out, t.tok, (size_t)a.rows * nbest);
+  });
+}
+
+// ---- beams with a word list (ctc_vocab.h): the vocabulary in its id form, compiled by the check; its tables go to the device as
+// rt_vocab_create puts them
+int rt_debug_vocab_compile(const void* dict, size_t dict_len, const char* utf8, size_t len, int flags, int32_t* word_ids_out, int ids_cap,
+                           int32_t* word_lens_out, int n_cap, int* n_ids_out, int* n_out, int* words_out, int* nodes_out,
+                           int* word_classes_out, int* variants_dropped_out, int* n_classes, char* err, size_t err_cap) {
+  const bool bad = (!dict && dict_len) || (!utf8 && len) || !n_ids_out || !n_out || !words_out || !nodes_out || !word_classes_out ||
+                   !variants_dropped_out || !n_classes || ids_cap < 0 || n_cap < 0 || (!word_ids_out && ids_cap) || (!word_lens_out && n_cap);
+  if (!bad) { *n_ids_out = 0; *n_out = 0; *words_out = 0; *nodes_out = 0; *word_classes_out = 0; *variants_dropped_out = 0; }
+  return compile_hook("rt_debug_vocab_compile", bad, dict, dict_len, n_classes, err, err_cap, [&](const std::vector<std::string>& d) {
+    vc::Ids f;
+    const vc::Vocab m = rt::compile_vocab(d, utf8, len, nullptr, nullptr, 0, flags, f);
+    *n_ids_out = (int)f.ids.size(); *n_out = f.n(); *words_out = m.n_words; *nodes_out = (int)m.nodes.size();
+    *word_classes_out = m.n_word_classes; *variants_dropped_out = m.variants_dropped;
+    if ((size_t)ids_cap < f.ids.size() || n_cap < f.n())
+      throw RtError(RT_ERR_INVALID, "rt_debug_vocab_compile: the vocabulary needs " + std::to_string(f.ids.size()) + " ids and " + std::to_string(f.n()) + " words");
+    memcpy(word_ids_out, f.ids.data(), f.ids.size() * sizeof(int32_t));
+    memcpy(word_lens_out, f.lens.data(), f.lens.size() * sizeof(int32_t));
+  });
+}
+int rt_debug_vocab_walk(int classes, const int32_t* word_ids, const int32_t* word_lens, int n_words, const int32_t* strings,
+                        const int32_t* string_lens, int n_strings, int32_t* open_out, int32_t* closed_out, int32_t* state_out, char* err,
+                        size_t err_cap) {
+  if (err && err_cap) err[0] = 0;
+  auto refuse = [&](int code, const std::string& why) {
+    if (err && err_cap) snprintf(err, err_cap, "rt_debug_vocab_walk: %s", why.c_str());
+    return code;
+  };
+  if (n_strings < 0 || (n_strings > 0 && (!strings || !string_lens || !open_out || !closed_out || !state_out))) return refuse(RT_ERR_INVALID, "bad argument");
+  if (n_words < 0 || (n_words > 0 && (!word_ids || !word_lens))) return refuse(RT_ERR_INVALID, "the vocabulary's arrays are null or n_words is negative");
+  try {
+    vc::Vocab m; std::string msg;
+    const int rc = vc::compile(classes, word_ids, word_lens, n_words, m, msg);
+    if (rc != vc::OK) return refuse(rc, msg);
+    long long o = 0;
+    for (int i = 0; i < n_strings; i++) {
+      if (string_lens[i] < 0) return refuse(RT_ERR_INVALID, "string " + std::to_string(i) + " has a negative length");
+      for (int k = 0; k < string_lens[i]; k++)
+        if (strings[o + k] < 1 || strings[o + k] >= classes)
+          return refuse(RT_ERR_INVALID, "class id " + std::to_string(strings[o + k]) + " in string " + std::to_string(i) + " is outside [1, " + std::to_string(classes) + ")");
+      o += string_lens[i];
+    }
+    const vc::View v = m.view();
+    o = 0;
+    for (int i = 0; i < n_strings; i++) {
+      const vc::Walk x = vc::walk(v, strings + o, string_lens[i]);
+      open_out[i] = x.oov; closed_out[i] = x.closed; state_out[i] = x.state;
+      o += string_lens[i];
+    }
+    return RT_OK;
+  } catch (const std::exception& e) {
+    if (err && err_cap) snprintf(err, err_cap, "%s", e.what());
+    return RT_ERR_BACKEND;
+  }
+}
+namespace {
+void fill_vocab_args(hr::BeamVocabArgs& a, const float* z5, const float* W, const float* bias, int N, const int32_t* tokens_per_line, int n_lines,
+          int beam, int nbest, const int32_t* ngram_ids, const int32_t* ngram_lens, const float* logp, const float* backoff, int n,
+          float oov, float alpha, float beta, const int32_t* word_ids, const int32_t* word_lens, int n_words, float gamma,
+          int32_t* counts_out, rt_beam* beams_out, int32_t* tokens_out, rt_beam_lm* lm_out, rt_beam_vocab* vocab_out) {
+  static_cast<hr::Head&>(a) = hr::Head{z5, W, bias, N, tokens_per_line, n_lines};
+  a.beam = beam; a.nbest = nbest; a.counts_out = counts_out; a.beams_out = beams_out; a.tokens_out = tokens_out;
+  a.ids = {ngram_ids, ngram_lens, logp, backoff, n, oov}; a.alpha = alpha; a.beta = beta; a.lm_out = lm_out;
+  a.words = {word_ids, word_lens, n_words}; a.gamma = gamma; a.vocab_out = vocab_out;
+}
+}  // namespace
+int rt_debug_ctc_beam_vocab_host(const float* z5, const float* W, const float* bias, int N, const int32_t* tokens_per_line, int n_lines,
+                                 int beam, int nbest, const int32_t* ngram_ids, const int32_t* ngram_lens, const float* logp,
+                                 const float* backoff, int n, float oov, float alpha, float beta, const int32_t* word_ids,
+                                 const int32_t* word_lens, int n_words, float gamma, int32_t* counts_out, rt_beam* beams_out,
+                                 int32_t* tokens_out, rt_beam_lm* lm_out, rt_beam_vocab* vocab_out) {
+  hr::BeamVocabArgs a;
+  fill_vocab_args(a, z5, W, bias, N, tokens_per_line, n_lines, beam, nbest, ngram_ids, ngram_lens, logp, backoff, n, oov, alpha, beta, word_ids,
+       word_lens, n_words, gamma, counts_out, beams_out, tokens_out, lm_out, vocab_out);
+  return host_entry("rt_debug_ctc_beam_vocab_host", a, hr::beam_vocab_ref);
+}
+RT_API int rt_debug_ctc_beam_vocab(rt_session* s, const float* z5, const float* W, const float* bias, int N, const int32_t* tokens_per_line,
+                                   int n_lines, int beam, int nbest, int chunk_rows, const int32_t* ngram_ids, const int32_t* ngram_lens,
+                                   const float* logp, const float* backoff, int n, float oov, float alpha, float beta,
+                                   const int32_t* word_ids, const int32_t* word_lens, int n_words, float gamma, int32_t* counts_out,
+                                   rt_beam* beams_out, int32_t* tokens_out, rt_beam_lm* lm_out, rt_beam_vocab* vocab_out) {
+  hr::BeamVocabArgs a;
+  fill_vocab_args(a, z5, W, bias, N, tokens_per_line, n_lines, beam, nbest, ngram_ids, ngram_lens, logp, backoff, n, oov, alpha, beta, word_ids,
+       word_lens, n_words, gamma, counts_out, beams_out, tokens_out, lm_out, vocab_out);
+  if (const int rc = device_check(s, "rt_debug_ctc_beam_vocab", a, chunk_rows)) return rc;
+  return guarded(s, [&] {
+    if (beam == 0 || n_lines == 0) return;   // (off, or no line: no launch, no write)
+    TailHook h(s, a, {nullptr, nullptr, 0, chunk_rows, beam, nbest}, std::vector<RecLineOpts>((size_t)n_lines), RecStores{});
+    rt_session::RecTail::Beam& t = h.t.beam;
+    // (what the kernels write starts as the caller's values: a slot they leave alone comes back untouched)
+    const size_t nt = (size_t)std::max<long long>(a.rows, 1) * nbest, nr = (size_t)n_lines * nbest;
+    const bool fused = a.has_model();
+    t.count = h.bufs.upload(counts_out, (size_t)n_lines);
+    t.recs = h.bufs.upload(reinterpret_cast<const bm::Beam*>(beams_out), nr);
+    t.vocs = h.bufs.upload(reinterpret_cast<const vc::BeamVocab*>(vocab_out), nr);
+    t.tok = h.bufs.alloc<int>(nt);
+    DevBufs::put(t.tok, tokens_out, (size_t)a.rows * nbest);
+    if (fused) {
+      const lm::Model& m = a.model;
+      t.lms = h.bufs.upload(reinterpret_cast<const lm::BeamLm*>(lm_out), nr);
+      t.fused = true;
+      t.fu = lm::Fusion{lm::View{h.bufs.upload(m.uni.data(), m.uni.size()), h.bufs.upload(m.states.data(), m.states.size()),
+                                 h.bufs.upload(m.arcs.data(), m.arcs.size()), m.classes, (int32_t)m.states.size(), (int32_t)m.arcs.size(), m.start},
+                        alpha, beta};
+    }
+    const vc::Vocab& w = a.vocab;
+    t.worded = true;
+    t.wc = vc::Constraint{vc::View{h.bufs.upload(w.nodes.data(), w.nodes.size()), h.bufs.upload(w.arcs.data(), w.arcs.size()),
+                                   h.bufs.upload(w.mask.data(), w.mask.size()), h.bufs.upload(w.root.data(), w.root.size()), w.classes,
+                                   (int32_t)w.nodes.size(), (int32_t)w.arcs.size()},
+                          gamma};
+    h.run();
+    DevBufs::download(counts_out, t.count, (size_t)n_lines);
+    DevBufs::download(reinterpret_cast<bm::Beam*>(beams_out), t.recs, nr);
+    DevBufs::download(reinterpret_cast<vc::BeamVocab*>(vocab_out), t.vocs, nr);
+    if (fused) DevBufs::download(reinterpret_cast<lm::BeamLm*>(lm_out), t.lms, nr);
     DevBufs::download(tokens_out, t.tok, (size_t)a.rows * nbest);
   });
 }

@@ -33,8 +33,11 @@
 // alignments -- those that stayed inside the beam -- so it never exceeds the string's full CTC forward log-likelihood; with a beam
 // that never overflows it IS that likelihood.  Language-model fusion (rt_set_rec_beam_lm) is ctc_lm.h's: with a lm::Fusion
 // every member also carries the model's sum over its string and its model state, and "selection" orders by lm::key_of() -- the
-// fused score -- in place of the total; everything else above, logprob included, stays.  Out of scope: a charset- or
-// pattern-restricted beam, per-region widths or models, time steps or word boxes of the alternatives.
+// fused score -- in place of the total; everything else above, logprob included, stays.  A word list (rt_set_rec_beam_vocab) is
+// ctc_vocab.h's: with a vc::Constraint every member also carries its trie state and its count of words that are no entries,
+// "selection" orders by vc::key_of() -- the fused score (or the total) minus gamma per such word -- and "result" ranks the final
+// beam once more by the closing key before it takes the first N.  Out of scope: a charset- or pattern-restricted beam,
+// per-region widths, models or vocabularies, word-level n-grams, time steps or word boxes of the alternatives.
 //
 // Device form.  Strings live in a per-line trie of (parent, token) nodes with find-or-create, so that one string always has one
 // node: "member j' is string_j + c" is then parent(j') == node_j && last_j' == c.  Only the at most B survivors of a step need
@@ -48,6 +51,7 @@
 
 #include "ctc_lexicon.h"
 #include "ctc_lm.h"
+#include "ctc_vocab.h"
 
 namespace rt {
 namespace bm {
@@ -97,13 +101,21 @@ inline void row_topc(const float* logits, int N, TopC* out) {
 }
 // Host reference: the hypotheses of one line from its logits [T][ld] (N classes) and lse [T] -> out[0 .. count) and hypothesis k's
 // tokens at tokens[k * T ...]; returns the count.  Strings are plain vectors here: identity is comparison.  f (with lm_out
-// [nbest]): language-model fusion (ctc_lm.h); null: a candidate's key is its total
+// [nbest]): language-model fusion (ctc_lm.h); null: a candidate's key is its total.  w (with vocab_out [nbest]): the word-list
+// constraint (ctc_vocab.h) on top of either
 inline int line_beams(const float* logits, int ld, const float* lse, int T, int N, int B, int nbest, Beam* out, int32_t* tokens,
-                      const lm::Fusion* f = nullptr, lm::BeamLm* lm_out = nullptr) {
+                      const lm::Fusion* f = nullptr, lm::BeamLm* lm_out = nullptr, const vc::Constraint* w = nullptr,
+                      vc::BeamVocab* vocab_out = nullptr) {
   if (T <= 0) return 0;
-  struct Hyp { std::vector<int32_t> s; float pb, pnb, lm; int state; };
-  struct Cand { float total, pb, pnb; int index, j, c; float key, lm; int state; };
-  std::vector<Hyp> beam(1, Hyp{{}, 0.0f, -INFINITY, 0.0f, f ? f->m.start : 0}), next;
+  struct Hyp { std::vector<int32_t> s; float pb, pnb, lm; int state, vstate, oov; };
+  struct Cand { float total, pb, pnb; int index, j, c; float key, lm; int state, vstate, oov; };
+  // a candidate's key from its total, lm, length and count: vc::key_of over the fused score or the total with a word list,
+  // lm::key_of with a model alone, the total otherwise
+  auto key_of = [&](float total, float lmv, int len, int oov) {
+    if (w) return vc::key_of(total, f ? lm::fused_of(total, lmv, len, f->alpha, f->beta) : total, oov, w->gamma);
+    return f ? lm::key_of(total, lmv, len, f->alpha, f->beta) : total;
+  };
+  std::vector<Hyp> beam(1, Hyp{{}, 0.0f, -INFINITY, 0.0f, f ? f->m.start : 0, 0, 0}), next;
   std::vector<Cand> cands;
   for (int t = 0; t < T; t++) {
     const float* l = logits + (size_t)t * ld;
@@ -132,21 +144,24 @@ inline int line_beams(const float* logits, int ld, const float* lse, int T, int 
         }
         if (target >= 0) spnb[target] = merged(spnb[target], v);
         else {
-          Cand a{total_of(-INFINITY, v), -INFINITY, v, ext_index(j, r), j, c, 0.0f, 0.0f, 0};
-          a.key = a.total;
+          Cand a{total_of(-INFINITY, v), -INFINITY, v, ext_index(j, r), j, c, 0.0f, 0.0f, 0, 0, 0};
           if (f) {
             const lm::Step x = lm::step(f->m, h.state, c);
             a.lm = h.lm + x.score; a.state = x.next;
-            a.key = lm::key_of(a.total, a.lm, (int)h.s.size() + 1, f->alpha, f->beta);
           }
+          if (w) {
+            const vc::Step x = vc::step(w->v, h.vstate, c);
+            a.vstate = x.next; a.oov = h.oov + x.add;
+          }
+          a.key = key_of(a.total, a.lm, (int)h.s.size() + 1, a.oov);
           cands.push_back(a);
         }
       }
     }
     for (int j = 0; j < n; j++) {
       const Hyp& h = beam[(size_t)j];
-      Cand a{total_of(spb[j], spnb[j]), spb[j], spnb[j], j, j, 0, 0.0f, h.lm, h.state};
-      a.key = f ? lm::key_of(a.total, a.lm, (int)h.s.size(), f->alpha, f->beta) : a.total;
+      Cand a{total_of(spb[j], spnb[j]), spb[j], spnb[j], j, j, 0, 0.0f, h.lm, h.state, h.vstate, h.oov};
+      a.key = key_of(a.total, a.lm, (int)h.s.size(), a.oov);
       cands.push_back(a);
     }
     cands.erase(std::remove_if(cands.begin(), cands.end(), [](const Cand& a) { return !alive(a.total); }), cands.end());
@@ -154,17 +169,29 @@ inline int line_beams(const float* logits, int ld, const float* lse, int T, int 
     next.clear();
     for (size_t i = 0; i < cands.size() && (int)i < B; i++) {
       const Cand& a = cands[i];
-      Hyp h{beam[(size_t)a.j].s, a.pb, a.pnb, a.lm, a.state};
+      Hyp h{beam[(size_t)a.j].s, a.pb, a.pnb, a.lm, a.state, a.vstate, a.oov};
       if (a.index >= MAX_BEAM) h.s.push_back(a.c);
       next.push_back(std::move(h));
     }
     beam.swap(next);
   }
-  const int count = std::min(nbest, (int)beam.size());
+  // (with a word list: the final beam ranked by the closing key, then beam order)
+  const int n = (int)beam.size();
+  int order[MAX_BEAM], closed[MAX_BEAM]; float ckey[MAX_BEAM];
+  for (int j = 0; j < n; j++) {
+    const Hyp& h = beam[(size_t)j];
+    order[j] = j;
+    closed[j] = w ? h.oov + vc::close(w->v, h.vstate) : 0;
+    ckey[j] = w ? key_of(total_of(h.pb, h.pnb), h.lm, (int)h.s.size(), closed[j]) : 0.0f;
+  }
+  if (w) std::sort(order, order + n, [&](int a, int b) { return cc::better(ckey[a], a, ckey[b], b); });
+  const int count = std::min(nbest, n);
   for (int k = 0; k < count; k++) {
-    const Hyp& h = beam[(size_t)k];
+    const Hyp& h = beam[(size_t)order[k]];
     out[k] = Beam{total_of(h.pb, h.pnb), (int32_t)h.s.size()};
-    if (f && lm_out) lm_out[k] = lm::BeamLm{h.lm, lm::fused_of(out[k].logprob, h.lm, out[k].n_tokens, f->alpha, f->beta)};
+    const float fused = f ? lm::fused_of(out[k].logprob, h.lm, out[k].n_tokens, f->alpha, f->beta) : out[k].logprob;
+    if (f && lm_out) lm_out[k] = lm::BeamLm{h.lm, fused};
+    if (w && vocab_out) vocab_out[k] = vc::BeamVocab{closed[order[k]], vc::score_of(fused, closed[order[k]], w->gamma)};
     for (size_t i = 0; i < h.s.size(); i++) tokens[(size_t)k * T + i] = h.s[i];
   }
   return count;

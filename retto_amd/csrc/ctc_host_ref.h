@@ -391,5 +391,50 @@ inline void beam_lm_ref(const BeamLmArgs& a) {
   });
 }
 
+// ---- beams with a word list (ctc_vocab.h), with or without a model: the fused beam's arguments -- n = 0 n-grams with
+// alpha = beta = 0 means no model, and lm_out may be null then -- plus the vocabulary in its id form over the head's N classes
+// and gamma; the check compiles both.  vocab_out [n_lines][nbest] beside beams_out
+struct IdVocab {
+  const int32_t* word_ids = nullptr; const int32_t* word_lens = nullptr; int n = 0;
+  // the first requirement that fails, or the empty string with the vocabulary compiled into m
+  std::string compile(int classes, vc::Vocab& m) const {
+    if (n < 0 || (n > 0 && (!word_ids || !word_lens))) return "the vocabulary's arrays are null or n_words is negative";
+    std::string msg;
+    return vc::compile(classes, word_ids, word_lens, n, m, msg) == vc::OK ? std::string() : msg;
+  }
+};
+struct BeamVocabArgs : BeamArgs {
+  IdModel ids; float alpha = 0.0f, beta = 0.0f;
+  rt_beam_lm* lm_out = nullptr;
+  IdVocab words; float gamma = 0.0f;
+  rt_beam_vocab* vocab_out = nullptr;
+  lm::Model model; vc::Vocab vocab;
+  bool has_model() const { return ids.n != 0 || alpha != 0.0f || beta != 0.0f; }
+  std::string error() {
+    if (!vocab_out || (has_model() && !lm_out)) return "a required pointer is null";
+    const std::string bad = BeamArgs::error();
+    if (!bad.empty()) return bad;
+    if (const char* why = lm::check_weights(alpha, beta)) return why;
+    if (const char* why = vc::check_gamma(gamma)) return why;
+    if (has_model()) {
+      const std::string m = ids.compile(N, model);
+      if (!m.empty()) return m;
+    }
+    return words.compile(N, vocab);
+  }
+};
+inline void beam_vocab_ref(const BeamVocabArgs& a) {
+  if (a.beam == 0) return;
+  const lm::Fusion f{a.model.view(), a.alpha, a.beta};
+  const vc::Constraint w{a.vocab.view(), a.gamma};
+  const bool fused = a.has_model();
+  walk_lines(a, lx::row_lse, [](int) { return true; }, [&](int i, long long o, int T, const float* logits, const float* lse) {
+    a.counts_out[i] = bm::line_beams(logits, a.N, lse, T, a.N, a.beam, a.nbest, reinterpret_cast<bm::Beam*>(a.beams_out) + (size_t)i * a.nbest,
+                                     a.tokens_out + o * a.nbest, fused ? &f : nullptr,
+                                     fused ? reinterpret_cast<lm::BeamLm*>(a.lm_out) + (size_t)i * a.nbest : nullptr, &w,
+                                     reinterpret_cast<vc::BeamVocab*>(a.vocab_out) + (size_t)i * a.nbest);
+  });
+}
+
 }  // namespace hr
 }  // namespace rt

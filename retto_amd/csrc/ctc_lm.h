@@ -34,7 +34,9 @@
 // candidate index (cc::better): the fused score fused_of(total, lm, len, alpha, beta) = total + (alpha * lm + beta * len), kept
 // above -inf for a live candidate so that it never ties with a dead one.  alpha >= 0, alpha and beta finite.  A hypothesis'
 // logprob stays its CTC total; BeamLm carries lm and the fused score.  alpha = beta = 0 ranks by total + 0: the plain beam.
-// Out of scope: per-region models, word-level or neural models, a charset- or pattern-restricted beam.
+// A word list beside the model is ctc_vocab.h's (rt_set_rec_beam_vocab): its key is this fused score minus gamma per word that
+// is no entry.  Out of scope: per-region models or vocabularies, word-level n-grams or neural models, a charset- or
+// pattern-restricted beam.
 #pragma once
 #include <float.h>
 #include <math.h>

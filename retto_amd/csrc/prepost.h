@@ -142,7 +142,8 @@ void ctc_beam_topc(hipStream_t st, const float* logits, int ld, int classes, int
 // group's trie, bm::nodes_of(T, B) nodes per line from line.lex on; needs no initialisation.
 void ctc_beam_search(hipStream_t st, const float* logits, int ld, const float* lse, const bm::TopC* topc, const bm::Line* lines,
                      int n_lines, int chunk_row0, int B, int nbest, bm::Node* nodes, bm::Beam* beams, int* tokens, int* counts,
-                     const lm::Fusion* fu = nullptr, lm::BeamLm* lms = nullptr);
+                     const lm::Fusion* fu = nullptr, lm::BeamLm* lms = nullptr, const vc::Constraint* wc = nullptr,
+                     vc::BeamVocab* vocs = nullptr);
 // Lexicon snap (ctc_lexicon_align.h): one wave64 per line of lines[0..n_lines) (one chunk, resident as for ctc_lexicon_forward,
 // after ctc_lexicon_topk over the same lines).  snapped[line.slot] <- 0 / 1 for every line; a line whose lexicon has
 // min_post[line.lex] > 0 and whose match 0 reaches it has its winner aligned (CTC Viterbi) and its rows rows[line.row0 ..

@@ -849,19 +849,33 @@ void ctc_beam_topc(hipStream_t st, const float* logits, int ld, int classes, int
 // writes the survivors' state and lm; the trie is untouched.  Bounds: lm::step reads state s only for 0 < s < n_states (anything
 // else is the empty context), cuts a state's arc slice to [0, n_arcs) and searches inside it in at most lm::ARC_STEPS halvings,
 // walks at most lm::MAX_ORDER levels, and reads uni[c] only for 1 <= c < classes; a record slot < n_lines nbest as beams'.
-template <bool LM>
+// VC: the word-list constraint (ctc_vocab.h), a second compile-time switch; the instances without it are the kernel as it was, to
+// the bit.  A member's trie state and its count of words that are no entries live in LDS twice beside state and lm; the
+// candidates have keys (vc::key_of over the fused score with LM, over the total without).  In B thread (j, r) takes vc::step
+// from vstate_j BEFORE it scans the beam for its merge target: the lookup -- one mask word, then one indexed load of the root's
+// dense table or one node record and a binary search of its arc slice -- needs only what the last barrier published, so its
+// loads are in flight under the scan and not behind it.  C gives the stays their keys, D ranks by the key, E writes the
+// survivors' vstate and count.  After the last step a closing phase: thread j < n takes its closing key (the count plus
+// vc::close of its state), counts the members that rank before it (the same counting selection: no sort, no atomics) and, if
+// its place is below nbest, writes its record, its rt_beam_vocab and its tokens there.  The tables are read-only global memory.
+// Bounds: vc::step reads mask[c >> 5] and root[c] only for 1 <= c < classes, node s only for 0 < s < n_nodes (anything else is
+// OFF), cuts a node's arc slice to [0, n_arcs) and searches inside it in at most vc::ARC_STEPS halvings; vc::close reads node s
+// only for 0 < s < n_nodes; a closing place is < n <= B, written only below nbest: a record slot < n_lines nbest as beams'.
+template <bool LM, bool VC>
 __global__ __launch_bounds__(256) void k_ctc_beam_search(const float* __restrict__ logits, int ld, const float* __restrict__ lse,
                                                          const bm::TopC* __restrict__ topc, const bm::Line* __restrict__ lines,
                                                          int chunk_row0, int B, int nbest, bm::Node* nodes,
                                                          bm::Beam* __restrict__ beams, int* __restrict__ tokens,
-                                                         int* __restrict__ counts, lm::Fusion fu, lm::BeamLm* __restrict__ lms) {
+                                                         int* __restrict__ counts, lm::Fusion fu, lm::BeamLm* __restrict__ lms,
+                                                         vc::Constraint wc, vc::BeamVocab* __restrict__ vocs) {
   constexpr int MB = bm::MAX_BEAM, TC = bm::TOP_C;
   static_assert(MB * TC == 256 && bm::CANDS == MB + 256, "one thread per extension");
   __shared__ int s_node[2][MB], s_par[2][MB], s_last[2][MB], s_len[2][MB], s_n[2];
   __shared__ float s_pb[2][MB], s_pnb[2][MB], s_tot[MB], s_spb[MB], s_spnb[MB], s_cand[bm::CANDS];
   __shared__ int s_state[2][LM ? MB : 1];
-  __shared__ float s_lm[2][LM ? MB : 1], s_key[LM ? bm::CANDS : 1];
-  const float* rank = LM ? s_key : s_cand;   // what D orders by
+  __shared__ float s_lm[2][LM ? MB : 1], s_key[LM || VC ? bm::CANDS : 1];
+  __shared__ int s_vstate[2][VC ? MB : 1], s_oov[2][VC ? MB : 1];
+  const float* rank = LM || VC ? s_key : s_cand;   // what D orders by
   const int tid = threadIdx.x, j = tid / TC, r = tid % TC;
   const bm::Line ln = lines[blockIdx.x];
   const int T = ln.T;
@@ -873,6 +887,7 @@ __global__ __launch_bounds__(256) void k_ctc_beam_search(const float* __restrict
     nd[0] = bm::Node{-1, 0, -1, -1};
     s_node[0][0] = 0; s_par[0][0] = -1; s_last[0][0] = 0; s_len[0][0] = 0; s_pb[0][0] = 0.0f; s_pnb[0][0] = -INFINITY; s_n[0] = 1;
     if (LM) { s_state[0][0] = fu.m.start; s_lm[0][0] = 0.0f; }
+    if (VC) { s_vstate[0][0] = 0; s_oov[0][0] = 0; }
   }
   __syncthreads();
   int cur = 0;
@@ -896,6 +911,11 @@ __global__ __launch_bounds__(256) void k_ctc_beam_search(const float* __restrict
     const bool ext = j < n && c != cc::EMPTY_ID;
     const int node = ext ? s_node[cur][j] : 0;
     float v = -INFINITY; int target = -1;
+    int evstate = 0, eoov = 0;
+    if (VC && ext) {   // (before the scan: see above)
+      const vc::Step x = vc::step(wc.v, s_vstate[cur][j], c);
+      evstate = x.next; eoov = s_oov[cur][j] + x.add;
+    }
     if (ext) {
       v = bm::ext_pnb(s_pb[cur][j], s_tot[j], c == s_last[cur][j], lc - ls);
       for (int q = 0; q < n; q++)
@@ -904,12 +924,16 @@ __global__ __launch_bounds__(256) void k_ctc_beam_search(const float* __restrict
     }
     s_cand[MB + tid] = ext && target < 0 ? bm::total_of(-INFINITY, v) : -INFINITY;
     float elm = 0.0f; int estate = 0;
-    if (LM) {
+    if (LM || VC) {
       float key = -INFINITY;
       if (ext && target < 0) {
-        const lm::Step x = lm::step(fu.m, s_state[cur][j], c);
-        elm = s_lm[cur][j] + x.score; estate = x.next;
-        key = lm::key_of(s_cand[MB + tid], elm, s_len[cur][j] + 1, fu.alpha, fu.beta);
+        const float total = s_cand[MB + tid];
+        if (LM) {
+          const lm::Step x = lm::step(fu.m, s_state[cur][j], c);
+          elm = s_lm[cur][j] + x.score; estate = x.next;
+        }
+        if (VC) key = vc::key_of(total, LM ? lm::fused_of(total, elm, s_len[cur][j] + 1, fu.alpha, fu.beta) : total, eoov, wc.gamma);
+        else key = lm::key_of(total, elm, s_len[cur][j] + 1, fu.alpha, fu.beta);
       }
       s_key[MB + tid] = key;
     }
@@ -917,7 +941,15 @@ __global__ __launch_bounds__(256) void k_ctc_beam_search(const float* __restrict
     // C
     if (tid < MB) {
       s_cand[tid] = tid < n ? bm::total_of(s_spb[tid], s_spnb[tid]) : -INFINITY;
-      if (LM) s_key[tid] = tid < n ? lm::key_of(s_cand[tid], s_lm[cur][tid], s_len[cur][tid], fu.alpha, fu.beta) : -INFINITY;
+      if (LM && !VC) s_key[tid] = tid < n ? lm::key_of(s_cand[tid], s_lm[cur][tid], s_len[cur][tid], fu.alpha, fu.beta) : -INFINITY;
+      if (VC) {
+        float key = -INFINITY;
+        if (tid < n) {
+          const float total = s_cand[tid];
+          key = vc::key_of(total, LM ? lm::fused_of(total, s_lm[cur][tid], s_len[cur][tid], fu.alpha, fu.beta) : total, s_oov[cur][tid], wc.gamma);
+        }
+        s_key[tid] = key;
+      }
     }
     __syncthreads();
     // D  (a dead candidate's key is -inf and a live one's is above it: lm::key_of)
@@ -950,12 +982,14 @@ __global__ __launch_bounds__(256) void k_ctc_beam_search(const float* __restrict
       s_node[nxt][eplace] = id; s_par[nxt][eplace] = node; s_last[nxt][eplace] = c; s_len[nxt][eplace] = s_len[cur][j] + 1;
       s_pb[nxt][eplace] = -INFINITY; s_pnb[nxt][eplace] = v;
       if (LM) { s_state[nxt][eplace] = estate; s_lm[nxt][eplace] = elm; }
+      if (VC) { s_vstate[nxt][eplace] = evstate; s_oov[nxt][eplace] = eoov; }
       atomicMax(&s_n[nxt], eplace + 1);
     }
     if (splace < B) {
       s_node[nxt][splace] = s_node[cur][tid]; s_par[nxt][splace] = s_par[cur][tid]; s_last[nxt][splace] = s_last[cur][tid];
       s_len[nxt][splace] = s_len[cur][tid]; s_pb[nxt][splace] = s_spb[tid]; s_pnb[nxt][splace] = s_spnb[tid];
       if (LM) { s_state[nxt][splace] = s_state[cur][tid]; s_lm[nxt][splace] = s_lm[cur][tid]; }
+      if (VC) { s_vstate[nxt][splace] = s_vstate[cur][tid]; s_oov[nxt][splace] = s_oov[cur][tid]; }
       atomicMax(&s_n[nxt], splace + 1);
     }
     __syncthreads();
@@ -963,6 +997,32 @@ __global__ __launch_bounds__(256) void k_ctc_beam_search(const float* __restrict
   }
   const int n = s_n[cur], count = n < nbest ? n : nbest;
   if (tid == 0) counts[ln.slot] = count;
+  if (VC) {   // the closing phase: the final beam ranked by the closing key, then beam order (n <= B <= MB; block-uniform)
+    float total = -INFINITY, fused = -INFINITY, ckey = -INFINITY; int closed = 0;
+    if (tid < n) {
+      total = bm::total_of(s_pb[cur][tid], s_pnb[cur][tid]);
+      fused = LM ? lm::fused_of(total, s_lm[cur][tid], s_len[cur][tid], fu.alpha, fu.beta) : total;
+      closed = s_oov[cur][tid] + vc::close(wc.v, s_vstate[cur][tid]);
+      ckey = vc::key_of(total, fused, closed, wc.gamma);
+      s_key[tid] = ckey;
+    }
+    __syncthreads();
+    if (tid < n) {
+      int place = 0;
+      for (int k = 0; k < n; k++) place += cc::better(s_key[k], k, ckey, tid) ? 1 : 0;
+      if (place < nbest) {
+        const int len = s_len[cur][tid];
+        const long long rec = (long long)ln.slot * nbest + place;
+        beams[rec] = bm::Beam{total, len};
+        if (LM) lms[rec] = lm::BeamLm{s_lm[cur][tid], fused};
+        vocs[rec] = vc::BeamVocab{closed, vc::score_of(fused, closed, wc.gamma)};
+        int* out = tokens + ln.out + (long long)place * T;
+        int q = s_node[cur][tid];
+        for (int i = len - 1; i >= 0 && q > 0 && q < n_nodes; i--) { out[i] = nd[q].tok; q = nd[q].parent; }
+      }
+    }
+    return;
+  }
   if (tid < count) {
     const int len = s_len[cur][tid];
     const float total = bm::total_of(s_pb[cur][tid], s_pnb[cur][tid]);
@@ -975,14 +1035,20 @@ __global__ __launch_bounds__(256) void k_ctc_beam_search(const float* __restrict
 }
 void ctc_beam_search(hipStream_t st, const float* logits, int ld, const float* lse, const bm::TopC* topc, const bm::Line* lines,
                      int n_lines, int chunk_row0, int B, int nbest, bm::Node* nodes, bm::Beam* beams, int* tokens, int* counts,
-                     const lm::Fusion* fu, lm::BeamLm* lms) {
+                     const lm::Fusion* fu, lm::BeamLm* lms, const vc::Constraint* wc, vc::BeamVocab* vocs) {
   if (n_lines <= 0) return;
-  if (fu)
-    RT_LAUNCH(k_ctc_beam_search<true>, dim3(n_lines), dim3(256), 0, st, logits, ld, lse, topc, lines, chunk_row0, B, nbest, nodes,
-              beams, tokens, counts, *fu, lms);
+  if (fu && wc)
+    RT_LAUNCH((k_ctc_beam_search<true, true>), dim3(n_lines), dim3(256), 0, st, logits, ld, lse, topc, lines, chunk_row0, B, nbest,
+              nodes, beams, tokens, counts, *fu, lms, *wc, vocs);
+  else if (wc)
+    RT_LAUNCH((k_ctc_beam_search<false, true>), dim3(n_lines), dim3(256), 0, st, logits, ld, lse, topc, lines, chunk_row0, B, nbest,
+              nodes, beams, tokens, counts, lm::Fusion{}, nullptr, *wc, vocs);
+  else if (fu)
+    RT_LAUNCH((k_ctc_beam_search<true, false>), dim3(n_lines), dim3(256), 0, st, logits, ld, lse, topc, lines, chunk_row0, B, nbest,
+              nodes, beams, tokens, counts, *fu, lms, vc::Constraint{}, nullptr);
   else
-    RT_LAUNCH(k_ctc_beam_search<false>, dim3(n_lines), dim3(256), 0, st, logits, ld, lse, topc, lines, chunk_row0, B, nbest, nodes,
-              beams, tokens, counts, lm::Fusion{}, nullptr);
+    RT_LAUNCH((k_ctc_beam_search<false, false>), dim3(n_lines), dim3(256), 0, st, logits, ld, lse, topc, lines, chunk_row0, B, nbest,
+              nodes, beams, tokens, counts, lm::Fusion{}, nullptr, vc::Constraint{}, nullptr);
 }
 
 // Lexicon snap (ctc_lexicon_align.h).  One wave64 per lexicon line of one chunk, after k_ctc_lexicon_topk has written the line's

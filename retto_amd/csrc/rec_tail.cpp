@@ -169,6 +169,117 @@ void compile_lexicon(const std::vector<std::string>& dict, const char* utf8, siz
   }
   if (lens_out.empty()) throw RtError(RT_ERR_INVALID, "lexicon: no entry");
 }
+void compile_vocab(const std::vector<std::string>& dict, const char* utf8, size_t len, const int32_t* ids, const int32_t* word_lens,
+                   int n_id_words, int flags, vc::Ids& out, int* variants_dropped) {
+  const int classes = (int)dict.size();
+  out = vc::Ids{};
+  *variants_dropped = 0;
+  if (flags & ~vc::CASE_VARIANTS) {
+    char b[64];
+    snprintf(b, sizeof b, "vocab: unknown flag bits 0x%x", (unsigned)(flags & ~vc::CASE_VARIANTS));
+    throw RtError(RT_ERR_INVALID, b);
+  }
+  // every class whose whole entry is one code point, under its code point: the lowest id wins (as compile_lexicon)
+  std::unordered_map<uint32_t, int> one;
+  for (int c = classes - 1; c >= 1; c--) {
+    const std::string& d = dict[(size_t)c];
+    uint32_t cp;
+    if (!d.empty() && (size_t)utf8_decode_strict((const unsigned char*)d.data(), d.size(), &cp) == d.size()) one[cp] = c;
+  }
+  std::unordered_map<std::string, int> seen;   // a word given twice is one word: the id form holds its first occurrence
+  auto add = [&](const std::vector<int32_t>& w) {
+    if (!seen.emplace(std::string((const char*)w.data(), w.size() * sizeof(int32_t)), 0).second) return;
+    if (out.n() >= vc::MAX_WORDS)
+      throw RtError(RT_ERR_CAPACITY, "vocab: more than RT_VOCAB_MAX_WORDS (" + std::to_string(vc::MAX_WORDS) + ") words");
+    out.ids.insert(out.ids.end(), w.begin(), w.end()); out.lens.push_back((int32_t)w.size());
+  };
+  // the code points -> ids; false (nothing appended) where the dictionary lacks one, *missing = that code point
+  auto to_ids = [&](const std::vector<uint32_t>& cps, std::vector<int32_t>& w, uint32_t* missing) {
+    w.clear();
+    for (uint32_t cp : cps) {
+      const auto it = one.find(cp);
+      if (it == one.end()) { *missing = cp; return false; }
+      w.push_back(it->second);
+    }
+    return true;
+  };
+  auto lower = [](uint32_t c) { return c >= 'a' && c <= 'z'; };
+  const unsigned char* p = (const unsigned char*)utf8;
+  std::vector<uint32_t> cps, var;
+  std::vector<int32_t> w;
+  size_t word = 0;   // (the line's number among the lines that hold a word, for the messages)
+  for (size_t pos = 0; pos < len; word++) {
+    size_t e = pos;
+    while (e < len && p[e] != '\n') e++;
+    size_t le = e;
+    if (e < len && le > pos && p[le - 1] == '\r') le--;
+    size_t first = std::string::npos, last_end = 0;   // (trimmed as a dictionary line is)
+    for (size_t i = pos; i < le;) {
+      uint32_t cp;
+      const int k = utf8_decode_strict(p + i, le - i, &cp);
+      if (k == 0) throw RtError(RT_ERR_UTF8, "vocab: the text is not valid UTF-8 (byte offset " + std::to_string(i) + ")");
+      if (!is_rust_whitespace(cp)) { if (first == std::string::npos) first = i; last_end = i + (size_t)k; }
+      i += (size_t)k;
+    }
+    pos = e + 1;
+    if (first == std::string::npos) { word--; continue; }
+    const std::string text((const char*)p + first, std::min<size_t>(last_end - first, 48));   // (the start of the word, for the messages)
+    cps.clear();
+    for (size_t i = first; i < last_end;) {
+      uint32_t cp;
+      i += (size_t)utf8_decode_strict(p + i, last_end - i, &cp);
+      cps.push_back(cp);
+    }
+    if ((int)cps.size() > vc::MAX_LEN)
+      throw RtError(RT_ERR_INVALID, "vocab: word " + std::to_string(word) + " (\"" + text + "...\") has " + std::to_string(cps.size()) +
+                                        " code points, more than RT_VOCAB_MAX_LEN (" + std::to_string(vc::MAX_LEN) + ")");
+    uint32_t missing = 0;
+    if (!to_ids(cps, w, &missing)) {
+      char b[160];
+      snprintf(b, sizeof b, "vocab: U+%04X in word %zu (\"%s\") matches no dictionary entry", (unsigned)missing, word, text.c_str());
+      throw RtError(RT_ERR_INVALID, b);
+    }
+    add(w);
+    if (!(flags & vc::CASE_VARIANTS)) continue;
+    for (int form = 0; form < 2; form++) {   // the first ASCII letter upper-cased; all of them
+      var = cps;
+      bool changed = false;
+      for (uint32_t& c : var)
+        if (lower(c)) { c -= 'a' - 'A'; changed = true; if (form == 0) break; }
+        else if (form == 0 && c >= 'A' && c <= 'Z') break;   // (its first letter is a capital already)
+      if (!changed) continue;
+      if (to_ids(var, w, &missing)) add(w); else (*variants_dropped)++;
+    }
+  }
+  size_t o = 0;
+  for (int j = 0; j < n_id_words; j++) {
+    const int n = word_lens[j];
+    if (n <= 0) throw RtError(RT_ERR_INVALID, "vocab: id word " + std::to_string(j) + " is empty");
+    if (n > vc::MAX_LEN)
+      throw RtError(RT_ERR_INVALID, "vocab: id word " + std::to_string(j) + " has " + std::to_string(n) + " ids, more than RT_VOCAB_MAX_LEN (" +
+                                        std::to_string(vc::MAX_LEN) + ")");
+    w.assign(ids + o, ids + o + (size_t)n);
+    for (int c : w) {
+      if (c == 0) throw RtError(RT_ERR_INVALID, "vocab: id word " + std::to_string(j) + ": the blank (class 0) is not a token");
+      if (c < 0 || c >= classes)
+        throw RtError(RT_ERR_INVALID, "vocab: class id " + std::to_string(c) + " in id word " + std::to_string(j) + " is outside [1, " +
+                                          std::to_string(classes) + ")");
+    }
+    add(w);
+    o += (size_t)n;
+  }
+  if (out.lens.empty()) throw RtError(RT_ERR_INVALID, "vocab: no word at all");
+}
+vc::Vocab compile_vocab(const std::vector<std::string>& dict, const char* utf8, size_t len, const int32_t* ids, const int32_t* word_lens,
+                        int n_id_words, int flags, vc::Ids& f) {
+  int dropped = 0;
+  compile_vocab(dict, utf8, len, ids, word_lens, n_id_words, flags, f, &dropped);
+  vc::Vocab m; std::string msg;
+  const int rc = vc::compile((int)dict.size(), f, m, msg);
+  if (rc != vc::OK) throw RtError(rc, msg);
+  m.variants_dropped = dropped;
+  return m;
+}
 }  // namespace rt
 
 // ---- the tail of one rec group (session.h "the rec network's CTC tail") ----
@@ -378,9 +489,11 @@ void rt_lane::ctc_beams(const RecTailPlan& p, const SvtrCore& core, const RecTai
       pp::ctc_beam_topc(st, lc.logits, lc.ld, core.classes, m, topc);
     }
     // (with a language model the search is its own profile family: its cost is then read off apart from the plain beam's)
-    ProfScope ps(&prof, st, o.fused ? "ctc_beam_search_lm" : "ctc_beam_search");
+    // (so is each instance with a word list)
+    ProfScope ps(&prof, st, o.worded ? (o.fused ? "ctc_beam_search_lm_vocab" : "ctc_beam_search_vocab")
+                                     : (o.fused ? "ctc_beam_search_lm" : "ctc_beam_search"));
     pp::ctc_beam_search(st, lc.logits, lc.ld, pass.lse, topc, d_lines, n, r0, o.b, o.n, nodes, o.recs, o.tok, o.count,
-                        o.fused ? &o.fu : nullptr, o.lms);
+                        o.fused ? &o.fu : nullptr, o.lms, o.worded ? &o.wc : nullptr, o.vocs);
   });
 }
 
@@ -486,6 +599,36 @@ int rt_session::lm_create(const char* arpa, size_t len, float oov_log10) {
   if (rc != lm::OK) throw RtError(rc, "rt_lm_create: " + msg);
   RT_HIP_CHECK(hipSetDevice(device));
   return lms->add(std::move(m));
+}
+
+// ---- the vocabularies (session.h rt_vocabs) ----
+namespace {
+void free_view(const vc::View& v) {
+  const void* p[] = {v.nodes, v.arcs, v.mask, v.root};
+  for (const void* q : p) if (q) (void)hipFree(const_cast<void*>(q));
+}
+}  // namespace
+rt_vocabs::~rt_vocabs() { for (const vc::View& v : dev) free_view(v); }
+int rt_vocabs::add(vc::Vocab m) {
+  host.reserve(host.size() + 1); dev.reserve(dev.size() + 1);   // (so that nothing behind the copies throws)
+  std::unique_ptr<vc::Vocab> h(new vc::Vocab(std::move(m)));
+  vc::View v = h->view();
+  v.nodes = nullptr; v.arcs = nullptr; v.mask = nullptr; v.root = nullptr;
+  try {
+    upload_table(&v.nodes, h->nodes); upload_table(&v.arcs, h->arcs); upload_table(&v.mask, h->mask); upload_table(&v.root, h->root);
+  } catch (...) { free_view(v); throw; }
+  host.push_back(std::move(h)); dev.push_back(v);
+  return (int)host.size() - 1;
+}
+int rt_session::vocab_create(const char* utf8, size_t len, const int32_t* ids, const int32_t* word_lens, int n_id_words, int flags) {
+  if ((int)vocabs->host.size() >= vc::MAX_VOCABS)
+    throw RtError(RT_ERR_CAPACITY, "rt_vocab_create: the session holds RT_MAX_VOCABS (" + std::to_string(vc::MAX_VOCABS) + ") vocabularies already");
+  vc::Ids f;
+  vc::Vocab m;
+  try { m = compile_vocab(dict, utf8, len, ids, word_lens, n_id_words, flags, f); }
+  catch (const RtError& e) { throw RtError(e.code, std::string("rt_vocab_create: ") + e.what()); }
+  RT_HIP_CHECK(hipSetDevice(device));
+  return vocabs->add(std::move(m));
 }
 
 int rt_session::pattern_create(const char* utf8, size_t len) {

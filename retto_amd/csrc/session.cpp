@@ -70,6 +70,7 @@ rt_session* rt_session_create(const rt_config* cfg) {
   s->patterns.reset(new rt_patterns());
   s->keywords.reset(new rt_keywords());
   s->lms.reset(new rt_lms());
+  s->vocabs.reset(new rt_vocabs());
   if ((int)s->dict.size() != s->rec->classes())
     throw RtError(RT_ERR_SHAPE, "dictionary has " + std::to_string(s->dict.size()) + " entries but the rec head has " +
                                     std::to_string(s->rec->classes()) + " classes");
@@ -601,6 +602,8 @@ struct Pipeline {
   Mirror<int> bmn; Mirror<bm::Beam> bmrec; Mirror<int> bmtok;
   // rec language model (ctc_lm.h; call.set.fused()): per record slot lm and the fused score; null otherwise
   Mirror<lm::BeamLm> bmlm;
+  // rec vocabulary (ctc_vocab.h; call.set.worded()): per record slot the closed count and the closing score; null otherwise
+  Mirror<vc::BeamVocab> bmvc;
 };
 
 // Launch groups: items [g0, end) where the group always takes its first item; with max_items > 0 it takes up to max_items items,
@@ -1055,6 +1058,7 @@ void rec_groups(rt_lane& s, Pipeline& P) {
   if (P.any.keywords) { P.kwh.alloc(s, (size_t)P.NLp * kw::HITS); P.kwn.alloc(s, P.NLp); }
   if (set.beam_b > 0) { P.bmn.alloc(s, P.NLp); P.bmrec.alloc(s, (size_t)P.NLp * set.beam_n); P.bmtok.alloc(s, ntok * (size_t)set.beam_n); }
   if (set.fused()) P.bmlm.alloc(s, (size_t)P.NLp * set.beam_n);
+  if (set.worded()) P.bmvc.alloc(s, (size_t)P.NLp * set.beam_n);
   static const long long REC_GROUP_PX = getenv("RT_REC_GROUP_PX") ? atoll(getenv("RT_REC_GROUP_PX")) : (long long)24000000;  // measured sweet spot (profiles/README.md)
   for (int l0 = 0; l0 < P.NL;) {
     // (a windowed line is charged with its units' pixels, rec_windows.h: what the network is run on)
@@ -1111,6 +1115,7 @@ void rec_groups(rt_lane& s, Pipeline& P) {
     t.beam.b = set.beam_b; t.beam.n = set.beam_n; t.beam.count = P.bmn.d; t.beam.recs = P.bmrec.d;
     if (P.bmtok.d) t.beam.tok = P.bmtok.d + t0 * set.beam_n;
     if (set.fused()) { t.beam.fused = true; t.beam.fu = lm::Fusion{s.sh->lms->dev[(size_t)set.lm], set.lm_alpha, set.lm_beta}; t.beam.lms = P.bmlm.d; }
+    if (set.worded()) { t.beam.worded = true; t.beam.wc = vc::Constraint{s.sh->vocabs->dev[(size_t)set.beam_vocab], set.vocab_gamma}; t.beam.vocs = P.bmvc.d; }
     t.cand.k = cand_k;
     if (cand_k > 0) { t.cand.col = P.d_ccol + t0; t.cand.cands = P.d_cands + t0 * cand_k; }
     s.rec_tail(tail, s.sh->rec->core(), t);
@@ -1137,7 +1142,7 @@ void line_round_trip(rt_lane& s, Pipeline& P) {
   }
   // (and what the lexicons, the snap, the patterns, the keywords and the beams left, where the call has them)
   P.lexm.fetch(s.st); P.lexn.fetch(s.st); P.lexs.fetch(s.st); P.pat.fetch(s.st); P.kwh.fetch(s.st); P.kwn.fetch(s.st);
-  P.bmn.fetch(s.st); P.bmrec.fetch(s.st); P.bmtok.fetch(s.st); P.bmlm.fetch(s.st);
+  P.bmn.fetch(s.st); P.bmrec.fetch(s.st); P.bmtok.fetch(s.st); P.bmlm.fetch(s.st); P.bmvc.fetch(s.st);
   s.sync(); s.check_flags();
 }
 // ---- results (session.rs:94-105) ----------------------------------------------------
@@ -1220,6 +1225,7 @@ void results(const rt_session& s, const Pipeline& P, rt_results& res) {
       R.beam_n = N; R.bm_count.assign((size_t)nb, 0); R.bm_recs.assign((size_t)nb * N, bm::Beam{0.0f, 0});
       R.bm_tokens.assign((size_t)nb * N, std::vector<int32_t>()); R.bm_text.assign((size_t)nb * N, std::string());
       if (P.bmlm.h) R.bm_lm.assign((size_t)nb * N, lm::BeamLm{0.0f, 0.0f});
+      if (P.bmvc.h) R.bm_vocab.assign((size_t)nb * N, vc::BeamVocab{0, 0.0f});
       for (int k = 0; k < nb; k++) {
         const int li = p.first_line + k;
         const long long T = P.tok_off[li + 1] - P.tok_off[li];
@@ -1229,6 +1235,7 @@ void results(const rt_session& s, const Pipeline& P, rt_results& res) {
           b = P.bmrec.h[(size_t)li * N + q];
           b.n_tokens = (int32_t)std::min<long long>(std::max(b.n_tokens, 0), T);
           if (P.bmlm.h) R.bm_lm[(size_t)k * N + q] = P.bmlm.h[(size_t)li * N + q];
+          if (P.bmvc.h) R.bm_vocab[(size_t)k * N + q] = P.bmvc.h[(size_t)li * N + q];
           const int* tk = P.bmtok.h + P.tok_off[li] * N + q * T;
           R.bm_tokens[(size_t)k * N + q].assign(tk, tk + b.n_tokens);
           std::string& t = R.bm_text[(size_t)k * N + q];

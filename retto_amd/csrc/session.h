@@ -67,6 +67,9 @@ struct rt_results {
     std::vector<std::string> bm_text;
     // rec language model (ctc_lm.h; rt_set_rec_beam_lm): per record slot the hypothesis' lm and fused score; empty when fusion was off
     std::vector<rt::lm::BeamLm> bm_lm;
+    // rec vocabulary (ctc_vocab.h; rt_set_rec_beam_vocab): per record slot the hypothesis' closed count and closing score; empty
+    // when no vocabulary was attached
+    std::vector<rt::vc::BeamVocab> bm_vocab;
     // rec windows (rec_windows.h; rt_set_rec_windows): per line the number of units it was read in, 1 for a whole line
     std::vector<int32_t> rec_units;
     std::string json[3];
@@ -93,11 +96,14 @@ struct LaneWorker {
 // What a pipeline call reads of the session's settings, as they were when the call was submitted: the default options of every
 // line (rt_set_rec_charset / _lexicon / _pattern / _keywords, rec_line_opts.h), the det tiles (rt_set_det_tiles, det_tiles.h; 0 = off)
 // the rec beam (rt_set_rec_beam, ctc_beam.h; beam_b = 0: off), the rec windows (rt_set_rec_windows, rec_windows.h; 0 = off) and
-// the beam's language model (rt_set_rec_beam_lm, ctc_lm.h; lm = -1: off, and without effect while beam_b = 0)
+// the beam's language model (rt_set_rec_beam_lm, ctc_lm.h; lm = -1: off, and without effect while beam_b = 0) and its word list
+// (rt_set_rec_beam_vocab, ctc_vocab.h; beam_vocab = -1: off, likewise)
 struct CallSettings {
   rt::RecLineOpts rec; int det_tile = 0, det_overlap = 0, beam_b = 0, beam_n = 0, rec_window = 0, rec_overlap = 0;
   int lm = -1; float lm_alpha = 0.0f, lm_beta = 0.0f;
+  int beam_vocab = -1; float vocab_gamma = 0.0f;
   bool fused() const { return beam_b > 0 && lm >= 0; }
+  bool worded() const { return beam_b > 0 && beam_vocab >= 0; }
 };
 
 // One pipeline call over some pages: what rt_lane::run_pages runs, whoever asked for it (rt_run_batch, rt_submit_batch,
@@ -254,6 +260,17 @@ struct rt_lms {
   ~rt_lms();
 };
 
+// The session's rec vocabularies (ctc_vocab.h), shared with the helper lanes.  Vocabulary k (0-based, rt_vocab_create's handle) is
+// host[k], whose four tables sit on the device as dev[k], uploaded once at creation and kept until the session goes.  Only
+// changed while no ticket is in flight (rt_vocab_create is a guarded call), with blocking copies.
+struct rt_vocabs {
+  std::vector<std::unique_ptr<rt::vc::Vocab>> host;
+  std::vector<rt::vc::View> dev;
+  // the vocabulary's tables onto the current device; returns its handle.  Whatever throws leaves the store as it was.
+  int add(rt::vc::Vocab m);
+  ~rt_vocabs();
+};
+
 // internal to the library (never accepted from a caller): pages already in HBM, det map overrides still host pointers
 #define RT_MEM_STAGED_MAPS_HOST 3
 
@@ -338,6 +355,9 @@ struct rt_lane {
     struct Beam {
       int b = 0, n = 0; int* count = nullptr; rt::bm::Beam* recs = nullptr; int* tok = nullptr;
       bool fused = false; rt::lm::Fusion fu{}; rt::lm::BeamLm* lms = nullptr;
+      // worded: the word-list constraint (ctc_vocab.h) with wc, whose tables are on the device, and the records' closed count /
+      // closing score [slot][n]
+      bool worded = false; rt::vc::Constraint wc{}; rt::vc::BeamVocab* vocs = nullptr;
     } beam;
     // rec_return_candidates = k > 0 (ctc_candidates.h): the kept tokens' time steps and [k] candidates
     struct Candidates { int k = 0; int* col = nullptr; rt::cc::Cand* cands = nullptr; } cand;
@@ -394,6 +414,7 @@ struct rt_session : rt_lane {
   std::unique_ptr<rt_patterns> patterns;
   std::unique_ptr<rt_keywords> keywords;
   std::unique_ptr<rt_lms> lms;
+  std::unique_ptr<rt_vocabs> vocabs;
   rt::RecLineOpts rec_counts() const {
     return {(int)charsets->ids.size(), (int)lexicons->host.size(), (int)patterns->host.size(), (int)keywords->host.size()};
   }
@@ -409,10 +430,13 @@ struct rt_session : rt_lane {
   // rt_set_rec_beam_lm (ctc_lm.h): the beam search of the calls that follow ranks by total + (alpha * lm + beta * len) under
   // model beam_lm; -1 = off.  Without effect while beam_b = 0
   int beam_lm = -1; float lm_alpha = 0.0f, lm_beta = 0.0f;
+  // rt_set_rec_beam_vocab (ctc_vocab.h): the beam search of the calls that follow charges every word of a hypothesis that is not
+  // in vocabulary beam_vocab with vocab_gamma; -1 = off.  Without effect while beam_b = 0
+  int beam_vocab = -1; float vocab_gamma = 0.0f;
   // rt_set_rec_windows (rec_windows.h): lines at least 8 columns wider than rec_window are read as overlapping windows whose
   // trusted time steps are stitched into the line's rows; 0 = off
   int rec_window = 0, rec_overlap = 0;
-  CallSettings settings() const { return {rec_default, det_tile, det_overlap, beam_b, beam_n, rec_window, rec_overlap, beam_lm, lm_alpha, lm_beta}; }
+  CallSettings settings() const { return {rec_default, det_tile, det_overlap, beam_b, beam_n, rec_window, rec_overlap, beam_lm, lm_alpha, lm_beta, beam_vocab, vocab_gamma}; }
   std::string last_error;
   // rt_charset_create: compiles the set (rt::compile_charset), stores it and returns its id
   int charset_create(const char* utf8, size_t len, const int32_t* ids, int n_ids);
@@ -422,6 +446,8 @@ struct rt_session : rt_lane {
   int keywords_create(const char* utf8, size_t len, const int32_t* ids, const int32_t* entry_lens, int n_id_entries, float min_score);
   // rt_lm_create: compiles the ARPA text (rt::lm::compile_arpa over the dictionary), stores the model and returns its handle
   int lm_create(const char* arpa, size_t len, float oov_log10);
+  // rt_vocab_create: compiles the words (rt::compile_vocab over the dictionary), stores the vocabulary and returns its handle
+  int vocab_create(const char* utf8, size_t len, const int32_t* ids, const int32_t* word_lens, int n_id_words, int flags);
   // rt_pattern_create: compiles the pattern (rt::pt::compile), stores it and returns its id
   int pattern_create(const char* utf8, size_t len);
   // rt_lexicon_set_snap: the lexicon's min_posterior (ctc_lexicon_align.h), on the host and in the device table
@@ -496,4 +522,14 @@ std::vector<uint32_t> compile_charset(const std::vector<std::string>& dict, cons
 // [1, dict.size()), an empty id entry, an entry longer than lx::MAX_LEN, or no entry at all; RT_ERR_CAPACITY past lx::MAX_ENTRIES.
 void compile_lexicon(const std::vector<std::string>& dict, const char* utf8, size_t len, const int32_t* ids,
                      const int32_t* entry_lens, int n_id_entries, std::vector<int32_t>& ids_out, std::vector<int32_t>& lens_out);
+// A vocabulary's words (ctc_vocab.h) in their id form: the lines of utf8 [len], split, trimmed and mapped as compile_lexicon maps
+// them -- with flags & vc::CASE_VARIANTS each followed by the word with its first ASCII letter upper-cased and the word with all
+// of them upper-cased, a variant with a code point the dictionary lacks being left out and counted -- then n_id_words words of
+// word_lens[i] ids each.  A word already there is not added again.  Throws RT_ERR_UTF8 for malformed text; RT_ERR_INVALID, naming
+// the word, for a code point that matches no entry ("U+XXXX"), the blank or an id outside [1, dict.size()), an empty or over-long
+// word, no word at all, unknown flag bits; RT_ERR_CAPACITY past vc::MAX_WORDS.  The second form also compiles it (vc::compile).
+void compile_vocab(const std::vector<std::string>& dict, const char* utf8, size_t len, const int32_t* ids, const int32_t* word_lens,
+                   int n_id_words, int flags, vc::Ids& out, int* variants_dropped);
+vc::Vocab compile_vocab(const std::vector<std::string>& dict, const char* utf8, size_t len, const int32_t* ids, const int32_t* word_lens,
+                        int n_id_words, int flags, vc::Ids& f);
 }
