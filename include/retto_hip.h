@@ -298,6 +298,46 @@ RT_API int rt_results_rec_windows(const rt_results* r, int page, int line);
 RT_API int rt_debug_rec_windows(rt_session* s, const float* nchw, int n, const int* widths, int32_t* unit_idx_out,
                                 float* unit_prob_out, float* unit_z5_out, int32_t* line_idx_out, float* line_prob_out,
                                 float* line_z5_out);
+/* Rec flip (retto_amd/csrc/rec_flip.h states the rule): lines the angle classifier is unsure of are read both ways up, and the
+ * better reading is kept.  Whether a line is upside down is otherwise decided by the small classifier and the fixed cls_thresh
+ * alone: a line labelled 180 at score 0.7 is not rotated, a line wrongly labelled 0 stays upside down, and rt_run_regions*
+ * callers hand in quads in any corner order -- and an upside-down line is garbage for every rec option.  With cls_below > 0 a
+ * line whose classifier score (rt_results_cls_scores) is below cls_below (fp32 <) is run through the recogniser as it is (view
+ * 0) and rotated by 180 degrees (view 1: the rotated crop through the same resize_norm at the same width), both in the one pass
+ * of its rec launch group; each view gets the greedy CTC score (kept probabilities summed in step order over the kept count),
+ * and view 1 is taken iff it kept a token and view 0 kept none or score1 > score0 (a tie or a NaN keeps view 0).  The chosen
+ * view's per-step rows become the line's rows by copy, so the greedy decode, charsets, lexicons and snap, patterns, keywords,
+ * beams, word boxes, candidates and windows run on the chosen reading; word boxes and keyword quads take (classifier rotated)
+ * XOR (view 1 taken) as their rotation.  rt_results_cls_labels / _cls_scores stay the classifier's own outputs.
+ * cls_below = 0: off (the default); any value above 1 reads every line both ways; NaN, a negative value or an infinity:
+ * RT_ERR_INVALID naming the parameter.  The setting holds for the pipeline calls that follow on every lane (rt_submit_* takes it
+ * as it is at the call), rt_run_regions* and the encoded entry points included; rt_rec, rt_rec_ragged and rt_ctc_decode never
+ * flip; fails like every other call while tickets are in flight.
+ * Cost: a both-ways line costs the rec network twice (it is charged twice in its launch group's pixel budget), plus two small
+ * copy kernels per group with such a line.  With 0 < cls_below <= 1 every call SYNCS ITS LANE ONCE MORE, between the classifier
+ * and the rec plan, to bring one float per line to the host; above 1 there is no extra sync.  A group without a both-ways line,
+ * and every call with flip off, launch and allocate nothing new.
+ * Not supported: a per-region flag, 90 / 270 degree views, switching the classifier off, a choice by anything but the greedy
+ * score.  What flipping does to accuracy with trained PP-OCRv4 weights has NOT been measured (the weights here are synthetic). */
+RT_API int rt_set_rec_flip(rt_session* s, float cls_below);
+/* the setting (optional); RT_ERR_INVALID for a NULL session */
+RT_API int rt_rec_flip(const rt_session* s, float* cls_below);
+/* The rule of the choice, GPU-free and sessionless: 1 when view 1 is taken given the two views' kept tokens and greedy scores */
+RT_API int rt_rec_flip_choose(int ntok0, float score0, int ntok1, float score1);
+/* line `line` of page `page`: 0 when it was read one way or is out of range (the scores are then untouched), 1 when it was read
+ * both ways and view 0 was kept, 2 when view 1 was taken; score0 / score1 (each optional): the views' greedy scores (NaN for a
+ * view that kept no token) */
+RT_API int rt_results_rec_flip(const rt_results* r, int page, int line, float* score0, float* score1);
+/* n RGB8 crops packed back to back in host memory (crop i is hw[2 i] rows of hw[2 i + 1] pixels) run as ONE rec group through the
+ * pipeline's own rotate, resize_norm, network, score and select functions under the session's rec windows, every line at the
+ * padded width of max_wh_ratio with T time steps.  both[i] != 0: line i is read both ways.  The views are the n lines' view 0 in
+ * line order, then the flagged lines' view 1 in line order.  Every output is optional: per view its rows (view_idx_out /
+ * view_prob_out [views][T], view_z5_out [views][T][120]), kept tokens and greedy score ([views]); taken_out [n]: 1 where view 1 was taken; the lines' final
+ * rows idx_out / prob_out [n][T] and z5_out [n][T][120].  NULL or bad arguments (n <= 0, an empty crop, a ratio that is not
+ * positive and finite): RT_ERR_INVALID before any device work. */
+RT_API int rt_debug_rec_flip(rt_session* s, const uint8_t* crops, const int32_t* hw, int n, const uint8_t* both, float max_wh_ratio,
+                             int32_t* view_idx_out, float* view_prob_out, float* view_z5_out, int32_t* view_ntok_out,
+                             float* view_score_out, int32_t* taken_out, int32_t* idx_out, float* prob_out, float* z5_out);
 /* The pipeline over regions the caller already knows (form fields, subtitles, corrected boxes, another detector's boxes):
  * quads[i] = n_quads[i] x 8 floats in host memory, TL, TR, BR, BL of each region in original-page coordinates; mem
  * (RT_MEM_HOST or RT_MEM_DEVICE) says where the pages live.  Every coordinate is clamped to [0, ori - 1] (no rounding); line k

@@ -206,6 +206,13 @@ class BeamHypothesis:   # rt_beam, with its tokens and text
 
 
 @dataclass
+class RecFlip:   # rt_results_rec_flip
+    outcome: int     # 1: the line was read both ways up and view 0 (the crop as the classifier left it) was kept; 2: view 1 taken
+    score0: float    # the views' greedy CTC scores; NaN for a view that kept no token
+    score1: float
+
+
+@dataclass
 class RecProcessorSingleResult:
     text: str
     score: float
@@ -234,6 +241,9 @@ class RecProcessorSingleResult:
     beams: Optional[List["BeamHypothesis"]] = None
     # rec windows (set_rec_windows): the number of units the line was read in, 1 for a whole line (retto_amd/csrc/rec_windows.h)
     windows: int = 1
+    # rec flip (set_rec_flip): None when the line was read one way, else the outcome and the two views' scores
+    # (retto_amd/csrc/rec_flip.h)
+    flip: Optional["RecFlip"] = None
 
 
 @dataclass
@@ -719,8 +729,13 @@ class RettoSession:
             rec.append(RecProcessorSingleResult(lib.rt_results_rec_text(r, page, k).decode("utf-8"), float(rs[k]), toks, words,
                                                 cands, cols, matches, snapped, self._pattern(r, page, k),
                                                 self._keywords(r, page, k), self._beams(r, page, k, beam_on),
-                                                int(lib.rt_results_rec_windows(r, page, k))))
+                                                int(lib.rt_results_rec_windows(r, page, k)), self._flip(r, page, k)))
         return RettoWorkerResult(det, cls, rec)
+
+    def _flip(self, r, page: int, k: int) -> Optional[RecFlip]:
+        s0, s1 = C.c_float(), C.c_float()
+        o = self._hd.lib.rt_results_rec_flip(r, page, k, C.byref(s0), C.byref(s1))
+        return RecFlip(int(o), s0.value, s1.value) if o else None
 
     def _dictionary(self) -> List[str]:
         if getattr(self, "_dict", None) is None:
@@ -952,6 +967,53 @@ class RettoSession:
             units.append(us)
             stitched.append((l_idx[lo:lo + p["T"]].copy(), l_prob[lo:lo + p["T"]].copy(), l_z5[lo:lo + p["T"]].copy())); lo += p["T"]
         return units, stitched, plans
+
+    # -- rec flip ---------------------------------------------------------------------------
+    def set_rec_flip(self, cls_below: float) -> None:
+        """rt_set_rec_flip: lines whose classifier score is below ``cls_below`` are read both ways up and the reading with the
+        better greedy CTC score is kept (retto_amd/csrc/rec_flip.h); 0 = off, the default; above 1 = every line.  A both-ways
+        line costs the rec network twice; with 0 < cls_below <= 1 every call syncs once more, for the classifier scores.  Holds
+        for the pipeline calls that follow.  The effect on accuracy with trained weights has not been measured."""
+        _check(self._hd.lib.rt_set_rec_flip(self._hd.h, float(cls_below)), self._hd.h)
+
+    @property
+    def rec_flip(self) -> float:
+        """rt_rec_flip: cls_below as set; 0 = off."""
+        v = C.c_float()
+        _check(self._hd.lib.rt_rec_flip(self._hd.h, C.byref(v)), self._hd.h)
+        return v.value
+
+    def debug_rec_flip(self, crops: Sequence[np.ndarray], both: Sequence[int], max_wh_ratio: float) -> dict:
+        """rt_debug_rec_flip: the crops ([h, w, 3] uint8 each) as ONE rec group through the pipeline's own rotate, resize_norm,
+        network, score and select under the session's rec windows, every line at the padded width of ``max_wh_ratio``; both[i]:
+        line i is read both ways.  Returns a dict: view_idx / view_prob [views, T] and view_z5 [views, T, 120] (the lines' view 0,
+        then the flagged lines' view 1, in line order), view_ntok / view_score [views], view1 (line -> its view-1 index), taken [n], and the lines'
+        final rows idx / prob [n, T] and z5 [n, T, 120]."""
+        lib = _lib.load()
+        arrs = [np.ascontiguousarray(a, np.uint8) for a in crops]
+        for a in arrs:
+            if a.ndim != 3 or a.shape[2] != 3:
+                raise ValueError("debug_rec_flip: every crop is [h, w, 3]")
+        n = len(arrs)
+        flags = np.array([1 if b else 0 for b in both], np.uint8)
+        if len(flags) != n:
+            raise ValueError("debug_rec_flip: one flag per crop")
+        hw = np.array([[a.shape[0], a.shape[1]] for a in arrs], np.int32).reshape(-1)
+        flat = np.concatenate([a.ravel() for a in arrs]) if n else np.zeros(0, np.uint8)
+        rh, rw = self.config.rec_processor_config.image_shape[1:3]
+        W = int(lib.rt_resize_norm_width(int(rh), int(rw), float(max_wh_ratio)))
+        T = rec_window_plan(W, 0, 0)["T"]
+        nv = n + int(flags.sum())
+        out = {"view_idx": np.empty((nv, T), np.int32), "view_prob": np.empty((nv, T), np.float32),
+               "view_z5": np.empty((nv, T, 120), np.float32),
+               "view_ntok": np.empty(nv, np.int32), "view_score": np.empty(nv, np.float32), "taken": np.empty(n, np.int32),
+               "idx": np.empty((n, T), np.int32), "prob": np.empty((n, T), np.float32), "z5": np.empty((n, T, 120), np.float32)}
+        _check(lib.rt_debug_rec_flip(self._hd.h, flat.ctypes.data, hw.ctypes.data, n, flags.ctypes.data, float(max_wh_ratio),
+                                     *[out[k].ctypes.data for k in ("view_idx", "view_prob", "view_z5", "view_ntok", "view_score", "taken",
+                                                                    "idx", "prob", "z5")]), self._hd.h)
+        out["view1"] = {int(i): n + j for j, i in enumerate(np.flatnonzero(flags))}
+        out["W"], out["T"] = W, T
+        return out
 
     # -- rec charsets -----------------------------------------------------------------------
     def create_charset(self, text: str = "", ids: Sequence[int] = ()) -> int:

@@ -135,6 +135,7 @@ EXPORTS = [
     "rt_debug_vocab_compile", "rt_debug_vocab_walk", "rt_debug_ctc_beam_vocab", "rt_debug_ctc_beam_vocab_host",
     "rt_set_det_tiles", "rt_det_tiles", "rt_det_tile_plan", "rt_debug_det_tiles", "rt_debug_arena_high_water", "rt_bench_memcpy_d2d",
     "rt_set_rec_windows", "rt_rec_windows", "rt_rec_window_plan", "rt_results_rec_windows", "rt_debug_rec_windows",
+    "rt_set_rec_flip", "rt_rec_flip", "rt_rec_flip_choose", "rt_results_rec_flip", "rt_debug_rec_flip",
 ]
 
 STAGE_CALLBACK = C.CFUNCTYPE(None, C.c_void_p, C.c_int, C.c_int, C.c_char_p)  # rt_stage_callback
@@ -417,5 +418,10 @@ def load():
     lib.rt_results_rec_windows.argtypes = [C.c_void_p, C.c_int, C.c_int]
     lib.rt_debug_rec_windows.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                          C.c_void_p, C.c_void_p]
+    lib.rt_set_rec_flip.argtypes = [C.c_void_p, C.c_float]
+    lib.rt_rec_flip.argtypes = [C.c_void_p, P(C.c_float)]
+    lib.rt_rec_flip_choose.argtypes = [C.c_int, C.c_float, C.c_int, C.c_float]
+    lib.rt_results_rec_flip.argtypes = [C.c_void_p, C.c_int, C.c_int, P(C.c_float), P(C.c_float)]
+    lib.rt_debug_rec_flip.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_float] + [C.c_void_p] * 9
     _lib = lib
     return lib

@@ -82,6 +82,10 @@ def build_parser() -> argparse.ArgumentParser:
                     help="with --rec-vocab: the cost of a word that is not in the list, in nats (default 4.0)")
     ap.add_argument("--rec-vocab-case-variants", action="store_true",
                     help="with --rec-vocab: every word also Capitalised and in UPPER CASE")
+    ap.add_argument("--rec-flip", type=float, default=0.0, metavar="CLS_BELOW",
+                    help="read lines whose classifier score is below CLS_BELOW both ways up and keep the reading with the better "
+                         "greedy CTC score (such a line costs the rec network twice; the effect on accuracy is not measured); "
+                         "above 1 = every line; 0 = off")
     return ap
 
 
@@ -133,6 +137,8 @@ def main(argv=None) -> int:
         session.set_det_tiles(a.det_tile, a.det_tile_overlap)
     if a.rec_window:
         session.set_rec_windows(a.rec_window, a.rec_window_overlap)
+    if a.rec_flip:
+        session.set_rec_flip(a.rec_flip)
     if a.rec_charset is not None:
         session.set_rec_charset(session.create_charset(a.rec_charset))
     if a.rec_lexicon is not None:

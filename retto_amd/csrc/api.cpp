@@ -457,6 +457,26 @@ int rt_rec_windows(const rt_session* s, int* window, int* overlap) {
   if (overlap) *overlap = s->rec_overlap;
   return RT_OK;
 }
+int rt_set_rec_flip(rt_session* s, float cls_below) {
+  RT_REQUIRE(s, s, "rt_set_rec_flip: null session");
+  return guarded(s, [&] {
+    if (const char* why = rf::check_param(cls_below)) throw RtError(RT_ERR_INVALID, std::string("rt_set_rec_flip: ") + why);
+    s->rec_flip_below = cls_below;   // (the helper lanes get it with every call: CallSettings)
+  });
+}
+int rt_rec_flip(const rt_session* s, float* cls_below) {
+  if (!s) return RT_ERR_INVALID;
+  if (cls_below) *cls_below = s->rec_flip_below;
+  return RT_OK;
+}
+int rt_rec_flip_choose(int ntok0, float score0, int ntok1, float score1) { return rf::choose(ntok0, score0, ntok1, score1); }
+int rt_results_rec_flip(const rt_results* r, int page, int line, float* score0, float* score1) {
+  const rt_results::Page* p = r && page >= 0 && (size_t)page < r->pages.size() ? &r->pages[(size_t)page] : nullptr;
+  if (!p || line < 0 || (size_t)line >= p->flip_outcome.size() || p->flip_outcome[(size_t)line] == 0) return 0;
+  if (score0) *score0 = p->flip_scores[2 * (size_t)line];
+  if (score1) *score1 = p->flip_scores[2 * (size_t)line + 1];
+  return p->flip_outcome[(size_t)line];
+}
 int rt_rec_window_plan(int L, int window, int overlap, int32_t* origin, int32_t* width, int32_t* bound, int cap, int* n, int* T) {
   return guarded(nullptr, [&] {
     if (const char* why = rw::check_params(window, overlap)) throw RtError(RT_ERR_INVALID, std::string("rt_rec_window_plan: ") + why);

@@ -1213,6 +1213,24 @@ RT_API int rt_debug_rec_windows(rt_session* s, const float* nchw, int n, const i
     s->debug_rec_windows(nchw, n, widths, unit_idx_out, unit_prob_out, unit_z5_out, line_idx_out, line_prob_out, line_z5_out);
   });
 }
+// n RGB8 crops as ONE rec group through the pipeline's own rotate, resize_norm, network, score and select, under the session's rec
+// windows (rt_session::debug_rec_flip), for tests/test_gpu_rec_flip.py.  Everything is checked before any device work.
+RT_API int rt_debug_rec_flip(rt_session* s, const uint8_t* crops, const int32_t* hw, int n, const uint8_t* both, float max_wh_ratio,
+                             int32_t* view_idx_out, float* view_prob_out, float* view_z5_out, int32_t* view_ntok_out,
+                             float* view_score_out, int32_t* taken_out, int32_t* idx_out, float* prob_out, float* z5_out) {
+  RT_REQUIRE(s && crops && hw && both && n > 0, s, "rt_debug_rec_flip: bad argument");
+  RT_REQUIRE(max_wh_ratio > 0.0f && max_wh_ratio - max_wh_ratio == 0.0f && max_wh_ratio <= 1024.0f, s,
+             "rt_debug_rec_flip: max_wh_ratio must be positive, finite and at most 1024");
+  for (int i = 0; i < n; i++)
+    RT_REQUIRE(hw[2 * i] >= 1 && hw[2 * i + 1] >= 1 && hw[2 * i] <= 16384 && hw[2 * i + 1] <= 16384, s,
+               "rt_debug_rec_flip: every crop must be 1 .. 16384 pixels either way");
+  return guarded(s, [&] {
+    rt_session::RecFlipOut out;
+    out.view_idx = view_idx_out; out.view_prob = view_prob_out; out.view_z5 = view_z5_out; out.view_ntok = view_ntok_out; out.view_score = view_score_out;
+    out.taken = taken_out; out.idx = idx_out; out.prob = prob_out; out.z5 = z5_out;
+    s->debug_rec_flip(crops, hw, n, both, max_wh_ratio, out);
+  });
+}
 // The main lane's arenas, for tools/bench_det_tiles.py: the largest pass so far of the call arena, the scratch arena (network
 // activations, rewound per launch group) and the DB post-processing workspace, in bytes.
 RT_API int rt_debug_arena_high_water(rt_session* s, long long* out3) {

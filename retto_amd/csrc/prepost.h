@@ -14,6 +14,7 @@
 #include "ctc_pattern.h"
 #include "det_tiles.h"
 #include "rec_windows.h"
+#include "rec_flip.h"
 
 namespace rt {
 namespace pp {
@@ -84,12 +85,13 @@ void ctc_decode(hipStream_t st, const int* idx, const float* prob, const ImgGeom
 
 // rt_config.rec_return_word_box: the words of n lines of one rec group (word_boxes.h), one wave64 per line.  idx: the group's
 // argmax rows; tokens / n_tokens: what ctc_decode wrote for the same lines; label / cls_score: the lines' cls results (the
-// rotate180 predicate of cls_post_rotate); raw_of_id: the session's class table.  Per line i: word count -> n_words[i], words
+// rotate180 predicate of cls_post_rotate); flip: the lines' rec flip outcomes (rec_flip.h: a taken view 1 inverts rot180), or
+// null; raw_of_id: the session's class table.  Per line i: word count -> n_words[i], words
 // -> words[tok_off ...] (a line has at most as many words as kept tokens); cols: scratch of the group's token count.
 struct WordLineDesc { long long tok_off; wb::WordGeom g; };   // tok_off: first argmax row of the line inside the group
 void word_boxes(hipStream_t st, const int* idx, const int* tokens, const int* n_tokens, const int* label, const float* cls_score,
-                float cls_thresh, const uint8_t* raw_of_id, const WordLineDesc* lines, int n, int* cols, int* n_words,
-                wb::Word* words);
+                float cls_thresh, const int* flip, const uint8_t* raw_of_id, const WordLineDesc* lines, int n, int* cols,
+                int* n_words, wb::Word* words);
 
 // rt_config.rec_return_candidates (ctc_candidates.h) over the n lines of one rec group; lines[i] = {first row, 1, T_i}, what
 // ctc_decode got.  kept_rows: one wave64 per line writes, at the line's row offset, the kept time steps -> cols and rank 0
@@ -180,6 +182,15 @@ void det_tile_stitch(hipStream_t st, const dt::TileDesc* tiles, int n, long long
 void rec_window_cut(hipStream_t st, const rw::UnitDesc* units, int n, int h, int max_w, const float* lines, float* unit);
 void rec_window_stitch(hipStream_t st, const rw::UnitDesc* units, int n, int max_rows, const int* unit_idx, const float* unit_prob,
                        const float* unit_z5, int* line_idx, float* line_prob, float* line_z5);
+
+// rec flip (rec_flip.h), one launch per rec group with a both-ways line each.  rotate: the n flagged crops (crops: device) as one
+// flat list of total_pix pixels, crop c from pool + src_off rotated by 180 degrees to flipped + dst_off.  select: per both-ways
+// line (lines: device, n of them, max_T the most time steps of one) the choice between its two views from ctc_decode's v_ntok /
+// v_score over the views, -> outcome[slot] (rf::KEPT_0 / TOOK_1) and scores[2 slot ...]; the chosen view's rows of v_idx /
+// v_prob -> idx / prob, and a taken view 1's z5 rows over the line's rows INSIDE v_z5 (or null), whose prefix the lines' z5 is.
+void rec_flip_rotate(hipStream_t st, const rf::FlipCrop* crops, int n, long long total_pix, const uint8_t* pool, uint8_t* flipped);
+void rec_flip_select(hipStream_t st, const rf::SelectDesc* lines, int n, int max_T, const int* v_ntok, const float* v_score,
+                     const int* v_idx, const float* v_prob, float* v_z5, int* idx, float* prob, int* outcome, float* scores);
 
 }  // namespace pp
 }  // namespace rt

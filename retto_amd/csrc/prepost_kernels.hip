@@ -312,7 +312,8 @@ void ctc_decode(hipStream_t st, const int* idx, const float* prob, const ImgGeom
 __global__ __launch_bounds__(64) void k_word_boxes(const int* __restrict__ idx, const int* __restrict__ tokens,
                                                    const int* __restrict__ n_tokens, const int* __restrict__ label,
                                                    const float* __restrict__ cls_score, float thresh,
-                                                   const u8* __restrict__ raw_of_id, const WordLineDesc* __restrict__ lines,
+                                                   const int* __restrict__ flip, const u8* __restrict__ raw_of_id,
+                                                   const WordLineDesc* __restrict__ lines,
                                                    int* __restrict__ cols, int* __restrict__ n_words, wb::Word* __restrict__ words) {
   const int line = blockIdx.x, lane = threadIdx.x;
   const WordLineDesc d = lines[line];
@@ -330,15 +331,16 @@ __global__ __launch_bounds__(64) void k_word_boxes(const int* __restrict__ idx, 
   __syncthreads();   // the columns other lanes wrote, for lane 0
   if (lane != 0) return;
   const int n = min(kept, n_tokens[line]);   // (equal: the same selection)
-  const int rot180 = (label[line] == 1 && cls_score[line] >= thresh) ? 1 : 0;
+  // (rec flip, rec_flip.h: a line whose view 1 was taken is the other way up than the classifier left it; flip null = off)
+  const int rot180 = rf::rot180(label[line] == 1 && cls_score[line] >= thresh, flip ? flip[line] : rf::ONE_WAY);
   n_words[line] = wb::line_words(raw_of_id, tokens + d.tok_off, col, n, d.g, rot180, words + d.tok_off);
 }
 void word_boxes(hipStream_t st, const int* idx, const int* tokens, const int* n_tokens, const int* label, const float* cls_score,
-                float cls_thresh, const uint8_t* raw_of_id, const WordLineDesc* lines, int n, int* cols, int* n_words,
-                wb::Word* words) {
+                float cls_thresh, const int* flip, const uint8_t* raw_of_id, const WordLineDesc* lines, int n, int* cols,
+                int* n_words, wb::Word* words) {
   if (n <= 0) return;
-  RT_LAUNCH(k_word_boxes, dim3(n), dim3(64), 0, st, idx, tokens, n_tokens, label, cls_score, cls_thresh, raw_of_id, lines, cols,
-            n_words, words);
+  RT_LAUNCH(k_word_boxes, dim3(n), dim3(64), 0, st, idx, tokens, n_tokens, label, cls_score, cls_thresh, flip, raw_of_id, lines,
+            cols, n_words, words);
 }
 
 // rt_config.rec_return_candidates (ctc_candidates.h).  One wave64 per line, the ballot / popcount-prefix compaction of
@@ -1471,6 +1473,65 @@ void rec_window_stitch(hipStream_t st, const rw::UnitDesc* units, int n, int max
   const long long want = ((long long)max_rows * 32 + 255) / 256;
   RT_LAUNCH(k_rec_window_stitch, dim3((unsigned)std::min<long long>(want, RW_MAX_BLOCKS_X), n), dim3(256), 0, st, units, unit_idx,
             unit_prob, reinterpret_cast<const float4*>(unit_z5), line_idx, line_prob, reinterpret_cast<float4*>(line_z5));
+}
+
+// ---- rec flip (rec_flip.h): pure data movement --------------------------------------------------------------------------
+// rotate: the flagged crops of a rec group as one flat list of pixels, the way k_warp_crops_flat walks its crops (their sizes
+// differ by orders of magnitude).  Thread g writes destination pixel p = g - pix_base of its crop from source pixel npix - 1 - p:
+// a byte permutation in whole pixels.  Consecutive threads write consecutive pixels and read consecutive pixels backwards, so a
+// wave's 192 bytes lie in the same cache lines either way.  Inside its buffers by the table: p < npix on both sides.
+__global__ __launch_bounds__(256) void k_rec_flip_rotate(const rf::FlipCrop* __restrict__ crops, int n, long long total,
+                                                         const u8* __restrict__ pool, u8* __restrict__ flipped) {
+  for (long long g = (long long)blockIdx.x * 256 + threadIdx.x; g < total; g += (long long)gridDim.x * 256) {
+    const rf::FlipCrop& c = crops[rf::find_crop(crops, n, g)];
+    const long long p = g - c.pix_base;
+    if (p < 0 || p >= c.npix) continue;   // (a table whose bases do not match its sizes writes nothing)
+    const u8* a = pool + c.src_off + rf::src_pixel(c.npix, p) * 3;
+    u8* q = flipped + c.dst_off + p * 3;
+    const u8 r = a[0], gg = a[1], b = a[2];
+    q[0] = r; q[1] = gg; q[2] = b;
+  }
+}
+void rec_flip_rotate(hipStream_t st, const rf::FlipCrop* crops, int n, long long total_pix, const uint8_t* pool, uint8_t* flipped) {
+  if (n <= 0 || total_pix <= 0) return;
+  const long long want = (total_pix + 255) / 256;
+  RT_LAUNCH(k_rec_flip_rotate, dim3((unsigned)std::min<long long>(want, WARP_FLAT_MAX_BLOCKS)), dim3(256), 0, st, crops, n, total_pix,
+            pool, flipped);
+}
+// select: blockIdx.y = both-ways line of the group.  Every thread reads the two views' (kept tokens, score) -- k_ctc_decode's
+// outputs over the views -- and applies rf::choose; the block's first thread writes the outcome and the two scores.  Then the
+// chosen view's T rows go to the line's rows, 32 lanes a row as k_rec_window_stitch: lanes 0..29 the row's 30 float4 of z5,
+// lane 30 its idx, lane 31 its prob.  z5 and v_z5 are ONE buffer (the lines' rows are the views' prefix, rec_flip.h): a kept
+// view 0 is in place and only a taken view 1 is moved, from rows behind the prefix, so no thread reads what another writes.
+__global__ __launch_bounds__(256) void k_rec_flip_select(const rf::SelectDesc* __restrict__ lines, const int* __restrict__ v_ntok,
+                                                         const float* __restrict__ v_score, const int* __restrict__ v_idx,
+                                                         const float* __restrict__ v_prob, const float4* v_z5, int* __restrict__ idx,
+                                                         float* __restrict__ prob, float4* z5, int* __restrict__ outcome,
+                                                         float* __restrict__ scores) {
+  const rf::SelectDesc d = lines[blockIdx.y];
+  const float s0 = v_score[d.v0], s1 = v_score[d.v1];
+  const int take = rf::choose(v_ntok[d.v0], s0, v_ntok[d.v1], s1);
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    outcome[d.slot] = take ? rf::TOOK_1 : rf::KEPT_0;
+    scores[2 * (long long)d.slot] = s0; scores[2 * (long long)d.slot + 1] = s1;
+  }
+  const long long src = take ? d.row1 : d.row0;
+  const long long total = (long long)d.T * 32;
+  for (long long v = (long long)blockIdx.x * 256 + threadIdx.x; v < total; v += (long long)gridDim.x * 256) {
+    const int t = (int)(v >> 5), lane = (int)(v & 31);
+    const long long s = src + t, o = d.out_row + t;
+    if (lane < rw::Z5_D / 4) { if (v_z5 && take) z5[o * (rw::Z5_D / 4) + lane] = v_z5[s * (rw::Z5_D / 4) + lane]; }
+    else if (lane == 30) idx[o] = v_idx[s];
+    else prob[o] = v_prob[s];
+  }
+}
+void rec_flip_select(hipStream_t st, const rf::SelectDesc* lines, int n, int max_T, const int* v_ntok, const float* v_score,
+                     const int* v_idx, const float* v_prob, float* v_z5, int* idx, float* prob, int* outcome, float* scores) {
+  if (n <= 0) return;
+  static_assert(rw::Z5_D / 4 == 30, "k_rec_flip_select gives a z5 row 30 of its 32 lanes");
+  const long long want = std::max<long long>(((long long)max_T * 32 + 255) / 256, 1);   // (T = 0: the outcome is still written)
+  RT_LAUNCH(k_rec_flip_select, dim3((unsigned)std::min<long long>(want, RW_MAX_BLOCKS_X), n), dim3(256), 0, st, lines, v_ntok, v_score,
+            v_idx, v_prob, reinterpret_cast<const float4*>(v_z5), idx, prob, reinterpret_cast<float4*>(v_z5), outcome, scores);
 }
 
 }  // namespace pp

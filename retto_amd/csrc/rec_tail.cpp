@@ -379,7 +379,7 @@ void rt_lane::rec_tail(const RecTailPlan& p, const SvtrCore& core, const RecTail
     pp::WordLineDesc* dw = scratch.alloc<pp::WordLineDesc>(t.n_lines);
     RT_HIP_CHECK(hipMemcpyAsync(dw, t.wb->h_lines, (size_t)t.n_lines * sizeof(pp::WordLineDesc), hipMemcpyHostToDevice, st));
     ProfScope ps(&prof, st, "word_boxes");
-    pp::word_boxes(st, t.idx, t.tok, t.ntok, t.wb->label, t.wb->cscore, sh->cfg.cls_thresh, sh->d_word_raw, dw, t.n_lines, t.wb->cols,
+    pp::word_boxes(st, t.idx, t.tok, t.ntok, t.wb->label, t.wb->cscore, sh->cfg.cls_thresh, t.wb->flip, sh->d_word_raw, dw, t.n_lines, t.wb->cols,
                    t.wb->n_words, t.wb->words);
   }
   if (!p.snap && p.has_lex()) ctc_lexicon(p, core, t);

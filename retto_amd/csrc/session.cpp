@@ -604,6 +604,9 @@ struct Pipeline {
   Mirror<lm::BeamLm> bmlm;
   // rec vocabulary (ctc_vocab.h; call.set.worded()): per record slot the closed count and the closing score; null otherwise
   Mirror<vc::BeamVocab> bmvc;
+  // rec flip (rec_flip.h; call.set.flip_cls_below > 0): per line whether it is read both ways (host; empty: no line of the call
+  // is), and then per line its outcome (zeroed: 0 = read one way) and the two views' scores
+  std::vector<uint8_t> both; Mirror<int> flipo; Mirror<float> flips;
 };
 
 // Launch groups: items [g0, end) where the group always takes its first item; with max_items > 0 it takes up to max_items items,
@@ -914,6 +917,25 @@ void cls_stage(rt_lane& s, Pipeline& P) {
     pp::cls_post_rotate(s.st, probs, drow, cn, s.sh->cfg.cls_thresh, P.d_refs, P.pool, P.plan.max_pix, P.d_meta.label, P.d_meta.cscore);
   }
 }
+// ---- rec flip (rec_flip.h): which lines are read both ways.  With 0 < cls_below <= 1 that takes the classifier scores: one copy
+// of NL floats and one lane sync, only then; above 1 every line is, without a sync.  A call without a both-ways line allocates nothing.
+void flip_plan(rt_lane& s, Pipeline& P) {
+  const float below = P.call.set.flip_cls_below;
+  if (!(below > 0.0f) || P.NL == 0) return;
+  bool any = false;
+  if (rf::every_line(below)) { P.both.assign((size_t)P.NL, 1); any = true; }
+  else {
+    float* h = s.pinned.alloc<float>((size_t)P.NL);
+    RT_HIP_CHECK(hipMemcpyAsync(h, P.d_meta.cscore, (size_t)P.NL * sizeof(float), hipMemcpyDeviceToHost, s.st));
+    s.sync();
+    P.both.resize((size_t)P.NL);
+    for (int l = 0; l < P.NL; l++) { P.both[(size_t)l] = rf::both_ways(h[l], below) ? 1 : 0; any = any || P.both[(size_t)l]; }
+  }
+  if (!any) { P.both.clear(); return; }
+  P.flipo.alloc(s, P.NLp); P.flips.alloc(s, (size_t)2 * P.NLp);
+  RT_HIP_CHECK(hipMemsetAsync(P.flipo.d, 0, (size_t)P.NLp * sizeof(int), s.st));
+  RT_HIP_CHECK(hipMemsetAsync(P.flips.d, 0, (size_t)2 * P.NLp * sizeof(float), s.st));
+}
 // ---- a10: rec plan: per page, order by h/w descending (stable), chunks of batch_num, running max_wh_ratio ----
 void rec_plan(rt_lane& s, Pipeline& P) {
   const int rh = s.sh->cfg.rec_image_shape[1], rw = s.sh->cfg.rec_image_shape[2];
@@ -1032,6 +1054,92 @@ void rec_group_net(rt_lane& s, const float* x, int rh, const int* W, int ln, int
   upload_levels(c, {&Lt});
   tap(u_idx, u_prob, u_z5, unit_rows);
 }
+// ---- ONE rec group with a both-ways line (rec_flip.h) ----------------------------------
+// lines / W / both: the group's ln lines as the rec plan left them (crop_off into pool) and their flags, at least one set.  The
+// group's tensor is the lines followed by the view-1 copies of the flagged lines: k_rec_flip_rotate writes their crops rotated
+// into a second pool region in scratch, resize_norm reads the pool for the lines and that region for the copies, and
+// rec_group_net runs ONCE over the views with idx / prob / z5 in scratch (rec windows apply to each view as to any line).
+// k_ctc_decode over the views' rows gives each its kept count and greedy score; the views' leading rows are the lines' view 0 in
+// the lines' own layout, so one block copy brings them to idx / prob and the z5 prefix is the lines' z5; k_rec_flip_select then
+// writes the flagged lines' outcome and scores at slot0 + k and copies a chosen view's rows over the line's.  Lt: the LINES'
+// token level, as RecModel::run would have left it.  taps (rt_debug_rec_flip): host arrays, each optional.
+struct RecFlipTaps { int32_t* view_idx = nullptr; float* view_prob = nullptr; float* view_z5 = nullptr; int32_t* view_ntok = nullptr; float* view_score = nullptr; };
+void rec_group_flip(rt_lane& s, const uint8_t* pool, const pp::LineDesc* lines, const int* W, const uint8_t* both, int ln, int slot0,
+                    int rh, int window, int overlap, int* idx, float* prob, const float** z5, Level& Lt, int* outcome, float* scores,
+                    const RecFlipTaps* taps = nullptr) {
+  int nf = 0;
+  for (int k = 0; k < ln; k++) nf += both[k] ? 1 : 0;
+  const int nv = ln + nf;
+  rf::FlipCrop* hc = s.pinned.alloc<rf::FlipCrop>((size_t)nf);
+  rf::SelectDesc* hs = s.pinned.alloc<rf::SelectDesc>((size_t)nf);
+  pp::LineDesc* hl = s.pinned.alloc<pp::LineDesc>((size_t)nv);
+  std::vector<int> Wv((size_t)nv);
+  std::vector<std::pair<int, int>> thw;
+  long long off = 0, rows = 0, fpix = 0;
+  int maxW = 0, maxWf = 0, maxT = 0;
+  for (int k = 0; k < ln; k++) {
+    hl[k] = lines[k]; hl[k].out_off = off * 4;
+    off += (long long)rh * W[k]; Wv[(size_t)k] = W[k]; maxW = std::max(maxW, W[k]);
+    const int T = RecNet::tokens_for_width(W[k]);
+    thw.push_back({1, T}); rows += T;
+  }
+  long long vrows = rows, row0 = 0;
+  for (int k = 0, f = 0; k < ln; k++) {
+    const int T = RecNet::tokens_for_width(W[k]);
+    if (both[k]) {
+      const long long npix = (long long)lines[k].h * lines[k].w;
+      if (npix <= 0) throw RtError(RT_ERR_BACKEND, "rec flip: an empty crop");
+      hc[f] = rf::FlipCrop{lines[k].crop_off, fpix * 3, fpix, npix};
+      pp::LineDesc& v = hl[ln + f];
+      v = lines[k]; v.crop_off = fpix * 3; v.out_off = off * 4;   // (the same thumbnail and padded width, read from the second region)
+      off += (long long)rh * W[k]; Wv[(size_t)(ln + f)] = W[k]; maxWf = std::max(maxWf, W[k]);
+      hs[f] = rf::SelectDesc{row0, vrows, row0, k, ln + f, T, slot0 + k};
+      fpix += npix; vrows += T; maxT = std::max(maxT, T); f++;
+    }
+    row0 += T;
+  }
+  rf::FlipCrop* dc = s.scratch.alloc<rf::FlipCrop>((size_t)nf);
+  rf::SelectDesc* ds = s.scratch.alloc<rf::SelectDesc>((size_t)nf);
+  pp::LineDesc* dl = s.scratch.alloc<pp::LineDesc>((size_t)nv);
+  RT_HIP_CHECK(hipMemcpyAsync(dc, hc, (size_t)nf * sizeof(rf::FlipCrop), hipMemcpyHostToDevice, s.st));
+  RT_HIP_CHECK(hipMemcpyAsync(ds, hs, (size_t)nf * sizeof(rf::SelectDesc), hipMemcpyHostToDevice, s.st));
+  RT_HIP_CHECK(hipMemcpyAsync(dl, hl, (size_t)nv * sizeof(pp::LineDesc), hipMemcpyHostToDevice, s.st));
+  uint8_t* flipped = s.scratch.alloc<uint8_t>((size_t)fpix * 3);
+  { ProfScope ps(&s.prof, s.st, "rec_flip_rotate");
+    pp::rec_flip_rotate(s.st, dc, nf, fpix, pool, flipped); }
+  float* x = s.scratch.alloc<float>((size_t)off * 4);
+  { ProfScope ps(&s.prof, s.st, "resize_norm");
+    pp::resize_norm(s.st, dl, ln, rh, maxW, pool, 0, x, s.d_flags); }
+  { ProfScope ps(&s.prof, s.st, "resize_norm");
+    pp::resize_norm(s.st, dl + ln, nf, rh, maxWf, flipped, 0, x, s.d_flags); }
+  int* v_idx = s.scratch.alloc<int>((size_t)std::max<long long>(vrows, 1)); float* v_prob = s.scratch.alloc<float>((size_t)std::max<long long>(vrows, 1));
+  const float* v_z5 = nullptr;
+  Level Lv;
+  rec_group_net(s, x, rh, Wv.data(), nv, window, overlap, v_idx, v_prob, z5 ? &v_z5 : nullptr, Lv);
+  if (Lv.total != vrows) throw RtError(RT_ERR_SHAPE, "token count mismatch");
+  // the views' (kept tokens, greedy score): k_ctc_decode itself, its tokens into scratch
+  int* v_tok = s.scratch.alloc<int>((size_t)std::max<long long>(vrows, 1));
+  int* v_ntok = s.scratch.alloc<int>((size_t)nv); float* v_score = s.scratch.alloc<float>((size_t)nv);
+  { ProfScope ps(&s.prof, s.st, "rec_flip_score");
+    pp::ctc_decode(s.st, v_idx, v_prob, Lv.d, nv, v_tok, v_ntok, v_score); }
+  if (taps && vrows > 0) {   // (the views' rows as the network left them: before the select moves a taken view 1 into the z5 prefix)
+    if (taps->view_idx) RT_HIP_CHECK(hipMemcpyAsync(taps->view_idx, v_idx, (size_t)vrows * 4, hipMemcpyDeviceToHost, s.st));
+    if (taps->view_prob) RT_HIP_CHECK(hipMemcpyAsync(taps->view_prob, v_prob, (size_t)vrows * 4, hipMemcpyDeviceToHost, s.st));
+    if (taps->view_z5 && v_z5) RT_HIP_CHECK(hipMemcpyAsync(taps->view_z5, v_z5, (size_t)vrows * rw::Z5_D * 4, hipMemcpyDeviceToHost, s.st));
+  }
+  if (taps && taps->view_ntok) RT_HIP_CHECK(hipMemcpyAsync(taps->view_ntok, v_ntok, (size_t)nv * 4, hipMemcpyDeviceToHost, s.st));
+  if (taps && taps->view_score) RT_HIP_CHECK(hipMemcpyAsync(taps->view_score, v_score, (size_t)nv * 4, hipMemcpyDeviceToHost, s.st));
+  if (rows > 0) {
+    RT_HIP_CHECK(hipMemcpyAsync(idx, v_idx, (size_t)rows * sizeof(int), hipMemcpyDeviceToDevice, s.st));
+    RT_HIP_CHECK(hipMemcpyAsync(prob, v_prob, (size_t)rows * sizeof(float), hipMemcpyDeviceToDevice, s.st));
+  }
+  { ProfScope ps(&s.prof, s.st, "rec_flip_select");
+    pp::rec_flip_select(s.st, ds, nf, maxT, v_ntok, v_score, v_idx, v_prob, const_cast<float*>(v_z5), idx, prob, outcome, scores); }
+  if (z5) *z5 = v_z5;
+  Lt = make_level(thw);
+  RunCtx c = s.ctx(&s.scratch);
+  upload_levels(c, {&Lt});
+}
 // ---- a11 + a12: rec network + CTC decode in launch groups (+ word boxes) --------------
 void rec_groups(rt_lane& s, Pipeline& P) {
   const CallSettings& set = P.call.set;
@@ -1061,23 +1169,31 @@ void rec_groups(rt_lane& s, Pipeline& P) {
   if (set.worded()) P.bmvc.alloc(s, (size_t)P.NLp * set.beam_n);
   static const long long REC_GROUP_PX = getenv("RT_REC_GROUP_PX") ? atoll(getenv("RT_REC_GROUP_PX")) : (long long)24000000;  // measured sweet spot (profiles/README.md)
   for (int l0 = 0; l0 < P.NL;) {
-    // (a windowed line is charged with its units' pixels, rec_windows.h: what the network is run on)
-    const int l1 = group_end(l0, P.NL, 0, REC_GROUP_PX, [&](int l) { return (long long)rh * rw::unit_columns(P.line_W[l], set.rec_window, set.rec_overlap); });
+    // (a windowed line is charged with its units' pixels, rec_windows.h: what the network is run on; a both-ways line, rec_flip.h,
+    //  twice: both views run in the group's one pass)
+    const int l1 = group_end(l0, P.NL, 0, REC_GROUP_PX, [&](int l) {
+      return (!P.both.empty() && P.both[(size_t)l] ? 2 : 1) * (long long)rh * rw::unit_columns(P.line_W[l], set.rec_window, set.rec_overlap);
+    });
     const int ln = l1 - l0;
+    // a group without a both-ways line takes the path it took before rec flip existed: nothing new is launched or allocated
+    const bool flip = !P.both.empty() && std::any_of(P.both.begin() + l0, P.both.begin() + l1, [](uint8_t b) { return b != 0; });
     s.scratch.rewind();
-    pp::LineDesc* hl = s.pinned.alloc<pp::LineDesc>(ln);
-    long long off = 0; int maxW = 0;
-    for (int k = 0; k < ln; k++) {
-      hl[k] = P.lines[l0 + k];
-      hl[k].out_off = off * 4;
-      off += (long long)rh * P.line_W[l0 + k];
-      maxW = std::max(maxW, P.line_W[l0 + k]);
+    float* x = nullptr;
+    if (!flip) {
+      pp::LineDesc* hl = s.pinned.alloc<pp::LineDesc>(ln);
+      long long off = 0; int maxW = 0;
+      for (int k = 0; k < ln; k++) {
+        hl[k] = P.lines[l0 + k];
+        hl[k].out_off = off * 4;
+        off += (long long)rh * P.line_W[l0 + k];
+        maxW = std::max(maxW, P.line_W[l0 + k]);
+      }
+      pp::LineDesc* dl = s.scratch.alloc<pp::LineDesc>(ln);
+      RT_HIP_CHECK(hipMemcpyAsync(dl, hl, (size_t)ln * sizeof(pp::LineDesc), hipMemcpyHostToDevice, s.st));
+      x = s.scratch.alloc<float>((size_t)off * 4);
+      { ProfScope ps(&s.prof, s.st, "resize_norm");
+        pp::resize_norm(s.st, dl, ln, rh, maxW, P.pool, 0, x, s.d_flags); }
     }
-    pp::LineDesc* dl = s.scratch.alloc<pp::LineDesc>(ln);
-    RT_HIP_CHECK(hipMemcpyAsync(dl, hl, (size_t)ln * sizeof(pp::LineDesc), hipMemcpyHostToDevice, s.st));
-    float* x = s.scratch.alloc<float>((size_t)off * 4);
-    { ProfScope ps(&s.prof, s.st, "resize_norm");
-      pp::resize_norm(s.st, dl, ln, rh, maxW, P.pool, 0, x, s.d_flags); }
     Level Lt;
     // (the token count per line only depends on the widths, so the offsets are known before the net runs)
     const long long t0 = P.tok_off[l0];
@@ -1088,7 +1204,9 @@ void rec_groups(rt_lane& s, Pipeline& P) {
     const std::string refused = tail.refusal(set.beam_b);
     if (!refused.empty()) throw RtError(RT_ERR_CAPACITY, refused);
     const float* z5 = nullptr;   // the head's input, for the candidates', the charsets', the lexicons', the keywords' and the beams' logits
-    rec_group_net(s, x, rh, P.line_W.data() + l0, ln, set.rec_window, set.rec_overlap, d_idx + t0, d_prob + t0, tail.needs_z5(cand_k) ? &z5 : nullptr, Lt);
+    if (!flip) rec_group_net(s, x, rh, P.line_W.data() + l0, ln, set.rec_window, set.rec_overlap, d_idx + t0, d_prob + t0, tail.needs_z5(cand_k) ? &z5 : nullptr, Lt);
+    else rec_group_flip(s, P.pool, P.lines.data() + l0, P.line_W.data() + l0, P.both.data() + l0, ln, l0, rh, set.rec_window, set.rec_overlap,
+                        d_idx + t0, d_prob + t0, tail.needs_z5(cand_k) ? &z5 : nullptr, Lt, P.flipo.d, P.flips.d);
     if (Lt.total != tail.rows) throw RtError(RT_ERR_SHAPE, "token count mismatch");
     rt_lane::WordBoxes words{};
     if (s.sh->cfg.rec_return_word_box) {
@@ -1098,7 +1216,7 @@ void rec_groups(rt_lane& s, Pipeline& P) {
         hwl[k].tok_off = P.tok_off[li] - t0;
         hwl[k].g = word_geom(P, li);
       }
-      words = {hwl, P.d_meta.label + l0, P.d_meta.cscore + l0, d_wcol + t0, P.d_wcount + l0, P.d_words + t0};
+      words = {hwl, P.d_meta.label + l0, P.d_meta.cscore + l0, d_wcol + t0, P.d_wcount + l0, P.d_words + t0, P.flipo.d ? P.flipo.d + l0 : nullptr};
     }
     rt_lane::RecTail t;
     t.z5 = z5; t.idx = d_idx + t0; t.prob = d_prob + t0; t.lines = Lt.d; t.n_lines = ln;
@@ -1143,6 +1261,7 @@ void line_round_trip(rt_lane& s, Pipeline& P) {
   // (and what the lexicons, the snap, the patterns, the keywords and the beams left, where the call has them)
   P.lexm.fetch(s.st); P.lexn.fetch(s.st); P.lexs.fetch(s.st); P.pat.fetch(s.st); P.kwh.fetch(s.st); P.kwn.fetch(s.st);
   P.bmn.fetch(s.st); P.bmrec.fetch(s.st); P.bmtok.fetch(s.st); P.bmlm.fetch(s.st); P.bmvc.fetch(s.st);
+  P.flipo.fetch(s.st); P.flips.fetch(s.st);
   s.sync(); s.check_flags();
 }
 // ---- results (session.rs:94-105) ----------------------------------------------------
@@ -1157,6 +1276,15 @@ void results(const rt_session& s, const Pipeline& P, rt_results& res) {
     R.cls_labels.resize(nb); R.cls_scores.resize(nb); R.rec_scores.resize(nb); R.tokens.resize(nb); R.text.resize(nb);
     R.rec_units.resize(nb);
     for (int k = 0; k < nb; k++) R.rec_units[k] = rw::units(P.line_W[p.first_line + k], P.call.set.rec_window, P.call.set.rec_overlap);
+    if (P.flipo.h) {   // rec flip: a line read one way reports 0 (its slots were never written)
+      R.flip_outcome.assign((size_t)nb, 0); R.flip_scores.assign((size_t)2 * nb, 0.0f);
+      for (int k = 0; k < nb; k++) {
+        const int li = p.first_line + k;
+        if (!P.both[(size_t)li]) continue;
+        R.flip_outcome[k] = P.flipo.h[li] == rf::TOOK_1 ? rf::TOOK_1 : rf::KEPT_0;
+        R.flip_scores[2 * (size_t)k] = P.flips.h[2 * (size_t)li]; R.flip_scores[2 * (size_t)k + 1] = P.flips.h[2 * (size_t)li + 1];
+      }
+    }
     for (int k = 0; k < nb; k++) {
       int li = p.first_line + k;
       R.cls_labels[k] = LABELS[m.label[li] ? 1 : 0]; R.cls_scores[k] = m.cscore[li]; R.rec_scores[k] = m.rscore[li];
@@ -1209,9 +1337,10 @@ void results(const rt_session& s, const Pipeline& P, rt_results& res) {
         R.kw_n[k] = std::min(std::max(P.kwn.h[li], 0), kw::HITS);
         if (R.kw_n[k] == 0) continue;
         // the span [first_col, last_col + 1) as an ALNUM word's (wb::line_words): crop pixels per column, the crop's homography,
-        // the classifier's rot180 as k_word_boxes takes it, then original-image coordinates
+        // the line's rot180 as k_word_boxes takes it (the classifier's, inverted where rec flip took view 1), then
+        // original-image coordinates
         const wb::WordGeom g = word_geom(P, li);
-        const int rot180 = (m.label[li] == 1 && m.cscore[li] >= s.cfg.cls_thresh) ? 1 : 0;
+        const int rot180 = rf::rot180(m.label[li] == 1 && m.cscore[li] >= s.cfg.cls_thresh, P.flipo.h && P.both[(size_t)li] ? P.flipo.h[li] : rf::ONE_WAY);
         for (int j = 0; j < R.kw_n[k]; j++) {
           kw::Hit& h = R.kw_hits[(size_t)k * kw::HITS + j];
           h = P.kwh.h[(size_t)li * kw::HITS + j];
@@ -1297,6 +1426,7 @@ rt_results* rt_lane::run_pages(const PageCall& call) {
   if (P.NL > 0) {
     tick.lap("crop plan + warp enqueue");
     cls_stage(*this, P); tick.lap("cls enqueue");
+    flip_plan(*this, P);   // (rec flip with 0 < cls_below <= 1: the call's one extra sync, for the classifier scores)
     rec_plan(*this, P);
     rec_groups(*this, P); tick.lap("rec enqueue");
     line_round_trip(*this, P);
@@ -1356,6 +1486,58 @@ void rt_session::debug_rec_windows(const float* nchw, int n, const int* widths, 
   if (line_prob_out) RT_HIP_CHECK(hipMemcpyAsync(line_prob_out, d_prob, nt * 4, hipMemcpyDeviceToHost, st));
   if (line_z5_out) RT_HIP_CHECK(hipMemcpyAsync(line_z5_out, z5, nt * rw::Z5_D * 4, hipMemcpyDeviceToHost, st));
   sync();
+}
+
+// rt_debug_rec_flip: the crops as ONE rec group through rec_group_flip, the function rec_groups runs for a group with a both-ways
+// line (a call without one: the whole-line path of rec_groups, resize_norm and rec_group_net), under the session's rec windows.
+void rt_session::debug_rec_flip(const uint8_t* crops, const int* hw, int n, const uint8_t* both, float max_wh_ratio, const RecFlipOut& out) {
+  const int rh = cfg.rec_image_shape[1];
+  const int W = gm::resize_norm_width(rh, cfg.rec_image_shape[2], max_wh_ratio);
+  if (W < 8) throw RtError(RT_ERR_INVALID, "rt_debug_rec_flip: max_wh_ratio gives a line less than 8 wide");
+  const int T = RecNet::tokens_for_width(W);
+  size_t bytes = 0; int nf = 0;
+  std::vector<pp::LineDesc> lines((size_t)n);
+  std::vector<int> Ws((size_t)n, W);
+  for (int i = 0; i < n; i++) {
+    lines[(size_t)i] = line_desc(pp::CropRef{(long long)bytes, hw[2 * i], hw[2 * i + 1], 0}, hw[2 * i], hw[2 * i + 1], rh, W);
+    bytes += (size_t)hw[2 * i] * hw[2 * i + 1] * 3;
+    nf += both[i] ? 1 : 0;
+  }
+  begin_call();
+  uint8_t* pool = arena.alloc<uint8_t>(bytes);
+  RT_HIP_CHECK(hipMemcpyAsync(pool, crops, bytes, hipMemcpyHostToDevice, st));
+  const size_t nt = (size_t)n * T;
+  int* d_idx = arena.alloc<int>(std::max<size_t>(nt, 1)); float* d_prob = arena.alloc<float>(std::max<size_t>(nt, 1));
+  int* d_out = arena.alloc<int>((size_t)n); float* d_sc = arena.alloc<float>((size_t)2 * n);
+  RT_HIP_CHECK(hipMemsetAsync(d_out, 0, (size_t)n * sizeof(int), st));
+  const float* z5 = nullptr;
+  Level Lt;
+  const RecFlipTaps taps{out.view_idx, out.view_prob, out.view_z5, out.view_ntok, out.view_score};
+  if (nf > 0) rec_group_flip(*this, pool, lines.data(), Ws.data(), both, n, 0, rh, rec_window, rec_overlap, d_idx, d_prob, &z5, Lt, d_out, d_sc, &taps);
+  else {   // (no both-ways line: the group's former path, rec_groups' own steps; the views are the lines)
+    pp::LineDesc* hl = pinned.alloc<pp::LineDesc>((size_t)n);
+    for (int i = 0; i < n; i++) { hl[i] = lines[(size_t)i]; hl[i].out_off = (long long)i * rh * W * 4; }
+    pp::LineDesc* dl = scratch.alloc<pp::LineDesc>((size_t)n);
+    RT_HIP_CHECK(hipMemcpyAsync(dl, hl, (size_t)n * sizeof(pp::LineDesc), hipMemcpyHostToDevice, st));
+    float* x = scratch.alloc<float>((size_t)n * rh * W * 4);
+    pp::resize_norm(st, dl, n, rh, W, pool, 0, x, d_flags);
+    rec_group_net(*this, x, rh, Ws.data(), n, rec_window, rec_overlap, d_idx, d_prob, &z5, Lt);
+    int* v_tok = scratch.alloc<int>(std::max<size_t>(nt, 1)); int* v_ntok = scratch.alloc<int>((size_t)n); float* v_score = scratch.alloc<float>((size_t)n);
+    pp::ctc_decode(st, d_idx, d_prob, Lt.d, n, v_tok, v_ntok, v_score);
+    if (out.view_idx) RT_HIP_CHECK(hipMemcpyAsync(out.view_idx, d_idx, nt * 4, hipMemcpyDeviceToHost, st));
+    if (out.view_prob) RT_HIP_CHECK(hipMemcpyAsync(out.view_prob, d_prob, nt * 4, hipMemcpyDeviceToHost, st));
+    if (out.view_z5) RT_HIP_CHECK(hipMemcpyAsync(out.view_z5, z5, nt * rw::Z5_D * 4, hipMemcpyDeviceToHost, st));
+    if (out.view_ntok) RT_HIP_CHECK(hipMemcpyAsync(out.view_ntok, v_ntok, (size_t)n * 4, hipMemcpyDeviceToHost, st));
+    if (out.view_score) RT_HIP_CHECK(hipMemcpyAsync(out.view_score, v_score, (size_t)n * 4, hipMemcpyDeviceToHost, st));
+  }
+  if ((size_t)Lt.total != nt) throw RtError(RT_ERR_BACKEND, "rt_debug_rec_flip: token count mismatch");
+  std::vector<int> h_out((size_t)n);
+  RT_HIP_CHECK(hipMemcpyAsync(h_out.data(), d_out, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, st));
+  if (out.idx) RT_HIP_CHECK(hipMemcpyAsync(out.idx, d_idx, nt * 4, hipMemcpyDeviceToHost, st));
+  if (out.prob) RT_HIP_CHECK(hipMemcpyAsync(out.prob, d_prob, nt * 4, hipMemcpyDeviceToHost, st));
+  if (out.z5) RT_HIP_CHECK(hipMemcpyAsync(out.z5, z5, nt * rw::Z5_D * 4, hipMemcpyDeviceToHost, st));
+  sync(); check_flags();
+  if (out.taken) for (int i = 0; i < n; i++) out.taken[i] = h_out[(size_t)i] == rf::TOOK_1 ? 1 : 0;
 }
 
 const char* rt_results_json_impl(rt_results* r, int page, int stage) {

@@ -72,6 +72,9 @@ struct rt_results {
     std::vector<rt::vc::BeamVocab> bm_vocab;
     // rec windows (rec_windows.h; rt_set_rec_windows): per line the number of units it was read in, 1 for a whole line
     std::vector<int32_t> rec_units;
+    // rec flip (rec_flip.h; rt_set_rec_flip): per line its outcome (0: read one way, 1: both ways and view 0 kept, 2: view 1
+    // taken) and the two views' greedy scores [2 per line]; empty when no line of the call was read both ways
+    std::vector<uint8_t> flip_outcome; std::vector<float> flip_scores;
     std::string json[3];
   };
   std::vector<Page> pages;
@@ -97,11 +100,14 @@ struct LaneWorker {
 // line (rt_set_rec_charset / _lexicon / _pattern / _keywords, rec_line_opts.h), the det tiles (rt_set_det_tiles, det_tiles.h; 0 = off)
 // the rec beam (rt_set_rec_beam, ctc_beam.h; beam_b = 0: off), the rec windows (rt_set_rec_windows, rec_windows.h; 0 = off) and
 // the beam's language model (rt_set_rec_beam_lm, ctc_lm.h; lm = -1: off, and without effect while beam_b = 0) and its word list
-// (rt_set_rec_beam_vocab, ctc_vocab.h; beam_vocab = -1: off, likewise)
+// (rt_set_rec_beam_vocab, ctc_vocab.h; beam_vocab = -1: off, likewise), and the rec flip (rt_set_rec_flip, rec_flip.h; 0 = off).
+// With 0 < flip_cls_below <= 1 the call syncs its lane once more, between the cls stage and the rec plan, to bring the
+// classifier scores to the host
 struct CallSettings {
   rt::RecLineOpts rec; int det_tile = 0, det_overlap = 0, beam_b = 0, beam_n = 0, rec_window = 0, rec_overlap = 0;
   int lm = -1; float lm_alpha = 0.0f, lm_beta = 0.0f;
   int beam_vocab = -1; float vocab_gamma = 0.0f;
+  float flip_cls_below = 0.0f;
   bool fused() const { return beam_b > 0 && lm >= 0; }
   bool worded() const { return beam_b > 0 && beam_vocab >= 0; }
 };
@@ -324,8 +330,9 @@ struct rt_lane {
   // What rec_tail reads and writes for ONE rec group, everything on the device: what every group has, then one member per kind,
   // left as it is where the plan has nothing of the kind.  Row and line arrays start at the group's first row / line; a kind's
   // per-line outputs are indexed by its Line::slot, the line's index in the call.
-  // (rec_return_word_box, word_boxes.h: pp::word_boxes' arguments; h_lines: the group's descriptors in pinned memory)
-  struct WordBoxes { const rt::pp::WordLineDesc* h_lines; const int* label; const float* cscore; int* cols; int* n_words; rt::wb::Word* words; };
+  // (rec_return_word_box, word_boxes.h: pp::word_boxes' arguments; h_lines: the group's descriptors in pinned memory; flip: the
+  // lines' rec flip outcomes, rec_flip.h, or null)
+  struct WordBoxes { const rt::pp::WordLineDesc* h_lines; const int* label; const float* cscore; int* cols; int* n_words; rt::wb::Word* words; const int* flip = nullptr; };
   struct RecTail {
     const float* z5 = nullptr;                // [rows, core.D] the head's input, inside a larger allocation (RecTailPlan::needs_z5)
     int* idx = nullptr; float* prob = nullptr;   // [rows] the fused head's argmax rows, in and out
@@ -436,7 +443,13 @@ struct rt_session : rt_lane {
   // rt_set_rec_windows (rec_windows.h): lines at least 8 columns wider than rec_window are read as overlapping windows whose
   // trusted time steps are stitched into the line's rows; 0 = off
   int rec_window = 0, rec_overlap = 0;
-  CallSettings settings() const { return {rec_default, det_tile, det_overlap, beam_b, beam_n, rec_window, rec_overlap, beam_lm, lm_alpha, lm_beta, beam_vocab, vocab_gamma}; }
+  // rt_set_rec_flip (rec_flip.h): lines whose classifier score is below rec_flip_below are read both ways up and the reading
+  // with the better greedy CTC score is kept; 0 = off.  In (0, 1] every call syncs its lane once more, for the scores
+  float rec_flip_below = 0.0f;
+  CallSettings settings() const {
+    return {rec_default, det_tile, det_overlap, beam_b, beam_n, rec_window, rec_overlap, beam_lm, lm_alpha, lm_beta, beam_vocab, vocab_gamma,
+            rec_flip_below};
+  }
   std::string last_error;
   // rt_charset_create: compiles the set (rt::compile_charset), stores it and returns its id
   int charset_create(const char* utf8, size_t len, const int32_t* ids, int n_ids);
@@ -460,6 +473,17 @@ struct rt_session : rt_lane {
   // units' rows in unit order, line after line (idx / prob [unit rows], z5 [unit rows][120]), and the lines' stitched rows
   void debug_rec_windows(const float* nchw, int n, const int* widths, int32_t* unit_idx_out, float* unit_prob_out, float* unit_z5_out,
                          int32_t* line_idx_out, float* line_prob_out, float* line_z5_out);
+  // rt_debug_rec_flip: n RGB8 crops (host, packed back to back, hw[2 i] x hw[2 i + 1] pixels) as ONE rec group through the
+  // pipeline's own rotate, resize_norm, network, score and select (rec_group_flip) at the padded width of max_wh_ratio, under
+  // the session's rec windows; both[i] != 0: line i is read both ways.  Every output is optional and on the host
+  struct RecFlipOut {
+    int32_t* view_idx = nullptr; float* view_prob = nullptr;     // [views][T]: the n lines' view 0, then the flagged lines' view 1
+    float* view_z5 = nullptr;                                    // [views][T][120]
+    int32_t* view_ntok = nullptr; float* view_score = nullptr;   // [views]
+    int32_t* taken = nullptr;                                    // [n]: 1 where view 1 was taken
+    int32_t* idx = nullptr; float* prob = nullptr; float* z5 = nullptr;   // [n][T] (z5: [n][T][120]) the lines' final rows
+  };
+  void debug_rec_flip(const uint8_t* crops, const int* hw, int n, const uint8_t* both, float max_wh_ratio, const RecFlipOut& out);
 
   // ---- lanes, tickets, staging (session_batch.cpp) ----
   // extra lanes: own stream / arenas; rt_run_batch splits the pages over the lanes and runs them on concurrent host threads
