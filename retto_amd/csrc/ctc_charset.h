@@ -17,14 +17,17 @@
 // kernel skips disallowed columns instead of lowering their logits (list_insert ranks a -inf entry ahead of EMPTY_ID).
 // Lines of charset 0 (none) take no part: no row of theirs is gathered, no value of theirs is written.
 //
-// Batch invariance.  The logits come from nn::gemm with K = 120, N = 6625 (Npad16 = 6640).  gemm_plan.cpp sends that shape to the
-// narrow kernel for every M: 6640 is no multiple of 240 (no wide or persistent tile), N is not 128 (no LDS-resident weights), and
-// the streaming kernel takes Npad16 <= 64 only.  M changes the grid and, while there are fewer workgroups than twice the CUs,
-// how many 16-column tiles a workgroup takes (nt); a column's sum over K runs in the same order whatever nt is, and rows never
-// mix.  So under the production plan a restricted line's (idx, prob), and with them its tokens and score, do not depend on what
-// else is in the batch or on the chunking.  That is a property of today's plan, not a promise of the interface: as for
-// candidates ranks >= 1, what is promised is that results are repeatable run to run and equal across the entry points on one
-// batch.
+// Batch invariance.  The logits come from nn::gemm with K = 120 and N = the model's class count (nets.cpp: head.fc's width).  What
+// follows holds for the 6625 classes of the PP-OCRv4 dictionary (Npad16 = 6640).  gemm_plan.cpp sends that shape to the narrow
+// kernel for every M: 6640 is no multiple of 240 (no wide or persistent tile), N is not 128 (no LDS-resident weights), and the
+// streaming kernel takes Npad16 <= 64 only.  M changes the grid and, while there are fewer workgroups than twice the CUs, how many
+// 16-column tiles a workgroup takes (nt); a column's sum over K runs in the same order whatever nt is, and rows never mix.  So
+// under the production plan a restricted line's (idx, prob), and with them its tokens and score, do not depend on what else is in
+// the batch or on the chunking.  A class count whose Npad16 is a multiple of 240 (240, 18480) meets production_variant()'s wide
+// tiles from 16384 rows on, so there the kernel can change with M; that a row gets the same bits from those routes at K = 120 is
+// not measured (test_gemm_routes_are_bit_identical runs K = 240, 128 and 64).  Either way this is a property of today's plan, not
+// a promise of the interface: as for candidates ranks >= 1, what is promised is that results are repeatable run to run and equal
+// across the entry points on one batch.
 #pragma once
 #include <math.h>
 #include <stdint.h>
