@@ -18,6 +18,7 @@
 #include "geom_math.h"
 #include "onnx_import.h"
 #include "image_decode.h"
+#include "rec_text.h"
 
 using namespace rt;
 

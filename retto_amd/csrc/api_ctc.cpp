@@ -8,6 +8,7 @@
 
 #include "api_internal.h"
 #include "ctc_host_ref.h"
+#include "rec_text.h"
 
 using namespace rt;
 
@@ -160,6 +161,59 @@ void debug_ctc_lexicon(rt_session* s, const hr::LexiconArgs& a, int chunk_rows) 
     DevBufs::download(a.idx, h.t.idx, (size_t)a.rows); DevBufs::download(a.prob, h.t.prob, (size_t)a.rows);
     DevBufs::download(a.snapped_out, t.snapped, (size_t)n_lines); DevBufs::download(a.vit_out, t.vit, (size_t)n_lines);
   }
+}
+
+// A beam entry's struct with what every form takes; the _lm and _vocab entries add theirs by name.
+hr::BeamArgs beam_args(hr::BeamArgs::Form form, const hr::Head& head, int beam, int nbest, int32_t* counts_out, rt_beam* beams_out,
+                       int32_t* tokens_out) {
+  hr::BeamArgs a{head};
+  a.form = form; a.beam = beam; a.nbest = nbest; a.counts_out = counts_out; a.beams_out = beams_out; a.tokens_out = tokens_out;
+  return a;
+}
+// Rec beams' device path on host arrays: every line carries the beam, as in a pipeline call after rt_set_rec_beam.  Where the
+// call is fused (a.fused()) the model the check compiled and the lm records go along, where it is worded (a.worded()) the
+// vocabulary and the vocab records; their tables go to the device as rt_lm_create / rt_vocab_create put them.
+void debug_ctc_beam(rt_session* s, const hr::BeamArgs& a, int chunk_rows) {
+  const int n_lines = a.n_lines, nbest = a.nbest;
+  if (a.beam == 0 || n_lines == 0) return;   // (off, or no line: no launch, no write)
+  TailHook h(s, a, {nullptr, nullptr, 0, chunk_rows, a.beam, nbest}, std::vector<RecLineOpts>((size_t)n_lines), RecStores{});
+  rt_session::RecTail::Beam& t = h.t.beam;
+  // (what the kernels write starts as the caller's values: a slot they leave alone comes back untouched)
+  const size_t nt = (size_t)std::max<long long>(a.rows, 1) * nbest, nr = (size_t)n_lines * nbest;
+  t.count = h.bufs.upload(a.counts_out, (size_t)n_lines);
+  t.recs = h.bufs.upload(reinterpret_cast<const bm::Beam*>(a.beams_out), nr);
+  t.tok = h.bufs.alloc<int>(nt);
+  DevBufs::put(t.tok, a.tokens_out, (size_t)a.rows * nbest);
+  auto up = [&](const auto& table) { return h.bufs.upload(table.data(), table.size()); };
+  if (a.fused()) {
+    t.lms = h.bufs.upload(reinterpret_cast<const lm::BeamLm*>(a.lm_out), nr);
+    t.fused = true;
+    t.fu = lm::Fusion{a.model.view_through(up), a.alpha, a.beta};
+  }
+  if (a.worded()) {
+    t.vocs = h.bufs.upload(reinterpret_cast<const vc::BeamVocab*>(a.vocab_out), nr);
+    t.worded = true;
+    t.wc = vc::Constraint{a.vocab.view_through(up), a.gamma};
+  }
+  h.run();
+  DevBufs::download(a.counts_out, t.count, (size_t)n_lines);
+  DevBufs::download(reinterpret_cast<bm::Beam*>(a.beams_out), t.recs, nr);
+  if (a.fused()) DevBufs::download(reinterpret_cast<lm::BeamLm*>(a.lm_out), t.lms, nr);
+  if (a.worded()) DevBufs::download(reinterpret_cast<vc::BeamVocab*>(a.vocab_out), t.vocs, nr);
+  DevBufs::download(a.tokens_out, t.tok, (size_t)a.rows * nbest);
+}
+// What rt_debug_lm_score and rt_debug_vocab_walk require of their strings (string i has string_lens[i] ids, one after the other
+// in strings): the first requirement that fails, or the empty string
+std::string strings_error(const int32_t* strings, const int32_t* string_lens, int n_strings, int classes) {
+  long long o = 0;
+  for (int i = 0; i < n_strings; i++) {
+    if (string_lens[i] < 0) return "string " + std::to_string(i) + " has a negative length";
+    for (int k = 0; k < string_lens[i]; k++)
+      if (strings[o + k] < 1 || strings[o + k] >= classes)
+        return "class id " + std::to_string(strings[o + k]) + " in string " + std::to_string(i) + " is outside [1, " + std::to_string(classes) + ")";
+    o += string_lens[i];
+  }
+  return std::string();
 }
 
 // What the three rt_debug_*_compile hooks share: err cleared, `bad` (the entry's own argument check) refused under its name,
@@ -424,35 +478,18 @@ RT_API int rt_debug_ctc_keywords(rt_session* s, const float* z5, const float* W,
 // ---- beams: every line carries the beam, as in a pipeline call after rt_set_rec_beam
 int rt_debug_ctc_beam_host(const float* z5, const float* W, const float* bias, int N, const int32_t* tokens_per_line, int n_lines,
                            int beam, int nbest, int32_t* counts_out, rt_beam* beams_out, int32_t* tokens_out) {
-  hr::BeamArgs a{{z5, W, bias, N, tokens_per_line, n_lines}};
-  a.beam = beam; a.nbest = nbest; a.counts_out = counts_out; a.beams_out = beams_out; a.tokens_out = tokens_out;
+  hr::BeamArgs a = beam_args(hr::BeamArgs::PLAIN, {z5, W, bias, N, tokens_per_line, n_lines}, beam, nbest, counts_out, beams_out, tokens_out);
   return host_entry("rt_debug_ctc_beam_host", a, hr::beam_ref);
 }
 RT_API int rt_debug_ctc_beam(rt_session* s, const float* z5, const float* W, const float* bias, int N, const int32_t* tokens_per_line,
                              int n_lines, int beam, int nbest, int chunk_rows, int32_t* counts_out, rt_beam* beams_out,
                              int32_t* tokens_out) {
-  hr::BeamArgs a{{z5, W, bias, N, tokens_per_line, n_lines}};
-  a.beam = beam; a.nbest = nbest; a.counts_out = counts_out; a.beams_out = beams_out; a.tokens_out = tokens_out;
+  hr::BeamArgs a = beam_args(hr::BeamArgs::PLAIN, {z5, W, bias, N, tokens_per_line, n_lines}, beam, nbest, counts_out, beams_out, tokens_out);
   if (const int rc = device_check(s, "rt_debug_ctc_beam", a, chunk_rows)) return rc;
-  return guarded(s, [&] {
-    if (beam == 0 || n_lines == 0) return;   // (off, or no line: no launch, no write)
-    TailHook h(s, a, {nullptr, nullptr, 0, chunk_rows, beam, nbest}, std::vector<RecLineOpts>((size_t)n_lines), RecStores{});
-    rt_session::RecTail::Beam& t = h.t.beam;
-    // (what the kernels write starts as the caller's values: a slot they leave alone comes back untouched)
-    const size_t nt = (size_t)std::max<long long>(a.rows, 1) * nbest;
-    t.count = h.bufs.upload(counts_out, (size_t)n_lines);
-    t.recs = h.bufs.upload(reinterpret_cast<const bm::Beam*>(beams_out), (size_t)n_lines * nbest);
-    t.tok = h.bufs.alloc<int>(nt);
-    DevBufs::put(t.tok, tokens_out, (size_t)a.rows * nbest);
-    h.run();
-    DevBufs::download(counts_out, t.count, (size_t)n_lines);
-    DevBufs::download(reinterpret_cast<bm::Beam*>(beams_out), t.recs, (size_t)n_lines * nbest);
-    DevBufs::download(tokens_out, t.tok, (size_t)a.rows * nbest);
-  });
+  return guarded(s, [&] { debug_ctc_beam(s, a, chunk_rows); });
 }
 
-// ---- beams with language-model fusion (ctc_lm.h): the model in its id form, compiled by the check; its tables go to the device
-// as rt_lm_create puts them
+// ---- beams with language-model fusion (ctc_lm.h): the model in its id form, compiled by the check
 int rt_debug_lm_compile(const void* dict, size_t dict_len, const char* arpa, size_t len, float oov_log10, int32_t* ngram_ids_out,
                         int ids_cap, int32_t* ngram_lens_out, float* logp_out, float* backoff_out, int n_cap, int* n_ids_out, int* n_out,
                         int* order_out, int* dropped_out, int* states_out, float* oov_out, int* n_classes, char* err, size_t err_cap) {
@@ -485,16 +522,10 @@ int rt_debug_lm_score(int classes, const int32_t* ngram_ids, const int32_t* ngra
     lm::Model m;
     const std::string bad = hr::IdModel{ngram_ids, ngram_lens, logp, backoff, n, oov}.compile(classes, m);
     if (!bad.empty()) return refuse(bad);
-    long long o = 0;
-    for (int i = 0; i < n_strings; i++) {
-      if (string_lens[i] < 0) return refuse("string " + std::to_string(i) + " has a negative length");
-      for (int k = 0; k < string_lens[i]; k++)
-        if (strings[o + k] < 1 || strings[o + k] >= classes)
-          return refuse("class id " + std::to_string(strings[o + k]) + " in string " + std::to_string(i) + " is outside [1, " + std::to_string(classes) + ")");
-      o += string_lens[i];
-    }
+    const std::string bad_string = strings_error(strings, string_lens, n_strings, classes);
+    if (!bad_string.empty()) return refuse(bad_string);
     const lm::View v = m.view();
-    o = 0;
+    long long o = 0;
     for (int i = 0; i < n_strings; i++) {
       const lm::Step x = lm::walk(v, strings + o, string_lens[i]);
       lm_out[i] = x.score; state_out[i] = x.next;
@@ -510,47 +541,21 @@ int rt_debug_ctc_beam_lm_host(const float* z5, const float* W, const float* bias
                               int beam, int nbest, const int32_t* ngram_ids, const int32_t* ngram_lens, const float* logp,
                               const float* backoff, int n, float oov, float alpha, float beta, int32_t* counts_out, rt_beam* beams_out,
                               int32_t* tokens_out, rt_beam_lm* lm_out) {
-  hr::BeamLmArgs a;
-  static_cast<hr::Head&>(a) = hr::Head{z5, W, bias, N, tokens_per_line, n_lines};
-  a.beam = beam; a.nbest = nbest; a.counts_out = counts_out; a.beams_out = beams_out; a.tokens_out = tokens_out;
+  hr::BeamArgs a = beam_args(hr::BeamArgs::LM, {z5, W, bias, N, tokens_per_line, n_lines}, beam, nbest, counts_out, beams_out, tokens_out);
   a.ids = {ngram_ids, ngram_lens, logp, backoff, n, oov}; a.alpha = alpha; a.beta = beta; a.lm_out = lm_out;
-  return host_entry("rt_debug_ctc_beam_lm_host", a, hr::beam_lm_ref);
+  return host_entry("rt_debug_ctc_beam_lm_host", a, hr::beam_ref);
 }
 RT_API int rt_debug_ctc_beam_lm(rt_session* s, const float* z5, const float* W, const float* bias, int N, const int32_t* tokens_per_line,
                                 int n_lines, int beam, int nbest, int chunk_rows, const int32_t* ngram_ids, const int32_t* ngram_lens,
                                 const float* logp, const float* backoff, int n, float oov, float alpha, float beta, int32_t* counts_out,
                                 rt_beam* beams_out, int32_t* tokens_out, rt_beam_lm* lm_out) {
-  hr::BeamLmArgs a;
-  static_cast<hr::Head&>(a) = hr::Head{z5, W, bias, N, tokens_per_line, n_lines};
-  a.beam = beam; a.nbest = nbest; a.counts_out = counts_out; a.beams_out = beams_out; a.tokens_out = tokens_out;
+  hr::BeamArgs a = beam_args(hr::BeamArgs::LM, {z5, W, bias, N, tokens_per_line, n_lines}, beam, nbest, counts_out, beams_out, tokens_out);
   a.ids = {ngram_ids, ngram_lens, logp, backoff, n, oov}; a.alpha = alpha; a.beta = beta; a.lm_out = lm_out;
   if (const int rc = device_check(s, "rt_debug_ctc_beam_lm", a, chunk_rows)) return rc;
-  return guarded(s, [&] {
-    if (beam == 0 || n_lines == 0) return;   // (off, or no line: no launch, no write)
-    TailHook h(s, a, {nullptr, nullptr, 0, chunk_rows, beam, nbest}, std::vector<RecLineOpts>((size_t)n_lines), RecStores{});
-    rt_session::RecTail::Beam& t = h.t.beam;
-    // (what the kernels write starts as the caller's values: a slot they leave alone comes back untouched)
-    const size_t nt = (size_t)std::max<long long>(a.rows, 1) * nbest;
-    t.count = h.bufs.upload(counts_out, (size_t)n_lines);
-    t.recs = h.bufs.upload(reinterpret_cast<const bm::Beam*>(beams_out), (size_t)n_lines * nbest);
-    t.lms = h.bufs.upload(reinterpret_cast<const lm::BeamLm*>(lm_out), (size_t)n_lines * nbest);
-    t.tok = h.bufs.alloc<int>(nt);
-    DevBufs::put(t.tok, tokens_out, (size_t)a.rows * nbest);
-    const lm::Model& m = a.model;
-    t.fused = true;
-    t.fu = lm::Fusion{lm::View{h.bufs.upload(m.uni.data(), m.uni.size()), h.bufs.upload(m.states.data(), m.states.size()),
-                               h.bufs.upload(m.arcs.data(), m.arcs.size()), m.classes, (int32_t)m.states.size(), (int32_t)m.arcs.size(), m.start},
-                      alpha, beta};
-    h.run();
-    DevBufs::download(counts_out, t.count, (size_t)n_lines);
-    DevBufs::download(reinterpret_cast<bm::Beam*>(beams_out), t.recs, (size_t)n_lines * nbest);
-    DevBufs::download(reinterpret_cast<lm::BeamLm*>(lm_out), t.lms, (size_t)n_lines * nbest);
-    DevBufs::download(tokens_out, t.tok, (size_t)a.rows * nbest);
-  });
+  return guarded(s, [&] { debug_ctc_beam(s, a, chunk_rows); });
 }
 
-// ---- beams with a word list (ctc_vocab.h): the vocabulary in its id form, compiled by the check; its tables go to the device as
-// rt_vocab_create puts them
+// ---- beams with a word list (ctc_vocab.h), with or without a model: the vocabulary in its id form, compiled by the check
 int rt_debug_vocab_compile(const void* dict, size_t dict_len, const char* utf8, size_t len, int flags, int32_t* word_ids_out, int ids_cap,
                            int32_t* word_lens_out, int n_cap, int* n_ids_out, int* n_out, int* words_out, int* nodes_out,
                            int* word_classes_out, int* variants_dropped_out, int* n_classes, char* err, size_t err_cap) {
@@ -582,16 +587,10 @@ int rt_debug_vocab_walk(int classes, const int32_t* word_ids, const int32_t* wor
     vc::Vocab m; std::string msg;
     const int rc = vc::compile(classes, word_ids, word_lens, n_words, m, msg);
     if (rc != vc::OK) return refuse(rc, msg);
-    long long o = 0;
-    for (int i = 0; i < n_strings; i++) {
-      if (string_lens[i] < 0) return refuse(RT_ERR_INVALID, "string " + std::to_string(i) + " has a negative length");
-      for (int k = 0; k < string_lens[i]; k++)
-        if (strings[o + k] < 1 || strings[o + k] >= classes)
-          return refuse(RT_ERR_INVALID, "class id " + std::to_string(strings[o + k]) + " in string " + std::to_string(i) + " is outside [1, " + std::to_string(classes) + ")");
-      o += string_lens[i];
-    }
+    const std::string bad_string = strings_error(strings, string_lens, n_strings, classes);
+    if (!bad_string.empty()) return refuse(RT_ERR_INVALID, bad_string);
     const vc::View v = m.view();
-    o = 0;
+    long long o = 0;
     for (int i = 0; i < n_strings; i++) {
       const vc::Walk x = vc::walk(v, strings + o, string_lens[i]);
       open_out[i] = x.oov; closed_out[i] = x.closed; state_out[i] = x.state;
@@ -603,69 +602,26 @@ int rt_debug_vocab_walk(int classes, const int32_t* word_ids, const int32_t* wor
     return RT_ERR_BACKEND;
   }
 }
-namespace {
-void fill_vocab_args(hr::BeamVocabArgs& a, const float* z5, const float* W, const float* bias, int N, const int32_t* tokens_per_line, int n_lines,
-          int beam, int nbest, const int32_t* ngram_ids, const int32_t* ngram_lens, const float* logp, const float* backoff, int n,
-          float oov, float alpha, float beta, const int32_t* word_ids, const int32_t* word_lens, int n_words, float gamma,
-          int32_t* counts_out, rt_beam* beams_out, int32_t* tokens_out, rt_beam_lm* lm_out, rt_beam_vocab* vocab_out) {
-  static_cast<hr::Head&>(a) = hr::Head{z5, W, bias, N, tokens_per_line, n_lines};
-  a.beam = beam; a.nbest = nbest; a.counts_out = counts_out; a.beams_out = beams_out; a.tokens_out = tokens_out;
-  a.ids = {ngram_ids, ngram_lens, logp, backoff, n, oov}; a.alpha = alpha; a.beta = beta; a.lm_out = lm_out;
-  a.words = {word_ids, word_lens, n_words}; a.gamma = gamma; a.vocab_out = vocab_out;
-}
-}  // namespace
 int rt_debug_ctc_beam_vocab_host(const float* z5, const float* W, const float* bias, int N, const int32_t* tokens_per_line, int n_lines,
                                  int beam, int nbest, const int32_t* ngram_ids, const int32_t* ngram_lens, const float* logp,
                                  const float* backoff, int n, float oov, float alpha, float beta, const int32_t* word_ids,
                                  const int32_t* word_lens, int n_words, float gamma, int32_t* counts_out, rt_beam* beams_out,
                                  int32_t* tokens_out, rt_beam_lm* lm_out, rt_beam_vocab* vocab_out) {
-  hr::BeamVocabArgs a;
-  fill_vocab_args(a, z5, W, bias, N, tokens_per_line, n_lines, beam, nbest, ngram_ids, ngram_lens, logp, backoff, n, oov, alpha, beta, word_ids,
-       word_lens, n_words, gamma, counts_out, beams_out, tokens_out, lm_out, vocab_out);
-  return host_entry("rt_debug_ctc_beam_vocab_host", a, hr::beam_vocab_ref);
+  hr::BeamArgs a = beam_args(hr::BeamArgs::VOCAB, {z5, W, bias, N, tokens_per_line, n_lines}, beam, nbest, counts_out, beams_out, tokens_out);
+  a.ids = {ngram_ids, ngram_lens, logp, backoff, n, oov}; a.alpha = alpha; a.beta = beta; a.lm_out = lm_out;
+  a.words = {word_ids, word_lens, n_words}; a.gamma = gamma; a.vocab_out = vocab_out;
+  return host_entry("rt_debug_ctc_beam_vocab_host", a, hr::beam_ref);
 }
 RT_API int rt_debug_ctc_beam_vocab(rt_session* s, const float* z5, const float* W, const float* bias, int N, const int32_t* tokens_per_line,
                                    int n_lines, int beam, int nbest, int chunk_rows, const int32_t* ngram_ids, const int32_t* ngram_lens,
                                    const float* logp, const float* backoff, int n, float oov, float alpha, float beta,
                                    const int32_t* word_ids, const int32_t* word_lens, int n_words, float gamma, int32_t* counts_out,
                                    rt_beam* beams_out, int32_t* tokens_out, rt_beam_lm* lm_out, rt_beam_vocab* vocab_out) {
-  hr::BeamVocabArgs a;
-  fill_vocab_args(a, z5, W, bias, N, tokens_per_line, n_lines, beam, nbest, ngram_ids, ngram_lens, logp, backoff, n, oov, alpha, beta, word_ids,
-       word_lens, n_words, gamma, counts_out, beams_out, tokens_out, lm_out, vocab_out);
+  hr::BeamArgs a = beam_args(hr::BeamArgs::VOCAB, {z5, W, bias, N, tokens_per_line, n_lines}, beam, nbest, counts_out, beams_out, tokens_out);
+  a.ids = {ngram_ids, ngram_lens, logp, backoff, n, oov}; a.alpha = alpha; a.beta = beta; a.lm_out = lm_out;
+  a.words = {word_ids, word_lens, n_words}; a.gamma = gamma; a.vocab_out = vocab_out;
   if (const int rc = device_check(s, "rt_debug_ctc_beam_vocab", a, chunk_rows)) return rc;
-  return guarded(s, [&] {
-    if (beam == 0 || n_lines == 0) return;   // (off, or no line: no launch, no write)
-    TailHook h(s, a, {nullptr, nullptr, 0, chunk_rows, beam, nbest}, std::vector<RecLineOpts>((size_t)n_lines), RecStores{});
-    rt_session::RecTail::Beam& t = h.t.beam;
-    // (what the kernels write starts as the caller's values: a slot they leave alone comes back untouched)
-    const size_t nt = (size_t)std::max<long long>(a.rows, 1) * nbest, nr = (size_t)n_lines * nbest;
-    const bool fused = a.has_model();
-    t.count = h.bufs.upload(counts_out, (size_t)n_lines);
-    t.recs = h.bufs.upload(reinterpret_cast<const bm::Beam*>(beams_out), nr);
-    t.vocs = h.bufs.upload(reinterpret_cast<const vc::BeamVocab*>(vocab_out), nr);
-    t.tok = h.bufs.alloc<int>(nt);
-    DevBufs::put(t.tok, tokens_out, (size_t)a.rows * nbest);
-    if (fused) {
-      const lm::Model& m = a.model;
-      t.lms = h.bufs.upload(reinterpret_cast<const lm::BeamLm*>(lm_out), nr);
-      t.fused = true;
-      t.fu = lm::Fusion{lm::View{h.bufs.upload(m.uni.data(), m.uni.size()), h.bufs.upload(m.states.data(), m.states.size()),
-                                 h.bufs.upload(m.arcs.data(), m.arcs.size()), m.classes, (int32_t)m.states.size(), (int32_t)m.arcs.size(), m.start},
-                        alpha, beta};
-    }
-    const vc::Vocab& w = a.vocab;
-    t.worded = true;
-    t.wc = vc::Constraint{vc::View{h.bufs.upload(w.nodes.data(), w.nodes.size()), h.bufs.upload(w.arcs.data(), w.arcs.size()),
-                                   h.bufs.upload(w.mask.data(), w.mask.size()), h.bufs.upload(w.root.data(), w.root.size()), w.classes,
-                                   (int32_t)w.nodes.size(), (int32_t)w.arcs.size()},
-                          gamma};
-    h.run();
-    DevBufs::download(counts_out, t.count, (size_t)n_lines);
-    DevBufs::download(reinterpret_cast<bm::Beam*>(beams_out), t.recs, nr);
-    DevBufs::download(reinterpret_cast<vc::BeamVocab*>(vocab_out), t.vocs, nr);
-    if (fused) DevBufs::download(reinterpret_cast<lm::BeamLm*>(lm_out), t.lms, nr);
-    DevBufs::download(tokens_out, t.tok, (size_t)a.rows * nbest);
-  });
+  return guarded(s, [&] { debug_ctc_beam(s, a, chunk_rows); });
 }
 
 }  // extern "C"

@@ -3,8 +3,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include <stdexcept>
 #include <string>
+
+#include "rt_error.h"
 
 namespace rt {
 
@@ -40,11 +41,6 @@ struct Epilogue {
   int* am_idx = nullptr;
   float* am_sum = nullptr;
   int am_tiles = 0;
-};
-
-struct RtError : std::runtime_error {
-  int code;
-  RtError(int c, const std::string& m) : std::runtime_error(m), code(c) {}
 };
 
 #define RT_HIP_CHECK(expr)                                                                       \

@@ -332,34 +332,10 @@ inline void keywords_ref(const KeywordArgs& a) {
   });
 }
 
-// ---- beams (ctc_beam.h); beam = 0 (off) and n_lines = 0 pass the check: nothing is computed or written then --------------------
-struct BeamArgs : Head {
-  int beam = 0, nbest = 0;
-  int32_t* counts_out = nullptr; rt_beam* beams_out = nullptr; int32_t* tokens_out = nullptr;
-  std::string error() {
-    if (!z5 || !W || !tokens_per_line || !counts_out || !beams_out || !tokens_out) return "a required pointer is null";
-    if (n_lines < 0) return "n_lines is negative";
-    if (N <= 1) return "N must be at least 2 (the blank and one class)";
-    if (beam < 0 || beam > RT_MAX_BEAM) return "beam = " + S(beam) + " is outside [0, RT_MAX_BEAM]";
-    if (beam > 0 && (nbest < 1 || nbest > std::min(beam, RT_MAX_NBEST)))
-      return "nbest = " + S(nbest) + " is outside [1, min(beam, RT_MAX_NBEST)]";
-    const std::string bad = lines_error(*this, nullptr, 0, "");
-    if (!bad.empty()) return bad;
-    if (beam > 0 && n_lines + rows * beam > bm::MAX_GROUP_NODES)
-      return "the lines need " + S(n_lines + rows * beam) + " trie nodes, more than a group's trie holds";
-    return std::string();
-  }
-};
-inline void beam_ref(const BeamArgs& a) {
-  if (a.beam == 0) return;
-  walk_lines(a, lx::row_lse, [](int) { return true; }, [&](int i, long long o, int T, const float* logits, const float* lse) {
-    a.counts_out[i] = bm::line_beams(logits, a.N, lse, T, a.N, a.beam, a.nbest, reinterpret_cast<bm::Beam*>(a.beams_out) + (size_t)i * a.nbest,
-                                     a.tokens_out + o * a.nbest);
-  });
-}
-
-// ---- beams with language-model fusion (ctc_lm.h): the beam's arguments, the model in its id form over the head's N classes
-// (<s> = N), oov as a natural log, the weights; the check compiles the model.  lm_out [n_lines][nbest] beside beams_out
+// ---- beams (ctc_beam.h), plain or with their add-ons; beam = 0 (off) and n_lines = 0 pass the check: nothing is computed or
+// written then.  The add-ons in their id form over the head's N classes, compiled by the check:
+// a language model (ctc_lm.h; <s> = N, oov a natural log) with its weights, and lm_out [n_lines][nbest] beside beams_out;
+// a word list (ctc_vocab.h) with gamma, and vocab_out [n_lines][nbest] beside beams_out
 struct IdModel {
   const int32_t* ngram_ids = nullptr; const int32_t* ngram_lens = nullptr; const float* logp = nullptr; const float* backoff = nullptr;
   int n = 0; float oov = 0.0f;
@@ -370,30 +346,6 @@ struct IdModel {
     return lm::compile(classes, ngram_ids, ngram_lens, logp, backoff, n, nullptr, oov, m, msg) == lm::OK ? std::string() : msg;
   }
 };
-struct BeamLmArgs : BeamArgs {
-  IdModel ids; float alpha = 0.0f, beta = 0.0f;
-  rt_beam_lm* lm_out = nullptr;
-  lm::Model model;
-  std::string error() {
-    if (!lm_out) return "a required pointer is null";
-    const std::string bad = BeamArgs::error();
-    if (!bad.empty()) return bad;
-    if (const char* why = lm::check_weights(alpha, beta)) return why;
-    return ids.compile(N, model);
-  }
-};
-inline void beam_lm_ref(const BeamLmArgs& a) {
-  if (a.beam == 0) return;
-  const lm::Fusion f{a.model.view(), a.alpha, a.beta};
-  walk_lines(a, lx::row_lse, [](int) { return true; }, [&](int i, long long o, int T, const float* logits, const float* lse) {
-    a.counts_out[i] = bm::line_beams(logits, a.N, lse, T, a.N, a.beam, a.nbest, reinterpret_cast<bm::Beam*>(a.beams_out) + (size_t)i * a.nbest,
-                                     a.tokens_out + o * a.nbest, &f, reinterpret_cast<lm::BeamLm*>(a.lm_out) + (size_t)i * a.nbest);
-  });
-}
-
-// ---- beams with a word list (ctc_vocab.h), with or without a model: the fused beam's arguments -- n = 0 n-grams with
-// alpha = beta = 0 means no model, and lm_out may be null then -- plus the vocabulary in its id form over the head's N classes
-// and gamma; the check compiles both.  vocab_out [n_lines][nbest] beside beams_out
 struct IdVocab {
   const int32_t* word_ids = nullptr; const int32_t* word_lens = nullptr; int n = 0;
   // the first requirement that fails, or the empty string with the vocabulary compiled into m
@@ -403,36 +355,54 @@ struct IdVocab {
     return vc::compile(classes, word_ids, word_lens, n, m, msg) == vc::OK ? std::string() : msg;
   }
 };
-struct BeamVocabArgs : BeamArgs {
+struct BeamArgs : Head {
+  int beam = 0, nbest = 0;
+  int32_t* counts_out = nullptr; rt_beam* beams_out = nullptr; int32_t* tokens_out = nullptr;
+  // which entry filled it: rt_debug_ctc_beam*, _beam_lm* (always fused, whatever the model holds) or _beam_vocab* (fused where a
+  // model is given: n = 0 n-grams with alpha = beta = 0 means none, and lm_out may be null then)
+  enum Form { PLAIN, LM, VOCAB };
+  Form form = PLAIN;
   IdModel ids; float alpha = 0.0f, beta = 0.0f;
   rt_beam_lm* lm_out = nullptr;
   IdVocab words; float gamma = 0.0f;
   rt_beam_vocab* vocab_out = nullptr;
-  lm::Model model; vc::Vocab vocab;
+  lm::Model model; vc::Vocab vocab;   // (the check's)
   bool has_model() const { return ids.n != 0 || alpha != 0.0f || beta != 0.0f; }
+  bool fused() const { return form == LM || (form == VOCAB && has_model()); }
+  bool worded() const { return form == VOCAB; }
   std::string error() {
-    if (!vocab_out || (has_model() && !lm_out)) return "a required pointer is null";
-    const std::string bad = BeamArgs::error();
+    if ((fused() && !lm_out) || (worded() && !vocab_out)) return "a required pointer is null";
+    if (!z5 || !W || !tokens_per_line || !counts_out || !beams_out || !tokens_out) return "a required pointer is null";
+    if (n_lines < 0) return "n_lines is negative";
+    if (N <= 1) return "N must be at least 2 (the blank and one class)";
+    if (beam < 0 || beam > RT_MAX_BEAM) return "beam = " + S(beam) + " is outside [0, RT_MAX_BEAM]";
+    if (beam > 0 && (nbest < 1 || nbest > std::min(beam, RT_MAX_NBEST)))
+      return "nbest = " + S(nbest) + " is outside [1, min(beam, RT_MAX_NBEST)]";
+    const std::string bad = lines_error(*this, nullptr, 0, "");
     if (!bad.empty()) return bad;
+    if (beam > 0 && n_lines + rows * beam > bm::MAX_GROUP_NODES)
+      return "the lines need " + S(n_lines + rows * beam) + " trie nodes, more than a group's trie holds";
+    if (form == PLAIN) return std::string();
     if (const char* why = lm::check_weights(alpha, beta)) return why;
-    if (const char* why = vc::check_gamma(gamma)) return why;
-    if (has_model()) {
+    if (const char* why = worded() ? vc::check_gamma(gamma) : nullptr) return why;
+    if (fused()) {
       const std::string m = ids.compile(N, model);
       if (!m.empty()) return m;
     }
-    return words.compile(N, vocab);
+    return worded() ? words.compile(N, vocab) : std::string();
   }
 };
-inline void beam_vocab_ref(const BeamVocabArgs& a) {
+inline void beam_ref(const BeamArgs& a) {
   if (a.beam == 0) return;
+  // an add-on the form does not carry is an empty model's null view here, and is never passed on: null goes in its place
   const lm::Fusion f{a.model.view(), a.alpha, a.beta};
   const vc::Constraint w{a.vocab.view(), a.gamma};
-  const bool fused = a.has_model();
+  const bool fused = a.fused(), worded = a.worded();
   walk_lines(a, lx::row_lse, [](int) { return true; }, [&](int i, long long o, int T, const float* logits, const float* lse) {
     a.counts_out[i] = bm::line_beams(logits, a.N, lse, T, a.N, a.beam, a.nbest, reinterpret_cast<bm::Beam*>(a.beams_out) + (size_t)i * a.nbest,
                                      a.tokens_out + o * a.nbest, fused ? &f : nullptr,
-                                     fused ? reinterpret_cast<lm::BeamLm*>(a.lm_out) + (size_t)i * a.nbest : nullptr, &w,
-                                     reinterpret_cast<vc::BeamVocab*>(a.vocab_out) + (size_t)i * a.nbest);
+                                     fused ? reinterpret_cast<lm::BeamLm*>(a.lm_out) + (size_t)i * a.nbest : nullptr, worded ? &w : nullptr,
+                                     worded ? reinterpret_cast<vc::BeamVocab*>(a.vocab_out) + (size_t)i * a.nbest : nullptr);
   });
 }
 

@@ -128,7 +128,10 @@ struct Model {
   int classes = 0, order = 1, n_ngrams = 0, dropped = 0, start = 0;
   float oov = 0.0f;
   std::vector<Uni> uni; std::vector<State> states; std::vector<Arc> arcs;
-  View view() const { return View{uni.data(), states.data(), arcs.data(), classes, (int32_t)states.size(), (int32_t)arcs.size(), start}; }
+  // the View with every table where put(table) says it is: the one place that lists the tables.  (A store's put uploads them.)
+  template <class Put>
+  View view_through(Put&& put) const { return View{put(uni), put(states), put(arcs), classes, (int32_t)states.size(), (int32_t)arcs.size(), start}; }
+  View view() const { return view_through([](const auto& table) { return table.data(); }); }
 };
 
 inline std::string key_of_ids(const int32_t* p, int n) { return std::string((const char*)p, (size_t)n * sizeof(int32_t)); }

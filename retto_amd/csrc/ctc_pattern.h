@@ -75,6 +75,7 @@
 #include <vector>
 
 #include "ctc_lexicon.h"
+#include "rec_text.h"
 
 namespace rt {
 namespace pt {
@@ -282,27 +283,6 @@ struct Compiled {
 };
 struct Fail { int code; std::string msg; };
 
-inline int utf8_strict(const unsigned char* p, size_t n, uint32_t* cp) {  // bytes consumed, 0 = invalid (Rust's from_utf8 rule)
-  if (n == 0) return 0;
-  const unsigned char c = p[0];
-  if (c < 0x80) { *cp = c; return 1; }
-  auto cont = [&](size_t i) { return i < n && (p[i] & 0xC0) == 0x80; };
-  if (c >= 0xC2 && c <= 0xDF) { if (!cont(1)) return 0; *cp = ((c & 0x1Fu) << 6) | (p[1] & 0x3Fu); return 2; }
-  if (c >= 0xE0 && c <= 0xEF) {
-    if (!cont(1) || !cont(2)) return 0;
-    if (c == 0xE0 && p[1] < 0xA0) return 0;
-    if (c == 0xED && p[1] >= 0xA0) return 0;
-    *cp = ((c & 0x0Fu) << 12) | ((p[1] & 0x3Fu) << 6) | (p[2] & 0x3Fu); return 3;
-  }
-  if (c >= 0xF0 && c <= 0xF4) {
-    if (!cont(1) || !cont(2) || !cont(3)) return 0;
-    if (c == 0xF0 && p[1] < 0x90) return 0;
-    if (c == 0xF4 && p[1] >= 0x90) return 0;
-    *cp = ((c & 0x07u) << 18) | ((p[1] & 0x3Fu) << 12) | ((p[2] & 0x3Fu) << 6) | (p[3] & 0x3Fu); return 4;
-  }
-  return 0;
-}
-
 namespace detail {
 typedef std::vector<int32_t> Set;   // sorted class ids
 typedef std::vector<uint64_t> Bits;
@@ -317,20 +297,14 @@ struct Parser {
   const std::vector<std::string>& dict;
   const unsigned char* s; size_t n, i = 0;
   int classes;
-  std::vector<std::pair<uint32_t, int32_t>> single;   // (code point, class) of the one-code-point entries, sorted
+  CodePointTable single;                               // the one-code-point entries (rec_text.h)
   std::vector<Node> nodes;
   std::vector<Set> atoms;                              // unique class sets
   std::map<Set, int> atom_id;
   int positions = 0, depth = 0;
 
-  Parser(const std::vector<std::string>& d, const char* utf8, size_t len) : dict(d), s((const unsigned char*)utf8), n(len), classes((int)d.size()) {
-    for (int c = 1; c < classes; c++) {   // (class 0 is the blank, whatever its placeholder text)
-      const std::string& e = dict[(size_t)c];
-      uint32_t cp;
-      if (!e.empty() && (size_t)utf8_strict((const unsigned char*)e.data(), e.size(), &cp) == e.size()) single.push_back({cp, c});
-    }
-    std::sort(single.begin(), single.end());
-  }
+  Parser(const std::vector<std::string>& d, const char* utf8, size_t len)
+      : dict(d), s((const unsigned char*)utf8), n(len), classes((int)d.size()), single(d) {}
   [[noreturn]] void fail(int code, const std::string& what, size_t at) const {
     throw Fail{code, "pattern: " + what + " (byte offset " + std::to_string(at) + ")"};
   }
@@ -341,7 +315,7 @@ struct Parser {
   }
   uint32_t next_cp() {   // the code point at i, consumed
     uint32_t cp;
-    const int k = utf8_strict(s + i, n - i, &cp);
+    const int k = utf8_decode_strict(s + i, n - i, &cp);
     if (k == 0) fail(ERR_UTF8, "the text is not valid UTF-8", i);
     i += (size_t)k;
     return cp;
@@ -364,16 +338,13 @@ struct Parser {
     return node(ATOM, -1, -1, it->second);
   }
   void add_cp(Set& out, uint32_t cp, size_t at) const {
-    auto lo = std::lower_bound(single.begin(), single.end(), std::make_pair(cp, (int32_t)0));
-    if (lo == single.end() || lo->first != cp) fail(ERR_INVALID, uplus(cp) + " matches no dictionary entry", at);
-    for (; lo != single.end() && lo->first == cp; ++lo) out.push_back(lo->second);
+    if (!single.all(cp, [&](int32_t c) { out.push_back(c); })) fail(ERR_INVALID, uplus(cp) + " matches no dictionary entry", at);
   }
   void add_range(Set& out, uint32_t a, uint32_t z, size_t at_a, size_t at_z) const {
     Set probe;
     add_cp(probe, a, at_a); add_cp(probe, z, at_z);   // (both ends must exist)
     if (a > z) fail(ERR_INVALID, "syntax error: the range " + uplus(a) + "-" + uplus(z) + " is reversed", at_a);
-    for (auto lo = std::lower_bound(single.begin(), single.end(), std::make_pair(a, (int32_t)0)); lo != single.end() && lo->first <= z; ++lo)
-      out.push_back(lo->second);
+    for (const CodePointTable::Entry* e = single.from(a); e != single.end() && e->first <= z; ++e) out.push_back(e->second);
   }
   int number(size_t at) {   // decimal digits at i
     if (i >= n || s[i] < '0' || s[i] > '9') fail(ERR_INVALID, "syntax error: a number is expected", i);

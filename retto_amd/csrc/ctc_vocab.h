@@ -132,7 +132,10 @@ struct Ids {
 struct Vocab {
   int classes = 0, n_words = 0, n_word_classes = 0, variants_dropped = 0;
   std::vector<Node> nodes; std::vector<Arc> arcs; std::vector<uint32_t> mask; std::vector<int32_t> root;
-  View view() const { return View{nodes.data(), arcs.data(), mask.data(), root.data(), classes, (int32_t)nodes.size(), (int32_t)arcs.size()}; }
+  // the View with every table where put(table) says it is: the one place that lists the tables.  (A store's put uploads them.)
+  template <class Put>
+  View view_through(Put&& put) const { return View{put(nodes), put(arcs), put(mask), put(root), classes, (int32_t)nodes.size(), (int32_t)arcs.size()}; }
+  View view() const { return view_through([](const auto& table) { return table.data(); }); }
 };
 
 // The id form (n words; a word given twice counts once) -> m.  Returns OK, or the code with msg, which names the word.

@@ -1,286 +1,13 @@
-// The rec network's CTC tail and what feeds it: the dictionary, charset and lexicon text compilers, the session's charset and
-// lexicon stores, the pattern pass (ctc_pattern.h), and rt_lane::rec_tail -- the one launch sequence behind the net that the
-// pipeline (session.cpp rec_groups) and the debug hooks (api_debug.cpp rt_debug_ctc_*) both run, on the tables of rec_tail_plan.h.
+// The rec network's CTC tail: rt_lane::rec_tail -- the one launch sequence behind the net that the pipeline (session.cpp
+// rec_groups) and the debug hooks (api_ctc.cpp rt_debug_ctc_*) both run, on the tables of rec_tail_plan.h -- and the create calls
+// of the session's rec stores, which put on the device what the text compilers of rec_text.h give.
 #include "session.h"
 
-#include <cstdio>
 #include <cstring>
-#include <unordered_map>
+
+#include "rec_text.h"
 
 using namespace rt;
-
-// ---------------------------------------------------------------------------
-// RecCharacter::new (rec_processor.rs:29-46): String::from_utf8(bytes)? -> lines().map(|l| l.trim()) -> push " "
-// -> insert "blank" at 0.  Rust semantics, restated exactly:
-//  * String::from_utf8 is strict: overlong forms, surrogates (U+D800-DFFF) and code points above U+10FFFF
-//    are errors (Utf8Error);
-//  * str::lines splits after every '\n', drops that '\n' and one '\r' in front of it; a trailing '\n' does not
-//    open a last empty line;
-//  * str::trim strips every char with the Unicode White_Space property (char::is_whitespace): U+0009-000D,
-//    U+0020, U+0085, U+00A0, U+1680, U+2000-200A, U+2028, U+2029, U+202F, U+205F, U+3000 -- a dictionary line
-//    that holds only U+3000 becomes the empty string.
-// ---------------------------------------------------------------------------
-namespace rt {
-static int utf8_decode_strict(const unsigned char* p, size_t n, uint32_t* cp) {  // bytes consumed, 0 = invalid
-  if (n == 0) return 0;
-  const unsigned char c = p[0];
-  if (c < 0x80) { *cp = c; return 1; }
-  auto cont = [&](size_t i) { return i < n && (p[i] & 0xC0) == 0x80; };
-  if (c >= 0xC2 && c <= 0xDF) { if (!cont(1)) return 0; *cp = ((c & 0x1F) << 6) | (p[1] & 0x3F); return 2; }
-  if (c >= 0xE0 && c <= 0xEF) {
-    if (!cont(1) || !cont(2)) return 0;
-    if (c == 0xE0 && p[1] < 0xA0) return 0;   // overlong
-    if (c == 0xED && p[1] >= 0xA0) return 0;  // surrogate
-    *cp = ((c & 0x0F) << 12) | ((p[1] & 0x3F) << 6) | (p[2] & 0x3F); return 3;
-  }
-  if (c >= 0xF0 && c <= 0xF4) {
-    if (!cont(1) || !cont(2) || !cont(3)) return 0;
-    if (c == 0xF0 && p[1] < 0x90) return 0;   // overlong
-    if (c == 0xF4 && p[1] >= 0x90) return 0;  // above U+10FFFF
-    *cp = ((c & 0x07) << 18) | ((p[1] & 0x3F) << 12) | ((p[2] & 0x3F) << 6) | (p[3] & 0x3F); return 4;
-  }
-  return 0;  // 0x80-0xC1 (continuation / overlong lead), 0xF5-0xFF
-}
-static bool is_rust_whitespace(uint32_t c) {
-  return (c >= 0x09 && c <= 0x0D) || c == 0x20 || c == 0x85 || c == 0xA0 || c == 0x1680 || (c >= 0x2000 && c <= 0x200A) ||
-         c == 0x2028 || c == 0x2029 || c == 0x202F || c == 0x205F || c == 0x3000;
-}
-std::vector<std::string> load_dictionary(const std::vector<uint8_t>& bytes) {
-  const unsigned char* p = bytes.data();
-  const size_t n = bytes.size();
-  std::vector<std::string> dict;
-  dict.push_back("blank");
-  size_t pos = 0;
-  while (pos < n) {
-    // one line: [pos, e) without its terminator
-    size_t e = pos;
-    while (e < n && p[e] != '\n') e++;
-    size_t le = e;
-    if (e < n && le > pos && p[le - 1] == '\r') le--;
-    // trim: first / last non-whitespace char, validating as we decode
-    size_t first = std::string::npos, last_end = 0;
-    for (size_t i = pos; i < le;) {
-      uint32_t cp;
-      int k = utf8_decode_strict(p + i, le - i, &cp);
-      if (k == 0) throw RtError(RT_ERR_UTF8, "dictionary is not valid UTF-8 (byte offset " + std::to_string(i) + ")");
-      if (!is_rust_whitespace(cp)) { if (first == std::string::npos) first = i; last_end = i + (size_t)k; }
-      i += (size_t)k;
-    }
-    dict.push_back(first == std::string::npos ? std::string() : std::string((const char*)p + first, last_end - first));
-    if (e >= n) break;
-    pos = e + 1;
-  }
-  dict.push_back(" ");
-  return dict;
-}
-std::vector<uint32_t> compile_charset(const std::vector<std::string>& dict, const char* utf8, size_t len, const int32_t* ids,
-                                      int n_ids) {
-  const int classes = (int)dict.size();
-  std::vector<uint32_t> mask((size_t)cs::mask_words(classes), 0u);
-  auto add = [&](int c) { mask[(size_t)c >> 5] |= 1u << (c & 31); };
-  add(0);
-  const unsigned char* p = (const unsigned char*)utf8;
-  for (size_t i = 0; i < len;) {
-    uint32_t cp;
-    const int k = utf8_decode_strict(p + i, len - i, &cp);
-    if (k == 0) throw RtError(RT_ERR_UTF8, "charset: the text is not valid UTF-8 (byte offset " + std::to_string(i) + ")");
-    bool any = false;
-    for (int c = 1; c < classes; c++)   // (class 0 is the blank, whatever its placeholder text)
-      if (dict[(size_t)c].size() == (size_t)k && memcmp(dict[(size_t)c].data(), p + i, (size_t)k) == 0) { add(c); any = true; }
-    if (!any) {
-      char b[64];
-      snprintf(b, sizeof b, "charset: U+%04X matches no dictionary entry", (unsigned)cp);
-      throw RtError(RT_ERR_INVALID, b);
-    }
-    i += (size_t)k;
-  }
-  for (int j = 0; j < n_ids; j++) {
-    if (ids[j] < 0 || ids[j] >= classes)
-      throw RtError(RT_ERR_INVALID, "charset: class id " + std::to_string(ids[j]) + " is outside [0, " + std::to_string(classes) + ")");
-    add(ids[j]);
-  }
-  return mask;
-}
-void compile_lexicon(const std::vector<std::string>& dict, const char* utf8, size_t len, const int32_t* ids,
-                     const int32_t* entry_lens, int n_id_entries, std::vector<int32_t>& ids_out, std::vector<int32_t>& lens_out) {
-  const int classes = (int)dict.size();
-  ids_out.clear(); lens_out.clear();
-  // every class whose whole entry is one code point, under its bytes: the lowest id wins (class 0 is the blank, whatever its
-  // placeholder text)
-  std::unordered_map<std::string, int> one;
-  for (int c = classes - 1; c >= 1; c--) {
-    const std::string& d = dict[(size_t)c];
-    uint32_t cp;
-    if (!d.empty() && (size_t)utf8_decode_strict((const unsigned char*)d.data(), d.size(), &cp) == d.size()) one[d] = c;
-  }
-  auto entry_done = [&](int n) {
-    if (n > lx::MAX_LEN)
-      throw RtError(RT_ERR_INVALID, "lexicon: entry " + std::to_string(lens_out.size()) + " has " + std::to_string(n) +
-                                        " tokens, more than RT_LEXICON_MAX_LEN (" + std::to_string(lx::MAX_LEN) + ")");
-    if ((int)lens_out.size() >= lx::MAX_ENTRIES)
-      throw RtError(RT_ERR_CAPACITY, "lexicon: more than RT_LEXICON_MAX_ENTRIES (" + std::to_string(lx::MAX_ENTRIES) + ") entries");
-    lens_out.push_back(n);
-  };
-  const unsigned char* p = (const unsigned char*)utf8;
-  for (size_t pos = 0; pos < len;) {
-    size_t e = pos;
-    while (e < len && p[e] != '\n') e++;
-    size_t le = e;
-    if (e < len && le > pos && p[le - 1] == '\r') le--;
-    size_t first = std::string::npos, last_end = 0;   // (trimmed as a dictionary line is)
-    for (size_t i = pos; i < le;) {
-      uint32_t cp;
-      const int k = utf8_decode_strict(p + i, le - i, &cp);
-      if (k == 0) throw RtError(RT_ERR_UTF8, "lexicon: the text is not valid UTF-8 (byte offset " + std::to_string(i) + ")");
-      if (!is_rust_whitespace(cp)) { if (first == std::string::npos) first = i; last_end = i + (size_t)k; }
-      i += (size_t)k;
-    }
-    if (first != std::string::npos) {
-      int n = 0;
-      for (size_t i = first; i < last_end;) {
-        uint32_t cp;
-        const int k = utf8_decode_strict(p + i, last_end - i, &cp);
-        const auto it = one.find(std::string((const char*)p + i, (size_t)k));
-        if (it == one.end()) {
-          char b[96];
-          snprintf(b, sizeof b, "lexicon: U+%04X in entry %zu matches no dictionary entry", (unsigned)cp, lens_out.size());
-          throw RtError(RT_ERR_INVALID, b);
-        }
-        ids_out.push_back(it->second); n++;
-        i += (size_t)k;
-      }
-      entry_done(n);
-    }
-    pos = e + 1;
-  }
-  size_t o = 0;
-  for (int j = 0; j < n_id_entries; j++) {
-    const int n = entry_lens[j];
-    if (n <= 0) throw RtError(RT_ERR_INVALID, "lexicon: entry " + std::to_string(lens_out.size()) + " is empty");
-    for (int i = 0; i < n && i < lx::MAX_LEN; i++) {
-      const int c = ids[o + (size_t)i];
-      if (c < 1 || c >= classes)
-        throw RtError(RT_ERR_INVALID, "lexicon: class id " + std::to_string(c) + " in entry " + std::to_string(lens_out.size()) +
-                                          " is outside [1, " + std::to_string(classes) + ")");
-      ids_out.push_back(c);
-    }
-    entry_done(n);
-    o += (size_t)n;
-  }
-  if (lens_out.empty()) throw RtError(RT_ERR_INVALID, "lexicon: no entry");
-}
-void compile_vocab(const std::vector<std::string>& dict, const char* utf8, size_t len, const int32_t* ids, const int32_t* word_lens,
-                   int n_id_words, int flags, vc::Ids& out, int* variants_dropped) {
-  const int classes = (int)dict.size();
-  out = vc::Ids{};
-  *variants_dropped = 0;
-  if (flags & ~vc::CASE_VARIANTS) {
-    char b[64];
-    snprintf(b, sizeof b, "vocab: unknown flag bits 0x%x", (unsigned)(flags & ~vc::CASE_VARIANTS));
-    throw RtError(RT_ERR_INVALID, b);
-  }
-  // every class whose whole entry is one code point, under its code point: the lowest id wins (as compile_lexicon)
-  std::unordered_map<uint32_t, int> one;
-  for (int c = classes - 1; c >= 1; c--) {
-    const std::string& d = dict[(size_t)c];
-    uint32_t cp;
-    if (!d.empty() && (size_t)utf8_decode_strict((const unsigned char*)d.data(), d.size(), &cp) == d.size()) one[cp] = c;
-  }
-  std::unordered_map<std::string, int> seen;   // a word given twice is one word: the id form holds its first occurrence
-  auto add = [&](const std::vector<int32_t>& w) {
-    if (!seen.emplace(std::string((const char*)w.data(), w.size() * sizeof(int32_t)), 0).second) return;
-    if (out.n() >= vc::MAX_WORDS)
-      throw RtError(RT_ERR_CAPACITY, "vocab: more than RT_VOCAB_MAX_WORDS (" + std::to_string(vc::MAX_WORDS) + ") words");
-    out.ids.insert(out.ids.end(), w.begin(), w.end()); out.lens.push_back((int32_t)w.size());
-  };
-  // the code points -> ids; false (nothing appended) where the dictionary lacks one, *missing = that code point
-  auto to_ids = [&](const std::vector<uint32_t>& cps, std::vector<int32_t>& w, uint32_t* missing) {
-    w.clear();
-    for (uint32_t cp : cps) {
-      const auto it = one.find(cp);
-      if (it == one.end()) { *missing = cp; return false; }
-      w.push_back(it->second);
-    }
-    return true;
-  };
-  auto lower = [](uint32_t c) { return c >= 'a' && c <= 'z'; };
-  const unsigned char* p = (const unsigned char*)utf8;
-  std::vector<uint32_t> cps, var;
-  std::vector<int32_t> w;
-  size_t word = 0;   // (the line's number among the lines that hold a word, for the messages)
-  for (size_t pos = 0; pos < len; word++) {
-    size_t e = pos;
-    while (e < len && p[e] != '\n') e++;
-    size_t le = e;
-    if (e < len && le > pos && p[le - 1] == '\r') le--;
-    size_t first = std::string::npos, last_end = 0;   // (trimmed as a dictionary line is)
-    for (size_t i = pos; i < le;) {
-      uint32_t cp;
-      const int k = utf8_decode_strict(p + i, le - i, &cp);
-      if (k == 0) throw RtError(RT_ERR_UTF8, "vocab: the text is not valid UTF-8 (byte offset " + std::to_string(i) + ")");
-      if (!is_rust_whitespace(cp)) { if (first == std::string::npos) first = i; last_end = i + (size_t)k; }
-      i += (size_t)k;
-    }
-    pos = e + 1;
-    if (first == std::string::npos) { word--; continue; }
-    const std::string text((const char*)p + first, std::min<size_t>(last_end - first, 48));   // (the start of the word, for the messages)
-    cps.clear();
-    for (size_t i = first; i < last_end;) {
-      uint32_t cp;
-      i += (size_t)utf8_decode_strict(p + i, last_end - i, &cp);
-      cps.push_back(cp);
-    }
-    if ((int)cps.size() > vc::MAX_LEN)
-      throw RtError(RT_ERR_INVALID, "vocab: word " + std::to_string(word) + " (\"" + text + "...\") has " + std::to_string(cps.size()) +
-                                        " code points, more than RT_VOCAB_MAX_LEN (" + std::to_string(vc::MAX_LEN) + ")");
-    uint32_t missing = 0;
-    if (!to_ids(cps, w, &missing)) {
-      char b[160];
-      snprintf(b, sizeof b, "vocab: U+%04X in word %zu (\"%s\") matches no dictionary entry", (unsigned)missing, word, text.c_str());
-      throw RtError(RT_ERR_INVALID, b);
-    }
-    add(w);
-    if (!(flags & vc::CASE_VARIANTS)) continue;
-    for (int form = 0; form < 2; form++) {   // the first ASCII letter upper-cased; all of them
-      var = cps;
-      bool changed = false;
-      for (uint32_t& c : var)
-        if (lower(c)) { c -= 'a' - 'A'; changed = true; if (form == 0) break; }
-        else if (form == 0 && c >= 'A' && c <= 'Z') break;   // (its first letter is a capital already)
-      if (!changed) continue;
-      if (to_ids(var, w, &missing)) add(w); else (*variants_dropped)++;
-    }
-  }
-  size_t o = 0;
-  for (int j = 0; j < n_id_words; j++) {
-    const int n = word_lens[j];
-    if (n <= 0) throw RtError(RT_ERR_INVALID, "vocab: id word " + std::to_string(j) + " is empty");
-    if (n > vc::MAX_LEN)
-      throw RtError(RT_ERR_INVALID, "vocab: id word " + std::to_string(j) + " has " + std::to_string(n) + " ids, more than RT_VOCAB_MAX_LEN (" +
-                                        std::to_string(vc::MAX_LEN) + ")");
-    w.assign(ids + o, ids + o + (size_t)n);
-    for (int c : w) {
-      if (c == 0) throw RtError(RT_ERR_INVALID, "vocab: id word " + std::to_string(j) + ": the blank (class 0) is not a token");
-      if (c < 0 || c >= classes)
-        throw RtError(RT_ERR_INVALID, "vocab: class id " + std::to_string(c) + " in id word " + std::to_string(j) + " is outside [1, " +
-                                          std::to_string(classes) + ")");
-    }
-    add(w);
-    o += (size_t)n;
-  }
-  if (out.lens.empty()) throw RtError(RT_ERR_INVALID, "vocab: no word at all");
-}
-vc::Vocab compile_vocab(const std::vector<std::string>& dict, const char* utf8, size_t len, const int32_t* ids, const int32_t* word_lens,
-                        int n_id_words, int flags, vc::Ids& f) {
-  int dropped = 0;
-  compile_vocab(dict, utf8, len, ids, word_lens, n_id_words, flags, f, &dropped);
-  vc::Vocab m; std::string msg;
-  const int rc = vc::compile((int)dict.size(), f, m, msg);
-  if (rc != vc::OK) throw RtError(rc, msg);
-  m.variants_dropped = dropped;
-  return m;
-}
-}  // namespace rt
 
 // ---- the tail of one rec group (session.h "the rec network's CTC tail") ----
 namespace {
@@ -356,12 +83,12 @@ struct LinePass {
     }
   }
 };
-// one table of a store (rt_entry_store, rt_patterns) into a device allocation of its own, with a blocking copy (an empty one gets
-// one element and no copy); the store's holder frees it
-template <typename T>
-void upload_table(const T** d, const std::vector<T>& v) {
+// one table of a store into a device allocation of its own (*d: a const T*, or a rt_view_store's untyped slot), with a blocking
+// copy (an empty one gets one element and no copy); the store's holder frees it
+template <typename P, typename T>
+void upload_table(P** d, const std::vector<T>& v) {
   RT_HIP_CHECK(hipMalloc((void**)d, std::max<size_t>(v.size(), 1) * sizeof(T)));
-  if (!v.empty()) RT_HIP_CHECK(hipMemcpy(const_cast<T*>(*d), v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
+  if (!v.empty()) RT_HIP_CHECK(hipMemcpy((void*)*d, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
 }
 }  // namespace
 
@@ -572,25 +299,29 @@ int rt_session::keywords_create(const char* utf8, size_t len, const int32_t* ids
   return id;
 }
 
-// ---- the language models (session.h rt_lms) ----
-namespace {
-void free_view(const lm::View& v) {
-  const void* p[] = {v.uni, v.states, v.arcs};
-  for (const void* q : p) if (q) (void)hipFree(const_cast<void*>(q));
-}
-}  // namespace
-rt_lms::~rt_lms() { for (const lm::View& v : dev) free_view(v); }
-int rt_lms::add(lm::Model m) {
+// ---- the language models and the vocabularies (session.h rt_view_store) ----
+template <class Model, class View>
+rt_view_store<Model, View>::~rt_view_store() { for (void* q : owned) (void)hipFree(q); }
+template <class Model, class View>
+int rt_view_store<Model, View>::add(Model m) {
   host.reserve(host.size() + 1); dev.reserve(dev.size() + 1);   // (so that nothing behind the copies throws)
-  std::unique_ptr<lm::Model> h(new lm::Model(std::move(m)));
-  lm::View v = h->view();
-  v.uni = nullptr; v.states = nullptr; v.arcs = nullptr;
+  std::unique_ptr<Model> h(new Model(std::move(m)));
+  const size_t held = owned.size();
   try {
-    upload_table(&v.uni, h->uni); upload_table(&v.states, h->states); upload_table(&v.arcs, h->arcs);
-  } catch (...) { free_view(v); throw; }
-  host.push_back(std::move(h)); dev.push_back(v);
+    dev.push_back(h->view_through([&](const auto& table) {
+      owned.push_back(nullptr);   // (its slot first: an allocation whose copy throws is freed below too)
+      upload_table(&owned.back(), table);
+      return (decltype(table.data()))owned.back();
+    }));
+  } catch (...) {
+    for (; owned.size() > held; owned.pop_back()) (void)hipFree(owned.back());
+    throw;
+  }
+  host.push_back(std::move(h));
   return (int)host.size() - 1;
 }
+template struct rt_view_store<lm::Model, lm::View>;
+template struct rt_view_store<vc::Vocab, vc::View>;
 int rt_session::lm_create(const char* arpa, size_t len, float oov_log10) {
   if ((int)lms->host.size() >= lm::MAX_LMS)
     throw RtError(RT_ERR_CAPACITY, "rt_lm_create: the session holds RT_MAX_LMS (" + std::to_string(lm::MAX_LMS) + ") language models already");
@@ -601,25 +332,6 @@ int rt_session::lm_create(const char* arpa, size_t len, float oov_log10) {
   return lms->add(std::move(m));
 }
 
-// ---- the vocabularies (session.h rt_vocabs) ----
-namespace {
-void free_view(const vc::View& v) {
-  const void* p[] = {v.nodes, v.arcs, v.mask, v.root};
-  for (const void* q : p) if (q) (void)hipFree(const_cast<void*>(q));
-}
-}  // namespace
-rt_vocabs::~rt_vocabs() { for (const vc::View& v : dev) free_view(v); }
-int rt_vocabs::add(vc::Vocab m) {
-  host.reserve(host.size() + 1); dev.reserve(dev.size() + 1);   // (so that nothing behind the copies throws)
-  std::unique_ptr<vc::Vocab> h(new vc::Vocab(std::move(m)));
-  vc::View v = h->view();
-  v.nodes = nullptr; v.arcs = nullptr; v.mask = nullptr; v.root = nullptr;
-  try {
-    upload_table(&v.nodes, h->nodes); upload_table(&v.arcs, h->arcs); upload_table(&v.mask, h->mask); upload_table(&v.root, h->root);
-  } catch (...) { free_view(v); throw; }
-  host.push_back(std::move(h)); dev.push_back(v);
-  return (int)host.size() - 1;
-}
 int rt_session::vocab_create(const char* utf8, size_t len, const int32_t* ids, const int32_t* word_lens, int n_id_words, int flags) {
   if ((int)vocabs->host.size() >= vc::MAX_VOCABS)
     throw RtError(RT_ERR_CAPACITY, "rt_vocab_create: the session holds RT_MAX_VOCABS (" + std::to_string(vc::MAX_VOCABS) + ") vocabularies already");

@@ -6,6 +6,7 @@
 
 #include <charconv>
 #include "onnx_import.h"
+#include "rec_text.h"
 
 #include <algorithm>
 #include <cmath>

@@ -255,27 +255,21 @@ struct rt_keywords : rt_entry_store {
   ~rt_keywords() { if (d_min) (void)hipFree(const_cast<float*>(d_min)); }
 };
 
-// The session's rec language models (ctc_lm.h), shared with the helper lanes.  Model k (0-based, rt_lm_create's handle) is
-// host[k], whose three tables sit on the device as dev[k], uploaded once at creation and kept until the session goes.  Only
-// changed while no ticket is in flight (rt_lm_create is a guarded call), with blocking copies.
-struct rt_lms {
-  std::vector<std::unique_ptr<rt::lm::Model>> host;
-  std::vector<rt::lm::View> dev;
-  // the model's tables onto the current device; returns its handle.  Whatever throws leaves the store as it was.
-  int add(rt::lm::Model m);
-  ~rt_lms();
+// The session's rec language models (ctc_lm.h) and rec vocabularies (ctc_vocab.h), shared with the helper lanes: one store over
+// the kind's compiled form and the view of its tables.  Item k (0-based, the handle of rt_lm_create / rt_vocab_create) is
+// host[k], whose tables (Model::view_through names them) sit on the device as dev[k], uploaded once at creation and kept until
+// the session goes.  Only changed while no ticket is in flight (the create calls are guarded), with blocking copies.
+template <class Model, class View>
+struct rt_view_store {
+  std::vector<std::unique_ptr<Model>> host;
+  std::vector<View> dev;
+  std::vector<void*> owned;   // the device allocations behind dev, freed with the store
+  // the item's tables onto the current device; returns its handle.  Whatever throws leaves the store as it was.
+  int add(Model m);
+  ~rt_view_store();
 };
-
-// The session's rec vocabularies (ctc_vocab.h), shared with the helper lanes.  Vocabulary k (0-based, rt_vocab_create's handle) is
-// host[k], whose four tables sit on the device as dev[k], uploaded once at creation and kept until the session goes.  Only
-// changed while no ticket is in flight (rt_vocab_create is a guarded call), with blocking copies.
-struct rt_vocabs {
-  std::vector<std::unique_ptr<rt::vc::Vocab>> host;
-  std::vector<rt::vc::View> dev;
-  // the vocabulary's tables onto the current device; returns its handle.  Whatever throws leaves the store as it was.
-  int add(rt::vc::Vocab m);
-  ~rt_vocabs();
-};
+typedef rt_view_store<rt::lm::Model, rt::lm::View> rt_lms;
+typedef rt_view_store<rt::vc::Vocab, rt::vc::View> rt_vocabs;
 
 // internal to the library (never accepted from a caller): pages already in HBM, det map overrides still host pointers
 #define RT_MEM_STAGED_MAPS_HOST 3
@@ -530,30 +524,3 @@ struct rt_session : rt_lane {
 
 rt_session* rt_session_create(const rt_config* cfg);
 std::string rt_format_f32_impl(float v);  // serde_json / ryu form of an f32
-namespace rt {
-// (the three below live in rec_tail.cpp)
-// RecCharacter::new (rec_processor.rs:29-46) with Rust's from_utf8 / lines / trim semantics
-std::vector<std::string> load_dictionary(const std::vector<uint8_t>& bytes);
-// A rec charset (ctc_charset.h) as its mask of cs::mask_words(dict.size()) words: the blank, every dictionary class whose whole
-// entry is one code point of utf8 [len] (duplicates all join; U+0020 is the appended " "), and ids [n_ids].  Throws RT_ERR_UTF8
-// for malformed text, RT_ERR_INVALID for a code point that matches no entry ("U+XXXX") or an id outside [0, dict.size()).
-std::vector<uint32_t> compile_charset(const std::vector<std::string>& dict, const char* utf8, size_t len, const int32_t* ids,
-                                      int n_ids);
-// A rec lexicon (ctc_lexicon.h) as flat class ids and one length per entry: the lines of utf8 [len] (split and trimmed as the
-// dictionary's lines are; empty lines skipped), each code point the LOWEST class id whose whole dictionary entry is that code
-// point (U+0020 is the appended " "), then n_id_entries entries of entry_lens[i] ids each, consecutive in ids.  Throws RT_ERR_UTF8
-// for malformed text; RT_ERR_INVALID for a code point that matches no entry ("U+XXXX", naming the entry), an id outside
-// [1, dict.size()), an empty id entry, an entry longer than lx::MAX_LEN, or no entry at all; RT_ERR_CAPACITY past lx::MAX_ENTRIES.
-void compile_lexicon(const std::vector<std::string>& dict, const char* utf8, size_t len, const int32_t* ids,
-                     const int32_t* entry_lens, int n_id_entries, std::vector<int32_t>& ids_out, std::vector<int32_t>& lens_out);
-// A vocabulary's words (ctc_vocab.h) in their id form: the lines of utf8 [len], split, trimmed and mapped as compile_lexicon maps
-// them -- with flags & vc::CASE_VARIANTS each followed by the word with its first ASCII letter upper-cased and the word with all
-// of them upper-cased, a variant with a code point the dictionary lacks being left out and counted -- then n_id_words words of
-// word_lens[i] ids each.  A word already there is not added again.  Throws RT_ERR_UTF8 for malformed text; RT_ERR_INVALID, naming
-// the word, for a code point that matches no entry ("U+XXXX"), the blank or an id outside [1, dict.size()), an empty or over-long
-// word, no word at all, unknown flag bits; RT_ERR_CAPACITY past vc::MAX_WORDS.  The second form also compiles it (vc::compile).
-void compile_vocab(const std::vector<std::string>& dict, const char* utf8, size_t len, const int32_t* ids, const int32_t* word_lens,
-                   int n_id_words, int flags, vc::Ids& out, int* variants_dropped);
-vc::Vocab compile_vocab(const std::vector<std::string>& dict, const char* utf8, size_t len, const int32_t* ids, const int32_t* word_lens,
-                        int n_id_words, int flags, vc::Ids& f);
-}

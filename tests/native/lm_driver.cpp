@@ -10,7 +10,7 @@
 //   lm_driver beam IN OUT
 //     IN: int32 N, n_lines, beam, nbest, n, then float32 oov, alpha, beta, then tokens_per_line [n_lines], ngram_lens [n], ngram_ids,
 //     logp [n], backoff [n], z5 [rows][120], W [120][N], bias [N], then the initial counts [n_lines], beams [n_lines][nbest] (2 words
-//     each), tokens [rows * nbest], lm [n_lines][nbest] (2 words each).  hr::BeamLmArgs' check and hr::beam_lm_ref on them
+//     each), tokens [rows * nbest], lm [n_lines][nbest] (2 words each).  hr::BeamArgs' check in its LM form and hr::beam_ref on them
 //     -> OUT: the four outputs in that order; stdout: "ok" or "error: <message>"
 #include <cstdio>
 #include <cstdlib>
@@ -117,12 +117,11 @@ int main(int argc, char** argv) {
     std::vector<rt_beam> beams((size_t)n_lines * nbest);
     std::vector<rt_beam_lm> lms((size_t)n_lines * nbest);
     take(counts.data(), counts.size() * 4); take(beams.data(), beams.size() * 8); take(tokens.data(), tokens.size() * 4); take(lms.data(), lms.size() * 8);
-    hr::BeamLmArgs a;
-    static_cast<hr::Head&>(a) = hr::Head{z.data(), W.data(), b.data(), N, tpl.data(), n_lines};
-    a.beam = beam; a.nbest = nbest; a.counts_out = counts.data(); a.beams_out = beams.data(); a.tokens_out = tokens.data();
+    hr::BeamArgs a{{z.data(), W.data(), b.data(), N, tpl.data(), n_lines}};
+    a.form = hr::BeamArgs::LM; a.beam = beam; a.nbest = nbest; a.counts_out = counts.data(); a.beams_out = beams.data(); a.tokens_out = tokens.data();
     a.ids = {ids.data(), lens.data(), logp.data(), bo.data(), n, w[0]}; a.alpha = w[1]; a.beta = w[2]; a.lm_out = lms.data();
     const std::string bad = a.error();
-    if (bad.empty()) hr::beam_lm_ref(a);
+    if (bad.empty()) hr::beam_ref(a);
     std::ofstream out(argv[3], std::ios::binary);
     out.write((const char*)counts.data(), (std::streamsize)(counts.size() * 4)); out.write((const char*)beams.data(), (std::streamsize)(beams.size() * 8));
     out.write((const char*)tokens.data(), (std::streamsize)(tokens.size() * 4)); out.write((const char*)lms.data(), (std::streamsize)(lms.size() * 8));

@@ -13,7 +13,7 @@
 //     IN: int32 N, n_lines, beam, nbest, n, n_words, then float32 oov, alpha, beta, gamma, then tokens_per_line [n_lines], ngram_lens
 //     [n], word_lens [n_words], ngram_ids, logp [n], backoff [n], word_ids, z5 [rows][120], W [120][N], bias [N], then the initial
 //     counts [n_lines], beams [n_lines][nbest] (2 words each), tokens [rows * nbest], lm [n_lines][nbest], vocab [n_lines][nbest] (2
-//     words each).  hr::BeamVocabArgs' check and hr::beam_vocab_ref on them -> OUT: the five outputs in that order; stdout: "ok" or
+//     words each).  hr::BeamArgs' check in its VOCAB form and hr::beam_ref on them -> OUT: the five outputs in that order; stdout: "ok" or
 //     "error: <message>"
 #include <cstdio>
 #include <cstdlib>
@@ -131,13 +131,12 @@ int main(int argc, char** argv) {
     std::vector<rt_beam_vocab> vocs((size_t)n_lines * nbest);
     r.take(counts.data(), counts.size() * 4); r.take(beams.data(), beams.size() * 8); r.take(tokens.data(), tokens.size() * 4);
     r.take(lms.data(), lms.size() * 8); r.take(vocs.data(), vocs.size() * 8);
-    hr::BeamVocabArgs a;
-    static_cast<hr::Head&>(a) = hr::Head{z.data(), W.data(), b.data(), N, tpl.data(), n_lines};
-    a.beam = beam; a.nbest = nbest; a.counts_out = counts.data(); a.beams_out = beams.data(); a.tokens_out = tokens.data();
+    hr::BeamArgs a{{z.data(), W.data(), b.data(), N, tpl.data(), n_lines}};
+    a.form = hr::BeamArgs::VOCAB; a.beam = beam; a.nbest = nbest; a.counts_out = counts.data(); a.beams_out = beams.data(); a.tokens_out = tokens.data();
     a.ids = {ids.data(), lens.data(), logp.data(), bo.data(), n, w[0]}; a.alpha = w[1]; a.beta = w[2]; a.lm_out = lms.data();
     a.words = {wids.data(), wlens.data(), n_words}; a.gamma = w[3]; a.vocab_out = vocs.data();
     const std::string bad = a.error();
-    if (bad.empty()) hr::beam_vocab_ref(a);
+    if (bad.empty()) hr::beam_ref(a);
     std::ofstream out(argv[3], std::ios::binary);
     out.write((const char*)counts.data(), (std::streamsize)(counts.size() * 4)); out.write((const char*)beams.data(), (std::streamsize)(beams.size() * 8));
     out.write((const char*)tokens.data(), (std::streamsize)(tokens.size() * 4)); out.write((const char*)lms.data(), (std::streamsize)(lms.size() * 8));

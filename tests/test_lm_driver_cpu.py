@@ -1,7 +1,7 @@
 """The rec language model's parser, compiler and walk (retto_amd/csrc/ctc_lm.h) and the host beam rule with fusion
 (ctc_host_ref.h) under AddressSanitizer + UBSan: a stand-alone driver (tests/native/lm_driver.cpp, run as a program; nothing is
 loaded into Python under a sanitizer) compiles valid, truncated and byte-mutated ARPA files over exactly sized buffers, and runs
-hr::BeamLmArgs' check and hr::beam_lm_ref on test_ctc_host_driver_cpu.py's shapes -- N = 9 classes, lines of 0, 1, 2, 7 and 40
+hr::BeamArgs' check in its LM form and hr::beam_ref on test_ctc_host_driver_cpu.py's shapes -- N = 9 classes, lines of 0, 1, 2, 7 and 40
 time steps -- whose outputs must be the bytes of the library's rt_debug_ctc_beam_lm_host.  Exit code 0 and an empty stderr
 throughout.  No GPU."""
 import os

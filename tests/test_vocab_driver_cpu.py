@@ -1,7 +1,7 @@
 """The rec vocabulary's compiler and walk (retto_amd/csrc/ctc_vocab.h) and the host beam rule with a word list (ctc_host_ref.h)
 under AddressSanitizer + UBSan: a stand-alone driver (tests/native/vocab_driver.cpp, run as a program; nothing is loaded into
 Python under a sanitizer) compiles seeded and malformed id forms over exactly sized buffers, walks strings and steps from every
-state, those outside the trie included, and runs hr::BeamVocabArgs' check and hr::beam_vocab_ref on test_ctc_host_driver_cpu.py's
+state, those outside the trie included, and runs hr::BeamArgs' check in its VOCAB form and hr::beam_ref on test_ctc_host_driver_cpu.py's
 shapes -- N = 9 classes, lines of 0, 1, 2, 7 and 40 time steps -- whose outputs must be the bytes of the library's
 rt_debug_ctc_beam_vocab_host.  Every input ends in a status code: exit code 0 and an empty stderr throughout.  No GPU."""
 import os
