@@ -978,6 +978,26 @@ RT_API int rt_decode_batch(rt_session* s, const void* const* files, const size_t
                            uint8_t* const* out, int mem, int* on_device);
 RT_API int rt_debug_jpeg_reconstruct(const void* data, size_t len, uint8_t** rgb, int* h, int* w, int* on_device, char* err,
                                      size_t err_cap);
+/* JPEG entropy decoding on the GPU.  rt_set_jpeg_entropy(s, 1): rt_submit_encoded_batch, rt_run_encoded_batch (without a
+ * callback) and rt_decode_batch only parse the headers of a baseline Huffman JPEG page, remove its byte stuffing and upload the
+ * compressed bytes; the page's coefficients are decoded by the kernels of retto_amd/csrc/jpeg_huff.hip straight into the planes
+ * the reconstruction kernels read.  Taken this way: SOF0 / SOF1, 8-bit, one scan carrying all components (interleaved, or one
+ * grey component), a sampling layout of the device path above, restart intervals or none, no marker inside the entropy data but
+ * RSTn in order, a marker behind it.  Every other page -- and a page the kernels flag, because they met something the host decoder
+ * would reject or could not prove their reading equal to the host's -- is decoded by the host as with mode 0 inside the same call,
+ * so pixels, results and error texts are those of mode 0.  rt_run_encoded_batch takes this path only without a callback (the
+ * stages of a ticket are not streamed) and with at least one page; otherwise it decodes on the host as with mode 0, with the same
+ * results.  Mode 0 (host) is the default.  rt_decode_batch's on_device[i] is 2
+ * for a page whose entropy decoding ran on the GPU as well.  rt_jpeg_entropy reads the mode back.
+ *
+ * rt_debug_jpeg_entropy: one page's quantised coefficients, the components' MCU-padded planes back to back in `coefs` (cap
+ * int16 values; NULL: sizes only), decoded by how = 0 the host decoder, 1 the kernels, 2 the kernels' decode step run serially
+ * on the CPU over the prepared stream (no GPU work).  info[9]: [0..2] the planes' sizes in values, [3] the page's flag, [4] its
+ * subsequences, [5] its workgroups, [6] [7] the rounds the synchronise and link passes took (how = 1), [8] 1 when the page was
+ * taken (how = 1, 2: 0 = the preparation refuses it, nothing else is written).  how = 0 and 2 need no session (s may be NULL). */
+RT_API int rt_set_jpeg_entropy(rt_session* s, int mode);
+RT_API int rt_jpeg_entropy(const rt_session* s, int* mode);
+RT_API int rt_debug_jpeg_entropy(rt_session* s, const void* data, size_t len, int how, int16_t* coefs, size_t cap, int* info);
 /* RecCharacter::new (retto-core/src/processor/rec_processor.rs:29-46) on the bytes of ppocr_keys_v1.txt, with
  * Rust's semantics: strict String::from_utf8 (RT_ERR_UTF8 on overlong forms, surrogates, > U+10FFFF), str::lines,
  * str::trim over the Unicode White_Space set (a U+3000-only line becomes ""), "blank" inserted at 0 and " "

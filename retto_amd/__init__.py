@@ -402,6 +402,25 @@ def decode_image(data: bytes) -> np.ndarray:
         lib.rt_buffer_free(out)
 
 
+def debug_jpeg_entropy(data: bytes, how: int, session=None):
+    """rt_debug_jpeg_entropy: (the components' int16 coefficient planes, info) of one JPEG page decoded by how = 0 the host
+    decoder, 1 the kernels (needs ``session``), 2 the kernels' decode step run serially on the CPU over the prepared stream.
+    info: dict with flag, subsequences, workgroups, sync_rounds, link_rounds, taken; planes is None for a page the preparation
+    refuses (how 1, 2)."""
+    data = bytes(data)
+    lib = _lib.load()
+    h = session._hd.h if session is not None else None
+    info = (C.c_int * 9)()
+    _check(lib.rt_debug_jpeg_entropy(h, data, len(data), how, None, 0, info), h)
+    names = ("flag", "subsequences", "workgroups", "sync_rounds", "link_rounds", "taken")
+    if not info[8]:
+        return None, dict(zip(names, list(info)[3:]))
+    sizes = [info[0], info[1], info[2]]
+    buf = np.zeros(sum(sizes), np.int16)
+    _check(lib.rt_debug_jpeg_entropy(h, data, len(data), how, buf.ctypes.data, buf.size, info), h)
+    return [buf[sum(sizes[:c]):sum(sizes[:c + 1])] for c in range(3) if sizes[c]], dict(zip(names, list(info)[3:]))
+
+
 def debug_jpeg_reconstruct(data: bytes):
     """rt_debug_jpeg_reconstruct: the device decode path's host stage plus the reconstruction kernels' arithmetic, run on the
     CPU.  Returns (RGB8 [H,W,3], on_device); on_device False means the device path decodes this file on the host."""
@@ -1238,8 +1257,27 @@ class RettoSession:
         finally:
             self._hd.lib.rt_results_free(r)
 
-    def decode_batch(self, files: Sequence[bytes]):
-        """rt_decode_batch into host memory: (list of RGB8 [H,W,3] pages, list of on_device flags)."""
+    def set_jpeg_entropy(self, mode: int) -> None:
+        """rt_set_jpeg_entropy: 0 = JPEG pages are entropy-decoded on the host (the default), 1 = baseline Huffman pages are
+        entropy-decoded by the kernels of retto_amd/csrc/jpeg_huff.hip (every other page, and a page the kernels flag, goes the
+        host's way inside the same call).  Holds for the encoded-page calls that follow; results and errors do not change."""
+        _check(self._hd.lib.rt_set_jpeg_entropy(self._hd.h, int(mode)), self._hd.h)
+
+    @property
+    def jpeg_entropy(self) -> int:
+        """rt_jpeg_entropy: the mode as set."""
+        v = C.c_int()
+        _check(self._hd.lib.rt_jpeg_entropy(self._hd.h, C.byref(v)), self._hd.h)
+        return v.value
+
+    def debug_jpeg_entropy(self, data: bytes, how: int):
+        """debug_jpeg_entropy (module level) on this session: how = 1 runs the kernels."""
+        return debug_jpeg_entropy(data, how, self)
+
+    def decode_batch(self, files: Sequence[bytes], with_entropy: bool = False):
+        """rt_decode_batch into host memory: (list of RGB8 [H,W,3] pages, list of on_device flags).  with_entropy: a third list,
+        rt_decode_batch's own values: 2 where the page's entropy decoding ran on the GPU as well (rt_set_jpeg_entropy mode 1), 1
+        pixels only, 0 host."""
         n = len(files)
         files = [bytes(f) for f in files]
         ptrs = (C.c_char_p * max(n, 1))(*files); lens = (C.c_size_t * max(n, 1))(*[len(f) for f in files])
@@ -1249,6 +1287,8 @@ class RettoSession:
         pages = [np.empty((hs[i], ws[i], 3), np.uint8) for i in range(n)]
         outs = (C.c_void_p * max(n, 1))(*[p.ctypes.data for p in pages])
         _check(lib.rt_decode_batch(h, ptrs, lens, n, hs, ws, outs, RT_MEM_HOST, dev), h)
+        if with_entropy:
+            return pages, [bool(dev[i]) for i in range(n)], [int(dev[i]) for i in range(n)]
         return pages, [bool(dev[i]) for i in range(n)]
 
     def run_stream(self, image, sender: Callable[[str, list], None]) -> None:

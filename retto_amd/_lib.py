@@ -136,6 +136,7 @@ EXPORTS = [
     "rt_set_det_tiles", "rt_det_tiles", "rt_det_tile_plan", "rt_debug_det_tiles", "rt_debug_arena_high_water", "rt_bench_memcpy_d2d",
     "rt_set_rec_windows", "rt_rec_windows", "rt_rec_window_plan", "rt_results_rec_windows", "rt_debug_rec_windows",
     "rt_set_rec_flip", "rt_rec_flip", "rt_rec_flip_choose", "rt_results_rec_flip", "rt_debug_rec_flip",
+    "rt_set_jpeg_entropy", "rt_jpeg_entropy", "rt_debug_jpeg_entropy",
 ]
 
 STAGE_CALLBACK = C.CFUNCTYPE(None, C.c_void_p, C.c_int, C.c_int, C.c_char_p)  # rt_stage_callback
@@ -423,5 +424,8 @@ def load():
     lib.rt_rec_flip_choose.argtypes = [C.c_int, C.c_float, C.c_int, C.c_float]
     lib.rt_results_rec_flip.argtypes = [C.c_void_p, C.c_int, C.c_int, P(C.c_float), P(C.c_float)]
     lib.rt_debug_rec_flip.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_float] + [C.c_void_p] * 9
+    lib.rt_set_jpeg_entropy.argtypes = [C.c_void_p, C.c_int]
+    lib.rt_jpeg_entropy.argtypes = [C.c_void_p, P(C.c_int)]
+    lib.rt_debug_jpeg_entropy.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t, C.c_int, C.c_void_p, C.c_size_t, P(C.c_int)]
     _lib = lib
     return lib

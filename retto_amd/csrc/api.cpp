@@ -597,6 +597,13 @@ int rt_run_encoded_batch(rt_session* s, const void* const* files, const size_t* 
                          void* user, rt_results** out) {
   RT_REQUIRE(s && out && n_pages >= 0 && (n_pages == 0 || (files && lens)), s, "rt_run_encoded_batch: bad argument");
   *out = nullptr;
+  // mode 1: the device decode path, collected at once.  (With tickets in flight the call is refused below, like every call other
+  // than submit / wait.  rt_wait_batch consumes the ticket whether it succeeds or fails, so nothing is left behind on an error.)
+  if (s->jpeg_entropy && !cb && n_pages > 0 && s->inflight.load() == 0) {
+    rt_ticket* t = nullptr;
+    const int rc = rt_submit_encoded_batch(s, files, lens, n_pages, &t);
+    return rc != RT_OK ? rc : rt_wait_batch(s, t, out);
+  }
   return guarded(s, [&] {
     std::vector<std::vector<uint8_t>> px((size_t)n_pages);
     std::vector<int> hs((size_t)n_pages), ws((size_t)n_pages);
@@ -610,11 +617,12 @@ int rt_run_encoded_batch(rt_session* s, const void* const* files, const size_t* 
   });
 }
 // The host stage of the device decode path: every page parsed and entropy-decoded (JPEG) or decoded (anything else) on the
-// decode pool
-static std::vector<rt::EncodedPage> host_stage(const void* const* files, const size_t* lens, int n_pages) {
+// decode pool.  entropy 1 (rt_set_jpeg_entropy): a baseline JPEG page is only prepared for jpeg_huff.hip -- headers, unstuffing
+static std::vector<rt::EncodedPage> host_stage(const void* const* files, const size_t* lens, int n_pages, int entropy) {
   std::vector<rt::EncodedPage> enc((size_t)n_pages);
   decode_pool(n_pages, [&](int i) {
     if (!files[i]) throw RtError(RT_ERR_IMAGE, "image decode: null input");
+    if (entropy && rt::prepare_entropy((const uint8_t*)files[i], lens[i], &enc[(size_t)i])) return;
     rt::decode_for_device((const uint8_t*)files[i], lens[i], &enc[(size_t)i]);
   });
   return enc;
@@ -624,7 +632,7 @@ int rt_submit_encoded_batch(rt_session* s, const void* const* files, const size_
   RT_REQUIRE(s && out && n_pages >= 0 && (n_pages == 0 || (files && lens)), s, "rt_submit_encoded_batch: bad argument");
   RT_REQUIRE(s->inflight.load() < RT_MAX_INFLIGHT, s, "rt_submit_encoded_batch: too many batches in flight (RT_MAX_INFLIGHT)");
   return guarded<true>(s, [&] {
-    std::vector<rt::EncodedPage> enc = host_stage(files, lens, n_pages);
+    std::vector<rt::EncodedPage> enc = host_stage(files, lens, n_pages, s->jpeg_entropy);
     std::vector<const uint8_t*> rgb((size_t)n_pages, nullptr);
     std::vector<int> hs((size_t)n_pages), ws((size_t)n_pages);
     for (int i = 0; i < n_pages; i++) { hs[(size_t)i] = enc[(size_t)i].h; ws[(size_t)i] = enc[(size_t)i].w; }
@@ -645,12 +653,46 @@ int rt_decode_batch(rt_session* s, const void* const* files, const size_t* lens,
       }
       return;
     }
-    std::vector<rt::EncodedPage> enc = host_stage(files, lens, n);
-    for (int i = 0; i < n; i++) {
-      hs[i] = enc[(size_t)i].h; ws[i] = enc[(size_t)i].w;
-      if (on_device) on_device[i] = enc[(size_t)i].on_device ? 1 : 0;
-    }
+    std::vector<rt::EncodedPage> enc = host_stage(files, lens, n, s->jpeg_entropy);
+    for (int i = 0; i < n; i++) { hs[i] = enc[(size_t)i].h; ws[i] = enc[(size_t)i].w; }
     if (n) s->decode_batch(enc, out, mem);
+    // (behind the kernels: a page they flagged went back to the host decoder)
+    for (int i = 0; on_device && i < n; i++) on_device[i] = enc[(size_t)i].entropy_on_device ? 2 : enc[(size_t)i].on_device ? 1 : 0;
+  });
+}
+int rt_set_jpeg_entropy(rt_session* s, int mode) {
+  RT_REQUIRE(s && (mode == 0 || mode == 1), s, "rt_set_jpeg_entropy: bad argument");
+  return guarded(s, [&] { s->jpeg_entropy = mode; });
+}
+int rt_jpeg_entropy(const rt_session* s, int* mode) {
+  if (!s) return RT_ERR_INVALID;
+  if (mode) *mode = s->jpeg_entropy;
+  return RT_OK;
+}
+int rt_debug_jpeg_entropy(rt_session* s, const void* data, size_t len, int how, int16_t* coefs, size_t cap, int* info) {
+  RT_REQUIRE((s || how != 1) && data && info && how >= 0 && how <= 2, s, "rt_debug_jpeg_entropy: bad argument");
+  return guarded(s, [&] {
+    for (int k = 0; k < 9; k++) info[k] = 0;
+    rt::EncodedPage e;
+    if (how == 0) rt::decode_for_device((const uint8_t*)data, len, &e);
+    else if (!rt::prepare_entropy((const uint8_t*)data, len, &e)) return;   // info[8] stays 0: the page goes the host's way
+    if (!e.on_device) throw RtError(RT_ERR_INVALID, "rt_debug_jpeg_entropy: not a page the device path takes");
+    info[8] = 1;
+    size_t total = 0;
+    for (int c = 0; c < e.jpeg.nc; c++) { info[c] = e.jpeg.c[c].stride * e.jpeg.c[c].rows; total += (size_t)info[c]; }
+    if (!coefs) return;
+    if (cap < total) throw RtError(RT_ERR_INVALID, "rt_debug_jpeg_entropy: coefs too small");
+    if (how == 1) return s->debug_jpeg_entropy(e, coefs, info);
+    std::vector<int16_t> planes[3];
+    if (how == 2) {
+      info[3] = rt::huff_decode_host(e, planes) ? 0 : 1;
+      info[4] = (int)e.huff.nsubs; info[5] = (int)((e.huff.nsubs + rt::jpeg::HUFF_WG - 1) / rt::jpeg::HUFF_WG);
+    }
+    for (int c = 0; c < e.jpeg.nc; c++) {
+      const std::vector<int16_t>& q = how == 0 ? e.jpeg.c[c].coef : planes[c];
+      memcpy(coefs, q.data(), q.size() * sizeof(int16_t));
+      coefs += q.size();
+    }
   });
 }
 int rt_debug_jpeg_reconstruct(const void* data, size_t len, uint8_t** rgb, int* h, int* w, int* on_device, char* err,

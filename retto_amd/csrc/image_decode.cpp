@@ -8,6 +8,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <new>
 #include <string>
 
 #include "../../include/retto_hip.h"
@@ -287,6 +288,8 @@ struct JpegDec {
   // coefficient mode (decode_for_device): sequential blocks keep their quantised coefficients in JComp::q16 instead of being
   // transformed; `wide` records a DC predictor that left int16 (only a corrupt stream does that)
   bool coef_mode = false, wide = false;
+  // preparation mode (prepare_entropy): parse() hands the scan to prep_scan instead of decoding it
+  HuffPrep* prep = nullptr; int prep_scans = 0;
 
   void fill() {
     while (nbits <= 56) {
@@ -577,6 +580,94 @@ struct JpegDec {
     if (!hit_marker) { while (pos + 1 < n && !(d[pos] == 0xff && d[pos + 1] != 0x00 && d[pos + 1] != 0xff)) pos++; }
   }
 
+  // Preparation mode: the scan's geometry and tables, then the entropy bytes from pos on, unstuffed, one segment per restart
+  // interval.  One linear pass (memchr for the next FF, bulk copy in between).  Anything outside the device path's scope throws
+  // PrepRefused; pos ends on the marker behind the entropy data.
+  struct PrepRefused {};
+  void prep_scan(const int* idx, int ns) {
+    HuffPrep& P = *prep;
+    if (prep_scans++ || progressive || ns != nc) throw PrepRefused();
+    for (int i = 0; i < ns; i++)   // a scan header naming a component twice: the host's reading, whatever it is
+      for (int k = 0; k < i; k++) if (idx[k] == idx[i]) throw PrepRefused();
+    jpeg::HuffGeom& G = P.G;
+    G = jpeg::HuffGeom{};
+    int fh[3], fv[3];
+    for (int i = 0; i < nc; i++) {
+      if (hmax % c[i].hs || vmax % c[i].vs) throw PrepRefused();
+      fh[i] = hmax / c[i].hs; fv[i] = vmax / c[i].vs;
+    }
+    if (!jpeg::layout_on_device(nc, fh, fv)) throw PrepRefused();
+    G.nc = nc;
+    G.mcus_w = (W + 8 * hmax - 1) / (8 * hmax);
+    G.total_mcus = G.mcus_w * ((H + 8 * vmax - 1) / (8 * vmax));
+    for (int i = 0; i < ns; i++) {
+      JComp& cm = c[idx[i]];
+      if (!dc[cm.td].ok || !ac[cm.ta].ok || !qt_ok[cm.tq]) throw PrepRefused();
+      for (int k = 0; k < 64; k++) cm.qn[kZigzag[k]] = qt[cm.tq][k];
+      G.hs[idx[i]] = cm.hs; G.vs[idx[i]] = cm.vs; G.blocks_w[idx[i]] = cm.stride / 8;
+      for (int v = 0; v < cm.vs; v++)
+        for (int h = 0; h < cm.hs; h++) {
+          if (G.bpm == jpeg::HUFF_MAX_BPM) throw PrepRefused();
+          G.comp[G.bpm] = (uint8_t)idx[i]; G.bh[G.bpm] = (uint8_t)h; G.bv[G.bpm] = (uint8_t)v;
+          G.bpm++;
+        }
+    }
+    const uint32_t per_seg = restart ? (uint32_t)restart : (uint32_t)G.total_mcus;
+    const uint32_t want_segs = ((uint32_t)G.total_mcus + per_seg - 1) / per_seg;
+    // (every segment takes at least one subsequence: refused before anything is reserved for it)
+    if (want_segs > (uint32_t)jpeg::HUFF_WG * jpeg::HUFF_MAX_WGS) throw PrepRefused();
+    std::vector<uint8_t>& o = P.blob;
+    o.clear();
+    o.reserve((n - pos) + (size_t)want_segs * jpeg::HUFF_SUB_BYTES + 8 * sizeof(jpeg::HuffTab));
+    std::vector<jpeg::HuffSeg> segs;
+    size_t seg_at = 0;
+    auto close = [&] {   // the segment's exact bit length, then zero fill up to the next subsequence boundary
+      jpeg::HuffSeg sg;
+      sg.first_sub = (uint32_t)(seg_at / jpeg::HUFF_SUB_BYTES); sg.nbits = (uint32_t)((o.size() - seg_at) * 8);
+      sg.first_mcu = (uint32_t)segs.size() * per_seg;
+      sg.n_mcus = std::min(per_seg, (uint32_t)G.total_mcus - sg.first_mcu);
+      segs.push_back(sg);
+      o.resize(std::max(o.size() + jpeg::HUFF_SUB_BYTES - 1, seg_at + jpeg::HUFF_SUB_BYTES) / jpeg::HUFF_SUB_BYTES * jpeg::HUFF_SUB_BYTES, 0);
+      seg_at = o.size();
+    };
+    for (;;) {
+      const uint8_t* ff = (const uint8_t*)memchr(d + pos, 0xff, n - pos);
+      if (!ff || (size_t)(ff - d) + 1 >= n) throw PrepRefused();   // the entropy data must end at a marker
+      if (o.size() + (size_t)(ff - (d + pos)) - seg_at > 0x1fffffffu) throw PrepRefused();   // bit positions are 32-bit
+      o.insert(o.end(), d + pos, ff);
+      pos = (size_t)(ff - d);
+      const int m = d[pos + 1];
+      if (m == 0x00) { o.push_back(0xff); pos += 2; continue; }
+      if (m >= 0xd0 && m <= 0xd7) {
+        if (segs.size() + 1 >= want_segs || m != (0xd0 | (int)(segs.size() & 7))) throw PrepRefused();
+        close();
+        pos += 2;
+        continue;
+      }
+      if (m == 0xff) throw PrepRefused();   // fill bytes: the host's way
+      break;
+    }
+    close();
+    if (segs.size() != want_segs) throw PrepRefused();
+    P.nsubs = (uint32_t)(o.size() / jpeg::HUFF_SUB_BYTES); P.nsegs = (uint32_t)segs.size();
+    if (P.nsubs > (uint32_t)jpeg::HUFF_WG * jpeg::HUFF_MAX_WGS) throw PrepRefused();
+    o.resize(o.size() + jpeg::HUFF_PAD, 0);
+    P.tabs_at = o.size();
+    o.resize(o.size() + 6 * sizeof(jpeg::HuffTab), 0);
+    for (int i = 0; i < nc; i++)
+      for (int a = 0; a < 2; a++) {
+        const Huff& h = a ? ac[c[i].ta] : dc[c[i].td];
+        jpeg::HuffTab t;
+        memcpy(t.look, h.look, sizeof(t.look)); memcpy(t.maxcode, h.maxcode, sizeof(t.maxcode));
+        memcpy(t.valoff, h.valoff, sizeof(t.valoff)); memcpy(t.vals, h.vals, sizeof(t.vals));
+        memcpy(o.data() + P.tabs_at + (size_t)(2 * i + a) * sizeof(t), &t, sizeof(t));
+      }
+    o.resize((o.size() + 15) & ~(size_t)15, 0);
+    P.segs_at = o.size();
+    o.resize(o.size() + segs.size() * sizeof(jpeg::HuffSeg));
+    memcpy(o.data() + P.segs_at, segs.data(), segs.size() * sizeof(jpeg::HuffSeg));
+  }
+
   // One component plane -> full resolution [H][W]
   void upsample(const JComp& cm, std::vector<uint8_t>& out) {
     out.resize((size_t)W * H);
@@ -688,6 +779,7 @@ struct JpegDec {
         for (int i = 0; i < nc; i++) {
           c[i].cw = (W * c[i].hs + hmax - 1) / hmax; c[i].ch = (H * c[i].vs + vmax - 1) / vmax;
           c[i].stride = mx * c[i].hs * 8; c[i].rows = my * c[i].vs * 8;
+          if (prep) continue;   // headers only: nothing is decoded into planes
           if (!coef_mode) c[i].plane.assign((size_t)c[i].stride * c[i].rows, 128);
           else if (m != 0xc2) c[i].q16.assign((size_t)c[i].stride * c[i].rows, 0);
           if (m == 0xc2) c[i].coef.assign((size_t)c[i].stride * c[i].rows, 0);
@@ -716,7 +808,7 @@ struct JpegDec {
         if (ns > 1 && ns != nc) bad("JPEG: partially interleaved scans are not supported");
         const uint8_t* sp = s + 1 + 2 * ns;
         Ss = sp[0]; Se = sp[1]; Ah = sp[2] >> 4; Al = sp[2] & 15;
-        scan(idx, ns);
+        if (prep) prep_scan(idx, ns); else scan(idx, ns);
         scans++;
       }
       // everything else (APPn, COM, ...) is skipped
@@ -824,6 +916,71 @@ void decode_for_device(const uint8_t* data, size_t len, EncodedPage* out) {
     out->jpeg = JpegCoefs();
   }
   decode_image(data, len, &out->rgb, &out->h, &out->w);
+}
+
+bool prepare_entropy(const uint8_t* data, size_t len, EncodedPage* out) {
+  if (!data || len < 4 || !is_jpeg(data)) return false;
+  HuffPrep prep;
+  JpegDec j{data, len};
+  j.coef_mode = true;
+  j.prep = &prep;
+  try {
+    j.parse(false);
+  } catch (const JpegDec::PrepRefused&) { return false; } catch (const RtError&) { return false; } catch (const std::bad_alloc&) { return false; }
+  if (j.prep_scans != 1) return false;
+  JpegCoefs& J = out->jpeg;
+  J = JpegCoefs();
+  J.W = j.W; J.H = j.H; J.nc = j.nc; J.hmax = j.hmax; J.vmax = j.vmax;
+  J.is_rgb = j.nc == 3 && j.is_rgb();
+  for (int i = 0; i < j.nc; i++) {
+    const JComp& cm = j.c[i];
+    JpegCoefs::Comp& o = J.c[i];
+    o.hs = cm.hs; o.vs = cm.vs; o.cw = cm.cw; o.ch = cm.ch; o.stride = cm.stride; o.rows = cm.rows;
+    memcpy(o.q, cm.qn, sizeof(o.q));
+  }
+  out->h = j.H; out->w = j.W;
+  out->on_device = out->entropy_on_device = true;
+  out->huff = std::move(prep);
+  out->src = data; out->src_len = len;
+  return true;
+}
+
+bool huff_decode_host(const EncodedPage& e, std::vector<int16_t> planes[3]) {
+  const HuffPrep& P = e.huff;
+  const jpeg::HuffGeom& G = P.G;
+  jpeg::HuffCoefSink sink;
+  sink.G = &G;
+  for (int c = 0; c < 3; c++) {
+    planes[c].assign(c < G.nc ? (size_t)e.jpeg.c[c].stride * e.jpeg.c[c].rows : 0, 0);
+    sink.plane[c] = planes[c].data();
+  }
+  bool ok = true;
+  const uint32_t limit = P.nsubs * jpeg::HUFF_SUB_BYTES + jpeg::HUFF_PAD;
+  for (uint32_t si = 0; si < P.nsegs && ok; si++) {
+    const jpeg::HuffSeg& sg = P.segs()[si];
+    jpeg::HuffState st{0, 0, 0};
+    sink.first = sg.first_mcu * (uint32_t)G.bpm;
+    sink.seg_end = (sg.first_mcu + sg.n_mcus) * (uint32_t)G.bpm;
+    const uint32_t nss = jpeg::huff_seg_subs(sg);
+    for (uint32_t cur = 0; cur < nss; cur++) {   // subsequence by subsequence, as the write pass's lanes
+      const uint32_t end = std::min((cur + 1) * (uint32_t)jpeg::HUFF_S, sg.nbits);
+      if (jpeg::huff_decode_sub(P.tabs(), G, P.blob.data(), (int)(sg.first_sub * jpeg::HUFF_SUB_BYTES), limit, sg.nbits, end, st,
+                                sink) == jpeg::HUFF_BAD) { ok = false; break; }
+      if (cur == nss - 1) ok = jpeg::huff_seg_end_ok(sg, G, st, sink.first);
+      sink.first += st.n;
+    }
+    for (int c = 0; c < G.nc && ok; c++) {   // the DC pass
+      const uint32_t nb = sg.n_mcus * (uint32_t)(G.hs[c] * G.vs[c]);
+      int pred = 0;
+      for (uint32_t i = 0; i < nb; i++) {
+        int16_t* at = planes[c].data() + jpeg::huff_comp_block_pos(G, c, sg.first_mcu, i);
+        pred = (int)((unsigned)pred + (unsigned)(int)*at);
+        if (pred < -32768 || pred > 32767) ok = false;
+        *at = (int16_t)pred;
+      }
+    }
+  }
+  return ok;
 }
 
 void reconstruct_host(const JpegCoefs& J, std::vector<uint8_t>* rgb) {

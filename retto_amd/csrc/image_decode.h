@@ -11,6 +11,8 @@
 #include <cstdint>
 #include <vector>
 
+#include "jpeg_huff.h"
+
 namespace rt {
 
 // Throws RtError(RT_ERR_IMAGE) with the reason (unknown format, truncated stream, CRC mismatch, ...).
@@ -31,13 +33,38 @@ struct JpegCoefs {
 // One encoded page for the device path.  on_device: a JPEG whose pixels the kernels reconstruct from `jpeg` -- every quantised
 // coefficient fits int16 and its sampling layout is one jpeg::layout_on_device accepts.  Otherwise `rgb` holds the page as
 // decode_image decodes it (any other JPEG, PNG, PNM, BMP).  Errors are decode_image's.
+// A baseline JPEG page prepared for entropy decoding on the device (jpeg_huff.h): one upload.  blob = the unstuffed entropy bytes
+// (FF 00 -> FF), every restart interval starting on a subsequence boundary, nsubs * HUFF_SUB_BYTES + HUFF_PAD bytes; at tabs_at
+// the page's HuffTab[6] (DC, AC per component); at segs_at its HuffSeg[nsegs].
+struct HuffPrep {
+  std::vector<uint8_t> blob;
+  size_t tabs_at = 0, segs_at = 0;
+  uint32_t nsubs = 0, nsegs = 0;
+  jpeg::HuffGeom G{};
+  const jpeg::HuffTab* tabs() const { return (const jpeg::HuffTab*)(blob.data() + tabs_at); }
+  const jpeg::HuffSeg* segs() const { return (const jpeg::HuffSeg*)(blob.data() + segs_at); }
+};
 struct EncodedPage {
   int h = 0, w = 0;
   bool on_device = false;
   JpegCoefs jpeg;
   std::vector<uint8_t> rgb;
+  // rt_set_jpeg_entropy mode 1: `jpeg` describes the page but holds no coefficients, the kernels decode `huff` into the slot.
+  // src: the file, valid for the call that uploads the page (a page the kernels flag is decoded from it on the host)
+  bool entropy_on_device = false;
+  HuffPrep huff;
+  const uint8_t* src = nullptr;
+  size_t src_len = 0;
 };
 void decode_for_device(const uint8_t* data, size_t len, EncodedPage* out);
+// The host side of device entropy decoding: headers and tables through JpegDec::parse, then one linear pass over the entropy
+// bytes.  true: out is an on_device page with entropy_on_device set.  false (out untouched): not SOF0 / SOF1 with one scan
+// carrying all components, a sampling layout off the device, a marker other than RSTn (in order) inside the entropy data, no
+// marker behind it, too large, or a header error -- the caller takes decode_for_device, which also reports errors as before.
+bool prepare_entropy(const uint8_t* data, size_t len, EncodedPage* out);
+// jpeg_huff.h's decode step run serially over a prepared page, then the DC sums: coefficient planes as decode_for_device fills
+// them.  false: the page's flag -- something the kernels would flag as well.
+bool huff_decode_host(const EncodedPage& e, std::vector<int16_t> planes[3]);
 // k_jpeg_idct + k_jpeg_color's arithmetic (jpeg_recon.h) run on the CPU: the RGB8 page the kernels produce from J
 void reconstruct_host(const JpegCoefs& J, std::vector<uint8_t>* rgb);
 // Page size from the header alone (no pixel work): RT_ERR_IMAGE for an unknown format or a bad header.

@@ -178,6 +178,11 @@ struct rt_ticket {
     size_t comps_off = 0, pages_off = 0;   // the two tables inside the slot
     int blocks = 0;
     int64_t pixels = 0;
+    // pages whose entropy decoding runs on the device (rt_set_jpeg_entropy mode 1, jpeg_huff.hip): their table, behind it in the
+    // slot HUFF_INFO ints per page (flag, rounds); per table entry the page's index in the call and its first DevComp
+    std::vector<rt::jpeg::DevHuffPage> hpages;
+    std::vector<int> hpage_enc, hpage_comp;
+    size_t hmeta_off = 0;
   };
   std::vector<EncPart> enc_parts;   // per lane part
 };
@@ -514,6 +519,11 @@ struct rt_session : rt_lane {
   rt_results* run_batch(const PageCall& call);
   // rt_decode_batch: pages through the host stage and the reconstruction kernels into out[i] (mem: RT_MEM_HOST / RT_MEM_DEVICE)
   void decode_batch(std::vector<rt::EncodedPage>& enc, uint8_t* const* out, int mem);
+  // rt_set_jpeg_entropy: 0 = the host entropy-decodes JPEG pages (default), 1 = jpeg_huff.hip does for the pages
+  // rt::prepare_entropy accepts
+  int jpeg_entropy = 0;
+  // rt_debug_jpeg_entropy, how = 1: one prepared page through passes 1-5; planes back to back into coefs, info[3..7]
+  void debug_jpeg_entropy(rt::EncodedPage& e, int16_t* coefs, int* info);
   // rt_run_regions: checks and clamps every quad (RT_ERR_INVALID naming page and region; nothing is queued then), then the
   // pages go over the lanes as run_batch's do, from the crop plan on
   // ids[j] (the kinds of rec_line_opts.h: charsets, lexicons, patterns, keywords; each or null; entries may be null): per region

@@ -89,16 +89,18 @@ static size_t enc_layout(const std::vector<rt::EncodedPage>& enc, int i0, int i1
     at += al256((size_t)e.h * e.w * 3);
     if (!e.on_device) continue;
     const rt::JpegCoefs& J = e.jpeg;
+    rt::jpeg::DevHuffPage hp{};
     rt::jpeg::DevPage dp{};
     dp.rgb_off = rgb_off[(size_t)i]; dp.pix_base = P.pixels; dp.W = J.W; dp.H = J.H; dp.nc = J.nc; dp.is_rgb = J.is_rgb;
     for (int k = 0; k < J.nc; k++) {
       const rt::JpegCoefs::Comp& C = J.c[k];
       rt::jpeg::DevComp dc{};
       dc.plane_off = at; at += al256((size_t)C.stride * C.rows);
-      dc.coef_off = at; at += al256(C.coef.size() * sizeof(int16_t));
       dc.blocks_w = C.stride / 8; dc.nblocks = (C.stride / 8) * (C.rows / 8); dc.block_base = (int)blocks;
+      dc.coef_off = at; at += al256((size_t)dc.nblocks * 64 * sizeof(int16_t));
+      hp.coef_off[k] = dc.coef_off; hp.coef_bytes[k] = (uint32_t)dc.nblocks * 64 * sizeof(int16_t);
       blocks += dc.nblocks;
-      if (blocks > 0x7fffffff || C.coef.size() != (size_t)dc.nblocks * 64) throw RtError(RT_ERR_BACKEND, "encoded batch: too many JPEG blocks in one part");
+      if (blocks > 0x7fffffff || (!e.entropy_on_device && C.coef.size() != (size_t)dc.nblocks * 64)) throw RtError(RT_ERR_BACKEND, "encoded batch: too many JPEG blocks in one part");
       dc.stride = C.stride; dc.cw = C.cw; dc.ch = C.ch; dc.fh = J.hmax / C.hs; dc.fv = J.vmax / C.vs;
       memcpy(dc.q, C.q, sizeof(dc.q));
       dp.comp[k] = (int)P.comps.size();
@@ -106,20 +108,72 @@ static size_t enc_layout(const std::vector<rt::EncodedPage>& enc, int i0, int i1
     }
     P.pixels += (int64_t)J.W * J.H;
     P.pages.push_back(dp);
+    if (!e.entropy_on_device) continue;
+    // the prepared stream, tables and segments (one upload), then the lanes' exit states and first-block indices
+    const rt::HuffPrep& H = e.huff;
+    hp.stream_off = at; hp.tabs_off = at + H.tabs_at; hp.segs_off = at + H.segs_at; at += al256(H.blob.size());
+    hp.state_off = at; at += al256((size_t)H.nsubs * sizeof(rt::jpeg::HuffState));
+    hp.first_off = at; at += al256((size_t)H.nsubs * sizeof(uint32_t));
+    hp.nsubs = H.nsubs; hp.nsegs = H.nsegs; hp.nwg = (H.nsubs + rt::jpeg::HUFF_WG - 1) / rt::jpeg::HUFF_WG;
+    if (!P.hpages.empty()) { hp.wg_base = P.hpages.back().wg_base + P.hpages.back().nwg; hp.seg_base = P.hpages.back().seg_base + P.hpages.back().nsegs; }
+    hp.G = H.G;
+    P.hpages.push_back(hp);
+    P.hpage_enc.push_back(i);
+    P.hpage_comp.push_back((int)P.comps.size() - J.nc);
   }
+  P.hmeta_off = at; at += al256(P.hpages.size() * (sizeof(rt::jpeg::DevHuffPage) + rt::jpeg::HUFF_INFO * sizeof(int)));
   P.blocks = (int)blocks;
   P.comps_off = at; at += al256(P.comps.size() * sizeof(rt::jpeg::DevComp));
   P.pages_off = at; at += al256(P.pages.size() * sizeof(rt::jpeg::DevPage));
   return at;
 }
-// uploads pages [i0, i1) (coefficients of the device pages, pixels of the others) and the tables, then reconstructs on `st`
-static void enc_upload(uint8_t* base, const std::vector<rt::EncodedPage>& enc, int i0, int i1, const std::vector<size_t>& rgb_off,
+// Device entropy decoding of the part's prepared pages on `st`: the table with its cleared flags goes up, passes 1-5 run, the
+// flags come back (waiting for `st` alone).  info (optional): the HUFF_INFO ints of every page.  A flagged page is decoded by
+// the host decoder from its file, errors included, and takes the coefficient upload as if it had never been prepared; one the
+// host reconstructs as well (a DC value outside int16) has its pixels in e.rgb afterwards, for the caller to upload behind the
+// kernels.
+static void enc_entropy(uint8_t* base, std::vector<rt::EncodedPage>& enc, const rt_ticket::EncPart& P, hipStream_t st,
+                        std::vector<int>* info = nullptr, bool host_decode = true) {
+  const size_t np = P.hpages.size(), tab = np * sizeof(rt::jpeg::DevHuffPage);
+  std::vector<uint8_t> meta(tab + np * rt::jpeg::HUFF_INFO * sizeof(int), 0);
+  memcpy(meta.data(), P.hpages.data(), tab);
+  RT_HIP_CHECK(hipMemcpyAsync(base + P.hmeta_off, meta.data(), meta.size(), hipMemcpyHostToDevice, st));
+  int* d_info = (int*)(base + P.hmeta_off + tab);
+  rt::launch_jpeg_huff(base, (const rt::jpeg::DevHuffPage*)(base + P.hmeta_off), d_info, P.hpages.data(), (int)np, st);
+  std::vector<int> got(np * rt::jpeg::HUFF_INFO);
+  RT_HIP_CHECK(hipMemcpyAsync(got.data(), d_info, got.size() * sizeof(int), hipMemcpyDeviceToHost, st));
+  RT_HIP_CHECK(hipStreamSynchronize(st));
+  if (info) *info = got;
+  for (size_t k = 0; host_decode && k < np; k++) {
+    if (!got[k * rt::jpeg::HUFF_INFO]) continue;
+    rt::EncodedPage& e = enc[(size_t)P.hpage_enc[k]];
+    rt::EncodedPage host;
+    rt::decode_for_device(e.src, e.src_len, &host);
+    e.entropy_on_device = false;
+    // (as mode 0 reports it: a host page.  It stays in the part's tables, so the reconstruction kernels still pass over its
+    // cleared planes before the upload replaces their pixels -- only a corrupt stream gets here)
+    if (!host.on_device) { e.rgb = std::move(host.rgb); e.on_device = false; continue; }
+    for (int c = 0; c < e.jpeg.nc; c++) {
+      e.jpeg.c[c].coef = std::move(host.jpeg.c[c].coef);
+      const std::vector<int16_t>& q = e.jpeg.c[c].coef;
+      RT_HIP_CHECK(hipMemcpyAsync(base + P.comps[(size_t)P.hpage_comp[k] + c].coef_off, q.data(), q.size() * sizeof(int16_t), hipMemcpyHostToDevice, st));
+    }
+  }
+}
+// uploads pages [i0, i1) (coefficients or prepared streams of the device pages, pixels of the others) and the tables, then
+// decodes and reconstructs on `st`
+static void enc_upload(uint8_t* base, std::vector<rt::EncodedPage>& enc, int i0, int i1, const std::vector<size_t>& rgb_off,
                        const rt_ticket::EncPart& P, hipStream_t st) {
-  size_t c = 0;
+  size_t c = 0, hk = 0;
   for (int i = i0; i < i1; i++) {
     const rt::EncodedPage& e = enc[(size_t)i];
     if (!e.on_device) {
       RT_HIP_CHECK(hipMemcpyAsync(base + rgb_off[(size_t)i], e.rgb.data(), e.rgb.size(), hipMemcpyHostToDevice, st));
+      continue;
+    }
+    if (e.entropy_on_device) {
+      RT_HIP_CHECK(hipMemcpyAsync(base + P.hpages[hk++].stream_off, e.huff.blob.data(), e.huff.blob.size(), hipMemcpyHostToDevice, st));
+      c += (size_t)e.jpeg.nc;
       continue;
     }
     for (int k = 0; k < e.jpeg.nc; k++, c++) {
@@ -128,11 +182,37 @@ static void enc_upload(uint8_t* base, const std::vector<rt::EncodedPage>& enc, i
     }
   }
   if (P.pages.empty()) return;
+  if (!P.hpages.empty()) enc_entropy(base, enc, P, st);
   RT_HIP_CHECK(hipMemcpyAsync(base + P.comps_off, P.comps.data(), P.comps.size() * sizeof(rt::jpeg::DevComp), hipMemcpyHostToDevice, st));
   RT_HIP_CHECK(hipMemcpyAsync(base + P.pages_off, P.pages.data(), P.pages.size() * sizeof(rt::jpeg::DevPage), hipMemcpyHostToDevice, st));
   const auto* comps = (const rt::jpeg::DevComp*)(base + P.comps_off);
   rt::launch_jpeg_idct(base, comps, (int)P.comps.size(), P.blocks, st);
   rt::launch_jpeg_color(base, comps, (const rt::jpeg::DevPage*)(base + P.pages_off), (int)P.pages.size(), P.pixels, st);
+  for (int i : P.hpage_enc) {   // flagged pages the host reconstructed too: their pixels replace the kernels'
+    const rt::EncodedPage& e = enc[(size_t)i];
+    if (!e.rgb.empty()) RT_HIP_CHECK(hipMemcpyAsync(base + rgb_off[(size_t)i], e.rgb.data(), e.rgb.size(), hipMemcpyHostToDevice, st));
+  }
+}
+void rt_session::debug_jpeg_entropy(rt::EncodedPage& e, int16_t* coefs, int* info) {
+  std::vector<rt::EncodedPage> enc(1);
+  enc[0] = std::move(e);
+  std::vector<size_t> off(1, 0);
+  rt_ticket::EncPart P;
+  const size_t total = enc_layout(enc, 0, 1, 0, off, P);
+  const int slot = acquire_slot(total, 1);
+  if (slot < 0) throw RtError(RT_ERR_BACKEND, "rt_debug_jpeg_entropy: out of device memory for the page");
+  uint8_t* base = stage_slots[(size_t)slot].p;
+  RT_HIP_CHECK(hipMemcpyAsync(base + P.hpages[0].stream_off, enc[0].huff.blob.data(), enc[0].huff.blob.size(), hipMemcpyHostToDevice, st_copy));
+  std::vector<int> got;
+  enc_entropy(base, enc, P, st_copy, &got, false);   // (the flag is reported, not acted on)
+  const rt::jpeg::DevHuffPage& hp = P.hpages[0];
+  for (int c = 0; c < enc[0].jpeg.nc; c++) {
+    RT_HIP_CHECK(hipMemcpyAsync(coefs, base + hp.coef_off[c], hp.coef_bytes[c], hipMemcpyDeviceToHost, st_copy));
+    coefs += hp.coef_bytes[c] / sizeof(int16_t);
+  }
+  RT_HIP_CHECK(hipStreamSynchronize(st_copy));
+  info[3] = got[0]; info[4] = (int)hp.nsubs; info[5] = (int)hp.nwg; info[6] = got[1]; info[7] = got[2];
+  e = std::move(enc[0]);
 }
 // an encoded ticket: every part in one slot, laid out part after part (staging is not optional here: the lanes need pixels)
 static void stage_encoded_layout(rt_ticket* t, size_t* total) {

@@ -6,7 +6,10 @@ one process, `--repeats` times each; reported: pages/s (median and spread) and h
 over the timed window).  Kernel times of k_jpeg_idct / k_jpeg_color come from a separate rocprofv3 --kernel-trace --stats run
 of this script.
 
-    python tools/bench_encoded.py --steps 10 --warmup 2 --repeats 3
+--entropy device: the same with rt_set_jpeg_entropy mode 1 (baseline JPEG pages entropy-decoded by jpeg_huff.hip; the sync form
+then goes through the device decode path as well).  Its kernels (k_huff_*) are timed by the same separate rocprofv3 run.
+
+    python tools/bench_encoded.py --steps 10 --warmup 2 --repeats 3 [--entropy device]
 """
 import argparse
 import io
@@ -63,13 +66,15 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--seed", type=int, default=1000)
+    ap.add_argument("--entropy", choices=("host", "device"), default="host")
     a = ap.parse_args()
     if a.steps < 1 or a.repeats < 1:
         ap.error("--steps and --repeats must be at least 1")
     files = pages(a.pages, a.seed)
     sess = retto_amd.RettoSession(retto_amd.synthetic_session_config(0))
     try:
-        ref = sess.run_encoded_batch(files)
+        ref = sess.run_encoded_batch(files)   # (mode 0: the reference the chosen mode must reproduce)
+        sess.set_jpeg_entropy(1 if a.entropy == "device" else 0)
         got = sess.wait_batch(sess.submit_encoded_batch(files))
         same = all(len(x.det_result) == len(y.det_result) and [r.text for r in x.rec_result] == [r.text for r in y.rec_result]
                    for x, y in zip(ref, got))
@@ -79,7 +84,7 @@ def main():
         for _ in range(a.repeats):
             res["sync"].append(timed(run_sync, sess, files, a.steps))
             res["pipelined"].append(timed(run_pipelined, sess, files, a.steps))
-        out = {"pages": a.pages, "steps": a.steps, "repeats": a.repeats, "results_equal": same,
+        out = {"entropy": a.entropy, "pages": a.pages, "steps": a.steps, "repeats": a.repeats, "results_equal": same,
                "host_cpu_budget": sess._hd.lib.rt_host_cpu_budget()}
         for k, v in res.items():
             rate = [r for r, _ in v]; cpu = [c for _, c in v]
