@@ -338,6 +338,37 @@ RT_API int rt_results_rec_flip(const rt_results* r, int page, int line, float* s
 RT_API int rt_debug_rec_flip(rt_session* s, const uint8_t* crops, const int32_t* hw, int n, const uint8_t* both, float max_wh_ratio,
                              int32_t* view_idx_out, float* view_prob_out, float* view_z5_out, int32_t* view_ntok_out,
                              float* view_score_out, int32_t* taken_out, int32_t* idx_out, float* prob_out, float* z5_out);
+/* Page enhance (retto_amd/csrc/page_enhance.h states the rule): tile-wise contrast equalisation of every page before anything
+ * reads it.  A faded thermal receipt, a pencil form, a photographed page with a shadow across it, a grey-on-grey scan reach
+ * resize_both, the detector and the crops exactly as they arrived.  The usual remedy in document OCR is contrast-limited adaptive
+ * histogram equalisation (CLAHE) of the luma; done on the host it is one more pass over pages that are otherwise only uploaded,
+ * and it is impossible for RT_MEM_DEVICE pages and for pages decoded on the device.  With enhance on, every page of rt_run_batch,
+ * rt_run_batch_stream, rt_submit_batch, the encoded entry points (after decoding, on the host or on the device) and
+ * rt_run_regions* is enhanced on the GPU as soon as it is in device memory, into a NEW buffer -- a caller's RT_MEM_DEVICE page is
+ * never written -- and resize_both, the detector, both crop sources and the regions read the enhanced page.  Box coordinates, a
+ * det_map_override and everything downstream are untouched.  All pages of a lane's part share two launches.
+ * The rule is 32-bit integer arithmetic throughout, so rt_enhance_page, the pipeline and rt_debug_enhance_page_host agree bit
+ * for bit: luma Y = (77 R + 150 G + 29 B + 128) >> 8; per tile of tile x tile pixels (edge tiles partial, no padding) the
+ * histogram of Y is clipped at max(1, (lrintf(clip * 16) * area) >> 12), the excess spread evenly over the 256 bins, and the
+ * prefix sum scaled to a 256-byte table; a pixel's new luma is the bilinear blend of the tables of the four tiles whose centres
+ * surround it (the nearest tiles alone towards the page border), and R, G, B all move by the luma's change, clamped to [0, 255]:
+ * a grey page stays grey, chroma differences are kept.
+ * tile = 0: off, the default (clip is then ignored); otherwise a multiple of 32 with 32 <= tile <= 512, and clip finite with
+ * 1 <= clip <= 64 (clip 1 leaves a tile nearly as it is, 64 is close to unlimited equalisation).  Anything else: RT_ERR_INVALID naming the parameter.  The setting holds for
+ * the pipeline calls that follow on every lane (rt_submit_* takes it as it is at the call); fails like every other call while
+ * tickets are in flight.  With enhance off nothing is launched or allocated that was not before.
+ * Not supported: per-page or per-region settings; other colour models than this luma of an RGB8 page; enhancing inside the stage
+ * functions (rt_resize_both, rt_det_preprocess, rt_crop_images take the page as it is).  What enhancing does to recognition
+ * accuracy with trained PP-OCRv4 weights has NOT been measured (the weights here are synthetic). */
+RT_API int rt_set_page_enhance(rt_session* s, int tile, float clip);
+/* the setting (each optional); RT_ERR_INVALID for a NULL session */
+RT_API int rt_page_enhance(const rt_session* s, int* tile, float* clip);
+/* stage function beside rt_resize_both: one RGB8 HWC page in host memory through the pipeline's own launcher, into out [h * w * 3]
+ * (host).  tile and clip as above, whatever the session's setting is; tile = 0 copies the page. */
+RT_API int rt_enhance_page(rt_session* s, const uint8_t* rgb, int h, int w, int tile, float clip, uint8_t* out);
+/* The rule on the CPU, in plain loops over the same header; GPU-free and sessionless (rt_last_error(NULL)).  luts_out (optional):
+ * the tiles' tables, ceil(h / tile) * ceil(w / tile) * 256 bytes in row-major tile order (not written for tile = 0). */
+RT_API int rt_debug_enhance_page_host(const uint8_t* rgb, int h, int w, int tile, float clip, uint8_t* out, uint8_t* luts_out);
 /* The pipeline over regions the caller already knows (form fields, subtitles, corrected boxes, another detector's boxes):
  * quads[i] = n_quads[i] x 8 floats in host memory, TL, TR, BR, BL of each region in original-page coordinates; mem
  * (RT_MEM_HOST or RT_MEM_DEVICE) says where the pages live.  Every coordinate is clamped to [0, ori - 1] (no rounding); line k

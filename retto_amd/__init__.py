@@ -568,6 +568,18 @@ def det_tile_plan(h: int, w: int, tile: int, overlap: int = 64) -> dict:
                 "col_origins": co[:nc.value], "col_bounds": cb[:nc.value]}
 
 
+def debug_enhance_page_host(img: np.ndarray, tile: int, clip: float = 2.5, with_luts: bool = False):
+    """rt_debug_enhance_page_host: the page enhance rule (retto_amd/csrc/page_enhance.h) on the CPU, GPU-free: the enhanced RGB8
+    page [h, w, 3]; with_luts: (page, luts [ceil(h / tile), ceil(w / tile), 256])."""
+    lib = _lib.load()
+    img = np.ascontiguousarray(img, np.uint8); h, w = img.shape[:2]
+    out = np.empty((h, w, 3), np.uint8)
+    luts = np.zeros((-(-h // tile), -(-w // tile), 256), np.uint8) if with_luts and tile > 0 else None
+    _check(lib.rt_debug_enhance_page_host(img.ctypes.data, h, w, int(tile), float(clip), out.ctypes.data,
+                                          None if luts is None else luts.ctypes.data), None)
+    return (out, luts) if with_luts else out
+
+
 _WINDOW_PLAN_BUFS = None   # the three output arrays of rec_window_plan, grown on demand, as det_tile_plan's
 
 
@@ -840,6 +852,27 @@ class RettoSession:
         trusted parts are stitched into the one page map (retto_amd/csrc/det_tiles.h); 0 = off, the default.  tile: a multiple
         of 32, at least 64; overlap: a multiple of 32, at most tile / 2.  Holds for the pipeline calls that follow."""
         _check(self._hd.lib.rt_set_det_tiles(self._hd.h, int(tile), int(overlap)), self._hd.h)
+
+    # -- page enhance -----------------------------------------------------------------------
+    def set_page_enhance(self, tile: int, clip: float = 2.5) -> None:
+        """rt_set_page_enhance: every page of the pipeline calls that follow is contrast-equalised tile-wise (CLAHE of the luma,
+        retto_amd/csrc/page_enhance.h) on the GPU before anything else reads it; 0 = off, the default.  tile: a multiple of 32
+        in [32, 512]; clip: finite, in [1, 64].  The effect on accuracy with the real weights is not measured."""
+        _check(self._hd.lib.rt_set_page_enhance(self._hd.h, int(tile), float(clip)), self._hd.h)
+
+    def page_enhance(self) -> Tuple[int, float]:
+        """rt_page_enhance: (tile, clip) as set; tile 0 = off."""
+        t, c = C.c_int(), C.c_float()
+        _check(self._hd.lib.rt_page_enhance(self._hd.h, C.byref(t), C.byref(c)), self._hd.h)
+        return t.value, c.value
+
+    def enhance_page(self, img: np.ndarray, tile: int, clip: float = 2.5) -> np.ndarray:
+        """rt_enhance_page: one RGB8 page [h, w, 3] enhanced on the GPU through the pipeline's own launcher, whatever the
+        session's setting is; tile = 0 returns a copy."""
+        img = np.ascontiguousarray(img, np.uint8); h, w = img.shape[:2]
+        out = np.empty((h, w, 3), np.uint8)
+        _check(self._hd.lib.rt_enhance_page(self._hd.h, img.ctypes.data, h, w, int(tile), float(clip), out.ctypes.data), self._hd.h)
+        return out
 
     # -- rec beams --------------------------------------------------------------------------
     def set_rec_beam(self, beam: int, nbest: int = 1) -> None:

@@ -58,6 +58,10 @@ def build_parser() -> argparse.ArgumentParser:
                          "into one page map (large scans at their own resolution); a multiple of 32, at least 64; 0 = off")
     ap.add_argument("--det-tile-overlap", type=int, default=64, metavar="M",
                     help="with --det-tile: the tiles' overlap, a multiple of 32, at most N / 2")
+    ap.add_argument("--enhance", default=None, metavar="TILE,CLIP",
+                    help="contrast-equalise every page tile-wise on the GPU before anything reads it (CLAHE of the luma; faded or "
+                         "shadowed pages; the effect on accuracy is not measured); TILE a multiple of 32 in [32, 512], CLIP in "
+                         "[1, 64], e.g. 64,2.5; default off")
     ap.add_argument("--rec-window", type=int, default=0, metavar="N",
                     help="read rec lines at least 8 columns wider than N as overlapping windows of N columns, stitched into the "
                          "one line (long lines at a familiar width; the effect on accuracy is not measured); a multiple of 32, "
@@ -135,6 +139,13 @@ def main(argv=None) -> int:
     session = retto_amd.RettoSession(cfg)
     if a.det_tile:
         session.set_det_tiles(a.det_tile, a.det_tile_overlap)
+    if a.enhance:
+        try:
+            tile, clip = a.enhance.split(",")
+            tile, clip = int(tile), float(clip)
+        except ValueError:
+            ap.error("--enhance takes TILE,CLIP, e.g. 64,2.5")
+        session.set_page_enhance(tile, clip)
     if a.rec_window:
         session.set_rec_windows(a.rec_window, a.rec_window_overlap)
     if a.rec_flip:

@@ -478,6 +478,37 @@ int rt_results_rec_flip(const rt_results* r, int page, int line, float* score0, 
   if (score1) *score1 = p->flip_scores[2 * (size_t)line + 1];
   return p->flip_outcome[(size_t)line];
 }
+int rt_set_page_enhance(rt_session* s, int tile, float clip) {
+  RT_REQUIRE(s, s, "rt_set_page_enhance: null session");
+  return guarded(s, [&] {
+    if (const char* why = pe::check_params(tile, clip)) throw RtError(RT_ERR_INVALID, std::string("rt_set_page_enhance: ") + why);
+    s->enhance_tile = tile; s->enhance_clip = tile ? clip : 0.0f;   // (the helper lanes get it with every call: CallSettings)
+  });
+}
+int rt_page_enhance(const rt_session* s, int* tile, float* clip) {
+  if (!s) return RT_ERR_INVALID;
+  if (tile) *tile = s->enhance_tile;
+  if (clip) *clip = s->enhance_clip;
+  return RT_OK;
+}
+int rt_enhance_page(rt_session* s, const uint8_t* rgb, int h, int w, int tile, float clip, uint8_t* out) {
+  RT_REQUIRE(s && rgb && out && h > 0 && w > 0, s, "rt_enhance_page: bad argument");
+  return guarded(s, [&] {
+    if (const char* why = pe::check_params(tile, clip)) throw RtError(RT_ERR_INVALID, std::string("rt_enhance_page: ") + why);
+    if ((long long)h * w > 0x7fffffffLL / 3) throw RtError(RT_ERR_CAPACITY, "rt_enhance_page: the page is larger than 2^31 - 1 bytes");
+    if (tile == 0) { memcpy(out, rgb, (size_t)h * w * 3); return; }   // off: the page as it is
+    s->enhance_page(rgb, h, w, tile, pe::clip_x16_of(clip), out);
+  });
+}
+int rt_debug_enhance_page_host(const uint8_t* rgb, int h, int w, int tile, float clip, uint8_t* out, uint8_t* luts_out) {
+  RT_REQUIRE(rgb && out && h > 0 && w > 0, (rt_session*)nullptr, "rt_debug_enhance_page_host: bad argument");
+  return guarded(nullptr, [&] {
+    if (const char* why = pe::check_params(tile, clip)) throw RtError(RT_ERR_INVALID, std::string("rt_debug_enhance_page_host: ") + why);
+    if ((long long)h * w > 0x7fffffffLL / 3) throw RtError(RT_ERR_CAPACITY, "rt_debug_enhance_page_host: the page is larger than 2^31 - 1 bytes");
+    if (tile == 0) { memcpy(out, rgb, (size_t)h * w * 3); return; }   // off: the page as it is, no LUTs
+    pe::enhance_page_host(rgb, h, w, tile, pe::clip_x16_of(clip), out, luts_out);
+  });
+}
 int rt_rec_window_plan(int L, int window, int overlap, int32_t* origin, int32_t* width, int32_t* bound, int cap, int* n, int* T) {
   return guarded(nullptr, [&] {
     if (const char* why = rw::check_params(window, overlap)) throw RtError(RT_ERR_INVALID, std::string("rt_rec_window_plan: ") + why);

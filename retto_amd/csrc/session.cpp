@@ -288,6 +288,34 @@ void rt_lane::resize_both(const uint8_t* rgb, int h, int w, uint8_t* out, int oh
   sync(); check_flags();
 }
 
+void rt_lane::enhance_pages(int n, const uint8_t* const* src, const int* hs, const int* ws, int tile, int clip_x16, const uint8_t** out,
+                            const uint8_t** luts_out) {
+  if (n <= 0) return;
+  pe::DevPage* hp = pinned.alloc<pe::DevPage>((size_t)n);
+  for (int i = 0; i < n; i++) { hp[i] = pe::DevPage{}; hp[i].src = src[i]; hp[i].h = hs[i]; hp[i].w = ws[i]; }
+  if (!pe::plan_pages(hp, n, tile)) throw RtError(RT_ERR_CAPACITY, "page enhance: more than 2^31 - 1 tiles in one call");
+  for (int i = 0; i < n; i++) {
+    hp[i].dst = arena.alloc<uint8_t>((size_t)hs[i] * ws[i] * 3);
+    hp[i].luts = arena.alloc<uint8_t>((size_t)hp[i].nty * hp[i].ntx * 256);
+    out[i] = hp[i].dst;
+    if (luts_out) luts_out[i] = hp[i].luts;
+  }
+  pe::DevPage* dp = arena.alloc<pe::DevPage>((size_t)n);
+  RT_HIP_CHECK(hipMemcpyAsync(dp, hp, (size_t)n * sizeof(pe::DevPage), hipMemcpyHostToDevice, st));
+  pe::launch(st, &prof, dp, hp, n, tile, clip_x16);
+}
+
+void rt_lane::enhance_page(const uint8_t* rgb, int h, int w, int tile, int clip_x16, uint8_t* out) {
+  begin_call();
+  const size_t bytes = (size_t)h * w * 3;
+  uint8_t* d = arena.alloc<uint8_t>(bytes);
+  RT_HIP_CHECK(hipMemcpyAsync(d, rgb, bytes, hipMemcpyHostToDevice, st));
+  const uint8_t* src = d; const uint8_t* e = nullptr;
+  enhance_pages(1, &src, &h, &w, tile, clip_x16, &e);
+  RT_HIP_CHECK(hipMemcpyAsync(out, e, bytes, hipMemcpyDeviceToHost, st));
+  sync();
+}
+
 void rt_lane::det_preprocess(const uint8_t* rgb, int h, int w, float* out) {
   begin_call();
   uint8_t* d = arena.alloc<uint8_t>((size_t)h * w * 3);
@@ -547,7 +575,8 @@ void emit_stage(const PageCall& call, int page, int stage, const rt_results::Pag
 // ---------------------------------------------------------------------------
 struct PageState {
   int ori_h, ori_w, after_h, after_w, det_h, det_w;
-  const uint8_t* raw;      // device, the caller's page (ori_h x ori_w): what crop_source = Original and the regions are cut from
+  const uint8_t* raw;      // device, the caller's page (ori_h x ori_w; its enhanced copy under the call's page enhance): what
+                           // crop_source = Original and the regions are cut from
   const uint8_t* img;      // device, after resize_both
   const uint8_t* det_img;  // device, det input size (RGB8: the det stem normalises it)
   const float* map;        // device det map used for boxes
@@ -642,6 +671,23 @@ const uint8_t* page_on_device(rt_lane& s, const PageCall& c, int i) {
   RT_HIP_CHECK(hipMemcpyAsync(d, rgb[i], (size_t)hs[i] * ws[i] * 3, hipMemcpyHostToDevice, s.st));
   return d;
 }
+// Page enhance (page_enhance.h; call.set.enhance_tile > 0): every page of the call that is read (all of them, or with `needed` those
+// with needed[i] > 0) put in HBM by page_on_device and enhanced, all in pe::launch's two launches: [n_pages] pointers to the new
+// pages, what PageState::raw becomes (null for a page that is not read).  Off: empty, and nothing is allocated or launched.
+std::vector<const uint8_t*> enhanced_pages(rt_lane& s, const PageCall& c, const int* needed = nullptr) {
+  std::vector<const uint8_t*> out;
+  if (c.set.enhance_tile <= 0) return out;
+  out.assign((size_t)c.n_pages, nullptr);
+  std::vector<const uint8_t*> src, dst; std::vector<int> hs, ws, at;
+  for (int i = 0; i < c.n_pages; i++) {
+    if (needed && needed[i] <= 0) continue;
+    src.push_back(page_on_device(s, c, i)); hs.push_back(c.hs[i]); ws.push_back(c.ws[i]); at.push_back(i);
+  }
+  dst.resize(src.size());
+  s.enhance_pages((int)src.size(), src.data(), hs.data(), ws.data(), c.set.enhance_tile, c.set.enhance_clip_x16, dst.data());
+  for (size_t k = 0; k < at.size(); k++) out[(size_t)at[k]] = dst[k];
+  return out;
+}
 // ---- a2 + a3: size limits, det resize (the normalise is folded into the det stem) ----
 void page_sizes(rt_lane& s, Pipeline& P) {
   const int* hs = P.call.hs; const int* ws = P.call.ws;
@@ -656,10 +702,11 @@ void page_sizes(rt_lane& s, Pipeline& P) {
     std::string why;
     if (dh > 0 && dw > 0 && dt::check_page(dh, dw, &why) == dt::ERR_CAPACITY) throw RtError(RT_ERR_CAPACITY, "page " + std::to_string(i) + ": " + why);
   }
+  const std::vector<const uint8_t*> enhanced = enhanced_pages(s, P.call);
   for (int i = 0; i < P.call.n_pages; i++) {
     PageState& p = P.pg[i];
     p.ori_h = hs[i]; p.ori_w = ws[i];
-    const uint8_t* raw = p.raw = page_on_device(s, P.call, i);
+    const uint8_t* raw = p.raw = enhanced.empty() ? page_on_device(s, P.call, i) : enhanced[(size_t)i];
     p.img = dev_resize_both(&s, raw, hs[i], ws[i], &p.after_h, &p.after_w);
     if (p.after_h <= 0 || p.after_w <= 0) throw RtError(RT_ERR_SHAPE, "page collapses to zero size in resize_both");
     gm::resize_either_dims(p.after_h, p.after_w, s.sh->cfg.det_limit_type, s.sh->cfg.det_limit_side_len, &p.det_h, &p.det_w);
@@ -854,11 +901,12 @@ void region_pages(rt_lane& s, Pipeline& P) {
   for (int i = 0; i < c.n_pages; i++) total_lines += c.n_quads[i];
   P.region_boxes.resize((size_t)total_lines);
   total_lines = 0;
+  const std::vector<const uint8_t*> enhanced = enhanced_pages(s, c, c.n_quads);
   for (int i = 0; i < P.call.n_pages; i++) {
     PageState& p = P.pg[i];
     p.ori_h = p.after_h = c.hs[i]; p.ori_w = p.after_w = c.ws[i]; p.det_h = p.det_w = 0;
     p.n_boxes = c.n_quads[i]; p.first_line = total_lines;
-    p.raw = p.img = p.n_boxes > 0 ? page_on_device(s, c, i) : nullptr;   // (a page without regions is never read)
+    p.raw = p.img = p.n_boxes <= 0 ? nullptr : enhanced.empty() ? page_on_device(s, c, i) : enhanced[(size_t)i];   // (a page without regions is never read)
     p.det_img = nullptr; p.map = nullptr;
     for (int k = 0; k < p.n_boxes; k++) {
       pp::DbBox& b = P.region_boxes[(size_t)total_lines + k];

@@ -22,6 +22,7 @@
 #include "lane_split.h"
 #include "nets.h"
 #include "nets_f16.h"
+#include "page_enhance.h"
 #include "prepost.h"
 #include "rec_line_opts.h"
 #include "rec_tail_plan.h"
@@ -102,12 +103,13 @@ struct LaneWorker {
 // the beam's language model (rt_set_rec_beam_lm, ctc_lm.h; lm = -1: off, and without effect while beam_b = 0) and its word list
 // (rt_set_rec_beam_vocab, ctc_vocab.h; beam_vocab = -1: off, likewise), and the rec flip (rt_set_rec_flip, rec_flip.h; 0 = off).
 // With 0 < flip_cls_below <= 1 the call syncs its lane once more, between the cls stage and the rec plan, to bring the
-// classifier scores to the host
+// classifier scores to the host.  enhance_tile / enhance_clip_x16: the page enhance (rt_set_page_enhance, page_enhance.h; 0 = off)
 struct CallSettings {
   rt::RecLineOpts rec; int det_tile = 0, det_overlap = 0, beam_b = 0, beam_n = 0, rec_window = 0, rec_overlap = 0;
   int lm = -1; float lm_alpha = 0.0f, lm_beta = 0.0f;
   int beam_vocab = -1; float vocab_gamma = 0.0f;
   float flip_cls_below = 0.0f;
+  int enhance_tile = 0, enhance_clip_x16 = 0;
   bool fused() const { return beam_b > 0 && lm >= 0; }
   bool worded() const { return beam_b > 0 && beam_vocab >= 0; }
 };
@@ -316,6 +318,12 @@ struct rt_lane {
   void rec_forward_ragged(const float* nchw, int n, const int* widths, float* out, int* t_out);
   // stages
   void resize_both(const uint8_t* rgb, int h, int w, uint8_t* out, int oh, int ow);
+  // Page enhance (page_enhance.h) of n pages on the device (src[i]: hs[i] x ws[i] RGB8) in the two launches of pe::launch: new
+  // pages and LUTs from `arena`, the descriptors through `pinned`; out[i] = page i enhanced, luts_out[i] (optional) = its LUTs
+  void enhance_pages(int n, const uint8_t* const* src, const int* hs, const int* ws, int tile, int clip_x16, const uint8_t** out,
+                     const uint8_t** luts_out = nullptr);
+  // rt_enhance_page: one host page through enhance_pages
+  void enhance_page(const uint8_t* rgb, int h, int w, int tile, int clip_x16, uint8_t* out);
   void det_preprocess(const uint8_t* rgb, int h, int w, float* out);
   void det_postprocess(const float* pred, int h, int w, int ori_h, int ori_w, float* boxes, float* scores, int max_out,
                        int* n_out);
@@ -445,9 +453,12 @@ struct rt_session : rt_lane {
   // rt_set_rec_flip (rec_flip.h): lines whose classifier score is below rec_flip_below are read both ways up and the reading
   // with the better greedy CTC score is kept; 0 = off.  In (0, 1] every call syncs its lane once more, for the scores
   float rec_flip_below = 0.0f;
+  // rt_set_page_enhance (page_enhance.h): every page of the pipeline calls that follow is contrast-equalised tile-wise before
+  // anything else reads it; enhance_tile = 0: off.  enhance_clip is the caller's value, what the calls carry is clip_x16_of it
+  int enhance_tile = 0; float enhance_clip = 0.0f;
   CallSettings settings() const {
     return {rec_default, det_tile, det_overlap, beam_b, beam_n, rec_window, rec_overlap, beam_lm, lm_alpha, lm_beta, beam_vocab, vocab_gamma,
-            rec_flip_below};
+            rec_flip_below, enhance_tile, enhance_tile ? rt::pe::clip_x16_of(enhance_clip) : 0};
   }
   std::string last_error;
   // rt_charset_create: compiles the set (rt::compile_charset), stores it and returns its id
