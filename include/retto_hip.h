@@ -1065,11 +1065,13 @@ RT_API int rt_broadcast_blobs(const void* id, int rank, int world, int device_id
  * k_dwconv_rows (instead of the column sweep), 10 the angle classifier's blocks as the unfused launch
  * series (instead of k_cls_block), 11 the RSEFPN output convs and the DB head conv as the round-3 launch
  * series over materialised upsampled tensors (instead of the upsampling-aware k_fpn_phase / k_fpn_class /
- * k_fpn_compose).
- * Process-wide; every setting but bits 10 and 11 computes bit-identical results (tests/test_gpu_parity.py
+ * k_fpn_compose), 12 the wide rec-net GEMMs in split-bf16 arithmetic (k_gemm_split, as RT_GEMM_SPLIT=1), 13 those AND the
+ * fused CTC head in split-bf16 arithmetic (k_ctc_head_split, as RT_GEMM_SPLIT=2; bit 12 alone leaves the head on fp32).
+ * Process-wide; every setting but bits 10 - 13 computes bit-identical results (tests/test_gpu_parity.py
  * checks bits 7-9 on whole networks; bit 10 changes the order of the squeeze-excite pooling sums:
  * equal within 1e-6 on the class probabilities; bit 11 changes the summation order of the pre-summed phase
- * weights: equal within 2e-5 on the DB probability map). */
+ * weights: equal within 2e-5 on the DB probability map; bits 12 and 13 are fp32-width arithmetic in another summation
+ * order: line scores within 1e-5). */
 RT_API void rt_debug_set_variants(int gemm_variant, int dw_variant, int flags);
 /* one launch of the fp16 implicit-GEMM conv kernel on host tensors: x [n, cin, h, w], wt [cout, cin, kh, kw], bias [cout] or
  * NULL, "same" padding k/2, stride (sh, sw), act = 0 none / 1 relu / 2 hardswish / 3 swish / 4 sigmoid -> out [n, cout, ho, wo] */
@@ -1087,7 +1089,9 @@ RT_API int rt_bench_gemm_err(rt_session* s, long long M, int K, int N, int varia
  * (as rt_debug_conv16), LAB (has_lab, lab_a, lab_c), residual [M][ld_res] or NULL.  Squeeze-excite: se_scale [n_img][ld_scale]
  * (NULL: none) over img_rows[n_img] consecutive images of M rows in all; se_rows = the row-block table's form (0 = what the
  * networks ask for, 128 or 256).  variant: 0 = production rule, else as rt_bench_gemm.  ctc = -1: the plain GEMM; 0 / 1 / 2: the
- * CTC head with that argmax form (idx_out / prob_out [M]: argmax and its softmax probability per row).  out [(M + 64) * ldc] is
+ * CTC head with that argmax form (idx_out / prob_out [M]: argmax and its softmax probability per row); with variant 40, ctc = 0
+ * runs the split-bf16 head (k_ctc_head_split, GemmKernel::argmax_split in plan_out[0]; K < 128) and ctc = 1 / 2 keep their fp32
+ * wide-tile forms.  out [(M + 64) * ldc] is
  * filled with RT_DEBUG_CANARY before the launch and returned whole.  plan_out[5] = {GemmKernel value (gemm_plan.h), nt, kg, se,
  * bf} of the plan that ran. */
 #define RT_DEBUG_CANARY 0x7FA5C3E1u

@@ -84,7 +84,8 @@ RT_API void rt_debug_set_variants(int gemm_variant, int dw_variant, int flags) {
   nn::g_gemm_dma = (flags & 256) ? 0 : gemm_dma0;
   nn::g_dw_sweep = (flags & 512) ? 0 : dw_sweep0;
   nn::g_fpn_phase_off = (flags & 2048) ? 1 : 0;   // (bit 11: RSEFPN / DB-head convs as the round-3 launch series; not bit-identical: both forms stand against fp64 in tests/test_gpu_fpn_kernels.py)
-  nn::g_gemm_split = (flags & 4096) ? 1 : g_default_gemm_split;   // (bit 12: the split-bf16 form of the wide rec-net GEMMs, opt-in)
+  // (bit 12: the split-bf16 form of the wide rec-net GEMMs, opt-in; bit 13: that and the split-bf16 CTC head)
+  nn::g_gemm_split = (flags & 8192) ? 2 : (flags & 4096) ? 1 : g_default_gemm_split;
   nn::g_cls_fused = (flags & 1024) ? 0 : cls_fused0;   // (bit 10: the classifier's blocks as the unfused launch series; fp32-tolerance equal, not bit-identical)
 }
 // Runs one nh::conv16 launch on host tensors (diagnostics: the numerics tests compare it with torch conv2d).
@@ -286,7 +287,7 @@ RT_API int rt_debug_gemm(rt_session* s, const float* A, long long M, int K, int 
     float* dC = bufs.canary<float>(out_n, s->st);
     const nn::GemmPlan plan = nn::gemm_plan(lda, M, pw.K, N, pw.Npad, ldc, coff, e, stream_cus(s->st));
     nn::gemm(s->st, plan, dA, lda, M, pw.K, pw.w, N, pw.Npad, dC, ldc, coff, e);
-    if (ctc >= 0) nn::argmax_merge(s->st, e.am_max, e.am_idx, e.am_sum, e.am_tiles, M, didx, dprob);
+    if (ctc >= 0) nn::argmax_merge(s->st, e.am_max, e.am_idx, e.am_sum, plan.am_stats, M, didx, dprob);
     RT_HIP_CHECK(hipStreamSynchronize(s->st));
     DevBufs::download(out, dC, out_n);
     if (ctc >= 0) { DevBufs::download(idx_out, didx, (size_t)M); DevBufs::download(prob_out, dprob, (size_t)M); }

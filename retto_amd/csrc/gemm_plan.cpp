@@ -83,6 +83,17 @@ bool split_fits(int lda, long long M, int K, int N, int Npad16, const Epilogue& 
   return M >= 32768 && K > 3 * KC;   // (>= 4 slabs: the request streams read the next tile's id two slabs before a tile ends; it is published in the tile's first slab)
 }
 
+// k_ctc_head_split: the CTC head with the bias in the K padding (channel K: hence K < 128), any row pitch >= K (the head's
+// tokens have pitch K = 120: the kernel masks k >= K itself), the planes of all class tiles within a 2-GB buffer range.
+// epi.act and the LAB are not looked at: no argmax form applies them (the statistic is taken of the logits)
+bool ctc_split_fits(int lda, long long M, int K, int N, int Npad16, const Epilogue& epi) {
+  if (!epi.am_max || !epi.am_idx || !epi.am_sum || epi.residual || epi.a_scale) return false;
+  if (K < 1 || K >= 128 || lda < K || (lda & 3)) return false;   // 16-byte loads of the token rows
+  if ((long long)lda * 4 * 32 >= (1ll << 31)) return false;      // a wave's 32 rows under one buffer descriptor
+  if (N < 1 || Npad16 != round_up(N, 16)) return false;
+  return M >= 1 && (long long)(Npad16 / 16) * (K / KC + 1) * 3072 < (1ll << 31);
+}
+
 // buffer-resource fetch of k_gemm (k_gemm<NT, *, true>): a tile's 128 rows and the packed weights within the 2-GB offset range
 bool bf_fits(int lda, int K, int Npad16) {
   return env().bf && (long long)128 * lda * 4 < (1ll << 31) && (long long)((K + KC - 1) / KC) * Npad16 * KC * 4 < (1ll << 31);
@@ -95,7 +106,8 @@ int bucket(int n, std::initializer_list<int> sizes) {
   return *(sizes.end() - 1);
 }
 
-GemmPlan plan(int lda, long long M, int K, int N, int Npad16, int ldc, int coff, const Epilogue& epi, int cus, bool split_on) {
+GemmPlan plan(int lda, long long M, int K, int N, int Npad16, int ldc, int coff, const Epilogue& epi, int cus, int split) {
+  const bool split_on = split != 0;
   GemmPlan p;
   auto take = [&](GemmKernel k, const char* label, long long gx = 0, long long gy = 0) {
     p.kernel = k; p.label = label; p.grid_x = (unsigned)gx; p.grid_y = (unsigned)gy;
@@ -110,8 +122,13 @@ GemmPlan plan(int lda, long long M, int K, int N, int Npad16, int ldc, int coff,
   if (M <= 0) return take(GemmKernel::none, "gemm_pw/none");
   if (epi.am_max) {  // CTC head: softmax statistics per column tile instead of the logits (argmax_merge folds them)
     if (epi.am_tiles != gemm_argmax_tiles(Npad16)) return fail("gemm: am_tiles must be gemm_argmax_tiles(Npad16)");
+    p.am_stats = epi.am_tiles;
     if (g_argmax_wide == 1) return take(GemmKernel::argmax_256x240, "gemm_ctc_fc", rb256, cb240);
     if (g_argmax_wide == 2) return take(GemmKernel::argmax_128x128, "gemm_ctc_fc", rb128, cb128);
+    if ((g_gemm_variant == 40 || (!g_gemm_variant && split >= 2)) && ctc_split_fits(lda, M, K, N, Npad16, epi)) {
+      p.am_stats = 1;   // the row's final triple
+      return take(GemmKernel::argmax_split, "gemm_ctc_fc", rb128, 1);
+    }
     p.nt = 8; p.bf = bf_fits(lda, K, Npad16);   // narrow kernel, 128-column blocks
     return take(GemmKernel::argmax_narrow, "gemm_ctc_fc", rb128, cb128);
   }
@@ -169,7 +186,7 @@ GemmPlan plan(int lda, long long M, int K, int N, int Npad16, int ldc, int coff,
 }  // namespace
 
 GemmPlan gemm_plan(int lda, long long M, int K, int N, int Npad16, int ldc, int coff, const Epilogue& epi, int cus) {
-  return plan(lda, M, K, N, Npad16, ldc, coff, epi, cus, g_gemm_split != 0);
+  return plan(lda, M, K, N, Npad16, ldc, coff, epi, cus, g_gemm_split);
 }
 
 int gemm_se_rows(int lda, long long M, int K, int N, int Npad16, int act, long long min_pix) {
@@ -181,7 +198,7 @@ int gemm_se_rows(int lda, long long M, int K, int N, int Npad16, int act, long l
   probe.act = act; probe.a_scale = &scale; probe.ld_scale = lda; probe.a_tab = &tab; probe.n_img = 1;
   for (const int stride : {3, 2}) {
     probe.a_tab_stride = stride;
-    if (plan(lda, M, K, N, Npad16, chan_pitch(N), 0, probe, 0, false).se) return stride == 3 ? 256 : 128;
+    if (plan(lda, M, K, N, Npad16, chan_pitch(N), 0, probe, 0, 0).se) return stride == 3 ? 256 : 128;
   }
   return 0;
 }

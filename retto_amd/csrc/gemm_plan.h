@@ -9,9 +9,11 @@ namespace nn {
 // Switches of the decision (defaults in gemm_plan.cpp; the RT_GEMM_W / _MID / _OCC / _BF and RT_GS_ONLY environment variables are
 // read there once).
 extern int g_gemm_variant;  // kernel micro-benchmark hook (rt_bench_gemm): 0 = production choice; 1 narrow, 8 / 10 / 15 wide tiles,
-                            // 20 streaming, 30 k_gemm32p, 40 k_gemm_split (falling back 40 -> 30 -> 15 where a form does not apply)
+                            // 20 streaming, 30 k_gemm32p, 40 k_gemm_split (falling back 40 -> 30 -> 15 where a form does not apply;
+                            // on the CTC head with g_argmax_wide == 0: k_ctc_head_split, else the fp32 form)
 extern int g_gemm_dma;      // A/B: persistent LDS-DMA wide GEMM on (default) / off
-extern int g_gemm_split;    // opt-in: split-bf16 form of the wide layers (RT_GEMM_SPLIT=1, rt_debug_set_variants flag bit 12)
+extern int g_gemm_split;    // opt-in: 1 = split-bf16 form of the wide layers (RT_GEMM_SPLIT=1, rt_debug_set_variants flag bit 12);
+                            // 2 = those and the CTC head (RT_GEMM_SPLIT=2, flag bit 13)
 extern int g_argmax_wide;   // CTC head: 0 = narrow kernel with 128-column blocks; 2 = 128 x 128 wide tile; 1 = 256 x 240 tile
 
 int env_int(const char* name, int def);   // an integer switch of the environment, or its default
@@ -37,6 +39,7 @@ enum class GemmKernel {
   argmax_256x240,  // CTC head (Epilogue::am_*): k_gemm_wide<4,5,4,3,0,0,0,1>
   argmax_128x128,  //   k_gemm_wide<2,4,4,2,0,0,0,1>
   argmax_narrow,   //   k_gemm<8,1> (bf)
+  argmax_split,    //   k_ctc_head_split: ctc_head_split(); one statistic per row
 };
 
 struct GemmPlan {
@@ -44,6 +47,7 @@ struct GemmPlan {
   bool se = false;               // the squeeze-excite scale (Epilogue::a_scale) is folded into the A staging
   int nt = 0, kg = 0;            // k_gemm<nt>; k_gemm_stream<nt, kg>
   bool bf = false;               // k_gemm<nt, *, true>
+  int am_stats = 0;              // CTC head: statistics per row the kernel leaves (the `tiles` of argmax_merge): am_tiles, or 1
   unsigned grid_x = 0, grid_y = 0;   // register-staged wide tiles, stream and narrow kernels (the persistent ones size their own)
   const char* label = nullptr;   // profiler label of a pointwise-conv GEMM that runs this kernel
   const char* error = nullptr;   // kernel == invalid

@@ -689,10 +689,11 @@ float* SvtrCore::head(RunCtx& c, const float* z5, long long rows, int* idx_out, 
     e.am_sum = c.arena->alloc<float>((size_t)rows * tiles);
     e.am_idx = c.arena->alloc<int>((size_t)rows * tiles);
     e.am_tiles = tiles;
+    const nn::GemmPlan plan = nn::gemm_plan(D, rows, fc.K, classes, fc.Npad, 0, 0, e, stream_cus(c.st));
     { ProfScope ps(c.prof, c.st, "gemm_ctc_fc", shape_str(rows, fc.K, classes, 1));
-      nn::gemm(c.st, z5, D, rows, fc.K, fc.w, classes, fc.Npad, nullptr, 0, 0, e); }
-    { ProfScope ps(c.prof, c.st, "ctc_argmax");
-      nn::argmax_merge(c.st, e.am_max, e.am_idx, e.am_sum, tiles, rows, idx_out, prob_out); }
+      nn::gemm(c.st, plan, z5, D, rows, fc.K, fc.w, classes, fc.Npad, nullptr, 0, 0, e); }
+    { ProfScope ps(c.prof, c.st, "ctc_argmax");   // (plan.am_stats: `tiles` per row, or the split head's one)
+      nn::argmax_merge(c.st, e.am_max, e.am_idx, e.am_sum, plan.am_stats, rows, idx_out, prob_out); }
     return nullptr;
   }
   const int ld = round_up(classes, 4);

@@ -29,6 +29,12 @@ void gemm_dma(hipStream_t st, const float* A, int lda, long long M, int K, const
 void gemm_split(hipStream_t st, const float* A, int lda, long long M, int K, const float* Wp, int N, int Npad16, float* C,
                 int ldc, int coff, const Epilogue& epi);
 void gemm_split_forget(const float* Wp);   // drops the cached split planes of a weight pack (before its memory is freed / reused)
+// Split-bf16 form of the fused CTC head (k_ctc_head_split, nn_gemm_split.hip; GemmKernel::argmax_split): the token tile stays in
+// registers, the class weights stream through LDS, and every row's final (max, class, sum exp) lands in epi.am_max / am_idx /
+// am_sum[row] -- ONE statistic per row (GemmPlan::am_stats), which argmax_merge turns into idx and prob.  Its planes are cached
+// and forgotten with the pack like gemm_split's; they hold epi.bias (as weight row K), so a pack is always called with the bias
+// it was first called with -- the networks' packs own theirs -- and a call with another throws.  Opt-in: g_gemm_split >= 2 (RT_GEMM_SPLIT=2, rt_debug_set_variants flag bit 13).
+void ctc_head_split(hipStream_t st, const float* A, int lda, long long M, int K, const float* Wp, int N, int Npad16, const Epilogue& epi);
 
 // Dense stride-1 "same" convolution, kernel (KH,KW) in {(3,3),(1,3)}; W packed as
 // [ceil(Cin/KC)][KH*KW][Npad16][KC].

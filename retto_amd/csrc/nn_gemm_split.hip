@@ -506,30 +506,39 @@ __global__ __launch_bounds__(S_NTHR, 2) void k_gemm_split(const GemmSArgs g) {
 // ---- host side ----------------------------------------------------------------------------------------------------------------
 // the split planes of a packed fp32 weight matrix, built on first use and kept for the life of the process (keyed by the
 // device pointer of the fp32 pack: the networks' weights live as long as their session)
+// (a pack has up to two sets of planes: k_gemm_split's layout and k_ctc_head_split's; both go when the pack is forgotten)
+// (the head's planes hold the bias as weight row K: head_bias is the bias they were built from, and a call with another is refused)
+struct SplitPlanes { unsigned short* gemm = nullptr; unsigned short* head = nullptr; const float* head_bias = nullptr; bool head_checked = false; };
 static std::mutex g_split_mu;
-static std::map<std::pair<int, const float*>, unsigned short*> g_split_cache;
-static const unsigned short* split_pack_of(hipStream_t st, const float* Wp, int nslab, int Npad, int n_cb) {
+static std::map<std::pair<int, const float*>, SplitPlanes> g_split_cache;
+// the planes of `Wp` in the layout of `slot`: `bytes` of them, written by launch(p) on `st`
+template <typename Launch>
+static const unsigned short* planes_of(hipStream_t st, const float* Wp, unsigned short* SplitPlanes::*slot, size_t bytes, Launch launch) {
   int dev = 0;
   RT_HIP_CHECK(hipGetDevice(&dev));
   std::lock_guard<std::mutex> lk(g_split_mu);
   auto it = g_split_cache.find({dev, Wp});
-  if (it != g_split_cache.end()) return it->second;
+  if (it != g_split_cache.end() && it->second.*slot) return it->second.*slot;
   // First use of this pack on this device: build the planes and WAIT for them before the entry becomes visible -- the session's
   // lanes launch the same layers from their own threads on their own streams, and a lane that found the entry while the pack
   // kernel was still queued on another lane's stream multiplied by whatever the allocation held.
   unsigned short* p = nullptr;
-  const size_t bytes = (size_t)n_cb * nslab * S_WSLAB;
   RT_HIP_CHECK(hipMalloc((void**)&p, bytes + 65536));   // (+ slack behind the last group)
   hipError_t e = hipMemsetAsync(p, 0, bytes + 65536, st);
   if (e == hipSuccess) {
-    const long long total = (long long)n_cb * nslab * S_NT * 64;
-    hipLaunchKernelGGL(k_split_pack, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, Wp, nslab, Npad, n_cb, p);
+    launch(p);
     e = hipGetLastError();
   }
   if (e == hipSuccess) e = hipStreamSynchronize(st);
   if (e != hipSuccess) { (void)hipFree(p); throw RtError(4, std::string("gemm_split: building the split planes failed: ") + hipGetErrorString(e)); }
-  g_split_cache[{dev, Wp}] = p;
+  g_split_cache[{dev, Wp}].*slot = p;
   return p;
+}
+static const unsigned short* split_pack_of(hipStream_t st, const float* Wp, int nslab, int Npad, int n_cb) {
+  return planes_of(st, Wp, &SplitPlanes::gemm, (size_t)n_cb * nslab * S_WSLAB, [&](unsigned short* p) {
+    const long long total = (long long)n_cb * nslab * S_NT * 64;
+    hipLaunchKernelGGL(k_split_pack, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, Wp, nslab, Npad, n_cb, p);
+  });
 }
 
 void gemm_split_forget(const float* Wp) {
@@ -537,7 +546,7 @@ void gemm_split_forget(const float* Wp) {
   if (hipGetDevice(&dev) != hipSuccess) return;
   std::lock_guard<std::mutex> lk(g_split_mu);
   auto it = g_split_cache.find({dev, Wp});
-  if (it != g_split_cache.end()) { (void)hipFree(it->second); g_split_cache.erase(it); }
+  if (it != g_split_cache.end()) { (void)hipFree(it->second.gemm); (void)hipFree(it->second.head); g_split_cache.erase(it); }
 }
 
 void gemm_split(hipStream_t st, const float* A, int lda, long long M, int K, const float* Wp, int N, int Npad16, float* C,
@@ -571,6 +580,233 @@ void gemm_split(hipStream_t st, const float* A, int lda, long long M, int K, con
   else if (epi.act == ACT_HSWISH) RT_GS(ACT_HSWISH, 0);
   else RT_GS(-1, -1);
 #undef RT_GS
+}
+
+// ---- split-bf16 CTC head ------------------------------------------------------------------------------------------------------
+// rows x K x N with K < 128 and N in the thousands (120 x 6625), followed by a softmax statistic instead of a store: the token
+// tile stays, the classes stream.
+//   * a workgroup owns 128 rows, a wave 32 of them (two 16-row blocks).  The wave loads its rows ONCE from global memory (any
+//     pitch >= K, no pad channels needed: k >= K is masked), splits them once and keeps the three planes of all NSLAB = K / 32 + 1
+//     slabs in registers for the whole launch: 2 x NSLAB x 3 x 4 = 96 VGPRs at K = 120;
+//   * the bias rides in the K padding: token channel K holds 1.0 (exact in the h plane), weight row K holds the bias split into
+//     its three planes, and ah wh + ah wm + ah wl -- three of the six kept terms -- add it exactly.  Hence K < 128 (K % 32 == 0
+//     costs one more slab);
+//   * the weights are split once on the device into [16-class tile][slab][plane h, m, l][lane][8 bf16] (3 KB per slab, 12 KB per
+//     tile at NSLAB = 4); lane (r, q) element e holds class 16 ct + r, k = 32 slab + 8 q + e, the k order of the token fragments;
+//   * the class tiles pass through a ring of FOUR tile buffers in LDS (48 KB; with 152 VGPRs that leaves room for three workgroups per
+//     CU -- a C3 launch has 400 workgroups for 256 CUs, so one or two are resident), requested three tiles ahead
+//     by buffer_load ... lds, every wave a quarter of the tile's 1-KB pieces; one workgroup barrier per tile.  A request for a
+//     tile that does not exist carries an out-of-range offset and writes zeros, so every wave issues the same count per tile and
+//     the vmcnt wait is one number;
+//   * per tile and wave: NSLAB x 2 x 6 MFMAs into 2 x 4 accumulator registers; lane (r, q) then holds the logits of row r,
+//     classes 16 ct + 4 q .. + 3.  The statistic of tile ct - 1 (even and odd tiles have their own accumulators) is computed
+//     behind the first slab's MFMAs of tile ct, so that its VALU work does not wait for the matrix pipe to drain;
+//   * the statistic: per lane a running (max, first class of it, sum exp(l - max)) over the lane's classes in ascending order,
+//     one exp per logit (e = exp(-|l - max|): sum = sum e + 1 when the max moves, sum += e otherwise); classes >= N take no
+//     part.  The four lanes of a row are folded once, at the end, the lowest class winning a tie; lane q = 0 writes the row's
+//     triple.  No state outlives the launch: one workgroup per row tile, no queue.
+constexpr int H_BM = 128, H_NB = 4, H_AHEAD = 3, H_NTHR = 256;
+constexpr unsigned H_SLAB_B = 3 * 1024;   // one slab of a class tile: planes h, m, l
+
+struct CtcHeadArgs {
+  const float* A; const unsigned short* Ws;
+  float* am_max; int* am_idx; float* am_sum;
+  long long M;
+  int lda, K, N, n_ct;
+};
+
+// fp32 packed weights [ceil(K / 32)][Npad][32] (+ bias [Npad] or null) -> [ct][slab][plane][lane][8]
+__global__ void k_ctc_split_pack(const float* __restrict__ Wp, const float* __restrict__ bias, int K, int nslab, int N, int Npad,
+                                 unsigned short* __restrict__ out) {
+  const long long total = (long long)(Npad / 16) * nslab * 64;
+  for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
+    const int lane = (int)(i & 63);
+    const long long t = i >> 6;
+    const int slab = (int)(t % nslab), ct = (int)(t / nslab);
+    const int r = lane & 15, q = lane >> 4;
+    const int n = ct * 16 + r;
+    unsigned short* o = out + ((long long)ct * nslab + slab) * (H_SLAB_B / 2) + lane * 8;
+    for (int e = 0; e < 8; e++) {
+      const int kk = 8 * q + e, k = slab * KC + kk;
+      float w = 0.f;
+      if (k < K) w = Wp[((long long)slab * Npad + n) * KC + kk];
+      else if (k == K && bias && n < N) w = bias[n];
+      const unsigned h = cvt_pk_bf16(w, 0.f) & 0xffffu;
+      const float r1 = w - __uint_as_float(h << 16);
+      const unsigned m = cvt_pk_bf16(r1, 0.f) & 0xffffu;
+      const float r2 = r1 - __uint_as_float(m << 16);
+      const unsigned l = cvt_pk_bf16(r2, 0.f) & 0xffffu;
+      o[e] = (unsigned short)h; o[512 + e] = (unsigned short)m; o[1024 + e] = (unsigned short)l;
+    }
+  }
+}
+
+template <int NSLAB>
+__global__ __launch_bounds__(H_NTHR, 2) void k_ctc_head_split(const CtcHeadArgs g) {
+  constexpr unsigned TILE_B = NSLAB * H_SLAB_B;
+  constexpr int NP = 3 * NSLAB;   // 1-KB pieces of a class tile: wave w requests w, w + 4, w + 8
+  __shared__ __attribute__((aligned(16))) unsigned char ring[H_NB * TILE_B];
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int r = lane & 15, q = lane >> 4;
+  const unsigned lds_b = __builtin_amdgcn_readfirstlane(lds_addr(ring));
+  const long long m0 = (long long)blockIdx.x * H_BM + 32 * wid;
+
+  // ---- the wave's tokens: loaded, split and kept ----------------------------------------------------------------------------------
+  // (a descriptor over the wave's rows below M: rows past M read zeros.  A 16-byte chunk is requested when it BEGINS below K --
+  //  it then ends within the row, lda being a multiple of 4 -- and what it holds at k >= K is replaced: 1.0 at K, zeros beyond)
+  u32x4 Th[2][NSLAB], Tm[2][NSLAB], Tl[2][NSLAB];
+  {
+    const unsigned rows_here = (unsigned)max(0ll, min(32ll, g.M - m0)), pitch = (unsigned)g.lda * 4u;
+    const __amdgpu_buffer_rsrc_t ars =
+        __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(g.A + (rows_here ? m0 * g.lda : 0)), 0, rows_here * pitch, 0x00020000);
+#pragma unroll
+    for (int mt = 0; mt < 2; mt++)
+#pragma unroll
+      for (int s = 0; s < NSLAB; s++) {
+        const int k0 = KC * s + 8 * q;
+        const unsigned off = (unsigned)(16 * mt + r) * pitch + (unsigned)k0 * 4u;
+        f32x4 x[2];
+#pragma unroll
+        for (int h = 0; h < 2; h++) {
+          const int kc = k0 + 4 * h;
+          x[h] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(ars, kc < g.K ? off + 16u * h : 0x80000000u, 0, 0));
+#pragma unroll
+          for (int e = 0; e < 4; e++) x[h][e] = kc + e < g.K ? x[h][e] : (kc + e == g.K ? 1.0f : 0.0f);
+        }
+        split8(x[0], x[1], Th[mt][s], Tm[mt][s], Tl[mt][s]);
+      }
+  }
+
+  // ---- class tile requests --------------------------------------------------------------------------------------------------------
+  const __amdgpu_buffer_rsrc_t wrs =
+      __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned short*>(g.Ws), 0, (unsigned)g.n_ct * TILE_B, 0x00020000);
+  const int n_w = (wid < NP ? 1 : 0) + (wid + 4 < NP ? 1 : 0) + (wid + 8 < NP ? 1 : 0);   // requests of this wave per tile
+  auto request = [&](int c) __attribute__((always_inline)) {
+    const unsigned src = c < g.n_ct ? (unsigned)c * TILE_B + (unsigned)lane * 16u : 0x80000000u;
+    const unsigned dst = lds_b + (unsigned)(c & (H_NB - 1)) * TILE_B;
+#pragma unroll
+    for (int i = 0; i < 3; i++) {
+      const int p = wid + 4 * i;
+      if (p < NP) blds16(src + (unsigned)p * 1024u, wrs, dst + (unsigned)p * 1024u, 0u);
+    }
+    __builtin_amdgcn_sched_barrier(0);
+  };
+
+  // ---- the running statistic of the lane's classes, per 16-row block ---------------------------------------------------------------
+  float sm[2] = {-INFINITY, -INFINITY}, ss[2] = {0.f, 0.f};
+  int si[2] = {0x7fffffff, 0x7fffffff};
+  auto stat = [&](const f32x4 (&a)[2], int ct) __attribute__((always_inline)) {
+    const int col = ct * 16 + 4 * q;
+#pragma unroll
+    for (int mt = 0; mt < 2; mt++)
+#pragma unroll
+      for (int j = 0; j < 4; j++) {
+        const float v = a[mt][j];
+        const bool ok = col + j < g.N;
+        const float d = v - sm[mt];                 // (+inf at the lane's first class: e = 0, sum = 1)
+        const float e = __expf(-fabsf(d));
+        const bool up = ok && d > 0.f;
+        ss[mt] = up ? fmaf(ss[mt], e, 1.0f) : (ok ? ss[mt] + e : ss[mt]);
+        sm[mt] = up ? v : sm[mt];
+        si[mt] = up ? col + j : si[mt];
+      }
+  };
+
+#pragma unroll
+  for (int c = 0; c < H_AHEAD; c++) request(c);
+  // One class tile into `acc`, with the statistic of the tile before it (in `prev`) behind the first slab's MFMAs.  The walk below
+  // is unrolled by two with the roles of the two accumulator sets swapped: no hand-over copy that would wait for the last MFMAs.
+  auto tile = [&](int c, f32x4 (&acc)[2], const f32x4 (&prev)[2]) __attribute__((always_inline)) {
+    // tile c has landed: this wave's pieces (the two tiles requested since may stay in flight), then everybody's.  The barrier
+    // also says that every wave has read tile c - 1 out of its buffer, which the request for tile c + 3 overwrites.
+    vm_wait<2 * 3>(2 * n_w);
+    __builtin_amdgcn_sched_barrier(0);
+    __builtin_amdgcn_s_barrier();
+    __builtin_amdgcn_sched_barrier(0);
+    request(c + H_AHEAD);
+    const unsigned fr = lds_b + (unsigned)(c & (H_NB - 1)) * TILE_B + (unsigned)lane * 16u;
+    u32x4 Bf[2][3];
+    Bf[0][0] = lds_read16<u32x4, 0>(fr); Bf[0][1] = lds_read16<u32x4, 1024>(fr); Bf[0][2] = lds_read16<u32x4, 2048>(fr);
+    acc[0] = acc[1] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int s = 0; s < NSLAB; s++) {
+      const int b = s & 1;
+      if (s + 1 < NSLAB) {
+        const unsigned fn = fr + (unsigned)(s + 1) * H_SLAB_B;
+        Bf[b ^ 1][0] = lds_read16<u32x4, 0>(fn); Bf[b ^ 1][1] = lds_read16<u32x4, 1024>(fn); Bf[b ^ 1][2] = lds_read16<u32x4, 2048>(fn);
+        lgkm_wait<3>();
+      } else {
+        lgkm_wait<0>();
+      }
+      // the six kept terms, the small ones first (k_gemm_split's order)
+#pragma unroll
+      for (int mt = 0; mt < 2; mt++) acc[mt] = mfma_bf16(Bf[b][2], Th[mt][s], acc[mt]);
+#pragma unroll
+      for (int mt = 0; mt < 2; mt++) acc[mt] = mfma_bf16(Bf[b][0], Tl[mt][s], acc[mt]);
+#pragma unroll
+      for (int mt = 0; mt < 2; mt++) acc[mt] = mfma_bf16(Bf[b][1], Tm[mt][s], acc[mt]);
+#pragma unroll
+      for (int mt = 0; mt < 2; mt++) acc[mt] = mfma_bf16(Bf[b][1], Th[mt][s], acc[mt]);
+#pragma unroll
+      for (int mt = 0; mt < 2; mt++) acc[mt] = mfma_bf16(Bf[b][0], Tm[mt][s], acc[mt]);
+#pragma unroll
+      for (int mt = 0; mt < 2; mt++) acc[mt] = mfma_bf16(Bf[b][0], Th[mt][s], acc[mt]);
+      if (s == 0 && c > 0) stat(prev, c - 1);
+    }
+  };
+  f32x4 even[2] = {}, odd[2] = {};   // accumulators of the even / odd class tiles
+  for (int c = 0; c < g.n_ct; c += 2) {
+    tile(c, even, odd);
+    if (c + 1 < g.n_ct) tile(c + 1, odd, even);
+  }
+  vm_wait<0>();   // (the requests for tiles past the last one write zeros into the ring)
+  if (g.n_ct > 0) { if (g.n_ct & 1) stat(even, g.n_ct - 1); else stat(odd, g.n_ct - 1); }
+
+  // ---- the four lanes of a row -> its triple; the lowest class wins a tie -------------------------------------------------------------
+#pragma unroll
+  for (int mt = 0; mt < 2; mt++) {
+    float m = sm[mt], sum = ss[mt];
+    int mi = si[mt];
+#pragma unroll
+    for (int d = 16; d < 64; d <<= 1) {
+      const float om = __shfl_xor(m, d), os = __shfl_xor(sum, d);
+      const int oi = __shfl_xor(mi, d);
+      const float nm = fmaxf(m, om);
+      sum = sum * (m == nm ? 1.0f : __expf(m - nm)) + os * (om == nm ? 1.0f : __expf(om - nm));
+      if (om > m || (om == m && oi < mi)) mi = oi;
+      m = nm;
+    }
+    const long long row = m0 + 16 * mt + r;
+    if (q == 0 && row < g.M) { g.am_max[row] = m; g.am_sum[row] = sum; g.am_idx[row] = mi; }
+  }
+}
+
+void ctc_head_split(hipStream_t st, const float* A, int lda, long long M, int K, const float* Wp, int N, int Npad16, const Epilogue& epi) {
+  CtcHeadArgs g;
+  g.A = A; g.M = M; g.lda = lda; g.K = K; g.N = N; g.n_ct = Npad16 / 16;
+  g.am_max = epi.am_max; g.am_idx = epi.am_idx; g.am_sum = epi.am_sum;
+  const int nslab = K / KC + 1;   // (channel K carries the bias)
+  g.Ws = planes_of(st, Wp, &SplitPlanes::head, (size_t)g.n_ct * nslab * H_SLAB_B, [&](unsigned short* p) {
+    const long long total = (long long)g.n_ct * nslab * 64;
+    hipLaunchKernelGGL(k_ctc_split_pack, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, Wp, epi.bias, K, nslab, N, Npad16, p);
+  });
+  {   // the planes carry the bias they were built with
+    int dev = 0;
+    RT_HIP_CHECK(hipGetDevice(&dev));
+    std::lock_guard<std::mutex> lk(g_split_mu);
+    SplitPlanes& e = g_split_cache[{dev, Wp}];
+    if (!e.head_checked) { e.head_bias = epi.bias; e.head_checked = true; }
+    else if (e.head_bias != epi.bias) throw RtError(8, "ctc_head_split: this weight pack's planes were built with another bias");
+  }
+  const dim3 grid((unsigned)((M + H_BM - 1) / H_BM));
+  switch (nslab) {
+    case 1: RT_LAUNCH((k_ctc_head_split<1>), grid, dim3(H_NTHR), 0, st, g); return;
+    case 2: RT_LAUNCH((k_ctc_head_split<2>), grid, dim3(H_NTHR), 0, st, g); return;
+    case 3: RT_LAUNCH((k_ctc_head_split<3>), grid, dim3(H_NTHR), 0, st, g); return;
+    case 4: RT_LAUNCH((k_ctc_head_split<4>), grid, dim3(H_NTHR), 0, st, g); return;
+  }
+  throw RtError(8, "ctc_head_split: K must be below 128");
 }
 
 }  // namespace nn

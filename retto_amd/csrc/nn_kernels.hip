@@ -783,6 +783,7 @@ void gemm(hipStream_t st, const GemmPlan& p, const float* A, int lda, long long 
       if (p.bf) RT_LAUNCH((k_gemm<8, 1, true>), grid, dim3(256), 0, st, RT_GEMM_ARGS);
       else RT_LAUNCH((k_gemm<8, 1>), grid, dim3(256), 0, st, RT_GEMM_ARGS);
       return;
+    case GemmKernel::argmax_split: ctc_head_split(st, A, lda, M, K, Wp, N, Npad16, epi); return;
   }
 #undef RT_GEMM_ARGS
   throw RtError(8, "gemm: the plan names no kernel instance");
