@@ -369,6 +369,39 @@ RT_API int rt_enhance_page(rt_session* s, const uint8_t* rgb, int h, int w, int 
 /* The rule on the CPU, in plain loops over the same header; GPU-free and sessionless (rt_last_error(NULL)).  luts_out (optional):
  * the tiles' tables, ceil(h / tile) * ceil(w / tile) * 256 bytes in row-major tile order (not written for tile = 0). */
 RT_API int rt_debug_enhance_page_host(const uint8_t* rgb, int h, int w, int tile, float clip, uint8_t* out, uint8_t* luts_out);
+/* Page flatten (retto_amd/csrc/page_flatten.h states the rule): every page divided, channel by channel, by the paper level
+ * estimated around each pixel, before anything reads it -- flat-fielding, the "scanner app" filter.  A photographed page with a
+ * shadow across it or under a coloured lamp is not served by equalisation: a shadow edge inside a tile stays an edge, the texture
+ * of the dark half is amplified, and a colour cast stays because only the luma moves.  Dividing by the level makes paper white,
+ * keeps ink's relative darkness and removes the illumination gradient and the cast.  With flatten on, every page of rt_run_batch,
+ * rt_run_batch_stream, rt_submit_batch, the encoded entry points (after decoding, on the host or on the device) and
+ * rt_run_regions* is flattened on the GPU as soon as it is in device memory, into a NEW buffer -- a caller's RT_MEM_DEVICE page is
+ * never written -- and resize_both, the detector, both crop sources and the regions read the flattened page.  With page enhance
+ * on as well the order is fixed: a page is flattened first and the flattened page is enhanced, enhance(flatten(page)).  Box
+ * coordinates, a det_map_override and everything downstream are untouched.  All pages of a lane's part share three launches.
+ * The rule is 32-bit integer arithmetic throughout, so rt_flatten_page, the pipeline and rt_debug_flatten_page_host agree byte
+ * for byte.  Per channel: the page is pooled into cells of 4 x 4 pixels by their maximum (edge cells partial, no padding); the
+ * cell grid is closed with a (2 radius + 1)^2 window clipped to the grid (max, then min: strokes narrower than the window leave no
+ * trace) and smoothed with the same window's mean, (S + n / 2) / n over its n cells; the level L at a pixel is the bilinear
+ * blend of that grid at the cell centres in 1 / 64 units (the nearest cells alone towards the border), raised to at least
+ * 64 floor; and the channel becomes min(255, (p * 16320 + L / 2) / L).  A channel equal to its level maps to 255; the floor keeps
+ * large dark areas (photographs, black bars) from being blown up to noise.
+ * radius = 0: off, the default (floor is then ignored); otherwise 1 <= radius <= 16 (cells) and 1 <= floor <= 255.  Anything
+ * else: RT_ERR_INVALID naming the parameter.  The setting holds for the pipeline calls that follow on every lane (rt_submit_*
+ * takes it as it is at the call); fails like every other call while tickets are in flight.  With flatten off nothing is launched
+ * or allocated that was not before.
+ * Not supported: per-page or per-region settings; flattening inside the stage functions (rt_resize_both, rt_det_preprocess,
+ * rt_crop_images take the page as it is).  What flattening does to recognition accuracy with trained PP-OCRv4 weights has NOT
+ * been measured (the weights here are synthetic). */
+RT_API int rt_set_page_flatten(rt_session* s, int radius, int floor);
+/* the setting (each optional); RT_ERR_INVALID for a NULL session */
+RT_API int rt_page_flatten(const rt_session* s, int* radius, int* floor);
+/* stage function beside rt_enhance_page: one RGB8 HWC page in host memory through the pipeline's own launcher, into out
+ * [h * w * 3] (host).  radius and floor as above, whatever the session's setting is; radius = 0 copies the page. */
+RT_API int rt_flatten_page(rt_session* s, const uint8_t* rgb, int h, int w, int radius, int floor, uint8_t* out);
+/* The rule on the CPU, in plain loops over the same header; GPU-free and sessionless (rt_last_error(NULL)).  level_out (optional):
+ * the smoothed level per channel, 3 * ceil(h / 4) * ceil(w / 4) bytes as [3][gh][gw] (not written for radius = 0). */
+RT_API int rt_debug_flatten_page_host(const uint8_t* rgb, int h, int w, int radius, int floor, uint8_t* out, uint8_t* level_out);
 /* The pipeline over regions the caller already knows (form fields, subtitles, corrected boxes, another detector's boxes):
  * quads[i] = n_quads[i] x 8 floats in host memory, TL, TR, BR, BL of each region in original-page coordinates; mem
  * (RT_MEM_HOST or RT_MEM_DEVICE) says where the pages live.  Every coordinate is clamped to [0, ori - 1] (no rounding); line k

@@ -580,6 +580,18 @@ def debug_enhance_page_host(img: np.ndarray, tile: int, clip: float = 2.5, with_
     return (out, luts) if with_luts else out
 
 
+def debug_flatten_page_host(img: np.ndarray, radius: int, floor: int = 64, with_level: bool = False):
+    """rt_debug_flatten_page_host: the page flatten rule (retto_amd/csrc/page_flatten.h) on the CPU, GPU-free: the flattened RGB8
+    page [h, w, 3]; with_level: (page, level [3, ceil(h / 4), ceil(w / 4)]), the smoothed paper level B per channel."""
+    lib = _lib.load()
+    img = np.ascontiguousarray(img, np.uint8); h, w = img.shape[:2]
+    out = np.empty((h, w, 3), np.uint8)
+    level = np.zeros((3, -(-h // 4), -(-w // 4)), np.uint8) if with_level and radius > 0 else None
+    _check(lib.rt_debug_flatten_page_host(img.ctypes.data, h, w, int(radius), int(floor), out.ctypes.data,
+                                          None if level is None else level.ctypes.data), None)
+    return (out, level) if with_level else out
+
+
 _WINDOW_PLAN_BUFS = None   # the three output arrays of rec_window_plan, grown on demand, as det_tile_plan's
 
 
@@ -872,6 +884,28 @@ class RettoSession:
         img = np.ascontiguousarray(img, np.uint8); h, w = img.shape[:2]
         out = np.empty((h, w, 3), np.uint8)
         _check(self._hd.lib.rt_enhance_page(self._hd.h, img.ctypes.data, h, w, int(tile), float(clip), out.ctypes.data), self._hd.h)
+        return out
+
+    # -- page flatten -----------------------------------------------------------------------
+    def set_page_flatten(self, radius: int, floor: int = 64) -> None:
+        """rt_set_page_flatten: every page of the pipeline calls that follow is divided, channel by channel, by the paper level
+        estimated around each pixel (flat-fielding, retto_amd/csrc/page_flatten.h) on the GPU before anything else reads it, page
+        enhance included; 0 = off, the default.  radius: the closing's reach in 4-pixel cells, in [1, 16]; floor: the lowest
+        level divided by, in [1, 255].  The effect on accuracy with the real weights is not measured."""
+        _check(self._hd.lib.rt_set_page_flatten(self._hd.h, int(radius), int(floor)), self._hd.h)
+
+    def page_flatten(self) -> Tuple[int, int]:
+        """rt_page_flatten: (radius, floor) as set; radius 0 = off."""
+        r, f = C.c_int(), C.c_int()
+        _check(self._hd.lib.rt_page_flatten(self._hd.h, C.byref(r), C.byref(f)), self._hd.h)
+        return r.value, f.value
+
+    def flatten_page(self, img: np.ndarray, radius: int, floor: int = 64) -> np.ndarray:
+        """rt_flatten_page: one RGB8 page [h, w, 3] flattened on the GPU through the pipeline's own launcher, whatever the
+        session's setting is; radius = 0 returns a copy."""
+        img = np.ascontiguousarray(img, np.uint8); h, w = img.shape[:2]
+        out = np.empty((h, w, 3), np.uint8)
+        _check(self._hd.lib.rt_flatten_page(self._hd.h, img.ctypes.data, h, w, int(radius), int(floor), out.ctypes.data), self._hd.h)
         return out
 
     # -- rec beams --------------------------------------------------------------------------

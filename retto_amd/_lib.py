@@ -138,6 +138,7 @@ EXPORTS = [
     "rt_set_rec_flip", "rt_rec_flip", "rt_rec_flip_choose", "rt_results_rec_flip", "rt_debug_rec_flip",
     "rt_set_jpeg_entropy", "rt_jpeg_entropy", "rt_debug_jpeg_entropy",
     "rt_set_page_enhance", "rt_page_enhance", "rt_enhance_page", "rt_debug_enhance_page_host",
+    "rt_set_page_flatten", "rt_page_flatten", "rt_flatten_page", "rt_debug_flatten_page_host",
 ]
 
 STAGE_CALLBACK = C.CFUNCTYPE(None, C.c_void_p, C.c_int, C.c_int, C.c_char_p)  # rt_stage_callback
@@ -432,5 +433,9 @@ def load():
     lib.rt_page_enhance.argtypes = [C.c_void_p, P(C.c_int), P(C.c_float)]
     lib.rt_enhance_page.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p]
     lib.rt_debug_enhance_page_host.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p]
+    lib.rt_set_page_flatten.argtypes = [C.c_void_p, C.c_int, C.c_int]
+    lib.rt_page_flatten.argtypes = [C.c_void_p, P(C.c_int), P(C.c_int)]
+    lib.rt_flatten_page.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]
+    lib.rt_debug_flatten_page_host.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
     _lib = lib
     return lib

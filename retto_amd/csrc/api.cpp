@@ -509,6 +509,37 @@ int rt_debug_enhance_page_host(const uint8_t* rgb, int h, int w, int tile, float
     pe::enhance_page_host(rgb, h, w, tile, pe::clip_x16_of(clip), out, luts_out);
   });
 }
+int rt_set_page_flatten(rt_session* s, int radius, int floor) {
+  RT_REQUIRE(s, s, "rt_set_page_flatten: null session");
+  return guarded(s, [&] {
+    if (const char* why = pf::check_params(radius, floor)) throw RtError(RT_ERR_INVALID, std::string("rt_set_page_flatten: ") + why);
+    s->flatten_radius = radius; s->flatten_floor = radius ? floor : 0;   // (the helper lanes get it with every call: CallSettings)
+  });
+}
+int rt_page_flatten(const rt_session* s, int* radius, int* floor) {
+  if (!s) return RT_ERR_INVALID;
+  if (radius) *radius = s->flatten_radius;
+  if (floor) *floor = s->flatten_floor;
+  return RT_OK;
+}
+int rt_flatten_page(rt_session* s, const uint8_t* rgb, int h, int w, int radius, int floor, uint8_t* out) {
+  RT_REQUIRE(s && rgb && out && h > 0 && w > 0, s, "rt_flatten_page: bad argument");
+  return guarded(s, [&] {
+    if (const char* why = pf::check_params(radius, floor)) throw RtError(RT_ERR_INVALID, std::string("rt_flatten_page: ") + why);
+    if ((long long)h * w > 0x7fffffffLL / 3) throw RtError(RT_ERR_CAPACITY, "rt_flatten_page: the page is larger than 2^31 - 1 bytes");
+    if (radius == 0) { memcpy(out, rgb, (size_t)h * w * 3); return; }   // off: the page as it is
+    s->flatten_page(rgb, h, w, radius, floor, out);
+  });
+}
+int rt_debug_flatten_page_host(const uint8_t* rgb, int h, int w, int radius, int floor, uint8_t* out, uint8_t* level_out) {
+  RT_REQUIRE(rgb && out && h > 0 && w > 0, (rt_session*)nullptr, "rt_debug_flatten_page_host: bad argument");
+  return guarded(nullptr, [&] {
+    if (const char* why = pf::check_params(radius, floor)) throw RtError(RT_ERR_INVALID, std::string("rt_debug_flatten_page_host: ") + why);
+    if ((long long)h * w > 0x7fffffffLL / 3) throw RtError(RT_ERR_CAPACITY, "rt_debug_flatten_page_host: the page is larger than 2^31 - 1 bytes");
+    if (radius == 0) { memcpy(out, rgb, (size_t)h * w * 3); return; }   // off: the page as it is, no level
+    pf::flatten_page_host(rgb, h, w, radius, floor, out, level_out);
+  });
+}
 int rt_rec_window_plan(int L, int window, int overlap, int32_t* origin, int32_t* width, int32_t* bound, int cap, int* n, int* T) {
   return guarded(nullptr, [&] {
     if (const char* why = rw::check_params(window, overlap)) throw RtError(RT_ERR_INVALID, std::string("rt_rec_window_plan: ") + why);

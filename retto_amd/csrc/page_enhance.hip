@@ -18,6 +18,7 @@
 // Every loop is bounded by the descriptors; every pixel address is formed from coordinates clipped to the page.
 #include "common.h"
 #include "page_enhance.h"
+#include "page_rows.h"
 #include "runtime.h"
 
 namespace rt {
@@ -36,40 +37,7 @@ __device__ inline int find_page(const DevPage* pages, int n, uint32_t g, bool by
   return lo;
 }
 
-// Item j of a row segment of n pixels whose cut address is a: its first pixel and its number of pixels (0 .. 4); exactly 4 for
-// the dword-aligned groups.  items_per_row(n) bounds the items of any such segment.
-__device__ inline int items_per_row(int n) { return n / 4 + 2; }
-__device__ inline int row_item(uintptr_t a, int n, int j, int* first) {
-  const int head = min(n, (int)(a & 3)), groups = (n - head) >> 2;
-  if (j == 0) { *first = 0; return head; }
-  if (j <= groups) { *first = head + 4 * (j - 1); return 4; }
-  *first = head + 4 * groups;
-  return j == groups + 1 ? n - *first : 0;
-}
-// count (<= 4) pixels at p into px[k] = R | G << 8 | B << 16: three dword loads when there are 4 and p is a dword address
-__device__ inline void load_pixels(const uint8_t* p, int count, uint32_t px[4]) {
-  if (count == 4 && ((uintptr_t)p & 3) == 0) {
-    const uint32_t* q = (const uint32_t*)p;
-    const uint32_t w0 = q[0], w1 = q[1], w2 = q[2];
-    px[0] = w0 & 0xffffffu;
-    px[1] = (w0 >> 24) | ((w1 & 0xffffu) << 8);
-    px[2] = (w1 >> 16) | ((w2 & 0xffu) << 16);
-    px[3] = w2 >> 8;
-  } else {
-    for (int k = 0; k < 4; k++)
-      px[k] = k < count ? (uint32_t)p[3 * k] | ((uint32_t)p[3 * k + 1] << 8) | ((uint32_t)p[3 * k + 2] << 16) : 0u;
-  }
-}
-__device__ inline void store_pixels(uint8_t* p, int count, const uint32_t px[4]) {
-  if (count == 4 && ((uintptr_t)p & 3) == 0) {
-    uint32_t* q = (uint32_t*)p;
-    q[0] = px[0] | (px[1] << 24);
-    q[1] = (px[1] >> 8) | (px[2] << 16);
-    q[2] = (px[2] >> 16) | (px[3] << 8);
-  } else {
-    for (int k = 0; k < count; k++) { p[3 * k] = (uint8_t)px[k]; p[3 * k + 1] = (uint8_t)(px[k] >> 8); p[3 * k + 2] = (uint8_t)(px[k] >> 16); }
-  }
-}
+using namespace rows;   // row_item, load_pixels, store_pixels: page_rows.h
 __device__ inline int luma_of(uint32_t px) { return luma((int)(px & 255u), (int)((px >> 8) & 255u), (int)(px >> 16)); }
 
 // One value per lane (live: the lane has one) into the wave's sub-histogram h.  Called by all 64 lanes of the wave together.

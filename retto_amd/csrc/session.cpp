@@ -316,6 +316,33 @@ void rt_lane::enhance_page(const uint8_t* rgb, int h, int w, int tile, int clip_
   sync();
 }
 
+void rt_lane::flatten_pages(int n, const uint8_t* const* src, const int* hs, const int* ws, int radius, int floor, const uint8_t** out) {
+  if (n <= 0) return;
+  pf::DevPage* hp = pinned.alloc<pf::DevPage>((size_t)n);
+  for (int i = 0; i < n; i++) { hp[i] = pf::DevPage{}; hp[i].src = src[i]; hp[i].h = hs[i]; hp[i].w = ws[i]; }
+  if (!pf::plan_pages(hp, n)) throw RtError(RT_ERR_CAPACITY, "page flatten: more than 2^31 - 1 workgroups in one call");
+  for (int i = 0; i < n; i++) {
+    hp[i].dst = arena.alloc<uint8_t>((size_t)hs[i] * ws[i] * 3);
+    hp[i].cells = arena.alloc<uint8_t>(3 * (size_t)hp[i].gh * hp[i].gp);
+    hp[i].base = arena.alloc<uint8_t>(3 * (size_t)hp[i].gh * hp[i].gp);
+    out[i] = hp[i].dst;
+  }
+  pf::DevPage* dp = arena.alloc<pf::DevPage>((size_t)n);
+  RT_HIP_CHECK(hipMemcpyAsync(dp, hp, (size_t)n * sizeof(pf::DevPage), hipMemcpyHostToDevice, st));
+  pf::launch(st, &prof, dp, hp, n, radius, floor);
+}
+
+void rt_lane::flatten_page(const uint8_t* rgb, int h, int w, int radius, int floor, uint8_t* out) {
+  begin_call();
+  const size_t bytes = (size_t)h * w * 3;
+  uint8_t* d = arena.alloc<uint8_t>(bytes);
+  RT_HIP_CHECK(hipMemcpyAsync(d, rgb, bytes, hipMemcpyHostToDevice, st));
+  const uint8_t* src = d; const uint8_t* e = nullptr;
+  flatten_pages(1, &src, &h, &w, radius, floor, &e);
+  RT_HIP_CHECK(hipMemcpyAsync(out, e, bytes, hipMemcpyDeviceToHost, st));
+  sync();
+}
+
 void rt_lane::det_preprocess(const uint8_t* rgb, int h, int w, float* out) {
   begin_call();
   uint8_t* d = arena.alloc<uint8_t>((size_t)h * w * 3);
@@ -575,7 +602,7 @@ void emit_stage(const PageCall& call, int page, int stage, const rt_results::Pag
 // ---------------------------------------------------------------------------
 struct PageState {
   int ori_h, ori_w, after_h, after_w, det_h, det_w;
-  const uint8_t* raw;      // device, the caller's page (ori_h x ori_w; its enhanced copy under the call's page enhance): what
+  const uint8_t* raw;      // device, the caller's page (ori_h x ori_w; its flattened / enhanced copy under the call's page flatten / enhance): what
                            // crop_source = Original and the regions are cut from
   const uint8_t* img;      // device, after resize_both
   const uint8_t* det_img;  // device, det input size (RGB8: the det stem normalises it)
@@ -671,12 +698,14 @@ const uint8_t* page_on_device(rt_lane& s, const PageCall& c, int i) {
   RT_HIP_CHECK(hipMemcpyAsync(d, rgb[i], (size_t)hs[i] * ws[i] * 3, hipMemcpyHostToDevice, s.st));
   return d;
 }
-// Page enhance (page_enhance.h; call.set.enhance_tile > 0): every page of the call that is read (all of them, or with `needed` those
-// with needed[i] > 0) put in HBM by page_on_device and enhanced, all in pe::launch's two launches: [n_pages] pointers to the new
-// pages, what PageState::raw becomes (null for a page that is not read).  Off: empty, and nothing is allocated or launched.
+// Page flatten and page enhance (page_flatten.h, page_enhance.h; call.set.flatten_radius > 0, call.set.enhance_tile > 0): every page
+// of the call that is read (all of them, or with `needed` those with needed[i] > 0) put in HBM by page_on_device, flattened in
+// pf::launch's three launches and / or enhanced in pe::launch's two -- flatten first, so with both on the result is
+// enhance(flatten(page)): [n_pages] pointers to the new pages, what PageState::raw becomes (null for a page that is not read).
+// Both off: empty, and nothing is allocated or launched.
 std::vector<const uint8_t*> enhanced_pages(rt_lane& s, const PageCall& c, const int* needed = nullptr) {
   std::vector<const uint8_t*> out;
-  if (c.set.enhance_tile <= 0) return out;
+  if (c.set.enhance_tile <= 0 && c.set.flatten_radius <= 0) return out;
   out.assign((size_t)c.n_pages, nullptr);
   std::vector<const uint8_t*> src, dst; std::vector<int> hs, ws, at;
   for (int i = 0; i < c.n_pages; i++) {
@@ -684,7 +713,12 @@ std::vector<const uint8_t*> enhanced_pages(rt_lane& s, const PageCall& c, const 
     src.push_back(page_on_device(s, c, i)); hs.push_back(c.hs[i]); ws.push_back(c.ws[i]); at.push_back(i);
   }
   dst.resize(src.size());
-  s.enhance_pages((int)src.size(), src.data(), hs.data(), ws.data(), c.set.enhance_tile, c.set.enhance_clip_x16, dst.data());
+  if (c.set.flatten_radius > 0) {
+    s.flatten_pages((int)src.size(), src.data(), hs.data(), ws.data(), c.set.flatten_radius, c.set.flatten_floor, dst.data());
+    src = dst;
+  }
+  if (c.set.enhance_tile > 0)
+    s.enhance_pages((int)src.size(), src.data(), hs.data(), ws.data(), c.set.enhance_tile, c.set.enhance_clip_x16, dst.data());
   for (size_t k = 0; k < at.size(); k++) out[(size_t)at[k]] = dst[k];
   return out;
 }

@@ -23,6 +23,7 @@
 #include "nets.h"
 #include "nets_f16.h"
 #include "page_enhance.h"
+#include "page_flatten.h"
 #include "prepost.h"
 #include "rec_line_opts.h"
 #include "rec_tail_plan.h"
@@ -103,13 +104,15 @@ struct LaneWorker {
 // the beam's language model (rt_set_rec_beam_lm, ctc_lm.h; lm = -1: off, and without effect while beam_b = 0) and its word list
 // (rt_set_rec_beam_vocab, ctc_vocab.h; beam_vocab = -1: off, likewise), and the rec flip (rt_set_rec_flip, rec_flip.h; 0 = off).
 // With 0 < flip_cls_below <= 1 the call syncs its lane once more, between the cls stage and the rec plan, to bring the
-// classifier scores to the host.  enhance_tile / enhance_clip_x16: the page enhance (rt_set_page_enhance, page_enhance.h; 0 = off)
+// classifier scores to the host.  enhance_tile / enhance_clip_x16: the page enhance (rt_set_page_enhance, page_enhance.h; 0 = off);
+// flatten_radius / flatten_floor: the page flatten (rt_set_page_flatten, page_flatten.h; 0 = off), which comes first when both are on
 struct CallSettings {
   rt::RecLineOpts rec; int det_tile = 0, det_overlap = 0, beam_b = 0, beam_n = 0, rec_window = 0, rec_overlap = 0;
   int lm = -1; float lm_alpha = 0.0f, lm_beta = 0.0f;
   int beam_vocab = -1; float vocab_gamma = 0.0f;
   float flip_cls_below = 0.0f;
   int enhance_tile = 0, enhance_clip_x16 = 0;
+  int flatten_radius = 0, flatten_floor = 0;
   bool fused() const { return beam_b > 0 && lm >= 0; }
   bool worded() const { return beam_b > 0 && beam_vocab >= 0; }
 };
@@ -324,6 +327,11 @@ struct rt_lane {
                      const uint8_t** luts_out = nullptr);
   // rt_enhance_page: one host page through enhance_pages
   void enhance_page(const uint8_t* rgb, int h, int w, int tile, int clip_x16, uint8_t* out);
+  // Page flatten (page_flatten.h) of n pages on the device in the three launches of pf::launch: new pages and the cell planes from
+  // `arena`, the descriptors through `pinned`; out[i] = page i flattened
+  void flatten_pages(int n, const uint8_t* const* src, const int* hs, const int* ws, int radius, int floor, const uint8_t** out);
+  // rt_flatten_page: one host page through flatten_pages
+  void flatten_page(const uint8_t* rgb, int h, int w, int radius, int floor, uint8_t* out);
   void det_preprocess(const uint8_t* rgb, int h, int w, float* out);
   void det_postprocess(const float* pred, int h, int w, int ori_h, int ori_w, float* boxes, float* scores, int max_out,
                        int* n_out);
@@ -456,9 +464,12 @@ struct rt_session : rt_lane {
   // rt_set_page_enhance (page_enhance.h): every page of the pipeline calls that follow is contrast-equalised tile-wise before
   // anything else reads it; enhance_tile = 0: off.  enhance_clip is the caller's value, what the calls carry is clip_x16_of it
   int enhance_tile = 0; float enhance_clip = 0.0f;
+  // rt_set_page_flatten (page_flatten.h): every page of the pipeline calls that follow is divided by its estimated paper level
+  // before anything else reads it, page enhance included; flatten_radius = 0: off
+  int flatten_radius = 0, flatten_floor = 0;
   CallSettings settings() const {
     return {rec_default, det_tile, det_overlap, beam_b, beam_n, rec_window, rec_overlap, beam_lm, lm_alpha, lm_beta, beam_vocab, vocab_gamma,
-            rec_flip_below, enhance_tile, enhance_tile ? rt::pe::clip_x16_of(enhance_clip) : 0};
+            rec_flip_below, enhance_tile, enhance_tile ? rt::pe::clip_x16_of(enhance_clip) : 0, flatten_radius, flatten_floor};
   }
   std::string last_error;
   // rt_charset_create: compiles the set (rt::compile_charset), stores it and returns its id
