@@ -402,6 +402,48 @@ RT_API int rt_flatten_page(rt_session* s, const uint8_t* rgb, int h, int w, int 
 /* The rule on the CPU, in plain loops over the same header; GPU-free and sessionless (rt_last_error(NULL)).  level_out (optional):
  * the smoothed level per channel, 3 * ceil(h / 4) * ceil(w / 4) bytes as [3][gh][gw] (not written for radius = 0). */
 RT_API int rt_debug_flatten_page_host(const uint8_t* rgb, int h, int w, int radius, int floor, uint8_t* out, uint8_t* level_out);
+/* Page deskew (retto_amd/csrc/page_deskew.h states the rule): the skew of every page estimated from its own text lines and the
+ * page rotated back by it on the GPU, before anything reads it.  Flatten and enhance correct a page's light and contrast; deskew
+ * corrects its geometry: a scan or photograph a few degrees off otherwise gives slanted DB quads, a rotating warp per line crop,
+ * and a reading order by y, word boxes and keyword quads that inherit the slant.  With deskew on, every page of rt_run_batch,
+ * rt_run_batch_stream, rt_submit_batch and the encoded entry points is turned as soon as it is in device memory, after flatten
+ * and enhance -- deskew(enhance(flatten(page))) -- into a NEW buffer of the same h x w (a caller's RT_MEM_DEVICE page is never
+ * written; edge pixels are replicated into the corners the turn uncovers), and resize_both, the detector, the det tiles and both
+ * crop sources read the turned page.  rt_run_regions* NEVER deskews: the caller's quads define the geometry there.
+ * COORDINATES: every box, word box and keyword quad of a deskewed call is in the DESKEWED page's coordinates.
+ * rt_results_page_deskew returns the page's slope and the affine that takes a point of the deskewed page back to the original
+ * page; mapping the results back is left to the caller.
+ * The rule is 32-bit and 64-bit integer arithmetic throughout (no trigonometry or square root of a maths library), so
+ * rt_deskew_page, the pipeline and rt_debug_deskew_page_host agree byte for byte.  The unit of slope is 1 / 512 (about 0.112
+ * degrees); positive: the lines rise to the right.  The page's ink (255 - the minimum luma of each 4 x 4-pixel cell; cells of 8,
+ * 16 ... pixels on pages beyond 2048 pixels, so that the grid stays within 512 x 512) is summed along rows sheared by every
+ * candidate slope k in [-range, range]; the score S_k of a slope is the sum of the squared differences of neighbouring row sums
+ * -- text lines seen edge-on give sharp rows; the slope of largest score wins (ties: the smaller |k|, then the positive one),
+ * unless S_k* * 100 < S_0 * (100 + min_gain), in which case the page is left as it is (slope 0, a plain copy).  The page is then
+ * turned about its centre by atan(k / 512) with bilinear sampling in 8-bit fractions.  Four launches per lane part, no host wait.
+ * range = 0: off, the default (min_gain is then ignored); otherwise 1 <= range <= 128 (14 degrees) and 0 <= min_gain <= 10000
+ * (per cent).  Anything else: RT_ERR_INVALID naming the parameter.  The setting holds for the pipeline calls that follow on every
+ * lane (rt_submit_* takes it as it is at the call); fails like every other call while tickets are in flight.  With deskew off
+ * nothing is launched or allocated that was not before.
+ * Not supported: per-page settings; deskew inside the stage functions or rt_run_regions*; pages turned by 90 or 180 degrees.
+ * What deskew does to recognition accuracy with trained PP-OCRv4 weights has NOT been measured (the weights here are
+ * synthetic). */
+RT_API int rt_set_page_deskew(rt_session* s, int range, int min_gain);
+/* the setting (each optional); RT_ERR_INVALID for a NULL session */
+RT_API int rt_page_deskew(const rt_session* s, int* range, int* min_gain);
+/* stage function beside rt_flatten_page: one RGB8 HWC page in host memory through the pipeline's own launcher, into out
+ * [h * w * 3] (host); *slope (optional): the chosen slope.  range and min_gain as above, whatever the session's setting is;
+ * range = 0 copies the page. */
+RT_API int rt_deskew_page(rt_session* s, const uint8_t* rgb, int h, int w, int range, int min_gain, uint8_t* out, int* slope);
+/* The rule on the CPU, in plain loops over the same header; GPU-free and sessionless (rt_last_error(NULL)).  scores_out
+ * (optional): S_k for k = -range .. range, 2 * range + 1 values (not written for range = 0). */
+RT_API int rt_debug_deskew_page_host(const uint8_t* rgb, int h, int w, int range, int min_gain, uint8_t* out, int* slope,
+                                     uint64_t* scores_out);
+/* A page's deskew: *slope (optional) = the slope it was turned by -- 0 when deskew was off, the page was left as it is, or the call
+ * was a regions call -- and m (optional) = the affine that takes a point (x, y) of the deskewed page to the original page,
+ * u = m[0] x + m[1] y + m[2], v = m[3] x + m[4] y + m[5] (the identity for slope 0).  RT_ERR_INVALID for a NULL r or a page out of
+ * range (slope 0 and the identity are still written). */
+RT_API int rt_results_page_deskew(const rt_results* r, int page, int* slope, float m[6]);
 /* The pipeline over regions the caller already knows (form fields, subtitles, corrected boxes, another detector's boxes):
  * quads[i] = n_quads[i] x 8 floats in host memory, TL, TR, BR, BL of each region in original-page coordinates; mem
  * (RT_MEM_HOST or RT_MEM_DEVICE) says where the pages live.  Every coordinate is clamped to [0, ori - 1] (no rounding); line k

@@ -247,10 +247,19 @@ class RecProcessorSingleResult:
 
 
 @dataclass
+class PageDeskew:   # rt_results_page_deskew
+    slope: int            # in 1 / 512, positive: the lines rose to the right; 0: the page was not turned
+    matrix: np.ndarray    # [2, 3] float32: a point (x, y, 1) of the deskewed page -> the original page
+
+
+@dataclass
 class RettoWorkerResult:  # session.rs:44-48
     det_result: List[DetProcessorInnerResult]
     cls_result: List[ClsProcessorSingleResult]
     rec_result: List[RecProcessorSingleResult]
+    # page deskew (set_page_deskew): the page's slope and the map of its results' coordinates back to the original page; slope 0
+    # and the identity when deskew was off, the page was left as it is, or the call was a regions call
+    deskew: Optional[PageDeskew] = None
 
 
 def _src(s: Optional[RettoWorkerModelSource], keep: list) -> ModelSource:
@@ -592,7 +601,19 @@ def debug_flatten_page_host(img: np.ndarray, radius: int, floor: int = 64, with_
     return (out, level) if with_level else out
 
 
-_WINDOW_PLAN_BUFS = None   # the three output arrays of rec_window_plan, grown on demand, as det_tile_plan's
+def debug_deskew_page_host(img: np.ndarray, range: int, min_gain: int = 25, with_scores: bool = False):
+    """rt_debug_deskew_page_host: the page deskew rule (retto_amd/csrc/page_deskew.h) on the CPU, GPU-free: (page, slope); with_scores:
+    (page, slope, scores [2 range + 1] uint64), the score S_k of every candidate slope k = -range .. range."""
+    lib = _lib.load()
+    img = np.ascontiguousarray(img, np.uint8); h, w = img.shape[:2]
+    out = np.empty((h, w, 3), np.uint8); slope = C.c_int()
+    scores = np.zeros(2 * int(range) + 1, np.uint64) if with_scores and range > 0 else None
+    _check(lib.rt_debug_deskew_page_host(img.ctypes.data, h, w, int(range), int(min_gain), out.ctypes.data, C.byref(slope),
+                                         None if scores is None else scores.ctypes.data), None)
+    return (out, slope.value, scores) if with_scores else (out, slope.value)
+
+
+_WINDOW_PLAN_BUFS = None  # the three output arrays of rec_window_plan, grown on demand, as det_tile_plan's
 
 
 def rec_window_plan(L: int, window: int, overlap: int = 0) -> dict:
@@ -773,7 +794,9 @@ class RettoSession:
                                                 cands, cols, matches, snapped, self._pattern(r, page, k),
                                                 self._keywords(r, page, k), self._beams(r, page, k, beam_on),
                                                 int(lib.rt_results_rec_windows(r, page, k)), self._flip(r, page, k)))
-        return RettoWorkerResult(det, cls, rec)
+        slope = C.c_int(); m = (C.c_float * 6)()
+        lib.rt_results_page_deskew(r, page, C.byref(slope), m)
+        return RettoWorkerResult(det, cls, rec, PageDeskew(slope.value, np.array(list(m), np.float32).reshape(2, 3)))
 
     def _flip(self, r, page: int, k: int) -> Optional[RecFlip]:
         s0, s1 = C.c_float(), C.c_float()
@@ -907,6 +930,30 @@ class RettoSession:
         out = np.empty((h, w, 3), np.uint8)
         _check(self._hd.lib.rt_flatten_page(self._hd.h, img.ctypes.data, h, w, int(radius), int(floor), out.ctypes.data), self._hd.h)
         return out
+
+    # -- page deskew ------------------------------------------------------------------------
+    def set_page_deskew(self, range: int, min_gain: int = 25) -> None:
+        """rt_set_page_deskew: every page of the pipeline calls that follow (run_regions excepted) is turned by its own estimated
+        skew (retto_amd/csrc/page_deskew.h) on the GPU, after flatten and enhance and before anything else reads it; 0 = off, the
+        default.  range: the largest slope tried, in 1 / 512, in [1, 128]; min_gain: by how many per cent the best slope's score
+        must beat slope 0's, in [0, 10000].  Boxes, word boxes and keyword quads are then in the deskewed page's coordinates
+        (RettoWorkerResult.deskew maps them back).  The effect on accuracy with the real weights is not measured."""
+        _check(self._hd.lib.rt_set_page_deskew(self._hd.h, int(range), int(min_gain)), self._hd.h)
+
+    def page_deskew(self) -> Tuple[int, int]:
+        """rt_page_deskew: (range, min_gain) as set; range 0 = off."""
+        r, g = C.c_int(), C.c_int()
+        _check(self._hd.lib.rt_page_deskew(self._hd.h, C.byref(r), C.byref(g)), self._hd.h)
+        return r.value, g.value
+
+    def deskew_page(self, img: np.ndarray, range: int, min_gain: int = 25) -> Tuple[np.ndarray, int]:
+        """rt_deskew_page: one RGB8 page [h, w, 3] deskewed on the GPU through the pipeline's own launcher, whatever the
+        session's setting is: (page, slope); range = 0 returns a copy and 0."""
+        img = np.ascontiguousarray(img, np.uint8); h, w = img.shape[:2]
+        out = np.empty((h, w, 3), np.uint8); slope = C.c_int()
+        _check(self._hd.lib.rt_deskew_page(self._hd.h, img.ctypes.data, h, w, int(range), int(min_gain), out.ctypes.data,
+                                           C.byref(slope)), self._hd.h)
+        return out, slope.value
 
     # -- rec beams --------------------------------------------------------------------------
     def set_rec_beam(self, beam: int, nbest: int = 1) -> None:

@@ -62,6 +62,10 @@ def build_parser() -> argparse.ArgumentParser:
                     help="contrast-equalise every page tile-wise on the GPU before anything reads it (CLAHE of the luma; faded or "
                          "shadowed pages; the effect on accuracy is not measured); TILE a multiple of 32 in [32, 512], CLIP in "
                          "[1, 64], e.g. 64,2.5; default off")
+    ap.add_argument("--deskew", default=None, metavar="R,G",
+                    help="estimate every page's skew on the GPU and rotate the page back before anything reads it (boxes are then "
+                         "in the deskewed page's coordinates; the effect on accuracy is not measured); R the largest slope tried "
+                         "in 1/512, in [1, 128], G the least gain over no turn in per cent, in [0, 10000], e.g. 64,25; default off")
     ap.add_argument("--rec-window", type=int, default=0, metavar="N",
                     help="read rec lines at least 8 columns wider than N as overlapping windows of N columns, stitched into the "
                          "one line (long lines at a familiar width; the effect on accuracy is not measured); a multiple of 32, "
@@ -146,6 +150,12 @@ def main(argv=None) -> int:
         except ValueError:
             ap.error("--enhance takes TILE,CLIP, e.g. 64,2.5")
         session.set_page_enhance(tile, clip)
+    if a.deskew:
+        try:
+            rng, gain = (int(v) for v in a.deskew.split(","))
+        except ValueError:
+            ap.error("--deskew takes R,G, e.g. 64,25")
+        session.set_page_deskew(rng, gain)
     if a.rec_window:
         session.set_rec_windows(a.rec_window, a.rec_window_overlap)
     if a.rec_flip:

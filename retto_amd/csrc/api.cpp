@@ -136,6 +136,7 @@ void rt_destroy(rt_session* s) {
   s->free_stage();
   s->det.reset(); s->cls.reset(); s->rec.reset();
   if (s->d_word_raw) (void)hipFree(s->d_word_raw);
+  if (s->d_deskew_table) (void)hipFree(s->d_deskew_table);
   delete s;   // (and with it the rec stores' device tables)
 }
 const char* rt_last_error(const rt_session* s) { return s ? s->last_error.c_str() : create_error().c_str(); }
@@ -539,6 +540,49 @@ int rt_debug_flatten_page_host(const uint8_t* rgb, int h, int w, int radius, int
     if (radius == 0) { memcpy(out, rgb, (size_t)h * w * 3); return; }   // off: the page as it is, no level
     pf::flatten_page_host(rgb, h, w, radius, floor, out, level_out);
   });
+}
+int rt_set_page_deskew(rt_session* s, int range, int min_gain) {
+  RT_REQUIRE(s, s, "rt_set_page_deskew: null session");
+  return guarded(s, [&] {
+    if (const char* why = pd::check_params(range, min_gain)) throw RtError(RT_ERR_INVALID, std::string("rt_set_page_deskew: ") + why);
+    if (range) s->deskew_table();   // (the angle table goes up with the first setting that turns deskew on)
+    s->deskew_range = range; s->deskew_gain = range ? min_gain : 0;   // (the helper lanes get it with every call: CallSettings)
+  });
+}
+int rt_page_deskew(const rt_session* s, int* range, int* min_gain) {
+  if (!s) return RT_ERR_INVALID;
+  if (range) *range = s->deskew_range;
+  if (min_gain) *min_gain = s->deskew_gain;
+  return RT_OK;
+}
+int rt_deskew_page(rt_session* s, const uint8_t* rgb, int h, int w, int range, int min_gain, uint8_t* out, int* slope) {
+  RT_REQUIRE(s && rgb && out && h > 0 && w > 0, s, "rt_deskew_page: bad argument");
+  return guarded(s, [&] {
+    if (const char* why = pd::check_params(range, min_gain)) throw RtError(RT_ERR_INVALID, std::string("rt_deskew_page: ") + why);
+    if ((long long)h * w > 0x7fffffffLL / 3) throw RtError(RT_ERR_CAPACITY, "rt_deskew_page: the page is larger than 2^31 - 1 bytes");
+    int k = 0;
+    if (range == 0) memcpy(out, rgb, (size_t)h * w * 3);   // off: the page as it is
+    else k = s->deskew_page(rgb, h, w, range, min_gain, s->deskew_table(), out);
+    if (slope) *slope = k;
+  });
+}
+int rt_debug_deskew_page_host(const uint8_t* rgb, int h, int w, int range, int min_gain, uint8_t* out, int* slope, uint64_t* scores_out) {
+  RT_REQUIRE(rgb && out && h > 0 && w > 0, (rt_session*)nullptr, "rt_debug_deskew_page_host: bad argument");
+  return guarded(nullptr, [&] {
+    if (const char* why = pd::check_params(range, min_gain)) throw RtError(RT_ERR_INVALID, std::string("rt_debug_deskew_page_host: ") + why);
+    if ((long long)h * w > 0x7fffffffLL / 3) throw RtError(RT_ERR_CAPACITY, "rt_debug_deskew_page_host: the page is larger than 2^31 - 1 bytes");
+    int k = 0;
+    if (range == 0) memcpy(out, rgb, (size_t)h * w * 3);   // off: the page as it is, no scores
+    else pd::deskew_page_host(rgb, h, w, range, min_gain, out, &k, scores_out);
+    if (slope) *slope = k;
+  });
+}
+int rt_results_page_deskew(const rt_results* r, int page, int* slope, float m[6]) {
+  const rt_results::Page* p = r && page >= 0 && (size_t)page < r->pages.size() ? &r->pages[(size_t)page] : nullptr;
+  const pd::Record rec = p ? p->deskew : pd::Record{0, 65536, 0};
+  if (slope) *slope = rec.k;
+  if (m) pd::matrix_of(rec, p ? p->deskew_h : 1, p ? p->deskew_w : 1, m);
+  return p ? RT_OK : RT_ERR_INVALID;
 }
 int rt_rec_window_plan(int L, int window, int overlap, int32_t* origin, int32_t* width, int32_t* bound, int cap, int* n, int* T) {
   return guarded(nullptr, [&] {

@@ -343,6 +343,52 @@ void rt_lane::flatten_page(const uint8_t* rgb, int h, int w, int radius, int flo
   sync();
 }
 
+const int32_t* rt_session::deskew_table() {
+  if (!d_deskew_table) {
+    const std::vector<int32_t> t = pd::angle_table();
+    RT_HIP_CHECK(hipSetDevice(device));
+    RT_HIP_CHECK(hipMalloc((void**)&d_deskew_table, t.size() * sizeof(int32_t)));
+    RT_HIP_CHECK(hipMemcpy(d_deskew_table, t.data(), t.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+  }
+  return d_deskew_table;
+}
+
+const pd::Record* rt_lane::deskew_pages(int n, const uint8_t* const* src, const int* hs, const int* ws, int range, int min_gain,
+                                        const int32_t* table, const uint8_t** out) {
+  if (n <= 0) return nullptr;
+  if (!table) throw RtError(RT_ERR_BACKEND, "page deskew: the angle table is not on the device");
+  pd::DevPage* hp = pinned.alloc<pd::DevPage>((size_t)n);
+  for (int i = 0; i < n; i++) { hp[i] = pd::DevPage{}; hp[i].src = src[i]; hp[i].h = hs[i]; hp[i].w = ws[i]; }
+  if (!pd::plan_pages(hp, n, range)) throw RtError(RT_ERR_CAPACITY, "page deskew: more than 2^31 - 1 workgroups in one call");
+  pd::Record* d_rec = arena.alloc<pd::Record>((size_t)n);
+  uint64_t* d_scores = arena.alloc<uint64_t>((size_t)n * (2 * (size_t)range + 1));
+  for (int i = 0; i < n; i++) {
+    hp[i].dst = arena.alloc<uint8_t>((size_t)hs[i] * ws[i] * 3);
+    hp[i].cells = arena.alloc<uint8_t>((size_t)hp[i].gw * hp[i].gp);
+    hp[i].scores = d_scores + (size_t)i * (2 * (size_t)range + 1);
+    hp[i].rec = d_rec + i;
+    out[i] = hp[i].dst;
+  }
+  pd::DevPage* dp = arena.alloc<pd::DevPage>((size_t)n);
+  RT_HIP_CHECK(hipMemcpyAsync(dp, hp, (size_t)n * sizeof(pd::DevPage), hipMemcpyHostToDevice, st));
+  pd::launch(st, &prof, dp, hp, n, range, min_gain, table);
+  pd::Record* h_rec = pinned.alloc<pd::Record>((size_t)n);
+  RT_HIP_CHECK(hipMemcpyAsync(h_rec, d_rec, (size_t)n * sizeof(pd::Record), hipMemcpyDeviceToHost, st));
+  return h_rec;
+}
+
+int rt_lane::deskew_page(const uint8_t* rgb, int h, int w, int range, int min_gain, const int32_t* table, uint8_t* out) {
+  begin_call();
+  const size_t bytes = (size_t)h * w * 3;
+  uint8_t* d = arena.alloc<uint8_t>(bytes);
+  RT_HIP_CHECK(hipMemcpyAsync(d, rgb, bytes, hipMemcpyHostToDevice, st));
+  const uint8_t* src = d; const uint8_t* e = nullptr;
+  const pd::Record* rec = deskew_pages(1, &src, &h, &w, range, min_gain, table, &e);
+  RT_HIP_CHECK(hipMemcpyAsync(out, e, bytes, hipMemcpyDeviceToHost, st));
+  sync();
+  return rec->k;
+}
+
 void rt_lane::det_preprocess(const uint8_t* rgb, int h, int w, float* out) {
   begin_call();
   uint8_t* d = arena.alloc<uint8_t>((size_t)h * w * 3);
@@ -664,6 +710,9 @@ struct Pipeline {
   // rec flip (rec_flip.h; call.set.flip_cls_below > 0): per line whether it is read both ways (host; empty: no line of the call
   // is), and then per line its outcome (zeroed: 0 = read one way) and the two views' scores
   std::vector<uint8_t> both; Mirror<int> flipo; Mirror<float> flips;
+  // page deskew (page_deskew.h; call.set.deskew_range > 0 and not a regions call): per page its record, pinned, copied behind the
+  // deskew launches and read after the box round trip's sync; null otherwise
+  const pd::Record* deskew = nullptr;
 };
 
 // Launch groups: items [g0, end) where the group always takes its first item; with max_items > 0 it takes up to max_items items,
@@ -702,10 +751,15 @@ const uint8_t* page_on_device(rt_lane& s, const PageCall& c, int i) {
 // of the call that is read (all of them, or with `needed` those with needed[i] > 0) put in HBM by page_on_device, flattened in
 // pf::launch's three launches and / or enhanced in pe::launch's two -- flatten first, so with both on the result is
 // enhance(flatten(page)): [n_pages] pointers to the new pages, what PageState::raw becomes (null for a page that is not read).
-// Both off: empty, and nothing is allocated or launched.
-std::vector<const uint8_t*> enhanced_pages(rt_lane& s, const PageCall& c, const int* needed = nullptr) {
+// Page deskew (page_deskew.h; call.set.deskew_range > 0) comes last, in pd::launch's four launches, and only where the caller asks
+// for it with `deskew` (the detector's calls; never rt_run_regions*, whose quads define the geometry): *deskew = the [n_pages] page
+// records in pinned memory, valid after the lane's next sync, or null when deskew is off.  The page is then
+// deskew(enhance(flatten(page))).  All off: empty, and nothing is allocated or launched.
+std::vector<const uint8_t*> enhanced_pages(rt_lane& s, const PageCall& c, const int* needed = nullptr, const pd::Record** deskew = nullptr) {
   std::vector<const uint8_t*> out;
-  if (c.set.enhance_tile <= 0 && c.set.flatten_radius <= 0) return out;
+  const bool turn = deskew && c.set.deskew_range > 0;
+  if (deskew) *deskew = nullptr;
+  if (c.set.enhance_tile <= 0 && c.set.flatten_radius <= 0 && !turn) return out;
   out.assign((size_t)c.n_pages, nullptr);
   std::vector<const uint8_t*> src, dst; std::vector<int> hs, ws, at;
   for (int i = 0; i < c.n_pages; i++) {
@@ -717,8 +771,12 @@ std::vector<const uint8_t*> enhanced_pages(rt_lane& s, const PageCall& c, const 
     s.flatten_pages((int)src.size(), src.data(), hs.data(), ws.data(), c.set.flatten_radius, c.set.flatten_floor, dst.data());
     src = dst;
   }
-  if (c.set.enhance_tile > 0)
+  if (c.set.enhance_tile > 0) {
     s.enhance_pages((int)src.size(), src.data(), hs.data(), ws.data(), c.set.enhance_tile, c.set.enhance_clip_x16, dst.data());
+    src = dst;
+  }
+  if (turn)   // (needed is null with deskew: record k is page k's)
+    *deskew = s.deskew_pages((int)src.size(), src.data(), hs.data(), ws.data(), c.set.deskew_range, c.set.deskew_gain, c.set.d_deskew_table, dst.data());
   for (size_t k = 0; k < at.size(); k++) out[(size_t)at[k]] = dst[k];
   return out;
 }
@@ -736,7 +794,7 @@ void page_sizes(rt_lane& s, Pipeline& P) {
     std::string why;
     if (dh > 0 && dw > 0 && dt::check_page(dh, dw, &why) == dt::ERR_CAPACITY) throw RtError(RT_ERR_CAPACITY, "page " + std::to_string(i) + ": " + why);
   }
-  const std::vector<const uint8_t*> enhanced = enhanced_pages(s, P.call);
+  const std::vector<const uint8_t*> enhanced = enhanced_pages(s, P.call, nullptr, &P.deskew);
   for (int i = 0; i < P.call.n_pages; i++) {
     PageState& p = P.pg[i];
     p.ori_h = hs[i]; p.ori_w = ws[i];
@@ -1356,6 +1414,8 @@ void results(const rt_session& s, const Pipeline& P, rt_results& res) {
     const PageState& p = P.pg[i];
     int nb = p.n_boxes;
     page_boxes(p, R, P.call.regions());
+    R.deskew_h = p.ori_h; R.deskew_w = p.ori_w;
+    if (P.deskew) R.deskew = P.deskew[i];
     R.cls_labels.resize(nb); R.cls_scores.resize(nb); R.rec_scores.resize(nb); R.tokens.resize(nb); R.text.resize(nb);
     R.rec_units.resize(nb);
     for (int k = 0; k < nb; k++) R.rec_units[k] = rw::units(P.line_W[p.first_line + k], P.call.set.rec_window, P.call.set.rec_overlap);

@@ -22,6 +22,7 @@
 #include "lane_split.h"
 #include "nets.h"
 #include "nets_f16.h"
+#include "page_deskew.h"
 #include "page_enhance.h"
 #include "page_flatten.h"
 #include "prepost.h"
@@ -77,6 +78,9 @@ struct rt_results {
     // rec flip (rec_flip.h; rt_set_rec_flip): per line its outcome (0: read one way, 1: both ways and view 0 kept, 2: view 1
     // taken) and the two views' greedy scores [2 per line]; empty when no line of the call was read both ways
     std::vector<uint8_t> flip_outcome; std::vector<float> flip_scores;
+    // page deskew (page_deskew.h; rt_set_page_deskew): the slope the page was turned by and its (cosq, sinq); k = 0 when deskew was
+    // off, the page was not turned, or the call was a regions call
+    rt::pd::Record deskew{0, 65536, 0}; int deskew_h = 0, deskew_w = 0;
     std::string json[3];
   };
   std::vector<Page> pages;
@@ -105,7 +109,9 @@ struct LaneWorker {
 // (rt_set_rec_beam_vocab, ctc_vocab.h; beam_vocab = -1: off, likewise), and the rec flip (rt_set_rec_flip, rec_flip.h; 0 = off).
 // With 0 < flip_cls_below <= 1 the call syncs its lane once more, between the cls stage and the rec plan, to bring the
 // classifier scores to the host.  enhance_tile / enhance_clip_x16: the page enhance (rt_set_page_enhance, page_enhance.h; 0 = off);
-// flatten_radius / flatten_floor: the page flatten (rt_set_page_flatten, page_flatten.h; 0 = off), which comes first when both are on
+// flatten_radius / flatten_floor: the page flatten (rt_set_page_flatten, page_flatten.h; 0 = off), which comes first when both are on;
+// deskew_range / deskew_gain: the page deskew (rt_set_page_deskew, page_deskew.h; 0 = off), which comes last, and d_deskew_table, the
+// session's angle table on the device (non-null whenever deskew_range > 0)
 struct CallSettings {
   rt::RecLineOpts rec; int det_tile = 0, det_overlap = 0, beam_b = 0, beam_n = 0, rec_window = 0, rec_overlap = 0;
   int lm = -1; float lm_alpha = 0.0f, lm_beta = 0.0f;
@@ -113,6 +119,7 @@ struct CallSettings {
   float flip_cls_below = 0.0f;
   int enhance_tile = 0, enhance_clip_x16 = 0;
   int flatten_radius = 0, flatten_floor = 0;
+  int deskew_range = 0, deskew_gain = 0; const int32_t* d_deskew_table = nullptr;
   bool fused() const { return beam_b > 0 && lm >= 0; }
   bool worded() const { return beam_b > 0 && beam_vocab >= 0; }
 };
@@ -332,6 +339,13 @@ struct rt_lane {
   void flatten_pages(int n, const uint8_t* const* src, const int* hs, const int* ws, int radius, int floor, const uint8_t** out);
   // rt_flatten_page: one host page through flatten_pages
   void flatten_page(const uint8_t* rgb, int h, int w, int radius, int floor, uint8_t* out);
+  // Page deskew (page_deskew.h) of n pages on the device in the four launches of pd::launch: new pages, the cell grids, the scores
+  // and the records from `arena`, the descriptors through `pinned`; out[i] = page i deskewed.  Returns the [n] page records in
+  // pinned memory, their copy queued behind the launches: valid after the lane's next sync.  table: the angle table (device)
+  const rt::pd::Record* deskew_pages(int n, const uint8_t* const* src, const int* hs, const int* ws, int range, int min_gain,
+                                     const int32_t* table, const uint8_t** out);
+  // rt_deskew_page: one host page through deskew_pages; returns the chosen slope
+  int deskew_page(const uint8_t* rgb, int h, int w, int range, int min_gain, const int32_t* table, uint8_t* out);
   void det_preprocess(const uint8_t* rgb, int h, int w, float* out);
   void det_postprocess(const float* pred, int h, int w, int ori_h, int ori_w, float* boxes, float* scores, int max_out,
                        int* n_out);
@@ -467,9 +481,16 @@ struct rt_session : rt_lane {
   // rt_set_page_flatten (page_flatten.h): every page of the pipeline calls that follow is divided by its estimated paper level
   // before anything else reads it, page enhance included; flatten_radius = 0: off
   int flatten_radius = 0, flatten_floor = 0;
+  // rt_set_page_deskew (page_deskew.h): every page of the pipeline calls that follow, regions calls excepted, is turned by its own
+  // estimated skew after flatten and enhance; deskew_range = 0: off.  d_deskew_table: the 129 (cosq, sinq) pairs, uploaded by
+  // deskew_table() the first time deskew is set or rt_deskew_page is called, and kept for the session
+  int deskew_range = 0, deskew_gain = 0;
+  int32_t* d_deskew_table = nullptr;
+  const int32_t* deskew_table();
   CallSettings settings() const {
     return {rec_default, det_tile, det_overlap, beam_b, beam_n, rec_window, rec_overlap, beam_lm, lm_alpha, lm_beta, beam_vocab, vocab_gamma,
-            rec_flip_below, enhance_tile, enhance_tile ? rt::pe::clip_x16_of(enhance_clip) : 0, flatten_radius, flatten_floor};
+            rec_flip_below, enhance_tile, enhance_tile ? rt::pe::clip_x16_of(enhance_clip) : 0, flatten_radius, flatten_floor,
+            deskew_range, deskew_gain, d_deskew_table};
   }
   std::string last_error;
   // rt_charset_create: compiles the set (rt::compile_charset), stores it and returns its id
