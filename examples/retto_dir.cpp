@@ -81,6 +81,7 @@ int main(int argc, char** argv) {
   int enhance_tile = 0; float enhance_clip = 0.0f;   // --enhance TILE,CLIP: rt_set_page_enhance
   int flatten_radius = 0, flatten_floor = 0;         // --flatten R,F: rt_set_page_flatten
   int deskew_range = 0, deskew_gain = 0;             // --deskew R,G: rt_set_page_deskew
+  int derule_len = 0, derule_thick = 0, derule_ink = 0;   // --derule L,T,I: rt_set_page_derule
   for (int i = 1; i + 1 < argc; i += 2) {
     std::string k = argv[i], v = argv[i + 1];
     if (k == "--det") det = v; else if (k == "--cls") cls = v; else if (k == "--rec") rec = v;
@@ -97,10 +98,13 @@ int main(int argc, char** argv) {
     else if (k == "--deskew") {
       if (sscanf(v.c_str(), "%d,%d", &deskew_range, &deskew_gain) != 2) { fprintf(stderr, "--deskew takes R,G, e.g. 64,25\n"); return 2; }
     }
+    else if (k == "--derule") {
+      if (sscanf(v.c_str(), "%d,%d,%d", &derule_len, &derule_thick, &derule_ink) != 3) { fprintf(stderr, "--derule takes L,T,I, e.g. 64,4,96\n"); return 2; }
+    }
     else { fprintf(stderr, "unknown option %s\n", k.c_str()); return 2; }
   }
   if (det.empty() || cls.empty() || rec.empty() || keys.empty() || images.empty() || batch <= 0) {
-    fprintf(stderr, "usage: retto_dir --det M --cls M --rec M --keys K --images DIR [--batch N] [--device-id D] [--ranks N] [--quiet 1] [--enhance TILE,CLIP] [--flatten R,F] [--deskew R,G]\n");
+    fprintf(stderr, "usage: retto_dir --det M --cls M --rec M --keys K --images DIR [--batch N] [--device-id D] [--ranks N] [--quiet 1] [--enhance TILE,CLIP] [--flatten R,F] [--deskew R,G] [--derule L,T,I]\n");
     return 2;
   }
   // the file list is the same on every rank (sorted walk), so is its split
@@ -174,6 +178,7 @@ int main(int argc, char** argv) {
   if (flatten_radius && rt_set_page_flatten(s, flatten_radius, flatten_floor) != RT_OK) { fprintf(stderr, "%s\n", rt_last_error(s)); return 2; }
   if (enhance_tile && rt_set_page_enhance(s, enhance_tile, enhance_clip) != RT_OK) { fprintf(stderr, "%s\n", rt_last_error(s)); return 2; }
   if (deskew_range && rt_set_page_deskew(s, deskew_range, deskew_gain) != RT_OK) { fprintf(stderr, "%s\n", rt_last_error(s)); return 2; }
+  if (derule_len && rt_set_page_derule(s, derule_len, derule_thick, derule_ink) != RT_OK) { fprintf(stderr, "%s\n", rt_last_error(s)); return 2; }
   fprintf(stderr, "[rank %d/%d] %zu files, processing...\n", rank, world, files.size());
   size_t done = 0;
   const int threads = std::max(1, std::min(16, (int)std::thread::hardware_concurrency()));

@@ -444,6 +444,35 @@ RT_API int rt_debug_deskew_page_host(const uint8_t* rgb, int h, int w, int range
  * u = m[0] x + m[1] y + m[2], v = m[3] x + m[4] y + m[5] (the identity for slope 0).  RT_ERR_INVALID for a NULL r or a page out of
  * range (slope 0 and the identity are still written). */
 RT_API int rt_results_page_deskew(const rt_results* r, int page, int* slope, float m[6]);
+/* Page derule (retto_amd/csrc/page_derule.h states the rule): the ruling lines of forms and tables -- table grids, underlines, the
+ * ______ of a blank field -- erased from every page on the GPU before anything reads it.  A rule that touches a row of text welds
+ * it to its neighbours in the detector's probability map, and a rule inside a crop is read as _ | l or 1.  With derule on, every
+ * page of every pipeline call -- host, RT_MEM_DEVICE, encoded, rt_run_regions* -- goes through it as soon as it is in device
+ * memory, last of the page steps -- derule(deskew(enhance(flatten(page)))), lines must be level before their runs are long -- into
+ * a NEW buffer of the same h x w (a caller's RT_MEM_DEVICE page is never written).  It moves no coordinate.
+ * The rule is integer comparisons and pixel copies, so rt_derule_page, the pipeline and rt_debug_derule_page_host agree byte for
+ * byte.  A pixel is ink when 255 - luma >= ink.  In the horizontal pass a vertical run of ink of at most max_thick pixels, one of
+ * whose pixels lies in a horizontal run of at least min_len, is a cross-section of a line: it and the one clear pixel above and
+ * below it (the anti-aliased fringe) take the pixel two rows above or below the run, whichever is lighter (above on a tie).  A
+ * stroke that crosses the line has a longer vertical run and stays.  The vertical pass is the same on the transposed result, which
+ * removes grid junctions with it.  Seven launches per lane part on packed bit-planes, no host wait.
+ * min_len = 0: off, the default (the other two are then ignored); otherwise 16 <= min_len <= 512 (pixels, any value),
+ * 1 <= max_thick <= 8 and 1 <= ink <= 255.  Anything else: RT_ERR_INVALID naming the parameter.  Pages wider than 16384 pixels:
+ * RT_ERR_CAPACITY.  The setting holds for the pipeline calls that follow on every lane (rt_submit_* takes it as it is at the
+ * call); fails like every other call while tickets are in flight.  With derule off nothing is launched or allocated that was not
+ * before.
+ * Not claimed: a line steeper than about max_thick / min_len breaks into shorter runs and stays; dashed and dotted rules stay.
+ * Not supported: per-page or per-region settings; derule inside rt_resize_both, rt_det_preprocess or rt_crop_images; the removed
+ * segments as a table structure.  What derule does to recognition accuracy with trained PP-OCRv4 weights has NOT been measured
+ * (the weights here are synthetic). */
+RT_API int rt_set_page_derule(rt_session* s, int min_len, int max_thick, int ink);
+/* the setting (each optional); RT_ERR_INVALID for a NULL session */
+RT_API int rt_page_derule(const rt_session* s, int* min_len, int* max_thick, int* ink);
+/* stage function beside rt_deskew_page: one RGB8 HWC page in host memory through the pipeline's own launcher, into out
+ * [h * w * 3] (host).  The three parameters as above, whatever the session's setting is; min_len = 0 copies the page. */
+RT_API int rt_derule_page(rt_session* s, const uint8_t* rgb, int h, int w, int min_len, int max_thick, int ink, uint8_t* out);
+/* The rule on the CPU, in plain loops over the same header; GPU-free and sessionless (rt_last_error(NULL)). */
+RT_API int rt_debug_derule_page_host(const uint8_t* rgb, int h, int w, int min_len, int max_thick, int ink, uint8_t* out);
 /* The pipeline over regions the caller already knows (form fields, subtitles, corrected boxes, another detector's boxes):
  * quads[i] = n_quads[i] x 8 floats in host memory, TL, TR, BR, BL of each region in original-page coordinates; mem
  * (RT_MEM_HOST or RT_MEM_DEVICE) says where the pages live.  Every coordinate is clamped to [0, ori - 1] (no rounding); line k

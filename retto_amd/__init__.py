@@ -613,6 +613,15 @@ def debug_deskew_page_host(img: np.ndarray, range: int, min_gain: int = 25, with
     return (out, slope.value, scores) if with_scores else (out, slope.value)
 
 
+def debug_derule_page_host(img: np.ndarray, min_len: int, max_thick: int = 4, ink: int = 96) -> np.ndarray:
+    """rt_debug_derule_page_host: the page derule rule (retto_amd/csrc/page_derule.h) on the CPU, GPU-free."""
+    lib = _lib.load()
+    img = np.ascontiguousarray(img, np.uint8); h, w = img.shape[:2]
+    out = np.empty((h, w, 3), np.uint8)
+    _check(lib.rt_debug_derule_page_host(img.ctypes.data, h, w, int(min_len), int(max_thick), int(ink), out.ctypes.data), None)
+    return out
+
+
 _WINDOW_PLAN_BUFS = None  # the three output arrays of rec_window_plan, grown on demand, as det_tile_plan's
 
 
@@ -954,6 +963,30 @@ class RettoSession:
         _check(self._hd.lib.rt_deskew_page(self._hd.h, img.ctypes.data, h, w, int(range), int(min_gain), out.ctypes.data,
                                            C.byref(slope)), self._hd.h)
         return out, slope.value
+
+    # -- page derule ------------------------------------------------------------------------
+    def set_page_derule(self, min_len: int, max_thick: int = 4, ink: int = 96) -> None:
+        """rt_set_page_derule: the ruling lines of every page of the pipeline calls that follow (table grids, underlines, blank-field
+        rules; retto_amd/csrc/page_derule.h) are erased on the GPU, after flatten, enhance and deskew and before anything else
+        reads the page; 0 = off, the default.  min_len: the shortest run that is a line, in [16, 512] pixels; max_thick: the
+        thickest line, in [1, 8]; ink: the least darkness (255 - luma) of ink, in [1, 255].  The effect on accuracy with the real
+        weights is not measured."""
+        _check(self._hd.lib.rt_set_page_derule(self._hd.h, int(min_len), int(max_thick), int(ink)), self._hd.h)
+
+    def page_derule(self) -> Tuple[int, int, int]:
+        """rt_page_derule: (min_len, max_thick, ink) as set; min_len 0 = off."""
+        a, b, c = C.c_int(), C.c_int(), C.c_int()
+        _check(self._hd.lib.rt_page_derule(self._hd.h, C.byref(a), C.byref(b), C.byref(c)), self._hd.h)
+        return a.value, b.value, c.value
+
+    def derule_page(self, img: np.ndarray, min_len: int, max_thick: int = 4, ink: int = 96) -> np.ndarray:
+        """rt_derule_page: one RGB8 page [h, w, 3] deruled on the GPU through the pipeline's own launcher, whatever the session's
+        setting is; min_len = 0 returns a copy."""
+        img = np.ascontiguousarray(img, np.uint8); h, w = img.shape[:2]
+        out = np.empty((h, w, 3), np.uint8)
+        _check(self._hd.lib.rt_derule_page(self._hd.h, img.ctypes.data, h, w, int(min_len), int(max_thick), int(ink), out.ctypes.data),
+               self._hd.h)
+        return out
 
     # -- rec beams --------------------------------------------------------------------------
     def set_rec_beam(self, beam: int, nbest: int = 1) -> None:

@@ -140,6 +140,7 @@ EXPORTS = [
     "rt_set_page_enhance", "rt_page_enhance", "rt_enhance_page", "rt_debug_enhance_page_host",
     "rt_set_page_flatten", "rt_page_flatten", "rt_flatten_page", "rt_debug_flatten_page_host",
     "rt_set_page_deskew", "rt_page_deskew", "rt_deskew_page", "rt_debug_deskew_page_host", "rt_results_page_deskew",
+    "rt_set_page_derule", "rt_page_derule", "rt_derule_page", "rt_debug_derule_page_host",
 ]
 
 STAGE_CALLBACK = C.CFUNCTYPE(None, C.c_void_p, C.c_int, C.c_int, C.c_char_p)  # rt_stage_callback
@@ -443,5 +444,9 @@ def load():
     lib.rt_deskew_page.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, P(C.c_int)]
     lib.rt_debug_deskew_page_host.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, P(C.c_int), C.c_void_p]
     lib.rt_results_page_deskew.argtypes = [C.c_void_p, C.c_int, P(C.c_int), P(C.c_float)]
+    lib.rt_set_page_derule.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int]
+    lib.rt_page_derule.argtypes = [C.c_void_p, P(C.c_int), P(C.c_int), P(C.c_int)]
+    lib.rt_derule_page.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]
+    lib.rt_debug_derule_page_host.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]
     _lib = lib
     return lib

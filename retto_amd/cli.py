@@ -66,6 +66,11 @@ def build_parser() -> argparse.ArgumentParser:
                     help="estimate every page's skew on the GPU and rotate the page back before anything reads it (boxes are then "
                          "in the deskewed page's coordinates; the effect on accuracy is not measured); R the largest slope tried "
                          "in 1/512, in [1, 128], G the least gain over no turn in per cent, in [0, 10000], e.g. 64,25; default off")
+    ap.add_argument("--derule", default=None, metavar="L,T,I",
+                    help="erase ruling lines (table grids, underlines, blank-field rules) from every page on the GPU before "
+                         "anything reads it, after --deskew (the effect on accuracy is not measured); L the shortest run that is "
+                         "a line, in [16, 512] pixels, T the thickest line, in [1, 8], I the least darkness (255 - luma) of ink, "
+                         "in [1, 255], e.g. 64,4,96; default off")
     ap.add_argument("--rec-window", type=int, default=0, metavar="N",
                     help="read rec lines at least 8 columns wider than N as overlapping windows of N columns, stitched into the "
                          "one line (long lines at a familiar width; the effect on accuracy is not measured); a multiple of 32, "
@@ -156,6 +161,12 @@ def main(argv=None) -> int:
         except ValueError:
             ap.error("--deskew takes R,G, e.g. 64,25")
         session.set_page_deskew(rng, gain)
+    if a.derule:
+        try:
+            min_len, max_thick, ink = (int(v) for v in a.derule.split(","))
+        except ValueError:
+            ap.error("--derule takes L,T,I, e.g. 64,4,96")
+        session.set_page_derule(min_len, max_thick, ink)
     if a.rec_window:
         session.set_rec_windows(a.rec_window, a.rec_window_overlap)
     if a.rec_flip:

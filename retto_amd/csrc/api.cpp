@@ -584,6 +584,38 @@ int rt_results_page_deskew(const rt_results* r, int page, int* slope, float m[6]
   if (m) pd::matrix_of(rec, p ? p->deskew_h : 1, p ? p->deskew_w : 1, m);
   return p ? RT_OK : RT_ERR_INVALID;
 }
+int rt_set_page_derule(rt_session* s, int min_len, int max_thick, int ink) {
+  RT_REQUIRE(s, s, "rt_set_page_derule: null session");
+  return guarded(s, [&] {
+    if (const char* why = pr::check_params(min_len, max_thick, ink)) throw RtError(RT_ERR_INVALID, std::string("rt_set_page_derule: ") + why);
+    s->derule_len = min_len; s->derule_thick = min_len ? max_thick : 0; s->derule_ink = min_len ? ink : 0;   // (the helper lanes get it with every call: CallSettings)
+  });
+}
+int rt_page_derule(const rt_session* s, int* min_len, int* max_thick, int* ink) {
+  if (!s) return RT_ERR_INVALID;
+  if (min_len) *min_len = s->derule_len;
+  if (max_thick) *max_thick = s->derule_thick;
+  if (ink) *ink = s->derule_ink;
+  return RT_OK;
+}
+int rt_derule_page(rt_session* s, const uint8_t* rgb, int h, int w, int min_len, int max_thick, int ink, uint8_t* out) {
+  RT_REQUIRE(s && rgb && out && h > 0 && w > 0, s, "rt_derule_page: bad argument");
+  return guarded(s, [&] {
+    if (const char* why = pr::check_params(min_len, max_thick, ink)) throw RtError(RT_ERR_INVALID, std::string("rt_derule_page: ") + why);
+    if ((long long)h * w > 0x7fffffffLL / 3) throw RtError(RT_ERR_CAPACITY, "rt_derule_page: the page is larger than 2^31 - 1 bytes");
+    if (min_len == 0) memcpy(out, rgb, (size_t)h * w * 3);   // off: the page as it is
+    else s->derule_page(rgb, h, w, min_len, max_thick, ink, out);
+  });
+}
+int rt_debug_derule_page_host(const uint8_t* rgb, int h, int w, int min_len, int max_thick, int ink, uint8_t* out) {
+  RT_REQUIRE(rgb && out && h > 0 && w > 0, (rt_session*)nullptr, "rt_debug_derule_page_host: bad argument");
+  return guarded(nullptr, [&] {
+    if (const char* why = pr::check_params(min_len, max_thick, ink)) throw RtError(RT_ERR_INVALID, std::string("rt_debug_derule_page_host: ") + why);
+    if ((long long)h * w > 0x7fffffffLL / 3) throw RtError(RT_ERR_CAPACITY, "rt_debug_derule_page_host: the page is larger than 2^31 - 1 bytes");
+    if (min_len == 0) memcpy(out, rgb, (size_t)h * w * 3);   // off: the page as it is
+    else pr::derule_page_host(rgb, h, w, min_len, max_thick, ink, out);
+  });
+}
 int rt_rec_window_plan(int L, int window, int overlap, int32_t* origin, int32_t* width, int32_t* bound, int cap, int* n, int* T) {
   return guarded(nullptr, [&] {
     if (const char* why = rw::check_params(window, overlap)) throw RtError(RT_ERR_INVALID, std::string("rt_rec_window_plan: ") + why);

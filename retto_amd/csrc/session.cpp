@@ -389,6 +389,34 @@ int rt_lane::deskew_page(const uint8_t* rgb, int h, int w, int range, int min_ga
   return rec->k;
 }
 
+void rt_lane::derule_pages(int n, const uint8_t* const* src, const int* hs, const int* ws, int min_len, int max_thick, int ink, const uint8_t** out) {
+  if (n <= 0) return;
+  pr::DevPage* hp = pinned.alloc<pr::DevPage>((size_t)n);
+  for (int i = 0; i < n; i++) { hp[i] = pr::DevPage{}; hp[i].src = src[i]; hp[i].h = hs[i]; hp[i].w = ws[i]; }
+  if (const char* why = pr::plan_pages(hp, n, min_len)) throw RtError(RT_ERR_CAPACITY, std::string("page derule: ") + why);
+  for (int i = 0; i < n; i++) {
+    const size_t plane = (size_t)hs[i] * hp[i].wp;
+    hp[i].mid = arena.alloc<uint8_t>((size_t)hs[i] * ws[i] * 3);
+    hp[i].dst = arena.alloc<uint8_t>((size_t)hs[i] * ws[i] * 3);
+    hp[i].bits = arena.alloc<uint32_t>(plane); hp[i].keep = arena.alloc<uint32_t>(plane); hp[i].lng = arena.alloc<uint32_t>(plane);
+    out[i] = hp[i].dst;
+  }
+  pr::DevPage* dp = arena.alloc<pr::DevPage>((size_t)n);
+  RT_HIP_CHECK(hipMemcpyAsync(dp, hp, (size_t)n * sizeof(pr::DevPage), hipMemcpyHostToDevice, st));
+  pr::launch(st, &prof, dp, hp, n, min_len, max_thick, ink);
+}
+
+void rt_lane::derule_page(const uint8_t* rgb, int h, int w, int min_len, int max_thick, int ink, uint8_t* out) {
+  begin_call();
+  const size_t bytes = (size_t)h * w * 3;
+  uint8_t* d = arena.alloc<uint8_t>(bytes);
+  RT_HIP_CHECK(hipMemcpyAsync(d, rgb, bytes, hipMemcpyHostToDevice, st));
+  const uint8_t* src = d; const uint8_t* e = nullptr;
+  derule_pages(1, &src, &h, &w, min_len, max_thick, ink, &e);
+  RT_HIP_CHECK(hipMemcpyAsync(out, e, bytes, hipMemcpyDeviceToHost, st));
+  sync();
+}
+
 void rt_lane::det_preprocess(const uint8_t* rgb, int h, int w, float* out) {
   begin_call();
   uint8_t* d = arena.alloc<uint8_t>((size_t)h * w * 3);
@@ -754,12 +782,14 @@ const uint8_t* page_on_device(rt_lane& s, const PageCall& c, int i) {
 // Page deskew (page_deskew.h; call.set.deskew_range > 0) comes last, in pd::launch's four launches, and only where the caller asks
 // for it with `deskew` (the detector's calls; never rt_run_regions*, whose quads define the geometry): *deskew = the [n_pages] page
 // records in pinned memory, valid after the lane's next sync, or null when deskew is off.  The page is then
-// deskew(enhance(flatten(page))).  All off: empty, and nothing is allocated or launched.
+// deskew(enhance(flatten(page))).  Page derule (page_derule.h; call.set.derule_len > 0) comes after that, in pr::launch's seven
+// launches, in every call like flatten and enhance: lines must be level before their runs are long, and it moves no coordinate.
+// All off: empty, and nothing is allocated or launched.
 std::vector<const uint8_t*> enhanced_pages(rt_lane& s, const PageCall& c, const int* needed = nullptr, const pd::Record** deskew = nullptr) {
   std::vector<const uint8_t*> out;
   const bool turn = deskew && c.set.deskew_range > 0;
   if (deskew) *deskew = nullptr;
-  if (c.set.enhance_tile <= 0 && c.set.flatten_radius <= 0 && !turn) return out;
+  if (c.set.enhance_tile <= 0 && c.set.flatten_radius <= 0 && !turn && c.set.derule_len <= 0) return out;
   out.assign((size_t)c.n_pages, nullptr);
   std::vector<const uint8_t*> src, dst; std::vector<int> hs, ws, at;
   for (int i = 0; i < c.n_pages; i++) {
@@ -775,8 +805,12 @@ std::vector<const uint8_t*> enhanced_pages(rt_lane& s, const PageCall& c, const 
     s.enhance_pages((int)src.size(), src.data(), hs.data(), ws.data(), c.set.enhance_tile, c.set.enhance_clip_x16, dst.data());
     src = dst;
   }
-  if (turn)   // (needed is null with deskew: record k is page k's)
+  if (turn) {   // (needed is null with deskew: record k is page k's)
     *deskew = s.deskew_pages((int)src.size(), src.data(), hs.data(), ws.data(), c.set.deskew_range, c.set.deskew_gain, c.set.d_deskew_table, dst.data());
+    src = dst;
+  }
+  if (c.set.derule_len > 0)
+    s.derule_pages((int)src.size(), src.data(), hs.data(), ws.data(), c.set.derule_len, c.set.derule_thick, c.set.derule_ink, dst.data());
   for (size_t k = 0; k < at.size(); k++) out[(size_t)at[k]] = dst[k];
   return out;
 }

@@ -22,6 +22,7 @@
 #include "lane_split.h"
 #include "nets.h"
 #include "nets_f16.h"
+#include "page_derule.h"
 #include "page_deskew.h"
 #include "page_enhance.h"
 #include "page_flatten.h"
@@ -111,7 +112,8 @@ struct LaneWorker {
 // classifier scores to the host.  enhance_tile / enhance_clip_x16: the page enhance (rt_set_page_enhance, page_enhance.h; 0 = off);
 // flatten_radius / flatten_floor: the page flatten (rt_set_page_flatten, page_flatten.h; 0 = off), which comes first when both are on;
 // deskew_range / deskew_gain: the page deskew (rt_set_page_deskew, page_deskew.h; 0 = off), which comes last, and d_deskew_table, the
-// session's angle table on the device (non-null whenever deskew_range > 0)
+// session's angle table on the device (non-null whenever deskew_range > 0); derule_len / derule_thick / derule_ink: the page derule
+// (rt_set_page_derule, page_derule.h; 0 = off), which comes after deskew
 struct CallSettings {
   rt::RecLineOpts rec; int det_tile = 0, det_overlap = 0, beam_b = 0, beam_n = 0, rec_window = 0, rec_overlap = 0;
   int lm = -1; float lm_alpha = 0.0f, lm_beta = 0.0f;
@@ -120,6 +122,7 @@ struct CallSettings {
   int enhance_tile = 0, enhance_clip_x16 = 0;
   int flatten_radius = 0, flatten_floor = 0;
   int deskew_range = 0, deskew_gain = 0; const int32_t* d_deskew_table = nullptr;
+  int derule_len = 0, derule_thick = 0, derule_ink = 0;
   bool fused() const { return beam_b > 0 && lm >= 0; }
   bool worded() const { return beam_b > 0 && beam_vocab >= 0; }
 };
@@ -346,6 +349,11 @@ struct rt_lane {
                                      const int32_t* table, const uint8_t** out);
   // rt_deskew_page: one host page through deskew_pages; returns the chosen slope
   int deskew_page(const uint8_t* rgb, int h, int w, int range, int min_gain, const int32_t* table, uint8_t* out);
+  // Page derule (page_derule.h) of n pages on the device in the seven launches of pr::launch: the pages after the horizontal pass,
+  // the new pages and three bit-planes per page from `arena`, the descriptors through `pinned`; out[i] = page i deruled
+  void derule_pages(int n, const uint8_t* const* src, const int* hs, const int* ws, int min_len, int max_thick, int ink, const uint8_t** out);
+  // rt_derule_page: one host page through derule_pages
+  void derule_page(const uint8_t* rgb, int h, int w, int min_len, int max_thick, int ink, uint8_t* out);
   void det_preprocess(const uint8_t* rgb, int h, int w, float* out);
   void det_postprocess(const float* pred, int h, int w, int ori_h, int ori_w, float* boxes, float* scores, int max_out,
                        int* n_out);
@@ -487,10 +495,13 @@ struct rt_session : rt_lane {
   int deskew_range = 0, deskew_gain = 0;
   int32_t* d_deskew_table = nullptr;
   const int32_t* deskew_table();
+  // rt_set_page_derule (page_derule.h): the ruling lines of every page of the pipeline calls that follow are erased, after flatten,
+  // enhance and deskew; derule_len = 0: off
+  int derule_len = 0, derule_thick = 0, derule_ink = 0;
   CallSettings settings() const {
     return {rec_default, det_tile, det_overlap, beam_b, beam_n, rec_window, rec_overlap, beam_lm, lm_alpha, lm_beta, beam_vocab, vocab_gamma,
             rec_flip_below, enhance_tile, enhance_tile ? rt::pe::clip_x16_of(enhance_clip) : 0, flatten_radius, flatten_floor,
-            deskew_range, deskew_gain, d_deskew_table};
+            deskew_range, deskew_gain, d_deskew_table, derule_len, derule_thick, derule_ink};
   }
   std::string last_error;
   // rt_charset_create: compiles the set (rt::compile_charset), stores it and returns its id
